@@ -7,11 +7,15 @@ all-gather the per-shard top-k over RCCL (N > 1 only) and merge.  The index and 
 queries are resident in HBM before the timed region starts.
 
     python bench.py                         # 1 GPU, 100M rows (204.8 GB), defaults
+    python bench.py --full                  # + CPU baseline, extras (C2-C5 sections), bench_detail.json
+    python bench.py --dump-outputs DIR      # + the last timed step's top-k as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Scaling is STRONG: the same 100M rows are split over the N ranks (BASELINE config C4).
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the
+line; everything else it can measure (cpu_baseline, extras, feedback-loop replicas at N > 1,
+the detail file) runs only with --full.
 """
 import argparse
 import json
@@ -830,8 +834,8 @@ def _get(d, *path):
     return d
 
 
-def compact_line(full: dict) -> str:
-    """The ONE stdout line, built from the full result (which goes to bench_detail.json and stderr): the contract's
+def compact_line(full: dict, detail: bool = True) -> str:
+    """The ONE stdout line, built from the full result (which a --full run writes to bench_detail.json and stderr): the contract's
     fields, `roofline`, `cpu_baseline`, `allgather_us`, and a flat `extras` of NUMBERS only -- one or two scalars per
     BASELINE config.  No per-session lists, no prose.  Asserted < LINE_LIMIT characters (tests/test_bench_cpu.py)."""
     keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -914,7 +918,7 @@ def compact_line(full: dict) -> str:
         flat["sections_failed"] = len(errs)
     put("wall_s_extras", sum((ex.get("section_seconds") or {}).values()) if ex.get("section_seconds") else None)
     out["extras"] = flat
-    out["detail"] = "bench_detail.json"
+    out["detail"] = "bench_detail.json" if detail else None  # written by --full runs only
     line = json.dumps(out, separators=(",", ":"), allow_nan=False)
     if len(line) >= LINE_LIMIT:  # never let the line outgrow what the driver reads: drop extras from the end
         keys = list(flat)
@@ -954,7 +958,13 @@ def main():
     ap.add_argument("--loop-images", type=int, default=120000, help="images of the full-size feedback-loop dataset")
     ap.add_argument("--clustered-graph", action="store_true",
                     help="also time the label-propagation sweep on a clustered graph with the locality order (20 s of set-up)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline and the extras sections and write bench_detail.json (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's top-k (images f64, scores f32) as DIR/topk_*.npy")
     args = ap.parse_args()
+    if not args.full:  # the sections below are the --full run's; a plain run times the headline only
+        args.no_cpu_baseline = args.no_extras = True
 
     # The job's stdout is ONE JSON line.  Libraries underneath write to file descriptor 1 whenever they like (RCCL's
     # version banner at communicator creation, gloo's connection notes): for the whole run descriptor 1 points at
@@ -1037,6 +1047,10 @@ def main():
     from seesaw_amd.device_index import decode_keys
     c = int(count.item())
     imgs, scores = decode_keys(keys[:c].cpu().numpy().view(np.uint64))
+    if args.dump_outputs and rank == 0:  # what a caller of the timed path receives: ranked images and their scores
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "topk_images.npy"), imgs.astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "topk_scores.npy"), scores.astype(np.float32))
 
     t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearsal else dev)
     if dist is not None:
@@ -1130,8 +1144,9 @@ def main():
         if replicas is not None:
             out["extras"] = {"feedback_loop_replicas": aggregate_replicas(replicas, world)}
         sys.stdout.flush()
-        write_detail(out)
-        os.write(json_fd, (compact_line(out) + "\n").encode())
+        if args.full:
+            write_detail(out)
+        os.write(json_fd, (compact_line(out, detail=args.full) + "\n").encode())
     os.close(json_fd)
     index.close()
     if dist is not None:

@@ -12,7 +12,7 @@ OUT=${1:-gpurun_out/rehearsal}
 mkdir -p "$OUT"
 export SSW_BENCH_REHEARSAL=gloo PYTHONPATH=. HSA_ENABLE_IPC_MODE_LEGACY=0
 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29531 \
-    bench.py --gpus 4 --steps 10 --warmup 3 --rows 50e6 --loop-images 2000 > "$OUT/rehearsal_world4_12p5M_rows_per_rank.json" 2> "$OUT/rehearsal_a.err"
+    bench.py --gpus 4 --steps 10 --warmup 3 --rows 50e6 --loop-images 2000 --full > "$OUT/rehearsal_world4_12p5M_rows_per_rank.json" 2> "$OUT/rehearsal_a.err"
 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29532 \
     bench.py --gpus 4 --steps 10 --warmup 3 --rows 100e6 --no-extras > "$OUT/rehearsal_world4_25M_rows_per_rank.json" 2> "$OUT/rehearsal_b.err"
 echo "rehearsal lines written to $OUT"
