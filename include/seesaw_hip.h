@@ -65,6 +65,19 @@ typedef struct ssw_index ssw_index;
  * bytes itself.  dim must be a multiple of 256 and <= 1024 (CLIP: 512). */
 ssw_status ssw_index_create(int32_t device, int64_t n_rows, int32_t dim,
                             const float *dev_vectors_or_null, ssw_index **out);
+/* Element type of the resident matrix.  SSW_DTYPE_F16 stores every element as IEEE binary16, rounded to nearest
+ * even (subnormals kept, overflow to +-inf: numpy's astype(float16)), in a private lane-interleaved row layout
+ * (dim * 2 bytes a row).  Every operation on an f16 index returns the bits the same operation returns on an f32 index
+ * of the widened rows: the query stays f32, products and sums are f32 in the f32 scan's order.  Entries that read the
+ * matrix as f32 through the handle and have no f16 form (ssw_knn_build, ssw_xlx) return SSW_ERR_UNSUPPORTED;
+ * ssw_index_device_ptrs hands out the private layout. */
+#define SSW_DTYPE_F32 0
+#define SSW_DTYPE_F16 1
+/* ssw_index_create with an element type.  SSW_DTYPE_F32 is ssw_index_create; SSW_DTYPE_F16 allocates
+ * n_rows*dim*2 bytes and cannot borrow a device matrix (dev_vectors_or_null != NULL -> SSW_ERR_UNSUPPORTED). */
+ssw_status ssw_index_create_typed(int32_t device, int64_t n_rows, int32_t dim, int32_t dtype,
+                                  const void *dev_vectors_or_null, ssw_index **out);
+ssw_status ssw_index_dtype(const ssw_index *idx, int32_t *out);
 ssw_status ssw_index_destroy(ssw_index *idx);
 /* run all of this handle's work on an existing hipStream_t (e.g. torch's current
  * stream) instead of the handle's own (non-blocking) stream.  NULL restores the own stream; to name the
@@ -77,9 +90,12 @@ ssw_status ssw_index_shape(const ssw_index *idx, int64_t *n_rows, int32_t *dim, 
  * valid after the last scan). */
 ssw_status ssw_index_device_ptrs(ssw_index *idx, void **dev_vectors, void **dev_scores);
 
-/* copy rows [first_row, first_row+n) from host memory into the index. */
+/* copy rows [first_row, first_row+n) from host memory into the index (an f16 index rounds them on the device,
+ * through a bounded staging buffer). */
 ssw_status ssw_index_upload(ssw_index *idx, const float *host_rows, int64_t first_row, int64_t n);
-/* copy rows back (tests / subset()). */
+/* the same from rows that are already binary16 (natural element order); f16 index only, else SSW_ERR_UNSUPPORTED. */
+ssw_status ssw_index_upload_f16(ssw_index *idx, const uint16_t *rows_f16, int64_t first_row, int64_t n);
+/* copy rows back as f32 (tests / subset(); an f16 index widens them). */
 ssw_status ssw_index_download(ssw_index *idx, float *host_rows, int64_t first_row, int64_t n);
 /* fill the whole index on the device with the counter-based synthetic generator
  * (unit-norm rows; bit-identical to oracle.synth_rows(seed, global_first_row+i)). */
@@ -388,6 +404,14 @@ ssw_status ssw_fb_set_pseudo_sample(ssw_fb *fb, const float *dev_matrix, int64_t
  * ssw_index_device_ptrs) -- `index.vectors[matchdf.index.values]`, multi_reg.py:204. */
 ssw_status ssw_fb_set_data_from_device(ssw_fb *fb, const float *dev_matrix, int64_t n_matrix_rows,
                                        const int64_t *rows_host, int64_t n, int32_t center);
+/* the two entries above with the rows gathered out of an index handle's matrix of either element type (an f16
+ * index's rows are widened to f32): the same data as the raw-pointer forms on an f32 index of the widened rows. */
+ssw_status ssw_fb_set_data_from_index(ssw_fb *fb, const ssw_index *index, const int64_t *rows_host, int64_t n,
+                                      int32_t center);
+ssw_status ssw_fb_set_pseudo_sample_from_index(ssw_fb *fb, const ssw_index *index, const double *dev_scores,
+                                               const int64_t *labelled_rows_sorted, const float *labelled_y,
+                                               int64_t n_lab, const int64_t *drawn, int64_t n_drawn, float real_weight,
+                                               int32_t center);
 /* targets y [n] f32 and optional per-item sample weights [n] f32. */
 ssw_status ssw_fb_set_targets(ssw_fb *fb, const float *y_host, const float *sample_weight_or_null);
 /* regulariser vector / query vector (normalised inside, F.normalize) and X'LX [dim, dim]. */

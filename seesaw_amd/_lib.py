@@ -18,6 +18,7 @@ DEBUG_HEADER_PATH = os.path.join(os.path.dirname(_PKG_DIR), "include", "seesaw_h
 SSW_OK = 0
 SSW_ERR_INVALID, SSW_ERR_HIP, SSW_ERR_NOMEM, SSW_ERR_UNSUPPORTED, SSW_ERR_NUMERIC = -1, -2, -3, -4, -5
 SSW_MAX_TOPK = 4096
+SSW_DTYPE_F32, SSW_DTYPE_F16 = 0, 1
 
 
 class SeesawHipError(RuntimeError):
@@ -45,12 +46,15 @@ _SIGNATURES = {
     "ssw_device_count": (c_i32, [c_i32_p]),
     "ssw_device_info": (c_i32, [c_i32, ctypes.c_char_p, c_i32, c_i32_p, c_i64_p]),
     "ssw_index_create": (c_i32, [c_i32, c_i64, c_i32, c_void_p, c_void_pp]),
+    "ssw_index_create_typed": (c_i32, [c_i32, c_i64, c_i32, c_i32, c_void_p, c_void_pp]),
+    "ssw_index_dtype": (c_i32, [c_void_p, c_i32_p]),
     "ssw_index_destroy": (c_i32, [c_void_p]),
     "ssw_index_set_stream": (c_i32, [c_void_p, c_void_p]),
     "ssw_index_sync": (c_i32, [c_void_p]),
     "ssw_index_shape": (c_i32, [c_void_p, c_i64_p, c_i32_p, c_i64_p]),
     "ssw_index_device_ptrs": (c_i32, [c_void_p, c_void_pp, c_void_pp]),
     "ssw_index_upload": (c_i32, [c_void_p, c_void_p, c_i64, c_i64]),
+    "ssw_index_upload_f16": (c_i32, [c_void_p, c_void_p, c_i64, c_i64]),
     "ssw_index_download": (c_i32, [c_void_p, c_void_p, c_i64, c_i64]),
     "ssw_index_fill_random": (c_i32, [c_void_p, c_u64, c_i64]),
     "ssw_index_set_row2image": (c_i32, [c_void_p, c_void_p, c_i64]),
@@ -81,6 +85,9 @@ _SIGNATURES = {
     "ssw_fb_destroy": (c_i32, [c_void_p]),
     "ssw_fb_set_data": (c_i32, [c_void_p, c_void_p, c_i64, c_i32]),
     "ssw_fb_set_data_from_device": (c_i32, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i32]),
+    "ssw_fb_set_data_from_index": (c_i32, [c_void_p, c_void_p, c_void_p, c_i64, c_i32]),
+    "ssw_fb_set_pseudo_sample_from_index": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p,
+                                                    c_i64, ctypes.c_float, c_i32]),
     "ssw_fb_set_targets": (c_i32, [c_void_p, c_void_p, c_void_p]),
     "ssw_fb_set_pseudo_sample": (c_i32, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64,
                                          ctypes.c_float, c_i32]),

@@ -75,8 +75,12 @@ struct ssw_index {
     int32_t dim = 0;
     int64_t n_images = 0;
     bool has_map = false;
-    float *X = nullptr;
+    int32_t dtype = SSW_DTYPE_F32;
+    float *X = nullptr;  // SSW_DTYPE_F16: binary16 rows in the lane-interleaved layout (ssw_common.h), see Xh()
     bool owns_X = false;
+    // f16 upload / download: bounded device staging of natural-order rows (f32 or binary16)
+    void *xfer = nullptr;
+    size_t xfer_bytes = 0;
     float *scores = nullptr;      // [n]
     float *q_dev = nullptr;       // [dim] device copy of a host query
     PinnedStage q_stage;
@@ -112,6 +116,9 @@ struct ssw_index {
     std::vector<hipEvent_t> ev;  // pairs
     int ev_used = 0;
 };
+
+static const uint16_t *Xh(const ssw_index *idx) { return reinterpret_cast<const uint16_t *>(idx->X); }
+static uint16_t *Xh(ssw_index *idx) { return reinterpret_cast<uint16_t *>(idx->X); }
 
 static ssw_status ensure_ws(ssw_index *idx) {
     if (idx->ws_ready) return SSW_OK;
@@ -150,15 +157,21 @@ static ssw_status stage_query(ssw_index *idx, const float *q_host) {
     return SSW_OK;
 }
 
+static ssw_status launch_index_scan(ssw_index *idx, const float *q_dev) {
+    if (idx->dtype == SSW_DTYPE_F16)
+        return launch_scan_h16(Xh(idx), q_dev, idx->scores, idx->n, idx->dim, idx->device, idx->stream);
+    return launch_scan(idx->X, q_dev, idx->scores, idx->n, idx->dim, idx->device, idx->stream);
+}
+
 static ssw_status do_scan(ssw_index *idx, const float *q_dev) {
     if (idx->profiling && idx->ev_used + 2 <= (int)idx->ev.size()) {
         SSW_HIP_TRY(hipEventRecord(idx->ev[idx->ev_used], idx->stream));
-        SSW_TRY(launch_scan(idx->X, q_dev, idx->scores, idx->n, idx->dim, idx->device, idx->stream));
+        SSW_TRY(launch_index_scan(idx, q_dev));
         SSW_HIP_TRY(hipEventRecord(idx->ev[idx->ev_used + 1], idx->stream));
         idx->ev_used += 2;
         return SSW_OK;
     }
-    return launch_scan(idx->X, q_dev, idx->scores, idx->n, idx->dim, idx->device, idx->stream);
+    return launch_index_scan(idx, q_dev);
 }
 
 static ssw_status do_select(ssw_index *idx, int32_t k) {
@@ -199,9 +212,22 @@ ssw_status ssw_device_info(int32_t device, char *name, int32_t name_cap, int32_t
 
 ssw_status ssw_index_create(int32_t device, int64_t n_rows, int32_t dim,
                             const float *dev_vectors_or_null, ssw_index **out) {
+    return ssw_index_create_typed(device, n_rows, dim, SSW_DTYPE_F32, dev_vectors_or_null, out);
+}
+
+ssw_status ssw_index_create_typed(int32_t device, int64_t n_rows, int32_t dim, int32_t dtype,
+                                  const void *dev_vectors_or_null, ssw_index **out) {
     SSW_REQUIRE(out != nullptr, "out is NULL");
     *out = nullptr;
     SSW_REQUIRE(n_rows >= 0, "n_rows=%lld < 0", (long long)n_rows);
+    if (dtype != SSW_DTYPE_F32 && dtype != SSW_DTYPE_F16) {
+        set_error("index: dtype=%d unsupported (SSW_DTYPE_F32 = 0, SSW_DTYPE_F16 = 1)", dtype);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    if (dtype == SSW_DTYPE_F16 && dev_vectors_or_null) {
+        set_error("index: an f16 index keeps its rows in a private layout and cannot borrow a device matrix");
+        return SSW_ERR_UNSUPPORTED;
+    }
     if (dim <= 0 || dim % 256 != 0 || dim > 1024) {
         set_error("index: dim=%d unsupported (need a multiple of 256, <= 1024)", dim);
         return SSW_ERR_UNSUPPORTED;
@@ -221,6 +247,7 @@ ssw_status ssw_index_create(int32_t device, int64_t n_rows, int32_t dim,
     idx->device = device;
     idx->n = n_rows;
     idx->dim = dim;
+    idx->dtype = dtype;
     idx->n_images = n_rows;
     ssw_status st = SSW_OK;
     auto fail = [&](ssw_status s) {
@@ -233,13 +260,14 @@ ssw_status ssw_index_create(int32_t device, int64_t n_rows, int32_t dim,
     }
     idx->stream = idx->own_stream;
     const size_t row_bytes = (size_t)dim * sizeof(float);
+    const size_t elem_bytes = dtype == SSW_DTYPE_F16 ? 2 : 4;
     if (dev_vectors_or_null) {
-        idx->X = const_cast<float *>(dev_vectors_or_null);
+        idx->X = const_cast<float *>(static_cast<const float *>(dev_vectors_or_null));
     } else {
-        hipError_t e = hipMalloc((void **)&idx->X, (size_t)(n_rows > 0 ? n_rows : 1) * row_bytes);
+        hipError_t e = hipMalloc((void **)&idx->X, (size_t)(n_rows > 0 ? n_rows : 1) * dim * elem_bytes);
         if (e != hipSuccess) {
             set_error("hipMalloc of %.2f GB for the index failed: %s",
-                      (double)n_rows * row_bytes / 1e9, hipGetErrorString(e));
+                      (double)n_rows * dim * elem_bytes / 1e9, hipGetErrorString(e));
             idx->X = nullptr;
             return fail(SSW_ERR_NOMEM);
         }
@@ -262,6 +290,7 @@ ssw_status ssw_index_destroy(ssw_index *idx) {
     for (hipEvent_t e : idx->ev) (void)hipEventDestroy(e);
     if (idx->ws_ready) select_free(idx->ws);
     if (idx->owns_X) (void)hipFree(idx->X);
+    (void)hipFree(idx->xfer);
     (void)hipFree(idx->scores);
     (void)hipFree(idx->q_dev);
     idx->q_stage.release();
@@ -308,10 +337,49 @@ ssw_status ssw_index_shape(const ssw_index *idx, int64_t *n_rows, int32_t *dim, 
     return SSW_OK;
 }
 
+ssw_status ssw_index_dtype(const ssw_index *idx, int32_t *out) {
+    SSW_REQUIRE(idx != nullptr && out != nullptr, "NULL argument");
+    *out = idx->dtype;
+    return SSW_OK;
+}
+
 ssw_status ssw_index_device_ptrs(ssw_index *idx, void **dev_vectors, void **dev_scores) {
     SSW_REQUIRE(idx != nullptr, "idx is NULL");
     if (dev_vectors) *dev_vectors = idx->X;
     if (dev_scores) *dev_scores = idx->scores;
+    return SSW_OK;
+}
+
+// f16 index: host rows go through a bounded device staging buffer (never an n x dim x 4 temporary)
+constexpr size_t XFER_BYTES = (size_t)32 << 20;
+
+static ssw_status ensure_xfer(ssw_index *idx) {
+    if (idx->xfer) return SSW_OK;
+    if (hipMalloc(&idx->xfer, XFER_BYTES) != hipSuccess) {
+        idx->xfer = nullptr;
+        set_error("hipMalloc of the %zu-byte f16 staging buffer failed", XFER_BYTES);
+        return SSW_ERR_NOMEM;
+    }
+    idx->xfer_bytes = XFER_BYTES;
+    return SSW_OK;
+}
+
+// natural-order host rows (f32, or binary16 when src_h16) -> rows [first_row, first_row + n) of an f16 index
+static ssw_status upload_h16(ssw_index *idx, const void *host_rows, bool src_h16, int64_t first_row, int64_t n) {
+    SSW_TRY(ensure_xfer(idx));
+    const size_t row_bytes = (size_t)idx->dim * (src_h16 ? 2 : 4);
+    const int64_t chunk = (int64_t)(idx->xfer_bytes / row_bytes);
+    const unsigned char *src = static_cast<const unsigned char *>(host_rows);
+    for (int64_t r = 0; r < n; r += chunk) {
+        const int64_t m = std::min(chunk, n - r);
+        // stream order: the copy into the staging buffer waits for the previous chunk's conversion
+        SSW_HIP_TRY(hipMemcpyAsync(idx->xfer, src + (size_t)r * row_bytes, (size_t)m * row_bytes, hipMemcpyHostToDevice,
+                                   idx->stream));
+        SSW_TRY(launch_rows_to_h16(src_h16 ? nullptr : static_cast<const float *>(idx->xfer),
+                                   src_h16 ? static_cast<const uint16_t *>(idx->xfer) : nullptr, m, idx->dim,
+                                   Xh(idx) + (first_row + r) * idx->dim, idx->stream));
+    }
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
     return SSW_OK;
 }
 
@@ -321,11 +389,25 @@ ssw_status ssw_index_upload(ssw_index *idx, const float *host_rows, int64_t firs
                 "rows [%lld, %lld) outside the index of %lld rows", (long long)first_row,
                 (long long)(first_row + n), (long long)idx->n);
     DeviceGuard guard(idx->device);
+    if (idx->dtype == SSW_DTYPE_F16) return upload_h16(idx, host_rows, false, first_row, n);
     SSW_HIP_TRY(hipMemcpyAsync(idx->X + first_row * idx->dim, host_rows,
                                (size_t)n * idx->dim * sizeof(float), hipMemcpyHostToDevice,
                                idx->stream));
     SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
     return SSW_OK;
+}
+
+ssw_status ssw_index_upload_f16(ssw_index *idx, const uint16_t *rows_f16, int64_t first_row, int64_t n) {
+    SSW_REQUIRE(idx != nullptr && rows_f16 != nullptr, "NULL argument");
+    if (idx->dtype != SSW_DTYPE_F16) {
+        set_error("ssw_index_upload_f16: the index holds f32 rows (use ssw_index_upload)");
+        return SSW_ERR_UNSUPPORTED;
+    }
+    SSW_REQUIRE(first_row >= 0 && n >= 0 && first_row + n <= idx->n,
+                "rows [%lld, %lld) outside the index of %lld rows", (long long)first_row,
+                (long long)(first_row + n), (long long)idx->n);
+    DeviceGuard guard(idx->device);
+    return upload_h16(idx, rows_f16, true, first_row, n);
 }
 
 ssw_status ssw_index_download(ssw_index *idx, float *host_rows, int64_t first_row, int64_t n) {
@@ -334,6 +416,20 @@ ssw_status ssw_index_download(ssw_index *idx, float *host_rows, int64_t first_ro
                 "rows [%lld, %lld) outside the index of %lld rows", (long long)first_row,
                 (long long)(first_row + n), (long long)idx->n);
     DeviceGuard guard(idx->device);
+    if (idx->dtype == SSW_DTYPE_F16) {  // widened, natural element order, through the staging buffer
+        SSW_TRY(ensure_xfer(idx));
+        const size_t row_bytes = (size_t)idx->dim * sizeof(float);
+        const int64_t chunk = (int64_t)(idx->xfer_bytes / row_bytes);
+        for (int64_t r = 0; r < n; r += chunk) {
+            const int64_t m = std::min(chunk, n - r);
+            SSW_TRY(launch_rows_from_h16(Xh(idx), nullptr, first_row + r, m, idx->dim, static_cast<float *>(idx->xfer),
+                                         idx->stream));
+            SSW_HIP_TRY(hipMemcpyAsync(host_rows + (size_t)r * idx->dim, idx->xfer, (size_t)m * row_bytes,
+                                       hipMemcpyDeviceToHost, idx->stream));
+        }
+        SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+        return SSW_OK;
+    }
     SSW_HIP_TRY(hipMemcpyAsync(host_rows, idx->X + first_row * idx->dim,
                                (size_t)n * idx->dim * sizeof(float), hipMemcpyDeviceToHost,
                                idx->stream));
@@ -344,7 +440,10 @@ ssw_status ssw_index_download(ssw_index *idx, float *host_rows, int64_t first_ro
 ssw_status ssw_index_fill_random(ssw_index *idx, uint64_t seed, int64_t global_first_row) {
     SSW_REQUIRE(idx != nullptr, "idx is NULL");
     DeviceGuard guard(idx->device);
-    SSW_TRY(launch_fill_random(idx->X, idx->n, idx->dim, seed, global_first_row, idx->stream));
+    if (idx->dtype == SSW_DTYPE_F16)
+        SSW_TRY(launch_fill_random_h16(Xh(idx), idx->n, idx->dim, seed, global_first_row, idx->stream));
+    else
+        SSW_TRY(launch_fill_random(idx->X, idx->n, idx->dim, seed, global_first_row, idx->stream));
     SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
     return SSW_OK;
 }
@@ -830,6 +929,12 @@ ssw_status index_collect_topk(ssw_index *idx, hipStream_t on_stream, int32_t k, 
 }
 
 int index_device(const ssw_index *idx) { return idx ? idx->device : -1; }
+int32_t index_dtype(const ssw_index *idx) { return idx ? idx->dtype : SSW_DTYPE_F32; }
+const void *index_matrix(const ssw_index *idx, int64_t *n_rows, int32_t *dim) {
+    if (n_rows) *n_rows = idx->n;
+    if (dim) *dim = idx->dim;
+    return idx->X;
+}
 }  // namespace ssw
 }  // extern "C++"
 
@@ -895,8 +1000,11 @@ ssw_status ssw_index_score_rows(ssw_index *idx, const float *q_host, const int64
     SSW_TRY(stage_rows(idx, rows_host, n));
     if (!idx->q2_dev) SSW_HIP_TRY(hipMalloc((void **)&idx->q2_dev, (size_t)idx->dim * sizeof(float)));
     SSW_TRY(idx->q2_stage.push(idx->q2_dev, q_host, (size_t)idx->dim * sizeof(float), idx->stream));
-    SSW_TRY(launch_score_rows(idx->X, idx->q2_dev, idx->gather_idx, n, idx->dim, idx->gather_out,
-                              idx->stream));
+    if (idx->dtype == SSW_DTYPE_F16)
+        SSW_TRY(launch_score_rows_h16(Xh(idx), idx->q2_dev, idx->gather_idx, n, idx->dim, idx->gather_out, idx->stream));
+    else
+        SSW_TRY(launch_score_rows(idx->X, idx->q2_dev, idx->gather_idx, n, idx->dim, idx->gather_out,
+                                  idx->stream));
     SSW_HIP_TRY(hipMemcpyAsync(out_scores_host, idx->gather_out, (size_t)n * sizeof(float),
                                hipMemcpyDeviceToHost, idx->stream));
     SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
@@ -941,8 +1049,16 @@ ssw_status ssw_index_gather_rows(ssw_index *idx, const int64_t *rows_host, int64
     SSW_TRY(stage_rows(idx, rows_host, n));
     float *buf = nullptr;
     SSW_HIP_TRY(hipMalloc((void **)&buf, (size_t)n * idx->dim * sizeof(float)));
-    hipLaunchKernelGGL(k_gather_rows_f32, dim3((unsigned)n), dim3(128), 0, idx->stream, idx->X, idx->gather_idx, n,
-                       (int)idx->dim, buf);
+    if (idx->dtype == SSW_DTYPE_F16) {  // widened, natural element order
+        const ssw_status st = launch_rows_from_h16(Xh(idx), idx->gather_idx, 0, n, idx->dim, buf, idx->stream);
+        if (st != SSW_OK) {
+            (void)hipFree(buf);
+            return st;
+        }
+    } else {
+        hipLaunchKernelGGL(k_gather_rows_f32, dim3((unsigned)n), dim3(128), 0, idx->stream, idx->X, idx->gather_idx, n,
+                           (int)idx->dim, buf);
+    }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess)
         e = hipMemcpyAsync(out_host, buf, (size_t)n * idx->dim * sizeof(float), hipMemcpyDeviceToHost, idx->stream);
@@ -1002,6 +1118,7 @@ ssw_status ssw_tune_topk(int32_t flags) {
 
 ssw_status ssw_tune_scan(int32_t variant, int32_t blocks_per_cu) {
     tune_scan(variant, blocks_per_cu);
+    tune_scan_h16(variant, blocks_per_cu);
     return SSW_OK;
 }
 #endif

@@ -598,6 +598,10 @@ extern "C" ssw_status ssw_knn_build(ssw_index *index, int32_t k, uint64_t seed, 
     int64_t n = 0, n_images = 0;
     int32_t D = 0;
     void *Xv = nullptr, *scores_unused = nullptr;
+    if (index_dtype(index) != SSW_DTYPE_F32) {  // the build reads the matrix as f32 rows
+        set_error("ssw_knn_build: the index holds f16 rows; build the graph from an f32 index of the widened rows");
+        return SSW_ERR_UNSUPPORTED;
+    }
     SSW_TRY(ssw_index_shape(index, &n, &D, &n_images));
     SSW_TRY(ssw_index_device_ptrs(index, &Xv, &scores_unused));
     SSW_REQUIRE(n >= 1 && n < (int64_t)0x7fff0000, "ssw_knn_build: n=%lld out of range", (long long)n);

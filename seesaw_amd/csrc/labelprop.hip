@@ -1687,6 +1687,10 @@ ssw_status ssw_labelprop_round(ssw_lp *lp, ssw_index *index, int32_t propagate, 
 ssw_status ssw_xlx(ssw_index *index, ssw_lp *lap, double *out_host) {
     SSW_REQUIRE(index != nullptr && lap != nullptr && out_host != nullptr, "NULL argument");
     SSW_REQUIRE(lap->perm == nullptr, "ssw_xlx: the Laplacian handle must be in original node order");
+    if (index_dtype(index) != SSW_DTYPE_F32) {  // the product reads the matrix as f32 rows
+        set_error("ssw_xlx: the index holds f16 rows; compute X'LX from an f32 index of the widened rows");
+        return SSW_ERR_UNSUPPORTED;
+    }
     int64_t n = 0, n_images = 0;
     int32_t D = 0;
     void *Xv = nullptr, *scores = nullptr;

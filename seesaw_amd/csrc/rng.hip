@@ -34,9 +34,14 @@ __device__ __forceinline__ int synth_int(uint32_t rowkey, uint32_t col) {
     return (int)((h1 & 0xffffu) + (h1 >> 16) + (h2 & 0xffffu) + (h2 >> 16)) - 131070;
 }
 
-// one wave per row; lane l produces columns 256*c + 4*l .. +3 (the scan's load layout)
-template <int C>
-__global__ __launch_bounds__(256) void k_fill_random(float *__restrict__ X, int64_t n,
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
+// one wave per row; lane l produces columns 256*c + 4*l .. +3 (the scan's load layout).  H: the f16 index -- the
+// same f32 values rounded to binary16 (nearest even), lane l's 8*C bytes contiguous (ssw_common.h, h16_group_pos)
+template <int C, bool H = false>
+__global__ __launch_bounds__(256) void k_fill_random(void *__restrict__ Xv, int64_t n,
                                                      uint64_t seed, int64_t first_row) {
     const int lane = threadIdx.x & 63;
     const int64_t gwave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -62,7 +67,8 @@ __global__ __launch_bounds__(256) void k_fill_random(float *__restrict__ X, int6
         for (int off = 32; off >= 1; off >>= 1) tot += __shfl_xor(tot, off, 64);
         const bool degenerate = !(tot > 0.0);
         const double norm = degenerate ? 1.0 : sqrt(tot);
-        float4 *dst = reinterpret_cast<float4 *>(X + r * (int64_t)(C * 256)) + lane;
+        float4 *dst = reinterpret_cast<float4 *>(static_cast<float *>(Xv) + r * (int64_t)(C * 256)) + lane;
+        u32x2 *dsth = reinterpret_cast<u32x2 *>(static_cast<uint16_t *>(Xv) + r * (int64_t)(C * 256) + lane * 4 * C);
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             float4 o;
@@ -71,33 +77,35 @@ __global__ __launch_bounds__(256) void k_fill_random(float *__restrict__ X, int6
             o.z = (float)((double)xi[c * 4 + 2] / norm);
             o.w = (float)((double)xi[c * 4 + 3] / norm);
             if (degenerate && c == 0 && lane == 0) o.x = 1.0f;
-            dst[c * 64] = o;
+            if constexpr (H) dsth[c] = __builtin_bit_cast(u32x2, __builtin_convertvector((f32x4{o.x, o.y, o.z, o.w}), h16x4));
+            else dst[c * 64] = o;
         }
     }
 }
 
 }  // namespace
 
-ssw_status launch_fill_random(float *X, int64_t n, int32_t dim, uint64_t seed, int64_t first_row,
-                              hipStream_t stream) {
+template <bool H>
+static ssw_status launch_fill_random_t(void *X, int64_t n, int32_t dim, uint64_t seed, int64_t first_row,
+                                       hipStream_t stream) {
     if (n <= 0) return SSW_OK;
     int64_t grid = (n + 3) / 4;
     if (grid > 256 * 8 * 4) grid = 256 * 8 * 4;
     switch (dim) {
         case 256:
-            hipLaunchKernelGGL(k_fill_random<1>, dim3((unsigned)grid), dim3(256), 0, stream, X, n,
+            hipLaunchKernelGGL((k_fill_random<1, H>), dim3((unsigned)grid), dim3(256), 0, stream, X, n,
                                seed, first_row);
             break;
         case 512:
-            hipLaunchKernelGGL(k_fill_random<2>, dim3((unsigned)grid), dim3(256), 0, stream, X, n,
+            hipLaunchKernelGGL((k_fill_random<2, H>), dim3((unsigned)grid), dim3(256), 0, stream, X, n,
                                seed, first_row);
             break;
         case 768:
-            hipLaunchKernelGGL(k_fill_random<3>, dim3((unsigned)grid), dim3(256), 0, stream, X, n,
+            hipLaunchKernelGGL((k_fill_random<3, H>), dim3((unsigned)grid), dim3(256), 0, stream, X, n,
                                seed, first_row);
             break;
         case 1024:
-            hipLaunchKernelGGL(k_fill_random<4>, dim3((unsigned)grid), dim3(256), 0, stream, X, n,
+            hipLaunchKernelGGL((k_fill_random<4, H>), dim3((unsigned)grid), dim3(256), 0, stream, X, n,
                                seed, first_row);
             break;
         default:
@@ -106,6 +114,16 @@ ssw_status launch_fill_random(float *X, int64_t n, int32_t dim, uint64_t seed, i
     }
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
+}
+
+ssw_status launch_fill_random(float *X, int64_t n, int32_t dim, uint64_t seed, int64_t first_row,
+                              hipStream_t stream) {
+    return launch_fill_random_t<false>(X, n, dim, seed, first_row, stream);
+}
+
+ssw_status launch_fill_random_h16(uint16_t *X, int64_t n, int32_t dim, uint64_t seed, int64_t first_row,
+                                  hipStream_t stream) {
+    return launch_fill_random_t<true>(X, n, dim, seed, first_row, stream);
 }
 
 }  // namespace ssw

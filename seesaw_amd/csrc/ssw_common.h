@@ -127,14 +127,39 @@ ssw_status index_enqueue_topk_resident(ssw_index *idx, hipStream_t on_stream, co
 ssw_status index_collect_topk(ssw_index *idx, hipStream_t on_stream, int32_t k, int64_t *out_images, float *out_scores,
                               int64_t *out_best_rows, int32_t *out_count);
 int index_device(const ssw_index *idx);
+// element type of the resident matrix (SSW_DTYPE_*), its device pointer and shape, for the entries outside
+// capi_index.hip that read it through a handle (feedback gathers; k-NN and X'LX refuse an f16 matrix)
+int32_t index_dtype(const ssw_index *idx);
+const void *index_matrix(const ssw_index *idx, int64_t *n_rows, int32_t *dim);
+
+// ---- the f16 index's row layout ---------------------------------------------------------------------------------
+// A row of dim = 256*C binary16 elements is stored LANE-INTERLEAVED: the 4*C elements scan lane l works on
+// (256*c + 4*l + j, c < C, j < 4, the f32 scan's lane/element map) are the 8*C contiguous bytes at l*8*C, chunk c at
+// byte 8*c inside them.  A row stays dim*2 contiguous bytes; at dim 512 a lane reads its part with one 16-byte load.
+// Position (in elements) of the 4-element group that starts at natural element e (e % 4 == 0) of a row:
+__host__ __device__ inline int h16_group_pos(int e, int C) { return ((e & 255) >> 2) * 4 * C + (e >> 8) * 4; }
 
 // scan.hip: scores[i] = dot(X[i,:], q) in the fixed kernel order (see scan.hip).
 ssw_status launch_scan(const float *X, const float *q_dev, float *scores, int64_t n, int32_t dim,
                        int device, hipStream_t stream);
 ssw_status launch_score_rows(const float *X, const float *q_dev, const int64_t *rows_dev, int64_t n,
                              int32_t dim, float *out, hipStream_t stream);
+// scan_f16.hip: the same over an f16 index (lane-interleaved rows, see above): the bits of the f32 kernels on the
+// widened rows
+ssw_status launch_scan_h16(const uint16_t *X, const float *q_dev, float *scores, int64_t n, int32_t dim,
+                           int device, hipStream_t stream);
+ssw_status launch_score_rows_h16(const uint16_t *X, const float *q_dev, const int64_t *rows_dev, int64_t n,
+                                 int32_t dim, float *out, hipStream_t stream);
+// natural-order rows <-> the f16 layout.  to_h16: n rows of natural-order f32 (src_f32) or binary16 (src_h16, the
+// other NULL) -> rows [0, n) of dst, rounded to nearest even.  to_f32: rows (rows_dev[i], or first_row + i when
+// rows_dev is NULL) of X -> n natural-order f32 rows of out.
+ssw_status launch_rows_to_h16(const float *src_f32, const uint16_t *src_h16, int64_t n, int32_t dim, uint16_t *dst,
+                              hipStream_t stream);
+ssw_status launch_rows_from_h16(const uint16_t *X, const int64_t *rows_dev, int64_t first_row, int64_t n, int32_t dim,
+                                float *out, hipStream_t stream);
 #ifdef SSW_DEBUG_HOOKS
 void tune_scan(int variant, int blocks_per_cu);
+void tune_scan_h16(int variant, int blocks_per_cu);  // scan_f16.hip
 #endif
 // knn.hip's last stage (lives in scan.hip to share the scan's summation order)
 ssw_status launch_knn_rescore(const float *X, int32_t dim, const int32_t *perm, int r0, int rows, const uint64_t *buf,
@@ -200,6 +225,9 @@ ssw_status launch_gemm_pw4(int epi, hipStream_t stream, const void *A, const voi
 // rng.hip: synthetic unit-norm rows.
 ssw_status launch_fill_random(float *X, int64_t n, int32_t dim, uint64_t seed, int64_t first_row,
                               hipStream_t stream);
+// the same values rounded to binary16, written in the f16 index's row layout
+ssw_status launch_fill_random_h16(uint16_t *X, int64_t n, int32_t dim, uint64_t seed, int64_t first_row,
+                                  hipStream_t stream);
 
 // side outputs / inputs of the selection's last kernel for the row-sharded exchange (select.hip, k_final)
 struct FinalExchange {

@@ -1,4 +1,7 @@
-"""DeviceIndex: the [N, d] f32 vector matrix resident in HBM + scan / top-k over the C-ABI.
+"""DeviceIndex: the [N, d] vector matrix resident in HBM + scan / top-k over the C-ABI.
+
+The matrix is f32 by default; `dtype=np.float16` stores it as IEEE binary16 (half the bytes), and every result is then
+the bits an f32 index of the widened rows `X.astype(np.float16).astype(np.float32)` returns.
 
 This is the object the reference-shaped indices (`seesaw_amd.indices.*`,
 `seesaw_amd.vector_index.VectorIndex`) delegate their numeric work to.  It replaces
@@ -20,34 +23,69 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else ctypes.c_void_p(a.ctypes.data)
 
 
+_DTYPE_CODES = {np.dtype(np.float32): _lib.SSW_DTYPE_F32, np.dtype(np.float16): _lib.SSW_DTYPE_F16}
+
+
+def vector_dtype(dtype) -> np.dtype:
+    """np.float32 / np.float16 (or "float32" / "float16", "f4" / "f2") -> the numpy dtype of the index's storage;
+    anything else raises ValueError"""
+    try:
+        dt = np.dtype(dtype)
+    except TypeError:
+        dt = None
+    if dt not in _DTYPE_CODES:
+        raise ValueError(f"vector dtype {dtype!r} unsupported (float32 or float16)")
+    return dt
+
+
+def round_vectors(vectors: np.ndarray, dtype) -> np.ndarray:
+    """the f32 rows an index of storage `dtype` holds for `vectors`: the rows themselves for float32, the widened
+    binary16 rounding (numpy's astype(float16): nearest even) for float16"""
+    dt = vector_dtype(dtype)
+    if dt == np.float16:
+        return np.asarray(vectors).astype(np.float16).astype(np.float32)
+    return np.ascontiguousarray(vectors, dtype=np.float32)
+
+
 class DeviceIndex:
-    def __init__(self, n_rows: int, dim: int = 512, device: int = 0, dev_ptr: int = 0):
+    def __init__(self, n_rows: int, dim: int = 512, device: int = 0, dev_ptr: int = 0, dtype=np.float32):
         self._h = ctypes.c_void_p()
         self.n_rows = int(n_rows)
         self.dim = int(dim)
         self.device = int(device)
         self.n_images = self.n_rows
-        _lib.call("ssw_index_create", self.device, self.n_rows, self.dim,
+        self.dtype = vector_dtype(dtype)
+        _lib.call("ssw_index_create_typed", self.device, self.n_rows, self.dim, _DTYPE_CODES[self.dtype],
                   ctypes.c_void_p(dev_ptr) if dev_ptr else None, ctypes.byref(self._h))
 
     # -- construction -----------------------------------------------------------------
     @classmethod
     def from_numpy(cls, vectors: np.ndarray, row2image: Optional[np.ndarray] = None,
-                   device: int = 0, chunk_rows: int = 1 << 18) -> "DeviceIndex":
+                   device: int = 0, chunk_rows: int = 1 << 18, dtype=np.float32) -> "DeviceIndex":
+        """dtype=np.float16: the rows become numpy's `vectors.astype(np.float16)`.  binary16 input goes up as it is, f32
+        input is rounded on the device, any other input (f64, ...) is rounded on the host chunk by chunk -- directly, as
+        numpy rounds it, not through f32 (f64 -> f32 -> f16 could round a tie differently)"""
         vectors = np.asarray(vectors)
         assert vectors.ndim == 2, "vectors must be [N, d]"
-        idx = cls(vectors.shape[0], vectors.shape[1], device=device)
+        idx = cls(vectors.shape[0], vectors.shape[1], device=device, dtype=dtype)
+        raw = idx.dtype == np.float16 and vectors.dtype != np.float32
         for r0 in range(0, vectors.shape[0], chunk_rows):
-            chunk = np.ascontiguousarray(vectors[r0:r0 + chunk_rows], dtype=np.float32)
-            _lib.call("ssw_index_upload", idx._h, _ptr(chunk), r0, chunk.shape[0])
+            if raw:
+                chunk = np.ascontiguousarray(vectors[r0:r0 + chunk_rows], dtype=np.float16)
+                _lib.call("ssw_index_upload_f16", idx._h, _ptr(chunk), r0, chunk.shape[0])
+            else:
+                chunk = np.ascontiguousarray(vectors[r0:r0 + chunk_rows], dtype=np.float32)
+                _lib.call("ssw_index_upload", idx._h, _ptr(chunk), r0, chunk.shape[0])
         if row2image is not None:
             idx.set_row2image(row2image)
         return idx
 
     @classmethod
     def synthetic(cls, n_rows: int, dim: int = 512, seed: int = 0, first_row: int = 0,
-                  device: int = 0) -> "DeviceIndex":
-        idx = cls(n_rows, dim, device=device)
+                  device: int = 0, dtype=np.float32) -> "DeviceIndex":
+        """rows oracle.synth_rows(seed, first_row, n_rows, dim) generated on the device (rounded to binary16 for
+        dtype=np.float16)"""
+        idx = cls(n_rows, dim, device=device, dtype=dtype)
         _lib.call("ssw_index_fill_random", idx._h, ctypes.c_uint64(seed), int(first_row))
         return idx
 
@@ -82,6 +120,7 @@ class DeviceIndex:
         return out
 
     def device_ptrs(self):
+        """(matrix, scores) device pointers.  An f16 index's matrix is in its private lane-interleaved layout."""
         v, s = ctypes.c_void_p(), ctypes.c_void_p()
         _lib.call("ssw_index_device_ptrs", self._h, ctypes.byref(v), ctypes.byref(s))
         return v.value, s.value
@@ -152,7 +191,7 @@ class DeviceIndex:
         return out
 
     def gather_rows(self, rows: np.ndarray) -> np.ndarray:
-        """`vectors[rows]` [n, dim] f32 out of the resident matrix"""
+        """`vectors[rows]` [n, dim] f32 out of the resident matrix (widened for an f16 index)"""
         rows = np.ascontiguousarray(rows, dtype=np.int64)
         out = np.empty((rows.shape[0], self.dim), dtype=np.float32)
         _lib.call("ssw_index_gather_rows", self._h, _ptr(rows), rows.shape[0], _ptr(out))

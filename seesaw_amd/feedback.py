@@ -72,8 +72,11 @@ class FeedbackEngine:
     def set_data_from_index(self, device_index, rows: np.ndarray, center: bool):
         """gather the labelled rows out of the index matrix already resident in HBM."""
         rows = np.ascontiguousarray(rows, dtype=np.int64)
-        vec_ptr, _ = device_index.device_ptrs()
         self.n = rows.shape[0]
+        if getattr(device_index, "dtype", np.float32) == np.float16:  # the handle tells the gather the element type
+            _lib.call("ssw_fb_set_data_from_index", self._h, device_index._h, _p(rows), self.n, int(center))
+            return
+        vec_ptr, _ = device_index.device_ptrs()
         _lib.call("ssw_fb_set_data_from_device", self._h, ctypes.c_void_p(vec_ptr), device_index.n_rows,
                   _p(rows), self.n, int(center))
 
@@ -85,8 +88,12 @@ class FeedbackEngine:
         y = np.ascontiguousarray(labelled_y, dtype=np.float32)
         drawn = np.ascontiguousarray(drawn, dtype=np.int64)
         assert rows.shape == y.shape
-        vec_ptr, _ = device_index.device_ptrs()
         self.n = rows.shape[0] + drawn.shape[0]
+        if getattr(device_index, "dtype", np.float32) == np.float16:
+            _lib.call("ssw_fb_set_pseudo_sample_from_index", self._h, device_index._h, ctypes.c_void_p(dev_scores_ptr),
+                      _p(rows), _p(y), rows.shape[0], _p(drawn), drawn.shape[0], float(real_weight), int(center))
+            return self.n
+        vec_ptr, _ = device_index.device_ptrs()
         _lib.call("ssw_fb_set_pseudo_sample", self._h, ctypes.c_void_p(vec_ptr), device_index.n_rows,
                   ctypes.c_void_p(dev_scores_ptr), _p(rows), _p(y), rows.shape[0], _p(drawn), drawn.shape[0],
                   float(real_weight), int(center))

@@ -15,7 +15,7 @@ import numpy as np
 import pandas as pd
 
 from ...bitmap import BitMap, FrozenBitMap
-from ...device_index import DeviceIndex
+from ...device_index import DeviceIndex, round_vectors, vector_dtype as _vector_dtype
 from ...query_interface import AccessMethod, InteractiveQuery
 from ..interface import ActivationFrames, resolve_path
 
@@ -31,17 +31,20 @@ def _positions_of(sorted_dbidx: np.ndarray, ids) -> np.ndarray:
 
 class CoarseIndex(AccessMethod):
     def __init__(self, embedding, vectors: np.ndarray, vector_meta: pd.DataFrame, path: str = None,
-                 device: int = 0):
+                 device: int = 0, vector_dtype: str = "float32"):
+        """vector_dtype="float16": the resident matrix is binary16 and `self.vectors` holds the widened rounded rows
+        (what every host-side expression then reads is what the device scans)"""
         self.path = path
         self.embedding = embedding
-        self.vectors = np.ascontiguousarray(vectors, dtype=np.float32)
+        self.vector_dtype = _vector_dtype(vector_dtype)
+        self.vectors = round_vectors(vectors, self.vector_dtype)
         self.vector_meta = vector_meta
         dbidx = np.asarray(vector_meta.dbidx.values, dtype=np.int64)
         assert np.all(np.diff(dbidx) > 0), "one vector per image, sorted by dbidx (coarse_index.py:49)"
         self._dbidx = dbidx
         self.all_indices = FrozenBitMap(dbidx)
         self.device = device
-        self._dev = DeviceIndex.from_numpy(self.vectors, device=device)
+        self._dev = DeviceIndex.from_numpy(self.vectors, device=device, dtype=self.vector_dtype)
 
     def __len__(self):
         return len(self.all_indices)
@@ -54,7 +57,8 @@ class CoarseIndex(AccessMethod):
         return self._dev.scores(tvec)
 
     @staticmethod
-    def from_path(index_path: str, *, use_vec_index=False, exclude=None, device: int = 0, **_):
+    def from_path(index_path: str, *, use_vec_index=False, exclude=None, device: int = 0, vector_dtype: str = "float32",
+                  **_):
         """<index>/vectors.npy [N,512] f32 + <index>/vector_meta.parquet (dbidx, ...) + info.json."""
         index_path = resolve_path(index_path)
         info = json.load(open(f"{index_path}/info.json"))
@@ -64,7 +68,7 @@ class CoarseIndex(AccessMethod):
         meta = pd.read_parquet(f"{index_path}/vector_meta.parquet")
         assert meta.dbidx.is_monotonic_increasing, "sanity check"
         return CoarseIndex(embedding=embedding, vectors=np.asarray(vectors), vector_meta=meta,
-                           path=index_path, device=device)
+                           path=index_path, device=device, vector_dtype=vector_dtype)
 
     def query(self, *, topk, vector=None, exclude=None, startk=None, **kwargs):
         exclude = BitMap() if exclude is None else exclude
@@ -93,7 +97,8 @@ class CoarseIndex(AccessMethod):
     def subset(self, indices: BitMap):
         mask = np.isin(self._dbidx, np.asarray(indices, dtype=np.int64))
         return CoarseIndex(embedding=self.embedding, vectors=self.vectors[mask],
-                           vector_meta=self.vector_meta[mask].reset_index(drop=True), device=self.device)
+                           vector_meta=self.vector_meta[mask].reset_index(drop=True), device=self.device,
+                           vector_dtype=self.vector_dtype)
 
 
 class CoarseQuery(InteractiveQuery):

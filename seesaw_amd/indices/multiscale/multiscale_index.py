@@ -166,8 +166,14 @@ class MultiscaleIndex(AccessMethod):
     """implements a two stage lookup"""
 
     def __init__(self, *, embedding, vectors: np.ndarray, vector_meta: pd.DataFrame, vec_index=None,
-                 min_zoom_level=1, path: str = None, excluded: BitMap = None, device: int = 0):
+                 min_zoom_level=1, path: str = None, excluded: BitMap = None, device: int = 0,
+                 vector_dtype: str = "float32"):
+        """vector_dtype="float16": the resident matrix is binary16 (half the HBM) and `self.vectors` holds the widened
+        rounded rows, so every host-side expression (`index.vectors[rows]` of the fitting loops) reads the numbers the
+        device scans"""
+        from ...device_index import vector_dtype as _vector_dtype
         self.embedding = embedding
+        self.vector_dtype = _vector_dtype(vector_dtype)
         self.path = path
         self.excluded = BitMap([]) if excluded is None else excluded
         if min_zoom_level != 1:  # drop the finest zoom level except where it is the only one
@@ -176,7 +182,8 @@ class MultiscaleIndex(AccessMethod):
             keep = ((vector_meta.zoom_level == zmax) | (vector_meta.zoom_level >= min_zoom_level)).values
             vector_meta = vector_meta[keep].reset_index(drop=True)
             vectors = vectors[keep]
-        self.vectors = np.ascontiguousarray(vectors, dtype=np.float32)
+        from ...device_index import round_vectors
+        self.vectors = round_vectors(vectors, self.vector_dtype)
         self.vector_meta = vector_meta.reset_index(drop=True)
         self.vec_index = vec_index  # accepted for signature parity; the exact GPU scan is always used
         row_dbidx = np.asarray(self.vector_meta.dbidx.values, dtype=np.int64)
@@ -195,13 +202,15 @@ class MultiscaleIndex(AccessMethod):
 
     def _init_device(self):
         """the whole matrix into HBM (a sharded index overrides this with its own slice)"""
-        self._dev = DeviceIndex.from_numpy(self.vectors, row2image=self._row2pos.astype(np.int32), device=self.device)
+        self._dev = DeviceIndex.from_numpy(self.vectors, row2image=self._row2pos.astype(np.int32), device=self.device,
+                                           dtype=self.vector_dtype)
         if self._has_tile_meta:  # tile geometry next to the vectors: the avg_score aggregation runs on the device
             self._dev.set_tile_meta(self._box, self.vector_meta.zoom_level.values)
 
     # ---- construction -----------------------------------------------------------------
     @staticmethod
-    def from_path(index_path: str, *, use_vec_index=True, exclude=None, device: int = 0, **options):
+    def from_path(index_path: str, *, use_vec_index=True, exclude=None, device: int = 0, vector_dtype: str = "float32",
+                  **options):
         """<index>/info.json {"constructor", "model", ...} plus either the reference's
         <index>/vectors.sorted.cached parquet (as create_multiscale_index writes it) or
         <index>/vectors.npy [N,512] f32 + <index>/vector_meta.parquet; rows sorted by dbidx."""
@@ -218,7 +227,8 @@ class MultiscaleIndex(AccessMethod):
         meta = meta[["dbidx", "zoom_level", "x1", "y1", "x2", "y2"]]
         return MultiscaleIndex(embedding=embedding, vectors=np.asarray(vectors), vector_meta=meta,
                                vec_index=None, path=index_path,
-                               excluded=info.get("excluded", None) if exclude is None else exclude, device=device)
+                               excluded=info.get("excluded", None) if exclude is None else exclude, device=device,
+                               vector_dtype=vector_dtype)
 
     def get_knng(self, path=None):
         from ...knn_graph import KNNGraph
@@ -373,7 +383,7 @@ class MultiscaleIndex(AccessMethod):
             return self
         return MultiscaleIndex(embedding=self.embedding, vectors=self.vectors[mask],
                                vector_meta=self.vector_meta[mask].reset_index(drop=True), vec_index=None,
-                               device=self.device)
+                               device=self.device, vector_dtype=self.vector_dtype)
 
 
 class BoxFeedbackQuery(InteractiveQuery):

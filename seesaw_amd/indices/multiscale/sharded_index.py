@@ -45,13 +45,14 @@ class DeviceShard:
     """one rank's slice in HBM: the same DeviceIndex the unsharded index uses, results left on the device"""
 
     def __init__(self, vectors: np.ndarray, row2image: np.ndarray, boxes: Optional[np.ndarray], zoom: Optional[np.ndarray],
-                 device: int):
+                 device: int, vector_dtype: str = "float32"):
         import torch
         from ... import _lib
         from ...device_index import DeviceIndex
         self.torch = torch
         self.tdev = torch.device("cuda", device)
-        self.index = DeviceIndex.from_numpy(vectors, row2image=row2image.astype(np.int32), device=device)
+        self.index = DeviceIndex.from_numpy(vectors, row2image=row2image.astype(np.int32), device=device,
+                                            dtype=vector_dtype)
         if boxes is not None:
             self.index.set_tile_meta(boxes, zoom)
         self.index.set_stream(torch.cuda.current_stream(self.tdev).cuda_stream)
@@ -132,19 +133,21 @@ class _ShardedRows:
 class ShardedMultiscaleIndex(MultiscaleIndex):
     def __init__(self, *, embedding, vectors: Optional[np.ndarray], vector_meta: pd.DataFrame, rank: int, world: int,
                  local_vectors: Optional[np.ndarray] = None, device: int = 0, group=None, k_max: int = 1024,
-                 comm_device=None, shard_factory=DeviceShard, merge=None, path: str = None, excluded: BitMap = None):
+                 comm_device=None, shard_factory=DeviceShard, merge=None, path: str = None, excluded: BitMap = None,
+                 vector_dtype: str = "float32"):
         """vectors: the full [N, 512] host array (sliced here) or None with `local_vectors` = this rank's rows.
         comm_device: where the collective's tensors live -- None = the shard's GPU (backend nccl = RCCL); "cpu"
         for a gloo group (the messages make a host round trip; used by the tests on one-GPU boxes)."""
         self.rank, self.world, self.group = int(rank), int(world), group
         self._k_max, self._comm_device, self._shard_factory, self._merge = int(k_max), comm_device, shard_factory, merge
-        self._local_vectors = local_vectors
+        from ...device_index import round_vectors
+        self._local_vectors = None if local_vectors is None else round_vectors(local_vectors, vector_dtype)
         serve_rows = vectors is None
         if vectors is None:
             assert local_vectors is not None
             vectors = np.zeros((vector_meta.shape[0], 0), dtype=np.float32)  # placeholder: meta only
         super().__init__(embedding=embedding, vectors=vectors, vector_meta=vector_meta, vec_index=None, path=path,
-                         excluded=excluded, device=device)
+                         excluded=excluded, device=device, vector_dtype=vector_dtype)
         if serve_rows:  # no rank holds the matrix: `index.vectors[rows]` gathers from the owning shards
             self.vectors = _ShardedRows(self, int(local_vectors.shape[1]))
 
@@ -168,7 +171,8 @@ class ShardedMultiscaleIndex(MultiscaleIndex):
             r2i = self._row2pos[self.row_lo:self.row_hi] - self.img_lo
             boxes = self._box[self.row_lo:self.row_hi] if self._has_tile_meta else None
             zoom = self.vector_meta.zoom_level.values[self.row_lo:self.row_hi] if self._has_tile_meta else None
-            self._shard = self._shard_factory(np.ascontiguousarray(local, dtype=np.float32), r2i, boxes, zoom, self.device)
+            kw = {} if self.vector_dtype == np.float32 else {"vector_dtype": self.vector_dtype}
+            self._shard = self._shard_factory(np.ascontiguousarray(local, dtype=np.float32), r2i, boxes, zoom, self.device, **kw)
         compute_dev = torch.device("cuda", self.device) if self._shard_factory is DeviceShard else torch.device("cpu")
         kw = {} if self._merge is None else {"merge": self._merge}
         self._xchg = ShardedTopK(rank=self.rank, world=self.world, device=compute_dev, image_offset=self.img_lo,

@@ -256,7 +256,8 @@ class ShardedSyntheticIndex:
     over the ranks of the default process group; each rank generates its slice in place."""
 
     def __init__(self, n_total: int, dim: int, seed: int, rank: int, world: int,
-                 local_device: int, k_max: int = 128, group=None, force_collective: bool = False, comm_device=None):
+                 local_device: int, k_max: int = 128, group=None, force_collective: bool = False, comm_device=None,
+                 vector_dtype: str = "float32"):
         import torch
         from .device_index import DeviceIndex
         self.torch = torch
@@ -266,7 +267,7 @@ class ShardedSyntheticIndex:
         self.n_local = self.row_hi - self.row_lo
         self.device = torch.device("cuda", local_device)
         self.local = DeviceIndex.synthetic(self.n_local, dim, seed=seed, first_row=self.row_lo,
-                                           device=local_device)
+                                           device=local_device, dtype=vector_dtype)
         # run the library's kernels on torch's current stream so the collective and the
         # merge are ordered behind the scan without host synchronisation
         self.local.set_stream(torch.cuda.current_stream(self.device).cuda_stream)

@@ -72,8 +72,10 @@ class SyntheticDataset:
         self.paths = self.file_meta.file_path.values
         self.embedding = embedding or SyntheticEmbedding(directions, vectors.shape[1])
         self.knn_k = knn_k
-        self._index = None
-        self._knng = None
+        self._index = None   # the index of the last load_index
+        self._indexes = {}   # vector dtype -> index: an f16 request never returns an f32 index, nor the reverse
+        self._knngs = {}     # vector dtype -> k-NN graph of the rows that index holds
+        self._dtype = np.dtype(np.float32)
 
     # ---- what Session / benchmark_loop call ---------------------------------------------
     def load_subset(self, c_name):
@@ -94,29 +96,36 @@ class SyntheticDataset:
         return [f"/data/{self.name}/{int(i):08d}.jpg" for i in idxbatch]
 
     def knn_graph(self, name="exact") -> KNNGraph:
-        if self._knng is None:
+        if self._dtype not in self._knngs:
             assert self.knn_k > 0, "dataset built without a k-NN graph"
             dev = getattr(self._index, "_dev", None) if self._index is not None else None  # matrix already resident
             # stored like the reference's graphs: a pool larger than the k the loops keep, so that
             # KNNGraph.restrict_k(k=knn_k) applies `dst_rank < knn_k` (self + knn_k - 1 neighbours) exactly as
             # it does to the reference's 60-neighbour pools (knn_graph.py:264-266)
             pool = min(MAX_EXACT_K, self.knn_k + 1)
-            self._knng = KNNGraph(compute_exact_knn(self.vectors, n_neighbors=pool, device_index=dev,
-                                                    device=getattr(self, "device", 0) or 0))
-        return self._knng
+            # (the rows the index holds: an f16 index's are the widened rounded rows; the graph is built from f32 rows)
+            vecs = self._index.vectors if self._index is not None else self.vectors
+            self._knngs[self._dtype] = KNNGraph(compute_exact_knn(vecs, n_neighbors=pool, device_index=dev,
+                                                                  device=getattr(self, "device", 0) or 0))
+        return self._knngs[self._dtype]
 
     def load_index(self, i_name=None, *, options=None):
+        """options["vector_dtype"] ("float32" default, "float16") selects the resident matrix's element type; the
+        cached index is kept per dtype (a request of the other dtype builds a new one)"""
+        from .device_index import vector_dtype as _vector_dtype
+        dt = _vector_dtype((options or {}).get("vector_dtype", "float32"))
+        self._index, self._dtype = self._indexes.get(dt), dt
         if self._index is None:
             tiles = self.vector_meta.groupby("dbidx").size().max()
             if tiles == 1 and i_name != "multiscale":
                 from .indices.coarse.coarse_index import CoarseIndex
                 idx = CoarseIndex(embedding=self.embedding, vectors=self.vectors, vector_meta=self.vector_meta,
-                                  path=self.path, device=self.device)
+                                  path=self.path, device=self.device, vector_dtype=dt)
             else:
                 from .indices.multiscale.multiscale_index import MultiscaleIndex
                 idx = MultiscaleIndex(embedding=self.embedding, vectors=self.vectors, vector_meta=self.vector_meta,
-                                      vec_index=None, path=self.path, device=self.device)
-            self._index = idx  # before the graph is built: knn_graph() then uses the matrix the index already holds in HBM
+                                      vec_index=None, path=self.path, device=self.device, vector_dtype=dt)
+            self._index = self._indexes[dt] = idx  # before the graph is built: knn_graph() then uses the matrix the index already holds in HBM
             if self.knn_k > 0:
                 graph = self.knn_graph()
                 idx.knng = {name: graph for name in ("exact", "nndescent60", "")}

@@ -11,7 +11,7 @@ import time
 
 import numpy as np
 
-from .device_index import DeviceIndex
+from .device_index import DeviceIndex, vector_dtype as _vector_dtype
 
 
 def build_annoy_idx(*, vecs, output_path, n_trees=None):
@@ -30,11 +30,12 @@ def build_nndescent_idx(vecs, output_path, n_trees=None):
 
 
 class VectorIndex:
-    def __init__(self, *, load_path=None, prefault=False, vectors: np.ndarray = None, device: int = 0):
+    def __init__(self, *, load_path=None, prefault=False, vectors: np.ndarray = None, device: int = 0,
+                 vector_dtype: str = "float32"):
         if vectors is None:
             vectors = np.load(load_path, mmap_mode=None if prefault else "r")
         assert vectors.ndim == 2 and vectors.shape[1] == 512, "VectorIndex holds [N, 512] vectors"
-        self._dev = DeviceIndex.from_numpy(np.asarray(vectors), device=device)
+        self._dev = DeviceIndex.from_numpy(np.asarray(vectors), device=device, dtype=_vector_dtype(vector_dtype))
         self.n = vectors.shape[0]
 
     def ready(self):
