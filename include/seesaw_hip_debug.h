@@ -20,7 +20,7 @@ extern "C" {
  * (0 u4, 1 u4+nt, 2 u8, 3 u8+nt, 4 u2+nt; -1 = default) and cap its resident blocks per CU
  * (0 = no cap, -1 = default).  Indexes under 65 536 rows run a latency-shaped kernel (8 rows in flight per wave, query
  * through LDS) unless a variant is named; -2 = the default streaming variant at every size.  All produce identical bits.
- * The f16 index's scan (scan_f16.hip) takes the same call: at dim=512 0 u4, 1 u8+nt, 4 u2+nt, other = default u4+nt. */
+ * The f16 index's scan reads the same switches: at dim=512 0 u4, 1 u8+nt, 4 u2+nt, other = default u4+nt. */
 ssw_status ssw_tune_scan(int32_t variant, int32_t blocks_per_cu);
 
 /* ssw_index_topk on an index of <= 8192 images / 65536 rows and <= 8192 excluded ids runs as three launches (query staged

@@ -76,7 +76,7 @@ struct ssw_index {
     int64_t n_images = 0;
     bool has_map = false;
     int32_t dtype = SSW_DTYPE_F32;
-    float *X = nullptr;  // SSW_DTYPE_F16: binary16 rows in the lane-interleaved layout (ssw_common.h), see Xh()
+    float *X = nullptr;  // SSW_DTYPE_F16: binary16 rows in the lane-interleaved layout (ssw_common.h)
     bool owns_X = false;
     // f16 upload / download: bounded device staging of natural-order rows (f32 or binary16)
     void *xfer = nullptr;
@@ -117,9 +117,6 @@ struct ssw_index {
     int ev_used = 0;
 };
 
-static const uint16_t *Xh(const ssw_index *idx) { return reinterpret_cast<const uint16_t *>(idx->X); }
-static uint16_t *Xh(ssw_index *idx) { return reinterpret_cast<uint16_t *>(idx->X); }
-
 static ssw_status ensure_ws(ssw_index *idx) {
     if (idx->ws_ready) return SSW_OK;
     SSW_TRY(select_alloc(idx->ws, idx->n, idx->n_images, idx->has_map));
@@ -158,9 +155,7 @@ static ssw_status stage_query(ssw_index *idx, const float *q_host) {
 }
 
 static ssw_status launch_index_scan(ssw_index *idx, const float *q_dev) {
-    if (idx->dtype == SSW_DTYPE_F16)
-        return launch_scan_h16(Xh(idx), q_dev, idx->scores, idx->n, idx->dim, idx->device, idx->stream);
-    return launch_scan(idx->X, q_dev, idx->scores, idx->n, idx->dim, idx->device, idx->stream);
+    return launch_scan(idx->X, idx->dtype, q_dev, idx->scores, idx->n, idx->dim, idx->device, idx->stream);
 }
 
 static ssw_status do_scan(ssw_index *idx, const float *q_dev) {
@@ -377,7 +372,7 @@ static ssw_status upload_h16(ssw_index *idx, const void *host_rows, bool src_h16
                                    idx->stream));
         SSW_TRY(launch_rows_to_h16(src_h16 ? nullptr : static_cast<const float *>(idx->xfer),
                                    src_h16 ? static_cast<const uint16_t *>(idx->xfer) : nullptr, m, idx->dim,
-                                   Xh(idx) + (first_row + r) * idx->dim, idx->stream));
+                                   reinterpret_cast<uint16_t *>(idx->X) + (first_row + r) * idx->dim, idx->stream));
     }
     SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
     return SSW_OK;
@@ -422,8 +417,8 @@ ssw_status ssw_index_download(ssw_index *idx, float *host_rows, int64_t first_ro
         const int64_t chunk = (int64_t)(idx->xfer_bytes / row_bytes);
         for (int64_t r = 0; r < n; r += chunk) {
             const int64_t m = std::min(chunk, n - r);
-            SSW_TRY(launch_rows_from_h16(Xh(idx), nullptr, first_row + r, m, idx->dim, static_cast<float *>(idx->xfer),
-                                         idx->stream));
+            SSW_TRY(launch_gather_rows(idx->X, idx->dtype, nullptr, first_row + r, m, idx->dim,
+                                       static_cast<float *>(idx->xfer), idx->stream));
             SSW_HIP_TRY(hipMemcpyAsync(host_rows + (size_t)r * idx->dim, idx->xfer, (size_t)m * row_bytes,
                                        hipMemcpyDeviceToHost, idx->stream));
         }
@@ -440,10 +435,7 @@ ssw_status ssw_index_download(ssw_index *idx, float *host_rows, int64_t first_ro
 ssw_status ssw_index_fill_random(ssw_index *idx, uint64_t seed, int64_t global_first_row) {
     SSW_REQUIRE(idx != nullptr, "idx is NULL");
     DeviceGuard guard(idx->device);
-    if (idx->dtype == SSW_DTYPE_F16)
-        SSW_TRY(launch_fill_random_h16(Xh(idx), idx->n, idx->dim, seed, global_first_row, idx->stream));
-    else
-        SSW_TRY(launch_fill_random(idx->X, idx->n, idx->dim, seed, global_first_row, idx->stream));
+    SSW_TRY(launch_fill_random(idx->X, idx->dtype, idx->n, idx->dim, seed, global_first_row, idx->stream));
     SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
     return SSW_OK;
 }
@@ -1000,11 +992,8 @@ ssw_status ssw_index_score_rows(ssw_index *idx, const float *q_host, const int64
     SSW_TRY(stage_rows(idx, rows_host, n));
     if (!idx->q2_dev) SSW_HIP_TRY(hipMalloc((void **)&idx->q2_dev, (size_t)idx->dim * sizeof(float)));
     SSW_TRY(idx->q2_stage.push(idx->q2_dev, q_host, (size_t)idx->dim * sizeof(float), idx->stream));
-    if (idx->dtype == SSW_DTYPE_F16)
-        SSW_TRY(launch_score_rows_h16(Xh(idx), idx->q2_dev, idx->gather_idx, n, idx->dim, idx->gather_out, idx->stream));
-    else
-        SSW_TRY(launch_score_rows(idx->X, idx->q2_dev, idx->gather_idx, n, idx->dim, idx->gather_out,
-                                  idx->stream));
+    SSW_TRY(launch_score_rows(idx->X, idx->dtype, idx->q2_dev, idx->gather_idx, n, idx->dim, idx->gather_out,
+                              idx->stream));
     SSW_HIP_TRY(hipMemcpyAsync(out_scores_host, idx->gather_out, (size_t)n * sizeof(float),
                                hipMemcpyDeviceToHost, idx->stream));
     SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
@@ -1025,16 +1014,6 @@ ssw_status ssw_index_gather_scores(ssw_index *idx, const int64_t *rows_host, int
     return SSW_OK;
 }
 
-namespace {
-__global__ void k_gather_rows_f32(const float *__restrict__ X, const int64_t *__restrict__ rows, int64_t n, int dim,
-                                  float *__restrict__ out) {
-    const int64_t r = blockIdx.x;
-    const float4 *src = reinterpret_cast<const float4 *>(X + rows[r] * dim);
-    float4 *dst = reinterpret_cast<float4 *>(out + r * dim);
-    for (int c = threadIdx.x; c < dim / 4; c += blockDim.x) dst[c] = src[c];
-}
-}  // namespace
-
 // the vectors of arbitrary rows (`index.vectors[rows]`: what the fitting loops read of the labelled tiles,
 // multi_reg.py:204, loops/util.py:6,11) out of the resident matrix -- for callers that do not hold a host copy of it
 // (a rank of the row-sharded index serves its own rows this way)
@@ -1049,19 +1028,14 @@ ssw_status ssw_index_gather_rows(ssw_index *idx, const int64_t *rows_host, int64
     SSW_TRY(stage_rows(idx, rows_host, n));
     float *buf = nullptr;
     SSW_HIP_TRY(hipMalloc((void **)&buf, (size_t)n * idx->dim * sizeof(float)));
-    if (idx->dtype == SSW_DTYPE_F16) {  // widened, natural element order
-        const ssw_status st = launch_rows_from_h16(Xh(idx), idx->gather_idx, 0, n, idx->dim, buf, idx->stream);
-        if (st != SSW_OK) {
-            (void)hipFree(buf);
-            return st;
-        }
-    } else {
-        hipLaunchKernelGGL(k_gather_rows_f32, dim3((unsigned)n), dim3(128), 0, idx->stream, idx->X, idx->gather_idx, n,
-                           (int)idx->dim, buf);
+    // f16 rows come back widened, in natural element order
+    const ssw_status st = launch_gather_rows(idx->X, idx->dtype, idx->gather_idx, 0, n, idx->dim, buf, idx->stream);
+    if (st != SSW_OK) {
+        (void)hipFree(buf);
+        return st;
     }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(out_host, buf, (size_t)n * idx->dim * sizeof(float), hipMemcpyDeviceToHost, idx->stream);
+    hipError_t e =
+        hipMemcpyAsync(out_host, buf, (size_t)n * idx->dim * sizeof(float), hipMemcpyDeviceToHost, idx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(idx->stream);
     (void)hipFree(buf);
     if (e != hipSuccess) {
@@ -1118,7 +1092,6 @@ ssw_status ssw_tune_topk(int32_t flags) {
 
 ssw_status ssw_tune_scan(int32_t variant, int32_t blocks_per_cu) {
     tune_scan(variant, blocks_per_cu);
-    tune_scan_h16(variant, blocks_per_cu);
     return SSW_OK;
 }
 #endif

@@ -43,40 +43,6 @@ constexpr int FB_SLAB = 32;          // rows per fb_grad workgroup
 constexpr int FB_MAX_PAIRWISE = 4096;  // items the one-workgroup pairwise kernel takes
 
 // ---- data preparation ---------------------------------------------------------------
-__global__ void k_fb_gather_rows(const float *__restrict__ X, const int64_t *__restrict__ rows,
-                                 int64_t n, int dim, float *__restrict__ out) {
-    const int64_t i = blockIdx.x;
-    const float4 *src = reinterpret_cast<const float4 *>(X + rows[i] * dim);
-    float4 *dst = reinterpret_cast<float4 *>(out + i * dim);
-    for (int c = threadIdx.x; c < dim / 4; c += blockDim.x) dst[c] = src[c];
-}
-
-// the same out of an f16 index (lane-interleaved binary16 rows, ssw_common.h): widened, natural element order
-typedef unsigned fb_u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 fb_h16x4 __attribute__((ext_vector_type(4)));
-typedef float fb_f32x4 __attribute__((ext_vector_type(4)));
-__global__ void k_fb_gather_rows_h16(const uint16_t *__restrict__ X, const int64_t *__restrict__ rows,
-                                     int64_t n, int dim, float *__restrict__ out) {
-    const int64_t i = blockIdx.x;
-    const uint16_t *src = X + rows[i] * dim;
-    float4 *dst = reinterpret_cast<float4 *>(out + i * dim);
-    for (int c = threadIdx.x; c < dim / 4; c += blockDim.x) {
-        const fb_u32x2 w = *reinterpret_cast<const fb_u32x2 *>(src + h16_group_pos(4 * c, dim >> 8));
-        const fb_f32x4 f = __builtin_convertvector(__builtin_bit_cast(fb_h16x4, w), fb_f32x4);
-        dst[c] = make_float4(f.x, f.y, f.z, f.w);
-    }
-}
-
-// rows[0, n) of the matrix (f32 or f16 index layout) -> fb->X
-void fb_gather(const void *X, bool h16, const int64_t *rows, int64_t n, int dim, float *out, hipStream_t s) {
-    if (h16)
-        hipLaunchKernelGGL(k_fb_gather_rows_h16, dim3((unsigned)n), dim3(128), 0, s, static_cast<const uint16_t *>(X), rows,
-                           n, dim, out);
-    else
-        hipLaunchKernelGGL(k_fb_gather_rows, dim3((unsigned)n), dim3(128), 0, s, static_cast<const float *>(X), rows, n,
-                           dim, out);
-}
-
 // column means in f64 (fixed order), then subtract: StandardScaler(with_std=False) /
 // `X - X.mean(axis=0)` (logistic_regression.py:353-355, multi_reg.py:168-169).  Three small launches: per-column sums
 // of 256-row blocks, the block sums added in block order, the subtraction over all elements.  (One thread walking a
@@ -2488,7 +2454,7 @@ ssw_status ssw_fb_set_data(ssw_fb *fb, const float *X_host, int64_t n, int32_t c
     return SSW_OK;
 }
 
-static ssw_status fb_set_data_gathered(ssw_fb *fb, const void *dev_matrix, bool h16, int64_t n_matrix_rows,
+static ssw_status fb_set_data_gathered(ssw_fb *fb, const void *dev_matrix, int32_t dtype, int64_t n_matrix_rows,
                                        const int64_t *rows_host, int64_t n, int32_t center) {
     SSW_REQUIRE(fb != nullptr && dev_matrix != nullptr && n >= 0 && (n == 0 || rows_host != nullptr), "bad argument");
     for (int64_t i = 0; i < n; ++i)
@@ -2501,8 +2467,7 @@ static ssw_status fb_set_data_gathered(ssw_fb *fb, const void *dev_matrix, bool 
     fb->targets_on_device = false;
     if (n > 0) {
         SSW_TRY(fb->rows_stage.push(fb->rows, rows_host, (size_t)n * sizeof(int64_t), fb->stream));
-        fb_gather(dev_matrix, h16, fb->rows, n, fb->dim, fb->X, fb->stream);
-        SSW_HIP_TRY(hipGetLastError());
+        SSW_TRY(launch_gather_rows(dev_matrix, dtype, fb->rows, 0, n, fb->dim, fb->X, fb->stream));
     }
     SSW_TRY(fb_center(fb, center));
     return SSW_OK;  // no wait: every consumer (the fit, lossgrad, get_mean, scores) is ordered behind this on the stream
@@ -2510,15 +2475,16 @@ static ssw_status fb_set_data_gathered(ssw_fb *fb, const void *dev_matrix, bool 
 
 ssw_status ssw_fb_set_data_from_device(ssw_fb *fb, const float *dev_matrix, int64_t n_matrix_rows,
                                        const int64_t *rows_host, int64_t n, int32_t center) {
-    return fb_set_data_gathered(fb, dev_matrix, false, n_matrix_rows, rows_host, n, center);
+    return fb_set_data_gathered(fb, dev_matrix, SSW_DTYPE_F32, n_matrix_rows, rows_host, n, center);
 }
 
 // the matrix, its row count and element type out of an index handle whose dim must be the engine's
-static ssw_status fb_index_matrix(const ssw_fb *fb, const ssw_index *index, const void **X, int64_t *n_rows, bool *h16) {
+static ssw_status fb_index_matrix(const ssw_fb *fb, const ssw_index *index, const void **X, int64_t *n_rows,
+                                  int32_t *dtype) {
     SSW_REQUIRE(fb != nullptr && index != nullptr, "NULL argument");
     int32_t dim = 0;
     *X = index_matrix(index, n_rows, &dim);
-    *h16 = index_dtype(index) == SSW_DTYPE_F16;
+    *dtype = index_dtype(index);
     SSW_REQUIRE(dim == fb->dim, "the index has dim %d, the feedback engine %d", dim, fb->dim);
     return SSW_OK;
 }
@@ -2527,12 +2493,12 @@ ssw_status ssw_fb_set_data_from_index(ssw_fb *fb, const ssw_index *index, const 
                                       int32_t center) {
     const void *X = nullptr;
     int64_t n_rows = 0;
-    bool h16 = false;
-    SSW_TRY(fb_index_matrix(fb, index, &X, &n_rows, &h16));
-    return fb_set_data_gathered(fb, X, h16, n_rows, rows_host, n, center);
+    int32_t dtype = SSW_DTYPE_F32;
+    SSW_TRY(fb_index_matrix(fb, index, &X, &n_rows, &dtype));
+    return fb_set_data_gathered(fb, X, dtype, n_rows, rows_host, n, center);
 }
 
-static ssw_status fb_set_pseudo_sample(ssw_fb *fb, const void *dev_matrix, bool h16, int64_t n_matrix_rows,
+static ssw_status fb_set_pseudo_sample(ssw_fb *fb, const void *dev_matrix, int32_t dtype, int64_t n_matrix_rows,
                                        const double *dev_scores, const int64_t *labelled_rows_sorted,
                                        const float *labelled_y, int64_t n_lab, const int64_t *drawn, int64_t n_drawn,
                                        float real_weight, int32_t center) {
@@ -2591,8 +2557,7 @@ static ssw_status fb_set_pseudo_sample(ssw_fb *fb, const void *dev_matrix, bool 
             hipLaunchKernelGGL(k_fb_pseudo_rows, dim3((unsigned)((n_drawn + 255) / 256)), dim3(256), 0, fb->stream, fb->th, (int)n_lab,
                                fb->drawn, n_drawn, dev_scores, n_matrix_rows, fb->rows, fb->y);
         }
-        fb_gather(dev_matrix, h16, fb->rows, n, fb->dim, fb->X, fb->stream);
-        SSW_HIP_TRY(hipGetLastError());
+        SSW_TRY(launch_gather_rows(dev_matrix, dtype, fb->rows, 0, n, fb->dim, fb->X, fb->stream));
     }
     SSW_TRY(fb_center(fb, center));
     return SSW_OK;  // no wait: the fit is ordered behind this on the stream
@@ -2601,8 +2566,8 @@ static ssw_status fb_set_pseudo_sample(ssw_fb *fb, const void *dev_matrix, bool 
 ssw_status ssw_fb_set_pseudo_sample(ssw_fb *fb, const float *dev_matrix, int64_t n_matrix_rows, const double *dev_scores,
                                     const int64_t *labelled_rows_sorted, const float *labelled_y, int64_t n_lab,
                                     const int64_t *drawn, int64_t n_drawn, float real_weight, int32_t center) {
-    return fb_set_pseudo_sample(fb, dev_matrix, false, n_matrix_rows, dev_scores, labelled_rows_sorted, labelled_y, n_lab,
-                                drawn, n_drawn, real_weight, center);
+    return fb_set_pseudo_sample(fb, dev_matrix, SSW_DTYPE_F32, n_matrix_rows, dev_scores, labelled_rows_sorted, labelled_y,
+                                n_lab, drawn, n_drawn, real_weight, center);
 }
 
 ssw_status ssw_fb_set_pseudo_sample_from_index(ssw_fb *fb, const ssw_index *index, const double *dev_scores,
@@ -2611,9 +2576,9 @@ ssw_status ssw_fb_set_pseudo_sample_from_index(ssw_fb *fb, const ssw_index *inde
                                                int32_t center) {
     const void *X = nullptr;
     int64_t n_rows = 0;
-    bool h16 = false;
-    SSW_TRY(fb_index_matrix(fb, index, &X, &n_rows, &h16));
-    return fb_set_pseudo_sample(fb, X, h16, n_rows, dev_scores, labelled_rows_sorted, labelled_y, n_lab, drawn, n_drawn,
+    int32_t dtype = SSW_DTYPE_F32;
+    SSW_TRY(fb_index_matrix(fb, index, &X, &n_rows, &dtype));
+    return fb_set_pseudo_sample(fb, X, dtype, n_rows, dev_scores, labelled_rows_sorted, labelled_y, n_lab, drawn, n_drawn,
                                 real_weight, center);
 }
 

@@ -34,13 +34,9 @@ __device__ __forceinline__ int synth_int(uint32_t rowkey, uint32_t col) {
     return (int)((h1 & 0xffffu) + (h1 >> 16) + (h2 & 0xffffu) + (h2 >> 16)) - 131070;
 }
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
 // one wave per row; lane l produces columns 256*c + 4*l .. +3 (the scan's load layout).  H: the f16 index -- the
 // same f32 values rounded to binary16 (nearest even), lane l's 8*C bytes contiguous (ssw_common.h, h16_group_pos)
-template <int C, bool H = false>
+template <int C, bool H>
 __global__ __launch_bounds__(256) void k_fill_random(void *__restrict__ Xv, int64_t n,
                                                      uint64_t seed, int64_t first_row) {
     const int lane = threadIdx.x & 63;
@@ -77,7 +73,7 @@ __global__ __launch_bounds__(256) void k_fill_random(void *__restrict__ Xv, int6
             o.z = (float)((double)xi[c * 4 + 2] / norm);
             o.w = (float)((double)xi[c * 4 + 3] / norm);
             if (degenerate && c == 0 && lane == 0) o.x = 1.0f;
-            if constexpr (H) dsth[c] = __builtin_bit_cast(u32x2, __builtin_convertvector((f32x4{o.x, o.y, o.z, o.w}), h16x4));
+            if constexpr (H) dsth[c] = round_h16x4(o);
             else dst[c * 64] = o;
         }
     }
@@ -85,45 +81,25 @@ __global__ __launch_bounds__(256) void k_fill_random(void *__restrict__ Xv, int6
 
 }  // namespace
 
-template <bool H>
-static ssw_status launch_fill_random_t(void *X, int64_t n, int32_t dim, uint64_t seed, int64_t first_row,
-                                       hipStream_t stream) {
+ssw_status launch_fill_random(void *X, int32_t dtype, int64_t n, int32_t dim, uint64_t seed, int64_t first_row,
+                              hipStream_t stream) {
     if (n <= 0) return SSW_OK;
     int64_t grid = (n + 3) / 4;
     if (grid > 256 * 8 * 4) grid = 256 * 8 * 4;
+    const bool h16 = dtype == SSW_DTYPE_F16;
+    void (*kernel)(void *, int64_t, uint64_t, int64_t);
     switch (dim) {
-        case 256:
-            hipLaunchKernelGGL((k_fill_random<1, H>), dim3((unsigned)grid), dim3(256), 0, stream, X, n,
-                               seed, first_row);
-            break;
-        case 512:
-            hipLaunchKernelGGL((k_fill_random<2, H>), dim3((unsigned)grid), dim3(256), 0, stream, X, n,
-                               seed, first_row);
-            break;
-        case 768:
-            hipLaunchKernelGGL((k_fill_random<3, H>), dim3((unsigned)grid), dim3(256), 0, stream, X, n,
-                               seed, first_row);
-            break;
-        case 1024:
-            hipLaunchKernelGGL((k_fill_random<4, H>), dim3((unsigned)grid), dim3(256), 0, stream, X, n,
-                               seed, first_row);
-            break;
+        case 256: kernel = h16 ? k_fill_random<1, true> : k_fill_random<1, false>; break;
+        case 512: kernel = h16 ? k_fill_random<2, true> : k_fill_random<2, false>; break;
+        case 768: kernel = h16 ? k_fill_random<3, true> : k_fill_random<3, false>; break;
+        case 1024: kernel = h16 ? k_fill_random<4, true> : k_fill_random<4, false>; break;
         default:
             set_error("fill_random: dim=%d unsupported", dim);
             return SSW_ERR_UNSUPPORTED;
     }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), 0, stream, X, n, seed, first_row);
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
-}
-
-ssw_status launch_fill_random(float *X, int64_t n, int32_t dim, uint64_t seed, int64_t first_row,
-                              hipStream_t stream) {
-    return launch_fill_random_t<false>(X, n, dim, seed, first_row, stream);
-}
-
-ssw_status launch_fill_random_h16(uint16_t *X, int64_t n, int32_t dim, uint64_t seed, int64_t first_row,
-                                  hipStream_t stream) {
-    return launch_fill_random_t<true>(X, n, dim, seed, first_row, stream);
 }
 
 }  // namespace ssw

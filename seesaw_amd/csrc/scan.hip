@@ -36,6 +36,13 @@
 //   oracle/ssw_oracle.c::ssw_oracle_scores_kernel_order restates exactly this order,
 //   which makes the scores BIT-EXACT against the CPU oracle, not merely close.
 //
+// The f16 index (SSW_DTYPE_F16) runs the same kernels with another row format (H16Rows below): binary16 rows in the
+// lane-interleaved layout of ssw_common.h (h16_group_pos), where lane l's 4*C elements are 8*C contiguous bytes -- one
+// 16-byte load per lane per row at dim 512.  A fragment stays packed while it is in flight and is widened exactly
+// (v_cvt_f32_f16; the code object keeps f16 denormals) into the float4s the f32 kernel would have loaded for the
+// widened row right before dot_frag, so the scores are the BITS of the f32 scan over X.astype(float16).astype(float32).
+// A row is dim*2 bytes, so a group takes twice the rows of the f32 schedule: the same bytes in flight per wave.
+//
 // Grid: persistent, (#CUs x resident blocks per CU) blocks of 256 threads; waves
 // stride over the batches.
 #include <cstdlib>
@@ -51,24 +58,85 @@ struct RowFrag {
     float4 v[C];
 };
 
+// ---- row formats: how a lane's part of a row is stored and loaded, and how it becomes the RowFrag dot_frag reads.
 // NT: non-temporal loads (`global_load_dwordx4 ... nt`): the index is streamed once per query
 // and is far larger than L2 / Infinity Cache, so it should not displace anything.
-template <int C, bool NT = false>
-__device__ __forceinline__ RowFrag<C> load_row(const float4 *__restrict__ X4, int row, int lane) {
-    RowFrag<C> r;
-    const float4 *p = X4 + (int64_t)row * (C * 64) + lane;
+
+// f32 rows in natural order: chunk c of lane l is the float4 at element 256*c + 4*l, used as loaded
+struct F32Rows {
+    typedef float T;
+    template <int C>
+    using Frag = RowFrag<C>;
+
+    template <int C, bool NT>
+    static __device__ __forceinline__ RowFrag<C> load(const float *__restrict__ X, int row, int lane) {
+        RowFrag<C> r;
+        const float4 *p = reinterpret_cast<const float4 *>(X) + (int64_t)row * (C * 64) + lane;
 #pragma unroll
-    for (int c = 0; c < C; ++c) {
-        if (NT) {
-            typedef float f32x4_t __attribute__((ext_vector_type(4)));
-            const f32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t *>(p + c * 64));
-            r.v[c] = make_float4(v.x, v.y, v.z, v.w);
-        } else {
-            r.v[c] = p[c * 64];
+        for (int c = 0; c < C; ++c) {
+            if (NT) {
+                const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(p + c * 64));
+                r.v[c] = make_float4(v.x, v.y, v.z, v.w);
+            } else {
+                r.v[c] = p[c * 64];
+            }
         }
+        return r;
     }
-    return r;
-}
+    template <int C>
+    static __device__ __forceinline__ const RowFrag<C> &widen(const RowFrag<C> &f) { return f; }
+    // the 4 elements from natural element e of a row
+    static __device__ __forceinline__ float4 group4(const float *row, int e, int dim) {
+        return reinterpret_cast<const float4 *>(row)[e >> 2];
+    }
+};
+
+// binary16 rows in the f16 index's lane-interleaved layout: lane l's 4*C elements are its 8*C contiguous bytes
+template <int C>
+struct HalfFrag {
+    u32x2 w[C];  // chunk c = elements 256*c + 4*l .. +3
+};
+
+struct H16Rows {
+    typedef uint16_t T;
+    template <int C>
+    using Frag = HalfFrag<C>;
+
+    template <int C, bool NT>
+    static __device__ __forceinline__ HalfFrag<C> load(const uint16_t *__restrict__ X, int row, int lane) {
+        HalfFrag<C> r;
+        const unsigned char *p = reinterpret_cast<const unsigned char *>(X) + (int64_t)row * (C * 512) + lane * (C * 8);
+        if constexpr (C % 2 == 0) {  // 16-byte aligned: one dwordx4 per two chunks (dim 512: one per lane per row)
+            const u32x4 *p4 = reinterpret_cast<const u32x4 *>(p);
+#pragma unroll
+            for (int i = 0; i < C / 2; ++i) {
+                u32x4 v;
+                if constexpr (NT) v = __builtin_nontemporal_load(p4 + i);
+                else v = p4[i];
+                r.w[2 * i] = u32x2{v.x, v.y};
+                r.w[2 * i + 1] = u32x2{v.z, v.w};
+            }
+        } else {
+            const u32x2 *p2 = reinterpret_cast<const u32x2 *>(p);
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                if constexpr (NT) r.w[c] = __builtin_nontemporal_load(p2 + c);
+                else r.w[c] = p2[c];
+            }
+        }
+        return r;
+    }
+    template <int C>
+    static __device__ __forceinline__ RowFrag<C> widen(const HalfFrag<C> &f) {
+        RowFrag<C> r;
+#pragma unroll
+        for (int c = 0; c < C; ++c) r.v[c] = widen_h16x4(f.w[c]);
+        return r;
+    }
+    static __device__ __forceinline__ float4 group4(const uint16_t *row, int e, int dim) {
+        return widen_h16x4(*reinterpret_cast<const u32x2 *>(row + h16_group_pos(e, dim >> 8)));
+    }
+};
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -106,20 +174,20 @@ __device__ __forceinline__ float group_reduce(float (&acc)[U], int lane) {
     return v;
 }
 
-template <int C, int U>
+template <class R, int C, int U>
 struct Group {
-    RowFrag<C> r[U];
+    typename R::template Frag<C> r[U];
 };
 
-template <int C, int U, bool NT>
-__device__ __forceinline__ void load_group(Group<C, U> &g, const float4 *__restrict__ X4,
+template <class R, int C, int U, bool NT>
+__device__ __forceinline__ void load_group(Group<R, C, U> &g, const typename R::T *__restrict__ X,
                                            int first_row, int last, int lane) {
 #pragma unroll
-    for (int u = 0; u < U; ++u) g.r[u] = load_row<C, NT>(X4, min(first_row + u, last), lane);
+    for (int u = 0; u < U; ++u) g.r[u] = R::template load<C, NT>(X, min(first_row + u, last), lane);
 }
 
-template <int C, int U, bool NT>
-__global__ __launch_bounds__(256) void scan_scores_kernel(const float *__restrict__ X,
+template <class R, int C, int U, bool NT>
+__global__ __launch_bounds__(256) void scan_scores_kernel(const typename R::T *__restrict__ X,
                                                          const float *__restrict__ q,
                                                          float *__restrict__ scores, int n) {
     constexpr int GPB = 64 / U;  // groups per batch
@@ -130,7 +198,6 @@ __global__ __launch_bounds__(256) void scan_scores_kernel(const float *__restric
     const int nwaves = gridDim.x * 4;
     const int nbatches = (n + 63) >> 6;
     const int last = n - 1;
-    const float4 *X4 = reinterpret_cast<const float4 *>(X);
     if (gwave >= nbatches) return;
 
     RowFrag<C> qf;
@@ -138,8 +205,8 @@ __global__ __launch_bounds__(256) void scan_scores_kernel(const float *__restric
     for (int c = 0; c < C; ++c) qf.v[c] = reinterpret_cast<const float4 *>(q)[c * 64 + lane];
 
     const int my_group = lane / U;
-    Group<C, U> cur, nxt;
-    load_group<C, U, NT>(cur, X4, gwave << 6, last, lane);
+    Group<R, C, U> cur, nxt;
+    load_group<R, C, U, NT>(cur, X, gwave << 6, last, lane);
     for (int b = gwave; b < nbatches; b += nwaves) {
         const int row0 = b << 6;
         const int nb = b + nwaves;
@@ -149,11 +216,11 @@ __global__ __launch_bounds__(256) void scan_scores_kernel(const float *__restric
         for (int g = 0; g < GPB; ++g) {
             // request group g+1 (or the first group of this wave's next batch) ...
             const int nrow = (g + 1 < GPB) ? row0 + (g + 1) * U : next0;
-            load_group<C, U, NT>(nxt, X4, nrow, last, lane);
+            load_group<R, C, U, NT>(nxt, X, nrow, last, lane);
             // ... then finish group g
             float acc[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) acc[u] = dot_frag<C>(cur.r[u], qf);
+            for (int u = 0; u < U; ++u) acc[u] = dot_frag<C>(R::widen(cur.r[u]), qf);
             const float v = group_reduce<U>(acc, lane);
             out = (my_group == g) ? v : out;
             cur = nxt;
@@ -169,17 +236,16 @@ __global__ __launch_bounds__(256) void scan_scores_kernel(const float *__restric
 // flight at once), four waves a workgroup: 32 rows per workgroup, 451 workgroups for the LVIS subset.  The query comes
 // through LDS (one wave's read per workgroup, from L2).  Same dot_frag / group_reduce order: identical bits.  Plain
 // loads: an index this size stays in the Infinity Cache between rounds.
-template <int C, int U>
-__global__ __launch_bounds__(256) void scan_small_kernel(const float *__restrict__ X, const float *__restrict__ q,
+template <class R, int C, int U>
+__global__ __launch_bounds__(256) void scan_small_kernel(const typename R::T *__restrict__ X, const float *__restrict__ q,
                                                          float *__restrict__ scores, int n, int steps) {
     __shared__ float4 ql[C * 64];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int last = n - 1;
-    const float4 *X4 = reinterpret_cast<const float4 *>(X);
     const int row_base = (blockIdx.x * 4 + wave) * U * steps;
-    Group<C, U> cur, nxt;
-    load_group<C, U, false>(cur, X4, row_base, last, lane);
+    Group<R, C, U> cur, nxt;
+    load_group<R, C, U, false>(cur, X, row_base, last, lane);
     for (int i = threadIdx.x; i < C * 64; i += 256) ql[i] = reinterpret_cast<const float4 *>(q)[i];
     __syncthreads();
     RowFrag<C> qf;
@@ -188,10 +254,10 @@ __global__ __launch_bounds__(256) void scan_small_kernel(const float *__restrict
     for (int g = 0; g < steps; ++g) {
         const int row0 = row_base + g * U;
         if (row0 >= n) break;
-        if (g + 1 < steps) load_group<C, U, false>(nxt, X4, row0 + U, last, lane);
+        if (g + 1 < steps) load_group<R, C, U, false>(nxt, X, row0 + U, last, lane);
         float acc[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) acc[u] = dot_frag<C>(cur.r[u], qf);
+        for (int u = 0; u < U; ++u) acc[u] = dot_frag<C>(R::widen(cur.r[u]), qf);
         const float v = group_reduce<U>(acc, lane);
         if (lane < U && row0 + lane < n) scores[row0 + lane] = v;
         cur = nxt;
@@ -201,19 +267,18 @@ __global__ __launch_bounds__(256) void scan_small_kernel(const float *__restrict
 // scores of an explicit list of rows, same summation order as the full scan (one wave per
 // row, plain butterfly) -- stage-2 rescoring against a second vector
 // (multiscale_index.py:347-349).
-template <int C>
-__global__ __launch_bounds__(256) void score_rows_kernel(const float *__restrict__ X,
+template <class R, int C>
+__global__ __launch_bounds__(256) void score_rows_kernel(const typename R::T *__restrict__ X,
                                                         const float *__restrict__ q,
                                                         const int64_t *__restrict__ rows, int64_t n,
                                                         float *__restrict__ out) {
     const int lane = threadIdx.x & 63;
     const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (w >= n) return;
-    const float4 *X4 = reinterpret_cast<const float4 *>(X);
     RowFrag<C> qf;
 #pragma unroll
     for (int c = 0; c < C; ++c) qf.v[c] = reinterpret_cast<const float4 *>(q)[c * 64 + lane];
-    const RowFrag<C> x = load_row<C, false>(X4, (int)rows[w], lane);
+    const RowFrag<C> x = R::widen(R::template load<C, false>(X, (int)rows[w], lane));
     float v = dot_frag<C>(x, qf);
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) v = v + __shfl_xor(v, off, 64);
@@ -236,17 +301,16 @@ __global__ __launch_bounds__(256) void knn_rescore_kernel(const float *__restric
     const int lane = threadIdx.x & 63;
     const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (w >= rows) return;
-    const float4 *X4 = reinterpret_cast<const float4 *>(X);
     const int orig_i = perm[r0 + w];
     const int c = min((int)cnt[w], M);
     const uint64_t key = lane < c ? buf[(int64_t)w * cap + lane] : 0ull;
     const int orig_c = lane < c ? perm[0xFFFFFFFFu - (uint32_t)key] : -1;
     const float approx = ord_to_f32((uint32_t)(key >> 32));  // fp16-path score (scaled)
-    const RowFrag<C> xi = load_row<C, false>(X4, orig_i, lane);
+    const RowFrag<C> xi = F32Rows::load<C, false>(X, orig_i, lane);
     float mine = -INFINITY;
     for (int t = 0; t < c; ++t) {
         const int j = __shfl(orig_c, t, 64);
-        const RowFrag<C> xj = load_row<C, false>(X4, j, lane);
+        const RowFrag<C> xj = F32Rows::load<C, false>(X, j, lane);
         float v = dot_frag<C>(xj, xi);
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) v = v + __shfl_xor(v, off, 64);
@@ -287,17 +351,18 @@ __global__ __launch_bounds__(256) void knn_rescore_kernel(const float *__restric
 // 6.17 TB/s; 1 M rows: 6.66 vs 5.65 TB/s.  All variants produce identical bits.
 constexpr int64_t SCAN_SMALL_ROWS = 65536;  // below: the streaming kernel has under one 4-wave workgroup per CU
 SSW_TUNABLE bool g_scan_small = true;       // tuning hook (ssw_tune_scan variant -2: streaming kernel at every size)
-SSW_TUNABLE int g_scan_variant = -1;        // tuning hook (ssw_tune_scan): -1 = default (u2 + nt)
+SSW_TUNABLE int g_scan_variant = -1;        // tuning hook (ssw_tune_scan): -1 = default (u2 + nt; f16: u4 + nt)
 SSW_TUNABLE int g_scan_blocks_per_cu = -1;  // -1 = default (1 per CU for dim 512), 0 = as many as fit
 
-template <int C, int U, bool NT>
-ssw_status launch_scan_t(const float *X, const float *q, float *scores, int64_t n, int device,
+template <class R, int C, int U, bool NT>
+ssw_status launch_scan_t(const void *Xv, const float *q, float *scores, int64_t n, int device,
                          hipStream_t stream) {
+    const typename R::T *X = static_cast<const typename R::T *>(Xv);
     static int max_blocks_per_cu[16] = {0};
     int dev_slot = device & 15;
     if (max_blocks_per_cu[dev_slot] == 0) {
         int nb = 0;
-        SSW_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, scan_scores_kernel<C, U, NT>,
+        SSW_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, scan_scores_kernel<R, C, U, NT>,
                                                                  256, 0));
         if (nb < 1) nb = 1;
         if (nb > 8) nb = 8;
@@ -316,8 +381,8 @@ ssw_status launch_scan_t(const float *X, const float *q, float *scores, int64_t 
         const int64_t per_step = 4 * SU;  // rows a workgroup takes per step
         const int steps = (int)((n + 4096 * per_step - 1) / (4096 * per_step));  // 1 below 131 072 rows
         const int64_t sgrid = (n + per_step * steps - 1) / (per_step * steps);
-        hipLaunchKernelGGL((scan_small_kernel<C, SU>), dim3((unsigned)sgrid), dim3(256), 0, stream, X, q, scores, (int)n,
-                           steps);
+        hipLaunchKernelGGL((scan_small_kernel<R, C, SU>), dim3((unsigned)sgrid), dim3(256), 0, stream, X, q, scores,
+                           (int)n, steps);
         SSW_HIP_TRY(hipGetLastError());
         return SSW_OK;
     }
@@ -326,53 +391,75 @@ ssw_status launch_scan_t(const float *X, const float *q, float *scores, int64_t 
     const int64_t need = (nbatches + 3) / 4;
     if (grid > need) grid = need;
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL((scan_scores_kernel<C, U, NT>), dim3((unsigned)grid), dim3(256), 0, stream, X,
+    hipLaunchKernelGGL((scan_scores_kernel<R, C, U, NT>), dim3((unsigned)grid), dim3(256), 0, stream, X,
                        q, scores, (int)n);
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
 }
 
-}  // namespace
-
-ssw_status launch_scan(const float *X, const float *q_dev, float *scores, int64_t n, int32_t dim,
-                       int device, hipStream_t stream) {
-    if (n <= 0) return SSW_OK;
-    switch (dim) {
-        case 256: return launch_scan_t<1, 8, true>(X, q_dev, scores, n, device, stream);
-        case 512: {
-            // variants differ in schedule only (rows per group, load policy); numerics are identical
-            switch (g_scan_variant) {
-                case 0: return launch_scan_t<2, 4, false>(X, q_dev, scores, n, device, stream);
-                case 2: return launch_scan_t<2, 8, false>(X, q_dev, scores, n, device, stream);
-                case 3: return launch_scan_t<2, 8, true>(X, q_dev, scores, n, device, stream);
-                case 4: return launch_scan_t<2, 2, true>(X, q_dev, scores, n, device, stream);
-                case 1: return launch_scan_t<2, 4, true>(X, q_dev, scores, n, device, stream);
-                default: return launch_scan_t<2, 2, true>(X, q_dev, scores, n, device, stream);
-            }
-        }
-        case 768: return launch_scan_t<3, 2, true>(X, q_dev, scores, n, device, stream);
-        case 1024: return launch_scan_t<4, 2, true>(X, q_dev, scores, n, device, stream);
-        default:
-            set_error("scan: dim=%d unsupported (need a multiple of 256, <= 1024)", dim);
-            return SSW_ERR_UNSUPPORTED;
-    }
-}
-
-ssw_status launch_score_rows(const float *X, const float *q_dev, const int64_t *rows_dev, int64_t n,
-                             int32_t dim, float *out, hipStream_t stream) {
-    if (n <= 0) return SSW_OK;
+template <class R>
+ssw_status launch_score_rows_t(const void *Xv, const float *q_dev, const int64_t *rows_dev, int64_t n, int32_t dim,
+                               float *out, hipStream_t stream) {
+    const typename R::T *X = static_cast<const typename R::T *>(Xv);
     const dim3 grid((unsigned)((n + 3) / 4)), block(256);
     switch (dim) {
-        case 256: hipLaunchKernelGGL(score_rows_kernel<1>, grid, block, 0, stream, X, q_dev, rows_dev, n, out); break;
-        case 512: hipLaunchKernelGGL(score_rows_kernel<2>, grid, block, 0, stream, X, q_dev, rows_dev, n, out); break;
-        case 768: hipLaunchKernelGGL(score_rows_kernel<3>, grid, block, 0, stream, X, q_dev, rows_dev, n, out); break;
-        case 1024: hipLaunchKernelGGL(score_rows_kernel<4>, grid, block, 0, stream, X, q_dev, rows_dev, n, out); break;
+        case 256: hipLaunchKernelGGL((score_rows_kernel<R, 1>), grid, block, 0, stream, X, q_dev, rows_dev, n, out); break;
+        case 512: hipLaunchKernelGGL((score_rows_kernel<R, 2>), grid, block, 0, stream, X, q_dev, rows_dev, n, out); break;
+        case 768: hipLaunchKernelGGL((score_rows_kernel<R, 3>), grid, block, 0, stream, X, q_dev, rows_dev, n, out); break;
+        case 1024: hipLaunchKernelGGL((score_rows_kernel<R, 4>), grid, block, 0, stream, X, q_dev, rows_dev, n, out); break;
         default:
             set_error("score_rows: dim=%d unsupported", dim);
             return SSW_ERR_UNSUPPORTED;
     }
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
+}
+
+}  // namespace
+
+// Variants differ in schedule only (rows per group, load policy); numerics are identical.  A binary16 row is half the
+// bytes of an f32 row, so the f16 schedule takes twice the rows per group (one 4-wave block per CU at dim 512 for both).
+ssw_status launch_scan(const void *X, int32_t dtype, const float *q_dev, float *scores, int64_t n, int32_t dim,
+                       int device, hipStream_t stream) {
+    if (n <= 0) return SSW_OK;
+    if (dtype == SSW_DTYPE_F16) {
+        switch (dim) {
+            case 256: return launch_scan_t<H16Rows, 1, 16, true>(X, q_dev, scores, n, device, stream);
+            case 512:
+                switch (g_scan_variant) {
+                    case 0: return launch_scan_t<H16Rows, 2, 4, false>(X, q_dev, scores, n, device, stream);
+                    case 1: return launch_scan_t<H16Rows, 2, 8, true>(X, q_dev, scores, n, device, stream);
+                    case 4: return launch_scan_t<H16Rows, 2, 2, true>(X, q_dev, scores, n, device, stream);
+                    default: return launch_scan_t<H16Rows, 2, 4, true>(X, q_dev, scores, n, device, stream);
+                }
+            case 768: return launch_scan_t<H16Rows, 3, 4, true>(X, q_dev, scores, n, device, stream);
+            case 1024: return launch_scan_t<H16Rows, 4, 4, true>(X, q_dev, scores, n, device, stream);
+        }
+    } else {
+        switch (dim) {
+            case 256: return launch_scan_t<F32Rows, 1, 8, true>(X, q_dev, scores, n, device, stream);
+            case 512:
+                switch (g_scan_variant) {
+                    case 0: return launch_scan_t<F32Rows, 2, 4, false>(X, q_dev, scores, n, device, stream);
+                    case 2: return launch_scan_t<F32Rows, 2, 8, false>(X, q_dev, scores, n, device, stream);
+                    case 3: return launch_scan_t<F32Rows, 2, 8, true>(X, q_dev, scores, n, device, stream);
+                    case 4: return launch_scan_t<F32Rows, 2, 2, true>(X, q_dev, scores, n, device, stream);
+                    case 1: return launch_scan_t<F32Rows, 2, 4, true>(X, q_dev, scores, n, device, stream);
+                    default: return launch_scan_t<F32Rows, 2, 2, true>(X, q_dev, scores, n, device, stream);
+                }
+            case 768: return launch_scan_t<F32Rows, 3, 2, true>(X, q_dev, scores, n, device, stream);
+            case 1024: return launch_scan_t<F32Rows, 4, 2, true>(X, q_dev, scores, n, device, stream);
+        }
+    }
+    set_error("scan: dim=%d unsupported (need a multiple of 256, <= 1024)", dim);
+    return SSW_ERR_UNSUPPORTED;
+}
+
+ssw_status launch_score_rows(const void *X, int32_t dtype, const float *q_dev, const int64_t *rows_dev, int64_t n,
+                             int32_t dim, float *out, hipStream_t stream) {
+    if (n <= 0) return SSW_OK;
+    if (dtype == SSW_DTYPE_F16) return launch_score_rows_t<H16Rows>(X, q_dev, rows_dev, n, dim, out, stream);
+    return launch_score_rows_t<F32Rows>(X, q_dev, rows_dev, n, dim, out, stream);
 }
 
 ssw_status launch_knn_rescore(const float *X, int32_t dim, const int32_t *perm, int r0, int rows, const uint64_t *buf,
@@ -395,6 +482,64 @@ ssw_status launch_knn_rescore(const float *X, int32_t dim, const int32_t *perm, 
             return SSW_ERR_UNSUPPORTED;
     }
 #undef SSW_KNN_RESCORE
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+// ---- moving rows between natural-order f32 and the index (upload, download, gather) --------------------------------
+namespace {
+// one thread per 4-element group of a row (8 bytes of binary16, one float4)
+template <bool FROM_F32>
+__global__ __launch_bounds__(256) void k_rows_to_h16(const float *__restrict__ src_f32,
+                                                     const uint16_t *__restrict__ src_h16, int64_t n, int dim,
+                                                     uint16_t *__restrict__ dst) {
+    const int groups = dim >> 2;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n * groups) return;
+    const int64_t r = t / groups;
+    const int e = (int)(t - r * groups) << 2;
+    u32x2 w;
+    if constexpr (FROM_F32) w = round_h16x4(reinterpret_cast<const float4 *>(src_f32 + r * dim)[e >> 2]);
+    else w = reinterpret_cast<const u32x2 *>(src_h16 + r * dim)[e >> 2];
+    *reinterpret_cast<u32x2 *>(dst + r * dim + h16_group_pos(e, dim >> 8)) = w;
+}
+
+// one 128-thread block per row, one thread per 4-element group
+template <class R>
+__global__ void k_gather_rows(const typename R::T *__restrict__ X, const int64_t *__restrict__ rows, int64_t first_row,
+                              int dim, float *__restrict__ out) {
+    const int64_t i = blockIdx.x;
+    const typename R::T *src = X + (rows ? rows[i] : first_row + i) * dim;
+    float4 *dst = reinterpret_cast<float4 *>(out + i * dim);
+    for (int c = threadIdx.x; c < dim / 4; c += blockDim.x) dst[c] = R::group4(src, 4 * c, dim);
+}
+}  // namespace
+
+ssw_status launch_rows_to_h16(const float *src_f32, const uint16_t *src_h16, int64_t n, int32_t dim, uint16_t *dst,
+                              hipStream_t stream) {
+    if (n <= 0) return SSW_OK;
+    if (dim <= 0 || dim % 256 != 0 || dim > 1024) {
+        set_error("rows_to_h16: dim=%d unsupported", dim);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    const int64_t blocks = (n * (dim / 4) + 255) / 256;
+    if (src_f32)
+        hipLaunchKernelGGL(k_rows_to_h16<true>, dim3((unsigned)blocks), dim3(256), 0, stream, src_f32, nullptr, n, (int)dim, dst);
+    else
+        hipLaunchKernelGGL(k_rows_to_h16<false>, dim3((unsigned)blocks), dim3(256), 0, stream, nullptr, src_h16, n, (int)dim, dst);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+ssw_status launch_gather_rows(const void *X, int32_t dtype, const int64_t *rows_or_null, int64_t first_row, int64_t n,
+                              int32_t dim, float *out, hipStream_t stream) {
+    if (n <= 0) return SSW_OK;
+    if (dtype == SSW_DTYPE_F16)
+        hipLaunchKernelGGL(k_gather_rows<H16Rows>, dim3((unsigned)n), dim3(128), 0, stream,
+                           static_cast<const uint16_t *>(X), rows_or_null, first_row, (int)dim, out);
+    else
+        hipLaunchKernelGGL(k_gather_rows<F32Rows>, dim3((unsigned)n), dim3(128), 0, stream,
+                           static_cast<const float *>(X), rows_or_null, first_row, (int)dim, out);
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
 }

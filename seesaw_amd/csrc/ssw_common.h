@@ -138,28 +138,36 @@ const void *index_matrix(const ssw_index *idx, int64_t *n_rows, int32_t *dim);
 // byte 8*c inside them.  A row stays dim*2 contiguous bytes; at dim 512 a lane reads its part with one 16-byte load.
 // Position (in elements) of the 4-element group that starts at natural element e (e % 4 == 0) of a row:
 __host__ __device__ inline int h16_group_pos(int e, int C) { return ((e & 255) >> 2) * 4 * C + (e >> 8) * 4; }
+// A 4-element group of binary16 is one u32x2.  Widening is exact (v_cvt_f32_f16; the code objects keep f16 denormals,
+// .amdhsa_float_denorm_mode_16_64 3); rounding is to nearest even with subnormals kept and overflow to +-inf
+// (v_cvt_f16_f32: numpy's astype(float16)).
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 widen_h16x4(u32x2 w) {
+    const f32x4 f = __builtin_convertvector(__builtin_bit_cast(h16x4, w), f32x4);
+    return make_float4(f.x, f.y, f.z, f.w);
+}
+__device__ __forceinline__ u32x2 round_h16x4(float4 v) {
+    return __builtin_bit_cast(u32x2, __builtin_convertvector((f32x4{v.x, v.y, v.z, v.w}), h16x4));
+}
 
-// scan.hip: scores[i] = dot(X[i,:], q) in the fixed kernel order (see scan.hip).
-ssw_status launch_scan(const float *X, const float *q_dev, float *scores, int64_t n, int32_t dim,
+// scan.hip: scores[i] = dot(X[i,:], q) in the fixed kernel order (see scan.hip), over an index matrix of element type
+// dtype (SSW_DTYPE_F32, or SSW_DTYPE_F16 in the layout above: the bits of the f32 kernels on the widened rows)
+ssw_status launch_scan(const void *X, int32_t dtype, const float *q_dev, float *scores, int64_t n, int32_t dim,
                        int device, hipStream_t stream);
-ssw_status launch_score_rows(const float *X, const float *q_dev, const int64_t *rows_dev, int64_t n,
+ssw_status launch_score_rows(const void *X, int32_t dtype, const float *q_dev, const int64_t *rows_dev, int64_t n,
                              int32_t dim, float *out, hipStream_t stream);
-// scan_f16.hip: the same over an f16 index (lane-interleaved rows, see above): the bits of the f32 kernels on the
-// widened rows
-ssw_status launch_scan_h16(const uint16_t *X, const float *q_dev, float *scores, int64_t n, int32_t dim,
-                           int device, hipStream_t stream);
-ssw_status launch_score_rows_h16(const uint16_t *X, const float *q_dev, const int64_t *rows_dev, int64_t n,
-                                 int32_t dim, float *out, hipStream_t stream);
-// natural-order rows <-> the f16 layout.  to_h16: n rows of natural-order f32 (src_f32) or binary16 (src_h16, the
-// other NULL) -> rows [0, n) of dst, rounded to nearest even.  to_f32: rows (rows_dev[i], or first_row + i when
-// rows_dev is NULL) of X -> n natural-order f32 rows of out.
+// rows between natural order and the index.  to_h16: n rows of natural-order f32 (src_f32) or binary16 (src_h16, the
+// other NULL) -> rows [0, n) of dst in the f16 layout, rounded to nearest even.  gather: rows (rows_or_null[i], or
+// first_row + i when it is NULL) of an index matrix of element type dtype -> n natural-order f32 rows of out.
 ssw_status launch_rows_to_h16(const float *src_f32, const uint16_t *src_h16, int64_t n, int32_t dim, uint16_t *dst,
                               hipStream_t stream);
-ssw_status launch_rows_from_h16(const uint16_t *X, const int64_t *rows_dev, int64_t first_row, int64_t n, int32_t dim,
-                                float *out, hipStream_t stream);
+ssw_status launch_gather_rows(const void *X, int32_t dtype, const int64_t *rows_or_null, int64_t first_row, int64_t n,
+                              int32_t dim, float *out, hipStream_t stream);
 #ifdef SSW_DEBUG_HOOKS
 void tune_scan(int variant, int blocks_per_cu);
-void tune_scan_h16(int variant, int blocks_per_cu);  // scan_f16.hip
 #endif
 // knn.hip's last stage (lives in scan.hip to share the scan's summation order)
 ssw_status launch_knn_rescore(const float *X, int32_t dim, const int32_t *perm, int r0, int rows, const uint64_t *buf,
@@ -222,12 +230,9 @@ ssw_status gemm_pw4_read_wg(unsigned long long *out);
 ssw_status launch_gemm_pw4(int epi, hipStream_t stream, const void *A, const void *W, const float *bias,
                            const float *residual, void *C, int M, int N, int K, int bn);
 #endif
-// rng.hip: synthetic unit-norm rows.
-ssw_status launch_fill_random(float *X, int64_t n, int32_t dim, uint64_t seed, int64_t first_row,
+// rng.hip: synthetic unit-norm rows (SSW_DTYPE_F16: the same values rounded to binary16, in the f16 index's layout)
+ssw_status launch_fill_random(void *X, int32_t dtype, int64_t n, int32_t dim, uint64_t seed, int64_t first_row,
                               hipStream_t stream);
-// the same values rounded to binary16, written in the f16 index's row layout
-ssw_status launch_fill_random_h16(uint16_t *X, int64_t n, int32_t dim, uint64_t seed, int64_t first_row,
-                                  hipStream_t stream);
 
 // side outputs / inputs of the selection's last kernel for the row-sharded exchange (select.hip, k_final)
 struct FinalExchange {
