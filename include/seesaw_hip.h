@@ -87,7 +87,9 @@ ssw_status ssw_index_set_stream(ssw_index *idx, void *hip_stream);
 ssw_status ssw_index_sync(ssw_index *idx);
 ssw_status ssw_index_shape(const ssw_index *idx, int64_t *n_rows, int32_t *dim, int64_t *n_images);
 /* device pointers of the resident matrix and of the score buffer ([n_rows] f32,
- * valid after the last scan). */
+ * valid after the last scan).  After a pruned top-k (ssw_index_prune_stats) this first completes the score buffer with
+ * the full scan of that query.  Handing out dev_vectors ends the index's int8 shadow for good: the caller may write
+ * the rows through it. */
 ssw_status ssw_index_device_ptrs(ssw_index *idx, void **dev_vectors, void **dev_scores);
 
 /* copy rows [first_row, first_row+n) from host memory into the index (an f16 index rounds them on the device,
@@ -227,6 +229,20 @@ ssw_status ssw_topk_allgather(ssw_comm *comm, void *hip_stream, const uint64_t *
  * the durations in milliseconds. */
 ssw_status ssw_index_profile(ssw_index *idx, int32_t enable);
 ssw_status ssw_index_profile_read(ssw_index *idx, float *out_ms, int32_t cap, int32_t *out_n);
+
+/* Pruned top-k.  ssw_index_topk / ssw_index_topk_dev with a query, on an f32 index of at least 2^22 rows that owns its
+ * matrix (dim 256, 512 or 1024), scan an int8 shadow of the rows (dim + 8 bytes a row, built on the first such call
+ * after the rows last changed, only if 4 GiB of device memory stay free beside it) for certified lower and upper bounds
+ * of every score, and rescore exactly only the rows whose upper bound reaches the k-th image's lower bound.  The result
+ * is the bits of the full scan; the call waits once on the host for the survivor count.  Whenever the certificate
+ * fails the full scan runs instead.  The score buffer then holds exact scores for the survivors only; every entry that
+ * reads it (topk with q = NULL, select_deep_dev, gather_scores, rescore_avg, device_ptrs, the labelprop top-k) first
+ * completes it with the full scan of the kept query, and upload / fill_random do so before they change the rows.
+ * An index that borrows a device matrix, an f16 index, and an index whose row pointer ssw_index_device_ptrs has handed
+ * out never get a shadow.  The environment variable SSW_TOPK_FULL_SCAN (read once) forces the full scan everywhere.
+ * out6: [0] shadow 0 none / 1 current / 2 stale / 3 refused (memory), [1] 1 = the next top-k with a query is pruned,
+ * [2] survivors of the last pruned call (-1 = it fell back), [3] pruned calls, [4] fallbacks, [5] shadow bytes. */
+ssw_status ssw_index_prune_stats(ssw_index *idx, int64_t *out6);
 
 /* ------------------------------------------------------------------------- */
 /* k-NN-graph label propagation                                               */

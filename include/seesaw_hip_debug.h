@@ -30,6 +30,12 @@ ssw_status ssw_tune_scan(int32_t variant, int32_t blocks_per_cu);
  * candidates raises the overflow word and the deep path runs).  Default 3; tests switch the forms off to compare. */
 ssw_status ssw_tune_topk(int32_t flags);
 
+/* The pruned top-k (seesaw_hip.h, ssw_index_prune_stats): enable 0 = every top-k scans in full (what
+ * SSW_TOPK_FULL_SCAN does), min_rows = the smallest index that is pruned, reserve_bytes = the free device memory a
+ * shadow must leave (-1 = default for either: 2^22 rows, 4 GiB).  Applies to the next top-k of every index; a shadow
+ * refused for memory is retried only after its rows change. */
+ssw_status ssw_tune_prune(int32_t enable, int64_t min_rows, int64_t reserve_bytes);
+
 /* Kernel A/B harness for the towers' bf16 GEMM (C[M,N] = A[M,K] W[N,K]^T + epilogue `epi`, see
  * csrc/gemm_bf16.hip): runs `variant` on seeded operands, reports ms per launch over `iters`
  * launches and the max |difference| to variant 0.  Not part of the reference's interface. */

@@ -142,6 +142,7 @@ _SIGNATURES = {
     "ssw_topk_allgather": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_i32]),
     "ssw_index_profile": (c_i32, [c_void_p, c_i32]),
     "ssw_index_profile_read": (c_i32, [c_void_p, c_void_p, c_i32, c_i32_p]),
+    "ssw_index_prune_stats": (c_i32, [c_void_p, c_i64_p]),
 }
 
 
@@ -149,6 +150,7 @@ _SIGNATURES = {
 _DEBUG_SIGNATURES = {
     "ssw_tune_scan": (c_i32, [c_i32, c_i32]),
     "ssw_tune_topk": (c_i32, [c_i32]),
+    "ssw_tune_prune": (c_i32, [c_i32, c_i64, c_i64]),
     "ssw_tune_gemm": (c_i32, [c_i32]),
     "ssw_debug_gemm": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_void_p, c_void_p]),
     "ssw_debug_gemm_pw4_mode": (c_i32, [c_i32, c_void_p]),

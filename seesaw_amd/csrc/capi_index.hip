@@ -111,6 +111,22 @@ struct ssw_index {
     float *rs_score = nullptr;     // [rs_cap]
     float *rs_minus = nullptr;     // [rs_minus_cap]
     int64_t rs_cap = 0, rs_minus_cap = 0;
+    // certified int8 pre-scan of the top-k (prune.hip): the shadow of the rows, built lazily by the first top-k with a
+    // query after the rows last changed.  Never for a borrowed matrix or once ssw_index_device_ptrs handed out the rows.
+    int8_t *q8 = nullptr;                            // [n, dim] codes
+    float *q8_scale = nullptr, *q8_err = nullptr;    // [n] s_r, a_r
+    bool q8_stale = true;                            // the rows changed since the shadow was built
+    bool q8_refused = false;                         // too little free memory at the last attempt (until the rows change)
+    bool rows_escaped = false;                       // the row pointer was handed out: never a shadow
+    unsigned *prune_state = nullptr;                 // [4] device words (ssw_common.h, launch_q8_query)
+    int64_t *surv_rows = nullptr;                    // [SURV_CAP]
+    float *surv_scores = nullptr;                    // [SURV_CAP]
+    int32_t *prune_host = nullptr;                   // pinned, mapped: [seq, survivors or -1]
+    unsigned prune_seq = 0;
+    hipEvent_t prune_ev = nullptr;                   // after the shadow scan: the host sleeps on it, then spins
+    float *q_last = nullptr;                         // [dim] the query of the last pruned scan
+    bool scores_partial = false;                     // scores hold exact values for the survivors only (materialise)
+    int64_t prune_last = 0, prune_queries = 0, prune_fallbacks = 0;
     // profiling of the scan kernel
     bool profiling = false;
     std::vector<hipEvent_t> ev;  // pairs
@@ -159,6 +175,7 @@ static ssw_status launch_index_scan(ssw_index *idx, const float *q_dev) {
 }
 
 static ssw_status do_scan(ssw_index *idx, const float *q_dev) {
+    idx->scores_partial = false;
     if (idx->profiling && idx->ev_used + 2 <= (int)idx->ev.size()) {
         SSW_HIP_TRY(hipEventRecord(idx->ev[idx->ev_used], idx->stream));
         SSW_TRY(launch_index_scan(idx, q_dev));
@@ -179,6 +196,52 @@ static ssw_status do_select(ssw_index *idx, int32_t k) {
     }
     return launch_select_topk(idx->ws, idx->scores, idx->n, nullptr, k, idx->device, idx->stream);
 }
+
+// ---- the certified pre-scan (prune.hip) -------------------------------------------------------
+// Top-k with a query on an index of at least PRUNE_MIN_ROWS f32 rows scans the int8 shadow instead of the rows and
+// rescores the survivors exactly; the score buffer then holds exact scores for the survivors and lower bounds elsewhere
+// (scores_partial) until a consumer that reads it materialises the full scan of the kept query.
+constexpr int64_t PRUNE_MIN_ROWS = (int64_t)1 << 22;  // above the feedback loop's 1.56 M rows, below a rank's 12.5 M
+constexpr int64_t PRUNE_RESERVE = (int64_t)4 << 30;   // free device memory the shadow must leave
+constexpr int64_t SURV_CAP = (int64_t)1 << 18;        // survivors rescored at most; more: the full scan
+static SSW_TUNABLE bool g_prune = true;               // ssw_tune_prune
+static SSW_TUNABLE int64_t g_prune_min_rows = PRUNE_MIN_ROWS;
+static SSW_TUNABLE int64_t g_prune_reserve = PRUNE_RESERVE;
+
+static bool prune_forced_off() {
+    static const bool v = getenv("SSW_TOPK_FULL_SCAN") != nullptr;  // A/B: every top-k runs the full f32 scan
+    return v;
+}
+
+static bool prune_eligible(const ssw_index *idx) {
+    return g_prune && !prune_forced_off() && idx->dtype == SSW_DTYPE_F32 && idx->owns_X && !idx->rows_escaped &&
+           idx->n >= g_prune_min_rows && idx->n_images > 0 && q8_dim_supported(idx->dim);
+}
+
+static void free_shadow(ssw_index *idx) {
+    (void)hipFree(idx->q8);
+    (void)hipFree(idx->q8_scale);
+    (void)hipFree(idx->q8_err);
+    idx->q8 = nullptr;
+    idx->q8_scale = idx->q8_err = nullptr;
+    idx->q8_stale = true;
+}
+
+static ssw_status ensure_full_scores(ssw_index *idx) {
+    if (!idx->scores_partial) return SSW_OK;
+    idx->scores_partial = false;
+    return launch_index_scan(idx, idx->q_last);
+}
+
+// the rows are about to change: the buffer keeps the scores of the rows it was computed from, the shadow goes stale
+static ssw_status rows_changing(ssw_index *idx) {
+    SSW_TRY(ensure_full_scores(idx));
+    idx->q8_stale = true;
+    idx->q8_refused = false;
+    return SSW_OK;
+}
+
+static ssw_status scan_for_topk(ssw_index *idx, const float *q_dev, int32_t k);
 
 extern "C" {
 
@@ -284,6 +347,13 @@ ssw_status ssw_index_destroy(ssw_index *idx) {
     if (idx->own_stream) (void)hipStreamSynchronize(idx->own_stream);
     for (hipEvent_t e : idx->ev) (void)hipEventDestroy(e);
     if (idx->ws_ready) select_free(idx->ws);
+    free_shadow(idx);
+    (void)hipFree(idx->prune_state);
+    (void)hipFree(idx->surv_rows);
+    (void)hipFree(idx->surv_scores);
+    (void)hipFree(idx->q_last);
+    if (idx->prune_host) (void)hipHostFree(idx->prune_host);
+    if (idx->prune_ev) (void)hipEventDestroy(idx->prune_ev);
     if (idx->owns_X) (void)hipFree(idx->X);
     (void)hipFree(idx->xfer);
     (void)hipFree(idx->scores);
@@ -340,7 +410,14 @@ ssw_status ssw_index_dtype(const ssw_index *idx, int32_t *out) {
 
 ssw_status ssw_index_device_ptrs(ssw_index *idx, void **dev_vectors, void **dev_scores) {
     SSW_REQUIRE(idx != nullptr, "idx is NULL");
-    if (dev_vectors) *dev_vectors = idx->X;
+    DeviceGuard guard(idx->device);
+    SSW_TRY(ensure_full_scores(idx));
+    if (dev_vectors) {  // the caller may write the rows through it: no shadow from now on
+        idx->rows_escaped = true;
+        SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+        free_shadow(idx);
+        *dev_vectors = idx->X;
+    }
     if (dev_scores) *dev_scores = idx->scores;
     return SSW_OK;
 }
@@ -384,6 +461,7 @@ ssw_status ssw_index_upload(ssw_index *idx, const float *host_rows, int64_t firs
                 "rows [%lld, %lld) outside the index of %lld rows", (long long)first_row,
                 (long long)(first_row + n), (long long)idx->n);
     DeviceGuard guard(idx->device);
+    SSW_TRY(rows_changing(idx));
     if (idx->dtype == SSW_DTYPE_F16) return upload_h16(idx, host_rows, false, first_row, n);
     SSW_HIP_TRY(hipMemcpyAsync(idx->X + first_row * idx->dim, host_rows,
                                (size_t)n * idx->dim * sizeof(float), hipMemcpyHostToDevice,
@@ -402,6 +480,7 @@ ssw_status ssw_index_upload_f16(ssw_index *idx, const uint16_t *rows_f16, int64_
                 "rows [%lld, %lld) outside the index of %lld rows", (long long)first_row,
                 (long long)(first_row + n), (long long)idx->n);
     DeviceGuard guard(idx->device);
+    SSW_TRY(rows_changing(idx));
     return upload_h16(idx, rows_f16, true, first_row, n);
 }
 
@@ -435,6 +514,7 @@ ssw_status ssw_index_download(ssw_index *idx, float *host_rows, int64_t first_ro
 ssw_status ssw_index_fill_random(ssw_index *idx, uint64_t seed, int64_t global_first_row) {
     SSW_REQUIRE(idx != nullptr, "idx is NULL");
     DeviceGuard guard(idx->device);
+    SSW_TRY(rows_changing(idx));
     SSW_TRY(launch_fill_random(idx->X, idx->dtype, idx->n, idx->dim, seed, global_first_row, idx->stream));
     SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
     return SSW_OK;
@@ -510,6 +590,7 @@ ssw_status ssw_index_rescore_avg(ssw_index *idx, const int64_t *image_positions,
     SSW_REQUIRE(idx->has_map && idx->tile_boxes && idx->tile_zoom,
                 "rescore_avg needs ssw_index_set_row2image and ssw_index_set_tile_meta first");
     DeviceGuard guard(idx->device);
+    SSW_TRY(ensure_full_scores(idx));
     std::vector<int64_t> off((size_t)m);
     int64_t total = 0, max_tiles = 0;
     for (int32_t c = 0; c < m; ++c) {
@@ -642,6 +723,7 @@ ssw_status ssw_index_scan(ssw_index *idx, const float *q_host, float *out_scores
 ssw_status ssw_index_load_scores(ssw_index *idx, const float *scores_host) {
     SSW_REQUIRE(idx != nullptr && (idx->n == 0 || scores_host != nullptr), "NULL argument");
     DeviceGuard guard(idx->device);
+    idx->scores_partial = false;  // the whole buffer is overwritten
     if (idx->n > 0) {
         SSW_HIP_TRY(hipMemcpyAsync(idx->scores, scores_host, (size_t)idx->n * sizeof(float),
                                    hipMemcpyHostToDevice, idx->stream));
@@ -666,7 +748,8 @@ ssw_status ssw_index_set_excluded(ssw_index *idx, const int64_t *excluded_images
 ssw_status ssw_index_topk_dev(ssw_index *idx, const float *q_dev, int32_t k) {
     SSW_REQUIRE(idx != nullptr, "idx is NULL");
     DeviceGuard guard(idx->device);
-    if (q_dev) SSW_TRY(do_scan(idx, q_dev));
+    if (q_dev) SSW_TRY(scan_for_topk(idx, q_dev, k));
+    else SSW_TRY(ensure_full_scores(idx));
     if (idx->n_images == 0) {  // an empty shard still takes part in the exchange: its message says "0 keys"
         if (idx->ws.xchg.msg_out)
             SSW_HIP_TRY(hipMemsetAsync(idx->ws.xchg.msg_out + (idx->ws.xchg.msg_len - 1), 0, sizeof(uint64_t), idx->stream));
@@ -685,6 +768,12 @@ ssw_status ssw_index_select_deep_dev(ssw_index *idx, int32_t k) {
     if (idx->n_images == 0) return SSW_OK;
     DeviceGuard guard(idx->device);
     SSW_TRY(ensure_ws(idx));
+    if (idx->scores_partial) {  // the per-image values of the last selection came from a pruned buffer
+        SSW_TRY(ensure_full_scores(idx));
+        if (idx->has_map)
+            SSW_TRY(launch_image_max(idx->scores, idx->row_start, idx->n_images, idx->ws.img_score, idx->ws.img_best,
+                                     idx->stream));
+    }
     const float *values = idx->has_map ? idx->ws.img_score : idx->scores;
     const uint32_t *best = idx->has_map ? idx->ws.img_best : nullptr;
     return launch_select_topk_deep(idx->ws, values, idx->n_images, best, k, idx->device, idx->stream);
@@ -737,6 +826,111 @@ static ssw_status wait_host_seq(hipStream_t stream, const unsigned *flag, unsign
         set_error("topk: the selection kernel finished without publishing its result");
         return SSW_ERR_HIP;
     }
+    return SSW_OK;
+}
+
+// shadow of the rows for the pruned scan: (re)built when stale, if the device keeps PRUNE_RESERVE free beside it
+static ssw_status ensure_shadow(ssw_index *idx, bool *ready) {
+    *ready = false;
+    if (idx->q8 && !idx->q8_stale) {
+        *ready = true;
+        return SSW_OK;
+    }
+    if (idx->q8_refused) return SSW_OK;
+    if (!idx->q8) {
+        const size_t codes = (size_t)idx->n * idx->dim, consts = (size_t)idx->n * sizeof(float);
+        size_t free_b = 0, total_b = 0;
+        SSW_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        const size_t need = codes + 2 * consts + (size_t)SURV_CAP * 12 + ((size_t)idx->dim + 64) * sizeof(float);
+        if (free_b < need || free_b - need < (size_t)g_prune_reserve) {
+            idx->q8_refused = true;
+            return SSW_OK;
+        }
+        if (hipMalloc((void **)&idx->q8, codes) != hipSuccess || hipMalloc((void **)&idx->q8_scale, consts) != hipSuccess ||
+            hipMalloc((void **)&idx->q8_err, consts) != hipSuccess) {
+            (void)hipGetLastError();
+            free_shadow(idx);
+            idx->q8_refused = true;
+            return SSW_OK;
+        }
+    }
+    if (!idx->prune_state) {
+        SSW_HIP_TRY(hipMalloc((void **)&idx->prune_state, 4 * sizeof(unsigned)));
+        SSW_HIP_TRY(hipMalloc((void **)&idx->surv_rows, (size_t)SURV_CAP * sizeof(int64_t)));
+        SSW_HIP_TRY(hipMalloc((void **)&idx->surv_scores, (size_t)SURV_CAP * sizeof(float)));
+        SSW_HIP_TRY(hipMalloc((void **)&idx->q_last, (size_t)idx->dim * sizeof(float)));
+        SSW_HIP_TRY(hipHostMalloc((void **)&idx->prune_host, 16, hipHostMallocMapped | hipHostMallocCoherent));
+        memset(idx->prune_host, 0, 16);
+        SSW_HIP_TRY(hipEventCreateWithFlags(&idx->prune_ev, hipEventDisableTiming));
+    }
+    SSW_TRY(launch_q8_build(idx->X, idx->n, idx->dim, idx->q8, idx->q8_scale, idx->q8_err, idx->stream));
+    idx->q8_stale = false;
+    *ready = true;
+    return SSW_OK;
+}
+
+// The score buffer for the selection of the top-k of query q_dev (exclusions installed): the full f32 scan, or on a
+// large index the certified pre-scan -- shadow scan (lower bounds), threshold selection over them that publishes
+// nothing, survivors, exact rescoring of the survivors.  One host wait for the survivor count; any failure of the
+// certificate (fewer than k keys or an overflow in the threshold selection, more survivors than SURV_CAP, a query
+// that cannot be bounded) runs the full scan instead.  The profiling events bracket the whole replacement.
+static ssw_status scan_for_topk(ssw_index *idx, const float *q_dev, int32_t k) {
+    bool ready = false;
+    const bool k_ok = k >= 1 && k <= SSW_MAX_TOPK && (idx->ws.xchg.msg_out == nullptr || k <= idx->ws.xchg.k_max);
+    if (k_ok && prune_eligible(idx)) SSW_TRY(ensure_shadow(idx, &ready));
+    if (!ready) return do_scan(idx, q_dev);
+    SSW_TRY(ensure_ws(idx));
+    const bool prof = idx->profiling && idx->ev_used + 2 <= (int)idx->ev.size();
+    if (prof) SSW_HIP_TRY(hipEventRecord(idx->ev[idx->ev_used], idx->stream));
+    SSW_TRY(launch_q8_query(q_dev, idx->dim, idx->q_last, idx->prune_state, idx->stream));
+    SSW_TRY(launch_q8_bounds(idx->q8, idx->q8_scale, idx->q8_err, idx->q_last, idx->prune_state, idx->scores, idx->n,
+                             idx->dim, idx->device, idx->stream));
+    idx->scores_partial = true;  // from here on the buffer holds bounds: a consumer rescans q_last
+    SSW_HIP_TRY(hipEventRecord(idx->prune_ev, idx->stream));
+    // threshold: the ordinary selection over the lower bounds, with the exclusions, without a message or host result
+    const FinalExchange keep_x = idx->ws.xchg;
+    unsigned char *keep_packed = idx->ws.host_packed;
+    idx->ws.xchg = FinalExchange();
+    idx->ws.host_packed = nullptr;
+    const ssw_status st = do_select(idx, k);
+    idx->ws.xchg = keep_x;
+    idx->ws.host_packed = keep_packed;
+    SSW_TRY(st);
+    unsigned seq = ++idx->prune_seq;
+    if (seq == 0) seq = ++idx->prune_seq;
+    int32_t *host_dev = nullptr;
+    SSW_HIP_TRY(hipHostGetDevicePointer((void **)&host_dev, idx->prune_host, 0));
+    SSW_TRY(launch_survivors(idx->scores, idx->q8_err, idx->n, idx->ws.out_keys, idx->ws.out_count, k, idx->prune_state,
+                             idx->surv_rows, SURV_CAP, host_dev, seq, idx->device, idx->stream));
+    SSW_HIP_TRY(hipEventSynchronize(idx->prune_ev));  // sleep through the shadow scan, spin on the rest
+    SSW_TRY(wait_host_seq(idx->stream, reinterpret_cast<const unsigned *>(idx->prune_host), seq));
+    const int32_t m = __atomic_load_n(idx->prune_host + 1, __ATOMIC_ACQUIRE);
+    idx->prune_last = m;
+    ++idx->prune_queries;
+    if (m < 0) {
+        ++idx->prune_fallbacks;
+        idx->scores_partial = false;
+        SSW_TRY(launch_index_scan(idx, idx->q_last));
+    } else {
+        SSW_TRY(launch_score_rows(idx->X, idx->dtype, idx->q_last, idx->surv_rows, m, idx->dim, idx->surv_scores,
+                                  idx->stream));
+        SSW_TRY(launch_scatter_scores(idx->surv_rows, idx->surv_scores, m, idx->scores, idx->stream));
+    }
+    if (prof) {
+        SSW_HIP_TRY(hipEventRecord(idx->ev[idx->ev_used + 1], idx->stream));
+        idx->ev_used += 2;
+    }
+    return SSW_OK;
+}
+
+ssw_status ssw_index_prune_stats(ssw_index *idx, int64_t *out6) {
+    SSW_REQUIRE(idx != nullptr && out6 != nullptr, "NULL argument");
+    out6[0] = idx->q8 ? (idx->q8_stale ? 2 : 1) : (idx->q8_refused ? 3 : 0);
+    out6[1] = prune_eligible(idx) ? 1 : 0;
+    out6[2] = idx->prune_last;
+    out6[3] = idx->prune_queries;
+    out6[4] = idx->prune_fallbacks;
+    out6[5] = idx->q8 ? idx->n * (idx->dim + 8) : 0;
     return SSW_OK;
 }
 
@@ -899,6 +1093,7 @@ ssw_status index_enqueue_topk_resident(ssw_index *idx, hipStream_t on_stream, co
     SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
     SSW_REQUIRE(n_excluded == 0 || excluded_images != nullptr, "excluded_images is NULL");
     StreamSwap sw(idx, on_stream);
+    SSW_TRY(ensure_full_scores(idx));
     if (small_path_ok(idx, n_excluded)) return topk_small_enqueue(idx, nullptr, excluded_images, n_excluded, k);
     if (idx->n_images == 0) return SSW_OK;
     SSW_TRY(ssw_index_set_excluded(idx, excluded_images, n_excluded));
@@ -945,10 +1140,13 @@ ssw_status ssw_index_topk(ssw_index *idx, const float *q_host, const int64_t *ex
     if (q_host) {
         SSW_TRY(check_query(idx, q_host));
         SSW_TRY(stage_query(idx, q_host));
-        SSW_TRY(do_scan(idx, idx->q_dev));
+    } else {
+        SSW_TRY(ensure_full_scores(idx));
     }
+    // the exclusions first: a pruned scan selects its threshold with them
+    if (idx->n_images > 0) SSW_TRY(ssw_index_set_excluded(idx, excluded_images, n_excluded));
+    if (q_host) SSW_TRY(scan_for_topk(idx, idx->q_dev, k));
     if (idx->n_images == 0) return SSW_OK;
-    SSW_TRY(ssw_index_set_excluded(idx, excluded_images, n_excluded));
     // the selection's last kernel writes the packed result into the pinned mirror and releases a sequence word: the
     // host spins on it (no device-to-host copy, no stream wait)
     SSW_TRY(arm_host_result(idx));
@@ -1006,6 +1204,7 @@ ssw_status ssw_index_gather_scores(ssw_index *idx, const int64_t *rows_host, int
     if (n <= 0) return SSW_OK;
     SSW_REQUIRE(rows_host != nullptr && out_scores_host != nullptr, "NULL argument");
     DeviceGuard guard(idx->device);
+    SSW_TRY(ensure_full_scores(idx));
     SSW_TRY(stage_rows(idx, rows_host, n));
     SSW_TRY(launch_gather_f32(idx->scores, idx->gather_idx, n, idx->gather_out, idx->stream));
     SSW_HIP_TRY(hipMemcpyAsync(out_scores_host, idx->gather_out, (size_t)n * sizeof(float),
@@ -1092,6 +1291,13 @@ ssw_status ssw_tune_topk(int32_t flags) {
 
 ssw_status ssw_tune_scan(int32_t variant, int32_t blocks_per_cu) {
     tune_scan(variant, blocks_per_cu);
+    return SSW_OK;
+}
+
+ssw_status ssw_tune_prune(int32_t enable, int64_t min_rows, int64_t reserve_bytes) {
+    g_prune = enable != 0;
+    g_prune_min_rows = min_rows < 0 ? PRUNE_MIN_ROWS : min_rows;
+    g_prune_reserve = reserve_bytes < 0 ? PRUNE_RESERVE : reserve_bytes;
     return SSW_OK;
 }
 #endif

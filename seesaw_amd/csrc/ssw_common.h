@@ -159,6 +159,20 @@ ssw_status launch_scan(const void *X, int32_t dtype, const float *q_dev, float *
                        int device, hipStream_t stream);
 ssw_status launch_score_rows(const void *X, int32_t dtype, const float *q_dev, const int64_t *rows_dev, int64_t n,
                              int32_t dim, float *out, hipStream_t stream);
+// prune.hip: the int8 shadow of an f32 index and the certified pre-scan of the exact top-k (see prune.hip).
+// query state words: [0] survivors, [1] Q = ||q|| rounded up (f32 bits), [2] 1 = the query cannot be bounded
+bool q8_dim_supported(int32_t dim);
+ssw_status launch_q8_build(const float *X, int64_t n, int32_t dim, int8_t *codes, float *scale, float *err,
+                           hipStream_t stream);
+ssw_status launch_q8_query(const float *q_dev, int32_t dim, float *q_keep, unsigned *state, hipStream_t stream);
+ssw_status launch_q8_bounds(const int8_t *codes, const float *scale, const float *err, const float *q_dev,
+                            const unsigned *state, float *scores, int64_t n, int32_t dim, int device, hipStream_t stream);
+// rows with upper bound >= the k-th key of the last selection -> rows[0, cap), then host_block[1] = survivors or -1
+// (fall back to the full scan) and host_block[0] = seq, released to the host
+ssw_status launch_survivors(const float *lb, const float *err, int64_t n, const uint64_t *keys, const int32_t *sel_count,
+                            int32_t k, unsigned *state, int64_t *rows, int64_t cap, int32_t *host_block, unsigned seq,
+                            int device, hipStream_t stream);
+ssw_status launch_scatter_scores(const int64_t *rows, const float *v, int64_t m, float *scores, hipStream_t stream);
 // rows between natural order and the index.  to_h16: n rows of natural-order f32 (src_f32) or binary16 (src_h16, the
 // other NULL) -> rows [0, n) of dst in the f16 layout, rounded to nearest even.  gather: rows (rows_or_null[i], or
 // first_row + i when it is NULL) of an index matrix of element type dtype -> n natural-order f32 rows of out.
