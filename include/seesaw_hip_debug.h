@@ -36,6 +36,29 @@ ssw_status ssw_tune_topk(int32_t flags);
  * refused for memory is retried only after its rows change. */
 ssw_status ssw_tune_prune(int32_t enable, int64_t min_rows, int64_t reserve_bytes);
 
+/* The pre-scan's intermediate state, for tests/test_prune_certificate_gpu.py.  The three hooks run the product's
+ * kernels through the launch functions of the pruned top-k on the index's own buffers; all out pointers are HOST
+ * memory; the index must be one the next top-k would prune (ssw_tune_prune, f32, dim 256 / 512 / 1024, own rows).
+ * shadow: builds the int8 shadow if it is missing or stale (the product's ensure_shadow -> k_q8_build; SSW_ERR_NOMEM
+ *   when it is refused for memory) and copies out the codes [n_rows, dim] int8, s_r and a_r [n_rows] of the rows
+ *   [first_row, first_row + n_rows); an output that is NULL is skipped.
+ * bounds: k_q8_query + k_q8_bounds for a host query (finite, as for ssw_index_topk): out_lb [n] = every row's lower
+ *   bound, *out_Q = the state's Q, *out_unbounded = its "the query cannot be bounded" word.  The bounds stay in the
+ *   score buffer, marked partial with the query kept, exactly as after the product's shadow scan: every reader of
+ *   the buffer (ssw_index_topk without a query, gather, ...) first completes it with the full scan of that query.
+ * survivors: k_survivors + k_prune_publish over the bounds of the last ssw_debug_prune_bounds (SSW_ERR_INVALID when a
+ *   reader has completed the buffer since) against the caller's threshold, standing in for what the threshold
+ *   selection leaves: k keys of that value, a count of sel_count keys and the overflow word sel_overflow.  cap <= 2^18
+ *   is the list's capacity.  *out_published = what the host would read (survivors, or -1 = fall back to the full scan),
+ *   *out_collected = the device's survivor counter (it passes cap when more rows qualify; 0 when nothing was
+ *   collected), out_rows [cap] receives the first *out_published rows of the list (unordered). */
+ssw_status ssw_debug_prune_shadow(ssw_index *idx, int64_t first_row, int64_t n_rows, int8_t *out_codes, float *out_scale,
+                                  float *out_err);
+ssw_status ssw_debug_prune_bounds(ssw_index *idx, const float *q_host, float *out_lb, float *out_Q,
+                                  int32_t *out_unbounded);
+ssw_status ssw_debug_prune_survivors(ssw_index *idx, float threshold, int32_t k, int32_t sel_count, int32_t sel_overflow,
+                                     int64_t cap, int32_t *out_published, int64_t *out_collected, int64_t *out_rows);
+
 /* Kernel A/B harness for the towers' bf16 GEMM (C[M,N] = A[M,K] W[N,K]^T + epilogue `epi`, see
  * csrc/gemm_bf16.hip): runs `variant` on seeded operands, reports ms per launch over `iters`
  * launches and the max |difference| to variant 0.  Not part of the reference's interface. */

@@ -1300,6 +1300,97 @@ ssw_status ssw_tune_prune(int32_t enable, int64_t min_rows, int64_t reserve_byte
     g_prune_reserve = reserve_bytes < 0 ? PRUNE_RESERVE : reserve_bytes;
     return SSW_OK;
 }
+
+// ---- the pre-scan's intermediate state (tests/test_prune_certificate_gpu.py) ----------------------------------------
+// Each hook drives the product's kernels through the launch_* functions scan_for_topk uses, on the index's own buffers.
+ssw_status ssw_debug_prune_shadow(ssw_index *idx, int64_t first_row, int64_t n_rows, int8_t *out_codes, float *out_scale,
+                                  float *out_err) {
+    SSW_REQUIRE(idx != nullptr, "idx is NULL");
+    SSW_REQUIRE(first_row >= 0 && n_rows >= 0 && first_row + n_rows <= idx->n, "rows [%lld, +%lld) outside [0, %lld)",
+                (long long)first_row, (long long)n_rows, (long long)idx->n);
+    SSW_REQUIRE(prune_eligible(idx), "the index is not pruned (ssw_tune_prune, dtype, dim, borrowed or escaped rows)");
+    DeviceGuard guard(idx->device);
+    bool ready = false;
+    SSW_TRY(ensure_shadow(idx, &ready));
+    if (!ready) {
+        set_error("prune_shadow: the shadow was refused for memory");
+        return SSW_ERR_NOMEM;
+    }
+    if (n_rows > 0 && out_codes)
+        SSW_HIP_TRY(hipMemcpyAsync(out_codes, idx->q8 + first_row * idx->dim, (size_t)n_rows * idx->dim,
+                                   hipMemcpyDeviceToHost, idx->stream));
+    if (n_rows > 0 && out_scale)
+        SSW_HIP_TRY(hipMemcpyAsync(out_scale, idx->q8_scale + first_row, (size_t)n_rows * sizeof(float),
+                                   hipMemcpyDeviceToHost, idx->stream));
+    if (n_rows > 0 && out_err)
+        SSW_HIP_TRY(hipMemcpyAsync(out_err, idx->q8_err + first_row, (size_t)n_rows * sizeof(float),
+                                   hipMemcpyDeviceToHost, idx->stream));
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_prune_bounds(ssw_index *idx, const float *q_host, float *out_lb, float *out_Q,
+                                  int32_t *out_unbounded) {
+    SSW_REQUIRE(idx != nullptr && q_host != nullptr && out_lb != nullptr && out_Q != nullptr && out_unbounded != nullptr,
+                "NULL argument");
+    SSW_TRY(check_query(idx, q_host));
+    SSW_REQUIRE(prune_eligible(idx), "the index is not pruned (ssw_tune_prune, dtype, dim, borrowed or escaped rows)");
+    DeviceGuard guard(idx->device);
+    bool ready = false;
+    SSW_TRY(ensure_shadow(idx, &ready));
+    if (!ready) {
+        set_error("prune_bounds: the shadow was refused for memory");
+        return SSW_ERR_NOMEM;
+    }
+    SSW_TRY(idx->q_stage.push(idx->q_dev, q_host, (size_t)idx->dim * sizeof(float), idx->stream));
+    SSW_TRY(launch_q8_query(idx->q_dev, idx->dim, idx->q_last, idx->prune_state, idx->stream));
+    SSW_TRY(launch_q8_bounds(idx->q8, idx->q8_scale, idx->q8_err, idx->q_last, idx->prune_state, idx->scores, idx->n,
+                             idx->dim, idx->device, idx->stream));
+    idx->scores_partial = true;  // as after scan_for_topk: every reader completes the buffer with the scan of q_last
+    unsigned state[4] = {0u, 0u, 0u, 0u};
+    SSW_HIP_TRY(hipMemcpyAsync(state, idx->prune_state, sizeof(state), hipMemcpyDeviceToHost, idx->stream));
+    SSW_HIP_TRY(hipMemcpyAsync(out_lb, idx->scores, (size_t)idx->n * sizeof(float), hipMemcpyDeviceToHost, idx->stream));
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+    memcpy(out_Q, &state[1], sizeof(float));
+    *out_unbounded = (int32_t)state[2];
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_prune_survivors(ssw_index *idx, float threshold, int32_t k, int32_t sel_count, int32_t sel_overflow,
+                                     int64_t cap, int32_t *out_published, int64_t *out_collected, int64_t *out_rows) {
+    SSW_REQUIRE(idx != nullptr && out_published != nullptr && out_collected != nullptr, "NULL argument");
+    SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
+    SSW_REQUIRE(cap >= 0 && cap <= SURV_CAP, "cap=%lld outside [0, %lld]", (long long)cap, (long long)SURV_CAP);
+    SSW_REQUIRE(cap == 0 || out_rows != nullptr, "out_rows is NULL");
+    SSW_REQUIRE(idx->scores_partial && idx->q8 && !idx->q8_stale, "no bounds in the buffer: ssw_debug_prune_bounds first");
+    DeviceGuard guard(idx->device);
+    SSW_TRY(ensure_ws(idx));
+    // what the threshold selection leaves behind: k keys (only the k-th is read) and [count, overflow]
+    std::vector<uint64_t> keys((size_t)k, (uint64_t)f32_to_ord(threshold) << 32);
+    const int32_t count[2] = {sel_count, sel_overflow};
+    SSW_HIP_TRY(hipMemcpyAsync(idx->ws.out_keys, keys.data(), keys.size() * sizeof(uint64_t), hipMemcpyHostToDevice,
+                               idx->stream));
+    SSW_HIP_TRY(hipMemcpyAsync(idx->ws.out_count, count, sizeof(count), hipMemcpyHostToDevice, idx->stream));
+    SSW_HIP_TRY(hipMemsetAsync(idx->prune_state, 0, sizeof(unsigned), idx->stream));  // the counter k_q8_query resets
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));  // keys and count are pageable host memory
+    unsigned seq = ++idx->prune_seq;
+    if (seq == 0) seq = ++idx->prune_seq;
+    int32_t *host_dev = nullptr;
+    SSW_HIP_TRY(hipHostGetDevicePointer((void **)&host_dev, idx->prune_host, 0));
+    SSW_TRY(launch_survivors(idx->scores, idx->q8_err, idx->n, idx->ws.out_keys, idx->ws.out_count, k, idx->prune_state,
+                             idx->surv_rows, cap, host_dev, seq, idx->device, idx->stream));
+    SSW_TRY(wait_host_seq(idx->stream, reinterpret_cast<const unsigned *>(idx->prune_host), seq));
+    const int32_t m = __atomic_load_n(idx->prune_host + 1, __ATOMIC_ACQUIRE);
+    unsigned collected = 0u;
+    SSW_HIP_TRY(hipMemcpyAsync(&collected, idx->prune_state, sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
+    if (m > 0)
+        SSW_HIP_TRY(hipMemcpyAsync(out_rows, idx->surv_rows, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost,
+                                   idx->stream));
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+    *out_published = m;
+    *out_collected = (int64_t)collected;
+    return SSW_OK;
+}
 #endif
 
 ssw_status ssw_index_profile(ssw_index *idx, int32_t enable) {

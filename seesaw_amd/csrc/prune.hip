@@ -31,7 +31,8 @@ constexpr int Q8_GROUP_LOADS = 8;      // 16-byte loads a lane keeps in flight p
 constexpr double PAD_ABS = 0x1p-100;   // covers underflow of both computations (dim + 16 roundings at 2^-126 each)
 constexpr double SAFETY = 1.0 + 0x1p-10;  // explicit factor on every a_r (covers the double-precision sums and sqrt)
 constexpr float MAX_ABS = 0x1p60f, MIN_ABS = 0x1p-60f;  // a row's max |x| outside this range is not bounded
-constexpr float MAX_QNORM = 0x1p40f;  // ... nor a query above this norm: |S| < 2^104 keeps every partial sum finite
+constexpr float MAX_QNORM = 0x1p40f;  // ... nor a query above this norm (|S| < 2^104 keeps every partial sum finite),
+                                      // nor the zero query (k_q8_query)
 
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
@@ -126,7 +127,9 @@ __global__ __launch_bounds__(256) void k_q8_query(const float *__restrict__ q, i
     if (threadIdx.x == 0) {
         const double t = part[0] + part[1] + part[2] + part[3];
         const float Q = __double2float_ru(sqrt(t) * (1.0 + 0x1p-40));
-        const bool bad = !all_finite || !(Q <= MAX_QNORM);
+        // the zero query bounds nothing (every score is +-0 or NaN) and a * Q = inf * 0 would make the lower bound of an
+        // unbounded row NaN: as the k-th key that is a threshold no upper bound is below, so every row would survive
+        const bool bad = !all_finite || !(Q <= MAX_QNORM) || Q == 0.0f;
         state[0] = 0u;
         state[1] = __float_as_uint(Q);
         state[2] = bad ? 1u : 0u;

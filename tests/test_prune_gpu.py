@@ -6,45 +6,11 @@ import ctypes
 import numpy as np
 import pytest
 
+from _prune_helpers import both, mode, query, same, stats
+
 pytestmark = pytest.mark.gpu
 
 MIN_ROWS = 1 << 22
-
-
-def stats(idx):
-    from seesaw_amd import _lib
-    out = np.zeros(6, dtype=np.int64)
-    _lib.call("ssw_index_prune_stats", idx._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
-    return out
-
-
-def mode(lib, on, min_rows=-1, reserve=-1):
-    from seesaw_amd import _lib
-    _lib.call("ssw_tune_prune", 1 if on else 0, int(min_rows), int(reserve))
-
-
-def query(seed, dim=512):
-    q = np.random.default_rng(seed).standard_normal(dim).astype(np.float32)
-    return (q / np.linalg.norm(q)).astype(np.float32)
-
-
-def both(lib, idx, fn, min_rows=-1):
-    """fn() with pruning off, then on: (full, pruned, stats after the pruned call)"""
-    mode(lib, False)
-    full = fn()
-    mode(lib, True, min_rows)
-    got = fn()
-    st = stats(idx)
-    mode(lib, True)
-    return full, got, st
-
-
-def same(a, b):
-    assert len(a) == len(b)
-    for x, y in zip(a, b):
-        x, y = np.asarray(x), np.asarray(y)
-        assert x.dtype == y.dtype and x.shape == y.shape
-        assert np.array_equal(x.view(np.uint8), y.view(np.uint8)), (x[:8], y[:8])
 
 
 @pytest.mark.parametrize("log_rows", [22, 23, 25])
