@@ -36,6 +36,12 @@ ssw_status ssw_tune_topk(int32_t flags);
  * refused for memory is retried only after its rows change. */
 ssw_status ssw_tune_prune(int32_t enable, int64_t min_rows, int64_t reserve_bytes);
 
+/* The launch shape of the shadow scan (k_q8_bounds): four-wave blocks per CU (1 .. 8) and 16-byte loads a lane keeps in
+ * flight per group (4, 8 or 16: 4, 8 or 16 KiB a wave); any other value = the product's (1 block, 8 loads).  Every
+ * shape writes bounds that satisfy the same certificate; the summation order of a row's products differs with the
+ * loads a group.  tools/sweep_prune.py times them. */
+ssw_status ssw_tune_prune_scan(int32_t blocks_per_cu, int32_t group_loads);
+
 /* The pre-scan's intermediate state, for tests/test_prune_certificate_gpu.py.  The three hooks run the product's
  * kernels through the launch functions of the pruned top-k on the index's own buffers; all out pointers are HOST
  * memory; the index must be one the next top-k would prune (ssw_tune_prune, f32, dim 256 / 512 / 1024, own rows).

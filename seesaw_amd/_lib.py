@@ -151,6 +151,7 @@ _DEBUG_SIGNATURES = {
     "ssw_tune_scan": (c_i32, [c_i32, c_i32]),
     "ssw_tune_topk": (c_i32, [c_i32]),
     "ssw_tune_prune": (c_i32, [c_i32, c_i64, c_i64]),
+    "ssw_tune_prune_scan": (c_i32, [c_i32, c_i32]),
     "ssw_debug_prune_shadow": (c_i32, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p]),
     "ssw_debug_prune_bounds": (c_i32, [c_void_p, c_void_p, c_void_p, c_f32_p, c_i32_p]),
     "ssw_debug_prune_survivors": (c_i32, [c_void_p, ctypes.c_float, c_i32, c_i32, c_i32, c_i64, c_i32_p, c_i64_p,

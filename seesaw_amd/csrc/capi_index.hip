@@ -1301,6 +1301,11 @@ ssw_status ssw_tune_prune(int32_t enable, int64_t min_rows, int64_t reserve_byte
     return SSW_OK;
 }
 
+ssw_status ssw_tune_prune_scan(int32_t blocks_per_cu, int32_t group_loads) {
+    tune_q8_bounds(blocks_per_cu, group_loads);
+    return SSW_OK;
+}
+
 // ---- the pre-scan's intermediate state (tests/test_prune_certificate_gpu.py) ----------------------------------------
 // Each hook drives the product's kernels through the launch_* functions scan_for_topk uses, on the index's own buffers.
 ssw_status ssw_debug_prune_shadow(ssw_index *idx, int64_t first_row, int64_t n_rows, int8_t *out_codes, float *out_scale,

@@ -28,6 +28,10 @@ namespace ssw {
 namespace {
 
 constexpr int Q8_GROUP_LOADS = 8;      // 16-byte loads a lane keeps in flight per group (8 KiB a wave)
+constexpr int Q8_BLOCKS_PER_CU = 1;    // four-wave blocks of the shadow scan per CU (one wave a SIMD)
+// tuning hooks (ssw_tune_prune_scan, lab build only): group loads 4 / 8 / 16, blocks per CU 1 .. 8
+SSW_TUNABLE int g_q8_group_loads = Q8_GROUP_LOADS;
+SSW_TUNABLE int g_q8_blocks_per_cu = Q8_BLOCKS_PER_CU;
 constexpr double PAD_ABS = 0x1p-100;   // covers underflow of both computations (dim + 16 roundings at 2^-126 each)
 constexpr double SAFETY = 1.0 + 0x1p-10;  // explicit factor on every a_r (covers the double-precision sums and sqrt)
 constexpr float MAX_ABS = 0x1p60f, MIN_ABS = 0x1p-60f;  // a row's max |x| outside this range is not bounded
@@ -136,76 +140,158 @@ __global__ __launch_bounds__(256) void k_q8_query(const float *__restrict__ q, i
     }
 }
 
-// the shadow scan: lb_r into scores[r] for every row.  C = dim / 256; L = 16 C lanes a row, 4 / C rows per
-// wave-instruction; a wave walks groups of Q8_GROUP_LOADS wave-instructions (double-buffered), grid-strided.
-template <int C>
+// v of the lane whose index differs by the DPP control: quad_perm [1,0,3,2] (lane ^ 1), quad_perm [2,3,0,1] (lane ^ 2),
+// row_half_mirror (lane ^ 7) and row_ror:8 (lane ^ 8).  One VALU instruction each, where __shfl_xor goes through the LDS
+// crossbar (ds_bpermute_b32) and needs an address register.
+constexpr int DPP_XOR1 = 0xB1, DPP_XOR2 = 0x4E, DPP_XOR7 = 0x141, DPP_XOR8 = 0x128;
+template <int CTRL>
+__device__ __forceinline__ float dpp(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
+}
+
+// v of lane ^ (1 << BIT) (lane ^ 7 for BIT 2: see q8_group_reduce)
+template <int BIT>
+__device__ __forceinline__ float q8_partner(float v) {
+    if constexpr (BIT == 0) return dpp<DPP_XOR1>(v);
+    else if constexpr (BIT == 1) return dpp<DPP_XOR2>(v);
+    else if constexpr (BIT == 2) return dpp<DPP_XOR7>(v);
+    else if constexpr (BIT == 3) return dpp<DPP_XOR8>(v);
+    else return __shfl_xor(v, 1 << BIT, 64);
+}
+
+// one transposing step over lane bit BIT: the H pairs (acc[i], acc[i + H]) become acc[i] = own + partner's of the half
+// the lane's bit selects, so H values are left; then the steps below it
+template <int BIT, int H>
+__device__ __forceinline__ void q8_fold(float *acc, int j) {
+    const bool upper = (j >> BIT) & 1;
+#pragma unroll
+    for (int i = 0; i < H; ++i) {
+        const float keep = upper ? acc[i + H] : acc[i];
+        const float send = upper ? acc[i] : acc[i + H];
+        acc[i] = keep + q8_partner<BIT>(send);
+    }
+    if constexpr (H > 1) q8_fold<BIT - 1, H / 2>(acc, j);
+}
+
+// Sums the U accumulators of a group over the L lanes of a row together: log2 U transposing steps from lane bit
+// log2 U - 1 down to bit 0 (U - 1 exchanges in all), then one value over the remaining lane bits: lane j of a row's L
+// lanes ends with the whole sum of load j % U.  Bit 2's partner is lane ^ 7, not lane ^ 4 (DPP has no xor 4): both lanes
+// of that pair still hold all values of the bits below, which are folded afterwards, so every lane is still counted once.
+template <int U, int L>
+__device__ __forceinline__ float q8_group_reduce(float (&acc)[U], int j) {
+    static_assert(U == 4 || U == 8 || U == 16, "loads a group");
+    constexpr int TOP = U == 4 ? 1 : U == 8 ? 2 : 3;
+    q8_fold<TOP, U / 2>(acc, j);
+    float v = acc[0];
+    // lanes now differ in what they hold by their bits below log2 U: from here on plain xor partners only
+    if constexpr (U <= 4 && L > 4) v += __shfl_xor(v, 4, 64);
+    if constexpr (U <= 8 && L > 8) v += dpp<DPP_XOR8>(v);
+#pragma unroll
+    for (int off = 16; off < L; off <<= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// the shadow scan: lb_r into scores[r] for every row.  C = dim / 256; L = 16 C lanes a row, RPL = 4 / C rows per
+// wave-instruction (1 KiB at every dim); a wave walks the full groups of U wave-instructions, grid-strided.  Two
+// register sets (a, b) take turns: while one group is multiplied the next group's codes AND its rows' constants are in
+// flight, so the only waits inside the loop are counted ones for the group that was requested an iteration earlier.
+// Lane j < U of row segment `seg` owns row j * RPL + seg of its group: it loads that row's s_r and a_r and writes its
+// bound.  The loop has one exit and no branch around a request: a path with fewer loads outstanding would make the
+// compiler's wait counts conservative on every path.  The last n % G rows are one clamped group of their own, after
+// the loop, for one wave.
+template <int C, int U>
 __global__ __launch_bounds__(256) void k_q8_bounds(const int8_t *__restrict__ codes, const float *__restrict__ scale,
                                                    const float *__restrict__ err, const float *__restrict__ q,
                                                    const unsigned *__restrict__ state, float *__restrict__ scores,
                                                    int64_t n) {
-    constexpr int L = 16 * C, RPL = 4 / C, U = Q8_GROUP_LOADS, G = U * RPL;  // G rows a group
+    constexpr int L = 16 * C, RPL = 4 / C, G = U * RPL;  // G rows a group
+    constexpr unsigned LOAD_BYTES = 1024;               // RPL rows of 256 C bytes
     const int lane = threadIdx.x & 63;
     const int seg = lane / L, j = lane % L;
     const int64_t gwave = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t nwaves = (int64_t)gridDim.x * 4;
-    const int64_t ngroups = (n + G - 1) / G;
-    if (gwave >= ngroups) return;
-    const int64_t last = n - 1;
+    const int64_t nfull = n / G;       // groups of G rows
+    const int ragged = (int)(n % G);   // rows of the group after them
     const double Qd = (double)__uint_as_float(state[1]);
-    float qv[16];
+    f32x2 qv[8];
 #pragma unroll
-    for (int t = 0; t < 16; t += 4) {
-        const float4 v = reinterpret_cast<const float4 *>(q)[(16 * j + t) >> 2];
-        qv[t] = v.x;
-        qv[t + 1] = v.y;
-        qv[t + 2] = v.z;
-        qv[t + 3] = v.w;
+    for (int t = 0; t < 4; ++t) {
+        const float4 v = reinterpret_cast<const float4 *>(q)[4 * j + t];
+        qv[2 * t] = f32x2{v.x, v.y};
+        qv[2 * t + 1] = f32x2{v.z, v.w};
     }
-    u32x4 cur[U], nxt[U];
-    auto load = [&](u32x4(&dst)[U], int64_t g) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t row = min(g * G + u * RPL + seg, last);
-            dst[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(codes + row * (256 * C)) + j);
-        }
+    const unsigned lane_byte = (unsigned)(seg * 256 * C + 16 * j);  // of this lane's 16 codes in a wave-instruction
+    const int mine = (j % U) * RPL + seg;                           // the group row this lane holds the constants of
+    struct Set {
+        u32x4 c[U];
+        float s, a;
     };
-    load(cur, gwave);
-    for (int64_t g = gwave; g < ngroups; g += nwaves) {
-        const int64_t gn = g + nwaves < ngroups ? g + nwaves : g;  // no next group: re-touch own rows
-        load(nxt, gn);
-        // this group's per-row constants: lane i < G holds row g*G + i
-        const int64_t my_row = g * G + lane;
-        float s_r = 0.0f, a_r = 0.0f;
-        if (lane < G && my_row < n) {
-            s_r = scale[my_row];
-            a_r = err[my_row];
-        }
+    // all requests of a full group: U code loads and the two constants (every lane loads them: lanes j >= U those of
+    // lane j % U, the same cache line)
+    auto load = [&](Set &d, int64_t g) {
+        const int8_t *base = codes + g * (int64_t)(G * 256 * C);  // wave-uniform
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            d.c[u] = __builtin_nontemporal_load(
+                reinterpret_cast<const u32x4 *>(base + (lane_byte + (unsigned)u * LOAD_BYTES)));
+        d.s = (scale + g * G)[mine];
+        d.a = (err + g * G)[mine];
+        // left alone the scheduler sinks these requests into the multiplies that follow, to reuse the registers of
+        // the set being consumed: the next group would be requested half a group late
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // the bounds of the first `rows` rows of group g from a set that has arrived
+    auto bounds = [&](const Set &d, int64_t g, int rows) {
         float acc[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const unsigned w[4] = {cur[u].x, cur[u].y, cur[u].z, cur[u].w};
-            float a = 0.0f;
+            const unsigned w[4] = {d.c[u].x, d.c[u].y, d.c[u].z, d.c[u].w};
+            f32x2 a2 = {0.0f, 0.0f};  // even and odd elements: the order of the dim products is free
 #pragma unroll
-            for (int t = 0; t < 16; ++t) a = fmaf((float)(int)(int8_t)(w[t >> 2] >> (8 * (t & 3))), qv[t], a);
-#pragma unroll
-            for (int off = 1; off < L; off <<= 1) a += __shfl_xor(a, off, 64);
-            acc[u] = a;
+            for (int t = 0; t < 16; t += 2) {
+                const f32x2 c2 = {(float)(int)(int8_t)(w[t >> 2] >> (8 * (t & 3))),
+                                  (float)(int)(int8_t)(w[t >> 2] >> (8 * ((t + 1) & 3)))};
+                a2 = __builtin_elementwise_fma(c2, qv[t >> 1], a2);
+            }
+            acc[u] = a2.x + a2.y;
         }
-        // lane i < G takes row i of the group: load u = i / RPL, segment i % RPL
-        float mine = 0.0f;
+        const float A = q8_group_reduce<U, L>(acc, j);
+        if (j < U && mine < rows) {
+            // s * A and a * Q are exact in double; the subtraction's rounding is covered by the relative pad
+            double lb = (double)d.s * (double)A - (double)d.a * Qd;
+            lb -= fabs(lb) * 0x1p-50 + PAD_ABS;
+            (scores + g * G)[mine] = __double2float_rd(lb);
+        }
+    };
+    if (gwave < nfull) {
+        Set a, b;
+        int64_t g = gwave;
+        load(a, g);
+        for (;;) {
+            // a wave without a next group requests its last one once more (cache hits) and writes nothing for it
+            const int64_t g1 = g + nwaves < nfull ? g + nwaves : g;
+            load(b, g1);
+            bounds(a, g, G);
+            const int64_t g2 = g1 + nwaves < nfull ? g1 + nwaves : g1;
+            load(a, g2);
+            bounds(b, g1, g1 != g ? G : 0);
+            if (g2 == g1) break;
+            g = g2;
+        }
+    }
+    if (ragged != 0 && gwave == nfull % nwaves) {
+        Set t;
+        const int8_t *base = codes + nfull * (int64_t)(G * 256 * C);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const float v = __shfl(acc[u], (lane % RPL) * L, 64);
-            mine = (lane / RPL == u) ? v : mine;
+            const unsigned row = (unsigned)min(u * RPL + seg, ragged - 1);  // nothing beyond row n - 1
+            t.c[u] = *reinterpret_cast<const u32x4 *>(base + (row * (unsigned)(256 * C) + 16u * (unsigned)j));
         }
-        if (lane < G && my_row < n) {
-            // s * A and a * Q are exact in double; the subtraction's rounding is covered by the relative pad
-            double lb = (double)s_r * (double)mine - (double)a_r * Qd;
-            lb -= fabs(lb) * 0x1p-50 + PAD_ABS;
-            scores[my_row] = __double2float_rd(lb);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+        t.s = (scale + nfull * G)[min(mine, ragged - 1)];
+        t.a = (err + nfull * G)[min(mine, ragged - 1)];
+        bounds(t, nfull, ragged);
     }
 }
 
@@ -222,23 +308,40 @@ __global__ __launch_bounds__(256) void k_survivors(const float *__restrict__ lb,
     const float T = ord_to_f32((uint32_t)(keys[k - 1] >> 32));
     const double Qd = (double)__uint_as_float(state[1]);
     const int lane = threadIdx.x & 63;
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t base = (int64_t)blockIdx.x * 256 + (threadIdx.x & ~63u); base < n; base += stride) {  // wave-uniform
-        const int64_t r = base + lane;
-        bool keep = false;
-        if (r < n) {
-            const double l = (double)lb[r], w = (double)err[r] * Qd;
-            const double ub = l + 2.0 * w + (fabs(l) + w) * 0x1p-20 + 2.0 * PAD_ABS;
-            keep = !(ub < (double)T);  // NaN survives
+    const uint64_t below = (1ull << lane) - 1ull;
+    const int64_t stride = (int64_t)gridDim.x * 1024;
+    // a lane takes four consecutive rows (one 16-byte load of each array), a wave 256: wave-uniform loop
+    for (int64_t base = (int64_t)blockIdx.x * 1024 + (threadIdx.x & ~63u) * 4; base < n; base += stride) {
+        const int64_t r0 = base + 4 * lane;
+        float l4[4] = {0.0f, 0.0f, 0.0f, 0.0f}, e4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (r0 + 3 < n) {
+            const float4 lv = *reinterpret_cast<const float4 *>(lb + r0), ev = *reinterpret_cast<const float4 *>(err + r0);
+            l4[0] = lv.x, l4[1] = lv.y, l4[2] = lv.z, l4[3] = lv.w;
+            e4[0] = ev.x, e4[1] = ev.y, e4[2] = ev.z, e4[3] = ev.w;
+        } else {
+            for (int t = 0; t < 4; ++t)
+                if (r0 + t < n) l4[t] = lb[r0 + t], e4[t] = err[r0 + t];
         }
-        const uint64_t ballot = __ballot(keep);
-        if (ballot == 0ull) continue;
-        unsigned slot0 = 0u;
-        if (lane == __builtin_ctzll(ballot)) slot0 = atomicAdd(&state[0], (unsigned)__popcll(ballot));
-        slot0 = __shfl(slot0, __builtin_ctzll(ballot), 64);
-        if (keep) {
-            const int64_t at = (int64_t)slot0 + __popcll(ballot & ((1ull << lane) - 1ull));
-            if (at < cap) rows[at] = r;
+        bool keep[4];
+        uint64_t ballot[4];
+        unsigned total = 0u;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const double l = (double)l4[t], w = (double)e4[t] * Qd;
+            const double ub = l + 2.0 * w + (fabs(l) + w) * 0x1p-20 + 2.0 * PAD_ABS;
+            keep[t] = r0 + t < n && !(ub < (double)T);  // NaN survives
+            ballot[t] = __ballot(keep[t]);
+            total += (unsigned)__popcll(ballot[t]);
+        }
+        if (total == 0u) continue;
+        unsigned slot = 0u;
+        if (lane == 0) slot = atomicAdd(&state[0], total);
+        slot = __shfl(slot, 0, 64);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int64_t at = (int64_t)slot + __popcll(ballot[t] & below);
+            if (keep[t] && at < cap) rows[at] = r0 + t;
+            slot += (unsigned)__popcll(ballot[t]);
         }
     }
 }
@@ -289,38 +392,53 @@ ssw_status launch_q8_bounds(const int8_t *codes, const float *scale, const float
                             const unsigned *state, float *scores, int64_t n, int32_t dim, int device,
                             hipStream_t stream) {
     if (n <= 0) return SSW_OK;
+    if (!q8_dim_supported(dim)) {
+        set_error("q8_bounds: dim=%d unsupported", dim);
+        return SSW_ERR_UNSUPPORTED;
+    }
     const int C = dim / 256;
-    const int64_t rows_per_group = (int64_t)Q8_GROUP_LOADS * (4 / C);
+    const int64_t rows_per_group = (int64_t)g_q8_group_loads * (4 / C);
     const int64_t need = ((n + rows_per_group - 1) / rows_per_group + 3) / 4;
-    int64_t grid = (int64_t)num_cus(device) * 2;  // two 4-wave blocks per CU
+    int64_t grid = (int64_t)num_cus(device) * g_q8_blocks_per_cu;  // four-wave blocks
     if (grid > need) grid = need;
     if (grid < 1) grid = 1;
-    switch (dim) {
-        case 256:
-            hipLaunchKernelGGL(k_q8_bounds<1>, dim3((unsigned)grid), dim3(256), 0, stream, codes, scale, err, q_dev, state,
-                               scores, n);
-            break;
-        case 512:
-            hipLaunchKernelGGL(k_q8_bounds<2>, dim3((unsigned)grid), dim3(256), 0, stream, codes, scale, err, q_dev, state,
-                               scores, n);
-            break;
-        case 1024:
-            hipLaunchKernelGGL(k_q8_bounds<4>, dim3((unsigned)grid), dim3(256), 0, stream, codes, scale, err, q_dev, state,
-                               scores, n);
-            break;
-        default:
-            set_error("q8_bounds: dim=%d unsupported", dim);
-            return SSW_ERR_UNSUPPORTED;
+#define SSW_Q8_BOUNDS(C_, U_)                                                                                         \
+    hipLaunchKernelGGL((k_q8_bounds<C_, U_>), dim3((unsigned)grid), dim3(256), 0, stream, codes, scale, err, q_dev, \
+                       state, scores, n)
+#define SSW_Q8_BOUNDS_DIM(U_)                 \
+    switch (C) {                              \
+        case 1: SSW_Q8_BOUNDS(1, U_); break;  \
+        case 2: SSW_Q8_BOUNDS(2, U_); break;  \
+        default: SSW_Q8_BOUNDS(4, U_); break; \
     }
+#ifdef SSW_DEBUG_HOOKS
+    if (g_q8_group_loads == 4) {
+        SSW_Q8_BOUNDS_DIM(4)
+    } else if (g_q8_group_loads == 16) {
+        SSW_Q8_BOUNDS_DIM(16)
+    } else
+#endif
+    {
+        SSW_Q8_BOUNDS_DIM(Q8_GROUP_LOADS)
+    }
+#undef SSW_Q8_BOUNDS_DIM
+#undef SSW_Q8_BOUNDS
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
 }
+
+#ifdef SSW_DEBUG_HOOKS
+void tune_q8_bounds(int blocks_per_cu, int group_loads) {
+    g_q8_blocks_per_cu = blocks_per_cu >= 1 && blocks_per_cu <= 8 ? blocks_per_cu : Q8_BLOCKS_PER_CU;
+    g_q8_group_loads = group_loads == 4 || group_loads == 16 ? group_loads : Q8_GROUP_LOADS;
+}
+#endif
 
 ssw_status launch_survivors(const float *lb, const float *err, int64_t n, const uint64_t *keys, const int32_t *sel_count,
                             int32_t k, unsigned *state, int64_t *rows, int64_t cap, int32_t *host_block, unsigned seq,
                             int device, hipStream_t stream) {
     int64_t grid = (int64_t)num_cus(device) * 4;
-    const int64_t need = (n + 255) / 256;
+    const int64_t need = (n + 1023) / 1024;  // four rows a lane
     if (grid > need) grid = need;
     if (grid < 1) grid = 1;
     hipLaunchKernelGGL(k_survivors, dim3((unsigned)grid), dim3(256), 0, stream, lb, err, n, keys, sel_count, k, state,

@@ -182,6 +182,7 @@ ssw_status launch_gather_rows(const void *X, int32_t dtype, const int64_t *rows_
                               int32_t dim, float *out, hipStream_t stream);
 #ifdef SSW_DEBUG_HOOKS
 void tune_scan(int variant, int blocks_per_cu);
+void tune_q8_bounds(int blocks_per_cu, int group_loads);
 #endif
 // knn.hip's last stage (lives in scan.hip to share the scan's summation order)
 ssw_status launch_knn_rescore(const float *X, int32_t dim, const int32_t *perm, int r0, int rows, const uint64_t *buf,
