@@ -129,6 +129,47 @@ ssw_status ssw_index_load_scores(ssw_index *idx, const float *scores_host);
 ssw_status ssw_index_topk(ssw_index *idx, const float *q_host, const int64_t *excluded_images,
                           int64_t n_excluded, int32_t k, int64_t *out_images, float *out_scores,
                           int64_t *out_best_rows, int32_t *out_count);
+/* Several queries in ONE pass over the rows.  The scan is bound by HBM: a row that sits in registers for one query
+ * scores a second, a fourth, a sixteenth one for almost no extra traffic.  At dim 512 and >= 65 536 rows (f32 and f16
+ * rows) a batch is cut into chunks of 16 queries for f32 rows and 8 for f16 rows (the widths with the lowest measured
+ * time per query), the remainder into chunks of 8, 4 and 2 and at last a single query, and every chunk is one launch
+ * of the multi-query scan kernel; the other dims (256, 768, 1024) and smaller indexes are served by one single-query
+ * scan launch per query.  Either way query b's scores are the BITS ssw_index_scan returns for q[b].  Any nq >= 1;
+ * nq == 1 IS the single-query call.
+ *
+ * ssw_index_scan_batch: scores[b, :] = vectors @ q[b].  q_host [nq, dim], out_scores_host [nq, n_rows] (may be NULL:
+ * nothing is copied back).  Afterwards the resident scores are those of the LAST query, as after ssw_index_scan(q[nq-1]).
+ *
+ * ssw_index_topk_batch: ssw_index_topk for nq queries.  Query b's excluded images are
+ * excluded_images[excluded_offsets[b] .. excluded_offsets[b+1]) (excluded_offsets [nq + 1]; NULL: no exclusions).
+ * Outputs are [nq, k] row-major (row b filled up to out_counts[b]); out_counts [nq].  Query b's row is exactly what
+ * ssw_index_topk(idx, q[b], its excluded list, k) returns -- images, best rows, score bits and count, the mass-tie
+ * case through the deep selection included.  One selection and one host wait per query.
+ * State afterwards: that of ssw_index_topk with the last query and its excluded list after a full scan -- the resident
+ * scores, the installed excluded set and the device result buffers are the last query's, so ssw_index_topk(q = NULL),
+ * ssw_index_gather_scores, ssw_index_rescore_avg and ssw_index_result_ptrs refer to it.
+ * Pruning (ssw_index_prune_stats): a batch of nq >= 2 always runs the full-precision scan; it never reads or builds
+ * the int8 shadow and leaves the prune counters alone.  It first completes a partial score buffer: right after a pruned
+ * single top-k that is one full scan of the previous query (31 ms at 100 M rows) before the batch starts.
+ * Measured on one MI355X ("Batched scan"; k = 100): one launch costs 1.04-1.07 x a single-query
+ * scan at 2 queries, 1.08-1.17 x at 4, 1.14-1.20 x (f32) at 8 and 1.57-1.68 x (f32) at 16.  Per query, against single
+ * calls that scan in full (f32 below 2^22 rows or a borrowed matrix; every f16 index), topk_batch takes 0.52-0.62 x
+ * at nq = 2, 0.27-0.40 x at 4, 0.15-0.32 x at 8 and, f32, 0.10-0.17 x at 16.  Where the single call is PRUNED (f32, >= 2^22 rows) the
+ * crossover is nq = 4: the batch is slower at nq = 2 (16.3 against 8.4 ms per query at 100 M rows), equal at 4 (8.46
+ * against 8.42; 1.17 against 1.19 at 12.5 M), faster from 8 on (4.6, and 3.2 at 16, against 8.4; 0.67 and 0.49 against
+ * 1.20).  Callers choose; nothing dispatches silently.
+ * Memory: the scores of a chunk's last query go to the handle's own buffer, the others to a side buffer of at most
+ * 15 x n_rows x 4 bytes (7 x for f16 rows) allocated by the first batched call and sized by the widest chunk it
+ * needed; if it cannot be allocated the call falls back to narrower chunks and in the end to one query at a time -- it
+ * does not fail.
+ * Errors, both before anything is enqueued: a non-finite component in any query is SSW_ERR_NUMERIC (the message
+ * names the query and the component); nq < 1, a NULL pointer, decreasing offsets or an excluded id out of range are
+ * SSW_ERR_INVALID.  ssw_index_profile records one event pair per scan launch, batched or not. */
+ssw_status ssw_index_scan_batch(ssw_index *idx, const float *q_host, int32_t nq, float *out_scores_host);
+ssw_status ssw_index_topk_batch(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
+                                const int64_t *excluded_offsets, int32_t k, int64_t *out_images, float *out_scores,
+                                int64_t *out_best_rows, int32_t *out_counts);
+
 /* device-resident form used by bench.py and the sharded index: q_dev [dim] f32;
  * the excluded set is whatever the last ssw_index_set_excluded installed; results
  * stay on the device in the handle's result buffers (ssw_index_result_ptrs).

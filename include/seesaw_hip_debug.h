@@ -23,6 +23,11 @@ extern "C" {
  * The f16 index's scan reads the same switches: at dim=512 0 u4, 1 u8+nt, 4 u2+nt, other = default u4+nt. */
 ssw_status ssw_tune_scan(int32_t variant, int32_t blocks_per_cu);
 
+/* The widest chunk of ssw_index_scan_batch / ssw_index_topk_batch: 1 (every query through the single-query scan), 2, 4,
+ * 8 or 16; any other value = the product's (16 for f32 rows, 8 for f16 rows).  All widths write identical bits.  blocks_per_cu: four-wave blocks per CU of the multi-query
+ * kernel (1 .. 8; any other value = the product's, 2).  tools/perf_topk_batch.py sweeps both. */
+ssw_status ssw_tune_scan_batch(int32_t max_width, int32_t blocks_per_cu);
+
 /* ssw_index_topk on an index of <= 8192 images / 65536 rows and <= 8192 excluded ids runs as three launches (query staged
  * through a kernel argument; scan; per-image max + exclusion + selection in one workgroup) with the ids and the result in
  * pinned memory the device maps -- no copies, no stream wait (flag bit 0).  From 2^24 values on and k <= 2048 the selection's threshold comes from a

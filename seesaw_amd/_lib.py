@@ -63,6 +63,9 @@ _SIGNATURES = {
     "ssw_index_load_scores": (c_i32, [c_void_p, c_void_p]),
     "ssw_index_topk": (c_i32, [c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_void_p, c_void_p,
                                c_void_p, c_i32_p]),
+    "ssw_index_scan_batch": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p]),
+    "ssw_index_topk_batch": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p,
+                                     c_void_p]),
     "ssw_index_set_excluded": (c_i32, [c_void_p, c_void_p, c_i64]),
     "ssw_index_topk_dev": (c_i32, [c_void_p, c_void_p, c_i32]),
     "ssw_index_set_tile_meta": (c_i32, [c_void_p, c_void_p, c_void_p]),
@@ -149,6 +152,7 @@ _SIGNATURES = {
 # include/seesaw_hip_debug.h: the lab build's extra entry points (libseesaw_hip_debug.so only)
 _DEBUG_SIGNATURES = {
     "ssw_tune_scan": (c_i32, [c_i32, c_i32]),
+    "ssw_tune_scan_batch": (c_i32, [c_i32, c_i32]),
     "ssw_tune_topk": (c_i32, [c_i32]),
     "ssw_tune_prune": (c_i32, [c_i32, c_i64, c_i64]),
     "ssw_tune_prune_scan": (c_i32, [c_i32, c_i32]),

@@ -127,6 +127,12 @@ struct ssw_index {
     float *q_last = nullptr;                         // [dim] the query of the last pruned scan
     bool scores_partial = false;                     // scores hold exact values for the survivors only (materialise)
     int64_t prune_last = 0, prune_queries = 0, prune_fallbacks = 0;
+    // batched scan (ssw_index_scan_batch / ssw_index_topk_batch): the queries of one chunk, and the score slabs of all
+    // but its last query (that one's slab is `scores`); allocated by the first batched call
+    float *qb_dev = nullptr;                         // [BATCH_MAX_WIDTH, dim]
+    PinnedStage qb_stage;
+    float *side = nullptr;                           // [side_slabs, slab_stride]
+    int side_slabs = 0;
     // profiling of the scan kernel
     bool profiling = false;
     std::vector<hipEvent_t> ev;  // pairs
@@ -359,6 +365,9 @@ ssw_status ssw_index_destroy(ssw_index *idx) {
     (void)hipFree(idx->scores);
     (void)hipFree(idx->q_dev);
     idx->q_stage.release();
+    (void)hipFree(idx->qb_dev);
+    (void)hipFree(idx->side);
+    idx->qb_stage.release();
     (void)hipFree(idx->tile_boxes);
     (void)hipFree(idx->tile_zoom);
     (void)hipFree(idx->rs_pos);
@@ -1159,6 +1168,182 @@ ssw_status ssw_index_topk(ssw_index *idx, const float *q_host, const int64_t *ex
     return ssw_index_topk_fetch(idx, k, out_images, out_scores, out_best_rows, out_count);
 }
 
+// ---- several queries in one pass over the rows (scan.hip: batch_scores_kernel) --------------------------------------
+// A batch is cut into chunks of the widest kernel form the shape and the side buffer allow, the remainder into
+// narrower ones and at last single queries.  A chunk's last query scores into the handle's own buffer, the others into
+// the side slabs; the selection then runs slab by slab through the single-query path with `scores` pointing at the slab.
+constexpr int BATCH_MAX_WIDTH = 16;
+
+static int64_t slab_stride(const ssw_index *idx) { return (idx->n + 64 + 63) & ~(int64_t)63; }  // slabs stay 256-byte aligned
+
+// the chunk width to use for nq queries: limited by the shape, by nq and by what the side buffer could be grown to
+static ssw_status batch_width(ssw_index *idx, int32_t nq, int *out_w) {
+    int w = scan_batch_max_width(idx->n, idx->dim, idx->dtype);
+    if (w > BATCH_MAX_WIDTH) w = BATCH_MAX_WIDTH;
+    while (w > nq) w >>= 1;
+    if (w >= 2 && !idx->qb_dev) {
+        if (hipMalloc((void **)&idx->qb_dev, (size_t)BATCH_MAX_WIDTH * idx->dim * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            idx->qb_dev = nullptr;
+            w = 1;
+        }
+    }
+    while (w >= 2 && idx->side_slabs < w - 1) {  // grow; on failure keep halving the width
+        SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+        (void)hipFree(idx->side);
+        idx->side = nullptr;
+        idx->side_slabs = 0;
+        if (hipMalloc((void **)&idx->side, (size_t)(w - 1) * slab_stride(idx) * sizeof(float)) == hipSuccess) {
+            idx->side_slabs = w - 1;
+        } else {
+            (void)hipGetLastError();
+            idx->side = nullptr;
+            w >>= 1;
+        }
+    }
+    *out_w = w < 1 ? 1 : w;
+    return SSW_OK;
+}
+
+// queries [w, dim] (host) -> one launch that fills slab[j] = scores of query j; slab[w - 1] is the handle's buffer
+static ssw_status do_scan_chunk(ssw_index *idx, const float *q_host, int w, float **slab) {
+    for (int j = 0; j + 1 < w; ++j) slab[j] = idx->side + (int64_t)j * slab_stride(idx);
+    slab[w - 1] = idx->scores;
+    SSW_TRY(idx->qb_stage.push(idx->qb_dev, q_host, (size_t)w * idx->dim * sizeof(float), idx->stream));
+    idx->scores_partial = false;
+    const bool prof = idx->profiling && idx->ev_used + 2 <= (int)idx->ev.size();
+    if (prof) SSW_HIP_TRY(hipEventRecord(idx->ev[idx->ev_used], idx->stream));
+    SSW_TRY(launch_scan_batch(idx->X, idx->dtype, idx->qb_dev, slab, w, idx->n, idx->dim, idx->device, idx->stream));
+    if (prof) {
+        SSW_HIP_TRY(hipEventRecord(idx->ev[idx->ev_used + 1], idx->stream));
+        idx->ev_used += 2;
+    }
+    return SSW_OK;
+}
+
+static ssw_status check_query_batch(const ssw_index *idx, const float *q_host, int32_t nq) {
+    for (int32_t b = 0; b < nq; ++b) {
+        for (int i = 0; i < idx->dim; ++i) {
+            if (!std::isfinite(q_host[(size_t)b * idx->dim + i])) {
+                set_error("query %d of the batch has a non-finite component at %d", b, i);
+                return SSW_ERR_NUMERIC;
+            }
+        }
+    }
+    return SSW_OK;
+}
+
+// the selection half of ssw_index_topk over the scores in `slab` (which may be the handle's own buffer)
+static ssw_status select_slab(ssw_index *idx, float *slab, const int64_t *excluded_images, int64_t n_excluded, int32_t k,
+                              int64_t *out_images, float *out_scores, int64_t *out_best_rows, int32_t *out_count) {
+    struct Swap {  // every kernel of the selection (and the deep rerun of the fetch) reads idx->scores
+        ssw_index *idx;
+        float *keep;
+        Swap(ssw_index *i, float *s) : idx(i), keep(i->scores) { idx->scores = s; }
+        ~Swap() { idx->scores = keep; }
+    } swap(idx, slab);
+    if (small_path_ok(idx, n_excluded))
+        return topk_small(idx, nullptr, excluded_images, n_excluded, k, out_images, out_scores, out_best_rows, out_count);
+    if (idx->n_images == 0) return SSW_OK;
+    SSW_TRY(ssw_index_set_excluded(idx, excluded_images, n_excluded));
+    SSW_TRY(arm_host_result(idx));
+    const ssw_status st = do_select(idx, k);
+    if (st != SSW_OK) {
+        idx->ws.host_packed = nullptr;
+        idx->res_pending_seq = 0;
+        return st;
+    }
+    return ssw_index_topk_fetch(idx, k, out_images, out_scores, out_best_rows, out_count);
+}
+
+ssw_status ssw_index_scan_batch(ssw_index *idx, const float *q_host, int32_t nq, float *out_scores_host) {
+    SSW_REQUIRE(nq >= 1, "nq=%d < 1", nq);
+    SSW_REQUIRE(idx != nullptr && q_host != nullptr, "NULL argument");
+    SSW_TRY(check_query_batch(idx, q_host, nq));
+    if (nq == 1) return ssw_index_scan(idx, q_host, out_scores_host);
+    DeviceGuard guard(idx->device);
+    int W = 1;
+    SSW_TRY(batch_width(idx, nq, &W));
+    const size_t dim = (size_t)idx->dim, row_bytes = (size_t)idx->n * sizeof(float);
+    for (int32_t b = 0; b < nq;) {
+        int w = W;
+        while (w > nq - b) w >>= 1;
+        float *slab[BATCH_MAX_WIDTH];
+        if (w >= 2) {
+            SSW_TRY(do_scan_chunk(idx, q_host + b * dim, w, slab));
+        } else {
+            w = 1;
+            slab[0] = idx->scores;
+            SSW_TRY(idx->q_stage.push(idx->q_dev, q_host + b * dim, dim * sizeof(float), idx->stream));
+            SSW_TRY(do_scan(idx, idx->q_dev));
+        }
+        if (out_scores_host && idx->n > 0) {
+            for (int j = 0; j < w; ++j)
+                SSW_HIP_TRY(hipMemcpyAsync(out_scores_host + (size_t)(b + j) * idx->n, slab[j], row_bytes,
+                                           hipMemcpyDeviceToHost, idx->stream));
+        }
+        b += w;
+    }
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+    return SSW_OK;
+}
+
+ssw_status ssw_index_topk_batch(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
+                                const int64_t *excluded_offsets, int32_t k, int64_t *out_images, float *out_scores,
+                                int64_t *out_best_rows, int32_t *out_counts) {
+    SSW_REQUIRE(nq >= 1, "nq=%d < 1", nq);
+    SSW_REQUIRE(idx != nullptr && q_host != nullptr && out_counts != nullptr, "NULL argument");
+    SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
+    if (excluded_offsets) {
+        SSW_REQUIRE(excluded_offsets[0] >= 0, "excluded_offsets[0]=%lld < 0", (long long)excluded_offsets[0]);
+        for (int32_t b = 0; b < nq; ++b)
+            SSW_REQUIRE(excluded_offsets[b] <= excluded_offsets[b + 1], "excluded_offsets decrease at query %d", b);
+        SSW_REQUIRE(excluded_offsets[nq] == excluded_offsets[0] || excluded_images != nullptr, "excluded_images is NULL");
+        for (int64_t i = excluded_offsets[0]; i < excluded_offsets[nq]; ++i)
+            SSW_REQUIRE(excluded_images[i] >= 0 && excluded_images[i] < idx->n_images,
+                        "excluded image %lld outside [0, %lld)", (long long)excluded_images[i], (long long)idx->n_images);
+    }
+    SSW_TRY(check_query_batch(idx, q_host, nq));
+    for (int32_t b = 0; b < nq; ++b) out_counts[b] = 0;
+    auto excl = [&](int32_t b, int64_t *n_ex) -> const int64_t * {
+        *n_ex = excluded_offsets ? excluded_offsets[b + 1] - excluded_offsets[b] : 0;
+        return *n_ex > 0 ? excluded_images + excluded_offsets[b] : nullptr;
+    };
+    if (nq == 1) {  // the single call itself, pruning included
+        int64_t n_ex = 0;
+        const int64_t *ex = excl(0, &n_ex);
+        return ssw_index_topk(idx, q_host, ex, n_ex, k, out_images, out_scores, out_best_rows, out_counts);
+    }
+    DeviceGuard guard(idx->device);
+    SSW_TRY(ensure_full_scores(idx));
+    int W = 1;
+    SSW_TRY(batch_width(idx, nq, &W));
+    const size_t dim = (size_t)idx->dim;
+    for (int32_t b = 0; b < nq;) {
+        int w = W;
+        while (w > nq - b) w >>= 1;
+        float *slab[BATCH_MAX_WIDTH];
+        if (w >= 2) {
+            SSW_TRY(do_scan_chunk(idx, q_host + b * dim, w, slab));
+        } else {  // one query: the full single-query scan (never the pre-scan) into the handle's buffer
+            w = 1;
+            slab[0] = idx->scores;
+            SSW_TRY(stage_query(idx, q_host + b * dim));
+            SSW_TRY(do_scan(idx, idx->q_dev));
+        }
+        for (int j = 0; j < w; ++j) {
+            int64_t n_ex = 0;
+            const int64_t *ex = excl(b + j, &n_ex);
+            const size_t o = (size_t)(b + j) * k;
+            SSW_TRY(select_slab(idx, slab[j], ex, n_ex, k, out_images ? out_images + o : nullptr,
+                                out_scores ? out_scores + o : nullptr, out_best_rows ? out_best_rows + o : nullptr,
+                                out_counts + b + j));
+        }
+        b += w;
+    }
+    return SSW_OK;
+}
+
 static ssw_status stage_rows(ssw_index *idx, const int64_t *rows_host, int64_t n) {
     for (int64_t i = 0; i < n; ++i) {
         SSW_REQUIRE(rows_host[i] >= 0 && rows_host[i] < idx->n, "row %lld outside [0, %lld)",
@@ -1291,6 +1476,11 @@ ssw_status ssw_tune_topk(int32_t flags) {
 
 ssw_status ssw_tune_scan(int32_t variant, int32_t blocks_per_cu) {
     tune_scan(variant, blocks_per_cu);
+    return SSW_OK;
+}
+
+ssw_status ssw_tune_scan_batch(int32_t max_width, int32_t blocks_per_cu) {
+    tune_scan_batch(max_width, blocks_per_cu);
     return SSW_OK;
 }
 

@@ -152,19 +152,35 @@ __device__ __forceinline__ float dot_frag(const RowFrag<C> &x, const RowFrag<C> 
     return a.x + a.y;
 }
 
+// all-ones where the lane has bit `off` set, as a plain lane value the optimiser cannot turn back into a lane mask
+__device__ __forceinline__ unsigned lane_bit_mask(int lane, int off) {
+    unsigned m = (lane & off) ? 0xffffffffu : 0u;
+    asm volatile("" : "+v"(m));
+    return m;
+}
+// m all-ones: b, m zero: a (one v_bfi_b32)
+__device__ __forceinline__ float pick(unsigned m, float a, float b) {
+    return __uint_as_float((__float_as_uint(b) & m) | (__float_as_uint(a) & ~m));
+}
+
 // U lane-partial registers (acc[j] = row j of the group) -> every lane l holds the
 // complete sum of row (l % U): transpose-reduce over offsets 1..U/2, then butterfly
 // over offsets U..32.  Canonical offset order 1,2,4,8,16,32 for every U.
-template <int U>
+// BITSEL: the keep / send choice as bit selects on a per-lane mask instead of selects on a lane mask in SGPRs.  Same
+// values.  The multi-query kernel's 8- and 16-register sets need it: the optimiser merged their select trees into chains
+// over 2^k combined lane masks, which no longer fit the SGPRs and were spilled into VGPR lanes (v_readlane + s_nop per
+// select: 80 a group at 8 registers).
+template <int U, bool BITSEL = false>
 __device__ __forceinline__ float group_reduce(float (&acc)[U], int lane) {
 #pragma unroll
     for (int off = 1; off < U; off <<= 1) {
         // register distance of the pair merged at this offset == off
         const bool upper = (lane & off) != 0;
+        const unsigned m = BITSEL ? lane_bit_mask(lane, off) : 0u;
 #pragma unroll
         for (int i = 0; i < U; i += 2 * off) {
-            const float keep = upper ? acc[i + off] : acc[i];
-            const float send = upper ? acc[i] : acc[i + off];
+            const float keep = BITSEL ? pick(m, acc[i], acc[i + off]) : (upper ? acc[i + off] : acc[i]);
+            const float send = BITSEL ? pick(m, acc[i + off], acc[i]) : (upper ? acc[i] : acc[i + off]);
             acc[i] = keep + __shfl_xor(send, off, 64);
         }
     }
@@ -226,6 +242,109 @@ __global__ __launch_bounds__(256) void scan_scores_kernel(const typename R::T *_
             cur = nxt;
         }
         if (row0 + lane < n) scores[row0 + lane] = out;
+    }
+}
+
+// Multi-query form of the streaming kernel: the rows are walked exactly as above (persistent grid, 64-row batches,
+// groups of U rows, non-temporal 16-byte loads, register double buffer), but a lane holds the fragments of B queries
+// and forms B lane partials per row, so one pass over the rows in HBM scores B queries.  Per query the two fma chains
+// of dot_frag and the offset order 1, 2, 4, 8, 16, 32 of the lane sum are the single-query kernel's: slab b receives
+// the BITS scan_scores_kernel writes for query b.
+//   * the V = U*B (row, query) partials of a group are ONE register set for group_reduce (item u + U*b): V - 1
+//     exchanges of the transpose-reduce and log2(64 / V) butterfly steps leave lane l with the finished score of row
+//     l % U for query (l / U) % B -- 10 exchanges per two rows at U = 2, B = 4 where four butterflies take 24.
+//   * every value exists 64 / V times; lane l keeps, into register t, the value of group s*B + t for s = l / V.  After
+//     the 64 / U groups of a batch lane l = s*V + b*U + u holds rows s*V + t*U + u (t < B) of query b: a B x B
+//     transpose between register index and lane bits (B/2 * log2(B) exchanges per 64 rows) gives lane l row l of
+//     every query, and the wave stores one coalesced 256-byte line per slab.
+// (The name carries no "scan": tests/test_index_f16_cpu.py pins the kernels so named to the three single-query ones;
+//  tests/test_topk_batch_cpu.py asserts for this kernel what that test asserts for them.)
+template <int B>
+struct ScoreSlabs {
+    float *p[B];
+};
+
+template <class R, int C, int U, int B, bool NT>
+__global__ __launch_bounds__(256) void batch_scores_kernel(const typename R::T *__restrict__ X,
+                                                               const float *__restrict__ q,  // [B, 256*C]
+                                                               ScoreSlabs<B> out, int n) {
+    constexpr int V = U * B;
+    static_assert(V <= 64 && (B & (B - 1)) == 0 && (U & (U - 1)) == 0, "U*B (row, query) partials share one wave-wide reduce");
+    constexpr int GPB = 64 / U;  // groups per batch
+    constexpr int T = B <= 4 ? B : 4;  // groups unrolled per trip
+    const int lane = threadIdx.x & 63;
+    const int gwave = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int nwaves = gridDim.x * 4;
+    const int nbatches = (n + 63) >> 6;
+    const int last = n - 1;
+    if (gwave >= nbatches) return;
+
+    RowFrag<C> qf[B];
+#pragma unroll
+    for (int b = 0; b < B; ++b) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) qf[b].v[c] = reinterpret_cast<const float4 *>(q)[(b * C + c) * 64 + lane];
+    }
+
+    const int my_run = lane / V;
+    Group<R, C, U> cur, nxt;
+    load_group<R, C, U, NT>(cur, X, gwave << 6, last, lane);
+    for (int bt = gwave; bt < nbatches; bt += nwaves) {
+        const int row0 = bt << 6;
+        const int nb = bt + nwaves;
+        const int next0 = (nb < nbatches ? nb : bt) << 6;  // no next batch: re-touch own rows
+        float o[B];
+#pragma unroll
+        for (int t = 0; t < B; ++t) o[t] = 0.0f;
+        // T groups are unrolled inside a rolled loop, so that a group's value goes to a register chosen at compile time
+        // (T = B up to 4; a runtime slot costs B selects and B live lane masks a group, which at 16 partials spilled
+        // SGPRs into VGPR lanes).  All B groups unrolled is 64 KiB of code at B = 8, more than the instruction cache.
+        // The scheduling barriers keep a group's arithmetic behind the request for the next group and ahead of the one
+        // after: without them the two groups' fma chains were interleaved and every trip waited for vmcnt(0).
+#pragma unroll 1
+        for (int s = 0; s < GPB / T; ++s) {
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                const int g = s * T + t;
+                const int nrow = (g + 1 < GPB) ? row0 + (g + 1) * U : next0;
+                load_group<R, C, U, NT>(nxt, X, nrow, last, lane);
+                __builtin_amdgcn_sched_barrier(0);
+                float acc[V];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const RowFrag<C> x = R::widen(cur.r[u]);
+#pragma unroll
+                    for (int b = 0; b < B; ++b) acc[b * U + u] = dot_frag<C>(x, qf[b]);
+                }
+                const float v = group_reduce<V, true>(acc, lane);
+                const bool mine = my_run == s / (B / T);
+#pragma unroll
+                for (int j = 0; j < B / T; ++j) {
+                    const bool here = (B == T) || (s % (B / T)) == j;  // wave-uniform
+                    unsigned m = (mine && here) ? 0xffffffffu : 0u;
+                    asm volatile("" : "+v"(m));
+                    o[t + T * j] = pick(m, o[t + T * j], v);
+                }
+                cur = nxt;
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        // register t <-> query bits of the lane
+#pragma unroll
+        for (int off = 1; off < B; off <<= 1) {
+            const unsigned m = lane_bit_mask(lane, U * off);  // (my_q & off) != 0
+#pragma unroll
+            for (int i = 0; i < B; ++i) {
+                if ((i & off) != 0) continue;
+                const float got = __shfl_xor(pick(m, o[i + off], o[i]), U * off, 64);
+                o[i] = pick(m, o[i], got);
+                o[i + off] = pick(m, got, o[i + off]);
+            }
+        }
+        if (row0 + lane < n) {
+#pragma unroll
+            for (int b = 0; b < B; ++b) out.p[b][row0 + lane] = o[b];
+        }
     }
 }
 
@@ -397,6 +516,32 @@ ssw_status launch_scan_t(const void *Xv, const float *q, float *scores, int64_t 
     return SSW_OK;
 }
 
+// Batch widths are compile-time: 2, 4, 8 and 16.  The widest one the product uses is, per row format, the width with
+// the lowest measured time per query (docs/EXPERIMENTS.md): 16 for f32 rows, 8 for f16 rows, with
+// two four-wave blocks per CU (the second block hides what one wave's exchange chain leaves idle).
+constexpr int SCAN_BATCH_MAX_F32 = 16, SCAN_BATCH_MAX_F16 = 8;
+constexpr int SCAN_BATCH_BLOCKS_PER_CU = 2;
+SSW_TUNABLE int g_scan_batch_max = -1;  // tuning hook (ssw_tune_scan_batch): -1 = the product's widths
+SSW_TUNABLE int g_scan_batch_blocks_per_cu = SCAN_BATCH_BLOCKS_PER_CU;  // the same hook: four-wave blocks per CU
+
+template <class R, int C, int U, int B>
+ssw_status launch_scan_batch_t(const void *Xv, const float *qb, float *const *slabs, int64_t n, int device,
+                               hipStream_t stream) {
+    const typename R::T *X = static_cast<const typename R::T *>(Xv);
+    ScoreSlabs<B> out;
+    for (int b = 0; b < B; ++b) out.p[b] = slabs[b];
+    const int per_cu = g_scan_batch_blocks_per_cu;
+    const int64_t nbatches = (n + 63) >> 6;
+    int64_t grid = (int64_t)num_cus(device) * per_cu;
+    const int64_t need = (nbatches + 3) / 4;
+    if (grid > need) grid = need;
+    if (grid < 1) grid = 1;
+    hipLaunchKernelGGL((batch_scores_kernel<R, C, U, B, true>), dim3((unsigned)grid), dim3(256), 0, stream, X, qb,
+                       out, (int)n);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
 template <class R>
 ssw_status launch_score_rows_t(const void *Xv, const float *q_dev, const int64_t *rows_dev, int64_t n, int32_t dim,
                                float *out, hipStream_t stream) {
@@ -452,6 +597,42 @@ ssw_status launch_scan(const void *X, int32_t dtype, const float *q_dev, float *
         }
     }
     set_error("scan: dim=%d unsupported (need a multiple of 256, <= 1024)", dim);
+    return SSW_ERR_UNSUPPORTED;
+}
+
+// The widest batch launch_scan_batch takes for this shape: the multi-query kernel serves dim 512 from the streaming
+// kernel's range on; 1 = every query goes through launch_scan.
+int scan_batch_max_width(int64_t n, int32_t dim, int32_t dtype) {
+    if (dim != 512 || n < SCAN_SMALL_ROWS || n >= (int64_t)0x7fff0000) return 1;
+    if (g_scan_batch_max > 0) return g_scan_batch_max;
+    return dtype == SSW_DTYPE_F16 ? SCAN_BATCH_MAX_F16 : SCAN_BATCH_MAX_F32;
+}
+
+// slabs[b][i] = <X[i,:], qb[b,:]> for b < nb (a power of two, 2 <= nb <= scan_batch_max_width): the bits of launch_scan
+// per query
+ssw_status launch_scan_batch(const void *X, int32_t dtype, const float *qb_dev, float *const *slabs, int32_t nb,
+                             int64_t n, int32_t dim, int device, hipStream_t stream) {
+    if (n <= 0) return SSW_OK;
+    if (nb < 2 || nb > scan_batch_max_width(n, dim, dtype)) {
+        set_error("scan_batch: a batch of %d queries over %lld rows of dim %d has no kernel", nb, (long long)n, dim);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    const bool h16 = dtype == SSW_DTYPE_F16;
+    switch (nb) {
+        case 2:
+            return h16 ? launch_scan_batch_t<H16Rows, 2, 4, 2>(X, qb_dev, slabs, n, device, stream)
+                       : launch_scan_batch_t<F32Rows, 2, 2, 2>(X, qb_dev, slabs, n, device, stream);
+        case 4:
+            return h16 ? launch_scan_batch_t<H16Rows, 2, 4, 4>(X, qb_dev, slabs, n, device, stream)
+                       : launch_scan_batch_t<F32Rows, 2, 2, 4>(X, qb_dev, slabs, n, device, stream);
+        case 8:
+            return h16 ? launch_scan_batch_t<H16Rows, 2, 4, 8>(X, qb_dev, slabs, n, device, stream)
+                       : launch_scan_batch_t<F32Rows, 2, 2, 8>(X, qb_dev, slabs, n, device, stream);
+        case 16:
+            return h16 ? launch_scan_batch_t<H16Rows, 2, 4, 16>(X, qb_dev, slabs, n, device, stream)
+                       : launch_scan_batch_t<F32Rows, 2, 2, 16>(X, qb_dev, slabs, n, device, stream);
+    }
+    set_error("scan_batch: width %d has no kernel in this build", nb);
     return SSW_ERR_UNSUPPORTED;
 }
 
@@ -550,6 +731,11 @@ void tune_scan(int variant, int blocks_per_cu) {
     if (variant < -1) variant = -1;
     g_scan_variant = variant;
     g_scan_blocks_per_cu = blocks_per_cu;
+}
+void tune_scan_batch(int max_width, int blocks_per_cu) {
+    g_scan_batch_max = (max_width == 1 || max_width == 2 || max_width == 4 || max_width == 8 || max_width == 16)
+                           ? max_width : -1;
+    g_scan_batch_blocks_per_cu = (blocks_per_cu >= 1 && blocks_per_cu <= 8) ? blocks_per_cu : SCAN_BATCH_BLOCKS_PER_CU;
 }
 #endif
 

@@ -159,6 +159,11 @@ ssw_status launch_scan(const void *X, int32_t dtype, const float *q_dev, float *
                        int device, hipStream_t stream);
 ssw_status launch_score_rows(const void *X, int32_t dtype, const float *q_dev, const int64_t *rows_dev, int64_t n,
                              int32_t dim, float *out, hipStream_t stream);
+// the multi-query form: slabs[b][i] = dot(X[i,:], qb_dev[b,:]) for b < nb in ONE pass over the rows, per query the bits
+// of launch_scan.  nb = 2, 4, 8 or 16, at most scan_batch_max_width(n, dim, dtype) (1 = this shape has no batched kernel)
+int scan_batch_max_width(int64_t n, int32_t dim, int32_t dtype);
+ssw_status launch_scan_batch(const void *X, int32_t dtype, const float *qb_dev, float *const *slabs, int32_t nb,
+                             int64_t n, int32_t dim, int device, hipStream_t stream);
 // prune.hip: the int8 shadow of an f32 index and the certified pre-scan of the exact top-k (see prune.hip).
 // query state words: [0] survivors, [1] Q = ||q|| rounded up (f32 bits), [2] 1 = the query cannot be bounded
 bool q8_dim_supported(int32_t dim);
@@ -182,6 +187,7 @@ ssw_status launch_gather_rows(const void *X, int32_t dtype, const int64_t *rows_
                               int32_t dim, float *out, hipStream_t stream);
 #ifdef SSW_DEBUG_HOOKS
 void tune_scan(int variant, int blocks_per_cu);
+void tune_scan_batch(int max_width, int blocks_per_cu);
 void tune_q8_bounds(int blocks_per_cu, int group_loads);
 #endif
 // knn.hip's last stage (lives in scan.hip to share the scan's summation order)

@@ -178,6 +178,53 @@ class DeviceIndex:
         c = cnt.value
         return imgs[:c], scs[:c], rows[:c]
 
+    def _queries(self, Q) -> np.ndarray:
+        Q = np.asarray(Q)
+        if Q.ndim == 1:
+            Q = Q.reshape(1, -1)
+        Q = np.ascontiguousarray(Q.reshape(Q.shape[0], -1), dtype=np.float32)
+        if Q.shape[0] < 1 or Q.shape[1] != self.dim:
+            raise ValueError(f"queries must be [nq >= 1, {self.dim}], got {Q.shape}")
+        return Q
+
+    @staticmethod
+    def _excluded_batch(excluded, nq: int):
+        """None, or nq iterables (each may be None) -> (ids int64 or None, offsets int64 [nq + 1] or None)"""
+        if excluded is None:
+            return None, None
+        lists = list(excluded)
+        if len(lists) != nq:
+            raise ValueError(f"excluded has {len(lists)} lists for {nq} queries")
+        arrs = [np.empty(0, dtype=np.int64) if e is None else np.fromiter(e, dtype=np.int64) for e in lists]
+        offsets = np.zeros(nq + 1, dtype=np.int64)
+        np.cumsum([a.shape[0] for a in arrs], out=offsets[1:])
+        ids = np.ascontiguousarray(np.concatenate(arrs)) if offsets[-1] else None
+        return ids, offsets
+
+    def scores_batch(self, Q: np.ndarray) -> np.ndarray:
+        """[nq, n_rows] f32: row b is the bits of `scores(Q[b])`, all from one pass over the rows per chunk of queries
+        (ssw_index_scan_batch).  The resident scores are then those of the last query."""
+        Q = self._queries(Q)
+        out = np.empty((Q.shape[0], self.n_rows), dtype=np.float32)
+        _lib.call("ssw_index_scan_batch", self._h, _ptr(Q), Q.shape[0], _ptr(out))
+        return out
+
+    def topk_batch(self, Q: np.ndarray, k: int, excluded=None):
+        """`[topk(Q[b], k, excluded[b]) for b]` with the rows read once per chunk of queries (ssw_index_topk_batch):
+        a list of (images, scores, rows), bit for bit what the single calls return.  `excluded` is None or a sequence of
+        nq iterables of image positions, each of which may be None.  The handle is left as after the last query's topk."""
+        k = int(k)
+        Q = self._queries(Q)
+        nq = Q.shape[0]
+        ids, offsets = self._excluded_batch(excluded, nq)
+        imgs = np.empty((nq, k), dtype=np.int64)
+        scs = np.empty((nq, k), dtype=np.float32)
+        rows = np.empty((nq, k), dtype=np.int64)
+        cnt = np.zeros(nq, dtype=np.int32)
+        _lib.call("ssw_index_topk_batch", self._h, _ptr(Q), nq, _ptr(ids), _ptr(offsets), k, _ptr(imgs), _ptr(scs),
+                  _ptr(rows), _ptr(cnt))
+        return [(imgs[b, :c].copy(), scs[b, :c].copy(), rows[b, :c].copy()) for b, c in enumerate(cnt.tolist())]
+
     def load_scores(self, scores: np.ndarray):
         """overwrite the resident per-row scores (f32; -inf rows are never selected)."""
         s = np.ascontiguousarray(scores, dtype=np.float32)

@@ -91,6 +91,35 @@ class CoarseIndex(AccessMethod):
         return {"dbidxs": ret, "nextstartk": len(exclude) + ret.shape[0],
                 "activations": ActivationFrames(boxes, ret, np.asarray(scores))}
 
+    def query_batch(self, *, topk, vectors, excludes=None, **kwargs):
+        """one `DeviceIndex.topk_batch` call for the vectors that are given: the list of dicts `query` returns, entry by
+        entry identical to it.  A `None` vector (random order) and a query whose exclude set covers the whole index
+        keep going through `query`."""
+        vectors = list(vectors)
+        excludes = [None] * len(vectors) if excludes is None else list(excludes)
+        if len(excludes) != len(vectors):
+            raise ValueError(f"excludes has {len(excludes)} entries for {len(vectors)} vectors")
+        out = [None] * len(vectors)
+        n = self._dbidx.shape[0]
+        excl_pos = [_positions_of(self._dbidx, np.asarray(BitMap() if e is None else e, dtype=np.int64)) for e in excludes]
+        batch = [i for i, v in enumerate(vectors) if v is not None and excl_pos[i].shape[0] < n]
+        for i in range(len(vectors)):
+            if i not in batch:
+                out[i] = self.query(topk=topk, vector=vectors[i], exclude=excludes[i], **kwargs)
+        if batch:
+            Q = np.stack([np.asarray(vectors[i], dtype=np.float32).reshape(-1) for i in batch])
+            # one k for the launch; every query keeps its own min(topk, included) results
+            ks = [min(int(topk), n - excl_pos[i].shape[0]) for i in batch]
+            res = self._dev.topk_batch(Q, max(ks), excluded=[excl_pos[i] for i in batch])
+            for i, k_i, (pos, scores, _) in zip(batch, ks, res):
+                ret = self._dbidx[pos[:k_i]]
+                assert ret.shape[0] == k_i
+                boxes = np.tile(np.array([[0, 0, 224, 224]], dtype=np.int64), (ret.shape[0], 1))
+                n_excl = 0 if excludes[i] is None else len(excludes[i])
+                out[i] = {"dbidxs": ret, "nextstartk": n_excl + ret.shape[0],
+                          "activations": ActivationFrames(boxes, ret, np.asarray(scores[:k_i]))}
+        return out
+
     def new_query(self):
         return CoarseQuery(self)
 

@@ -84,6 +84,16 @@ class AccessMethod:
     # subset(BitMap of dbidxs) -> AccessMethod over those images only
     subset = _not_here("subset")
 
+    def query_batch(self, *, topk, vectors, excludes=None, **kwargs):
+        """`[query(vector=v, topk=topk, exclude=e, **kwargs) for v, e in zip(vectors, excludes)]`.  `excludes` is None
+        or one exclude set (or None) per vector.  This default asks one query at a time; an index whose device path
+        scores several queries in one pass over its rows overrides it (CoarseIndex)."""
+        vectors = list(vectors)
+        excludes = [None] * len(vectors) if excludes is None else list(excludes)
+        if len(excludes) != len(vectors):
+            raise ValueError(f"excludes has {len(excludes)} entries for {len(vectors)} vectors")
+        return [self.query(topk=topk, vector=v, exclude=e, **kwargs) for v, e in zip(vectors, excludes)]
+
     def get_knng_path(self, name: str = None) -> str:
         """directory of a named k-NN graph of this index (`forward.parquet` inside)"""
         return f"{self.path}/knn_graph/{name or ''}"

@@ -319,6 +319,12 @@ class MultiscaleIndex(AccessMethod):
         return np.concatenate([np.arange(self._row_start[p], self._row_start[p + 1]) for p in positions]) \
             if positions.size else np.zeros(0, dtype=np.int64)
 
+    def query_batch(self, *, topk, vectors, excludes=None, **kwargs):
+        """the per-query loop of AccessMethod.query_batch, on purpose: the second stage (rescore_avg) reads the
+        RESIDENT tile scores of its own query, and DeviceIndex.topk_batch leaves only the last query's resident.
+        A device batch here needs the aggregation to read a selectable score slab -- a follow-up."""
+        return super().query_batch(topk=topk, vectors=vectors, excludes=excludes, **kwargs)
+
     def query(self, *, vector, vector2=None, topk, shortlist_size, exclude=None, force_exact=False, **kwargs):
         if shortlist_size is None:
             shortlist_size = topk * 5

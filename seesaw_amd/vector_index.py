@@ -45,3 +45,9 @@ class VectorIndex:
         assert vector.shape == (1, 512) or vector.shape == (512,)
         ids, scores, _ = self._dev.topk(vector, min(int(top_k), self.n))
         return ids, scores
+
+    def query_batch(self, vectors, top_k):
+        """`[query(v, top_k) for v in vectors]` from one pass over the rows per chunk of queries: vectors [nq, 512]"""
+        vectors = np.asarray(vectors)
+        assert vectors.ndim == 2 and vectors.shape[1] == 512
+        return [(ids, scores) for ids, scores, _ in self._dev.topk_batch(vectors, min(int(top_k), self.n))]

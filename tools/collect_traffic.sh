@@ -9,6 +9,8 @@ OUT=${1:-gpurun_out/collect}
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$OLDPWD"
 export PYTHONPATH=.
+# the record is of the full f32 scan kernel; the bench's top-k is pruned from 2^22 rows on and would never launch it
+export SSW_TOPK_FULL_SCAN=1
 for ROWS in 100000000 50000000 25000000 12500000; do
     SUF="_$ROWS"; [ "$ROWS" = 100000000 ] && SUF=""
     rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/bench_fetch$SUF" -o bench -- \
