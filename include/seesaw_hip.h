@@ -68,9 +68,10 @@ ssw_status ssw_index_create(int32_t device, int64_t n_rows, int32_t dim,
 /* Element type of the resident matrix.  SSW_DTYPE_F16 stores every element as IEEE binary16, rounded to nearest
  * even (subnormals kept, overflow to +-inf: numpy's astype(float16)), in a private lane-interleaved row layout
  * (dim * 2 bytes a row).  Every operation on an f16 index returns the bits the same operation returns on an f32 index
- * of the widened rows: the query stays f32, products and sums are f32 in the f32 scan's order.  Entries that read the
- * matrix as f32 through the handle and have no f16 form (ssw_knn_build, ssw_xlx) return SSW_ERR_UNSUPPORTED;
- * ssw_index_device_ptrs hands out the private layout. */
+ * of the widened rows: the query stays f32, products and sums are f32 in the f32 scan's order.  A large f16 index
+ * prunes its single-query top-k like an f32 index (ssw_index_prune_stats: the int8 shadow is built from the widened
+ * rows, from 2^22 rows on, as for f32 rows).  Entries that read the matrix as f32 through the handle and have no f16
+ * form (ssw_knn_build, ssw_xlx) return SSW_ERR_UNSUPPORTED; ssw_index_device_ptrs hands out the private layout. */
 #define SSW_DTYPE_F32 0
 #define SSW_DTYPE_F16 1
 /* ssw_index_create with an element type.  SSW_DTYPE_F32 is ssw_index_create; SSW_DTYPE_F16 allocates
@@ -153,8 +154,9 @@ ssw_status ssw_index_topk(ssw_index *idx, const float *q_host, const int64_t *ex
  * single top-k that is one full scan of the previous query (31 ms at 100 M rows) before the batch starts.
  * Measured on one MI355X ("Batched scan"; k = 100): one launch costs 1.04-1.07 x a single-query
  * scan at 2 queries, 1.08-1.17 x at 4, 1.14-1.20 x (f32) at 8 and 1.57-1.68 x (f32) at 16.  Per query, against single
- * calls that scan in full (f32 below 2^22 rows or a borrowed matrix; every f16 index), topk_batch takes 0.52-0.62 x
- * at nq = 2, 0.27-0.40 x at 4, 0.15-0.32 x at 8 and, f32, 0.10-0.17 x at 16.  Where the single call is PRUNED (f32, >= 2^22 rows) the
+ * calls that scan in full (below 2^22 rows, or a borrowed matrix), topk_batch takes
+ * 0.52-0.62 x at nq = 2, 0.27-0.40 x at 4, 0.15-0.32 x at 8 and, f32, 0.10-0.17 x at 16 (the f16 figures were taken
+ * against the f16 full scan at every size).  Where the single call is PRUNED (measured for f32, >= 2^22 rows) the
  * crossover is nq = 4: the batch is slower at nq = 2 (16.3 against 8.4 ms per query at 100 M rows), equal at 4 (8.46
  * against 8.42; 1.17 against 1.19 at 12.5 M), faster from 8 on (4.6, and 3.2 at 16, against 8.4; 0.67 and 0.49 against
  * 1.20).  Callers choose; nothing dispatches silently.
@@ -271,16 +273,18 @@ ssw_status ssw_topk_allgather(ssw_comm *comm, void *hip_stream, const uint64_t *
 ssw_status ssw_index_profile(ssw_index *idx, int32_t enable);
 ssw_status ssw_index_profile_read(ssw_index *idx, float *out_ms, int32_t cap, int32_t *out_n);
 
-/* Pruned top-k.  ssw_index_topk / ssw_index_topk_dev with a query, on an f32 index of at least 2^22 rows that owns its
- * matrix (dim 256, 512 or 1024), scan an int8 shadow of the rows (dim + 8 bytes a row, built on the first such call
+/* Pruned top-k.  ssw_index_topk / ssw_index_topk_dev with a query, on an index of at least 2^22 rows (f32 or f16) that
+ * owns its matrix (dim 256, 512 or 1024), scan an int8 shadow of the rows -- of the widened rows for f16 -- (dim + 8
+ * bytes a row, built on the first such call
  * after the rows last changed, only if 4 GiB of device memory stay free beside it) for certified lower and upper bounds
  * of every score, and rescore exactly only the rows whose upper bound reaches the k-th image's lower bound.  The result
  * is the bits of the full scan; the call waits once on the host for the survivor count.  Whenever the certificate
  * fails the full scan runs instead.  The score buffer then holds exact scores for the survivors only; every entry that
  * reads it (topk with q = NULL, select_deep_dev, gather_scores, rescore_avg, device_ptrs, the labelprop top-k) first
  * completes it with the full scan of the kept query, and upload / fill_random do so before they change the rows.
- * An index that borrows a device matrix, an f16 index, and an index whose row pointer ssw_index_device_ptrs has handed
- * out never get a shadow.  The environment variable SSW_TOPK_FULL_SCAN (read once) forces the full scan everywhere.
+ * An index that borrows a device matrix and an index whose row pointer ssw_index_device_ptrs has handed out never get
+ * a shadow.  An f16 index with its shadow holds dim * 3 + 8 bytes a row.  The environment variable SSW_TOPK_FULL_SCAN
+ * (read once) forces the full scan everywhere, for both element types.
  * out6: [0] shadow 0 none / 1 current / 2 stale / 3 refused (memory), [1] 1 = the next top-k with a query is pruned,
  * [2] survivors of the last pruned call (-1 = it fell back), [3] pruned calls, [4] fallbacks, [5] shadow bytes. */
 ssw_status ssw_index_prune_stats(ssw_index *idx, int64_t *out6);

@@ -36,9 +36,10 @@ ssw_status ssw_tune_scan_batch(int32_t max_width, int32_t blocks_per_cu);
 ssw_status ssw_tune_topk(int32_t flags);
 
 /* The pruned top-k (seesaw_hip.h, ssw_index_prune_stats): enable 0 = every top-k scans in full (what
- * SSW_TOPK_FULL_SCAN does), min_rows = the smallest index that is pruned, reserve_bytes = the free device memory a
- * shadow must leave (-1 = default for either: 2^22 rows, 4 GiB).  Applies to the next top-k of every index; a shadow
- * refused for memory is retried only after its rows change. */
+ * SSW_TOPK_FULL_SCAN does), min_rows >= 0 = the smallest index that is pruned, for f32 and f16 rows alike,
+ * reserve_bytes = the free device memory a shadow must leave (< 0 = the defaults: 2^22 rows for f32 and for f16 rows,
+ * 4 GiB).  Applies to the next top-k of every index; a shadow refused for memory is retried only after its rows
+ * change. */
 ssw_status ssw_tune_prune(int32_t enable, int64_t min_rows, int64_t reserve_bytes);
 
 /* The launch shape of the shadow scan (k_q8_bounds): four-wave blocks per CU (1 .. 8) and 16-byte loads a lane keeps in
@@ -49,7 +50,7 @@ ssw_status ssw_tune_prune_scan(int32_t blocks_per_cu, int32_t group_loads);
 
 /* The pre-scan's intermediate state, for tests/test_prune_certificate_gpu.py.  The three hooks run the product's
  * kernels through the launch functions of the pruned top-k on the index's own buffers; all out pointers are HOST
- * memory; the index must be one the next top-k would prune (ssw_tune_prune, f32, dim 256 / 512 / 1024, own rows).
+ * memory; the index must be one the next top-k would prune (ssw_tune_prune, dim 256 / 512 / 1024, own rows).
  * shadow: builds the int8 shadow if it is missing or stale (the product's ensure_shadow -> k_q8_build; SSW_ERR_NOMEM
  *   when it is refused for memory) and copies out the codes [n_rows, dim] int8, s_r and a_r [n_rows] of the rows
  *   [first_row, first_row + n_rows); an output that is NULL is skipped.

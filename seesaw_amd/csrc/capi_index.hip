@@ -204,14 +204,19 @@ static ssw_status do_select(ssw_index *idx, int32_t k) {
 }
 
 // ---- the certified pre-scan (prune.hip) -------------------------------------------------------
-// Top-k with a query on an index of at least PRUNE_MIN_ROWS f32 rows scans the int8 shadow instead of the rows and
-// rescores the survivors exactly; the score buffer then holds exact scores for the survivors and lower bounds elsewhere
-// (scores_partial) until a consumer that reads it materialises the full scan of the kept query.
+// Top-k with a query on an index of at least PRUNE_MIN_ROWS f32 rows, or PRUNE_MIN_ROWS_F16 f16 rows, scans the int8
+// shadow instead of the rows and rescores the survivors exactly; the score buffer then holds exact scores for the
+// survivors and lower bounds elsewhere (scores_partial) until a consumer that reads it materialises the full scan of
+// the kept query.
 constexpr int64_t PRUNE_MIN_ROWS = (int64_t)1 << 22;  // above the feedback loop's 1.56 M rows, below a rank's 12.5 M
+// f16 rows: the full scan reads half the bytes, yet the pruned call is ahead from the smallest size of the measured
+// sweep on (2^22 rows: 0.49 against 0.72 ms a call, profiles/prune_f16_sweep.txt), so the value is the f32 one.  Its
+// own constant: the two row formats are measured separately and need not stay equal.
+constexpr int64_t PRUNE_MIN_ROWS_F16 = (int64_t)1 << 22;
 constexpr int64_t PRUNE_RESERVE = (int64_t)4 << 30;   // free device memory the shadow must leave
 constexpr int64_t SURV_CAP = (int64_t)1 << 18;        // survivors rescored at most; more: the full scan
 static SSW_TUNABLE bool g_prune = true;               // ssw_tune_prune
-static SSW_TUNABLE int64_t g_prune_min_rows = PRUNE_MIN_ROWS;
+static SSW_TUNABLE int64_t g_prune_min_rows = -1;      // >= 0: this many rows for both dtypes instead
 static SSW_TUNABLE int64_t g_prune_reserve = PRUNE_RESERVE;
 
 static bool prune_forced_off() {
@@ -219,9 +224,14 @@ static bool prune_forced_off() {
     return v;
 }
 
+static int64_t prune_min_rows(const ssw_index *idx) {
+    if (g_prune_min_rows >= 0) return g_prune_min_rows;
+    return idx->dtype == SSW_DTYPE_F16 ? PRUNE_MIN_ROWS_F16 : PRUNE_MIN_ROWS;
+}
+
 static bool prune_eligible(const ssw_index *idx) {
-    return g_prune && !prune_forced_off() && idx->dtype == SSW_DTYPE_F32 && idx->owns_X && !idx->rows_escaped &&
-           idx->n >= g_prune_min_rows && idx->n_images > 0 && q8_dim_supported(idx->dim);
+    return g_prune && !prune_forced_off() && idx->owns_X && !idx->rows_escaped && idx->n >= prune_min_rows(idx) &&
+           idx->n_images > 0 && q8_dim_supported(idx->dim);
 }
 
 static void free_shadow(ssw_index *idx) {
@@ -872,7 +882,7 @@ static ssw_status ensure_shadow(ssw_index *idx, bool *ready) {
         memset(idx->prune_host, 0, 16);
         SSW_HIP_TRY(hipEventCreateWithFlags(&idx->prune_ev, hipEventDisableTiming));
     }
-    SSW_TRY(launch_q8_build(idx->X, idx->n, idx->dim, idx->q8, idx->q8_scale, idx->q8_err, idx->stream));
+    SSW_TRY(launch_q8_build(idx->X, idx->dtype, idx->n, idx->dim, idx->q8, idx->q8_scale, idx->q8_err, idx->stream));
     idx->q8_stale = false;
     *ready = true;
     return SSW_OK;
@@ -1486,7 +1496,7 @@ ssw_status ssw_tune_scan_batch(int32_t max_width, int32_t blocks_per_cu) {
 
 ssw_status ssw_tune_prune(int32_t enable, int64_t min_rows, int64_t reserve_bytes) {
     g_prune = enable != 0;
-    g_prune_min_rows = min_rows < 0 ? PRUNE_MIN_ROWS : min_rows;
+    g_prune_min_rows = min_rows < 0 ? -1 : min_rows;  // < 0: PRUNE_MIN_ROWS / PRUNE_MIN_ROWS_F16 again
     g_prune_reserve = reserve_bytes < 0 ? PRUNE_RESERVE : reserve_bytes;
     return SSW_OK;
 }
@@ -1503,7 +1513,7 @@ ssw_status ssw_debug_prune_shadow(ssw_index *idx, int64_t first_row, int64_t n_r
     SSW_REQUIRE(idx != nullptr, "idx is NULL");
     SSW_REQUIRE(first_row >= 0 && n_rows >= 0 && first_row + n_rows <= idx->n, "rows [%lld, +%lld) outside [0, %lld)",
                 (long long)first_row, (long long)n_rows, (long long)idx->n);
-    SSW_REQUIRE(prune_eligible(idx), "the index is not pruned (ssw_tune_prune, dtype, dim, borrowed or escaped rows)");
+    SSW_REQUIRE(prune_eligible(idx), "the index is not pruned (ssw_tune_prune, dim, borrowed or escaped rows)");
     DeviceGuard guard(idx->device);
     bool ready = false;
     SSW_TRY(ensure_shadow(idx, &ready));
@@ -1529,7 +1539,7 @@ ssw_status ssw_debug_prune_bounds(ssw_index *idx, const float *q_host, float *ou
     SSW_REQUIRE(idx != nullptr && q_host != nullptr && out_lb != nullptr && out_Q != nullptr && out_unbounded != nullptr,
                 "NULL argument");
     SSW_TRY(check_query(idx, q_host));
-    SSW_REQUIRE(prune_eligible(idx), "the index is not pruned (ssw_tune_prune, dtype, dim, borrowed or escaped rows)");
+    SSW_REQUIRE(prune_eligible(idx), "the index is not pruned (ssw_tune_prune, dim, borrowed or escaped rows)");
     DeviceGuard guard(idx->device);
     bool ready = false;
     SSW_TRY(ensure_shadow(idx, &ready));

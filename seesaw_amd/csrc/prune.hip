@@ -1,4 +1,4 @@
-// prune.hip -- certified int8 pre-scan for the exact top-k of a large f32 index (gfx950 / MI355X)
+// prune.hip -- certified int8 pre-scan for the exact top-k of a large f32 or f16 index (gfx950 / MI355X)
 //
 // The f32 scan (scan.hip) streams dim*4 bytes a row and is HBM-bound.  An exact top-k needs the exact score of only a
 // few rows: the ones that can still reach the k-th image.  This file keeps an int8 SHADOW of every row (dim bytes, plus
@@ -8,8 +8,9 @@
 //     | S_r - s~_r | <= a_r * Q + PAD_ABS                                                                    (*)
 //
 // where S_r is the BITS the f32 scan computes for row r (any summation order of dim products: the bound is the
-// standard gamma_dim one, DESIGN.md section 4 derives it).  k_q8_bounds writes lb_r = s~_r - a_r Q - pad, rounded down,
-// into the score buffer.  The caller (capi_index.hip, scan_for_topk) selects the k-th image over those lower bounds
+// standard gamma_dim one, DESIGN.md section 4 derives it).  For an f16 index the rows x are the widened binary16 rows:
+// widening is exact and the f16 scan returns the f32 scan's bits on them, so the same statement holds unchanged.
+// k_q8_bounds writes lb_r = s~_r - a_r Q - pad, rounded down, into the score buffer.  The caller (capi_index.hip, scan_for_topk) selects the k-th image over those lower bounds
 // (threshold T <= the exact k-th image score), keeps the rows whose upper bound reaches T (k_survivors), rescores them
 // with the f32 scan's own arithmetic (score_rows_kernel) and scatters the exact scores back (k_scatter_scores).  The
 // normal selection over that buffer then returns the bits of a full scan.
@@ -44,20 +45,13 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     return v;
 }
 
+// The part of a row's conversion both builders share: the lane's 4C elements x (any fixed assignment of the row's
+// elements to lanes and slots) -> their codes, slot i in byte i % 4 of packed[i / 4], and the row's s_r and a_r, which
+// lane 0 writes.  The codes and s_r do not depend on the assignment; a_r's double sums are taken in its order.
 template <int C>
-__device__ __forceinline__ void q8_build_row(const float *__restrict__ X, int64_t r, int lane, int8_t *__restrict__ codes,
-                                             float *__restrict__ scale, float *__restrict__ err) {
+__device__ __forceinline__ void q8_quantise_row(const float (&x)[4 * C], int64_t r, int lane, unsigned (&packed)[C],
+                                                float *__restrict__ scale, float *__restrict__ err) {
     constexpr int dim = 256 * C;
-    const float4 *src = reinterpret_cast<const float4 *>(X + r * dim) + lane * C;
-    float x[4 * C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        const float4 v = src[c];
-        x[4 * c] = v.x;
-        x[4 * c + 1] = v.y;
-        x[4 * c + 2] = v.z;
-        x[4 * c + 3] = v.w;
-    }
     float m = 0.0f;
     bool finite = true;
 #pragma unroll
@@ -70,7 +64,6 @@ __device__ __forceinline__ void q8_build_row(const float *__restrict__ X, int64_
     const bool ok = __all(finite) && (m == 0.0f || (m >= MIN_ABS && m <= MAX_ABS));
     const float s = (ok && m > 0.0f) ? m / 127.0f : 0.0f;
     double e2 = 0.0, x2 = 0.0, c2 = 0.0;
-    unsigned packed[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) packed[c] = 0u;
 #pragma unroll
@@ -85,9 +78,6 @@ __device__ __forceinline__ void q8_build_row(const float *__restrict__ X, int64_
         if (ok) x2 += (double)x[i] * (double)x[i];
         c2 += (double)ci * (double)ci;
     }
-    unsigned *dst = reinterpret_cast<unsigned *>(codes + r * dim) + lane * C;
-#pragma unroll
-    for (int c = 0; c < C; ++c) dst[c] = packed[c];
     e2 = wave_sum_d(e2);
     x2 = wave_sum_d(x2);
     c2 = wave_sum_d(c2);
@@ -100,14 +90,81 @@ __device__ __forceinline__ void q8_build_row(const float *__restrict__ X, int64_
     }
 }
 
-// one wave per row (grid-strided: the grid stays far below 2^32 threads); lane l converts the 4C elements
-// 4C*l .. 4C*l + 4C - 1 (natural order, C = dim / 256)
+// f32 rows: lane l converts the 4C elements 4C*l .. 4C*l + 4C - 1 (natural order, C = dim / 256)
+template <int C>
+__device__ __forceinline__ void q8_build_row(const float *__restrict__ X, int64_t r, int lane, int8_t *__restrict__ codes,
+                                             float *__restrict__ scale, float *__restrict__ err) {
+    constexpr int dim = 256 * C;
+    const float4 *src = reinterpret_cast<const float4 *>(X + r * dim) + lane * C;
+    float x[4 * C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const float4 v = src[c];
+        x[4 * c] = v.x;
+        x[4 * c + 1] = v.y;
+        x[4 * c + 2] = v.z;
+        x[4 * c + 3] = v.w;
+    }
+    unsigned packed[C];
+    q8_quantise_row<C>(x, r, lane, packed, scale, err);
+    unsigned *dst = reinterpret_cast<unsigned *>(codes + r * dim) + lane * C;
+#pragma unroll
+    for (int c = 0; c < C; ++c) dst[c] = packed[c];
+}
+
+// binary16 rows in the f16 index's lane-interleaved layout (ssw_common.h): lane l reads its 8C contiguous bytes at
+// l * 8C of the row (one 16-byte load at dim 512, two at dim 1024, 8 bytes at dim 256) and widens them, exactly; chunk c
+// of them is the natural elements 256c + 4l .. + 3, so its four codes are the 4 bytes at 256c + 4l of the row's code
+// line: a wave writes 256 contiguous bytes a chunk, and the shadow is in natural element order as for f32 rows.
+template <int C>
+__device__ __forceinline__ void q8_build_row_h16(const uint16_t *__restrict__ X, int64_t r, int lane,
+                                                 int8_t *__restrict__ codes, float *__restrict__ scale,
+                                                 float *__restrict__ err) {
+    constexpr int dim = 256 * C;
+    const u32x2 *src = reinterpret_cast<const u32x2 *>(X + r * dim) + lane * C;
+    u32x2 w[C];
+    if constexpr (C == 1) {
+        w[0] = src[0];
+    } else {
+#pragma unroll
+        for (int c = 0; c < C; c += 2) {
+            const u32x4 v = *reinterpret_cast<const u32x4 *>(src + c);
+            w[c] = u32x2{v.x, v.y};
+            w[c + 1] = u32x2{v.z, v.w};
+        }
+    }
+    float x[4 * C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const float4 v = widen_h16x4(w[c]);
+        x[4 * c] = v.x;
+        x[4 * c + 1] = v.y;
+        x[4 * c + 2] = v.z;
+        x[4 * c + 3] = v.w;
+    }
+    unsigned packed[C];
+    q8_quantise_row<C>(x, r, lane, packed, scale, err);
+    unsigned *dst = reinterpret_cast<unsigned *>(codes + r * dim) + lane;
+#pragma unroll
+    for (int c = 0; c < C; ++c) dst[64 * c] = packed[c];
+}
+
+// one wave per row (grid-strided: the grid stays far below 2^32 threads)
 template <int C>
 __global__ __launch_bounds__(256) void k_q8_build(const float *__restrict__ X, int64_t n, int8_t *__restrict__ codes,
                                                   float *__restrict__ scale, float *__restrict__ err) {
     const int lane = threadIdx.x & 63;
     for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < n; r += (int64_t)gridDim.x * 4)
         q8_build_row<C>(X, r, lane, codes, scale, err);
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void k_q8_build_h16(const uint16_t *__restrict__ X, int64_t n,
+                                                      int8_t *__restrict__ codes, float *__restrict__ scale,
+                                                      float *__restrict__ err) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < n; r += (int64_t)gridDim.x * 4)
+        q8_build_row_h16<C>(X, r, lane, codes, scale, err);
 }
 
 // ||q|| rounded up (Q), the validity of the query for the bound, the survivor counter reset, and the query copied into
@@ -366,17 +423,28 @@ __global__ __launch_bounds__(256) void k_scatter_scores(const int64_t *__restric
 
 bool q8_dim_supported(int32_t dim) { return dim == 256 || dim == 512 || dim == 1024; }
 
-ssw_status launch_q8_build(const float *X, int64_t n, int32_t dim, int8_t *codes, float *scale, float *err,
-                           hipStream_t stream) {
+ssw_status launch_q8_build(const void *X, int32_t dtype, int64_t n, int32_t dim, int8_t *codes, float *scale,
+                           float *err, hipStream_t stream) {
     if (n <= 0) return SSW_OK;
+    if (!q8_dim_supported(dim) || (dtype != SSW_DTYPE_F32 && dtype != SSW_DTYPE_F16)) {
+        set_error("q8_build: dim=%d, dtype=%d unsupported", dim, dtype);
+        return SSW_ERR_UNSUPPORTED;
+    }
     const dim3 grid((unsigned)std::min<int64_t>((n + 3) / 4, (int64_t)1 << 20)), block(256);
-    switch (dim) {
-        case 256: hipLaunchKernelGGL(k_q8_build<1>, grid, block, 0, stream, X, n, codes, scale, err); break;
-        case 512: hipLaunchKernelGGL(k_q8_build<2>, grid, block, 0, stream, X, n, codes, scale, err); break;
-        case 1024: hipLaunchKernelGGL(k_q8_build<4>, grid, block, 0, stream, X, n, codes, scale, err); break;
-        default:
-            set_error("q8_build: dim=%d unsupported", dim);
-            return SSW_ERR_UNSUPPORTED;
+    if (dtype == SSW_DTYPE_F16) {
+        const uint16_t *Xh = static_cast<const uint16_t *>(X);
+        switch (dim) {
+            case 256: hipLaunchKernelGGL(k_q8_build_h16<1>, grid, block, 0, stream, Xh, n, codes, scale, err); break;
+            case 512: hipLaunchKernelGGL(k_q8_build_h16<2>, grid, block, 0, stream, Xh, n, codes, scale, err); break;
+            default: hipLaunchKernelGGL(k_q8_build_h16<4>, grid, block, 0, stream, Xh, n, codes, scale, err); break;
+        }
+    } else {
+        const float *Xf = static_cast<const float *>(X);
+        switch (dim) {
+            case 256: hipLaunchKernelGGL(k_q8_build<1>, grid, block, 0, stream, Xf, n, codes, scale, err); break;
+            case 512: hipLaunchKernelGGL(k_q8_build<2>, grid, block, 0, stream, Xf, n, codes, scale, err); break;
+            default: hipLaunchKernelGGL(k_q8_build<4>, grid, block, 0, stream, Xf, n, codes, scale, err); break;
+        }
     }
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;

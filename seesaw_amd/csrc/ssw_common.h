@@ -164,11 +164,12 @@ ssw_status launch_score_rows(const void *X, int32_t dtype, const float *q_dev, c
 int scan_batch_max_width(int64_t n, int32_t dim, int32_t dtype);
 ssw_status launch_scan_batch(const void *X, int32_t dtype, const float *qb_dev, float *const *slabs, int32_t nb,
                              int64_t n, int32_t dim, int device, hipStream_t stream);
-// prune.hip: the int8 shadow of an f32 index and the certified pre-scan of the exact top-k (see prune.hip).
+// prune.hip: the int8 shadow of an index (rows of element type dtype: f32, or binary16 in the layout above, taken as
+// their widened values) and the certified pre-scan of the exact top-k (see prune.hip).
 // query state words: [0] survivors, [1] Q = ||q|| rounded up (f32 bits), [2] 1 = the query cannot be bounded
 bool q8_dim_supported(int32_t dim);
-ssw_status launch_q8_build(const float *X, int64_t n, int32_t dim, int8_t *codes, float *scale, float *err,
-                           hipStream_t stream);
+ssw_status launch_q8_build(const void *X, int32_t dtype, int64_t n, int32_t dim, int8_t *codes, float *scale,
+                           float *err, hipStream_t stream);
 ssw_status launch_q8_query(const float *q_dev, int32_t dim, float *q_keep, unsigned *state, hipStream_t stream);
 ssw_status launch_q8_bounds(const int8_t *codes, const float *scale, const float *err, const float *q_dev,
                             const unsigned *state, float *scores, int64_t n, int32_t dim, int device, hipStream_t stream);

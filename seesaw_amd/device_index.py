@@ -348,6 +348,20 @@ class DeviceIndex:
                 view.close()
         return dst, score, int(redo.shape[0])
 
+    # -- pruned top-k ----------------------------------------------------------------
+    _SHADOW_STATES = ("none", "current", "stale", "refused")
+
+    def prune_stats(self) -> dict:
+        """state of the certified int8 pre-scan of `topk` with a query (ssw_index_prune_stats): `shadow` is "none",
+        "current", "stale" (the rows changed since it was built; the next pruned call rebuilds it) or "refused" (too
+        little free device memory beside it); `eligible`: the next top-k with a query is pruned; `last_survivors`: rows
+        the last pruned call rescored (-1 = it fell back to the full scan); `queries` / `fallbacks`: pruned calls and
+        how many of them fell back; `shadow_bytes`: device memory the shadow holds"""
+        out = np.zeros(6, dtype=np.int64)
+        _lib.call("ssw_index_prune_stats", self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
+        return {"shadow": self._SHADOW_STATES[int(out[0])], "eligible": bool(out[1]), "last_survivors": int(out[2]),
+                "queries": int(out[3]), "fallbacks": int(out[4]), "shadow_bytes": int(out[5])}
+
     # -- profiling --------------------------------------------------------------------
     def profile(self, enable: bool):
         _lib.call("ssw_index_profile", self._h, int(bool(enable)))
