@@ -69,6 +69,49 @@ void PinnedStage::release() {
 
 using namespace ssw;
 
+// certified int8 pre-scan of the top-k (prune.hip): the shadow of the rows, built lazily by the first top-k with a query
+// after the rows last changed, and the buffers of one pruned call
+struct PruneState {
+    int8_t *q8 = nullptr;                          // [n, dim] codes
+    float *q8_scale = nullptr, *q8_err = nullptr;  // [n] s_r, a_r
+    bool stale = true;                             // the rows changed since the shadow was built
+    bool refused = false;                          // too little free memory at the last attempt (until the rows change)
+    unsigned *state = nullptr;                     // [4] device words (ssw_common.h, launch_q8_query)
+    int64_t *surv_rows = nullptr;                  // [SURV_CAP]
+    float *surv_scores = nullptr;                  // [SURV_CAP]
+    int32_t *host = nullptr;                       // pinned, mapped: [seq, survivors or -1]
+    unsigned seq = 0;
+    hipEvent_t ev = nullptr;                       // after the shadow scan: the host sleeps on it, then spins
+    float *q_last = nullptr;                       // [dim] the query of the last pruned scan
+    int64_t last = 0, queries = 0, fallbacks = 0;
+    void free_shadow() {
+        for (void *p : {(void *)q8, (void *)q8_scale, (void *)q8_err}) (void)hipFree(p);
+        q8 = nullptr;
+        q8_scale = q8_err = nullptr;
+        stale = true;
+    }
+    void release() {
+        free_shadow();
+        for (void *p : {(void *)state, (void *)surv_rows, (void *)surv_scores, (void *)q_last}) (void)hipFree(p);
+        if (host) (void)hipHostFree(host);
+        if (ev) (void)hipEventDestroy(ev);
+    }
+};
+
+// batched scan (ssw_index_scan_batch / ssw_index_topk_batch): the queries of one chunk, and the score slabs of all but
+// its last query (that one's slab is `scores`); allocated by the first batched call
+struct BatchState {
+    float *qb_dev = nullptr;  // [BATCH_MAX_WIDTH, dim]
+    PinnedStage qb_stage;
+    float *side = nullptr;    // [side_slabs, slab_stride]
+    int side_slabs = 0;
+    void release() {
+        (void)hipFree(qb_dev);
+        (void)hipFree(side);
+        qb_stage.release();
+    }
+};
+
 struct ssw_index {
     int device = 0;
     int64_t n = 0;
@@ -100,7 +143,7 @@ struct ssw_index {
     unsigned char *small_host = nullptr;
     unsigned small_seq = 0;
     unsigned res_pending_seq = 0;  // != 0: the selection in flight publishes into res_host under this sequence number
-    unsigned small_pending_seq = 0;  // the same for the small form (topk_small_enqueue / _collect)
+    unsigned small_pending_seq = 0;  // the same for the small form, into small_host
     float *q2_dev = nullptr;  // second query vector (score_rows)
     PinnedStage q2_stage;
     // tile geometry + staging of the avg_score aggregation (rescore.hip)
@@ -111,28 +154,10 @@ struct ssw_index {
     float *rs_score = nullptr;     // [rs_cap]
     float *rs_minus = nullptr;     // [rs_minus_cap]
     int64_t rs_cap = 0, rs_minus_cap = 0;
-    // certified int8 pre-scan of the top-k (prune.hip): the shadow of the rows, built lazily by the first top-k with a
-    // query after the rows last changed.  Never for a borrowed matrix or once ssw_index_device_ptrs handed out the rows.
-    int8_t *q8 = nullptr;                            // [n, dim] codes
-    float *q8_scale = nullptr, *q8_err = nullptr;    // [n] s_r, a_r
-    bool q8_stale = true;                            // the rows changed since the shadow was built
-    bool q8_refused = false;                         // too little free memory at the last attempt (until the rows change)
-    bool rows_escaped = false;                       // the row pointer was handed out: never a shadow
-    unsigned *prune_state = nullptr;                 // [4] device words (ssw_common.h, launch_q8_query)
-    int64_t *surv_rows = nullptr;                    // [SURV_CAP]
-    float *surv_scores = nullptr;                    // [SURV_CAP]
-    int32_t *prune_host = nullptr;                   // pinned, mapped: [seq, survivors or -1]
-    unsigned prune_seq = 0;
-    hipEvent_t prune_ev = nullptr;                   // after the shadow scan: the host sleeps on it, then spins
-    float *q_last = nullptr;                         // [dim] the query of the last pruned scan
-    bool scores_partial = false;                     // scores hold exact values for the survivors only (materialise)
-    int64_t prune_last = 0, prune_queries = 0, prune_fallbacks = 0;
-    // batched scan (ssw_index_scan_batch / ssw_index_topk_batch): the queries of one chunk, and the score slabs of all
-    // but its last query (that one's slab is `scores`); allocated by the first batched call
-    float *qb_dev = nullptr;                         // [BATCH_MAX_WIDTH, dim]
-    PinnedStage qb_stage;
-    float *side = nullptr;                           // [side_slabs, slab_stride]
-    int side_slabs = 0;
+    PruneState prune;           // never for a borrowed matrix or once ssw_index_device_ptrs handed out the rows
+    bool rows_escaped = false;  // the row pointer was handed out: never a shadow
+    bool scores_partial = false;  // scores hold exact values for the survivors only (ensure_full_scores materialises)
+    BatchState batch;
     // profiling of the scan kernel
     bool profiling = false;
     std::vector<hipEvent_t> ev;  // pairs
@@ -143,6 +168,38 @@ static ssw_status ensure_ws(ssw_index *idx) {
     if (idx->ws_ready) return SSW_OK;
     SSW_TRY(select_alloc(idx->ws, idx->n, idx->n_images, idx->has_map));
     idx->ws_ready = true;
+    return SSW_OK;
+}
+
+static unsigned next_seq(unsigned &counter) {  // sequence numbers are never 0 ("nothing in flight")
+    if (++counter == 0) ++counter;
+    return counter;
+}
+
+static ssw_status check_row_range(const ssw_index *idx, int64_t first_row, int64_t n) {
+    SSW_REQUIRE(first_row >= 0 && n >= 0 && first_row + n <= idx->n,
+                "rows [%lld, %lld) outside the index of %lld rows", (long long)first_row,
+                (long long)(first_row + n), (long long)idx->n);
+    return SSW_OK;
+}
+
+static ssw_status check_excluded(const ssw_index *idx, const int64_t *ids, int64_t first, int64_t last) {
+    for (int64_t i = first; i < last; ++i)
+        SSW_REQUIRE(ids[i] >= 0 && ids[i] < idx->n_images, "excluded image %lld outside [0, %lld)", (long long)ids[i],
+                    (long long)idx->n_images);
+    return SSW_OK;
+}
+
+// one pair of profiling events around `work`, the scan or whatever replaces it; none when fewer than two are left
+template <class F>
+static ssw_status profiled(ssw_index *idx, F work) {
+    const bool prof = idx->profiling && idx->ev_used + 2 <= (int)idx->ev.size();
+    if (prof) SSW_HIP_TRY(hipEventRecord(idx->ev[idx->ev_used], idx->stream));
+    SSW_TRY(work());
+    if (prof) {
+        SSW_HIP_TRY(hipEventRecord(idx->ev[idx->ev_used + 1], idx->stream));
+        idx->ev_used += 2;
+    }
     return SSW_OK;
 }
 
@@ -176,31 +233,30 @@ static ssw_status stage_query(ssw_index *idx, const float *q_host) {
     return SSW_OK;
 }
 
-static ssw_status launch_index_scan(ssw_index *idx, const float *q_dev) {
-    return launch_scan(idx->X, idx->dtype, q_dev, idx->scores, idx->n, idx->dim, idx->device, idx->stream);
+static ssw_status launch_index_scan(ssw_index *idx, const float *q_dev, hipStream_t stream) {
+    return launch_scan(idx->X, idx->dtype, q_dev, idx->scores, idx->n, idx->dim, idx->device, stream);
 }
 
 static ssw_status do_scan(ssw_index *idx, const float *q_dev) {
     idx->scores_partial = false;
-    if (idx->profiling && idx->ev_used + 2 <= (int)idx->ev.size()) {
-        SSW_HIP_TRY(hipEventRecord(idx->ev[idx->ev_used], idx->stream));
-        SSW_TRY(launch_index_scan(idx, q_dev));
-        SSW_HIP_TRY(hipEventRecord(idx->ev[idx->ev_used + 1], idx->stream));
-        idx->ev_used += 2;
-        return SSW_OK;
-    }
-    return launch_index_scan(idx, q_dev);
+    return profiled(idx, [&] { return launch_index_scan(idx, q_dev, idx->stream); });
 }
 
-static ssw_status do_select(ssw_index *idx, int32_t k) {
+// the selection over the row scores in `scores`: per-image maxima first when the index has an image map
+static ssw_status do_select(ssw_index *idx, const float *scores, int32_t k, SelectDest dest, hipStream_t stream) {
     SSW_TRY(ensure_ws(idx));
     if (idx->has_map) {
-        SSW_TRY(launch_image_max(idx->scores, idx->row_start, idx->n_images, idx->ws.img_score,
-                                 idx->ws.img_best, idx->stream));
-        return launch_select_topk(idx->ws, idx->ws.img_score, idx->n_images, idx->ws.img_best, k,
-                                  idx->device, idx->stream);
+        SSW_TRY(launch_image_max(scores, idx->row_start, idx->n_images, idx->ws.img_score, idx->ws.img_best, stream));
+        return launch_select_topk(idx->ws, idx->ws.img_score, idx->n_images, idx->ws.img_best, k, dest, idx->device, stream);
     }
-    return launch_select_topk(idx->ws, idx->scores, idx->n, nullptr, k, idx->device, idx->stream);
+    return launch_select_topk(idx->ws, scores, idx->n, nullptr, k, dest, idx->device, stream);
+}
+
+// the deep path over what the last do_select of `scores` left (the per-image maxima are still in the workspace)
+static ssw_status do_select_deep(ssw_index *idx, const float *scores, int32_t k, SelectDest dest, hipStream_t stream) {
+    const float *values = idx->has_map ? idx->ws.img_score : scores;
+    const uint32_t *best = idx->has_map ? idx->ws.img_best : nullptr;
+    return launch_select_topk_deep(idx->ws, values, idx->n_images, best, k, dest, idx->device, stream);
 }
 
 // ---- the certified pre-scan (prune.hip) -------------------------------------------------------
@@ -234,27 +290,42 @@ static bool prune_eligible(const ssw_index *idx) {
            idx->n_images > 0 && q8_dim_supported(idx->dim);
 }
 
-static void free_shadow(ssw_index *idx) {
-    (void)hipFree(idx->q8);
-    (void)hipFree(idx->q8_scale);
-    (void)hipFree(idx->q8_err);
-    idx->q8 = nullptr;
-    idx->q8_scale = idx->q8_err = nullptr;
-    idx->q8_stale = true;
-}
-
-static ssw_status ensure_full_scores(ssw_index *idx) {
+static ssw_status ensure_full_scores(ssw_index *idx, hipStream_t stream) {
     if (!idx->scores_partial) return SSW_OK;
     idx->scores_partial = false;
-    return launch_index_scan(idx, idx->q_last);
+    return launch_index_scan(idx, idx->prune.q_last, stream);
 }
+static ssw_status ensure_full_scores(ssw_index *idx) { return ensure_full_scores(idx, idx->stream); }
 
 // the rows are about to change: the buffer keeps the scores of the rows it was computed from, the shadow goes stale
 static ssw_status rows_changing(ssw_index *idx) {
     SSW_TRY(ensure_full_scores(idx));
-    idx->q8_stale = true;
-    idx->q8_refused = false;
+    idx->prune.stale = true;
+    idx->prune.refused = false;
     return SSW_OK;
+}
+
+// the candidates' tiles laid end to end: off[c] = first tile of candidate c, their total and the most of one image
+static ssw_status candidate_geometry(const ssw_index *idx, const int64_t *image_positions, int32_t m,
+                                     std::vector<int64_t> &off, int64_t *total, int64_t *max_tiles) {
+    off.resize((size_t)m);
+    *total = *max_tiles = 0;
+    for (int32_t c = 0; c < m; ++c) {
+        const int64_t p = image_positions[c];
+        SSW_REQUIRE(p >= 0 && p < idx->n_images, "image position %lld outside [0, %lld)", (long long)p,
+                    (long long)idx->n_images);
+        const int64_t t = idx->row_start_host[(size_t)p + 1] - idx->row_start_host[(size_t)p];
+        off[(size_t)c] = *total;
+        *total += t;
+        *max_tiles = std::max(*max_tiles, t);
+    }
+    return SSW_OK;
+}
+
+static ssw_status install_excluded(ssw_index *idx, const int64_t *excluded_images, int64_t n_excluded, hipStream_t stream) {
+    SSW_TRY(check_excluded(idx, excluded_images, 0, n_excluded));
+    SSW_TRY(ensure_ws(idx));
+    return select_set_excluded(idx->ws, idx->n_images, excluded_images, n_excluded, stream);
 }
 
 static ssw_status scan_for_topk(ssw_index *idx, const float *q_dev, int32_t k);
@@ -363,21 +434,13 @@ ssw_status ssw_index_destroy(ssw_index *idx) {
     if (idx->own_stream) (void)hipStreamSynchronize(idx->own_stream);
     for (hipEvent_t e : idx->ev) (void)hipEventDestroy(e);
     if (idx->ws_ready) select_free(idx->ws);
-    free_shadow(idx);
-    (void)hipFree(idx->prune_state);
-    (void)hipFree(idx->surv_rows);
-    (void)hipFree(idx->surv_scores);
-    (void)hipFree(idx->q_last);
-    if (idx->prune_host) (void)hipHostFree(idx->prune_host);
-    if (idx->prune_ev) (void)hipEventDestroy(idx->prune_ev);
+    idx->prune.release();
+    idx->batch.release();
     if (idx->owns_X) (void)hipFree(idx->X);
     (void)hipFree(idx->xfer);
     (void)hipFree(idx->scores);
     (void)hipFree(idx->q_dev);
     idx->q_stage.release();
-    (void)hipFree(idx->qb_dev);
-    (void)hipFree(idx->side);
-    idx->qb_stage.release();
     (void)hipFree(idx->tile_boxes);
     (void)hipFree(idx->tile_zoom);
     (void)hipFree(idx->rs_pos);
@@ -434,7 +497,7 @@ ssw_status ssw_index_device_ptrs(ssw_index *idx, void **dev_vectors, void **dev_
     if (dev_vectors) {  // the caller may write the rows through it: no shadow from now on
         idx->rows_escaped = true;
         SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
-        free_shadow(idx);
+        idx->prune.free_shadow();
         *dev_vectors = idx->X;
     }
     if (dev_scores) *dev_scores = idx->scores;
@@ -476,9 +539,7 @@ static ssw_status upload_h16(ssw_index *idx, const void *host_rows, bool src_h16
 
 ssw_status ssw_index_upload(ssw_index *idx, const float *host_rows, int64_t first_row, int64_t n) {
     SSW_REQUIRE(idx != nullptr && host_rows != nullptr, "NULL argument");
-    SSW_REQUIRE(first_row >= 0 && n >= 0 && first_row + n <= idx->n,
-                "rows [%lld, %lld) outside the index of %lld rows", (long long)first_row,
-                (long long)(first_row + n), (long long)idx->n);
+    SSW_TRY(check_row_range(idx, first_row, n));
     DeviceGuard guard(idx->device);
     SSW_TRY(rows_changing(idx));
     if (idx->dtype == SSW_DTYPE_F16) return upload_h16(idx, host_rows, false, first_row, n);
@@ -495,9 +556,7 @@ ssw_status ssw_index_upload_f16(ssw_index *idx, const uint16_t *rows_f16, int64_
         set_error("ssw_index_upload_f16: the index holds f32 rows (use ssw_index_upload)");
         return SSW_ERR_UNSUPPORTED;
     }
-    SSW_REQUIRE(first_row >= 0 && n >= 0 && first_row + n <= idx->n,
-                "rows [%lld, %lld) outside the index of %lld rows", (long long)first_row,
-                (long long)(first_row + n), (long long)idx->n);
+    SSW_TRY(check_row_range(idx, first_row, n));
     DeviceGuard guard(idx->device);
     SSW_TRY(rows_changing(idx));
     return upload_h16(idx, rows_f16, true, first_row, n);
@@ -505,9 +564,7 @@ ssw_status ssw_index_upload_f16(ssw_index *idx, const uint16_t *rows_f16, int64_
 
 ssw_status ssw_index_download(ssw_index *idx, float *host_rows, int64_t first_row, int64_t n) {
     SSW_REQUIRE(idx != nullptr && host_rows != nullptr, "NULL argument");
-    SSW_REQUIRE(first_row >= 0 && n >= 0 && first_row + n <= idx->n,
-                "rows [%lld, %lld) outside the index of %lld rows", (long long)first_row,
-                (long long)(first_row + n), (long long)idx->n);
+    SSW_TRY(check_row_range(idx, first_row, n));
     DeviceGuard guard(idx->device);
     if (idx->dtype == SSW_DTYPE_F16) {  // widened, natural element order, through the staging buffer
         SSW_TRY(ensure_xfer(idx));
@@ -610,17 +667,9 @@ ssw_status ssw_index_rescore_avg(ssw_index *idx, const int64_t *image_positions,
                 "rescore_avg needs ssw_index_set_row2image and ssw_index_set_tile_meta first");
     DeviceGuard guard(idx->device);
     SSW_TRY(ensure_full_scores(idx));
-    std::vector<int64_t> off((size_t)m);
+    std::vector<int64_t> off;
     int64_t total = 0, max_tiles = 0;
-    for (int32_t c = 0; c < m; ++c) {
-        const int64_t p = image_positions[c];
-        SSW_REQUIRE(p >= 0 && p < idx->n_images, "image position %lld outside [0, %lld)", (long long)p,
-                    (long long)idx->n_images);
-        const int64_t t = idx->row_start_host[(size_t)p + 1] - idx->row_start_host[(size_t)p];
-        off[(size_t)c] = total;
-        total += t;
-        max_tiles = std::max(max_tiles, t);
-    }
+    SSW_TRY(candidate_geometry(idx, image_positions, m, off, &total, &max_tiles));
     SSW_REQUIRE(max_tiles <= SSW_RESCORE_MAX_TILES, "an image with %lld tiles exceeds the %d the kernel keeps in LDS",
                 (long long)max_tiles, SSW_RESCORE_MAX_TILES);
     hipStream_t s = idx->stream;
@@ -673,17 +722,9 @@ ssw_status ssw_index_rescore_avg_f64(ssw_index *idx, const double *dev_scores, c
     SSW_REQUIRE(idx->has_map && idx->tile_boxes && idx->tile_zoom,
                 "rescore_avg needs ssw_index_set_row2image and ssw_index_set_tile_meta first");
     DeviceGuard guard(idx->device);
-    std::vector<int64_t> off((size_t)m);
+    std::vector<int64_t> off;
     int64_t total = 0, max_tiles = 0;
-    for (int32_t c = 0; c < m; ++c) {
-        const int64_t p = image_positions[c];
-        SSW_REQUIRE(p >= 0 && p < idx->n_images, "image position %lld outside [0, %lld)", (long long)p,
-                    (long long)idx->n_images);
-        const int64_t t = idx->row_start_host[(size_t)p + 1] - idx->row_start_host[(size_t)p];
-        off[(size_t)c] = total;
-        total += t;
-        max_tiles = std::max(max_tiles, t);
-    }
+    SSW_TRY(candidate_geometry(idx, image_positions, m, off, &total, &max_tiles));
     hipStream_t s = idx->stream;
     int64_t *d_pos = nullptr, *d_off = nullptr, *d_row = nullptr;
     double *d_score = nullptr;
@@ -754,14 +795,8 @@ ssw_status ssw_index_load_scores(ssw_index *idx, const float *scores_host) {
 ssw_status ssw_index_set_excluded(ssw_index *idx, const int64_t *excluded_images, int64_t n_excluded) {
     SSW_REQUIRE(idx != nullptr, "idx is NULL");
     SSW_REQUIRE(n_excluded == 0 || excluded_images != nullptr, "excluded_images is NULL");
-    for (int64_t i = 0; i < n_excluded; ++i) {
-        SSW_REQUIRE(excluded_images[i] >= 0 && excluded_images[i] < idx->n_images,
-                    "excluded image %lld outside [0, %lld)", (long long)excluded_images[i],
-                    (long long)idx->n_images);
-    }
     DeviceGuard guard(idx->device);
-    SSW_TRY(ensure_ws(idx));
-    return select_set_excluded(idx->ws, idx->n_images, excluded_images, n_excluded, idx->stream);
+    return install_excluded(idx, excluded_images, n_excluded, idx->stream);
 }
 
 ssw_status ssw_index_topk_dev(ssw_index *idx, const float *q_dev, int32_t k) {
@@ -774,7 +809,7 @@ ssw_status ssw_index_topk_dev(ssw_index *idx, const float *q_dev, int32_t k) {
             SSW_HIP_TRY(hipMemsetAsync(idx->ws.xchg.msg_out + (idx->ws.xchg.msg_len - 1), 0, sizeof(uint64_t), idx->stream));
         return SSW_OK;
     }
-    return do_select(idx, k);
+    return do_select(idx, idx->scores, k, SelectDest(), idx->stream);
 }
 
 // The fast selection keeps at most 8192 candidates; when more images than that share the 24-bit score prefix
@@ -793,9 +828,7 @@ ssw_status ssw_index_select_deep_dev(ssw_index *idx, int32_t k) {
             SSW_TRY(launch_image_max(idx->scores, idx->row_start, idx->n_images, idx->ws.img_score, idx->ws.img_best,
                                      idx->stream));
     }
-    const float *values = idx->has_map ? idx->ws.img_score : idx->scores;
-    const uint32_t *best = idx->has_map ? idx->ws.img_best : nullptr;
-    return launch_select_topk_deep(idx->ws, values, idx->n_images, best, k, idx->device, idx->stream);
+    return do_select_deep(idx, idx->scores, k, SelectDest(), idx->stream);
 }
 
 ssw_status ssw_index_result_ptrs(ssw_index *idx, void **dev_keys, void **dev_count,
@@ -809,28 +842,14 @@ ssw_status ssw_index_result_ptrs(ssw_index *idx, void **dev_keys, void **dev_cou
     return SSW_OK;
 }
 
-// one pinned block receives the packed result [count, overflow, k, 0][keys k][best k]:
-// one async copy, one synchronisation
+// one pinned block receives the packed result [count, overflow, k, seq][keys k][best k]: written by the selection
+// itself (select_to_host), else one async copy + one synchronisation
 static ssw_status ensure_res_host(ssw_index *idx) {
     const size_t cap = 16 + (size_t)SSW_MAX_TOPK * 12;
     if (!idx->res_host) {
         SSW_HIP_TRY(hipHostMalloc((void **)&idx->res_host, cap, hipHostMallocMapped | hipHostMallocCoherent));
         memset(idx->res_host, 0, cap);
     }
-    return SSW_OK;
-}
-
-// the next selection on this index publishes into res_host (see SelectWorkspace::host_packed)
-static ssw_status arm_host_result(ssw_index *idx) {
-    SSW_TRY(ensure_ws(idx));
-    SSW_TRY(ensure_res_host(idx));
-    unsigned char *dev_view = nullptr;
-    SSW_HIP_TRY(hipHostGetDevicePointer((void **)&dev_view, idx->res_host, 0));
-    unsigned seq = ++idx->small_seq;
-    if (seq == 0) seq = ++idx->small_seq;
-    idx->ws.host_packed = dev_view;
-    idx->ws.host_seq = seq;
-    idx->res_pending_seq = seq;
     return SSW_OK;
 }
 
@@ -850,41 +869,68 @@ static ssw_status wait_host_seq(hipStream_t stream, const unsigned *flag, unsign
 
 // shadow of the rows for the pruned scan: (re)built when stale, if the device keeps PRUNE_RESERVE free beside it
 static ssw_status ensure_shadow(ssw_index *idx, bool *ready) {
+    PruneState &p = idx->prune;
     *ready = false;
-    if (idx->q8 && !idx->q8_stale) {
+    if (p.q8 && !p.stale) {
         *ready = true;
         return SSW_OK;
     }
-    if (idx->q8_refused) return SSW_OK;
-    if (!idx->q8) {
+    if (p.refused) return SSW_OK;
+    if (!p.q8) {
         const size_t codes = (size_t)idx->n * idx->dim, consts = (size_t)idx->n * sizeof(float);
         size_t free_b = 0, total_b = 0;
         SSW_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
         const size_t need = codes + 2 * consts + (size_t)SURV_CAP * 12 + ((size_t)idx->dim + 64) * sizeof(float);
         if (free_b < need || free_b - need < (size_t)g_prune_reserve) {
-            idx->q8_refused = true;
+            p.refused = true;
             return SSW_OK;
         }
-        if (hipMalloc((void **)&idx->q8, codes) != hipSuccess || hipMalloc((void **)&idx->q8_scale, consts) != hipSuccess ||
-            hipMalloc((void **)&idx->q8_err, consts) != hipSuccess) {
+        if (hipMalloc((void **)&p.q8, codes) != hipSuccess || hipMalloc((void **)&p.q8_scale, consts) != hipSuccess ||
+            hipMalloc((void **)&p.q8_err, consts) != hipSuccess) {
             (void)hipGetLastError();
-            free_shadow(idx);
-            idx->q8_refused = true;
+            p.free_shadow();
+            p.refused = true;
             return SSW_OK;
         }
     }
-    if (!idx->prune_state) {
-        SSW_HIP_TRY(hipMalloc((void **)&idx->prune_state, 4 * sizeof(unsigned)));
-        SSW_HIP_TRY(hipMalloc((void **)&idx->surv_rows, (size_t)SURV_CAP * sizeof(int64_t)));
-        SSW_HIP_TRY(hipMalloc((void **)&idx->surv_scores, (size_t)SURV_CAP * sizeof(float)));
-        SSW_HIP_TRY(hipMalloc((void **)&idx->q_last, (size_t)idx->dim * sizeof(float)));
-        SSW_HIP_TRY(hipHostMalloc((void **)&idx->prune_host, 16, hipHostMallocMapped | hipHostMallocCoherent));
-        memset(idx->prune_host, 0, 16);
-        SSW_HIP_TRY(hipEventCreateWithFlags(&idx->prune_ev, hipEventDisableTiming));
+    if (!p.state) {
+        SSW_HIP_TRY(hipMalloc((void **)&p.state, 4 * sizeof(unsigned)));
+        SSW_HIP_TRY(hipMalloc((void **)&p.surv_rows, (size_t)SURV_CAP * sizeof(int64_t)));
+        SSW_HIP_TRY(hipMalloc((void **)&p.surv_scores, (size_t)SURV_CAP * sizeof(float)));
+        SSW_HIP_TRY(hipMalloc((void **)&p.q_last, (size_t)idx->dim * sizeof(float)));
+        SSW_HIP_TRY(hipHostMalloc((void **)&p.host, 16, hipHostMallocMapped | hipHostMallocCoherent));
+        memset(p.host, 0, 16);
+        SSW_HIP_TRY(hipEventCreateWithFlags(&p.ev, hipEventDisableTiming));
     }
-    SSW_TRY(launch_q8_build(idx->X, idx->dtype, idx->n, idx->dim, idx->q8, idx->q8_scale, idx->q8_err, idx->stream));
-    idx->q8_stale = false;
+    SSW_TRY(launch_q8_build(idx->X, idx->dtype, idx->n, idx->dim, p.q8, p.q8_scale, p.q8_err, idx->stream));
+    p.stale = false;
     *ready = true;
+    return SSW_OK;
+}
+
+// The two steps of the pre-scan that the lab hooks (ssw_debug_prune_*) drive as well; the shadow is ready.
+// Lower bounds of the scores of q_dev into the buffer, which is partial from here on: a consumer rescans q_last.
+static ssw_status prune_bounds(ssw_index *idx, const float *q_dev) {
+    PruneState &p = idx->prune;
+    SSW_TRY(launch_q8_query(q_dev, idx->dim, p.q_last, p.state, idx->stream));
+    SSW_TRY(launch_q8_bounds(p.q8, p.q8_scale, p.q8_err, p.q_last, p.state, idx->scores, idx->n, idx->dim, idx->device,
+                             idx->stream));
+    idx->scores_partial = true;
+    return SSW_OK;
+}
+
+// The rows that may still reach the k-th key of the last selection, at most cap of them -> *out_m = their published
+// count, -1 = run the full scan.  One host wait: a sleep on sleep_ev_or_null first, then a spin.
+static ssw_status prune_survivors(ssw_index *idx, int32_t k, int64_t cap, hipEvent_t sleep_ev_or_null, int32_t *out_m) {
+    PruneState &p = idx->prune;
+    const unsigned seq = next_seq(p.seq);
+    int32_t *host_dev = nullptr;
+    SSW_HIP_TRY(hipHostGetDevicePointer((void **)&host_dev, p.host, 0));
+    SSW_TRY(launch_survivors(idx->scores, p.q8_err, idx->n, idx->ws.out_keys, idx->ws.out_count, k, p.state, p.surv_rows, cap,
+                             host_dev, seq, idx->device, idx->stream));
+    if (sleep_ev_or_null) SSW_HIP_TRY(hipEventSynchronize(sleep_ev_or_null));
+    SSW_TRY(wait_host_seq(idx->stream, reinterpret_cast<const unsigned *>(p.host), seq));
+    *out_m = __atomic_load_n(p.host + 1, __ATOMIC_ACQUIRE);
     return SSW_OK;
 }
 
@@ -899,118 +945,41 @@ static ssw_status scan_for_topk(ssw_index *idx, const float *q_dev, int32_t k) {
     if (k_ok && prune_eligible(idx)) SSW_TRY(ensure_shadow(idx, &ready));
     if (!ready) return do_scan(idx, q_dev);
     SSW_TRY(ensure_ws(idx));
-    const bool prof = idx->profiling && idx->ev_used + 2 <= (int)idx->ev.size();
-    if (prof) SSW_HIP_TRY(hipEventRecord(idx->ev[idx->ev_used], idx->stream));
-    SSW_TRY(launch_q8_query(q_dev, idx->dim, idx->q_last, idx->prune_state, idx->stream));
-    SSW_TRY(launch_q8_bounds(idx->q8, idx->q8_scale, idx->q8_err, idx->q_last, idx->prune_state, idx->scores, idx->n,
-                             idx->dim, idx->device, idx->stream));
-    idx->scores_partial = true;  // from here on the buffer holds bounds: a consumer rescans q_last
-    SSW_HIP_TRY(hipEventRecord(idx->prune_ev, idx->stream));
-    // threshold: the ordinary selection over the lower bounds, with the exclusions, without a message or host result
-    const FinalExchange keep_x = idx->ws.xchg;
-    unsigned char *keep_packed = idx->ws.host_packed;
-    idx->ws.xchg = FinalExchange();
-    idx->ws.host_packed = nullptr;
-    const ssw_status st = do_select(idx, k);
-    idx->ws.xchg = keep_x;
-    idx->ws.host_packed = keep_packed;
-    SSW_TRY(st);
-    unsigned seq = ++idx->prune_seq;
-    if (seq == 0) seq = ++idx->prune_seq;
-    int32_t *host_dev = nullptr;
-    SSW_HIP_TRY(hipHostGetDevicePointer((void **)&host_dev, idx->prune_host, 0));
-    SSW_TRY(launch_survivors(idx->scores, idx->q8_err, idx->n, idx->ws.out_keys, idx->ws.out_count, k, idx->prune_state,
-                             idx->surv_rows, SURV_CAP, host_dev, seq, idx->device, idx->stream));
-    SSW_HIP_TRY(hipEventSynchronize(idx->prune_ev));  // sleep through the shadow scan, spin on the rest
-    SSW_TRY(wait_host_seq(idx->stream, reinterpret_cast<const unsigned *>(idx->prune_host), seq));
-    const int32_t m = __atomic_load_n(idx->prune_host + 1, __ATOMIC_ACQUIRE);
-    idx->prune_last = m;
-    ++idx->prune_queries;
-    if (m < 0) {
-        ++idx->prune_fallbacks;
-        idx->scores_partial = false;
-        SSW_TRY(launch_index_scan(idx, idx->q_last));
-    } else {
-        SSW_TRY(launch_score_rows(idx->X, idx->dtype, idx->q_last, idx->surv_rows, m, idx->dim, idx->surv_scores,
-                                  idx->stream));
-        SSW_TRY(launch_scatter_scores(idx->surv_rows, idx->surv_scores, m, idx->scores, idx->stream));
-    }
-    if (prof) {
-        SSW_HIP_TRY(hipEventRecord(idx->ev[idx->ev_used + 1], idx->stream));
-        idx->ev_used += 2;
-    }
-    return SSW_OK;
+    return profiled(idx, [&]() -> ssw_status {
+        PruneState &p = idx->prune;
+        SSW_TRY(prune_bounds(idx, q_dev));
+        SSW_HIP_TRY(hipEventRecord(p.ev, idx->stream));
+        // threshold: the ordinary selection over the lower bounds, with the exclusions, without a message or host result
+        SSW_TRY(do_select(idx, idx->scores, k, SelectDest{nullptr, 0u, false}, idx->stream));
+        int32_t m = -1;
+        SSW_TRY(prune_survivors(idx, k, SURV_CAP, p.ev, &m));  // sleep through the shadow scan, spin on the rest
+        p.last = m;
+        ++p.queries;
+        if (m < 0) {
+            ++p.fallbacks;
+            idx->scores_partial = false;
+            return launch_index_scan(idx, p.q_last, idx->stream);
+        }
+        SSW_TRY(launch_score_rows(idx->X, idx->dtype, p.q_last, p.surv_rows, m, idx->dim, p.surv_scores, idx->stream));
+        return launch_scatter_scores(p.surv_rows, p.surv_scores, m, idx->scores, idx->stream);
+    });
 }
 
 ssw_status ssw_index_prune_stats(ssw_index *idx, int64_t *out6) {
     SSW_REQUIRE(idx != nullptr && out6 != nullptr, "NULL argument");
-    out6[0] = idx->q8 ? (idx->q8_stale ? 2 : 1) : (idx->q8_refused ? 3 : 0);
+    const PruneState &p = idx->prune;
+    out6[0] = p.q8 ? (p.stale ? 2 : 1) : (p.refused ? 3 : 0);
     out6[1] = prune_eligible(idx) ? 1 : 0;
-    out6[2] = idx->prune_last;
-    out6[3] = idx->prune_queries;
-    out6[4] = idx->prune_fallbacks;
-    out6[5] = idx->q8 ? idx->n * (idx->dim + 8) : 0;
+    out6[2] = p.last;
+    out6[3] = p.queries;
+    out6[4] = p.fallbacks;
+    out6[5] = p.q8 ? idx->n * (idx->dim + 8) : 0;
     return SSW_OK;
 }
 
-// one pinned block receives the packed result [count, overflow, k, seq][keys k][best k]: written by the selection
-// itself when armed (arm_host_result), else one async copy + one synchronisation
-static ssw_status fetch_results(ssw_index *idx, int32_t k, int32_t *count, bool *overflow) {
-    SSW_TRY(ensure_res_host(idx));
-    if (idx->res_pending_seq != 0) {
-        const unsigned seq = idx->res_pending_seq;
-        idx->res_pending_seq = 0;
-        SSW_TRY(wait_host_seq(idx->stream, reinterpret_cast<const unsigned *>(idx->res_host) + 3, seq));
-    } else {
-        SSW_HIP_TRY(hipMemcpyAsync(idx->res_host, idx->ws.packed, 16 + (size_t)k * 12, hipMemcpyDeviceToHost,
-                                   idx->stream));
-        SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
-    }
-    const int32_t *hdr = reinterpret_cast<const int32_t *>(idx->res_host);
-    *count = hdr[0];
-    *overflow = hdr[1] != 0;
-    if (hdr[2] != k) {
-        set_error("topk_fetch: k=%d does not match the k=%d of the selection that produced the result", k, hdr[2]);
-        return SSW_ERR_INVALID;
-    }
-    return SSW_OK;
-}
-
-ssw_status ssw_index_topk_fetch(ssw_index *idx, int32_t k, int64_t *out_images, float *out_scores,
-                                int64_t *out_best_rows, int32_t *out_count) {
-    SSW_REQUIRE(idx != nullptr && out_count != nullptr, "NULL argument");
-    SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
-    *out_count = 0;
-    if (idx->n_images == 0) return SSW_OK;
-    DeviceGuard guard(idx->device);
-    SSW_TRY(ensure_ws(idx));
-    int32_t count = 0;
-    bool overflow = false;
-    SSW_TRY(fetch_results(idx, k, &count, &overflow));
-    if (overflow) {  // massive exact ties: rerun the selection on the deep path
-        const float *values = idx->has_map ? idx->ws.img_score : idx->scores;
-        const uint32_t *best = idx->has_map ? idx->ws.img_best : nullptr;
-        SSW_TRY(arm_host_result(idx));
-        SSW_TRY(launch_select_topk_deep(idx->ws, values, idx->n_images, best, k, idx->device,
-                                        idx->stream));
-        SSW_TRY(fetch_results(idx, k, &count, &overflow));
-    }
-    const char *h = reinterpret_cast<const char *>(idx->res_host);
-    const uint64_t *keys = reinterpret_cast<const uint64_t *>(h + 16);
-    const uint32_t *best = reinterpret_cast<const uint32_t *>(h + 16 + (size_t)k * sizeof(uint64_t));
-    if (count > k) count = k;
-    for (int32_t i = 0; i < count; ++i) {
-        const uint64_t key = keys[i];
-        if (out_images) out_images[i] = (int64_t)(0xffffffffu - (uint32_t)(key & 0xffffffffull));
-        if (out_scores) out_scores[i] = ord_to_f32((uint32_t)(key >> 32));
-        if (out_best_rows) out_best_rows[i] = (int64_t)best[i];
-    }
-    *out_count = count;
-    return SSW_OK;
-}
-
+// ---- top-k of row scores that are resident on the device -> host: ONE path, in an enqueue and a collect half ----------
 // An index of a few thousand images (an LVIS-category subset: 1 109 images x 13 tiles) spends its round in fixed
-// costs, not in the scan: three copies, five launches and a stream wait were ~95 us around ~10 us of kernels.  This form
+// costs, not in the scan: three copies, five launches and a stream wait were ~95 us around ~10 us of kernels.  Its form
 // is three launches and no copy: the query goes to q_dev through a kernel argument, the scan runs on every CU, and ONE
 // kernel takes the per-image maximum, strikes out the excluded ids (read from pinned memory the device maps), selects
 // and writes the packed result into the same pinned block, releasing a sequence word the host spins on.
@@ -1024,10 +993,10 @@ static bool small_path_ok(const ssw_index *idx, int64_t n_excluded) {
            n_excluded <= SMALL_EXCL_CAP;
 }
 
-// enqueue half: [stage the query, scan,] exclusion list into the pinned block, ONE selection launch that publishes the
-// packed result under a fresh sequence number (idx->small_pending_seq)
-static ssw_status topk_small_enqueue(ssw_index *idx, const float *q_host, const int64_t *excluded_images, int64_t n_excluded,
-                                     int32_t k) {
+// the small form's enqueue: [stage the query, scan,] exclusion list into the pinned block, ONE selection launch that
+// publishes the packed result under a fresh sequence number (idx->small_pending_seq)
+static ssw_status small_enqueue(ssw_index *idx, const float *q_host, const float *scores, hipStream_t stream,
+                                const int64_t *excluded_images, int64_t n_excluded, int32_t k) {
     const size_t q_bytes = (size_t)idx->dim * sizeof(float), ex_bytes = (size_t)SMALL_EXCL_CAP * sizeof(int64_t);
     const size_t res_bytes = 16 + (size_t)SSW_MAX_TOPK * 12;
     if (!idx->small_host) {
@@ -1037,13 +1006,10 @@ static ssw_status topk_small_enqueue(ssw_index *idx, const float *q_host, const 
     }
     unsigned char *dev_view = nullptr;
     SSW_HIP_TRY(hipHostGetDevicePointer((void **)&dev_view, idx->small_host, 0));
-    for (int64_t i = 0; i < n_excluded; ++i) {
-        SSW_REQUIRE(excluded_images[i] >= 0 && excluded_images[i] < idx->n_images,
-                    "excluded image %lld outside [0, %lld)", (long long)excluded_images[i], (long long)idx->n_images);
-    }
+    SSW_TRY(check_excluded(idx, excluded_images, 0, n_excluded));
     SSW_TRY(ensure_ws(idx));
     if (idx->ws.excl_dirty)  // a list installed by ssw_index_set_excluded does not apply to this call
-        SSW_TRY(select_set_excluded(idx->ws, idx->n_images, nullptr, 0, idx->stream));
+        SSW_TRY(select_set_excluded(idx->ws, idx->n_images, nullptr, 0, stream));
     if (q_host) {
         if (idx->dim <= Q_ARG_FLOATS) {  // through a kernel argument into q_dev: 451 workgroups then read it out of L2
             SSW_TRY(stage_query(idx, q_host));
@@ -1054,29 +1020,49 @@ static ssw_status topk_small_enqueue(ssw_index *idx, const float *q_host, const 
         }
     }
     if (n_excluded > 0) memcpy(idx->small_host + q_bytes, excluded_images, (size_t)n_excluded * sizeof(int64_t));
-    unsigned seq = ++idx->small_seq;
-    if (seq == 0) seq = ++idx->small_seq;
-    SSW_TRY(launch_select_small(idx->ws, idx->scores, idx->has_map ? idx->row_start : nullptr, idx->n_images,
+    const unsigned seq = next_seq(idx->small_seq);
+    SSW_TRY(launch_select_small(idx->ws, scores, idx->has_map ? idx->row_start : nullptr, idx->n_images,
                                 reinterpret_cast<const int64_t *>(dev_view + q_bytes), n_excluded, k,
-                                dev_view + q_bytes + ex_bytes, seq, idx->stream));
+                                dev_view + q_bytes + ex_bytes, seq, stream));
     idx->small_pending_seq = seq;
     return SSW_OK;
 }
 
-// collect half: spin on the sequence word, decode the packed result
-static ssw_status topk_small_collect(ssw_index *idx, int32_t k, int64_t *out_images, float *out_scores, int64_t *out_best_rows,
-                                     int32_t *out_count) {
-    const size_t q_bytes = (size_t)idx->dim * sizeof(float), ex_bytes = (size_t)SMALL_EXCL_CAP * sizeof(int64_t);
-    const unsigned seq = idx->small_pending_seq;
-    SSW_REQUIRE(seq != 0 && idx->small_host != nullptr, "topk: no small selection in flight");
-    idx->small_pending_seq = 0;
-    unsigned char *res = idx->small_host + q_bytes + ex_bytes;
-    SSW_TRY(wait_host_seq(idx->stream, reinterpret_cast<const unsigned *>(res) + 3, seq));
-    const int32_t *hdr = reinterpret_cast<const int32_t *>(res);
-    int32_t count = hdr[0];
-    if (count > k) count = k;
-    const uint64_t *keys = reinterpret_cast<const uint64_t *>(res + 16);
-    const uint32_t *best = reinterpret_cast<const uint32_t *>(res + 16 + (size_t)k * sizeof(uint64_t));
+// the general form's selection (deep: the rerun after an overflow): its last kernel writes the packed result into the
+// pinned mirror and releases a fresh sequence word the host spins on (no device-to-host copy, no stream wait)
+static ssw_status select_to_host(ssw_index *idx, const float *scores, hipStream_t stream, int32_t k, bool deep) {
+    SSW_TRY(ensure_ws(idx));
+    SSW_TRY(ensure_res_host(idx));
+    SelectDest dest;
+    SSW_HIP_TRY(hipHostGetDevicePointer((void **)&dest.host_packed, idx->res_host, 0));
+    dest.seq = idx->res_pending_seq = next_seq(idx->small_seq);
+    idx->small_pending_seq = 0;  // this selection is the one in flight: topk_collect reads res_host
+    const ssw_status st = deep ? do_select_deep(idx, scores, k, dest, stream) : do_select(idx, scores, k, dest, stream);
+    if (st != SSW_OK) idx->res_pending_seq = 0;  // nothing was launched that would publish
+    return st;
+}
+
+// Enqueue half.  q_host = NULL: the top-k of the row scores in `scores`, which are complete (the handle's buffer after
+// ensure_full_scores, or a slab of a batch).  With a query, which is scanned into the handle's buffer on the handle's
+// stream, those are `scores` and `stream`: the query is staged and scanned first -- after the exclusions are
+// installed, a pruned scan selects its threshold with them.
+static ssw_status topk_enqueue(ssw_index *idx, const float *q_host, const float *scores, hipStream_t stream,
+                               const int64_t *excluded_images, int64_t n_excluded, int32_t k) {
+    SSW_REQUIRE(!q_host || (scores == idx->scores && stream == idx->stream), "topk: a query scans into the handle's buffer");
+    if (small_path_ok(idx, n_excluded)) return small_enqueue(idx, q_host, scores, stream, excluded_images, n_excluded, k);
+    if (q_host) SSW_TRY(stage_query(idx, q_host));
+    if (idx->n_images > 0) SSW_TRY(install_excluded(idx, excluded_images, n_excluded, stream));
+    if (q_host) SSW_TRY(scan_for_topk(idx, idx->q_dev, k));
+    if (idx->n_images == 0) return SSW_OK;
+    return select_to_host(idx, scores, stream, k, false);
+}
+
+// the packed block [count, overflow, k, seq][keys k][best k] -> the caller's arrays
+static void decode_packed(const unsigned char *block, int32_t k, int64_t *out_images, float *out_scores,
+                          int64_t *out_best_rows, int32_t *out_count) {
+    const uint64_t *keys = reinterpret_cast<const uint64_t *>(block + 16);
+    const uint32_t *best = reinterpret_cast<const uint32_t *>(block + 16 + (size_t)k * sizeof(uint64_t));
+    const int32_t count = std::min(*reinterpret_cast<const int32_t *>(block), k);
     for (int32_t i = 0; i < count; ++i) {
         const uint64_t key = keys[i];
         if (out_images) out_images[i] = (int64_t)(0xffffffffu - (uint32_t)(key & 0xffffffffull));
@@ -1084,54 +1070,85 @@ static ssw_status topk_small_collect(ssw_index *idx, int32_t k, int64_t *out_ima
         if (out_best_rows) out_best_rows[i] = (int64_t)best[i];
     }
     *out_count = count;
+}
+
+// the result of the last general selection into res_host: published there by the selection itself, else copied
+static ssw_status fetch_results(ssw_index *idx, hipStream_t stream, int32_t k, bool *overflow) {
+    SSW_TRY(ensure_res_host(idx));
+    if (idx->res_pending_seq != 0) {
+        const unsigned seq = idx->res_pending_seq;
+        idx->res_pending_seq = 0;
+        SSW_TRY(wait_host_seq(stream, reinterpret_cast<const unsigned *>(idx->res_host) + 3, seq));
+    } else {
+        SSW_HIP_TRY(hipMemcpyAsync(idx->res_host, idx->ws.packed, 16 + (size_t)k * 12, hipMemcpyDeviceToHost, stream));
+        SSW_HIP_TRY(hipStreamSynchronize(stream));
+    }
+    const int32_t *hdr = reinterpret_cast<const int32_t *>(idx->res_host);
+    *overflow = hdr[1] != 0;
+    if (hdr[2] != k) {
+        set_error("topk_fetch: k=%d does not match the k=%d of the selection that produced the result", k, hdr[2]);
+        return SSW_ERR_INVALID;
+    }
     return SSW_OK;
 }
 
-static ssw_status topk_small(ssw_index *idx, const float *q_host, const int64_t *excluded_images, int64_t n_excluded,
-                             int32_t k, int64_t *out_images, float *out_scores, int64_t *out_best_rows,
-                             int32_t *out_count) {
-    SSW_TRY(topk_small_enqueue(idx, q_host, excluded_images, n_excluded, k));
-    return topk_small_collect(idx, k, out_images, out_scores, out_best_rows, out_count);
+// The general form's result over `scores`: the wait (a spin on the sequence word; without a selection in flight the
+// result of the last ssw_index_topk_dev / _select_deep_dev, copied), the deep rerun when the fast selection
+// overflowed, the decode.
+static ssw_status fetch_topk(ssw_index *idx, const float *scores, hipStream_t stream, int32_t k, int64_t *out_images,
+                             float *out_scores, int64_t *out_best_rows, int32_t *out_count) {
+    SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
+    *out_count = 0;
+    if (idx->n_images == 0) return SSW_OK;
+    SSW_TRY(ensure_ws(idx));
+    bool overflow = false;
+    SSW_TRY(fetch_results(idx, stream, k, &overflow));
+    if (overflow) {  // massive exact ties: rerun the selection on the deep path (over the per-image maxima the fast
+                     // selection left in the workspace; `scores` itself is read only by an index without an image map)
+        SSW_TRY(select_to_host(idx, scores, stream, k, true));
+        SSW_TRY(fetch_results(idx, stream, k, &overflow));
+    }
+    decode_packed(static_cast<const unsigned char *>(idx->res_host), k, out_images, out_scores, out_best_rows, out_count);
+    return SSW_OK;
 }
 
-// ---- the two halves of ssw_index_topk(q = NULL) for callers that put more work on the stream in between or ahead
-// (ssw_labelprop_round: propagation -> scores -> this selection, ONE wait).  `on_stream` replaces the handle's stream for
-// the duration of the call; the caller has made sure the handle's own stream is idle (ssw_index_sync).
+// Collect half of topk_enqueue
+static ssw_status topk_collect(ssw_index *idx, const float *scores, hipStream_t stream, int32_t k, int64_t *out_images,
+                               float *out_scores, int64_t *out_best_rows, int32_t *out_count) {
+    *out_count = 0;
+    if (idx->small_pending_seq == 0) return fetch_topk(idx, scores, stream, k, out_images, out_scores, out_best_rows, out_count);
+    const unsigned seq = idx->small_pending_seq;
+    idx->small_pending_seq = 0;
+    const unsigned char *res = idx->small_host + (size_t)idx->dim * sizeof(float) + (size_t)SMALL_EXCL_CAP * sizeof(int64_t);
+    SSW_TRY(wait_host_seq(stream, reinterpret_cast<const unsigned *>(res) + 3, seq));
+    decode_packed(res, k, out_images, out_scores, out_best_rows, out_count);
+    return SSW_OK;
+}
+
+ssw_status ssw_index_topk_fetch(ssw_index *idx, int32_t k, int64_t *out_images, float *out_scores,
+                                int64_t *out_best_rows, int32_t *out_count) {
+    SSW_REQUIRE(idx != nullptr && out_count != nullptr, "NULL argument");
+    DeviceGuard guard(idx->device);
+    return fetch_topk(idx, idx->scores, idx->stream, k, out_images, out_scores, out_best_rows, out_count);
+}
+
+// ---- the two halves for callers that put more work on the stream in between or ahead (ssw_labelprop_round:
+// propagation -> scores -> this selection, ONE wait), on a stream of theirs
 extern "C++" {
 namespace ssw {
-struct StreamSwap {
-    ssw_index *idx;
-    hipStream_t keep;
-    StreamSwap(ssw_index *i, hipStream_t s) : idx(i), keep(i->stream) { idx->stream = s; }
-    ~StreamSwap() { idx->stream = keep; }
-};
-
 ssw_status index_enqueue_topk_resident(ssw_index *idx, hipStream_t on_stream, const int64_t *excluded_images, int64_t n_excluded,
                                        int32_t k) {
     SSW_REQUIRE(idx != nullptr, "NULL argument");
     SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
     SSW_REQUIRE(n_excluded == 0 || excluded_images != nullptr, "excluded_images is NULL");
-    StreamSwap sw(idx, on_stream);
-    SSW_TRY(ensure_full_scores(idx));
-    if (small_path_ok(idx, n_excluded)) return topk_small_enqueue(idx, nullptr, excluded_images, n_excluded, k);
-    if (idx->n_images == 0) return SSW_OK;
-    SSW_TRY(ssw_index_set_excluded(idx, excluded_images, n_excluded));
-    SSW_TRY(arm_host_result(idx));
-    const ssw_status st = do_select(idx, k);
-    if (st != SSW_OK) {
-        idx->ws.host_packed = nullptr;
-        idx->res_pending_seq = 0;
-    }
-    return st;
+    SSW_TRY(ensure_full_scores(idx, on_stream));
+    return topk_enqueue(idx, nullptr, idx->scores, on_stream, excluded_images, n_excluded, k);
 }
 
 ssw_status index_collect_topk(ssw_index *idx, hipStream_t on_stream, int32_t k, int64_t *out_images, float *out_scores,
                               int64_t *out_best_rows, int32_t *out_count) {
     SSW_REQUIRE(idx != nullptr && out_count != nullptr, "NULL argument");
-    *out_count = 0;
-    StreamSwap sw(idx, on_stream);
-    if (idx->small_pending_seq != 0) return topk_small_collect(idx, k, out_images, out_scores, out_best_rows, out_count);
-    return ssw_index_topk_fetch(idx, k, out_images, out_scores, out_best_rows, out_count);
+    return topk_collect(idx, idx->scores, on_stream, k, out_images, out_scores, out_best_rows, out_count);
 }
 
 int index_device(const ssw_index *idx) { return idx ? idx->device : -1; }
@@ -1152,62 +1169,43 @@ ssw_status ssw_index_topk(ssw_index *idx, const float *q_host, const int64_t *ex
     SSW_REQUIRE(n_excluded == 0 || excluded_images != nullptr, "excluded_images is NULL");
     *out_count = 0;
     DeviceGuard guard(idx->device);
-    if (small_path_ok(idx, n_excluded)) {
-        if (q_host) SSW_TRY(check_query(idx, q_host));
-        return topk_small(idx, q_host, excluded_images, n_excluded, k, out_images, out_scores, out_best_rows, out_count);
-    }
-    if (q_host) {
-        SSW_TRY(check_query(idx, q_host));
-        SSW_TRY(stage_query(idx, q_host));
-    } else {
-        SSW_TRY(ensure_full_scores(idx));
-    }
-    // the exclusions first: a pruned scan selects its threshold with them
-    if (idx->n_images > 0) SSW_TRY(ssw_index_set_excluded(idx, excluded_images, n_excluded));
-    if (q_host) SSW_TRY(scan_for_topk(idx, idx->q_dev, k));
-    if (idx->n_images == 0) return SSW_OK;
-    // the selection's last kernel writes the packed result into the pinned mirror and releases a sequence word: the
-    // host spins on it (no device-to-host copy, no stream wait)
-    SSW_TRY(arm_host_result(idx));
-    const ssw_status st = do_select(idx, k);
-    if (st != SSW_OK) {  // nothing was launched that would publish: disarm
-        idx->ws.host_packed = nullptr;
-        idx->res_pending_seq = 0;
-        return st;
-    }
-    return ssw_index_topk_fetch(idx, k, out_images, out_scores, out_best_rows, out_count);
+    if (q_host) SSW_TRY(check_query(idx, q_host));
+    else SSW_TRY(ensure_full_scores(idx));
+    SSW_TRY(topk_enqueue(idx, q_host, idx->scores, idx->stream, excluded_images, n_excluded, k));
+    return topk_collect(idx, idx->scores, idx->stream, k, out_images, out_scores, out_best_rows, out_count);
 }
 
 // ---- several queries in one pass over the rows (scan.hip: batch_scores_kernel) --------------------------------------
 // A batch is cut into chunks of the widest kernel form the shape and the side buffer allow, the remainder into
 // narrower ones and at last single queries.  A chunk's last query scores into the handle's own buffer, the others into
-// the side slabs; the selection then runs slab by slab through the single-query path with `scores` pointing at the slab.
+// the side slabs; the selection then runs slab by slab through the single-query path (topk_enqueue / topk_collect).
 constexpr int BATCH_MAX_WIDTH = 16;
 
 static int64_t slab_stride(const ssw_index *idx) { return (idx->n + 64 + 63) & ~(int64_t)63; }  // slabs stay 256-byte aligned
 
 // the chunk width to use for nq queries: limited by the shape, by nq and by what the side buffer could be grown to
 static ssw_status batch_width(ssw_index *idx, int32_t nq, int *out_w) {
+    BatchState &bt = idx->batch;
     int w = scan_batch_max_width(idx->n, idx->dim, idx->dtype);
     if (w > BATCH_MAX_WIDTH) w = BATCH_MAX_WIDTH;
     while (w > nq) w >>= 1;
-    if (w >= 2 && !idx->qb_dev) {
-        if (hipMalloc((void **)&idx->qb_dev, (size_t)BATCH_MAX_WIDTH * idx->dim * sizeof(float)) != hipSuccess) {
+    if (w >= 2 && !bt.qb_dev) {
+        if (hipMalloc((void **)&bt.qb_dev, (size_t)BATCH_MAX_WIDTH * idx->dim * sizeof(float)) != hipSuccess) {
             (void)hipGetLastError();
-            idx->qb_dev = nullptr;
+            bt.qb_dev = nullptr;
             w = 1;
         }
     }
-    while (w >= 2 && idx->side_slabs < w - 1) {  // grow; on failure keep halving the width
+    while (w >= 2 && bt.side_slabs < w - 1) {  // grow; on failure keep halving the width
         SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
-        (void)hipFree(idx->side);
-        idx->side = nullptr;
-        idx->side_slabs = 0;
-        if (hipMalloc((void **)&idx->side, (size_t)(w - 1) * slab_stride(idx) * sizeof(float)) == hipSuccess) {
-            idx->side_slabs = w - 1;
+        (void)hipFree(bt.side);
+        bt.side = nullptr;
+        bt.side_slabs = 0;
+        if (hipMalloc((void **)&bt.side, (size_t)(w - 1) * slab_stride(idx) * sizeof(float)) == hipSuccess) {
+            bt.side_slabs = w - 1;
         } else {
             (void)hipGetLastError();
-            idx->side = nullptr;
+            bt.side = nullptr;
             w >>= 1;
         }
     }
@@ -1217,18 +1215,14 @@ static ssw_status batch_width(ssw_index *idx, int32_t nq, int *out_w) {
 
 // queries [w, dim] (host) -> one launch that fills slab[j] = scores of query j; slab[w - 1] is the handle's buffer
 static ssw_status do_scan_chunk(ssw_index *idx, const float *q_host, int w, float **slab) {
-    for (int j = 0; j + 1 < w; ++j) slab[j] = idx->side + (int64_t)j * slab_stride(idx);
+    BatchState &bt = idx->batch;
+    for (int j = 0; j + 1 < w; ++j) slab[j] = bt.side + (int64_t)j * slab_stride(idx);
     slab[w - 1] = idx->scores;
-    SSW_TRY(idx->qb_stage.push(idx->qb_dev, q_host, (size_t)w * idx->dim * sizeof(float), idx->stream));
+    SSW_TRY(bt.qb_stage.push(bt.qb_dev, q_host, (size_t)w * idx->dim * sizeof(float), idx->stream));
     idx->scores_partial = false;
-    const bool prof = idx->profiling && idx->ev_used + 2 <= (int)idx->ev.size();
-    if (prof) SSW_HIP_TRY(hipEventRecord(idx->ev[idx->ev_used], idx->stream));
-    SSW_TRY(launch_scan_batch(idx->X, idx->dtype, idx->qb_dev, slab, w, idx->n, idx->dim, idx->device, idx->stream));
-    if (prof) {
-        SSW_HIP_TRY(hipEventRecord(idx->ev[idx->ev_used + 1], idx->stream));
-        idx->ev_used += 2;
-    }
-    return SSW_OK;
+    return profiled(idx, [&] {
+        return launch_scan_batch(idx->X, idx->dtype, bt.qb_dev, slab, w, idx->n, idx->dim, idx->device, idx->stream);
+    });
 }
 
 static ssw_status check_query_batch(const ssw_index *idx, const float *q_host, int32_t nq) {
@@ -1241,29 +1235,6 @@ static ssw_status check_query_batch(const ssw_index *idx, const float *q_host, i
         }
     }
     return SSW_OK;
-}
-
-// the selection half of ssw_index_topk over the scores in `slab` (which may be the handle's own buffer)
-static ssw_status select_slab(ssw_index *idx, float *slab, const int64_t *excluded_images, int64_t n_excluded, int32_t k,
-                              int64_t *out_images, float *out_scores, int64_t *out_best_rows, int32_t *out_count) {
-    struct Swap {  // every kernel of the selection (and the deep rerun of the fetch) reads idx->scores
-        ssw_index *idx;
-        float *keep;
-        Swap(ssw_index *i, float *s) : idx(i), keep(i->scores) { idx->scores = s; }
-        ~Swap() { idx->scores = keep; }
-    } swap(idx, slab);
-    if (small_path_ok(idx, n_excluded))
-        return topk_small(idx, nullptr, excluded_images, n_excluded, k, out_images, out_scores, out_best_rows, out_count);
-    if (idx->n_images == 0) return SSW_OK;
-    SSW_TRY(ssw_index_set_excluded(idx, excluded_images, n_excluded));
-    SSW_TRY(arm_host_result(idx));
-    const ssw_status st = do_select(idx, k);
-    if (st != SSW_OK) {
-        idx->ws.host_packed = nullptr;
-        idx->res_pending_seq = 0;
-        return st;
-    }
-    return ssw_index_topk_fetch(idx, k, out_images, out_scores, out_best_rows, out_count);
 }
 
 ssw_status ssw_index_scan_batch(ssw_index *idx, const float *q_host, int32_t nq, float *out_scores_host) {
@@ -1309,9 +1280,7 @@ ssw_status ssw_index_topk_batch(ssw_index *idx, const float *q_host, int32_t nq,
         for (int32_t b = 0; b < nq; ++b)
             SSW_REQUIRE(excluded_offsets[b] <= excluded_offsets[b + 1], "excluded_offsets decrease at query %d", b);
         SSW_REQUIRE(excluded_offsets[nq] == excluded_offsets[0] || excluded_images != nullptr, "excluded_images is NULL");
-        for (int64_t i = excluded_offsets[0]; i < excluded_offsets[nq]; ++i)
-            SSW_REQUIRE(excluded_images[i] >= 0 && excluded_images[i] < idx->n_images,
-                        "excluded image %lld outside [0, %lld)", (long long)excluded_images[i], (long long)idx->n_images);
+        SSW_TRY(check_excluded(idx, excluded_images, excluded_offsets[0], excluded_offsets[nq]));
     }
     SSW_TRY(check_query_batch(idx, q_host, nq));
     for (int32_t b = 0; b < nq; ++b) out_counts[b] = 0;
@@ -1345,9 +1314,10 @@ ssw_status ssw_index_topk_batch(ssw_index *idx, const float *q_host, int32_t nq,
             int64_t n_ex = 0;
             const int64_t *ex = excl(b + j, &n_ex);
             const size_t o = (size_t)(b + j) * k;
-            SSW_TRY(select_slab(idx, slab[j], ex, n_ex, k, out_images ? out_images + o : nullptr,
-                                out_scores ? out_scores + o : nullptr, out_best_rows ? out_best_rows + o : nullptr,
-                                out_counts + b + j));
+            SSW_TRY(topk_enqueue(idx, nullptr, slab[j], idx->stream, ex, n_ex, k));
+            SSW_TRY(topk_collect(idx, slab[j], idx->stream, k, out_images ? out_images + o : nullptr,
+                                 out_scores ? out_scores + o : nullptr, out_best_rows ? out_best_rows + o : nullptr,
+                                 out_counts + b + j));
         }
         b += w;
     }
@@ -1507,7 +1477,7 @@ ssw_status ssw_tune_prune_scan(int32_t blocks_per_cu, int32_t group_loads) {
 }
 
 // ---- the pre-scan's intermediate state (tests/test_prune_certificate_gpu.py) ----------------------------------------
-// Each hook drives the product's kernels through the launch_* functions scan_for_topk uses, on the index's own buffers.
+// Each hook drives the product's kernels through the steps scan_for_topk is made of, on the index's own buffers.
 ssw_status ssw_debug_prune_shadow(ssw_index *idx, int64_t first_row, int64_t n_rows, int8_t *out_codes, float *out_scale,
                                   float *out_err) {
     SSW_REQUIRE(idx != nullptr, "idx is NULL");
@@ -1522,13 +1492,13 @@ ssw_status ssw_debug_prune_shadow(ssw_index *idx, int64_t first_row, int64_t n_r
         return SSW_ERR_NOMEM;
     }
     if (n_rows > 0 && out_codes)
-        SSW_HIP_TRY(hipMemcpyAsync(out_codes, idx->q8 + first_row * idx->dim, (size_t)n_rows * idx->dim,
+        SSW_HIP_TRY(hipMemcpyAsync(out_codes, idx->prune.q8 + first_row * idx->dim, (size_t)n_rows * idx->dim,
                                    hipMemcpyDeviceToHost, idx->stream));
     if (n_rows > 0 && out_scale)
-        SSW_HIP_TRY(hipMemcpyAsync(out_scale, idx->q8_scale + first_row, (size_t)n_rows * sizeof(float),
+        SSW_HIP_TRY(hipMemcpyAsync(out_scale, idx->prune.q8_scale + first_row, (size_t)n_rows * sizeof(float),
                                    hipMemcpyDeviceToHost, idx->stream));
     if (n_rows > 0 && out_err)
-        SSW_HIP_TRY(hipMemcpyAsync(out_err, idx->q8_err + first_row, (size_t)n_rows * sizeof(float),
+        SSW_HIP_TRY(hipMemcpyAsync(out_err, idx->prune.q8_err + first_row, (size_t)n_rows * sizeof(float),
                                    hipMemcpyDeviceToHost, idx->stream));
     SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
     return SSW_OK;
@@ -1548,12 +1518,9 @@ ssw_status ssw_debug_prune_bounds(ssw_index *idx, const float *q_host, float *ou
         return SSW_ERR_NOMEM;
     }
     SSW_TRY(idx->q_stage.push(idx->q_dev, q_host, (size_t)idx->dim * sizeof(float), idx->stream));
-    SSW_TRY(launch_q8_query(idx->q_dev, idx->dim, idx->q_last, idx->prune_state, idx->stream));
-    SSW_TRY(launch_q8_bounds(idx->q8, idx->q8_scale, idx->q8_err, idx->q_last, idx->prune_state, idx->scores, idx->n,
-                             idx->dim, idx->device, idx->stream));
-    idx->scores_partial = true;  // as after scan_for_topk: every reader completes the buffer with the scan of q_last
+    SSW_TRY(prune_bounds(idx, idx->q_dev));  // as in scan_for_topk: every reader completes the buffer with the scan of q_last
     unsigned state[4] = {0u, 0u, 0u, 0u};
-    SSW_HIP_TRY(hipMemcpyAsync(state, idx->prune_state, sizeof(state), hipMemcpyDeviceToHost, idx->stream));
+    SSW_HIP_TRY(hipMemcpyAsync(state, idx->prune.state, sizeof(state), hipMemcpyDeviceToHost, idx->stream));
     SSW_HIP_TRY(hipMemcpyAsync(out_lb, idx->scores, (size_t)idx->n * sizeof(float), hipMemcpyDeviceToHost, idx->stream));
     SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
     memcpy(out_Q, &state[1], sizeof(float));
@@ -1567,7 +1534,7 @@ ssw_status ssw_debug_prune_survivors(ssw_index *idx, float threshold, int32_t k,
     SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
     SSW_REQUIRE(cap >= 0 && cap <= SURV_CAP, "cap=%lld outside [0, %lld]", (long long)cap, (long long)SURV_CAP);
     SSW_REQUIRE(cap == 0 || out_rows != nullptr, "out_rows is NULL");
-    SSW_REQUIRE(idx->scores_partial && idx->q8 && !idx->q8_stale, "no bounds in the buffer: ssw_debug_prune_bounds first");
+    SSW_REQUIRE(idx->scores_partial && idx->prune.q8 && !idx->prune.stale, "no bounds in the buffer: ssw_debug_prune_bounds first");
     DeviceGuard guard(idx->device);
     SSW_TRY(ensure_ws(idx));
     // what the threshold selection leaves behind: k keys (only the k-th is read) and [count, overflow]
@@ -1576,20 +1543,14 @@ ssw_status ssw_debug_prune_survivors(ssw_index *idx, float threshold, int32_t k,
     SSW_HIP_TRY(hipMemcpyAsync(idx->ws.out_keys, keys.data(), keys.size() * sizeof(uint64_t), hipMemcpyHostToDevice,
                                idx->stream));
     SSW_HIP_TRY(hipMemcpyAsync(idx->ws.out_count, count, sizeof(count), hipMemcpyHostToDevice, idx->stream));
-    SSW_HIP_TRY(hipMemsetAsync(idx->prune_state, 0, sizeof(unsigned), idx->stream));  // the counter k_q8_query resets
+    SSW_HIP_TRY(hipMemsetAsync(idx->prune.state, 0, sizeof(unsigned), idx->stream));  // the counter k_q8_query resets
     SSW_HIP_TRY(hipStreamSynchronize(idx->stream));  // keys and count are pageable host memory
-    unsigned seq = ++idx->prune_seq;
-    if (seq == 0) seq = ++idx->prune_seq;
-    int32_t *host_dev = nullptr;
-    SSW_HIP_TRY(hipHostGetDevicePointer((void **)&host_dev, idx->prune_host, 0));
-    SSW_TRY(launch_survivors(idx->scores, idx->q8_err, idx->n, idx->ws.out_keys, idx->ws.out_count, k, idx->prune_state,
-                             idx->surv_rows, cap, host_dev, seq, idx->device, idx->stream));
-    SSW_TRY(wait_host_seq(idx->stream, reinterpret_cast<const unsigned *>(idx->prune_host), seq));
-    const int32_t m = __atomic_load_n(idx->prune_host + 1, __ATOMIC_ACQUIRE);
+    int32_t m = -1;
+    SSW_TRY(prune_survivors(idx, k, cap, nullptr, &m));
     unsigned collected = 0u;
-    SSW_HIP_TRY(hipMemcpyAsync(&collected, idx->prune_state, sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
+    SSW_HIP_TRY(hipMemcpyAsync(&collected, idx->prune.state, sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
     if (m > 0)
-        SSW_HIP_TRY(hipMemcpyAsync(out_rows, idx->surv_rows, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost,
+        SSW_HIP_TRY(hipMemcpyAsync(out_rows, idx->prune.surv_rows, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost,
                                    idx->stream));
     SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
     *out_published = m;

@@ -762,8 +762,16 @@ ssw_status launch_select_small(SelectWorkspace &ws, const float *row_scores, con
     return SSW_OK;
 }
 
+// the packed block and the side outputs of k_final for one selection
+static FinalExchange final_outputs(const SelectWorkspace &ws, SelectDest dest, unsigned char **packed) {
+    *packed = dest.host_packed ? dest.host_packed : ws.packed;
+    FinalExchange x = dest.message ? ws.xchg : FinalExchange();
+    x.host_seq = dest.host_packed ? dest.seq : 0u;
+    return x;
+}
+
 ssw_status launch_select_topk(SelectWorkspace &ws, const float *values, int64_t m,
-                              const uint32_t *best_rows_or_null, int32_t k, int device,
+                              const uint32_t *best_rows_or_null, int32_t k, SelectDest dest, int device,
                               hipStream_t stream) {
     if (k < 1 || k > SSW_MAX_TOPK) {
         set_error("topk: k=%d outside [1, %d]", k, SSW_MAX_TOPK);
@@ -775,10 +783,8 @@ ssw_status launch_select_topk(SelectWorkspace &ws, const float *values, int64_t 
     }
     SSW_TRY(exchange_fits(ws, k));
     const uint32_t *excl = ws.excl_dirty ? ws.excl_bits : nullptr;
-    unsigned char *packed = ws.host_packed ? ws.host_packed : ws.packed;
-    FinalExchange xg = ws.xchg;
-    xg.host_seq = ws.host_packed ? ws.host_seq : 0u;
-    ws.host_packed = nullptr;
+    unsigned char *packed = nullptr;
+    FinalExchange xg = final_outputs(ws, dest, &packed);
     if (m <= FINAL_CAP) {  // one launch: the sort takes every image
         FinalExchange x = xg;
         x.values_all = values;
@@ -817,9 +823,8 @@ ssw_status launch_select_topk(SelectWorkspace &ws, const float *values, int64_t 
     return SSW_OK;
 }
 
-
 ssw_status launch_select_topk_deep(SelectWorkspace &ws, const float *values, int64_t m,
-                                   const uint32_t *best_rows_or_null, int32_t k, int device,
+                                   const uint32_t *best_rows_or_null, int32_t k, SelectDest dest, int device,
                                    hipStream_t stream) {
     if (k < 1 || k > SSW_MAX_TOPK) {
         set_error("topk: k=%d outside [1, %d]", k, SSW_MAX_TOPK);
@@ -857,10 +862,8 @@ ssw_status launch_select_topk_deep(SelectWorkspace &ws, const float *values, int
     hipLaunchKernelGGL(k_collect_deep, dim3(g), dim3(256), 0, stream, values, m, excl, ws.state,
                        ws.cand, threshold);
     SSW_TRY(final_lds_ready());
-    unsigned char *packed = ws.host_packed ? ws.host_packed : ws.packed;
-    FinalExchange xg = ws.xchg;
-    xg.host_seq = ws.host_packed ? ws.host_seq : 0u;
-    ws.host_packed = nullptr;
+    unsigned char *packed = nullptr;
+    FinalExchange xg = final_outputs(ws, dest, &packed);
     hipLaunchKernelGGL(k_final, dim3(1), dim3(1024), FINAL_LDS_BYTES, stream, ws.cand,
                        0, 0, (const int32_t *)nullptr, ws.state + ST_NCAND, (const uint32_t *)ws.state, (int)k,
                        best_rows_or_null, ws.out_keys, ws.out_count, ws.out_best, packed, xg);

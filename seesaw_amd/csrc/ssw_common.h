@@ -121,7 +121,9 @@ struct PinnedStage {
 
 // ---- launchers implemented in the kernel translation units -----------------
 
-// capi_index.hip: the two halves of ssw_index_topk(q = NULL) on a stream of the caller's (ssw_labelprop_round)
+// capi_index.hip: the two halves of ssw_index_topk(q = NULL) on a stream of the caller's (ssw_labelprop_round), which
+// has made sure that the handle's own stream is idle (ssw_index_sync) and holds a DeviceGuard on the index's device
+// (neither half sets the device itself)
 ssw_status index_enqueue_topk_resident(ssw_index *idx, hipStream_t on_stream, const int64_t *excluded_images, int64_t n_excluded,
                                        int32_t k);
 ssw_status index_collect_topk(ssw_index *idx, hipStream_t on_stream, int32_t k, int64_t *out_images, float *out_scores,
@@ -301,10 +303,13 @@ struct SelectWorkspace {
     int64_t n_excluded_distinct = 0;  // distinct excluded images currently installed
     bool excl_dirty = false;          // bitmap currently has bits set
     std::vector<int64_t> excl_installed;  // the installed set, sorted: a new list costs its difference from this one
-    // when set, the next selection writes its packed result here (pinned host memory, device view) and releases
-    // host_seq into header word 3 instead of filling `packed`; cleared by the launch
-    unsigned char *host_packed = nullptr;
-    unsigned host_seq = 0;
+};
+
+// where the last kernel of one selection leaves its result
+struct SelectDest {
+    unsigned char *host_packed = nullptr;  // pinned host block (device view) instead of ws.packed ...
+    unsigned seq = 0;                      // ... whose header word 3 receives seq, released to the host
+    bool message = true;                   // write the message of ws.xchg too, when a target is attached
 };
 
 #ifdef SSW_DEBUG_HOOKS
@@ -318,9 +323,9 @@ ssw_status select_set_excluded(SelectWorkspace &ws, int64_t n_images, const int6
 // per-image max over contiguous row ranges (row_start [n_images+1]).
 ssw_status launch_image_max(const float *scores, const int64_t *row_start, int64_t n_images,
                             float *img_score, uint32_t *img_best, hipStream_t stream);
-// top-k over values[m] (f32), skipping ids whose excl bit is set. Results in ws.out_*.
+// top-k over values[m] (f32), skipping ids whose excl bit is set. Results in ws.out_* and where dest says.
 ssw_status launch_select_topk(SelectWorkspace &ws, const float *values, int64_t m,
-                              const uint32_t *best_rows_or_null, int32_t k, int device,
+                              const uint32_t *best_rows_or_null, int32_t k, SelectDest dest, int device,
                               hipStream_t stream);
 // small index (n_images <= SELECT_SMALL_IMAGES): per-image max, exclusion by id list, selection and the packed result
 // into pinned host memory in ONE launch; the host waits for header word 3 == seq (see FinalExchange)
@@ -331,7 +336,7 @@ ssw_status launch_select_small(SelectWorkspace &ws, const float *row_scores, con
 // the fast path flags (out_count[1]) a 24-bit prefix bin with more candidates than the final
 // sort can take (massive exact ties); the caller then reruns the selection on the deep path.
 ssw_status launch_select_topk_deep(SelectWorkspace &ws, const float *values, int64_t m,
-                                   const uint32_t *best_rows_or_null, int32_t k, int device,
+                                   const uint32_t *best_rows_or_null, int32_t k, SelectDest dest, int device,
                                    hipStream_t stream);
 ssw_status launch_merge_topk(const uint64_t *keys_in, int32_t n_lists, int32_t list_stride,
                              const int32_t *counts, int32_t k, uint64_t *keys_out,
