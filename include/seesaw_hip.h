@@ -172,6 +172,24 @@ ssw_status ssw_index_topk_batch(ssw_index *idx, const float *q_host, int32_t nq,
                                 const int64_t *excluded_offsets, int32_t k, int64_t *out_images, float *out_scores,
                                 int64_t *out_best_rows, int32_t *out_counts);
 
+/* ssw_index_topk_batch with the certified int8 pre-scan (ssw_index_prune_stats) shared by a chunk of up to 16 queries:
+ * arguments, results, errors and the deep-selection case exactly as ssw_index_topk_batch; every query's row is the
+ * bits of ssw_index_topk for it.  On an index the single call would prune (own rows, dim 256 / 512 / 1024, at least
+ * 2^22 rows, the shadow not refused for memory) a chunk is ONE pass over the int8 shadow on the int8 matrix core
+ * (v_mfma_i32_16x16x64_i8: the queries are quantised to two int8 planes, the integer sums are exact) that writes a
+ * certified lower bound of every row for every query; per query a threshold selection, the survivors and their exact
+ * rescoring follow, with ONE host wait per chunk, and then the ordinary selection.  A query that cannot be bounded (zero,
+ * norm above 2^40, largest element outside [2^-60, 2^60]), one with more than 2^18 survivors or fewer than k keys runs
+ * the full scan by itself.  Any other index takes ssw_index_topk_batch itself and leaves the prune counters alone.
+ * State afterwards: that of a pruned ssw_index_topk of the last query with its excluded list (the resident scores are
+ * completed by the first reader).  ssw_index_prune_stats counts every query of a pruned batch in [3] and every one that
+ * fell back in [4]; [2] is the last query's.  ssw_index_profile records one event pair per chunk.
+ * Memory: the side buffer of ssw_index_topk_batch at up to 15 slabs (f16 rows too) and 16 survivor lists of 3 MiB; a
+ * failed allocation narrows the chunk.  Opt-in: nothing dispatches to it silently. */
+ssw_status ssw_index_topk_batch_pruned(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
+                                       const int64_t *excluded_offsets, int32_t k, int64_t *out_images,
+                                       float *out_scores, int64_t *out_best_rows, int32_t *out_counts);
+
 /* device-resident form used by bench.py and the sharded index: q_dev [dim] f32;
  * the excluded set is whatever the last ssw_index_set_excluded installed; results
  * stay on the device in the handle's result buffers (ssw_index_result_ptrs).

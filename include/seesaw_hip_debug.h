@@ -71,6 +71,29 @@ ssw_status ssw_debug_prune_bounds(ssw_index *idx, const float *q_host, float *ou
 ssw_status ssw_debug_prune_survivors(ssw_index *idx, float threshold, int32_t k, int32_t sel_count, int32_t sel_overflow,
                                      int64_t cap, int32_t *out_published, int64_t *out_collected, int64_t *out_rows);
 
+/* The pruned batch (seesaw_hip.h, ssw_index_topk_batch_pruned).
+ * ssw_tune_prune_scan_mq: the launch shape of its shadow scan (k_q8_bounds_mq): four-wave blocks per CU (1 .. 8) and
+ *   16-row tiles a wave requests at a time (1, 2 or 4, as far as two register sets of them fit: tiles x dim <= 1024);
+ *   any other value = the product's (1 block; 2 tiles at dim 256 and 512, 1 at dim 1024).  ssw_tune_prune's min_rows
+ *   and reserve apply to the pruned batch as well.
+ * ssw_debug_prune_scan_mq_shape: the blocks and tiles the next launch over this index would use (a wave's request is
+ *   16 x tiles rows; a launch has 4 x blocks waves).
+ * ssw_debug_prune_bounds_mq: k_q8_query_mq + k_q8_bounds_mq for nq <= 16 host queries (non-finite ones allowed: they are
+ *   flagged) on the index's own buffers, with the kernel's debug flag on when an integer output is asked for.
+ *   out_I_hi / out_I_lo [nq, n] = the exact int32 sums of a row's codes with the query's two code planes, out_lb [nq, n],
+ *   out_Qe [nq, 4] = Q, e, t2 and the "cannot be bounded" word (0 / 1) as floats, out_codes [nq, 2, dim] = the hi and
+ *   the lo plane in natural element order.  Any output may be NULL.  The handle is left as after the product's shadow
+ *   scan of the chunk: partial, the last query kept.
+ * ssw_debug_prune_survivors_mq: k_survivors_mq for one slot of the chunk of nq queries the last ssw_debug_prune_bounds_mq
+ *   bounded, then k_prune_publish_mq; arguments and outputs as ssw_debug_prune_survivors. */
+ssw_status ssw_tune_prune_scan_mq(int32_t blocks_per_cu, int32_t tiles);
+ssw_status ssw_debug_prune_scan_mq_shape(ssw_index *idx, int32_t *out_blocks, int32_t *out_tiles);
+ssw_status ssw_debug_prune_bounds_mq(ssw_index *idx, const float *q_host, int32_t nq, int32_t *out_I_hi, int32_t *out_I_lo,
+                                     float *out_lb, float *out_Qe, int8_t *out_codes);
+ssw_status ssw_debug_prune_survivors_mq(ssw_index *idx, int32_t nq, int32_t slot, float threshold, int32_t k,
+                                        int32_t sel_count, int32_t sel_overflow, int64_t cap, int32_t *out_published,
+                                        int64_t *out_collected, int64_t *out_rows);
+
 /* Kernel A/B harness for the towers' bf16 GEMM (C[M,N] = A[M,K] W[N,K]^T + epilogue `epi`, see
  * csrc/gemm_bf16.hip): runs `variant` on seeded operands, reports ms per launch over `iters`
  * launches and the max |difference| to variant 0.  Not part of the reference's interface. */

@@ -66,6 +66,8 @@ _SIGNATURES = {
     "ssw_index_scan_batch": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p]),
     "ssw_index_topk_batch": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p,
                                      c_void_p]),
+    "ssw_index_topk_batch_pruned": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p, c_void_p,
+                                            c_void_p, c_void_p]),
     "ssw_index_set_excluded": (c_i32, [c_void_p, c_void_p, c_i64]),
     "ssw_index_topk_dev": (c_i32, [c_void_p, c_void_p, c_i32]),
     "ssw_index_set_tile_meta": (c_i32, [c_void_p, c_void_p, c_void_p]),
@@ -156,6 +158,11 @@ _DEBUG_SIGNATURES = {
     "ssw_tune_topk": (c_i32, [c_i32]),
     "ssw_tune_prune": (c_i32, [c_i32, c_i64, c_i64]),
     "ssw_tune_prune_scan": (c_i32, [c_i32, c_i32]),
+    "ssw_tune_prune_scan_mq": (c_i32, [c_i32, c_i32]),
+    "ssw_debug_prune_scan_mq_shape": (c_i32, [c_void_p, c_i32_p, c_i32_p]),
+    "ssw_debug_prune_bounds_mq": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ssw_debug_prune_survivors_mq": (c_i32, [c_void_p, c_i32, c_i32, ctypes.c_float, c_i32, c_i32, c_i32, c_i64, c_i32_p,
+                                             c_i64_p, c_void_p]),
     "ssw_debug_prune_shadow": (c_i32, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p]),
     "ssw_debug_prune_bounds": (c_i32, [c_void_p, c_void_p, c_void_p, c_f32_p, c_i32_p]),
     "ssw_debug_prune_survivors": (c_i32, [c_void_p, ctypes.c_float, c_i32, c_i32, c_i32, c_i64, c_i32_p, c_i64_p,

@@ -98,6 +98,22 @@ struct PruneState {
     }
 };
 
+// pruned batch (ssw_index_topk_batch_pruned): the per-query state, query codes and survivor lists of one chunk of up to
+// Q8_MQ_WIDTH queries; allocated by the first pruned batch
+struct PruneBatchState {
+    unsigned *mq = nullptr;        // [Q8_MQ_WIDTH][Q8_MQ_WORDS] (ssw_common.h)
+    int8_t *planes = nullptr;      // q8_mq_plane_bytes(dim)
+    int64_t *surv_rows = nullptr;  // [slots][SURV_CAP]
+    float *surv_scores = nullptr;  // [slots][SURV_CAP]
+    int slots = 0;
+    int32_t *host = nullptr;       // pinned, mapped: [seq, survivors or -1 of each slot]
+    unsigned seq = 0;
+    void release() {
+        for (void *p : {(void *)mq, (void *)planes, (void *)surv_rows, (void *)surv_scores}) (void)hipFree(p);
+        if (host) (void)hipHostFree(host);
+    }
+};
+
 // batched scan (ssw_index_scan_batch / ssw_index_topk_batch): the queries of one chunk, and the score slabs of all but
 // its last query (that one's slab is `scores`); allocated by the first batched call
 struct BatchState {
@@ -158,6 +174,7 @@ struct ssw_index {
     bool rows_escaped = false;  // the row pointer was handed out: never a shadow
     bool scores_partial = false;  // scores hold exact values for the survivors only (ensure_full_scores materialises)
     BatchState batch;
+    PruneBatchState prune_batch;
     // profiling of the scan kernel
     bool profiling = false;
     std::vector<hipEvent_t> ev;  // pairs
@@ -269,6 +286,9 @@ constexpr int64_t PRUNE_MIN_ROWS = (int64_t)1 << 22;  // above the feedback loop
 // sweep on (2^22 rows: 0.49 against 0.72 ms a call, profiles/prune_f16_sweep.txt), so the value is the f32 one.  Its
 // own constant: the two row formats are measured separately and need not stay equal.
 constexpr int64_t PRUNE_MIN_ROWS_F16 = (int64_t)1 << 22;
+// the pruned batch (ssw_index_topk_batch_pruned) against the plain batch at 16 queries: its own constant, chosen by its
+// own sweep ("Pruned batch")
+constexpr int64_t PRUNE_BATCH_MIN_ROWS = PRUNE_MIN_ROWS;
 constexpr int64_t PRUNE_RESERVE = (int64_t)4 << 30;   // free device memory the shadow must leave
 constexpr int64_t SURV_CAP = (int64_t)1 << 18;        // survivors rescored at most; more: the full scan
 static SSW_TUNABLE bool g_prune = true;               // ssw_tune_prune
@@ -285,9 +305,13 @@ static int64_t prune_min_rows(const ssw_index *idx) {
     return idx->dtype == SSW_DTYPE_F16 ? PRUNE_MIN_ROWS_F16 : PRUNE_MIN_ROWS;
 }
 
-static bool prune_eligible(const ssw_index *idx) {
-    return g_prune && !prune_forced_off() && idx->owns_X && !idx->rows_escaped && idx->n >= prune_min_rows(idx) &&
+static bool prune_eligible_from(const ssw_index *idx, int64_t min_rows) {
+    return g_prune && !prune_forced_off() && idx->owns_X && !idx->rows_escaped && idx->n >= min_rows &&
            idx->n_images > 0 && q8_dim_supported(idx->dim);
+}
+static bool prune_eligible(const ssw_index *idx) { return prune_eligible_from(idx, prune_min_rows(idx)); }
+static bool prune_batch_eligible(const ssw_index *idx) {
+    return prune_eligible_from(idx, g_prune_min_rows >= 0 ? g_prune_min_rows : PRUNE_BATCH_MIN_ROWS);
 }
 
 static ssw_status ensure_full_scores(ssw_index *idx, hipStream_t stream) {
@@ -436,6 +460,7 @@ ssw_status ssw_index_destroy(ssw_index *idx) {
     if (idx->ws_ready) select_free(idx->ws);
     idx->prune.release();
     idx->batch.release();
+    idx->prune_batch.release();
     if (idx->owns_X) (void)hipFree(idx->X);
     (void)hipFree(idx->xfer);
     (void)hipFree(idx->scores);
@@ -1183,12 +1208,9 @@ constexpr int BATCH_MAX_WIDTH = 16;
 
 static int64_t slab_stride(const ssw_index *idx) { return (idx->n + 64 + 63) & ~(int64_t)63; }  // slabs stay 256-byte aligned
 
-// the chunk width to use for nq queries: limited by the shape, by nq and by what the side buffer could be grown to
-static ssw_status batch_width(ssw_index *idx, int32_t nq, int *out_w) {
+// the chunk's buffers for a width of w: the width they could be grown to
+static ssw_status batch_buffers(ssw_index *idx, int w, int *out_w) {
     BatchState &bt = idx->batch;
-    int w = scan_batch_max_width(idx->n, idx->dim, idx->dtype);
-    if (w > BATCH_MAX_WIDTH) w = BATCH_MAX_WIDTH;
-    while (w > nq) w >>= 1;
     if (w >= 2 && !bt.qb_dev) {
         if (hipMalloc((void **)&bt.qb_dev, (size_t)BATCH_MAX_WIDTH * idx->dim * sizeof(float)) != hipSuccess) {
             (void)hipGetLastError();
@@ -1211,6 +1233,14 @@ static ssw_status batch_width(ssw_index *idx, int32_t nq, int *out_w) {
     }
     *out_w = w < 1 ? 1 : w;
     return SSW_OK;
+}
+
+// the chunk width to use for nq queries: limited by the shape, by nq and by what the side buffer could be grown to
+static ssw_status batch_width(ssw_index *idx, int32_t nq, int *out_w) {
+    int w = scan_batch_max_width(idx->n, idx->dim, idx->dtype);
+    if (w > BATCH_MAX_WIDTH) w = BATCH_MAX_WIDTH;
+    while (w > nq) w >>= 1;
+    return batch_buffers(idx, w, out_w);
 }
 
 // queries [w, dim] (host) -> one launch that fills slab[j] = scores of query j; slab[w - 1] is the handle's buffer
@@ -1316,6 +1346,177 @@ ssw_status ssw_index_topk_batch(ssw_index *idx, const float *q_host, int32_t nq,
             const size_t o = (size_t)(b + j) * k;
             SSW_TRY(topk_enqueue(idx, nullptr, slab[j], idx->stream, ex, n_ex, k));
             SSW_TRY(topk_collect(idx, slab[j], idx->stream, k, out_images ? out_images + o : nullptr,
+                                 out_scores ? out_scores + o : nullptr, out_best_rows ? out_best_rows + o : nullptr,
+                                 out_counts + b + j));
+        }
+        b += w;
+    }
+    return SSW_OK;
+}
+
+// ---- the pruned batch: ONE pass over the int8 shadow bounds a chunk of up to 16 queries (prune.hip, "Pruned batch") ----
+static_assert(BATCH_MAX_WIDTH == Q8_MQ_WIDTH, "a chunk of the pruned batch uses the batch's slabs");
+
+// the state of a chunk of w queries; the survivor lists may only be had for fewer slots: *out_w
+static ssw_status ensure_prune_batch(ssw_index *idx, int w, int *out_w) {
+    PruneBatchState &pb = idx->prune_batch;
+    if (!pb.mq) {
+        SSW_HIP_TRY(hipMalloc((void **)&pb.mq, (size_t)Q8_MQ_WIDTH * Q8_MQ_WORDS * sizeof(unsigned)));
+        SSW_HIP_TRY(hipMemsetAsync(pb.mq, 0, (size_t)Q8_MQ_WIDTH * Q8_MQ_WORDS * sizeof(unsigned), idx->stream));
+        SSW_HIP_TRY(hipMalloc((void **)&pb.planes, q8_mq_plane_bytes(idx->dim)));
+        SSW_HIP_TRY(hipHostMalloc((void **)&pb.host, (1 + Q8_MQ_WIDTH) * sizeof(int32_t),
+                                  hipHostMallocMapped | hipHostMallocCoherent));
+        memset(pb.host, 0, (1 + Q8_MQ_WIDTH) * sizeof(int32_t));
+    }
+    while (pb.slots < w) {  // grow; on failure keep halving the width
+        SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+        (void)hipFree(pb.surv_rows);
+        (void)hipFree(pb.surv_scores);
+        pb.surv_rows = nullptr;
+        pb.surv_scores = nullptr;
+        pb.slots = 0;
+        if (hipMalloc((void **)&pb.surv_rows, (size_t)w * SURV_CAP * sizeof(int64_t)) == hipSuccess &&
+            hipMalloc((void **)&pb.surv_scores, (size_t)w * SURV_CAP * sizeof(float)) == hipSuccess) {
+            pb.slots = w;
+        } else {
+            (void)hipGetLastError();
+            (void)hipFree(pb.surv_rows);
+            pb.surv_rows = nullptr;
+            pb.surv_scores = nullptr;
+            if (w == 1) {
+                set_error("topk_batch_pruned: no memory for one survivor list");
+                return SSW_ERR_NOMEM;
+            }
+            w >>= 1;
+        }
+    }
+    *out_w = w;
+    return SSW_OK;
+}
+
+// slab j of a chunk of w queries, exactly as do_scan_chunk places them
+static float *chunk_slab(ssw_index *idx, int w, int j) {
+    return j + 1 < w ? idx->batch.side + (int64_t)j * slab_stride(idx) : idx->scores;
+}
+
+// The two device steps of a chunk that the lab hook drives as well; the shadow and the chunk's buffers are ready and
+// the w queries are in batch.qb_dev.  Lower bounds of query j into slab j; the handle's buffer (the last query's slab)
+// is partial from here on and q_last is the last query.
+static ssw_status prune_bounds_mq(ssw_index *idx, int w, int32_t *dbg_hi, int32_t *dbg_lo) {
+    PruneState &p = idx->prune;
+    PruneBatchState &pb = idx->prune_batch;
+    SSW_TRY(launch_q8_query_mq(idx->batch.qb_dev, idx->dim, w, pb.mq, pb.planes, p.q_last, idx->stream));
+    SSW_TRY(launch_q8_bounds_mq(p.q8, p.q8_scale, p.q8_err, pb.planes, pb.mq, w, idx->batch.side, slab_stride(idx),
+                                idx->scores, idx->n, idx->dim, dbg_hi, dbg_lo, idx->device, idx->stream));
+    idx->scores_partial = true;
+    return SSW_OK;
+}
+
+// the survivors of slot j against the keys the last selection left, into the slot's list (no publish)
+static ssw_status prune_survivors_slot(ssw_index *idx, int w, int j, int32_t k, int64_t cap) {
+    PruneState &p = idx->prune;
+    PruneBatchState &pb = idx->prune_batch;
+    return launch_survivors_mq(chunk_slab(idx, w, j), p.q8_err, p.q8_scale, idx->n, idx->dim, idx->ws.out_keys,
+                               idx->ws.out_count, k, pb.mq + j * Q8_MQ_WORDS, pb.surv_rows + (int64_t)j * SURV_CAP, cap,
+                               idx->device, idx->stream);
+}
+
+// every slot's count (or -1) of the chunk -> out_m[w]; ONE host wait: a sleep on sleep_ev_or_null first, then a spin
+static ssw_status prune_publish_mq(ssw_index *idx, int w, int64_t cap, hipEvent_t sleep_ev_or_null, int32_t *out_m) {
+    PruneBatchState &pb = idx->prune_batch;
+    const unsigned seq = next_seq(pb.seq);
+    int32_t *host_dev = nullptr;
+    SSW_HIP_TRY(hipHostGetDevicePointer((void **)&host_dev, pb.host, 0));
+    SSW_TRY(launch_prune_publish_mq(pb.mq, w, cap, host_dev, seq, idx->stream));
+    if (sleep_ev_or_null) SSW_HIP_TRY(hipEventSynchronize(sleep_ev_or_null));
+    SSW_TRY(wait_host_seq(idx->stream, reinterpret_cast<const unsigned *>(pb.host), seq));
+    for (int j = 0; j < w; ++j) out_m[j] = __atomic_load_n(pb.host + 1 + j, __ATOMIC_ACQUIRE);
+    return SSW_OK;
+}
+
+ssw_status ssw_index_topk_batch_pruned(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
+                                       const int64_t *excluded_offsets, int32_t k, int64_t *out_images,
+                                       float *out_scores, int64_t *out_best_rows, int32_t *out_counts) {
+    SSW_REQUIRE(nq >= 1, "nq=%d < 1", nq);
+    SSW_REQUIRE(idx != nullptr && q_host != nullptr && out_counts != nullptr, "NULL argument");
+    SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
+    bool ready = false;
+    int W = 1;
+    {
+        DeviceGuard guard(idx->device);
+        if (prune_batch_eligible(idx) && idx->ws.xchg.msg_out == nullptr) SSW_TRY(ensure_shadow(idx, &ready));
+        if (ready && !idx->batch.qb_dev &&
+            hipMalloc((void **)&idx->batch.qb_dev, (size_t)BATCH_MAX_WIDTH * idx->dim * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            idx->batch.qb_dev = nullptr;
+            ready = false;
+        }
+    }
+    if (!ready)  // not eligible, or the shadow is refused: the plain batch, which leaves the counters alone
+        return ssw_index_topk_batch(idx, q_host, nq, excluded_images, excluded_offsets, k, out_images, out_scores,
+                                    out_best_rows, out_counts);
+    if (excluded_offsets) {
+        SSW_REQUIRE(excluded_offsets[0] >= 0, "excluded_offsets[0]=%lld < 0", (long long)excluded_offsets[0]);
+        for (int32_t b = 0; b < nq; ++b)
+            SSW_REQUIRE(excluded_offsets[b] <= excluded_offsets[b + 1], "excluded_offsets decrease at query %d", b);
+        SSW_REQUIRE(excluded_offsets[nq] == excluded_offsets[0] || excluded_images != nullptr, "excluded_images is NULL");
+        SSW_TRY(check_excluded(idx, excluded_images, excluded_offsets[0], excluded_offsets[nq]));
+    }
+    SSW_TRY(check_query_batch(idx, q_host, nq));
+    for (int32_t b = 0; b < nq; ++b) out_counts[b] = 0;
+    auto excl = [&](int32_t b, int64_t *n_ex) -> const int64_t * {
+        *n_ex = excluded_offsets ? excluded_offsets[b + 1] - excluded_offsets[b] : 0;
+        return *n_ex > 0 ? excluded_images + excluded_offsets[b] : nullptr;
+    };
+    DeviceGuard guard(idx->device);
+    // (a partial buffer is not completed first: every chunk overwrites it and the kept query together)
+    SSW_TRY(ensure_ws(idx));
+    SSW_TRY(batch_buffers(idx, std::min<int32_t>(nq, Q8_MQ_WIDTH), &W));
+    SSW_TRY(ensure_prune_batch(idx, W, &W));
+    PruneState &p = idx->prune;
+    PruneBatchState &pb = idx->prune_batch;
+    BatchState &bt = idx->batch;
+    const size_t dim = (size_t)idx->dim;
+    for (int32_t b = 0; b < nq;) {
+        const int w = std::min<int32_t>(W, nq - b);
+        int32_t m[Q8_MQ_WIDTH];
+        SSW_TRY(bt.qb_stage.push(bt.qb_dev, q_host + b * dim, (size_t)w * dim * sizeof(float), idx->stream));
+        SSW_TRY(profiled(idx, [&]() -> ssw_status {
+            SSW_TRY(prune_bounds_mq(idx, w, nullptr, nullptr));
+            SSW_HIP_TRY(hipEventRecord(p.ev, idx->stream));
+            for (int j = 0; j < w; ++j) {  // threshold and survivors of each query, in stream order
+                int64_t n_ex = 0;
+                const int64_t *ex = excl(b + j, &n_ex);
+                SSW_TRY(install_excluded(idx, ex, n_ex, idx->stream));
+                SSW_TRY(do_select(idx, chunk_slab(idx, w, j), k, SelectDest{nullptr, 0u, false}, idx->stream));
+                SSW_TRY(prune_survivors_slot(idx, w, j, k, SURV_CAP));
+            }
+            SSW_TRY(prune_publish_mq(idx, w, SURV_CAP, p.ev, m));  // sleep through the shadow scan, spin on the rest
+            for (int j = 0; j < w; ++j) {
+                const float *qj = bt.qb_dev + (size_t)j * dim;
+                float *slab = chunk_slab(idx, w, j);
+                ++p.queries;
+                if (m[j] < 0) {
+                    ++p.fallbacks;
+                    SSW_TRY(launch_scan(idx->X, idx->dtype, qj, slab, idx->n, idx->dim, idx->device, idx->stream));
+                } else {
+                    const int64_t *rows = pb.surv_rows + (int64_t)j * SURV_CAP;
+                    float *vals = pb.surv_scores + (int64_t)j * SURV_CAP;
+                    SSW_TRY(launch_score_rows(idx->X, idx->dtype, qj, rows, m[j], idx->dim, vals, idx->stream));
+                    SSW_TRY(launch_scatter_scores(rows, vals, m[j], slab, idx->stream));
+                }
+            }
+            p.last = m[w - 1];
+            idx->scores_partial = m[w - 1] >= 0;  // the handle's buffer is the last query's slab
+            return SSW_OK;
+        }));
+        for (int j = 0; j < w; ++j) {
+            int64_t n_ex = 0;
+            const int64_t *ex = excl(b + j, &n_ex);
+            const size_t o = (size_t)(b + j) * k;
+            float *slab = chunk_slab(idx, w, j);
+            SSW_TRY(topk_enqueue(idx, nullptr, slab, idx->stream, ex, n_ex, k));
+            SSW_TRY(topk_collect(idx, slab, idx->stream, k, out_images ? out_images + o : nullptr,
                                  out_scores ? out_scores + o : nullptr, out_best_rows ? out_best_rows + o : nullptr,
                                  out_counts + b + j));
         }
@@ -1554,6 +1755,126 @@ ssw_status ssw_debug_prune_survivors(ssw_index *idx, float threshold, int32_t k,
                                    idx->stream));
     SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
     *out_published = m;
+    *out_collected = (int64_t)collected;
+    return SSW_OK;
+}
+ssw_status ssw_tune_prune_scan_mq(int32_t blocks_per_cu, int32_t tiles) {
+    tune_q8_bounds_mq(blocks_per_cu, tiles);
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_prune_scan_mq_shape(ssw_index *idx, int32_t *out_blocks, int32_t *out_tiles) {
+    SSW_REQUIRE(idx != nullptr && out_blocks != nullptr && out_tiles != nullptr, "NULL argument");
+    SSW_REQUIRE(q8_dim_supported(idx->dim), "dim=%d has no shadow scan", idx->dim);
+    int blocks = 0, tiles = 0;
+    q8_bounds_mq_shape(idx->dim, idx->device, idx->n, &blocks, &tiles);
+    *out_blocks = blocks;
+    *out_tiles = tiles;
+    return SSW_OK;
+}
+
+// the chunk's buffers for nq queries staged from the host, for the two hooks below
+static ssw_status debug_chunk_ready(ssw_index *idx, int32_t nq) {
+    SSW_REQUIRE(prune_batch_eligible(idx), "the index is not pruned (ssw_tune_prune, dim, borrowed or escaped rows)");
+    bool ready = false;
+    SSW_TRY(ensure_shadow(idx, &ready));
+    if (!ready) {
+        set_error("prune_bounds_mq: the shadow was refused for memory");
+        return SSW_ERR_NOMEM;
+    }
+    SSW_TRY(ensure_ws(idx));
+    if (!idx->batch.qb_dev)
+        SSW_HIP_TRY(hipMalloc((void **)&idx->batch.qb_dev, (size_t)BATCH_MAX_WIDTH * idx->dim * sizeof(float)));
+    int w = 0;
+    SSW_TRY(batch_buffers(idx, nq, &w));
+    if (w == nq) SSW_TRY(ensure_prune_batch(idx, nq, &w));
+    if (w != nq) {
+        set_error("prune_bounds_mq: no memory for a chunk of %d queries", nq);
+        return SSW_ERR_NOMEM;
+    }
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_prune_bounds_mq(ssw_index *idx, const float *q_host, int32_t nq, int32_t *out_I_hi, int32_t *out_I_lo,
+                                     float *out_lb, float *out_Qe, int8_t *out_codes) {
+    SSW_REQUIRE(idx != nullptr && q_host != nullptr, "NULL argument");
+    SSW_REQUIRE(nq >= 1 && nq <= Q8_MQ_WIDTH, "nq=%d outside [1, %d]", nq, Q8_MQ_WIDTH);
+    DeviceGuard guard(idx->device);
+    SSW_TRY(debug_chunk_ready(idx, nq));
+    PruneBatchState &pb = idx->prune_batch;
+    const size_t dim = (size_t)idx->dim, cells = (size_t)nq * idx->n;
+    int32_t *dbg = nullptr;
+    if (out_I_hi || out_I_lo) SSW_HIP_TRY(hipMalloc((void **)&dbg, 2 * cells * sizeof(int32_t)));
+    std::vector<unsigned> mq((size_t)Q8_MQ_WIDTH * Q8_MQ_WORDS);
+    std::vector<int8_t> planes(q8_mq_plane_bytes(idx->dim));
+    auto run = [&]() -> ssw_status {
+        SSW_TRY(idx->batch.qb_stage.push(idx->batch.qb_dev, q_host, (size_t)nq * dim * sizeof(float), idx->stream));
+        SSW_TRY(prune_bounds_mq(idx, nq, dbg, dbg ? dbg + cells : nullptr));
+        if (out_I_hi) SSW_HIP_TRY(hipMemcpyAsync(out_I_hi, dbg, cells * sizeof(int32_t), hipMemcpyDeviceToHost, idx->stream));
+        if (out_I_lo)
+            SSW_HIP_TRY(hipMemcpyAsync(out_I_lo, dbg + cells, cells * sizeof(int32_t), hipMemcpyDeviceToHost, idx->stream));
+        if (out_lb)
+            for (int j = 0; j < nq; ++j)
+                SSW_HIP_TRY(hipMemcpyAsync(out_lb + (size_t)j * idx->n, chunk_slab(idx, nq, j), (size_t)idx->n * sizeof(float),
+                                           hipMemcpyDeviceToHost, idx->stream));
+        SSW_HIP_TRY(hipMemcpyAsync(mq.data(), pb.mq, mq.size() * sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
+        SSW_HIP_TRY(hipMemcpyAsync(planes.data(), pb.planes, planes.size(), hipMemcpyDeviceToHost, idx->stream));
+        SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+        return SSW_OK;
+    };
+    const ssw_status st = run();
+    if (st != SSW_OK) (void)hipStreamSynchronize(idx->stream);
+    (void)hipFree(dbg);
+    SSW_TRY(st);
+    for (int j = 0; j < nq; ++j) {
+        const unsigned *w = mq.data() + (size_t)j * Q8_MQ_WORDS;
+        if (out_Qe) {
+            memcpy(out_Qe + 4 * j, &w[1], 4);      // Q
+            memcpy(out_Qe + 4 * j + 1, &w[3], 4);  // e
+            memcpy(out_Qe + 4 * j + 2, &w[4], 4);  // t2
+            out_Qe[4 * j + 3] = (float)w[2];       // 1 = the query cannot be bounded
+        }
+        if (out_codes)  // the planes' fragment order (prune.hip) back to natural element order
+            for (int pl = 0; pl < 2; ++pl)
+                for (size_t i = 0; i < dim; ++i)
+                    out_codes[((size_t)j * 2 + pl) * dim + i] =
+                        planes[(((i >> 6) * 2 + pl) * 64 + ((i & 63) >> 4) * 16 + j) * 16 + (i & 15)];
+    }
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_prune_survivors_mq(ssw_index *idx, int32_t nq, int32_t slot, float threshold, int32_t k,
+                                        int32_t sel_count, int32_t sel_overflow, int64_t cap, int32_t *out_published,
+                                        int64_t *out_collected, int64_t *out_rows) {
+    SSW_REQUIRE(idx != nullptr && out_published != nullptr && out_collected != nullptr, "NULL argument");
+    SSW_REQUIRE(nq >= 1 && nq <= Q8_MQ_WIDTH && slot >= 0 && slot < nq, "slot=%d outside the chunk of %d", slot, nq);
+    SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
+    SSW_REQUIRE(cap >= 0 && cap <= SURV_CAP, "cap=%lld outside [0, %lld]", (long long)cap, (long long)SURV_CAP);
+    SSW_REQUIRE(cap == 0 || out_rows != nullptr, "out_rows is NULL");
+    PruneBatchState &pb = idx->prune_batch;
+    SSW_REQUIRE(idx->scores_partial && idx->prune.q8 && !idx->prune.stale && pb.slots >= nq && idx->batch.side_slabs >= nq - 1,
+                "no bounds of such a chunk in the buffers: ssw_debug_prune_bounds_mq first");
+    DeviceGuard guard(idx->device);
+    SSW_TRY(ensure_ws(idx));
+    std::vector<uint64_t> keys((size_t)k, (uint64_t)f32_to_ord(threshold) << 32);
+    const int32_t count[2] = {sel_count, sel_overflow};
+    unsigned *st = pb.mq + slot * Q8_MQ_WORDS;
+    SSW_HIP_TRY(hipMemcpyAsync(idx->ws.out_keys, keys.data(), keys.size() * sizeof(uint64_t), hipMemcpyHostToDevice,
+                               idx->stream));
+    SSW_HIP_TRY(hipMemcpyAsync(idx->ws.out_count, count, sizeof(count), hipMemcpyHostToDevice, idx->stream));
+    SSW_HIP_TRY(hipMemsetAsync(st, 0, sizeof(unsigned), idx->stream));      // the counter and the "selection failed"
+    SSW_HIP_TRY(hipMemsetAsync(st + 5, 0, sizeof(unsigned), idx->stream));  // word k_q8_query_mq resets
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));  // keys and count are pageable host memory
+    SSW_TRY(prune_survivors_slot(idx, nq, slot, k, cap));
+    int32_t m[Q8_MQ_WIDTH];
+    SSW_TRY(prune_publish_mq(idx, nq, cap, nullptr, m));
+    unsigned collected = 0u;
+    SSW_HIP_TRY(hipMemcpyAsync(&collected, st, sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
+    if (m[slot] > 0)
+        SSW_HIP_TRY(hipMemcpyAsync(out_rows, pb.surv_rows + (int64_t)slot * SURV_CAP, (size_t)m[slot] * sizeof(int64_t),
+                                   hipMemcpyDeviceToHost, idx->stream));
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+    *out_published = m[slot];
     *out_collected = (int64_t)collected;
     return SSW_OK;
 }

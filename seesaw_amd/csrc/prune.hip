@@ -413,6 +413,298 @@ __global__ void k_prune_publish(const int32_t *__restrict__ sel_count, int32_t k
     __hip_atomic_store(reinterpret_cast<unsigned *>(host_block), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// ---- the pre-scan of a chunk of up to 16 queries on the int8 matrix core ("Pruned batch") -----
+// The queries are quantised to two int8 planes, q ~ t2 (256 d_hi + d_lo) with t2 = max|q| / 127 / 256, and one
+// v_mfma_i32_16x16x64_i8 forms 16 rows x 16 queries x 64 elements of sum_i c_i d_i, exactly.  With e >= ||q - t2 (256
+// d_hi + d_lo)|| and ||c|| <= 127 sqrt(dim)
+//
+//     | S_r - s_r t2 (256 I_hi + I_lo) | <= a_r Q + s_r 127 sqrt(dim) e =: w                                  (**)
+//
+// Per-query state, MQ_WORDS words a slot: [0] survivors, [1] Q, [2] 1 = the query cannot be bounded, [3] e, [4] t2,
+// [5] 1 = the slot's threshold selection failed (k_survivors_mq).
+// Query planes: the fragment of k-step ks (64 elements), plane p (0 hi, 1 lo) and lane l is the u32x4 at
+// (ks * 2 + p) * 64 + l: bytes j = 0 .. 15 are the codes of query l & 15 at elements 64 ks + 16 (l >> 4) + j.  The
+// rows' fragments take the same elements: lane l loads the 16 bytes at 64 ks + 16 (l >> 4) of row l & 15 of its tile,
+// so the four lanes of a row read 64 contiguous bytes per load instruction and two adjacent k-steps a whole line.
+// Whatever element of K the matrix core pairs byte j of lane group l >> 4 with, it pairs the same one of A and B:
+// the sum over all of them does not depend on it.
+constexpr int MQ_WIDTH = 16, MQ_WORDS = 8;
+constexpr double MQ_INFLATE = 1.0 + 0x1p-40;  // on w: the double roundings of w and of s t2 I (a few 2^-53 (|lb| + w))
+constexpr int MQ_BLOCKS_PER_CU = 1;
+SSW_TUNABLE int g_mq_blocks_per_cu = MQ_BLOCKS_PER_CU;
+SSW_TUNABLE int g_mq_tiles = 0;  // 0: mq_default_tiles(C)
+constexpr int mq_default_tiles(int C) { return C == 4 ? 1 : 2; }  // 16-row tiles of one request: 8 / 16 / 16 KiB a wave
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+// 127 sqrt(dim), rounded up
+__host__ __device__ constexpr double mq_code_norm(int dim) { return dim == 256 ? 2032.0 : dim == 512 ? 2873.6819588 : 4064.0; }
+
+// One block a slot.  Slots >= w get zero codes and nothing else.
+__global__ __launch_bounds__(256) void k_q8_query_mq(const float *__restrict__ qb, int dim, int w, unsigned *__restrict__ mq,
+                                                     int8_t *__restrict__ planes, float *__restrict__ q_last) {
+    __shared__ double part[4], part_e[4];
+    __shared__ float part_m[4];
+    const int b = blockIdx.x;
+    auto code_at = [&](int i, int p) -> int8_t * {
+        const int ks = i >> 6, g = (i & 63) >> 4, j = i & 15;
+        return planes + ((size_t)((ks * 2 + p) * 64 + g * 16 + b) * 16 + j);
+    };
+    if (b >= w) {
+        for (int i = threadIdx.x; i < dim; i += 256) *code_at(i, 0) = 0, *code_at(i, 1) = 0;
+        return;
+    }
+    const float *q = qb + (size_t)b * dim;
+    double s = 0.0;
+    float m = 0.0f;
+    bool finite = true;
+    for (int i = threadIdx.x; i < dim; i += 256) {
+        const float v = q[i];
+        if (b == w - 1) q_last[i] = v;
+        finite = finite && isfinite(v);
+        m = fmaxf(m, fabsf(v));
+        s += (double)v * (double)v;
+    }
+    s = wave_sum_d(s);
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+    const bool all_finite = __syncthreads_and(finite);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s, part_m[threadIdx.x >> 6] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(part_m[0], part_m[1]), fmaxf(part_m[2], part_m[3]));
+    const double tot = part[0] + part[1] + part[2] + part[3];
+    const float Q = __double2float_ru(sqrt(tot) * (1.0 + 0x1p-40));  // k_q8_query's Q
+    const bool bad = !all_finite || !(Q <= MAX_QNORM) || Q == 0.0f || !(m >= MIN_ABS && m <= MAX_ABS);
+    const float t = m / 127.0f, t2 = t * 0x1p-8f;
+    double e2 = 0.0;
+    for (int i = threadIdx.x; i < dim; i += 256) {
+        int hi = 0, lo = 0;
+        if (!bad) {
+            const double v = (double)q[i];
+            const double dh = rint(v / (double)t);
+            const double r1 = v - (double)t * dh;  // exact
+            const double dl = fmin(fmax(rint(r1 / (double)t2), -127.0), 127.0);
+            const double r2 = r1 - (double)t2 * dl;
+            e2 = __dadd_rn(e2, __dmul_rn(r2, r2));  // not contracted: the numpy twin adds the rounded square
+            hi = (int)dh, lo = (int)dl;
+        }
+        *code_at(i, 0) = (int8_t)hi;
+        *code_at(i, 1) = (int8_t)lo;
+    }
+    e2 = wave_sum_d(e2);
+    if ((threadIdx.x & 63) == 0) part_e[threadIdx.x >> 6] = e2;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double te = part_e[0] + part_e[1] + part_e[2] + part_e[3];
+        unsigned *st = mq + b * MQ_WORDS;
+        st[0] = 0u;
+        st[1] = __float_as_uint(Q);
+        st[2] = bad ? 1u : 0u;
+        st[3] = __float_as_uint(__double2float_ru(sqrt(te) * SAFETY));
+        st[4] = __float_as_uint(t2);
+        st[5] = 0u;
+    }
+}
+
+// lb of every row for every query of the chunk: query j's into slab j (j + 1 < w: side + j * stride, the last: own).
+// C = dim / 256; a wave takes groups of T tiles of 16 consecutive rows, grid-strided, and keeps two register sets in
+// turn as k_q8_bounds does: the next group's codes and constants are requested before the current group's MFMAs, the
+// waits inside the loop are counted ones, the loop has one exit, and the last n % (16 T) rows are one clamped group
+// for one wave after it.  Result map of the 16x16 product: lane l holds query l & 15 and rows 4 (l >> 4) .. + 3 of the
+// tile, so it loads those rows' s and a with one 16-byte load each and writes its four bounds with one 16-byte store.
+// DEBUG (lab hook only): the integer sums go to dbg_hi / dbg_lo [query][n] as well.
+template <int C, int T, bool DEBUG>
+__global__ __launch_bounds__(256) void k_q8_bounds_mq(const int8_t *__restrict__ codes, const float *__restrict__ scale,
+                                                      const float *__restrict__ err, const u32x4 *__restrict__ planes,
+                                                      const unsigned *__restrict__ mq, int w, float *__restrict__ side,
+                                                      int64_t stride, float *__restrict__ own, int64_t n,
+                                                      int32_t *__restrict__ dbg_hi, int32_t *__restrict__ dbg_lo) {
+    constexpr int dim = 256 * C, KS = dim / 64, G = 16 * T;
+    const int lane = threadIdx.x & 63;
+    const int col = lane & 15, quad = lane >> 4;
+    const int64_t gwave = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t nwaves = (int64_t)gridDim.x * 4;
+    const int64_t nfull = n / G;
+    const int ragged = (int)(n % G);
+    i32x4 qh[KS], ql[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        qh[ks] = __builtin_bit_cast(i32x4, planes[(ks * 2) * 64 + lane]);
+        ql[ks] = __builtin_bit_cast(i32x4, planes[(ks * 2 + 1) * 64 + lane]);
+    }
+    const bool live = col < w;
+    float *__restrict__ slab = col + 1 < w ? side + (int64_t)col * stride : own;
+    const unsigned *st = mq + (live ? col : 0) * MQ_WORDS;
+    const double t2d = (double)__uint_as_float(st[4]);
+    const double wQ = (double)__uint_as_float(st[1]) * MQ_INFLATE;
+    const double wE = (double)__uint_as_float(st[3]) * mq_code_norm(dim) * MQ_INFLATE;
+    const unsigned lane_byte = (unsigned)(col * dim + 16 * quad);  // of the lane's 16 codes of k-step 0 in a tile
+    struct Set {
+        u32x4 c[T][KS];
+        float s[T][4], a[T][4];
+    };
+    auto load = [&](Set &d, int64_t g) {
+        const int8_t *base = codes + g * (int64_t)(G * dim);  // wave-uniform
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks)
+                d.c[t][ks] = __builtin_nontemporal_load(
+                    reinterpret_cast<const u32x4 *>(base + (lane_byte + (unsigned)(t * 16 * dim + ks * 64))));
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const float4 sv = *reinterpret_cast<const float4 *>(scale + g * G + t * 16 + 4 * quad);
+            const float4 av = *reinterpret_cast<const float4 *>(err + g * G + t * 16 + 4 * quad);
+            d.s[t][0] = sv.x, d.s[t][1] = sv.y, d.s[t][2] = sv.z, d.s[t][3] = sv.w;
+            d.a[t][0] = av.x, d.a[t][1] = av.y, d.a[t][2] = av.z, d.a[t][3] = av.w;
+        }
+        __builtin_amdgcn_sched_barrier(0);  // as in k_q8_bounds: the requests stay ahead of the products
+    };
+    // the bounds of the first `rows` rows of group g from a set that has arrived (rows == G: whole stores)
+    auto bounds = [&](const Set &d, int64_t g, int rows) {
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            i32x4 hi = {0, 0, 0, 0}, lo = {0, 0, 0, 0};
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const i32x4 a = __builtin_bit_cast(i32x4, d.c[t][ks]);
+                hi = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, qh[ks], hi, 0, 0, 0);
+                lo = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, ql[ks], lo, 0, 0, 0);
+            }
+            float out[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const double I = (double)hi[i] * 256.0 + (double)lo[i];  // exact
+                const double sd = (double)d.s[t][i];
+                const double wv = (double)d.a[t][i] * wQ + sd * wE;
+                double lb = sd * t2d * I - wv;
+                lb -= fabs(lb) * 0x1p-50 + PAD_ABS;
+                out[i] = __double2float_rd(lb);
+            }
+            const int r0 = t * 16 + 4 * quad;  // of the lane's four rows in the group
+            if (rows == G) {
+                if (live) *reinterpret_cast<float4 *>(slab + g * G + r0) = make_float4(out[0], out[1], out[2], out[3]);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (live && r0 + i < rows) (slab + g * G)[r0 + i] = out[i];
+            }
+            if constexpr (DEBUG) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (live && r0 + i < rows) {
+                        (dbg_hi + (int64_t)col * n + g * G)[r0 + i] = hi[i];
+                        (dbg_lo + (int64_t)col * n + g * G)[r0 + i] = lo[i];
+                    }
+            }
+        }
+    };
+    if (gwave < nfull) {
+        Set a, b;
+        int64_t g = gwave;
+        load(a, g);
+        for (;;) {
+            // a wave without a next group requests its last one once more (cache hits) and writes nothing for it
+            const int64_t g1 = g + nwaves < nfull ? g + nwaves : g;
+            load(b, g1);
+            bounds(a, g, G);
+            const int64_t g2 = g1 + nwaves < nfull ? g1 + nwaves : g1;
+            load(a, g2);
+            bounds(b, g1, g1 != g ? G : 0);
+            if (g2 == g1) break;
+            g = g2;
+        }
+    }
+    if (ragged != 0 && gwave == nfull % nwaves) {
+        Set t;
+        const int8_t *base = codes + nfull * (int64_t)(G * dim);
+#pragma unroll
+        for (int tt = 0; tt < T; ++tt) {
+            const unsigned row = (unsigned)min(tt * 16 + col, ragged - 1);  // nothing beyond row n - 1
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks)
+                t.c[tt][ks] = *reinterpret_cast<const u32x4 *>(base + (row * (unsigned)dim + (unsigned)(ks * 64 + 16 * quad)));
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int r = min(tt * 16 + 4 * quad + i, ragged - 1);
+                t.s[tt][i] = (scale + nfull * G)[r];
+                t.a[tt][i] = (err + nfull * G)[r];
+            }
+        }
+        bounds(t, nfull, ragged);
+    }
+}
+
+// k_survivors for one slot of a chunk: the width is w of (**), from the slot's state and the row's scale beside its
+// err; the list and the counter are the slot's.  A failed selection or a flagged query collects nothing and leaves
+// word [5] / [2] for k_prune_publish_mq.
+__global__ __launch_bounds__(256) void k_survivors_mq(const float *__restrict__ lb, const float *__restrict__ err,
+                                                      const float *__restrict__ scale, int64_t n, double code_norm,
+                                                      const uint64_t *__restrict__ keys,
+                                                      const int32_t *__restrict__ sel_count, int32_t k,
+                                                      unsigned *__restrict__ st, int64_t *__restrict__ rows,
+                                                      int64_t cap) {
+    if (sel_count[0] < k || sel_count[1] != 0) {
+        if (threadIdx.x == 0) st[5] = 1u;  // every block writes the same word
+        return;
+    }
+    if (st[2] != 0u) return;
+    const float T = ord_to_f32((uint32_t)(keys[k - 1] >> 32));
+    const double wQ = (double)__uint_as_float(st[1]) * MQ_INFLATE;
+    const double wE = (double)__uint_as_float(st[3]) * code_norm * MQ_INFLATE;
+    const int lane = threadIdx.x & 63;
+    const uint64_t below = (1ull << lane) - 1ull;
+    const int64_t stride = (int64_t)gridDim.x * 1024;
+    for (int64_t base = (int64_t)blockIdx.x * 1024 + (threadIdx.x & ~63u) * 4; base < n; base += stride) {
+        const int64_t r0 = base + 4 * lane;
+        float l4[4] = {0.0f, 0.0f, 0.0f, 0.0f}, e4[4] = {0.0f, 0.0f, 0.0f, 0.0f}, s4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (r0 + 3 < n) {
+            const float4 lv = *reinterpret_cast<const float4 *>(lb + r0), ev = *reinterpret_cast<const float4 *>(err + r0),
+                         sv = *reinterpret_cast<const float4 *>(scale + r0);
+            l4[0] = lv.x, l4[1] = lv.y, l4[2] = lv.z, l4[3] = lv.w;
+            e4[0] = ev.x, e4[1] = ev.y, e4[2] = ev.z, e4[3] = ev.w;
+            s4[0] = sv.x, s4[1] = sv.y, s4[2] = sv.z, s4[3] = sv.w;
+        } else {
+            for (int t = 0; t < 4; ++t)
+                if (r0 + t < n) l4[t] = lb[r0 + t], e4[t] = err[r0 + t], s4[t] = scale[r0 + t];
+        }
+        bool keep[4];
+        uint64_t ballot[4];
+        unsigned total = 0u;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const double l = (double)l4[t], w = (double)e4[t] * wQ + (double)s4[t] * wE;
+            const double ub = l + 2.0 * w + (fabs(l) + w) * 0x1p-20 + 2.0 * PAD_ABS;
+            keep[t] = r0 + t < n && !(ub < (double)T);  // NaN survives
+            ballot[t] = __ballot(keep[t]);
+            total += (unsigned)__popcll(ballot[t]);
+        }
+        if (total == 0u) continue;
+        unsigned slot = 0u;
+        if (lane == 0) slot = atomicAdd(&st[0], total);
+        slot = __shfl(slot, 0, 64);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int64_t at = (int64_t)slot + __popcll(ballot[t] & below);
+            if (keep[t] && at < cap) rows[at] = r0 + t;
+            slot += (unsigned)__popcll(ballot[t]);
+        }
+    }
+}
+
+// every slot's answer in one launch: host_block[1 + j] = survivors or -1, j < w, released under host_block[0] = seq
+__global__ void k_prune_publish_mq(const unsigned *__restrict__ mq, int w, int64_t cap, int32_t *__restrict__ host_block,
+                                   unsigned seq) {
+    if (threadIdx.x != 0) return;
+    for (int j = 0; j < w; ++j) {
+        const unsigned *st = mq + j * MQ_WORDS;
+        const bool fall = st[5] != 0u || st[2] != 0u || (int64_t)st[0] > cap;
+        host_block[1 + j] = fall ? -1 : (int32_t)st[0];
+    }
+    __threadfence_system();
+    __hip_atomic_store(reinterpret_cast<unsigned *>(host_block), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 __global__ __launch_bounds__(256) void k_scatter_scores(const int64_t *__restrict__ rows, const float *__restrict__ v,
                                                         int64_t m, float *__restrict__ scores) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -512,6 +804,98 @@ ssw_status launch_survivors(const float *lb, const float *err, int64_t n, const 
     hipLaunchKernelGGL(k_survivors, dim3((unsigned)grid), dim3(256), 0, stream, lb, err, n, keys, sel_count, k, state,
                        rows, cap);
     hipLaunchKernelGGL(k_prune_publish, dim3(1), dim3(64), 0, stream, sel_count, k, state, cap, host_block, seq);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+size_t q8_mq_plane_bytes(int32_t dim) { return (size_t)(dim / 64) * 2 * 64 * 16; }
+
+ssw_status launch_q8_query_mq(const float *qb_dev, int32_t dim, int32_t w, unsigned *mq, int8_t *planes, float *q_last,
+                              hipStream_t stream) {
+    hipLaunchKernelGGL(k_q8_query_mq, dim3(MQ_WIDTH), dim3(256), 0, stream, qb_dev, (int)dim, (int)w, mq, planes, q_last);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+static int mq_tiles(int C) {
+    int t = g_mq_tiles > 0 ? g_mq_tiles : mq_default_tiles(C);
+    while (t * C > 4) t >>= 1;  // two register sets of more than 16 KiB a wave do not fit beside the query planes
+    return t;
+}
+
+void q8_bounds_mq_shape(int32_t dim, int device, int64_t n, int *out_blocks, int *out_tiles) {
+    const int T = mq_tiles(dim / 256);
+    const int64_t need = ((n + 16 * T - 1) / (16 * T) + 3) / 4;
+    int64_t grid = (int64_t)num_cus(device) * g_mq_blocks_per_cu;
+    if (grid > need) grid = need;
+    if (grid < 1) grid = 1;
+    *out_blocks = (int)grid;
+    *out_tiles = T;
+}
+
+ssw_status launch_q8_bounds_mq(const int8_t *codes, const float *scale, const float *err, const int8_t *planes,
+                               const unsigned *mq, int32_t w, float *side, int64_t stride, float *own, int64_t n,
+                               int32_t dim, int32_t *dbg_hi, int32_t *dbg_lo, int device, hipStream_t stream) {
+    if (n <= 0) return SSW_OK;
+    if (!q8_dim_supported(dim) || w < 1 || w > MQ_WIDTH) {
+        set_error("q8_bounds_mq: dim=%d, w=%d unsupported", dim, w);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    const int C = dim / 256;
+    int grid = 1, T = 1;
+    q8_bounds_mq_shape(dim, device, n, &grid, &T);
+    const u32x4 *pl = reinterpret_cast<const u32x4 *>(planes);
+#define SSW_MQ(C_, T_, D_)                                                                                              \
+    hipLaunchKernelGGL((k_q8_bounds_mq<C_, T_, D_>), dim3((unsigned)grid), dim3(256), 0, stream, codes, scale, err, pl, \
+                       mq, (int)w, side, stride, own, n, dbg_hi, dbg_lo)
+#ifdef SSW_DEBUG_HOOKS
+#define SSW_MQ_T(C_, T_)          \
+    if (dbg_hi) SSW_MQ(C_, T_, true); \
+    else SSW_MQ(C_, T_, false)
+    if (C == 1) {
+        if (T == 1) { SSW_MQ_T(1, 1); } else if (T == 4) { SSW_MQ_T(1, 4); } else { SSW_MQ_T(1, 2); }
+    } else if (C == 2) {
+        if (T == 1) { SSW_MQ_T(2, 1); } else { SSW_MQ_T(2, 2); }
+    } else {
+        SSW_MQ_T(4, 1);
+    }
+#undef SSW_MQ_T
+#else
+    (void)T;
+    switch (C) {
+        case 1: SSW_MQ(1, mq_default_tiles(1), false); break;
+        case 2: SSW_MQ(2, mq_default_tiles(2), false); break;
+        default: SSW_MQ(4, mq_default_tiles(4), false); break;
+    }
+#endif
+#undef SSW_MQ
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+#ifdef SSW_DEBUG_HOOKS
+void tune_q8_bounds_mq(int blocks_per_cu, int tiles) {
+    g_mq_blocks_per_cu = blocks_per_cu >= 1 && blocks_per_cu <= 8 ? blocks_per_cu : MQ_BLOCKS_PER_CU;
+    g_mq_tiles = tiles == 1 || tiles == 2 || tiles == 4 ? tiles : 0;
+}
+#endif
+
+ssw_status launch_survivors_mq(const float *lb, const float *err, const float *scale, int64_t n, int32_t dim,
+                               const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *slot_state,
+                               int64_t *rows, int64_t cap, int device, hipStream_t stream) {
+    int64_t grid = (int64_t)num_cus(device) * 4;
+    const int64_t need = (n + 1023) / 1024;  // four rows a lane
+    if (grid > need) grid = need;
+    if (grid < 1) grid = 1;
+    hipLaunchKernelGGL(k_survivors_mq, dim3((unsigned)grid), dim3(256), 0, stream, lb, err, scale, n, mq_code_norm(dim),
+                       keys, sel_count, k, slot_state, rows, cap);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+ssw_status launch_prune_publish_mq(const unsigned *mq, int32_t w, int64_t cap, int32_t *host_block, unsigned seq,
+                                   hipStream_t stream) {
+    hipLaunchKernelGGL(k_prune_publish_mq, dim3(1), dim3(64), 0, stream, mq, (int)w, cap, host_block, seq);
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
 }

@@ -181,6 +181,23 @@ ssw_status launch_survivors(const float *lb, const float *err, int64_t n, const 
                             int32_t k, unsigned *state, int64_t *rows, int64_t cap, int32_t *host_block, unsigned seq,
                             int device, hipStream_t stream);
 ssw_status launch_scatter_scores(const int64_t *rows, const float *v, int64_t m, float *scores, hipStream_t stream);
+// the same for a chunk of w <= 16 queries, bounded together by one pass on the int8 matrix core (prune.hip, "Pruned
+// batch").  mq: Q8_MQ_WORDS words a slot ([0] survivors, [1] Q, [2] unboundable, [3] e, [4] t2, [5] selection failed);
+// planes: q8_mq_plane_bytes(dim) bytes of query codes; slab j of the bounds is side + j * stride, the last one `own`.
+constexpr int Q8_MQ_WIDTH = 16, Q8_MQ_WORDS = 8;
+size_t q8_mq_plane_bytes(int32_t dim);
+ssw_status launch_q8_query_mq(const float *qb_dev, int32_t dim, int32_t w, unsigned *mq, int8_t *planes, float *q_last,
+                              hipStream_t stream);
+ssw_status launch_q8_bounds_mq(const int8_t *codes, const float *scale, const float *err, const int8_t *planes,
+                               const unsigned *mq, int32_t w, float *side, int64_t stride, float *own, int64_t n,
+                               int32_t dim, int32_t *dbg_hi, int32_t *dbg_lo, int device, hipStream_t stream);
+ssw_status launch_survivors_mq(const float *lb, const float *err, const float *scale, int64_t n, int32_t dim,
+                               const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *slot_state,
+                               int64_t *rows, int64_t cap, int device, hipStream_t stream);
+ssw_status launch_prune_publish_mq(const unsigned *mq, int32_t w, int64_t cap, int32_t *host_block, unsigned seq,
+                                   hipStream_t stream);
+// blocks and 16-row tiles per request of the launch launch_q8_bounds_mq would make
+void q8_bounds_mq_shape(int32_t dim, int device, int64_t n, int *out_blocks, int *out_tiles);
 // rows between natural order and the index.  to_h16: n rows of natural-order f32 (src_f32) or binary16 (src_h16, the
 // other NULL) -> rows [0, n) of dst in the f16 layout, rounded to nearest even.  gather: rows (rows_or_null[i], or
 // first_row + i when it is NULL) of an index matrix of element type dtype -> n natural-order f32 rows of out.
@@ -192,6 +209,7 @@ ssw_status launch_gather_rows(const void *X, int32_t dtype, const int64_t *rows_
 void tune_scan(int variant, int blocks_per_cu);
 void tune_scan_batch(int max_width, int blocks_per_cu);
 void tune_q8_bounds(int blocks_per_cu, int group_loads);
+void tune_q8_bounds_mq(int blocks_per_cu, int tiles);
 #endif
 // knn.hip's last stage (lives in scan.hip to share the scan's summation order)
 ssw_status launch_knn_rescore(const float *X, int32_t dim, const int32_t *perm, int r0, int rows, const uint64_t *buf,

@@ -209,10 +209,13 @@ class DeviceIndex:
         _lib.call("ssw_index_scan_batch", self._h, _ptr(Q), Q.shape[0], _ptr(out))
         return out
 
-    def topk_batch(self, Q: np.ndarray, k: int, excluded=None):
+    def topk_batch(self, Q: np.ndarray, k: int, excluded=None, prune: bool = False):
         """`[topk(Q[b], k, excluded[b]) for b]` with the rows read once per chunk of queries (ssw_index_topk_batch):
         a list of (images, scores, rows), bit for bit what the single calls return.  `excluded` is None or a sequence of
-        nq iterables of image positions, each of which may be None.  The handle is left as after the last query's topk."""
+        nq iterables of image positions, each of which may be None.  The handle is left as after the last query's topk.
+        `prune=True` (ssw_index_topk_batch_pruned): on an index whose single `topk` is pruned, one pass over the int8
+        shadow bounds a chunk of up to 16 queries and only each query's survivors are scored exactly -- the same
+        results; `prune_stats` counts every query.  Any other index takes the plain batch."""
         k = int(k)
         Q = self._queries(Q)
         nq = Q.shape[0]
@@ -221,8 +224,8 @@ class DeviceIndex:
         scs = np.empty((nq, k), dtype=np.float32)
         rows = np.empty((nq, k), dtype=np.int64)
         cnt = np.zeros(nq, dtype=np.int32)
-        _lib.call("ssw_index_topk_batch", self._h, _ptr(Q), nq, _ptr(ids), _ptr(offsets), k, _ptr(imgs), _ptr(scs),
-                  _ptr(rows), _ptr(cnt))
+        _lib.call("ssw_index_topk_batch_pruned" if prune else "ssw_index_topk_batch", self._h, _ptr(Q), nq, _ptr(ids),
+                  _ptr(offsets), k, _ptr(imgs), _ptr(scs), _ptr(rows), _ptr(cnt))
         return [(imgs[b, :c].copy(), scs[b, :c].copy(), rows[b, :c].copy()) for b, c in enumerate(cnt.tolist())]
 
     def load_scores(self, scores: np.ndarray):

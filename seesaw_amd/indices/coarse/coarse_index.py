@@ -91,10 +91,11 @@ class CoarseIndex(AccessMethod):
         return {"dbidxs": ret, "nextstartk": len(exclude) + ret.shape[0],
                 "activations": ActivationFrames(boxes, ret, np.asarray(scores))}
 
-    def query_batch(self, *, topk, vectors, excludes=None, **kwargs):
+    def query_batch(self, *, topk, vectors, excludes=None, prune=False, **kwargs):
         """one `DeviceIndex.topk_batch` call for the vectors that are given: the list of dicts `query` returns, entry by
         entry identical to it.  A `None` vector (random order) and a query whose exclude set covers the whole index
-        keep going through `query`."""
+        keep going through `query`.  `prune` is `DeviceIndex.topk_batch`'s: the same results from the shared int8
+        pre-scan on an index large enough for it."""
         vectors = list(vectors)
         excludes = [None] * len(vectors) if excludes is None else list(excludes)
         if len(excludes) != len(vectors):
@@ -110,7 +111,7 @@ class CoarseIndex(AccessMethod):
             Q = np.stack([np.asarray(vectors[i], dtype=np.float32).reshape(-1) for i in batch])
             # one k for the launch; every query keeps its own min(topk, included) results
             ks = [min(int(topk), n - excl_pos[i].shape[0]) for i in batch]
-            res = self._dev.topk_batch(Q, max(ks), excluded=[excl_pos[i] for i in batch])
+            res = self._dev.topk_batch(Q, max(ks), excluded=[excl_pos[i] for i in batch], prune=prune)
             for i, k_i, (pos, scores, _) in zip(batch, ks, res):
                 ret = self._dbidx[pos[:k_i]]
                 assert ret.shape[0] == k_i

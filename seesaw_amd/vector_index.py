@@ -46,8 +46,9 @@ class VectorIndex:
         ids, scores, _ = self._dev.topk(vector, min(int(top_k), self.n))
         return ids, scores
 
-    def query_batch(self, vectors, top_k):
-        """`[query(v, top_k) for v in vectors]` from one pass over the rows per chunk of queries: vectors [nq, 512]"""
+    def query_batch(self, vectors, top_k, prune=False):
+        """`[query(v, top_k) for v in vectors]` from one pass over the rows per chunk of queries: vectors [nq, 512];
+        `prune` is `DeviceIndex.topk_batch`'s"""
         vectors = np.asarray(vectors)
         assert vectors.ndim == 2 and vectors.shape[1] == 512
-        return [(ids, scores) for ids, scores, _ in self._dev.topk_batch(vectors, min(int(top_k), self.n))]
+        return [(ids, scores) for ids, scores, _ in self._dev.topk_batch(vectors, min(int(top_k), self.n), prune=prune)]
