@@ -253,6 +253,28 @@ ssw_status ssw_index_rescore_avg(ssw_index *idx, const int64_t *image_positions,
 ssw_status ssw_index_rescore_avg_f64(ssw_index *idx, const double *dev_scores, const int64_t *image_positions, int32_t m,
                                      int32_t aug_larger, double *out_scores, int64_t *out_best_rows);
 
+/* Both stages of the multiscale lookup for nq queries: ssw_index_topk_batch, and for every query the aggregation of
+ * ssw_index_rescore_avg over the images it selected, read from the query's OWN score slab while the chunk is alive (a
+ * batch leaves only its last query's scores resident, so the single entry cannot follow it).
+ * First stage: arguments, results, errors, chunking, the side buffer and the state afterwards are exactly those of
+ * ssw_index_topk_batch -- the full-precision scan for nq >= 2; nq == 1 IS ssw_index_topk, pruning included, after
+ * which the resident scores are completed (one full scan of the query on a pruned index).
+ * Second stage: after query b's selection has been collected (so after a deep rerun too) one launch of one workgroup
+ * per result slot takes its candidates from the handle's device result buffers (ssw_index_result_ptrs) and the tile
+ * scores from slab b, on the same stream, before the next query's selection overwrites those buffers; no candidate
+ * list travels to the host and back.  A chunk's results come back in one copy per array and ONE host wait.
+ * out_avg_scores / out_avg_rows [nq, k]: entry [b, i], i < out_counts[b], belongs to out_images[b, i] and holds the
+ * bits ssw_index_rescore_avg returns for that image when q[b]'s scores are resident (no minus form); entries from
+ * out_counts[b] on are unspecified.  aug_larger: that entry's codes, 0 / 1 / 2, optionally + 4.
+ * Errors, before anything is enqueued: no row map or tile meta, a bad aug_larger or an image of more than 2048 tiles
+ * ANYWHERE in the index are SSW_ERR_INVALID -- index-wide, because the candidates are not known to the host at launch
+ * (ssw_index_rescore_avg checks the images it is given only).
+ * Memory: the first call adds two device arrays of 16 x SSW_MAX_TOPK entries (f32 + i64: 768 KiB). */
+ssw_status ssw_index_topk_batch_avg(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
+                                    const int64_t *excluded_offsets, int32_t k, int32_t aug_larger, int64_t *out_images,
+                                    float *out_scores, int64_t *out_best_rows, float *out_avg_scores,
+                                    int64_t *out_avg_rows, int32_t *out_counts);
+
 /* merge several sorted key lists (e.g. the all-gathered per-shard top-k of a
  * row-sharded index; keys as in ssw_index_result_ptrs but with GLOBAL image ids
  * added by the caller via id_offsets) into the global top-k.  All pointers device. */

@@ -121,9 +121,14 @@ struct BatchState {
     PinnedStage qb_stage;
     float *side = nullptr;    // [side_slabs, slab_stride]
     int side_slabs = 0;
+    // second stage of a chunk (ssw_index_topk_batch_avg): [BATCH_MAX_WIDTH, SSW_MAX_TOPK] each
+    float *avg_score = nullptr;
+    int64_t *avg_row = nullptr;
     void release() {
         (void)hipFree(qb_dev);
         (void)hipFree(side);
+        (void)hipFree(avg_score);
+        (void)hipFree(avg_row);
         qb_stage.release();
     }
 };
@@ -164,6 +169,7 @@ struct ssw_index {
     PinnedStage q2_stage;
     // tile geometry + staging of the avg_score aggregation (rescore.hip)
     std::vector<int64_t> row_start_host;  // host mirror of row_start
+    int64_t max_image_tiles = -1;  // the most rows of one image; -1: not computed since the map was set
     float *tile_boxes = nullptr;   // [n, 4] x1, y1, x2, y2
     int32_t *tile_zoom = nullptr;  // [n]
     int64_t *rs_pos = nullptr, *rs_off = nullptr, *rs_row = nullptr;  // [rs_cap]
@@ -632,6 +638,7 @@ ssw_status ssw_index_set_row2image(ssw_index *idx, const int32_t *row2image_host
     (void)hipFree(idx->row_start);
     idx->row_start = nullptr;
     idx->row_start_host.clear();
+    idx->max_image_tiles = -1;
     if (row2image_host == nullptr) {
         idx->has_map = false;
         idx->n_images = idx->n;
@@ -1299,9 +1306,55 @@ ssw_status ssw_index_scan_batch(ssw_index *idx, const float *q_host, int32_t nq,
     return SSW_OK;
 }
 
-ssw_status ssw_index_topk_batch(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
-                                const int64_t *excluded_offsets, int32_t k, int64_t *out_images, float *out_scores,
-                                int64_t *out_best_rows, int32_t *out_counts) {
+// the second stage of a batch (ssw_index_topk_batch_avg): the aggregation code and the host outputs [nq, k]
+struct AvgStage {
+    int32_t aug;
+    float *out_scores;
+    int64_t *out_rows;
+};
+
+// the most rows of one image of the index (the aggregation sizes its LDS by it): computed once per image map
+static int64_t max_image_tiles(ssw_index *idx) {
+    if (idx->max_image_tiles < 0) {
+        int64_t m = 0;
+        for (size_t p = 0; p + 1 < idx->row_start_host.size(); ++p)
+            m = std::max(m, idx->row_start_host[p + 1] - idx->row_start_host[p]);
+        idx->max_image_tiles = m;
+    }
+    return idx->max_image_tiles;
+}
+
+static ssw_status ensure_avg_buffers(ssw_index *idx) {
+    BatchState &bt = idx->batch;
+    const size_t slots = (size_t)BATCH_MAX_WIDTH * SSW_MAX_TOPK;
+    if (!bt.avg_row) SSW_HIP_TRY(hipMalloc((void **)&bt.avg_row, slots * sizeof(int64_t)));
+    if (!bt.avg_score) SSW_HIP_TRY(hipMalloc((void **)&bt.avg_score, slots * sizeof(float)));
+    return SSW_OK;
+}
+
+// the aggregation of the images the selection that has just run on the stream left in the handle's result buffers,
+// over the tile scores in `scores`, into row j of the chunk's device arrays
+static ssw_status enqueue_avg_of_result(ssw_index *idx, const float *scores, int32_t k, int32_t aug, int j) {
+    BatchState &bt = idx->batch;
+    return launch_avg_score_keys(idx->tile_boxes, idx->tile_zoom, scores, idx->row_start, idx->n_images, idx->ws.out_keys,
+                                 idx->ws.out_count, k, (int32_t)idx->max_image_tiles, aug, bt.avg_score + (size_t)j * k,
+                                 bt.avg_row + (size_t)j * k, idx->stream);
+}
+
+// rows [0, w) of the chunk's device arrays -> the caller's rows [b, b + w): one copy each and ONE host wait
+static ssw_status collect_avg(ssw_index *idx, const AvgStage *avg, int32_t b, int w, int32_t k) {
+    BatchState &bt = idx->batch;
+    const size_t o = (size_t)b * k, m = (size_t)w * k;
+    SSW_HIP_TRY(hipMemcpyAsync(avg->out_scores + o, bt.avg_score, m * sizeof(float), hipMemcpyDeviceToHost, idx->stream));
+    SSW_HIP_TRY(hipMemcpyAsync(avg->out_rows + o, bt.avg_row, m * sizeof(int64_t), hipMemcpyDeviceToHost, idx->stream));
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+    return SSW_OK;
+}
+
+// ssw_index_topk_batch; with `avg`, every query's selection is followed by the aggregation over its own slab
+static ssw_status topk_batch_run(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
+                                 const int64_t *excluded_offsets, int32_t k, int64_t *out_images, float *out_scores,
+                                 int64_t *out_best_rows, int32_t *out_counts, const AvgStage *avg) {
     SSW_REQUIRE(nq >= 1, "nq=%d < 1", nq);
     SSW_REQUIRE(idx != nullptr && q_host != nullptr && out_counts != nullptr, "NULL argument");
     SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
@@ -1321,10 +1374,17 @@ ssw_status ssw_index_topk_batch(ssw_index *idx, const float *q_host, int32_t nq,
     if (nq == 1) {  // the single call itself, pruning included
         int64_t n_ex = 0;
         const int64_t *ex = excl(0, &n_ex);
-        return ssw_index_topk(idx, q_host, ex, n_ex, k, out_images, out_scores, out_best_rows, out_counts);
+        SSW_TRY(ssw_index_topk(idx, q_host, ex, n_ex, k, out_images, out_scores, out_best_rows, out_counts));
+        if (!avg || idx->n_images == 0) return SSW_OK;
+        DeviceGuard guard(idx->device);
+        SSW_TRY(ensure_full_scores(idx));  // a pruned top-k left exact scores for its survivors only
+        SSW_TRY(ensure_avg_buffers(idx));
+        SSW_TRY(enqueue_avg_of_result(idx, idx->scores, k, avg->aug, 0));
+        return collect_avg(idx, avg, 0, 1, k);
     }
     DeviceGuard guard(idx->device);
     SSW_TRY(ensure_full_scores(idx));
+    if (avg) SSW_TRY(ensure_avg_buffers(idx));
     int W = 1;
     SSW_TRY(batch_width(idx, nq, &W));
     const size_t dim = (size_t)idx->dim;
@@ -1348,10 +1408,41 @@ ssw_status ssw_index_topk_batch(ssw_index *idx, const float *q_host, int32_t nq,
             SSW_TRY(topk_collect(idx, slab[j], idx->stream, k, out_images ? out_images + o : nullptr,
                                  out_scores ? out_scores + o : nullptr, out_best_rows ? out_best_rows + o : nullptr,
                                  out_counts + b + j));
+            // after the collect: after a deep rerun too, and before the next query's selection takes the result buffers
+            if (avg) SSW_TRY(enqueue_avg_of_result(idx, slab[j], k, avg->aug, j));
         }
+        if (avg) SSW_TRY(collect_avg(idx, avg, b, w, k));  // (before the next chunk's scan takes the slabs)
         b += w;
     }
     return SSW_OK;
+}
+
+ssw_status ssw_index_topk_batch(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
+                                const int64_t *excluded_offsets, int32_t k, int64_t *out_images, float *out_scores,
+                                int64_t *out_best_rows, int32_t *out_counts) {
+    return topk_batch_run(idx, q_host, nq, excluded_images, excluded_offsets, k, out_images, out_scores, out_best_rows,
+                          out_counts, nullptr);
+}
+
+ssw_status ssw_index_topk_batch_avg(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
+                                    const int64_t *excluded_offsets, int32_t k, int32_t aug_larger, int64_t *out_images,
+                                    float *out_scores, int64_t *out_best_rows, float *out_avg_scores,
+                                    int64_t *out_avg_rows, int32_t *out_counts) {
+    SSW_REQUIRE(nq >= 1, "nq=%d < 1", nq);
+    SSW_REQUIRE(idx != nullptr && q_host != nullptr && out_counts != nullptr && out_avg_scores != nullptr &&
+                    out_avg_rows != nullptr,
+                "NULL argument");
+    SSW_REQUIRE(aug_larger >= 0 && (aug_larger & 3) <= 2 && aug_larger <= 6,
+                "aug_larger=%d is not 0 (all), 1 (greater) or 2 (adjacent), optionally + 4 (aug_weight = cont_weighted)", aug_larger);
+    SSW_REQUIRE(idx->has_map && idx->tile_boxes && idx->tile_zoom,
+                "topk_batch_avg needs ssw_index_set_row2image and ssw_index_set_tile_meta first");
+    const int64_t max_tiles = max_image_tiles(idx);
+    SSW_REQUIRE(max_tiles <= SSW_RESCORE_MAX_TILES,
+                "the index has an image with %lld tiles, more than the %d the kernel keeps in LDS", (long long)max_tiles,
+                SSW_RESCORE_MAX_TILES);
+    const AvgStage avg{aug_larger, out_avg_scores, out_avg_rows};
+    return topk_batch_run(idx, q_host, nq, excluded_images, excluded_offsets, k, out_images, out_scores, out_best_rows,
+                          out_counts, &avg);
 }
 
 // ---- the pruned batch: ONE pass over the int8 shadow bounds a chunk of up to 16 queries (prune.hip, "Pruned batch") ----

@@ -39,27 +39,18 @@ __device__ __forceinline__ float iou_f32(const float4 a, float area_a, const flo
     return __fdiv_rn(inter, uni);
 }
 
-// boxes: x1, y1, x2, y2 per row.  cand_pos[c] = image position; its rows are [row_start[p], row_start[p+1]).
-// minus (optional) holds one value per candidate row, in candidate order (cand_off[c] = first), subtracted from
-// the resident score (the vector2 form of MultiscaleIndex.query).
+// The aggregation of ONE image by one workgroup: its tiles are rows [r0, r0 + T), `scores` holds one value per index
+// row, minus_or_null (optional) one per tile of this image.  Writes out_score[c] / out_row[c].  Both entry kernels
+// below run it, so the arithmetic exists once.
 // ST = the dtype of the score column: float for the scan's scores (pandas' float32 group mean), double for the graph
 // loops, which hand rescore_candidates the label-propagation output as float64 (graph_based.py:100-108; pandas' float64
 // group mean is the same Kahan sum in f64).  IoUs are f32 either way (the boxes are).
 template <typename ST>
-__global__ __launch_bounds__(RS_THREADS) void k_avg_score(const float4 *__restrict__ boxes,
-                                                          const int32_t *__restrict__ zoom,
-                                                          const ST *__restrict__ scores,
-                                                          const ST *__restrict__ minus_or_null,
-                                                          const int64_t *__restrict__ row_start,
-                                                          const int64_t *__restrict__ cand_pos,
-                                                          const int64_t *__restrict__ cand_off, int aug,
-                                                          ST *__restrict__ out_score,
-                                                          int64_t *__restrict__ out_row) {
+__device__ __forceinline__ void avg_score_of_image(const float4 *__restrict__ boxes, const int32_t *__restrict__ zoom,
+                                                   const ST *__restrict__ scores, const ST *__restrict__ minus_or_null,
+                                                   const int64_t r0, const int T, int aug, const int c,
+                                                   ST *__restrict__ out_score, int64_t *__restrict__ out_row) {
     extern __shared__ float4 sh4[];
-    const int c = blockIdx.x;
-    const int64_t p = cand_pos[c];
-    const int64_t r0 = row_start[p];
-    const int T = (int)(row_start[p + 1] - r0);
     float4 *sbox = sh4;                                   // [T]
     ST *sscore = reinterpret_cast<ST *>(sbox + T);        // [T]  (8-byte types first: the base is 16-byte aligned)
     ST *sagg = sscore + T;                                // [T]
@@ -73,7 +64,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_avg_score(const float4 *__restri
         sbox[i] = b;
         sarea[i] = __fmul_rn(__fsub_rn(b.z, b.x), __fsub_rn(b.w, b.y));
         ST s = scores[r0 + i];
-        if (minus_or_null) s = s - minus_or_null[cand_off[c] + i];
+        if (minus_or_null) s = s - minus_or_null[i];
         sscore[i] = s;
         const int z = zoom[r0 + i];
         szoom[i] = z;
@@ -174,10 +165,67 @@ __global__ __launch_bounds__(RS_THREADS) void k_avg_score(const float4 *__restri
     }
 }
 
+// boxes: x1, y1, x2, y2 per row.  cand_pos[c] = image position; its rows are [row_start[p], row_start[p+1]).
+// minus (optional) holds one value per candidate row, in candidate order (cand_off[c] = first), subtracted from
+// the resident score (the vector2 form of MultiscaleIndex.query).
+template <typename ST>
+__global__ __launch_bounds__(RS_THREADS) void k_avg_score(const float4 *__restrict__ boxes,
+                                                          const int32_t *__restrict__ zoom,
+                                                          const ST *__restrict__ scores,
+                                                          const ST *__restrict__ minus_or_null,
+                                                          const int64_t *__restrict__ row_start,
+                                                          const int64_t *__restrict__ cand_pos,
+                                                          const int64_t *__restrict__ cand_off, int aug,
+                                                          ST *__restrict__ out_score,
+                                                          int64_t *__restrict__ out_row) {
+    const int c = blockIdx.x;
+    const int64_t p = cand_pos[c];
+    const int64_t r0 = row_start[p];
+    const int T = (int)(row_start[p + 1] - r0);
+    avg_score_of_image<ST>(boxes, zoom, scores, minus_or_null ? minus_or_null + cand_off[c] : nullptr, r0, T, aug, c,
+                           out_score, out_row);
+}
+
+// The candidates are the result slots of the selection that has just run on the stream (select.hip: keys [count] =
+// (orderable(score) << 32) | (0xFFFFFFFF - image position), descending): one workgroup per slot, launched for k slots;
+// a slot the selection did not fill writes nothing.  `scores` is the score slab the selection ranked -- of a batch,
+// the slab of this query -- so no candidate list travels to the host and back between the two stages.
+__global__ __launch_bounds__(RS_THREADS) void k_avg_score_keys(const float4 *__restrict__ boxes,
+                                                               const int32_t *__restrict__ zoom,
+                                                               const float *__restrict__ scores,
+                                                               const int64_t *__restrict__ row_start, int64_t n_images,
+                                                               const uint64_t *__restrict__ keys,
+                                                               const int32_t *__restrict__ count, int aug,
+                                                               float *__restrict__ out_score,
+                                                               int64_t *__restrict__ out_row) {
+    const int c = blockIdx.x;
+    if (c >= count[0]) return;
+    const int64_t p = (int64_t)(0xffffffffu - (uint32_t)(keys[c] & 0xffffffffull));
+    if (p >= n_images) return;  // (never a key of this index: the LDS is sized for its images only)
+    const int64_t r0 = row_start[p];
+    const int T = (int)(row_start[p + 1] - r0);
+    avg_score_of_image<float>(boxes, zoom, scores, nullptr, r0, T, aug, c, out_score, out_row);
+}
+
 }  // namespace
 
 size_t avg_score_lds_bytes(int max_tiles, size_t score_bytes) {
     return (size_t)max_tiles * (sizeof(float4) + 2 * score_bytes + sizeof(float) + sizeof(int));
+}
+
+// the dynamic LDS of a launch of `kernel` for images of up to max_tiles tiles; above 64 KB the kernel's limit is raised
+static ssw_status avg_score_lds(const void *kernel, int32_t max_tiles, size_t score_bytes, size_t *out_lds) {
+    if (max_tiles > SSW_RESCORE_MAX_TILES) {
+        set_error("avg_score: an image with %d tiles exceeds the %d the kernel keeps in LDS", max_tiles,
+                  SSW_RESCORE_MAX_TILES);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    *out_lds = avg_score_lds_bytes(max_tiles, score_bytes);
+    if (*out_lds > (size_t)64 * 1024) {  // 2048 tiles of f64 scores: 80 KB
+        // per device and cheap: set on every such launch instead of caching a process-wide flag
+        SSW_HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+    }
+    return SSW_OK;
 }
 
 template <typename ST>
@@ -185,20 +233,24 @@ static ssw_status launch_avg_score_t(const float *boxes, const int32_t *zoom, co
                                      const int64_t *row_start, const int64_t *cand_pos, const int64_t *cand_off, int32_t m,
                                      int32_t max_tiles, int32_t aug, ST *out_score, int64_t *out_row, hipStream_t stream) {
     if (m <= 0) return SSW_OK;
-    if (max_tiles > SSW_RESCORE_MAX_TILES) {
-        set_error("avg_score: an image with %d tiles exceeds the %d the kernel keeps in LDS", max_tiles,
-                  SSW_RESCORE_MAX_TILES);
-        return SSW_ERR_UNSUPPORTED;
-    }
-    const size_t lds = avg_score_lds_bytes(max_tiles, sizeof(ST));
-    if (lds > (size_t)64 * 1024) {  // 2048 tiles of f64 scores: 80 KB
-        // per device and cheap: set on every such launch instead of caching a process-wide flag
-        SSW_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_avg_score<ST>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    }
+    size_t lds = 0;
+    SSW_TRY(avg_score_lds(reinterpret_cast<const void *>(k_avg_score<ST>), max_tiles, sizeof(ST), &lds));
     hipLaunchKernelGGL(k_avg_score<ST>, dim3((unsigned)m), dim3(RS_THREADS), lds, stream,
                        reinterpret_cast<const float4 *>(boxes), zoom, scores, minus_or_null, row_start, cand_pos,
                        cand_off, (int)aug, out_score, out_row);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+ssw_status launch_avg_score_keys(const float *boxes, const int32_t *zoom, const float *scores, const int64_t *row_start,
+                                 int64_t n_images, const uint64_t *keys, const int32_t *count, int32_t k,
+                                 int32_t max_tiles, int32_t aug, float *out_score, int64_t *out_row, hipStream_t stream) {
+    if (k <= 0) return SSW_OK;
+    size_t lds = 0;
+    SSW_TRY(avg_score_lds(reinterpret_cast<const void *>(k_avg_score_keys), max_tiles, sizeof(float), &lds));
+    hipLaunchKernelGGL(k_avg_score_keys, dim3((unsigned)k), dim3(RS_THREADS), lds, stream,
+                       reinterpret_cast<const float4 *>(boxes), zoom, scores, row_start, n_images, keys, count, (int)aug,
+                       out_score, out_row);
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
 }

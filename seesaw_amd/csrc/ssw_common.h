@@ -377,6 +377,12 @@ constexpr int SSW_RESCORE_MAX_ZOOM = 31;     // zoom levels index a 32-bit prese
 ssw_status launch_avg_score(const float *boxes, const int32_t *zoom, const float *scores, const float *minus_or_null,
                             const int64_t *row_start, const int64_t *cand_pos, const int64_t *cand_off, int32_t m,
                             int32_t max_tiles, int32_t aug, float *out_score, int64_t *out_row, hipStream_t stream);
+// the same aggregation for the result slots of the selection that has just run on `stream` (keys / count as in
+// SelectWorkspace): k workgroups, slot c < count writes out_score[c] / out_row[c]; max_tiles = the most tiles of any
+// image of the index
+ssw_status launch_avg_score_keys(const float *boxes, const int32_t *zoom, const float *scores, const int64_t *row_start,
+                                 int64_t n_images, const uint64_t *keys, const int32_t *count, int32_t k,
+                                 int32_t max_tiles, int32_t aug, float *out_score, int64_t *out_row, hipStream_t stream);
 // the same aggregation over float64 scores that live on the device (label-propagation output)
 ssw_status launch_avg_score_f64(const float *boxes, const int32_t *zoom, const double *scores,
                                 const int64_t *row_start, const int64_t *cand_pos, const int64_t *cand_off, int32_t m,

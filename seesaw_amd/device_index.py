@@ -257,6 +257,7 @@ class DeviceIndex:
 
     # -- second stage: avg_score aggregation ------------------------------------------
     AUG_LARGER = {"all": 0, "greater": 1, "adjacent": 2}
+    RESCORE_MAX_TILES = 2048  # tiles of one image the aggregation kernel keeps in LDS (csrc/ssw_common.h)
 
     def set_tile_meta(self, boxes: np.ndarray, zoom_level: np.ndarray):
         """tile boxes [n_rows, 4] = x1, y1, x2, y2 (f32) and zoom levels [n_rows] of every row"""
@@ -277,6 +278,28 @@ class DeviceIndex:
         aug = self.AUG_LARGER[aug_larger] | {"level_max": 0, "cont_weighted": 4}[aug_weight]
         _lib.call("ssw_index_rescore_avg", self._h, _ptr(pos), m, aug, _ptr(minus), _ptr(scores), _ptr(rows))
         return scores, rows
+
+    def topk_batch_avg(self, Q: np.ndarray, k: int, aug_larger: str, excluded=None, aug_weight: str = "level_max"):
+        """both stages for a batch (ssw_index_topk_batch_avg): `topk_batch(Q, k, excluded)` and, for every query, what
+        `rescore_avg(images, aug_larger, aug_weight=aug_weight)` returns for the images it selected while that query's
+        scores are resident -- read from the query's own score slab inside the batch.  A list of
+        (images, scores, rows, avg_scores, avg_rows), `avg_*[i]` belonging to `images[i]` (selection order, not the
+        ascending order `rescore_avg` is usually given).  The handle is left as after the last query's topk."""
+        k = int(k)
+        Q = self._queries(Q)
+        nq = Q.shape[0]
+        ids, offsets = self._excluded_batch(excluded, nq)
+        aug = self.AUG_LARGER[aug_larger] | {"level_max": 0, "cont_weighted": 4}[aug_weight]
+        imgs = np.empty((nq, k), dtype=np.int64)
+        scs = np.empty((nq, k), dtype=np.float32)
+        rows = np.empty((nq, k), dtype=np.int64)
+        avg_scs = np.empty((nq, k), dtype=np.float32)
+        avg_rows = np.empty((nq, k), dtype=np.int64)
+        cnt = np.zeros(nq, dtype=np.int32)
+        _lib.call("ssw_index_topk_batch_avg", self._h, _ptr(Q), nq, _ptr(ids), _ptr(offsets), k, aug, _ptr(imgs),
+                  _ptr(scs), _ptr(rows), _ptr(avg_scs), _ptr(avg_rows), _ptr(cnt))
+        return [(imgs[b, :c].copy(), scs[b, :c].copy(), rows[b, :c].copy(), avg_scs[b, :c].copy(), avg_rows[b, :c].copy())
+                for b, c in enumerate(cnt.tolist())]
 
     def rescore_avg_f64(self, dev_scores_ptr: int, image_positions: np.ndarray, aug_larger: str,
                         aug_weight: str = "level_max"):

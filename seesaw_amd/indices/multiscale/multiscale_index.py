@@ -320,10 +320,60 @@ class MultiscaleIndex(AccessMethod):
             if positions.size else np.zeros(0, dtype=np.int64)
 
     def query_batch(self, *, topk, vectors, excludes=None, **kwargs):
-        """the per-query loop of AccessMethod.query_batch, on purpose: the second stage (rescore_avg) reads the
-        RESIDENT tile scores of its own query, and DeviceIndex.topk_batch leaves only the last query's resident.
-        A device batch here needs the aggregation to read a selectable score slab -- a follow-up."""
-        return super().query_batch(topk=topk, vectors=vectors, excludes=excludes, **kwargs)
+        """`[query(vector=v, topk=topk, exclude=e, **kwargs) for v, e in zip(vectors, excludes)]`, entry by entry
+        identical to it, with the rows read once per chunk of up to 16 queries: `plain_score` ends in
+        `DeviceIndex.topk_batch`, every other agg_method in `DeviceIndex.topk_batch_avg`, whose second stage reads each
+        query's own score slab while the chunk is alive (one k = the largest shortlist of the batch; each query keeps
+        its own first min(shortlist_size, included) candidates).  Entries that keep going through `query`: no vector,
+        an exclude set that covers the index, and the whole call when `vector2` is given, when the index has no tile
+        geometry on the device (the host-side `rescore_candidates` path) or holds an image of more tiles than the
+        kernel takes.  Afterwards `_resident_q` names the query whose scores are resident.
+        A batch always scans in full precision: on an index large enough for the single `query` to be pruned
+        (>= 2^22 rows) a small batch is expected to be slower per query than the loop (`topk_batch` against the
+        pruned `topk` crosses over at nq = 4 to 8; this method itself is not measured yet, DESIGN.md section 4,
+        "Batched multiscale query") -- callers who want the pruned single path call `query`.  The `vector2` form, the
+        pruned batch and the sharded index remain a follow-up."""
+        vectors = list(vectors)
+        excludes = [None] * len(vectors) if excludes is None else list(excludes)
+        if len(excludes) != len(vectors):
+            raise ValueError(f"excludes has {len(excludes)} entries for {len(vectors)} vectors")
+        plain = kwargs.get("agg_method") == "plain_score"
+        on_device = plain or (self._has_tile_meta and
+                              int(np.diff(self._row_start).max(initial=0)) <= DeviceIndex.RESCORE_MAX_TILES)
+        if kwargs.get("vector2") is not None or not on_device or "shortlist_size" not in kwargs:
+            return super().query_batch(topk=topk, vectors=vectors, excludes=excludes, **kwargs)
+        shortlist_size = kwargs["shortlist_size"]
+        if shortlist_size is None:
+            shortlist_size = topk * 5
+        n = self._dbidx.shape[0]
+        out = [None] * len(vectors)
+        excl_pos = [None if v is None else self._excluded_positions(e) for v, e in zip(vectors, excludes)]
+        batch = [i for i, v in enumerate(vectors) if v is not None and excl_pos[i].shape[0] < n]
+        for i in range(len(vectors)):
+            if i not in batch:
+                out[i] = self.query(topk=topk, vector=vectors[i], exclude=excludes[i], **kwargs)
+        if not batch:
+            return out
+        if shortlist_size < topk * 5:
+            print(f"Warning: shortlist_size parameter {shortlist_size} is small compared to topk param {topk}, "
+                  "you may consider increasing it")
+        Q = np.stack([np.asarray(vectors[i], dtype=np.float32).reshape(-1) for i in batch])
+        # one k for the launch; every query keeps its own min(shortlist_size, included) candidates
+        ks = [min(int(shortlist_size), n - excl_pos[i].shape[0]) for i in batch]
+        excluded = [excl_pos[i] for i in batch]
+        if plain:
+            for i, k_i, (pos, scores, best_rows) in zip(batch, ks, self._dev.topk_batch(Q, max(ks), excluded=excluded)):
+                cand = _Candidates(self._dbidx[pos[:k_i]], scores[:k_i], pos[:k_i], best_rows[:k_i])
+                out[i] = self._activations_from_best(cand, topk)
+        else:
+            aug_weight = kwargs.get("aug_weight", "level_max")
+            assert aug_weight in ("level_max", "cont_weighted"), aug_weight  # score_frame2's `assert False`
+            res = self._dev.topk_batch_avg(Q, max(ks), kwargs["aug_larger"], excluded=excluded, aug_weight=aug_weight)
+            for i, k_i, (pos, _, _, avg_scores, avg_rows) in zip(batch, ks, res):
+                order = np.argsort(pos[:k_i])  # rescore_candidates walks the frames in ascending dbidx order
+                out[i] = self._avg_result(pos[:k_i][order], avg_scores[:k_i][order], avg_rows[:k_i][order], topk)
+        self._resident_q = Q[-1].copy()
+        return out
 
     def query(self, *, vector, vector2=None, topk, shortlist_size, exclude=None, force_exact=False, **kwargs):
         if shortlist_size is None:
@@ -363,6 +413,11 @@ class MultiscaleIndex(AccessMethod):
             minus = self._dev.score_rows(vector2, self._candidate_rows(positions))
         assert aug_weight in ("level_max", "cont_weighted"), aug_weight  # score_frame2's `assert False`
         scores, rows = self._dev.rescore_avg(positions, aug_larger, minus, aug_weight=aug_weight)
+        return self._avg_result(positions, scores, rows, topk)
+
+    def _avg_result(self, positions, scores, rows, topk):
+        """the end of the second stage, shared by `query` and `query_batch`: `positions` ascending, with every
+        image's aggregated score and the row of its best tile -> the topk frames by np.argsort(-score)"""
         top = np.argsort(-scores.astype(np.float64))[:topk]
         return {"dbidxs": self._dbidx[positions[top]].astype("int"),
                 "activations": ActivationFrames(self._box[rows[top]], self._row_dbidx[rows[top]], scores[top])}

@@ -29,7 +29,7 @@ import pandas as pd
 
 from ...bitmap import BitMap
 from ...sharded import ShardedTopK, _DevArray, shard_bounds_by_image
-from ..interface import ActivationFrames
+from ..interface import AccessMethod, ActivationFrames
 from .multiscale_index import MultiscaleIndex, _Candidates
 
 
@@ -322,6 +322,9 @@ class ShardedMultiscaleIndex(MultiscaleIndex):
     def _activations(self, positions, rows, scores):
         return {"dbidxs": self._dbidx[positions].astype("int"),
                 "activations": ActivationFrames(self._box[rows], self._row_dbidx[rows], np.asarray(scores))}
+
+    # one query at a time: there is no whole-matrix device index (`_dev`) for MultiscaleIndex's device batch
+    query_batch = AccessMethod.query_batch
 
     def query(self, *, vector, vector2=None, topk, shortlist_size, exclude=None, force_exact=False, **kwargs):
         if shortlist_size is None:
