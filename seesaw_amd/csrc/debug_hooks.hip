@@ -2,7 +2,7 @@
 #ifndef SSW_DEBUG_HOOKS
 #error "debug_hooks.hip belongs to the lab build (-DSSW_DEBUG_HOOKS)"
 #endif
-#include "ssw_common.h"
+#include "index_handle.h"
 
 // ---------------------------------------------------------------------------------------
 // A/B harness (tools/perf_gemm.py): time one variant on seeded operands and compare its
@@ -318,3 +318,203 @@ extern "C" ssw_status ssw_debug_attn_out_stamps(uint64_t *out, int32_t n_words) 
     SSW_REQUIRE(out && n_words > 0 && n_words <= 32 * 1024, "ssw_debug_attn_out_stamps: bad arguments");
     return ssw::read_ao_stamps(out, n_words);
 }
+
+// ---------------------------------------------------------------------------------------
+// The index's certified pre-scan, step by step (csrc/index_prune.hip; the handle: index_handle.h).
+// ---------------------------------------------------------------------------------------
+using namespace ssw;
+
+static ssw_status require_shadow(ssw_index *idx, const char *who) {
+    bool ready = false;
+    SSW_TRY(ensure_shadow(idx, &ready));
+    if (!ready) {
+        set_error("%s: the shadow was refused for memory", who);
+        return SSW_ERR_NOMEM;
+    }
+    return SSW_OK;
+}
+
+// what the threshold selection leaves behind, written by hand: k keys (only the k-th is read) and [count, overflow]
+static ssw_status stand_in_threshold(ssw_index *idx, float threshold, int32_t k, int32_t sel_count, int32_t sel_overflow) {
+    std::vector<uint64_t> keys((size_t)k, (uint64_t)f32_to_ord(threshold) << 32);
+    const int32_t count[2] = {sel_count, sel_overflow};
+    SSW_HIP_TRY(hipMemcpyAsync(idx->ws.out_keys, keys.data(), keys.size() * sizeof(uint64_t), hipMemcpyHostToDevice,
+                               idx->stream));
+    SSW_HIP_TRY(hipMemcpyAsync(idx->ws.out_count, count, sizeof(count), hipMemcpyHostToDevice, idx->stream));
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));  // keys and count are pageable host memory
+    return SSW_OK;
+}
+
+extern "C" {
+
+// ---- the pre-scan's intermediate state (tests/test_prune_certificate_gpu.py) ----------------------------------------
+// Each hook drives the product's kernels through the steps scan_for_topk is made of, on the index's own buffers.
+ssw_status ssw_debug_prune_shadow(ssw_index *idx, int64_t first_row, int64_t n_rows, int8_t *out_codes, float *out_scale,
+                                  float *out_err) {
+    SSW_REQUIRE(idx != nullptr, "idx is NULL");
+    SSW_REQUIRE(first_row >= 0 && n_rows >= 0 && first_row + n_rows <= idx->n, "rows [%lld, +%lld) outside [0, %lld)",
+                (long long)first_row, (long long)n_rows, (long long)idx->n);
+    SSW_REQUIRE(prune_eligible(idx), "the index is not pruned (ssw_tune_prune, dim, borrowed or escaped rows)");
+    DeviceGuard guard(idx->device);
+    SSW_TRY(require_shadow(idx, "prune_shadow"));
+    if (n_rows > 0 && out_codes)
+        SSW_HIP_TRY(hipMemcpyAsync(out_codes, idx->prune.q8 + first_row * idx->dim, (size_t)n_rows * idx->dim,
+                                   hipMemcpyDeviceToHost, idx->stream));
+    if (n_rows > 0 && out_scale)
+        SSW_HIP_TRY(hipMemcpyAsync(out_scale, idx->prune.q8_scale + first_row, (size_t)n_rows * sizeof(float),
+                                   hipMemcpyDeviceToHost, idx->stream));
+    if (n_rows > 0 && out_err)
+        SSW_HIP_TRY(hipMemcpyAsync(out_err, idx->prune.q8_err + first_row, (size_t)n_rows * sizeof(float),
+                                   hipMemcpyDeviceToHost, idx->stream));
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_prune_bounds(ssw_index *idx, const float *q_host, float *out_lb, float *out_Q,
+                                  int32_t *out_unbounded) {
+    SSW_REQUIRE(idx != nullptr && q_host != nullptr && out_lb != nullptr && out_Q != nullptr && out_unbounded != nullptr,
+                "NULL argument");
+    SSW_TRY(check_query(idx, q_host));
+    SSW_REQUIRE(prune_eligible(idx), "the index is not pruned (ssw_tune_prune, dim, borrowed or escaped rows)");
+    DeviceGuard guard(idx->device);
+    SSW_TRY(require_shadow(idx, "prune_bounds"));
+    SSW_TRY(idx->q_stage.push(idx->q_dev, q_host, (size_t)idx->dim * sizeof(float), idx->stream));
+    SSW_TRY(prune_bounds(idx, idx->q_dev));  // as in scan_for_topk: every reader completes the buffer with the scan of q_last
+    unsigned state[4] = {0u, 0u, 0u, 0u};
+    SSW_HIP_TRY(hipMemcpyAsync(state, idx->prune.state, sizeof(state), hipMemcpyDeviceToHost, idx->stream));
+    SSW_HIP_TRY(hipMemcpyAsync(out_lb, idx->scores, (size_t)idx->n * sizeof(float), hipMemcpyDeviceToHost, idx->stream));
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+    memcpy(out_Q, &state[1], sizeof(float));
+    *out_unbounded = (int32_t)state[2];
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_prune_survivors(ssw_index *idx, float threshold, int32_t k, int32_t sel_count, int32_t sel_overflow,
+                                     int64_t cap, int32_t *out_published, int64_t *out_collected, int64_t *out_rows) {
+    SSW_REQUIRE(idx != nullptr && out_published != nullptr && out_collected != nullptr, "NULL argument");
+    SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
+    SSW_REQUIRE(cap >= 0 && cap <= SURV_CAP, "cap=%lld outside [0, %lld]", (long long)cap, (long long)SURV_CAP);
+    SSW_REQUIRE(cap == 0 || out_rows != nullptr, "out_rows is NULL");
+    SSW_REQUIRE(idx->scores_partial && idx->prune.q8 && !idx->prune.stale, "no bounds in the buffer: ssw_debug_prune_bounds first");
+    DeviceGuard guard(idx->device);
+    SSW_TRY(ensure_ws(idx));
+    SSW_HIP_TRY(hipMemsetAsync(idx->prune.state, 0, sizeof(unsigned), idx->stream));  // the counter k_q8_query resets
+    SSW_TRY(stand_in_threshold(idx, threshold, k, sel_count, sel_overflow));
+    int32_t m = -1;
+    SSW_TRY(prune_survivors(idx, k, cap, nullptr, &m));
+    unsigned collected = 0u;
+    SSW_HIP_TRY(hipMemcpyAsync(&collected, idx->prune.state, sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
+    if (m > 0)
+        SSW_HIP_TRY(hipMemcpyAsync(out_rows, idx->prune.surv_rows, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost,
+                                   idx->stream));
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+    *out_published = m;
+    *out_collected = (int64_t)collected;
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_prune_scan_mq_shape(ssw_index *idx, int32_t *out_blocks, int32_t *out_tiles) {
+    SSW_REQUIRE(idx != nullptr && out_blocks != nullptr && out_tiles != nullptr, "NULL argument");
+    SSW_REQUIRE(q8_dim_supported(idx->dim), "dim=%d has no shadow scan", idx->dim);
+    int blocks = 0, tiles = 0;
+    q8_bounds_mq_shape(idx->dim, idx->device, idx->n, &blocks, &tiles);
+    *out_blocks = blocks;
+    *out_tiles = tiles;
+    return SSW_OK;
+}
+
+// the chunk's buffers for nq queries staged from the host, for the two hooks below
+static ssw_status debug_chunk_ready(ssw_index *idx, int32_t nq) {
+    SSW_REQUIRE(prune_batch_eligible(idx), "the index is not pruned (ssw_tune_prune, dim, borrowed or escaped rows)");
+    SSW_TRY(require_shadow(idx, "prune_bounds_mq"));
+    SSW_TRY(ensure_ws(idx));
+    int w = 0;
+    SSW_TRY(batch_buffers(idx, nq, true, &w));
+    if (w == nq && idx->batch.qb_dev) SSW_TRY(ensure_prune_batch(idx, nq, &w));
+    if (w != nq || !idx->batch.qb_dev) {
+        set_error("prune_bounds_mq: no memory for a chunk of %d queries", nq);
+        return SSW_ERR_NOMEM;
+    }
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_prune_bounds_mq(ssw_index *idx, const float *q_host, int32_t nq, int32_t *out_I_hi, int32_t *out_I_lo,
+                                     float *out_lb, float *out_Qe, int8_t *out_codes) {
+    SSW_REQUIRE(idx != nullptr && q_host != nullptr, "NULL argument");
+    SSW_REQUIRE(nq >= 1 && nq <= Q8_MQ_WIDTH, "nq=%d outside [1, %d]", nq, Q8_MQ_WIDTH);
+    DeviceGuard guard(idx->device);
+    SSW_TRY(debug_chunk_ready(idx, nq));
+    PruneBatchState &pb = idx->prune_batch;
+    const size_t dim = (size_t)idx->dim, cells = (size_t)nq * idx->n;
+    int32_t *dbg = nullptr;
+    if (out_I_hi || out_I_lo) SSW_HIP_TRY(hipMalloc((void **)&dbg, 2 * cells * sizeof(int32_t)));
+    std::vector<unsigned> mq((size_t)Q8_MQ_WIDTH * Q8_MQ_WORDS);
+    std::vector<int8_t> planes(q8_mq_plane_bytes(idx->dim));
+    auto run = [&]() -> ssw_status {
+        SSW_TRY(idx->batch.qb_stage.push(idx->batch.qb_dev, q_host, (size_t)nq * dim * sizeof(float), idx->stream));
+        SSW_TRY(prune_bounds_mq(idx, nq, dbg, dbg ? dbg + cells : nullptr));
+        if (out_I_hi) SSW_HIP_TRY(hipMemcpyAsync(out_I_hi, dbg, cells * sizeof(int32_t), hipMemcpyDeviceToHost, idx->stream));
+        if (out_I_lo)
+            SSW_HIP_TRY(hipMemcpyAsync(out_I_lo, dbg + cells, cells * sizeof(int32_t), hipMemcpyDeviceToHost, idx->stream));
+        if (out_lb)
+            for (int j = 0; j < nq; ++j)
+                SSW_HIP_TRY(hipMemcpyAsync(out_lb + (size_t)j * idx->n, chunk_slab(idx, nq, j), (size_t)idx->n * sizeof(float),
+                                           hipMemcpyDeviceToHost, idx->stream));
+        SSW_HIP_TRY(hipMemcpyAsync(mq.data(), pb.mq, mq.size() * sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
+        SSW_HIP_TRY(hipMemcpyAsync(planes.data(), pb.planes, planes.size(), hipMemcpyDeviceToHost, idx->stream));
+        SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+        return SSW_OK;
+    };
+    const ssw_status st = run();
+    if (st != SSW_OK) (void)hipStreamSynchronize(idx->stream);
+    (void)hipFree(dbg);
+    SSW_TRY(st);
+    for (int j = 0; j < nq; ++j) {
+        const unsigned *w = mq.data() + (size_t)j * Q8_MQ_WORDS;
+        if (out_Qe) {
+            memcpy(out_Qe + 4 * j, &w[1], 4);      // Q
+            memcpy(out_Qe + 4 * j + 1, &w[3], 4);  // e
+            memcpy(out_Qe + 4 * j + 2, &w[4], 4);  // t2
+            out_Qe[4 * j + 3] = (float)w[2];       // 1 = the query cannot be bounded
+        }
+        if (out_codes)  // the planes' fragment order (prune.hip) back to natural element order
+            for (int pl = 0; pl < 2; ++pl)
+                for (size_t i = 0; i < dim; ++i)
+                    out_codes[((size_t)j * 2 + pl) * dim + i] =
+                        planes[(((i >> 6) * 2 + pl) * 64 + ((i & 63) >> 4) * 16 + j) * 16 + (i & 15)];
+    }
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_prune_survivors_mq(ssw_index *idx, int32_t nq, int32_t slot, float threshold, int32_t k,
+                                        int32_t sel_count, int32_t sel_overflow, int64_t cap, int32_t *out_published,
+                                        int64_t *out_collected, int64_t *out_rows) {
+    SSW_REQUIRE(idx != nullptr && out_published != nullptr && out_collected != nullptr, "NULL argument");
+    SSW_REQUIRE(nq >= 1 && nq <= Q8_MQ_WIDTH && slot >= 0 && slot < nq, "slot=%d outside the chunk of %d", slot, nq);
+    SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
+    SSW_REQUIRE(cap >= 0 && cap <= SURV_CAP, "cap=%lld outside [0, %lld]", (long long)cap, (long long)SURV_CAP);
+    SSW_REQUIRE(cap == 0 || out_rows != nullptr, "out_rows is NULL");
+    PruneBatchState &pb = idx->prune_batch;
+    SSW_REQUIRE(idx->scores_partial && idx->prune.q8 && !idx->prune.stale && pb.slots >= nq && idx->batch.side_slabs >= nq - 1,
+                "no bounds of such a chunk in the buffers: ssw_debug_prune_bounds_mq first");
+    DeviceGuard guard(idx->device);
+    SSW_TRY(ensure_ws(idx));
+    unsigned *st = pb.mq + slot * Q8_MQ_WORDS;
+    SSW_HIP_TRY(hipMemsetAsync(st, 0, sizeof(unsigned), idx->stream));      // the counter and the "selection failed"
+    SSW_HIP_TRY(hipMemsetAsync(st + 5, 0, sizeof(unsigned), idx->stream));  // word k_q8_query_mq resets
+    SSW_TRY(stand_in_threshold(idx, threshold, k, sel_count, sel_overflow));
+    SSW_TRY(prune_survivors_slot(idx, nq, slot, k, cap));
+    int32_t m[Q8_MQ_WIDTH];
+    SSW_TRY(prune_publish_mq(idx, nq, cap, nullptr, m));
+    unsigned collected = 0u;
+    SSW_HIP_TRY(hipMemcpyAsync(&collected, st, sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
+    if (m[slot] > 0)
+        SSW_HIP_TRY(hipMemcpyAsync(out_rows, pb.surv_rows + (int64_t)slot * SURV_CAP, (size_t)m[slot] * sizeof(int64_t),
+                                   hipMemcpyDeviceToHost, idx->stream));
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+    *out_published = m[slot];
+    *out_collected = (int64_t)collected;
+    return SSW_OK;
+}
+
+}  // extern "C"

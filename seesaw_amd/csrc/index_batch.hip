@@ -1,0 +1,310 @@
+// index_batch.hip -- several queries in one pass over the index's rows (scan.hip: batch_scores_kernel): the batched scan
+// and the batched top-k, plain, pruned and two-stage, on one driver.  The handle: index_handle.h.  A batch is cut into chunks of the widest kernel form the shape and the side buffer allow, the remainder into
+// narrower ones and at last single queries.  A chunk's last query scores into the handle's own buffer, the others into
+// the side slabs; the selection then runs slab by slab through the single-query path (topk_enqueue / topk_collect).
+#include <algorithm>
+#include <cmath>
+
+#include "index_handle.h"
+
+using namespace ssw;
+
+int64_t ssw::slab_stride(const ssw_index *idx) { return (idx->n + 64 + 63) & ~(int64_t)63; }  // slabs stay 256-byte aligned
+
+// slab j of a chunk of w queries: where the scan, the pruned chunk's steps and the lab hooks put query j's scores
+float *ssw::chunk_slab(ssw_index *idx, int w, int j) {
+    return j + 1 < w ? idx->batch.side + (int64_t)j * slab_stride(idx) : idx->scores;
+}
+
+// the chunk's buffers for a width of w: the width they could be grown to.  The query block is allocated from a width
+// of 2 on, with_queries: at any width (the pruned batch's chunk of one query reads it there); it may be missing after.
+ssw_status ssw::batch_buffers(ssw_index *idx, int w, bool with_queries, int *out_w) {
+    BatchState &bt = idx->batch;
+    if ((w >= 2 || with_queries) && !bt.qb_dev) {
+        if (hipMalloc((void **)&bt.qb_dev, (size_t)BATCH_MAX_WIDTH * idx->dim * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            bt.qb_dev = nullptr;
+            w = 1;
+        }
+    }
+    while (w >= 2 && bt.side_slabs < w - 1) {  // grow; on failure keep halving the width
+        SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+        (void)hipFree(bt.side);
+        bt.side = nullptr;
+        bt.side_slabs = 0;
+        if (hipMalloc((void **)&bt.side, (size_t)(w - 1) * slab_stride(idx) * sizeof(float)) == hipSuccess) {
+            bt.side_slabs = w - 1;
+        } else {
+            (void)hipGetLastError();
+            bt.side = nullptr;
+            w >>= 1;
+        }
+    }
+    *out_w = w < 1 ? 1 : w;
+    return SSW_OK;
+}
+
+// the chunk width to use for nq queries: limited by the shape, by nq and by what the side buffer could be grown to
+static ssw_status batch_width(ssw_index *idx, int32_t nq, int *out_w) {
+    int w = scan_batch_max_width(idx->n, idx->dim, idx->dtype);
+    if (w > BATCH_MAX_WIDTH) w = BATCH_MAX_WIDTH;
+    while (w > nq) w >>= 1;
+    return batch_buffers(idx, w, false, out_w);
+}
+
+// queries [w, dim] (host), w >= 2 -> one launch that fills chunk_slab(w, j) with the scores of query j
+static ssw_status do_scan_chunk(ssw_index *idx, const float *q_host, int w) {
+    BatchState &bt = idx->batch;
+    float *slab[BATCH_MAX_WIDTH];
+    for (int j = 0; j < w; ++j) slab[j] = chunk_slab(idx, w, j);
+    SSW_TRY(bt.qb_stage.push(bt.qb_dev, q_host, (size_t)w * idx->dim * sizeof(float), idx->stream));
+    idx->scores_partial = false;
+    return profiled(idx, [&] {
+        return launch_scan_batch(idx->X, idx->dtype, bt.qb_dev, slab, w, idx->n, idx->dim, idx->device, idx->stream);
+    });
+}
+
+static ssw_status check_query_batch(const ssw_index *idx, const float *q_host, int32_t nq) {
+    for (int32_t b = 0; b < nq; ++b) {
+        for (int i = 0; i < idx->dim; ++i) {
+            if (!std::isfinite(q_host[(size_t)b * idx->dim + i])) {
+                set_error("query %d of the batch has a non-finite component at %d", b, i);
+                return SSW_ERR_NUMERIC;
+            }
+        }
+    }
+    return SSW_OK;
+}
+
+extern "C" ssw_status ssw_index_scan_batch(ssw_index *idx, const float *q_host, int32_t nq, float *out_scores_host) {
+    SSW_REQUIRE(nq >= 1, "nq=%d < 1", nq);
+    SSW_REQUIRE(idx != nullptr && q_host != nullptr, "NULL argument");
+    SSW_TRY(check_query_batch(idx, q_host, nq));
+    if (nq == 1) return ssw_index_scan(idx, q_host, out_scores_host);
+    DeviceGuard guard(idx->device);
+    int W = 1;
+    SSW_TRY(batch_width(idx, nq, &W));
+    const size_t dim = (size_t)idx->dim, row_bytes = (size_t)idx->n * sizeof(float);
+    for (int32_t b = 0; b < nq;) {
+        int w = W;
+        while (w > nq - b) w >>= 1;
+        if (w >= 2) {
+            SSW_TRY(do_scan_chunk(idx, q_host + b * dim, w));
+        } else {
+            w = 1;
+            SSW_TRY(idx->q_stage.push(idx->q_dev, q_host + b * dim, dim * sizeof(float), idx->stream));
+            SSW_TRY(do_scan(idx, idx->q_dev));
+        }
+        if (out_scores_host && idx->n > 0) {
+            for (int j = 0; j < w; ++j)
+                SSW_HIP_TRY(hipMemcpyAsync(out_scores_host + (size_t)(b + j) * idx->n, chunk_slab(idx, w, j), row_bytes,
+                                           hipMemcpyDeviceToHost, idx->stream));
+        }
+        b += w;
+    }
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+    return SSW_OK;
+}
+
+// ---- the second stage of a batch (ssw_index_topk_batch_avg) -----------------------------------------------------------
+// the most rows of one image of the index (the aggregation sizes its LDS by it): computed once per image map
+static int64_t max_image_tiles(ssw_index *idx) {
+    if (idx->max_image_tiles < 0) {
+        int64_t m = 0;
+        for (size_t p = 0; p + 1 < idx->row_start_host.size(); ++p)
+            m = std::max(m, idx->row_start_host[p + 1] - idx->row_start_host[p]);
+        idx->max_image_tiles = m;
+    }
+    return idx->max_image_tiles;
+}
+
+static ssw_status ensure_avg_buffers(ssw_index *idx) {
+    BatchState &bt = idx->batch;
+    const size_t slots = (size_t)BATCH_MAX_WIDTH * SSW_MAX_TOPK;
+    if (!bt.avg_row) SSW_HIP_TRY(hipMalloc((void **)&bt.avg_row, slots * sizeof(int64_t)));
+    if (!bt.avg_score) SSW_HIP_TRY(hipMalloc((void **)&bt.avg_score, slots * sizeof(float)));
+    return SSW_OK;
+}
+
+// the aggregation of the images the selection that has just run on the stream left in the handle's result buffers,
+// over the tile scores in `scores`, into row j of the chunk's device arrays
+static ssw_status enqueue_avg_of_result(ssw_index *idx, const float *scores, int32_t k, int32_t aug, int j) {
+    BatchState &bt = idx->batch;
+    return launch_avg_score_keys(idx->tile_boxes, idx->tile_zoom, scores, idx->row_start, idx->n_images, idx->ws.out_keys,
+                                 idx->ws.out_count, k, (int32_t)idx->max_image_tiles, aug, bt.avg_score + (size_t)j * k,
+                                 bt.avg_row + (size_t)j * k, idx->stream);
+}
+
+// rows [0, w) of the chunk's device arrays -> the caller's rows [b, b + w): one copy each and ONE host wait
+static ssw_status collect_avg(ssw_index *idx, const AvgStage *avg, int32_t b, int w, int32_t k) {
+    BatchState &bt = idx->batch;
+    const size_t o = (size_t)b * k, m = (size_t)w * k;
+    SSW_HIP_TRY(hipMemcpyAsync(avg->out_scores + o, bt.avg_score, m * sizeof(float), hipMemcpyDeviceToHost, idx->stream));
+    SSW_HIP_TRY(hipMemcpyAsync(avg->out_rows + o, bt.avg_row, m * sizeof(int64_t), hipMemcpyDeviceToHost, idx->stream));
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+    return SSW_OK;
+}
+
+// ---- the batched top-k: one driver ----------------------------------------------------------------------------------
+// the exclusion lists of a batch: query b excludes images[offsets[b] .. offsets[b + 1]); no offsets: nobody excludes
+struct BatchExcluded {
+    const int64_t *images, *offsets;
+    const int64_t *of(int32_t b, int64_t *n_ex) const {
+        *n_ex = offsets ? offsets[b + 1] - offsets[b] : 0;
+        return *n_ex > 0 ? images + offsets[b] : nullptr;
+    }
+};
+
+static ssw_status check_excluded_offsets(const ssw_index *idx, const BatchExcluded &ex, int32_t nq) {
+    if (!ex.offsets) return SSW_OK;
+    SSW_REQUIRE(ex.offsets[0] >= 0, "excluded_offsets[0]=%lld < 0", (long long)ex.offsets[0]);
+    for (int32_t b = 0; b < nq; ++b)
+        SSW_REQUIRE(ex.offsets[b] <= ex.offsets[b + 1], "excluded_offsets decrease at query %d", b);
+    SSW_REQUIRE(ex.offsets[nq] == ex.offsets[0] || ex.images != nullptr, "excluded_images is NULL");
+    return check_excluded(idx, ex.images, ex.offsets[0], ex.offsets[nq]);
+}
+
+// The scores of a pruned chunk: ONE pass over the int8 shadow bounds its w queries [b, b + w), already in batch.qb_dev
+// (prune.hip, "Pruned batch"); per query a threshold selection and the survivors, one publish and ONE host wait for
+// the chunk, then exact rescoring of each query's survivors, or its full scan where the certificate failed.
+static ssw_status prune_scan_chunk(ssw_index *idx, const BatchExcluded &excl, int32_t b, int w, int32_t k) {
+    PruneState &p = idx->prune;
+    PruneBatchState &pb = idx->prune_batch;
+    int32_t m[Q8_MQ_WIDTH];
+    SSW_TRY(prune_bounds_mq(idx, w, nullptr, nullptr));
+    SSW_HIP_TRY(hipEventRecord(p.ev, idx->stream));
+    for (int j = 0; j < w; ++j) {  // threshold and survivors of each query, in stream order
+        int64_t n_ex = 0;
+        const int64_t *ex = excl.of(b + j, &n_ex);
+        SSW_TRY(install_excluded(idx, ex, n_ex, idx->stream));
+        SSW_TRY(do_select(idx, chunk_slab(idx, w, j), k, SelectDest{nullptr, 0u, false}, idx->stream));
+        SSW_TRY(prune_survivors_slot(idx, w, j, k, SURV_CAP));
+    }
+    SSW_TRY(prune_publish_mq(idx, w, SURV_CAP, p.ev, m));  // sleep through the shadow scan, spin on the rest
+    for (int j = 0; j < w; ++j) {
+        const float *qj = idx->batch.qb_dev + (size_t)j * idx->dim;
+        float *slab = chunk_slab(idx, w, j);
+        ++p.queries;
+        if (m[j] < 0) {
+            ++p.fallbacks;
+            SSW_TRY(launch_scan(idx->X, idx->dtype, qj, slab, idx->n, idx->dim, idx->device, idx->stream));
+        } else {
+            const int64_t *rows = pb.surv_rows + (int64_t)j * SURV_CAP;
+            float *vals = pb.surv_scores + (int64_t)j * SURV_CAP;
+            SSW_TRY(launch_score_rows(idx->X, idx->dtype, qj, rows, m[j], idx->dim, vals, idx->stream));
+            SSW_TRY(launch_scatter_scores(rows, vals, m[j], slab, idx->stream));
+        }
+    }
+    p.last = m[w - 1];
+    idx->scores_partial = m[w - 1] >= 0;  // the handle's buffer is the last query's slab
+    return SSW_OK;
+}
+
+// The three batched top-k entries.  `pruned`: a chunk's slabs get their scores from the certified pre-scan (if the index
+// is not eligible or its shadow is refused: from the plain scan, and the prune counters stay as they are).  With `avg`,
+// every query's selection is followed by the aggregation over its own slab; a pruned slab is exact on its survivors
+// only, so the two do not combine.
+static ssw_status topk_batch_run(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
+                                 const int64_t *excluded_offsets, int32_t k, int64_t *out_images, float *out_scores,
+                                 int64_t *out_best_rows, int32_t *out_counts, const AvgStage *avg, bool pruned) {
+    SSW_REQUIRE(nq >= 1, "nq=%d < 1", nq);
+    SSW_REQUIRE(idx != nullptr && q_host != nullptr && out_counts != nullptr, "NULL argument");
+    SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
+    SSW_REQUIRE(!(avg && pruned), "topk_batch: no second stage over pruned slabs");
+    const BatchExcluded excl{excluded_images, excluded_offsets};
+    SSW_TRY(check_excluded_offsets(idx, excl, nq));
+    SSW_TRY(check_query_batch(idx, q_host, nq));
+    for (int32_t b = 0; b < nq; ++b) out_counts[b] = 0;
+    DeviceGuard guard(idx->device);
+    int W = 1;
+    if (pruned) {
+        bool ready = false;
+        if (prune_batch_eligible(idx) && idx->ws.xchg.msg_out == nullptr) SSW_TRY(ensure_shadow(idx, &ready));
+        if (ready) SSW_TRY(batch_buffers(idx, std::min<int32_t>(nq, Q8_MQ_WIDTH), true, &W));
+        pruned = ready && idx->batch.qb_dev;
+    }
+    if (pruned) {
+        // (a partial buffer is not completed first: every chunk overwrites it and the kept query together)
+        SSW_TRY(ensure_ws(idx));
+        SSW_TRY(ensure_prune_batch(idx, W, &W));
+    } else if (nq == 1) {  // the single call itself, pruning included
+        int64_t n_ex = 0;
+        const int64_t *ex = excl.of(0, &n_ex);
+        SSW_TRY(ssw_index_topk(idx, q_host, ex, n_ex, k, out_images, out_scores, out_best_rows, out_counts));
+        if (!avg || idx->n_images == 0) return SSW_OK;
+        SSW_TRY(ensure_full_scores(idx));  // a pruned top-k left exact scores for its survivors only
+        SSW_TRY(ensure_avg_buffers(idx));
+        SSW_TRY(enqueue_avg_of_result(idx, idx->scores, k, avg->aug, 0));
+        return collect_avg(idx, avg, 0, 1, k);
+    } else {
+        SSW_TRY(ensure_full_scores(idx));
+        if (avg) SSW_TRY(ensure_avg_buffers(idx));
+        SSW_TRY(batch_width(idx, nq, &W));
+    }
+    const size_t dim = (size_t)idx->dim;
+    for (int32_t b = 0; b < nq;) {
+        const float *q = q_host + b * dim;
+        int w = W;
+        if (pruned) w = std::min<int32_t>(W, nq - b);  // the shadow scan takes any width,
+        else while (w > nq - b) w >>= 1;               // the row scan powers of two
+        if (pruned) {
+            SSW_TRY(idx->batch.qb_stage.push(idx->batch.qb_dev, q, (size_t)w * dim * sizeof(float), idx->stream));
+            SSW_TRY(profiled(idx, [&] { return prune_scan_chunk(idx, excl, b, w, k); }));
+        } else if (w >= 2) {
+            SSW_TRY(do_scan_chunk(idx, q, w));
+        } else {  // one query: the full single-query scan (never the pre-scan) into the handle's buffer
+            w = 1;
+            SSW_TRY(stage_query(idx, q));
+            SSW_TRY(do_scan(idx, idx->q_dev));
+        }
+        for (int j = 0; j < w; ++j) {
+            int64_t n_ex = 0;
+            const int64_t *ex = excl.of(b + j, &n_ex);
+            const size_t o = (size_t)(b + j) * k;
+            float *slab = chunk_slab(idx, w, j);
+            SSW_TRY(topk_enqueue(idx, nullptr, slab, idx->stream, ex, n_ex, k));
+            SSW_TRY(topk_collect(idx, slab, idx->stream, k, out_images ? out_images + o : nullptr,
+                                 out_scores ? out_scores + o : nullptr, out_best_rows ? out_best_rows + o : nullptr,
+                                 out_counts + b + j));
+            // after the collect: after a deep rerun too, and before the next query's selection takes the result buffers
+            if (avg) SSW_TRY(enqueue_avg_of_result(idx, slab, k, avg->aug, j));
+        }
+        if (avg) SSW_TRY(collect_avg(idx, avg, b, w, k));  // (before the next chunk's scan takes the slabs)
+        b += w;
+    }
+    return SSW_OK;
+}
+
+extern "C" {
+
+ssw_status ssw_index_topk_batch(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
+                                const int64_t *excluded_offsets, int32_t k, int64_t *out_images, float *out_scores,
+                                int64_t *out_best_rows, int32_t *out_counts) {
+    return topk_batch_run(idx, q_host, nq, excluded_images, excluded_offsets, k, out_images, out_scores, out_best_rows,
+                          out_counts, nullptr, false);
+}
+
+ssw_status ssw_index_topk_batch_pruned(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
+                                       const int64_t *excluded_offsets, int32_t k, int64_t *out_images,
+                                       float *out_scores, int64_t *out_best_rows, int32_t *out_counts) {
+    return topk_batch_run(idx, q_host, nq, excluded_images, excluded_offsets, k, out_images, out_scores, out_best_rows,
+                          out_counts, nullptr, true);
+}
+
+ssw_status ssw_index_topk_batch_avg(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
+                                    const int64_t *excluded_offsets, int32_t k, int32_t aug_larger, int64_t *out_images,
+                                    float *out_scores, int64_t *out_best_rows, float *out_avg_scores,
+                                    int64_t *out_avg_rows, int32_t *out_counts) {
+    SSW_REQUIRE(nq >= 1, "nq=%d < 1", nq);
+    SSW_REQUIRE(idx && q_host && out_counts && out_avg_scores && out_avg_rows, "NULL argument");
+    SSW_TRY(check_avg_args(idx, aug_larger, "topk_batch_avg"));
+    const int64_t max_tiles = max_image_tiles(idx);
+    SSW_REQUIRE(max_tiles <= SSW_RESCORE_MAX_TILES,
+                "the index has an image with %lld tiles, more than the %d the kernel keeps in LDS", (long long)max_tiles,
+                SSW_RESCORE_MAX_TILES);
+    const AvgStage avg{aug_larger, out_avg_scores, out_avg_rows};
+    return topk_batch_run(idx, q_host, nq, excluded_images, excluded_offsets, k, out_images, out_scores, out_best_rows,
+                          out_counts, &avg, false);
+}
+
+}  // extern "C"

@@ -1,0 +1,202 @@
+// index_handle.h -- the resident index's handle and the host helpers shared by the sources of its C-ABI: capi_index.hip,
+// index_topk.hip, index_prune.hip, index_batch.hip and, in the lab build, debug_hooks.hip.
+#pragma once
+#include "ssw_common.h"
+
+constexpr int BATCH_MAX_WIDTH = 16;                 // queries of one chunk of a batch (index_batch.hip)
+constexpr int64_t SURV_CAP = (int64_t)1 << 18;      // survivors rescored at most; more: the full scan
+constexpr int64_t SMALL_EXCL_CAP = 8192;            // the small form (index_topk.hip): excluded ids in its pinned block
+constexpr int64_t SMALL_ROWS = 65536;               // and the small scan kernel's range (scan.hip)
+
+// certified int8 pre-scan of the top-k (prune.hip): the shadow of the rows, built lazily by the first top-k with a query
+// after the rows last changed, and the buffers of one pruned call
+struct PruneState {
+    int8_t *q8 = nullptr;                          // [n, dim] codes
+    float *q8_scale = nullptr, *q8_err = nullptr;  // [n] s_r, a_r
+    bool stale = true;                             // the rows changed since the shadow was built
+    bool refused = false;                          // too little free memory at the last attempt (until the rows change)
+    unsigned *state = nullptr;                     // [4] device words (ssw_common.h, launch_q8_query)
+    int64_t *surv_rows = nullptr;                  // [SURV_CAP]
+    float *surv_scores = nullptr;                  // [SURV_CAP]
+    int32_t *host = nullptr;                       // pinned, mapped: [seq, survivors or -1]
+    unsigned seq = 0;
+    hipEvent_t ev = nullptr;                       // after the shadow scan: the host sleeps on it, then spins
+    float *q_last = nullptr;                       // [dim] the query of the last pruned scan
+    int64_t last = 0, queries = 0, fallbacks = 0;
+    void free_shadow() {
+        for (void *p : {(void *)q8, (void *)q8_scale, (void *)q8_err}) (void)hipFree(p);
+        q8 = nullptr;
+        q8_scale = q8_err = nullptr;
+        stale = true;
+    }
+    void release() {
+        free_shadow();
+        for (void *p : {(void *)state, (void *)surv_rows, (void *)surv_scores, (void *)q_last}) (void)hipFree(p);
+        if (host) (void)hipHostFree(host);
+        if (ev) (void)hipEventDestroy(ev);
+    }
+};
+
+// pruned batch (ssw_index_topk_batch_pruned): the per-query state, query codes and survivor lists of one chunk of up to
+// Q8_MQ_WIDTH queries; allocated by the first pruned batch
+struct PruneBatchState {
+    unsigned *mq = nullptr;        // [Q8_MQ_WIDTH][Q8_MQ_WORDS] (ssw_common.h)
+    int8_t *planes = nullptr;      // q8_mq_plane_bytes(dim)
+    int64_t *surv_rows = nullptr;  // [slots][SURV_CAP]
+    float *surv_scores = nullptr;  // [slots][SURV_CAP]
+    int slots = 0;
+    int32_t *host = nullptr;       // pinned, mapped: [seq, survivors or -1 of each slot]
+    unsigned seq = 0;
+    void release() {
+        for (void *p : {(void *)mq, (void *)planes, (void *)surv_rows, (void *)surv_scores}) (void)hipFree(p);
+        if (host) (void)hipHostFree(host);
+    }
+};
+
+// batched scan (ssw_index_scan_batch / ssw_index_topk_batch): the queries of one chunk, and the score slabs of all but
+// its last query (that one's slab is `scores`); allocated by the first batched call
+struct BatchState {
+    float *qb_dev = nullptr;  // [BATCH_MAX_WIDTH, dim]
+    ssw::PinnedStage qb_stage;
+    float *side = nullptr;    // [side_slabs, slab_stride]
+    int side_slabs = 0;
+    // second stage of a chunk (ssw_index_topk_batch_avg): [BATCH_MAX_WIDTH, SSW_MAX_TOPK] each
+    float *avg_score = nullptr;
+    int64_t *avg_row = nullptr;
+    void release() {
+        (void)hipFree(qb_dev);
+        (void)hipFree(side);
+        (void)hipFree(avg_score);
+        (void)hipFree(avg_row);
+        qb_stage.release();
+    }
+};
+
+struct ssw_index {
+    int device = 0;
+    int64_t n = 0;
+    int32_t dim = 0;
+    int64_t n_images = 0;
+    bool has_map = false;
+    int32_t dtype = SSW_DTYPE_F32;
+    float *X = nullptr;  // SSW_DTYPE_F16: binary16 rows in the lane-interleaved layout (ssw_common.h)
+    bool owns_X = false;
+    // f16 upload / download: bounded device staging of natural-order rows (f32 or binary16)
+    void *xfer = nullptr;
+    size_t xfer_bytes = 0;
+    float *scores = nullptr;      // [n]
+    float *q_dev = nullptr;       // [dim] device copy of a host query
+    ssw::PinnedStage q_stage;
+    int64_t *row_start = nullptr;  // [n_images + 1] when has_map
+    hipStream_t own_stream = nullptr;
+    hipStream_t stream = nullptr;
+    ssw::SelectWorkspace ws;
+    bool ws_ready = false;
+    // gather staging
+    int64_t *gather_idx = nullptr;
+    float *gather_out = nullptr;
+    int64_t gather_cap = 0;
+    ssw::PinnedStage rows_stage;
+    void *res_host = nullptr;  // pinned result mirror
+    // small index (one scan launch + one selection launch, no copies, no stream wait): pinned, device-visible block
+    // [query dim f32][excluded ids SMALL_EXCL_CAP i64][packed result], and the sequence number the host spins on
+    unsigned char *small_host = nullptr;
+    unsigned small_seq = 0;
+    unsigned res_pending_seq = 0;  // != 0: the selection in flight publishes into res_host under this sequence number
+    unsigned small_pending_seq = 0;  // the same for the small form, into small_host
+    float *q2_dev = nullptr;  // second query vector (score_rows)
+    ssw::PinnedStage q2_stage;
+    // tile geometry + staging of the avg_score aggregation (rescore.hip)
+    std::vector<int64_t> row_start_host;  // host mirror of row_start
+    int64_t max_image_tiles = -1;  // the most rows of one image; -1: not computed since the map was set
+    float *tile_boxes = nullptr;   // [n, 4] x1, y1, x2, y2
+    int32_t *tile_zoom = nullptr;  // [n]
+    int64_t *rs_pos = nullptr, *rs_off = nullptr, *rs_row = nullptr;  // [rs_cap]
+    float *rs_score = nullptr;     // [rs_cap]
+    float *rs_minus = nullptr;     // [rs_minus_cap]
+    int64_t rs_cap = 0, rs_minus_cap = 0;
+    PruneState prune;           // never for a borrowed matrix or once ssw_index_device_ptrs handed out the rows
+    bool rows_escaped = false;  // the row pointer was handed out: never a shadow
+    bool scores_partial = false;  // scores hold exact values for the survivors only (ensure_full_scores materialises)
+    BatchState batch;
+    PruneBatchState prune_batch;
+    // profiling of the scan kernel
+    bool profiling = false;
+    std::vector<hipEvent_t> ev;  // pairs
+    int ev_used = 0;
+};
+
+// the second stage of a batch (ssw_index_topk_batch_avg): the aggregation code and the host outputs [nq, k]
+struct AvgStage {
+    int32_t aug;
+    float *out_scores;
+    int64_t *out_rows;
+};
+
+#pragma GCC visibility push(hidden)  // shared between the library's own sources, not exported from it
+namespace ssw {
+
+inline ssw_status ensure_ws(ssw_index *idx) {
+    if (idx->ws_ready) return SSW_OK;
+    SSW_TRY(select_alloc(idx->ws, idx->n, idx->n_images, idx->has_map));
+    idx->ws_ready = true;
+    return SSW_OK;
+}
+
+inline unsigned next_seq(unsigned &counter) {  // sequence numbers are never 0 ("nothing in flight")
+    if (++counter == 0) ++counter;
+    return counter;
+}
+
+// one pair of profiling events around `work`, the scan or whatever replaces it; none when fewer than two are left
+template <class F>
+static ssw_status profiled(ssw_index *idx, F work) {
+    const bool prof = idx->profiling && idx->ev_used + 2 <= (int)idx->ev.size();
+    if (prof) SSW_HIP_TRY(hipEventRecord(idx->ev[idx->ev_used], idx->stream));
+    SSW_TRY(work());
+    if (prof) {
+        SSW_HIP_TRY(hipEventRecord(idx->ev[idx->ev_used + 1], idx->stream));
+        idx->ev_used += 2;
+    }
+    return SSW_OK;
+}
+
+// capi_index.hip
+ssw_status check_query(const ssw_index *idx, const float *q_host);
+ssw_status check_excluded(const ssw_index *idx, const int64_t *ids, int64_t first, int64_t last);
+ssw_status check_avg_args(const ssw_index *idx, int32_t aug_larger, const char *who);
+ssw_status launch_index_scan(ssw_index *idx, const float *q_dev, hipStream_t stream);
+ssw_status do_scan(ssw_index *idx, const float *q_dev);
+ssw_status ensure_full_scores(ssw_index *idx, hipStream_t stream);
+inline ssw_status ensure_full_scores(ssw_index *idx) { return ensure_full_scores(idx, idx->stream); }
+
+// index_topk.hip
+ssw_status stage_query(ssw_index *idx, const float *q_host);
+ssw_status do_select(ssw_index *idx, const float *scores, int32_t k, SelectDest dest, hipStream_t stream);
+ssw_status install_excluded(ssw_index *idx, const int64_t *excluded_images, int64_t n_excluded, hipStream_t stream);
+ssw_status topk_enqueue(ssw_index *idx, const float *q_host, const float *scores, hipStream_t stream,
+                        const int64_t *excluded_images, int64_t n_excluded, int32_t k);
+ssw_status topk_collect(ssw_index *idx, const float *scores, hipStream_t stream, int32_t k, int64_t *out_images,
+                        float *out_scores, int64_t *out_best_rows, int32_t *out_count);
+ssw_status wait_host_seq(hipStream_t stream, const unsigned *flag, unsigned seq);
+
+// index_prune.hip
+bool prune_eligible(const ssw_index *idx);
+bool prune_batch_eligible(const ssw_index *idx);
+ssw_status ensure_shadow(ssw_index *idx, bool *ready);
+ssw_status rows_changing(ssw_index *idx);
+ssw_status prune_bounds(ssw_index *idx, const float *q_dev);
+ssw_status prune_survivors(ssw_index *idx, int32_t k, int64_t cap, hipEvent_t sleep_ev_or_null, int32_t *out_m);
+ssw_status scan_for_topk(ssw_index *idx, const float *q_dev, int32_t k);
+ssw_status ensure_prune_batch(ssw_index *idx, int w, int *out_w);
+ssw_status prune_bounds_mq(ssw_index *idx, int w, int32_t *dbg_hi, int32_t *dbg_lo);
+ssw_status prune_survivors_slot(ssw_index *idx, int w, int j, int32_t k, int64_t cap);
+ssw_status prune_publish_mq(ssw_index *idx, int w, int64_t cap, hipEvent_t sleep_ev_or_null, int32_t *out_m);
+
+// index_batch.hip
+int64_t slab_stride(const ssw_index *idx);
+float *chunk_slab(ssw_index *idx, int w, int j);
+ssw_status batch_buffers(ssw_index *idx, int w, bool with_queries, int *out_w);
+
+}  // namespace ssw
+#pragma GCC visibility pop

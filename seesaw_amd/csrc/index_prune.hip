@@ -1,0 +1,258 @@
+// index_prune.hip -- the certified int8 pre-scan of the index's top-k: when it applies, the shadow of the rows, and the
+// steps of one pruned query and of one pruned chunk of a batch (kernels: prune.hip).  The handle: index_handle.h.
+#include "index_handle.h"
+
+using namespace ssw;
+
+// ---- the certified pre-scan (prune.hip) -------------------------------------------------------
+// Top-k with a query on an index of at least PRUNE_MIN_ROWS f32 rows, or PRUNE_MIN_ROWS_F16 f16 rows, scans the int8
+// shadow instead of the rows and rescores the survivors exactly; the score buffer then holds exact scores for the
+// survivors and lower bounds elsewhere (scores_partial) until a consumer that reads it materialises the full scan of
+// the kept query.
+constexpr int64_t PRUNE_MIN_ROWS = (int64_t)1 << 22;  // above the feedback loop's 1.56 M rows, below a rank's 12.5 M
+// f16 rows: the full scan reads half the bytes, yet the pruned call is ahead from the smallest size of the measured
+// sweep on (2^22 rows: 0.49 against 0.72 ms a call, profiles/prune_f16_sweep.txt), so the value is the f32 one.  Its
+// own constant: the two row formats are measured separately and need not stay equal.
+constexpr int64_t PRUNE_MIN_ROWS_F16 = (int64_t)1 << 22;
+// the pruned batch (ssw_index_topk_batch_pruned) against the plain batch at 16 queries: its own constant, chosen by its
+// own sweep ("Pruned batch")
+constexpr int64_t PRUNE_BATCH_MIN_ROWS = PRUNE_MIN_ROWS;
+constexpr int64_t PRUNE_RESERVE = (int64_t)4 << 30;   // free device memory the shadow must leave
+static SSW_TUNABLE bool g_prune = true;               // ssw_tune_prune
+static SSW_TUNABLE int64_t g_prune_min_rows = -1;      // >= 0: this many rows for both dtypes instead
+static SSW_TUNABLE int64_t g_prune_reserve = PRUNE_RESERVE;
+
+static bool prune_forced_off() {
+    static const bool v = getenv("SSW_TOPK_FULL_SCAN") != nullptr;  // A/B: every top-k runs the full f32 scan
+    return v;
+}
+
+static int64_t prune_min_rows(const ssw_index *idx) {
+    if (g_prune_min_rows >= 0) return g_prune_min_rows;
+    return idx->dtype == SSW_DTYPE_F16 ? PRUNE_MIN_ROWS_F16 : PRUNE_MIN_ROWS;
+}
+
+static bool prune_eligible_from(const ssw_index *idx, int64_t min_rows) {
+    return g_prune && !prune_forced_off() && idx->owns_X && !idx->rows_escaped && idx->n >= min_rows &&
+           idx->n_images > 0 && q8_dim_supported(idx->dim);
+}
+bool ssw::prune_eligible(const ssw_index *idx) { return prune_eligible_from(idx, prune_min_rows(idx)); }
+bool ssw::prune_batch_eligible(const ssw_index *idx) {
+    return prune_eligible_from(idx, g_prune_min_rows >= 0 ? g_prune_min_rows : PRUNE_BATCH_MIN_ROWS);
+}
+
+// the rows are about to change: the buffer keeps the scores of the rows it was computed from, the shadow goes stale
+ssw_status ssw::rows_changing(ssw_index *idx) {
+    SSW_TRY(ensure_full_scores(idx));
+    idx->prune.stale = true;
+    idx->prune.refused = false;
+    return SSW_OK;
+}
+
+// shadow of the rows for the pruned scan: (re)built when stale, if the device keeps PRUNE_RESERVE free beside it
+ssw_status ssw::ensure_shadow(ssw_index *idx, bool *ready) {
+    PruneState &p = idx->prune;
+    *ready = false;
+    if (p.q8 && !p.stale) {
+        *ready = true;
+        return SSW_OK;
+    }
+    if (p.refused) return SSW_OK;
+    if (!p.q8) {
+        const size_t codes = (size_t)idx->n * idx->dim, consts = (size_t)idx->n * sizeof(float);
+        size_t free_b = 0, total_b = 0;
+        SSW_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        const size_t need = codes + 2 * consts + (size_t)SURV_CAP * 12 + ((size_t)idx->dim + 64) * sizeof(float);
+        if (free_b < need || free_b - need < (size_t)g_prune_reserve) {
+            p.refused = true;
+            return SSW_OK;
+        }
+        if (hipMalloc((void **)&p.q8, codes) != hipSuccess || hipMalloc((void **)&p.q8_scale, consts) != hipSuccess ||
+            hipMalloc((void **)&p.q8_err, consts) != hipSuccess) {
+            (void)hipGetLastError();
+            p.free_shadow();
+            p.refused = true;
+            return SSW_OK;
+        }
+    }
+    if (!p.state) {
+        SSW_HIP_TRY(hipMalloc((void **)&p.state, 4 * sizeof(unsigned)));
+        SSW_HIP_TRY(hipMalloc((void **)&p.surv_rows, (size_t)SURV_CAP * sizeof(int64_t)));
+        SSW_HIP_TRY(hipMalloc((void **)&p.surv_scores, (size_t)SURV_CAP * sizeof(float)));
+        SSW_HIP_TRY(hipMalloc((void **)&p.q_last, (size_t)idx->dim * sizeof(float)));
+        SSW_HIP_TRY(hipHostMalloc((void **)&p.host, 16, hipHostMallocMapped | hipHostMallocCoherent));
+        memset(p.host, 0, 16);
+        SSW_HIP_TRY(hipEventCreateWithFlags(&p.ev, hipEventDisableTiming));
+    }
+    SSW_TRY(launch_q8_build(idx->X, idx->dtype, idx->n, idx->dim, p.q8, p.q8_scale, p.q8_err, idx->stream));
+    p.stale = false;
+    *ready = true;
+    return SSW_OK;
+}
+
+// The two steps of the pre-scan that the lab hooks (ssw_debug_prune_*) drive as well; the shadow is ready.
+// Lower bounds of the scores of q_dev into the buffer, which is partial from here on: a consumer rescans q_last.
+ssw_status ssw::prune_bounds(ssw_index *idx, const float *q_dev) {
+    PruneState &p = idx->prune;
+    SSW_TRY(launch_q8_query(q_dev, idx->dim, p.q_last, p.state, idx->stream));
+    SSW_TRY(launch_q8_bounds(p.q8, p.q8_scale, p.q8_err, p.q_last, p.state, idx->scores, idx->n, idx->dim, idx->device,
+                             idx->stream));
+    idx->scores_partial = true;
+    return SSW_OK;
+}
+
+// The rows that may still reach the k-th key of the last selection, at most cap of them -> *out_m = their published
+// count, -1 = run the full scan.  One host wait: a sleep on sleep_ev_or_null first, then a spin.
+ssw_status ssw::prune_survivors(ssw_index *idx, int32_t k, int64_t cap, hipEvent_t sleep_ev_or_null, int32_t *out_m) {
+    PruneState &p = idx->prune;
+    const unsigned seq = next_seq(p.seq);
+    int32_t *host_dev = nullptr;
+    SSW_HIP_TRY(hipHostGetDevicePointer((void **)&host_dev, p.host, 0));
+    SSW_TRY(launch_survivors(idx->scores, p.q8_err, idx->n, idx->ws.out_keys, idx->ws.out_count, k, p.state, p.surv_rows, cap,
+                             host_dev, seq, idx->device, idx->stream));
+    if (sleep_ev_or_null) SSW_HIP_TRY(hipEventSynchronize(sleep_ev_or_null));
+    SSW_TRY(wait_host_seq(idx->stream, reinterpret_cast<const unsigned *>(p.host), seq));
+    *out_m = __atomic_load_n(p.host + 1, __ATOMIC_ACQUIRE);
+    return SSW_OK;
+}
+
+// The score buffer for the selection of the top-k of query q_dev (exclusions installed): the full f32 scan, or on a
+// large index the certified pre-scan -- shadow scan (lower bounds), threshold selection over them that publishes
+// nothing, survivors, exact rescoring of the survivors.  One host wait for the survivor count; any failure of the
+// certificate (fewer than k keys or an overflow in the threshold selection, more survivors than SURV_CAP, a query
+// that cannot be bounded) runs the full scan instead.  The profiling events bracket the whole replacement.
+ssw_status ssw::scan_for_topk(ssw_index *idx, const float *q_dev, int32_t k) {
+    bool ready = false;
+    const bool k_ok = k >= 1 && k <= SSW_MAX_TOPK && (idx->ws.xchg.msg_out == nullptr || k <= idx->ws.xchg.k_max);
+    if (k_ok && prune_eligible(idx)) SSW_TRY(ensure_shadow(idx, &ready));
+    if (!ready) return do_scan(idx, q_dev);
+    SSW_TRY(ensure_ws(idx));
+    return profiled(idx, [&]() -> ssw_status {
+        PruneState &p = idx->prune;
+        SSW_TRY(prune_bounds(idx, q_dev));
+        SSW_HIP_TRY(hipEventRecord(p.ev, idx->stream));
+        // threshold: the ordinary selection over the lower bounds, with the exclusions, without a message or host result
+        SSW_TRY(do_select(idx, idx->scores, k, SelectDest{nullptr, 0u, false}, idx->stream));
+        int32_t m = -1;
+        SSW_TRY(prune_survivors(idx, k, SURV_CAP, p.ev, &m));  // sleep through the shadow scan, spin on the rest
+        p.last = m;
+        ++p.queries;
+        if (m < 0) {
+            ++p.fallbacks;
+            idx->scores_partial = false;
+            return launch_index_scan(idx, p.q_last, idx->stream);
+        }
+        SSW_TRY(launch_score_rows(idx->X, idx->dtype, p.q_last, p.surv_rows, m, idx->dim, p.surv_scores, idx->stream));
+        return launch_scatter_scores(p.surv_rows, p.surv_scores, m, idx->scores, idx->stream);
+    });
+}
+
+// ---- the pruned batch: ONE pass over the int8 shadow bounds a chunk of up to 16 queries (prune.hip, "Pruned batch") ----
+static_assert(BATCH_MAX_WIDTH == Q8_MQ_WIDTH, "a chunk of the pruned batch uses the batch's slabs");
+
+// the state of a chunk of w queries; the survivor lists may only be had for fewer slots: *out_w
+ssw_status ssw::ensure_prune_batch(ssw_index *idx, int w, int *out_w) {
+    PruneBatchState &pb = idx->prune_batch;
+    if (!pb.mq) {
+        SSW_HIP_TRY(hipMalloc((void **)&pb.mq, (size_t)Q8_MQ_WIDTH * Q8_MQ_WORDS * sizeof(unsigned)));
+        SSW_HIP_TRY(hipMemsetAsync(pb.mq, 0, (size_t)Q8_MQ_WIDTH * Q8_MQ_WORDS * sizeof(unsigned), idx->stream));
+        SSW_HIP_TRY(hipMalloc((void **)&pb.planes, q8_mq_plane_bytes(idx->dim)));
+        SSW_HIP_TRY(hipHostMalloc((void **)&pb.host, (1 + Q8_MQ_WIDTH) * sizeof(int32_t),
+                                  hipHostMallocMapped | hipHostMallocCoherent));
+        memset(pb.host, 0, (1 + Q8_MQ_WIDTH) * sizeof(int32_t));
+    }
+    while (pb.slots < w) {  // grow; on failure keep halving the width
+        SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+        (void)hipFree(pb.surv_rows);
+        (void)hipFree(pb.surv_scores);
+        pb.surv_rows = nullptr;
+        pb.surv_scores = nullptr;
+        pb.slots = 0;
+        if (hipMalloc((void **)&pb.surv_rows, (size_t)w * SURV_CAP * sizeof(int64_t)) == hipSuccess &&
+            hipMalloc((void **)&pb.surv_scores, (size_t)w * SURV_CAP * sizeof(float)) == hipSuccess) {
+            pb.slots = w;
+        } else {
+            (void)hipGetLastError();
+            (void)hipFree(pb.surv_rows);
+            pb.surv_rows = nullptr;
+            pb.surv_scores = nullptr;
+            if (w == 1) {
+                set_error("topk_batch_pruned: no memory for one survivor list");
+                return SSW_ERR_NOMEM;
+            }
+            w >>= 1;
+        }
+    }
+    *out_w = w;
+    return SSW_OK;
+}
+
+// The two device steps of a chunk that the lab hook drives as well; the shadow and the chunk's buffers are ready and
+// the w queries are in batch.qb_dev.  Lower bounds of query j into slab j; the handle's buffer (the last query's slab)
+// is partial from here on and q_last is the last query.
+ssw_status ssw::prune_bounds_mq(ssw_index *idx, int w, int32_t *dbg_hi, int32_t *dbg_lo) {
+    PruneState &p = idx->prune;
+    PruneBatchState &pb = idx->prune_batch;
+    SSW_TRY(launch_q8_query_mq(idx->batch.qb_dev, idx->dim, w, pb.mq, pb.planes, p.q_last, idx->stream));
+    SSW_TRY(launch_q8_bounds_mq(p.q8, p.q8_scale, p.q8_err, pb.planes, pb.mq, w, idx->batch.side, slab_stride(idx),
+                                idx->scores, idx->n, idx->dim, dbg_hi, dbg_lo, idx->device, idx->stream));
+    idx->scores_partial = true;
+    return SSW_OK;
+}
+
+// the survivors of slot j against the keys the last selection left, into the slot's list (no publish)
+ssw_status ssw::prune_survivors_slot(ssw_index *idx, int w, int j, int32_t k, int64_t cap) {
+    PruneState &p = idx->prune;
+    PruneBatchState &pb = idx->prune_batch;
+    return launch_survivors_mq(chunk_slab(idx, w, j), p.q8_err, p.q8_scale, idx->n, idx->dim, idx->ws.out_keys,
+                               idx->ws.out_count, k, pb.mq + j * Q8_MQ_WORDS, pb.surv_rows + (int64_t)j * SURV_CAP, cap,
+                               idx->device, idx->stream);
+}
+
+// every slot's count (or -1) of the chunk -> out_m[w]; ONE host wait: a sleep on sleep_ev_or_null first, then a spin
+ssw_status ssw::prune_publish_mq(ssw_index *idx, int w, int64_t cap, hipEvent_t sleep_ev_or_null, int32_t *out_m) {
+    PruneBatchState &pb = idx->prune_batch;
+    const unsigned seq = next_seq(pb.seq);
+    int32_t *host_dev = nullptr;
+    SSW_HIP_TRY(hipHostGetDevicePointer((void **)&host_dev, pb.host, 0));
+    SSW_TRY(launch_prune_publish_mq(pb.mq, w, cap, host_dev, seq, idx->stream));
+    if (sleep_ev_or_null) SSW_HIP_TRY(hipEventSynchronize(sleep_ev_or_null));
+    SSW_TRY(wait_host_seq(idx->stream, reinterpret_cast<const unsigned *>(pb.host), seq));
+    for (int j = 0; j < w; ++j) out_m[j] = __atomic_load_n(pb.host + 1 + j, __ATOMIC_ACQUIRE);
+    return SSW_OK;
+}
+
+extern "C" {
+
+ssw_status ssw_index_prune_stats(ssw_index *idx, int64_t *out6) {
+    SSW_REQUIRE(idx != nullptr && out6 != nullptr, "NULL argument");
+    const PruneState &p = idx->prune;
+    out6[0] = p.q8 ? (p.stale ? 2 : 1) : (p.refused ? 3 : 0);
+    out6[1] = prune_eligible(idx) ? 1 : 0;
+    out6[2] = p.last;
+    out6[3] = p.queries;
+    out6[4] = p.fallbacks;
+    out6[5] = p.q8 ? idx->n * (idx->dim + 8) : 0;
+    return SSW_OK;
+}
+
+#ifdef SSW_DEBUG_HOOKS
+ssw_status ssw_tune_prune(int32_t enable, int64_t min_rows, int64_t reserve_bytes) {
+    g_prune = enable != 0;
+    g_prune_min_rows = min_rows < 0 ? -1 : min_rows;  // < 0: PRUNE_MIN_ROWS / PRUNE_MIN_ROWS_F16 again
+    g_prune_reserve = reserve_bytes < 0 ? PRUNE_RESERVE : reserve_bytes;
+    return SSW_OK;
+}
+
+ssw_status ssw_tune_prune_scan(int32_t blocks_per_cu, int32_t group_loads) {
+    tune_q8_bounds(blocks_per_cu, group_loads);
+    return SSW_OK;
+}
+
+ssw_status ssw_tune_prune_scan_mq(int32_t blocks_per_cu, int32_t tiles) {
+    tune_q8_bounds_mq(blocks_per_cu, tiles);
+    return SSW_OK;
+}
+#endif
+
+}  // extern "C"

@@ -121,7 +121,7 @@ struct PinnedStage {
 
 // ---- launchers implemented in the kernel translation units -----------------
 
-// capi_index.hip: the two halves of ssw_index_topk(q = NULL) on a stream of the caller's (ssw_labelprop_round), which
+// index_topk.hip: the two halves of ssw_index_topk(q = NULL) on a stream of the caller's (ssw_labelprop_round), which
 // has made sure that the handle's own stream is idle (ssw_index_sync) and holds a DeviceGuard on the index's device
 // (neither half sets the device itself)
 ssw_status index_enqueue_topk_resident(ssw_index *idx, hipStream_t on_stream, const int64_t *excluded_images, int64_t n_excluded,
@@ -129,8 +129,8 @@ ssw_status index_enqueue_topk_resident(ssw_index *idx, hipStream_t on_stream, co
 ssw_status index_collect_topk(ssw_index *idx, hipStream_t on_stream, int32_t k, int64_t *out_images, float *out_scores,
                               int64_t *out_best_rows, int32_t *out_count);
 int index_device(const ssw_index *idx);
-// element type of the resident matrix (SSW_DTYPE_*), its device pointer and shape, for the entries outside
-// capi_index.hip that read it through a handle (feedback gathers; k-NN and X'LX refuse an f16 matrix)
+// element type of the resident matrix (SSW_DTYPE_*), its device pointer and shape, for the entries that read it through
+// a handle without index_handle.h (feedback gathers; k-NN and X'LX refuse an f16 matrix)
 int32_t index_dtype(const ssw_index *idx);
 const void *index_matrix(const ssw_index *idx, int64_t *n_rows, int32_t *dim);
 

@@ -8,6 +8,7 @@ k_prune_publish_mq) on the lab build.
 4. Results equal single full-scan top-k calls of a fresh handle, bit for bit.
 5. The handle's state after the call.
 6. One case at the product's default threshold (2^22 f16 rows).
+7. A bad argument is refused with the plain batch's error before a shadow is built.
 
 A non-finite query is SSW_ERR_NUMERIC for this entry point as for ssw_index_topk and ssw_index_topk_batch (there is no
 single-call result it could equal); that the kernel flags one is checked through the hook."""
@@ -333,3 +334,50 @@ def test_default_threshold_f16(lab_build):
         assert st[0] == 1 and st[3] == 16 and st[4] == 0 and 100 <= st[2] < (1 << 18), st
     finally:
         idx.close()
+
+
+def test_invalid_arguments_are_refused_before_the_shadow(lab_build):
+    """a pruned batch with a bad argument returns the plain batch's error and allocates and launches nothing: no shadow
+    is built for it and no query is counted; the valid call after it builds the shadow and equals the single calls"""
+    from seesaw_amd import _lib
+    from seesaw_amd.device_index import DeviceIndex, _ptr
+    n, dim, k, nq = 1000, 256, 10, 3
+    rows = np.random.default_rng(11).standard_normal((n, dim)).astype(np.float32)
+    r2i = (np.arange(n) // 4).astype(np.int32)
+    mode(lab_build, True, 1)
+    idx = DeviceIndex.from_numpy(rows, row2image=r2i)
+    try:
+        Q = batch_queries(nq, dim=dim, seed=2)
+        bad_q = Q.copy()
+        bad_q[1, 5] = np.nan
+        ids = np.arange(6, dtype=np.int64)
+        down = np.array([0, 4, 2, 6], dtype=np.int64)
+        out = [np.empty((nq, k), np.int64), np.empty((nq, k), np.float32), np.empty((nq, k), np.int64), np.zeros(nq, np.int32)]
+
+        def raw(name):  # decreasing offsets: DeviceIndex.topk_batch cannot express them
+            _lib.call(name, idx._h, _ptr(Q), nq, _ptr(ids), _ptr(down), k, *[_ptr(a) for a in out])
+
+        cases = [(_lib.SSW_ERR_NUMERIC, "query 1 of the batch has a non-finite component at 5",
+                  lambda prune: idx.topk_batch(bad_q, k, prune=prune)),
+                 (_lib.SSW_ERR_INVALID, "excluded_offsets decrease at query 1",
+                  lambda prune: raw("ssw_index_topk_batch_pruned" if prune else "ssw_index_topk_batch")),
+                 (_lib.SSW_ERR_INVALID, r"excluded image 250 outside \[0, 250\)",
+                  lambda prune: idx.topk_batch(Q, k, excluded=[None, [3], [7, idx.n_images]], prune=prune))]
+        for status, message, call in cases:
+            with pytest.raises(_lib.SeesawHipError, match=message) as plain:
+                call(False)
+            with pytest.raises(_lib.SeesawHipError, match=message) as pruned:
+                call(True)
+            assert pruned.value.status == plain.value.status == status
+            assert str(pruned.value) == str(plain.value)
+            st = idx.prune_stats()
+            assert st["shadow"] == "none" and st["queries"] == 0, (message, st)
+        ex = [None, [3], [7, 9]]
+        got = idx.topk_batch(Q, k, excluded=ex, prune=True)
+        st = idx.prune_stats()
+        assert st["shadow"] == "current" and st["queries"] == nq, st
+        for b in range(nq):
+            same(idx.topk(Q[b], k, excluded=ex[b]), got[b])
+    finally:
+        idx.close()
+        mode(lab_build, True)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Host-to-host time of one top-k call on a small index (1 000 images x 13 rows x 512: the one-launch form of
-csrc/capi_index.hip), call by call.
+csrc/index_topk.hip), call by call.
 
     python tools/perf_topk_small.py [--calls 5000] [--k 50]
 

@@ -4,9 +4,10 @@
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/trace_topk_paths.py
 
 Host top-k with the full scan and pruned, the one-launch top-k of a small index, the device form with an exchange
-target, a batch of 5 (a chunk of 4 and a single query), score_rows and rescore_avg, on the lab build (the pruning is
-forced on at this size).  Two builds launch the same kernels when their *_kernel_stats.csv agree in names and calls
-(profiles/topk_paths_kernel_stats_*.txt: tools/trace_topk_paths.py --summary OUT/.../*_kernel_stats.csv)."""
+target, a batch of 5 (a chunk of 4 and a single query) plain, pruned and with the second stage, score_rows and
+rescore_avg, on the lab build (the pruning is forced on at this size).  Two builds launch the same kernels when their
+*_kernel_stats.csv agree in names and calls (profiles/topk_paths_kernel_stats_*.txt and index_split_kernel_stats_*.txt:
+tools/trace_topk_paths.py --summary OUT/.../*_kernel_stats.csv)."""
 import csv
 import os
 import sys
@@ -53,6 +54,8 @@ def main():
         idx.sync()
         _lib.call("ssw_index_set_exchange_target", idx._h, None, 0, 0, 0, 0)
         idx.topk_batch(Q[:5], k, excluded=[[1], None, [2, 3], None, [5]])
+        idx.topk_batch(Q[:5], k, excluded=[[1], None, [2, 3], None, [5]], prune=True)
+        idx.topk_batch_avg(Q[:5], k, "greater")
         idx.score_rows(Q[5], np.arange(0, n, 101))
         idx.rescore_avg(np.arange(0, n_images, 301), "greater")
         _lib.call("ssw_tune_prune", 1, -1, -1)
