@@ -169,6 +169,11 @@ _DEBUG_SIGNATURES = {
     "ssw_debug_prune_bounds": (c_i32, [c_void_p, c_void_p, c_void_p, c_f32_p, c_i32_p]),
     "ssw_debug_prune_survivors": (c_i32, [c_void_p, ctypes.c_float, c_i32, c_i32, c_i32, c_i64, c_i32_p, c_i64_p,
                                           c_void_p]),
+    "ssw_tune_prune6": (c_i32, [c_i32, c_i64]),
+    "ssw_tune_prune6_scan": (c_i32, [c_i32, c_i32]),
+    "ssw_debug_prune6_scan_shape": (c_i32, [c_void_p, c_i32_p, c_i32_p]),
+    "ssw_debug_prune6_shadow": (c_i32, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p]),
+    "ssw_debug_prune6_bounds": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ssw_tune_gemm": (c_i32, [c_i32]),
     "ssw_debug_gemm": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_void_p, c_void_p]),
     "ssw_debug_gemm_pw4_mode": (c_i32, [c_i32, c_void_p]),

@@ -517,4 +517,113 @@ ssw_status ssw_debug_prune_survivors_mq(ssw_index *idx, int32_t nq, int32_t slot
     return SSW_OK;
 }
 
+// ---- the packed 6-bit shadow of single queries (prune.hip, "6-bit shadow"; tests/test_prune6_gpu.py) ----------------
+static ssw_status require_shadow6(ssw_index *idx, const char *who) {
+    SSW_REQUIRE(prune6_eligible(idx), "the index takes no 6-bit shadow (ssw_tune_prune6, f32, dim, borrowed or escaped rows)");
+    bool ready = false;
+    SSW_TRY(ensure_shadow6(idx, &ready));
+    if (!ready) {
+        set_error("%s: the shadow was refused for memory", who);
+        return SSW_ERR_NOMEM;
+    }
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_prune6_shadow(ssw_index *idx, int64_t first_row, int64_t n_rows, int8_t *out_codes, float *out_scale,
+                                   float *out_err) {
+    SSW_REQUIRE(idx != nullptr, "idx is NULL");
+    SSW_REQUIRE(first_row >= 0 && n_rows >= 0 && first_row + n_rows <= idx->n, "rows [%lld, +%lld) outside [0, %lld)",
+                (long long)first_row, (long long)n_rows, (long long)idx->n);
+    DeviceGuard guard(idx->device);
+    SSW_TRY(require_shadow6(idx, "prune6_shadow"));
+    if (n_rows == 0) return SSW_OK;
+    const PruneState &p = idx->prune;
+    const int dim = idx->dim;
+    const size_t tile_bytes = (size_t)16 * dim * 3 / 4;
+    const int64_t tile0 = first_row >> 4, tile1 = (first_row + n_rows - 1) >> 4;
+    std::vector<unsigned char> packed(out_codes ? (size_t)(tile1 - tile0 + 1) * tile_bytes : 0);
+    if (out_codes)
+        SSW_HIP_TRY(hipMemcpyAsync(packed.data(), p.q6 + (size_t)tile0 * tile_bytes, packed.size(), hipMemcpyDeviceToHost,
+                                   idx->stream));
+    if (out_scale)
+        SSW_HIP_TRY(hipMemcpyAsync(out_scale, p.q6_scale + first_row, (size_t)n_rows * sizeof(float), hipMemcpyDeviceToHost,
+                                   idx->stream));
+    if (out_err)
+        SSW_HIP_TRY(hipMemcpyAsync(out_err, p.q6_err + first_row, (size_t)n_rows * sizeof(float), hipMemcpyDeviceToHost,
+                                   idx->stream));
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+    if (!out_codes) return SSW_OK;
+    for (int64_t r = first_row; r < first_row + n_rows; ++r) {
+        const unsigned char *tile = packed.data() + (size_t)((r >> 4) - tile0) * tile_bytes;
+        for (int i = 0; i < dim; ++i) {
+            int u, g, j;
+            q6_slot(i, &u, &g, &j);
+            const int lane = 16 * g + (int)(r & 15);
+            int c;
+            if (j < 12) {
+                c = (int8_t)tile[q6_word_offset(lane, 3 * u + j / 4) + (size_t)(j % 4)] >> 2;  // arithmetic: sign kept
+            } else {
+                unsigned bits = 0u;
+                for (int part = 0; part < 3; ++part)
+                    bits = (bits << 2) | (tile[q6_word_offset(lane, 3 * u + part) + (size_t)(j - 12)] & 3u);
+                c = (int)(bits ^ 32u) - 32;  // six bits, two's complement
+            }
+            out_codes[(size_t)(r - first_row) * dim + i] = (int8_t)c;
+        }
+    }
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_prune6_bounds(ssw_index *idx, const float *q_host, int64_t *out_I, float *out_lb, float *out_Qe,
+                                   int8_t *out_codes) {
+    SSW_REQUIRE(idx != nullptr && q_host != nullptr, "NULL argument");
+    DeviceGuard guard(idx->device);
+    SSW_TRY(require_shadow6(idx, "prune6_bounds"));
+    PruneState &p = idx->prune;
+    const size_t dim = (size_t)idx->dim;
+    int64_t *dbg = nullptr;
+    if (out_I) SSW_HIP_TRY(hipMalloc((void **)&dbg, (size_t)idx->n * sizeof(int64_t)));
+    unsigned st[Q8_MQ_WORDS] = {};
+    std::vector<int8_t> planes(q6_plane_bytes(idx->dim));
+    auto run = [&]() -> ssw_status {
+        SSW_TRY(idx->q_stage.push(idx->q_dev, q_host, dim * sizeof(float), idx->stream));
+        SSW_TRY(prune6_bounds(idx, idx->q_dev, dbg));  // as in scan_for_topk: readers complete the buffer with q_last
+        if (out_I) SSW_HIP_TRY(hipMemcpyAsync(out_I, dbg, (size_t)idx->n * sizeof(int64_t), hipMemcpyDeviceToHost, idx->stream));
+        if (out_lb)
+            SSW_HIP_TRY(hipMemcpyAsync(out_lb, idx->scores, (size_t)idx->n * sizeof(float), hipMemcpyDeviceToHost, idx->stream));
+        SSW_HIP_TRY(hipMemcpyAsync(st, p.state6, sizeof(st), hipMemcpyDeviceToHost, idx->stream));
+        SSW_HIP_TRY(hipMemcpyAsync(planes.data(), p.planes6, planes.size(), hipMemcpyDeviceToHost, idx->stream));
+        SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+        return SSW_OK;
+    };
+    const ssw_status rc = run();
+    if (rc != SSW_OK) (void)hipStreamSynchronize(idx->stream);
+    (void)hipFree(dbg);
+    SSW_TRY(rc);
+    if (out_Qe) {
+        memcpy(out_Qe, &st[1], 4);      // Q
+        memcpy(out_Qe + 1, &st[3], 4);  // e
+        memcpy(out_Qe + 2, &st[4], 4);  // t2
+        out_Qe[3] = (float)st[2];       // 1 = the query cannot be bounded
+    }
+    if (out_codes)  // the operand's columns 0 (hi) and 1 (lo) back to natural element order
+        for (int pl = 0; pl < 2; ++pl)
+            for (size_t i = 0; i < dim; ++i) {
+                int u, g, j;
+                q6_slot((int)i, &u, &g, &j);
+                out_codes[(size_t)pl * dim + i] = planes[(size_t)(u * 64 + g * 16 + pl) * 16 + (size_t)j];
+            }
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_prune6_scan_shape(ssw_index *idx, int32_t *out_blocks, int32_t *out_tiles) {
+    SSW_REQUIRE(idx != nullptr && out_blocks != nullptr && out_tiles != nullptr, "NULL argument");
+    SSW_REQUIRE(q8_dim_supported(idx->dim), "dim=%d has no shadow scan", idx->dim);
+    int blocks = 0, tiles = 0;
+    q6_bounds_shape(idx->dim, idx->device, idx->n, &blocks, &tiles);
+    *out_blocks = blocks;
+    *out_tiles = tiles;
+    return SSW_OK;
+}
+
 }  // extern "C"

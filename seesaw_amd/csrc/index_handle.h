@@ -23,15 +23,27 @@ struct PruneState {
     hipEvent_t ev = nullptr;                       // after the shadow scan: the host sleeps on it, then spins
     float *q_last = nullptr;                       // [dim] the query of the last pruned scan
     int64_t last = 0, queries = 0, fallbacks = 0;
+    // the packed 6-bit shadow of f32 rows (prune.hip, "6-bit shadow"): what single queries scan on an index of at
+    // least PRUNE6_MIN_ROWS rows, instead of the int8 one; built lazily like it, with its own stale / refused
+    unsigned char *q6 = nullptr;                   // q6_code_bytes(n, dim): tiles of 16 rows
+    float *q6_scale = nullptr, *q6_err = nullptr;  // [q6_padded_rows(n)] s6_r, a6_r
+    bool stale6 = true, refused6 = false;
+    unsigned *state6 = nullptr;                    // [Q8_MQ_WORDS] the query's words, a slot's of the chunk
+    int8_t *planes6 = nullptr;                     // q6_plane_bytes(dim): the query's operand
     void free_shadow() {
-        for (void *p : {(void *)q8, (void *)q8_scale, (void *)q8_err}) (void)hipFree(p);
+        for (void *p : {(void *)q8, (void *)q8_scale, (void *)q8_err, (void *)q6, (void *)q6_scale, (void *)q6_err})
+            (void)hipFree(p);
         q8 = nullptr;
         q8_scale = q8_err = nullptr;
         stale = true;
+        q6 = nullptr;
+        q6_scale = q6_err = nullptr;
+        stale6 = true;
     }
     void release() {
         free_shadow();
-        for (void *p : {(void *)state, (void *)surv_rows, (void *)surv_scores, (void *)q_last}) (void)hipFree(p);
+        for (void *p : {(void *)state, (void *)surv_rows, (void *)surv_scores, (void *)q_last, (void *)state6, (void *)planes6})
+            (void)hipFree(p);
         if (host) (void)hipHostFree(host);
         if (ev) (void)hipEventDestroy(ev);
     }
@@ -183,7 +195,10 @@ ssw_status wait_host_seq(hipStream_t stream, const unsigned *flag, unsigned seq)
 // index_prune.hip
 bool prune_eligible(const ssw_index *idx);
 bool prune_batch_eligible(const ssw_index *idx);
+bool prune6_eligible(const ssw_index *idx);
 ssw_status ensure_shadow(ssw_index *idx, bool *ready);
+ssw_status ensure_shadow6(ssw_index *idx, bool *ready);
+ssw_status prune6_bounds(ssw_index *idx, const float *q_dev, int64_t *dbg_I);
 ssw_status rows_changing(ssw_index *idx);
 ssw_status prune_bounds(ssw_index *idx, const float *q_dev);
 ssw_status prune_survivors(ssw_index *idx, int32_t k, int64_t cap, hipEvent_t sleep_ev_or_null, int32_t *out_m);

@@ -1,5 +1,6 @@
-// index_prune.hip -- the certified int8 pre-scan of the index's top-k: when it applies, the shadow of the rows, and the
-// steps of one pruned query and of one pruned chunk of a batch (kernels: prune.hip).  The handle: index_handle.h.
+// index_prune.hip -- the certified pre-scan of the index's top-k: when it applies, the int8 and the packed 6-bit shadow of
+// the rows, and the steps of one pruned query and of one pruned chunk of a batch (kernels: prune.hip).  The handle:
+// index_handle.h.
 #include "index_handle.h"
 
 using namespace ssw;
@@ -17,8 +18,15 @@ constexpr int64_t PRUNE_MIN_ROWS_F16 = (int64_t)1 << 22;
 // the pruned batch (ssw_index_topk_batch_pruned) against the plain batch at 16 queries: its own constant, chosen by its
 // own sweep ("Pruned batch")
 constexpr int64_t PRUNE_BATCH_MIN_ROWS = PRUNE_MIN_ROWS;
+// Single queries on an f32 index of at least this many rows scan the packed 6-bit shadow (392 instead of 520 bytes a
+// row at dim 512, more survivors) and never need the int8 one.  The value follows from tools/perf_prune.py --three-way
+// ("6-bit shadow"): the smallest size from which the 6-bit call beats the int8 call, there and at
+// every larger size, by more than both spreads.
+constexpr int64_t PRUNE6_MIN_ROWS = (int64_t)1 << 24;
 constexpr int64_t PRUNE_RESERVE = (int64_t)4 << 30;   // free device memory the shadow must leave
 static SSW_TUNABLE bool g_prune = true;               // ssw_tune_prune
+static SSW_TUNABLE bool g_prune6 = true;              // ssw_tune_prune6
+static SSW_TUNABLE int64_t g_prune6_min_rows = -1;     // >= 0: this many rows instead of PRUNE6_MIN_ROWS
 static SSW_TUNABLE int64_t g_prune_min_rows = -1;      // >= 0: this many rows for both dtypes instead
 static SSW_TUNABLE int64_t g_prune_reserve = PRUNE_RESERVE;
 
@@ -40,12 +48,43 @@ bool ssw::prune_eligible(const ssw_index *idx) { return prune_eligible_from(idx,
 bool ssw::prune_batch_eligible(const ssw_index *idx) {
     return prune_eligible_from(idx, g_prune_min_rows >= 0 ? g_prune_min_rows : PRUNE_BATCH_MIN_ROWS);
 }
+bool ssw::prune6_eligible(const ssw_index *idx) {
+    return g_prune6 && idx->dtype == SSW_DTYPE_F32 &&
+           prune_eligible_from(idx, g_prune6_min_rows >= 0 ? g_prune6_min_rows : PRUNE6_MIN_ROWS);
+}
 
 // the rows are about to change: the buffer keeps the scores of the rows it was computed from, the shadow goes stale
 ssw_status ssw::rows_changing(ssw_index *idx) {
     SSW_TRY(ensure_full_scores(idx));
     idx->prune.stale = true;
     idx->prune.refused = false;
+    idx->prune.stale6 = true;
+    idx->prune.refused6 = false;
+    return SSW_OK;
+}
+
+// the buffers of one pruned call, whichever shadow it scans
+static ssw_status ensure_call_buffers(ssw_index *idx) {
+    PruneState &p = idx->prune;
+    // each under its own test: a call that failed part-way is completed by the next one
+    if (!p.state) SSW_HIP_TRY(hipMalloc((void **)&p.state, 4 * sizeof(unsigned)));
+    if (!p.surv_rows) SSW_HIP_TRY(hipMalloc((void **)&p.surv_rows, (size_t)SURV_CAP * sizeof(int64_t)));
+    if (!p.surv_scores) SSW_HIP_TRY(hipMalloc((void **)&p.surv_scores, (size_t)SURV_CAP * sizeof(float)));
+    if (!p.q_last) SSW_HIP_TRY(hipMalloc((void **)&p.q_last, (size_t)idx->dim * sizeof(float)));
+    if (!p.host) {
+        SSW_HIP_TRY(hipHostMalloc((void **)&p.host, 16, hipHostMallocMapped | hipHostMallocCoherent));
+        memset(p.host, 0, 16);
+    }
+    if (!p.ev) SSW_HIP_TRY(hipEventCreateWithFlags(&p.ev, hipEventDisableTiming));
+    return SSW_OK;
+}
+
+// does a shadow of `bytes` leave the reserve free, beside the buffers of a call?
+static ssw_status shadow_fits(const ssw_index *idx, size_t bytes, bool *fits) {
+    size_t free_b = 0, total_b = 0;
+    SSW_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    const size_t need = bytes + (size_t)SURV_CAP * 12 + ((size_t)idx->dim + 64) * sizeof(float);
+    *fits = free_b >= need && free_b - need >= (size_t)g_prune_reserve;
     return SSW_OK;
 }
 
@@ -60,32 +99,65 @@ ssw_status ssw::ensure_shadow(ssw_index *idx, bool *ready) {
     if (p.refused) return SSW_OK;
     if (!p.q8) {
         const size_t codes = (size_t)idx->n * idx->dim, consts = (size_t)idx->n * sizeof(float);
-        size_t free_b = 0, total_b = 0;
-        SSW_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-        const size_t need = codes + 2 * consts + (size_t)SURV_CAP * 12 + ((size_t)idx->dim + 64) * sizeof(float);
-        if (free_b < need || free_b - need < (size_t)g_prune_reserve) {
+        bool fits = false;
+        SSW_TRY(shadow_fits(idx, codes + 2 * consts, &fits));
+        if (!fits) {
             p.refused = true;
             return SSW_OK;
         }
         if (hipMalloc((void **)&p.q8, codes) != hipSuccess || hipMalloc((void **)&p.q8_scale, consts) != hipSuccess ||
             hipMalloc((void **)&p.q8_err, consts) != hipSuccess) {
             (void)hipGetLastError();
-            p.free_shadow();
+            for (void *b : {(void *)p.q8, (void *)p.q8_scale, (void *)p.q8_err}) (void)hipFree(b);
+            p.q8 = nullptr;
+            p.q8_scale = p.q8_err = nullptr;
             p.refused = true;
             return SSW_OK;
         }
     }
-    if (!p.state) {
-        SSW_HIP_TRY(hipMalloc((void **)&p.state, 4 * sizeof(unsigned)));
-        SSW_HIP_TRY(hipMalloc((void **)&p.surv_rows, (size_t)SURV_CAP * sizeof(int64_t)));
-        SSW_HIP_TRY(hipMalloc((void **)&p.surv_scores, (size_t)SURV_CAP * sizeof(float)));
-        SSW_HIP_TRY(hipMalloc((void **)&p.q_last, (size_t)idx->dim * sizeof(float)));
-        SSW_HIP_TRY(hipHostMalloc((void **)&p.host, 16, hipHostMallocMapped | hipHostMallocCoherent));
-        memset(p.host, 0, 16);
-        SSW_HIP_TRY(hipEventCreateWithFlags(&p.ev, hipEventDisableTiming));
-    }
+    SSW_TRY(ensure_call_buffers(idx));
     SSW_TRY(launch_q8_build(idx->X, idx->dtype, idx->n, idx->dim, p.q8, p.q8_scale, p.q8_err, idx->stream));
     p.stale = false;
+    *ready = true;
+    return SSW_OK;
+}
+
+// the packed 6-bit shadow of an f32 index, under the same rule
+ssw_status ssw::ensure_shadow6(ssw_index *idx, bool *ready) {
+    PruneState &p = idx->prune;
+    *ready = false;
+    if (p.q6 && !p.stale6) {
+        *ready = true;
+        return SSW_OK;
+    }
+    if (p.refused6) return SSW_OK;
+    if (!p.q6) {
+        const size_t codes = q6_code_bytes(idx->n, idx->dim), consts = (size_t)q6_padded_rows(idx->n) * sizeof(float);
+        bool fits = false;
+        SSW_TRY(shadow_fits(idx, codes + 2 * consts, &fits));
+        if (!fits) {
+            p.refused6 = true;
+            return SSW_OK;
+        }
+        if (hipMalloc((void **)&p.q6, codes) != hipSuccess || hipMalloc((void **)&p.q6_scale, consts) != hipSuccess ||
+            hipMalloc((void **)&p.q6_err, consts) != hipSuccess) {
+            (void)hipGetLastError();
+            for (void *b : {(void *)p.q6, (void *)p.q6_scale, (void *)p.q6_err}) (void)hipFree(b);
+            p.q6 = nullptr;
+            p.q6_scale = p.q6_err = nullptr;
+            p.refused6 = true;
+            return SSW_OK;
+        }
+    }
+    SSW_TRY(ensure_call_buffers(idx));
+    if (!p.state6) SSW_HIP_TRY(hipMalloc((void **)&p.state6, (size_t)Q8_MQ_WORDS * sizeof(unsigned)));
+    if (!p.planes6) {  // each buffer under its own test: a call that failed between them leaves no half-made state
+        SSW_HIP_TRY(hipMalloc((void **)&p.planes6, q6_plane_bytes(idx->dim)));
+        // columns 2 .. 15 of the query operand stay zero for good: k_q6_query writes columns 0 and 1 only
+        SSW_HIP_TRY(hipMemsetAsync(p.planes6, 0, q6_plane_bytes(idx->dim), idx->stream));
+    }
+    SSW_TRY(launch_q6_build(idx->X, idx->n, idx->dim, p.q6, p.q6_scale, p.q6_err, idx->stream));
+    p.stale6 = false;
     *ready = true;
     return SSW_OK;
 }
@@ -101,19 +173,37 @@ ssw_status ssw::prune_bounds(ssw_index *idx, const float *q_dev) {
     return SSW_OK;
 }
 
+// The same on the 6-bit shadow, which is ready (the lab hook ssw_debug_prune6_bounds drives it as well, with dbg_I).
+ssw_status ssw::prune6_bounds(ssw_index *idx, const float *q_dev, int64_t *dbg_I) {
+    PruneState &p = idx->prune;
+    SSW_TRY(launch_q6_query(q_dev, idx->dim, p.state6, p.planes6, p.q_last, idx->stream));
+    SSW_TRY(launch_q6_bounds(p.q6, p.q6_scale, p.q6_err, p.planes6, p.state6, idx->scores, idx->n, idx->dim, dbg_I,
+                             idx->device, idx->stream));
+    idx->scores_partial = true;
+    return SSW_OK;
+}
+
 // The rows that may still reach the k-th key of the last selection, at most cap of them -> *out_m = their published
-// count, -1 = run the full scan.  One host wait: a sleep on sleep_ev_or_null first, then a spin.
-ssw_status ssw::prune_survivors(ssw_index *idx, int32_t k, int64_t cap, hipEvent_t sleep_ev_or_null, int32_t *out_m) {
+// count, -1 = run the full scan.  One host wait: a sleep on sleep_ev_or_null first, then a spin.  six: the bounds in
+// the buffer are the 6-bit shadow's (width (***) of prune.hip), else the int8 shadow's.
+static ssw_status survivors_of(ssw_index *idx, bool six, int32_t k, int64_t cap, hipEvent_t sleep_ev_or_null, int32_t *out_m) {
     PruneState &p = idx->prune;
     const unsigned seq = next_seq(p.seq);
     int32_t *host_dev = nullptr;
     SSW_HIP_TRY(hipHostGetDevicePointer((void **)&host_dev, p.host, 0));
-    SSW_TRY(launch_survivors(idx->scores, p.q8_err, idx->n, idx->ws.out_keys, idx->ws.out_count, k, p.state, p.surv_rows, cap,
-                             host_dev, seq, idx->device, idx->stream));
+    if (six)
+        SSW_TRY(launch_survivors_q6(idx->scores, p.q6_err, p.q6_scale, idx->n, idx->dim, idx->ws.out_keys, idx->ws.out_count,
+                                    k, p.state6, p.surv_rows, cap, host_dev, seq, idx->device, idx->stream));
+    else
+        SSW_TRY(launch_survivors(idx->scores, p.q8_err, idx->n, idx->ws.out_keys, idx->ws.out_count, k, p.state, p.surv_rows,
+                                 cap, host_dev, seq, idx->device, idx->stream));
     if (sleep_ev_or_null) SSW_HIP_TRY(hipEventSynchronize(sleep_ev_or_null));
     SSW_TRY(wait_host_seq(idx->stream, reinterpret_cast<const unsigned *>(p.host), seq));
     *out_m = __atomic_load_n(p.host + 1, __ATOMIC_ACQUIRE);
     return SSW_OK;
+}
+ssw_status ssw::prune_survivors(ssw_index *idx, int32_t k, int64_t cap, hipEvent_t sleep_ev_or_null, int32_t *out_m) {
+    return survivors_of(idx, false, k, cap, sleep_ev_or_null, out_m);
 }
 
 // The score buffer for the selection of the top-k of query q_dev (exclusions installed): the full f32 scan, or on a
@@ -121,20 +211,24 @@ ssw_status ssw::prune_survivors(ssw_index *idx, int32_t k, int64_t cap, hipEvent
 // nothing, survivors, exact rescoring of the survivors.  One host wait for the survivor count; any failure of the
 // certificate (fewer than k keys or an overflow in the threshold selection, more survivors than SURV_CAP, a query
 // that cannot be bounded) runs the full scan instead.  The profiling events bracket the whole replacement.
+// The shadow is the 6-bit one where prune6_eligible says so (only that one is built then), else the int8 one; a 6-bit
+// shadow refused for memory leaves the int8 path, if an int8 shadow exists or fits.
 ssw_status ssw::scan_for_topk(ssw_index *idx, const float *q_dev, int32_t k) {
-    bool ready = false;
+    bool ready = false, six = false;
     const bool k_ok = k >= 1 && k <= SSW_MAX_TOPK && (idx->ws.xchg.msg_out == nullptr || k <= idx->ws.xchg.k_max);
-    if (k_ok && prune_eligible(idx)) SSW_TRY(ensure_shadow(idx, &ready));
-    if (!ready) return do_scan(idx, q_dev);
+    if (k_ok && prune6_eligible(idx)) SSW_TRY(ensure_shadow6(idx, &six));
+    if (k_ok && !six && prune_eligible(idx)) SSW_TRY(ensure_shadow(idx, &ready));
+    if (!ready && !six) return do_scan(idx, q_dev);
     SSW_TRY(ensure_ws(idx));
     return profiled(idx, [&]() -> ssw_status {
         PruneState &p = idx->prune;
-        SSW_TRY(prune_bounds(idx, q_dev));
+        if (six) SSW_TRY(prune6_bounds(idx, q_dev, nullptr));
+        else SSW_TRY(prune_bounds(idx, q_dev));
         SSW_HIP_TRY(hipEventRecord(p.ev, idx->stream));
         // threshold: the ordinary selection over the lower bounds, with the exclusions, without a message or host result
         SSW_TRY(do_select(idx, idx->scores, k, SelectDest{nullptr, 0u, false}, idx->stream));
         int32_t m = -1;
-        SSW_TRY(prune_survivors(idx, k, SURV_CAP, p.ev, &m));  // sleep through the shadow scan, spin on the rest
+        SSW_TRY(survivors_of(idx, six, k, SURV_CAP, p.ev, &m));  // sleep through the shadow scan, spin on the rest
         p.last = m;
         ++p.queries;
         if (m < 0) {
@@ -227,12 +321,15 @@ extern "C" {
 ssw_status ssw_index_prune_stats(ssw_index *idx, int64_t *out6) {
     SSW_REQUIRE(idx != nullptr && out6 != nullptr, "NULL argument");
     const PruneState &p = idx->prune;
-    out6[0] = p.q8 ? (p.stale ? 2 : 1) : (p.refused ? 3 : 0);
-    out6[1] = prune_eligible(idx) ? 1 : 0;
+    // the state of the shadow single queries use: the 6-bit one where it applies and was not refused
+    const bool six = prune6_eligible(idx) && !p.refused6;
+    if (six) out6[0] = p.q6 ? (p.stale6 ? 2 : 1) : 0;
+    else out6[0] = p.q8 ? (p.stale ? 2 : 1) : (p.refused ? 3 : 0);
+    out6[1] = prune_eligible(idx) || six ? 1 : 0;
     out6[2] = p.last;
     out6[3] = p.queries;
     out6[4] = p.fallbacks;
-    out6[5] = p.q8 ? idx->n * (idx->dim + 8) : 0;
+    out6[5] = (p.q8 ? idx->n * (idx->dim + 8) : 0) + (p.q6 ? q6_padded_rows(idx->n) * (idx->dim * 3 / 4 + 8) : 0);
     return SSW_OK;
 }
 
@@ -246,6 +343,17 @@ ssw_status ssw_tune_prune(int32_t enable, int64_t min_rows, int64_t reserve_byte
 
 ssw_status ssw_tune_prune_scan(int32_t blocks_per_cu, int32_t group_loads) {
     tune_q8_bounds(blocks_per_cu, group_loads);
+    return SSW_OK;
+}
+
+ssw_status ssw_tune_prune6(int32_t enable, int64_t min_rows) {
+    g_prune6 = enable != 0;
+    g_prune6_min_rows = min_rows < 0 ? -1 : min_rows;  // < 0: PRUNE6_MIN_ROWS again
+    return SSW_OK;
+}
+
+ssw_status ssw_tune_prune6_scan(int32_t blocks_per_cu, int32_t tiles) {
+    tune_q6_bounds(blocks_per_cu, tiles);
     return SSW_OK;
 }
 

@@ -48,10 +48,12 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 // The part of a row's conversion both builders share: the lane's 4C elements x (any fixed assignment of the row's
 // elements to lanes and slots) -> their codes, slot i in byte i % 4 of packed[i / 4], and the row's s_r and a_r, which
 // lane 0 writes.  The codes and s_r do not depend on the assignment; a_r's double sums are taken in its order.
-template <int C>
+// LEVELS: the largest |code|, 127 for the int8 shadow, 31 for the packed 6-bit one (k_q6_build).
+template <int C, int LEVELS = 127>
 __device__ __forceinline__ void q8_quantise_row(const float (&x)[4 * C], int64_t r, int lane, unsigned (&packed)[C],
                                                 float *__restrict__ scale, float *__restrict__ err) {
     constexpr int dim = 256 * C;
+    constexpr float LV = (float)LEVELS;
     float m = 0.0f;
     bool finite = true;
 #pragma unroll
@@ -62,14 +64,14 @@ __device__ __forceinline__ void q8_quantise_row(const float (&x)[4 * C], int64_t
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
     const bool ok = __all(finite) && (m == 0.0f || (m >= MIN_ABS && m <= MAX_ABS));
-    const float s = (ok && m > 0.0f) ? m / 127.0f : 0.0f;
+    const float s = (ok && m > 0.0f) ? m / LV : 0.0f;
     double e2 = 0.0, x2 = 0.0, c2 = 0.0;
 #pragma unroll
     for (int c = 0; c < C; ++c) packed[c] = 0u;
 #pragma unroll
     for (int i = 0; i < 4 * C; ++i) {
         float q = s > 0.0f ? rintf(x[i] / s) : 0.0f;
-        q = fminf(fmaxf(q, -127.0f), 127.0f);
+        q = fminf(fmaxf(q, -LV), LV);
         const int ci = (int)q;
         packed[i >> 2] |= ((unsigned)ci & 0xffu) << (8 * (i & 3));
         // x~_i = s * c_i is exact in double; so is its difference to x_i
@@ -440,27 +442,19 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 // 127 sqrt(dim), rounded up
 __host__ __device__ constexpr double mq_code_norm(int dim) { return dim == 256 ? 2032.0 : dim == 512 ? 2873.6819588 : 4064.0; }
 
-// One block a slot.  Slots >= w get zero codes and nothing else.
-__global__ __launch_bounds__(256) void k_q8_query_mq(const float *__restrict__ qb, int dim, int w, unsigned *__restrict__ mq,
-                                                     int8_t *__restrict__ planes, float *__restrict__ q_last) {
+// One query into its two code planes and its state words, by one block of 256 threads.  code_at(i, p) is where the
+// code of element i in plane p (0 hi, 1 lo) goes: the caller's operand layout.
+template <class CodeAt>
+__device__ __forceinline__ void mq_quantise_query(const float *__restrict__ q, int dim, float *__restrict__ q_keep,
+                                                  unsigned *__restrict__ st, CodeAt code_at) {
     __shared__ double part[4], part_e[4];
     __shared__ float part_m[4];
-    const int b = blockIdx.x;
-    auto code_at = [&](int i, int p) -> int8_t * {
-        const int ks = i >> 6, g = (i & 63) >> 4, j = i & 15;
-        return planes + ((size_t)((ks * 2 + p) * 64 + g * 16 + b) * 16 + j);
-    };
-    if (b >= w) {
-        for (int i = threadIdx.x; i < dim; i += 256) *code_at(i, 0) = 0, *code_at(i, 1) = 0;
-        return;
-    }
-    const float *q = qb + (size_t)b * dim;
     double s = 0.0;
     float m = 0.0f;
     bool finite = true;
     for (int i = threadIdx.x; i < dim; i += 256) {
         const float v = q[i];
-        if (b == w - 1) q_last[i] = v;
+        if (q_keep) q_keep[i] = v;
         finite = finite && isfinite(v);
         m = fmaxf(m, fabsf(v));
         s += (double)v * (double)v;
@@ -496,7 +490,6 @@ __global__ __launch_bounds__(256) void k_q8_query_mq(const float *__restrict__ q
     __syncthreads();
     if (threadIdx.x == 0) {
         const double te = part_e[0] + part_e[1] + part_e[2] + part_e[3];
-        unsigned *st = mq + b * MQ_WORDS;
         st[0] = 0u;
         st[1] = __float_as_uint(Q);
         st[2] = bad ? 1u : 0u;
@@ -504,6 +497,21 @@ __global__ __launch_bounds__(256) void k_q8_query_mq(const float *__restrict__ q
         st[4] = __float_as_uint(t2);
         st[5] = 0u;
     }
+}
+
+// One block a slot.  Slots >= w get zero codes and nothing else.
+__global__ __launch_bounds__(256) void k_q8_query_mq(const float *__restrict__ qb, int dim, int w, unsigned *__restrict__ mq,
+                                                     int8_t *__restrict__ planes, float *__restrict__ q_last) {
+    const int b = blockIdx.x;
+    auto code_at = [&](int i, int p) -> int8_t * {
+        const int ks = i >> 6, g = (i & 63) >> 4, j = i & 15;
+        return planes + ((size_t)((ks * 2 + p) * 64 + g * 16 + b) * 16 + j);
+    };
+    if (b >= w) {
+        for (int i = threadIdx.x; i < dim; i += 256) *code_at(i, 0) = 0, *code_at(i, 1) = 0;
+        return;
+    }
+    mq_quantise_query(qb + (size_t)b * dim, dim, b == w - 1 ? q_last : nullptr, mq + b * MQ_WORDS, code_at);
 }
 
 // lb of every row for every query of the chunk: query j's into slab j (j + 1 < w: side + j * stride, the last: own).
@@ -711,6 +719,202 @@ __global__ __launch_bounds__(256) void k_scatter_scores(const int64_t *__restric
     if (i < m) scores[rows[i]] = v[i];
 }
 
+
+// ---- the packed 6-bit shadow of f32 rows and its scan on the int8 matrix core ("6-bit shadow") ----
+// Codes c = rint(x / s6), |c| <= 31, s6 = max|x| / 31; a6 is the int8 shadow's a_r with these codes.  The query is the
+// chunk's (k_q8_query_mq: two int8 planes, residual norm e), so with ||c|| <= 31 sqrt(dim)
+//
+//     | S_r - (s6_r / 4) t2 I_r | <= a6_r Q + s6_r 31 sqrt(dim) e =: w,   I_r = sum_i 4 c_ri (256 d_hi,i + d_lo,i)   (***)
+//
+// Layout (q6_slot, q6_word_offset in ssw_common.h: the ONE placement function, shared with the lab hook and mirrored by
+// the tests' numpy twin): tiles of 16 consecutive rows; the lane of row r and element i is 16 ((i % 64) / 16) + r % 16,
+// which owns 3 dim / 64 words of the tile; k-step u = i / 64 takes its words 3u .. 3u + 2, slot j = i % 16: slots 0 ..
+// 11 are the upper six bits of those twelve bytes, slot 12 + b is spread over the low two bits of byte b of the three
+// words (code bits 5:4, 3:2, 1:0).  Word wi of lane l is the four bytes at (wi / 4) * 1024 + 16 l + 4 (wi % 4) of the
+// tile: every wave load instruction reads 1 KiB contiguous.  The state words are a slot's of the chunk (MQ_WORDS).
+// Query operand: k-step u, lane l: the u32x4 at u * 64 + l holds the hi plane's codes of elements 64 u + 16 (l >> 4) + j
+// in column 0 (l & 15 == 0), the lo plane's in column 1, zeros elsewhere (written once, when the buffer is made).
+constexpr int Q6_BLOCKS_PER_CU = 1;
+SSW_TUNABLE int g_q6_blocks_per_cu = Q6_BLOCKS_PER_CU;
+SSW_TUNABLE int g_q6_tiles = 0;  // 0: q6_default_tiles(C)
+constexpr int q6_default_tiles(int C) { return 4 / C; }  // 16-row tiles of one request: 12 KiB a wave at every dim
+
+// 31 sqrt(dim), rounded up
+__host__ __device__ constexpr double q6_code_norm(int dim) { return dim == 256 ? 496.0 : dim == 512 ? 701.4499270 : 992.0; }
+
+// one wave per row (grid-strided).  The row's codes in natural order go through the wave's own LDS line; lane l then
+// assembles words l, l + 64, .. of the row's 12 dim / 64 and stores each at its place in the tile.
+template <int C>
+__global__ __launch_bounds__(256) void k_q6_build(const float *__restrict__ X, int64_t n, unsigned char *__restrict__ codes,
+                                                  float *__restrict__ scale, float *__restrict__ err) {
+    constexpr int dim = 256 * C, KS = dim / 64, WPL = 3 * KS;  // words a lane of the tile owns
+    constexpr size_t TILE_BYTES = (size_t)16 * dim * 3 / 4;
+    __shared__ unsigned line[4][64 * C];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int8_t *cl = reinterpret_cast<const int8_t *>(line[wave]);
+    for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < n; r += (int64_t)gridDim.x * 4) {
+        const float4 *src = reinterpret_cast<const float4 *>(X + r * dim) + lane * C;
+        float x[4 * C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const float4 v = src[c];
+            x[4 * c] = v.x, x[4 * c + 1] = v.y, x[4 * c + 2] = v.z, x[4 * c + 3] = v.w;
+        }
+        unsigned packed[C];
+        q8_quantise_row<C, 31>(x, r, lane, packed, scale, err);
+        __builtin_amdgcn_wave_barrier();  // the previous row's reads of the line are issued (LDS is in order per wave)
+#pragma unroll
+        for (int c = 0; c < C; ++c) line[wave][lane * C + c] = packed[c];
+        __builtin_amdgcn_wave_barrier();
+        unsigned char *tile = codes + (size_t)(r >> 4) * TILE_BYTES;
+        for (int w = lane; w < 4 * WPL; w += 64) {
+            const int g = w / WPL, wi = w % WPL, u = wi / 3, part = wi % 3;
+            unsigned word = 0u;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const int main_c = cl[q6_element(u, g, 4 * part + b)], low_c = cl[q6_element(u, g, 12 + b)];
+                word |= ((((unsigned)main_c & 0x3fu) << 2) | (((unsigned)low_c >> (4 - 2 * part)) & 3u)) << (8 * b);
+            }
+            *reinterpret_cast<unsigned *>(tile + q6_word_offset(16 * g + (int)(r & 15), wi)) = word;
+        }
+    }
+}
+
+// the query's planes in the operand layout above, its state words and its copy into the index's own buffer
+__global__ __launch_bounds__(256) void k_q6_query(const float *__restrict__ q, int dim, unsigned *__restrict__ st,
+                                                  int8_t *__restrict__ planes, float *__restrict__ q_keep) {
+    mq_quantise_query(q, dim, q_keep, st, [&](int i, int p) -> int8_t * {
+        int u, g, j;
+        q6_slot(i, &u, &g, &j);
+        return planes + ((size_t)(u * 64 + g * 16 + p) * 16 + j);
+    });
+}
+
+template <int CTRL>
+__device__ __forceinline__ int dpp_i(int v) {
+    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true);
+}
+
+// lb of every row into scores[r].  C = dim / 256; a wave takes groups of T tiles, grid-strided, with k_q8_bounds_mq's
+// loop: two register sets in turn, the next group's codes and constants requested before the current group's
+// products, counted waits, one loop exit, and the last n % (16 T) rows as one clamped group for one wave after it
+// (the code and constant buffers are padded to whole tiles; a tile past the last one is the last one again and
+// nothing is stored for it or for a row >= n).
+// Unpack, per 16 codes = one k-step of a lane (ISA of <2, 2>: 3 v_and_b32 with 0xfcfcfcfc for the three operand words
+// 4c, and for the fourth 3 v_and_b32 with 0x03030303, 3 v_lshlrev_b32 and 1 v_or3_b32): 10 VALU instructions, no sign
+// extension.  Then ONE v_mfma_i32_16x16x64_i8 a k-step: result lane l holds rows 4 (l >> 4) .. + 3
+// of the tile for column l & 15, the hi sums in column 0 and the lo sums in column 1, which lane l & 15 == 0 fetches with
+// one DPP move each; those four lanes do the double epilogue and one 16-byte store.
+// DEBUG (lab hook only): I_r goes to dbg_I[r] as well.
+template <int C, int T, bool DEBUG>
+__global__ __launch_bounds__(256) void k_q6_bounds(const u32x4 *__restrict__ codes, const float *__restrict__ scale,
+                                                   const float *__restrict__ err, const u32x4 *__restrict__ planes,
+                                                   const unsigned *__restrict__ st, float *__restrict__ scores, int64_t n,
+                                                   int64_t *__restrict__ dbg_I) {
+    constexpr int dim = 256 * C, KS = dim / 64, NL = 3 * C, G = 16 * T;  // NL 1-KiB loads a tile
+    constexpr unsigned TILE_VECS = NL * 64;
+    const int lane = threadIdx.x & 63;
+    const int col = lane & 15, quad = lane >> 4;
+    const int64_t gwave = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t nwaves = (int64_t)gridDim.x * 4;
+    const int64_t nfull = n / G;
+    const int ragged = (int)(n % G);
+    i32x4 qp[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) qp[ks] = __builtin_bit_cast(i32x4, planes[ks * 64 + lane]);
+    const double t2q = (double)__uint_as_float(st[4]) * 0.25;  // exact: the sums are of 4 c
+    const double wQ = (double)__uint_as_float(st[1]) * MQ_INFLATE;
+    const double wE = (double)__uint_as_float(st[3]) * q6_code_norm(dim) * MQ_INFLATE;
+    struct Set {
+        u32x4 c[T][NL];
+        float s[T][4], a[T][4];
+    };
+    // tile0: the group's first tile; last_tile: none beyond it is read
+    auto load = [&](Set &d, int64_t tile0, int64_t last_tile, bool nt) {
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const int64_t tile = tile0 + t < last_tile ? tile0 + t : last_tile;  // wave-uniform
+            const u32x4 *base = codes + tile * (int64_t)TILE_VECS + lane;
+#pragma unroll
+            for (int l = 0; l < NL; ++l) d.c[t][l] = nt ? __builtin_nontemporal_load(base + l * 64) : base[l * 64];
+        }
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const int64_t tile = tile0 + t < last_tile ? tile0 + t : last_tile;
+            const float4 sv = *reinterpret_cast<const float4 *>(scale + tile * 16 + 4 * quad);
+            const float4 av = *reinterpret_cast<const float4 *>(err + tile * 16 + 4 * quad);
+            d.s[t][0] = sv.x, d.s[t][1] = sv.y, d.s[t][2] = sv.z, d.s[t][3] = sv.w;
+            d.a[t][0] = av.x, d.a[t][1] = av.y, d.a[t][2] = av.z, d.a[t][3] = av.w;
+        }
+        __builtin_amdgcn_sched_barrier(0);  // as in k_q8_bounds: the requests stay ahead of the products
+    };
+    // the bounds of the first `rows` rows of group g from a set that has arrived (rows == G: whole stores)
+    auto bounds = [&](const Set &d, int64_t g, int rows) {
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            unsigned w[4 * NL];
+#pragma unroll
+            for (int l = 0; l < NL; ++l) w[4 * l] = d.c[t][l].x, w[4 * l + 1] = d.c[t][l].y, w[4 * l + 2] = d.c[t][l].z, w[4 * l + 3] = d.c[t][l].w;
+            i32x4 acc = {0, 0, 0, 0};
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const unsigned w0 = w[3 * ks], w1 = w[3 * ks + 1], w2 = w[3 * ks + 2];
+                const i32x4 a = {(int)(w0 & 0xfcfcfcfcu), (int)(w1 & 0xfcfcfcfcu), (int)(w2 & 0xfcfcfcfcu),
+                                 (int)(((w0 & 0x03030303u) << 6) | ((w1 & 0x03030303u) << 4) | ((w2 & 0x03030303u) << 2))};
+                acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, qp[ks], acc, 0, 0, 0);
+            }
+            float out[4];
+            double I[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int lo = dpp_i<DPP_XOR1>(acc[i]);  // column 1's sum, for the lanes of column 0
+                I[i] = (double)acc[i] * 256.0 + (double)lo;  // exact: |I| < 2^33 at dim 1024
+                const double sd = (double)d.s[t][i];
+                const double wv = (double)d.a[t][i] * wQ + sd * wE;
+                double lb = sd * t2q * I[i] - wv;
+                lb -= fabs(lb) * 0x1p-50 + PAD_ABS;
+                out[i] = __double2float_rd(lb);
+            }
+            const int r0 = t * 16 + 4 * quad;  // of the lane's four rows in the group
+            if (col == 0) {
+                if (rows == G) {
+                    *reinterpret_cast<float4 *>(scores + g * G + r0) = make_float4(out[0], out[1], out[2], out[3]);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        if (r0 + i < rows) (scores + g * G)[r0 + i] = out[i];
+                }
+                if constexpr (DEBUG) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        if (r0 + i < rows) (dbg_I + g * G)[r0 + i] = (int64_t)I[i];
+                }
+            }
+        }
+    };
+    if (gwave < nfull) {
+        const int64_t last = nfull * T - 1;
+        Set a, b;
+        int64_t g = gwave;
+        load(a, g * T, last, true);
+        for (;;) {
+            // a wave without a next group requests its last one once more (cache hits) and writes nothing for it
+            const int64_t g1 = g + nwaves < nfull ? g + nwaves : g;
+            load(b, g1 * T, last, true);
+            bounds(a, g, G);
+            const int64_t g2 = g1 + nwaves < nfull ? g1 + nwaves : g1;
+            load(a, g2 * T, last, true);
+            bounds(b, g1, g1 != g ? G : 0);
+            if (g2 == g1) break;
+            g = g2;
+        }
+    }
+    if (ragged != 0 && gwave == nfull % nwaves) {
+        Set t;
+        load(t, nfull * T, (n - 1) >> 4, false);
+        bounds(t, nfull, ragged);
+    }
+}
 }  // namespace
 
 bool q8_dim_supported(int32_t dim) { return dim == 256 || dim == 512 || dim == 1024; }
@@ -896,6 +1100,122 @@ ssw_status launch_survivors_mq(const float *lb, const float *err, const float *s
 ssw_status launch_prune_publish_mq(const unsigned *mq, int32_t w, int64_t cap, int32_t *host_block, unsigned seq,
                                    hipStream_t stream) {
     hipLaunchKernelGGL(k_prune_publish_mq, dim3(1), dim3(64), 0, stream, mq, (int)w, cap, host_block, seq);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+// ---- the packed 6-bit shadow (f32 rows) -----------------------------------------------------------------------------
+int64_t q6_padded_rows(int64_t n) { return (n + 15) / 16 * 16; }
+size_t q6_code_bytes(int64_t n, int32_t dim) { return (size_t)q6_padded_rows(n) * (size_t)dim * 3 / 4; }
+size_t q6_plane_bytes(int32_t dim) { return (size_t)(dim / 64) * 64 * 16; }
+
+// codes / scale / err: q6_code_bytes and q6_padded_rows floats each; the rows past n of the last tile get zeros
+ssw_status launch_q6_build(const float *X, int64_t n, int32_t dim, unsigned char *codes, float *scale, float *err,
+                           hipStream_t stream) {
+    if (n <= 0) return SSW_OK;
+    if (!q8_dim_supported(dim)) {
+        set_error("q6_build: dim=%d unsupported", dim);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    const int64_t np = q6_padded_rows(n);
+    const size_t tile_bytes = (size_t)16 * dim * 3 / 4;
+    if (np != n) {
+        SSW_HIP_TRY(hipMemsetAsync(codes + q6_code_bytes(n, dim) - tile_bytes, 0, tile_bytes, stream));
+        SSW_HIP_TRY(hipMemsetAsync(scale + np - 16, 0, 16 * sizeof(float), stream));
+        SSW_HIP_TRY(hipMemsetAsync(err + np - 16, 0, 16 * sizeof(float), stream));
+    }
+    const dim3 grid((unsigned)std::min<int64_t>((n + 3) / 4, (int64_t)1 << 20)), block(256);
+    switch (dim) {
+        case 256: hipLaunchKernelGGL(k_q6_build<1>, grid, block, 0, stream, X, n, codes, scale, err); break;
+        case 512: hipLaunchKernelGGL(k_q6_build<2>, grid, block, 0, stream, X, n, codes, scale, err); break;
+        default: hipLaunchKernelGGL(k_q6_build<4>, grid, block, 0, stream, X, n, codes, scale, err); break;
+    }
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+// st: Q8_MQ_WORDS words (a slot's of the chunk); planes: q6_plane_bytes(dim), zeroed when they were allocated
+ssw_status launch_q6_query(const float *q_dev, int32_t dim, unsigned *st, int8_t *planes, float *q_keep,
+                           hipStream_t stream) {
+    hipLaunchKernelGGL(k_q6_query, dim3(1), dim3(256), 0, stream, q_dev, (int)dim, st, planes, q_keep);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+static int q6_tiles(int C) {
+    int t = g_q6_tiles > 0 ? g_q6_tiles : q6_default_tiles(C);
+    while (t * C > 4) t >>= 1;  // two register sets of more than 12 KiB a wave do not fit beside the query operand
+    return t;
+}
+
+void q6_bounds_shape(int32_t dim, int device, int64_t n, int *out_blocks, int *out_tiles) {
+    const int T = q6_tiles(dim / 256);
+    const int64_t need = ((n + 16 * T - 1) / (16 * T) + 3) / 4;
+    int64_t grid = (int64_t)num_cus(device) * g_q6_blocks_per_cu;
+    if (grid > need) grid = need;
+    if (grid < 1) grid = 1;
+    *out_blocks = (int)grid;
+    *out_tiles = T;
+}
+
+ssw_status launch_q6_bounds(const unsigned char *codes, const float *scale, const float *err, const int8_t *planes,
+                            const unsigned *st, float *scores, int64_t n, int32_t dim, int64_t *dbg_I, int device,
+                            hipStream_t stream) {
+    if (n <= 0) return SSW_OK;
+    if (!q8_dim_supported(dim)) {
+        set_error("q6_bounds: dim=%d unsupported", dim);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    const int C = dim / 256;
+    int grid = 1, T = 1;
+    q6_bounds_shape(dim, device, n, &grid, &T);
+    const u32x4 *cd = reinterpret_cast<const u32x4 *>(codes), *pl = reinterpret_cast<const u32x4 *>(planes);
+#define SSW_Q6(C_, T_, D_)                                                                                           \
+    hipLaunchKernelGGL((k_q6_bounds<C_, T_, D_>), dim3((unsigned)grid), dim3(256), 0, stream, cd, scale, err, pl, st, \
+                       scores, n, dbg_I)
+#ifdef SSW_DEBUG_HOOKS
+#define SSW_Q6_T(C_, T_)             \
+    if (dbg_I) SSW_Q6(C_, T_, true); \
+    else SSW_Q6(C_, T_, false)
+    if (C == 1) {
+        if (T == 1) { SSW_Q6_T(1, 1); } else if (T == 2) { SSW_Q6_T(1, 2); } else { SSW_Q6_T(1, 4); }
+    } else if (C == 2) {
+        if (T == 1) { SSW_Q6_T(2, 1); } else { SSW_Q6_T(2, 2); }
+    } else {
+        SSW_Q6_T(4, 1);
+    }
+#undef SSW_Q6_T
+#else
+    (void)T;
+    switch (C) {
+        case 1: SSW_Q6(1, q6_default_tiles(1), false); break;
+        case 2: SSW_Q6(2, q6_default_tiles(2), false); break;
+        default: SSW_Q6(4, q6_default_tiles(4), false); break;
+    }
+#endif
+#undef SSW_Q6
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+#ifdef SSW_DEBUG_HOOKS
+void tune_q6_bounds(int blocks_per_cu, int tiles) {
+    g_q6_blocks_per_cu = blocks_per_cu >= 1 && blocks_per_cu <= 8 ? blocks_per_cu : Q6_BLOCKS_PER_CU;
+    g_q6_tiles = tiles == 1 || tiles == 2 || tiles == 4 ? tiles : 0;
+}
+#endif
+
+// k_survivors_mq with the 6-bit shadow's code norm, then the answer of the one slot into host_block[1]
+ssw_status launch_survivors_q6(const float *lb, const float *err, const float *scale, int64_t n, int32_t dim,
+                               const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *st, int64_t *rows,
+                               int64_t cap, int32_t *host_block, unsigned seq, int device, hipStream_t stream) {
+    int64_t grid = (int64_t)num_cus(device) * 4;
+    const int64_t need = (n + 1023) / 1024;  // four rows a lane
+    if (grid > need) grid = need;
+    if (grid < 1) grid = 1;
+    hipLaunchKernelGGL(k_survivors_mq, dim3((unsigned)grid), dim3(256), 0, stream, lb, err, scale, n, q6_code_norm(dim),
+                       keys, sel_count, k, st, rows, cap);
+    hipLaunchKernelGGL(k_prune_publish_mq, dim3(1), dim3(64), 0, stream, st, 1, cap, host_block, seq);
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
 }

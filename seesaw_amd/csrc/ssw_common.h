@@ -198,6 +198,31 @@ ssw_status launch_prune_publish_mq(const unsigned *mq, int32_t w, int64_t cap, i
                                    hipStream_t stream);
 // blocks and 16-row tiles per request of the launch launch_q8_bounds_mq would make
 void q8_bounds_mq_shape(int32_t dim, int device, int64_t n, int *out_blocks, int *out_tiles);
+// the packed 6-bit shadow of f32 rows (prune.hip, "6-bit shadow"): tiles of 16 rows, 3 dim / 4 bytes a row, buffers padded
+// to whole tiles.  q6_slot / q6_element / q6_word_offset are the ONE placement of an element's code: k-step u, lane
+// group g (the lane of row r is 16 g + r % 16) and slot j of the lane's 16 codes of that k-step; slot j < 12 is the upper
+// six bits of byte j % 4 of the lane's word 3 u + j / 4, slot 12 + b the low two bits of byte b of words 3 u .. 3 u + 2
+// (code bits 5:4, 3:2, 1:0); word wi of lane l sits at q6_word_offset(l, wi) in the tile.
+__host__ __device__ inline void q6_slot(int i, int *u, int *g, int *j) { *u = i >> 6, *g = (i & 63) >> 4, *j = i & 15; }
+__host__ __device__ inline int q6_element(int u, int g, int j) { return 64 * u + 16 * g + j; }
+__host__ __device__ inline size_t q6_word_offset(int lane, int wi) {
+    return (size_t)(wi >> 2) * 1024 + (size_t)lane * 16 + (size_t)(wi & 3) * 4;
+}
+int64_t q6_padded_rows(int64_t n);
+size_t q6_code_bytes(int64_t n, int32_t dim);
+size_t q6_plane_bytes(int32_t dim);
+ssw_status launch_q6_build(const float *X, int64_t n, int32_t dim, unsigned char *codes, float *scale, float *err,
+                           hipStream_t stream);
+ssw_status launch_q6_query(const float *q_dev, int32_t dim, unsigned *st, int8_t *planes, float *q_keep,
+                           hipStream_t stream);
+// dbg_I (lab hook only, else NULL): [n] the exact integer sums
+ssw_status launch_q6_bounds(const unsigned char *codes, const float *scale, const float *err, const int8_t *planes,
+                            const unsigned *st, float *scores, int64_t n, int32_t dim, int64_t *dbg_I, int device,
+                            hipStream_t stream);
+void q6_bounds_shape(int32_t dim, int device, int64_t n, int *out_blocks, int *out_tiles);
+ssw_status launch_survivors_q6(const float *lb, const float *err, const float *scale, int64_t n, int32_t dim,
+                               const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *st, int64_t *rows,
+                               int64_t cap, int32_t *host_block, unsigned seq, int device, hipStream_t stream);
 // rows between natural order and the index.  to_h16: n rows of natural-order f32 (src_f32) or binary16 (src_h16, the
 // other NULL) -> rows [0, n) of dst in the f16 layout, rounded to nearest even.  gather: rows (rows_or_null[i], or
 // first_row + i when it is NULL) of an index matrix of element type dtype -> n natural-order f32 rows of out.
@@ -210,6 +235,7 @@ void tune_scan(int variant, int blocks_per_cu);
 void tune_scan_batch(int max_width, int blocks_per_cu);
 void tune_q8_bounds(int blocks_per_cu, int group_loads);
 void tune_q8_bounds_mq(int blocks_per_cu, int tiles);
+void tune_q6_bounds(int blocks_per_cu, int tiles);
 #endif
 // knn.hip's last stage (lives in scan.hip to share the scan's summation order)
 ssw_status launch_knn_rescore(const float *X, int32_t dim, const int32_t *perm, int r0, int rows, const uint64_t *buf,

@@ -3,13 +3,21 @@
 
     python tools/perf_prune.py [--rows 12.5e6 25e6 50e6 100e6] [--k 100] [--reps 10] [--dtype float32|float16]
                                [--warmup-pairs 2]
+    python tools/perf_prune.py --three-way [--rows ...] [--k 100]
 
 For each index size: a synthetic N x 512 index of f32 or binary16 rows, one first top-k (builds the int8 shadow, timed
 on its own), `warmup-pairs` untimed pairs, then `reps` pairs of top-k calls with the pruning switched off and on in turn
 (the lab build's ssw_tune_prune; the threshold is lowered to 1 row so that every size is pruned), each a different
 query.  Prints per size: host wall ms per call (median, and the spread min .. max), the HIP-event ms of the scan phase
 (the full scan, or shadow scan + threshold selection + survivors + rescoring), survivors and fallbacks, and whether
-both forms returned the same images, scores and best rows."""
+both forms returned the same images, scores and best rows.  This mode keeps f32 indexes on the int8 shadow at every size
+(ssw_tune_prune6(0)).
+
+--three-way (f32 rows; how PRUNE6_MIN_ROWS of csrc/index_prune.hip is chosen): full scan / int8 shadow / packed 6-bit
+shadow in turn in one process, two warm-up rounds, then 20 rounds, each a different query; per size one JSON line with
+the median and the spread (max - min) of the host wall ms of each form, the 6-bit survivors, and whether all three
+returned the same bytes.  Where the two shadows do not fit beside the rows together (100 M rows), the int8 rounds and
+the 6-bit rounds run one after the other on two indexes of the same rows, each alternating with the full scan."""
 import argparse
 import ctypes
 import json
@@ -29,6 +37,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--dtype", choices=("float32", "float16"), default="float32")
     ap.add_argument("--warmup-pairs", type=int, default=2)
+    ap.add_argument("--three-way", action="store_true")
     args = ap.parse_args()
     from seesaw_amd import _lib
     from seesaw_amd.device_index import DeviceIndex
@@ -42,7 +51,66 @@ def main():
         q = np.random.default_rng(10_000 + i).standard_normal(512).astype(np.float32)
         return (q / np.linalg.norm(q)).astype(np.float32)
 
+    def set_form(form):
+        _lib.call("ssw_tune_prune", 0 if form == "full" else 1, 1, -1)
+        _lib.call("ssw_tune_prune6", 1 if form == "q6" else 0, 1)
+
+    def rounds(n, forms, wall, surv):
+        """warm-up and timed rounds over `forms` on a fresh index; -> all forms returned the same bytes"""
+        idx = DeviceIndex.synthetic(n, 512, seed=2024)
+        same = True
+        try:
+            for form in forms:  # builds the shadows, untimed
+                set_form(form)
+                idx.topk(query(0), args.k)
+            for i in range(-2, 20):
+                q, out = query(3 + i), {}
+                for form in forms:
+                    set_form(form)
+                    t0 = time.perf_counter()
+                    out[form] = idx.topk(q, args.k)
+                    if i >= 0:
+                        wall.setdefault(form, []).append(1e3 * (time.perf_counter() - t0))
+                        if form == "q6":
+                            surv.append(int(stats(idx)[2]))
+                for form in forms[1:]:
+                    same = same and all(np.array_equal(np.asarray(a).view(np.uint8), np.asarray(b).view(np.uint8))
+                                        for a, b in zip(out[forms[0]], out[form]))
+            return same, int(stats(idx)[4])
+        finally:
+            idx.close()
+
+    def three_way(n):
+        import torch
+        total = torch.cuda.mem_get_info(0)[1]
+        together = n * (2048 + 520 + 392 + 8) + (5 << 30) < total
+        wall, surv = {}, []
+        if together:
+            same, fallbacks = rounds(n, ["full", "int8", "q6"], wall, surv)
+        else:
+            wall_b = {}
+            same_a, fa = rounds(n, ["full", "int8"], wall, surv)
+            same_b, fb = rounds(n, ["full", "q6"], wall_b, surv)
+            wall["q6"], wall["full_beside_q6"] = wall_b["q6"], wall_b["full"]
+            same, fallbacks = same_a and same_b, fa + fb
+        res = {"rows": n, "k": args.k, "one_index": bool(together)}
+        for form, v in wall.items():
+            res[form + "_ms_median"] = round(float(np.median(v)), 3)
+            res[form + "_ms_spread"] = round(float(np.max(v) - np.min(v)), 3)
+        res.update({"q6_survivors_min_median_max": [int(np.min(surv)), int(np.median(surv)), int(np.max(surv))],
+                    "fallbacks": fallbacks, "identical": bool(same)})
+        print(json.dumps(res), flush=True)
+
     with _lib.debug_hooks():
+        if args.three_way:
+            try:
+                for rows in args.rows:
+                    three_way(int(rows))
+            finally:
+                _lib.call("ssw_tune_prune", 1, -1, -1)
+                _lib.call("ssw_tune_prune6", 1, -1)
+            return
+        _lib.call("ssw_tune_prune6", 0, -1)
         for rows in args.rows:
             n = int(rows)
             idx = DeviceIndex.synthetic(n, 512, seed=2024, dtype=np.dtype(args.dtype))
@@ -91,6 +159,7 @@ def main():
             finally:
                 _lib.call("ssw_tune_prune", 1, -1, -1)
                 idx.close()
+        _lib.call("ssw_tune_prune6", 1, -1)
 
 
 if __name__ == "__main__":
