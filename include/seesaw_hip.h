@@ -295,6 +295,51 @@ ssw_status ssw_topk_merge_msgs_dev(int32_t device, void *hip_stream, const uint6
                                    int32_t k_max, int32_t with_best, int32_t k, uint64_t *dev_keys_out,
                                    int32_t *dev_count_out, int64_t *dev_flags_or_null, int64_t *dev_flags_seen_or_null);
 
+/* The sharded query for a CHUNK of queries: every rank reads its rows once per chunk and the exchange is one
+ * all-gather and one merge launch per chunk.  Opt-in and beside everything above: ssw_index_topk_dev, the
+ * ssw_index_topk_batch entries and the single exchange target keep their results, state and launch sequence.
+ *
+ * ssw_index_set_exchange_target_batch: dev_msgs [n_slots, msg_len] u64, msg_len = (with_best ? 2 : 1) * k_max + 1, every
+ * slot a message in the format of ssw_index_set_exchange_target (NULL detaches).  State of its own: the single target,
+ * if attached, is neither moved nor written by the batched entries, and they never write this one.  n_slots < 1 or
+ * k_max outside [1, SSW_MAX_TOPK] is SSW_ERR_INVALID.
+ *
+ * ssw_index_topk_batch_dev: queries and exclusion lists as ssw_index_topk_batch, validated the same way before anything
+ * is enqueued (SSW_ERR_NUMERIC / SSW_ERR_INVALID); also SSW_ERR_INVALID, before anything is enqueued: no batch target
+ * attached, k > k_max, first_slot < 0, first_slot + nq > n_slots.  ENQUEUES ONLY: it waits for the device only where a
+ * buffer has to grow or a staging block is reused (the side buffer, a long exclusion delta, the query block).  Chunking
+ * and the side buffer are ssw_index_topk_batch's; the scan is always the full-precision one (no shadow is built or read,
+ * the prune counters stay; a partial score buffer is completed first).  For query b the call installs its exclusion set
+ * and runs the ordinary selection on its slab -- the one-launch, the histogram or the sampled form -- whose last kernel
+ * writes message slot first_slot + b.  An overflowed fast selection (mass ties, a sampled threshold that left too few
+ * candidates) is NOT repaired here: the overflow bit travels in the slot's last word, as in the single path.  An index
+ * without images writes "0 keys" into its slots.
+ * State afterwards: that of ssw_index_topk_dev(q[nq-1]) with the last query's exclusion set installed (resident scores,
+ * result buffers, installed set).  ssw_index_profile records one event pair per scan launch.
+ * Not measured yet ("Sharded batch"; tools/perf_sharded_batch.py takes the figures).
+ *
+ * ssw_index_topk_slot_deep_dev: the repair of ONE flagged query: a single-query full scan of q_host (the slabs of the
+ * chunk are gone by the time the flags are read; the batched scan returns the bits of the single scan, so the result
+ * is the one the slab would have given), its exclusion list installed, the deep selection, the message into `slot` of
+ * the batch target.  Synchronises inside, like ssw_index_select_deep_dev.  Same refusals as above.
+ *
+ * ssw_topk_merge_msgs_batch_dev: ssw_topk_merge_msgs_dev for nq queries in ONE launch (one workgroup per query).  Rank
+ * r's message for query b starts at word r * rank_stride + b * msg_len -- the layout one all-gather of nq * msg_len
+ * words per rank leaves, with rank_stride = nq * msg_len.  dev_keys_out [nq, k_max], dev_counts_out [nq], dev_flags
+ * [nq, world] (i64), dev_flags_seen [1] (OR-ed, atomically).  Row b holds the bits ssw_topk_merge_msgs_dev produces
+ * from query b's `world` messages.  Limits: those of the single merge (world * k <= 8192, k <= k_max), nq >= 1,
+ * rank_stride >= nq * msg_len. */
+ssw_status ssw_index_set_exchange_target_batch(ssw_index *idx, uint64_t *dev_msgs_or_null, int32_t n_slots, int32_t k_max,
+                                               int32_t with_best, int64_t image_offset, int64_t row_offset);
+ssw_status ssw_index_topk_batch_dev(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
+                                    const int64_t *excluded_offsets, int32_t k, int32_t first_slot);
+ssw_status ssw_index_topk_slot_deep_dev(ssw_index *idx, const float *q_host, const int64_t *excluded_images,
+                                        int64_t n_excluded, int32_t k, int32_t slot);
+ssw_status ssw_topk_merge_msgs_batch_dev(int32_t device, void *hip_stream, const uint64_t *dev_msgs, int32_t world,
+                                         int64_t rank_stride, int32_t nq, int32_t k_max, int32_t with_best, int32_t k,
+                                         uint64_t *dev_keys_out, int32_t *dev_counts_out, int64_t *dev_flags_or_null,
+                                         int64_t *dev_flags_seen_or_null);
+
 /* The collective itself (`ssw_topk_allgather(ssw_comm *, ...)`): RCCL bound at run time (dlopen; the
  * copy torch mapped, if any).  ssw_comm_unique_id on one rank -> 128 bytes handed to every rank by the caller's own
  * means -> ssw_comm_create on every rank (collective).  ssw_topk_allgather enqueues ncclAllGather of msg_len u64 words

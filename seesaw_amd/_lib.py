@@ -143,6 +143,11 @@ _SIGNATURES = {
     "ssw_index_gather_rows": (c_i32, [c_void_p, c_void_p, c_i64, c_void_p]),
     "ssw_index_set_exchange_target": (c_i32, [c_void_p, c_void_p, c_i32, c_i32, c_i64, c_i64]),
     "ssw_topk_merge_msgs_dev": (c_i32, [c_i32, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ssw_index_set_exchange_target_batch": (c_i32, [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_i64, c_i64]),
+    "ssw_index_topk_batch_dev": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_i32]),
+    "ssw_index_topk_slot_deep_dev": (c_i32, [c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32]),
+    "ssw_topk_merge_msgs_batch_dev": (c_i32, [c_i32, c_void_p, c_void_p, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_void_p,
+                                              c_void_p, c_void_p, c_void_p]),
     "ssw_comm_unique_id": (c_i32, [c_void_p]),
     "ssw_comm_create": (c_i32, [c_i32, c_void_p, c_i32, c_i32, ctypes.POINTER(c_void_p)]),
     "ssw_comm_destroy": (c_i32, [c_void_p]),

@@ -701,6 +701,37 @@ ssw_status ssw_index_set_exchange_target(ssw_index *idx, uint64_t *dev_msg_or_nu
     return SSW_OK;
 }
 
+// the target of the batched form (ssw_index_topk_batch_dev): n_slots messages, beside the single target
+ssw_status ssw_index_set_exchange_target_batch(ssw_index *idx, uint64_t *dev_msgs_or_null, int32_t n_slots, int32_t k_max,
+                                               int32_t with_best, int64_t image_offset, int64_t row_offset) {
+    SSW_REQUIRE(idx != nullptr, "idx is NULL");
+    FinalExchange x;
+    if (dev_msgs_or_null) {
+        SSW_REQUIRE(n_slots >= 1, "n_slots=%d < 1", n_slots);
+        SSW_REQUIRE(k_max >= 1 && k_max <= SSW_MAX_TOPK && image_offset >= 0, "bad message geometry");
+        x.msg_out = dev_msgs_or_null;
+        x.image_offset = (uint64_t)image_offset;
+        x.row_offset = row_offset;
+        x.k_max = k_max;
+        x.with_best = with_best ? 1 : 0;
+        x.msg_len = (with_best ? 2 : 1) * k_max + 1;
+    }
+    idx->xchg_batch = x;
+    idx->xchg_batch_slots = dev_msgs_or_null ? n_slots : 0;
+    return SSW_OK;
+}
+
+ssw_status ssw_topk_merge_msgs_batch_dev(int32_t device, void *hip_stream, const uint64_t *dev_msgs, int32_t world,
+                                         int64_t rank_stride, int32_t nq, int32_t k_max, int32_t with_best, int32_t k,
+                                         uint64_t *dev_keys_out, int32_t *dev_counts_out, int64_t *dev_flags_or_null,
+                                         int64_t *dev_flags_seen_or_null) {
+    SSW_REQUIRE(dev_msgs && dev_keys_out && dev_counts_out, "NULL argument");
+    DeviceGuard guard(device);
+    return launch_merge_msgs_batch(dev_msgs, world, rank_stride, nq, k_max, with_best, k, dev_keys_out, dev_counts_out,
+                                   reinterpret_cast<long long *>(dev_flags_or_null),
+                                   reinterpret_cast<long long *>(dev_flags_seen_or_null), (hipStream_t)hip_stream);
+}
+
 ssw_status ssw_topk_merge_msgs_dev(int32_t device, void *hip_stream, const uint64_t *dev_msgs, int32_t world,
                                    int32_t k_max, int32_t with_best, int32_t k, uint64_t *dev_keys_out,
                                    int32_t *dev_count_out, int64_t *dev_flags_or_null, int64_t *dev_flags_seen_or_null) {

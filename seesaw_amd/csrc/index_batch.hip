@@ -291,6 +291,100 @@ ssw_status ssw_index_topk_batch_pruned(ssw_index *idx, const float *q_host, int3
                           out_counts, nullptr, true);
 }
 
+}  // extern "C"
+
+// ---- the batched top-k that stays on the device: every query's message into a slot of the batch exchange target ------
+// what a call that writes slots [first, first + n) of the batch target must hold, checked before anything is enqueued
+static ssw_status check_batch_target(const ssw_index *idx, int32_t k, int32_t first, int32_t n, const char *who) {
+    SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
+    SSW_REQUIRE(idx->xchg_batch.msg_out != nullptr, "%s: no batch exchange target attached", who);
+    SSW_REQUIRE(k <= idx->xchg_batch.k_max, "%s: k=%d exceeds the batch exchange target's k_max=%d", who, k,
+                idx->xchg_batch.k_max);
+    SSW_REQUIRE(first >= 0 && (int64_t)first + n <= idx->xchg_batch_slots, "%s: slots [%d, %lld) outside the target's %d",
+                who, first, (long long)first + n, idx->xchg_batch_slots);
+    return SSW_OK;
+}
+
+// the batch target narrowed to one slot: what the selection's last kernel takes as its message
+static FinalExchange batch_slot(const ssw_index *idx, int32_t slot) {
+    FinalExchange x = idx->xchg_batch;
+    x.msg_out += (int64_t)slot * x.msg_len;
+    return x;
+}
+
+// an index without images still takes part in the exchange: its slots say "0 keys"
+static ssw_status empty_slots(ssw_index *idx, int32_t first, int32_t n) {
+    for (int32_t s = first; s < first + n; ++s)
+        SSW_HIP_TRY(hipMemsetAsync(batch_slot(idx, s).msg_out + (idx->xchg_batch.msg_len - 1), 0, sizeof(uint64_t),
+                                   idx->stream));
+    return SSW_OK;
+}
+
+extern "C" ssw_status ssw_index_topk_batch_dev(ssw_index *idx, const float *q_host, int32_t nq,
+                                               const int64_t *excluded_images, const int64_t *excluded_offsets,
+                                               int32_t k, int32_t first_slot) {
+    SSW_REQUIRE(nq >= 1, "nq=%d < 1", nq);
+    SSW_REQUIRE(idx != nullptr && q_host != nullptr, "NULL argument");
+    SSW_TRY(check_batch_target(idx, k, first_slot, nq, "topk_batch_dev"));
+    const BatchExcluded excl{excluded_images, excluded_offsets};
+    SSW_TRY(check_excluded_offsets(idx, excl, nq));
+    SSW_TRY(check_query_batch(idx, q_host, nq));
+    DeviceGuard guard(idx->device);
+    if (idx->n_images == 0) return empty_slots(idx, first_slot, nq);
+    SSW_TRY(ensure_full_scores(idx));
+    SSW_TRY(ensure_ws(idx));
+    int W = 1;
+    SSW_TRY(batch_width(idx, nq, &W));
+    const size_t dim = (size_t)idx->dim;
+    for (int32_t b = 0; b < nq;) {
+        const float *q = q_host + b * dim;
+        int w = W;
+        while (w > nq - b) w >>= 1;
+        if (w >= 2) {
+            SSW_TRY(do_scan_chunk(idx, q, w));
+        } else {  // one query: the full single-query scan (never the pre-scan) into the handle's buffer
+            w = 1;
+            SSW_TRY(stage_query(idx, q));
+            SSW_TRY(do_scan(idx, idx->q_dev));
+        }
+        for (int j = 0; j < w; ++j) {  // the ordinary selection on each slab; its last kernel writes the slot
+            int64_t n_ex = 0;
+            const int64_t *ex = excl.of(b + j, &n_ex);
+            SSW_TRY(install_excluded(idx, ex, n_ex, idx->stream));
+            const FinalExchange slot = batch_slot(idx, first_slot + b + j);
+            SelectDest dest;
+            dest.target = &slot;
+            SSW_TRY(do_select(idx, chunk_slab(idx, w, j), k, dest, idx->stream));
+        }
+        b += w;
+    }
+    return SSW_OK;
+}
+
+extern "C" ssw_status ssw_index_topk_slot_deep_dev(ssw_index *idx, const float *q_host, const int64_t *excluded_images,
+                                                   int64_t n_excluded, int32_t k, int32_t slot) {
+    SSW_REQUIRE(idx != nullptr && q_host != nullptr, "NULL argument");
+    SSW_REQUIRE(n_excluded == 0 || excluded_images != nullptr, "excluded_images is NULL");
+    SSW_TRY(check_batch_target(idx, k, slot, 1, "topk_slot_deep_dev"));
+    SSW_TRY(check_excluded(idx, excluded_images, 0, n_excluded));
+    SSW_TRY(check_query(idx, q_host));
+    DeviceGuard guard(idx->device);
+    if (idx->n_images == 0) return empty_slots(idx, slot, 1);
+    SSW_TRY(ensure_ws(idx));
+    SSW_TRY(stage_query(idx, q_host));
+    SSW_TRY(do_scan(idx, idx->q_dev));  // the slab of the flagged query is gone: the same bits again
+    SSW_TRY(install_excluded(idx, excluded_images, n_excluded, idx->stream));
+    if (idx->has_map)
+        SSW_TRY(launch_image_max(idx->scores, idx->row_start, idx->n_images, idx->ws.img_score, idx->ws.img_best,
+                                 idx->stream));
+    const FinalExchange target = batch_slot(idx, slot);
+    SelectDest dest;
+    dest.target = &target;
+    return do_select_deep(idx, idx->scores, k, dest, idx->stream);
+}
+
+extern "C" {
+
 ssw_status ssw_index_topk_batch_avg(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
                                     const int64_t *excluded_offsets, int32_t k, int32_t aug_larger, int64_t *out_images,
                                     float *out_scores, int64_t *out_best_rows, float *out_avg_scores,

@@ -104,6 +104,10 @@ struct ssw_index {
     hipStream_t stream = nullptr;
     ssw::SelectWorkspace ws;
     bool ws_ready = false;
+    // the batched exchange target (ssw_index_set_exchange_target_batch): msg_out is slot 0 of [xchg_batch_slots, msg_len];
+    // state of its own beside ws.xchg, written only by ssw_index_topk_batch_dev / ssw_index_topk_slot_deep_dev
+    ssw::FinalExchange xchg_batch;
+    int32_t xchg_batch_slots = 0;
     // gather staging
     int64_t *gather_idx = nullptr;
     float *gather_out = nullptr;
@@ -185,6 +189,7 @@ inline ssw_status ensure_full_scores(ssw_index *idx) { return ensure_full_scores
 // index_topk.hip
 ssw_status stage_query(ssw_index *idx, const float *q_host);
 ssw_status do_select(ssw_index *idx, const float *scores, int32_t k, SelectDest dest, hipStream_t stream);
+ssw_status do_select_deep(ssw_index *idx, const float *scores, int32_t k, SelectDest dest, hipStream_t stream);
 ssw_status install_excluded(ssw_index *idx, const int64_t *excluded_images, int64_t n_excluded, hipStream_t stream);
 ssw_status topk_enqueue(ssw_index *idx, const float *q_host, const float *scores, hipStream_t stream,
                         const int64_t *excluded_images, int64_t n_excluded, int32_t k);

@@ -37,7 +37,7 @@ ssw_status ssw::do_select(ssw_index *idx, const float *scores, int32_t k, Select
 }
 
 // the deep path over what the last do_select of `scores` left (the per-image maxima are still in the workspace)
-static ssw_status do_select_deep(ssw_index *idx, const float *scores, int32_t k, SelectDest dest, hipStream_t stream) {
+ssw_status ssw::do_select_deep(ssw_index *idx, const float *scores, int32_t k, SelectDest dest, hipStream_t stream) {
     const float *values = idx->has_map ? idx->ws.img_score : scores;
     const uint32_t *best = idx->has_map ? idx->ws.img_best : nullptr;
     return launch_select_topk_deep(idx->ws, values, idx->n_images, best, k, dest, idx->device, stream);

@@ -462,8 +462,10 @@ __device__ __forceinline__ uint64_t *select_sorted_desc(uint64_t *s, int p, int 
 //   selection: msg_out = this rank's message -- keys made global (key - image_offset: the low word is
 //     0xFFFFFFFF - id) at [0, k), best rows + row_offset at [k_max, k_max + k) when with_best, and the word
 //     count | overflow << 32 at [msg_len - 1];
-//   merge (from_msgs): the lists ARE such messages (stride msg_len): a list's count is the low word of its last entry,
-//     its overflow flag goes to flags_out[l] and is OR-ed into flags_seen.
+//   merge (from_msgs): the lists ARE such messages (list_stride words apart, msg_len long): a list's count is the low
+//     word of its last entry, its overflow flag goes to flags_out[l] and is OR-ed into flags_seen.  A grid of several
+//     workgroups merges a chunk of queries (launch_merge_msgs_batch): workgroup b takes the messages that start
+//     b * msg_len words into each list's block and owns row b of the outputs.
 __global__ __launch_bounds__(1024) void k_final(const uint64_t *__restrict__ keys_in, int n_lists,
                                                 int list_stride, const int32_t *__restrict__ counts,
                                                 const uint32_t *__restrict__ ncand_ptr,
@@ -476,6 +478,14 @@ __global__ __launch_bounds__(1024) void k_final(const uint64_t *__restrict__ key
     extern __shared__ uint64_t s[];  // FINAL_CAP entries + FINAL_CAP / 2 for the halvings
     const int t = threadIdx.x;
     int n = 0;
+    long long *flags_row = x.flags_out;
+    if (x.from_msgs) {  // this workgroup's query of the chunk (the single merge: query 0 of 1)
+        const int64_t b = blockIdx.x;
+        keys_in += b * x.msg_len;
+        keys_out += b * x.k_max;
+        count_out += b;
+        if (flags_row) flags_row += b * n_lists;
+    }
     if (x.values_all != nullptr) {
         // few images (m <= FINAL_CAP: an LVIS-category subset has ~1 100): no histograms, no candidate pass -- every
         // image's composite key goes straight into the selection, excluded ones as 0 (below every real key)
@@ -517,7 +527,7 @@ __global__ __launch_bounds__(1024) void k_final(const uint64_t *__restrict__ key
     } else {
         for (int l = 0; l < n_lists; ++l) {
             // lists arrive sorted (descending): only a list's first k keys can reach the global top-k
-            const int have = x.from_msgs ? (int)(keys_in[(int64_t)l * list_stride + list_stride - 1] & 0xffffffffull)
+            const int have = x.from_msgs ? (int)(keys_in[(int64_t)l * list_stride + x.msg_len - 1] & 0xffffffffull)
                                          : counts[l];
             const int c = max(0, min(min(have, x.from_msgs ? x.k_max : list_stride), k));
             if (n + c > FINAL_CAP) break;  // launcher guarantees n_lists * min(stride, k) <= FINAL_CAP
@@ -580,11 +590,12 @@ __global__ __launch_bounds__(1024) void k_final(const uint64_t *__restrict__ key
     if (t == 0 && x.from_msgs) {
         long long any = 0;
         for (int l = 0; l < n_lists; ++l) {
-            const long long f = (long long)(keys_in[(int64_t)l * list_stride + list_stride - 1] >> 32);
-            if (x.flags_out) x.flags_out[l] = f;
+            const long long f = (long long)(keys_in[(int64_t)l * list_stride + x.msg_len - 1] >> 32);
+            if (flags_row) flags_row[l] = f;
             any |= f;
         }
-        if (x.flags_seen) *x.flags_seen |= any;
+        // (an atomic: the workgroups of a chunk's merge share the word)
+        if (x.flags_seen && any) atomicOr(reinterpret_cast<unsigned long long *>(x.flags_seen), (unsigned long long)any);
     }
     if (x.host_seq != 0) {  // the packed block is host memory: release everything, then the word the host spins on
         __threadfence_system();
@@ -728,9 +739,9 @@ static ssw_status final_lds_ready() {
 
 // With an exchange target attached (ssw_index_set_exchange_target) k_final writes k keys -- and k best rows from slot
 // k_max on -- into the rank's message: a k beyond k_max would run over the count word and past the send buffer.
-static ssw_status exchange_fits(const SelectWorkspace &ws, int32_t k) {
-    if (ws.xchg.msg_out != nullptr && k > ws.xchg.k_max) {
-        set_error("topk: k=%d exceeds the exchange target's k_max=%d", k, ws.xchg.k_max);
+static ssw_status exchange_fits(const FinalExchange &x, int32_t k) {
+    if (x.msg_out != nullptr && k > x.k_max) {
+        set_error("topk: k=%d exceeds the exchange target's k_max=%d", k, x.k_max);
         return SSW_ERR_INVALID;
     }
     return SSW_OK;
@@ -743,7 +754,7 @@ ssw_status launch_select_small(SelectWorkspace &ws, const float *row_scores, con
         set_error("select_small: n_images=%lld k=%d outside the one-launch path", (long long)n_images, k);
         return SSW_ERR_INVALID;
     }
-    SSW_TRY(exchange_fits(ws, k));
+    SSW_TRY(exchange_fits(ws.xchg, k));
     FinalExchange x = ws.xchg;
     x.values_all = row_scores;
     x.m_all = n_images;
@@ -765,7 +776,7 @@ ssw_status launch_select_small(SelectWorkspace &ws, const float *row_scores, con
 // the packed block and the side outputs of k_final for one selection
 static FinalExchange final_outputs(const SelectWorkspace &ws, SelectDest dest, unsigned char **packed) {
     *packed = dest.host_packed ? dest.host_packed : ws.packed;
-    FinalExchange x = dest.message ? ws.xchg : FinalExchange();
+    FinalExchange x = dest.target ? *dest.target : dest.message ? ws.xchg : FinalExchange();
     x.host_seq = dest.host_packed ? dest.seq : 0u;
     return x;
 }
@@ -781,7 +792,7 @@ ssw_status launch_select_topk(SelectWorkspace &ws, const float *values, int64_t 
         set_error("topk: %lld images exceed the 32-bit id space of one shard", (long long)m);
         return SSW_ERR_UNSUPPORTED;
     }
-    SSW_TRY(exchange_fits(ws, k));
+    SSW_TRY(exchange_fits(dest.target ? *dest.target : ws.xchg, k));
     const uint32_t *excl = ws.excl_dirty ? ws.excl_bits : nullptr;
     unsigned char *packed = nullptr;
     FinalExchange xg = final_outputs(ws, dest, &packed);
@@ -830,7 +841,7 @@ ssw_status launch_select_topk_deep(SelectWorkspace &ws, const float *values, int
         set_error("topk: k=%d outside [1, %d]", k, SSW_MAX_TOPK);
         return SSW_ERR_INVALID;
     }
-    SSW_TRY(exchange_fits(ws, k));
+    SSW_TRY(exchange_fits(dest.target ? *dest.target : ws.xchg, k));
     const uint32_t *excl = ws.excl_dirty ? ws.excl_bits : nullptr;
     const int g = grid_for(m, device);
     static const int digit_shift[6] = {52, 40, 32, 20, 8, 0};
@@ -892,10 +903,11 @@ ssw_status launch_merge_topk(const uint64_t *keys_in, int32_t n_lists, int32_t l
     return SSW_OK;
 }
 
-// the merge side of the sharded exchange: the gathered messages themselves are the lists
-ssw_status launch_merge_msgs(const uint64_t *msgs, int32_t world, int32_t k_max, int32_t with_best, int32_t k,
-                             uint64_t *keys_out, int32_t *count_out, long long *flags_out, long long *flags_seen,
-                             hipStream_t stream) {
+// the merge side of the sharded exchange: the gathered messages themselves are the lists.  One workgroup per query of a
+// chunk; the single merge is the chunk of one query whose lists lie msg_len words apart.
+ssw_status launch_merge_msgs_batch(const uint64_t *msgs, int32_t world, int64_t rank_stride, int32_t nq, int32_t k_max,
+                                   int32_t with_best, int32_t k, uint64_t *keys_out, int32_t *counts_out,
+                                   long long *flags_out, long long *flags_seen, hipStream_t stream) {
     if (k < 1 || k > SSW_MAX_TOPK || k_max < k) {
         set_error("merge: k=%d outside [1, min(%d, k_max = %d)]", k, SSW_MAX_TOPK, k_max);
         return SSW_ERR_INVALID;
@@ -911,13 +923,25 @@ ssw_status launch_merge_msgs(const uint64_t *msgs, int32_t world, int32_t k_max,
     x.msg_len = (with_best ? 2 : 1) * k_max + 1;
     x.flags_out = flags_out;
     x.flags_seen = flags_seen;
+    if (nq < 1 || rank_stride < (int64_t)nq * x.msg_len || rank_stride > (int64_t)INT32_MAX) {
+        set_error("merge: nq=%d queries of %d words do not fit a rank stride of %lld words", nq, x.msg_len,
+                  (long long)rank_stride);
+        return SSW_ERR_INVALID;
+    }
     SSW_TRY(final_lds_ready());
-    hipLaunchKernelGGL(k_final, dim3(1), dim3(1024), FINAL_LDS_BYTES, stream, msgs, (int)world,
-                       (int)x.msg_len, (const int32_t *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
-                       (int)k, (const uint32_t *)nullptr, keys_out, count_out, (uint32_t *)nullptr,
+    hipLaunchKernelGGL(k_final, dim3((unsigned)nq), dim3(1024), FINAL_LDS_BYTES, stream, msgs, (int)world,
+                       (int)rank_stride, (const int32_t *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
+                       (int)k, (const uint32_t *)nullptr, keys_out, counts_out, (uint32_t *)nullptr,
                        (unsigned char *)nullptr, x);
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
+}
+
+ssw_status launch_merge_msgs(const uint64_t *msgs, int32_t world, int32_t k_max, int32_t with_best, int32_t k,
+                             uint64_t *keys_out, int32_t *count_out, long long *flags_out, long long *flags_seen,
+                             hipStream_t stream) {
+    return launch_merge_msgs_batch(msgs, world, (int64_t)(with_best ? 2 : 1) * k_max + 1, 1, k_max, with_best, k, keys_out,
+                                   count_out, flags_out, flags_seen, stream);
 }
 
 ssw_status launch_gather_f32(const float *src, const int64_t *idx_dev, int64_t n, float *dst,

@@ -310,6 +310,9 @@ struct FinalExchange {
     int32_t k_max = 0, with_best = 0, msg_len = 0;
     int32_t from_msgs = 0;         // merge: the input lists are messages
     long long *flags_out = nullptr, *flags_seen = nullptr;
+    // merge of a chunk of queries (launch_merge_msgs_batch): workgroup b merges query b's messages, which start
+    // b * msg_len words into every rank's block; its keys go to row b of [nq, k_max], its count to word b, its flags to
+    // row b of [nq, n_lists].  The single merge is the grid of one workgroup.
     // few images (<= the sort's capacity): the selection is this one kernel over all of them
     const float *values_all = nullptr;
     int64_t m_all = 0;
@@ -354,6 +357,7 @@ struct SelectDest {
     unsigned char *host_packed = nullptr;  // pinned host block (device view) instead of ws.packed ...
     unsigned seq = 0;                      // ... whose header word 3 receives seq, released to the host
     bool message = true;                   // write the message of ws.xchg too, when a target is attached
+    const FinalExchange *target = nullptr; // ... or the message of this target instead (a slot of the batch target)
 };
 
 #ifdef SSW_DEBUG_HOOKS
@@ -388,6 +392,11 @@ ssw_status launch_merge_topk(const uint64_t *keys_in, int32_t n_lists, int32_t l
 ssw_status launch_merge_msgs(const uint64_t *msgs, int32_t world, int32_t k_max, int32_t with_best, int32_t k,
                              uint64_t *keys_out, int32_t *count_out, long long *flags_out, long long *flags_seen,
                              hipStream_t stream);
+// the merge of nq queries in one launch: rank r's message for query b starts at msgs + r * rank_stride + b * msg_len;
+// keys_out [nq, k_max], counts_out [nq], flags_out [nq, world]
+ssw_status launch_merge_msgs_batch(const uint64_t *msgs, int32_t world, int64_t rank_stride, int32_t nq, int32_t k_max,
+                                   int32_t with_best, int32_t k, uint64_t *keys_out, int32_t *counts_out,
+                                   long long *flags_out, long long *flags_seen, hipStream_t stream);
 ssw_status launch_gather_f32(const float *src, const int64_t *idx_dev, int64_t n, float *dst,
                              hipStream_t stream);
 

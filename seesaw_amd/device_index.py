@@ -332,6 +332,31 @@ class DeviceIndex:
         """exact selection for the mass-tie case (result_ptrs' overflow word set): same result buffers"""
         _lib.call("ssw_index_select_deep_dev", self._h, int(k))
 
+    def set_exchange_target_batch(self, dev_msgs_ptr: int, n_slots: int, k_max: int, with_best: bool, image_offset: int = 0,
+                                  row_offset: int = 0):
+        """attach (0 / None: detach) the message block [n_slots, msg_len] u64 that `topk_batch_dev` fills, one slot a
+        query (ssw_index_set_exchange_target_batch); the single exchange target is a state of its own beside it"""
+        _lib.call("ssw_index_set_exchange_target_batch", self._h, ctypes.c_void_p(dev_msgs_ptr) if dev_msgs_ptr else None,
+                  int(n_slots), int(k_max), int(bool(with_best)), int(image_offset), int(row_offset))
+
+    def topk_batch_dev(self, Q: np.ndarray, k: int, excluded=None, first_slot: int = 0):
+        """`topk_batch` that stays on the device (ssw_index_topk_batch_dev; enqueue only): the rows are read once per
+        chunk of queries and query b's selection writes its exchange message into slot `first_slot + b` of the attached
+        block.  An overflowed selection is not repaired: its flag travels in the slot (`topk_slot_deep_dev`).  The
+        handle is left as after `topk_dev` of the last query with its exclusion list."""
+        Q = self._queries(Q)
+        nq = Q.shape[0]
+        ids, offsets = self._excluded_batch(excluded, nq)
+        _lib.call("ssw_index_topk_batch_dev", self._h, _ptr(Q), nq, _ptr(ids), _ptr(offsets), int(k), int(first_slot))
+
+    def topk_slot_deep_dev(self, q: np.ndarray, k: int, excluded: Optional[Iterable[int]], slot: int):
+        """the repair of one flagged query of a batch (ssw_index_topk_slot_deep_dev): full scan of q, exact deep
+        selection, message into `slot`; synchronises inside"""
+        qa = self._query(q)
+        ex = None if excluded is None else np.ascontiguousarray(np.fromiter(excluded, dtype=np.int64))
+        n_ex = 0 if ex is None else ex.shape[0]
+        _lib.call("ssw_index_topk_slot_deep_dev", self._h, _ptr(qa), _ptr(ex) if n_ex else None, n_ex, int(k), int(slot))
+
     def scan_dev(self, q_dev_ptr: int):
         _lib.call("ssw_index_scan_dev", self._h, ctypes.c_void_p(q_dev_ptr))
 

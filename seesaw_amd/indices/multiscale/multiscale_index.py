@@ -331,8 +331,8 @@ class MultiscaleIndex(AccessMethod):
         A batch always scans in full precision: on an index large enough for the single `query` to be pruned
         (>= 2^22 rows) a small batch is expected to be slower per query than the loop (`topk_batch` against the
         pruned `topk` crosses over at nq = 4 to 8; this method itself is not measured yet, DESIGN.md section 4,
-        "Batched multiscale query") -- callers who want the pruned single path call `query`.  The `vector2` form, the
-        pruned batch and the sharded index remain a follow-up."""
+        "Batched multiscale query") -- callers who want the pruned single path call `query`.  The `vector2` form and the
+        pruned batch remain a follow-up (the sharded index batches its first stage: `ShardedMultiscaleIndex`)."""
         vectors = list(vectors)
         excludes = [None] * len(vectors) if excludes is None else list(excludes)
         if len(excludes) != len(vectors):

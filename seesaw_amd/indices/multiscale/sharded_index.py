@@ -63,7 +63,12 @@ class DeviceShard:
         self.best = torch.as_tensor(_DevArray(best_ptr, (_lib.SSW_MAX_TOPK,), "<i4"), device=self.tdev)
 
     def select(self, q: np.ndarray, k: int, excluded_local: np.ndarray):
-        """scan + top-k of the slice; -> (keys int64 [>=k], (count, overflow) int32 [2], best local rows int64 [>=k])"""
+        """scan + top-k of the slice; -> (keys int64 [>=k], (count, overflow) int32 [2], best local rows int64 [>=k]).
+        q None: the top-k of the scores that are resident (DeviceIndex.topk(q=None))"""
+        if q is None:
+            self.index.set_excluded(excluded_local)
+            self.index.topk_dev(0, k)
+            return self.keys, self.count, self.best.to(self.torch.int64) & 0xFFFFFFFF
         qd = self.torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32).reshape(-1)).to(self.tdev)
         self.index.set_excluded(excluded_local)
         self.index.topk_dev(qd.data_ptr(), k)
@@ -73,6 +78,15 @@ class DeviceShard:
     def select_deep(self, k: int):
         self.index.select_deep_dev(k)
         return self.keys, self.count, self.best.to(self.torch.int64) & 0xFFFFFFFF
+
+    def select_batch(self, Q: np.ndarray, k: int, excluded_locals):
+        """scan + top-k of the slice for a chunk of queries, the rows read once per chunk of up to 16 (enqueue only):
+        query b's message goes into slot b of the block `ShardedTopK.attach_batch` attached to `self.index`"""
+        self.index.topk_batch_dev(Q, k, excluded=excluded_locals)
+
+    def select_slot_deep(self, q: np.ndarray, k: int, excluded_local: np.ndarray, slot: int):
+        """the exact repair of one flagged query of the chunk: rescan, deep selection, message into `slot`"""
+        self.index.topk_slot_deep_dev(q, k, excluded_local, slot)
 
     def select_scores(self, row_scores: np.ndarray, k: int, excluded_local: np.ndarray):
         """top-k of the slice by caller-supplied per-row scores (f32, -inf = skip): the label-propagation ranking"""
@@ -134,12 +148,13 @@ class ShardedMultiscaleIndex(MultiscaleIndex):
     def __init__(self, *, embedding, vectors: Optional[np.ndarray], vector_meta: pd.DataFrame, rank: int, world: int,
                  local_vectors: Optional[np.ndarray] = None, device: int = 0, group=None, k_max: int = 1024,
                  comm_device=None, shard_factory=DeviceShard, merge=None, path: str = None, excluded: BitMap = None,
-                 vector_dtype: str = "float32"):
+                 vector_dtype: str = "float32", n_slots: int = 16):
         """vectors: the full [N, 512] host array (sliced here) or None with `local_vectors` = this rank's rows.
         comm_device: where the collective's tensors live -- None = the shard's GPU (backend nccl = RCCL); "cpu"
         for a gloo group (the messages make a host round trip; used by the tests on one-GPU boxes)."""
         self.rank, self.world, self.group = int(rank), int(world), group
         self._k_max, self._comm_device, self._shard_factory, self._merge = int(k_max), comm_device, shard_factory, merge
+        self._n_slots = int(n_slots)  # queries of one batched exchange (query_batch)
         from ...device_index import round_vectors
         self._local_vectors = None if local_vectors is None else round_vectors(local_vectors, vector_dtype)
         serve_rows = vectors is None
@@ -178,12 +193,13 @@ class ShardedMultiscaleIndex(MultiscaleIndex):
         self._xchg = ShardedTopK(rank=self.rank, world=self.world, device=compute_dev, image_offset=self.img_lo,
                                  k_max=self._k_max, group=self.group, with_best=True, comm_device=self._comm_device, **kw)
         self._dev = None  # there is no whole-matrix device index
+        self.query_batch = self._query_batch_sharded  # (see the class attribute of that name)
 
     # ---- stage 1 ------------------------------------------------------------------------
     def _prelim(self, *, vector, topk_dbidx, exclude_dbidx=None, force_exact=False):
         cand = self._select_and_exchange(lambda shard, k_local, mine: shard.select(vector, k_local, mine), topk_dbidx,
                                          exclude_dbidx)
-        if not isinstance(cand, tuple):
+        if not isinstance(cand, tuple) and vector is not None:
             self._resident_q = np.asarray(vector, dtype=np.float32).reshape(-1).copy()
         return cand
 
@@ -323,8 +339,76 @@ class ShardedMultiscaleIndex(MultiscaleIndex):
         return {"dbidxs": self._dbidx[positions].astype("int"),
                 "activations": ActivationFrames(self._box[rows], self._row_dbidx[rows], np.asarray(scores))}
 
-    # one query at a time: there is no whole-matrix device index (`_dev`) for MultiscaleIndex's device batch
+    # The class keeps the per-query loop under this name: there is no whole-matrix device index (`_dev`) for
+    # MultiscaleIndex's device batch, and `AccessMethod.query_batch(index, ...)` stays the loop that the batched form is
+    # compared against.  Every INSTANCE answers `index.query_batch(...)` with `_query_batch_sharded` (bound in
+    # `_init_device`), which falls back to this loop for whatever it does not serve.
     query_batch = AccessMethod.query_batch
+
+    def _query_batch_sharded(self, *, topk, vectors, excludes=None, **kwargs):
+        """`index.query_batch`: `[query(vector=v, topk=topk, exclude=e, **kwargs) for v, e in zip(vectors, excludes)]`,
+        entry by entry identical to it.  For `agg_method="plain_score"` without `vector2` every rank reads its rows once per chunk of up
+        to 16 queries (`DeviceShard.select_batch`) and the ranks exchange once per group of `n_slots` queries: one
+        all-gather and one merge launch (`ShardedTopK.exchange_fused_batch`), one host read of counts and flags.  A
+        flagged (query, rank) is repaired by a rescan with the deep selection on that rank, after which all ranks repeat
+        the group's exchange once.  The entry rules are `MultiscaleIndex.query_batch`'s: entries without a vector or
+        with an exclusion set that covers the index go through `query`; one k = the largest shortlist, every query
+        keeps its own first min(shortlist_size, included) candidates.  Everything else -- other aggregation methods,
+        `vector2`, a shard factory without `select_batch` -- is the per-query loop; the second stage over a sharded
+        batch remains a follow-up.  Afterwards `_resident_q` names the last query."""
+        vectors = list(vectors)
+        excludes = [None] * len(vectors) if excludes is None else list(excludes)
+        if len(excludes) != len(vectors):
+            raise ValueError(f"excludes has {len(excludes)} entries for {len(vectors)} vectors")
+        if kwargs.get("agg_method") != "plain_score" or kwargs.get("vector2") is not None \
+                or "shortlist_size" not in kwargs or not hasattr(self._shard_factory, "select_batch"):
+            return AccessMethod.query_batch(self, topk=topk, vectors=vectors, excludes=excludes, **kwargs)
+        shortlist_size = kwargs["shortlist_size"]
+        if shortlist_size is None:
+            shortlist_size = topk * 5
+        n = self._dbidx.shape[0]
+        out = [None] * len(vectors)
+        excl_pos = [None if v is None else self._excluded_positions(e) for v, e in zip(vectors, excludes)]
+        batch = [i for i, v in enumerate(vectors) if v is not None and excl_pos[i].shape[0] < n]
+        for i in range(len(vectors)):
+            if i not in batch:
+                out[i] = self.query(topk=topk, vector=vectors[i], exclude=excludes[i], **kwargs)
+        if not batch:
+            return out
+        ks = [min(int(shortlist_size), n - excl_pos[i].shape[0]) for i in batch]
+        k = max(ks)
+        assert k <= self._k_max, f"shortlist {k} exceeds the exchange buffers (k_max={self._k_max})"
+        Q = np.stack([np.asarray(vectors[i], dtype=np.float32).reshape(-1) for i in batch])
+        mine = [p[(p >= self.img_lo) & (p < self.img_hi)] - self.img_lo for p in (excl_pos[i] for i in batch)]
+        x = self._xchg
+        if getattr(x, "send_batch", None) is None:
+            x.attach_batch(self._shard.index if self._shard is not None else None, self._n_slots, row_offset=self.row_lo)
+        k_local = min(k, self.n_local_images)  # (the merge takes k; a shard sends what it has)
+        from ...device_index import decode_keys
+        for g in range(0, len(batch), self._n_slots):
+            Qg, nq = Q[g:g + self._n_slots], len(batch[g:g + self._n_slots])
+            if self._shard is not None:
+                self._shard.select_batch(Qg, k_local, mine[g:g + nq])
+            else:
+                x.pack_empty_batch(nq)
+            keys, counts = x.exchange_fused_batch(nq, k)
+            over = x.overflowed_batch()  # host read: synchronises
+            if over:  # the same list on every rank: the flagged ones redo their query exactly, all re-exchange
+                for b, r in over:
+                    if r == self.rank:
+                        self._shard.select_slot_deep(Qg[b], k_local, mine[g + b], b)
+                keys, counts = x.exchange_fused_batch(nq, k)
+                assert not x.overflowed_batch()
+                x.reset_overflow_seen()
+            keys_h, counts_h, gathered = keys.cpu().numpy().view(np.uint64), counts.cpu().numpy(), x.gathered_batch()
+            for b in range(nq):
+                k_i = ks[g + b]
+                merged = keys_h[b, :min(int(counts_h[b]), k_i)]
+                pos, scores = decode_keys(merged)
+                cand = _Candidates(self._dbidx[pos], scores, pos, x.best_rows_of(merged, query=b, gathered=gathered))
+                out[batch[g + b]] = self._activations_from_best(cand, topk)
+        self._resident_q = Q[-1].copy()
+        return out
 
     def query(self, *, vector, vector2=None, topk, shortlist_size, exclude=None, force_exact=False, **kwargs):
         if shortlist_size is None:

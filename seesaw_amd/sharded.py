@@ -51,6 +51,45 @@ class _DevArray:
                                          "data": (int(ptr), False), "version": 2}
 
 
+def pack_message_block(lists, k_max: int, with_best: bool) -> np.ndarray:
+    """the exchange messages of a chunk as one all-gather leaves them: `lists[r][b]` = (keys u64 [c], best rows i64 [c]
+    or None, overflow flag) of rank r for query b -> u64 [world, nq, msg_len], msg_len = (2 if with_best else 1) * k_max
+    + 1: keys at [0, c), best rows at [k_max, k_max + c), count | overflow << 32 in the last word
+    (ssw_index_set_exchange_target)"""
+    world, nq = len(lists), len(lists[0])
+    msg_len = (2 if with_best else 1) * k_max + 1
+    block = np.zeros((world, nq, msg_len), dtype=np.uint64)
+    for r in range(world):
+        assert len(lists[r]) == nq
+        for b, (keys, best, flag) in enumerate(lists[r]):
+            keys = np.asarray(keys, dtype=np.uint64)
+            c = keys.shape[0]
+            assert c <= k_max
+            block[r, b, :c] = keys
+            if with_best:
+                block[r, b, k_max:k_max + c] = np.asarray(best, dtype=np.int64).view(np.uint64)
+            block[r, b, msg_len - 1] = np.uint64(c) | (np.uint64(int(flag)) << np.uint64(32))
+    return block
+
+
+def unpack_message_block(block: np.ndarray, k_max: int, with_best: bool):
+    """inverse of pack_message_block: [world, nq, msg_len] (u64 or its i64 bit pattern) -> lists[r][b] = (keys u64 [c],
+    best rows i64 [c] or None, overflow flag)"""
+    block = np.ascontiguousarray(block).view(np.uint64)
+    msg_len = (2 if with_best else 1) * k_max + 1
+    assert block.ndim == 3 and block.shape[2] == msg_len, block.shape
+    out = []
+    for r in range(block.shape[0]):
+        row = []
+        for b in range(block.shape[1]):
+            word = int(block[r, b, msg_len - 1])
+            c = word & 0xFFFFFFFF
+            best = block[r, b, k_max:k_max + c].view(np.int64).copy() if with_best else None
+            row.append((block[r, b, :c].copy(), best, word >> 32))
+        out.append(row)
+    return out
+
+
 def merge_keys_hip(device: int, stream_ptr: int, keys, counts, k: int, out_keys, out_count):
     """Global top-k of `world` sorted key lists on the GPU (ssw_topk_merge_dev)."""
     world, stride = keys.shape
@@ -159,6 +198,80 @@ class ShardedTopK:
                   ctypes.c_void_p(self.flags.data_ptr()), ctypes.c_void_p(self.flags_seen.data_ptr()))
         return self.out_keys, self.out_count
 
+    # ---- a chunk of queries per exchange ------------------------------------------------------------------
+    def attach_batch(self, dev_index, n_slots: int = 16, row_offset: int = 0):
+        """the batched form's buffers, beside the single query's: `send_batch` [n_slots, msg_len] is the message block
+        the index's `topk_batch_dev` fills, one slot a query (ssw_index_set_exchange_target_batch); `all_batch` receives
+        one all-gather of a chunk, `out_keys_batch` [n_slots, k_max], `out_counts_batch` [n_slots] and `flags_batch`
+        [n_slots, world] its merge.  dev_index None: a rank without images, which sends count-0 slots
+        (`pack_empty_batch`)."""
+        torch = self.torch
+        dev = self.send_buf.device
+        assert self.send_buf.is_cuda
+        self.n_slots = int(n_slots)
+        self.send_batch = torch.zeros((self.n_slots, self.msg_len), dtype=torch.int64, device=dev)
+        self.all_batch = torch.zeros(self.world * self.n_slots * self.msg_len, dtype=torch.int64, device=dev)
+        self.out_keys_batch = torch.zeros((self.n_slots, self.k_max), dtype=torch.int64, device=dev)
+        self.out_counts_batch = torch.zeros(self.n_slots, dtype=torch.int32, device=dev)
+        self.flags_batch = torch.zeros((self.n_slots, self.world), dtype=torch.int64, device=dev)
+        self._batch_nq = 0
+        if dev_index is not None:
+            dev_index.set_exchange_target_batch(self.send_batch.data_ptr(), self.n_slots, self.k_max, self.with_best,
+                                                self.image_offset, int(row_offset))
+        self._attached_batch = dev_index
+        return self
+
+    def pack_empty_batch(self, nq: int):
+        """a rank without images still takes part in the chunk's collective: count 0 in every slot"""
+        self.send_batch[:nq, self.msg_len - 1] = 0
+        return self.send_batch
+
+    def gather_batch(self, nq: int):
+        """one all-gather of the chunk's nq messages per rank into all_batch, laid out [world, nq, msg_len]: the three
+        routes of `gather`"""
+        words = nq * self.msg_len
+        send, recv = self.send_batch.view(-1)[:words], self.all_batch[:self.world * words]
+        if self.world > 1 or self.force_collective:
+            import torch.distributed as dist
+            if self.comm_device is None or self.comm_device == send.device:
+                dist.all_gather_into_tensor(recv, send, group=self.group)
+            else:
+                out = self.torch.empty(self.world * words, dtype=self.torch.int64, device=self.comm_device)
+                dist.all_gather_into_tensor(out, send.to(self.comm_device), group=self.group)
+                recv.copy_(out)
+        else:
+            recv.copy_(send)
+
+    def exchange_fused_batch(self, nq: int, k: int):
+        """the attached index has just run topk_batch_dev(Q[:nq], k) into slots [0, nq): ONE all-gather of nq * msg_len
+        words per rank and ONE merge launch for the chunk (ssw_topk_merge_msgs_batch_dev, one workgroup a query) ->
+        (out_keys_batch[:nq], out_counts_batch[:nq]); the overflow flags of every (query, rank) go to flags_batch"""
+        torch = self.torch
+        assert getattr(self, "send_batch", None) is not None, "attach_batch(dev_index) first"
+        if not 1 <= nq <= self.n_slots:
+            raise ValueError(f"nq={nq} outside [1, n_slots={self.n_slots}] of this exchange")
+        if not 1 <= k <= self.k_max:
+            raise ValueError(f"k={k} outside [1, k_max={self.k_max}] of this exchange")
+        stream_ptr = torch.cuda.current_stream().cuda_stream
+        words = nq * self.msg_len
+        if getattr(self, "_comm", None):
+            _lib.call("ssw_topk_allgather", self._comm, ctypes.c_void_p(stream_ptr),
+                      ctypes.c_void_p(self.send_batch.data_ptr()), ctypes.c_void_p(self.all_batch.data_ptr()), words)
+        else:
+            self.gather_batch(nq)
+        _lib.call("ssw_topk_merge_msgs_batch_dev", int(self.all_batch.device.index), ctypes.c_void_p(stream_ptr),
+                  ctypes.c_void_p(self.all_batch.data_ptr()), self.world, words, int(nq), self.k_max, int(self.with_best),
+                  int(k), ctypes.c_void_p(self.out_keys_batch.data_ptr()), ctypes.c_void_p(self.out_counts_batch.data_ptr()),
+                  ctypes.c_void_p(self.flags_batch.data_ptr()), ctypes.c_void_p(self.flags_seen.data_ptr()))
+        self._batch_nq = int(nq)
+        return self.out_keys_batch[:nq], self.out_counts_batch[:nq]
+
+    def overflowed_batch(self):
+        """[(query, rank), ...] whose local selection overflowed its fast path in the last batched exchange (host read:
+        synchronises once).  Every rank sees the same list."""
+        f = self.flags_batch[:self._batch_nq].cpu().numpy()
+        return [(int(b), int(r)) for b, r in zip(*np.nonzero(f))]
+
     def time_collective(self, on: bool = True):
         """bracket every exchange_fused collective with HIP events (two event records per step on the stream)"""
         self._coll_events = [] if on else None
@@ -223,10 +336,20 @@ class ShardedTopK:
         self.gather()
         return self.merge_gathered(k)
 
-    def best_rows_of(self, merged_keys: np.ndarray) -> np.ndarray:
-        """the best-row number every rank sent along with each of the merged keys (keys are unique)"""
+    def gathered_batch(self) -> np.ndarray:
+        """host copy of what the last batched all-gather left: i64 [world, nq, msg_len] (synchronises)"""
+        nq = self._batch_nq
+        return self.all_batch[:self.world * nq * self.msg_len].view(self.world, nq, self.msg_len).cpu().numpy()
+
+    def best_rows_of(self, merged_keys: np.ndarray, query: Optional[int] = None, gathered=None) -> np.ndarray:
+        """the best-row number every rank sent along with each of the merged keys (keys are unique); `query`: of that
+        query of the last batched exchange instead of the last single one (`gathered`: a `gathered_batch()` the caller
+        already holds, which saves the read per query)"""
         assert self.with_best
-        buf = self.all_buf.cpu().numpy()
+        if query is None:
+            buf = self.all_buf.cpu().numpy()
+        else:
+            buf = (self.gathered_batch() if gathered is None else gathered)[:, query]
         counts = (buf[:, self.msg_len - 1] & 0xFFFFFFFF).astype(np.int64)
         keys = np.concatenate([buf[r, :counts[r]] for r in range(self.world)]).view(np.uint64)
         rows = np.concatenate([buf[r, self.k_max:self.k_max + counts[r]] for r in range(self.world)])
@@ -257,7 +380,7 @@ class ShardedSyntheticIndex:
 
     def __init__(self, n_total: int, dim: int, seed: int, rank: int, world: int,
                  local_device: int, k_max: int = 128, group=None, force_collective: bool = False, comm_device=None,
-                 vector_dtype: str = "float32"):
+                 vector_dtype: str = "float32", n_slots: int = 16):
         import torch
         from .device_index import DeviceIndex
         self.torch = torch
@@ -282,6 +405,7 @@ class ShardedSyntheticIndex:
         self.xchg.attach(self.local)
         if os.environ.get("SSW_C_COMM"):  # the collective through the library's own RCCL entry point
             self.xchg.use_c_comm()
+        self.n_slots = int(n_slots)  # queries of one batched exchange (topk_batch*); its buffers come with the first one
 
     def topk_async(self, q_dev_ptr: int, k: int):
         """scan + local select + all-gather + merge, all enqueued on the current stream.  The overflow flags
@@ -308,6 +432,45 @@ class ShardedSyntheticIndex:
         c = int(count.item())
         imgs, scores = decode_keys(keys[:c].cpu().numpy().view(np.uint64))
         return imgs, scores
+
+    def topk_batch_async(self, Q, k: int):
+        """`topk_async` for a chunk of nq <= n_slots host queries Q [nq, dim]: every shard reads its rows once per chunk
+        of up to 16 queries (DeviceIndex.topk_batch_dev), then ONE all-gather and ONE merge launch, all enqueued on the
+        current stream -> (keys [nq, k_max], counts [nq]) on the device.  The overflow flags travel with the messages;
+        check `xchg.assert_no_overflow_seen()` after synchronising."""
+        if not 1 <= k <= self.xchg.k_max:
+            raise ValueError(f"k={k} outside [1, k_max={self.xchg.k_max}] of this index's exchange")
+        Q = self.local._queries(Q)
+        if Q.shape[0] > self.n_slots:
+            raise ValueError(f"nq={Q.shape[0]} exceeds n_slots={self.n_slots}: topk_batch() cuts a batch into groups")
+        if getattr(self.xchg, "send_batch", None) is None:
+            self.xchg.attach_batch(self.local, self.n_slots)
+        self.local.topk_batch_dev(Q, k)
+        return self.xchg.exchange_fused_batch(Q.shape[0], k)
+
+    def topk_batch(self, Q, k: int):
+        """`[topk(q, k) for q in Q]` with the rows read once per chunk and one exchange per group of n_slots queries: a
+        list of (images, scores).  A flagged (query, rank) redoes that query exactly on that rank (a rescan: the chunk's
+        slabs are gone) and all ranks repeat the exchange once for the group."""
+        from .device_index import decode_keys
+        Q = self.local._queries(Q)
+        out = []
+        for g in range(0, Q.shape[0], self.n_slots):
+            Qg = Q[g:g + self.n_slots]
+            keys, counts = self.topk_batch_async(Qg, k)
+            self.torch.cuda.synchronize(self.device)
+            over = self.xchg.overflowed_batch()
+            if over:  # the same list on every rank
+                for b, r in over:
+                    if r == self.rank:
+                        self.local.topk_slot_deep_dev(Qg[b], k, None, b)
+                keys, counts = self.xchg.exchange_fused_batch(Qg.shape[0], k)
+                self.torch.cuda.synchronize(self.device)
+                assert not self.xchg.overflowed_batch()
+                self.xchg.reset_overflow_seen()
+            keys_h, counts_h = keys.cpu().numpy().view(np.uint64), counts.cpu().numpy()
+            out.extend(decode_keys(keys_h[b, :int(counts_h[b])]) for b in range(Qg.shape[0]))
+        return out
 
     def close(self):
         self.xchg.close_c_comm()
