@@ -1223,9 +1223,72 @@ def gen_tiling():
     save("tiling", **out)
 
 
+def gen_avg_score_edges():
+    """(ii-c) score_frame2 (multiscale_index.py:112-150) itself, one image at a time, on the seeded edge layouts of
+    tests/_rescore_helpers.py: images of 1 .. 2048 tiles (the device kernel has 256 threads and an LDS ceiling of 2048
+    tiles), zoom levels up to 31, exactly tied IoUs and scores, a zero-area box, NaN / +inf / -inf scores.  The inputs
+    regenerate from the helper's seed; recorded per mode are every image's best row (inside the image) and score, and the
+    per-tile aggregates of the images of at most 513 tiles (`agg_*`, concatenated in image order).
+    Modes `<weight>_<aug>_<dtype>_<scores>`: weight lm (level_max) | cw (cont_weighted); the three aug_larger modes;
+    f32 | f64 score columns; scores fin (finite) | ld (with the NaN / inf plants) | ldm (ld minus the helper's `minus`
+    vector, f32 only).  cont_weighted runs on the finite scores only.  The image of zero-area tiles is left out: with
+    every aggregate NaN the reference's frame is empty and its caller raises.  The pandas join of the 2048-tile image
+    (~1.5 M pairs) runs in seconds here, so every image is recorded from the full layout."""
+    import pandas as pd
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    try:
+        import _rescore_helpers as H
+    finally:
+        sys.path.pop(0)
+    msi = R.ref("seesaw.indices.multiscale.multiscale_index")
+    lay = H.Layout()
+    images = [p for p in range(lay.n_images) if p != lay.all_nan_position]
+    out = {"seed": np.asarray(H.SEED), "tile_counts": np.asarray([lay.tile_counts[p] for p in images], dtype=np.int64),
+           "agg_max_tiles": np.asarray(513)}
+    modes = [("lm", aug, dt, sc) for aug in H.AUGS for dt in ("f32", "f64") for sc in ("fin", "ld")]
+    modes += [("lm", aug, "f32", "ldm") for aug in H.AUGS]
+    modes += [("cw", aug, dt, "fin") for aug in H.AUGS for dt in ("f32", "f64")]
+    for weight, aug, dt, sc in modes:
+        dtype = np.float32 if dt == "f32" else np.float64
+        scores = lay.scores(dtype, loaded=sc != "fin")
+        if sc == "ldm":
+            scores = scores - lay.minus()
+        best_row, best_score, aggs = [], [], []
+        for p in images:
+            r = lay.rows(p)
+            b = lay.boxes[r]
+            meta = pd.DataFrame({"dbidx": np.full(b.shape[0], p, dtype=np.int64), "zoom_level": lay.zoom[r].astype(np.int16),
+                                 "x1": b[:, 0], "y1": b[:, 1], "x2": b[:, 2], "y2": b[:, 3], "score": scores[r]})
+            seen = {}
+            orig_assign = pd.DataFrame.assign
+
+            def assign(self, _o=orig_assign, **kw):  # the per-tile aggregates, as score_frame2 attaches them
+                if "unadjusted_score" in kw:
+                    seen["agg"] = np.asarray(_o(self, **kw).score.values).copy()
+                return _o(self, **kw)
+
+            pd.DataFrame.assign = assign
+            try:
+                tup = msi.score_frame2(meta, agg_method="avg_score", aug_larger=aug,
+                                       aug_weight={"lm": "level_max", "cw": "cont_weighted"}[weight])
+            finally:
+                pd.DataFrame.assign = orig_assign
+            assert tup.shape[0] == 1 and seen["agg"].dtype == dtype, (p, tup.shape, seen["agg"].dtype)
+            best_row.append(int(tup.index[0]))
+            best_score.append(tup.score.iloc[0])
+            if b.shape[0] <= 513:
+                aggs.append(seen["agg"])
+        tag = f"{weight}_{aug}_{dt}_{sc}"
+        out[f"row_{tag}"] = np.asarray(best_row, dtype=np.int64)
+        out[f"score_{tag}"] = np.asarray(best_score, dtype=dtype)
+        out[f"agg_{tag}"] = np.concatenate(aggs).astype(dtype)
+        print(tag, best_row)
+    save("avg_score_edges", **out)
+
+
 FAMILIES = {"tiling": gen_tiling, "sliding": gen_sliding, "lknn": gen_lknn, "scan_topk": gen_scan_topk, "multiscale_query": gen_multiscale_query, "labelprop": gen_labelprop,
             "rank_loss": gen_rank_loss, "logreg": gen_logreg, "multireg": gen_multireg, "bench_loop": gen_bench_loop,
-            "multiregneg": gen_multiregneg, "contweighted": gen_contweighted,
+            "multiregneg": gen_multiregneg, "contweighted": gen_contweighted, "avg_score_edges": gen_avg_score_edges,
             "c5_sequence": gen_c5_sequence, "multireg_det": gen_multireg_det}
 HEAVY = {"c5_sequence"}  # minutes each: regenerated only when named or with SSW_GOLDEN_ALL=1
 

@@ -296,42 +296,93 @@ def box_iou_f32(boxes: np.ndarray):
         return (inter / union).astype(np.float32)
 
 
+def _kahan_mean(values, dt=np.float32):
+    """pandas' groupby mean of a column of dtype `dt` (group_mean): NaN entries are skipped (no entry left: NaN);
+    Kahan-compensated sum in `dt` in row order, the compensation reset to 0 when an infinity turns it into NaN; one
+    division in `dt`"""
+    s, c, n = dt(0), dt(0), 0
+    with np.errstate(invalid="ignore", over="ignore"):
+        for x in values:
+            x = dt(x)
+            if x != x:
+                continue
+            y = dt(x - c)
+            t = dt(s + y)
+            c = dt(dt(t - s) - y)
+            if c != c:
+                c = dt(0)
+            s = t
+            n += 1
+        return dt(s / dt(n)) if n else dt(np.nan)
+
+
 def _kahan_mean_f32(values):
-    """pandas' groupby mean of a float32 column: Kahan-compensated f32 sum in row order, f32 division"""
-    s = np.float32(0)
-    c = np.float32(0)
-    for x in values:
-        y = np.float32(np.float32(x) - c)
-        t = np.float32(s + y)
-        c = np.float32(np.float32(t - s) - y)
-        s = t
-    return np.float32(s / np.float32(len(values)))
+    return _kahan_mean(values, np.float32)
 
 
-def avg_score_image(boxes: np.ndarray, zoom: np.ndarray, scores: np.ndarray, aug_larger: str):
-    """score_frame2 with aug_weight='level_max' for ONE image (multiscale_index.py:112-150): tile i's score becomes
-    the mean, over the zoom levels z allowed by aug_larger, of the score of the tile of level z overlapping i most
-    (first such tile on ties; only pairs with IoU > 0 take part).  -> (index of the first tile with the highest
-    aggregated score, that score f32, all aggregated scores)."""
+def avg_score_image(boxes: np.ndarray, zoom: np.ndarray, scores: np.ndarray, aug_larger: str, dtype=np.float32,
+                    aug_weight: str = "level_max"):
+    """score_frame2 for ONE image (multiscale_index.py:112-150); `dtype` is the score column's (float32 or float64: the
+    dtype pandas' group mean runs in); the IoUs are f32 either way, as the boxes are.
+    aug_weight='level_max': tile i's score becomes the mean, over the zoom levels z allowed by aug_larger, of the score of
+    the tile of level z overlapping i most (first such tile on ties; only pairs with IoU > 0 take part).
+      -> (index of the first tile with the highest aggregated score, that score, all aggregated scores), bit for bit.
+    aug_weight='cont_weighted': softmax(containment) weights over all joined partners -- a HIGH-PRECISION reference, not a
+    restatement: float64 throughout from the f32 IoU (which decides the partners) and the f32 containment.
+      -> (best, score f64, aggregates f64, P [T] partner counts, A [T] = sum_j w_ij |s_j|).
+    A tile without a partner aggregates to NaN; NaN aggregates never win; an image of NaN aggregates -> (0, NaN, ...)."""
+    assert aug_larger in ("all", "greater", "adjacent") and aug_weight in ("level_max", "cont_weighted")
+    dt = np.dtype(dtype).type
     iou = box_iou_f32(boxes)
     zoom = np.asarray(zoom).astype(np.int64)
-    scores = np.asarray(scores, dtype=np.float32)
+    scores = np.asarray(scores, dtype=dt)
     T = zoom.shape[0]
-    agg = np.empty(T, dtype=np.float32)
+    joined = iou > 0
+    if aug_larger == "greater":
+        joined &= zoom[None, :] >= zoom[:, None]
+    elif aug_larger == "adjacent":
+        joined &= zoom[None, :] == zoom[:, None]
+
+    def first_best(agg):
+        ok = ~np.isnan(agg)
+        if not ok.any():
+            return 0, agg.dtype.type(np.nan)
+        best = int(np.flatnonzero(ok & (agg == agg[ok].max()))[0])
+        return best, agg[best]
+
+    if aug_weight == "cont_weighted":
+        b = np.asarray(boxes, dtype=np.float32)
+        area = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+        w = np.maximum(np.minimum(b[:, None, 2], b[None, :, 2]) - np.maximum(b[:, None, 0], b[None, :, 0]), np.float32(0))
+        h = np.maximum(np.minimum(b[:, None, 3], b[None, :, 3]) - np.maximum(b[:, None, 1], b[None, :, 1]), np.float32(0))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            cont = ((w * h).astype(np.float32) / area[:, None]).astype(np.float32)  # box_utils.py:345, f32
+        agg = np.full(T, np.nan)
+        P = joined.sum(axis=1)
+        A = np.zeros(T)
+        s64 = scores.astype(np.float64)
+        with np.errstate(invalid="ignore", over="ignore"):
+            for i in np.flatnonzero(P > 0):
+                js = np.flatnonzero(joined[i])
+                c = cont[i, js].astype(np.float64)
+                e = np.exp(c - c.max())
+                wgt = e / e.sum()
+                agg[i] = wgt @ s64[js]
+                A[i] = wgt @ np.abs(s64[js])
+        best, sc = first_best(agg)
+        return best, sc, agg, P, A
+
+    levels = np.unique(zoom)  # ascending: the order pandas sums the groups' rows in
+    agg = np.empty(T, dtype=dt)
     for i in range(T):
         winners = []
-        for z in np.unique(zoom):  # ascending: the order pandas sums the groups' rows in
-            if aug_larger == "greater" and z < zoom[i]:
-                continue
-            if aug_larger == "adjacent" and z != zoom[i]:
-                continue
-            assert aug_larger in ("all", "greater", "adjacent")
-            js = np.nonzero((zoom == z) & (iou[i] > 0))[0]
+        for z in levels:
+            js = np.flatnonzero((zoom == z) & joined[i])
             if js.size:
                 winners.append(scores[js[np.argmax(iou[i, js])]])  # argmax: first maximum
-        agg[i] = _kahan_mean_f32(winners) if winners else np.float32(np.nan)
-    best = int(np.flatnonzero(agg == np.nanmax(agg))[0])
-    return best, agg[best], agg
+        agg[i] = _kahan_mean(winners, dt)
+    best, sc = first_best(agg)
+    return best, sc, agg
 
 
 def rescore_avg_score(row_dbidx, boxes, zoom, scores, topk: int, aug_larger: str):

@@ -17,7 +17,8 @@
 // Arithmetic is the reference's, op for op, so results are bit-identical to it given identical tile scores:
 //   IoU in f32 exactly as torchvision's _box_inter_union forms it on float32 boxes
 //     (area = (x2-x1)*(y2-y1); wh = max(min(rb) - max(lt), 0); inter = w*h; union = (a_i + a_j) - inter),
-//   the mean as pandas' float32 group_mean: Kahan-compensated f32 sum in ascending zoom level, f32 division.
+//   the mean as pandas' float32 group_mean: Kahan-compensated f32 sum in ascending zoom level, f32 division; a NaN
+//   score is skipped (and its level not counted), the compensation restarts at 0 after an infinite score.
 // aug_weight = 'cont_weighted' (bit 2 of `aug`): softmax-of-containment weights over all partners instead (f32 like
 // scipy.special.softmax on float32 input; the weighted sum runs in partner order, numpy's dot in BLAS order: 1e-6).
 // Explicitly rounded intrinsics keep the compiler from contracting w*h into the union's subtraction.
@@ -138,10 +139,12 @@ __device__ __forceinline__ void avg_score_of_image(const float4 *__restrict__ bo
                     bj = j;
                 }
             }
-            if (bj >= 0) {
-                const ST y = sscore[bj] - comp;  // (this file is compiled without fma contraction)
+            const ST x = bj >= 0 ? sscore[bj] : (ST)__builtin_nanf("");
+            if (x == x) {  // pandas' group mean skips a NaN score (and so does not count its level)
+                const ST y = x - comp;  // (this file is compiled without fma contraction)
                 const ST t = sum + y;
                 comp = (t - sum) - y;
+                if (comp != comp) comp = 0;  // an infinite score: pandas restarts the compensation, the sum stays infinite
                 sum = t;
                 ++groups;
             }
@@ -213,7 +216,8 @@ size_t avg_score_lds_bytes(int max_tiles, size_t score_bytes) {
     return (size_t)max_tiles * (sizeof(float4) + 2 * score_bytes + sizeof(float) + sizeof(int));
 }
 
-// the dynamic LDS of a launch of `kernel` for images of up to max_tiles tiles; above 64 KB the kernel's limit is raised
+// the dynamic LDS of a launch of `kernel` for images of up to max_tiles tiles; the kernel's limit is raised when that and
+// its static LDS (the 4-byte level mask) together exceed 64 KB: 2048 tiles of f32 scores are 65 536 + 4 bytes
 static ssw_status avg_score_lds(const void *kernel, int32_t max_tiles, size_t score_bytes, size_t *out_lds) {
     if (max_tiles > SSW_RESCORE_MAX_TILES) {
         set_error("avg_score: an image with %d tiles exceeds the %d the kernel keeps in LDS", max_tiles,
@@ -221,7 +225,7 @@ static ssw_status avg_score_lds(const void *kernel, int32_t max_tiles, size_t sc
         return SSW_ERR_UNSUPPORTED;
     }
     *out_lds = avg_score_lds_bytes(max_tiles, score_bytes);
-    if (*out_lds > (size_t)64 * 1024) {  // 2048 tiles of f64 scores: 80 KB
+    if (*out_lds + sizeof(unsigned) > (size_t)64 * 1024) {  // 2048 tiles: 64 KB + 4 B (f32 scores), 80 KB + 4 B (f64)
         // per device and cheap: set on every such launch instead of caching a process-wide flag
         SSW_HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
     }

@@ -407,7 +407,7 @@ ssw_status launch_rank_quick(const float *target_dev, const float *scores_dev, i
                              float *maxrev_dev_or_null, unsigned long long *total_dev_or_null, hipStream_t stream);
 
 // rescore.hip: avg_score aggregation of candidate images' tiles (score_frame2 / box_join).
-constexpr int SSW_RESCORE_MAX_TILES = 2048;  // tiles of one image held in LDS (28 B each)
+constexpr int SSW_RESCORE_MAX_TILES = 2048;  // tiles of one image held in LDS (32 B each with f32 scores, 40 B with f64)
 constexpr int SSW_RESCORE_MAX_ZOOM = 31;     // zoom levels index a 32-bit presence mask
 ssw_status launch_avg_score(const float *boxes, const int32_t *zoom, const float *scores, const float *minus_or_null,
                             const int64_t *row_start, const int64_t *cand_pos, const int64_t *cand_off, int32_t m,

@@ -52,17 +52,21 @@ def match_labels_to_vectors(label_db: LabelDB, vec_meta: pd.DataFrame, target_de
 
 def _kahan_mean_rows(vals: np.ndarray, mask: np.ndarray) -> np.ndarray:
     """per row: mean of vals where mask, summed column by column with a Kahan-compensated sum in vals' dtype --
-    pandas' group_mean, which is what the reference's `.groupby('iloc_left').score_right.mean()` runs"""
+    pandas' group_mean, which is what the reference's `.groupby('iloc_left').score_right.mean()` runs: NaN values are
+    skipped, and a compensation that an infinite value turned into NaN restarts at 0"""
     dt = vals.dtype
+    mask = mask & ~np.isnan(vals)
     total = np.zeros(vals.shape[0], dtype=dt)
     comp = np.zeros(vals.shape[0], dtype=dt)
     count = mask.sum(axis=1)
-    for col in range(vals.shape[1]):
-        m = mask[:, col]
-        y = np.where(m, vals[:, col] - comp, dt.type(0))
-        t = total + y
-        comp = np.where(m, (t - total) - y, comp)
-        total = np.where(m, t, total)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for col in range(vals.shape[1]):
+            m = mask[:, col]
+            y = np.where(m, vals[:, col] - comp, dt.type(0))
+            t = total + y
+            c = (t - total) - y
+            comp = np.where(m, np.where(np.isnan(c), dt.type(0), c), comp)
+            total = np.where(m, t, total)
     with np.errstate(invalid="ignore", divide="ignore"):
         return np.where(count > 0, total / count.astype(dt), dt.type(np.nan))
 

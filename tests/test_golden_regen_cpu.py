@@ -1,4 +1,4 @@
-"""CPU: the committed generator of tests/golden/ and the committed fixtures name the same FOURTEEN families.
+"""CPU: the committed generator of tests/golden/ and the committed fixtures name the same FIFTEEN families.
 
 The fixtures themselves are regenerated from the reference with `python oracle/gen_golden.py --check` (all light
 families; name `c5_sequence` for the heavy one), which needs a checkout of the reference beside the build and fails
@@ -9,7 +9,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIGHT = ("tiling", "sliding", "lknn", "scan_topk", "multiscale_query", "labelprop", "rank_loss", "logreg", "multireg", "bench_loop",
-         "multiregneg", "contweighted", "multireg_det")
+         "multiregneg", "contweighted", "multireg_det", "avg_score_edges")
 HEAVY = ("c5_sequence",)
 
 
