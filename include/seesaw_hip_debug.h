@@ -71,17 +71,18 @@ ssw_status ssw_debug_prune_bounds(ssw_index *idx, const float *q_host, float *ou
 ssw_status ssw_debug_prune_survivors(ssw_index *idx, float threshold, int32_t k, int32_t sel_count, int32_t sel_overflow,
                                      int64_t cap, int32_t *out_published, int64_t *out_collected, int64_t *out_rows);
 
-/* The packed 6-bit shadow that single queries on a large f32 index scan instead of the int8 one (csrc/prune.hip,
- * "6-bit shadow"; tests/test_prune6_gpu.py).  None of these changes what the hooks above do: they keep building and
- * driving the int8 shadow, and ssw_tune_prune's min_rows keeps governing the int8 path only.
- * ssw_tune_prune6: enable 0 = f32 indexes take the int8 path at every size (A/B in one process); min_rows >= 0 = the
- *   smallest f32 index whose single queries scan the 6-bit shadow, < 0 = the product's constant again.
+/* The packed 6-bit shadow that single queries on a large f32 or f16 index scan instead of the int8 one (csrc/prune.hip,
+ * "6-bit shadow"; tests/test_prune6_gpu.py, tests/test_prune6_f16_gpu.py).  None of these changes what the hooks above
+ * do: they keep building and driving the int8 shadow, and ssw_tune_prune's min_rows keeps governing the int8 path only.
+ * ssw_tune_prune6: enable 0 = every index takes the int8 path at every size (A/B in one process); min_rows >= 0 = the
+ *   smallest index, of either dtype, whose single queries scan the 6-bit shadow, < 0 = the product's two constants again.
  * ssw_tune_prune6_scan: the launch shape of k_q6_bounds: four-wave blocks per CU (1 .. 8) and 16-row tiles a wave
  *   requests at a time (1, 2 or 4, as far as tiles x dim <= 1024); any other value = the product's (1 block; 4 / 2 / 1
  *   tiles at dim 256 / 512 / 1024).  ssw_debug_prune6_scan_shape: the blocks and tiles of the next launch.
  * ssw_debug_prune6_shadow: builds the 6-bit shadow if it is missing or stale (the product's ensure_shadow6 ->
- *   k_q6_build) and copies out, for the rows [first_row, first_row + n_rows): the codes [n_rows, dim] unpacked to int8
- *   in natural element order (by the placement function the kernels use), s6_r and a6_r.  NULL outputs are skipped.
+ *   k_q6_build or k_q6_build_h16) and copies out, for the rows [first_row, first_row + n_rows): the codes [n_rows, dim]
+ *   unpacked to int8 in natural element order (by the placement function the kernels use), s6_r and a6_r.  NULL
+ *   outputs are skipped.
  * ssw_debug_prune6_bounds: k_q6_query + k_q6_bounds through the product's launch functions for one host query
  *   (non-finite allowed: it is flagged).  out_I [n] = the exact integer sums of 4 c with 256 d_hi + d_lo (int64),
  *   out_lb [n], out_Qe [4] = Q, e, t2 and the "cannot be bounded" word as floats, out_codes [2, dim] = the query's hi

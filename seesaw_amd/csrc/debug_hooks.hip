@@ -519,7 +519,7 @@ ssw_status ssw_debug_prune_survivors_mq(ssw_index *idx, int32_t nq, int32_t slot
 
 // ---- the packed 6-bit shadow of single queries (prune.hip, "6-bit shadow"; tests/test_prune6_gpu.py) ----------------
 static ssw_status require_shadow6(ssw_index *idx, const char *who) {
-    SSW_REQUIRE(prune6_eligible(idx), "the index takes no 6-bit shadow (ssw_tune_prune6, f32, dim, borrowed or escaped rows)");
+    SSW_REQUIRE(prune6_eligible(idx), "the index takes no 6-bit shadow (ssw_tune_prune6, rows, dim, borrowed or escaped rows)");
     bool ready = false;
     SSW_TRY(ensure_shadow6(idx, &ready));
     if (!ready) {

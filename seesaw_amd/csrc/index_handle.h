@@ -23,8 +23,9 @@ struct PruneState {
     hipEvent_t ev = nullptr;                       // after the shadow scan: the host sleeps on it, then spins
     float *q_last = nullptr;                       // [dim] the query of the last pruned scan
     int64_t last = 0, queries = 0, fallbacks = 0;
-    // the packed 6-bit shadow of f32 rows (prune.hip, "6-bit shadow"): what single queries scan on an index of at
-    // least PRUNE6_MIN_ROWS rows, instead of the int8 one; built lazily like it, with its own stale / refused
+    // the packed 6-bit shadow of the rows (prune.hip, "6-bit shadow"): what single queries scan on an index of at least
+    // PRUNE6_MIN_ROWS f32 or PRUNE6_MIN_ROWS_F16 f16 rows, instead of the int8 one; built lazily like it, with its own
+    // stale / refused
     unsigned char *q6 = nullptr;                   // q6_code_bytes(n, dim): tiles of 16 rows
     float *q6_scale = nullptr, *q6_err = nullptr;  // [q6_padded_rows(n)] s6_r, a6_r
     bool stale6 = true, refused6 = false;

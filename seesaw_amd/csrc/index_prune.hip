@@ -22,11 +22,19 @@ constexpr int64_t PRUNE_BATCH_MIN_ROWS = PRUNE_MIN_ROWS;
 // row at dim 512, more survivors) and never need the int8 one.  The value follows from tools/perf_prune.py --three-way
 // ("6-bit shadow"): the smallest size from which the 6-bit call beats the int8 call, there and at
 // every larger size, by more than both spreads.
+// Measured since (profiles/prune6_f32_sweep.txt): the rule gives 2^25 (2.55 against 2.81 ms a call there; at 2^24 and at
+// 25 M rows the gap, 0.09 ms, is inside the spreads).  Moving this constant is left to a change of its own.
 constexpr int64_t PRUNE6_MIN_ROWS = (int64_t)1 << 24;
+// f16 rows (the shadow is built from the widened rows by k_q6_build_h16, the same bytes a row): its own constant under
+// the same rule, from the same tool with --dtype float16 (profiles/prune6_f16_sweep.txt): 2^25 rows is the smallest
+// measured size from which the 6-bit call is ahead by more than both spreads, there and above (2.59 against 2.78 ms a
+// call; 7.05 against 8.93 at 100 M).  At 2^24 rows the two are level (1.49 against 1.48), at 25 M the gap of 0.11 ms is
+// inside the spreads' 0.13.
+constexpr int64_t PRUNE6_MIN_ROWS_F16 = (int64_t)1 << 25;
 constexpr int64_t PRUNE_RESERVE = (int64_t)4 << 30;   // free device memory the shadow must leave
 static SSW_TUNABLE bool g_prune = true;               // ssw_tune_prune
 static SSW_TUNABLE bool g_prune6 = true;              // ssw_tune_prune6
-static SSW_TUNABLE int64_t g_prune6_min_rows = -1;     // >= 0: this many rows instead of PRUNE6_MIN_ROWS
+static SSW_TUNABLE int64_t g_prune6_min_rows = -1;     // >= 0: this many rows for both dtypes instead
 static SSW_TUNABLE int64_t g_prune_min_rows = -1;      // >= 0: this many rows for both dtypes instead
 static SSW_TUNABLE int64_t g_prune_reserve = PRUNE_RESERVE;
 
@@ -48,10 +56,11 @@ bool ssw::prune_eligible(const ssw_index *idx) { return prune_eligible_from(idx,
 bool ssw::prune_batch_eligible(const ssw_index *idx) {
     return prune_eligible_from(idx, g_prune_min_rows >= 0 ? g_prune_min_rows : PRUNE_BATCH_MIN_ROWS);
 }
-bool ssw::prune6_eligible(const ssw_index *idx) {
-    return g_prune6 && idx->dtype == SSW_DTYPE_F32 &&
-           prune_eligible_from(idx, g_prune6_min_rows >= 0 ? g_prune6_min_rows : PRUNE6_MIN_ROWS);
+static int64_t prune6_min_rows(const ssw_index *idx) {
+    if (g_prune6_min_rows >= 0) return g_prune6_min_rows;
+    return idx->dtype == SSW_DTYPE_F16 ? PRUNE6_MIN_ROWS_F16 : PRUNE6_MIN_ROWS;
 }
+bool ssw::prune6_eligible(const ssw_index *idx) { return g_prune6 && prune_eligible_from(idx, prune6_min_rows(idx)); }
 
 // the rows are about to change: the buffer keeps the scores of the rows it was computed from, the shadow goes stale
 ssw_status ssw::rows_changing(ssw_index *idx) {
@@ -122,7 +131,7 @@ ssw_status ssw::ensure_shadow(ssw_index *idx, bool *ready) {
     return SSW_OK;
 }
 
-// the packed 6-bit shadow of an f32 index, under the same rule
+// the packed 6-bit shadow of the rows, under the same rule
 ssw_status ssw::ensure_shadow6(ssw_index *idx, bool *ready) {
     PruneState &p = idx->prune;
     *ready = false;
@@ -156,7 +165,7 @@ ssw_status ssw::ensure_shadow6(ssw_index *idx, bool *ready) {
         // columns 2 .. 15 of the query operand stay zero for good: k_q6_query writes columns 0 and 1 only
         SSW_HIP_TRY(hipMemsetAsync(p.planes6, 0, q6_plane_bytes(idx->dim), idx->stream));
     }
-    SSW_TRY(launch_q6_build(idx->X, idx->n, idx->dim, p.q6, p.q6_scale, p.q6_err, idx->stream));
+    SSW_TRY(launch_q6_build(idx->X, idx->dtype, idx->n, idx->dim, p.q6, p.q6_scale, p.q6_err, idx->stream));
     p.stale6 = false;
     *ready = true;
     return SSW_OK;
@@ -348,7 +357,7 @@ ssw_status ssw_tune_prune_scan(int32_t blocks_per_cu, int32_t group_loads) {
 
 ssw_status ssw_tune_prune6(int32_t enable, int64_t min_rows) {
     g_prune6 = enable != 0;
-    g_prune6_min_rows = min_rows < 0 ? -1 : min_rows;  // < 0: PRUNE6_MIN_ROWS again
+    g_prune6_min_rows = min_rows < 0 ? -1 : min_rows;  // < 0: PRUNE6_MIN_ROWS / PRUNE6_MIN_ROWS_F16 again
     return SSW_OK;
 }
 

@@ -116,12 +116,9 @@ __device__ __forceinline__ void q8_build_row(const float *__restrict__ X, int64_
 
 // binary16 rows in the f16 index's lane-interleaved layout (ssw_common.h): lane l reads its 8C contiguous bytes at
 // l * 8C of the row (one 16-byte load at dim 512, two at dim 1024, 8 bytes at dim 256) and widens them, exactly; chunk c
-// of them is the natural elements 256c + 4l .. + 3, so its four codes are the 4 bytes at 256c + 4l of the row's code
-// line: a wave writes 256 contiguous bytes a chunk, and the shadow is in natural element order as for f32 rows.
+// of them, x[4c .. 4c + 3], is the natural elements 256c + 4l .. + 3.
 template <int C>
-__device__ __forceinline__ void q8_build_row_h16(const uint16_t *__restrict__ X, int64_t r, int lane,
-                                                 int8_t *__restrict__ codes, float *__restrict__ scale,
-                                                 float *__restrict__ err) {
+__device__ __forceinline__ void load_row_h16(const uint16_t *__restrict__ X, int64_t r, int lane, float (&x)[4 * C]) {
     constexpr int dim = 256 * C;
     const u32x2 *src = reinterpret_cast<const u32x2 *>(X + r * dim) + lane * C;
     u32x2 w[C];
@@ -135,7 +132,6 @@ __device__ __forceinline__ void q8_build_row_h16(const uint16_t *__restrict__ X,
             w[c + 1] = u32x2{v.z, v.w};
         }
     }
-    float x[4 * C];
 #pragma unroll
     for (int c = 0; c < C; ++c) {
         const float4 v = widen_h16x4(w[c]);
@@ -144,6 +140,17 @@ __device__ __forceinline__ void q8_build_row_h16(const uint16_t *__restrict__ X,
         x[4 * c + 2] = v.z;
         x[4 * c + 3] = v.w;
     }
+}
+
+// binary16 rows: the four codes of chunk c are the 4 bytes at 256c + 4l of the row's code line: a wave writes 256
+// contiguous bytes a chunk, and the shadow is in natural element order as for f32 rows.
+template <int C>
+__device__ __forceinline__ void q8_build_row_h16(const uint16_t *__restrict__ X, int64_t r, int lane,
+                                                 int8_t *__restrict__ codes, float *__restrict__ scale,
+                                                 float *__restrict__ err) {
+    constexpr int dim = 256 * C;
+    float x[4 * C];
+    load_row_h16<C>(X, r, lane, x);
     unsigned packed[C];
     q8_quantise_row<C>(x, r, lane, packed, scale, err);
     unsigned *dst = reinterpret_cast<unsigned *>(codes + r * dim) + lane;
@@ -720,9 +727,10 @@ __global__ __launch_bounds__(256) void k_scatter_scores(const int64_t *__restric
 }
 
 
-// ---- the packed 6-bit shadow of f32 rows and its scan on the int8 matrix core ("6-bit shadow") ----
-// Codes c = rint(x / s6), |c| <= 31, s6 = max|x| / 31; a6 is the int8 shadow's a_r with these codes.  The query is the
-// chunk's (k_q8_query_mq: two int8 planes, residual norm e), so with ||c|| <= 31 sqrt(dim)
+// ---- the packed 6-bit shadow of the rows and its scan on the int8 matrix core ("6-bit shadow") -----
+// The rows x are the f32 rows, or the widened binary16 rows of an f16 index (as for the int8 shadow: the head of this
+// file).  Codes c = rint(x / s6), |c| <= 31, s6 = max|x| / 31; a6 is the int8 shadow's a_r with these codes.  The query
+// is the chunk's (k_q8_query_mq: two int8 planes, residual norm e), so with ||c|| <= 31 sqrt(dim)
 //
 //     | S_r - (s6_r / 4) t2 I_r | <= a6_r Q + s6_r 31 sqrt(dim) e =: w,   I_r = sum_i 4 c_ri (256 d_hi,i + d_lo,i)   (***)
 //
@@ -742,13 +750,31 @@ constexpr int q6_default_tiles(int C) { return 4 / C; }  // 16-row tiles of one 
 // 31 sqrt(dim), rounded up
 __host__ __device__ constexpr double q6_code_norm(int dim) { return dim == 256 ? 496.0 : dim == 512 ? 701.4499270 : 992.0; }
 
-// one wave per row (grid-strided).  The row's codes in natural order go through the wave's own LDS line; lane l then
-// assembles words l, l + 64, .. of the row's 12 dim / 64 and stores each at its place in the tile.
+// The tile assembly both builders share: cl is the wave's LDS line with the codes of row r in natural element order,
+// one byte each; lane l assembles words l, l + 64, .. of the row's 12 dim / 64 and stores each at its place in the tile.
+template <int C>
+__device__ __forceinline__ void q6_store_row(const int8_t *cl, int64_t r, int lane, unsigned char *__restrict__ codes) {
+    constexpr int dim = 256 * C, KS = dim / 64, WPL = 3 * KS;  // words a lane of the tile owns
+    constexpr size_t TILE_BYTES = (size_t)16 * dim * 3 / 4;
+    unsigned char *tile = codes + (size_t)(r >> 4) * TILE_BYTES;
+    for (int w = lane; w < 4 * WPL; w += 64) {
+        const int g = w / WPL, wi = w % WPL, u = wi / 3, part = wi % 3;
+        unsigned word = 0u;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int main_c = cl[q6_element(u, g, 4 * part + b)], low_c = cl[q6_element(u, g, 12 + b)];
+            word |= ((((unsigned)main_c & 0x3fu) << 2) | (((unsigned)low_c >> (4 - 2 * part)) & 3u)) << (8 * b);
+        }
+        *reinterpret_cast<unsigned *>(tile + q6_word_offset(16 * g + (int)(r & 15), wi)) = word;
+    }
+}
+
+// one wave per row (grid-strided).  The row's codes in natural order go through the wave's own LDS line (lane l holds
+// the elements 4C l .. + 4C - 1: words l C .. + C - 1 of the line), then q6_store_row.
 template <int C>
 __global__ __launch_bounds__(256) void k_q6_build(const float *__restrict__ X, int64_t n, unsigned char *__restrict__ codes,
                                                   float *__restrict__ scale, float *__restrict__ err) {
-    constexpr int dim = 256 * C, KS = dim / 64, WPL = 3 * KS;  // words a lane of the tile owns
-    constexpr size_t TILE_BYTES = (size_t)16 * dim * 3 / 4;
+    constexpr int dim = 256 * C;
     __shared__ unsigned line[4][64 * C];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int8_t *cl = reinterpret_cast<const int8_t *>(line[wave]);
@@ -766,17 +792,31 @@ __global__ __launch_bounds__(256) void k_q6_build(const float *__restrict__ X, i
 #pragma unroll
         for (int c = 0; c < C; ++c) line[wave][lane * C + c] = packed[c];
         __builtin_amdgcn_wave_barrier();
-        unsigned char *tile = codes + (size_t)(r >> 4) * TILE_BYTES;
-        for (int w = lane; w < 4 * WPL; w += 64) {
-            const int g = w / WPL, wi = w % WPL, u = wi / 3, part = wi % 3;
-            unsigned word = 0u;
+        q6_store_row<C>(cl, r, lane, codes);
+    }
+}
+
+// The same from binary16 rows in the f16 index's layout (load_row_h16): chunk c of lane l is the natural elements
+// 256c + 4l .. + 3, so its word of codes is word 64c + l of the line (a wave's store of a chunk is 256 contiguous bytes,
+// no bank is hit twice).  The codes and s6_r are those of k_q6_build on the widened rows; a6_r's double sums are taken
+// over another assignment of elements to lanes.
+template <int C>
+__global__ __launch_bounds__(256) void k_q6_build_h16(const uint16_t *__restrict__ X, int64_t n,
+                                                      unsigned char *__restrict__ codes, float *__restrict__ scale,
+                                                      float *__restrict__ err) {
+    __shared__ unsigned line[4][64 * C];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int8_t *cl = reinterpret_cast<const int8_t *>(line[wave]);
+    for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < n; r += (int64_t)gridDim.x * 4) {
+        float x[4 * C];
+        load_row_h16<C>(X, r, lane, x);
+        unsigned packed[C];
+        q8_quantise_row<C, 31>(x, r, lane, packed, scale, err);
+        __builtin_amdgcn_wave_barrier();  // as in k_q6_build
 #pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const int main_c = cl[q6_element(u, g, 4 * part + b)], low_c = cl[q6_element(u, g, 12 + b)];
-                word |= ((((unsigned)main_c & 0x3fu) << 2) | (((unsigned)low_c >> (4 - 2 * part)) & 3u)) << (8 * b);
-            }
-            *reinterpret_cast<unsigned *>(tile + q6_word_offset(16 * g + (int)(r & 15), wi)) = word;
-        }
+        for (int c = 0; c < C; ++c) line[wave][64 * c + lane] = packed[c];
+        __builtin_amdgcn_wave_barrier();
+        q6_store_row<C>(cl, r, lane, codes);
     }
 }
 
@@ -1104,17 +1144,17 @@ ssw_status launch_prune_publish_mq(const unsigned *mq, int32_t w, int64_t cap, i
     return SSW_OK;
 }
 
-// ---- the packed 6-bit shadow (f32 rows) -----------------------------------------------------------------------------
+// ---- the packed 6-bit shadow ----------------------------------------------------------------------------------------
 int64_t q6_padded_rows(int64_t n) { return (n + 15) / 16 * 16; }
 size_t q6_code_bytes(int64_t n, int32_t dim) { return (size_t)q6_padded_rows(n) * (size_t)dim * 3 / 4; }
 size_t q6_plane_bytes(int32_t dim) { return (size_t)(dim / 64) * 64 * 16; }
 
 // codes / scale / err: q6_code_bytes and q6_padded_rows floats each; the rows past n of the last tile get zeros
-ssw_status launch_q6_build(const float *X, int64_t n, int32_t dim, unsigned char *codes, float *scale, float *err,
-                           hipStream_t stream) {
+ssw_status launch_q6_build(const void *X, int32_t dtype, int64_t n, int32_t dim, unsigned char *codes, float *scale,
+                           float *err, hipStream_t stream) {
     if (n <= 0) return SSW_OK;
-    if (!q8_dim_supported(dim)) {
-        set_error("q6_build: dim=%d unsupported", dim);
+    if (!q8_dim_supported(dim) || (dtype != SSW_DTYPE_F32 && dtype != SSW_DTYPE_F16)) {
+        set_error("q6_build: dim=%d, dtype=%d unsupported", dim, dtype);
         return SSW_ERR_UNSUPPORTED;
     }
     const int64_t np = q6_padded_rows(n);
@@ -1125,10 +1165,20 @@ ssw_status launch_q6_build(const float *X, int64_t n, int32_t dim, unsigned char
         SSW_HIP_TRY(hipMemsetAsync(err + np - 16, 0, 16 * sizeof(float), stream));
     }
     const dim3 grid((unsigned)std::min<int64_t>((n + 3) / 4, (int64_t)1 << 20)), block(256);
-    switch (dim) {
-        case 256: hipLaunchKernelGGL(k_q6_build<1>, grid, block, 0, stream, X, n, codes, scale, err); break;
-        case 512: hipLaunchKernelGGL(k_q6_build<2>, grid, block, 0, stream, X, n, codes, scale, err); break;
-        default: hipLaunchKernelGGL(k_q6_build<4>, grid, block, 0, stream, X, n, codes, scale, err); break;
+    if (dtype == SSW_DTYPE_F16) {
+        const uint16_t *Xh = static_cast<const uint16_t *>(X);
+        switch (dim) {
+            case 256: hipLaunchKernelGGL(k_q6_build_h16<1>, grid, block, 0, stream, Xh, n, codes, scale, err); break;
+            case 512: hipLaunchKernelGGL(k_q6_build_h16<2>, grid, block, 0, stream, Xh, n, codes, scale, err); break;
+            default: hipLaunchKernelGGL(k_q6_build_h16<4>, grid, block, 0, stream, Xh, n, codes, scale, err); break;
+        }
+    } else {
+        const float *Xf = static_cast<const float *>(X);
+        switch (dim) {
+            case 256: hipLaunchKernelGGL(k_q6_build<1>, grid, block, 0, stream, Xf, n, codes, scale, err); break;
+            case 512: hipLaunchKernelGGL(k_q6_build<2>, grid, block, 0, stream, Xf, n, codes, scale, err); break;
+            default: hipLaunchKernelGGL(k_q6_build<4>, grid, block, 0, stream, Xf, n, codes, scale, err); break;
+        }
     }
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;

@@ -198,8 +198,8 @@ ssw_status launch_prune_publish_mq(const unsigned *mq, int32_t w, int64_t cap, i
                                    hipStream_t stream);
 // blocks and 16-row tiles per request of the launch launch_q8_bounds_mq would make
 void q8_bounds_mq_shape(int32_t dim, int device, int64_t n, int *out_blocks, int *out_tiles);
-// the packed 6-bit shadow of f32 rows (prune.hip, "6-bit shadow"): tiles of 16 rows, 3 dim / 4 bytes a row, buffers padded
-// to whole tiles.  q6_slot / q6_element / q6_word_offset are the ONE placement of an element's code: k-step u, lane
+// the packed 6-bit shadow of f32 or f16 rows (prune.hip, "6-bit shadow"): tiles of 16 rows, 3 dim / 4 bytes a row, buffers
+// padded to whole tiles.  q6_slot / q6_element / q6_word_offset are the ONE placement of an element's code: k-step u, lane
 // group g (the lane of row r is 16 g + r % 16) and slot j of the lane's 16 codes of that k-step; slot j < 12 is the upper
 // six bits of byte j % 4 of the lane's word 3 u + j / 4, slot 12 + b the low two bits of byte b of words 3 u .. 3 u + 2
 // (code bits 5:4, 3:2, 1:0); word wi of lane l sits at q6_word_offset(l, wi) in the tile.
@@ -211,8 +211,9 @@ __host__ __device__ inline size_t q6_word_offset(int lane, int wi) {
 int64_t q6_padded_rows(int64_t n);
 size_t q6_code_bytes(int64_t n, int32_t dim);
 size_t q6_plane_bytes(int32_t dim);
-ssw_status launch_q6_build(const float *X, int64_t n, int32_t dim, unsigned char *codes, float *scale, float *err,
-                           hipStream_t stream);
+// X: f32 rows in natural order, or binary16 rows in the f16 index's lane-interleaved layout (dtype: SSW_DTYPE_*)
+ssw_status launch_q6_build(const void *X, int32_t dtype, int64_t n, int32_t dim, unsigned char *codes, float *scale,
+                           float *err, hipStream_t stream);
 ssw_status launch_q6_query(const float *q_dev, int32_t dim, unsigned *st, int8_t *planes, float *q_keep,
                            hipStream_t stream);
 // dbg_I (lab hook only, else NULL): [n] the exact integer sums

@@ -159,7 +159,10 @@ class DeviceIndex:
 
     def topk(self, q: Optional[np.ndarray], k: int, excluded: Optional[Iterable[int]] = None):
         """Top-k distinct images (positions), their max score and the row attaining it.
-        q=None reuses the scores of the previous scan."""
+        q=None reuses the scores of the previous scan.  With a query, a large index (f32 or float16 rows alike) scans a
+        quantised shadow of the rows first and scores only the rows that can still reach the k-th image exactly: the
+        int8 shadow from 2^22 rows, the packed 6-bit shadow from 2^24 f32 or 2^25 float16 rows.  The results are the
+        full scan's bits."""
         k = int(k)
         qa = None if q is None else self._query(q)
         ex = None
@@ -403,11 +406,13 @@ class DeviceIndex:
     _SHADOW_STATES = ("none", "current", "stale", "refused")
 
     def prune_stats(self) -> dict:
-        """state of the certified int8 pre-scan of `topk` with a query (ssw_index_prune_stats): `shadow` is "none",
-        "current", "stale" (the rows changed since it was built; the next pruned call rebuilds it) or "refused" (too
-        little free device memory beside it); `eligible`: the next top-k with a query is pruned; `last_survivors`: rows
-        the last pruned call rescored (-1 = it fell back to the full scan); `queries` / `fallbacks`: pruned calls and
-        how many of them fell back; `shadow_bytes`: device memory the shadow holds"""
+        """state of the certified pre-scan of `topk` with a query (ssw_index_prune_stats).  `shadow` describes the
+        shadow single queries scan -- the packed 6-bit one on an index of at least 2^24 f32 or 2^25 float16 rows, else
+        the int8 one: "none", "current", "stale" (the rows changed since it was built; the next pruned call rebuilds
+        it) or "refused" (too little free device memory beside it); `eligible`: the next top-k with a query is pruned;
+        `last_survivors`: rows the last pruned call rescored (-1 = it fell back to the full scan); `queries` /
+        `fallbacks`: pruned calls and how many of them fell back; `shadow_bytes`: device memory the shadows hold
+        (dim + 8 bytes a row for the int8 one, 3 dim / 4 + 8 for the 6-bit one; a pruned batch builds the int8 one)"""
         out = np.zeros(6, dtype=np.int64)
         _lib.call("ssw_index_prune_stats", self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
         return {"shadow": self._SHADOW_STATES[int(out[0])], "eligible": bool(out[1]), "last_survivors": int(out[2]),

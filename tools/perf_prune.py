@@ -3,21 +3,23 @@
 
     python tools/perf_prune.py [--rows 12.5e6 25e6 50e6 100e6] [--k 100] [--reps 10] [--dtype float32|float16]
                                [--warmup-pairs 2]
-    python tools/perf_prune.py --three-way [--rows ...] [--k 100]
+    python tools/perf_prune.py --three-way [--rows ...] [--k 100] [--dtype float32|float16]
 
 For each index size: a synthetic N x 512 index of f32 or binary16 rows, one first top-k (builds the int8 shadow, timed
 on its own), `warmup-pairs` untimed pairs, then `reps` pairs of top-k calls with the pruning switched off and on in turn
 (the lab build's ssw_tune_prune; the threshold is lowered to 1 row so that every size is pruned), each a different
 query.  Prints per size: host wall ms per call (median, and the spread min .. max), the HIP-event ms of the scan phase
 (the full scan, or shadow scan + threshold selection + survivors + rescoring), survivors and fallbacks, and whether
-both forms returned the same images, scores and best rows.  This mode keeps f32 indexes on the int8 shadow at every size
+both forms returned the same images, scores and best rows.  This mode keeps every index on the int8 shadow at every size
 (ssw_tune_prune6(0)).
 
---three-way (f32 rows; how PRUNE6_MIN_ROWS of csrc/index_prune.hip is chosen): full scan / int8 shadow / packed 6-bit
-shadow in turn in one process, two warm-up rounds, then 20 rounds, each a different query; per size one JSON line with
-the median and the spread (max - min) of the host wall ms of each form, the 6-bit survivors, and whether all three
-returned the same bytes.  Where the two shadows do not fit beside the rows together (100 M rows), the int8 rounds and
-the 6-bit rounds run one after the other on two indexes of the same rows, each alternating with the full scan."""
+--three-way (how PRUNE6_MIN_ROWS and, with --dtype float16, PRUNE6_MIN_ROWS_F16 of csrc/index_prune.hip are chosen):
+full scan / int8 shadow / packed 6-bit shadow in turn in one process, two warm-up rounds, then 20 rounds, each a
+different query; per size one JSON line with the median and the spread (max - min) of the host wall ms of each form, the
+6-bit survivors, whether all three returned the same bytes, and under "shadows" which shadow each form's first call
+built, from the growth of prune_stats' shadow_bytes ("none", "int8" or "6-bit"; a form that built another shadow than
+its name says ends the run).  Where the two shadows do not fit beside the rows together, the int8 rounds and the 6-bit
+rounds run one after the other on two indexes of the same rows, each alternating with the full scan."""
 import argparse
 import ctypes
 import json
@@ -55,14 +57,23 @@ def main():
         _lib.call("ssw_tune_prune", 0 if form == "full" else 1, 1, -1)
         _lib.call("ssw_tune_prune6", 1 if form == "q6" else 0, 1)
 
-    def rounds(n, forms, wall, surv):
+    dtype = np.dtype(args.dtype)
+    built_by = {"full": "none", "int8": "int8", "q6": "6-bit"}
+
+    def rounds(n, forms, wall, surv, shadows):
         """warm-up and timed rounds over `forms` on a fresh index; -> all forms returned the same bytes"""
-        idx = DeviceIndex.synthetic(n, 512, seed=2024)
+        idx = DeviceIndex.synthetic(n, 512, seed=2024, dtype=dtype)
+        grows = {0: "none", n * (512 + 8): "int8", (n + 15) // 16 * 16 * (512 * 3 // 4 + 8): "6-bit"}
         same = True
         try:
             for form in forms:  # builds the shadows, untimed
                 set_form(form)
+                before = idx.prune_stats()["shadow_bytes"]
                 idx.topk(query(0), args.k)
+                grew = idx.prune_stats()["shadow_bytes"] - before
+                shadows[form] = grows.get(grew, f"{grew} bytes")
+                if shadows[form] != built_by[form]:
+                    raise SystemExit(f"{n} rows: the {form} form built {shadows[form]!r}, not {built_by[form]!r}")
             for i in range(-2, 20):
                 q, out = query(3 + i), {}
                 for form in forms:
@@ -83,17 +94,17 @@ def main():
     def three_way(n):
         import torch
         total = torch.cuda.mem_get_info(0)[1]
-        together = n * (2048 + 520 + 392 + 8) + (5 << 30) < total
-        wall, surv = {}, []
+        together = n * (512 * dtype.itemsize + 520 + 392 + 8) + (5 << 30) < total
+        wall, surv, shadows = {}, [], {}
         if together:
-            same, fallbacks = rounds(n, ["full", "int8", "q6"], wall, surv)
+            same, fallbacks = rounds(n, ["full", "int8", "q6"], wall, surv, shadows)
         else:
             wall_b = {}
-            same_a, fa = rounds(n, ["full", "int8"], wall, surv)
-            same_b, fb = rounds(n, ["full", "q6"], wall_b, surv)
+            same_a, fa = rounds(n, ["full", "int8"], wall, surv, shadows)
+            same_b, fb = rounds(n, ["full", "q6"], wall_b, surv, shadows)
             wall["q6"], wall["full_beside_q6"] = wall_b["q6"], wall_b["full"]
             same, fallbacks = same_a and same_b, fa + fb
-        res = {"rows": n, "k": args.k, "one_index": bool(together)}
+        res = {"rows": n, "dtype": args.dtype, "k": args.k, "one_index": bool(together), "shadows": shadows}
         for form, v in wall.items():
             res[form + "_ms_median"] = round(float(np.median(v)), 3)
             res[form + "_ms_spread"] = round(float(np.max(v) - np.min(v)), 3)
