@@ -258,7 +258,8 @@ ssw_status ssw_index_rescore_avg_f64(ssw_index *idx, const double *dev_scores, c
  * batch leaves only its last query's scores resident, so the single entry cannot follow it).
  * First stage: arguments, results, errors, chunking, the side buffer and the state afterwards are exactly those of
  * ssw_index_topk_batch -- the full-precision scan for nq >= 2; nq == 1 IS ssw_index_topk, pruning included, after
- * which the resident scores are completed (one full scan of the query on a pruned index).
+ * which the tiles of the selected images are rescored exactly into the partial score buffer (as in
+ * ssw_index_topk_batch_avg_pruned below; the buffer stays partial).
  * Second stage: after query b's selection has been collected (so after a deep rerun too) one launch of one workgroup
  * per result slot takes its candidates from the handle's device result buffers (ssw_index_result_ptrs) and the tile
  * scores from slab b, on the same stream, before the next query's selection overwrites those buffers; no candidate
@@ -274,6 +275,20 @@ ssw_status ssw_index_topk_batch_avg(ssw_index *idx, const float *q_host, int32_t
                                     const int64_t *excluded_offsets, int32_t k, int32_t aug_larger, int64_t *out_images,
                                     float *out_scores, int64_t *out_best_rows, float *out_avg_scores,
                                     int64_t *out_avg_rows, int32_t *out_counts);
+/* ssw_index_topk_batch_avg with the first stage of ssw_index_topk_batch_pruned: arguments, results, errors and the
+ * state afterwards as there, every output the bits of ssw_index_topk_batch_avg.  A pruned slab is exact on the query's
+ * survivors only, and the aggregation reads the tiles of the k selected images and nothing else: after query b's
+ * selection has been collected, one launch lists those tiles from the device result buffers (one workgroup a slot,
+ * k x T entries, T = the most tiles of any image, short images padded with their first row), the rows are scored
+ * exactly with q[b] by gather and scattered into slab b, then the aggregation runs as above.  A slot whose first stage
+ * fell back holds the full scan already; where k x T exceeds 2^18 the slab is completed by the full scan of q[b]
+ * (counted in ssw_index_prune_completions [0]).  nq == 1 is ssw_index_topk followed by the same steps on the handle's
+ * buffer.  An index that is not pruned, or whose int8 shadow is refused, takes ssw_index_topk_batch_avg itself and
+ * leaves every prune counter alone.  Opt-in: nothing dispatches to it silently. */
+ssw_status ssw_index_topk_batch_avg_pruned(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
+                                           const int64_t *excluded_offsets, int32_t k, int32_t aug_larger,
+                                           int64_t *out_images, float *out_scores, int64_t *out_best_rows,
+                                           float *out_avg_scores, int64_t *out_avg_rows, int32_t *out_counts);
 
 /* merge several sorted key lists (e.g. the all-gathered per-shard top-k of a
  * row-sharded index; keys as in ssw_index_result_ptrs but with GLOBAL image ids
@@ -365,14 +380,22 @@ ssw_status ssw_index_profile_read(ssw_index *idx, float *out_ms, int32_t cap, in
  * of every score, and rescore exactly only the rows whose upper bound reaches the k-th image's lower bound.  The result
  * is the bits of the full scan; the call waits once on the host for the survivor count.  Whenever the certificate
  * fails the full scan runs instead.  The score buffer then holds exact scores for the survivors only; every entry that
- * reads it (topk with q = NULL, select_deep_dev, gather_scores, rescore_avg, device_ptrs, the labelprop top-k) first
- * completes it with the full scan of the kept query, and upload / fill_random do so before they change the rows.
+ * reads all of it (topk with q = NULL, select_deep_dev, device_ptrs, the labelprop top-k) first completes it with the
+ * full scan of the kept query, and upload / fill_random do so before they change the rows.  The second-stage readers
+ * make exact what they read and leave it partial: rescore_avg scores the candidates' tiles with the kept query by
+ * gather and scatters them into the buffer, gather_scores scores the requested rows straight into its output -- both
+ * the full scan's bits; above 2^18 rows in one call either completes the buffer instead.
  * An index that borrows a device matrix and an index whose row pointer ssw_index_device_ptrs has handed out never get
  * a shadow.  An f16 index with its shadow holds dim * 3 + 8 bytes a row.  The environment variable SSW_TOPK_FULL_SCAN
  * (read once) forces the full scan everywhere, for both element types.
  * out6: [0] shadow 0 none / 1 current / 2 stale / 3 refused (memory), [1] 1 = the next top-k with a query is pruned,
  * [2] survivors of the last pruned call (-1 = it fell back), [3] pruned calls, [4] fallbacks, [5] shadow bytes. */
 ssw_status ssw_index_prune_stats(ssw_index *idx, int64_t *out6);
+/* what the readers of a partial score buffer or slab cost: out2 [0] full scans launched to complete one (by a reader of
+ * the whole buffer, by a second-stage call over more than 2^18 rows, before the rows change), [1] rows scored by gather
+ * instead -- the candidates' tile total of ssw_index_rescore_avg, the rows of ssw_index_gather_scores, the k x T list
+ * entries of the two-stage batch. */
+ssw_status ssw_index_prune_completions(ssw_index *idx, int64_t *out2);
 
 /* ------------------------------------------------------------------------- */
 /* k-NN-graph label propagation                                               */

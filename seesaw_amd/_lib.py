@@ -70,6 +70,8 @@ _SIGNATURES = {
                                             c_void_p, c_void_p]),
     "ssw_index_topk_batch_avg": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ssw_index_topk_batch_avg_pruned": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_i32, c_void_p,
+                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ssw_index_set_excluded": (c_i32, [c_void_p, c_void_p, c_i64]),
     "ssw_index_topk_dev": (c_i32, [c_void_p, c_void_p, c_i32]),
     "ssw_index_set_tile_meta": (c_i32, [c_void_p, c_void_p, c_void_p]),
@@ -155,6 +157,7 @@ _SIGNATURES = {
     "ssw_index_profile": (c_i32, [c_void_p, c_i32]),
     "ssw_index_profile_read": (c_i32, [c_void_p, c_void_p, c_i32, c_i32_p]),
     "ssw_index_prune_stats": (c_i32, [c_void_p, c_i64_p]),
+    "ssw_index_prune_completions": (c_i32, [c_void_p, c_i64_p]),
 }
 
 

@@ -106,6 +106,7 @@ ssw_status ssw::do_scan(ssw_index *idx, const float *q_dev) {
 ssw_status ssw::ensure_full_scores(ssw_index *idx, hipStream_t stream) {
     if (!idx->scores_partial) return SSW_OK;
     idx->scores_partial = false;
+    ++idx->prune.completions;
     return launch_index_scan(idx, idx->prune.q_last, stream);
 }
 
@@ -468,12 +469,16 @@ ssw_status ssw_index_rescore_avg(ssw_index *idx, const int64_t *image_positions,
     SSW_REQUIRE(image_positions && out_scores && out_best_rows, "NULL argument");
     SSW_TRY(check_avg_args(idx, aug_larger, "rescore_avg"));
     DeviceGuard guard(idx->device);
-    SSW_TRY(ensure_full_scores(idx));
     std::vector<int64_t> off;
     int64_t total = 0, max_tiles = 0;
     SSW_TRY(candidate_geometry(idx, image_positions, m, off, &total, &max_tiles));
     SSW_REQUIRE(max_tiles <= SSW_RESCORE_MAX_TILES, "an image with %lld tiles exceeds the %d the kernel keeps in LDS",
                 (long long)max_tiles, SSW_RESCORE_MAX_TILES);
+    // after a pruned top-k the kernel reads exact scores on the candidates' tiles and nowhere else: up to SURV_CAP of
+    // them are rescored by gather with the kept query and the buffer stays partial; more take the full scan
+    PruneState &pr = idx->prune;
+    const bool on_demand = idx->scores_partial && total <= SURV_CAP && pr.surv_rows && pr.surv_scores;
+    if (!on_demand) SSW_TRY(ensure_full_scores(idx));
     hipStream_t s = idx->stream;
     if (m > idx->rs_cap) {
         SSW_HIP_TRY(hipStreamSynchronize(s));
@@ -505,6 +510,10 @@ ssw_status ssw_index_rescore_avg(ssw_index *idx, const int64_t *image_positions,
     if (minus_scores_or_null)
         SSW_HIP_TRY(hipMemcpyAsync(idx->rs_minus, minus_scores_or_null, (size_t)total * 4, hipMemcpyHostToDevice, s));
     SSW_HIP_TRY(hipStreamSynchronize(s));  // `off` is a local; pageable sources are staged by now
+    if (on_demand) {  // (the survivor lists are free: their own rescoring ran before the wait above)
+        SSW_TRY(launch_candidate_tiles(idx->row_start, idx->rs_pos, idx->rs_off, m, pr.surv_rows, s));
+        SSW_TRY(rescore_rows(idx, pr.q_last, pr.surv_rows, pr.surv_scores, total, idx->scores, s));
+    }
     SSW_TRY(launch_avg_score(idx->tile_boxes, idx->tile_zoom, idx->scores, minus_scores_or_null ? idx->rs_minus : nullptr,
                              idx->row_start, idx->rs_pos, idx->rs_off, m, (int32_t)max_tiles, aug_larger,
                              idx->rs_score, idx->rs_row, s));
@@ -636,9 +645,17 @@ ssw_status ssw_index_gather_scores(ssw_index *idx, const int64_t *rows_host, int
     if (n <= 0) return SSW_OK;
     SSW_REQUIRE(rows_host != nullptr && out_scores_host != nullptr, "NULL argument");
     DeviceGuard guard(idx->device);
-    SSW_TRY(ensure_full_scores(idx));
-    SSW_TRY(stage_rows(idx, rows_host, n));
-    SSW_TRY(launch_gather_f32(idx->scores, idx->gather_idx, n, idx->gather_out, idx->stream));
+    if (idx->scores_partial && n <= SURV_CAP) {
+        // after a pruned top-k: the requested rows scored with the kept query, the scan's bits; the buffer stays partial
+        SSW_TRY(stage_rows(idx, rows_host, n));
+        SSW_TRY(launch_score_rows(idx->X, idx->dtype, idx->prune.q_last, idx->gather_idx, n, idx->dim, idx->gather_out,
+                                  idx->stream));
+        idx->prune.rescored_rows += n;
+    } else {
+        SSW_TRY(ensure_full_scores(idx));
+        SSW_TRY(stage_rows(idx, rows_host, n));
+        SSW_TRY(launch_gather_f32(idx->scores, idx->gather_idx, n, idx->gather_out, idx->stream));
+    }
     SSW_HIP_TRY(hipMemcpyAsync(out_scores_host, idx->gather_out, (size_t)n * sizeof(float),
                                hipMemcpyDeviceToHost, idx->stream));
     SSW_HIP_TRY(hipStreamSynchronize(idx->stream));

@@ -126,6 +126,23 @@ static ssw_status ensure_avg_buffers(ssw_index *idx) {
     return SSW_OK;
 }
 
+// `partial_q`: `scores` is a pruned buffer or slab of that query (device), exact on its survivors only.  The tiles of the
+// result's images are made exact first -- listed by k_candidate_tiles_keys into `rows`, scored by gather through `vals`
+// (both [SURV_CAP]: survivor lists whose own rescoring is already on the stream) -- or, where k slots of max_tiles
+// entries exceed the lists, the whole of `scores` by the full scan of the query.  *completed says which.
+static ssw_status exact_tiles_of_result(ssw_index *idx, const float *partial_q, float *scores, int32_t k, int64_t *rows,
+                                        float *vals, bool *completed) {
+    const int64_t entries = (int64_t)k * idx->max_image_tiles;
+    *completed = entries > SURV_CAP || !rows || !vals;
+    if (*completed) {
+        ++idx->prune.completions;
+        return launch_scan(idx->X, idx->dtype, partial_q, scores, idx->n, idx->dim, idx->device, idx->stream);
+    }
+    SSW_TRY(launch_candidate_tiles_keys(idx->row_start, idx->n_images, idx->ws.out_keys, idx->ws.out_count, k,
+                                        (int32_t)idx->max_image_tiles, rows, idx->stream));
+    return rescore_rows(idx, partial_q, rows, vals, entries, scores, idx->stream);
+}
+
 // the aggregation of the images the selection that has just run on the stream left in the handle's result buffers,
 // over the tile scores in `scores`, into row j of the chunk's device arrays
 static ssw_status enqueue_avg_of_result(ssw_index *idx, const float *scores, int32_t k, int32_t aug, int j) {
@@ -167,10 +184,10 @@ static ssw_status check_excluded_offsets(const ssw_index *idx, const BatchExclud
 // The scores of a pruned chunk: ONE pass over the int8 shadow bounds its w queries [b, b + w), already in batch.qb_dev
 // (prune.hip, "Pruned batch"); per query a threshold selection and the survivors, one publish and ONE host wait for
 // the chunk, then exact rescoring of each query's survivors, or its full scan where the certificate failed.
-static ssw_status prune_scan_chunk(ssw_index *idx, const BatchExcluded &excl, int32_t b, int w, int32_t k) {
+// m[j]: the survivors of slot j, -1 where its slab holds the full scan.
+static ssw_status prune_scan_chunk(ssw_index *idx, const BatchExcluded &excl, int32_t b, int w, int32_t k, int32_t *m) {
     PruneState &p = idx->prune;
     PruneBatchState &pb = idx->prune_batch;
-    int32_t m[Q8_MQ_WIDTH];
     SSW_TRY(prune_bounds_mq(idx, w, nullptr, nullptr));
     SSW_HIP_TRY(hipEventRecord(p.ev, idx->stream));
     for (int j = 0; j < w; ++j) {  // threshold and survivors of each query, in stream order
@@ -200,23 +217,23 @@ static ssw_status prune_scan_chunk(ssw_index *idx, const BatchExcluded &excl, in
     return SSW_OK;
 }
 
-// The three batched top-k entries.  `pruned`: a chunk's slabs get their scores from the certified pre-scan (if the index
+// The four batched top-k entries.  `pruned`: a chunk's slabs get their scores from the certified pre-scan (if the index
 // is not eligible or its shadow is refused: from the plain scan, and the prune counters stay as they are).  With `avg`,
 // every query's selection is followed by the aggregation over its own slab; a pruned slab is exact on its survivors
-// only, so the two do not combine.
+// only, so the tiles of the selected images are rescored into it first (exact_tiles_of_result).
 static ssw_status topk_batch_run(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
                                  const int64_t *excluded_offsets, int32_t k, int64_t *out_images, float *out_scores,
                                  int64_t *out_best_rows, int32_t *out_counts, const AvgStage *avg, bool pruned) {
     SSW_REQUIRE(nq >= 1, "nq=%d < 1", nq);
     SSW_REQUIRE(idx != nullptr && q_host != nullptr && out_counts != nullptr, "NULL argument");
     SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
-    SSW_REQUIRE(!(avg && pruned), "topk_batch: no second stage over pruned slabs");
     const BatchExcluded excl{excluded_images, excluded_offsets};
     SSW_TRY(check_excluded_offsets(idx, excl, nq));
     SSW_TRY(check_query_batch(idx, q_host, nq));
     for (int32_t b = 0; b < nq; ++b) out_counts[b] = 0;
     DeviceGuard guard(idx->device);
     int W = 1;
+    if (avg && nq == 1) pruned = false;  // the single call below prunes by itself, on whichever shadow applies
     if (pruned) {
         bool ready = false;
         if (prune_batch_eligible(idx) && idx->ws.xchg.msg_out == nullptr) SSW_TRY(ensure_shadow(idx, &ready));
@@ -232,8 +249,13 @@ static ssw_status topk_batch_run(ssw_index *idx, const float *q_host, int32_t nq
         const int64_t *ex = excl.of(0, &n_ex);
         SSW_TRY(ssw_index_topk(idx, q_host, ex, n_ex, k, out_images, out_scores, out_best_rows, out_counts));
         if (!avg || idx->n_images == 0) return SSW_OK;
-        SSW_TRY(ensure_full_scores(idx));  // a pruned top-k left exact scores for its survivors only
         SSW_TRY(ensure_avg_buffers(idx));
+        if (idx->scores_partial) {  // a pruned top-k left exact scores for its survivors only
+            bool completed = false;
+            SSW_TRY(exact_tiles_of_result(idx, idx->prune.q_last, idx->scores, k, idx->prune.surv_rows,
+                                          idx->prune.surv_scores, &completed));
+            if (completed) idx->scores_partial = false;
+        }
         SSW_TRY(enqueue_avg_of_result(idx, idx->scores, k, avg->aug, 0));
         return collect_avg(idx, avg, 0, 1, k);
     } else {
@@ -241,7 +263,9 @@ static ssw_status topk_batch_run(ssw_index *idx, const float *q_host, int32_t nq
         if (avg) SSW_TRY(ensure_avg_buffers(idx));
         SSW_TRY(batch_width(idx, nq, &W));
     }
+    if (pruned && avg) SSW_TRY(ensure_avg_buffers(idx));
     const size_t dim = (size_t)idx->dim;
+    int32_t surv[Q8_MQ_WIDTH];  // of a pruned chunk's slots, -1: the slab holds the full scan
     for (int32_t b = 0; b < nq;) {
         const float *q = q_host + b * dim;
         int w = W;
@@ -249,7 +273,7 @@ static ssw_status topk_batch_run(ssw_index *idx, const float *q_host, int32_t nq
         else while (w > nq - b) w >>= 1;               // the row scan powers of two
         if (pruned) {
             SSW_TRY(idx->batch.qb_stage.push(idx->batch.qb_dev, q, (size_t)w * dim * sizeof(float), idx->stream));
-            SSW_TRY(profiled(idx, [&] { return prune_scan_chunk(idx, excl, b, w, k); }));
+            SSW_TRY(profiled(idx, [&] { return prune_scan_chunk(idx, excl, b, w, k, surv); }));
         } else if (w >= 2) {
             SSW_TRY(do_scan_chunk(idx, q, w));
         } else {  // one query: the full single-query scan (never the pre-scan) into the handle's buffer
@@ -267,6 +291,14 @@ static ssw_status topk_batch_run(ssw_index *idx, const float *q_host, int32_t nq
                                  out_scores ? out_scores + o : nullptr, out_best_rows ? out_best_rows + o : nullptr,
                                  out_counts + b + j));
             // after the collect: after a deep rerun too, and before the next query's selection takes the result buffers
+            if (avg && pruned && surv[j] >= 0) {
+                PruneBatchState &pb = idx->prune_batch;
+                bool completed = false;
+                SSW_TRY(exact_tiles_of_result(idx, idx->batch.qb_dev + (size_t)j * dim, slab, k,
+                                              pb.surv_rows + (int64_t)j * SURV_CAP, pb.surv_scores + (int64_t)j * SURV_CAP,
+                                              &completed));
+                if (completed && slab == idx->scores) idx->scores_partial = false;
+            }
             if (avg) SSW_TRY(enqueue_avg_of_result(idx, slab, k, avg->aug, j));
         }
         if (avg) SSW_TRY(collect_avg(idx, avg, b, w, k));  // (before the next chunk's scan takes the slabs)
@@ -383,12 +415,11 @@ extern "C" ssw_status ssw_index_topk_slot_deep_dev(ssw_index *idx, const float *
     return do_select_deep(idx, idx->scores, k, dest, idx->stream);
 }
 
-extern "C" {
-
-ssw_status ssw_index_topk_batch_avg(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
-                                    const int64_t *excluded_offsets, int32_t k, int32_t aug_larger, int64_t *out_images,
-                                    float *out_scores, int64_t *out_best_rows, float *out_avg_scores,
-                                    int64_t *out_avg_rows, int32_t *out_counts) {
+// the two-stage entries: the first stage plain or, `pruned`, from the certified pre-scan
+static ssw_status topk_batch_avg(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
+                                 const int64_t *excluded_offsets, int32_t k, int32_t aug_larger, int64_t *out_images,
+                                 float *out_scores, int64_t *out_best_rows, float *out_avg_scores, int64_t *out_avg_rows,
+                                 int32_t *out_counts, bool pruned) {
     SSW_REQUIRE(nq >= 1, "nq=%d < 1", nq);
     SSW_REQUIRE(idx && q_host && out_counts && out_avg_scores && out_avg_rows, "NULL argument");
     SSW_TRY(check_avg_args(idx, aug_larger, "topk_batch_avg"));
@@ -398,7 +429,25 @@ ssw_status ssw_index_topk_batch_avg(ssw_index *idx, const float *q_host, int32_t
                 SSW_RESCORE_MAX_TILES);
     const AvgStage avg{aug_larger, out_avg_scores, out_avg_rows};
     return topk_batch_run(idx, q_host, nq, excluded_images, excluded_offsets, k, out_images, out_scores, out_best_rows,
-                          out_counts, &avg, false);
+                          out_counts, &avg, pruned);
+}
+
+extern "C" {
+
+ssw_status ssw_index_topk_batch_avg(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
+                                    const int64_t *excluded_offsets, int32_t k, int32_t aug_larger, int64_t *out_images,
+                                    float *out_scores, int64_t *out_best_rows, float *out_avg_scores,
+                                    int64_t *out_avg_rows, int32_t *out_counts) {
+    return topk_batch_avg(idx, q_host, nq, excluded_images, excluded_offsets, k, aug_larger, out_images, out_scores,
+                          out_best_rows, out_avg_scores, out_avg_rows, out_counts, false);
+}
+
+ssw_status ssw_index_topk_batch_avg_pruned(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
+                                           const int64_t *excluded_offsets, int32_t k, int32_t aug_larger,
+                                           int64_t *out_images, float *out_scores, int64_t *out_best_rows,
+                                           float *out_avg_scores, int64_t *out_avg_rows, int32_t *out_counts) {
+    return topk_batch_avg(idx, q_host, nq, excluded_images, excluded_offsets, k, aug_larger, out_images, out_scores,
+                          out_best_rows, out_avg_scores, out_avg_rows, out_counts, true);
 }
 
 }  // extern "C"

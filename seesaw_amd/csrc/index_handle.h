@@ -23,6 +23,8 @@ struct PruneState {
     hipEvent_t ev = nullptr;                       // after the shadow scan: the host sleeps on it, then spins
     float *q_last = nullptr;                       // [dim] the query of the last pruned scan
     int64_t last = 0, queries = 0, fallbacks = 0;
+    // ssw_index_prune_completions: full scans that completed a partial buffer or slab, rows rescored on demand instead
+    int64_t completions = 0, rescored_rows = 0;
     // the packed 6-bit shadow of the rows (prune.hip, "6-bit shadow"): what single queries scan on an index of at least
     // PRUNE6_MIN_ROWS f32 or PRUNE6_MIN_ROWS_F16 f16 rows, instead of the int8 one; built lazily like it, with its own
     // stale / refused
@@ -134,7 +136,9 @@ struct ssw_index {
     int64_t rs_cap = 0, rs_minus_cap = 0;
     PruneState prune;           // never for a borrowed matrix or once ssw_index_device_ptrs handed out the rows
     bool rows_escaped = false;  // the row pointer was handed out: never a shadow
-    bool scores_partial = false;  // scores hold exact values for the survivors only (ensure_full_scores materialises)
+    // scores hold exact values for the survivors only: ensure_full_scores materialises, a second-stage reader makes the
+    // rows it reads exact (rescore_rows) and leaves the buffer partial
+    bool scores_partial = false;
     BatchState batch;
     PruneBatchState prune_batch;
     // profiling of the scan kernel
@@ -213,6 +217,8 @@ ssw_status ensure_prune_batch(ssw_index *idx, int w, int *out_w);
 ssw_status prune_bounds_mq(ssw_index *idx, int w, int32_t *dbg_hi, int32_t *dbg_lo);
 ssw_status prune_survivors_slot(ssw_index *idx, int w, int j, int32_t k, int64_t cap);
 ssw_status prune_publish_mq(ssw_index *idx, int w, int64_t cap, hipEvent_t sleep_ev_or_null, int32_t *out_m);
+ssw_status rescore_rows(ssw_index *idx, const float *q_dev, const int64_t *rows_dev, float *vals_dev, int64_t m, float *dst,
+                        hipStream_t stream);
 
 // index_batch.hip
 int64_t slab_stride(const ssw_index *idx);

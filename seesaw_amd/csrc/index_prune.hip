@@ -8,8 +8,8 @@ using namespace ssw;
 // ---- the certified pre-scan (prune.hip) -------------------------------------------------------
 // Top-k with a query on an index of at least PRUNE_MIN_ROWS f32 rows, or PRUNE_MIN_ROWS_F16 f16 rows, scans the int8
 // shadow instead of the rows and rescores the survivors exactly; the score buffer then holds exact scores for the
-// survivors and lower bounds elsewhere (scores_partial) until a consumer that reads it materialises the full scan of
-// the kept query.
+// survivors and lower bounds elsewhere (scores_partial) until a consumer that reads all of it materialises the full scan
+// of the kept query; the second-stage readers make exact the rows they read (rescore_rows) and leave it partial.
 constexpr int64_t PRUNE_MIN_ROWS = (int64_t)1 << 22;  // above the feedback loop's 1.56 M rows, below a rank's 12.5 M
 // f16 rows: the full scan reads half the bytes, yet the pruned call is ahead from the smallest size of the measured
 // sweep on (2^22 rows: 0.49 against 0.72 ms a call, profiles/prune_f16_sweep.txt), so the value is the f32 one.  Its
@@ -250,6 +250,18 @@ ssw_status ssw::scan_for_topk(ssw_index *idx, const float *q_dev, int32_t k) {
     });
 }
 
+// "make dst[rows] exact for query q_dev": the scan's bits of the m listed rows (any rows of the index, repeats allowed)
+// into vals_dev and from there into dst, the handle's buffer or a slab of a chunk.  What a second-stage reader of a
+// partial buffer runs on the rows it is about to read, instead of the full scan; an exact value over a lower bound or
+// over itself changes nothing for anybody else.
+ssw_status ssw::rescore_rows(ssw_index *idx, const float *q_dev, const int64_t *rows_dev, float *vals_dev, int64_t m,
+                             float *dst, hipStream_t stream) {
+    SSW_TRY(launch_score_rows(idx->X, idx->dtype, q_dev, rows_dev, m, idx->dim, vals_dev, stream));
+    SSW_TRY(launch_scatter_scores(rows_dev, vals_dev, m, dst, stream));
+    idx->prune.rescored_rows += m;
+    return SSW_OK;
+}
+
 // ---- the pruned batch: ONE pass over the int8 shadow bounds a chunk of up to 16 queries (prune.hip, "Pruned batch") ----
 static_assert(BATCH_MAX_WIDTH == Q8_MQ_WIDTH, "a chunk of the pruned batch uses the batch's slabs");
 
@@ -339,6 +351,13 @@ ssw_status ssw_index_prune_stats(ssw_index *idx, int64_t *out6) {
     out6[3] = p.queries;
     out6[4] = p.fallbacks;
     out6[5] = (p.q8 ? idx->n * (idx->dim + 8) : 0) + (p.q6 ? q6_padded_rows(idx->n) * (idx->dim * 3 / 4 + 8) : 0);
+    return SSW_OK;
+}
+
+ssw_status ssw_index_prune_completions(ssw_index *idx, int64_t *out2) {
+    SSW_REQUIRE(idx != nullptr && out2 != nullptr, "NULL argument");
+    out2[0] = idx->prune.completions;
+    out2[1] = idx->prune.rescored_rows;
     return SSW_OK;
 }
 

@@ -210,6 +210,42 @@ __global__ __launch_bounds__(RS_THREADS) void k_avg_score_keys(const float4 *__r
     avg_score_of_image<float>(boxes, zoom, scores, nullptr, r0, T, aug, c, out_score, out_row);
 }
 
+// The rows the aggregation above is about to read, as a list the gather scoring can take: candidate c's tiles at
+// rows_out[cand_off[c] ..).  One workgroup a candidate.
+__global__ __launch_bounds__(RS_THREADS) void k_candidate_tiles(const int64_t *__restrict__ row_start,
+                                                                const int64_t *__restrict__ cand_pos,
+                                                                const int64_t *__restrict__ cand_off,
+                                                                int64_t *__restrict__ rows_out) {
+    const int c = blockIdx.x;
+    const int64_t p = cand_pos[c];
+    const int64_t r0 = row_start[p];
+    const int T = (int)(row_start[p + 1] - r0);
+    int64_t *out = rows_out + cand_off[c];
+    for (int i = threadIdx.x; i < T; i += RS_THREADS) out[i] = r0 + i;
+}
+
+// The same for the result slots k_avg_score_keys reads, decoded as there: slot c's tiles at rows_out[c * max_tiles ..),
+// padded to max_tiles entries with the image's first row; a slot the selection did not fill (or a key of no image of
+// this index) lists row 0 throughout.  Every entry is a row of the index, so the list can be scored as it stands.
+__global__ __launch_bounds__(RS_THREADS) void k_candidate_tiles_keys(const int64_t *__restrict__ row_start,
+                                                                     int64_t n_images,
+                                                                     const uint64_t *__restrict__ keys,
+                                                                     const int32_t *__restrict__ count, int max_tiles,
+                                                                     int64_t *__restrict__ rows_out) {
+    const int c = blockIdx.x;
+    int64_t r0 = 0;
+    int T = 0;
+    if (c < count[0]) {
+        const int64_t p = (int64_t)(0xffffffffu - (uint32_t)(keys[c] & 0xffffffffull));
+        if (p < n_images) {
+            r0 = row_start[p];
+            T = (int)(row_start[p + 1] - r0);
+        }
+    }
+    int64_t *out = rows_out + (int64_t)c * max_tiles;
+    for (int i = threadIdx.x; i < max_tiles; i += RS_THREADS) out[i] = i < T ? r0 + i : r0;
+}
+
 }  // namespace
 
 size_t avg_score_lds_bytes(int max_tiles, size_t score_bytes) {
@@ -255,6 +291,25 @@ ssw_status launch_avg_score_keys(const float *boxes, const int32_t *zoom, const 
     hipLaunchKernelGGL(k_avg_score_keys, dim3((unsigned)k), dim3(RS_THREADS), lds, stream,
                        reinterpret_cast<const float4 *>(boxes), zoom, scores, row_start, n_images, keys, count, (int)aug,
                        out_score, out_row);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+ssw_status launch_candidate_tiles(const int64_t *row_start, const int64_t *cand_pos, const int64_t *cand_off, int32_t m,
+                                  int64_t *rows_out, hipStream_t stream) {
+    if (m <= 0) return SSW_OK;
+    hipLaunchKernelGGL(k_candidate_tiles, dim3((unsigned)m), dim3(RS_THREADS), 0, stream, row_start, cand_pos, cand_off,
+                       rows_out);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+ssw_status launch_candidate_tiles_keys(const int64_t *row_start, int64_t n_images, const uint64_t *keys,
+                                       const int32_t *count, int32_t k, int32_t max_tiles, int64_t *rows_out,
+                                       hipStream_t stream) {
+    if (k <= 0 || max_tiles <= 0) return SSW_OK;
+    hipLaunchKernelGGL(k_candidate_tiles_keys, dim3((unsigned)k), dim3(RS_THREADS), 0, stream, row_start, n_images, keys,
+                       count, (int)max_tiles, rows_out);
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
 }

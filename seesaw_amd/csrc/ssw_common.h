@@ -419,6 +419,14 @@ ssw_status launch_avg_score(const float *boxes, const int32_t *zoom, const float
 ssw_status launch_avg_score_keys(const float *boxes, const int32_t *zoom, const float *scores, const int64_t *row_start,
                                  int64_t n_images, const uint64_t *keys, const int32_t *count, int32_t k,
                                  int32_t max_tiles, int32_t aug, float *out_score, int64_t *out_row, hipStream_t stream);
+// the rows those two launches read, as row lists for launch_score_rows: candidate c's tiles at rows_out[cand_off[c] ..)
+// (the candidates' tile total entries); slot c's at rows_out[c * max_tiles ..), padded with rows of the index to
+// k * max_tiles entries in all
+ssw_status launch_candidate_tiles(const int64_t *row_start, const int64_t *cand_pos, const int64_t *cand_off, int32_t m,
+                                  int64_t *rows_out, hipStream_t stream);
+ssw_status launch_candidate_tiles_keys(const int64_t *row_start, int64_t n_images, const uint64_t *keys,
+                                       const int32_t *count, int32_t k, int32_t max_tiles, int64_t *rows_out,
+                                       hipStream_t stream);
 // the same aggregation over float64 scores that live on the device (label-propagation output)
 ssw_status launch_avg_score_f64(const float *boxes, const int32_t *zoom, const double *scores,
                                 const int64_t *row_start, const int64_t *cand_pos, const int64_t *cand_off, int32_t m,

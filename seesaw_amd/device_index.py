@@ -282,12 +282,16 @@ class DeviceIndex:
         _lib.call("ssw_index_rescore_avg", self._h, _ptr(pos), m, aug, _ptr(minus), _ptr(scores), _ptr(rows))
         return scores, rows
 
-    def topk_batch_avg(self, Q: np.ndarray, k: int, aug_larger: str, excluded=None, aug_weight: str = "level_max"):
+    def topk_batch_avg(self, Q: np.ndarray, k: int, aug_larger: str, excluded=None, aug_weight: str = "level_max",
+                       prune: bool = False):
         """both stages for a batch (ssw_index_topk_batch_avg): `topk_batch(Q, k, excluded)` and, for every query, what
         `rescore_avg(images, aug_larger, aug_weight=aug_weight)` returns for the images it selected while that query's
         scores are resident -- read from the query's own score slab inside the batch.  A list of
         (images, scores, rows, avg_scores, avg_rows), `avg_*[i]` belonging to `images[i]` (selection order, not the
-        ascending order `rescore_avg` is usually given).  The handle is left as after the last query's topk."""
+        ascending order `rescore_avg` is usually given).  The handle is left as after the last query's topk.
+        `prune=True` (ssw_index_topk_batch_avg_pruned): the first stage is `topk_batch(prune=True)`'s, and only the tiles of
+        each query's selected images are then scored exactly into its slab for the second stage -- the same results;
+        `prune_stats` counts every query and the rows rescored.  Any other index takes the plain batch."""
         k = int(k)
         Q = self._queries(Q)
         nq = Q.shape[0]
@@ -299,7 +303,8 @@ class DeviceIndex:
         avg_scs = np.empty((nq, k), dtype=np.float32)
         avg_rows = np.empty((nq, k), dtype=np.int64)
         cnt = np.zeros(nq, dtype=np.int32)
-        _lib.call("ssw_index_topk_batch_avg", self._h, _ptr(Q), nq, _ptr(ids), _ptr(offsets), k, aug, _ptr(imgs),
+        _lib.call("ssw_index_topk_batch_avg_pruned" if prune else "ssw_index_topk_batch_avg", self._h, _ptr(Q), nq,
+                  _ptr(ids), _ptr(offsets), k, aug, _ptr(imgs),
                   _ptr(scs), _ptr(rows), _ptr(avg_scs), _ptr(avg_rows), _ptr(cnt))
         return [(imgs[b, :c].copy(), scs[b, :c].copy(), rows[b, :c].copy(), avg_scs[b, :c].copy(), avg_rows[b, :c].copy())
                 for b, c in enumerate(cnt.tolist())]
@@ -405,18 +410,27 @@ class DeviceIndex:
     # -- pruned top-k ----------------------------------------------------------------
     _SHADOW_STATES = ("none", "current", "stale", "refused")
 
-    def prune_stats(self) -> dict:
+    def prune_stats(self, completions: bool = False) -> dict:
         """state of the certified pre-scan of `topk` with a query (ssw_index_prune_stats).  `shadow` describes the
         shadow single queries scan -- the packed 6-bit one on an index of at least 2^24 f32 or 2^25 float16 rows, else
         the int8 one: "none", "current", "stale" (the rows changed since it was built; the next pruned call rebuilds
         it) or "refused" (too little free device memory beside it); `eligible`: the next top-k with a query is pruned;
         `last_survivors`: rows the last pruned call rescored (-1 = it fell back to the full scan); `queries` /
         `fallbacks`: pruned calls and how many of them fell back; `shadow_bytes`: device memory the shadows hold
-        (dim + 8 bytes a row for the int8 one, 3 dim / 4 + 8 for the 6-bit one; a pruned batch builds the int8 one)"""
+        (dim + 8 bytes a row for the int8 one, 3 dim / 4 + 8 for the 6-bit one; a pruned batch builds the int8 one).
+        `completions=True` adds the two words of ssw_index_prune_completions (the six above stay what they were for
+        callers that compare the whole dict): `completions`: full scans that completed a partial score buffer or slab
+        for a reader; `rescored_rows`: rows the second-stage readers (`rescore_avg`, `gather_scores`, `topk_batch_avg`)
+        scored exactly on demand instead"""
         out = np.zeros(6, dtype=np.int64)
         _lib.call("ssw_index_prune_stats", self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
-        return {"shadow": self._SHADOW_STATES[int(out[0])], "eligible": bool(out[1]), "last_survivors": int(out[2]),
-                "queries": int(out[3]), "fallbacks": int(out[4]), "shadow_bytes": int(out[5])}
+        st = {"shadow": self._SHADOW_STATES[int(out[0])], "eligible": bool(out[1]), "last_survivors": int(out[2]),
+              "queries": int(out[3]), "fallbacks": int(out[4]), "shadow_bytes": int(out[5])}
+        if completions:
+            more = np.zeros(2, dtype=np.int64)
+            _lib.call("ssw_index_prune_completions", self._h, more.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
+            st.update(completions=int(more[0]), rescored_rows=int(more[1]))
+        return st
 
     # -- profiling --------------------------------------------------------------------
     def profile(self, enable: bool):

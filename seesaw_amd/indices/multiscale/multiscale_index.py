@@ -323,7 +323,7 @@ class MultiscaleIndex(AccessMethod):
         return np.concatenate([np.arange(self._row_start[p], self._row_start[p + 1]) for p in positions]) \
             if positions.size else np.zeros(0, dtype=np.int64)
 
-    def query_batch(self, *, topk, vectors, excludes=None, **kwargs):
+    def query_batch(self, *, topk, vectors, excludes=None, prune=False, **kwargs):
         """`[query(vector=v, topk=topk, exclude=e, **kwargs) for v, e in zip(vectors, excludes)]`, entry by entry
         identical to it, with the rows read once per chunk of up to 16 queries: `plain_score` ends in
         `DeviceIndex.topk_batch`, every other agg_method in `DeviceIndex.topk_batch_avg`, whose second stage reads each
@@ -332,11 +332,13 @@ class MultiscaleIndex(AccessMethod):
         an exclude set that covers the index, and the whole call when `vector2` is given, when the index has no tile
         geometry on the device (the host-side `rescore_candidates` path) or holds an image of more tiles than the
         kernel takes.  Afterwards `_resident_q` names the query whose scores are resident.
-        A batch always scans in full precision: on an index large enough for the single `query` to be pruned
-        (>= 2^22 rows) a small batch is expected to be slower per query than the loop (`topk_batch` against the
-        pruned `topk` crosses over at nq = 4 to 8; this method itself is not measured yet, DESIGN.md section 4,
-        "Batched multiscale query") -- callers who want the pruned single path call `query`.  The `vector2` form and the
-        pruned batch remain a follow-up (the sharded index batches its first stage: `ShardedMultiscaleIndex`)."""
+        `prune` is `DeviceIndex.topk_batch`'s and `DeviceIndex.topk_batch_avg`'s: the same results from the shared int8
+        pre-scan on an index large enough for it, the second stage on the exactly rescored tiles of each query's
+        candidates.  It is consumed here: the entries that keep going through `query` never see it.  Without it a
+        batch scans in full precision: on an index large enough for the single `query` to be pruned (>= 2^22 rows) a
+        small batch is slower per query than the loop (at 2^22 f32 rows it crosses over between nq = 4 and 8, while
+        the pruned batch is ahead from nq = 2: DESIGN.md section 10, "Pruned two-stage query").  The `vector2` form remains a follow-up (the sharded index batches its first stage:
+        `ShardedMultiscaleIndex`)."""
         vectors = list(vectors)
         excludes = [None] * len(vectors) if excludes is None else list(excludes)
         if len(excludes) != len(vectors):
@@ -366,13 +368,15 @@ class MultiscaleIndex(AccessMethod):
         ks = [min(int(shortlist_size), n - excl_pos[i].shape[0]) for i in batch]
         excluded = [excl_pos[i] for i in batch]
         if plain:
-            for i, k_i, (pos, scores, best_rows) in zip(batch, ks, self._dev.topk_batch(Q, max(ks), excluded=excluded)):
+            for i, k_i, (pos, scores, best_rows) in zip(batch, ks, self._dev.topk_batch(Q, max(ks), excluded=excluded,
+                                                                                  prune=prune)):
                 cand = _Candidates(self._dbidx[pos[:k_i]], scores[:k_i], pos[:k_i], best_rows[:k_i])
                 out[i] = self._activations_from_best(cand, topk)
         else:
             aug_weight = kwargs.get("aug_weight", "level_max")
             assert aug_weight in ("level_max", "cont_weighted"), aug_weight  # score_frame2's `assert False`
-            res = self._dev.topk_batch_avg(Q, max(ks), kwargs["aug_larger"], excluded=excluded, aug_weight=aug_weight)
+            res = self._dev.topk_batch_avg(Q, max(ks), kwargs["aug_larger"], excluded=excluded, aug_weight=aug_weight,
+                                           prune=prune)
             for i, k_i, (pos, _, _, avg_scores, avg_rows) in zip(batch, ks, res):
                 order = np.argsort(pos[:k_i])  # rescore_candidates walks the frames in ascending dbidx order
                 out[i] = self._avg_result(pos[:k_i][order], avg_scores[:k_i][order], avg_rows[:k_i][order], topk)
