@@ -331,7 +331,7 @@ ssw_status ssw_topk_merge_msgs_dev(int32_t device, void *hip_stream, const uint6
  * without images writes "0 keys" into its slots.
  * State afterwards: that of ssw_index_topk_dev(q[nq-1]) with the last query's exclusion set installed (resident scores,
  * result buffers, installed set).  ssw_index_profile records one event pair per scan launch.
- * Not measured yet ("Sharded batch"; tools/perf_sharded_batch.py takes the figures).
+ * Measured with tools/perf_sharded_batch.py ("Sharded batch").
  *
  * ssw_index_topk_slot_deep_dev: the repair of ONE flagged query: a single-query full scan of q_host (the slabs of the
  * chunk are gone by the time the flags are read; the batched scan returns the bits of the single scan, so the result
@@ -350,6 +350,28 @@ ssw_status ssw_index_topk_batch_dev(ssw_index *idx, const float *q_host, int32_t
                                     const int64_t *excluded_offsets, int32_t k, int32_t first_slot);
 ssw_status ssw_index_topk_slot_deep_dev(ssw_index *idx, const float *q_host, const int64_t *excluded_images,
                                         int64_t n_excluded, int32_t k, int32_t slot);
+
+/* ssw_index_topk_batch_dev with the certified int8 pre-scan of ssw_index_topk_batch_pruned, and still ENQUEUE ONLY: no
+ * survivor count is published and nothing waits for the device.  Arguments, refusals and the empty index are
+ * ssw_index_topk_batch_dev's.  On an index the pruned batch does not serve (fewer than 2^22 rows, dim other than 256 /
+ * 512 / 1024, borrowed or escaped rows, a shadow refused for memory) the call IS ssw_index_topk_batch_dev.  Otherwise,
+ * per chunk of up to 16 queries (any width): one pass over the shadow bounds the chunk; per query the threshold
+ * selection and the survivor list; ONE launch (k_rescore_survivors, csrc/rescore_dev.hip), sized by the device alone,
+ * scores every certified slot's survivors -- the full scan's bits -- straight into its slab; per query the ordinary
+ * selection writes message slot first_slot + b.  A slot whose certificate failed (threshold selection short of k keys or
+ * overflowed, unboundable query, more than 2^18 survivors) is NOT repaired here: its selection ran over bounds and BIT
+ * 33 (value 2 in the upper half) of its message's last word says so, beside the overflow bit 32.  The merge reports
+ * either as a non-zero flag of that (query, rank), and ssw_index_topk_slot_deep_dev repairs either exactly.
+ * State afterwards: that of ssw_index_topk_batch_dev, except that the score buffer is partial with the last query kept
+ * (every reader completes or rescores it by the rules of the pruned top-k), and ssw_index_prune_stats counts every
+ * query in [3]; [2] and [4] stay, the host does not know them.
+ * ssw_index_prune_batch_dev_read: what the device decided for the LAST chunk of the last such call: waits for the
+ * stream, then out32 [2 * 16]: for slot j < *out_w, out32[2 j] = the raw survivor count (it passes the cap when more
+ * rows qualify) and out32[2 j + 1] = the reasons it failed: 1 threshold selection, 2 unboundable query, 4 over the cap;
+ * 0 = certified.  *out_w = 0 when the last call took the plain scan or a host-waiting pruned batch ran since. */
+ssw_status ssw_index_topk_batch_dev_pruned(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
+                                           const int64_t *excluded_offsets, int32_t k, int32_t first_slot);
+ssw_status ssw_index_prune_batch_dev_read(ssw_index *idx, int32_t *out32, int32_t *out_w);
 ssw_status ssw_topk_merge_msgs_batch_dev(int32_t device, void *hip_stream, const uint64_t *dev_msgs, int32_t world,
                                          int64_t rank_stride, int32_t nq, int32_t k_max, int32_t with_best, int32_t k,
                                          uint64_t *dev_keys_out, int32_t *dev_counts_out, int64_t *dev_flags_or_null,

@@ -119,6 +119,21 @@ ssw_status ssw_debug_prune_survivors_mq(ssw_index *idx, int32_t nq, int32_t slot
                                         int32_t sel_count, int32_t sel_overflow, int64_t cap, int32_t *out_published,
                                         int64_t *out_collected, int64_t *out_rows);
 
+/* The pruned batch that stays on the device (seesaw_hip.h, ssw_index_topk_batch_dev_pruned; csrc/rescore_dev.hip).
+ * ssw_tune_surv_cap: the survivors a slot of that entry may have and still be certified, 1 .. 2^18; any other value =
+ *   the product's 2^18.  Governs that entry and the hook below only.
+ * ssw_debug_rescore_survivors: k_rescore_survivors alone, through the product's launch function, on the index's own
+ *   chunk buffers (dim 256 / 512 / 1024; no shadow is needed).  nq <= 16 host queries [nq, dim]; slot j's state words
+ *   are set to counts[j] survivors, "selection failed" = fail_bits[j] & 1, "unboundable" = (fail_bits[j] >> 1) & 1;
+ *   its list is the next min(counts[j], cap) entries of rows_host (the lists lie end to end; rows in [0, n), repeats
+ *   allowed), cap being ssw_tune_surv_cap's.  Every slab is filled with the f32 of bits 0x7FC0BEEF first;
+ *   out_slabs_host [nq, n] receives the slabs after the launch and *out_waves the waves a slot had in it.  The
+ *   handle's score buffer is left as after ssw_index_scan of the last query. */
+ssw_status ssw_tune_surv_cap(int64_t cap);
+ssw_status ssw_debug_rescore_survivors(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *rows_host,
+                                       const int64_t *counts, const int32_t *fail_bits, float *out_slabs_host,
+                                       int32_t *out_waves);
+
 /* Kernel A/B harness for the towers' bf16 GEMM (C[M,N] = A[M,K] W[N,K]^T + epilogue `epi`, see
  * csrc/gemm_bf16.hip): runs `variant` on seeded operands, reports ms per launch over `iters`
  * launches and the max |difference| to variant 0.  Not part of the reference's interface. */

@@ -148,6 +148,8 @@ _SIGNATURES = {
     "ssw_index_set_exchange_target_batch": (c_i32, [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_i64, c_i64]),
     "ssw_index_topk_batch_dev": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_i32]),
     "ssw_index_topk_slot_deep_dev": (c_i32, [c_void_p, c_void_p, c_void_p, c_i64, c_i32, c_i32]),
+    "ssw_index_topk_batch_dev_pruned": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_i32]),
+    "ssw_index_prune_batch_dev_read": (c_i32, [c_void_p, c_i32_p, c_i32_p]),
     "ssw_topk_merge_msgs_batch_dev": (c_i32, [c_i32, c_void_p, c_void_p, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_void_p,
                                               c_void_p, c_void_p, c_void_p]),
     "ssw_comm_unique_id": (c_i32, [c_void_p]),
@@ -173,6 +175,8 @@ _DEBUG_SIGNATURES = {
     "ssw_debug_prune_bounds_mq": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ssw_debug_prune_survivors_mq": (c_i32, [c_void_p, c_i32, c_i32, ctypes.c_float, c_i32, c_i32, c_i32, c_i64, c_i32_p,
                                              c_i64_p, c_void_p]),
+    "ssw_tune_surv_cap": (c_i32, [c_i64]),
+    "ssw_debug_rescore_survivors": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_i32_p]),
     "ssw_debug_prune_shadow": (c_i32, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p]),
     "ssw_debug_prune_bounds": (c_i32, [c_void_p, c_void_p, c_void_p, c_f32_p, c_i32_p]),
     "ssw_debug_prune_survivors": (c_i32, [c_void_p, ctypes.c_float, c_i32, c_i32, c_i32, c_i64, c_i32_p, c_i64_p,

@@ -2,6 +2,8 @@
 #ifndef SSW_DEBUG_HOOKS
 #error "debug_hooks.hip belongs to the lab build (-DSSW_DEBUG_HOOKS)"
 #endif
+#include <algorithm>
+
 #include "index_handle.h"
 
 // ---------------------------------------------------------------------------------------
@@ -514,6 +516,67 @@ ssw_status ssw_debug_prune_survivors_mq(ssw_index *idx, int32_t nq, int32_t slot
     SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
     *out_published = m[slot];
     *out_collected = (int64_t)collected;
+    return SSW_OK;
+}
+
+// ---- the device-sized rescoring alone (rescore_dev.hip; tests/test_rescore_dev_gpu.py) --------------------------------
+__global__ void k_fill_u32(unsigned *__restrict__ p, int64_t n, unsigned v) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = v;
+}
+
+ssw_status ssw_debug_rescore_survivors(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *rows_host,
+                                       const int64_t *counts, const int32_t *fail_bits, float *out_slabs_host,
+                                       int32_t *out_waves) {
+    SSW_REQUIRE(idx && q_host && counts && fail_bits && out_slabs_host && out_waves, "NULL argument");
+    SSW_REQUIRE(nq >= 1 && nq <= Q8_MQ_WIDTH, "nq=%d outside [1, %d]", nq, Q8_MQ_WIDTH);
+    SSW_REQUIRE(q8_dim_supported(idx->dim) && idx->n >= 1, "dim=%d or n=%lld has no pruned chunk", idx->dim, (long long)idx->n);
+    const int64_t cap = batch_dev_surv_cap();
+    int64_t listed = 0;
+    for (int j = 0; j < nq; ++j) {
+        SSW_REQUIRE(counts[j] >= 0 && counts[j] <= 0x7fffffff, "counts[%d]=%lld", j, (long long)counts[j]);
+        listed += std::min(counts[j], cap);
+    }
+    SSW_REQUIRE(listed == 0 || rows_host != nullptr, "rows_host is NULL");
+    for (int64_t i = 0; i < listed; ++i)
+        SSW_REQUIRE(rows_host[i] >= 0 && rows_host[i] < idx->n, "rows_host[%lld]=%lld outside [0, %lld)", (long long)i,
+                    (long long)rows_host[i], (long long)idx->n);
+    DeviceGuard guard(idx->device);
+    int w = 0;
+    SSW_TRY(batch_buffers(idx, nq, true, &w));
+    if (w == nq && idx->batch.qb_dev) SSW_TRY(ensure_prune_batch(idx, nq, &w));
+    if (w != nq || !idx->batch.qb_dev) {
+        set_error("rescore_survivors: no memory for a chunk of %d queries", nq);
+        return SSW_ERR_NOMEM;
+    }
+    PruneBatchState &pb = idx->prune_batch;
+    pb.dev_w = 0;
+    std::vector<unsigned> mq((size_t)Q8_MQ_WIDTH * Q8_MQ_WORDS, 0u);
+    const size_t dim = (size_t)idx->dim;
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));  // the copies below read pageable host memory
+    const int64_t *list = rows_host;
+    for (int j = 0; j < nq; ++j) {
+        unsigned *st = mq.data() + (size_t)j * Q8_MQ_WORDS;
+        st[0] = (unsigned)counts[j];
+        st[5] = (unsigned)(fail_bits[j] & 1);
+        st[2] = (unsigned)((fail_bits[j] >> 1) & 1);
+        const int64_t m = std::min(counts[j], cap);
+        if (m > 0)
+            SSW_HIP_TRY(hipMemcpyAsync(pb.surv_rows + (int64_t)j * SURV_CAP, list, (size_t)m * sizeof(int64_t),
+                                       hipMemcpyHostToDevice, idx->stream));
+        list += m;
+        hipLaunchKernelGGL(k_fill_u32, dim3(256), dim3(256), 0, idx->stream,
+                           reinterpret_cast<unsigned *>(chunk_slab(idx, nq, j)), idx->n, 0x7FC0BEEFu);
+        SSW_HIP_TRY(hipGetLastError());
+    }
+    SSW_HIP_TRY(hipMemcpyAsync(pb.mq, mq.data(), mq.size() * sizeof(unsigned), hipMemcpyHostToDevice, idx->stream));
+    SSW_HIP_TRY(hipMemcpyAsync(idx->batch.qb_dev, q_host, (size_t)nq * dim * sizeof(float), hipMemcpyHostToDevice, idx->stream));
+    SSW_TRY(rescore_survivors_chunk(idx, nq, cap));
+    for (int j = 0; j < nq; ++j)
+        SSW_HIP_TRY(hipMemcpyAsync(out_slabs_host + (size_t)j * idx->n, chunk_slab(idx, nq, j), (size_t)idx->n * sizeof(float),
+                                   hipMemcpyDeviceToHost, idx->stream));
+    SSW_TRY(do_scan(idx, idx->batch.qb_dev + (size_t)(nq - 1) * dim));  // the buffer held the sentinel
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+    *out_waves = rescore_survivors_waves(idx->device, cap);
     return SSW_OK;
 }
 

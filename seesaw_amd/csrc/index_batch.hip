@@ -188,6 +188,7 @@ static ssw_status check_excluded_offsets(const ssw_index *idx, const BatchExclud
 static ssw_status prune_scan_chunk(ssw_index *idx, const BatchExcluded &excl, int32_t b, int w, int32_t k, int32_t *m) {
     PruneState &p = idx->prune;
     PruneBatchState &pb = idx->prune_batch;
+    pb.dev_w = 0;  // the state words are this chunk's from here on
     SSW_TRY(prune_bounds_mq(idx, w, nullptr, nullptr));
     SSW_HIP_TRY(hipEventRecord(p.ev, idx->stream));
     for (int j = 0; j < w; ++j) {  // threshold and survivors of each query, in stream order
@@ -352,9 +353,37 @@ static ssw_status empty_slots(ssw_index *idx, int32_t first, int32_t n) {
     return SSW_OK;
 }
 
-extern "C" ssw_status ssw_index_topk_batch_dev(ssw_index *idx, const float *q_host, int32_t nq,
-                                               const int64_t *excluded_images, const int64_t *excluded_offsets,
-                                               int32_t k, int32_t first_slot) {
+// The chunk of w queries [b, b + w) of ssw_index_topk_batch_dev_pruned, already in batch.qb_dev: prune_scan_chunk without
+// its host wait.  The bounds of all w queries from one pass over the int8 shadow; per slot the threshold selection (no
+// message, no host result) and the survivors; ONE launch scores every certified slot's survivors into its slab
+// (rescore_dev.hip).  Nothing is published: which slots failed their certificate stays on the device, where
+// launch_mark_uncertified tells the slot's message after the selection.
+static ssw_status prune_scan_chunk_dev(ssw_index *idx, const BatchExcluded &excl, int32_t b, int w, int32_t k, int64_t cap) {
+    PruneBatchState &pb = idx->prune_batch;
+    pb.dev_w = w;
+    pb.dev_cap = cap;
+    SSW_TRY(prune_bounds_mq(idx, w, nullptr, nullptr));
+    const FinalExchange none;  // (not ws.xchg either: a single target may be attached beside the batch target)
+    for (int j = 0; j < w; ++j) {
+        int64_t n_ex = 0;
+        const int64_t *ex = excl.of(b + j, &n_ex);
+        SSW_TRY(install_excluded(idx, ex, n_ex, idx->stream));
+        SelectDest quiet;
+        quiet.message = false;
+        quiet.target = &none;
+        SSW_TRY(do_select(idx, chunk_slab(idx, w, j), k, quiet, idx->stream));
+        SSW_TRY(prune_survivors_slot(idx, w, j, k, cap));
+    }
+    SSW_TRY(rescore_survivors_chunk(idx, w, cap));
+    idx->prune.queries += w;  // (last_survivors and fallbacks: the host does not know them)
+    return SSW_OK;
+}
+
+// The two batched top-k entries that stay on the device.  `pruned`: a chunk's slabs get their scores from the certified
+// pre-scan without a host wait (if the index is not eligible or its shadow is refused: from the plain scan, and the
+// call is ssw_index_topk_batch_dev).
+static ssw_status topk_batch_dev_run(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
+                                     const int64_t *excluded_offsets, int32_t k, int32_t first_slot, bool pruned) {
     SSW_REQUIRE(nq >= 1, "nq=%d < 1", nq);
     SSW_REQUIRE(idx != nullptr && q_host != nullptr, "NULL argument");
     SSW_TRY(check_batch_target(idx, k, first_slot, nq, "topk_batch_dev"));
@@ -363,16 +392,34 @@ extern "C" ssw_status ssw_index_topk_batch_dev(ssw_index *idx, const float *q_ho
     SSW_TRY(check_query_batch(idx, q_host, nq));
     DeviceGuard guard(idx->device);
     if (idx->n_images == 0) return empty_slots(idx, first_slot, nq);
-    SSW_TRY(ensure_full_scores(idx));
-    SSW_TRY(ensure_ws(idx));
     int W = 1;
-    SSW_TRY(batch_width(idx, nq, &W));
+    if (pruned) {
+        bool ready = false;
+        idx->prune_batch.dev_w = 0;  // until a chunk of this call says otherwise
+        if (prune_batch_eligible(idx)) SSW_TRY(ensure_shadow(idx, &ready));
+        if (ready) SSW_TRY(batch_buffers(idx, std::min<int32_t>(nq, Q8_MQ_WIDTH), true, &W));
+        pruned = ready && idx->batch.qb_dev;
+    }
+    if (pruned) {
+        // (a partial buffer is not completed first: every chunk overwrites it and the kept query together)
+        SSW_TRY(ensure_ws(idx));
+        SSW_TRY(ensure_prune_batch(idx, W, &W));
+    } else {
+        SSW_TRY(ensure_full_scores(idx));
+        SSW_TRY(ensure_ws(idx));
+        SSW_TRY(batch_width(idx, nq, &W));
+    }
+    const int64_t cap = batch_dev_surv_cap();
     const size_t dim = (size_t)idx->dim;
     for (int32_t b = 0; b < nq;) {
         const float *q = q_host + b * dim;
         int w = W;
-        while (w > nq - b) w >>= 1;
-        if (w >= 2) {
+        if (pruned) w = std::min<int32_t>(W, nq - b);  // the shadow scan takes any width,
+        else while (w > nq - b) w >>= 1;               // the row scan powers of two
+        if (pruned) {
+            SSW_TRY(idx->batch.qb_stage.push(idx->batch.qb_dev, q, (size_t)w * dim * sizeof(float), idx->stream));
+            SSW_TRY(profiled(idx, [&] { return prune_scan_chunk_dev(idx, excl, b, w, k, cap); }));
+        } else if (w >= 2) {
             SSW_TRY(do_scan_chunk(idx, q, w));
         } else {  // one query: the full single-query scan (never the pre-scan) into the handle's buffer
             w = 1;
@@ -387,10 +434,25 @@ extern "C" ssw_status ssw_index_topk_batch_dev(ssw_index *idx, const float *q_ho
             SelectDest dest;
             dest.target = &slot;
             SSW_TRY(do_select(idx, chunk_slab(idx, w, j), k, dest, idx->stream));
+            if (pruned)  // a slot that failed its certificate selected among bounds: bit 33 of its last word says so
+                SSW_TRY(launch_mark_uncertified(idx->prune_batch.mq + j * Q8_MQ_WORDS, cap,
+                                                slot.msg_out + (slot.msg_len - 1), idx->stream));
         }
         b += w;
     }
     return SSW_OK;
+}
+
+extern "C" ssw_status ssw_index_topk_batch_dev(ssw_index *idx, const float *q_host, int32_t nq,
+                                               const int64_t *excluded_images, const int64_t *excluded_offsets,
+                                               int32_t k, int32_t first_slot) {
+    return topk_batch_dev_run(idx, q_host, nq, excluded_images, excluded_offsets, k, first_slot, false);
+}
+
+extern "C" ssw_status ssw_index_topk_batch_dev_pruned(ssw_index *idx, const float *q_host, int32_t nq,
+                                                      const int64_t *excluded_images, const int64_t *excluded_offsets,
+                                                      int32_t k, int32_t first_slot) {
+    return topk_batch_dev_run(idx, q_host, nq, excluded_images, excluded_offsets, k, first_slot, true);
 }
 
 extern "C" ssw_status ssw_index_topk_slot_deep_dev(ssw_index *idx, const float *q_host, const int64_t *excluded_images,

@@ -62,6 +62,10 @@ struct PruneBatchState {
     int slots = 0;
     int32_t *host = nullptr;       // pinned, mapped: [seq, survivors or -1 of each slot]
     unsigned seq = 0;
+    // the last chunk of ssw_index_topk_batch_dev_pruned, for ssw_index_prune_batch_dev_read: its width (0: the words
+    // above are not such a chunk's) and the cap its slots were held to
+    int dev_w = 0;
+    int64_t dev_cap = 0;
     void release() {
         for (void *p : {(void *)mq, (void *)planes, (void *)surv_rows, (void *)surv_scores}) (void)hipFree(p);
         if (host) (void)hipHostFree(host);
@@ -219,6 +223,8 @@ ssw_status prune_survivors_slot(ssw_index *idx, int w, int j, int32_t k, int64_t
 ssw_status prune_publish_mq(ssw_index *idx, int w, int64_t cap, hipEvent_t sleep_ev_or_null, int32_t *out_m);
 ssw_status rescore_rows(ssw_index *idx, const float *q_dev, const int64_t *rows_dev, float *vals_dev, int64_t m, float *dst,
                         hipStream_t stream);
+int64_t batch_dev_surv_cap();
+ssw_status rescore_survivors_chunk(ssw_index *idx, int w, int64_t cap);
 
 // index_batch.hip
 int64_t slab_stride(const ssw_index *idx);

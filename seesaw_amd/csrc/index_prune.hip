@@ -37,6 +37,7 @@ static SSW_TUNABLE bool g_prune6 = true;              // ssw_tune_prune6
 static SSW_TUNABLE int64_t g_prune6_min_rows = -1;     // >= 0: this many rows for both dtypes instead
 static SSW_TUNABLE int64_t g_prune_min_rows = -1;      // >= 0: this many rows for both dtypes instead
 static SSW_TUNABLE int64_t g_prune_reserve = PRUNE_RESERVE;
+static SSW_TUNABLE int64_t g_surv_cap_dev = SURV_CAP;  // ssw_tune_surv_cap: of ssw_index_topk_batch_dev_pruned only
 
 static bool prune_forced_off() {
     static const bool v = getenv("SSW_TOPK_FULL_SCAN") != nullptr;  // A/B: every top-k runs the full f32 scan
@@ -337,7 +338,37 @@ ssw_status ssw::prune_publish_mq(ssw_index *idx, int w, int64_t cap, hipEvent_t 
     return SSW_OK;
 }
 
+// ---- the chunk that never waits (ssw_index_topk_batch_dev_pruned, index_batch.hip) ------------------------------------
+int64_t ssw::batch_dev_surv_cap() { return g_surv_cap_dev; }
+
+// exact scores of the survivors of every certified slot of the chunk of w, straight into the slabs: ONE launch, sized
+// without a count from the device (rescore_dev.hip); the lab hook drives it as well
+ssw_status ssw::rescore_survivors_chunk(ssw_index *idx, int w, int64_t cap) {
+    PruneBatchState &pb = idx->prune_batch;
+    return launch_rescore_survivors(idx->X, idx->dtype, idx->batch.qb_dev, pb.mq, pb.surv_rows, SURV_CAP, cap, w,
+                                    idx->batch.side, slab_stride(idx), idx->scores, idx->n, idx->dim, idx->device,
+                                    idx->stream);
+}
+
 extern "C" {
+
+ssw_status ssw_index_prune_batch_dev_read(ssw_index *idx, int32_t *out32, int32_t *out_w) {
+    SSW_REQUIRE(idx != nullptr && out32 != nullptr && out_w != nullptr, "NULL argument");
+    const PruneBatchState &pb = idx->prune_batch;
+    *out_w = 0;
+    if (pb.dev_w <= 0 || !pb.mq) return SSW_OK;
+    DeviceGuard guard(idx->device);
+    unsigned mq[Q8_MQ_WIDTH * Q8_MQ_WORDS];
+    SSW_HIP_TRY(hipMemcpyAsync(mq, pb.mq, sizeof(mq), hipMemcpyDeviceToHost, idx->stream));
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+    for (int j = 0; j < pb.dev_w; ++j) {
+        const unsigned *st = mq + j * Q8_MQ_WORDS;
+        out32[2 * j] = (int32_t)st[0];
+        out32[2 * j + 1] = (st[5] != 0u ? 1 : 0) | (st[2] != 0u ? 2 : 0) | ((int64_t)st[0] > pb.dev_cap ? 4 : 0);
+    }
+    *out_w = pb.dev_w;
+    return SSW_OK;
+}
 
 ssw_status ssw_index_prune_stats(ssw_index *idx, int64_t *out6) {
     SSW_REQUIRE(idx != nullptr && out6 != nullptr, "NULL argument");
@@ -366,6 +397,11 @@ ssw_status ssw_tune_prune(int32_t enable, int64_t min_rows, int64_t reserve_byte
     g_prune = enable != 0;
     g_prune_min_rows = min_rows < 0 ? -1 : min_rows;  // < 0: PRUNE_MIN_ROWS / PRUNE_MIN_ROWS_F16 again
     g_prune_reserve = reserve_bytes < 0 ? PRUNE_RESERVE : reserve_bytes;
+    return SSW_OK;
+}
+
+ssw_status ssw_tune_surv_cap(int64_t cap) {
+    g_surv_cap_dev = cap >= 1 && cap <= SURV_CAP ? cap : SURV_CAP;
     return SSW_OK;
 }
 

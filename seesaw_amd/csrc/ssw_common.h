@@ -196,6 +196,16 @@ ssw_status launch_survivors_mq(const float *lb, const float *err, const float *s
                                int64_t *rows, int64_t cap, int device, hipStream_t stream);
 ssw_status launch_prune_publish_mq(const unsigned *mq, int32_t w, int64_t cap, int32_t *host_block, unsigned seq,
                                    hipStream_t stream);
+// rescore_dev.hip: the exact scores (launch_scan's bits) of every certified slot's survivors in ONE launch sized by the
+// device alone: slot j < w reads mq + j * Q8_MQ_WORDS and, unless it failed ([5] | [2] | [0] > cap), scores the first
+// [0] rows of lists + j * list_stride for query qb_dev + j * dim straight into its slab (side + j * stride, the last
+// one `own`).  rescore_survivors_waves: the waves a slot gets in that launch.  mark_uncertified: one thread ORs bit 33
+// into a message's last word if the slot failed.
+ssw_status launch_rescore_survivors(const void *X, int32_t dtype, const float *qb_dev, const unsigned *mq,
+                                    const int64_t *lists, int64_t list_stride, int64_t cap, int32_t w, float *side,
+                                    int64_t stride, float *own, int64_t n, int32_t dim, int device, hipStream_t stream);
+int rescore_survivors_waves(int device, int64_t cap);
+ssw_status launch_mark_uncertified(const unsigned *slot_state, int64_t cap, uint64_t *msg_last_word, hipStream_t stream);
 // blocks and 16-row tiles per request of the launch launch_q8_bounds_mq would make
 void q8_bounds_mq_shape(int32_t dim, int device, int64_t n, int *out_blocks, int *out_tiles);
 // the packed 6-bit shadow of f32 or f16 rows (prune.hip, "6-bit shadow"): tiles of 16 rows, 3 dim / 4 bytes a row, buffers

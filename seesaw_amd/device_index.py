@@ -347,15 +347,32 @@ class DeviceIndex:
         _lib.call("ssw_index_set_exchange_target_batch", self._h, ctypes.c_void_p(dev_msgs_ptr) if dev_msgs_ptr else None,
                   int(n_slots), int(k_max), int(bool(with_best)), int(image_offset), int(row_offset))
 
-    def topk_batch_dev(self, Q: np.ndarray, k: int, excluded=None, first_slot: int = 0):
+    def topk_batch_dev(self, Q: np.ndarray, k: int, excluded=None, first_slot: int = 0, prune: bool = False):
         """`topk_batch` that stays on the device (ssw_index_topk_batch_dev; enqueue only): the rows are read once per
         chunk of queries and query b's selection writes its exchange message into slot `first_slot + b` of the attached
         block.  An overflowed selection is not repaired: its flag travels in the slot (`topk_slot_deep_dev`).  The
-        handle is left as after `topk_dev` of the last query with its exclusion list."""
+        handle is left as after `topk_dev` of the last query with its exclusion list.
+        `prune=True` (ssw_index_topk_batch_dev_pruned): on an index the pruned batch serves, one pass over the int8 shadow
+        bounds a chunk of up to 16 queries and one launch scores every query's survivors exactly, still without a host
+        wait.  A query whose certificate failed on this shard is flagged with the value 2 in its slot and repaired the
+        same way; `prune_batch_dev_counts` reads what the device decided.  Any other index takes the plain call."""
         Q = self._queries(Q)
         nq = Q.shape[0]
         ids, offsets = self._excluded_batch(excluded, nq)
-        _lib.call("ssw_index_topk_batch_dev", self._h, _ptr(Q), nq, _ptr(ids), _ptr(offsets), int(k), int(first_slot))
+        _lib.call("ssw_index_topk_batch_dev_pruned" if prune else "ssw_index_topk_batch_dev", self._h, _ptr(Q), nq,
+                  _ptr(ids), _ptr(offsets), int(k), int(first_slot))
+
+    def prune_batch_dev_counts(self):
+        """what the device decided for the last chunk of the last `topk_batch_dev(prune=True)`
+        (ssw_index_prune_batch_dev_read; synchronises): (survivors int64 [w], fail_bits int32 [w]) -- the raw survivor
+        count of each slot and why it was not certified (1 threshold selection failed, 2 unboundable query, 4 more
+        survivors than the cap; 0 = certified).  w = 0 when that call took the plain scan."""
+        out = np.zeros(32, dtype=np.int32)
+        w = ctypes.c_int32(0)
+        _lib.call("ssw_index_prune_batch_dev_read", self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                  ctypes.byref(w))
+        pairs = out[:2 * w.value].reshape(-1, 2)
+        return pairs[:, 0].astype(np.int64), pairs[:, 1].copy()
 
     def topk_slot_deep_dev(self, q: np.ndarray, k: int, excluded: Optional[Iterable[int]], slot: int):
         """the repair of one flagged query of a batch (ssw_index_topk_slot_deep_dev): full scan of q, exact deep

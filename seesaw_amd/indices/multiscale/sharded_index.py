@@ -79,10 +79,14 @@ class DeviceShard:
         self.index.select_deep_dev(k)
         return self.keys, self.count, self.best.to(self.torch.int64) & 0xFFFFFFFF
 
-    def select_batch(self, Q: np.ndarray, k: int, excluded_locals):
+    def select_batch(self, Q: np.ndarray, k: int, excluded_locals, prune: bool = False):
         """scan + top-k of the slice for a chunk of queries, the rows read once per chunk of up to 16 (enqueue only):
-        query b's message goes into slot b of the block `ShardedTopK.attach_batch` attached to `self.index`"""
-        self.index.topk_batch_dev(Q, k, excluded=excluded_locals)
+        query b's message goes into slot b of the block `ShardedTopK.attach_batch` attached to `self.index`.
+        `prune`: from the certified int8 pre-scan where the slice is large enough (DeviceIndex.topk_batch_dev)"""
+        if prune:
+            self.index.topk_batch_dev(Q, k, excluded=excluded_locals, prune=True)
+        else:
+            self.index.topk_batch_dev(Q, k, excluded=excluded_locals)
 
     def select_slot_deep(self, q: np.ndarray, k: int, excluded_local: np.ndarray, slot: int):
         """the exact repair of one flagged query of the chunk: rescan, deep selection, message into `slot`"""
@@ -345,7 +349,7 @@ class ShardedMultiscaleIndex(MultiscaleIndex):
     # `_init_device`), which falls back to this loop for whatever it does not serve.
     query_batch = AccessMethod.query_batch
 
-    def _query_batch_sharded(self, *, topk, vectors, excludes=None, **kwargs):
+    def _query_batch_sharded(self, *, topk, vectors, excludes=None, prune=False, **kwargs):
         """`index.query_batch`: `[query(vector=v, topk=topk, exclude=e, **kwargs) for v, e in zip(vectors, excludes)]`,
         entry by entry identical to it.  For `agg_method="plain_score"` without `vector2` every rank reads its rows once per chunk of up
         to 16 queries (`DeviceShard.select_batch`) and the ranks exchange once per group of `n_slots` queries: one
@@ -355,7 +359,10 @@ class ShardedMultiscaleIndex(MultiscaleIndex):
         with an exclusion set that covers the index go through `query`; one k = the largest shortlist, every query
         keeps its own first min(shortlist_size, included) candidates.  Everything else -- other aggregation methods,
         `vector2`, a shard factory without `select_batch` -- is the per-query loop; the second stage over a sharded
-        batch remains a follow-up.  Afterwards `_resident_q` names the last query."""
+        batch remains a follow-up.  Afterwards `_resident_q` names the last query.
+        `prune=True`: the served route's chunks take the certified int8 pre-scan on every shard that is large enough
+        (`DeviceShard.select_batch(prune=True)`); a (query, rank) whose certificate failed is flagged and repaired like
+        an overflow.  The same entries; every other route runs its loop as before and ignores the flag."""
         vectors = list(vectors)
         excludes = [None] * len(vectors) if excludes is None else list(excludes)
         if len(excludes) != len(vectors):
@@ -388,7 +395,10 @@ class ShardedMultiscaleIndex(MultiscaleIndex):
         for g in range(0, len(batch), self._n_slots):
             Qg, nq = Q[g:g + self._n_slots], len(batch[g:g + self._n_slots])
             if self._shard is not None:
-                self._shard.select_batch(Qg, k_local, mine[g:g + nq])
+                if prune:
+                    self._shard.select_batch(Qg, k_local, mine[g:g + nq], prune=True)
+                else:
+                    self._shard.select_batch(Qg, k_local, mine[g:g + nq])
             else:
                 x.pack_empty_batch(nq)
             keys, counts = x.exchange_fused_batch(nq, k)

@@ -433,11 +433,13 @@ class ShardedSyntheticIndex:
         imgs, scores = decode_keys(keys[:c].cpu().numpy().view(np.uint64))
         return imgs, scores
 
-    def topk_batch_async(self, Q, k: int):
+    def topk_batch_async(self, Q, k: int, prune: bool = False):
         """`topk_async` for a chunk of nq <= n_slots host queries Q [nq, dim]: every shard reads its rows once per chunk
         of up to 16 queries (DeviceIndex.topk_batch_dev), then ONE all-gather and ONE merge launch, all enqueued on the
         current stream -> (keys [nq, k_max], counts [nq]) on the device.  The overflow flags travel with the messages;
-        check `xchg.assert_no_overflow_seen()` after synchronising."""
+        check `xchg.assert_no_overflow_seen()` after synchronising.  `prune=True`: every shard that is large enough
+        bounds the chunk with one pass over its int8 shadow and scores only the survivors exactly, still enqueue-only
+        (DeviceIndex.topk_batch_dev); a query whose certificate failed on a shard carries the flag value 2."""
         if not 1 <= k <= self.xchg.k_max:
             raise ValueError(f"k={k} outside [1, k_max={self.xchg.k_max}] of this index's exchange")
         Q = self.local._queries(Q)
@@ -445,19 +447,23 @@ class ShardedSyntheticIndex:
             raise ValueError(f"nq={Q.shape[0]} exceeds n_slots={self.n_slots}: topk_batch() cuts a batch into groups")
         if getattr(self.xchg, "send_batch", None) is None:
             self.xchg.attach_batch(self.local, self.n_slots)
-        self.local.topk_batch_dev(Q, k)
+        if prune:
+            self.local.topk_batch_dev(Q, k, prune=True)
+        else:
+            self.local.topk_batch_dev(Q, k)
         return self.xchg.exchange_fused_batch(Q.shape[0], k)
 
-    def topk_batch(self, Q, k: int):
+    def topk_batch(self, Q, k: int, prune: bool = False):
         """`[topk(q, k) for q in Q]` with the rows read once per chunk and one exchange per group of n_slots queries: a
         list of (images, scores).  A flagged (query, rank) redoes that query exactly on that rank (a rescan: the chunk's
-        slabs are gone) and all ranks repeat the exchange once for the group."""
+        slabs are gone) and all ranks repeat the exchange once for the group.  `prune=True`: `topk_batch_async`'s; a
+        failed certificate is such a flag."""
         from .device_index import decode_keys
         Q = self.local._queries(Q)
         out = []
         for g in range(0, Q.shape[0], self.n_slots):
             Qg = Q[g:g + self.n_slots]
-            keys, counts = self.topk_batch_async(Qg, k)
+            keys, counts = self.topk_batch_async(Qg, k, prune=prune)
             self.torch.cuda.synchronize(self.device)
             over = self.xchg.overflowed_batch()
             if over:  # the same list on every rank

@@ -2,7 +2,7 @@
 """The batched sharded top-k against the loop of single sharded queries, in one process ("Sharded
 batch"; ssw_index_topk_batch_dev, ssw_topk_merge_msgs_batch_dev).
 
-    python tools/perf_sharded_batch.py [--rows 12.5e6] [--dtype float32] [--k 100] [--reps 9] [--out FILE]
+    python tools/perf_sharded_batch.py [--rows 12.5e6] [--dtype float32] [--k 100] [--reps 9] [--prune] [--out FILE]
 
 World 1 with `force_collective` over RCCL: one rank's share of the 8-GPU configuration (12.5 M x 512 rows), with the
 all-gather really issued.  One row format per invocation (run each under its own `timeout`, chained with `&&`).  For
@@ -14,9 +14,15 @@ nq = 2 / 4 / 8 / 16, k = 100:
      this without the batched path, as the product runs it: on an index the single query prunes (own rows, >= 2^22
      of them) every topk_async is the certified pre-scan with its host wait inside, while A always scans in full.
 
-A and B alternate after two warm-up pairs; one JSON line per nq with the median, the minimum and the quartile spread of
-the wall ms per query of either form, their ratio, and whether both returned the same keys.  The raw lines are appended
-to --out (profiles/sharded_batch_ab.txt)."""
+  C  (--prune) `topk_batch_async(Q[:nq], k, prune=True)` + one synchronisation: ONE pass over the int8 shadow per
+     chunk, nq threshold selections and survivor lists, ONE rescoring launch sized by the device, nq selections, ONE
+     all-gather, ONE merge launch, no host wait inside (ssw_index_topk_batch_dev_pruned).
+
+A, B (and C) alternate after two warm-up rounds; one JSON line per nq with the median, the minimum, the quartiles and
+the max - min spread of the wall ms per query of every form, the ratios of the medians, and whether all returned the
+same keys; with --prune also the survivors and the failure bits of the last pruned chunk, read back from the device
+(ssw_index_prune_batch_dev_read), and whether C is ahead of A and of B by more than the two spreads together.  The raw
+lines are appended to --out (profiles/sharded_batch_ab.txt; with --prune profiles/sharded_batch_pruned_ab.txt)."""
 import argparse
 import json
 import os
@@ -35,7 +41,7 @@ NQS = (2, 4, 8, 16)
 def spread(ms):
     a = np.sort(np.asarray(ms))
     return {"median": float(np.median(a)), "min": float(a[0]), "q1": float(np.percentile(a, 25)),
-            "q3": float(np.percentile(a, 75)), "max": float(a[-1])}
+            "q3": float(np.percentile(a, 75)), "max": float(a[-1]), "spread": float(a[-1] - a[0])}
 
 
 def main():
@@ -44,8 +50,11 @@ def main():
     ap.add_argument("--dtype", default="float32", choices=["float32", "float16"])
     ap.add_argument("--k", type=int, default=100)
     ap.add_argument("--reps", type=int, default=9)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sharded_batch_ab.txt"))
+    ap.add_argument("--prune", action="store_true", help="a third column: the pruned batch (topk_batch_async(prune=True))")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "sharded_batch_pruned_ab.txt" if args.prune else "sharded_batch_ab.txt")
     import torch
     import torch.distributed as dist
     from seesaw_amd.sharded import ShardedSyntheticIndex
@@ -65,9 +74,12 @@ def main():
     qptrs = [Qd[b].data_ptr() for b in range(Q.shape[0])]
     k = args.k
 
-    def batch(nq):
+    def batch(nq, prune=False):
         t0 = time.perf_counter()
-        keys, counts = idx.topk_batch_async(Q[:nq], k)
+        if prune:
+            keys, counts = idx.topk_batch_async(Q[:nq], k, prune=True)
+        else:
+            keys, counts = idx.topk_batch_async(Q[:nq], k)
         torch.cuda.synchronize(idx.device)
         return (time.perf_counter() - t0) * 1e3 / nq, keys[:, :k].clone()
 
@@ -83,20 +95,36 @@ def main():
     lines = []
     try:
         for nq in NQS:
-            for _ in range(2):  # warm-up pairs: the side buffer, the batch target, RCCL's first call
+            for _ in range(2):  # warm-up rounds: the side buffer, the batch target, the shadow, RCCL's first call
                 batch(nq)
                 loop(nq)
-            a_ms, b_ms, same = [], [], True
+                if args.prune:
+                    batch(nq, prune=True)
+            a_ms, b_ms, c_ms, same = [], [], [], True
             for _ in range(args.reps):
                 ta, ka = batch(nq)
                 tb, kb = loop(nq)
                 a_ms.append(ta)
                 b_ms.append(tb)
                 same = same and bool(torch.equal(ka, kb))
+                if args.prune:
+                    tc, kc = batch(nq, prune=True)
+                    c_ms.append(tc)
+                    same = same and bool(torch.equal(kc, kb))
             idx.xchg.assert_no_overflow_seen()
             a, b = spread(a_ms), spread(b_ms)
             line = {"rows": n, "dtype": args.dtype, "k": k, "nq": nq, "reps": args.reps, "batch_ms_per_query": a,
                     "loop_ms_per_query": b, "ratio_of_medians": a["median"] / b["median"], "same_keys": same}
+            if args.prune:
+                c = spread(c_ms)
+                surv, why = idx.local.prune_batch_dev_counts()  # of the last pruned chunk
+                line.update({"pruned_batch_ms_per_query": c, "pruned_over_batch": c["median"] / a["median"],
+                             "pruned_over_loop": c["median"] / b["median"],
+                             # a win counts only where the gap exceeds the two spreads together
+                             "pruned_beats_batch": bool(a["median"] - c["median"] > a["spread"] + c["spread"]),
+                             "pruned_beats_loop": bool(b["median"] - c["median"] > b["spread"] + c["spread"]),
+                             "survivors": surv.tolist(), "fail_bits": why.tolist(),
+                             "loop_is_pruned": bool(idx.local.prune_stats()["eligible"])})
             print(json.dumps(line), flush=True)
             lines.append(json.dumps(line))
     finally:
