@@ -95,6 +95,14 @@ ssw_status ssw_debug_prune6_shadow(ssw_index *idx, int64_t first_row, int64_t n_
                                    float *out_err);
 ssw_status ssw_debug_prune6_bounds(ssw_index *idx, const float *q_host, int64_t *out_I, float *out_lb, float *out_Qe,
                                    int8_t *out_codes);
+/* The survivor passes' pre-test on the bounds alone (csrc/prune.hip, survivor_pass; tests/test_prune_tail_gpu.py).
+ * ssw_debug_prune_maxima: builds the int8 (six = 0) or the 6-bit (six != 0) shadow if it is missing or stale and copies
+ *   out what k_shadow_max left for it: out2 [2] = the largest finite a_r and the largest finite s_r.
+ * ssw_debug_prune6_survivors: k_survivors_mq with the 6-bit code norm + k_prune_publish_mq over the bounds of the last
+ *   ssw_debug_prune6_bounds; arguments and outputs as ssw_debug_prune_survivors. */
+ssw_status ssw_debug_prune_maxima(ssw_index *idx, int32_t six, float *out2);
+ssw_status ssw_debug_prune6_survivors(ssw_index *idx, float threshold, int32_t k, int32_t sel_count, int32_t sel_overflow,
+                                      int64_t cap, int32_t *out_published, int64_t *out_collected, int64_t *out_rows);
 
 /* The pruned batch (seesaw_hip.h, ssw_index_topk_batch_pruned).
  * ssw_tune_prune_scan_mq: the launch shape of its shadow scan (k_q8_bounds_mq): four-wave blocks per CU (1 .. 8) and

@@ -186,6 +186,9 @@ _DEBUG_SIGNATURES = {
     "ssw_debug_prune6_scan_shape": (c_i32, [c_void_p, c_i32_p, c_i32_p]),
     "ssw_debug_prune6_shadow": (c_i32, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p]),
     "ssw_debug_prune6_bounds": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ssw_debug_prune_maxima": (c_i32, [c_void_p, c_i32, c_void_p]),
+    "ssw_debug_prune6_survivors": (c_i32, [c_void_p, ctypes.c_float, c_i32, c_i32, c_i32, c_i64, c_i32_p, c_i64_p,
+                                           c_void_p]),
     "ssw_tune_gemm": (c_i32, [c_i32]),
     "ssw_debug_gemm": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_void_p, c_void_p]),
     "ssw_debug_gemm_pw4_mode": (c_i32, [c_i32, c_void_p]),

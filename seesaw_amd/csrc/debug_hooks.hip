@@ -679,6 +679,47 @@ ssw_status ssw_debug_prune6_bounds(ssw_index *idx, const float *q_host, int64_t 
     return SSW_OK;
 }
 
+// ---- the survivor pass's pre-test (tests/test_prune_tail_gpu.py) ------------------------------------------------------
+ssw_status ssw_debug_prune_maxima(ssw_index *idx, int32_t six, float *out2) {
+    SSW_REQUIRE(idx != nullptr && out2 != nullptr, "NULL argument");
+    DeviceGuard guard(idx->device);
+    if (six) SSW_TRY(require_shadow6(idx, "prune_maxima"));
+    else {
+        SSW_REQUIRE(prune_eligible(idx), "the index is not pruned (ssw_tune_prune, dim, borrowed or escaped rows)");
+        SSW_TRY(require_shadow(idx, "prune_maxima"));
+    }
+    SSW_HIP_TRY(hipMemcpyAsync(out2, six ? idx->prune.q6_max : idx->prune.q8_max, SHADOW_MAX_WORDS * sizeof(float),
+                               hipMemcpyDeviceToHost, idx->stream));
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_prune6_survivors(ssw_index *idx, float threshold, int32_t k, int32_t sel_count, int32_t sel_overflow,
+                                      int64_t cap, int32_t *out_published, int64_t *out_collected, int64_t *out_rows) {
+    SSW_REQUIRE(idx != nullptr && out_published != nullptr && out_collected != nullptr, "NULL argument");
+    SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
+    SSW_REQUIRE(cap >= 0 && cap <= SURV_CAP, "cap=%lld outside [0, %lld]", (long long)cap, (long long)SURV_CAP);
+    SSW_REQUIRE(cap == 0 || out_rows != nullptr, "out_rows is NULL");
+    SSW_REQUIRE(idx->scores_partial && idx->prune.q6 && !idx->prune.stale6, "no bounds in the buffer: ssw_debug_prune6_bounds first");
+    DeviceGuard guard(idx->device);
+    SSW_TRY(ensure_ws(idx));
+    unsigned *st = idx->prune.state6;
+    SSW_HIP_TRY(hipMemsetAsync(st, 0, sizeof(unsigned), idx->stream));      // the counter and the "selection failed"
+    SSW_HIP_TRY(hipMemsetAsync(st + 5, 0, sizeof(unsigned), idx->stream));  // word k_q6_query resets
+    SSW_TRY(stand_in_threshold(idx, threshold, k, sel_count, sel_overflow));
+    int32_t m = -1;
+    SSW_TRY(prune6_survivors(idx, k, cap, nullptr, &m));
+    unsigned collected = 0u;
+    SSW_HIP_TRY(hipMemcpyAsync(&collected, st, sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
+    if (m > 0)
+        SSW_HIP_TRY(hipMemcpyAsync(out_rows, idx->prune.surv_rows, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost,
+                                   idx->stream));
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+    *out_published = m;
+    *out_collected = (int64_t)collected;
+    return SSW_OK;
+}
+
 ssw_status ssw_debug_prune6_scan_shape(ssw_index *idx, int32_t *out_blocks, int32_t *out_tiles) {
     SSW_REQUIRE(idx != nullptr && out_blocks != nullptr && out_tiles != nullptr, "NULL argument");
     SSW_REQUIRE(q8_dim_supported(idx->dim), "dim=%d has no shadow scan", idx->dim);

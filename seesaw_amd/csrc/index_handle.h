@@ -13,6 +13,7 @@ constexpr int64_t SMALL_ROWS = 65536;               // and the small scan kernel
 struct PruneState {
     int8_t *q8 = nullptr;                          // [n, dim] codes
     float *q8_scale = nullptr, *q8_err = nullptr;  // [n] s_r, a_r
+    unsigned *q8_max = nullptr;                    // [SHADOW_MAX_WORDS] the largest finite a_r, s_r (launch_shadow_max)
     bool stale = true;                             // the rows changed since the shadow was built
     bool refused = false;                          // too little free memory at the last attempt (until the rows change)
     unsigned *state = nullptr;                     // [4] device words (ssw_common.h, launch_q8_query)
@@ -30,6 +31,7 @@ struct PruneState {
     // stale / refused
     unsigned char *q6 = nullptr;                   // q6_code_bytes(n, dim): tiles of 16 rows
     float *q6_scale = nullptr, *q6_err = nullptr;  // [q6_padded_rows(n)] s6_r, a6_r
+    unsigned *q6_max = nullptr;                    // [SHADOW_MAX_WORDS] the same of the 6-bit shadow
     bool stale6 = true, refused6 = false;
     unsigned *state6 = nullptr;                    // [Q8_MQ_WORDS] the query's words, a slot's of the chunk
     int8_t *planes6 = nullptr;                     // q6_plane_bytes(dim): the query's operand
@@ -45,7 +47,8 @@ struct PruneState {
     }
     void release() {
         free_shadow();
-        for (void *p : {(void *)state, (void *)surv_rows, (void *)surv_scores, (void *)q_last, (void *)state6, (void *)planes6})
+        for (void *p : {(void *)state, (void *)surv_rows, (void *)surv_scores, (void *)q_last, (void *)state6, (void *)planes6,
+                        (void *)q8_max, (void *)q6_max})
             (void)hipFree(p);
         if (host) (void)hipHostFree(host);
         if (ev) (void)hipEventDestroy(ev);
@@ -197,7 +200,8 @@ inline ssw_status ensure_full_scores(ssw_index *idx) { return ensure_full_scores
 
 // index_topk.hip
 ssw_status stage_query(ssw_index *idx, const float *q_host);
-ssw_status do_select(ssw_index *idx, const float *scores, int32_t k, SelectDest dest, hipStream_t stream);
+ssw_status do_select(ssw_index *idx, const float *scores, int32_t k, SelectDest dest, hipStream_t stream,
+                     bool from_candidates = false);
 ssw_status do_select_deep(ssw_index *idx, const float *scores, int32_t k, SelectDest dest, hipStream_t stream);
 ssw_status install_excluded(ssw_index *idx, const int64_t *excluded_images, int64_t n_excluded, hipStream_t stream);
 ssw_status topk_enqueue(ssw_index *idx, const float *q_host, const float *scores, hipStream_t stream,
@@ -216,7 +220,8 @@ ssw_status prune6_bounds(ssw_index *idx, const float *q_dev, int64_t *dbg_I);
 ssw_status rows_changing(ssw_index *idx);
 ssw_status prune_bounds(ssw_index *idx, const float *q_dev);
 ssw_status prune_survivors(ssw_index *idx, int32_t k, int64_t cap, hipEvent_t sleep_ev_or_null, int32_t *out_m);
-ssw_status scan_for_topk(ssw_index *idx, const float *q_dev, int32_t k);
+ssw_status prune6_survivors(ssw_index *idx, int32_t k, int64_t cap, hipEvent_t sleep_ev_or_null, int32_t *out_m);
+ssw_status scan_for_topk(ssw_index *idx, const float *q_dev, int32_t k, bool *out_candidates);
 ssw_status ensure_prune_batch(ssw_index *idx, int w, int *out_w);
 ssw_status prune_bounds_mq(ssw_index *idx, int w, int32_t *dbg_hi, int32_t *dbg_lo);
 ssw_status prune_survivors_slot(ssw_index *idx, int w, int j, int32_t k, int64_t cap);

@@ -22,15 +22,16 @@ constexpr int64_t PRUNE_BATCH_MIN_ROWS = PRUNE_MIN_ROWS;
 // row at dim 512, more survivors) and never need the int8 one.  The value follows from tools/perf_prune.py --three-way
 // ("6-bit shadow"): the smallest size from which the 6-bit call beats the int8 call, there and at
 // every larger size, by more than both spreads.
-// Measured since (profiles/prune6_f32_sweep.txt): the rule gives 2^25 (2.55 against 2.81 ms a call there; at 2^24 and at
-// 25 M rows the gap, 0.09 ms, is inside the spreads).  Moving this constant is left to a change of its own.
-constexpr int64_t PRUNE6_MIN_ROWS = (int64_t)1 << 24;
+// Measured with the survivor pass that reads the bounds alone (profiles/prune_tail_sweep.txt): 2^23 (0.719 against 0.816
+// ms a call, spreads 0.043 together; at 2^22 the gap of 0.032 ms is inside the spreads' 0.042).  The ~22 000 survivors
+// of the 6-bit bounds no longer cost 0.3 ms, which was what kept the int8 call ahead below 2^25 rows.
+constexpr int64_t PRUNE6_MIN_ROWS = (int64_t)1 << 23;
 // f16 rows (the shadow is built from the widened rows by k_q6_build_h16, the same bytes a row): its own constant under
-// the same rule, from the same tool with --dtype float16 (profiles/prune6_f16_sweep.txt): 2^25 rows is the smallest
-// measured size from which the 6-bit call is ahead by more than both spreads, there and above (2.59 against 2.78 ms a
-// call; 7.05 against 8.93 at 100 M).  At 2^24 rows the two are level (1.49 against 1.48), at 25 M the gap of 0.11 ms is
-// inside the spreads' 0.13.
-constexpr int64_t PRUNE6_MIN_ROWS_F16 = (int64_t)1 << 25;
+// the same rule, from the same tool with --dtype float16 (the same file): 2^24 rows is the smallest measured size from
+// which the 6-bit call is ahead by more than both spreads, there and above (1.239 against 1.409 ms a call, spreads
+// 0.155; 6.75 against 8.10 at 100 M).  At 2^23 and 12.5 M rows the 6-bit call is ahead by 0.06 and 0.12 ms, but both
+// forms' spreads were 0.2-0.3 ms in that run, so the rule does not admit them.
+constexpr int64_t PRUNE6_MIN_ROWS_F16 = (int64_t)1 << 24;
 constexpr int64_t PRUNE_RESERVE = (int64_t)4 << 30;   // free device memory the shadow must leave
 static SSW_TUNABLE bool g_prune = true;               // ssw_tune_prune
 static SSW_TUNABLE bool g_prune6 = true;              // ssw_tune_prune6
@@ -126,7 +127,9 @@ ssw_status ssw::ensure_shadow(ssw_index *idx, bool *ready) {
         }
     }
     SSW_TRY(ensure_call_buffers(idx));
+    if (!p.q8_max) SSW_HIP_TRY(hipMalloc((void **)&p.q8_max, SHADOW_MAX_WORDS * sizeof(unsigned)));
     SSW_TRY(launch_q8_build(idx->X, idx->dtype, idx->n, idx->dim, p.q8, p.q8_scale, p.q8_err, idx->stream));
+    SSW_TRY(launch_shadow_max(p.q8_err, p.q8_scale, idx->n, p.q8_max, idx->device, idx->stream));
     p.stale = false;
     *ready = true;
     return SSW_OK;
@@ -166,7 +169,9 @@ ssw_status ssw::ensure_shadow6(ssw_index *idx, bool *ready) {
         // columns 2 .. 15 of the query operand stay zero for good: k_q6_query writes columns 0 and 1 only
         SSW_HIP_TRY(hipMemsetAsync(p.planes6, 0, q6_plane_bytes(idx->dim), idx->stream));
     }
+    if (!p.q6_max) SSW_HIP_TRY(hipMalloc((void **)&p.q6_max, SHADOW_MAX_WORDS * sizeof(unsigned)));
     SSW_TRY(launch_q6_build(idx->X, idx->dtype, idx->n, idx->dim, p.q6, p.q6_scale, p.q6_err, idx->stream));
+    SSW_TRY(launch_shadow_max(p.q6_err, p.q6_scale, idx->n, p.q6_max, idx->device, idx->stream));
     p.stale6 = false;
     *ready = true;
     return SSW_OK;
@@ -202,10 +207,10 @@ static ssw_status survivors_of(ssw_index *idx, bool six, int32_t k, int64_t cap,
     int32_t *host_dev = nullptr;
     SSW_HIP_TRY(hipHostGetDevicePointer((void **)&host_dev, p.host, 0));
     if (six)
-        SSW_TRY(launch_survivors_q6(idx->scores, p.q6_err, p.q6_scale, idx->n, idx->dim, idx->ws.out_keys, idx->ws.out_count,
+        SSW_TRY(launch_survivors_q6(idx->scores, p.q6_err, p.q6_scale, p.q6_max, idx->n, idx->dim, idx->ws.out_keys, idx->ws.out_count,
                                     k, p.state6, p.surv_rows, cap, host_dev, seq, idx->device, idx->stream));
     else
-        SSW_TRY(launch_survivors(idx->scores, p.q8_err, idx->n, idx->ws.out_keys, idx->ws.out_count, k, p.state, p.surv_rows,
+        SSW_TRY(launch_survivors(idx->scores, p.q8_err, p.q8_max, idx->n, idx->ws.out_keys, idx->ws.out_count, k, p.state, p.surv_rows,
                                  cap, host_dev, seq, idx->device, idx->stream));
     if (sleep_ev_or_null) SSW_HIP_TRY(hipEventSynchronize(sleep_ev_or_null));
     SSW_TRY(wait_host_seq(idx->stream, reinterpret_cast<const unsigned *>(p.host), seq));
@@ -215,6 +220,9 @@ static ssw_status survivors_of(ssw_index *idx, bool six, int32_t k, int64_t cap,
 ssw_status ssw::prune_survivors(ssw_index *idx, int32_t k, int64_t cap, hipEvent_t sleep_ev_or_null, int32_t *out_m) {
     return survivors_of(idx, false, k, cap, sleep_ev_or_null, out_m);
 }
+ssw_status ssw::prune6_survivors(ssw_index *idx, int32_t k, int64_t cap, hipEvent_t sleep_ev_or_null, int32_t *out_m) {
+    return survivors_of(idx, true, k, cap, sleep_ev_or_null, out_m);
+}
 
 // The score buffer for the selection of the top-k of query q_dev (exclusions installed): the full f32 scan, or on a
 // large index the certified pre-scan -- shadow scan (lower bounds), threshold selection over them that publishes
@@ -223,7 +231,11 @@ ssw_status ssw::prune_survivors(ssw_index *idx, int32_t k, int64_t cap, hipEvent
 // that cannot be bounded) runs the full scan instead.  The profiling events bracket the whole replacement.
 // The shadow is the 6-bit one where prune6_eligible says so (only that one is built then), else the int8 one; a 6-bit
 // shadow refused for memory leaves the int8 path, if an int8 shadow exists or fits.
-ssw_status ssw::scan_for_topk(ssw_index *idx, const float *q_dev, int32_t k) {
+// *out_candidates: the pruned path succeeded on an index without an image map, and the candidates of the final top-k
+// are in the selection's workspace (launch_scatter_candidates): the caller's selection, the next thing on the stream,
+// runs over them alone (do_select, from_candidates).  Nothing of it is kept in the handle.
+ssw_status ssw::scan_for_topk(ssw_index *idx, const float *q_dev, int32_t k, bool *out_candidates) {
+    *out_candidates = false;
     bool ready = false, six = false;
     const bool k_ok = k >= 1 && k <= SSW_MAX_TOPK && (idx->ws.xchg.msg_out == nullptr || k <= idx->ws.xchg.k_max);
     if (k_ok && prune6_eligible(idx)) SSW_TRY(ensure_shadow6(idx, &six));
@@ -237,6 +249,8 @@ ssw_status ssw::scan_for_topk(ssw_index *idx, const float *q_dev, int32_t k) {
         SSW_HIP_TRY(hipEventRecord(p.ev, idx->stream));
         // threshold: the ordinary selection over the lower bounds, with the exclusions, without a message or host result
         SSW_TRY(do_select(idx, idx->scores, k, SelectDest{nullptr, 0u, false}, idx->stream));
+        // (ahead of the host wait; the survivor pass reads the selection's keys and count, not these words)
+        if (!idx->has_map) SSW_TRY(select_reset_state(idx->ws, idx->stream));
         int32_t m = -1;
         SSW_TRY(survivors_of(idx, six, k, SURV_CAP, p.ev, &m));  // sleep through the shadow scan, spin on the rest
         p.last = m;
@@ -247,7 +261,9 @@ ssw_status ssw::scan_for_topk(ssw_index *idx, const float *q_dev, int32_t k) {
             return launch_index_scan(idx, p.q_last, idx->stream);
         }
         SSW_TRY(launch_score_rows(idx->X, idx->dtype, p.q_last, p.surv_rows, m, idx->dim, p.surv_scores, idx->stream));
-        return launch_scatter_scores(p.surv_rows, p.surv_scores, m, idx->scores, idx->stream);
+        if (idx->has_map) return launch_scatter_scores(p.surv_rows, p.surv_scores, m, idx->scores, idx->stream);
+        *out_candidates = m > 0;
+        return launch_scatter_candidates(idx->ws, p.surv_rows, p.surv_scores, m, k, idx->scores, idx->stream);
     });
 }
 
@@ -320,7 +336,7 @@ ssw_status ssw::prune_bounds_mq(ssw_index *idx, int w, int32_t *dbg_hi, int32_t 
 ssw_status ssw::prune_survivors_slot(ssw_index *idx, int w, int j, int32_t k, int64_t cap) {
     PruneState &p = idx->prune;
     PruneBatchState &pb = idx->prune_batch;
-    return launch_survivors_mq(chunk_slab(idx, w, j), p.q8_err, p.q8_scale, idx->n, idx->dim, idx->ws.out_keys,
+    return launch_survivors_mq(chunk_slab(idx, w, j), p.q8_err, p.q8_scale, p.q8_max, idx->n, idx->dim, idx->ws.out_keys,
                                idx->ws.out_count, k, pb.mq + j * Q8_MQ_WORDS, pb.surv_rows + (int64_t)j * SURV_CAP, cap,
                                idx->device, idx->stream);
 }

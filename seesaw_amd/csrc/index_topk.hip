@@ -26,9 +26,13 @@ ssw_status ssw::stage_query(ssw_index *idx, const float *q_host) {
     return SSW_OK;
 }
 
-// the selection over the row scores in `scores`: per-image maxima first when the index has an image map
-ssw_status ssw::do_select(ssw_index *idx, const float *scores, int32_t k, SelectDest dest, hipStream_t stream) {
+// the selection over the row scores in `scores`: per-image maxima first when the index has an image map.
+// from_candidates: scan_for_topk, just before on this stream, left the candidates of this very selection in the
+// workspace (an index without a map), so only the last kernel runs.
+ssw_status ssw::do_select(ssw_index *idx, const float *scores, int32_t k, SelectDest dest, hipStream_t stream,
+                          bool from_candidates) {
     SSW_TRY(ensure_ws(idx));
+    if (from_candidates) return launch_select_candidates(idx->ws, k, dest, stream);
     if (idx->has_map) {
         SSW_TRY(launch_image_max(scores, idx->row_start, idx->n_images, idx->ws.img_score, idx->ws.img_best, stream));
         return launch_select_topk(idx->ws, idx->ws.img_score, idx->n_images, idx->ws.img_best, k, dest, idx->device, stream);
@@ -124,14 +128,16 @@ static ssw_status small_enqueue(ssw_index *idx, const float *q_host, const float
 
 // the general form's selection (deep: the rerun after an overflow): its last kernel writes the packed result into the
 // pinned mirror and releases a fresh sequence word the host spins on (no device-to-host copy, no stream wait)
-static ssw_status select_to_host(ssw_index *idx, const float *scores, hipStream_t stream, int32_t k, bool deep) {
+static ssw_status select_to_host(ssw_index *idx, const float *scores, hipStream_t stream, int32_t k, bool deep,
+                                 bool from_candidates = false) {
     SSW_TRY(ensure_ws(idx));
     SSW_TRY(ensure_res_host(idx));
     SelectDest dest;
     SSW_HIP_TRY(hipHostGetDevicePointer((void **)&dest.host_packed, idx->res_host, 0));
     dest.seq = idx->res_pending_seq = next_seq(idx->small_seq);
     idx->small_pending_seq = 0;  // this selection is the one in flight: topk_collect reads res_host
-    const ssw_status st = deep ? do_select_deep(idx, scores, k, dest, stream) : do_select(idx, scores, k, dest, stream);
+    const ssw_status st = deep ? do_select_deep(idx, scores, k, dest, stream)
+                                : do_select(idx, scores, k, dest, stream, from_candidates);
     if (st != SSW_OK) idx->res_pending_seq = 0;  // nothing was launched that would publish
     return st;
 }
@@ -146,9 +152,10 @@ ssw_status ssw::topk_enqueue(ssw_index *idx, const float *q_host, const float *s
     if (small_path_ok(idx, n_excluded)) return small_enqueue(idx, q_host, scores, stream, excluded_images, n_excluded, k);
     if (q_host) SSW_TRY(stage_query(idx, q_host));
     if (idx->n_images > 0) SSW_TRY(install_excluded(idx, excluded_images, n_excluded, stream));
-    if (q_host) SSW_TRY(scan_for_topk(idx, idx->q_dev, k));
+    bool candidates = false;
+    if (q_host) SSW_TRY(scan_for_topk(idx, idx->q_dev, k, &candidates));
     if (idx->n_images == 0) return SSW_OK;
-    return select_to_host(idx, scores, stream, k, false);
+    return select_to_host(idx, scores, stream, k, false, candidates);
 }
 
 // the packed block [count, overflow, k, seq][keys k][best k] -> the caller's arrays
@@ -258,14 +265,15 @@ ssw_status ssw_index_set_excluded(ssw_index *idx, const int64_t *excluded_images
 ssw_status ssw_index_topk_dev(ssw_index *idx, const float *q_dev, int32_t k) {
     SSW_REQUIRE(idx != nullptr, "idx is NULL");
     DeviceGuard guard(idx->device);
-    if (q_dev) SSW_TRY(scan_for_topk(idx, q_dev, k));
+    bool candidates = false;
+    if (q_dev) SSW_TRY(scan_for_topk(idx, q_dev, k, &candidates));
     else SSW_TRY(ensure_full_scores(idx));
     if (idx->n_images == 0) {  // an empty shard still takes part in the exchange: its message says "0 keys"
         if (idx->ws.xchg.msg_out)
             SSW_HIP_TRY(hipMemsetAsync(idx->ws.xchg.msg_out + (idx->ws.xchg.msg_len - 1), 0, sizeof(uint64_t), idx->stream));
         return SSW_OK;
     }
-    return do_select(idx, idx->scores, k, SelectDest(), idx->stream);
+    return do_select(idx, idx->scores, k, SelectDest(), idx->stream, candidates);
 }
 
 // The fast selection keeps at most 8192 candidates; when more images than that share the 24-bit score prefix

@@ -13,7 +13,8 @@
 // k_q8_bounds writes lb_r = s~_r - a_r Q - pad, rounded down, into the score buffer.  The caller (capi_index.hip, scan_for_topk) selects the k-th image over those lower bounds
 // (threshold T <= the exact k-th image score), keeps the rows whose upper bound reaches T (k_survivors), rescores them
 // with the f32 scan's own arithmetic (score_rows_kernel) and scatters the exact scores back (k_scatter_scores).  The
-// normal selection over that buffer then returns the bits of a full scan.
+// normal selection over that buffer then returns the bits of a full scan (on an index without an image map it runs over
+// the survivors at or above T alone: select.hip, k_scatter_candidates).
 //
 // Shadow layout: natural row order, natural element order, one signed byte per element (c = rint(x / s), |c| <= 127,
 // s = max|x| / 127).  A 16-byte load of lane l covers bytes 16 (l % L) .. +15 of one row, L = dim / 16 lanes a row:
@@ -361,55 +362,182 @@ __global__ __launch_bounds__(256) void k_q8_bounds(const int8_t *__restrict__ co
     }
 }
 
-// the rows whose upper bound reaches T = the k-th key of the threshold selection over the lower bounds.
-// ub_r <= lb_r + 2 a_r Q + pads, so a row with lb + 2 a Q + pads < T is proven below the exact k-th image score.
-// Nothing is collected when the selection returned fewer than k keys or overflowed, or the query cannot be bounded:
-// the survivor count is then left at 0 and prune_publish reports the fallback.
-__global__ __launch_bounds__(256) void k_survivors(const float *__restrict__ lb, const float *__restrict__ err,
-                                                   int64_t n, const uint64_t *__restrict__ keys,
-                                                   const int32_t *__restrict__ sel_count, int32_t k,
-                                                   unsigned *__restrict__ state, int64_t *__restrict__ rows,
-                                                   int64_t cap) {
-    if (sel_count[0] < k || sel_count[1] != 0 || state[2] != 0u) return;
-    const float T = ord_to_f32((uint32_t)(keys[k - 1] >> 32));
-    const double Qd = (double)__uint_as_float(state[1]);
+// ---- the shadow's maxima: what lets the survivor pass read the bounds alone ---------------------------------------------
+// mx[0] = the largest finite a_r, mx[1] = the largest finite s_r of the shadow, as float bits (non-negative floats order as
+// their bit patterns, so atomicMax on unsigned is a float maximum); the caller zeroes both words first.  Rows with
+// a = +inf are left out: their lb is -inf, which the survivor pass keeps by a clause of its own.
+__global__ __launch_bounds__(256) void k_shadow_max(const float *__restrict__ err, const float *__restrict__ scale, int64_t n,
+                                                    unsigned *__restrict__ mx) {
+    float a = 0.0f, s = 0.0f;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const float e = err[i], c = scale[i];
+        if (isfinite(e)) a = fmaxf(a, e);
+        if (isfinite(c)) s = fmaxf(s, c);
+    }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        a = fmaxf(a, __shfl_xor(a, off, 64));
+        s = fmaxf(s, __shfl_xor(s, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (a > 0.0f) atomicMax(&mx[0], __float_as_uint(a));
+        if (s > 0.0f) atomicMax(&mx[1], __float_as_uint(s));
+    }
+}
+
+// the upper bound of a row from its lower bound l and the width w of its bound: ub_r <= l + 2 w + pads
+__device__ __forceinline__ double surv_ub(double l, double w) {
+    return l + 2.0 * w + (fabs(l) + w) * 0x1p-20 + 2.0 * PAD_ABS;
+}
+
+constexpr double WMAX_INFLATE = 1.0 + 0x1p-30;  // on w_max: a different fma contraction of the two ub's cannot matter
+constexpr int SURV_UNROLL = 4;                  // 16-byte loads of lb a lane keeps in flight
+constexpr int SURV_STAGE = 1024;                // survivors a block collects in LDS before it takes its place in the list
+
+// The survivor pass of both kernels below: the rows with !(ub < T), their number added to *counter and the first cap of
+// them listed in rows (any order).  MQ: the width is e wA + s wS ((**) / (***)), else e wA.
+// Two steps.  A lane takes four consecutive rows and first loads their lb ONLY; with w_max >= every bounded row's w
+// (from the shadow's maxima) surv_ub(l, w_max) >= surv_ub(l, w): the expression is monotone in w >= 0 under round to
+// nearest.  So a row with ub_max < T and lb > -inf cannot pass the test and its constants are never read; lb = -inf
+// (an unboundable row: a = +inf is not in the maxima) and a NaN bound stay candidates.  (The lb > -inf clause is
+// redundant: surv_ub's (|l| + w) 2^-20 term is +inf at l = -inf, so ub_max is the NaN of -inf + inf there whatever
+// w_max is, and !(NaN < T) holds.  It stays as a second line of defence should the ub expression ever change.)  A lane
+// with a candidate loads its four rows' constants and applies the test itself, unchanged.
+// The list: one atomicAdd with return on the one global counter per wave-step that found a survivor was most of the
+// pass once the 6-bit shadow left ~22 000 survivors (that many dependent atomics on one address).  A block now collects
+// its survivors in LDS (an LDS atomic a wave-step) and takes its place in the list once, at the end; a wave-step that
+// no longer fits the stage goes to the global counter directly, as before, and so does every wave-step of the block
+// after it (once a claim has failed the stage is closed).  Count and set are the same; only the order of the list,
+// which was the atomics' already, differs.
+template <bool MQ>
+__device__ __forceinline__ void survivor_pass(const float *__restrict__ lb, const float *__restrict__ err,
+                                              const float *__restrict__ scale, int64_t n, float T, double wA, double wS,
+                                              double w_max, unsigned *__restrict__ counter, int64_t *__restrict__ rows,
+                                              int64_t cap) {
     const int lane = threadIdx.x & 63;
     const uint64_t below = (1ull << lane) - 1ull;
     const int64_t stride = (int64_t)gridDim.x * 1024;
-    // a lane takes four consecutive rows (one 16-byte load of each array), a wave 256: wave-uniform loop
-    for (int64_t base = (int64_t)blockIdx.x * 1024 + (threadIdx.x & ~63u) * 4; base < n; base += stride) {
-        const int64_t r0 = base + 4 * lane;
-        float l4[4] = {0.0f, 0.0f, 0.0f, 0.0f}, e4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (r0 + 3 < n) {
-            const float4 lv = *reinterpret_cast<const float4 *>(lb + r0), ev = *reinterpret_cast<const float4 *>(err + r0);
-            l4[0] = lv.x, l4[1] = lv.y, l4[2] = lv.z, l4[3] = lv.w;
-            e4[0] = ev.x, e4[1] = ev.y, e4[2] = ev.z, e4[3] = ev.w;
-        } else {
-            for (int t = 0; t < 4; ++t)
-                if (r0 + t < n) l4[t] = lb[r0 + t], e4[t] = err[r0 + t];
+    const double Td = (double)T;
+    __shared__ int64_t stage[SURV_STAGE];
+    __shared__ unsigned staged, first_failed, stage_base;
+    if (threadIdx.x == 0) staged = 0u, first_failed = 0xffffffffu;
+    __syncthreads();
+    // the lane's rows r0 .. r0 + nv - 1 with the bounds l (nv = 4, 0 for a lane without rows, or the last n % 4 rows);
+    // called by whole waves
+    auto step = [&](int64_t r0, const float (&l4)[4], int nv) {
+        bool cand = false;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const double l = (double)l4[t];
+            cand = cand || (t < nv && (!(surv_ub(l, w_max) < Td) || !(l4[t] > -INFINITY)));
+        }
+        if (__ballot(cand) == 0ull) return;
+        float e4[4] = {0.0f, 0.0f, 0.0f, 0.0f}, s4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (cand) {
+            if (nv == 4) {
+                const float4 ev = *reinterpret_cast<const float4 *>(err + r0);
+                e4[0] = ev.x, e4[1] = ev.y, e4[2] = ev.z, e4[3] = ev.w;
+                if constexpr (MQ) {
+                    const float4 sv = *reinterpret_cast<const float4 *>(scale + r0);
+                    s4[0] = sv.x, s4[1] = sv.y, s4[2] = sv.z, s4[3] = sv.w;
+                }
+            } else {
+                for (int t = 0; t < nv; ++t) {
+                    e4[t] = err[r0 + t];
+                    if constexpr (MQ) s4[t] = scale[r0 + t];
+                }
+            }
         }
         bool keep[4];
         uint64_t ballot[4];
         unsigned total = 0u;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            const double l = (double)l4[t], w = (double)e4[t] * Qd;
-            const double ub = l + 2.0 * w + (fabs(l) + w) * 0x1p-20 + 2.0 * PAD_ABS;
-            keep[t] = r0 + t < n && !(ub < (double)T);  // NaN survives
+            const double l = (double)l4[t];
+            double w = (double)e4[t] * wA;
+            if constexpr (MQ) w = (double)e4[t] * wA + (double)s4[t] * wS;
+            keep[t] = cand && t < nv && !(surv_ub(l, w) < Td);  // NaN survives
             ballot[t] = __ballot(keep[t]);
             total += (unsigned)__popcll(ballot[t]);
         }
-        if (total == 0u) continue;
+        if (total == 0u) return;
+        // a place in the block's stage.  A claim is never undone: the first one that does not fit leaves `staged` above
+        // SURV_STAGE, so every later claim fails too, and the claims that hold are exactly those below the smallest
+        // failed slot, contiguous from 0 (claims only ever advance `staged`)
         unsigned slot = 0u;
-        if (lane == 0) slot = atomicAdd(&state[0], total);
+        int direct = 0;
+        if (lane == 0) {
+            slot = atomicAdd(&staged, total);
+            if (slot + total > (unsigned)SURV_STAGE) {
+                atomicMin(&first_failed, slot);
+                slot = atomicAdd(counter, total);
+                direct = 1;
+            }
+        }
         slot = __shfl(slot, 0, 64);
+        direct = __shfl(direct, 0, 64);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const int64_t at = (int64_t)slot + __popcll(ballot[t] & below);
-            if (keep[t] && at < cap) rows[at] = r0 + t;
+            if (keep[t]) {
+                if (!direct) stage[at] = r0 + t;
+                else if (at < cap) rows[at] = r0 + t;
+            }
             slot += (unsigned)__popcll(ballot[t]);
         }
+    };
+    // the whole groups of four rows: a wave takes 256 rows a step, SURV_UNROLL steps a stride apart at a time, their loads
+    // requested together (wave-uniform loop; no scalar path beside the loads, which would make the waits conservative)
+    const int64_t n4 = n & ~(int64_t)3;
+    for (int64_t base0 = (int64_t)blockIdx.x * 1024 + (threadIdx.x & ~63u) * 4; base0 < n4; base0 += SURV_UNROLL * stride) {
+        float4 lv[SURV_UNROLL];
+#pragma unroll
+        for (int u = 0; u < SURV_UNROLL; ++u) {
+            const int64_t r0 = base0 + u * stride + 4 * lane;
+            lv[u] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (r0 < n4) lv[u] = *reinterpret_cast<const float4 *>(lb + r0);
+        }
+#pragma unroll
+        for (int u = 0; u < SURV_UNROLL; ++u) {
+            const int64_t r0 = base0 + u * stride + 4 * lane;
+            const float l4[4] = {lv[u].x, lv[u].y, lv[u].z, lv[u].w};
+            step(r0, l4, r0 < n4 ? 4 : 0);
+        }
     }
+    // the last n % 4 rows: lane 0 of the first wave
+    if (n4 < n && blockIdx.x == 0 && threadIdx.x < 64) {
+        float l4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        const int nv = lane == 0 ? (int)(n - n4) : 0;
+        for (int t = 0; t < nv; ++t) l4[t] = lb[n4 + t];
+        step(n4, l4, nv);
+    }
+    // the block's staged survivors into the list, behind one claim on the global counter
+    __syncthreads();
+    const unsigned mine = min(staged, first_failed);  // <= SURV_STAGE: where the first claim that did not fit began
+    if (mine == 0u) return;
+    if (threadIdx.x == 0) stage_base = atomicAdd(counter, mine);
+    __syncthreads();
+    for (unsigned i = threadIdx.x; i < mine; i += 256) {
+        const int64_t at = (int64_t)stage_base + i;
+        if (at < cap) rows[at] = stage[i];
+    }
+}
+
+// the rows whose upper bound reaches T = the k-th key of the threshold selection over the lower bounds.
+// ub_r <= lb_r + 2 a_r Q + pads, so a row with lb + 2 a Q + pads < T is proven below the exact k-th image score.
+// Nothing is collected when the selection returned fewer than k keys or overflowed, or the query cannot be bounded:
+// the survivor count is then left at 0 and prune_publish reports the fallback.  mx: the shadow's maxima (k_shadow_max).
+__global__ __launch_bounds__(256) void k_survivors(const float *__restrict__ lb, const float *__restrict__ err,
+                                                   const unsigned *__restrict__ mx, int64_t n,
+                                                   const uint64_t *__restrict__ keys,
+                                                   const int32_t *__restrict__ sel_count, int32_t k,
+                                                   unsigned *__restrict__ state, int64_t *__restrict__ rows,
+                                                   int64_t cap) {
+    if (sel_count[0] < k || sel_count[1] != 0 || state[2] != 0u) return;
+    const float T = ord_to_f32((uint32_t)(keys[k - 1] >> 32));
+    const double Qd = (double)__uint_as_float(state[1]);
+    const double w_max = (double)__uint_as_float(mx[0]) * Qd * WMAX_INFLATE;
+    survivor_pass<false>(lb, err, nullptr, n, T, Qd, 0.0, w_max, &state[0], rows, cap);
 }
 
 // the host's answer: survivors (0 .. cap) or -1 = fall back to the full scan; released into pinned memory under seq
@@ -654,8 +782,8 @@ __global__ __launch_bounds__(256) void k_q8_bounds_mq(const int8_t *__restrict__
 // err; the list and the counter are the slot's.  A failed selection or a flagged query collects nothing and leaves
 // word [5] / [2] for k_prune_publish_mq.
 __global__ __launch_bounds__(256) void k_survivors_mq(const float *__restrict__ lb, const float *__restrict__ err,
-                                                      const float *__restrict__ scale, int64_t n, double code_norm,
-                                                      const uint64_t *__restrict__ keys,
+                                                      const float *__restrict__ scale, const unsigned *__restrict__ mx,
+                                                      int64_t n, double code_norm, const uint64_t *__restrict__ keys,
                                                       const int32_t *__restrict__ sel_count, int32_t k,
                                                       unsigned *__restrict__ st, int64_t *__restrict__ rows,
                                                       int64_t cap) {
@@ -667,44 +795,8 @@ __global__ __launch_bounds__(256) void k_survivors_mq(const float *__restrict__ 
     const float T = ord_to_f32((uint32_t)(keys[k - 1] >> 32));
     const double wQ = (double)__uint_as_float(st[1]) * MQ_INFLATE;
     const double wE = (double)__uint_as_float(st[3]) * code_norm * MQ_INFLATE;
-    const int lane = threadIdx.x & 63;
-    const uint64_t below = (1ull << lane) - 1ull;
-    const int64_t stride = (int64_t)gridDim.x * 1024;
-    for (int64_t base = (int64_t)blockIdx.x * 1024 + (threadIdx.x & ~63u) * 4; base < n; base += stride) {
-        const int64_t r0 = base + 4 * lane;
-        float l4[4] = {0.0f, 0.0f, 0.0f, 0.0f}, e4[4] = {0.0f, 0.0f, 0.0f, 0.0f}, s4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (r0 + 3 < n) {
-            const float4 lv = *reinterpret_cast<const float4 *>(lb + r0), ev = *reinterpret_cast<const float4 *>(err + r0),
-                         sv = *reinterpret_cast<const float4 *>(scale + r0);
-            l4[0] = lv.x, l4[1] = lv.y, l4[2] = lv.z, l4[3] = lv.w;
-            e4[0] = ev.x, e4[1] = ev.y, e4[2] = ev.z, e4[3] = ev.w;
-            s4[0] = sv.x, s4[1] = sv.y, s4[2] = sv.z, s4[3] = sv.w;
-        } else {
-            for (int t = 0; t < 4; ++t)
-                if (r0 + t < n) l4[t] = lb[r0 + t], e4[t] = err[r0 + t], s4[t] = scale[r0 + t];
-        }
-        bool keep[4];
-        uint64_t ballot[4];
-        unsigned total = 0u;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const double l = (double)l4[t], w = (double)e4[t] * wQ + (double)s4[t] * wE;
-            const double ub = l + 2.0 * w + (fabs(l) + w) * 0x1p-20 + 2.0 * PAD_ABS;
-            keep[t] = r0 + t < n && !(ub < (double)T);  // NaN survives
-            ballot[t] = __ballot(keep[t]);
-            total += (unsigned)__popcll(ballot[t]);
-        }
-        if (total == 0u) continue;
-        unsigned slot = 0u;
-        if (lane == 0) slot = atomicAdd(&st[0], total);
-        slot = __shfl(slot, 0, 64);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int64_t at = (int64_t)slot + __popcll(ballot[t] & below);
-            if (keep[t] && at < cap) rows[at] = r0 + t;
-            slot += (unsigned)__popcll(ballot[t]);
-        }
-    }
+    const double w_max = ((double)__uint_as_float(mx[0]) * wQ + (double)__uint_as_float(mx[1]) * wE) * WMAX_INFLATE;
+    survivor_pass<true>(lb, err, scale, n, T, wQ, wE, w_max, &st[0], rows, cap);
 }
 
 // every slot's answer in one launch: host_block[1 + j] = survivors or -1, j < w, released under host_block[0] = seq
@@ -1038,15 +1130,27 @@ void tune_q8_bounds(int blocks_per_cu, int group_loads) {
 }
 #endif
 
-ssw_status launch_survivors(const float *lb, const float *err, int64_t n, const uint64_t *keys, const int32_t *sel_count,
-                            int32_t k, unsigned *state, int64_t *rows, int64_t cap, int32_t *host_block, unsigned seq,
+// the maxima of a shadow's finite constants into mx[0] (a) and mx[1] (s): after every build of the shadow, on its stream
+ssw_status launch_shadow_max(const float *err, const float *scale, int64_t n, unsigned *mx, int device, hipStream_t stream) {
+    SSW_HIP_TRY(hipMemsetAsync(mx, 0, SHADOW_MAX_WORDS * sizeof(unsigned), stream));
+    if (n <= 0) return SSW_OK;
+    int64_t grid = (int64_t)num_cus(device) * 8;
+    const int64_t need = (n + 255) / 256;
+    if (grid > need) grid = need;
+    hipLaunchKernelGGL(k_shadow_max, dim3((unsigned)grid), dim3(256), 0, stream, err, scale, n, mx);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+ssw_status launch_survivors(const float *lb, const float *err, const unsigned *mx, int64_t n, const uint64_t *keys,
+                            const int32_t *sel_count, int32_t k, unsigned *state, int64_t *rows, int64_t cap, int32_t *host_block, unsigned seq,
                             int device, hipStream_t stream) {
     int64_t grid = (int64_t)num_cus(device) * 4;
     const int64_t need = (n + 1023) / 1024;  // four rows a lane
     if (grid > need) grid = need;
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(k_survivors, dim3((unsigned)grid), dim3(256), 0, stream, lb, err, n, keys, sel_count, k, state,
-                       rows, cap);
+    hipLaunchKernelGGL(k_survivors, dim3((unsigned)grid), dim3(256), 0, stream, lb, err, mx, n, keys, sel_count, k,
+                       state, rows, cap);
     hipLaunchKernelGGL(k_prune_publish, dim3(1), dim3(64), 0, stream, sel_count, k, state, cap, host_block, seq);
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
@@ -1124,14 +1228,14 @@ void tune_q8_bounds_mq(int blocks_per_cu, int tiles) {
 }
 #endif
 
-ssw_status launch_survivors_mq(const float *lb, const float *err, const float *scale, int64_t n, int32_t dim,
+ssw_status launch_survivors_mq(const float *lb, const float *err, const float *scale, const unsigned *mx, int64_t n, int32_t dim,
                                const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *slot_state,
                                int64_t *rows, int64_t cap, int device, hipStream_t stream) {
     int64_t grid = (int64_t)num_cus(device) * 4;
     const int64_t need = (n + 1023) / 1024;  // four rows a lane
     if (grid > need) grid = need;
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(k_survivors_mq, dim3((unsigned)grid), dim3(256), 0, stream, lb, err, scale, n, mq_code_norm(dim),
+    hipLaunchKernelGGL(k_survivors_mq, dim3((unsigned)grid), dim3(256), 0, stream, lb, err, scale, mx, n, mq_code_norm(dim),
                        keys, sel_count, k, slot_state, rows, cap);
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
@@ -1256,14 +1360,14 @@ void tune_q6_bounds(int blocks_per_cu, int tiles) {
 #endif
 
 // k_survivors_mq with the 6-bit shadow's code norm, then the answer of the one slot into host_block[1]
-ssw_status launch_survivors_q6(const float *lb, const float *err, const float *scale, int64_t n, int32_t dim,
+ssw_status launch_survivors_q6(const float *lb, const float *err, const float *scale, const unsigned *mx, int64_t n, int32_t dim,
                                const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *st, int64_t *rows,
                                int64_t cap, int32_t *host_block, unsigned seq, int device, hipStream_t stream) {
     int64_t grid = (int64_t)num_cus(device) * 4;
     const int64_t need = (n + 1023) / 1024;  // four rows a lane
     if (grid > need) grid = need;
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(k_survivors_mq, dim3((unsigned)grid), dim3(256), 0, stream, lb, err, scale, n, q6_code_norm(dim),
+    hipLaunchKernelGGL(k_survivors_mq, dim3((unsigned)grid), dim3(256), 0, stream, lb, err, scale, mx, n, q6_code_norm(dim),
                        keys, sel_count, k, st, rows, cap);
     hipLaunchKernelGGL(k_prune_publish_mq, dim3(1), dim3(64), 0, stream, st, 1, cap, host_block, seq);
     SSW_HIP_TRY(hipGetLastError());

@@ -310,6 +310,31 @@ __global__ __launch_bounds__(256) void k_collect_deep(const float *__restrict__ 
     }
 }
 
+// ---- the candidates of the final top-k straight from a pruned scan's survivors (index_prune.hip, scan_for_topk) ---------
+// Survivor i's exact score v[i] goes into the buffer at rows[i], as k_scatter_scores puts it there, and its composite
+// key joins `cand` if it is at or above the threshold T = the k-th key of the selection over the lower bounds, still in
+// `keys` (an ORDINAL comparison: sign-clear NaN scores lead, as in every selection here), and its image is not excluded.
+// Every row of the exact top-k is such a survivor, so k_final's single-list form over `cand` is
+// the selection over the whole buffer.  An index without an image map only: row = image.
+__global__ __launch_bounds__(256) void k_scatter_candidates(const int64_t *__restrict__ rows, const float *__restrict__ v,
+                                                            int64_t m, float *__restrict__ scores,
+                                                            const uint64_t *__restrict__ keys, int32_t k,
+                                                            const uint32_t *__restrict__ excl,
+                                                            uint32_t *__restrict__ state, uint64_t *__restrict__ cand) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t t_ord = (uint32_t)(keys[k - 1] >> 32);
+    const int64_t r = rows[i];
+    const float e = v[i];
+    scores[r] = e;
+    // (a NaN with the sign bit set keys below -inf: it can reach the top-k only where T = -inf left fewer than k other
+    // images, and then it must be listed; an extra exact key in the list never changes the k largest)
+    if ((f32_to_ord(e) >= t_ord || e != e) && !is_excluded(excl, r)) {
+        const uint32_t slot = atomicAdd(&state[ST_NCAND], 1u);
+        if (slot < (uint32_t)FINAL_CAP) cand[slot] = composite_key(e, r);
+    }
+}
+
 // ---- the final selection: the c largest of p keys in LDS, sorted descending, 1024 threads ------------------------------
 // A full bitonic sort of the candidates in LDS cost a barrier per stage -- 66 stages for 2048 keys, ~30 us of a ~35 us
 // kernel for an LVIS-subset index, where the selection is most of a feedback round.  This form:
@@ -830,6 +855,43 @@ ssw_status launch_select_topk(SelectWorkspace &ws, const float *values, int64_t 
     hipLaunchKernelGGL(k_final, dim3(1), dim3(1024), FINAL_LDS_BYTES, stream, ws.cand,
                        0, 0, (const int32_t *)nullptr, ws.state + ST_NCAND, (const uint32_t *)ws.state, (int)k,
                        best_rows_or_null, ws.out_keys, ws.out_count, ws.out_best, packed, xg);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+// the selection's state words to zero: before launch_scatter_candidates counts into them, after the threshold
+// selection's last kernel has read them
+ssw_status select_reset_state(SelectWorkspace &ws, hipStream_t stream) {
+    SSW_HIP_TRY(hipMemsetAsync(ws.state, 0, ST_WORDS * sizeof(uint32_t), stream));
+    return SSW_OK;
+}
+
+// k_scatter_candidates over the m survivors of a pruned scan; ws.out_keys still holds the threshold selection's keys
+ssw_status launch_scatter_candidates(SelectWorkspace &ws, const int64_t *rows, const float *v, int64_t m, int32_t k,
+                                     float *scores, hipStream_t stream) {
+    if (m <= 0) return SSW_OK;
+    const uint32_t *excl = ws.excl_dirty ? ws.excl_bits : nullptr;
+    hipLaunchKernelGGL(k_scatter_candidates, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, rows, v, m, scores,
+                       (const uint64_t *)ws.out_keys, k, excl, ws.state, ws.cand);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+// the selection over the list launch_scatter_candidates left in ws.cand: k_final alone, in its single-list form.  More
+// than FINAL_CAP candidates (mass ties at the top) raise the overflow word by k_final's own test.
+ssw_status launch_select_candidates(SelectWorkspace &ws, int32_t k, SelectDest dest, hipStream_t stream) {
+    if (k < 1 || k > SSW_MAX_TOPK) {
+        set_error("topk: k=%d outside [1, %d]", k, SSW_MAX_TOPK);
+        return SSW_ERR_INVALID;
+    }
+    SSW_TRY(exchange_fits(dest.target ? *dest.target : ws.xchg, k));
+    unsigned char *packed = nullptr;
+    FinalExchange xg = final_outputs(ws, dest, &packed);
+    xg.sampled = 0;
+    SSW_TRY(final_lds_ready());
+    hipLaunchKernelGGL(k_final, dim3(1), dim3(1024), FINAL_LDS_BYTES, stream, ws.cand, 0, 0, (const int32_t *)nullptr,
+                       ws.state + ST_NCAND, (const uint32_t *)ws.state, (int)k, (const uint32_t *)nullptr, ws.out_keys,
+                       ws.out_count, ws.out_best, packed, xg);
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
 }

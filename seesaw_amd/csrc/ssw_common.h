@@ -175,10 +175,13 @@ ssw_status launch_q8_build(const void *X, int32_t dtype, int64_t n, int32_t dim,
 ssw_status launch_q8_query(const float *q_dev, int32_t dim, float *q_keep, unsigned *state, hipStream_t stream);
 ssw_status launch_q8_bounds(const int8_t *codes, const float *scale, const float *err, const float *q_dev,
                             const unsigned *state, float *scores, int64_t n, int32_t dim, int device, hipStream_t stream);
+// mx[0], mx[1] = the largest finite a_r and s_r of a shadow (float bits): what the survivor passes pre-test lb with
+constexpr int SHADOW_MAX_WORDS = 2;
+ssw_status launch_shadow_max(const float *err, const float *scale, int64_t n, unsigned *mx, int device, hipStream_t stream);
 // rows with upper bound >= the k-th key of the last selection -> rows[0, cap), then host_block[1] = survivors or -1
 // (fall back to the full scan) and host_block[0] = seq, released to the host
-ssw_status launch_survivors(const float *lb, const float *err, int64_t n, const uint64_t *keys, const int32_t *sel_count,
-                            int32_t k, unsigned *state, int64_t *rows, int64_t cap, int32_t *host_block, unsigned seq,
+ssw_status launch_survivors(const float *lb, const float *err, const unsigned *mx, int64_t n, const uint64_t *keys,
+                            const int32_t *sel_count, int32_t k, unsigned *state, int64_t *rows, int64_t cap, int32_t *host_block, unsigned seq,
                             int device, hipStream_t stream);
 ssw_status launch_scatter_scores(const int64_t *rows, const float *v, int64_t m, float *scores, hipStream_t stream);
 // the same for a chunk of w <= 16 queries, bounded together by one pass on the int8 matrix core (prune.hip, "Pruned
@@ -191,7 +194,7 @@ ssw_status launch_q8_query_mq(const float *qb_dev, int32_t dim, int32_t w, unsig
 ssw_status launch_q8_bounds_mq(const int8_t *codes, const float *scale, const float *err, const int8_t *planes,
                                const unsigned *mq, int32_t w, float *side, int64_t stride, float *own, int64_t n,
                                int32_t dim, int32_t *dbg_hi, int32_t *dbg_lo, int device, hipStream_t stream);
-ssw_status launch_survivors_mq(const float *lb, const float *err, const float *scale, int64_t n, int32_t dim,
+ssw_status launch_survivors_mq(const float *lb, const float *err, const float *scale, const unsigned *mx, int64_t n, int32_t dim,
                                const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *slot_state,
                                int64_t *rows, int64_t cap, int device, hipStream_t stream);
 ssw_status launch_prune_publish_mq(const unsigned *mq, int32_t w, int64_t cap, int32_t *host_block, unsigned seq,
@@ -231,7 +234,7 @@ ssw_status launch_q6_bounds(const unsigned char *codes, const float *scale, cons
                             const unsigned *st, float *scores, int64_t n, int32_t dim, int64_t *dbg_I, int device,
                             hipStream_t stream);
 void q6_bounds_shape(int32_t dim, int device, int64_t n, int *out_blocks, int *out_tiles);
-ssw_status launch_survivors_q6(const float *lb, const float *err, const float *scale, int64_t n, int32_t dim,
+ssw_status launch_survivors_q6(const float *lb, const float *err, const float *scale, const unsigned *mx, int64_t n, int32_t dim,
                                const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *st, int64_t *rows,
                                int64_t cap, int32_t *host_block, unsigned seq, int device, hipStream_t stream);
 // rows between natural order and the index.  to_h16: n rows of natural-order f32 (src_f32) or binary16 (src_h16, the
@@ -394,6 +397,13 @@ ssw_status launch_select_small(SelectWorkspace &ws, const float *row_scores, con
                                unsigned char *packed_mapped, unsigned seq, hipStream_t stream);
 // the fast path flags (out_count[1]) a 24-bit prefix bin with more candidates than the final
 // sort can take (massive exact ties); the caller then reruns the selection on the deep path.
+// The final top-k of a pruned scan on an index without an image map, from its survivors (index_prune.hip): the state
+// words zeroed; survivor i's exact score v[i] into scores[rows[i]] and, at or above the k-th key still in ws.out_keys and
+// not excluded, its key into ws.cand; then the selection over that list alone (k_final, with dest as launch_select_topk).
+ssw_status select_reset_state(SelectWorkspace &ws, hipStream_t stream);
+ssw_status launch_scatter_candidates(SelectWorkspace &ws, const int64_t *rows, const float *v, int64_t m, int32_t k,
+                                     float *scores, hipStream_t stream);
+ssw_status launch_select_candidates(SelectWorkspace &ws, int32_t k, SelectDest dest, hipStream_t stream);
 ssw_status launch_select_topk_deep(SelectWorkspace &ws, const float *values, int64_t m,
                                    const uint32_t *best_rows_or_null, int32_t k, SelectDest dest, int device,
                                    hipStream_t stream);

@@ -161,7 +161,7 @@ class DeviceIndex:
         """Top-k distinct images (positions), their max score and the row attaining it.
         q=None reuses the scores of the previous scan.  With a query, a large index (f32 or float16 rows alike) scans a
         quantised shadow of the rows first and scores only the rows that can still reach the k-th image exactly: the
-        int8 shadow from 2^22 rows, the packed 6-bit shadow from 2^24 f32 or 2^25 float16 rows.  The results are the
+        int8 shadow from 2^22 rows, the packed 6-bit shadow from 2^23 f32 or 2^24 float16 rows.  The results are the
         full scan's bits."""
         k = int(k)
         qa = None if q is None else self._query(q)
@@ -429,7 +429,7 @@ class DeviceIndex:
 
     def prune_stats(self, completions: bool = False) -> dict:
         """state of the certified pre-scan of `topk` with a query (ssw_index_prune_stats).  `shadow` describes the
-        shadow single queries scan -- the packed 6-bit one on an index of at least 2^24 f32 or 2^25 float16 rows, else
+        shadow single queries scan -- the packed 6-bit one on an index of at least 2^23 f32 or 2^24 float16 rows, else
         the int8 one: "none", "current", "stale" (the rows changed since it was built; the next pruned call rebuilds
         it) or "refused" (too little free device memory beside it); `eligible`: the next top-k with a query is pruned;
         `last_survivors`: rows the last pruned call rescored (-1 = it fell back to the full scan); `queries` /

@@ -3,6 +3,7 @@ plus the weight-matrix / X'LX lookup shared with MultiReg and PseudoLR."""
 from __future__ import annotations
 
 import os
+import weakref
 
 import numpy as np
 import scipy.sparse as sp
@@ -15,6 +16,9 @@ from ..research.knn_methods import LabelPropagationRanker2
 from .loop_base import LoopBase
 
 _CACHE = {}  # process-local stand-in for the reference's Ray-backed `_cache_closure`
+# An in-memory graph's key names its index by id(), and an id is free for reuse once that index is gone: an entry made
+# from an in-memory graph is a hit only while that very graph is the one asked for.
+_CACHE_GRAPH = {}  # key -> weak reference to the in-memory graph the entry was made from
 
 
 class WeightMatrixOptions(BaseModel):
@@ -59,7 +63,9 @@ def lookup_weight_matrix(opts: WeightMatrixOptions, *, use_cache: bool, X_vector
     if opts.xlx_matrix:
         assert opts.symmetric and not opts.self_edges
     if use_cache and key in _CACHE:
-        return _CACHE[key]
+        made_from = _CACHE_GRAPH.get(key)
+        if knng is None or (made_from is not None and made_from() is knng):
+            return _CACHE[key]
     print(f"init weight matrix {opts=}")
     graph = (knng if knng is not None else KNNGraph.from_file(opts.knn_path)).restrict_k(k=opts.knn_k)
     wm = get_weight_matrix(graph.knn_df, kfun=rbf_kernel(opts.edist), self_edges=opts.self_edges,
@@ -70,6 +76,8 @@ def lookup_weight_matrix(opts: WeightMatrixOptions, *, use_cache: bool, X_vector
         wm = compute_xlx(wm, X_vectors, device_index=device_index)
     if use_cache:
         _CACHE[key] = wm
+        if knng is not None:
+            _CACHE_GRAPH[key] = weakref.ref(knng)
     return wm
 
 
