@@ -181,6 +181,10 @@ ssw_status ssw_index_topk_batch(ssw_index *idx, const float *q_host, int32_t nq,
  * rescoring follow, with ONE host wait per chunk, and then the ordinary selection.  A query that cannot be bounded (zero,
  * norm above 2^40, largest element outside [2^-60, 2^60]), one with more than 2^18 survivors or fewer than k keys runs
  * the full scan by itself.  Any other index takes ssw_index_topk_batch itself and leaves the prune counters alone.
+ * On an index of at least 25 M rows, f32 or f16, whose single queries scan the packed 6-bit shadow (that shadow not
+ * refused for memory) the chunk's pass runs over that shadow instead, 3 dim / 4 + 8 bytes a row, and no int8 shadow is
+ * built: one shadow serves both kinds of call.  The same holds for ssw_index_topk_batch_avg_pruned and
+ * ssw_index_topk_batch_dev_pruned.  Which shadow certifies never changes what is returned.
  * State afterwards: that of a pruned ssw_index_topk of the last query with its excluded list (the resident scores are
  * completed by the first reader).  ssw_index_prune_stats counts every query of a pruned batch in [3] and every one that
  * fell back in [4]; [2] is the last query's.  ssw_index_profile records one event pair per chunk.

@@ -127,6 +127,34 @@ ssw_status ssw_debug_prune_survivors_mq(ssw_index *idx, int32_t nq, int32_t slot
                                         int32_t sel_count, int32_t sel_overflow, int64_t cap, int32_t *out_published,
                                         int64_t *out_collected, int64_t *out_rows);
 
+/* The pruned batch's chunk on the packed 6-bit shadow (csrc/prune.hip, "a chunk of up to 16 queries on the 6-bit
+ * shadow"; tests/test_prune6_batch_gpu.py): what a pruned batch runs on an index that ssw_tune_prune6 and
+ * ssw_tune_prune6_batch make six-eligible, instead of the int8 chunk above.  The hooks above keep driving the int8 chunk; a chunk's state words,
+ * planes and slabs belong to whichever pair of hooks bounded it last.
+ * ssw_tune_prune6_batch: min_rows >= 0 = the smallest index, of either dtype, whose pruned batches scan the 6-bit
+ *   shadow, provided its single queries do (ssw_tune_prune6: the batch never goes below the single call); < 0 = the
+ *   product's two constants again (25 M rows).  ssw_tune_prune6's own min_rows does not move the batch: with it
+ *   alone a pruned batch on a small index keeps building and scanning the int8 shadow.
+ * ssw_tune_prune6_scan_mq: the launch shape of k_q6_bounds_mq: four-wave blocks per CU (1 .. 8) and 16-row tiles a wave
+ *   requests at a time (1, 2 or 4, as far as tiles x dim <= 1024); any other value = the product's (1 block; 4 / 2 / 1
+ *   tiles at dim 256 / 512 / 1024).  ssw_debug_prune6_scan_mq_shape: the blocks and tiles of the next launch.
+ * ssw_debug_prune6_bounds_mq: k_q6_query_mq + k_q6_bounds_mq through the product's launch functions for nq <= 16 host
+ *   queries (non-finite ones allowed: they are flagged) on the index's own buffers; builds the 6-bit shadow if it is
+ *   missing or stale.  out_I [nq, n] = the exact integer sums of 4 c with 256 d_hi + d_lo (int64), out_lb [nq, n],
+ *   out_Qe [nq, 4] = Q, e, t2 and the "cannot be bounded" word as floats, out_codes [nq, 2, dim] = the hi and the lo
+ *   plane, put back into natural element order by q6_slot.  Any output may be NULL.  The handle is left as after the
+ *   product's shadow scan of the chunk: partial, the last query kept.
+ * ssw_debug_prune6_survivors_mq: k_survivors_mq with the 6-bit code norm for one slot of the chunk the last
+ *   ssw_debug_prune6_bounds_mq bounded, then k_prune_publish_mq; arguments and outputs as ssw_debug_prune_survivors. */
+ssw_status ssw_tune_prune6_batch(int64_t min_rows);
+ssw_status ssw_tune_prune6_scan_mq(int32_t blocks_per_cu, int32_t tiles);
+ssw_status ssw_debug_prune6_scan_mq_shape(ssw_index *idx, int32_t *out_blocks, int32_t *out_tiles);
+ssw_status ssw_debug_prune6_bounds_mq(ssw_index *idx, const float *q_host, int32_t nq, int64_t *out_I, float *out_lb,
+                                      float *out_Qe, int8_t *out_codes);
+ssw_status ssw_debug_prune6_survivors_mq(ssw_index *idx, int32_t nq, int32_t slot, float threshold, int32_t k,
+                                         int32_t sel_count, int32_t sel_overflow, int64_t cap, int32_t *out_published,
+                                         int64_t *out_collected, int64_t *out_rows);
+
 /* The pruned batch that stays on the device (seesaw_hip.h, ssw_index_topk_batch_dev_pruned; csrc/rescore_dev.hip).
  * ssw_tune_surv_cap: the survivors a slot of that entry may have and still be certified, 1 .. 2^18; any other value =
  *   the product's 2^18.  Governs that entry and the hook below only.

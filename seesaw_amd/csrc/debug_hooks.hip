@@ -425,10 +425,17 @@ ssw_status ssw_debug_prune_scan_mq_shape(ssw_index *idx, int32_t *out_blocks, in
     return SSW_OK;
 }
 
-// the chunk's buffers for nq queries staged from the host, for the two hooks below
-static ssw_status debug_chunk_ready(ssw_index *idx, int32_t nq) {
-    SSW_REQUIRE(prune_batch_eligible(idx), "the index is not pruned (ssw_tune_prune, dim, borrowed or escaped rows)");
-    SSW_TRY(require_shadow(idx, "prune_bounds_mq"));
+static ssw_status require_shadow6(ssw_index *idx, const char *who);
+
+// the chunk's buffers for nq queries staged from the host, for the hooks below; six: on the 6-bit shadow
+static ssw_status debug_chunk_ready(ssw_index *idx, int32_t nq, bool six = false) {
+    if (six) {
+        SSW_TRY(require_shadow6(idx, "prune6_bounds_mq"));
+    } else {
+        SSW_REQUIRE(prune_batch_eligible(idx), "the index is not pruned (ssw_tune_prune, dim, borrowed or escaped rows)");
+        SSW_TRY(require_shadow(idx, "prune_bounds_mq"));
+    }
+    idx->prune_batch.six = six;  // what prune_batch_shadow would have left
     SSW_TRY(ensure_ws(idx));
     int w = 0;
     SSW_TRY(batch_buffers(idx, nq, true, &w));
@@ -497,7 +504,8 @@ ssw_status ssw_debug_prune_survivors_mq(ssw_index *idx, int32_t nq, int32_t slot
     SSW_REQUIRE(cap >= 0 && cap <= SURV_CAP, "cap=%lld outside [0, %lld]", (long long)cap, (long long)SURV_CAP);
     SSW_REQUIRE(cap == 0 || out_rows != nullptr, "out_rows is NULL");
     PruneBatchState &pb = idx->prune_batch;
-    SSW_REQUIRE(idx->scores_partial && idx->prune.q8 && !idx->prune.stale && pb.slots >= nq && idx->batch.side_slabs >= nq - 1,
+    SSW_REQUIRE(idx->scores_partial && !pb.six && idx->prune.q8 && !idx->prune.stale && pb.slots >= nq &&
+                    idx->batch.side_slabs >= nq - 1,
                 "no bounds of such a chunk in the buffers: ssw_debug_prune_bounds_mq first");
     DeviceGuard guard(idx->device);
     SSW_TRY(ensure_ws(idx));
@@ -716,6 +724,97 @@ ssw_status ssw_debug_prune6_survivors(ssw_index *idx, float threshold, int32_t k
                                    idx->stream));
     SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
     *out_published = m;
+    *out_collected = (int64_t)collected;
+    return SSW_OK;
+}
+
+// ---- the pruned batch's chunk on the 6-bit shadow (prune.hip, k_q6_query_mq / k_q6_bounds_mq; tests/test_prune6_batch_gpu.py)
+ssw_status ssw_debug_prune6_scan_mq_shape(ssw_index *idx, int32_t *out_blocks, int32_t *out_tiles) {
+    SSW_REQUIRE(idx != nullptr && out_blocks != nullptr && out_tiles != nullptr, "NULL argument");
+    SSW_REQUIRE(q8_dim_supported(idx->dim), "dim=%d has no shadow scan", idx->dim);
+    int blocks = 0, tiles = 0;
+    q6_bounds_mq_shape(idx->dim, idx->device, idx->n, &blocks, &tiles);
+    *out_blocks = blocks;
+    *out_tiles = tiles;
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_prune6_bounds_mq(ssw_index *idx, const float *q_host, int32_t nq, int64_t *out_I, float *out_lb,
+                                      float *out_Qe, int8_t *out_codes) {
+    SSW_REQUIRE(idx != nullptr && q_host != nullptr, "NULL argument");
+    SSW_REQUIRE(nq >= 1 && nq <= Q8_MQ_WIDTH, "nq=%d outside [1, %d]", nq, Q8_MQ_WIDTH);
+    DeviceGuard guard(idx->device);
+    SSW_TRY(debug_chunk_ready(idx, nq, true));
+    PruneBatchState &pb = idx->prune_batch;
+    const size_t dim = (size_t)idx->dim, cells = (size_t)nq * idx->n;
+    int64_t *dbg = nullptr;
+    if (out_I) SSW_HIP_TRY(hipMalloc((void **)&dbg, cells * sizeof(int64_t)));
+    std::vector<unsigned> mq((size_t)Q8_MQ_WIDTH * Q8_MQ_WORDS);
+    std::vector<int8_t> planes(q8_mq_plane_bytes(idx->dim));
+    auto run = [&]() -> ssw_status {
+        SSW_TRY(idx->batch.qb_stage.push(idx->batch.qb_dev, q_host, (size_t)nq * dim * sizeof(float), idx->stream));
+        SSW_TRY(prune_bounds_mq(idx, nq, nullptr, nullptr, dbg));
+        if (out_I) SSW_HIP_TRY(hipMemcpyAsync(out_I, dbg, cells * sizeof(int64_t), hipMemcpyDeviceToHost, idx->stream));
+        if (out_lb)
+            for (int j = 0; j < nq; ++j)
+                SSW_HIP_TRY(hipMemcpyAsync(out_lb + (size_t)j * idx->n, chunk_slab(idx, nq, j), (size_t)idx->n * sizeof(float),
+                                           hipMemcpyDeviceToHost, idx->stream));
+        SSW_HIP_TRY(hipMemcpyAsync(mq.data(), pb.mq, mq.size() * sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
+        SSW_HIP_TRY(hipMemcpyAsync(planes.data(), pb.planes, planes.size(), hipMemcpyDeviceToHost, idx->stream));
+        SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+        return SSW_OK;
+    };
+    const ssw_status st = run();
+    if (st != SSW_OK) (void)hipStreamSynchronize(idx->stream);
+    (void)hipFree(dbg);
+    SSW_TRY(st);
+    for (int b = 0; b < nq; ++b) {
+        const unsigned *w = mq.data() + (size_t)b * Q8_MQ_WORDS;
+        if (out_Qe) {
+            memcpy(out_Qe + 4 * b, &w[1], 4);      // Q
+            memcpy(out_Qe + 4 * b + 1, &w[3], 4);  // e
+            memcpy(out_Qe + 4 * b + 2, &w[4], 4);  // t2
+            out_Qe[4 * b + 3] = (float)w[2];       // 1 = the query cannot be bounded
+        }
+        if (out_codes)  // the operand's placement (q6_slot) back to natural element order
+            for (int pl = 0; pl < 2; ++pl)
+                for (size_t i = 0; i < dim; ++i) {
+                    int u, g, j;
+                    q6_slot((int)i, &u, &g, &j);
+                    out_codes[((size_t)b * 2 + pl) * dim + i] = planes[(size_t)((u * 2 + pl) * 64 + 16 * g + b) * 16 + (size_t)j];
+                }
+    }
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_prune6_survivors_mq(ssw_index *idx, int32_t nq, int32_t slot, float threshold, int32_t k,
+                                         int32_t sel_count, int32_t sel_overflow, int64_t cap, int32_t *out_published,
+                                         int64_t *out_collected, int64_t *out_rows) {
+    SSW_REQUIRE(idx != nullptr && out_published != nullptr && out_collected != nullptr, "NULL argument");
+    SSW_REQUIRE(nq >= 1 && nq <= Q8_MQ_WIDTH && slot >= 0 && slot < nq, "slot=%d outside the chunk of %d", slot, nq);
+    SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
+    SSW_REQUIRE(cap >= 0 && cap <= SURV_CAP, "cap=%lld outside [0, %lld]", (long long)cap, (long long)SURV_CAP);
+    SSW_REQUIRE(cap == 0 || out_rows != nullptr, "out_rows is NULL");
+    PruneBatchState &pb = idx->prune_batch;
+    SSW_REQUIRE(idx->scores_partial && pb.six && idx->prune.q6 && !idx->prune.stale6 && pb.slots >= nq &&
+                    idx->batch.side_slabs >= nq - 1,
+                "no bounds of such a chunk in the buffers: ssw_debug_prune6_bounds_mq first");
+    DeviceGuard guard(idx->device);
+    SSW_TRY(ensure_ws(idx));
+    unsigned *st = pb.mq + slot * Q8_MQ_WORDS;
+    SSW_HIP_TRY(hipMemsetAsync(st, 0, sizeof(unsigned), idx->stream));      // the counter and the "selection failed"
+    SSW_HIP_TRY(hipMemsetAsync(st + 5, 0, sizeof(unsigned), idx->stream));  // word k_q6_query_mq resets
+    SSW_TRY(stand_in_threshold(idx, threshold, k, sel_count, sel_overflow));
+    SSW_TRY(prune_survivors_slot(idx, nq, slot, k, cap));
+    int32_t m[Q8_MQ_WIDTH];
+    SSW_TRY(prune_publish_mq(idx, nq, cap, nullptr, m));
+    unsigned collected = 0u;
+    SSW_HIP_TRY(hipMemcpyAsync(&collected, st, sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
+    if (m[slot] > 0)
+        SSW_HIP_TRY(hipMemcpyAsync(out_rows, pb.surv_rows + (int64_t)slot * SURV_CAP, (size_t)m[slot] * sizeof(int64_t),
+                                   hipMemcpyDeviceToHost, idx->stream));
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+    *out_published = m[slot];
     *out_collected = (int64_t)collected;
     return SSW_OK;
 }

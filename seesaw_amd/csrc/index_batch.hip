@@ -181,8 +181,8 @@ static ssw_status check_excluded_offsets(const ssw_index *idx, const BatchExclud
     return check_excluded(idx, ex.images, ex.offsets[0], ex.offsets[nq]);
 }
 
-// The scores of a pruned chunk: ONE pass over the int8 shadow bounds its w queries [b, b + w), already in batch.qb_dev
-// (prune.hip, "Pruned batch"); per query a threshold selection and the survivors, one publish and ONE host wait for
+// The scores of a pruned chunk: ONE pass over the shadow prune_batch_shadow chose bounds its w queries [b, b + w), already
+// in batch.qb_dev (prune.hip, "Pruned batch"); per query a threshold selection and the survivors, one publish and ONE host wait for
 // the chunk, then exact rescoring of each query's survivors, or its full scan where the certificate failed.
 // m[j]: the survivors of slot j, -1 where its slab holds the full scan.
 static ssw_status prune_scan_chunk(ssw_index *idx, const BatchExcluded &excl, int32_t b, int w, int32_t k, int32_t *m) {
@@ -237,7 +237,7 @@ static ssw_status topk_batch_run(ssw_index *idx, const float *q_host, int32_t nq
     if (avg && nq == 1) pruned = false;  // the single call below prunes by itself, on whichever shadow applies
     if (pruned) {
         bool ready = false;
-        if (prune_batch_eligible(idx) && idx->ws.xchg.msg_out == nullptr) SSW_TRY(ensure_shadow(idx, &ready));
+        if (idx->ws.xchg.msg_out == nullptr) SSW_TRY(prune_batch_shadow(idx, &ready));
         if (ready) SSW_TRY(batch_buffers(idx, std::min<int32_t>(nq, Q8_MQ_WIDTH), true, &W));
         pruned = ready && idx->batch.qb_dev;
     }
@@ -354,7 +354,7 @@ static ssw_status empty_slots(ssw_index *idx, int32_t first, int32_t n) {
 }
 
 // The chunk of w queries [b, b + w) of ssw_index_topk_batch_dev_pruned, already in batch.qb_dev: prune_scan_chunk without
-// its host wait.  The bounds of all w queries from one pass over the int8 shadow; per slot the threshold selection (no
+// its host wait.  The bounds of all w queries from one pass over the chosen shadow; per slot the threshold selection (no
 // message, no host result) and the survivors; ONE launch scores every certified slot's survivors into its slab
 // (rescore_dev.hip).  Nothing is published: which slots failed their certificate stays on the device, where
 // launch_mark_uncertified tells the slot's message after the selection.
@@ -396,7 +396,7 @@ static ssw_status topk_batch_dev_run(ssw_index *idx, const float *q_host, int32_
     if (pruned) {
         bool ready = false;
         idx->prune_batch.dev_w = 0;  // until a chunk of this call says otherwise
-        if (prune_batch_eligible(idx)) SSW_TRY(ensure_shadow(idx, &ready));
+        SSW_TRY(prune_batch_shadow(idx, &ready));
         if (ready) SSW_TRY(batch_buffers(idx, std::min<int32_t>(nq, Q8_MQ_WIDTH), true, &W));
         pruned = ready && idx->batch.qb_dev;
     }

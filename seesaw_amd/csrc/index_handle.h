@@ -63,6 +63,9 @@ struct PruneBatchState {
     int64_t *surv_rows = nullptr;  // [slots][SURV_CAP]
     float *surv_scores = nullptr;  // [slots][SURV_CAP]
     int slots = 0;
+    // the shadow that bounds the chunk (prune_batch_shadow): the packed 6-bit one, else the int8 one.  The state words,
+    // the planes and the slabs hold one chunk at a time, so only one shadow ever serves them
+    bool six = false;
     int32_t *host = nullptr;       // pinned, mapped: [seq, survivors or -1 of each slot]
     unsigned seq = 0;
     // the last chunk of ssw_index_topk_batch_dev_pruned, for ssw_index_prune_batch_dev_read: its width (0: the words
@@ -223,7 +226,8 @@ ssw_status prune_survivors(ssw_index *idx, int32_t k, int64_t cap, hipEvent_t sl
 ssw_status prune6_survivors(ssw_index *idx, int32_t k, int64_t cap, hipEvent_t sleep_ev_or_null, int32_t *out_m);
 ssw_status scan_for_topk(ssw_index *idx, const float *q_dev, int32_t k, bool *out_candidates);
 ssw_status ensure_prune_batch(ssw_index *idx, int w, int *out_w);
-ssw_status prune_bounds_mq(ssw_index *idx, int w, int32_t *dbg_hi, int32_t *dbg_lo);
+ssw_status prune_batch_shadow(ssw_index *idx, bool *ready);
+ssw_status prune_bounds_mq(ssw_index *idx, int w, int32_t *dbg_hi, int32_t *dbg_lo, int64_t *dbg_I = nullptr);
 ssw_status prune_survivors_slot(ssw_index *idx, int w, int j, int32_t k, int64_t cap);
 ssw_status prune_publish_mq(ssw_index *idx, int w, int64_t cap, hipEvent_t sleep_ev_or_null, int32_t *out_m);
 ssw_status rescore_rows(ssw_index *idx, const float *q_dev, const int64_t *rows_dev, float *vals_dev, int64_t m, float *dst,

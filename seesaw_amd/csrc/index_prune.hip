@@ -32,11 +32,23 @@ constexpr int64_t PRUNE6_MIN_ROWS = (int64_t)1 << 23;
 // 0.155; 6.75 against 8.10 at 100 M).  At 2^23 and 12.5 M rows the 6-bit call is ahead by 0.06 and 0.12 ms, but both
 // forms' spreads were 0.2-0.3 ms in that run, so the rule does not admit them.
 constexpr int64_t PRUNE6_MIN_ROWS_F16 = (int64_t)1 << 24;
+// The pruned batch on an index of at least this many rows bounds its chunks on the 6-bit shadow instead of the int8 one
+// ("Pruned batch on the 6-bit shadow"); below it, and never below the single call's constants
+// (prune6_eligible), the int8 shadow as before.  Constants of their own under the rule above, from
+// tools/perf_prune_batch.py --shadow both (profiles/prune6_batch_ab.txt; the plain, the int8 and the 6-bit batch
+// alternating in one process): 25 M rows is the smallest measured size from which the 6-bit batch is ahead of the
+// int8 batch by more than both spreads, there and above, at nq = 16 and nq = 4 (f32: 0.330 against 0.366 ms a query at
+// nq = 16, spreads 0.015 together; 0.864 against 1.030 at 100 M).  At 2^24 rows and nq = 16 it is ahead by 0.018 (f32)
+// and 0.017 ms (f16) with spreads of 0.021 and 0.019 together -- the two ranges do not overlap, but the rule does not
+// admit it; at 2^23 f32 rows it is ahead by 0.008 with spreads of 0.003, which a size above that fails does not carry.
+constexpr int64_t PRUNE6_BATCH_MIN_ROWS = 25000000;
+constexpr int64_t PRUNE6_BATCH_MIN_ROWS_F16 = 25000000;
 constexpr int64_t PRUNE_RESERVE = (int64_t)4 << 30;   // free device memory the shadow must leave
 static SSW_TUNABLE bool g_prune = true;               // ssw_tune_prune
 static SSW_TUNABLE bool g_prune6 = true;              // ssw_tune_prune6
 static SSW_TUNABLE int64_t g_prune6_min_rows = -1;     // >= 0: this many rows for both dtypes instead
 static SSW_TUNABLE int64_t g_prune_min_rows = -1;      // >= 0: this many rows for both dtypes instead
+static SSW_TUNABLE int64_t g_prune6_batch_min_rows = -1;  // ssw_tune_prune6_batch: >= 0: the batch's, for both dtypes
 static SSW_TUNABLE int64_t g_prune_reserve = PRUNE_RESERVE;
 static SSW_TUNABLE int64_t g_surv_cap_dev = SURV_CAP;  // ssw_tune_surv_cap: of ssw_index_topk_batch_dev_pruned only
 
@@ -63,6 +75,12 @@ static int64_t prune6_min_rows(const ssw_index *idx) {
     return idx->dtype == SSW_DTYPE_F16 ? PRUNE6_MIN_ROWS_F16 : PRUNE6_MIN_ROWS;
 }
 bool ssw::prune6_eligible(const ssw_index *idx) { return g_prune6 && prune_eligible_from(idx, prune6_min_rows(idx)); }
+// (ssw_tune_prune6's min_rows is the single call's constant alone: lowering it leaves the batch on the int8 shadow)
+static bool prune6_batch_eligible(const ssw_index *idx) {
+    int64_t batch_rows = idx->dtype == SSW_DTYPE_F16 ? PRUNE6_BATCH_MIN_ROWS_F16 : PRUNE6_BATCH_MIN_ROWS;
+    if (g_prune6_batch_min_rows >= 0) batch_rows = g_prune6_batch_min_rows;
+    return prune6_eligible(idx) && idx->n >= batch_rows;
+}
 
 // the rows are about to change: the buffer keeps the scores of the rows it was computed from, the shadow goes stale
 ssw_status ssw::rows_changing(ssw_index *idx) {
@@ -279,7 +297,8 @@ ssw_status ssw::rescore_rows(ssw_index *idx, const float *q_dev, const int64_t *
     return SSW_OK;
 }
 
-// ---- the pruned batch: ONE pass over the int8 shadow bounds a chunk of up to 16 queries (prune.hip, "Pruned batch") ----
+// ---- the pruned batch: ONE pass over the int8 or the 6-bit shadow bounds a chunk of up to 16 queries (prune.hip,
+// "Pruned batch") ----
 static_assert(BATCH_MAX_WIDTH == Q8_MQ_WIDTH, "a chunk of the pruned batch uses the batch's slabs");
 
 // the state of a chunk of w queries; the survivor lists may only be had for fewer slots: *out_w
@@ -319,15 +338,36 @@ ssw_status ssw::ensure_prune_batch(ssw_index *idx, int w, int *out_w) {
     return SSW_OK;
 }
 
-// The two device steps of a chunk that the lab hook drives as well; the shadow and the chunk's buffers are ready and
-// the w queries are in batch.qb_dev.  Lower bounds of query j into slab j; the handle's buffer (the last query's slab)
-// is partial from here on and q_last is the last query.
-ssw_status ssw::prune_bounds_mq(ssw_index *idx, int w, int32_t *dbg_hi, int32_t *dbg_lo) {
+// The shadow that bounds the chunks of a pruned batch, made ready: the single call's rule (scan_for_topk).  The 6-bit one
+// where prune6_eligible says so and the index has the batch's rows for it (only that one is built then); else, and
+// where the 6-bit shadow is refused for memory, the int8 one under prune_batch_eligible.  prune_batch.six remembers
+// the choice for the steps below.  *ready false: the batch is the plain one.
+ssw_status ssw::prune_batch_shadow(ssw_index *idx, bool *ready) {
+    *ready = false;
+    bool six = false;
+    if (prune6_batch_eligible(idx)) SSW_TRY(ensure_shadow6(idx, &six));
+    if (!six && prune_batch_eligible(idx)) SSW_TRY(ensure_shadow(idx, ready));
+    if (six) *ready = true;
+    if (*ready) idx->prune_batch.six = six;
+    return SSW_OK;
+}
+
+// The two device steps of a chunk that the lab hooks drive as well; the shadow prune_batch.six names and the chunk's
+// buffers are ready and the w queries are in batch.qb_dev.  Lower bounds of query j into slab j; the handle's buffer
+// (the last query's slab) is partial from here on and q_last is the last query.  dbg_hi / dbg_lo: of the int8 chunk,
+// dbg_I: of the 6-bit chunk (lab hooks only).
+ssw_status ssw::prune_bounds_mq(ssw_index *idx, int w, int32_t *dbg_hi, int32_t *dbg_lo, int64_t *dbg_I) {
     PruneState &p = idx->prune;
     PruneBatchState &pb = idx->prune_batch;
-    SSW_TRY(launch_q8_query_mq(idx->batch.qb_dev, idx->dim, w, pb.mq, pb.planes, p.q_last, idx->stream));
-    SSW_TRY(launch_q8_bounds_mq(p.q8, p.q8_scale, p.q8_err, pb.planes, pb.mq, w, idx->batch.side, slab_stride(idx),
-                                idx->scores, idx->n, idx->dim, dbg_hi, dbg_lo, idx->device, idx->stream));
+    if (pb.six) {
+        SSW_TRY(launch_q6_query_mq(idx->batch.qb_dev, idx->dim, w, pb.mq, pb.planes, p.q_last, idx->stream));
+        SSW_TRY(launch_q6_bounds_mq(p.q6, p.q6_scale, p.q6_err, pb.planes, pb.mq, w, idx->batch.side, slab_stride(idx),
+                                    idx->scores, idx->n, idx->dim, dbg_I, idx->device, idx->stream));
+    } else {
+        SSW_TRY(launch_q8_query_mq(idx->batch.qb_dev, idx->dim, w, pb.mq, pb.planes, p.q_last, idx->stream));
+        SSW_TRY(launch_q8_bounds_mq(p.q8, p.q8_scale, p.q8_err, pb.planes, pb.mq, w, idx->batch.side, slab_stride(idx),
+                                    idx->scores, idx->n, idx->dim, dbg_hi, dbg_lo, idx->device, idx->stream));
+    }
     idx->scores_partial = true;
     return SSW_OK;
 }
@@ -336,9 +376,11 @@ ssw_status ssw::prune_bounds_mq(ssw_index *idx, int w, int32_t *dbg_hi, int32_t 
 ssw_status ssw::prune_survivors_slot(ssw_index *idx, int w, int j, int32_t k, int64_t cap) {
     PruneState &p = idx->prune;
     PruneBatchState &pb = idx->prune_batch;
-    return launch_survivors_mq(chunk_slab(idx, w, j), p.q8_err, p.q8_scale, p.q8_max, idx->n, idx->dim, idx->ws.out_keys,
-                               idx->ws.out_count, k, pb.mq + j * Q8_MQ_WORDS, pb.surv_rows + (int64_t)j * SURV_CAP, cap,
-                               idx->device, idx->stream);
+    const bool six = pb.six;
+    return launch_survivors_mq(chunk_slab(idx, w, j), six ? p.q6_err : p.q8_err, six ? p.q6_scale : p.q8_scale,
+                               six ? p.q6_max : p.q8_max, idx->n, idx->dim, six, idx->ws.out_keys, idx->ws.out_count, k,
+                               pb.mq + j * Q8_MQ_WORDS, pb.surv_rows + (int64_t)j * SURV_CAP, cap, idx->device,
+                               idx->stream);
 }
 
 // every slot's count (or -1) of the chunk -> out_m[w]; ONE host wait: a sleep on sleep_ev_or_null first, then a spin
@@ -432,6 +474,11 @@ ssw_status ssw_tune_prune6(int32_t enable, int64_t min_rows) {
     return SSW_OK;
 }
 
+ssw_status ssw_tune_prune6_batch(int64_t min_rows) {
+    g_prune6_batch_min_rows = min_rows < 0 ? -1 : min_rows;  // < 0: PRUNE6_BATCH_MIN_ROWS / PRUNE6_BATCH_MIN_ROWS_F16 again
+    return SSW_OK;
+}
+
 ssw_status ssw_tune_prune6_scan(int32_t blocks_per_cu, int32_t tiles) {
     tune_q6_bounds(blocks_per_cu, tiles);
     return SSW_OK;
@@ -439,6 +486,11 @@ ssw_status ssw_tune_prune6_scan(int32_t blocks_per_cu, int32_t tiles) {
 
 ssw_status ssw_tune_prune_scan_mq(int32_t blocks_per_cu, int32_t tiles) {
     tune_q8_bounds_mq(blocks_per_cu, tiles);
+    return SSW_OK;
+}
+
+ssw_status ssw_tune_prune6_scan_mq(int32_t blocks_per_cu, int32_t tiles) {
+    tune_q6_bounds_mq(blocks_per_cu, tiles);
     return SSW_OK;
 }
 #endif

@@ -1047,6 +1047,157 @@ __global__ __launch_bounds__(256) void k_q6_bounds(const u32x4 *__restrict__ cod
         bounds(t, nfull, ragged);
     }
 }
+
+// ---- a chunk of up to 16 queries on the 6-bit shadow ("Pruned batch on the 6-bit shadow") ---------
+// k_q6_bounds multiplies 14 of the 16 query columns by zeros; here every column is a query of the chunk, (***) holds per
+// slot, and the pass costs the same code loads and the same unpack with two MFMAs a k-step instead of one.
+// Query operand: with (u, g, j) = q6_slot(i) the code of element i, plane p (0 hi, 1 lo) of query b is byte
+// (((u * 2 + p) * 64 + 16 g + b) * 16 + j): the operand of k-step u and plane p is the u32x4 at (u * 2 + p) * 64 + l of
+// lane l, column l & 15 the query, its elements those the row operand of k_q6_bounds holds in lane group l >> 4.  The
+// buffer is the int8 chunk's (q8_mq_plane_bytes): one shadow serves a chunk.
+// One block a slot.  Slots >= w get zero codes and nothing else.
+__global__ __launch_bounds__(256) void k_q6_query_mq(const float *__restrict__ qb, int dim, int w, unsigned *__restrict__ mq,
+                                                     int8_t *__restrict__ planes, float *__restrict__ q_last) {
+    const int b = blockIdx.x;
+    auto code_at = [&](int i, int p) -> int8_t * {
+        int u, g, j;
+        q6_slot(i, &u, &g, &j);
+        return planes + ((size_t)((u * 2 + p) * 64 + 16 * g + b) * 16 + j);
+    };
+    if (b >= w) {
+        for (int i = threadIdx.x; i < dim; i += 256) *code_at(i, 0) = 0, *code_at(i, 1) = 0;
+        return;
+    }
+    mq_quantise_query(qb + (size_t)b * dim, dim, b == w - 1 ? q_last : nullptr, mq + b * MQ_WORDS, code_at);
+}
+
+constexpr int Q6MQ_BLOCKS_PER_CU = 1;
+SSW_TUNABLE int g_q6mq_blocks_per_cu = Q6MQ_BLOCKS_PER_CU;
+SSW_TUNABLE int g_q6mq_tiles = 0;  // 0: q6mq_default_tiles(C)
+constexpr int q6mq_default_tiles(int C) { return 4 / C; }  // k_q6_bounds' request: 12 KiB a wave at every dim
+
+// lb of every row for every query of the chunk: query j's into slab j (j + 1 < w: side + j * stride, the last: own).
+// The tile loads (NL contiguous 1-KiB loads a tile, a tile past last_tile read as last_tile again) and the unpack are
+// k_q6_bounds'; the two accumulators, the two MFMAs a k-step and the result map are k_q8_bounds_mq's: lane l holds query
+// l & 15 and rows 4 (l >> 4) .. + 3 of the tile and writes its four bounds with one 16-byte store into its slot's slab.
+// The loop is theirs: two register sets in turn, the next group's codes and constants requested before the current
+// group's products, one exit, the last n % (16 T) rows as one clamped group for one wave, nothing stored for a row >= n
+// or by the lanes of a slot >= w.  The epilogue is (***) in double, per slot.
+// DEBUG (lab hook only): I_r of query j goes to dbg_I[j * n + r] as well.
+template <int C, int T, bool DEBUG>
+__global__ __launch_bounds__(256) void k_q6_bounds_mq(const u32x4 *__restrict__ codes, const float *__restrict__ scale,
+                                                      const float *__restrict__ err, const u32x4 *__restrict__ planes,
+                                                      const unsigned *__restrict__ mq, int w, float *__restrict__ side,
+                                                      int64_t stride, float *__restrict__ own, int64_t n,
+                                                      int64_t *__restrict__ dbg_I) {
+    constexpr int dim = 256 * C, KS = dim / 64, NL = 3 * C, G = 16 * T;  // NL 1-KiB loads a tile
+    constexpr unsigned TILE_VECS = NL * 64;
+    const int lane = threadIdx.x & 63;
+    const int col = lane & 15, quad = lane >> 4;
+    const int64_t gwave = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t nwaves = (int64_t)gridDim.x * 4;
+    const int64_t nfull = n / G;
+    const int ragged = (int)(n % G);
+    i32x4 qh[KS], ql[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        qh[ks] = __builtin_bit_cast(i32x4, planes[(ks * 2) * 64 + lane]);
+        ql[ks] = __builtin_bit_cast(i32x4, planes[(ks * 2 + 1) * 64 + lane]);
+    }
+    const bool live = col < w;
+    float *__restrict__ slab = col + 1 < w ? side + (int64_t)col * stride : own;
+    const unsigned *st = mq + (live ? col : 0) * MQ_WORDS;
+    const double t2q = (double)__uint_as_float(st[4]) * 0.25;  // exact: the sums are of 4 c
+    const double wQ = (double)__uint_as_float(st[1]) * MQ_INFLATE;
+    const double wE = (double)__uint_as_float(st[3]) * q6_code_norm(dim) * MQ_INFLATE;
+    struct Set {
+        u32x4 c[T][NL];
+        float s[T][4], a[T][4];
+    };
+    // tile0: the group's first tile; last_tile: none beyond it is read
+    auto load = [&](Set &d, int64_t tile0, int64_t last_tile, bool nt) {
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const int64_t tile = tile0 + t < last_tile ? tile0 + t : last_tile;  // wave-uniform
+            const u32x4 *base = codes + tile * (int64_t)TILE_VECS + lane;
+#pragma unroll
+            for (int l = 0; l < NL; ++l) d.c[t][l] = nt ? __builtin_nontemporal_load(base + l * 64) : base[l * 64];
+        }
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const int64_t tile = tile0 + t < last_tile ? tile0 + t : last_tile;
+            const float4 sv = *reinterpret_cast<const float4 *>(scale + tile * 16 + 4 * quad);
+            const float4 av = *reinterpret_cast<const float4 *>(err + tile * 16 + 4 * quad);
+            d.s[t][0] = sv.x, d.s[t][1] = sv.y, d.s[t][2] = sv.z, d.s[t][3] = sv.w;
+            d.a[t][0] = av.x, d.a[t][1] = av.y, d.a[t][2] = av.z, d.a[t][3] = av.w;
+        }
+        __builtin_amdgcn_sched_barrier(0);  // as in k_q8_bounds: the requests stay ahead of the products
+    };
+    // the bounds of the first `rows` rows of group g from a set that has arrived (rows == G: whole stores)
+    auto bounds = [&](const Set &d, int64_t g, int rows) {
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            unsigned wd[4 * NL];
+#pragma unroll
+            for (int l = 0; l < NL; ++l) wd[4 * l] = d.c[t][l].x, wd[4 * l + 1] = d.c[t][l].y, wd[4 * l + 2] = d.c[t][l].z, wd[4 * l + 3] = d.c[t][l].w;
+            i32x4 hi = {0, 0, 0, 0}, lo = {0, 0, 0, 0};
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const unsigned w0 = wd[3 * ks], w1 = wd[3 * ks + 1], w2 = wd[3 * ks + 2];
+                const i32x4 a = {(int)(w0 & 0xfcfcfcfcu), (int)(w1 & 0xfcfcfcfcu), (int)(w2 & 0xfcfcfcfcu),
+                                 (int)(((w0 & 0x03030303u) << 6) | ((w1 & 0x03030303u) << 4) | ((w2 & 0x03030303u) << 2))};
+                hi = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, qh[ks], hi, 0, 0, 0);
+                lo = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, ql[ks], lo, 0, 0, 0);
+            }
+            float out[4];
+            double I[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                I[i] = (double)hi[i] * 256.0 + (double)lo[i];  // exact: |I| < 2^33 at dim 1024
+                const double sd = (double)d.s[t][i];
+                const double wv = (double)d.a[t][i] * wQ + sd * wE;
+                double lb = sd * t2q * I[i] - wv;
+                lb -= fabs(lb) * 0x1p-50 + PAD_ABS;
+                out[i] = __double2float_rd(lb);
+            }
+            const int r0 = t * 16 + 4 * quad;  // of the lane's four rows in the group
+            if (rows == G) {
+                if (live) *reinterpret_cast<float4 *>(slab + g * G + r0) = make_float4(out[0], out[1], out[2], out[3]);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (live && r0 + i < rows) (slab + g * G)[r0 + i] = out[i];
+            }
+            if constexpr (DEBUG) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (live && r0 + i < rows) (dbg_I + (int64_t)col * n + g * G)[r0 + i] = (int64_t)I[i];
+            }
+        }
+    };
+    if (gwave < nfull) {
+        const int64_t last = nfull * T - 1;
+        Set a, b;
+        int64_t g = gwave;
+        load(a, g * T, last, true);
+        for (;;) {
+            // a wave without a next group requests its last one once more (cache hits) and writes nothing for it
+            const int64_t g1 = g + nwaves < nfull ? g + nwaves : g;
+            load(b, g1 * T, last, true);
+            bounds(a, g, G);
+            const int64_t g2 = g1 + nwaves < nfull ? g1 + nwaves : g1;
+            load(a, g2 * T, last, true);
+            bounds(b, g1, g1 != g ? G : 0);
+            if (g2 == g1) break;
+            g = g2;
+        }
+    }
+    if (ragged != 0 && gwave == nfull % nwaves) {
+        Set t;
+        load(t, nfull * T, (n - 1) >> 4, false);
+        bounds(t, nfull, ragged);
+    }
+}
 }  // namespace
 
 bool q8_dim_supported(int32_t dim) { return dim == 256 || dim == 512 || dim == 1024; }
@@ -1228,15 +1379,16 @@ void tune_q8_bounds_mq(int blocks_per_cu, int tiles) {
 }
 #endif
 
+// six: the bounds, err, scale and mx are the 6-bit shadow's (width (***)), else the int8 shadow's (width (**))
 ssw_status launch_survivors_mq(const float *lb, const float *err, const float *scale, const unsigned *mx, int64_t n, int32_t dim,
-                               const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *slot_state,
+                               bool six, const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *slot_state,
                                int64_t *rows, int64_t cap, int device, hipStream_t stream) {
     int64_t grid = (int64_t)num_cus(device) * 4;
     const int64_t need = (n + 1023) / 1024;  // four rows a lane
     if (grid > need) grid = need;
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(k_survivors_mq, dim3((unsigned)grid), dim3(256), 0, stream, lb, err, scale, mx, n, mq_code_norm(dim),
-                       keys, sel_count, k, slot_state, rows, cap);
+    hipLaunchKernelGGL(k_survivors_mq, dim3((unsigned)grid), dim3(256), 0, stream, lb, err, scale, mx, n,
+                       six ? q6_code_norm(dim) : mq_code_norm(dim), keys, sel_count, k, slot_state, rows, cap);
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
 }
@@ -1356,6 +1508,78 @@ ssw_status launch_q6_bounds(const unsigned char *codes, const float *scale, cons
 void tune_q6_bounds(int blocks_per_cu, int tiles) {
     g_q6_blocks_per_cu = blocks_per_cu >= 1 && blocks_per_cu <= 8 ? blocks_per_cu : Q6_BLOCKS_PER_CU;
     g_q6_tiles = tiles == 1 || tiles == 2 || tiles == 4 ? tiles : 0;
+}
+#endif
+
+// ---- a chunk of up to 16 queries on the 6-bit shadow ------------------------------------------------------------------
+// planes: q8_mq_plane_bytes(dim), the int8 chunk's buffer
+ssw_status launch_q6_query_mq(const float *qb_dev, int32_t dim, int32_t w, unsigned *mq, int8_t *planes, float *q_last,
+                              hipStream_t stream) {
+    hipLaunchKernelGGL(k_q6_query_mq, dim3(MQ_WIDTH), dim3(256), 0, stream, qb_dev, (int)dim, (int)w, mq, planes, q_last);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+static int q6mq_tiles(int C) {
+    int t = g_q6mq_tiles > 0 ? g_q6mq_tiles : q6mq_default_tiles(C);
+    while (t * C > 4) t >>= 1;  // two register sets of more than 12 KiB a wave do not fit beside the query planes
+    return t;
+}
+
+void q6_bounds_mq_shape(int32_t dim, int device, int64_t n, int *out_blocks, int *out_tiles) {
+    const int T = q6mq_tiles(dim / 256);
+    const int64_t need = ((n + 16 * T - 1) / (16 * T) + 3) / 4;
+    int64_t grid = (int64_t)num_cus(device) * g_q6mq_blocks_per_cu;
+    if (grid > need) grid = need;
+    if (grid < 1) grid = 1;
+    *out_blocks = (int)grid;
+    *out_tiles = T;
+}
+
+ssw_status launch_q6_bounds_mq(const unsigned char *codes, const float *scale, const float *err, const int8_t *planes,
+                               const unsigned *mq, int32_t w, float *side, int64_t stride, float *own, int64_t n,
+                               int32_t dim, int64_t *dbg_I, int device, hipStream_t stream) {
+    if (n <= 0) return SSW_OK;
+    if (!q8_dim_supported(dim) || w < 1 || w > MQ_WIDTH) {
+        set_error("q6_bounds_mq: dim=%d, w=%d unsupported", dim, w);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    const int C = dim / 256;
+    int grid = 1, T = 1;
+    q6_bounds_mq_shape(dim, device, n, &grid, &T);
+    const u32x4 *cd = reinterpret_cast<const u32x4 *>(codes), *pl = reinterpret_cast<const u32x4 *>(planes);
+#define SSW_Q6MQ(C_, T_, D_)                                                                                           \
+    hipLaunchKernelGGL((k_q6_bounds_mq<C_, T_, D_>), dim3((unsigned)grid), dim3(256), 0, stream, cd, scale, err, pl, mq, \
+                       (int)w, side, stride, own, n, dbg_I)
+#ifdef SSW_DEBUG_HOOKS
+#define SSW_Q6MQ_T(C_, T_)             \
+    if (dbg_I) SSW_Q6MQ(C_, T_, true); \
+    else SSW_Q6MQ(C_, T_, false)
+    if (C == 1) {
+        if (T == 1) { SSW_Q6MQ_T(1, 1); } else if (T == 2) { SSW_Q6MQ_T(1, 2); } else { SSW_Q6MQ_T(1, 4); }
+    } else if (C == 2) {
+        if (T == 1) { SSW_Q6MQ_T(2, 1); } else { SSW_Q6MQ_T(2, 2); }
+    } else {
+        SSW_Q6MQ_T(4, 1);
+    }
+#undef SSW_Q6MQ_T
+#else
+    (void)T;
+    switch (C) {
+        case 1: SSW_Q6MQ(1, q6mq_default_tiles(1), false); break;
+        case 2: SSW_Q6MQ(2, q6mq_default_tiles(2), false); break;
+        default: SSW_Q6MQ(4, q6mq_default_tiles(4), false); break;
+    }
+#endif
+#undef SSW_Q6MQ
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+#ifdef SSW_DEBUG_HOOKS
+void tune_q6_bounds_mq(int blocks_per_cu, int tiles) {
+    g_q6mq_blocks_per_cu = blocks_per_cu >= 1 && blocks_per_cu <= 8 ? blocks_per_cu : Q6MQ_BLOCKS_PER_CU;
+    g_q6mq_tiles = tiles == 1 || tiles == 2 || tiles == 4 ? tiles : 0;
 }
 #endif
 

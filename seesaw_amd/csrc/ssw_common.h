@@ -194,8 +194,9 @@ ssw_status launch_q8_query_mq(const float *qb_dev, int32_t dim, int32_t w, unsig
 ssw_status launch_q8_bounds_mq(const int8_t *codes, const float *scale, const float *err, const int8_t *planes,
                                const unsigned *mq, int32_t w, float *side, int64_t stride, float *own, int64_t n,
                                int32_t dim, int32_t *dbg_hi, int32_t *dbg_lo, int device, hipStream_t stream);
+// six: lb, err, scale and mx are the 6-bit shadow's (launch_q6_bounds_mq), else the int8 shadow's
 ssw_status launch_survivors_mq(const float *lb, const float *err, const float *scale, const unsigned *mx, int64_t n, int32_t dim,
-                               const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *slot_state,
+                               bool six, const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *slot_state,
                                int64_t *rows, int64_t cap, int device, hipStream_t stream);
 ssw_status launch_prune_publish_mq(const unsigned *mq, int32_t w, int64_t cap, int32_t *host_block, unsigned seq,
                                    hipStream_t stream);
@@ -237,6 +238,14 @@ void q6_bounds_shape(int32_t dim, int device, int64_t n, int *out_blocks, int *o
 ssw_status launch_survivors_q6(const float *lb, const float *err, const float *scale, const unsigned *mx, int64_t n, int32_t dim,
                                const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *st, int64_t *rows,
                                int64_t cap, int32_t *host_block, unsigned seq, int device, hipStream_t stream);
+// the chunk of w <= 16 queries on the 6-bit shadow (prune.hip): mq and planes are the int8 chunk's buffers
+// (q8_mq_plane_bytes), the slabs launch_q8_bounds_mq's; dbg_I (lab hook only, else NULL): [w, n] the exact integer sums
+ssw_status launch_q6_query_mq(const float *qb_dev, int32_t dim, int32_t w, unsigned *mq, int8_t *planes, float *q_last,
+                              hipStream_t stream);
+ssw_status launch_q6_bounds_mq(const unsigned char *codes, const float *scale, const float *err, const int8_t *planes,
+                               const unsigned *mq, int32_t w, float *side, int64_t stride, float *own, int64_t n,
+                               int32_t dim, int64_t *dbg_I, int device, hipStream_t stream);
+void q6_bounds_mq_shape(int32_t dim, int device, int64_t n, int *out_blocks, int *out_tiles);
 // rows between natural order and the index.  to_h16: n rows of natural-order f32 (src_f32) or binary16 (src_h16, the
 // other NULL) -> rows [0, n) of dst in the f16 layout, rounded to nearest even.  gather: rows (rows_or_null[i], or
 // first_row + i when it is NULL) of an index matrix of element type dtype -> n natural-order f32 rows of out.
@@ -250,6 +259,7 @@ void tune_scan_batch(int max_width, int blocks_per_cu);
 void tune_q8_bounds(int blocks_per_cu, int group_loads);
 void tune_q8_bounds_mq(int blocks_per_cu, int tiles);
 void tune_q6_bounds(int blocks_per_cu, int tiles);
+void tune_q6_bounds_mq(int blocks_per_cu, int tiles);
 #endif
 // knn.hip's last stage (lives in scan.hip to share the scan's summation order)
 ssw_status launch_knn_rescore(const float *X, int32_t dim, const int32_t *perm, int r0, int rows, const uint64_t *buf,

@@ -216,9 +216,10 @@ class DeviceIndex:
         """`[topk(Q[b], k, excluded[b]) for b]` with the rows read once per chunk of queries (ssw_index_topk_batch):
         a list of (images, scores, rows), bit for bit what the single calls return.  `excluded` is None or a sequence of
         nq iterables of image positions, each of which may be None.  The handle is left as after the last query's topk.
-        `prune=True` (ssw_index_topk_batch_pruned): on an index whose single `topk` is pruned, one pass over the int8
-        shadow bounds a chunk of up to 16 queries and only each query's survivors are scored exactly -- the same
-        results; `prune_stats` counts every query.  Any other index takes the plain batch."""
+        `prune=True` (ssw_index_topk_batch_pruned): on an index whose single `topk` is pruned, one pass over a shadow
+        -- from 25 M rows the packed 6-bit one single queries scan there, below that (or where that one is refused for
+        memory) the int8 one -- bounds a chunk of up to 16 queries and only each query's survivors are scored exactly
+        -- the same results; `prune_stats` counts every query.  Any other index takes the plain batch."""
         k = int(k)
         Q = self._queries(Q)
         nq = Q.shape[0]
@@ -289,8 +290,9 @@ class DeviceIndex:
         scores are resident -- read from the query's own score slab inside the batch.  A list of
         (images, scores, rows, avg_scores, avg_rows), `avg_*[i]` belonging to `images[i]` (selection order, not the
         ascending order `rescore_avg` is usually given).  The handle is left as after the last query's topk.
-        `prune=True` (ssw_index_topk_batch_avg_pruned): the first stage is `topk_batch(prune=True)`'s, and only the tiles of
-        each query's selected images are then scored exactly into its slab for the second stage -- the same results;
+        `prune=True` (ssw_index_topk_batch_avg_pruned): the first stage is `topk_batch(prune=True)`'s, on the same
+        shadow (6-bit or int8), and only the tiles of each query's selected images are then scored exactly into its
+        slab for the second stage -- the same results;
         `prune_stats` counts every query and the rows rescored.  Any other index takes the plain batch."""
         k = int(k)
         Q = self._queries(Q)
@@ -352,9 +354,9 @@ class DeviceIndex:
         chunk of queries and query b's selection writes its exchange message into slot `first_slot + b` of the attached
         block.  An overflowed selection is not repaired: its flag travels in the slot (`topk_slot_deep_dev`).  The
         handle is left as after `topk_dev` of the last query with its exclusion list.
-        `prune=True` (ssw_index_topk_batch_dev_pruned): on an index the pruned batch serves, one pass over the int8 shadow
-        bounds a chunk of up to 16 queries and one launch scores every query's survivors exactly, still without a host
-        wait.  A query whose certificate failed on this shard is flagged with the value 2 in its slot and repaired the
+        `prune=True` (ssw_index_topk_batch_dev_pruned): on an index the pruned batch serves, one pass over the shadow
+        `topk_batch(prune=True)` would scan (6-bit or int8) bounds a chunk of up to 16 queries and one launch scores
+        every query's survivors exactly, still without a host wait.  A query whose certificate failed on this shard is flagged with the value 2 in its slot and repaired the
         same way; `prune_batch_dev_counts` reads what the device decided.  Any other index takes the plain call."""
         Q = self._queries(Q)
         nq = Q.shape[0]
@@ -434,7 +436,8 @@ class DeviceIndex:
         it) or "refused" (too little free device memory beside it); `eligible`: the next top-k with a query is pruned;
         `last_survivors`: rows the last pruned call rescored (-1 = it fell back to the full scan); `queries` /
         `fallbacks`: pruned calls and how many of them fell back; `shadow_bytes`: device memory the shadows hold
-        (dim + 8 bytes a row for the int8 one, 3 dim / 4 + 8 for the 6-bit one; a pruned batch builds the int8 one).
+        (dim + 8 bytes a row for the int8 one, 3 dim / 4 + 8 for the 6-bit one; from 25 M rows a pruned batch scans
+        the 6-bit one single queries scan and builds no other, below that it builds and scans the int8 one).
         `completions=True` adds the two words of ssw_index_prune_completions (the six above stay what they were for
         callers that compare the whole dict): `completions`: full scans that completed a partial score buffer or slab
         for a reader; `rescored_rows`: rows the second-stage readers (`rescore_avg`, `gather_scores`, `topk_batch_avg`)
