@@ -961,14 +961,17 @@ __global__ __launch_bounds__(256) void k_q6_bounds(const u32x4 *__restrict__ cod
         u32x4 c[T][NL];
         float s[T][4], a[T][4];
     };
-    // tile0: the group's first tile; last_tile: none beyond it is read
-    auto load = [&](Set &d, int64_t tile0, int64_t last_tile, bool nt) {
+    // tile0: the group's first tile; last_tile: none beyond it is read.  Every code load is non-temporal, the ragged
+    // group's too, as in k_q8_bounds: with `nt ? __builtin_nontemporal_load(p) : *p` here the two arms were merged into
+    // one load before the constant got in, the hint was lost (no `nt` on any global_load_dwordx4 of the kernel) and the
+    // scan ran at the default policy's HBM rate.
+    auto load = [&](Set &d, int64_t tile0, int64_t last_tile) {
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             const int64_t tile = tile0 + t < last_tile ? tile0 + t : last_tile;  // wave-uniform
             const u32x4 *base = codes + tile * (int64_t)TILE_VECS + lane;
 #pragma unroll
-            for (int l = 0; l < NL; ++l) d.c[t][l] = nt ? __builtin_nontemporal_load(base + l * 64) : base[l * 64];
+            for (int l = 0; l < NL; ++l) d.c[t][l] = __builtin_nontemporal_load(base + l * 64);
         }
 #pragma unroll
         for (int t = 0; t < T; ++t) {
@@ -1028,14 +1031,14 @@ __global__ __launch_bounds__(256) void k_q6_bounds(const u32x4 *__restrict__ cod
         const int64_t last = nfull * T - 1;
         Set a, b;
         int64_t g = gwave;
-        load(a, g * T, last, true);
+        load(a, g * T, last);
         for (;;) {
             // a wave without a next group requests its last one once more (cache hits) and writes nothing for it
             const int64_t g1 = g + nwaves < nfull ? g + nwaves : g;
-            load(b, g1 * T, last, true);
+            load(b, g1 * T, last);
             bounds(a, g, G);
             const int64_t g2 = g1 + nwaves < nfull ? g1 + nwaves : g1;
-            load(a, g2 * T, last, true);
+            load(a, g2 * T, last);
             bounds(b, g1, g1 != g ? G : 0);
             if (g2 == g1) break;
             g = g2;
@@ -1043,7 +1046,7 @@ __global__ __launch_bounds__(256) void k_q6_bounds(const u32x4 *__restrict__ cod
     }
     if (ragged != 0 && gwave == nfull % nwaves) {
         Set t;
-        load(t, nfull * T, (n - 1) >> 4, false);
+        load(t, nfull * T, (n - 1) >> 4);
         bounds(t, nfull, ragged);
     }
 }
