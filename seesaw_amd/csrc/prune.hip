@@ -837,7 +837,11 @@ __global__ __launch_bounds__(256) void k_scatter_scores(const int64_t *__restric
 constexpr int Q6_BLOCKS_PER_CU = 1;
 SSW_TUNABLE int g_q6_blocks_per_cu = Q6_BLOCKS_PER_CU;
 SSW_TUNABLE int g_q6_tiles = 0;  // 0: q6_default_tiles(C)
-constexpr int q6_default_tiles(int C) { return 4 / C; }  // 16-row tiles of one request: 12 KiB a wave at every dim
+// 16-row tiles of one request of a wave: 6 KiB at dim 256 and 512, 12 KiB (one tile) at dim 1024.  From the traced sweep
+// of blocks a CU x tiles at 10^8 rows (docs/EXPERIMENTS.md, "The 6-bit scan's launch shape"): at dim 256 two tiles take
+// 3.63 ms a launch where the four of the 12-KiB rule took 4.13, at dim 512 one tile 6.17 where two took 6.25; a second
+// or fourth block a CU is level with one at dim 256 and behind it at dim 512 and 1024.
+constexpr int q6_default_tiles(int C) { return C == 1 ? 2 : 1; }
 
 // 31 sqrt(dim), rounded up
 __host__ __device__ constexpr double q6_code_norm(int dim) { return dim == 256 ? 496.0 : dim == 512 ? 701.4499270 : 992.0; }
@@ -1077,7 +1081,9 @@ __global__ __launch_bounds__(256) void k_q6_query_mq(const float *__restrict__ q
 constexpr int Q6MQ_BLOCKS_PER_CU = 1;
 SSW_TUNABLE int g_q6mq_blocks_per_cu = Q6MQ_BLOCKS_PER_CU;
 SSW_TUNABLE int g_q6mq_tiles = 0;  // 0: q6mq_default_tiles(C)
-constexpr int q6mq_default_tiles(int C) { return 4 / C; }  // k_q6_bounds' request: 12 KiB a wave at every dim
+// 12 KiB a wave at every dim, the request k_q6_bounds had when this was set; one tile at dim 512 is behind two at nq = 16
+// (profiles/q6_shape_batch_thresholds.txt)
+constexpr int q6mq_default_tiles(int C) { return 4 / C; }
 
 // lb of every row for every query of the chunk: query j's into slab j (j + 1 < w: side + j * stride, the last: own).
 // The tile loads (NL contiguous 1-KiB loads a tile, a tile past last_tile read as last_tile again) and the unpack are
@@ -1117,14 +1123,15 @@ __global__ __launch_bounds__(256) void k_q6_bounds_mq(const u32x4 *__restrict__ 
         u32x4 c[T][NL];
         float s[T][4], a[T][4];
     };
-    // tile0: the group's first tile; last_tile: none beyond it is read
-    auto load = [&](Set &d, int64_t tile0, int64_t last_tile, bool nt) {
+    // tile0: the group's first tile; last_tile: none beyond it is read.  Every code load is non-temporal, the ragged
+    // group's too, with the builtin called without a condition: k_q6_bounds' note on what `nt ? .. : *p` lost.
+    auto load = [&](Set &d, int64_t tile0, int64_t last_tile) {
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             const int64_t tile = tile0 + t < last_tile ? tile0 + t : last_tile;  // wave-uniform
             const u32x4 *base = codes + tile * (int64_t)TILE_VECS + lane;
 #pragma unroll
-            for (int l = 0; l < NL; ++l) d.c[t][l] = nt ? __builtin_nontemporal_load(base + l * 64) : base[l * 64];
+            for (int l = 0; l < NL; ++l) d.c[t][l] = __builtin_nontemporal_load(base + l * 64);
         }
 #pragma unroll
         for (int t = 0; t < T; ++t) {
@@ -1182,14 +1189,14 @@ __global__ __launch_bounds__(256) void k_q6_bounds_mq(const u32x4 *__restrict__ 
         const int64_t last = nfull * T - 1;
         Set a, b;
         int64_t g = gwave;
-        load(a, g * T, last, true);
+        load(a, g * T, last);
         for (;;) {
             // a wave without a next group requests its last one once more (cache hits) and writes nothing for it
             const int64_t g1 = g + nwaves < nfull ? g + nwaves : g;
-            load(b, g1 * T, last, true);
+            load(b, g1 * T, last);
             bounds(a, g, G);
             const int64_t g2 = g1 + nwaves < nfull ? g1 + nwaves : g1;
-            load(a, g2 * T, last, true);
+            load(a, g2 * T, last);
             bounds(b, g1, g1 != g ? G : 0);
             if (g2 == g1) break;
             g = g2;
@@ -1197,7 +1204,7 @@ __global__ __launch_bounds__(256) void k_q6_bounds_mq(const u32x4 *__restrict__ 
     }
     if (ragged != 0 && gwave == nfull % nwaves) {
         Set t;
-        load(t, nfull * T, (n - 1) >> 4, false);
+        load(t, nfull * T, (n - 1) >> 4);
         bounds(t, nfull, ragged);
     }
 }
