@@ -185,6 +185,9 @@ ssw_status ssw_index_topk_batch(ssw_index *idx, const float *q_host, int32_t nq,
  * refused for memory) the chunk's pass runs over that shadow instead, 3 dim / 4 + 8 bytes a row, and no int8 shadow is
  * built: one shadow serves both kinds of call.  The same holds for ssw_index_topk_batch_avg_pruned and
  * ssw_index_topk_batch_dev_pruned.  Which shadow certifies never changes what is returned.
+ * A dim-768 index has the packed 6-bit shadow only (584 bytes a row; there is no int8 shadow at that dim): its pruned
+ * batches scan it from 2^20 rows on (ssw_index_prune_stats) and are ssw_index_topk_batch itself below that count or
+ * when the shadow is refused for memory.
  * State afterwards: that of a pruned ssw_index_topk of the last query with its excluded list (the resident scores are
  * completed by the first reader).  ssw_index_prune_stats counts every query of a pruned batch in [3] and every one that
  * fell back in [4]; [2] is the last query's.  ssw_index_profile records one event pair per chunk.
@@ -358,7 +361,8 @@ ssw_status ssw_index_topk_slot_deep_dev(ssw_index *idx, const float *q_host, con
 /* ssw_index_topk_batch_dev with the certified int8 pre-scan of ssw_index_topk_batch_pruned, and still ENQUEUE ONLY: no
  * survivor count is published and nothing waits for the device.  Arguments, refusals and the empty index are
  * ssw_index_topk_batch_dev's.  On an index the pruned batch does not serve (fewer than 2^22 rows, dim other than 256 /
- * 512 / 1024, borrowed or escaped rows, a shadow refused for memory) the call IS ssw_index_topk_batch_dev.  Otherwise,
+ * 512 / 768 / 1024, a dim-768 index of fewer than 2^20 rows -- its own count --, borrowed or escaped rows, a shadow
+ * refused for memory) the call IS ssw_index_topk_batch_dev.  Otherwise,
  * per chunk of up to 16 queries (any width): one pass over the shadow bounds the chunk; per query the threshold
  * selection and the survivor list; ONE launch (k_rescore_survivors, csrc/rescore_dev.hip), sized by the device alone,
  * scores every certified slot's survivors -- the full scan's bits -- straight into its slab; per query the ordinary
@@ -414,6 +418,11 @@ ssw_status ssw_index_profile_read(ssw_index *idx, float *out_ms, int32_t cap, in
  * An index that borrows a device matrix and an index whose row pointer ssw_index_device_ptrs has handed out never get
  * a shadow.  An f16 index with its shadow holds dim * 3 + 8 bytes a row.  The environment variable SSW_TOPK_FULL_SCAN
  * (read once) forces the full scan everywhere, for both element types.
+ * Dim 768 (CLIP ViT-L/14): such an index is pruned on the packed 6-bit shadow alone -- 3 dim / 4 + 8 = 584 bytes a row in
+ * tiles of 16 rows, (n + 15) / 16 * 16 * 584 bytes in all, against 3072 (f32) or 1536 (f16) bytes of a row -- from 2^20
+ * rows on, f32 or f16, single queries and pruned batches alike (the smallest size measured; the pruned call is ahead of
+ * the full scan at every one); it never gets an int8 shadow, and below that count, or when the shadow is refused for
+ * memory, every call is the full-precision one.  [0] and [5] then report that shadow.
  * out6: [0] shadow 0 none / 1 current / 2 stale / 3 refused (memory), [1] 1 = the next top-k with a query is pruned,
  * [2] survivors of the last pruned call (-1 = it fell back), [3] pruned calls, [4] fallbacks, [5] shadow bytes. */
 ssw_status ssw_index_prune_stats(ssw_index *idx, int64_t *out6);

@@ -75,10 +75,14 @@ ssw_status ssw_debug_prune_survivors(ssw_index *idx, float threshold, int32_t k,
  * "6-bit shadow"; tests/test_prune6_gpu.py, tests/test_prune6_f16_gpu.py).  None of these changes what the hooks above
  * do: they keep building and driving the int8 shadow, and ssw_tune_prune's min_rows keeps governing the int8 path only.
  * ssw_tune_prune6: enable 0 = every index takes the int8 path at every size (A/B in one process); min_rows >= 0 = the
- *   smallest index, of either dtype, whose single queries scan the 6-bit shadow, < 0 = the product's two constants again.
+ *   smallest index, of either dtype, whose single queries scan the 6-bit shadow, < 0 = the product's constants again.
+ *   Dim 768: the 6-bit hooks (ssw_debug_prune6_shadow / _bounds / _survivors / _scan_shape, the _mq ones below and
+ *   ssw_debug_prune_maxima with six != 0) admit a dim-768 index, which has the 6-bit shadow alone and is governed by
+ *   ssw_tune_prune6 and ssw_tune_prune6_batch only, never by ssw_tune_prune's min_rows; the int8 hooks above keep
+ *   refusing it ("the index is not pruned", "dim=768 has no shadow scan").
  * ssw_tune_prune6_scan: the launch shape of k_q6_bounds: four-wave blocks per CU (1 .. 8) and 16-row tiles a wave
- *   requests at a time (1, 2 or 4, as far as tiles x dim <= 1024); any other value = the product's (1 block; 2 / 1 / 1
- *   tiles at dim 256 / 512 / 1024).  ssw_debug_prune6_scan_shape: the blocks and tiles of the next launch.
+ *   requests at a time (1, 2 or 4, as far as tiles x dim <= 1024); any other value = the product's (1 block; 2 / 1 / 1 / 1
+ *   tiles at dim 256 / 512 / 768 / 1024).  ssw_debug_prune6_scan_shape: the blocks and tiles of the next launch.
  * ssw_debug_prune6_shadow: builds the 6-bit shadow if it is missing or stale (the product's ensure_shadow6 ->
  *   k_q6_build or k_q6_build_h16) and copies out, for the rows [first_row, first_row + n_rows): the codes [n_rows, dim]
  *   unpacked to int8 in natural element order (by the placement function the kernels use), s6_r and a6_r.  NULL
@@ -136,8 +140,8 @@ ssw_status ssw_debug_prune_survivors_mq(ssw_index *idx, int32_t nq, int32_t slot
  *   product's two constants again (25 M rows).  ssw_tune_prune6's own min_rows does not move the batch: with it
  *   alone a pruned batch on a small index keeps building and scanning the int8 shadow.
  * ssw_tune_prune6_scan_mq: the launch shape of k_q6_bounds_mq: four-wave blocks per CU (1 .. 8) and 16-row tiles a wave
- *   requests at a time (1, 2 or 4, as far as tiles x dim <= 1024); any other value = the product's (1 block; 4 / 2 / 1
- *   tiles at dim 256 / 512 / 1024).  ssw_debug_prune6_scan_mq_shape: the blocks and tiles of the next launch.
+ *   requests at a time (1, 2 or 4, as far as tiles x dim <= 1024); any other value = the product's (1 block; 4 / 2 / 1 / 1
+ *   tiles at dim 256 / 512 / 768 / 1024).  ssw_debug_prune6_scan_mq_shape: the blocks and tiles of the next launch.
  * ssw_debug_prune6_bounds_mq: k_q6_query_mq + k_q6_bounds_mq through the product's launch functions for nq <= 16 host
  *   queries (non-finite ones allowed: they are flagged) on the index's own buffers; builds the 6-bit shadow if it is
  *   missing or stale.  out_I [nq, n] = the exact integer sums of 4 c with 256 d_hi + d_lo (int64), out_lb [nq, n],

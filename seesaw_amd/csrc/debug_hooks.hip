@@ -537,7 +537,7 @@ ssw_status ssw_debug_rescore_survivors(ssw_index *idx, const float *q_host, int3
                                        int32_t *out_waves) {
     SSW_REQUIRE(idx && q_host && counts && fail_bits && out_slabs_host && out_waves, "NULL argument");
     SSW_REQUIRE(nq >= 1 && nq <= Q8_MQ_WIDTH, "nq=%d outside [1, %d]", nq, Q8_MQ_WIDTH);
-    SSW_REQUIRE(q8_dim_supported(idx->dim) && idx->n >= 1, "dim=%d or n=%lld has no pruned chunk", idx->dim, (long long)idx->n);
+    SSW_REQUIRE(q6_dim_supported(idx->dim) && idx->n >= 1, "dim=%d or n=%lld has no pruned chunk", idx->dim, (long long)idx->n);
     const int64_t cap = batch_dev_surv_cap();
     int64_t listed = 0;
     for (int j = 0; j < nq; ++j) {
@@ -731,7 +731,7 @@ ssw_status ssw_debug_prune6_survivors(ssw_index *idx, float threshold, int32_t k
 // ---- the pruned batch's chunk on the 6-bit shadow (prune.hip, k_q6_query_mq / k_q6_bounds_mq; tests/test_prune6_batch_gpu.py)
 ssw_status ssw_debug_prune6_scan_mq_shape(ssw_index *idx, int32_t *out_blocks, int32_t *out_tiles) {
     SSW_REQUIRE(idx != nullptr && out_blocks != nullptr && out_tiles != nullptr, "NULL argument");
-    SSW_REQUIRE(q8_dim_supported(idx->dim), "dim=%d has no shadow scan", idx->dim);
+    SSW_REQUIRE(q6_dim_supported(idx->dim), "dim=%d has no shadow scan", idx->dim);
     int blocks = 0, tiles = 0;
     q6_bounds_mq_shape(idx->dim, idx->device, idx->n, &blocks, &tiles);
     *out_blocks = blocks;
@@ -821,7 +821,7 @@ ssw_status ssw_debug_prune6_survivors_mq(ssw_index *idx, int32_t nq, int32_t slo
 
 ssw_status ssw_debug_prune6_scan_shape(ssw_index *idx, int32_t *out_blocks, int32_t *out_tiles) {
     SSW_REQUIRE(idx != nullptr && out_blocks != nullptr && out_tiles != nullptr, "NULL argument");
-    SSW_REQUIRE(q8_dim_supported(idx->dim), "dim=%d has no shadow scan", idx->dim);
+    SSW_REQUIRE(q6_dim_supported(idx->dim), "dim=%d has no shadow scan", idx->dim);
     int blocks = 0, tiles = 0;
     q6_bounds_shape(idx->dim, idx->device, idx->n, &blocks, &tiles);
     *out_blocks = blocks;

@@ -43,6 +43,23 @@ constexpr int64_t PRUNE6_MIN_ROWS_F16 = (int64_t)1 << 24;
 // admit it; at 2^23 f32 rows it is ahead by 0.008 with spreads of 0.003, which a size above that fails does not carry.
 constexpr int64_t PRUNE6_BATCH_MIN_ROWS = 25000000;
 constexpr int64_t PRUNE6_BATCH_MIN_ROWS_F16 = 25000000;
+// A dim-768 index has the 6-bit shadow alone (584 bytes a row against 3072 of f32 and 1536 of f16 rows; the int8 scan's
+// lanes-per-row map has no C = 3, prune.hip), so the alternative of a pruned call there is the full-precision path: the
+// full scan for a single query, the plain batch for a batch.  Constants of their own, under the rule above and governed
+// by ssw_tune_prune6 / ssw_tune_prune6_batch alone -- never by ssw_tune_prune's min_rows, which is the int8 shadow's.
+// Single call, tools/perf_prune.py --dim 768 (profiles/prune6_dim768_sweep.txt; full scan and 6-bit call alternating in
+// one process, 2 + 20 rounds, 2^20 .. 2^25, 12.5 M, 25 M and 50 M rows): the 6-bit call is ahead by more than both
+// spreads at EVERY measured size, so each constant is the smallest size of the sweep, 2^20 rows.  f32: 0.208 against
+// 0.524 ms a call at 2^20 rows (spreads 0.026 together), 4.903 against 22.655 at 50 M.  f16: 0.203 against 0.320 at 2^20
+// (spreads 0.023), 4.896 against 12.871 at 50 M.  Nothing below 2^20 rows was measured.
+constexpr int64_t PRUNE6_MIN_ROWS_768 = (int64_t)1 << 20;
+constexpr int64_t PRUNE6_MIN_ROWS_768_F16 = (int64_t)1 << 20;
+// Batch, tools/perf_prune_batch.py --dim 768 --nq 16 4 (profiles/prune6_dim768_batch.txt; the plain batch there is a loop
+// of full scans, scan_batch_max_width is 1 off dim 512): the same at every size, at nq = 16 and nq = 4.  f32, 2^20 rows:
+// 0.115 against 0.562 ms a query at nq = 16 (spreads 0.008), 0.144 against 0.651 at nq = 4 (0.019); 50 M rows: 0.651
+// against 24.837 and 1.615 against 28.876.  f16, 2^20 rows: 0.110 against 0.336 (0.005) and 0.138 against 0.385 (0.008).
+constexpr int64_t PRUNE6_BATCH_MIN_ROWS_768 = (int64_t)1 << 20;
+constexpr int64_t PRUNE6_BATCH_MIN_ROWS_768_F16 = (int64_t)1 << 20;
 constexpr int64_t PRUNE_RESERVE = (int64_t)4 << 30;   // free device memory the shadow must leave
 static SSW_TUNABLE bool g_prune = true;               // ssw_tune_prune
 static SSW_TUNABLE bool g_prune6 = true;              // ssw_tune_prune6
@@ -62,22 +79,28 @@ static int64_t prune_min_rows(const ssw_index *idx) {
     return idx->dtype == SSW_DTYPE_F16 ? PRUNE_MIN_ROWS_F16 : PRUNE_MIN_ROWS;
 }
 
-static bool prune_eligible_from(const ssw_index *idx, int64_t min_rows) {
+// dim_ok: the dims of the shadow in question (q8_dim_supported: the int8 one, q6_dim_supported: the 6-bit one)
+static bool prune_eligible_from(const ssw_index *idx, int64_t min_rows, bool (*dim_ok)(int32_t)) {
     return g_prune && !prune_forced_off() && idx->owns_X && !idx->rows_escaped && idx->n >= min_rows &&
-           idx->n_images > 0 && q8_dim_supported(idx->dim);
+           idx->n_images > 0 && dim_ok(idx->dim);
 }
-bool ssw::prune_eligible(const ssw_index *idx) { return prune_eligible_from(idx, prune_min_rows(idx)); }
+bool ssw::prune_eligible(const ssw_index *idx) { return prune_eligible_from(idx, prune_min_rows(idx), q8_dim_supported); }
 bool ssw::prune_batch_eligible(const ssw_index *idx) {
-    return prune_eligible_from(idx, g_prune_min_rows >= 0 ? g_prune_min_rows : PRUNE_BATCH_MIN_ROWS);
+    return prune_eligible_from(idx, g_prune_min_rows >= 0 ? g_prune_min_rows : PRUNE_BATCH_MIN_ROWS, q8_dim_supported);
 }
 static int64_t prune6_min_rows(const ssw_index *idx) {
     if (g_prune6_min_rows >= 0) return g_prune6_min_rows;
+    if (idx->dim == 768) return idx->dtype == SSW_DTYPE_F16 ? PRUNE6_MIN_ROWS_768_F16 : PRUNE6_MIN_ROWS_768;
     return idx->dtype == SSW_DTYPE_F16 ? PRUNE6_MIN_ROWS_F16 : PRUNE6_MIN_ROWS;
 }
-bool ssw::prune6_eligible(const ssw_index *idx) { return g_prune6 && prune_eligible_from(idx, prune6_min_rows(idx)); }
-// (ssw_tune_prune6's min_rows is the single call's constant alone: lowering it leaves the batch on the int8 shadow)
+bool ssw::prune6_eligible(const ssw_index *idx) {
+    return g_prune6 && prune_eligible_from(idx, prune6_min_rows(idx), q6_dim_supported);
+}
+// (ssw_tune_prune6's min_rows is the single call's constant alone: lowering it leaves the batch on the int8 shadow, or at
+// dim 768, which has none, on the plain batch)
 static bool prune6_batch_eligible(const ssw_index *idx) {
     int64_t batch_rows = idx->dtype == SSW_DTYPE_F16 ? PRUNE6_BATCH_MIN_ROWS_F16 : PRUNE6_BATCH_MIN_ROWS;
+    if (idx->dim == 768) batch_rows = idx->dtype == SSW_DTYPE_F16 ? PRUNE6_BATCH_MIN_ROWS_768_F16 : PRUNE6_BATCH_MIN_ROWS_768;
     if (g_prune6_batch_min_rows >= 0) batch_rows = g_prune6_batch_min_rows;
     return prune6_eligible(idx) && idx->n >= batch_rows;
 }
@@ -248,7 +271,8 @@ ssw_status ssw::prune6_survivors(ssw_index *idx, int32_t k, int64_t cap, hipEven
 // certificate (fewer than k keys or an overflow in the threshold selection, more survivors than SURV_CAP, a query
 // that cannot be bounded) runs the full scan instead.  The profiling events bracket the whole replacement.
 // The shadow is the 6-bit one where prune6_eligible says so (only that one is built then), else the int8 one; a 6-bit
-// shadow refused for memory leaves the int8 path, if an int8 shadow exists or fits.
+// shadow refused for memory leaves the int8 path, if an int8 shadow exists or fits.  A dim-768 index is never
+// prune_eligible (no int8 shadow at that dim): it reaches ensure_shadow6 or the full scan.
 // *out_candidates: the pruned path succeeded on an index without an image map, and the candidates of the final top-k
 // are in the selection's workspace (launch_scatter_candidates): the caller's selection, the next thing on the stream,
 // runs over them alone (do_select, from_candidates).  Nothing of it is kept in the handle.
@@ -341,7 +365,8 @@ ssw_status ssw::ensure_prune_batch(ssw_index *idx, int w, int *out_w) {
 // The shadow that bounds the chunks of a pruned batch, made ready: the single call's rule (scan_for_topk).  The 6-bit one
 // where prune6_eligible says so and the index has the batch's rows for it (only that one is built then); else, and
 // where the 6-bit shadow is refused for memory, the int8 one under prune_batch_eligible.  prune_batch.six remembers
-// the choice for the steps below.  *ready false: the batch is the plain one.
+// the choice for the steps below.  *ready false: the batch is the plain one -- at dim 768, which has no int8 fallback,
+// whenever the index is below the batch's 6-bit constant or the 6-bit shadow was refused.
 ssw_status ssw::prune_batch_shadow(ssw_index *idx, bool *ready) {
     *ready = false;
     bool six = false;
@@ -432,8 +457,9 @@ ssw_status ssw_index_prune_stats(ssw_index *idx, int64_t *out6) {
     SSW_REQUIRE(idx != nullptr && out6 != nullptr, "NULL argument");
     const PruneState &p = idx->prune;
     // the state of the shadow single queries use: the 6-bit one where it applies and was not refused
-    const bool six = prune6_eligible(idx) && !p.refused6;
-    if (six) out6[0] = p.q6 ? (p.stale6 ? 2 : 1) : 0;
+    // (a dim-768 index has no other: there a refusal is the 6-bit shadow's)
+    const bool six = prune6_eligible(idx) && (!p.refused6 || !q8_dim_supported(idx->dim));
+    if (six) out6[0] = p.q6 ? (p.stale6 ? 2 : 1) : (p.refused6 ? 3 : 0);
     else out6[0] = p.q8 ? (p.stale ? 2 : 1) : (p.refused ? 3 : 0);
     out6[1] = prune_eligible(idx) || six ? 1 : 0;
     out6[2] = p.last;

@@ -116,15 +116,18 @@ __device__ __forceinline__ void q8_build_row(const float *__restrict__ X, int64_
 }
 
 // binary16 rows in the f16 index's lane-interleaved layout (ssw_common.h): lane l reads its 8C contiguous bytes at
-// l * 8C of the row (one 16-byte load at dim 512, two at dim 1024, 8 bytes at dim 256) and widens them, exactly; chunk c
+// l * 8C of the row (one 16-byte load at dim 512, two at dim 1024, 8 bytes at dim 256, three 8-byte loads at dim 768,
+// which only the 6-bit builder instantiates) and widens them, exactly; chunk c
 // of them, x[4c .. 4c + 3], is the natural elements 256c + 4l .. + 3.
 template <int C>
 __device__ __forceinline__ void load_row_h16(const uint16_t *__restrict__ X, int64_t r, int lane, float (&x)[4 * C]) {
     constexpr int dim = 256 * C;
     const u32x2 *src = reinterpret_cast<const u32x2 *>(X + r * dim) + lane * C;
     u32x2 w[C];
-    if constexpr (C == 1) {
-        w[0] = src[0];
+    if constexpr (C % 2 != 0) {
+        // a lane's 8C bytes are only 8-byte aligned (24 at dim 768): one 8-byte load a chunk, as H16Rows::load (scan.hip)
+#pragma unroll
+        for (int c = 0; c < C; ++c) w[c] = src[c];
     } else {
 #pragma unroll
         for (int c = 0; c < C; c += 2) {
@@ -840,11 +843,14 @@ SSW_TUNABLE int g_q6_tiles = 0;  // 0: q6_default_tiles(C)
 // 16-row tiles of one request of a wave: 6 KiB at dim 256 and 512, 12 KiB (one tile) at dim 1024.  From the traced sweep
 // of blocks a CU x tiles at 10^8 rows (docs/EXPERIMENTS.md, "The 6-bit scan's launch shape"): at dim 256 two tiles take
 // 3.63 ms a launch where the four of the 12-KiB rule took 4.13, at dim 512 one tile 6.17 where two took 6.25; a second
-// or fourth block a CU is level with one at dim 256 and behind it at dim 512 and 1024.
+// or fourth block a CU is level with one at dim 256 and behind it at dim 512 and 1024.  Dim 768 (C = 3, 9 KiB a tile) takes
+// one tile, the only count q6_tiles admits there; its launch shape has not been swept.
 constexpr int q6_default_tiles(int C) { return C == 1 ? 2 : 1; }
 
 // 31 sqrt(dim), rounded up
-__host__ __device__ constexpr double q6_code_norm(int dim) { return dim == 256 ? 496.0 : dim == 512 ? 701.4499270 : 992.0; }
+__host__ __device__ constexpr double q6_code_norm(int dim) {
+    return dim == 256 ? 496.0 : dim == 512 ? 701.4499270 : dim == 768 ? 859.0972006 : 992.0;
+}
 
 // The tile assembly both builders share: cl is the wave's LDS line with the codes of row r in natural element order,
 // one byte each; lane l assembles words l, l + 64, .. of the row's 12 dim / 64 and stores each at its place in the tile.
@@ -1082,7 +1088,7 @@ constexpr int Q6MQ_BLOCKS_PER_CU = 1;
 SSW_TUNABLE int g_q6mq_blocks_per_cu = Q6MQ_BLOCKS_PER_CU;
 SSW_TUNABLE int g_q6mq_tiles = 0;  // 0: q6mq_default_tiles(C)
 // 12 KiB a wave at every dim, the request k_q6_bounds had when this was set; one tile at dim 512 is behind two at nq = 16
-// (profiles/q6_shape_batch_thresholds.txt)
+// (profiles/q6_shape_batch_thresholds.txt); dim 768 (C = 3): one tile, 9 KiB
 constexpr int q6mq_default_tiles(int C) { return 4 / C; }
 
 // lb of every row for every query of the chunk: query j's into slab j (j + 1 < w: side + j * stride, the last: own).
@@ -1211,6 +1217,9 @@ __global__ __launch_bounds__(256) void k_q6_bounds_mq(const u32x4 *__restrict__ 
 }  // namespace
 
 bool q8_dim_supported(int32_t dim) { return dim == 256 || dim == 512 || dim == 1024; }
+// the packed 6-bit shadow also takes dim 768 (C = 3): its matrix-core scans work in k-steps of 64 elements, where
+// k_q8_bounds' lanes-per-row map needs 4 % C == 0
+bool q6_dim_supported(int32_t dim) { return q8_dim_supported(dim) || dim == 768; }
 
 ssw_status launch_q8_build(const void *X, int32_t dtype, int64_t n, int32_t dim, int8_t *codes, float *scale,
                            float *err, hipStream_t stream) {
@@ -1419,7 +1428,7 @@ size_t q6_plane_bytes(int32_t dim) { return (size_t)(dim / 64) * 64 * 16; }
 ssw_status launch_q6_build(const void *X, int32_t dtype, int64_t n, int32_t dim, unsigned char *codes, float *scale,
                            float *err, hipStream_t stream) {
     if (n <= 0) return SSW_OK;
-    if (!q8_dim_supported(dim) || (dtype != SSW_DTYPE_F32 && dtype != SSW_DTYPE_F16)) {
+    if (!q6_dim_supported(dim) || (dtype != SSW_DTYPE_F32 && dtype != SSW_DTYPE_F16)) {
         set_error("q6_build: dim=%d, dtype=%d unsupported", dim, dtype);
         return SSW_ERR_UNSUPPORTED;
     }
@@ -1436,6 +1445,7 @@ ssw_status launch_q6_build(const void *X, int32_t dtype, int64_t n, int32_t dim,
         switch (dim) {
             case 256: hipLaunchKernelGGL(k_q6_build_h16<1>, grid, block, 0, stream, Xh, n, codes, scale, err); break;
             case 512: hipLaunchKernelGGL(k_q6_build_h16<2>, grid, block, 0, stream, Xh, n, codes, scale, err); break;
+            case 768: hipLaunchKernelGGL(k_q6_build_h16<3>, grid, block, 0, stream, Xh, n, codes, scale, err); break;
             default: hipLaunchKernelGGL(k_q6_build_h16<4>, grid, block, 0, stream, Xh, n, codes, scale, err); break;
         }
     } else {
@@ -1443,6 +1453,7 @@ ssw_status launch_q6_build(const void *X, int32_t dtype, int64_t n, int32_t dim,
         switch (dim) {
             case 256: hipLaunchKernelGGL(k_q6_build<1>, grid, block, 0, stream, Xf, n, codes, scale, err); break;
             case 512: hipLaunchKernelGGL(k_q6_build<2>, grid, block, 0, stream, Xf, n, codes, scale, err); break;
+            case 768: hipLaunchKernelGGL(k_q6_build<3>, grid, block, 0, stream, Xf, n, codes, scale, err); break;
             default: hipLaunchKernelGGL(k_q6_build<4>, grid, block, 0, stream, Xf, n, codes, scale, err); break;
         }
     }
@@ -1478,7 +1489,7 @@ ssw_status launch_q6_bounds(const unsigned char *codes, const float *scale, cons
                             const unsigned *st, float *scores, int64_t n, int32_t dim, int64_t *dbg_I, int device,
                             hipStream_t stream) {
     if (n <= 0) return SSW_OK;
-    if (!q8_dim_supported(dim)) {
+    if (!q6_dim_supported(dim)) {
         set_error("q6_bounds: dim=%d unsupported", dim);
         return SSW_ERR_UNSUPPORTED;
     }
@@ -1497,6 +1508,8 @@ ssw_status launch_q6_bounds(const unsigned char *codes, const float *scale, cons
         if (T == 1) { SSW_Q6_T(1, 1); } else if (T == 2) { SSW_Q6_T(1, 2); } else { SSW_Q6_T(1, 4); }
     } else if (C == 2) {
         if (T == 1) { SSW_Q6_T(2, 1); } else { SSW_Q6_T(2, 2); }
+    } else if (C == 3) {
+        SSW_Q6_T(3, 1);
     } else {
         SSW_Q6_T(4, 1);
     }
@@ -1506,6 +1519,7 @@ ssw_status launch_q6_bounds(const unsigned char *codes, const float *scale, cons
     switch (C) {
         case 1: SSW_Q6(1, q6_default_tiles(1), false); break;
         case 2: SSW_Q6(2, q6_default_tiles(2), false); break;
+        case 3: SSW_Q6(3, q6_default_tiles(3), false); break;
         default: SSW_Q6(4, q6_default_tiles(4), false); break;
     }
 #endif
@@ -1550,7 +1564,7 @@ ssw_status launch_q6_bounds_mq(const unsigned char *codes, const float *scale, c
                                const unsigned *mq, int32_t w, float *side, int64_t stride, float *own, int64_t n,
                                int32_t dim, int64_t *dbg_I, int device, hipStream_t stream) {
     if (n <= 0) return SSW_OK;
-    if (!q8_dim_supported(dim) || w < 1 || w > MQ_WIDTH) {
+    if (!q6_dim_supported(dim) || w < 1 || w > MQ_WIDTH) {
         set_error("q6_bounds_mq: dim=%d, w=%d unsupported", dim, w);
         return SSW_ERR_UNSUPPORTED;
     }
@@ -1569,6 +1583,8 @@ ssw_status launch_q6_bounds_mq(const unsigned char *codes, const float *scale, c
         if (T == 1) { SSW_Q6MQ_T(1, 1); } else if (T == 2) { SSW_Q6MQ_T(1, 2); } else { SSW_Q6MQ_T(1, 4); }
     } else if (C == 2) {
         if (T == 1) { SSW_Q6MQ_T(2, 1); } else { SSW_Q6MQ_T(2, 2); }
+    } else if (C == 3) {
+        SSW_Q6MQ_T(3, 1);
     } else {
         SSW_Q6MQ_T(4, 1);
     }
@@ -1578,6 +1594,7 @@ ssw_status launch_q6_bounds_mq(const unsigned char *codes, const float *scale, c
     switch (C) {
         case 1: SSW_Q6MQ(1, q6mq_default_tiles(1), false); break;
         case 2: SSW_Q6MQ(2, q6mq_default_tiles(2), false); break;
+        case 3: SSW_Q6MQ(3, q6mq_default_tiles(3), false); break;
         default: SSW_Q6MQ(4, q6mq_default_tiles(4), false); break;
     }
 #endif

@@ -145,6 +145,7 @@ ssw_status launch_t(const void *Xv, const float *qb, const unsigned *mq, const i
     switch (dim) {
         case 256: SSW_RESCORE_DEV(1); break;
         case 512: SSW_RESCORE_DEV(2); break;
+        case 768: SSW_RESCORE_DEV(3); break;
         case 1024: SSW_RESCORE_DEV(4); break;
         default:
             set_error("rescore_survivors: dim=%d unsupported", dim);

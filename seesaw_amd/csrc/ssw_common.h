@@ -170,6 +170,8 @@ ssw_status launch_scan_batch(const void *X, int32_t dtype, const float *qb_dev, 
 // their widened values) and the certified pre-scan of the exact top-k (see prune.hip).
 // query state words: [0] survivors, [1] Q = ||q|| rounded up (f32 bits), [2] 1 = the query cannot be bounded
 bool q8_dim_supported(int32_t dim);
+// the dims of the packed 6-bit shadow's builders and scans: those of the int8 shadow and 768, which has no int8 shadow
+bool q6_dim_supported(int32_t dim);
 ssw_status launch_q8_build(const void *X, int32_t dtype, int64_t n, int32_t dim, int8_t *codes, float *scale,
                            float *err, hipStream_t stream);
 ssw_status launch_q8_query(const float *q_dev, int32_t dim, float *q_keep, unsigned *state, hipStream_t stream);

@@ -161,8 +161,8 @@ class DeviceIndex:
         """Top-k distinct images (positions), their max score and the row attaining it.
         q=None reuses the scores of the previous scan.  With a query, a large index (f32 or float16 rows alike) scans a
         quantised shadow of the rows first and scores only the rows that can still reach the k-th image exactly: the
-        int8 shadow from 2^22 rows, the packed 6-bit shadow from 2^23 f32 or 2^24 float16 rows.  The results are the
-        full scan's bits."""
+        int8 shadow from 2^22 rows, the packed 6-bit shadow from 2^23 f32 or 2^24 float16 rows; a dim-768 index the
+        6-bit shadow alone, from 2^20 rows.  The results are the full scan's bits."""
         k = int(k)
         qa = None if q is None else self._query(q)
         ex = None
@@ -218,8 +218,9 @@ class DeviceIndex:
         nq iterables of image positions, each of which may be None.  The handle is left as after the last query's topk.
         `prune=True` (ssw_index_topk_batch_pruned): on an index whose single `topk` is pruned, one pass over a shadow
         -- from 25 M rows the packed 6-bit one single queries scan there, below that (or where that one is refused for
-        memory) the int8 one -- bounds a chunk of up to 16 queries and only each query's survivors are scored exactly
-        -- the same results; `prune_stats` counts every query.  Any other index takes the plain batch."""
+        memory) the int8 one; at dim 768 the 6-bit one from 2^20 rows and no other -- bounds a chunk of up to 16 queries
+        and only each query's survivors are scored exactly -- the same results; `prune_stats` counts every query.  Any
+        other index takes the plain batch."""
         k = int(k)
         Q = self._queries(Q)
         nq = Q.shape[0]
@@ -438,6 +439,9 @@ class DeviceIndex:
         `fallbacks`: pruned calls and how many of them fell back; `shadow_bytes`: device memory the shadows hold
         (dim + 8 bytes a row for the int8 one, 3 dim / 4 + 8 for the 6-bit one; from 25 M rows a pruned batch scans
         the 6-bit one single queries scan and builds no other, below that it builds and scans the int8 one).
+        A dim-768 index (CLIP ViT-L/14) has the 6-bit shadow alone, 584 bytes a row: `shadow` and `shadow_bytes`
+        ((n + 15) // 16 * 16 * 584) are that shadow's, and single queries and pruned batches scan it from 2^20 rows
+        on, f32 or float16; below that every call is the full-precision one.
         `completions=True` adds the two words of ssw_index_prune_completions (the six above stay what they were for
         callers that compare the whole dict): `completions`: full scans that completed a partial score buffer or slab
         for a reader; `rescored_rows`: rows the second-stage readers (`rescore_avg`, `gather_scores`, `topk_batch_avg`)

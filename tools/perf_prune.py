@@ -4,6 +4,7 @@
     python tools/perf_prune.py [--rows 12.5e6 25e6 50e6 100e6] [--k 100] [--reps 10] [--dtype float32|float16]
                                [--warmup-pairs 2]
     python tools/perf_prune.py --three-way [--rows ...] [--k 100] [--dtype float32|float16]
+    python tools/perf_prune.py --dim 768 [--rows ...] [--k 100] [--dtype float32|float16]
 
 For each index size: a synthetic N x 512 index of f32 or binary16 rows, one first top-k (builds the int8 shadow, timed
 on its own), `warmup-pairs` untimed pairs, then `reps` pairs of top-k calls with the pruning switched off and on in turn
@@ -19,7 +20,12 @@ different query; per size one JSON line with the median and the spread (max - mi
 6-bit survivors, whether all three returned the same bytes, and under "shadows" which shadow each form's first call
 built, from the growth of prune_stats' shadow_bytes ("none", "int8" or "6-bit"; a form that built another shadow than
 its name says ends the run).  Where the two shadows do not fit beside the rows together, the int8 rounds and the 6-bit
-rounds run one after the other on two indexes of the same rows, each alternating with the full scan."""
+rounds run one after the other on two indexes of the same rows, each alternating with the full scan.
+
+--dim D (default 512): the width of the index.  --dim 768 (how PRUNE6_MIN_ROWS_768 and PRUNE6_MIN_ROWS_768_F16 are
+chosen): that dim has the 6-bit shadow alone, so the run is always the rounds of --three-way with two forms, full scan /
+packed 6-bit shadow, and the JSON line has no int8 column; it carries "dim".  Every other dim prints what it printed
+before the option existed."""
 import argparse
 import ctypes
 import json
@@ -40,9 +46,11 @@ def main():
     ap.add_argument("--dtype", choices=("float32", "float16"), default="float32")
     ap.add_argument("--warmup-pairs", type=int, default=2)
     ap.add_argument("--three-way", action="store_true")
+    ap.add_argument("--dim", type=int, choices=(256, 512, 768, 1024), default=512)
     args = ap.parse_args()
     from seesaw_amd import _lib
     from seesaw_amd.device_index import DeviceIndex
+    dim = args.dim
 
     def stats(idx):
         out = np.zeros(6, dtype=np.int64)
@@ -50,7 +58,7 @@ def main():
         return out
 
     def query(i):
-        q = np.random.default_rng(10_000 + i).standard_normal(512).astype(np.float32)
+        q = np.random.default_rng(10_000 + i).standard_normal(dim).astype(np.float32)
         return (q / np.linalg.norm(q)).astype(np.float32)
 
     def set_form(form):
@@ -58,12 +66,13 @@ def main():
         _lib.call("ssw_tune_prune6", 1 if form == "q6" else 0, 1)
 
     dtype = np.dtype(args.dtype)
+    six_only = dim == 768  # no int8 shadow at this dim
     built_by = {"full": "none", "int8": "int8", "q6": "6-bit"}
 
     def rounds(n, forms, wall, surv, shadows):
         """warm-up and timed rounds over `forms` on a fresh index; -> all forms returned the same bytes"""
-        idx = DeviceIndex.synthetic(n, 512, seed=2024, dtype=dtype)
-        grows = {0: "none", n * (512 + 8): "int8", (n + 15) // 16 * 16 * (512 * 3 // 4 + 8): "6-bit"}
+        idx = DeviceIndex.synthetic(n, dim, seed=2024, dtype=dtype)
+        grows = {0: "none", n * (dim + 8): "int8", (n + 15) // 16 * 16 * (dim * 3 // 4 + 8): "6-bit"}
         same = True
         try:
             for form in forms:  # builds the shadows, untimed
@@ -94,9 +103,11 @@ def main():
     def three_way(n):
         import torch
         total = torch.cuda.mem_get_info(0)[1]
-        together = n * (512 * dtype.itemsize + 520 + 392 + 8) + (5 << 30) < total
+        together = six_only or n * (dim * dtype.itemsize + (dim + 8) + (dim * 3 // 4 + 8) + 8) + (5 << 30) < total
         wall, surv, shadows = {}, [], {}
-        if together:
+        if six_only:
+            same, fallbacks = rounds(n, ["full", "q6"], wall, surv, shadows)
+        elif together:
             same, fallbacks = rounds(n, ["full", "int8", "q6"], wall, surv, shadows)
         else:
             wall_b = {}
@@ -105,6 +116,8 @@ def main():
             wall["q6"], wall["full_beside_q6"] = wall_b["q6"], wall_b["full"]
             same, fallbacks = same_a and same_b, fa + fb
         res = {"rows": n, "dtype": args.dtype, "k": args.k, "one_index": bool(together), "shadows": shadows}
+        if dim != 512:
+            res = {"dim": dim, **res}
         for form, v in wall.items():
             res[form + "_ms_median"] = round(float(np.median(v)), 3)
             res[form + "_ms_spread"] = round(float(np.max(v) - np.min(v)), 3)
@@ -113,7 +126,7 @@ def main():
         print(json.dumps(res), flush=True)
 
     with _lib.debug_hooks():
-        if args.three_way:
+        if args.three_way or six_only:
             try:
                 for rows in args.rows:
                     three_way(int(rows))
@@ -124,7 +137,7 @@ def main():
         _lib.call("ssw_tune_prune6", 0, -1)
         for rows in args.rows:
             n = int(rows)
-            idx = DeviceIndex.synthetic(n, 512, seed=2024, dtype=np.dtype(args.dtype))
+            idx = DeviceIndex.synthetic(n, dim, seed=2024, dtype=np.dtype(args.dtype))
             try:
                 _lib.call("ssw_tune_prune", 1, 1, -1)
                 t0 = time.perf_counter()
@@ -132,6 +145,8 @@ def main():
                 first_ms = 1e3 * (time.perf_counter() - t0)
                 res = {"rows": n, "dtype": args.dtype, "k": args.k, "first_call_ms_with_shadow_build": round(first_ms, 2),
                        "shadow_bytes": int(stats(idx)[5])}
+                if dim != 512:
+                    res = {"dim": dim, **res}
                 wall = {0: [], 1: []}
                 ev = {0: [], 1: []}
                 surv, same = [], True

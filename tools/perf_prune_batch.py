@@ -5,7 +5,7 @@ against pruned single calls, in one process (csrc/prune.hip k_q8_bounds_mq / k_q
 
     python tools/perf_prune_batch.py [--rows 4194304 ... 100e6] [--nq 2 4 8 16 64] [--k 100] [--reps 7]
                                      [--dtype float32|float16] [--warmup-rounds 2] [--shadow int8|six|both]
-                                     [--tiles T] [--blocks B] [--tiles6 T] [--blocks6 B]
+                                     [--tiles T] [--blocks B] [--tiles6 T] [--blocks6 B] [--dim 512]
 
 For each index size: a synthetic N x 512 index, one first pruned call per form (builds its shadow), then per nq
 `warmup-rounds` untimed rounds and `reps` timed rounds; a round runs the variants in turn on the same handle with fresh
@@ -15,7 +15,12 @@ last form's shadow).  The lab build lowers the thresholds to 1 row so that every
 ssw_tune_prune6, ssw_tune_prune6_batch).  Prints one JSON line per (size, nq): host wall ms PER QUERY of each variant (median, min, max and
 the max - min spread), the HIP-event ms per chunk of each pruned batch's replacement of the scan, survivors per query,
 fallbacks, whether all variants returned the same bits, and the shadow bytes resident; a form whose shadow was refused
-for memory ran the plain batch and is reported as `"resident": false`."""
+for memory ran the plain batch and is reported as `"resident": false`.
+
+--dim D (default 512): the width of the index.  --dim 768 (how PRUNE6_BATCH_MIN_ROWS_768 and its _F16 are chosen): that
+dim has the 6-bit shadow alone, so --shadow is taken as `six` whatever was given, the comparison is the 6-bit batch
+against the plain batch (at that dim a loop of full scans) and the pruned singles, there is no int8 column, and the
+JSON line carries "dim".  Every other dim prints what it printed before the option existed."""
 import argparse
 import ctypes
 import json
@@ -41,7 +46,11 @@ def main():
     ap.add_argument("--blocks", type=int, default=-1)
     ap.add_argument("--tiles6", type=int, default=-1)
     ap.add_argument("--blocks6", type=int, default=-1)
+    ap.add_argument("--dim", type=int, choices=(256, 512, 768, 1024), default=512)
     args = ap.parse_args()
+    dim = args.dim
+    if dim == 768:
+        args.shadow = "six"
     from seesaw_amd import _lib
     from seesaw_amd.device_index import DeviceIndex
     forms = {"int8": ["int8"], "six": ["six"], "both": ["int8", "six"]}[args.shadow]
@@ -55,7 +64,7 @@ def main():
         _lib.call("ssw_tune_prune6", 1 if form == "six" else 0, 1)
 
     def queries(seed, nq):
-        Q = np.random.default_rng(10_000 + seed).standard_normal((nq, 512)).astype(np.float32)
+        Q = np.random.default_rng(10_000 + seed).standard_normal((nq, dim)).astype(np.float32)
         return np.ascontiguousarray(Q / np.linalg.norm(Q, axis=1, keepdims=True), dtype=np.float32)
 
     def same(a, b):
@@ -71,7 +80,7 @@ def main():
         _lib.call("ssw_tune_prune6_scan_mq", args.blocks6, args.tiles6)
         for rows in args.rows:
             n = int(rows)
-            idx = DeviceIndex.synthetic(n, 512, seed=2024, dtype=np.dtype(args.dtype))
+            idx = DeviceIndex.synthetic(n, dim, seed=2024, dtype=np.dtype(args.dtype))
             try:
                 _lib.call("ssw_tune_prune", 1, 1, -1)
                 _lib.call("ssw_tune_prune6_batch", 1)
@@ -120,6 +129,8 @@ def main():
                     st = stats(idx)
                     res = {"rows": n, "dtype": args.dtype, "k": args.k, "nq": nq, "shadow": args.shadow,
                            "resident": resident, "shadow_bytes": int(st[5])}
+                    if dim != 512:
+                        res = {"dim": dim, **res}
                     for name, v in wall.items():
                         res[name + "_ms_per_query"] = summary(v)
                     for form in forms:
