@@ -83,7 +83,7 @@ ssw_status ssw_debug_prune_survivors(ssw_index *idx, float threshold, int32_t k,
  * ssw_tune_prune6_scan: the launch shape of k_q6_bounds: four-wave blocks per CU (1 .. 8) and 16-row tiles a wave
  *   requests at a time (1, 2 or 4, as far as tiles x dim <= 1024); any other value = the product's (1 block; 2 / 1 / 1 / 1
  *   tiles at dim 256 / 512 / 768 / 1024).  ssw_debug_prune6_scan_shape: the blocks and tiles of the next launch.
- * ssw_debug_prune6_shadow: builds the 6-bit shadow if it is missing or stale (the product's ensure_shadow6 ->
+ * ssw_debug_prune6_shadow: builds the 6-bit shadow if it is missing or stale (the product's ensure_shadow ->
  *   k_q6_build or k_q6_build_h16) and copies out, for the rows [first_row, first_row + n_rows): the codes [n_rows, dim]
  *   unpacked to int8 in natural element order (by the placement function the kernels use), s6_r and a6_r.  NULL
  *   outputs are skipped.

@@ -326,14 +326,18 @@ extern "C" ssw_status ssw_debug_attn_out_stamps(uint64_t *out, int32_t n_words) 
 // ---------------------------------------------------------------------------------------
 using namespace ssw;
 
-static ssw_status require_shadow(ssw_index *idx, const char *who) {
+static ssw_status require_shadow(ssw_index *idx, const char *who, ShadowKind kind = SHADOW_Q8) {
     bool ready = false;
-    SSW_TRY(ensure_shadow(idx, &ready));
+    SSW_TRY(ensure_shadow(idx, kind, &ready));
     if (!ready) {
         set_error("%s: the shadow was refused for memory", who);
         return SSW_ERR_NOMEM;
     }
     return SSW_OK;
+}
+
+static bool shadow_current(const ssw_index *idx, ShadowKind kind) {
+    return idx->prune.sh[kind].codes && !idx->prune.sh[kind].stale;
 }
 
 // what the threshold selection leaves behind, written by hand: k keys (only the k-th is read) and [count, overflow]
@@ -360,13 +364,13 @@ ssw_status ssw_debug_prune_shadow(ssw_index *idx, int64_t first_row, int64_t n_r
     DeviceGuard guard(idx->device);
     SSW_TRY(require_shadow(idx, "prune_shadow"));
     if (n_rows > 0 && out_codes)
-        SSW_HIP_TRY(hipMemcpyAsync(out_codes, idx->prune.q8 + first_row * idx->dim, (size_t)n_rows * idx->dim,
+        SSW_HIP_TRY(hipMemcpyAsync(out_codes, idx->prune.sh[SHADOW_Q8].codes + first_row * idx->dim, (size_t)n_rows * idx->dim,
                                    hipMemcpyDeviceToHost, idx->stream));
     if (n_rows > 0 && out_scale)
-        SSW_HIP_TRY(hipMemcpyAsync(out_scale, idx->prune.q8_scale + first_row, (size_t)n_rows * sizeof(float),
+        SSW_HIP_TRY(hipMemcpyAsync(out_scale, idx->prune.sh[SHADOW_Q8].scale + first_row, (size_t)n_rows * sizeof(float),
                                    hipMemcpyDeviceToHost, idx->stream));
     if (n_rows > 0 && out_err)
-        SSW_HIP_TRY(hipMemcpyAsync(out_err, idx->prune.q8_err + first_row, (size_t)n_rows * sizeof(float),
+        SSW_HIP_TRY(hipMemcpyAsync(out_err, idx->prune.sh[SHADOW_Q8].err + first_row, (size_t)n_rows * sizeof(float),
                                    hipMemcpyDeviceToHost, idx->stream));
     SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
     return SSW_OK;
@@ -381,7 +385,7 @@ ssw_status ssw_debug_prune_bounds(ssw_index *idx, const float *q_host, float *ou
     DeviceGuard guard(idx->device);
     SSW_TRY(require_shadow(idx, "prune_bounds"));
     SSW_TRY(idx->q_stage.push(idx->q_dev, q_host, (size_t)idx->dim * sizeof(float), idx->stream));
-    SSW_TRY(prune_bounds(idx, idx->q_dev));  // as in scan_for_topk: every reader completes the buffer with the scan of q_last
+    SSW_TRY(prune_bounds(idx, SHADOW_Q8, idx->q_dev, nullptr));  // as in scan_for_topk: every reader completes the buffer with the scan of q_last
     unsigned state[4] = {0u, 0u, 0u, 0u};
     SSW_HIP_TRY(hipMemcpyAsync(state, idx->prune.state, sizeof(state), hipMemcpyDeviceToHost, idx->stream));
     SSW_HIP_TRY(hipMemcpyAsync(out_lb, idx->scores, (size_t)idx->n * sizeof(float), hipMemcpyDeviceToHost, idx->stream));
@@ -397,13 +401,13 @@ ssw_status ssw_debug_prune_survivors(ssw_index *idx, float threshold, int32_t k,
     SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
     SSW_REQUIRE(cap >= 0 && cap <= SURV_CAP, "cap=%lld outside [0, %lld]", (long long)cap, (long long)SURV_CAP);
     SSW_REQUIRE(cap == 0 || out_rows != nullptr, "out_rows is NULL");
-    SSW_REQUIRE(idx->scores_partial && idx->prune.q8 && !idx->prune.stale, "no bounds in the buffer: ssw_debug_prune_bounds first");
+    SSW_REQUIRE(idx->scores_partial && shadow_current(idx, SHADOW_Q8), "no bounds in the buffer: ssw_debug_prune_bounds first");
     DeviceGuard guard(idx->device);
     SSW_TRY(ensure_ws(idx));
     SSW_HIP_TRY(hipMemsetAsync(idx->prune.state, 0, sizeof(unsigned), idx->stream));  // the counter k_q8_query resets
     SSW_TRY(stand_in_threshold(idx, threshold, k, sel_count, sel_overflow));
     int32_t m = -1;
-    SSW_TRY(prune_survivors(idx, k, cap, nullptr, &m));
+    SSW_TRY(prune_survivors(idx, SHADOW_Q8, k, cap, nullptr, &m));
     unsigned collected = 0u;
     SSW_HIP_TRY(hipMemcpyAsync(&collected, idx->prune.state, sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
     if (m > 0)
@@ -419,7 +423,7 @@ ssw_status ssw_debug_prune_scan_mq_shape(ssw_index *idx, int32_t *out_blocks, in
     SSW_REQUIRE(idx != nullptr && out_blocks != nullptr && out_tiles != nullptr, "NULL argument");
     SSW_REQUIRE(q8_dim_supported(idx->dim), "dim=%d has no shadow scan", idx->dim);
     int blocks = 0, tiles = 0;
-    q8_bounds_mq_shape(idx->dim, idx->device, idx->n, &blocks, &tiles);
+    scan_shape(SCAN_Q8_MQ, idx->dim, idx->device, idx->n, &blocks, &tiles);
     *out_blocks = blocks;
     *out_tiles = tiles;
     return SSW_OK;
@@ -435,7 +439,7 @@ static ssw_status debug_chunk_ready(ssw_index *idx, int32_t nq, bool six = false
         SSW_REQUIRE(prune_batch_eligible(idx), "the index is not pruned (ssw_tune_prune, dim, borrowed or escaped rows)");
         SSW_TRY(require_shadow(idx, "prune_bounds_mq"));
     }
-    idx->prune_batch.six = six;  // what prune_batch_shadow would have left
+    idx->prune_batch.kind = six ? SHADOW_Q6 : SHADOW_Q8;  // what prune_batch_shadow would have left
     SSW_TRY(ensure_ws(idx));
     int w = 0;
     SSW_TRY(batch_buffers(idx, nq, true, &w));
@@ -504,7 +508,7 @@ ssw_status ssw_debug_prune_survivors_mq(ssw_index *idx, int32_t nq, int32_t slot
     SSW_REQUIRE(cap >= 0 && cap <= SURV_CAP, "cap=%lld outside [0, %lld]", (long long)cap, (long long)SURV_CAP);
     SSW_REQUIRE(cap == 0 || out_rows != nullptr, "out_rows is NULL");
     PruneBatchState &pb = idx->prune_batch;
-    SSW_REQUIRE(idx->scores_partial && !pb.six && idx->prune.q8 && !idx->prune.stale && pb.slots >= nq &&
+    SSW_REQUIRE(idx->scores_partial && pb.kind == SHADOW_Q8 && shadow_current(idx, SHADOW_Q8) && pb.slots >= nq &&
                     idx->batch.side_slabs >= nq - 1,
                 "no bounds of such a chunk in the buffers: ssw_debug_prune_bounds_mq first");
     DeviceGuard guard(idx->device);
@@ -591,13 +595,7 @@ ssw_status ssw_debug_rescore_survivors(ssw_index *idx, const float *q_host, int3
 // ---- the packed 6-bit shadow of single queries (prune.hip, "6-bit shadow"; tests/test_prune6_gpu.py) ----------------
 static ssw_status require_shadow6(ssw_index *idx, const char *who) {
     SSW_REQUIRE(prune6_eligible(idx), "the index takes no 6-bit shadow (ssw_tune_prune6, rows, dim, borrowed or escaped rows)");
-    bool ready = false;
-    SSW_TRY(ensure_shadow6(idx, &ready));
-    if (!ready) {
-        set_error("%s: the shadow was refused for memory", who);
-        return SSW_ERR_NOMEM;
-    }
-    return SSW_OK;
+    return require_shadow(idx, who, SHADOW_Q6);
 }
 
 ssw_status ssw_debug_prune6_shadow(ssw_index *idx, int64_t first_row, int64_t n_rows, int8_t *out_codes, float *out_scale,
@@ -608,19 +606,19 @@ ssw_status ssw_debug_prune6_shadow(ssw_index *idx, int64_t first_row, int64_t n_
     DeviceGuard guard(idx->device);
     SSW_TRY(require_shadow6(idx, "prune6_shadow"));
     if (n_rows == 0) return SSW_OK;
-    const PruneState &p = idx->prune;
+    const Shadow &s = idx->prune.sh[SHADOW_Q6];
     const int dim = idx->dim;
     const size_t tile_bytes = (size_t)16 * dim * 3 / 4;
     const int64_t tile0 = first_row >> 4, tile1 = (first_row + n_rows - 1) >> 4;
     std::vector<unsigned char> packed(out_codes ? (size_t)(tile1 - tile0 + 1) * tile_bytes : 0);
     if (out_codes)
-        SSW_HIP_TRY(hipMemcpyAsync(packed.data(), p.q6 + (size_t)tile0 * tile_bytes, packed.size(), hipMemcpyDeviceToHost,
+        SSW_HIP_TRY(hipMemcpyAsync(packed.data(), s.codes + (size_t)tile0 * tile_bytes, packed.size(), hipMemcpyDeviceToHost,
                                    idx->stream));
     if (out_scale)
-        SSW_HIP_TRY(hipMemcpyAsync(out_scale, p.q6_scale + first_row, (size_t)n_rows * sizeof(float), hipMemcpyDeviceToHost,
+        SSW_HIP_TRY(hipMemcpyAsync(out_scale, s.scale + first_row, (size_t)n_rows * sizeof(float), hipMemcpyDeviceToHost,
                                    idx->stream));
     if (out_err)
-        SSW_HIP_TRY(hipMemcpyAsync(out_err, p.q6_err + first_row, (size_t)n_rows * sizeof(float), hipMemcpyDeviceToHost,
+        SSW_HIP_TRY(hipMemcpyAsync(out_err, s.err + first_row, (size_t)n_rows * sizeof(float), hipMemcpyDeviceToHost,
                                    idx->stream));
     SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
     if (!out_codes) return SSW_OK;
@@ -658,7 +656,7 @@ ssw_status ssw_debug_prune6_bounds(ssw_index *idx, const float *q_host, int64_t 
     std::vector<int8_t> planes(q6_plane_bytes(idx->dim));
     auto run = [&]() -> ssw_status {
         SSW_TRY(idx->q_stage.push(idx->q_dev, q_host, dim * sizeof(float), idx->stream));
-        SSW_TRY(prune6_bounds(idx, idx->q_dev, dbg));  // as in scan_for_topk: readers complete the buffer with q_last
+        SSW_TRY(prune_bounds(idx, SHADOW_Q6, idx->q_dev, dbg));  // as in scan_for_topk: readers complete the buffer with q_last
         if (out_I) SSW_HIP_TRY(hipMemcpyAsync(out_I, dbg, (size_t)idx->n * sizeof(int64_t), hipMemcpyDeviceToHost, idx->stream));
         if (out_lb)
             SSW_HIP_TRY(hipMemcpyAsync(out_lb, idx->scores, (size_t)idx->n * sizeof(float), hipMemcpyDeviceToHost, idx->stream));
@@ -696,7 +694,7 @@ ssw_status ssw_debug_prune_maxima(ssw_index *idx, int32_t six, float *out2) {
         SSW_REQUIRE(prune_eligible(idx), "the index is not pruned (ssw_tune_prune, dim, borrowed or escaped rows)");
         SSW_TRY(require_shadow(idx, "prune_maxima"));
     }
-    SSW_HIP_TRY(hipMemcpyAsync(out2, six ? idx->prune.q6_max : idx->prune.q8_max, SHADOW_MAX_WORDS * sizeof(float),
+    SSW_HIP_TRY(hipMemcpyAsync(out2, idx->prune.sh[six ? SHADOW_Q6 : SHADOW_Q8].max, SHADOW_MAX_WORDS * sizeof(float),
                                hipMemcpyDeviceToHost, idx->stream));
     SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
     return SSW_OK;
@@ -708,7 +706,7 @@ ssw_status ssw_debug_prune6_survivors(ssw_index *idx, float threshold, int32_t k
     SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
     SSW_REQUIRE(cap >= 0 && cap <= SURV_CAP, "cap=%lld outside [0, %lld]", (long long)cap, (long long)SURV_CAP);
     SSW_REQUIRE(cap == 0 || out_rows != nullptr, "out_rows is NULL");
-    SSW_REQUIRE(idx->scores_partial && idx->prune.q6 && !idx->prune.stale6, "no bounds in the buffer: ssw_debug_prune6_bounds first");
+    SSW_REQUIRE(idx->scores_partial && shadow_current(idx, SHADOW_Q6), "no bounds in the buffer: ssw_debug_prune6_bounds first");
     DeviceGuard guard(idx->device);
     SSW_TRY(ensure_ws(idx));
     unsigned *st = idx->prune.state6;
@@ -716,7 +714,7 @@ ssw_status ssw_debug_prune6_survivors(ssw_index *idx, float threshold, int32_t k
     SSW_HIP_TRY(hipMemsetAsync(st + 5, 0, sizeof(unsigned), idx->stream));  // word k_q6_query resets
     SSW_TRY(stand_in_threshold(idx, threshold, k, sel_count, sel_overflow));
     int32_t m = -1;
-    SSW_TRY(prune6_survivors(idx, k, cap, nullptr, &m));
+    SSW_TRY(prune_survivors(idx, SHADOW_Q6, k, cap, nullptr, &m));
     unsigned collected = 0u;
     SSW_HIP_TRY(hipMemcpyAsync(&collected, st, sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
     if (m > 0)
@@ -733,7 +731,7 @@ ssw_status ssw_debug_prune6_scan_mq_shape(ssw_index *idx, int32_t *out_blocks, i
     SSW_REQUIRE(idx != nullptr && out_blocks != nullptr && out_tiles != nullptr, "NULL argument");
     SSW_REQUIRE(q6_dim_supported(idx->dim), "dim=%d has no shadow scan", idx->dim);
     int blocks = 0, tiles = 0;
-    q6_bounds_mq_shape(idx->dim, idx->device, idx->n, &blocks, &tiles);
+    scan_shape(SCAN_Q6_MQ, idx->dim, idx->device, idx->n, &blocks, &tiles);
     *out_blocks = blocks;
     *out_tiles = tiles;
     return SSW_OK;
@@ -796,7 +794,7 @@ ssw_status ssw_debug_prune6_survivors_mq(ssw_index *idx, int32_t nq, int32_t slo
     SSW_REQUIRE(cap >= 0 && cap <= SURV_CAP, "cap=%lld outside [0, %lld]", (long long)cap, (long long)SURV_CAP);
     SSW_REQUIRE(cap == 0 || out_rows != nullptr, "out_rows is NULL");
     PruneBatchState &pb = idx->prune_batch;
-    SSW_REQUIRE(idx->scores_partial && pb.six && idx->prune.q6 && !idx->prune.stale6 && pb.slots >= nq &&
+    SSW_REQUIRE(idx->scores_partial && pb.kind == SHADOW_Q6 && shadow_current(idx, SHADOW_Q6) && pb.slots >= nq &&
                     idx->batch.side_slabs >= nq - 1,
                 "no bounds of such a chunk in the buffers: ssw_debug_prune6_bounds_mq first");
     DeviceGuard guard(idx->device);
@@ -823,7 +821,7 @@ ssw_status ssw_debug_prune6_scan_shape(ssw_index *idx, int32_t *out_blocks, int3
     SSW_REQUIRE(idx != nullptr && out_blocks != nullptr && out_tiles != nullptr, "NULL argument");
     SSW_REQUIRE(q6_dim_supported(idx->dim), "dim=%d has no shadow scan", idx->dim);
     int blocks = 0, tiles = 0;
-    q6_bounds_shape(idx->dim, idx->device, idx->n, &blocks, &tiles);
+    scan_shape(SCAN_Q6, idx->dim, idx->device, idx->n, &blocks, &tiles);
     *out_blocks = blocks;
     *out_tiles = tiles;
     return SSW_OK;

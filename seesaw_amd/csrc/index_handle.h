@@ -8,14 +8,27 @@ constexpr int64_t SURV_CAP = (int64_t)1 << 18;      // survivors rescored at mos
 constexpr int64_t SMALL_EXCL_CAP = 8192;            // the small form (index_topk.hip): excluded ids in its pinned block
 constexpr int64_t SMALL_ROWS = 65536;               // and the small scan kernel's range (scan.hip)
 
-// certified int8 pre-scan of the top-k (prune.hip): the shadow of the rows, built lazily by the first top-k with a query
-// after the rows last changed, and the buffers of one pruned call
+// a shadow of the rows for the certified pre-scan of the top-k (prune.hip): the int8 one, and the packed 6-bit one that
+// single queries scan instead on an index of enough rows (index_prune.hip, MIN_ROWS).  Each is built lazily by the first
+// top-k with a query that wants it after the rows last changed
+enum ShadowKind { SHADOW_Q8, SHADOW_Q6 };
+struct Shadow {
+    unsigned char *codes = nullptr;               // int8: [n, dim] codes; 6-bit: q6_code_bytes(n, dim), tiles of 16 rows
+    float *scale = nullptr, *err = nullptr;       // s_r, a_r: [n]; 6-bit: [q6_padded_rows(n)]
+    unsigned *max = nullptr;                      // [SHADOW_MAX_WORDS] the largest finite a_r, s_r (launch_shadow_max)
+    bool stale = true;                            // the rows changed since the shadow was built
+    bool refused = false;                         // too little free memory at the last attempt (until the rows change)
+    void free() {
+        for (void *p : {(void *)codes, (void *)scale, (void *)err}) (void)hipFree(p);
+        codes = nullptr;
+        scale = err = nullptr;
+        stale = true;
+    }
+};
+
+// the shadows and the buffers of one pruned call
 struct PruneState {
-    int8_t *q8 = nullptr;                          // [n, dim] codes
-    float *q8_scale = nullptr, *q8_err = nullptr;  // [n] s_r, a_r
-    unsigned *q8_max = nullptr;                    // [SHADOW_MAX_WORDS] the largest finite a_r, s_r (launch_shadow_max)
-    bool stale = true;                             // the rows changed since the shadow was built
-    bool refused = false;                          // too little free memory at the last attempt (until the rows change)
+    Shadow sh[2];                                  // by ShadowKind
     unsigned *state = nullptr;                     // [4] device words (ssw_common.h, launch_q8_query)
     int64_t *surv_rows = nullptr;                  // [SURV_CAP]
     float *surv_scores = nullptr;                  // [SURV_CAP]
@@ -26,29 +39,18 @@ struct PruneState {
     int64_t last = 0, queries = 0, fallbacks = 0;
     // ssw_index_prune_completions: full scans that completed a partial buffer or slab, rows rescored on demand instead
     int64_t completions = 0, rescored_rows = 0;
-    // the packed 6-bit shadow of the rows (prune.hip, "6-bit shadow"): what single queries scan on an index of at least
-    // PRUNE6_MIN_ROWS f32 or PRUNE6_MIN_ROWS_F16 f16 rows, instead of the int8 one; built lazily like it, with its own
-    // stale / refused
-    unsigned char *q6 = nullptr;                   // q6_code_bytes(n, dim): tiles of 16 rows
-    float *q6_scale = nullptr, *q6_err = nullptr;  // [q6_padded_rows(n)] s6_r, a6_r
-    unsigned *q6_max = nullptr;                    // [SHADOW_MAX_WORDS] the same of the 6-bit shadow
-    bool stale6 = true, refused6 = false;
+    // a single query on the 6-bit shadow
     unsigned *state6 = nullptr;                    // [Q8_MQ_WORDS] the query's words, a slot's of the chunk
     int8_t *planes6 = nullptr;                     // q6_plane_bytes(dim): the query's operand
     void free_shadow() {
-        for (void *p : {(void *)q8, (void *)q8_scale, (void *)q8_err, (void *)q6, (void *)q6_scale, (void *)q6_err})
-            (void)hipFree(p);
-        q8 = nullptr;
-        q8_scale = q8_err = nullptr;
-        stale = true;
-        q6 = nullptr;
-        q6_scale = q6_err = nullptr;
-        stale6 = true;
+        for (Shadow &s : sh) s.free();
     }
     void release() {
-        free_shadow();
-        for (void *p : {(void *)state, (void *)surv_rows, (void *)surv_scores, (void *)q_last, (void *)state6, (void *)planes6,
-                        (void *)q8_max, (void *)q6_max})
+        for (Shadow &s : sh) {
+            s.free();
+            (void)hipFree(s.max);
+        }
+        for (void *p : {(void *)state, (void *)surv_rows, (void *)surv_scores, (void *)q_last, (void *)state6, (void *)planes6})
             (void)hipFree(p);
         if (host) (void)hipHostFree(host);
         if (ev) (void)hipEventDestroy(ev);
@@ -65,7 +67,7 @@ struct PruneBatchState {
     int slots = 0;
     // the shadow that bounds the chunk (prune_batch_shadow): the packed 6-bit one, else the int8 one.  The state words,
     // the planes and the slabs hold one chunk at a time, so only one shadow ever serves them
-    bool six = false;
+    ShadowKind kind = SHADOW_Q8;
     int32_t *host = nullptr;       // pinned, mapped: [seq, survivors or -1 of each slot]
     unsigned seq = 0;
     // the last chunk of ssw_index_topk_batch_dev_pruned, for ssw_index_prune_batch_dev_read: its width (0: the words
@@ -217,13 +219,11 @@ ssw_status wait_host_seq(hipStream_t stream, const unsigned *flag, unsigned seq)
 bool prune_eligible(const ssw_index *idx);
 bool prune_batch_eligible(const ssw_index *idx);
 bool prune6_eligible(const ssw_index *idx);
-ssw_status ensure_shadow(ssw_index *idx, bool *ready);
-ssw_status ensure_shadow6(ssw_index *idx, bool *ready);
-ssw_status prune6_bounds(ssw_index *idx, const float *q_dev, int64_t *dbg_I);
+ssw_status ensure_shadow(ssw_index *idx, ShadowKind kind, bool *ready);
 ssw_status rows_changing(ssw_index *idx);
-ssw_status prune_bounds(ssw_index *idx, const float *q_dev);
-ssw_status prune_survivors(ssw_index *idx, int32_t k, int64_t cap, hipEvent_t sleep_ev_or_null, int32_t *out_m);
-ssw_status prune6_survivors(ssw_index *idx, int32_t k, int64_t cap, hipEvent_t sleep_ev_or_null, int32_t *out_m);
+ssw_status prune_bounds(ssw_index *idx, ShadowKind kind, const float *q_dev, int64_t *dbg_I);
+ssw_status prune_survivors(ssw_index *idx, ShadowKind kind, int32_t k, int64_t cap, hipEvent_t sleep_ev_or_null,
+                           int32_t *out_m);
 ssw_status scan_for_topk(ssw_index *idx, const float *q_dev, int32_t k, bool *out_candidates);
 ssw_status ensure_prune_batch(ssw_index *idx, int w, int *out_w);
 ssw_status prune_batch_shadow(ssw_index *idx, bool *ready);

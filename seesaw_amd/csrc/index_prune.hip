@@ -6,60 +6,69 @@
 using namespace ssw;
 
 // ---- the certified pre-scan (prune.hip) -------------------------------------------------------
-// Top-k with a query on an index of at least PRUNE_MIN_ROWS f32 rows, or PRUNE_MIN_ROWS_F16 f16 rows, scans the int8
-// shadow instead of the rows and rescores the survivors exactly; the score buffer then holds exact scores for the
-// survivors and lower bounds elsewhere (scores_partial) until a consumer that reads all of it materialises the full scan
-// of the kept query; the second-stage readers make exact the rows they read (rescore_rows) and leave it partial.
-constexpr int64_t PRUNE_MIN_ROWS = (int64_t)1 << 22;  // above the feedback loop's 1.56 M rows, below a rank's 12.5 M
-// f16 rows: the full scan reads half the bytes, yet the pruned call is ahead from the smallest size of the measured
-// sweep on (2^22 rows: 0.49 against 0.72 ms a call, profiles/prune_f16_sweep.txt), so the value is the f32 one.  Its
-// own constant: the two row formats are measured separately and need not stay equal.
-constexpr int64_t PRUNE_MIN_ROWS_F16 = (int64_t)1 << 22;
-// the pruned batch (ssw_index_topk_batch_pruned) against the plain batch at 16 queries: its own constant, chosen by its
-// own sweep ("Pruned batch")
-constexpr int64_t PRUNE_BATCH_MIN_ROWS = PRUNE_MIN_ROWS;
-// Single queries on an f32 index of at least this many rows scan the packed 6-bit shadow (392 instead of 520 bytes a
-// row at dim 512, more survivors) and never need the int8 one.  The value follows from tools/perf_prune.py --three-way
-// ("6-bit shadow"): the smallest size from which the 6-bit call beats the int8 call, there and at
-// every larger size, by more than both spreads.
-// Measured with the survivor pass that reads the bounds alone (profiles/prune_tail_sweep.txt): 2^23 (0.719 against 0.816
-// ms a call, spreads 0.043 together; at 2^22 the gap of 0.032 ms is inside the spreads' 0.042).  The ~22 000 survivors
-// of the 6-bit bounds no longer cost 0.3 ms, which was what kept the int8 call ahead below 2^25 rows.
-constexpr int64_t PRUNE6_MIN_ROWS = (int64_t)1 << 23;
-// f16 rows (the shadow is built from the widened rows by k_q6_build_h16, the same bytes a row): its own constant under
-// the same rule, from the same tool with --dtype float16 (the same file): 2^24 rows is the smallest measured size from
-// which the 6-bit call is ahead by more than both spreads, there and above (1.239 against 1.409 ms a call, spreads
-// 0.155; 6.75 against 8.10 at 100 M).  At 2^23 and 12.5 M rows the 6-bit call is ahead by 0.06 and 0.12 ms, but both
-// forms' spreads were 0.2-0.3 ms in that run, so the rule does not admit them.
-constexpr int64_t PRUNE6_MIN_ROWS_F16 = (int64_t)1 << 24;
-// The pruned batch on an index of at least this many rows bounds its chunks on the 6-bit shadow instead of the int8 one
-// ("Pruned batch on the 6-bit shadow"); below it, and never below the single call's constants
-// (prune6_eligible), the int8 shadow as before.  Constants of their own under the rule above, from
-// tools/perf_prune_batch.py --shadow both (profiles/prune6_batch_ab.txt; the plain, the int8 and the 6-bit batch
-// alternating in one process): 25 M rows is the smallest measured size from which the 6-bit batch is ahead of the
-// int8 batch by more than both spreads, there and above, at nq = 16 and nq = 4 (f32: 0.330 against 0.366 ms a query at
-// nq = 16, spreads 0.015 together; 0.864 against 1.030 at 100 M).  At 2^24 rows and nq = 16 it is ahead by 0.018 (f32)
-// and 0.017 ms (f16) with spreads of 0.021 and 0.019 together -- the two ranges do not overlap, but the rule does not
-// admit it; at 2^23 f32 rows it is ahead by 0.008 with spreads of 0.003, which a size above that fails does not carry.
-constexpr int64_t PRUNE6_BATCH_MIN_ROWS = 25000000;
-constexpr int64_t PRUNE6_BATCH_MIN_ROWS_F16 = 25000000;
-// A dim-768 index has the 6-bit shadow alone (584 bytes a row against 3072 of f32 and 1536 of f16 rows; the int8 scan's
-// lanes-per-row map has no C = 3, prune.hip), so the alternative of a pruned call there is the full-precision path: the
-// full scan for a single query, the plain batch for a batch.  Constants of their own, under the rule above and governed
-// by ssw_tune_prune6 / ssw_tune_prune6_batch alone -- never by ssw_tune_prune's min_rows, which is the int8 shadow's.
-// Single call, tools/perf_prune.py --dim 768 (profiles/prune6_dim768_sweep.txt; full scan and 6-bit call alternating in
-// one process, 2 + 20 rounds, 2^20 .. 2^25, 12.5 M, 25 M and 50 M rows): the 6-bit call is ahead by more than both
-// spreads at EVERY measured size, so each constant is the smallest size of the sweep, 2^20 rows.  f32: 0.208 against
-// 0.524 ms a call at 2^20 rows (spreads 0.026 together), 4.903 against 22.655 at 50 M.  f16: 0.203 against 0.320 at 2^20
-// (spreads 0.023), 4.896 against 12.871 at 50 M.  Nothing below 2^20 rows was measured.
-constexpr int64_t PRUNE6_MIN_ROWS_768 = (int64_t)1 << 20;
-constexpr int64_t PRUNE6_MIN_ROWS_768_F16 = (int64_t)1 << 20;
-// Batch, tools/perf_prune_batch.py --dim 768 --nq 16 4 (profiles/prune6_dim768_batch.txt; the plain batch there is a loop
-// of full scans, scan_batch_max_width is 1 off dim 512): the same at every size, at nq = 16 and nq = 4.  f32, 2^20 rows:
-// 0.115 against 0.562 ms a query at nq = 16 (spreads 0.008), 0.144 against 0.651 at nq = 4 (0.019); 50 M rows: 0.651
-// against 24.837 and 1.615 against 28.876.  f16, 2^20 rows: 0.110 against 0.336 (0.005) and 0.138 against 0.385 (0.008).
-constexpr int64_t PRUNE6_BATCH_MIN_ROWS_768 = (int64_t)1 << 20;
-constexpr int64_t PRUNE6_BATCH_MIN_ROWS_768_F16 = (int64_t)1 << 20;
+// Top-k with a query on an index of at least MIN_ROWS rows scans a shadow instead of the rows and rescores the
+// survivors exactly; the score buffer then holds exact scores for the survivors and lower bounds elsewhere
+// (scores_partial) until a consumer that reads all of it materialises the full scan of the kept query; the second-stage
+// readers make exact the rows they read (rescore_rows) and leave it partial.
+constexpr int64_t NO_SHADOW = INT64_MAX;  // the int8 shadow at dim 768: no such shadow (q8_dim_supported)
+// The rows from which a call is pruned on a shadow: [ShadowKind][single call, batch][dim 256 / 512 / 1024, dim 768]
+// [f32, f16 rows].  The two row formats are measured separately and need not stay equal.
+constexpr int64_t MIN_ROWS[2][2][2][2] = {
+    // ---- SHADOW_Q8 ----
+    {{// single call
+      {(int64_t)1 << 22,  // above the feedback loop's 1.56 M rows, below a rank's 12.5 M
+       // f16 rows: the full scan reads half the bytes, yet the pruned call is ahead from the smallest size of the
+       // measured sweep on (2^22 rows: 0.49 against 0.72 ms a call, profiles/prune_f16_sweep.txt), so the value is the
+       // f32 one
+       (int64_t)1 << 22},
+      {NO_SHADOW, NO_SHADOW}},
+     {// the pruned batch (ssw_index_topk_batch_pruned) against the plain batch at 16 queries: its own entries, chosen by
+      // its own sweep ("Pruned batch"), the single call's value for either row format
+      {(int64_t)1 << 22, (int64_t)1 << 22},
+      {NO_SHADOW, NO_SHADOW}}},
+    // ---- SHADOW_Q6 ----
+    {{// Single queries on an f32 index of at least this many rows scan the packed 6-bit shadow (392 instead of 520 bytes
+      // a row at dim 512, more survivors) and never need the int8 one.  The value follows from tools/perf_prune.py
+      // --three-way ("6-bit shadow"): the smallest size from which the 6-bit call beats the int8
+      // call, there and at every larger size, by more than both spreads.
+      // Measured with the survivor pass that reads the bounds alone (profiles/prune_tail_sweep.txt): 2^23 (0.719 against
+      // 0.816 ms a call, spreads 0.043 together; at 2^22 the gap of 0.032 ms is inside the spreads' 0.042).  The ~22 000
+      // survivors of the 6-bit bounds no longer cost 0.3 ms, which was what kept the int8 call ahead below 2^25 rows.
+      {(int64_t)1 << 23,
+       // f16 rows (the shadow is built from the widened rows by k_q6_build_h16, the same bytes a row): its own entry
+       // under the same rule, from the same tool with --dtype float16 (the same file): 2^24 rows is the smallest
+       // measured size from which the 6-bit call is ahead by more than both spreads, there and above (1.239 against
+       // 1.409 ms a call, spreads 0.155; 6.75 against 8.10 at 100 M).  At 2^23 and 12.5 M rows the 6-bit call is ahead by
+       // 0.06 and 0.12 ms, but both forms' spreads were 0.2-0.3 ms in that run, so the rule does not admit them.
+       (int64_t)1 << 24},
+      // A dim-768 index has the 6-bit shadow alone (584 bytes a row against 3072 of f32 and 1536 of f16 rows; the int8
+      // scan's lanes-per-row map has no C = 3, prune.hip), so the alternative of a pruned call there is the
+      // full-precision path: the full scan for a single query, the plain batch for a batch.  Entries of their own,
+      // under the rule above and governed by ssw_tune_prune6 / ssw_tune_prune6_batch alone -- never by ssw_tune_prune's
+      // min_rows, which is the int8 shadow's.
+      // Single call, tools/perf_prune.py --dim 768 (profiles/prune6_dim768_sweep.txt; full scan and 6-bit call
+      // alternating in one process, 2 + 20 rounds, 2^20 .. 2^25, 12.5 M, 25 M and 50 M rows): the 6-bit call is ahead by
+      // more than both spreads at EVERY measured size, so each entry is the smallest size of the sweep, 2^20 rows.
+      // f32: 0.208 against 0.524 ms a call at 2^20 rows (spreads 0.026 together), 4.903 against 22.655 at 50 M.  f16:
+      // 0.203 against 0.320 at 2^20 (spreads 0.023), 4.896 against 12.871 at 50 M.  Nothing below 2^20 rows was measured.
+      {(int64_t)1 << 20, (int64_t)1 << 20}},
+     {// The pruned batch on an index of at least this many rows bounds its chunks on the 6-bit shadow instead of the
+      // int8 one ("Pruned batch on the 6-bit shadow"); below it, and never below the single call's
+      // entries (prune6_eligible), the int8 shadow as before.  Entries of their own under the rule above, from
+      // tools/perf_prune_batch.py --shadow both (profiles/prune6_batch_ab.txt; the plain, the int8 and the 6-bit batch
+      // alternating in one process): 25 M rows is the smallest measured size from which the 6-bit batch is ahead of the
+      // int8 batch by more than both spreads, there and above, at nq = 16 and nq = 4 (f32: 0.330 against 0.366 ms a
+      // query at nq = 16, spreads 0.015 together; 0.864 against 1.030 at 100 M).  At 2^24 rows and nq = 16 it is ahead
+      // by 0.018 (f32) and 0.017 ms (f16) with spreads of 0.021 and 0.019 together -- the two ranges do not overlap, but
+      // the rule does not admit it; at 2^23 f32 rows it is ahead by 0.008 with spreads of 0.003, which a size above
+      // that fails does not carry.
+      {25000000, 25000000},
+      // Dim 768, tools/perf_prune_batch.py --dim 768 --nq 16 4 (profiles/prune6_dim768_batch.txt; the plain batch there
+      // is a loop of full scans, scan_batch_max_width is 1 off dim 512): ahead at every size, at nq = 16 and nq = 4.
+      // f32, 2^20 rows: 0.115 against 0.562 ms a query at nq = 16 (spreads 0.008), 0.144 against 0.651 at nq = 4
+      // (0.019); 50 M rows: 0.651 against 24.837 and 1.615 against 28.876.  f16, 2^20 rows: 0.110 against 0.336 (0.005)
+      // and 0.138 against 0.385 (0.008).
+      {(int64_t)1 << 20, (int64_t)1 << 20}}}};
 constexpr int64_t PRUNE_RESERVE = (int64_t)4 << 30;   // free device memory the shadow must leave
 static SSW_TUNABLE bool g_prune = true;               // ssw_tune_prune
 static SSW_TUNABLE bool g_prune6 = true;              // ssw_tune_prune6
@@ -69,49 +78,49 @@ static SSW_TUNABLE int64_t g_prune6_batch_min_rows = -1;  // ssw_tune_prune6_bat
 static SSW_TUNABLE int64_t g_prune_reserve = PRUNE_RESERVE;
 static SSW_TUNABLE int64_t g_surv_cap_dev = SURV_CAP;  // ssw_tune_surv_cap: of ssw_index_topk_batch_dev_pruned only
 
+// what differs between the shadows where they are made: the dims, the sizes of the codes and of the two constant
+// arrays, the builder, and whether a single query on it needs its own state words and operand (state6, planes6)
+struct ShadowDesc {
+    bool (*dim_ok)(int32_t dim);
+    size_t (*code_bytes)(int64_t n, int32_t dim);
+    int64_t (*const_rows)(int64_t n);
+    ssw_status (*build)(const void *X, int32_t dtype, int64_t n, int32_t dim, unsigned char *codes, float *scale, float *err,
+                        hipStream_t stream);
+    bool query_operand;
+};
+static const ShadowDesc SHADOW[2] = {
+    {q8_dim_supported, [](int64_t n, int32_t dim) { return (size_t)n * dim; }, [](int64_t n) { return n; }, launch_q8_build, false},
+    {q6_dim_supported, q6_code_bytes, q6_padded_rows, launch_q6_build, true},
+};
+
 static bool prune_forced_off() {
     static const bool v = getenv("SSW_TOPK_FULL_SCAN") != nullptr;  // A/B: every top-k runs the full f32 scan
     return v;
 }
 
-static int64_t prune_min_rows(const ssw_index *idx) {
-    if (g_prune_min_rows >= 0) return g_prune_min_rows;
-    return idx->dtype == SSW_DTYPE_F16 ? PRUNE_MIN_ROWS_F16 : PRUNE_MIN_ROWS;
+// MIN_ROWS' entry for the index, or the lab build's value in its place: ssw_tune_prune's min_rows is the int8 shadow's,
+// for the single call and the batch; ssw_tune_prune6's is the 6-bit single call's alone (lowering it leaves the batch
+// on the int8 shadow, or at dim 768, which has none, on the plain batch) and ssw_tune_prune6_batch's the 6-bit batch's
+static int64_t prune_min_rows(const ssw_index *idx, ShadowKind kind, bool batch) {
+    const int64_t lab = kind == SHADOW_Q8 ? g_prune_min_rows : batch ? g_prune6_batch_min_rows : g_prune6_min_rows;
+    return lab >= 0 ? lab : MIN_ROWS[kind][batch][idx->dim == 768][idx->dtype == SSW_DTYPE_F16];
 }
 
-// dim_ok: the dims of the shadow in question (q8_dim_supported: the int8 one, q6_dim_supported: the 6-bit one)
-static bool prune_eligible_from(const ssw_index *idx, int64_t min_rows, bool (*dim_ok)(int32_t)) {
-    return g_prune && !prune_forced_off() && idx->owns_X && !idx->rows_escaped && idx->n >= min_rows &&
-           idx->n_images > 0 && dim_ok(idx->dim);
+static bool prune_eligible_on(const ssw_index *idx, ShadowKind kind, bool batch) {
+    return g_prune && (kind == SHADOW_Q8 || g_prune6) && !prune_forced_off() && idx->owns_X && !idx->rows_escaped &&
+           idx->n >= prune_min_rows(idx, kind, batch) && idx->n_images > 0 && SHADOW[kind].dim_ok(idx->dim);
 }
-bool ssw::prune_eligible(const ssw_index *idx) { return prune_eligible_from(idx, prune_min_rows(idx), q8_dim_supported); }
-bool ssw::prune_batch_eligible(const ssw_index *idx) {
-    return prune_eligible_from(idx, g_prune_min_rows >= 0 ? g_prune_min_rows : PRUNE_BATCH_MIN_ROWS, q8_dim_supported);
-}
-static int64_t prune6_min_rows(const ssw_index *idx) {
-    if (g_prune6_min_rows >= 0) return g_prune6_min_rows;
-    if (idx->dim == 768) return idx->dtype == SSW_DTYPE_F16 ? PRUNE6_MIN_ROWS_768_F16 : PRUNE6_MIN_ROWS_768;
-    return idx->dtype == SSW_DTYPE_F16 ? PRUNE6_MIN_ROWS_F16 : PRUNE6_MIN_ROWS;
-}
-bool ssw::prune6_eligible(const ssw_index *idx) {
-    return g_prune6 && prune_eligible_from(idx, prune6_min_rows(idx), q6_dim_supported);
-}
-// (ssw_tune_prune6's min_rows is the single call's constant alone: lowering it leaves the batch on the int8 shadow, or at
-// dim 768, which has none, on the plain batch)
+bool ssw::prune_eligible(const ssw_index *idx) { return prune_eligible_on(idx, SHADOW_Q8, false); }
+bool ssw::prune_batch_eligible(const ssw_index *idx) { return prune_eligible_on(idx, SHADOW_Q8, true); }
+bool ssw::prune6_eligible(const ssw_index *idx) { return prune_eligible_on(idx, SHADOW_Q6, false); }
 static bool prune6_batch_eligible(const ssw_index *idx) {
-    int64_t batch_rows = idx->dtype == SSW_DTYPE_F16 ? PRUNE6_BATCH_MIN_ROWS_F16 : PRUNE6_BATCH_MIN_ROWS;
-    if (idx->dim == 768) batch_rows = idx->dtype == SSW_DTYPE_F16 ? PRUNE6_BATCH_MIN_ROWS_768_F16 : PRUNE6_BATCH_MIN_ROWS_768;
-    if (g_prune6_batch_min_rows >= 0) batch_rows = g_prune6_batch_min_rows;
-    return prune6_eligible(idx) && idx->n >= batch_rows;
+    return prune6_eligible(idx) && idx->n >= prune_min_rows(idx, SHADOW_Q6, true);
 }
 
 // the rows are about to change: the buffer keeps the scores of the rows it was computed from, the shadow goes stale
 ssw_status ssw::rows_changing(ssw_index *idx) {
     SSW_TRY(ensure_full_scores(idx));
-    idx->prune.stale = true;
-    idx->prune.refused = false;
-    idx->prune.stale6 = true;
-    idx->prune.refused6 = false;
+    for (Shadow &s : idx->prune.sh) s.stale = true, s.refused = false;
     return SSW_OK;
 }
 
@@ -140,129 +149,91 @@ static ssw_status shadow_fits(const ssw_index *idx, size_t bytes, bool *fits) {
     return SSW_OK;
 }
 
-// shadow of the rows for the pruned scan: (re)built when stale, if the device keeps PRUNE_RESERVE free beside it
-ssw_status ssw::ensure_shadow(ssw_index *idx, bool *ready) {
+// The shadow `kind` of the rows for the pruned scan: (re)built when stale, if the device keeps PRUNE_RESERVE free beside
+// it.  A refusal for memory holds until the rows change.
+ssw_status ssw::ensure_shadow(ssw_index *idx, ShadowKind kind, bool *ready) {
     PruneState &p = idx->prune;
+    Shadow &s = p.sh[kind];
+    const ShadowDesc &desc = SHADOW[kind];
     *ready = false;
-    if (p.q8 && !p.stale) {
+    if (s.codes && !s.stale) {
         *ready = true;
         return SSW_OK;
     }
-    if (p.refused) return SSW_OK;
-    if (!p.q8) {
-        const size_t codes = (size_t)idx->n * idx->dim, consts = (size_t)idx->n * sizeof(float);
+    if (s.refused) return SSW_OK;
+    if (!s.codes) {
+        const size_t codes = desc.code_bytes(idx->n, idx->dim), consts = (size_t)desc.const_rows(idx->n) * sizeof(float);
         bool fits = false;
         SSW_TRY(shadow_fits(idx, codes + 2 * consts, &fits));
         if (!fits) {
-            p.refused = true;
+            s.refused = true;
             return SSW_OK;
         }
-        if (hipMalloc((void **)&p.q8, codes) != hipSuccess || hipMalloc((void **)&p.q8_scale, consts) != hipSuccess ||
-            hipMalloc((void **)&p.q8_err, consts) != hipSuccess) {
+        if (hipMalloc((void **)&s.codes, codes) != hipSuccess || hipMalloc((void **)&s.scale, consts) != hipSuccess ||
+            hipMalloc((void **)&s.err, consts) != hipSuccess) {
             (void)hipGetLastError();
-            for (void *b : {(void *)p.q8, (void *)p.q8_scale, (void *)p.q8_err}) (void)hipFree(b);
-            p.q8 = nullptr;
-            p.q8_scale = p.q8_err = nullptr;
-            p.refused = true;
+            s.free();
+            s.refused = true;
             return SSW_OK;
         }
     }
+    // each buffer under its own test: a call that failed part-way is completed by the next one
     SSW_TRY(ensure_call_buffers(idx));
-    if (!p.q8_max) SSW_HIP_TRY(hipMalloc((void **)&p.q8_max, SHADOW_MAX_WORDS * sizeof(unsigned)));
-    SSW_TRY(launch_q8_build(idx->X, idx->dtype, idx->n, idx->dim, p.q8, p.q8_scale, p.q8_err, idx->stream));
-    SSW_TRY(launch_shadow_max(p.q8_err, p.q8_scale, idx->n, p.q8_max, idx->device, idx->stream));
-    p.stale = false;
-    *ready = true;
-    return SSW_OK;
-}
-
-// the packed 6-bit shadow of the rows, under the same rule
-ssw_status ssw::ensure_shadow6(ssw_index *idx, bool *ready) {
-    PruneState &p = idx->prune;
-    *ready = false;
-    if (p.q6 && !p.stale6) {
-        *ready = true;
-        return SSW_OK;
-    }
-    if (p.refused6) return SSW_OK;
-    if (!p.q6) {
-        const size_t codes = q6_code_bytes(idx->n, idx->dim), consts = (size_t)q6_padded_rows(idx->n) * sizeof(float);
-        bool fits = false;
-        SSW_TRY(shadow_fits(idx, codes + 2 * consts, &fits));
-        if (!fits) {
-            p.refused6 = true;
-            return SSW_OK;
-        }
-        if (hipMalloc((void **)&p.q6, codes) != hipSuccess || hipMalloc((void **)&p.q6_scale, consts) != hipSuccess ||
-            hipMalloc((void **)&p.q6_err, consts) != hipSuccess) {
-            (void)hipGetLastError();
-            for (void *b : {(void *)p.q6, (void *)p.q6_scale, (void *)p.q6_err}) (void)hipFree(b);
-            p.q6 = nullptr;
-            p.q6_scale = p.q6_err = nullptr;
-            p.refused6 = true;
-            return SSW_OK;
-        }
-    }
-    SSW_TRY(ensure_call_buffers(idx));
-    if (!p.state6) SSW_HIP_TRY(hipMalloc((void **)&p.state6, (size_t)Q8_MQ_WORDS * sizeof(unsigned)));
-    if (!p.planes6) {  // each buffer under its own test: a call that failed between them leaves no half-made state
+    if (desc.query_operand && !p.state6) SSW_HIP_TRY(hipMalloc((void **)&p.state6, (size_t)Q8_MQ_WORDS * sizeof(unsigned)));
+    if (desc.query_operand && !p.planes6) {
         SSW_HIP_TRY(hipMalloc((void **)&p.planes6, q6_plane_bytes(idx->dim)));
         // columns 2 .. 15 of the query operand stay zero for good: k_q6_query writes columns 0 and 1 only
         SSW_HIP_TRY(hipMemsetAsync(p.planes6, 0, q6_plane_bytes(idx->dim), idx->stream));
     }
-    if (!p.q6_max) SSW_HIP_TRY(hipMalloc((void **)&p.q6_max, SHADOW_MAX_WORDS * sizeof(unsigned)));
-    SSW_TRY(launch_q6_build(idx->X, idx->dtype, idx->n, idx->dim, p.q6, p.q6_scale, p.q6_err, idx->stream));
-    SSW_TRY(launch_shadow_max(p.q6_err, p.q6_scale, idx->n, p.q6_max, idx->device, idx->stream));
-    p.stale6 = false;
+    if (!s.max) SSW_HIP_TRY(hipMalloc((void **)&s.max, SHADOW_MAX_WORDS * sizeof(unsigned)));
+    SSW_TRY(desc.build(idx->X, idx->dtype, idx->n, idx->dim, s.codes, s.scale, s.err, idx->stream));
+    SSW_TRY(launch_shadow_max(s.err, s.scale, idx->n, s.max, idx->device, idx->stream));
+    s.stale = false;
     *ready = true;
     return SSW_OK;
 }
 
-// The two steps of the pre-scan that the lab hooks (ssw_debug_prune_*) drive as well; the shadow is ready.
-// Lower bounds of the scores of q_dev into the buffer, which is partial from here on: a consumer rescans q_last.
-ssw_status ssw::prune_bounds(ssw_index *idx, const float *q_dev) {
+// The two steps of the pre-scan that the lab hooks (ssw_debug_prune_*, ssw_debug_prune6_*) drive as well; the shadow
+// `kind` is ready.  Lower bounds of the scores of q_dev into the buffer, which is partial from here on: a consumer
+// rescans q_last.  dbg_I: of the 6-bit scan (lab hook only).
+ssw_status ssw::prune_bounds(ssw_index *idx, ShadowKind kind, const float *q_dev, int64_t *dbg_I) {
     PruneState &p = idx->prune;
-    SSW_TRY(launch_q8_query(q_dev, idx->dim, p.q_last, p.state, idx->stream));
-    SSW_TRY(launch_q8_bounds(p.q8, p.q8_scale, p.q8_err, p.q_last, p.state, idx->scores, idx->n, idx->dim, idx->device,
-                             idx->stream));
-    idx->scores_partial = true;
-    return SSW_OK;
-}
-
-// The same on the 6-bit shadow, which is ready (the lab hook ssw_debug_prune6_bounds drives it as well, with dbg_I).
-ssw_status ssw::prune6_bounds(ssw_index *idx, const float *q_dev, int64_t *dbg_I) {
-    PruneState &p = idx->prune;
-    SSW_TRY(launch_q6_query(q_dev, idx->dim, p.state6, p.planes6, p.q_last, idx->stream));
-    SSW_TRY(launch_q6_bounds(p.q6, p.q6_scale, p.q6_err, p.planes6, p.state6, idx->scores, idx->n, idx->dim, dbg_I,
-                             idx->device, idx->stream));
+    const Shadow &s = p.sh[kind];
+    if (kind == SHADOW_Q6) {
+        SSW_TRY(launch_q6_query(q_dev, idx->dim, p.state6, p.planes6, p.q_last, idx->stream));
+        SSW_TRY(launch_q6_bounds(s.codes, s.scale, s.err, p.planes6, p.state6, idx->scores, idx->n, idx->dim, dbg_I,
+                                 idx->device, idx->stream));
+    } else {
+        SSW_TRY(launch_q8_query(q_dev, idx->dim, p.q_last, p.state, idx->stream));
+        SSW_TRY(launch_q8_bounds(s.codes, s.scale, s.err, p.q_last, p.state, idx->scores, idx->n, idx->dim, idx->device,
+                                 idx->stream));
+    }
     idx->scores_partial = true;
     return SSW_OK;
 }
 
 // The rows that may still reach the k-th key of the last selection, at most cap of them -> *out_m = their published
-// count, -1 = run the full scan.  One host wait: a sleep on sleep_ev_or_null first, then a spin.  six: the bounds in
-// the buffer are the 6-bit shadow's (width (***) of prune.hip), else the int8 shadow's.
-static ssw_status survivors_of(ssw_index *idx, bool six, int32_t k, int64_t cap, hipEvent_t sleep_ev_or_null, int32_t *out_m) {
+// count, -1 = run the full scan.  One host wait: a sleep on sleep_ev_or_null first, then a spin.  The bounds in the
+// buffer are the shadow `kind`'s: the 6-bit query is a chunk of one slot (width (***) of prune.hip).
+ssw_status ssw::prune_survivors(ssw_index *idx, ShadowKind kind, int32_t k, int64_t cap, hipEvent_t sleep_ev_or_null,
+                                int32_t *out_m) {
     PruneState &p = idx->prune;
+    const Shadow &s = p.sh[kind];
     const unsigned seq = next_seq(p.seq);
     int32_t *host_dev = nullptr;
     SSW_HIP_TRY(hipHostGetDevicePointer((void **)&host_dev, p.host, 0));
-    if (six)
-        SSW_TRY(launch_survivors_q6(idx->scores, p.q6_err, p.q6_scale, p.q6_max, idx->n, idx->dim, idx->ws.out_keys, idx->ws.out_count,
-                                    k, p.state6, p.surv_rows, cap, host_dev, seq, idx->device, idx->stream));
-    else
-        SSW_TRY(launch_survivors(idx->scores, p.q8_err, p.q8_max, idx->n, idx->ws.out_keys, idx->ws.out_count, k, p.state, p.surv_rows,
+    if (kind == SHADOW_Q6) {
+        SSW_TRY(launch_survivors_mq(idx->scores, s.err, s.scale, s.max, idx->n, idx->dim, true, idx->ws.out_keys,
+                                    idx->ws.out_count, k, p.state6, p.surv_rows, cap, idx->device, idx->stream));
+        SSW_TRY(launch_prune_publish_mq(p.state6, 1, cap, host_dev, seq, idx->stream));
+    } else {
+        SSW_TRY(launch_survivors(idx->scores, s.err, s.max, idx->n, idx->ws.out_keys, idx->ws.out_count, k, p.state, p.surv_rows,
                                  cap, host_dev, seq, idx->device, idx->stream));
+    }
     if (sleep_ev_or_null) SSW_HIP_TRY(hipEventSynchronize(sleep_ev_or_null));
     SSW_TRY(wait_host_seq(idx->stream, reinterpret_cast<const unsigned *>(p.host), seq));
     *out_m = __atomic_load_n(p.host + 1, __ATOMIC_ACQUIRE);
     return SSW_OK;
-}
-ssw_status ssw::prune_survivors(ssw_index *idx, int32_t k, int64_t cap, hipEvent_t sleep_ev_or_null, int32_t *out_m) {
-    return survivors_of(idx, false, k, cap, sleep_ev_or_null, out_m);
-}
-ssw_status ssw::prune6_survivors(ssw_index *idx, int32_t k, int64_t cap, hipEvent_t sleep_ev_or_null, int32_t *out_m) {
-    return survivors_of(idx, true, k, cap, sleep_ev_or_null, out_m);
 }
 
 // The score buffer for the selection of the top-k of query q_dev (exclusions installed): the full f32 scan, or on a
@@ -272,29 +243,32 @@ ssw_status ssw::prune6_survivors(ssw_index *idx, int32_t k, int64_t cap, hipEven
 // that cannot be bounded) runs the full scan instead.  The profiling events bracket the whole replacement.
 // The shadow is the 6-bit one where prune6_eligible says so (only that one is built then), else the int8 one; a 6-bit
 // shadow refused for memory leaves the int8 path, if an int8 shadow exists or fits.  A dim-768 index is never
-// prune_eligible (no int8 shadow at that dim): it reaches ensure_shadow6 or the full scan.
+// prune_eligible (no int8 shadow at that dim): it reaches the 6-bit shadow or the full scan.
 // *out_candidates: the pruned path succeeded on an index without an image map, and the candidates of the final top-k
 // are in the selection's workspace (launch_scatter_candidates): the caller's selection, the next thing on the stream,
 // runs over them alone (do_select, from_candidates).  Nothing of it is kept in the handle.
 ssw_status ssw::scan_for_topk(ssw_index *idx, const float *q_dev, int32_t k, bool *out_candidates) {
     *out_candidates = false;
-    bool ready = false, six = false;
+    bool ready = false;
+    ShadowKind kind = SHADOW_Q6;
     const bool k_ok = k >= 1 && k <= SSW_MAX_TOPK && (idx->ws.xchg.msg_out == nullptr || k <= idx->ws.xchg.k_max);
-    if (k_ok && prune6_eligible(idx)) SSW_TRY(ensure_shadow6(idx, &six));
-    if (k_ok && !six && prune_eligible(idx)) SSW_TRY(ensure_shadow(idx, &ready));
-    if (!ready && !six) return do_scan(idx, q_dev);
+    if (k_ok && prune6_eligible(idx)) SSW_TRY(ensure_shadow(idx, kind, &ready));
+    if (k_ok && !ready && prune_eligible(idx)) {
+        kind = SHADOW_Q8;
+        SSW_TRY(ensure_shadow(idx, kind, &ready));
+    }
+    if (!ready) return do_scan(idx, q_dev);
     SSW_TRY(ensure_ws(idx));
     return profiled(idx, [&]() -> ssw_status {
         PruneState &p = idx->prune;
-        if (six) SSW_TRY(prune6_bounds(idx, q_dev, nullptr));
-        else SSW_TRY(prune_bounds(idx, q_dev));
+        SSW_TRY(prune_bounds(idx, kind, q_dev, nullptr));
         SSW_HIP_TRY(hipEventRecord(p.ev, idx->stream));
         // threshold: the ordinary selection over the lower bounds, with the exclusions, without a message or host result
         SSW_TRY(do_select(idx, idx->scores, k, SelectDest{nullptr, 0u, false}, idx->stream));
         // (ahead of the host wait; the survivor pass reads the selection's keys and count, not these words)
         if (!idx->has_map) SSW_TRY(select_reset_state(idx->ws, idx->stream));
         int32_t m = -1;
-        SSW_TRY(survivors_of(idx, six, k, SURV_CAP, p.ev, &m));  // sleep through the shadow scan, spin on the rest
+        SSW_TRY(prune_survivors(idx, kind, k, SURV_CAP, p.ev, &m));  // sleep through the shadow scan, spin on the rest
         p.last = m;
         ++p.queries;
         if (m < 0) {
@@ -364,33 +338,36 @@ ssw_status ssw::ensure_prune_batch(ssw_index *idx, int w, int *out_w) {
 
 // The shadow that bounds the chunks of a pruned batch, made ready: the single call's rule (scan_for_topk).  The 6-bit one
 // where prune6_eligible says so and the index has the batch's rows for it (only that one is built then); else, and
-// where the 6-bit shadow is refused for memory, the int8 one under prune_batch_eligible.  prune_batch.six remembers
+// where the 6-bit shadow is refused for memory, the int8 one under prune_batch_eligible.  prune_batch.kind remembers
 // the choice for the steps below.  *ready false: the batch is the plain one -- at dim 768, which has no int8 fallback,
 // whenever the index is below the batch's 6-bit constant or the 6-bit shadow was refused.
 ssw_status ssw::prune_batch_shadow(ssw_index *idx, bool *ready) {
     *ready = false;
-    bool six = false;
-    if (prune6_batch_eligible(idx)) SSW_TRY(ensure_shadow6(idx, &six));
-    if (!six && prune_batch_eligible(idx)) SSW_TRY(ensure_shadow(idx, ready));
-    if (six) *ready = true;
-    if (*ready) idx->prune_batch.six = six;
+    ShadowKind kind = SHADOW_Q6;
+    if (prune6_batch_eligible(idx)) SSW_TRY(ensure_shadow(idx, kind, ready));
+    if (!*ready && prune_batch_eligible(idx)) {
+        kind = SHADOW_Q8;
+        SSW_TRY(ensure_shadow(idx, kind, ready));
+    }
+    if (*ready) idx->prune_batch.kind = kind;
     return SSW_OK;
 }
 
-// The two device steps of a chunk that the lab hooks drive as well; the shadow prune_batch.six names and the chunk's
+// The two device steps of a chunk that the lab hooks drive as well; the shadow prune_batch.kind names and the chunk's
 // buffers are ready and the w queries are in batch.qb_dev.  Lower bounds of query j into slab j; the handle's buffer
 // (the last query's slab) is partial from here on and q_last is the last query.  dbg_hi / dbg_lo: of the int8 chunk,
 // dbg_I: of the 6-bit chunk (lab hooks only).
 ssw_status ssw::prune_bounds_mq(ssw_index *idx, int w, int32_t *dbg_hi, int32_t *dbg_lo, int64_t *dbg_I) {
     PruneState &p = idx->prune;
     PruneBatchState &pb = idx->prune_batch;
-    if (pb.six) {
+    const Shadow &s = p.sh[pb.kind];
+    if (pb.kind == SHADOW_Q6) {
         SSW_TRY(launch_q6_query_mq(idx->batch.qb_dev, idx->dim, w, pb.mq, pb.planes, p.q_last, idx->stream));
-        SSW_TRY(launch_q6_bounds_mq(p.q6, p.q6_scale, p.q6_err, pb.planes, pb.mq, w, idx->batch.side, slab_stride(idx),
+        SSW_TRY(launch_q6_bounds_mq(s.codes, s.scale, s.err, pb.planes, pb.mq, w, idx->batch.side, slab_stride(idx),
                                     idx->scores, idx->n, idx->dim, dbg_I, idx->device, idx->stream));
     } else {
         SSW_TRY(launch_q8_query_mq(idx->batch.qb_dev, idx->dim, w, pb.mq, pb.planes, p.q_last, idx->stream));
-        SSW_TRY(launch_q8_bounds_mq(p.q8, p.q8_scale, p.q8_err, pb.planes, pb.mq, w, idx->batch.side, slab_stride(idx),
+        SSW_TRY(launch_q8_bounds_mq(s.codes, s.scale, s.err, pb.planes, pb.mq, w, idx->batch.side, slab_stride(idx),
                                     idx->scores, idx->n, idx->dim, dbg_hi, dbg_lo, idx->device, idx->stream));
     }
     idx->scores_partial = true;
@@ -399,12 +376,10 @@ ssw_status ssw::prune_bounds_mq(ssw_index *idx, int w, int32_t *dbg_hi, int32_t 
 
 // the survivors of slot j against the keys the last selection left, into the slot's list (no publish)
 ssw_status ssw::prune_survivors_slot(ssw_index *idx, int w, int j, int32_t k, int64_t cap) {
-    PruneState &p = idx->prune;
     PruneBatchState &pb = idx->prune_batch;
-    const bool six = pb.six;
-    return launch_survivors_mq(chunk_slab(idx, w, j), six ? p.q6_err : p.q8_err, six ? p.q6_scale : p.q8_scale,
-                               six ? p.q6_max : p.q8_max, idx->n, idx->dim, six, idx->ws.out_keys, idx->ws.out_count, k,
-                               pb.mq + j * Q8_MQ_WORDS, pb.surv_rows + (int64_t)j * SURV_CAP, cap, idx->device,
+    const Shadow &s = idx->prune.sh[pb.kind];
+    return launch_survivors_mq(chunk_slab(idx, w, j), s.err, s.scale, s.max, idx->n, idx->dim, pb.kind == SHADOW_Q6,
+                               idx->ws.out_keys, idx->ws.out_count, k, pb.mq + j * Q8_MQ_WORDS, pb.surv_rows + (int64_t)j * SURV_CAP, cap, idx->device,
                                idx->stream);
 }
 
@@ -458,14 +433,15 @@ ssw_status ssw_index_prune_stats(ssw_index *idx, int64_t *out6) {
     const PruneState &p = idx->prune;
     // the state of the shadow single queries use: the 6-bit one where it applies and was not refused
     // (a dim-768 index has no other: there a refusal is the 6-bit shadow's)
-    const bool six = prune6_eligible(idx) && (!p.refused6 || !q8_dim_supported(idx->dim));
-    if (six) out6[0] = p.q6 ? (p.stale6 ? 2 : 1) : (p.refused6 ? 3 : 0);
-    else out6[0] = p.q8 ? (p.stale ? 2 : 1) : (p.refused ? 3 : 0);
+    const Shadow &q8 = p.sh[SHADOW_Q8], &q6 = p.sh[SHADOW_Q6];
+    const bool six = prune6_eligible(idx) && (!q6.refused || !q8_dim_supported(idx->dim));
+    const Shadow &s = six ? q6 : q8;
+    out6[0] = s.codes ? (s.stale ? 2 : 1) : (s.refused ? 3 : 0);
     out6[1] = prune_eligible(idx) || six ? 1 : 0;
     out6[2] = p.last;
     out6[3] = p.queries;
     out6[4] = p.fallbacks;
-    out6[5] = (p.q8 ? idx->n * (idx->dim + 8) : 0) + (p.q6 ? q6_padded_rows(idx->n) * (idx->dim * 3 / 4 + 8) : 0);
+    out6[5] = (q8.codes ? idx->n * (idx->dim + 8) : 0) + (q6.codes ? q6_padded_rows(idx->n) * (idx->dim * 3 / 4 + 8) : 0);
     return SSW_OK;
 }
 
@@ -479,7 +455,7 @@ ssw_status ssw_index_prune_completions(ssw_index *idx, int64_t *out2) {
 #ifdef SSW_DEBUG_HOOKS
 ssw_status ssw_tune_prune(int32_t enable, int64_t min_rows, int64_t reserve_bytes) {
     g_prune = enable != 0;
-    g_prune_min_rows = min_rows < 0 ? -1 : min_rows;  // < 0: PRUNE_MIN_ROWS / PRUNE_MIN_ROWS_F16 again
+    g_prune_min_rows = min_rows < 0 ? -1 : min_rows;  // < 0: MIN_ROWS' entries again
     g_prune_reserve = reserve_bytes < 0 ? PRUNE_RESERVE : reserve_bytes;
     return SSW_OK;
 }
@@ -496,27 +472,27 @@ ssw_status ssw_tune_prune_scan(int32_t blocks_per_cu, int32_t group_loads) {
 
 ssw_status ssw_tune_prune6(int32_t enable, int64_t min_rows) {
     g_prune6 = enable != 0;
-    g_prune6_min_rows = min_rows < 0 ? -1 : min_rows;  // < 0: PRUNE6_MIN_ROWS / PRUNE6_MIN_ROWS_F16 again
+    g_prune6_min_rows = min_rows < 0 ? -1 : min_rows;  // < 0: MIN_ROWS' entries again
     return SSW_OK;
 }
 
 ssw_status ssw_tune_prune6_batch(int64_t min_rows) {
-    g_prune6_batch_min_rows = min_rows < 0 ? -1 : min_rows;  // < 0: PRUNE6_BATCH_MIN_ROWS / PRUNE6_BATCH_MIN_ROWS_F16 again
+    g_prune6_batch_min_rows = min_rows < 0 ? -1 : min_rows;  // < 0: MIN_ROWS' entries again
     return SSW_OK;
 }
 
 ssw_status ssw_tune_prune6_scan(int32_t blocks_per_cu, int32_t tiles) {
-    tune_q6_bounds(blocks_per_cu, tiles);
+    tune_tile_scan(SCAN_Q6, blocks_per_cu, tiles);
     return SSW_OK;
 }
 
 ssw_status ssw_tune_prune_scan_mq(int32_t blocks_per_cu, int32_t tiles) {
-    tune_q8_bounds_mq(blocks_per_cu, tiles);
+    tune_tile_scan(SCAN_Q8_MQ, blocks_per_cu, tiles);
     return SSW_OK;
 }
 
 ssw_status ssw_tune_prune6_scan_mq(int32_t blocks_per_cu, int32_t tiles) {
-    tune_q6_bounds_mq(blocks_per_cu, tiles);
+    tune_tile_scan(SCAN_Q6_MQ, blocks_per_cu, tiles);
     return SSW_OK;
 }
 #endif

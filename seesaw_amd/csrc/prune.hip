@@ -22,6 +22,7 @@
 // outside [2^-60, 2^60] / 127) get c = 0, s = 0 and a = +inf: their upper bound is +inf, so they are always rescored.
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 #include "ssw_common.h"
 
@@ -571,8 +572,6 @@ __global__ void k_prune_publish(const int32_t *__restrict__ sel_count, int32_t k
 constexpr int MQ_WIDTH = 16, MQ_WORDS = 8;
 constexpr double MQ_INFLATE = 1.0 + 0x1p-40;  // on w: the double roundings of w and of s t2 I (a few 2^-53 (|lb| + w))
 constexpr int MQ_BLOCKS_PER_CU = 1;
-SSW_TUNABLE int g_mq_blocks_per_cu = MQ_BLOCKS_PER_CU;
-SSW_TUNABLE int g_mq_tiles = 0;  // 0: mq_default_tiles(C)
 constexpr int mq_default_tiles(int C) { return C == 4 ? 1 : 2; }  // 16-row tiles of one request: 8 / 16 / 16 KiB a wave
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -838,13 +837,11 @@ __global__ __launch_bounds__(256) void k_scatter_scores(const int64_t *__restric
 // Query operand: k-step u, lane l: the u32x4 at u * 64 + l holds the hi plane's codes of elements 64 u + 16 (l >> 4) + j
 // in column 0 (l & 15 == 0), the lo plane's in column 1, zeros elsewhere (written once, when the buffer is made).
 constexpr int Q6_BLOCKS_PER_CU = 1;
-SSW_TUNABLE int g_q6_blocks_per_cu = Q6_BLOCKS_PER_CU;
-SSW_TUNABLE int g_q6_tiles = 0;  // 0: q6_default_tiles(C)
 // 16-row tiles of one request of a wave: 6 KiB at dim 256 and 512, 12 KiB (one tile) at dim 1024.  From the traced sweep
 // of blocks a CU x tiles at 10^8 rows (docs/EXPERIMENTS.md, "The 6-bit scan's launch shape"): at dim 256 two tiles take
 // 3.63 ms a launch where the four of the 12-KiB rule took 4.13, at dim 512 one tile 6.17 where two took 6.25; a second
 // or fourth block a CU is level with one at dim 256 and behind it at dim 512 and 1024.  Dim 768 (C = 3, 9 KiB a tile) takes
-// one tile, the only count q6_tiles admits there; its launch shape has not been swept.
+// one tile, the only count scan_tiles admits there; its launch shape has not been swept.
 constexpr int q6_default_tiles(int C) { return C == 1 ? 2 : 1; }
 
 // 31 sqrt(dim), rounded up
@@ -1085,8 +1082,6 @@ __global__ __launch_bounds__(256) void k_q6_query_mq(const float *__restrict__ q
 }
 
 constexpr int Q6MQ_BLOCKS_PER_CU = 1;
-SSW_TUNABLE int g_q6mq_blocks_per_cu = Q6MQ_BLOCKS_PER_CU;
-SSW_TUNABLE int g_q6mq_tiles = 0;  // 0: q6mq_default_tiles(C)
 // 12 KiB a wave at every dim, the request k_q6_bounds had when this was set; one tile at dim 512 is behind two at nq = 16
 // (profiles/q6_shape_batch_thresholds.txt); dim 768 (C = 3): one tile, 9 KiB
 constexpr int q6mq_default_tiles(int C) { return 4 / C; }
@@ -1221,7 +1216,78 @@ bool q8_dim_supported(int32_t dim) { return dim == 256 || dim == 512 || dim == 1
 // k_q8_bounds' lanes-per-row map needs 4 % C == 0
 bool q6_dim_supported(int32_t dim) { return q8_dim_supported(dim) || dim == 768; }
 
-ssw_status launch_q8_build(const void *X, int32_t dtype, int64_t n, int32_t dim, int8_t *codes, float *scale,
+// ---- run-time shapes -> template instances ----------------------------------------------------------------------------
+template <int N>
+using Int = std::integral_constant<int, N>;
+
+// f(Int<C>) for C = dim / 256 of a supported dim; C3: the kernel has a C = 3 instance (the 6-bit shadow's do)
+template <bool C3, class F>
+static void dispatch_dim(int C, F f) {
+    if (C == 1) return f(Int<1>{});
+    if (C == 2) return f(Int<2>{});
+    if constexpr (C3)
+        if (C == 3) return f(Int<3>{});
+    f(Int<4>{});
+}
+
+// The launch shape of the three tile scans on the matrix core, by TileScan (ssw_tune_prune_scan_mq, ssw_tune_prune6_scan,
+// ssw_tune_prune6_scan_mq; lab build only): four-wave blocks per CU, and 16-row tiles of one request (0: the scan's
+// default for C)
+struct ScanTune {
+    int blocks_per_cu;
+    int tiles;
+};
+constexpr int SCAN_BLOCKS_PER_CU[3] = {MQ_BLOCKS_PER_CU, Q6_BLOCKS_PER_CU, Q6MQ_BLOCKS_PER_CU};
+static SSW_TUNABLE ScanTune g_scan_tune[3] = {{SCAN_BLOCKS_PER_CU[0], 0}, {SCAN_BLOCKS_PER_CU[1], 0}, {SCAN_BLOCKS_PER_CU[2], 0}};
+constexpr int scan_default_tiles(TileScan scan, int C) {
+    return scan == SCAN_Q8_MQ ? mq_default_tiles(C) : scan == SCAN_Q6 ? q6_default_tiles(C) : q6mq_default_tiles(C);
+}
+
+static int scan_tiles(const ScanTune &tune, int default_tiles, int C) {
+    int t = tune.tiles > 0 ? tune.tiles : default_tiles;
+    // two register sets of more than 16 KiB (int8 codes) or 12 KiB (6-bit codes) a wave do not fit beside the query operand
+    while (t * C > 4) t >>= 1;
+    return t;
+}
+
+void scan_shape(TileScan scan, int32_t dim, int device, int64_t n, int *out_blocks, int *out_tiles) {
+    const int T = scan_tiles(g_scan_tune[scan], scan_default_tiles(scan, dim / 256), dim / 256);
+    const int64_t need = ((n + 16 * T - 1) / (16 * T) + 3) / 4;
+    int64_t grid = (int64_t)num_cus(device) * g_scan_tune[scan].blocks_per_cu;
+    if (grid > need) grid = need;
+    if (grid < 1) grid = 1;
+    *out_blocks = (int)grid;
+    *out_tiles = T;
+}
+
+#ifdef SSW_DEBUG_HOOKS
+void tune_tile_scan(TileScan scan, int blocks_per_cu, int tiles) {
+    g_scan_tune[scan].blocks_per_cu = blocks_per_cu >= 1 && blocks_per_cu <= 8 ? blocks_per_cu : SCAN_BLOCKS_PER_CU[scan];
+    g_scan_tune[scan].tiles = tiles == 1 || tiles == 2 || tiles == 4 ? tiles : 0;
+}
+#endif
+
+// f(Int<C>, Int<T>, DEBUG) for the instance of tile scan S that scan_shape's T and the caller's debug output ask for.
+// The product has one instance per C, at the scan's default T and without DEBUG; the lab build has every T with
+// T * C <= 4 (scan_tiles), each with and without DEBUG.
+template <TileScan S, class F>
+static void dispatch_scan(int C, int T, bool debug, F f) {
+    dispatch_dim<S != SCAN_Q8_MQ>(C, [&](auto c) {
+#ifdef SSW_DEBUG_HOOKS
+        auto with_debug = [&](auto t) { debug ? f(c, t, std::true_type{}) : f(c, t, std::false_type{}); };
+        if constexpr (c.value == 1)
+            if (T == 4) return with_debug(Int<4>{});
+        if constexpr (c.value <= 2)
+            if (T == 2) return with_debug(Int<2>{});
+        with_debug(Int<1>{});
+#else
+        (void)T, (void)debug;
+        f(c, Int<scan_default_tiles(S, c.value)>{}, std::false_type{});
+#endif
+    });
+}
+
+ssw_status launch_q8_build(const void *X, int32_t dtype, int64_t n, int32_t dim, unsigned char *codes, float *scale,
                            float *err, hipStream_t stream) {
     if (n <= 0) return SSW_OK;
     if (!q8_dim_supported(dim) || (dtype != SSW_DTYPE_F32 && dtype != SSW_DTYPE_F16)) {
@@ -1229,21 +1295,13 @@ ssw_status launch_q8_build(const void *X, int32_t dtype, int64_t n, int32_t dim,
         return SSW_ERR_UNSUPPORTED;
     }
     const dim3 grid((unsigned)std::min<int64_t>((n + 3) / 4, (int64_t)1 << 20)), block(256);
-    if (dtype == SSW_DTYPE_F16) {
-        const uint16_t *Xh = static_cast<const uint16_t *>(X);
-        switch (dim) {
-            case 256: hipLaunchKernelGGL(k_q8_build_h16<1>, grid, block, 0, stream, Xh, n, codes, scale, err); break;
-            case 512: hipLaunchKernelGGL(k_q8_build_h16<2>, grid, block, 0, stream, Xh, n, codes, scale, err); break;
-            default: hipLaunchKernelGGL(k_q8_build_h16<4>, grid, block, 0, stream, Xh, n, codes, scale, err); break;
-        }
-    } else {
-        const float *Xf = static_cast<const float *>(X);
-        switch (dim) {
-            case 256: hipLaunchKernelGGL(k_q8_build<1>, grid, block, 0, stream, Xf, n, codes, scale, err); break;
-            case 512: hipLaunchKernelGGL(k_q8_build<2>, grid, block, 0, stream, Xf, n, codes, scale, err); break;
-            default: hipLaunchKernelGGL(k_q8_build<4>, grid, block, 0, stream, Xf, n, codes, scale, err); break;
-        }
-    }
+    int8_t *c8 = reinterpret_cast<int8_t *>(codes);
+    dispatch_dim<false>(dim / 256, [&](auto c) {
+        if (dtype == SSW_DTYPE_F16)
+            hipLaunchKernelGGL(k_q8_build_h16<c.value>, grid, block, 0, stream, static_cast<const uint16_t *>(X), n, c8, scale, err);
+        else
+            hipLaunchKernelGGL(k_q8_build<c.value>, grid, block, 0, stream, static_cast<const float *>(X), n, c8, scale, err);
+    });
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
 }
@@ -1254,7 +1312,7 @@ ssw_status launch_q8_query(const float *q_dev, int32_t dim, float *q_keep, unsig
     return SSW_OK;
 }
 
-ssw_status launch_q8_bounds(const int8_t *codes, const float *scale, const float *err, const float *q_dev,
+ssw_status launch_q8_bounds(const unsigned char *codes, const float *scale, const float *err, const float *q_dev,
                             const unsigned *state, float *scores, int64_t n, int32_t dim, int device,
                             hipStream_t stream) {
     if (n <= 0) return SSW_OK;
@@ -1268,27 +1326,18 @@ ssw_status launch_q8_bounds(const int8_t *codes, const float *scale, const float
     int64_t grid = (int64_t)num_cus(device) * g_q8_blocks_per_cu;  // four-wave blocks
     if (grid > need) grid = need;
     if (grid < 1) grid = 1;
-#define SSW_Q8_BOUNDS(C_, U_)                                                                                         \
-    hipLaunchKernelGGL((k_q8_bounds<C_, U_>), dim3((unsigned)grid), dim3(256), 0, stream, codes, scale, err, q_dev, \
-                       state, scores, n)
-#define SSW_Q8_BOUNDS_DIM(U_)                 \
-    switch (C) {                              \
-        case 1: SSW_Q8_BOUNDS(1, U_); break;  \
-        case 2: SSW_Q8_BOUNDS(2, U_); break;  \
-        default: SSW_Q8_BOUNDS(4, U_); break; \
-    }
+    const int8_t *cd = reinterpret_cast<const int8_t *>(codes);
+    dispatch_dim<false>(C, [&](auto c) {
+        auto launch = [&](auto u) {
+            hipLaunchKernelGGL((k_q8_bounds<c.value, u.value>), dim3((unsigned)grid), dim3(256), 0, stream, cd, scale, err,
+                               q_dev, state, scores, n);
+        };
 #ifdef SSW_DEBUG_HOOKS
-    if (g_q8_group_loads == 4) {
-        SSW_Q8_BOUNDS_DIM(4)
-    } else if (g_q8_group_loads == 16) {
-        SSW_Q8_BOUNDS_DIM(16)
-    } else
+        if (g_q8_group_loads == 4) return launch(Int<4>{});
+        if (g_q8_group_loads == 16) return launch(Int<16>{});
 #endif
-    {
-        SSW_Q8_BOUNDS_DIM(Q8_GROUP_LOADS)
-    }
-#undef SSW_Q8_BOUNDS_DIM
-#undef SSW_Q8_BOUNDS
+        launch(Int<Q8_GROUP_LOADS>{});
+    });
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
 }
@@ -1312,14 +1361,19 @@ ssw_status launch_shadow_max(const float *err, const float *scale, int64_t n, un
     return SSW_OK;
 }
 
-ssw_status launch_survivors(const float *lb, const float *err, const unsigned *mx, int64_t n, const uint64_t *keys,
-                            const int32_t *sel_count, int32_t k, unsigned *state, int64_t *rows, int64_t cap, int32_t *host_block, unsigned seq,
-                            int device, hipStream_t stream) {
+// the blocks of a survivor pass over n bounds
+static dim3 survivor_grid(int device, int64_t n) {
     int64_t grid = (int64_t)num_cus(device) * 4;
     const int64_t need = (n + 1023) / 1024;  // four rows a lane
     if (grid > need) grid = need;
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(k_survivors, dim3((unsigned)grid), dim3(256), 0, stream, lb, err, mx, n, keys, sel_count, k,
+    return dim3((unsigned)grid);
+}
+
+ssw_status launch_survivors(const float *lb, const float *err, const unsigned *mx, int64_t n, const uint64_t *keys,
+                            const int32_t *sel_count, int32_t k, unsigned *state, int64_t *rows, int64_t cap, int32_t *host_block, unsigned seq,
+                            int device, hipStream_t stream) {
+    hipLaunchKernelGGL(k_survivors, survivor_grid(device, n), dim3(256), 0, stream, lb, err, mx, n, keys, sel_count, k,
                        state, rows, cap);
     hipLaunchKernelGGL(k_prune_publish, dim3(1), dim3(64), 0, stream, sel_count, k, state, cap, host_block, seq);
     SSW_HIP_TRY(hipGetLastError());
@@ -1335,23 +1389,7 @@ ssw_status launch_q8_query_mq(const float *qb_dev, int32_t dim, int32_t w, unsig
     return SSW_OK;
 }
 
-static int mq_tiles(int C) {
-    int t = g_mq_tiles > 0 ? g_mq_tiles : mq_default_tiles(C);
-    while (t * C > 4) t >>= 1;  // two register sets of more than 16 KiB a wave do not fit beside the query planes
-    return t;
-}
-
-void q8_bounds_mq_shape(int32_t dim, int device, int64_t n, int *out_blocks, int *out_tiles) {
-    const int T = mq_tiles(dim / 256);
-    const int64_t need = ((n + 16 * T - 1) / (16 * T) + 3) / 4;
-    int64_t grid = (int64_t)num_cus(device) * g_mq_blocks_per_cu;
-    if (grid > need) grid = need;
-    if (grid < 1) grid = 1;
-    *out_blocks = (int)grid;
-    *out_tiles = T;
-}
-
-ssw_status launch_q8_bounds_mq(const int8_t *codes, const float *scale, const float *err, const int8_t *planes,
+ssw_status launch_q8_bounds_mq(const unsigned char *codes, const float *scale, const float *err, const int8_t *planes,
                                const unsigned *mq, int32_t w, float *side, int64_t stride, float *own, int64_t n,
                                int32_t dim, int32_t *dbg_hi, int32_t *dbg_lo, int device, hipStream_t stream) {
     if (n <= 0) return SSW_OK;
@@ -1359,54 +1397,23 @@ ssw_status launch_q8_bounds_mq(const int8_t *codes, const float *scale, const fl
         set_error("q8_bounds_mq: dim=%d, w=%d unsupported", dim, w);
         return SSW_ERR_UNSUPPORTED;
     }
-    const int C = dim / 256;
     int grid = 1, T = 1;
-    q8_bounds_mq_shape(dim, device, n, &grid, &T);
+    scan_shape(SCAN_Q8_MQ, dim, device, n, &grid, &T);
+    const int8_t *cd = reinterpret_cast<const int8_t *>(codes);
     const u32x4 *pl = reinterpret_cast<const u32x4 *>(planes);
-#define SSW_MQ(C_, T_, D_)                                                                                              \
-    hipLaunchKernelGGL((k_q8_bounds_mq<C_, T_, D_>), dim3((unsigned)grid), dim3(256), 0, stream, codes, scale, err, pl, \
-                       mq, (int)w, side, stride, own, n, dbg_hi, dbg_lo)
-#ifdef SSW_DEBUG_HOOKS
-#define SSW_MQ_T(C_, T_)          \
-    if (dbg_hi) SSW_MQ(C_, T_, true); \
-    else SSW_MQ(C_, T_, false)
-    if (C == 1) {
-        if (T == 1) { SSW_MQ_T(1, 1); } else if (T == 4) { SSW_MQ_T(1, 4); } else { SSW_MQ_T(1, 2); }
-    } else if (C == 2) {
-        if (T == 1) { SSW_MQ_T(2, 1); } else { SSW_MQ_T(2, 2); }
-    } else {
-        SSW_MQ_T(4, 1);
-    }
-#undef SSW_MQ_T
-#else
-    (void)T;
-    switch (C) {
-        case 1: SSW_MQ(1, mq_default_tiles(1), false); break;
-        case 2: SSW_MQ(2, mq_default_tiles(2), false); break;
-        default: SSW_MQ(4, mq_default_tiles(4), false); break;
-    }
-#endif
-#undef SSW_MQ
+    dispatch_scan<SCAN_Q8_MQ>(dim / 256, T, dbg_hi != nullptr, [&](auto c, auto t, auto d) {
+        hipLaunchKernelGGL((k_q8_bounds_mq<c.value, t.value, d.value>), dim3((unsigned)grid), dim3(256), 0, stream, cd, scale,
+                           err, pl, mq, (int)w, side, stride, own, n, dbg_hi, dbg_lo);
+    });
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
 }
-
-#ifdef SSW_DEBUG_HOOKS
-void tune_q8_bounds_mq(int blocks_per_cu, int tiles) {
-    g_mq_blocks_per_cu = blocks_per_cu >= 1 && blocks_per_cu <= 8 ? blocks_per_cu : MQ_BLOCKS_PER_CU;
-    g_mq_tiles = tiles == 1 || tiles == 2 || tiles == 4 ? tiles : 0;
-}
-#endif
 
 // six: the bounds, err, scale and mx are the 6-bit shadow's (width (***)), else the int8 shadow's (width (**))
 ssw_status launch_survivors_mq(const float *lb, const float *err, const float *scale, const unsigned *mx, int64_t n, int32_t dim,
                                bool six, const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *slot_state,
                                int64_t *rows, int64_t cap, int device, hipStream_t stream) {
-    int64_t grid = (int64_t)num_cus(device) * 4;
-    const int64_t need = (n + 1023) / 1024;  // four rows a lane
-    if (grid > need) grid = need;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(k_survivors_mq, dim3((unsigned)grid), dim3(256), 0, stream, lb, err, scale, mx, n,
+    hipLaunchKernelGGL(k_survivors_mq, survivor_grid(device, n), dim3(256), 0, stream, lb, err, scale, mx, n,
                        six ? q6_code_norm(dim) : mq_code_norm(dim), keys, sel_count, k, slot_state, rows, cap);
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
@@ -1440,23 +1447,12 @@ ssw_status launch_q6_build(const void *X, int32_t dtype, int64_t n, int32_t dim,
         SSW_HIP_TRY(hipMemsetAsync(err + np - 16, 0, 16 * sizeof(float), stream));
     }
     const dim3 grid((unsigned)std::min<int64_t>((n + 3) / 4, (int64_t)1 << 20)), block(256);
-    if (dtype == SSW_DTYPE_F16) {
-        const uint16_t *Xh = static_cast<const uint16_t *>(X);
-        switch (dim) {
-            case 256: hipLaunchKernelGGL(k_q6_build_h16<1>, grid, block, 0, stream, Xh, n, codes, scale, err); break;
-            case 512: hipLaunchKernelGGL(k_q6_build_h16<2>, grid, block, 0, stream, Xh, n, codes, scale, err); break;
-            case 768: hipLaunchKernelGGL(k_q6_build_h16<3>, grid, block, 0, stream, Xh, n, codes, scale, err); break;
-            default: hipLaunchKernelGGL(k_q6_build_h16<4>, grid, block, 0, stream, Xh, n, codes, scale, err); break;
-        }
-    } else {
-        const float *Xf = static_cast<const float *>(X);
-        switch (dim) {
-            case 256: hipLaunchKernelGGL(k_q6_build<1>, grid, block, 0, stream, Xf, n, codes, scale, err); break;
-            case 512: hipLaunchKernelGGL(k_q6_build<2>, grid, block, 0, stream, Xf, n, codes, scale, err); break;
-            case 768: hipLaunchKernelGGL(k_q6_build<3>, grid, block, 0, stream, Xf, n, codes, scale, err); break;
-            default: hipLaunchKernelGGL(k_q6_build<4>, grid, block, 0, stream, Xf, n, codes, scale, err); break;
-        }
-    }
+    dispatch_dim<true>(dim / 256, [&](auto c) {
+        if (dtype == SSW_DTYPE_F16)
+            hipLaunchKernelGGL(k_q6_build_h16<c.value>, grid, block, 0, stream, static_cast<const uint16_t *>(X), n, codes, scale, err);
+        else
+            hipLaunchKernelGGL(k_q6_build<c.value>, grid, block, 0, stream, static_cast<const float *>(X), n, codes, scale, err);
+    });
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
 }
@@ -1469,22 +1465,6 @@ ssw_status launch_q6_query(const float *q_dev, int32_t dim, unsigned *st, int8_t
     return SSW_OK;
 }
 
-static int q6_tiles(int C) {
-    int t = g_q6_tiles > 0 ? g_q6_tiles : q6_default_tiles(C);
-    while (t * C > 4) t >>= 1;  // two register sets of more than 12 KiB a wave do not fit beside the query operand
-    return t;
-}
-
-void q6_bounds_shape(int32_t dim, int device, int64_t n, int *out_blocks, int *out_tiles) {
-    const int T = q6_tiles(dim / 256);
-    const int64_t need = ((n + 16 * T - 1) / (16 * T) + 3) / 4;
-    int64_t grid = (int64_t)num_cus(device) * g_q6_blocks_per_cu;
-    if (grid > need) grid = need;
-    if (grid < 1) grid = 1;
-    *out_blocks = (int)grid;
-    *out_tiles = T;
-}
-
 ssw_status launch_q6_bounds(const unsigned char *codes, const float *scale, const float *err, const int8_t *planes,
                             const unsigned *st, float *scores, int64_t n, int32_t dim, int64_t *dbg_I, int device,
                             hipStream_t stream) {
@@ -1493,47 +1473,16 @@ ssw_status launch_q6_bounds(const unsigned char *codes, const float *scale, cons
         set_error("q6_bounds: dim=%d unsupported", dim);
         return SSW_ERR_UNSUPPORTED;
     }
-    const int C = dim / 256;
     int grid = 1, T = 1;
-    q6_bounds_shape(dim, device, n, &grid, &T);
+    scan_shape(SCAN_Q6, dim, device, n, &grid, &T);
     const u32x4 *cd = reinterpret_cast<const u32x4 *>(codes), *pl = reinterpret_cast<const u32x4 *>(planes);
-#define SSW_Q6(C_, T_, D_)                                                                                           \
-    hipLaunchKernelGGL((k_q6_bounds<C_, T_, D_>), dim3((unsigned)grid), dim3(256), 0, stream, cd, scale, err, pl, st, \
-                       scores, n, dbg_I)
-#ifdef SSW_DEBUG_HOOKS
-#define SSW_Q6_T(C_, T_)             \
-    if (dbg_I) SSW_Q6(C_, T_, true); \
-    else SSW_Q6(C_, T_, false)
-    if (C == 1) {
-        if (T == 1) { SSW_Q6_T(1, 1); } else if (T == 2) { SSW_Q6_T(1, 2); } else { SSW_Q6_T(1, 4); }
-    } else if (C == 2) {
-        if (T == 1) { SSW_Q6_T(2, 1); } else { SSW_Q6_T(2, 2); }
-    } else if (C == 3) {
-        SSW_Q6_T(3, 1);
-    } else {
-        SSW_Q6_T(4, 1);
-    }
-#undef SSW_Q6_T
-#else
-    (void)T;
-    switch (C) {
-        case 1: SSW_Q6(1, q6_default_tiles(1), false); break;
-        case 2: SSW_Q6(2, q6_default_tiles(2), false); break;
-        case 3: SSW_Q6(3, q6_default_tiles(3), false); break;
-        default: SSW_Q6(4, q6_default_tiles(4), false); break;
-    }
-#endif
-#undef SSW_Q6
+    dispatch_scan<SCAN_Q6>(dim / 256, T, dbg_I != nullptr, [&](auto c, auto t, auto d) {
+        hipLaunchKernelGGL((k_q6_bounds<c.value, t.value, d.value>), dim3((unsigned)grid), dim3(256), 0, stream, cd, scale, err,
+                           pl, st, scores, n, dbg_I);
+    });
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
 }
-
-#ifdef SSW_DEBUG_HOOKS
-void tune_q6_bounds(int blocks_per_cu, int tiles) {
-    g_q6_blocks_per_cu = blocks_per_cu >= 1 && blocks_per_cu <= 8 ? blocks_per_cu : Q6_BLOCKS_PER_CU;
-    g_q6_tiles = tiles == 1 || tiles == 2 || tiles == 4 ? tiles : 0;
-}
-#endif
 
 // ---- a chunk of up to 16 queries on the 6-bit shadow ------------------------------------------------------------------
 // planes: q8_mq_plane_bytes(dim), the int8 chunk's buffer
@@ -1544,22 +1493,6 @@ ssw_status launch_q6_query_mq(const float *qb_dev, int32_t dim, int32_t w, unsig
     return SSW_OK;
 }
 
-static int q6mq_tiles(int C) {
-    int t = g_q6mq_tiles > 0 ? g_q6mq_tiles : q6mq_default_tiles(C);
-    while (t * C > 4) t >>= 1;  // two register sets of more than 12 KiB a wave do not fit beside the query planes
-    return t;
-}
-
-void q6_bounds_mq_shape(int32_t dim, int device, int64_t n, int *out_blocks, int *out_tiles) {
-    const int T = q6mq_tiles(dim / 256);
-    const int64_t need = ((n + 16 * T - 1) / (16 * T) + 3) / 4;
-    int64_t grid = (int64_t)num_cus(device) * g_q6mq_blocks_per_cu;
-    if (grid > need) grid = need;
-    if (grid < 1) grid = 1;
-    *out_blocks = (int)grid;
-    *out_tiles = T;
-}
-
 ssw_status launch_q6_bounds_mq(const unsigned char *codes, const float *scale, const float *err, const int8_t *planes,
                                const unsigned *mq, int32_t w, float *side, int64_t stride, float *own, int64_t n,
                                int32_t dim, int64_t *dbg_I, int device, hipStream_t stream) {
@@ -1568,59 +1501,13 @@ ssw_status launch_q6_bounds_mq(const unsigned char *codes, const float *scale, c
         set_error("q6_bounds_mq: dim=%d, w=%d unsupported", dim, w);
         return SSW_ERR_UNSUPPORTED;
     }
-    const int C = dim / 256;
     int grid = 1, T = 1;
-    q6_bounds_mq_shape(dim, device, n, &grid, &T);
+    scan_shape(SCAN_Q6_MQ, dim, device, n, &grid, &T);
     const u32x4 *cd = reinterpret_cast<const u32x4 *>(codes), *pl = reinterpret_cast<const u32x4 *>(planes);
-#define SSW_Q6MQ(C_, T_, D_)                                                                                           \
-    hipLaunchKernelGGL((k_q6_bounds_mq<C_, T_, D_>), dim3((unsigned)grid), dim3(256), 0, stream, cd, scale, err, pl, mq, \
-                       (int)w, side, stride, own, n, dbg_I)
-#ifdef SSW_DEBUG_HOOKS
-#define SSW_Q6MQ_T(C_, T_)             \
-    if (dbg_I) SSW_Q6MQ(C_, T_, true); \
-    else SSW_Q6MQ(C_, T_, false)
-    if (C == 1) {
-        if (T == 1) { SSW_Q6MQ_T(1, 1); } else if (T == 2) { SSW_Q6MQ_T(1, 2); } else { SSW_Q6MQ_T(1, 4); }
-    } else if (C == 2) {
-        if (T == 1) { SSW_Q6MQ_T(2, 1); } else { SSW_Q6MQ_T(2, 2); }
-    } else if (C == 3) {
-        SSW_Q6MQ_T(3, 1);
-    } else {
-        SSW_Q6MQ_T(4, 1);
-    }
-#undef SSW_Q6MQ_T
-#else
-    (void)T;
-    switch (C) {
-        case 1: SSW_Q6MQ(1, q6mq_default_tiles(1), false); break;
-        case 2: SSW_Q6MQ(2, q6mq_default_tiles(2), false); break;
-        case 3: SSW_Q6MQ(3, q6mq_default_tiles(3), false); break;
-        default: SSW_Q6MQ(4, q6mq_default_tiles(4), false); break;
-    }
-#endif
-#undef SSW_Q6MQ
-    SSW_HIP_TRY(hipGetLastError());
-    return SSW_OK;
-}
-
-#ifdef SSW_DEBUG_HOOKS
-void tune_q6_bounds_mq(int blocks_per_cu, int tiles) {
-    g_q6mq_blocks_per_cu = blocks_per_cu >= 1 && blocks_per_cu <= 8 ? blocks_per_cu : Q6MQ_BLOCKS_PER_CU;
-    g_q6mq_tiles = tiles == 1 || tiles == 2 || tiles == 4 ? tiles : 0;
-}
-#endif
-
-// k_survivors_mq with the 6-bit shadow's code norm, then the answer of the one slot into host_block[1]
-ssw_status launch_survivors_q6(const float *lb, const float *err, const float *scale, const unsigned *mx, int64_t n, int32_t dim,
-                               const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *st, int64_t *rows,
-                               int64_t cap, int32_t *host_block, unsigned seq, int device, hipStream_t stream) {
-    int64_t grid = (int64_t)num_cus(device) * 4;
-    const int64_t need = (n + 1023) / 1024;  // four rows a lane
-    if (grid > need) grid = need;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(k_survivors_mq, dim3((unsigned)grid), dim3(256), 0, stream, lb, err, scale, mx, n, q6_code_norm(dim),
-                       keys, sel_count, k, st, rows, cap);
-    hipLaunchKernelGGL(k_prune_publish_mq, dim3(1), dim3(64), 0, stream, st, 1, cap, host_block, seq);
+    dispatch_scan<SCAN_Q6_MQ>(dim / 256, T, dbg_I != nullptr, [&](auto c, auto t, auto d) {
+        hipLaunchKernelGGL((k_q6_bounds_mq<c.value, t.value, d.value>), dim3((unsigned)grid), dim3(256), 0, stream, cd, scale,
+                           err, pl, mq, (int)w, side, stride, own, n, dbg_I);
+    });
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
 }

@@ -172,10 +172,10 @@ ssw_status launch_scan_batch(const void *X, int32_t dtype, const float *qb_dev, 
 bool q8_dim_supported(int32_t dim);
 // the dims of the packed 6-bit shadow's builders and scans: those of the int8 shadow and 768, which has no int8 shadow
 bool q6_dim_supported(int32_t dim);
-ssw_status launch_q8_build(const void *X, int32_t dtype, int64_t n, int32_t dim, int8_t *codes, float *scale,
+ssw_status launch_q8_build(const void *X, int32_t dtype, int64_t n, int32_t dim, unsigned char *codes, float *scale,
                            float *err, hipStream_t stream);
 ssw_status launch_q8_query(const float *q_dev, int32_t dim, float *q_keep, unsigned *state, hipStream_t stream);
-ssw_status launch_q8_bounds(const int8_t *codes, const float *scale, const float *err, const float *q_dev,
+ssw_status launch_q8_bounds(const unsigned char *codes, const float *scale, const float *err, const float *q_dev,
                             const unsigned *state, float *scores, int64_t n, int32_t dim, int device, hipStream_t stream);
 // mx[0], mx[1] = the largest finite a_r and s_r of a shadow (float bits): what the survivor passes pre-test lb with
 constexpr int SHADOW_MAX_WORDS = 2;
@@ -193,7 +193,7 @@ constexpr int Q8_MQ_WIDTH = 16, Q8_MQ_WORDS = 8;
 size_t q8_mq_plane_bytes(int32_t dim);
 ssw_status launch_q8_query_mq(const float *qb_dev, int32_t dim, int32_t w, unsigned *mq, int8_t *planes, float *q_last,
                               hipStream_t stream);
-ssw_status launch_q8_bounds_mq(const int8_t *codes, const float *scale, const float *err, const int8_t *planes,
+ssw_status launch_q8_bounds_mq(const unsigned char *codes, const float *scale, const float *err, const int8_t *planes,
                                const unsigned *mq, int32_t w, float *side, int64_t stride, float *own, int64_t n,
                                int32_t dim, int32_t *dbg_hi, int32_t *dbg_lo, int device, hipStream_t stream);
 // six: lb, err, scale and mx are the 6-bit shadow's (launch_q6_bounds_mq), else the int8 shadow's
@@ -212,8 +212,10 @@ ssw_status launch_rescore_survivors(const void *X, int32_t dtype, const float *q
                                     int64_t stride, float *own, int64_t n, int32_t dim, int device, hipStream_t stream);
 int rescore_survivors_waves(int device, int64_t cap);
 ssw_status launch_mark_uncertified(const unsigned *slot_state, int64_t cap, uint64_t *msg_last_word, hipStream_t stream);
-// blocks and 16-row tiles per request of the launch launch_q8_bounds_mq would make
-void q8_bounds_mq_shape(int32_t dim, int device, int64_t n, int *out_blocks, int *out_tiles);
+// the three tile scans on the int8 matrix core: launch_q8_bounds_mq, launch_q6_bounds, launch_q6_bounds_mq; scan_shape:
+// blocks and 16-row tiles per request of the launch the scan's launcher would make
+enum TileScan { SCAN_Q8_MQ, SCAN_Q6, SCAN_Q6_MQ };
+void scan_shape(TileScan scan, int32_t dim, int device, int64_t n, int *out_blocks, int *out_tiles);
 // the packed 6-bit shadow of f32 or f16 rows (prune.hip, "6-bit shadow"): tiles of 16 rows, 3 dim / 4 bytes a row, buffers
 // padded to whole tiles.  q6_slot / q6_element / q6_word_offset are the ONE placement of an element's code: k-step u, lane
 // group g (the lane of row r is 16 g + r % 16) and slot j of the lane's 16 codes of that k-step; slot j < 12 is the upper
@@ -236,10 +238,6 @@ ssw_status launch_q6_query(const float *q_dev, int32_t dim, unsigned *st, int8_t
 ssw_status launch_q6_bounds(const unsigned char *codes, const float *scale, const float *err, const int8_t *planes,
                             const unsigned *st, float *scores, int64_t n, int32_t dim, int64_t *dbg_I, int device,
                             hipStream_t stream);
-void q6_bounds_shape(int32_t dim, int device, int64_t n, int *out_blocks, int *out_tiles);
-ssw_status launch_survivors_q6(const float *lb, const float *err, const float *scale, const unsigned *mx, int64_t n, int32_t dim,
-                               const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *st, int64_t *rows,
-                               int64_t cap, int32_t *host_block, unsigned seq, int device, hipStream_t stream);
 // the chunk of w <= 16 queries on the 6-bit shadow (prune.hip): mq and planes are the int8 chunk's buffers
 // (q8_mq_plane_bytes), the slabs launch_q8_bounds_mq's; dbg_I (lab hook only, else NULL): [w, n] the exact integer sums
 ssw_status launch_q6_query_mq(const float *qb_dev, int32_t dim, int32_t w, unsigned *mq, int8_t *planes, float *q_last,
@@ -247,7 +245,6 @@ ssw_status launch_q6_query_mq(const float *qb_dev, int32_t dim, int32_t w, unsig
 ssw_status launch_q6_bounds_mq(const unsigned char *codes, const float *scale, const float *err, const int8_t *planes,
                                const unsigned *mq, int32_t w, float *side, int64_t stride, float *own, int64_t n,
                                int32_t dim, int64_t *dbg_I, int device, hipStream_t stream);
-void q6_bounds_mq_shape(int32_t dim, int device, int64_t n, int *out_blocks, int *out_tiles);
 // rows between natural order and the index.  to_h16: n rows of natural-order f32 (src_f32) or binary16 (src_h16, the
 // other NULL) -> rows [0, n) of dst in the f16 layout, rounded to nearest even.  gather: rows (rows_or_null[i], or
 // first_row + i when it is NULL) of an index matrix of element type dtype -> n natural-order f32 rows of out.
@@ -259,9 +256,7 @@ ssw_status launch_gather_rows(const void *X, int32_t dtype, const int64_t *rows_
 void tune_scan(int variant, int blocks_per_cu);
 void tune_scan_batch(int max_width, int blocks_per_cu);
 void tune_q8_bounds(int blocks_per_cu, int group_loads);
-void tune_q8_bounds_mq(int blocks_per_cu, int tiles);
-void tune_q6_bounds(int blocks_per_cu, int tiles);
-void tune_q6_bounds_mq(int blocks_per_cu, int tiles);
+void tune_tile_scan(TileScan scan, int blocks_per_cu, int tiles);
 #endif
 // knn.hip's last stage (lives in scan.hip to share the scan's summation order)
 ssw_status launch_knn_rescore(const float *X, int32_t dim, const int32_t *perm, int r0, int rows, const uint64_t *buf,

@@ -283,7 +283,7 @@ def test_non_finite_query_takes_the_full_scan(six):
 
 
 def test_product_threshold(lab_build):
-    """the default constants: an index of PRUNE6_MIN_ROWS rows filled on the device is pruned on the 6-bit shadow
+    """the default constants: an index of MIN_ROWS (6-bit single call, f32) rows filled on the device is pruned on the 6-bit shadow
     without a fallback and answers with the full scan's bits"""
     from seesaw_amd.device_index import DeviceIndex
     n = 1 << 24

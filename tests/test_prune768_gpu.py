@@ -28,7 +28,7 @@ pytestmark = pytest.mark.gpu
 
 SURV_CAP = 1 << 18
 DTYPES = [np.float32, np.float16]
-# the product's constants (csrc/index_prune.hip): PRUNE6_MIN_ROWS_768 / _F16 and PRUNE6_BATCH_MIN_ROWS_768 / _F16
+# the product's constants (csrc/index_prune.hip): MIN_ROWS of the 6-bit single call and of the 6-bit batch at dim 768
 MIN_ROWS_768 = {np.float32: 1 << 20, np.float16: 1 << 20}
 BATCH_MIN_ROWS_768 = {np.float32: 1 << 20, np.float16: 1 << 20}
 
@@ -435,10 +435,47 @@ def test_queries_that_cannot_be_bounded(six, dtype):
         idx.close()
 
 
+@pytest.mark.parametrize("dim", [DIM, 256])
+def test_the_6bit_shadow_refused_for_memory(lab_build, dim):
+    """no shadow fits beside the reserve: the call is the full scan, nothing is built, and the refusal holds until the
+    rows change, at the dim without an int8 shadow and at one that has it.  The first two words of the report are the
+    product's own at this state: at dim 768 the 6-bit shadow's refusal on an eligible index, at dim 256 the untouched
+    int8 shadow's "none", on an index of too few rows for it.  The three-launch top-k of small indexes is switched off
+    (ssw_tune_topk(2)): it never reaches the pre-scan."""
+    import ctypes
+    from seesaw_amd import _lib
+    n = 16 * 40 + 5  # more than one block of tiles, the last tile ragged
+    X = np.random.default_rng(dim).standard_normal((n, dim)).astype(np.float32) / np.float32(np.sqrt(dim))
+    q = query(1, dim)
+    refused = [3, 1] if dim == DIM else [0, 0]
+    idx = make(X, np.float32)
+    try:
+        _lib.call("ssw_tune_topk", 2)
+        full = unpruned(lab_build, lambda: idx.topk(q, 10))
+        mode6(True, 1)
+        mode(lab_build, True, reserve=1 << 60)
+        same(full, idx.topk(q, 10))
+        st = stats(idx)
+        assert list(st[:2]) == refused and st[3] == 0 and st[5] == 0, st
+        mode(lab_build, True)  # the reserve is the product's again, the refusal stands
+        same(full, idx.topk(q, 10))
+        st = stats(idx)
+        assert list(st[:2]) == refused and st[3] == 0 and st[5] == 0, st
+        _lib.call("ssw_index_upload", idx._h, ctypes.c_void_p(X.ctypes.data), 0, n)  # the same rows, changed
+        same(full, idx.topk(q, 10))
+        st = stats(idx)
+        assert list(st[:2]) == [1, 1] and st[3] == 1 and st[5] == shadow_bytes(n, dim), st
+    finally:
+        mode6(True, -1)
+        mode(lab_build, True)
+        _lib.call("ssw_tune_topk", 3)
+        idx.close()
+
+
 # ---- 8. the product's thresholds, without the lab switches ------------------------------------------------------------
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_product_threshold(lab_build, dtype):
-    """an index of PRUNE6_MIN_ROWS_768 (float16: _F16) rows filled on the device is pruned on the 6-bit shadow, single
+    """an index of MIN_ROWS (6-bit single call, dim 768, f32; float16: f16) rows filled on the device is pruned on the 6-bit shadow, single
     query and batch (the batch's constants are the same), and answers with the full scan's keys; one row fewer is not
     eligible: its single query is the full scan and, with no int8 fallback, its pruned batch is the plain batch"""
     from seesaw_amd.device_index import DeviceIndex

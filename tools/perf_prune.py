@@ -14,7 +14,7 @@ query.  Prints per size: host wall ms per call (median, and the spread min .. ma
 both forms returned the same images, scores and best rows.  This mode keeps every index on the int8 shadow at every size
 (ssw_tune_prune6(0)).
 
---three-way (how PRUNE6_MIN_ROWS and, with --dtype float16, PRUNE6_MIN_ROWS_F16 of csrc/index_prune.hip are chosen):
+--three-way (how MIN_ROWS (6-bit single call, f32) and, with --dtype float16, MIN_ROWS (6-bit single call, f16) of csrc/index_prune.hip are chosen):
 full scan / int8 shadow / packed 6-bit shadow in turn in one process, two warm-up rounds, then 20 rounds, each a
 different query; per size one JSON line with the median and the spread (max - min) of the host wall ms of each form, the
 6-bit survivors, whether all three returned the same bytes, and under "shadows" which shadow each form's first call
@@ -22,7 +22,7 @@ built, from the growth of prune_stats' shadow_bytes ("none", "int8" or "6-bit"; 
 its name says ends the run).  Where the two shadows do not fit beside the rows together, the int8 rounds and the 6-bit
 rounds run one after the other on two indexes of the same rows, each alternating with the full scan.
 
---dim D (default 512): the width of the index.  --dim 768 (how PRUNE6_MIN_ROWS_768 and PRUNE6_MIN_ROWS_768_F16 are
+--dim D (default 512): the width of the index.  --dim 768 (how MIN_ROWS (6-bit single call, dim 768, f32) and MIN_ROWS (6-bit single call, dim 768, f16) are
 chosen): that dim has the 6-bit shadow alone, so the run is always the rounds of --three-way with two forms, full scan /
 packed 6-bit shadow, and the JSON line has no int8 column; it carries "dim".  Every other dim prints what it printed
 before the option existed."""
