@@ -385,6 +385,31 @@ ssw_status ssw_topk_merge_msgs_batch_dev(int32_t device, void *hip_stream, const
                                          uint64_t *dev_keys_out, int32_t *dev_counts_out, int64_t *dev_flags_or_null,
                                          int64_t *dev_flags_seen_or_null);
 
+/* The SECOND STAGE of the sharded chunk, for the avg_score aggregation (rescore_candidates, multiscale_index.py:379-403):
+ * every merged candidate is aggregated on the rank that holds its tiles, in ONE launch for the group's nq queries
+ * (k_avg_score_owner, csrc/rescore.hip; DESIGN.md section 4, "Sharded batch: second stage").  dev_keys [nq, k_max] and
+ * dev_counts [nq] are what ssw_topk_merge_msgs_batch_dev wrote: the low word of a key holds 0xFFFFFFFF - the GLOBAL
+ * image position.  This handle's images are the positions [image_offset, image_offset + n_images) and its rows start at
+ * row_offset of the whole index.  For query b and slot c < k: if c < dev_counts[b] and the image is this handle's, its
+ * tiles are scored for q_host[b] straight from the index rows -- the bits of ssw_index_scan -- and aggregated as
+ * ssw_index_rescore_avg aggregates them (aug_larger: its codes, 0 / 1 / 2, optionally + 4);
+ *   dev_out[b][0][c] = 1 << 32 | the f32 bits of the aggregated score (the owned bit is apart: the score may be NaN),
+ *   dev_out[b][1][c] = row_offset + the image's first tile with that score (i64);
+ * otherwise both words are 0.  dev_out is [nq, 2, k_max] u64; every c < k is written, c >= k is left as it was.  Over
+ * all ranks every (b, c < dev_counts[b]) has exactly one owner.
+ * ENQUEUES ONLY, on the handle's stream: it waits for the device only where a staging block is reused (the query block,
+ * which holds 16 queries; a longer batch is served in parts).  Refused before anything is enqueued: NULL arguments,
+ * nq < 1, k outside [1, k_max], k_max > SSW_MAX_TOPK, a bad aug_larger, no image map or tile meta, an image of more than
+ * 2048 tiles anywhere in the index (SSW_ERR_INVALID); a non-finite query (SSW_ERR_NUMERIC); dim other than 256 / 512 /
+ * 768 / 1024 (SSW_ERR_UNSUPPORTED).
+ * State afterwards is the state before: the kernel reads the rows, the tile meta and the image map and nothing else,
+ * so the score buffer (partial or complete, with its kept query), the result buffers, the installed exclusion set and
+ * the counters of ssw_index_prune_stats / ssw_index_prune_completions stay as they were -- it follows the plain and the
+ * pruned first stage alike and never causes a completing full scan. */
+ssw_status ssw_index_stage2_avg_batch_dev(ssw_index *idx, const float *q_host, int32_t nq, const uint64_t *dev_keys,
+                                          const int32_t *dev_counts, int32_t k_max, int32_t k, int32_t aug_larger,
+                                          int64_t image_offset, int64_t row_offset, uint64_t *dev_out);
+
 /* The collective itself (`ssw_topk_allgather(ssw_comm *, ...)`): RCCL bound at run time (dlopen; the
  * copy torch mapped, if any).  ssw_comm_unique_id on one rank -> 128 bytes handed to every rank by the caller's own
  * means -> ssw_comm_create on every rank (collective).  ssw_topk_allgather enqueues ncclAllGather of msg_len u64 words

@@ -152,6 +152,8 @@ _SIGNATURES = {
     "ssw_index_prune_batch_dev_read": (c_i32, [c_void_p, c_i32_p, c_i32_p]),
     "ssw_topk_merge_msgs_batch_dev": (c_i32, [c_i32, c_void_p, c_void_p, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_void_p,
                                               c_void_p, c_void_p, c_void_p]),
+    "ssw_index_stage2_avg_batch_dev": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_i64,
+                                               c_i64, c_void_p]),
     "ssw_comm_unique_id": (c_i32, [c_void_p]),
     "ssw_comm_create": (c_i32, [c_i32, c_void_p, c_i32, c_i32, ctypes.POINTER(c_void_p)]),
     "ssw_comm_destroy": (c_i32, [c_void_p]),

@@ -128,9 +128,14 @@ static ssw_status candidate_geometry(const ssw_index *idx, const int64_t *image_
 }
 
 // the arguments of an avg_score aggregation over the index's tiles; `who` names the entry in the message
-ssw_status ssw::check_avg_args(const ssw_index *idx, int32_t aug_larger, const char *who) {
+ssw_status ssw::check_aug_code(int32_t aug_larger) {
     SSW_REQUIRE(aug_larger >= 0 && (aug_larger & 3) <= 2 && aug_larger <= 6,
                 "aug_larger=%d is not 0 (all), 1 (greater) or 2 (adjacent), optionally + 4 (aug_weight = cont_weighted)", aug_larger);
+    return SSW_OK;
+}
+
+ssw_status ssw::check_avg_args(const ssw_index *idx, int32_t aug_larger, const char *who) {
+    SSW_TRY(check_aug_code(aug_larger));
     SSW_REQUIRE(idx->has_map && idx->tile_boxes && idx->tile_zoom,
                 "%s needs ssw_index_set_row2image and ssw_index_set_tile_meta first", who);
     return SSW_OK;

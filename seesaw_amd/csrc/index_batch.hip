@@ -477,6 +477,55 @@ extern "C" ssw_status ssw_index_topk_slot_deep_dev(ssw_index *idx, const float *
     return do_select_deep(idx, idx->scores, k, dest, idx->stream);
 }
 
+// The second stage of a sharded batch on this handle (k_avg_score_owner, rescore.hip): the group's merged candidates are
+// aggregated where their tiles live, from the index rows alone.  It reads no score buffer, result buffer or prune state
+// and writes none, so it follows the plain and the pruned first stage alike and never completes a buffer.
+extern "C" ssw_status ssw_index_stage2_avg_batch_dev(ssw_index *idx, const float *q_host, int32_t nq,
+                                                     const uint64_t *dev_keys, const int32_t *dev_counts, int32_t k_max,
+                                                     int32_t k, int32_t aug_larger, int64_t image_offset,
+                                                     int64_t row_offset, uint64_t *dev_out) {
+    SSW_REQUIRE(nq >= 1, "nq=%d < 1", nq);
+    SSW_REQUIRE(k >= 1 && k <= k_max && k_max <= SSW_MAX_TOPK, "k=%d outside [1, k_max=%d], k_max at most %d", k, k_max,
+                SSW_MAX_TOPK);
+    SSW_TRY(check_aug_code(aug_larger));
+    SSW_REQUIRE(idx && q_host && dev_keys && dev_counts && dev_out, "NULL argument");
+    SSW_TRY(check_avg_args(idx, aug_larger, "stage2_avg_batch_dev"));
+    if (idx->dim != 256 && idx->dim != 512 && idx->dim != 768 && idx->dim != 1024) {
+        set_error("stage2_avg_batch_dev: dim=%d unsupported", idx->dim);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    const int64_t max_tiles = max_image_tiles(idx);
+    SSW_REQUIRE(max_tiles <= SSW_RESCORE_MAX_TILES,
+                "the index has an image with %lld tiles, more than the %d the kernel keeps in LDS", (long long)max_tiles,
+                SSW_RESCORE_MAX_TILES);
+    SSW_TRY(check_query_batch(idx, q_host, nq));
+    DeviceGuard guard(idx->device);
+    int W = 1;
+    SSW_TRY(batch_buffers(idx, 1, true, &W));  // the query block alone
+    if (!idx->batch.qb_dev) {
+        set_error("stage2_avg_batch_dev: no device memory for the query block");
+        return SSW_ERR_NOMEM;
+    }
+    const size_t dim = (size_t)idx->dim;
+    for (int32_t b = 0; b < nq; b += BATCH_MAX_WIDTH) {  // the block holds BATCH_MAX_WIDTH queries
+        const int32_t w = std::min<int32_t>(BATCH_MAX_WIDTH, nq - b);
+        SSW_TRY(idx->batch.qb_stage.push(idx->batch.qb_dev, q_host + b * dim, (size_t)w * dim * sizeof(float), idx->stream));
+        AvgOwnerArgs a;
+        a.qb = idx->batch.qb_dev;
+        a.boxes = idx->tile_boxes;
+        a.zoom = idx->tile_zoom;
+        a.row_start = idx->row_start;
+        a.n_images = idx->n_images;
+        a.keys = dev_keys + (size_t)b * k_max;
+        a.counts = dev_counts + b;
+        a.nq = w, a.k_max = k_max, a.k = k, a.max_tiles = (int32_t)max_tiles, a.aug = aug_larger;
+        a.image_offset = image_offset, a.row_offset = row_offset;
+        a.out = dev_out + (size_t)b * 2 * k_max;
+        SSW_TRY(launch_avg_score_owner(idx->X, idx->dtype, idx->dim, a, idx->stream));
+    }
+    return SSW_OK;
+}
+
 // the two-stage entries: the first stage plain or, `pruned`, from the certified pre-scan
 static ssw_status topk_batch_avg(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
                                  const int64_t *excluded_offsets, int32_t k, int32_t aug_larger, int64_t *out_images,

@@ -197,6 +197,7 @@ static ssw_status profiled(ssw_index *idx, F work) {
 // capi_index.hip
 ssw_status check_query(const ssw_index *idx, const float *q_host);
 ssw_status check_excluded(const ssw_index *idx, const int64_t *ids, int64_t first, int64_t last);
+ssw_status check_aug_code(int32_t aug_larger);
 ssw_status check_avg_args(const ssw_index *idx, int32_t aug_larger, const char *who);
 ssw_status launch_index_scan(ssw_index *idx, const float *q_dev, hipStream_t stream);
 ssw_status do_scan(ssw_index *idx, const float *q_dev);

@@ -22,10 +22,11 @@
 // aug_weight = 'cont_weighted' (bit 2 of `aug`): softmax-of-containment weights over all partners instead (f32 like
 // scipy.special.softmax on float32 input; the weighted sum runs in partner order, numpy's dot in BLAS order: 1e-6).
 // Explicitly rounded intrinsics keep the compiler from contracting w*h into the union's subtraction.
-#include "ssw_common.h"
+#include "rescore_rows.h"
 
 // Compiled with -ffp-contract=off (csrc/Makefile): results of this file are compared bit for bit with numpy /
 // scipy / torch, so every product and sum must round on its own (hipcc would contract a * b + c into an fma).
+// The row scoring k_avg_score_owner takes from rescore_rows.h asks for its fmas explicitly, so the flag leaves it alone.
 
 namespace ssw {
 namespace {
@@ -40,39 +41,72 @@ __device__ __forceinline__ float iou_f32(const float4 a, float area_a, const flo
     return __fdiv_rn(inter, uni);
 }
 
-// The aggregation of ONE image by one workgroup: its tiles are rows [r0, r0 + T), `scores` holds one value per index
-// row, minus_or_null (optional) one per tile of this image.  Writes out_score[c] / out_row[c].  Both entry kernels
-// below run it, so the arithmetic exists once.
-// ST = the dtype of the score column: float for the scan's scores (pandas' float32 group mean), double for the graph
-// loops, which hand rescore_candidates the label-propagation output as float64 (graph_based.py:100-108; pandas' float64
-// group mean is the same Kahan sum in f64).  IoUs are f32 either way (the boxes are).
+// The LDS of ONE image's aggregation: boxes, scores, aggregated scores, areas and zoom levels of its T tiles, and the
+// mask of the zoom levels present.  avg_score_lds_bytes sizes the dynamic part.
 template <typename ST>
-__device__ __forceinline__ void avg_score_of_image(const float4 *__restrict__ boxes, const int32_t *__restrict__ zoom,
-                                                   const ST *__restrict__ scores, const ST *__restrict__ minus_or_null,
-                                                   const int64_t r0, const int T, int aug, const int c,
-                                                   ST *__restrict__ out_score, int64_t *__restrict__ out_row) {
+struct AvgLds {
+    float4 *sbox;     // [T]
+    ST *sscore;       // [T]  (8-byte types first: the base is 16-byte aligned)
+    ST *sagg;         // [T]
+    float *sarea;     // [T]
+    int *szoom;       // [T]
+    unsigned *levels;
+};
+
+template <typename ST>
+__device__ __forceinline__ AvgLds<ST> avg_lds(const int T) {
     extern __shared__ float4 sh4[];
-    float4 *sbox = sh4;                                   // [T]
-    ST *sscore = reinterpret_cast<ST *>(sbox + T);        // [T]  (8-byte types first: the base is 16-byte aligned)
-    ST *sagg = sscore + T;                                // [T]
-    float *sarea = reinterpret_cast<float *>(sagg + T);   // [T]
-    int *szoom = reinterpret_cast<int *>(sarea + T);      // [T]
     __shared__ unsigned level_mask;
-    if (threadIdx.x == 0) level_mask = 0u;
+    AvgLds<ST> l;
+    l.sbox = sh4;
+    l.sscore = reinterpret_cast<ST *>(l.sbox + T);
+    l.sagg = l.sscore + T;
+    l.sarea = reinterpret_cast<float *>(l.sagg + T);
+    l.szoom = reinterpret_cast<int *>(l.sarea + T);
+    l.levels = &level_mask;
+    return l;
+}
+
+// First half, "fill LDS": the boxes, areas and zoom levels of the image's tiles (rows [r0, r0 + T)) and the level mask;
+// with SCORES also tile i's score, scores[r0 + i] minus minus_or_null[i] (optional, one per tile of this image).  A kernel
+// that computes the scores itself (k_avg_score_owner) stores them into sscore before it calls the second half.
+template <typename ST, bool SCORES>
+__device__ __forceinline__ void avg_score_fill(const AvgLds<ST> &l, const float4 *__restrict__ boxes,
+                                               const int32_t *__restrict__ zoom, const ST *__restrict__ scores,
+                                               const ST *__restrict__ minus_or_null, const int64_t r0, const int T) {
+    if (threadIdx.x == 0) *l.levels = 0u;
     __syncthreads();
     for (int i = threadIdx.x; i < T; i += RS_THREADS) {
         const float4 b = boxes[r0 + i];
-        sbox[i] = b;
-        sarea[i] = __fmul_rn(__fsub_rn(b.z, b.x), __fsub_rn(b.w, b.y));
-        ST s = scores[r0 + i];
-        if (minus_or_null) s = s - minus_or_null[i];
-        sscore[i] = s;
+        l.sbox[i] = b;
+        l.sarea[i] = __fmul_rn(__fsub_rn(b.z, b.x), __fsub_rn(b.w, b.y));
+        if constexpr (SCORES) {
+            ST s = scores[r0 + i];
+            if (minus_or_null) s = s - minus_or_null[i];
+            l.sscore[i] = s;
+        }
         const int z = zoom[r0 + i];
-        szoom[i] = z;
-        atomicOr(&level_mask, 1u << z);
+        l.szoom[i] = z;
+        atomicOr(l.levels, 1u << z);
     }
+}
+
+// Second half, "aggregate from LDS": the aggregation of ONE image by one workgroup over what the first half (and the
+// scores' writer) left in LDS -- it opens with the barrier that makes them visible.  Thread 0 ends with
+// out(aggregated score or NaN, the image's first tile with that score).  Every entry kernel below runs it, so the
+// arithmetic exists once.
+// ST = the dtype of the score column: float for the scan's scores (pandas' float32 group mean), double for the graph
+// loops, which hand rescore_candidates the label-propagation output as float64 (graph_based.py:100-108; pandas' float64
+// group mean is the same Kahan sum in f64).  IoUs are f32 either way (the boxes are).
+template <typename ST, class Out>
+__device__ __forceinline__ void avg_score_from_lds(const AvgLds<ST> &l, const int T, int aug, Out out) {
+    const float4 *sbox = l.sbox;
+    const ST *sscore = l.sscore;
+    ST *sagg = l.sagg;
+    const float *sarea = l.sarea;
+    const int *szoom = l.szoom;
     __syncthreads();
-    const unsigned levels = level_mask;
+    const unsigned levels = *l.levels;
     const bool cont_weighted = (aug & 4) != 0;
     aug &= 3;
     for (int i = threadIdx.x; i < T && cont_weighted; i += RS_THREADS) {
@@ -163,9 +197,22 @@ __device__ __forceinline__ void avg_score_of_image(const float4 *__restrict__ bo
                 bi = i;
             }
         }
-        out_score[c] = bi >= 0 ? bv : (ST)__builtin_nanf("");
-        out_row[c] = r0 + (bi >= 0 ? bi : 0);
+        out(bi >= 0 ? bv : (ST)__builtin_nanf(""), bi >= 0 ? bi : 0);
     }
+}
+
+// both halves over a score column: writes out_score[c] / out_row[c]
+template <typename ST>
+__device__ __forceinline__ void avg_score_of_image(const float4 *__restrict__ boxes, const int32_t *__restrict__ zoom,
+                                                   const ST *__restrict__ scores, const ST *__restrict__ minus_or_null,
+                                                   const int64_t r0, const int T, int aug, const int c,
+                                                   ST *__restrict__ out_score, int64_t *__restrict__ out_row) {
+    const AvgLds<ST> l = avg_lds<ST>(T);
+    avg_score_fill<ST, true>(l, boxes, zoom, scores, minus_or_null, r0, T);
+    avg_score_from_lds<ST>(l, T, aug, [&](ST score, int tile) {
+        out_score[c] = score;
+        out_row[c] = r0 + tile;
+    });
 }
 
 // boxes: x1, y1, x2, y2 per row.  cand_pos[c] = image position; its rows are [row_start[p], row_start[p+1]).
@@ -208,6 +255,54 @@ __global__ __launch_bounds__(RS_THREADS) void k_avg_score_keys(const float4 *__r
     const int64_t r0 = row_start[p];
     const int T = (int)(row_start[p + 1] - r0);
     avg_score_of_image<float>(boxes, zoom, scores, nullptr, r0, T, aug, c, out_score, out_row);
+}
+
+// The second stage of a sharded batch on the rank that OWNS the image ("Sharded batch: second
+// stage").  grid (k, nq): workgroup (c, b) takes merged key c of query b (keys [nq, k_max] / counts [nq] as the batched
+// merge wrote them; the low word holds 0xFFFFFFFF - the GLOBAL image position).  This handle's images are the positions
+// [image_offset, image_offset + n_images).  An image of another rank, or a slot past the count, stores two zero words and
+// touches nothing else.  An owned one needs no score buffer: wave w scores tiles w, w + 4, ... straight from the index
+// rows into sscore, two rows in flight -- the scan's bits (rescore_rows.h) -- and the aggregation above does the rest.
+// out [nq, 2, k_max]: [b, 0, c] = 1 << 32 | the f32 bits of the aggregated score (the owned bit is apart because the
+// score may be NaN), [b, 1, c] = row_offset + the best tile's row.
+template <class R, int C>
+__global__ __launch_bounds__(RS_THREADS) void k_avg_score_owner(
+    const typename R::T *__restrict__ X, const float *__restrict__ qb, const float4 *__restrict__ boxes,
+    const int32_t *__restrict__ zoom, const int64_t *__restrict__ row_start, int64_t n_images,
+    const uint64_t *__restrict__ keys, const int32_t *__restrict__ counts, int k_max, int aug, int64_t image_offset,
+    int64_t row_offset, unsigned long long *__restrict__ out) {
+    const int c = blockIdx.x, b = blockIdx.y;
+    unsigned long long *o = out + (size_t)b * 2 * k_max;
+    int64_t p = -1;
+    if (c < counts[b])
+        p = (int64_t)(0xffffffffu - (uint32_t)(keys[(size_t)b * k_max + c] & 0xffffffffull)) - image_offset;
+    if (p < 0 || p >= n_images) {  // not owned: before any row, box or row_start access
+        if (threadIdx.x == 0) o[c] = o[k_max + c] = 0ull;
+        return;
+    }
+    const int64_t r0 = row_start[p];
+    const int T = (int)(row_start[p + 1] - r0);
+    const AvgLds<float> l = avg_lds<float>(T);
+    avg_score_fill<float, false>(l, boxes, zoom, nullptr, nullptr, r0, T);
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const rows::Frag<C> qf = rows::load_query<C>(qb + (size_t)b * (C * 256), lane);
+    for (int i = w; i < T; i += 2 * (RS_THREADS / 64)) {
+        const int i1 = i + RS_THREADS / 64;
+        const bool two = i1 < T;
+        const rows::Frag<C> x0 = R::template load<C>(X, r0 + i, lane);
+        const rows::Frag<C> x1 = R::template load<C>(X, r0 + (two ? i1 : i), lane);
+        const float v0 = rows::wave_sum(rows::lane_partial<C>(x0, qf));
+        const float v1 = rows::wave_sum(rows::lane_partial<C>(x1, qf));
+        if (lane == 0) {
+            l.sscore[i] = v0;
+            if (two) l.sscore[i1] = v1;
+        }
+    }
+    avg_score_from_lds<float>(l, T, aug, [&](float score, int tile) {
+        o[c] = (1ull << 32) | (unsigned long long)__float_as_uint(score);
+        o[k_max + c] = (unsigned long long)(row_offset + r0 + tile);
+    });
 }
 
 // The rows the aggregation above is about to read, as a list the gather scoring can take: candidate c's tiles at
@@ -293,6 +388,34 @@ ssw_status launch_avg_score_keys(const float *boxes, const int32_t *zoom, const 
                        out_score, out_row);
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
+}
+
+template <class R, int C>
+static ssw_status launch_avg_score_owner_t(const void *X, const AvgOwnerArgs &a, hipStream_t stream) {
+    size_t lds = 0;
+    SSW_TRY(avg_score_lds(reinterpret_cast<const void *>(k_avg_score_owner<R, C>), a.max_tiles, sizeof(float), &lds));
+    hipLaunchKernelGGL((k_avg_score_owner<R, C>), dim3((unsigned)a.k, (unsigned)a.nq), dim3(RS_THREADS), lds, stream,
+                       static_cast<const typename R::T *>(X), a.qb, reinterpret_cast<const float4 *>(a.boxes), a.zoom,
+                       a.row_start, a.n_images, a.keys, a.counts, (int)a.k_max, (int)a.aug, a.image_offset, a.row_offset,
+                       reinterpret_cast<unsigned long long *>(a.out));
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+ssw_status launch_avg_score_owner(const void *X, int32_t dtype, int32_t dim, const AvgOwnerArgs &a, hipStream_t stream) {
+    if (a.nq <= 0 || a.k <= 0) return SSW_OK;
+    const bool h16 = dtype == SSW_DTYPE_F16;
+#define SSW_AVG_OWNER(C) \
+    return h16 ? launch_avg_score_owner_t<rows::H16Rows, C>(X, a, stream) : launch_avg_score_owner_t<rows::F32Rows, C>(X, a, stream)
+    switch (dim) {
+        case 256: SSW_AVG_OWNER(1);
+        case 512: SSW_AVG_OWNER(2);
+        case 768: SSW_AVG_OWNER(3);
+        case 1024: SSW_AVG_OWNER(4);
+    }
+#undef SSW_AVG_OWNER
+    set_error("avg_score_owner: dim=%d unsupported", dim);
+    return SSW_ERR_UNSUPPORTED;
 }
 
 ssw_status launch_candidate_tiles(const int64_t *row_start, const int64_t *cand_pos, const int64_t *cand_off, int32_t m,

@@ -6,76 +6,14 @@
 // survivor list and store each exact score straight into the slot's slab.  A slot whose certificate failed is left as it
 // is -- lower bounds -- and k_mark_uncertified says so in the slot's exchange message.
 //
-// The score is the BITS of scan.hip's kernels, whose summation order is restated here (scan.hip itself stays as
-// measured): lane l holds the float4 at element 256 c + 4 l of chunk c < C = dim / 256; two packed fma chains, over
-// .x/.y and then .z/.w, c ascending, from +0; the lane partial is a.x + a.y; the 64 partials are summed by the butterfly
-// v + shfl_xor(v, off), off = 1, 2, 4, 8, 16, 32.  An f16 row (ssw_common.h: lane l's 4 C elements are the 8 C bytes at
-// l * 8 C) is widened exactly first.
-#include "ssw_common.h"
+// The score is the BITS of scan.hip's kernels: the row loads and the summation order are rescore_rows.h's.
+#include "rescore_rows.h"
 
 namespace ssw {
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-template <int C>
-struct Frag {
-    float4 v[C];
-};
-
-struct F32Rows {
-    typedef float T;
-    template <int C>
-    static __device__ __forceinline__ Frag<C> load(const float *__restrict__ X, int64_t row, int lane) {
-        Frag<C> r;
-        const float4 *p = reinterpret_cast<const float4 *>(X) + row * (C * 64) + lane;
-#pragma unroll
-        for (int c = 0; c < C; ++c) r.v[c] = p[c * 64];
-        return r;
-    }
-};
-
-struct H16Rows {
-    typedef uint16_t T;
-    template <int C>
-    static __device__ __forceinline__ Frag<C> load(const uint16_t *__restrict__ X, int64_t row, int lane) {
-        Frag<C> r;
-        const unsigned char *p = reinterpret_cast<const unsigned char *>(X) + row * (C * 512) + lane * (C * 8);
-        if constexpr (C % 2 == 0) {  // 16-byte aligned: one dwordx4 per two chunks
-            const u32x4 *p4 = reinterpret_cast<const u32x4 *>(p);
-#pragma unroll
-            for (int i = 0; i < C / 2; ++i) {
-                const u32x4 w = p4[i];
-                r.v[2 * i] = widen_h16x4(u32x2{w.x, w.y});
-                r.v[2 * i + 1] = widen_h16x4(u32x2{w.z, w.w});
-            }
-        } else {
-            const u32x2 *p2 = reinterpret_cast<const u32x2 *>(p);
-#pragma unroll
-            for (int c = 0; c < C; ++c) r.v[c] = widen_h16x4(p2[c]);
-        }
-        return r;
-    }
-};
-
-// the lane partial: scan.hip's dot_frag
-template <int C>
-__device__ __forceinline__ float lane_partial(const Frag<C> &x, const Frag<C> &q) {
-    f32x2 a = {0.0f, 0.0f};
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        a = __builtin_elementwise_fma(f32x2{x.v[c].x, x.v[c].y}, f32x2{q.v[c].x, q.v[c].y}, a);
-        a = __builtin_elementwise_fma(f32x2{x.v[c].z, x.v[c].w}, f32x2{q.v[c].z, q.v[c].w}, a);
-    }
-    return a.x + a.y;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) v = v + __shfl_xor(v, off, 64);
-    return v;
-}
+using namespace rows;
 
 constexpr int RESCORE_BLOCKS_PER_CU = 1;  // four-wave blocks per CU and slot; a chunk of 16 slots is 16 of them a CU
 constexpr int RESCORE_IN_FLIGHT = 2;      // rows a wave has requested before it reduces the first
@@ -99,9 +37,7 @@ __global__ __launch_bounds__(256) void k_rescore_survivors(const typename R::T *
     if (gwave >= m) return;
     const int64_t *rows = lists + (int64_t)j * list_stride;
     float *slab = j + 1 < w ? side + (int64_t)j * stride : own;
-    Frag<C> qf;
-#pragma unroll
-    for (int c = 0; c < C; ++c) qf.v[c] = reinterpret_cast<const float4 *>(qb + (int64_t)j * (C * 256))[c * 64 + lane];
+    const Frag<C> qf = load_query<C>(qb + (int64_t)j * (C * 256), lane);
     for (int64_t i = gwave; i < m; i += RESCORE_IN_FLIGHT * nwaves) {
         const int64_t i1 = i + nwaves;
         const bool two = i1 < m;

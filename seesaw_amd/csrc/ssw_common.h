@@ -446,6 +446,24 @@ ssw_status launch_avg_score(const float *boxes, const int32_t *zoom, const float
 ssw_status launch_avg_score_keys(const float *boxes, const int32_t *zoom, const float *scores, const int64_t *row_start,
                                  int64_t n_images, const uint64_t *keys, const int32_t *count, int32_t k,
                                  int32_t max_tiles, int32_t aug, float *out_score, int64_t *out_row, hipStream_t stream);
+// the same aggregation on the owners of a sharded batch's merged candidates (k_avg_score_owner): grid (k, nq); workgroup
+// (c, b) decodes the GLOBAL image position of keys[b * k_max + c] (c < counts[b]), and if this index holds it -- the
+// positions [image_offset, image_offset + n_images) -- scores the image's tiles for query qb + b * dim straight from the
+// rows X (launch_scan's bits) and aggregates them.  out [nq, 2, k_max] u64: [b, 0, c] = 1 << 32 | f32 bits of the score,
+// [b, 1, c] = row_offset + the best tile's row; both 0 where the image is not this index's.  Every c < k is written.
+struct AvgOwnerArgs {
+    const float *qb;  // [nq, dim] device
+    const float *boxes;
+    const int32_t *zoom;
+    const int64_t *row_start;
+    int64_t n_images;
+    const uint64_t *keys;
+    const int32_t *counts;
+    int32_t nq, k_max, k, max_tiles, aug;
+    int64_t image_offset, row_offset;
+    uint64_t *out;
+};
+ssw_status launch_avg_score_owner(const void *X, int32_t dtype, int32_t dim, const AvgOwnerArgs &args, hipStream_t stream);
 // the rows those two launches read, as row lists for launch_score_rows: candidate c's tiles at rows_out[cand_off[c] ..)
 // (the candidates' tile total entries); slot c's at rows_out[c * max_tiles ..), padded with rows of the index to
 // k * max_tiles entries in all

@@ -365,6 +365,21 @@ class DeviceIndex:
         _lib.call("ssw_index_topk_batch_dev_pruned" if prune else "ssw_index_topk_batch_dev", self._h, _ptr(Q), nq,
                   _ptr(ids), _ptr(offsets), int(k), int(first_slot))
 
+    def stage2_avg_batch_dev(self, Q: np.ndarray, keys_ptr: int, counts_ptr: int, k_max: int, k: int, aug_larger: str,
+                             out_ptr: int, image_offset: int = 0, row_offset: int = 0, aug_weight: str = "level_max"):
+        """the second stage of a sharded chunk on this shard (ssw_index_stage2_avg_batch_dev; enqueue only): for the
+        merged keys [nq, k_max] / counts [nq] at the device pointers `keys_ptr` / `counts_ptr` (what
+        `ssw_topk_merge_msgs_batch_dev` wrote; global image positions), every candidate among the first `k` of query b
+        that is one of this shard's images -- positions [image_offset, image_offset + n_images) -- is scored for Q[b]
+        straight from the index rows and aggregated as `rescore_avg` aggregates it.  The block [nq, 2, k_max] u64 at
+        `out_ptr` receives `1 << 32 | f32 bits of the score` and `row_offset + best row`, zeros where the image is
+        another shard's.  The handle's scores, results and prune counters are not touched."""
+        Q = self._queries(Q)
+        aug = self.AUG_LARGER[aug_larger] | {"level_max": 0, "cont_weighted": 4}[aug_weight]
+        _lib.call("ssw_index_stage2_avg_batch_dev", self._h, _ptr(Q), Q.shape[0], ctypes.c_void_p(int(keys_ptr)),
+                  ctypes.c_void_p(int(counts_ptr)), int(k_max), int(k), aug, int(image_offset), int(row_offset),
+                  ctypes.c_void_p(int(out_ptr)))
+
     def prune_batch_dev_counts(self):
         """what the device decided for the last chunk of the last `topk_batch_dev(prune=True)`
         (ssw_index_prune_batch_dev_read; synchronises): (survivors int64 [w], fail_bits int32 [w]) -- the raw survivor

@@ -28,7 +28,7 @@ import numpy as np
 import pandas as pd
 
 from ...bitmap import BitMap
-from ...sharded import ShardedTopK, _DevArray, shard_bounds_by_image
+from ...sharded import ShardedTopK, _DevArray, combine_stage2_block, shard_bounds_by_image
 from ..interface import AccessMethod, ActivationFrames
 from .multiscale_index import MultiscaleIndex, _Candidates
 
@@ -91,6 +91,13 @@ class DeviceShard:
     def select_slot_deep(self, q: np.ndarray, k: int, excluded_local: np.ndarray, slot: int):
         """the exact repair of one flagged query of the chunk: rescan, deep selection, message into `slot`"""
         self.index.topk_slot_deep_dev(q, k, excluded_local, slot)
+
+    def stage2_batch(self, Q: np.ndarray, keys_ptr: int, counts_ptr: int, k_max: int, k: int, aug_larger: str, out_ptr: int,
+                     image_offset: int = 0, row_offset: int = 0, aug_weight: str = "level_max"):
+        """the avg_score aggregation of a chunk's merged candidates that this slice owns, one launch for the chunk
+        (enqueue only; DeviceIndex.stage2_avg_batch_dev)"""
+        self.index.stage2_avg_batch_dev(Q, keys_ptr, counts_ptr, k_max, k, aug_larger, out_ptr, image_offset=image_offset,
+                                        row_offset=row_offset, aug_weight=aug_weight)
 
     def select_scores(self, row_scores: np.ndarray, k: int, excluded_local: np.ndarray):
         """top-k of the slice by caller-supplied per-row scores (f32, -inf = skip): the label-propagation ranking"""
@@ -192,12 +199,17 @@ class ShardedMultiscaleIndex(MultiscaleIndex):
             zoom = self.vector_meta.zoom_level.values[self.row_lo:self.row_hi] if self._has_tile_meta else None
             kw = {} if self.vector_dtype == np.float32 else {"vector_dtype": self.vector_dtype}
             self._shard = self._shard_factory(np.ascontiguousarray(local, dtype=np.float32), r2i, boxes, zoom, self.device, **kw)
-        compute_dev = torch.device("cuda", self.device) if self._shard_factory is DeviceShard else torch.device("cpu")
+        compute_dev = torch.device("cuda", self.device) if self._device_shards() else torch.device("cpu")
         kw = {} if self._merge is None else {"merge": self._merge}
         self._xchg = ShardedTopK(rank=self.rank, world=self.world, device=compute_dev, image_offset=self.img_lo,
                                  k_max=self._k_max, group=self.group, with_best=True, comm_device=self._comm_device, **kw)
         self._dev = None  # there is no whole-matrix device index
         self.query_batch = self._query_batch_sharded  # (see the class attribute of that name)
+
+    def _device_shards(self) -> bool:
+        """the shards live in HBM: the factory is DeviceShard or a subclass of it (a test's counting shard)"""
+        f = self._shard_factory
+        return isinstance(f, type) and issubclass(f, DeviceShard)
 
     # ---- stage 1 ------------------------------------------------------------------------
     def _prelim(self, *, vector, topk_dbidx, exclude_dbidx=None, force_exact=False):
@@ -270,7 +282,7 @@ class ShardedMultiscaleIndex(MultiscaleIndex):
         import torch
         if self._comm_device is not None:
             return torch.device(self._comm_device)
-        return torch.device("cuda", self.device) if self._shard_factory is DeviceShard else torch.device("cpu")
+        return torch.device("cuda", self.device) if self._device_shards() else torch.device("cpu")
 
     def _all_gather_f64(self, vec: np.ndarray, cap: int):
         """fixed-size tensor collective: every rank contributes <= cap float64 values -> list of per-rank arrays.
@@ -346,29 +358,41 @@ class ShardedMultiscaleIndex(MultiscaleIndex):
     # The class keeps the per-query loop under this name: there is no whole-matrix device index (`_dev`) for
     # MultiscaleIndex's device batch, and `AccessMethod.query_batch(index, ...)` stays the loop that the batched form is
     # compared against.  Every INSTANCE answers `index.query_batch(...)` with `_query_batch_sharded` (bound in
-    # `_init_device`), which falls back to this loop for whatever it does not serve.
+    # `_init_device`), which serves both aggregation methods and falls back to this loop for whatever it does not serve
+    # (`vector2`, an index without tile meta, a shard factory without the batched methods).
     query_batch = AccessMethod.query_batch
 
     def _query_batch_sharded(self, *, topk, vectors, excludes=None, prune=False, **kwargs):
         """`index.query_batch`: `[query(vector=v, topk=topk, exclude=e, **kwargs) for v, e in zip(vectors, excludes)]`,
-        entry by entry identical to it.  For `agg_method="plain_score"` without `vector2` every rank reads its rows once per chunk of up
+        entry by entry identical to it.  Without `vector2` every rank reads its rows once per chunk of up
         to 16 queries (`DeviceShard.select_batch`) and the ranks exchange once per group of `n_slots` queries: one
         all-gather and one merge launch (`ShardedTopK.exchange_fused_batch`), one host read of counts and flags.  A
         flagged (query, rank) is repaired by a rescan with the deep selection on that rank, after which all ranks repeat
         the group's exchange once.  The entry rules are `MultiscaleIndex.query_batch`'s: entries without a vector or
         with an exclusion set that covers the index go through `query`; one k = the largest shortlist, every query
-        keeps its own first min(shortlist_size, included) candidates.  Everything else -- other aggregation methods,
-        `vector2`, a shard factory without `select_batch` -- is the per-query loop; the second stage over a sharded
-        batch remains a follow-up.  Afterwards `_resident_q` names the last query.
+        keeps its own first min(shortlist_size, included) candidates.
+        `agg_method="plain_score"` ends there: the best tile came with the key.  Any other aggregation method (on an
+        index with tile meta) adds the group's second stage once the merged keys are final: every rank with images
+        enqueues ONE launch that scores and aggregates the candidates it owns for all the group's queries
+        (`DeviceShard.stage2_batch`), ONE more all-gather carries the blocks (`ShardedTopK.exchange_stage2_batch`), and
+        the host combines them (`combine_stage2_block`) and finishes each query with the lines of
+        `_rescore_avg_on_device`: candidates in ascending position, `np.argsort(-scores)[:topk]`.
+        Everything else -- `vector2` with either method, an index without tile meta (the loop raises its
+        NotImplementedError), a shard factory without `select_batch` (or, for the second stage, `stage2_batch`) -- is
+        the per-query loop.  Afterwards `_resident_q` names the last query.
         `prune=True`: the served route's chunks take the certified int8 pre-scan on every shard that is large enough
         (`DeviceShard.select_batch(prune=True)`); a (query, rank) whose certificate failed is flagged and repaired like
-        an overflow.  The same entries; every other route runs its loop as before and ignores the flag."""
+        an overflow.  The second stage reads the index rows, not the slabs, so it is the same behind either first
+        stage.  The same entries; every other route runs its loop as before and ignores the flag."""
         vectors = list(vectors)
         excludes = [None] * len(vectors) if excludes is None else list(excludes)
         if len(excludes) != len(vectors):
             raise ValueError(f"excludes has {len(excludes)} entries for {len(vectors)} vectors")
-        if kwargs.get("agg_method") != "plain_score" or kwargs.get("vector2") is not None \
-                or "shortlist_size" not in kwargs or not hasattr(self._shard_factory, "select_batch"):
+        served = kwargs.get("vector2") is None and "shortlist_size" in kwargs and hasattr(self._shard_factory, "select_batch")
+        avg = kwargs.get("agg_method") != "plain_score"
+        if avg:  # the second stage too: on the owners, one launch and one more exchange a group
+            served = served and self._has_tile_meta and "aug_larger" in kwargs and hasattr(self._shard_factory, "stage2_batch")
+        if not served:
             return AccessMethod.query_batch(self, topk=topk, vectors=vectors, excludes=excludes, **kwargs)
         shortlist_size = kwargs["shortlist_size"]
         if shortlist_size is None:
@@ -410,11 +434,27 @@ class ShardedMultiscaleIndex(MultiscaleIndex):
                 keys, counts = x.exchange_fused_batch(nq, k)
                 assert not x.overflowed_batch()
                 x.reset_overflow_seen()
-            keys_h, counts_h, gathered = keys.cpu().numpy().view(np.uint64), counts.cpu().numpy(), x.gathered_batch()
+            if avg:  # the merged keys are final: every owner aggregates its candidates, the blocks are exchanged once
+                if self._shard is not None:
+                    self._shard.stage2_batch(Qg, keys.data_ptr(), counts.data_ptr(), x.k_max, k, kwargs["aug_larger"],
+                                             x.stage2_buffers().data_ptr(), image_offset=self.img_lo, row_offset=self.row_lo,
+                                             aug_weight=kwargs.get("aug_weight", "level_max"))
+                block = x.exchange_stage2_batch(nq)  # host read: synchronises
+            keys_h, counts_h = keys.cpu().numpy().view(np.uint64), counts.cpu().numpy()
+            if avg:
+                s2_scores, s2_rows = combine_stage2_block(block, counts_h, x.k_max)
+            else:
+                gathered = x.gathered_batch()
             for b in range(nq):
-                k_i = ks[g + b]
-                merged = keys_h[b, :min(int(counts_h[b]), k_i)]
+                m = min(int(counts_h[b]), ks[g + b])
+                merged = keys_h[b, :m]
                 pos, scores = decode_keys(merged)
+                if avg:  # from here on the lines of _rescore_avg_on_device: candidates in ascending position
+                    order = np.argsort(pos, kind="stable")
+                    positions, scores, rows = pos[order], s2_scores[b, :m][order], s2_rows[b, :m][order]
+                    top = np.argsort(-scores.astype(np.float64))[:topk]
+                    out[batch[g + b]] = self._activations(positions[top], rows[top], scores[top])
+                    continue
                 cand = _Candidates(self._dbidx[pos], scores, pos, x.best_rows_of(merged, query=b, gathered=gathered))
                 out[batch[g + b]] = self._activations_from_best(cand, topk)
         self._resident_q = Q[-1].copy()

@@ -90,6 +90,30 @@ def unpack_message_block(block: np.ndarray, k_max: int, with_best: bool):
     return out
 
 
+def combine_stage2_block(block: np.ndarray, counts, k_max: int):
+    """the second stage of a chunk as one all-gather leaves it: `block` [world, nq, 2, k_max] (u64 or its i64 bit
+    pattern), rank r's `[b, 0, c]` = 1 << 32 | f32 bits of the aggregated score and `[b, 1, c]` = the global best row
+    where r owns candidate c of query b, two zero words where it does not (ssw_index_stage2_avg_batch_dev) ->
+    (scores f32 [nq, k_max], rows i64 [nq, k_max]).  Every (b, c < counts[b]) must have exactly one owner -- the owned
+    bit decides, the score itself may be NaN; entries at c >= counts[b] are ignored and come back as zeros."""
+    block = np.ascontiguousarray(block).view(np.uint64)
+    assert block.ndim == 4 and block.shape[2] == 2 and block.shape[3] == k_max, block.shape
+    nq = block.shape[1]
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    assert counts.shape[0] == nq and (counts >= 0).all() and (counts <= k_max).all(), counts
+    live = np.arange(k_max)[None, :] < counts[:, None]                      # [nq, k_max]
+    owned = ((block[:, :, 0, :] >> np.uint64(32)) == np.uint64(1)) & live  # [world, nq, k_max]
+    owners = owned.sum(axis=0)
+    bad = np.argwhere(live & (owners != 1))
+    if bad.shape[0]:
+        b, c = (int(v) for v in bad[0])
+        raise ValueError(f"second stage: candidate {c} of query {b} has {int(owners[b, c])} owners, not one "
+                         f"({bad.shape[0]} such entries)")
+    words = np.where(owned, block[:, :, 0, :] & np.uint64(0xFFFFFFFF), np.uint64(0)).sum(axis=0, dtype=np.uint64)
+    rows = np.where(owned, block[:, :, 1, :], np.uint64(0)).sum(axis=0, dtype=np.uint64)  # one term is not zero
+    return words.astype(np.uint32).view(np.float32), rows.view(np.int64)
+
+
 def merge_keys_hip(device: int, stream_ptr: int, keys, counts, k: int, out_keys, out_count):
     """Global top-k of `world` sorted key lists on the GPU (ssw_topk_merge_dev)."""
     world, stride = keys.shape
@@ -230,13 +254,17 @@ class ShardedTopK:
         """one all-gather of the chunk's nq messages per rank into all_batch, laid out [world, nq, msg_len]: the three
         routes of `gather`"""
         words = nq * self.msg_len
-        send, recv = self.send_batch.view(-1)[:words], self.all_batch[:self.world * words]
+        self._gather_words(self.send_batch.view(-1)[:words], self.all_batch[:self.world * words])
+
+    def _gather_words(self, send, recv):
+        """all-gather `send` (i64 words, the same count on every rank) into `recv` [world * words] through
+        torch.distributed: on the device, or staged through `comm_device`; a world of one copies unless forced"""
         if self.world > 1 or self.force_collective:
             import torch.distributed as dist
             if self.comm_device is None or self.comm_device == send.device:
                 dist.all_gather_into_tensor(recv, send, group=self.group)
             else:
-                out = self.torch.empty(self.world * words, dtype=self.torch.int64, device=self.comm_device)
+                out = self.torch.empty(recv.numel(), dtype=self.torch.int64, device=self.comm_device)
                 dist.all_gather_into_tensor(out, send.to(self.comm_device), group=self.group)
                 recv.copy_(out)
         else:
@@ -271,6 +299,35 @@ class ShardedTopK:
         synchronises once).  Every rank sees the same list."""
         f = self.flags_batch[:self._batch_nq].cpu().numpy()
         return [(int(b), int(r)) for b, r in zip(*np.nonzero(f))]
+
+    # ---- the chunk's second stage -------------------------------------------------------------------------
+    def stage2_buffers(self):
+        """`send_stage2` [n_slots, 2, k_max] (i64 words): the block this rank's `stage2_avg_batch_dev` fills for the
+        group's merged keys -- a rank without images leaves it zero: it owns nothing --, and its gathered counterpart;
+        allocated with the first second stage after `attach_batch`"""
+        if getattr(self, "send_stage2", None) is None or self.send_stage2.shape[0] != self.n_slots:
+            torch, dev = self.torch, self.send_batch.device
+            self.send_stage2 = torch.zeros((self.n_slots, 2, self.k_max), dtype=torch.int64, device=dev)
+            self.all_stage2 = torch.zeros(self.world * self.n_slots * 2 * self.k_max, dtype=torch.int64, device=dev)
+        return self.send_stage2
+
+    def exchange_stage2_batch(self, nq: int) -> np.ndarray:
+        """ONE all-gather of the first nq slots of `send_stage2` (nq * 2 * k_max words per rank), by the route the
+        chunk's first exchange takes -> host array u64 [world, nq, 2, k_max] for `combine_stage2_block` (host read:
+        synchronises)"""
+        assert getattr(self, "send_batch", None) is not None, "attach_batch(dev_index) first"
+        if not 1 <= nq <= self.n_slots:
+            raise ValueError(f"nq={nq} outside [1, n_slots={self.n_slots}] of this exchange")
+        self.stage2_buffers()
+        words = nq * 2 * self.k_max
+        send, recv = self.send_stage2.view(-1)[:words], self.all_stage2[:self.world * words]
+        if getattr(self, "_comm", None):
+            stream_ptr = self.torch.cuda.current_stream().cuda_stream
+            _lib.call("ssw_topk_allgather", self._comm, ctypes.c_void_p(stream_ptr), ctypes.c_void_p(send.data_ptr()),
+                      ctypes.c_void_p(recv.data_ptr()), words)
+        else:
+            self._gather_words(send, recv)
+        return recv.view(self.world, nq, 2, self.k_max).cpu().numpy().view(np.uint64)
 
     def time_collective(self, on: bool = True):
         """bracket every exchange_fused collective with HIP events (two event records per step on the stream)"""
