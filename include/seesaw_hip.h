@@ -80,6 +80,35 @@ ssw_status ssw_index_create_typed(int32_t device, int64_t n_rows, int32_t dim, i
                                   const void *dev_vectors_or_null, ssw_index **out);
 ssw_status ssw_index_dtype(const ssw_index *idx, int32_t *out);
 ssw_status ssw_index_destroy(ssw_index *idx);
+
+/* A zero-copy VIEW of a resident index: a handle over the rows of m member images that scans them IN PLACE, out of the
+ * parent's matrix (AccessMethod.subset(BitMap) of the reference, seesaw/seesaw_session.py:216-225, without the host
+ * gather and the second upload a copied subset index costs).  image_positions [m] (host): parent image positions --
+ * row positions for a parent without an image map -- strictly ascending, inside the parent, m >= 1; anything else is
+ * SSW_ERR_INVALID, decided on the host before any device call, as are a NULL parent, NULL positions and a NULL out.
+ * The view is an ordinary ssw_index of n_rows = the members' rows (in the parent's order) and n_images = m, with the
+ * parent's dim, dtype and device; it owns a row table (4 bytes a row), a score buffer, streams, a selection workspace,
+ * staging and -- when the parent has an image map -- the image map of its members, and takes its own tile meta
+ * (ssw_index_set_tile_meta).  Rows, image positions and results are the VIEW's: what a copied subset index of
+ * X[member rows] returns, bit for bit (the scan runs the parent's lane arithmetic on the member rows).  It reads the
+ * parent's current rows: an ssw_index_upload into the parent shows in the view's next scan.  A view is never pruned
+ * and builds no shadow.
+ * Work on a view: shape, dtype, set_stream, sync, scan, scan_dev, load_scores, topk (small and general form),
+ * set_excluded, topk_dev, select_deep_dev, result_ptrs, topk_fetch, gather_scores, set_tile_meta, rescore_avg,
+ * rescore_avg_f64, profile, profile_read, prune_stats / prune_completions ("not pruned"), ssw_labelprop_scores_to_index,
+ * ssw_labelprop_round; ssw_index_device_ptrs hands out the view's score buffer and a NULL row pointer;
+ * ssw_index_score_rows, ssw_index_gather_rows and ssw_fb_set_data_from_index take VIEW rows and translate them.
+ * Refused on a view with SSW_ERR_UNSUPPORTED (the message says "view") before anything is touched: upload, upload_f16,
+ * download, fill_random, set_row2image, every *_batch* entry, topk_slot_deep_dev, stage2_avg_batch_dev, both exchange
+ * target setters, ssw_knn_build, ssw_xlx, ssw_fb_set_pseudo_sample_from_index, and a view of a view.
+ * Lifetime: the parent counts its live views; ssw_index_destroy(parent) with live views is SSW_ERR_INVALID and leaves
+ * the parent intact.  Destroy the views first.  A view's members are the rows the parent's image map gave those images
+ * when the view was made, so ssw_index_set_row2image(parent) with live views is SSW_ERR_INVALID too; the parent's ROWS
+ * may change under a view (ssw_index_upload).
+ * ssw_index_view_rows: the parent row of every view row, out_parent_rows_host [n_rows] (SSW_ERR_INVALID if the handle
+ * is not a view). */
+ssw_status ssw_index_create_view(ssw_index *parent, const int64_t *image_positions, int64_t m, ssw_index **out);
+ssw_status ssw_index_view_rows(const ssw_index *view, int64_t *out_parent_rows_host);
 /* run all of this handle's work on an existing hipStream_t (e.g. torch's current
  * stream) instead of the handle's own (non-blocking) stream.  NULL restores the own stream; to name the
  * default stream -- whose handle IS NULL, e.g. torch.cuda.current_stream().cuda_stream == 0 -- pass

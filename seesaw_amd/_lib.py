@@ -49,6 +49,8 @@ _SIGNATURES = {
     "ssw_index_create_typed": (c_i32, [c_i32, c_i64, c_i32, c_i32, c_void_p, c_void_pp]),
     "ssw_index_dtype": (c_i32, [c_void_p, c_i32_p]),
     "ssw_index_destroy": (c_i32, [c_void_p]),
+    "ssw_index_create_view": (c_i32, [c_void_p, c_void_p, c_i64, c_void_pp]),
+    "ssw_index_view_rows": (c_i32, [c_void_p, c_void_p]),
     "ssw_index_set_stream": (c_i32, [c_void_p, c_void_p]),
     "ssw_index_sync": (c_i32, [c_void_p]),
     "ssw_index_shape": (c_i32, [c_void_p, c_i64_p, c_i32_p, c_i64_p]),

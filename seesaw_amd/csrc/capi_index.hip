@@ -95,8 +95,19 @@ ssw_status ssw::check_query(const ssw_index *idx, const float *q_host) {
 }
 
 ssw_status ssw::launch_index_scan(ssw_index *idx, const float *q_dev, hipStream_t stream) {
+    if (idx->parent)  // a view: its member rows in place, out of the parent's matrix
+        return launch_scan_view(idx->X, idx->dtype, q_dev, idx->row_src, idx->scores, idx->n, idx->dim, idx->device, stream);
     return launch_scan(idx->X, idx->dtype, q_dev, idx->scores, idx->n, idx->dim, idx->device, stream);
 }
+
+ssw_status ssw::refuse_view(const ssw_index *idx, const char *who) {
+    if (!idx || !idx->parent) return SSW_OK;
+    set_error("%s: the index is a view of another index's rows and has no matrix of its own; call it on the parent or on a "
+              "copied subset", who);
+    return SSW_ERR_UNSUPPORTED;
+}
+
+const int32_t *ssw::index_view_rows(const ssw_index *idx) { return idx && idx->parent ? idx->row_src_host.data() : nullptr; }
 
 ssw_status ssw::do_scan(ssw_index *idx, const float *q_dev) {
     idx->scores_partial = false;
@@ -239,8 +250,15 @@ ssw_status ssw_index_create_typed(int32_t device, int64_t n_rows, int32_t dim, i
 
 ssw_status ssw_index_destroy(ssw_index *idx) {
     if (!idx) return SSW_OK;
+    SSW_REQUIRE(idx->live_views == 0, "ssw_index_destroy: %lld views still read this index's rows; destroy them first",
+                (long long)idx->live_views);
     DeviceGuard guard(idx->device);
     if (idx->own_stream) (void)hipStreamSynchronize(idx->own_stream);
+    if (idx->parent) {
+        if (idx->stream != idx->own_stream) (void)hipStreamSynchronize(idx->stream);  // its scans read the parent's rows
+        --idx->parent->live_views;
+    }
+    (void)hipFree(idx->row_src);
     for (hipEvent_t e : idx->ev) (void)hipEventDestroy(e);
     if (idx->ws_ready) select_free(idx->ws);
     idx->prune.release();
@@ -268,6 +286,82 @@ ssw_status ssw_index_destroy(ssw_index *idx) {
     idx->q2_stage.release();
     if (idx->own_stream) (void)hipStreamDestroy(idx->own_stream);
     delete idx;
+    return SSW_OK;
+}
+
+ssw_status ssw_index_create_view(ssw_index *parent, const int64_t *image_positions, int64_t m, ssw_index **out) {
+    SSW_REQUIRE(out != nullptr, "out is NULL");
+    *out = nullptr;
+    SSW_REQUIRE(parent != nullptr && image_positions != nullptr, "NULL argument");
+    if (parent->parent) {
+        set_error("ssw_index_create_view: the index is itself a view; take the view from its parent");
+        return SSW_ERR_UNSUPPORTED;
+    }
+    SSW_REQUIRE(m >= 1, "ssw_index_create_view: m=%lld < 1", (long long)m);
+    // the members' rows, in the parent's row order, and the view's own image map: all on the host, before any device call
+    std::vector<int32_t> src;
+    std::vector<int64_t> start;
+    if (parent->has_map) start.push_back(0);
+    for (int64_t i = 0; i < m; ++i) {
+        const int64_t p = image_positions[i];
+        SSW_REQUIRE(p >= 0 && p < parent->n_images, "ssw_index_create_view: position %lld outside [0, %lld)", (long long)p,
+                    (long long)parent->n_images);
+        SSW_REQUIRE(i == 0 || p > image_positions[i - 1], "ssw_index_create_view: positions must be strictly ascending (entry %lld)",
+                    (long long)i);
+        const int64_t r0 = parent->has_map ? parent->row_start_host[(size_t)p] : p;
+        const int64_t r1 = parent->has_map ? parent->row_start_host[(size_t)p + 1] : p + 1;
+        for (int64_t r = r0; r < r1; ++r) src.push_back((int32_t)r);  // (a shard has fewer than 2^31 rows)
+        if (parent->has_map) start.push_back((int64_t)src.size());
+    }
+    const int64_t n = (int64_t)src.size();
+    DeviceGuard guard(parent->device);
+    if (!guard.ok) {
+        set_error("hipSetDevice(%d) failed", parent->device);
+        return SSW_ERR_HIP;
+    }
+    ssw_index *idx = new (std::nothrow) ssw_index();
+    if (!idx) return SSW_ERR_NOMEM;
+    idx->device = parent->device;
+    idx->n = n;
+    idx->dim = parent->dim;
+    idx->dtype = parent->dtype;
+    idx->n_images = m;
+    idx->X = parent->X;  // borrowed: owns_X stays false, so the view is never pruned and builds no shadow
+    auto fail = [&](ssw_status s) {
+        ssw_index_destroy(idx);  // (not yet counted by the parent)
+        return s;
+    };
+    if (hipStreamCreateWithFlags(&idx->own_stream, hipStreamNonBlocking) != hipSuccess) {
+        set_error("hipStreamCreate failed");
+        return fail(SSW_ERR_HIP);
+    }
+    idx->stream = idx->own_stream;
+    if (hipMalloc((void **)&idx->row_src, (size_t)n * sizeof(int32_t)) != hipSuccess ||
+        hipMalloc((void **)&idx->scores, (size_t)(n + 64) * sizeof(float)) != hipSuccess ||
+        hipMalloc((void **)&idx->q_dev, (size_t)idx->dim * sizeof(float)) != hipSuccess ||
+        (parent->has_map && hipMalloc((void **)&idx->row_start, ((size_t)m + 1) * sizeof(int64_t)) != hipSuccess)) {
+        set_error("hipMalloc of the view's row table and score buffer failed");
+        return fail(SSW_ERR_NOMEM);
+    }
+    if (hipMemcpy(idx->row_src, src.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+        (parent->has_map && hipMemcpy(idx->row_start, start.data(), ((size_t)m + 1) * sizeof(int64_t),
+                                      hipMemcpyHostToDevice) != hipSuccess)) {
+        set_error("ssw_index_create_view: copying the row table failed");
+        return fail(SSW_ERR_HIP);
+    }
+    idx->row_src_host = std::move(src);
+    idx->row_start_host = std::move(start);
+    idx->has_map = parent->has_map;
+    idx->parent = parent;
+    ++parent->live_views;
+    *out = idx;
+    return SSW_OK;
+}
+
+ssw_status ssw_index_view_rows(const ssw_index *view, int64_t *out_parent_rows_host) {
+    SSW_REQUIRE(view != nullptr && out_parent_rows_host != nullptr, "NULL argument");
+    SSW_REQUIRE(view->parent != nullptr, "ssw_index_view_rows: the index is not a view");
+    for (size_t j = 0; j < view->row_src_host.size(); ++j) out_parent_rows_host[j] = view->row_src_host[j];
     return SSW_OK;
 }
 
@@ -304,7 +398,9 @@ ssw_status ssw_index_device_ptrs(ssw_index *idx, void **dev_vectors, void **dev_
     SSW_REQUIRE(idx != nullptr, "idx is NULL");
     DeviceGuard guard(idx->device);
     SSW_TRY(ensure_full_scores(idx));
-    if (dev_vectors) {  // the caller may write the rows through it: no shadow from now on
+    if (dev_vectors && idx->parent) {  // a view has no rows of its own to hand out
+        *dev_vectors = nullptr;
+    } else if (dev_vectors) {  // the caller may write the rows through it: no shadow from now on
         idx->rows_escaped = true;
         SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
         idx->prune.free_shadow();
@@ -349,6 +445,7 @@ static ssw_status upload_h16(ssw_index *idx, const void *host_rows, bool src_h16
 
 ssw_status ssw_index_upload(ssw_index *idx, const float *host_rows, int64_t first_row, int64_t n) {
     SSW_REQUIRE(idx != nullptr && host_rows != nullptr, "NULL argument");
+    SSW_TRY(refuse_view(idx, "ssw_index_upload"));
     SSW_TRY(check_row_range(idx, first_row, n));
     DeviceGuard guard(idx->device);
     SSW_TRY(rows_changing(idx));
@@ -362,6 +459,7 @@ ssw_status ssw_index_upload(ssw_index *idx, const float *host_rows, int64_t firs
 
 ssw_status ssw_index_upload_f16(ssw_index *idx, const uint16_t *rows_f16, int64_t first_row, int64_t n) {
     SSW_REQUIRE(idx != nullptr && rows_f16 != nullptr, "NULL argument");
+    SSW_TRY(refuse_view(idx, "ssw_index_upload_f16"));
     if (idx->dtype != SSW_DTYPE_F16) {
         set_error("ssw_index_upload_f16: the index holds f32 rows (use ssw_index_upload)");
         return SSW_ERR_UNSUPPORTED;
@@ -374,6 +472,7 @@ ssw_status ssw_index_upload_f16(ssw_index *idx, const uint16_t *rows_f16, int64_
 
 ssw_status ssw_index_download(ssw_index *idx, float *host_rows, int64_t first_row, int64_t n) {
     SSW_REQUIRE(idx != nullptr && host_rows != nullptr, "NULL argument");
+    SSW_TRY(refuse_view(idx, "ssw_index_download"));
     SSW_TRY(check_row_range(idx, first_row, n));
     DeviceGuard guard(idx->device);
     if (idx->dtype == SSW_DTYPE_F16) {  // widened, natural element order, through the staging buffer
@@ -399,6 +498,7 @@ ssw_status ssw_index_download(ssw_index *idx, float *host_rows, int64_t first_ro
 
 ssw_status ssw_index_fill_random(ssw_index *idx, uint64_t seed, int64_t global_first_row) {
     SSW_REQUIRE(idx != nullptr, "idx is NULL");
+    SSW_TRY(refuse_view(idx, "ssw_index_fill_random"));
     DeviceGuard guard(idx->device);
     SSW_TRY(rows_changing(idx));
     SSW_TRY(launch_fill_random(idx->X, idx->dtype, idx->n, idx->dim, seed, global_first_row, idx->stream));
@@ -408,6 +508,10 @@ ssw_status ssw_index_fill_random(ssw_index *idx, uint64_t seed, int64_t global_f
 
 ssw_status ssw_index_set_row2image(ssw_index *idx, const int32_t *row2image_host, int64_t n_images) {
     SSW_REQUIRE(idx != nullptr, "idx is NULL");
+    SSW_TRY(refuse_view(idx, "ssw_index_set_row2image"));  // (its image map is its members': ssw_index_create_view)
+    // a view's members are rows of the images the parent's map named when the view was made
+    SSW_REQUIRE(idx->live_views == 0, "ssw_index_set_row2image: %lld views were made from this index's image map; destroy them first",
+                (long long)idx->live_views);
     DeviceGuard guard(idx->device);
     SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
     if (idx->ws_ready) {
@@ -605,10 +709,17 @@ ssw_status ssw_index_load_scores(ssw_index *idx, const float *scores_host) {
     return SSW_OK;
 }
 
-static ssw_status stage_rows(ssw_index *idx, const int64_t *rows_host, int64_t n) {
+// matrix_rows: the staged rows index the matrix (score_rows, gather_rows), so a view stages its rows' parent rows
+static ssw_status stage_rows(ssw_index *idx, const int64_t *rows_host, int64_t n, bool matrix_rows = false) {
     for (int64_t i = 0; i < n; ++i) {
         SSW_REQUIRE(rows_host[i] >= 0 && rows_host[i] < idx->n, "row %lld outside [0, %lld)",
                     (long long)rows_host[i], (long long)idx->n);
+    }
+    std::vector<int64_t> parent_rows;
+    if (matrix_rows && idx->parent) {
+        parent_rows.resize((size_t)n);
+        for (int64_t i = 0; i < n; ++i) parent_rows[(size_t)i] = idx->row_src_host[(size_t)rows_host[i]];
+        rows_host = parent_rows.data();  // (push copies it into the pinned block before it returns)
     }
     if (n > idx->gather_cap) {
         SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
@@ -633,7 +744,7 @@ ssw_status ssw_index_score_rows(ssw_index *idx, const float *q_host, const int64
     SSW_REQUIRE(q_host && rows_host && out_scores_host, "NULL argument");
     SSW_TRY(check_query(idx, q_host));
     DeviceGuard guard(idx->device);
-    SSW_TRY(stage_rows(idx, rows_host, n));
+    SSW_TRY(stage_rows(idx, rows_host, n, true));
     if (!idx->q2_dev) SSW_HIP_TRY(hipMalloc((void **)&idx->q2_dev, (size_t)idx->dim * sizeof(float)));
     SSW_TRY(idx->q2_stage.push(idx->q2_dev, q_host, (size_t)idx->dim * sizeof(float), idx->stream));
     SSW_TRY(launch_score_rows(idx->X, idx->dtype, idx->q2_dev, idx->gather_idx, n, idx->dim, idx->gather_out,
@@ -652,7 +763,8 @@ ssw_status ssw_index_gather_scores(ssw_index *idx, const int64_t *rows_host, int
     DeviceGuard guard(idx->device);
     if (idx->scores_partial && n <= SURV_CAP) {
         // after a pruned top-k: the requested rows scored with the kept query, the scan's bits; the buffer stays partial
-        SSW_TRY(stage_rows(idx, rows_host, n));
+        // (never a view, which is not pruned; its rows would be translated all the same)
+        SSW_TRY(stage_rows(idx, rows_host, n, true));
         SSW_TRY(launch_score_rows(idx->X, idx->dtype, idx->prune.q_last, idx->gather_idx, n, idx->dim, idx->gather_out,
                                   idx->stream));
         idx->prune.rescored_rows += n;
@@ -675,7 +787,7 @@ ssw_status ssw_index_gather_rows(ssw_index *idx, const int64_t *rows_host, int64
     if (n <= 0) return SSW_OK;
     SSW_REQUIRE(rows_host != nullptr && out_host != nullptr, "NULL argument");
     DeviceGuard guard(idx->device);
-    SSW_TRY(stage_rows(idx, rows_host, n));
+    SSW_TRY(stage_rows(idx, rows_host, n, true));
     float *buf = nullptr;
     SSW_HIP_TRY(hipMalloc((void **)&buf, (size_t)n * idx->dim * sizeof(float)));
     // f16 rows come back widened, in natural element order
@@ -709,6 +821,7 @@ ssw_status ssw_topk_merge_dev(int32_t device, void *hip_stream, const uint64_t *
 ssw_status ssw_index_set_exchange_target(ssw_index *idx, uint64_t *dev_msg_or_null, int32_t k_max, int32_t with_best,
                                          int64_t image_offset, int64_t row_offset) {
     SSW_REQUIRE(idx != nullptr, "idx is NULL");
+    SSW_TRY(refuse_view(idx, "ssw_index_set_exchange_target"));
     FinalExchange x;
     if (dev_msg_or_null) {
         SSW_REQUIRE(k_max >= 1 && k_max <= SSW_MAX_TOPK && image_offset >= 0, "bad message geometry");
@@ -727,6 +840,7 @@ ssw_status ssw_index_set_exchange_target(ssw_index *idx, uint64_t *dev_msg_or_nu
 ssw_status ssw_index_set_exchange_target_batch(ssw_index *idx, uint64_t *dev_msgs_or_null, int32_t n_slots, int32_t k_max,
                                                int32_t with_best, int64_t image_offset, int64_t row_offset) {
     SSW_REQUIRE(idx != nullptr, "idx is NULL");
+    SSW_TRY(refuse_view(idx, "ssw_index_set_exchange_target_batch"));
     FinalExchange x;
     if (dev_msgs_or_null) {
         SSW_REQUIRE(n_slots >= 1, "n_slots=%d < 1", n_slots);

@@ -2495,6 +2495,18 @@ ssw_status ssw_fb_set_data_from_index(ssw_fb *fb, const ssw_index *index, const 
     int64_t n_rows = 0;
     int32_t dtype = SSW_DTYPE_F32;
     SSW_TRY(fb_index_matrix(fb, index, &X, &n_rows, &dtype));
+    if (const int32_t *parent_row = index_view_rows(index)) {  // a view: its rows' places in the parent's matrix
+        SSW_REQUIRE(n >= 0 && (n == 0 || rows_host != nullptr), "bad argument");
+        int64_t n_view = 0;
+        SSW_TRY(ssw_index_shape(index, &n_view, nullptr, nullptr));
+        std::vector<int64_t> rows((size_t)n);
+        for (int64_t i = 0; i < n; ++i) {
+            SSW_REQUIRE(rows_host[i] >= 0 && rows_host[i] < n_view, "row %lld outside [0, %lld)", (long long)rows_host[i],
+                        (long long)n_view);
+            rows[(size_t)i] = parent_row[rows_host[i]];
+        }
+        return fb_set_data_gathered(fb, X, dtype, n_rows, rows.data(), n, center);  // (staged before it returns)
+    }
     return fb_set_data_gathered(fb, X, dtype, n_rows, rows_host, n, center);
 }
 
@@ -2577,6 +2589,7 @@ ssw_status ssw_fb_set_pseudo_sample_from_index(ssw_fb *fb, const ssw_index *inde
     const void *X = nullptr;
     int64_t n_rows = 0;
     int32_t dtype = SSW_DTYPE_F32;
+    SSW_TRY(refuse_view(index, "ssw_fb_set_pseudo_sample_from_index"));  // its rows are drawn on the device, by row number
     SSW_TRY(fb_index_matrix(fb, index, &X, &n_rows, &dtype));
     return fb_set_pseudo_sample(fb, X, dtype, n_rows, dev_scores, labelled_rows_sorted, labelled_y, n_lab, drawn, n_drawn,
                                 real_weight, center);

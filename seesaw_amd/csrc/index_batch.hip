@@ -77,6 +77,7 @@ static ssw_status check_query_batch(const ssw_index *idx, const float *q_host, i
 }
 
 extern "C" ssw_status ssw_index_scan_batch(ssw_index *idx, const float *q_host, int32_t nq, float *out_scores_host) {
+    SSW_TRY(refuse_view(idx, "ssw_index_scan_batch"));  // a view has no batched scan: the chunk kernels walk the matrix by row number
     SSW_REQUIRE(nq >= 1, "nq=%d < 1", nq);
     SSW_REQUIRE(idx != nullptr && q_host != nullptr, "NULL argument");
     SSW_TRY(check_query_batch(idx, q_host, nq));
@@ -225,6 +226,8 @@ static ssw_status prune_scan_chunk(ssw_index *idx, const BatchExcluded &excl, in
 static ssw_status topk_batch_run(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
                                  const int64_t *excluded_offsets, int32_t k, int64_t *out_images, float *out_scores,
                                  int64_t *out_best_rows, int32_t *out_counts, const AvgStage *avg, bool pruned) {
+    SSW_TRY(refuse_view(idx, avg ? (pruned ? "ssw_index_topk_batch_avg_pruned" : "ssw_index_topk_batch_avg")
+                                 : (pruned ? "ssw_index_topk_batch_pruned" : "ssw_index_topk_batch")));  // no batched scan of a view
     SSW_REQUIRE(nq >= 1, "nq=%d < 1", nq);
     SSW_REQUIRE(idx != nullptr && q_host != nullptr && out_counts != nullptr, "NULL argument");
     SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
@@ -384,6 +387,8 @@ static ssw_status prune_scan_chunk_dev(ssw_index *idx, const BatchExcluded &excl
 // call is ssw_index_topk_batch_dev).
 static ssw_status topk_batch_dev_run(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
                                      const int64_t *excluded_offsets, int32_t k, int32_t first_slot, bool pruned) {
+    // a view has no batched scan: the chunk kernels walk the matrix by row number
+    SSW_TRY(refuse_view(idx, pruned ? "ssw_index_topk_batch_dev_pruned" : "ssw_index_topk_batch_dev"));
     SSW_REQUIRE(nq >= 1, "nq=%d < 1", nq);
     SSW_REQUIRE(idx != nullptr && q_host != nullptr, "NULL argument");
     SSW_TRY(check_batch_target(idx, k, first_slot, nq, "topk_batch_dev"));
@@ -457,6 +462,7 @@ extern "C" ssw_status ssw_index_topk_batch_dev_pruned(ssw_index *idx, const floa
 
 extern "C" ssw_status ssw_index_topk_slot_deep_dev(ssw_index *idx, const float *q_host, const int64_t *excluded_images,
                                                    int64_t n_excluded, int32_t k, int32_t slot) {
+    SSW_TRY(refuse_view(idx, "ssw_index_topk_slot_deep_dev"));
     SSW_REQUIRE(idx != nullptr && q_host != nullptr, "NULL argument");
     SSW_REQUIRE(n_excluded == 0 || excluded_images != nullptr, "excluded_images is NULL");
     SSW_TRY(check_batch_target(idx, k, slot, 1, "topk_slot_deep_dev"));
@@ -484,6 +490,7 @@ extern "C" ssw_status ssw_index_stage2_avg_batch_dev(ssw_index *idx, const float
                                                      const uint64_t *dev_keys, const int32_t *dev_counts, int32_t k_max,
                                                      int32_t k, int32_t aug_larger, int64_t image_offset,
                                                      int64_t row_offset, uint64_t *dev_out) {
+    SSW_TRY(refuse_view(idx, "ssw_index_stage2_avg_batch_dev"));  // k_avg_score_owner scores tiles from the matrix by row
     SSW_REQUIRE(nq >= 1, "nq=%d < 1", nq);
     SSW_REQUIRE(k >= 1 && k <= k_max && k_max <= SSW_MAX_TOPK, "k=%d outside [1, k_max=%d], k_max at most %d", k, k_max,
                 SSW_MAX_TOPK);
@@ -531,6 +538,7 @@ static ssw_status topk_batch_avg(ssw_index *idx, const float *q_host, int32_t nq
                                  const int64_t *excluded_offsets, int32_t k, int32_t aug_larger, int64_t *out_images,
                                  float *out_scores, int64_t *out_best_rows, float *out_avg_scores, int64_t *out_avg_rows,
                                  int32_t *out_counts, bool pruned) {
+    SSW_TRY(refuse_view(idx, pruned ? "ssw_index_topk_batch_avg_pruned" : "ssw_index_topk_batch_avg"));
     SSW_REQUIRE(nq >= 1, "nq=%d < 1", nq);
     SSW_REQUIRE(idx && q_host && out_counts && out_avg_scores && out_avg_rows, "NULL argument");
     SSW_TRY(check_avg_args(idx, aug_larger, "topk_batch_avg"));

@@ -108,6 +108,14 @@ struct ssw_index {
     int32_t dtype = SSW_DTYPE_F32;
     float *X = nullptr;  // SSW_DTYPE_F16: binary16 rows in the lane-interleaved layout (ssw_common.h)
     bool owns_X = false;
+    // a view (ssw_index_create_view): X is the parent's matrix and row j of the view is its row row_src[j].  Only the
+    // scan (launch_index_scan) and the entries that translate staged view rows to parent rows on the host (stage_rows
+    // with matrix_rows in capi_index.hip; index_view_rows in feedback.hip) read X of a view; every other reader of X
+    // refuses it (refuse_view).  The parent counts its live views and is not destroyed before them
+    ssw_index *parent = nullptr;
+    int32_t *row_src = nullptr;         // [n] device
+    std::vector<int32_t> row_src_host;  // its host mirror
+    int64_t live_views = 0;
     // f16 upload / download: bounded device staging of natural-order rows (f32 or binary16)
     void *xfer = nullptr;
     size_t xfer_bytes = 0;

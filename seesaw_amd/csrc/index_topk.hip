@@ -247,7 +247,7 @@ ssw_status index_collect_topk(ssw_index *idx, hipStream_t on_stream, int32_t k, 
 int index_device(const ssw_index *idx) { return idx ? idx->device : -1; }
 int32_t index_dtype(const ssw_index *idx) { return idx ? idx->dtype : SSW_DTYPE_F32; }
 const void *index_matrix(const ssw_index *idx, int64_t *n_rows, int32_t *dim) {
-    if (n_rows) *n_rows = idx->n;
+    if (n_rows) *n_rows = idx->parent ? idx->parent->n : idx->n;  // a view's matrix is its parent's (index_view_rows)
     if (dim) *dim = idx->dim;
     return idx->X;
 }

@@ -598,6 +598,7 @@ extern "C" ssw_status ssw_knn_build(ssw_index *index, int32_t k, uint64_t seed, 
     int64_t n = 0, n_images = 0;
     int32_t D = 0;
     void *Xv = nullptr, *scores_unused = nullptr;
+    SSW_TRY(refuse_view(index, "ssw_knn_build"));
     if (index_dtype(index) != SSW_DTYPE_F32) {  // the build reads the matrix as f32 rows
         set_error("ssw_knn_build: the index holds f16 rows; build the graph from an f32 index of the widened rows");
         return SSW_ERR_UNSUPPORTED;

@@ -1687,6 +1687,7 @@ ssw_status ssw_labelprop_round(ssw_lp *lp, ssw_index *index, int32_t propagate, 
 ssw_status ssw_xlx(ssw_index *index, ssw_lp *lap, double *out_host) {
     SSW_REQUIRE(index != nullptr && lap != nullptr && out_host != nullptr, "NULL argument");
     SSW_REQUIRE(lap->perm == nullptr, "ssw_xlx: the Laplacian handle must be in original node order");
+    SSW_TRY(refuse_view(index, "ssw_xlx"));
     if (index_dtype(index) != SSW_DTYPE_F32) {  // the product reads the matrix as f32 rows
         set_error("ssw_xlx: the index holds f16 rows; compute X'LX from an f32 index of the widened rows");
         return SSW_ERR_UNSUPPORTED;

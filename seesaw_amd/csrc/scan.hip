@@ -383,6 +383,99 @@ __global__ __launch_bounds__(256) void scan_small_kernel(const typename R::T *__
     }
 }
 
+// ---- the scan of a VIEW (ssw_index_create_view): scores[j] = <X[row_src[j], :], q> over the parent's matrix -----------
+// Row j of the view is row row_src[j] of X.  The wave reads the 64 (small form: U * steps) source rows of its batch with
+// one coalesced load, lane l holding the source of row row0 + l, and takes the U sources of a group out of that register
+// with wave-uniform lane reads (v_readlane_b32), so a row's address is formed on the SALU exactly as in the unmapped
+// kernels.  Lanes past the view's last row clamp to it, as load_group does with `last`.  dot_frag / group_reduce<U> and
+// the group order are the unmapped kernels': a view's score is the BITS the parent's scan gives the same row.
+// (The names carry neither "scan" nor "score_rows": tests/test_index_f16_cpu.py pins the kernels so named.)
+template <class R, int C, int U, bool NT>
+__device__ __forceinline__ void load_view_group(Group<R, C, U> &g, const typename R::T *__restrict__ X, int src,
+                                                int first_lane, int lane) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) g.r[u] = R::template load<C, NT>(X, __builtin_amdgcn_readlane(src, first_lane + u), lane);
+}
+
+// streaming form: scan_scores_kernel's schedule (persistent grid, 64-row batches, groups of U, register double buffer,
+// non-temporal loads); the sources of the wave's next batch are requested when a batch starts, a batch ahead of their use
+template <class R, int C, int U, bool NT>
+__global__ __launch_bounds__(256) void view_scores_kernel(const typename R::T *__restrict__ X,
+                                                         const float *__restrict__ q,
+                                                         const int32_t *__restrict__ row_src,
+                                                         float *__restrict__ scores, int n) {
+    constexpr int GPB = 64 / U;  // groups per batch
+    const int lane = threadIdx.x & 63;
+    const int gwave = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int nwaves = gridDim.x * 4;
+    const int nbatches = (n + 63) >> 6;
+    const int last = n - 1;
+    if (gwave >= nbatches) return;
+
+    RowFrag<C> qf;
+#pragma unroll
+    for (int c = 0; c < C; ++c) qf.v[c] = reinterpret_cast<const float4 *>(q)[c * 64 + lane];
+
+    const int my_group = lane / U;
+    int src = row_src[min((gwave << 6) + lane, last)];
+    Group<R, C, U> cur, nxt;
+    load_view_group<R, C, U, NT>(cur, X, src, 0, lane);
+    for (int b = gwave; b < nbatches; b += nwaves) {
+        const int row0 = b << 6;
+        const int nb = b + nwaves;
+        const int next0 = (nb < nbatches ? nb : b) << 6;  // no next batch: re-touch own rows
+        const int src_next = row_src[min(next0 + lane, last)];
+        float out = 0.0f;
+#pragma unroll 2
+        for (int g = 0; g < GPB; ++g) {
+            // request group g+1 (or the first group of this wave's next batch) ...
+            const bool more = g + 1 < GPB;
+            load_view_group<R, C, U, NT>(nxt, X, more ? src : src_next, more ? (g + 1) * U : 0, lane);
+            // ... then finish group g
+            float acc[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) acc[u] = dot_frag<C>(R::widen(cur.r[u]), qf);
+            const float v = group_reduce<U>(acc, lane);
+            out = (my_group == g) ? v : out;
+            cur = nxt;
+        }
+        if (row0 + lane < n) scores[row0 + lane] = out;
+        src = src_next;
+    }
+}
+
+// small form: scan_small_kernel's shape (U rows in flight per wave per step, the query through LDS, plain loads); the
+// launcher keeps U * steps <= 64, so one register holds the sources of all the wave's rows
+template <class R, int C, int U>
+__global__ __launch_bounds__(256) void view_small_kernel(const typename R::T *__restrict__ X, const float *__restrict__ q,
+                                                        const int32_t *__restrict__ row_src, float *__restrict__ scores,
+                                                        int n, int steps) {
+    __shared__ float4 ql[C * 64];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int last = n - 1;
+    const int row_base = (blockIdx.x * 4 + wave) * U * steps;
+    const int src = row_src[min(row_base + lane, last)];
+    for (int i = threadIdx.x; i < C * 64; i += 256) ql[i] = reinterpret_cast<const float4 *>(q)[i];
+    Group<R, C, U> cur, nxt;
+    load_view_group<R, C, U, false>(cur, X, src, 0, lane);
+    __syncthreads();
+    RowFrag<C> qf;
+#pragma unroll
+    for (int c = 0; c < C; ++c) qf.v[c] = ql[c * 64 + lane];
+    for (int g = 0; g < steps; ++g) {
+        const int row0 = row_base + g * U;
+        if (row0 >= n) break;
+        if (g + 1 < steps) load_view_group<R, C, U, false>(nxt, X, src, (g + 1) * U, lane);
+        float acc[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) acc[u] = dot_frag<C>(R::widen(cur.r[u]), qf);
+        const float v = group_reduce<U>(acc, lane);
+        if (lane < U && row0 + lane < n) scores[row0 + lane] = v;
+        cur = nxt;
+    }
+}
+
 // scores of an explicit list of rows, same summation order as the full scan (one wave per
 // row, plain butterfly) -- stage-2 rescoring against a second vector
 // (multiscale_index.py:347-349).
@@ -594,6 +687,64 @@ ssw_status launch_scan(const void *X, int32_t dtype, const float *q_dev, float *
                 }
             case 768: return launch_scan_t<F32Rows, 3, 2, true>(X, q_dev, scores, n, device, stream);
             case 1024: return launch_scan_t<F32Rows, 4, 2, true>(X, q_dev, scores, n, device, stream);
+        }
+    }
+    set_error("scan: dim=%d unsupported (need a multiple of 256, <= 1024)", dim);
+    return SSW_ERR_UNSUPPORTED;
+}
+
+namespace {
+// the view's scan in the default schedule of launch_scan_t: small form up to SCAN_SMALL_ROWS rows (inclusive: the
+// range of the small top-k form, index_handle.h SMALL_ROWS), the persistent streaming form above
+template <class R, int C, int U>
+ssw_status launch_view_t(const void *Xv, const float *q, const int32_t *row_src, float *scores, int64_t n, int device,
+                         hipStream_t stream) {
+    const typename R::T *X = static_cast<const typename R::T *>(Xv);
+    if (n <= SCAN_SMALL_ROWS) {
+        constexpr int SU = C <= 2 ? 8 : 4;
+        const int64_t per_step = 4 * SU;  // rows a workgroup takes per step
+        const int steps = (int)((n + 4096 * per_step - 1) / (4096 * per_step));
+        static_assert(SU * ((SCAN_SMALL_ROWS + 4096 * 4 * SU - 1) / (4096 * 4 * SU)) <= 64,
+                      "one register holds the sources of a wave's rows");
+        const int64_t sgrid = (n + per_step * steps - 1) / (per_step * steps);
+        hipLaunchKernelGGL((view_small_kernel<R, C, SU>), dim3((unsigned)sgrid), dim3(256), 0, stream, X, q, row_src,
+                           scores, (int)n, steps);
+        SSW_HIP_TRY(hipGetLastError());
+        return SSW_OK;
+    }
+    const int64_t nbatches = (n + 63) >> 6;
+    int64_t grid = (int64_t)num_cus(device) * (C == 2 ? 1 : 2);  // launch_scan_t's residency
+    const int64_t need = (nbatches + 3) / 4;
+    if (grid > need) grid = need;
+    hipLaunchKernelGGL((view_scores_kernel<R, C, U, true>), dim3((unsigned)grid), dim3(256), 0, stream, X, q, row_src,
+                       scores, (int)n);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+}  // namespace
+
+// scores[j] = <X[row_src[j], :], q> for j < n_view: the bits launch_scan gives row row_src[j].  row_src [n_view] i32
+// (device), every entry a row of X; the rows per group are launch_scan's defaults.
+ssw_status launch_scan_view(const void *X, int32_t dtype, const float *q_dev, const int32_t *row_src, float *scores,
+                            int64_t n_view, int32_t dim, int device, hipStream_t stream) {
+    if (n_view <= 0) return SSW_OK;
+    if (n_view >= (int64_t)0x7fff0000) {
+        set_error("scan: a view of %lld rows exceeds the 2^31 row limit of one index shard", (long long)n_view);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    if (dtype == SSW_DTYPE_F16) {
+        switch (dim) {
+            case 256: return launch_view_t<H16Rows, 1, 16>(X, q_dev, row_src, scores, n_view, device, stream);
+            case 512: return launch_view_t<H16Rows, 2, 4>(X, q_dev, row_src, scores, n_view, device, stream);
+            case 768: return launch_view_t<H16Rows, 3, 4>(X, q_dev, row_src, scores, n_view, device, stream);
+            case 1024: return launch_view_t<H16Rows, 4, 4>(X, q_dev, row_src, scores, n_view, device, stream);
+        }
+    } else {
+        switch (dim) {
+            case 256: return launch_view_t<F32Rows, 1, 8>(X, q_dev, row_src, scores, n_view, device, stream);
+            case 512: return launch_view_t<F32Rows, 2, 2>(X, q_dev, row_src, scores, n_view, device, stream);
+            case 768: return launch_view_t<F32Rows, 3, 2>(X, q_dev, row_src, scores, n_view, device, stream);
+            case 1024: return launch_view_t<F32Rows, 4, 2>(X, q_dev, row_src, scores, n_view, device, stream);
         }
     }
     set_error("scan: dim=%d unsupported (need a multiple of 256, <= 1024)", dim);

@@ -133,6 +133,12 @@ int index_device(const ssw_index *idx);
 // a handle without index_handle.h (feedback gathers; k-NN and X'LX refuse an f16 matrix)
 int32_t index_dtype(const ssw_index *idx);
 const void *index_matrix(const ssw_index *idx, int64_t *n_rows, int32_t *dim);
+// A view (ssw_index_create_view) reads its rows out of its parent's matrix through a row table.  refuse_view: the one
+// refusal of every entry that would read or write the matrix with the view's own row numbers (SSW_ERR_UNSUPPORTED, the
+// message names `who` and says "view").  index_view_rows: the parent row of each view row (host, [n]), NULL for an
+// index that is not a view; index_matrix then reports the PARENT's row count.
+ssw_status refuse_view(const ssw_index *idx, const char *who);
+const int32_t *index_view_rows(const ssw_index *idx);
 
 // ---- the f16 index's row layout ---------------------------------------------------------------------------------
 // A row of dim = 256*C binary16 elements is stored LANE-INTERLEAVED: the 4*C elements scan lane l works on
@@ -161,6 +167,9 @@ ssw_status launch_scan(const void *X, int32_t dtype, const float *q_dev, float *
                        int device, hipStream_t stream);
 ssw_status launch_score_rows(const void *X, int32_t dtype, const float *q_dev, const int64_t *rows_dev, int64_t n,
                              int32_t dim, float *out, hipStream_t stream);
+// the scan of a view (ssw_index_create_view): scores[j] = dot(X[row_src[j],:], q), the bits launch_scan gives that row
+ssw_status launch_scan_view(const void *X, int32_t dtype, const float *q_dev, const int32_t *row_src, float *scores,
+                            int64_t n_view, int32_t dim, int device, hipStream_t stream);
 // the multi-query form: slabs[b][i] = dot(X[i,:], qb_dev[b,:]) for b < nb in ONE pass over the rows, per query the bits
 // of launch_scan.  nb = 2, 4, 8 or 16, at most scan_batch_max_width(n, dim, dtype) (1 = this shape has no batched kernel)
 int scan_batch_max_width(int64_t n, int32_t dim, int32_t dtype);

@@ -47,6 +47,21 @@ def round_vectors(vectors: np.ndarray, dtype) -> np.ndarray:
     return np.ascontiguousarray(vectors, dtype=np.float32)
 
 
+def view_rows(row_start: np.ndarray, positions: np.ndarray):
+    """the rows of a view of the images `positions` (strictly ascending) of an index whose image p holds the rows
+    [row_start[p], row_start[p + 1]): -> (parent_rows int64 [n_view], the view's own row_start int64 [m + 1]) -- what
+    ssw_index_create_view builds on the host (row_start = np.arange(n + 1) for an index without an image map)"""
+    row_start = np.asarray(row_start, dtype=np.int64)
+    positions = np.asarray(positions, dtype=np.int64).reshape(-1)
+    if positions.size == 0 or positions[0] < 0 or positions[-1] >= row_start.shape[0] - 1 or np.any(np.diff(positions) <= 0):
+        raise ValueError("positions must be strictly ascending image positions of the index, at least one")
+    counts = row_start[positions + 1] - row_start[positions]
+    start = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
+    # row j of image i of the view: row_start[positions[i]] + (j - start[i])
+    parent_rows = np.repeat(row_start[positions] - start[:-1], counts) + np.arange(start[-1], dtype=np.int64)
+    return parent_rows, start
+
+
 class DeviceIndex:
     def __init__(self, n_rows: int, dim: int = 512, device: int = 0, dev_ptr: int = 0, dtype=np.float32):
         self._h = ctypes.c_void_p()
@@ -101,9 +116,37 @@ class DeviceIndex:
         _lib.call("ssw_index_set_row2image", self._h, _ptr(r2i), n_images)
         self.n_images = n_images
 
+    # -- zero-copy subset views -------------------------------------------------------
+    is_view = False  # a view scans its member rows in place, out of `parent`'s matrix
+    parent: Optional["DeviceIndex"] = None
+    parent_rows: Optional[np.ndarray] = None  # int64 [n_rows]: the parent row of every row of the view
+
+    def view(self, image_positions) -> "DeviceIndex":
+        """a DeviceIndex over the rows of the given images (positions of this index, strictly ascending; row positions
+        for an index without an image map) that reads them out of THIS index's resident matrix
+        (ssw_index_create_view): no rows are copied, the view holds a 4-byte row table, its own score buffer, selection
+        workspace and image map, and returns what `from_numpy(X[rows], row2image=compact)` returns, bit for bit.  It
+        sees this index's current rows and keeps it alive; `close()` of this index is refused while a view is open.
+        What reads or writes the matrix by row number (upload, download, the batched entries, knn, ...) raises on a
+        view; `score_rows` / `gather_rows` take the view's rows.  Close views before their parent: `__del__` cannot
+        raise, so a parent that is collected while a view is still open (interpreter shutdown, a reference cycle) keeps
+        its device memory until the process ends -- the refusal is silent there."""
+        pos = np.ascontiguousarray(image_positions, dtype=np.int64).reshape(-1)
+        v = object.__new__(DeviceIndex)
+        v._h = ctypes.c_void_p()
+        _lib.call("ssw_index_create_view", self._h, _ptr(pos), pos.shape[0], ctypes.byref(v._h))
+        n_rows, dim, n_images = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int64(0)
+        _lib.call("ssw_index_shape", v._h, ctypes.byref(n_rows), ctypes.byref(dim), ctypes.byref(n_images))
+        v.n_rows, v.dim, v.n_images = int(n_rows.value), int(dim.value), int(n_images.value)
+        v.device, v.dtype = self.device, self.dtype
+        v.is_view, v.parent = True, self
+        v.parent_rows = np.empty(v.n_rows, dtype=np.int64)
+        _lib.call("ssw_index_view_rows", v._h, _ptr(v.parent_rows))
+        return v
+
     def close(self):
         if self._h:
-            _lib.load().ssw_index_destroy(self._h)
+            _lib.check(_lib.load().ssw_index_destroy(self._h))  # refused while views of this index are open
             self._h = ctypes.c_void_p()
 
     def __del__(self):

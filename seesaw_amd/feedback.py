@@ -73,7 +73,8 @@ class FeedbackEngine:
         """gather the labelled rows out of the index matrix already resident in HBM."""
         rows = np.ascontiguousarray(rows, dtype=np.int64)
         self.n = rows.shape[0]
-        if getattr(device_index, "dtype", np.float32) == np.float16:  # the handle tells the gather the element type
+        if getattr(device_index, "dtype", np.float32) == np.float16 or getattr(device_index, "is_view", False):
+            # the handle tells the gather the element type and, for a view, the rows' places in the parent's matrix
             _lib.call("ssw_fb_set_data_from_index", self._h, device_index._h, _p(rows), self.n, int(center))
             return
         vec_ptr, _ = device_index.device_ptrs()

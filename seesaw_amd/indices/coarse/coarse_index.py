@@ -31,9 +31,11 @@ def _positions_of(sorted_dbidx: np.ndarray, ids) -> np.ndarray:
 
 class CoarseIndex(AccessMethod):
     def __init__(self, embedding, vectors: np.ndarray, vector_meta: pd.DataFrame, path: str = None,
-                 device: int = 0, vector_dtype: str = "float32"):
+                 device: int = 0, vector_dtype: str = "float32", _view_of=None):
         """vector_dtype="float16": the resident matrix is binary16 and `self.vectors` holds the widened rounded rows
-        (what every host-side expression then reads is what the device scans)"""
+        (what every host-side expression then reads is what the device scans).  `_view_of` (subset_view): (the parent's
+        DeviceIndex, the member images' positions in it) -- the device index is then a view of the parent's resident
+        rows, not an upload of `vectors`"""
         self.path = path
         self.embedding = embedding
         self.vector_dtype = _vector_dtype(vector_dtype)
@@ -44,7 +46,11 @@ class CoarseIndex(AccessMethod):
         self._dbidx = dbidx
         self.all_indices = FrozenBitMap(dbidx)
         self.device = device
-        self._dev = DeviceIndex.from_numpy(self.vectors, device=device, dtype=self.vector_dtype)
+        if _view_of is not None:
+            self._dev = _view_of[0].view(_view_of[1])
+            assert self._dev.n_rows == self.vectors.shape[0]
+        else:
+            self._dev = DeviceIndex.from_numpy(self.vectors, device=device, dtype=self.vector_dtype)
 
     def __len__(self):
         return len(self.all_indices)
@@ -93,13 +99,16 @@ class CoarseIndex(AccessMethod):
 
     def query_batch(self, *, topk, vectors, excludes=None, prune=False, **kwargs):
         """one `DeviceIndex.topk_batch` call for the vectors that are given: the list of dicts `query` returns, entry by
-        entry identical to it.  A `None` vector (random order) and a query whose exclude set covers the whole index
+        entry identical to it (on a subset_view index a loop over `query`: a view has no batched scan).  A `None`
+        vector (random order) and a query whose exclude set covers the whole index
         keep going through `query`.  `prune` is `DeviceIndex.topk_batch`'s: the same results from the shared int8
         pre-scan on an index large enough for it."""
         vectors = list(vectors)
         excludes = [None] * len(vectors) if excludes is None else list(excludes)
         if len(excludes) != len(vectors):
             raise ValueError(f"excludes has {len(excludes)} entries for {len(vectors)} vectors")
+        if getattr(self._dev, "is_view", False):
+            return [self.query(topk=topk, vector=v, exclude=e, **kwargs) for v, e in zip(vectors, excludes)]
         out = [None] * len(vectors)
         n = self._dbidx.shape[0]
         excl_pos = [_positions_of(self._dbidx, np.asarray(BitMap() if e is None else e, dtype=np.int64)) for e in excludes]
@@ -129,6 +138,18 @@ class CoarseIndex(AccessMethod):
         return CoarseIndex(embedding=self.embedding, vectors=self.vectors[mask],
                            vector_meta=self.vector_meta[mask].reset_index(drop=True), device=self.device,
                            vector_dtype=self.vector_dtype)
+
+    def subset_view(self, indices: BitMap):
+        """`subset(indices)` whose device index is a view of this index's resident rows (DeviceIndex.view): no second
+        copy of the member rows in HBM, no upload, the same results bit for bit; all of the index is the index itself"""
+        mask = np.isin(self._dbidx, np.asarray(indices, dtype=np.int64))
+        if mask.all():
+            return self
+        if getattr(self._dev, "is_view", False):
+            raise NotImplementedError("subset_view of a subset view: take it from the index that holds the rows")
+        return CoarseIndex(embedding=self.embedding, vectors=self.vectors[mask],
+                           vector_meta=self.vector_meta[mask].reset_index(drop=True), device=self.device,
+                           vector_dtype=self.vector_dtype, _view_of=(self._dev, np.nonzero(mask)[0]))
 
 
 class CoarseQuery(InteractiveQuery):

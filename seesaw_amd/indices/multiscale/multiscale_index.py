@@ -171,10 +171,11 @@ class MultiscaleIndex(AccessMethod):
 
     def __init__(self, *, embedding, vectors: np.ndarray, vector_meta: pd.DataFrame, vec_index=None,
                  min_zoom_level=1, path: str = None, excluded: BitMap = None, device: int = 0,
-                 vector_dtype: str = "float32"):
+                 vector_dtype: str = "float32", _view_of=None):
         """vector_dtype="float16": the resident matrix is binary16 (half the HBM) and `self.vectors` holds the widened
         rounded rows, so every host-side expression (`index.vectors[rows]` of the fitting loops) reads the numbers the
-        device scans"""
+        device scans.  `_view_of` (subset_view): (the parent's DeviceIndex, the member images' positions in it) -- the
+        device index is then a view of the parent's resident rows, not an upload of `vectors`"""
         from ...device_index import vector_dtype as _vector_dtype
         self.embedding = embedding
         self.vector_dtype = _vector_dtype(vector_dtype)
@@ -202,12 +203,19 @@ class MultiscaleIndex(AccessMethod):
         self._has_tile_meta = "zoom_level" in self.vector_meta and int(self.vector_meta.zoom_level.max()) <= 31 \
             and int(self.vector_meta.zoom_level.min()) >= 0 and self._box.dtype == np.float32
         self._resident_q = None
+        self._view_of = _view_of
         self._init_device()
 
     def _init_device(self):
-        """the whole matrix into HBM (a sharded index overrides this with its own slice)"""
-        self._dev = DeviceIndex.from_numpy(self.vectors, row2image=self._row2pos.astype(np.int32), device=self.device,
-                                           dtype=self.vector_dtype)
+        """the whole matrix into HBM (a sharded index overrides this with its own slice); for subset_view's index a
+        view of the parent's resident rows"""
+        if self._view_of is not None:
+            parent_dev, positions = self._view_of
+            self._dev = parent_dev.view(positions)
+            assert self._dev.n_rows == self.vectors.shape[0] and self._dev.n_images == self._dbidx.shape[0]
+        else:
+            self._dev = DeviceIndex.from_numpy(self.vectors, row2image=self._row2pos.astype(np.int32), device=self.device,
+                                               dtype=self.vector_dtype)
         if self._has_tile_meta:  # tile geometry next to the vectors: the avg_score aggregation runs on the device
             self._dev.set_tile_meta(self._box, self.vector_meta.zoom_level.values)
 
@@ -325,7 +333,8 @@ class MultiscaleIndex(AccessMethod):
 
     def query_batch(self, *, topk, vectors, excludes=None, prune=False, **kwargs):
         """`[query(vector=v, topk=topk, exclude=e, **kwargs) for v, e in zip(vectors, excludes)]`, entry by entry
-        identical to it, with the rows read once per chunk of up to 16 queries: `plain_score` ends in
+        identical to it (on a subset_view index exactly that loop: a view has no batched scan),
+        with the rows read once per chunk of up to 16 queries: `plain_score` ends in
         `DeviceIndex.topk_batch`, every other agg_method in `DeviceIndex.topk_batch_avg`, whose second stage reads each
         query's own score slab while the chunk is alive (one k = the largest shortlist of the batch; each query keeps
         its own first min(shortlist_size, included) candidates).  Entries that keep going through `query`: no vector,
@@ -346,7 +355,7 @@ class MultiscaleIndex(AccessMethod):
         plain = kwargs.get("agg_method") == "plain_score"
         on_device = plain or (self._has_tile_meta and
                               int(np.diff(self._row_start).max(initial=0)) <= DeviceIndex.RESCORE_MAX_TILES)
-        if kwargs.get("vector2") is not None or not on_device or "shortlist_size" not in kwargs:
+        if kwargs.get("vector2") is not None or not on_device or "shortlist_size" not in kwargs or getattr(self._dev, "is_view", False):
             return super().query_batch(topk=topk, vectors=vectors, excludes=excludes, **kwargs)
         shortlist_size = kwargs["shortlist_size"]
         if shortlist_size is None:
@@ -453,6 +462,22 @@ class MultiscaleIndex(AccessMethod):
         return MultiscaleIndex(embedding=self.embedding, vectors=self.vectors[mask],
                                vector_meta=self.vector_meta[mask].reset_index(drop=True), vec_index=None,
                                device=self.device, vector_dtype=self.vector_dtype)
+
+    def subset_view(self, indices: BitMap) -> AccessMethod:
+        """`subset(indices)` without a second copy of the rows in HBM: the same index object (vector_meta, len, host
+        `vectors` for get_data / getXy, its own tile meta) whose device index is a view of this index's resident matrix
+        (DeviceIndex.view) -- no host-to-device copy of the member rows, 4 bytes a row of device memory beside the
+        score buffer, the same results bit for bit.  The view index keeps this index's device index alive; a subset
+        view of a subset view is taken from the original index."""
+        mask = np.isin(self._row_dbidx, np.asarray(indices, dtype=np.int64))
+        if mask.all():
+            return self
+        if getattr(self._dev, "is_view", False):
+            raise NotImplementedError("subset_view of a subset view: take it from the index that holds the rows")
+        positions = np.unique(self._row2pos[mask])  # the member images' positions in this index's device index
+        return MultiscaleIndex(embedding=self.embedding, vectors=self.vectors[mask],
+                               vector_meta=self.vector_meta[mask].reset_index(drop=True), vec_index=None,
+                               device=self.device, vector_dtype=self.vector_dtype, _view_of=(self._dev, positions))
 
 
 class BoxFeedbackQuery(InteractiveQuery):

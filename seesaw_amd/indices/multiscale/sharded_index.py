@@ -518,6 +518,9 @@ class ShardedMultiscaleIndex(MultiscaleIndex):
     def subset(self, indices):
         raise NotImplementedError("subset of a sharded index")
 
+    def subset_view(self, indices):
+        raise NotImplementedError("subset view of a sharded index")
+
     def close(self):
         if self._shard is not None:
             self._shard.close()

@@ -171,8 +171,11 @@ def compute_exact_knn(vectors: np.ndarray, n_neighbors: int, device_index=None, 
     from .device_index import DeviceIndex
     n = vectors.shape[0]
     k = min(n_neighbors + 1, n) - 1
-    if device_index is not None and getattr(device_index, "dtype", np.float32) != np.float32:
-        device_index = None  # the build reads f32 rows: a temporary f32 copy of the (widened) host rows
+    if device_index is not None and (getattr(device_index, "dtype", np.float32) != np.float32 or
+                                     getattr(device_index, "is_view", False)):
+        # the build reads f32 rows of a matrix of its own: a temporary f32 copy of the (widened) host rows, for an f16
+        # index and for a view of another index's rows
+        device_index = None
     dev = device_index if device_index is not None else DeviceIndex.from_numpy(
         np.ascontiguousarray(vectors, dtype=np.float32), device=device)
     try:

@@ -43,8 +43,9 @@ def compute_xlx(laplacian, X_vectors: np.ndarray, device_index=None) -> np.ndarr
     from ..label_propagation import LabelPropagation
     L = sp.csr_array(laplacian / laplacian.diagonal().sum())
     L.sort_indices()
-    if device_index is not None and getattr(device_index, "dtype", np.float32) != np.float32:
-        device_index = None  # X'LX reads f32 rows: a temporary f32 copy of the (widened) host rows
+    if device_index is not None and (getattr(device_index, "dtype", np.float32) != np.float32 or
+                                     getattr(device_index, "is_view", False)):
+        device_index = None  # X'LX reads f32 rows of a matrix of its own: a temporary f32 copy of the (widened) host rows
     dev = device_index if device_index is not None else DeviceIndex.from_numpy(np.ascontiguousarray(X_vectors, dtype=np.float32))
     lap = LabelPropagation(L, reg_lambda=0.0, max_iter=0, device=dev.device)
     out = np.empty((dev.dim, dev.dim), dtype=np.float64)

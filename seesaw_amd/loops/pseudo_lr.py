@@ -67,7 +67,8 @@ class PseudoLR(PointBased):
         scorer = LogisticRegressionPT(regularizer_vector=self.state.tvec, device=getattr(self.index, "device", 0), **params)
         dev = getattr(self.index, "_dev", None)
         on_device = (dev is not None and lp is not None and getattr(model, "_label_map", None) is not None
-                     and getattr(model, "scores_on_device", lambda: False)() and params.get("class_weights") != "balanced")
+                     and getattr(model, "scores_on_device", lambda: False)() and params.get("class_weights") != "balanced"
+                     and not getattr(dev, "is_view", False))  # (a view's rows are not drawn by row number on the device)
         if on_device:
             # the training set never exists on the host: labelled rows + labels and the draw go down, the drawn rows'
             # propagated scores become their targets on the device (ssw_fb_set_pseudo_sample) -- makeXy_rows' values, rows
