@@ -160,12 +160,12 @@ ssw_status ssw_index_topk(ssw_index *idx, const float *q_host, const int64_t *ex
                           int64_t n_excluded, int32_t k, int64_t *out_images, float *out_scores,
                           int64_t *out_best_rows, int32_t *out_count);
 /* Several queries in ONE pass over the rows.  The scan is bound by HBM: a row that sits in registers for one query
- * scores a second, a fourth, a sixteenth one for almost no extra traffic.  At dim 512 and >= 65 536 rows (f32 and f16
- * rows) a batch is cut into chunks of 16 queries for f32 rows and 8 for f16 rows (the widths with the lowest measured
- * time per query), the remainder into chunks of 8, 4 and 2 and at last a single query, and every chunk is one launch
- * of the multi-query scan kernel; the other dims (256, 768, 1024) and smaller indexes are served by one single-query
- * scan launch per query.  Either way query b's scores are the BITS ssw_index_scan returns for q[b].  Any nq >= 1;
- * nq == 1 IS the single-query call.
+ * scores a second, a fourth, a sixteenth one for almost no extra traffic.  From 65 536 rows on (f32 and f16 rows,
+ * every dim) a batch is cut into chunks of the width with the lowest measured time per query for the shape -- f32 / f16
+ * rows: 16 / 16 queries at dim 256, 16 / 8 at dims 512 and 768, 8 / 8 at dim 1024 --, the remainder into chunks of 8,
+ * 4 and 2 and at last a single query, and every chunk is one launch of the multi-query scan kernel; smaller indexes
+ * are served by one single-query scan launch per query.  Either way query b's scores are the BITS ssw_index_scan
+ * returns for q[b].  Any nq >= 1; nq == 1 IS the single-query call.
  *
  * ssw_index_scan_batch: scores[b, :] = vectors @ q[b].  q_host [nq, dim], out_scores_host [nq, n_rows] (may be NULL:
  * nothing is copied back).  Afterwards the resident scores are those of the LAST query, as after ssw_index_scan(q[nq-1]).

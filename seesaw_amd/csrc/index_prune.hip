@@ -63,8 +63,9 @@ constexpr int64_t MIN_ROWS[2][2][2][2] = {
       // the rule does not admit it; at 2^23 f32 rows it is ahead by 0.008 with spreads of 0.003, which a size above
       // that fails does not carry.
       {25000000, 25000000},
-      // Dim 768, tools/perf_prune_batch.py --dim 768 --nq 16 4 (profiles/prune6_dim768_batch.txt; the plain batch there
-      // is a loop of full scans, scan_batch_max_width is 1 off dim 512): ahead at every size, at nq = 16 and nq = 4.
+      // Dim 768, tools/perf_prune_batch.py --dim 768 --nq 16 4 (profiles/prune6_dim768_batch.txt; the plain batch was
+      // a loop of full scans when this was measured; against the multi-query kernel the dim has now:
+      // profiles/batch_dims_ab.txt): ahead at every size, at nq = 16 and nq = 4.
       // f32, 2^20 rows: 0.115 against 0.562 ms a query at nq = 16 (spreads 0.008), 0.144 against 0.651 at nq = 4
       // (0.019); 50 M rows: 0.651 against 24.837 and 1.615 against 28.876.  f16, 2^20 rows: 0.110 against 0.336 (0.005)
       // and 0.138 against 0.385 (0.008).

@@ -614,6 +614,29 @@ ssw_status launch_scan_t(const void *Xv, const float *q, float *scores, int64_t 
 // two four-wave blocks per CU (the second block hides what one wave's exchange chain leaves idle).
 constexpr int SCAN_BATCH_MAX_F32 = 16, SCAN_BATCH_MAX_F16 = 8;
 constexpr int SCAN_BATCH_BLOCKS_PER_CU = 2;
+// The same per dim: the product's width (`f32`, `f16`) and the widest instance launch_scan_batch has (`*_built`, what a
+// wider request of the lab hook is clamped to).  Off dim 512 the instances are those whose code object uses no scratch
+// (profiles/batch_dims_resource_usage.txt): a lane holds B * C float4 of queries, so four chunks end at a width of 8,
+// and three chunks take 16 only past 256 registers (copies in AGPRs, one block a CU resident).  The product's width is
+// the one with the lowest time per query in profiles/batch_dims_sweep.txt, ahead of the next narrower one by more than
+// the run-to-run spread at 2^20, 12.5 M and (dim 768) 50 M rows ("Batched scan at dims 256 / 768
+// / 1024"): at 12.5 M rows and two blocks a CU, ms a query at 16 against 8 -- dim 256 0.277 / 0.300 (f32) and 0.257 /
+// 0.275 (f16), dim 768 f32 0.694 / 0.766; dim 768 f16 is slower at 16 (0.742 / 0.507).
+struct ScanBatchWidths {
+    int32_t dim;
+    int f32, f16, f32_built, f16_built;
+};
+constexpr ScanBatchWidths SCAN_BATCH_WIDTHS[] = {
+    {256, 16, 16, 16, 16},
+    {512, SCAN_BATCH_MAX_F32, SCAN_BATCH_MAX_F16, 16, 16},
+    {768, 16, 8, 16, 16},
+    {1024, 8, 8, 8, 8},
+};
+constexpr const ScanBatchWidths *scan_batch_widths(int32_t dim) {
+    for (const ScanBatchWidths &w : SCAN_BATCH_WIDTHS)
+        if (w.dim == dim) return &w;
+    return nullptr;
+}
 SSW_TUNABLE int g_scan_batch_max = -1;  // tuning hook (ssw_tune_scan_batch): -1 = the product's widths
 SSW_TUNABLE int g_scan_batch_blocks_per_cu = SCAN_BATCH_BLOCKS_PER_CU;  // the same hook: four-wave blocks per CU
 
@@ -751,12 +774,16 @@ ssw_status launch_scan_view(const void *X, int32_t dtype, const float *q_dev, co
     return SSW_ERR_UNSUPPORTED;
 }
 
-// The widest batch launch_scan_batch takes for this shape: the multi-query kernel serves dim 512 from the streaming
-// kernel's range on; 1 = every query goes through launch_scan.
+// The widest batch launch_scan_batch takes for this shape: the multi-query kernel serves every dim of the width table
+// from the streaming kernel's range on; 1 = every query goes through launch_scan.  A width asked for through the lab
+// hook is clamped to the widest instance of the shape, so that a chunk is never refused in the middle of a batch.
 int scan_batch_max_width(int64_t n, int32_t dim, int32_t dtype) {
-    if (dim != 512 || n < SCAN_SMALL_ROWS || n >= (int64_t)0x7fff0000) return 1;
-    if (g_scan_batch_max > 0) return g_scan_batch_max;
-    return dtype == SSW_DTYPE_F16 ? SCAN_BATCH_MAX_F16 : SCAN_BATCH_MAX_F32;
+    const ScanBatchWidths *w = scan_batch_widths(dim);
+    if (w == nullptr || n < SCAN_SMALL_ROWS || n >= (int64_t)0x7fff0000) return 1;
+    const bool h16 = dtype == SSW_DTYPE_F16;
+    const int built = h16 ? w->f16_built : w->f32_built;
+    if (g_scan_batch_max > 0) return g_scan_batch_max < built ? g_scan_batch_max : built;
+    return h16 ? w->f16 : w->f32;
 }
 
 // slabs[b][i] = <X[i,:], qb[b,:]> for b < nb (a power of two, 2 <= nb <= scan_batch_max_width): the bits of launch_scan
@@ -769,20 +796,73 @@ ssw_status launch_scan_batch(const void *X, int32_t dtype, const float *qb_dev, 
         return SSW_ERR_UNSUPPORTED;
     }
     const bool h16 = dtype == SSW_DTYPE_F16;
-    switch (nb) {
-        case 2:
-            return h16 ? launch_scan_batch_t<H16Rows, 2, 4, 2>(X, qb_dev, slabs, n, device, stream)
-                       : launch_scan_batch_t<F32Rows, 2, 2, 2>(X, qb_dev, slabs, n, device, stream);
-        case 4:
-            return h16 ? launch_scan_batch_t<H16Rows, 2, 4, 4>(X, qb_dev, slabs, n, device, stream)
-                       : launch_scan_batch_t<F32Rows, 2, 2, 4>(X, qb_dev, slabs, n, device, stream);
-        case 8:
-            return h16 ? launch_scan_batch_t<H16Rows, 2, 4, 8>(X, qb_dev, slabs, n, device, stream)
-                       : launch_scan_batch_t<F32Rows, 2, 2, 8>(X, qb_dev, slabs, n, device, stream);
-        case 16:
-            return h16 ? launch_scan_batch_t<H16Rows, 2, 4, 16>(X, qb_dev, slabs, n, device, stream)
-                       : launch_scan_batch_t<F32Rows, 2, 2, 16>(X, qb_dev, slabs, n, device, stream);
+    // <row format, chunks, rows a group, width>.  Rows a group: launch_scan's value at the dim, halved where U * B would
+    // pass the 64 partials of one reduce (dim 256) or the registers ask for it.
+#define SSW_BATCH_ARGS (X, qb_dev, slabs, n, device, stream)
+    switch (dim) {
+        case 256:
+            switch (nb) {
+                case 2:
+                    return h16 ? launch_scan_batch_t<H16Rows, 1, 16, 2> SSW_BATCH_ARGS
+                               : launch_scan_batch_t<F32Rows, 1, 8, 2> SSW_BATCH_ARGS;
+                case 4:
+                    return h16 ? launch_scan_batch_t<H16Rows, 1, 16, 4> SSW_BATCH_ARGS
+                               : launch_scan_batch_t<F32Rows, 1, 8, 4> SSW_BATCH_ARGS;
+                case 8:
+                    return h16 ? launch_scan_batch_t<H16Rows, 1, 8, 8> SSW_BATCH_ARGS
+                               : launch_scan_batch_t<F32Rows, 1, 8, 8> SSW_BATCH_ARGS;
+                case 16:
+                    return h16 ? launch_scan_batch_t<H16Rows, 1, 4, 16> SSW_BATCH_ARGS
+                               : launch_scan_batch_t<F32Rows, 1, 4, 16> SSW_BATCH_ARGS;
+            }
+            break;
+        case 512:
+            switch (nb) {
+                case 2:
+                    return h16 ? launch_scan_batch_t<H16Rows, 2, 4, 2> SSW_BATCH_ARGS
+                               : launch_scan_batch_t<F32Rows, 2, 2, 2> SSW_BATCH_ARGS;
+                case 4:
+                    return h16 ? launch_scan_batch_t<H16Rows, 2, 4, 4> SSW_BATCH_ARGS
+                               : launch_scan_batch_t<F32Rows, 2, 2, 4> SSW_BATCH_ARGS;
+                case 8:
+                    return h16 ? launch_scan_batch_t<H16Rows, 2, 4, 8> SSW_BATCH_ARGS
+                               : launch_scan_batch_t<F32Rows, 2, 2, 8> SSW_BATCH_ARGS;
+                case 16:
+                    return h16 ? launch_scan_batch_t<H16Rows, 2, 4, 16> SSW_BATCH_ARGS
+                               : launch_scan_batch_t<F32Rows, 2, 2, 16> SSW_BATCH_ARGS;
+            }
+            break;
+        case 768:
+            switch (nb) {
+                case 2:
+                    return h16 ? launch_scan_batch_t<H16Rows, 3, 4, 2> SSW_BATCH_ARGS
+                               : launch_scan_batch_t<F32Rows, 3, 2, 2> SSW_BATCH_ARGS;
+                case 4:
+                    return h16 ? launch_scan_batch_t<H16Rows, 3, 4, 4> SSW_BATCH_ARGS
+                               : launch_scan_batch_t<F32Rows, 3, 2, 4> SSW_BATCH_ARGS;
+                case 8:
+                    return h16 ? launch_scan_batch_t<H16Rows, 3, 4, 8> SSW_BATCH_ARGS
+                               : launch_scan_batch_t<F32Rows, 3, 2, 8> SSW_BATCH_ARGS;
+                case 16:  // 48 float4 of queries a lane: no scratch, but past 256 registers (one block a CU at most)
+                    return h16 ? launch_scan_batch_t<H16Rows, 3, 2, 16> SSW_BATCH_ARGS
+                               : launch_scan_batch_t<F32Rows, 3, 1, 16> SSW_BATCH_ARGS;
+            }
+            break;
+        case 1024:
+            switch (nb) {
+                case 2:
+                    return h16 ? launch_scan_batch_t<H16Rows, 4, 4, 2> SSW_BATCH_ARGS
+                               : launch_scan_batch_t<F32Rows, 4, 2, 2> SSW_BATCH_ARGS;
+                case 4:
+                    return h16 ? launch_scan_batch_t<H16Rows, 4, 4, 4> SSW_BATCH_ARGS
+                               : launch_scan_batch_t<F32Rows, 4, 2, 4> SSW_BATCH_ARGS;
+                case 8:  // 32 float4 of queries a lane: half launch_scan's rows a group keeps two blocks a CU
+                    return h16 ? launch_scan_batch_t<H16Rows, 4, 2, 8> SSW_BATCH_ARGS
+                               : launch_scan_batch_t<F32Rows, 4, 1, 8> SSW_BATCH_ARGS;
+            }
+            break;
     }
+#undef SSW_BATCH_ARGS
     set_error("scan_batch: width %d has no kernel in this build", nb);
     return SSW_ERR_UNSUPPORTED;
 }

@@ -19,7 +19,7 @@ for memory ran the plain batch and is reported as `"resident": false`.
 
 --dim D (default 512): the width of the index.  --dim 768 (how MIN_ROWS (6-bit batch, dim 768, f32 and f16) are chosen): that
 dim has the 6-bit shadow alone, so --shadow is taken as `six` whatever was given, the comparison is the 6-bit batch
-against the plain batch (at that dim a loop of full scans) and the pruned singles, there is no int8 column, and the
+against the plain batch and the pruned singles, there is no int8 column, and the
 JSON line carries "dim".  Every other dim prints what it printed before the option existed."""
 import argparse
 import ctypes
