@@ -477,6 +477,11 @@ ssw_status ssw_index_profile_read(ssw_index *idx, float *out_ms, int32_t cap, in
  * rows on, f32 or f16, single queries and pruned batches alike (the smallest size measured; the pruned call is ahead of
  * the full scan at every one); it never gets an int8 shadow, and below that count, or when the shadow is refused for
  * memory, every call is the full-precision one.  [0] and [5] then report that shadow.
+ * From 25 M rows on, single queries on an f32 index of dim 512 or 1024 that has no image map at the time of the call
+ * scan a packed 5-bit shadow instead of the 6-bit one -- 5 dim / 8 + 8 = 328 bytes a row at dim 512, (n + 15) / 16 * 16
+ * rows of it -- and raise the threshold to the k-th exact score of max(1024, 4 k) candidates before the survivors are
+ * listed; such an index builds no 6-bit shadow for single queries (a pruned batch still builds its own), [0] reports
+ * the 5-bit shadow and [5] includes its bytes.  Refused for memory, it leaves the 6-bit and then the int8 path.
  * out6: [0] shadow 0 none / 1 current / 2 stale / 3 refused (memory), [1] 1 = the next top-k with a query is pruned,
  * [2] survivors of the last pruned call (-1 = it fell back), [3] pruned calls, [4] fallbacks, [5] shadow bytes. */
 ssw_status ssw_index_prune_stats(ssw_index *idx, int64_t *out6);

@@ -108,6 +108,33 @@ ssw_status ssw_debug_prune_maxima(ssw_index *idx, int32_t six, float *out2);
 ssw_status ssw_debug_prune6_survivors(ssw_index *idx, float threshold, int32_t k, int32_t sel_count, int32_t sel_overflow,
                                       int64_t cap, int32_t *out_published, int64_t *out_collected, int64_t *out_rows);
 
+/* The packed 5-bit shadow that single queries on a large f32 index of dim 512 or 1024 without an image map scan instead
+ * of the 6-bit one, with the threshold raised to the k-th exact score of a thousand candidates (csrc/prune.hip, "5-bit
+ * shadow"; tests/test_prune5_gpu.py).  None of these changes what the hooks above do.
+ * ssw_tune_prune5: enable 0 = no index takes the 5-bit path (A/B in one process); min_rows >= 0 = the smallest index whose
+ *   single queries scan the 5-bit shadow, < 0 = the product's constant again (25 M rows).  ssw_tune_prune(0, ..) still
+ *   switches every pruned path off.
+ * ssw_tune_prune5_scan: the launch shape of k_q5_bounds: four-wave blocks per CU (1 .. 8) and 16-row tiles a wave
+ *   requests at a time (1 or 2 at dim 512, 1 at dim 1024); any other value = the product's (1 block; 2 / 1 tiles at dim
+ *   512 / 1024).  ssw_debug_prune5_scan_shape: the blocks and tiles of the next launch.
+ * ssw_debug_prune5_shadow: builds the 5-bit shadow if it is missing or stale (the product's ensure_shadow -> k_q5_build)
+ *   and copies out, for the rows [first_row, first_row + n_rows): the codes [n_rows, dim] unpacked to int8 in natural
+ *   element order (by q5_fields, the placement function the builder uses), s5_r and a5_r.  NULL outputs are skipped.
+ * ssw_debug_prune5_bounds: k_q6_query + k_q5_bounds through the product's launch functions for one host query; outputs
+ *   as ssw_debug_prune6_bounds, out_I [n] = the exact integer sums of 8 c with 256 d_hi + d_lo.
+ * ssw_debug_prune5_survivors: k_survivors_mq with the 5-bit code norm + k_prune_publish_mq over the bounds of the last
+ *   ssw_debug_prune5_bounds, against a threshold written by hand (the product raises the selection's k-th key to the
+ *   exact threshold first); arguments and outputs as ssw_debug_prune_survivors. */
+ssw_status ssw_tune_prune5(int32_t enable, int64_t min_rows);
+ssw_status ssw_tune_prune5_scan(int32_t blocks_per_cu, int32_t tiles);
+ssw_status ssw_debug_prune5_scan_shape(ssw_index *idx, int32_t *out_blocks, int32_t *out_tiles);
+ssw_status ssw_debug_prune5_shadow(ssw_index *idx, int64_t first_row, int64_t n_rows, int8_t *out_codes, float *out_scale,
+                                   float *out_err);
+ssw_status ssw_debug_prune5_bounds(ssw_index *idx, const float *q_host, int64_t *out_I, float *out_lb, float *out_Qe,
+                                   int8_t *out_codes);
+ssw_status ssw_debug_prune5_survivors(ssw_index *idx, float threshold, int32_t k, int32_t sel_count, int32_t sel_overflow,
+                                      int64_t cap, int32_t *out_published, int64_t *out_collected, int64_t *out_rows);
+
 /* The pruned batch (seesaw_hip.h, ssw_index_topk_batch_pruned).
  * ssw_tune_prune_scan_mq: the launch shape of its shadow scan (k_q8_bounds_mq): four-wave blocks per CU (1 .. 8) and
  *   16-row tiles a wave requests at a time (1, 2 or 4, as far as two register sets of them fit: tiles x dim <= 1024);

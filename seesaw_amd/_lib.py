@@ -193,6 +193,13 @@ _DEBUG_SIGNATURES = {
     "ssw_debug_prune_maxima": (c_i32, [c_void_p, c_i32, c_void_p]),
     "ssw_debug_prune6_survivors": (c_i32, [c_void_p, ctypes.c_float, c_i32, c_i32, c_i32, c_i64, c_i32_p, c_i64_p,
                                            c_void_p]),
+    "ssw_tune_prune5": (c_i32, [c_i32, c_i64]),
+    "ssw_tune_prune5_scan": (c_i32, [c_i32, c_i32]),
+    "ssw_debug_prune5_scan_shape": (c_i32, [c_void_p, c_i32_p, c_i32_p]),
+    "ssw_debug_prune5_shadow": (c_i32, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p]),
+    "ssw_debug_prune5_bounds": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ssw_debug_prune5_survivors": (c_i32, [c_void_p, ctypes.c_float, c_i32, c_i32, c_i32, c_i64, c_i32_p, c_i64_p,
+                                           c_void_p]),
     "ssw_tune_prune6_batch": (c_i32, [c_i64]),
     "ssw_tune_prune6_scan_mq": (c_i32, [c_i32, c_i32]),
     "ssw_debug_prune6_scan_mq_shape": (c_i32, [c_void_p, c_i32_p, c_i32_p]),

@@ -817,6 +817,132 @@ ssw_status ssw_debug_prune6_survivors_mq(ssw_index *idx, int32_t nq, int32_t slo
     return SSW_OK;
 }
 
+// ---- the packed 5-bit shadow of single queries (prune.hip, "5-bit shadow"; tests/test_prune5_gpu.py) ----------------
+static ssw_status require_shadow5(ssw_index *idx, const char *who) {
+    SSW_REQUIRE(prune5_eligible(idx),
+                "the index takes no 5-bit shadow (ssw_tune_prune5, rows, dim, dtype, image map, borrowed or escaped rows)");
+    return require_shadow(idx, who, SHADOW_Q5);
+}
+
+ssw_status ssw_debug_prune5_scan_shape(ssw_index *idx, int32_t *out_blocks, int32_t *out_tiles) {
+    SSW_REQUIRE(idx != nullptr && out_blocks != nullptr && out_tiles != nullptr, "NULL argument");
+    SSW_REQUIRE(q5_dim_supported(idx->dim), "dim=%d has no 5-bit shadow scan", idx->dim);
+    int blocks = 0, tiles = 0;
+    scan_shape(SCAN_Q5, idx->dim, idx->device, idx->n, &blocks, &tiles);
+    *out_blocks = blocks;
+    *out_tiles = tiles;
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_prune5_shadow(ssw_index *idx, int64_t first_row, int64_t n_rows, int8_t *out_codes, float *out_scale,
+                                   float *out_err) {
+    SSW_REQUIRE(idx != nullptr, "idx is NULL");
+    SSW_REQUIRE(first_row >= 0 && n_rows >= 0 && first_row + n_rows <= idx->n, "rows [%lld, +%lld) outside [0, %lld)",
+                (long long)first_row, (long long)n_rows, (long long)idx->n);
+    DeviceGuard guard(idx->device);
+    SSW_TRY(require_shadow5(idx, "prune5_shadow"));
+    if (n_rows == 0) return SSW_OK;
+    const Shadow &s = idx->prune.sh[SHADOW_Q5];
+    const int dim = idx->dim;
+    const size_t tile_bytes = (size_t)16 * dim * 5 / 8;
+    const int64_t tile0 = first_row >> 4, tile1 = (first_row + n_rows - 1) >> 4;
+    std::vector<unsigned char> packed(out_codes ? (size_t)(tile1 - tile0 + 1) * tile_bytes : 0);
+    if (out_codes)
+        SSW_HIP_TRY(hipMemcpyAsync(packed.data(), s.codes + (size_t)tile0 * tile_bytes, packed.size(), hipMemcpyDeviceToHost,
+                                   idx->stream));
+    if (out_scale)
+        SSW_HIP_TRY(hipMemcpyAsync(out_scale, s.scale + first_row, (size_t)n_rows * sizeof(float), hipMemcpyDeviceToHost,
+                                   idx->stream));
+    if (out_err)
+        SSW_HIP_TRY(hipMemcpyAsync(out_err, s.err + first_row, (size_t)n_rows * sizeof(float), hipMemcpyDeviceToHost,
+                                   idx->stream));
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+    if (!out_codes) return SSW_OK;
+    for (int64_t r = first_row; r < first_row + n_rows; ++r) {
+        const unsigned char *tile = packed.data() + (size_t)((r >> 4) - tile0) * tile_bytes;
+        for (int i = 0; i < dim; ++i) {
+            int u, g, j;
+            q6_slot(i, &u, &g, &j);
+            const int lane = 16 * g + (int)(r & 15);
+            Q5Field f[3];
+            const int nf = q5_fields(u, j, f);
+            unsigned bits = 0u;
+            for (int t = 0; t < nf; ++t)
+                bits |= ((tile[q6_word_offset(lane, f[t].word) + (size_t)f[t].byte] >> f[t].lo) & ((1u << f[t].bits) - 1u)) << f[t].from;
+            out_codes[(size_t)(r - first_row) * dim + i] = (int8_t)((int)(bits ^ 16u) - 16);  // five bits, two's complement
+        }
+    }
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_prune5_bounds(ssw_index *idx, const float *q_host, int64_t *out_I, float *out_lb, float *out_Qe,
+                                   int8_t *out_codes) {
+    SSW_REQUIRE(idx != nullptr && q_host != nullptr, "NULL argument");
+    DeviceGuard guard(idx->device);
+    SSW_TRY(require_shadow5(idx, "prune5_bounds"));
+    PruneState &p = idx->prune;
+    const size_t dim = (size_t)idx->dim;
+    int64_t *dbg = nullptr;
+    if (out_I) SSW_HIP_TRY(hipMalloc((void **)&dbg, (size_t)idx->n * sizeof(int64_t)));
+    unsigned st[Q8_MQ_WORDS] = {};
+    std::vector<int8_t> planes(q6_plane_bytes(idx->dim));
+    auto run = [&]() -> ssw_status {
+        SSW_TRY(idx->q_stage.push(idx->q_dev, q_host, dim * sizeof(float), idx->stream));
+        SSW_TRY(prune_bounds(idx, SHADOW_Q5, idx->q_dev, dbg));  // as in scan_for_topk: readers complete the buffer with q_last
+        if (out_I) SSW_HIP_TRY(hipMemcpyAsync(out_I, dbg, (size_t)idx->n * sizeof(int64_t), hipMemcpyDeviceToHost, idx->stream));
+        if (out_lb)
+            SSW_HIP_TRY(hipMemcpyAsync(out_lb, idx->scores, (size_t)idx->n * sizeof(float), hipMemcpyDeviceToHost, idx->stream));
+        SSW_HIP_TRY(hipMemcpyAsync(st, p.state6, sizeof(st), hipMemcpyDeviceToHost, idx->stream));
+        SSW_HIP_TRY(hipMemcpyAsync(planes.data(), p.planes6, planes.size(), hipMemcpyDeviceToHost, idx->stream));
+        SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+        return SSW_OK;
+    };
+    const ssw_status rc = run();
+    if (rc != SSW_OK) (void)hipStreamSynchronize(idx->stream);
+    (void)hipFree(dbg);
+    SSW_TRY(rc);
+    if (out_Qe) {
+        memcpy(out_Qe, &st[1], 4);      // Q
+        memcpy(out_Qe + 1, &st[3], 4);  // e
+        memcpy(out_Qe + 2, &st[4], 4);  // t2
+        out_Qe[3] = (float)st[2];       // 1 = the query cannot be bounded
+    }
+    if (out_codes)  // the operand's columns 0 (hi) and 1 (lo) back to natural element order
+        for (int pl = 0; pl < 2; ++pl)
+            for (size_t i = 0; i < dim; ++i) {
+                int u, g, j;
+                q6_slot((int)i, &u, &g, &j);
+                out_codes[(size_t)pl * dim + i] = planes[(size_t)(u * 64 + g * 16 + pl) * 16 + (size_t)j];
+            }
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_prune5_survivors(ssw_index *idx, float threshold, int32_t k, int32_t sel_count, int32_t sel_overflow,
+                                      int64_t cap, int32_t *out_published, int64_t *out_collected, int64_t *out_rows) {
+    SSW_REQUIRE(idx != nullptr && out_published != nullptr && out_collected != nullptr, "NULL argument");
+    SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
+    SSW_REQUIRE(cap >= 0 && cap <= SURV_CAP, "cap=%lld outside [0, %lld]", (long long)cap, (long long)SURV_CAP);
+    SSW_REQUIRE(cap == 0 || out_rows != nullptr, "out_rows is NULL");
+    SSW_REQUIRE(idx->scores_partial && shadow_current(idx, SHADOW_Q5), "no bounds in the buffer: ssw_debug_prune5_bounds first");
+    DeviceGuard guard(idx->device);
+    SSW_TRY(ensure_ws(idx));
+    unsigned *st = idx->prune.state6;
+    SSW_HIP_TRY(hipMemsetAsync(st, 0, sizeof(unsigned), idx->stream));      // the counter and the "selection failed"
+    SSW_HIP_TRY(hipMemsetAsync(st + 5, 0, sizeof(unsigned), idx->stream));  // word k_q6_query resets
+    SSW_TRY(stand_in_threshold(idx, threshold, k, sel_count, sel_overflow));
+    int32_t m = -1;
+    SSW_TRY(prune_survivors(idx, SHADOW_Q5, k, cap, nullptr, &m));
+    unsigned collected = 0u;
+    SSW_HIP_TRY(hipMemcpyAsync(&collected, st, sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
+    if (m > 0)
+        SSW_HIP_TRY(hipMemcpyAsync(out_rows, idx->prune.surv_rows, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost,
+                                   idx->stream));
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+    *out_published = m;
+    *out_collected = (int64_t)collected;
+    return SSW_OK;
+}
+
 ssw_status ssw_debug_prune6_scan_shape(ssw_index *idx, int32_t *out_blocks, int32_t *out_tiles) {
     SSW_REQUIRE(idx != nullptr && out_blocks != nullptr && out_tiles != nullptr, "NULL argument");
     SSW_REQUIRE(q6_dim_supported(idx->dim), "dim=%d has no shadow scan", idx->dim);

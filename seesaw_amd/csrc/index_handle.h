@@ -9,12 +9,14 @@ constexpr int64_t SMALL_EXCL_CAP = 8192;            // the small form (index_top
 constexpr int64_t SMALL_ROWS = 65536;               // and the small scan kernel's range (scan.hip)
 
 // a shadow of the rows for the certified pre-scan of the top-k (prune.hip): the int8 one, and the packed 6-bit one that
-// single queries scan instead on an index of enough rows (index_prune.hip, MIN_ROWS).  Each is built lazily by the first
-// top-k with a query that wants it after the rows last changed
-enum ShadowKind { SHADOW_Q8, SHADOW_Q6 };
+// single queries scan instead on an index of enough rows, and the packed 5-bit one that single queries on a still larger
+// f32 index without an image map scan instead of that (index_prune.hip, MIN_ROWS, MIN_ROWS_Q5).  Each is built lazily by
+// the first top-k with a query that wants it after the rows last changed
+enum ShadowKind { SHADOW_Q8, SHADOW_Q6, SHADOW_Q5 };
 struct Shadow {
-    unsigned char *codes = nullptr;               // int8: [n, dim] codes; 6-bit: q6_code_bytes(n, dim), tiles of 16 rows
-    float *scale = nullptr, *err = nullptr;       // s_r, a_r: [n]; 6-bit: [q6_padded_rows(n)]
+    unsigned char *codes = nullptr;               // int8: [n, dim] codes; 6-bit: q6_code_bytes(n, dim), tiles of 16 rows;
+                                                  // 5-bit: q5_code_bytes(n, dim), tiles of 16 rows
+    float *scale = nullptr, *err = nullptr;       // s_r, a_r: [n]; 6-bit, 5-bit: [q6_padded_rows(n)]
     unsigned *max = nullptr;                      // [SHADOW_MAX_WORDS] the largest finite a_r, s_r (launch_shadow_max)
     bool stale = true;                            // the rows changed since the shadow was built
     bool refused = false;                         // too little free memory at the last attempt (until the rows change)
@@ -28,7 +30,7 @@ struct Shadow {
 
 // the shadows and the buffers of one pruned call
 struct PruneState {
-    Shadow sh[2];                                  // by ShadowKind
+    Shadow sh[3];                                  // by ShadowKind
     unsigned *state = nullptr;                     // [4] device words (ssw_common.h, launch_q8_query)
     int64_t *surv_rows = nullptr;                  // [SURV_CAP]
     float *surv_scores = nullptr;                  // [SURV_CAP]
@@ -39,7 +41,7 @@ struct PruneState {
     int64_t last = 0, queries = 0, fallbacks = 0;
     // ssw_index_prune_completions: full scans that completed a partial buffer or slab, rows rescored on demand instead
     int64_t completions = 0, rescored_rows = 0;
-    // a single query on the 6-bit shadow
+    // a single query on the 6-bit or the 5-bit shadow
     unsigned *state6 = nullptr;                    // [Q8_MQ_WORDS] the query's words, a slot's of the chunk
     int8_t *planes6 = nullptr;                     // q6_plane_bytes(dim): the query's operand
     void free_shadow() {
@@ -228,6 +230,8 @@ ssw_status wait_host_seq(hipStream_t stream, const unsigned *flag, unsigned seq)
 bool prune_eligible(const ssw_index *idx);
 bool prune_batch_eligible(const ssw_index *idx);
 bool prune6_eligible(const ssw_index *idx);
+bool prune5_eligible(const ssw_index *idx);
+ssw_status prune_exact_threshold(ssw_index *idx, int32_t k, int32_t kc);
 ssw_status ensure_shadow(ssw_index *idx, ShadowKind kind, bool *ready);
 ssw_status rows_changing(ssw_index *idx);
 ssw_status prune_bounds(ssw_index *idx, ShadowKind kind, const float *q_dev, int64_t *dbg_I);

@@ -1,6 +1,8 @@
-// index_prune.hip -- the certified pre-scan of the index's top-k: when it applies, the int8 and the packed 6-bit shadow of
-// the rows, and the steps of one pruned query and of one pruned chunk of a batch (kernels: prune.hip).  The handle:
+// index_prune.hip -- the certified pre-scan of the index's top-k: when it applies, the int8, the packed 6-bit and the packed
+// 5-bit shadow of the rows, and the steps of one pruned query and of one pruned chunk of a batch (kernels: prune.hip).  The handle:
 // index_handle.h.
+#include <algorithm>
+
 #include "index_handle.h"
 
 using namespace ssw;
@@ -70,9 +72,21 @@ constexpr int64_t MIN_ROWS[2][2][2][2] = {
       // (0.019); 50 M rows: 0.651 against 24.837 and 1.615 against 28.876.  f16, 2^20 rows: 0.110 against 0.336 (0.005)
       // and 0.138 against 0.385 (0.008).
       {(int64_t)1 << 20, (int64_t)1 << 20}}}};
+// ---- SHADOW_Q5 ----
+// Single queries on an f32 index of dim 512 or 1024 without an image map and of at least this many rows scan the packed
+// 5-bit shadow (328 instead of 392 bytes a row at dim 512) and raise the threshold to the k-th exact score of a
+// thousand candidates (prune.hip, "5-bit shadow"); such an index builds no 6-bit shadow for single queries.  One entry,
+// under the rule of the 6-bit single call above, from tools/perf_prune.py --three-way with its fourth column, over 25 M,
+// 2^25, 50 M and 100 M rows; never below 25 M rows: tests/test_prune6_gpu.py pins 2^24 f32 rows to the 6-bit shadow's
+// bytes.  Measured (profiles/prune5_four_way_sweep.txt, host wall ms a call, 6-bit / 5-bit, medians of 20): 1.697 /
+// 1.539 at 25 M (spreads 0.071 together), 2.350 / 1.905 at 2^25, 3.408 / 2.972 at 50 M, 6.335 / 5.377 at 100 M (0.165):
+// ahead by more than both spreads at every size of the sweep, so the entry is its smallest.
+constexpr int64_t MIN_ROWS_Q5 = 25000000;
 constexpr int64_t PRUNE_RESERVE = (int64_t)4 << 30;   // free device memory the shadow must leave
 static SSW_TUNABLE bool g_prune = true;               // ssw_tune_prune
 static SSW_TUNABLE bool g_prune6 = true;              // ssw_tune_prune6
+static SSW_TUNABLE bool g_prune5 = true;              // ssw_tune_prune5
+static SSW_TUNABLE int64_t g_prune5_min_rows = -1;     // >= 0: this many rows instead of MIN_ROWS_Q5
 static SSW_TUNABLE int64_t g_prune6_min_rows = -1;     // >= 0: this many rows for both dtypes instead
 static SSW_TUNABLE int64_t g_prune_min_rows = -1;      // >= 0: this many rows for both dtypes instead
 static SSW_TUNABLE int64_t g_prune6_batch_min_rows = -1;  // ssw_tune_prune6_batch: >= 0: the batch's, for both dtypes
@@ -89,9 +103,10 @@ struct ShadowDesc {
                         hipStream_t stream);
     bool query_operand;
 };
-static const ShadowDesc SHADOW[2] = {
+static const ShadowDesc SHADOW[3] = {
     {q8_dim_supported, [](int64_t n, int32_t dim) { return (size_t)n * dim; }, [](int64_t n) { return n; }, launch_q8_build, false},
     {q6_dim_supported, q6_code_bytes, q6_padded_rows, launch_q6_build, true},
+    {q5_dim_supported, q5_code_bytes, q5_padded_rows, launch_q5_build, true},  // the 6-bit query's words and operand
 };
 
 static bool prune_forced_off() {
@@ -103,13 +118,20 @@ static bool prune_forced_off() {
 // for the single call and the batch; ssw_tune_prune6's is the 6-bit single call's alone (lowering it leaves the batch
 // on the int8 shadow, or at dim 768, which has none, on the plain batch) and ssw_tune_prune6_batch's the 6-bit batch's
 static int64_t prune_min_rows(const ssw_index *idx, ShadowKind kind, bool batch) {
+    if (kind == SHADOW_Q5) return g_prune5_min_rows >= 0 ? g_prune5_min_rows : MIN_ROWS_Q5;  // ssw_tune_prune5's alone
     const int64_t lab = kind == SHADOW_Q8 ? g_prune_min_rows : batch ? g_prune6_batch_min_rows : g_prune6_min_rows;
     return lab >= 0 ? lab : MIN_ROWS[kind][batch][idx->dim == 768][idx->dtype == SSW_DTYPE_F16];
 }
 
 static bool prune_eligible_on(const ssw_index *idx, ShadowKind kind, bool batch) {
-    return g_prune && (kind == SHADOW_Q8 || g_prune6) && !prune_forced_off() && idx->owns_X && !idx->rows_escaped &&
-           idx->n >= prune_min_rows(idx, kind, batch) && idx->n_images > 0 && SHADOW[kind].dim_ok(idx->dim);
+    return g_prune && (kind != SHADOW_Q6 || g_prune6) && (kind != SHADOW_Q5 || g_prune5) && !prune_forced_off() &&
+           idx->owns_X && !idx->rows_escaped && idx->n >= prune_min_rows(idx, kind, batch) && idx->n_images > 0 &&
+           SHADOW[kind].dim_ok(idx->dim);
+}
+// the 5-bit shadow: single queries on f32 rows of an index that has no image map at the time of the call (its exact
+// threshold reads rows out of the selection's keys); an index with a map keeps the 6-bit or int8 path
+bool ssw::prune5_eligible(const ssw_index *idx) {
+    return prune_eligible_on(idx, SHADOW_Q5, false) && idx->dtype == SSW_DTYPE_F32 && !idx->has_map;
 }
 bool ssw::prune_eligible(const ssw_index *idx) { return prune_eligible_on(idx, SHADOW_Q8, false); }
 bool ssw::prune_batch_eligible(const ssw_index *idx) { return prune_eligible_on(idx, SHADOW_Q8, true); }
@@ -200,7 +222,11 @@ ssw_status ssw::ensure_shadow(ssw_index *idx, ShadowKind kind, bool *ready) {
 ssw_status ssw::prune_bounds(ssw_index *idx, ShadowKind kind, const float *q_dev, int64_t *dbg_I) {
     PruneState &p = idx->prune;
     const Shadow &s = p.sh[kind];
-    if (kind == SHADOW_Q6) {
+    if (kind == SHADOW_Q5) {
+        SSW_TRY(launch_q6_query(q_dev, idx->dim, p.state6, p.planes6, p.q_last, idx->stream));
+        SSW_TRY(launch_q5_bounds(s.codes, s.scale, s.err, p.planes6, p.state6, idx->scores, idx->n, idx->dim, dbg_I,
+                                 idx->device, idx->stream));
+    } else if (kind == SHADOW_Q6) {
         SSW_TRY(launch_q6_query(q_dev, idx->dim, p.state6, p.planes6, p.q_last, idx->stream));
         SSW_TRY(launch_q6_bounds(s.codes, s.scale, s.err, p.planes6, p.state6, idx->scores, idx->n, idx->dim, dbg_I,
                                  idx->device, idx->stream));
@@ -223,7 +249,11 @@ ssw_status ssw::prune_survivors(ssw_index *idx, ShadowKind kind, int32_t k, int6
     const unsigned seq = next_seq(p.seq);
     int32_t *host_dev = nullptr;
     SSW_HIP_TRY(hipHostGetDevicePointer((void **)&host_dev, p.host, 0));
-    if (kind == SHADOW_Q6) {
+    if (kind == SHADOW_Q5) {
+        SSW_TRY(launch_survivors_q5(idx->scores, s.err, s.scale, s.max, idx->n, idx->dim, idx->ws.out_keys, idx->ws.out_count, k,
+                                    p.state6, p.surv_rows, cap, idx->device, idx->stream));
+        SSW_TRY(launch_prune_publish_mq(p.state6, 1, cap, host_dev, seq, idx->stream));
+    } else if (kind == SHADOW_Q6) {
         SSW_TRY(launch_survivors_mq(idx->scores, s.err, s.scale, s.max, idx->n, idx->dim, true, idx->ws.out_keys,
                                     idx->ws.out_count, k, p.state6, p.surv_rows, cap, idx->device, idx->stream));
         SSW_TRY(launch_prune_publish_mq(p.state6, 1, cap, host_dev, seq, idx->stream));
@@ -237,6 +267,16 @@ ssw_status ssw::prune_survivors(ssw_index *idx, ShadowKind kind, int32_t k, int6
     return SSW_OK;
 }
 
+// The exact threshold of the 5-bit path, between the threshold selection of kc keys and the survivor pass, all on the
+// device: the keys' rows, their exact scores for the kept query, and the k-th key raised to the k-th of those scores
+// (prune.hip, "the exact threshold").  The survivor list and its scores are free until the survivor pass.
+ssw_status ssw::prune_exact_threshold(ssw_index *idx, int32_t k, int32_t kc) {
+    PruneState &p = idx->prune;
+    SSW_TRY(launch_candidate_rows(idx->ws.out_keys, idx->ws.out_count, kc, idx->n, p.surv_rows, idx->stream));
+    SSW_TRY(launch_score_rows(idx->X, idx->dtype, p.q_last, p.surv_rows, kc, idx->dim, p.surv_scores, idx->stream));
+    return launch_exact_threshold(idx->ws.out_keys, idx->ws.out_count, p.surv_scores, k, kc, idx->stream);
+}
+
 // The score buffer for the selection of the top-k of query q_dev (exclusions installed): the full f32 scan, or on a
 // large index the certified pre-scan -- shadow scan (lower bounds), threshold selection over them that publishes
 // nothing, survivors, exact rescoring of the survivors.  One host wait for the survivor count; any failure of the
@@ -248,12 +288,21 @@ ssw_status ssw::prune_survivors(ssw_index *idx, ShadowKind kind, int32_t k, int6
 // *out_candidates: the pruned path succeeded on an index without an image map, and the candidates of the final top-k
 // are in the selection's workspace (launch_scatter_candidates): the caller's selection, the next thing on the stream,
 // runs over them alone (do_select, from_candidates).  Nothing of it is kept in the handle.
+// The 5-bit shadow comes first where prune5_eligible says so (and then no 6-bit shadow is built for single queries; a
+// refusal for memory falls through to the 6-bit and then the int8 shadow).  Its bounds are twice as wide, so its
+// threshold selection runs for kc = min(SSW_MAX_TOPK, max(1024, 4 k)) keys and prune_exact_threshold raises the k-th key
+// to the k-th exact score of those candidates before the survivor pass, on the device; everything after is the same.
 ssw_status ssw::scan_for_topk(ssw_index *idx, const float *q_dev, int32_t k, bool *out_candidates) {
     *out_candidates = false;
     bool ready = false;
-    ShadowKind kind = SHADOW_Q6;
+    ShadowKind kind = SHADOW_Q5;
     const bool k_ok = k >= 1 && k <= SSW_MAX_TOPK && (idx->ws.xchg.msg_out == nullptr || k <= idx->ws.xchg.k_max);
-    if (k_ok && prune6_eligible(idx)) SSW_TRY(ensure_shadow(idx, kind, &ready));
+    const int32_t kc = std::min<int32_t>(SSW_MAX_TOPK, std::max<int32_t>(1024, 4 * std::min<int32_t>(k, SSW_MAX_TOPK)));
+    if (k_ok && prune5_eligible(idx)) SSW_TRY(ensure_shadow(idx, kind, &ready));
+    if (k_ok && !ready && prune6_eligible(idx)) {
+        kind = SHADOW_Q6;
+        SSW_TRY(ensure_shadow(idx, kind, &ready));
+    }
     if (k_ok && !ready && prune_eligible(idx)) {
         kind = SHADOW_Q8;
         SSW_TRY(ensure_shadow(idx, kind, &ready));
@@ -265,9 +314,10 @@ ssw_status ssw::scan_for_topk(ssw_index *idx, const float *q_dev, int32_t k, boo
         SSW_TRY(prune_bounds(idx, kind, q_dev, nullptr));
         SSW_HIP_TRY(hipEventRecord(p.ev, idx->stream));
         // threshold: the ordinary selection over the lower bounds, with the exclusions, without a message or host result
-        SSW_TRY(do_select(idx, idx->scores, k, SelectDest{nullptr, 0u, false}, idx->stream));
+        SSW_TRY(do_select(idx, idx->scores, kind == SHADOW_Q5 ? kc : k, SelectDest{nullptr, 0u, false}, idx->stream));
         // (ahead of the host wait; the survivor pass reads the selection's keys and count, not these words)
         if (!idx->has_map) SSW_TRY(select_reset_state(idx->ws, idx->stream));
+        if (kind == SHADOW_Q5) SSW_TRY(prune_exact_threshold(idx, k, kc));
         int32_t m = -1;
         SSW_TRY(prune_survivors(idx, kind, k, SURV_CAP, p.ev, &m));  // sleep through the shadow scan, spin on the rest
         p.last = m;
@@ -434,15 +484,17 @@ ssw_status ssw_index_prune_stats(ssw_index *idx, int64_t *out6) {
     const PruneState &p = idx->prune;
     // the state of the shadow single queries use: the 6-bit one where it applies and was not refused
     // (a dim-768 index has no other: there a refusal is the 6-bit shadow's)
-    const Shadow &q8 = p.sh[SHADOW_Q8], &q6 = p.sh[SHADOW_Q6];
+    const Shadow &q8 = p.sh[SHADOW_Q8], &q6 = p.sh[SHADOW_Q6], &q5 = p.sh[SHADOW_Q5];
     const bool six = prune6_eligible(idx) && (!q6.refused || !q8_dim_supported(idx->dim));
-    const Shadow &s = six ? q6 : q8;
+    const bool five = prune5_eligible(idx) && !q5.refused;  // ... and before it the 5-bit one, on the same terms
+    const Shadow &s = five ? q5 : six ? q6 : q8;
     out6[0] = s.codes ? (s.stale ? 2 : 1) : (s.refused ? 3 : 0);
-    out6[1] = prune_eligible(idx) || six ? 1 : 0;
+    out6[1] = prune_eligible(idx) || six || five ? 1 : 0;
     out6[2] = p.last;
     out6[3] = p.queries;
     out6[4] = p.fallbacks;
-    out6[5] = (q8.codes ? idx->n * (idx->dim + 8) : 0) + (q6.codes ? q6_padded_rows(idx->n) * (idx->dim * 3 / 4 + 8) : 0);
+    out6[5] = (q8.codes ? idx->n * (idx->dim + 8) : 0) + (q6.codes ? q6_padded_rows(idx->n) * (idx->dim * 3 / 4 + 8) : 0) +
+              (q5.codes ? q5_padded_rows(idx->n) * (idx->dim * 5 / 8 + 8) : 0);
     return SSW_OK;
 }
 
@@ -474,6 +526,17 @@ ssw_status ssw_tune_prune_scan(int32_t blocks_per_cu, int32_t group_loads) {
 ssw_status ssw_tune_prune6(int32_t enable, int64_t min_rows) {
     g_prune6 = enable != 0;
     g_prune6_min_rows = min_rows < 0 ? -1 : min_rows;  // < 0: MIN_ROWS' entries again
+    return SSW_OK;
+}
+
+ssw_status ssw_tune_prune5(int32_t enable, int64_t min_rows) {
+    g_prune5 = enable != 0;
+    g_prune5_min_rows = min_rows < 0 ? -1 : min_rows;  // < 0: MIN_ROWS_Q5 again
+    return SSW_OK;
+}
+
+ssw_status ssw_tune_prune5_scan(int32_t blocks_per_cu, int32_t tiles) {
+    tune_tile_scan(SCAN_Q5, blocks_per_cu, tiles);
     return SSW_OK;
 }
 

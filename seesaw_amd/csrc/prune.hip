@@ -1209,6 +1209,248 @@ __global__ __launch_bounds__(256) void k_q6_bounds_mq(const u32x4 *__restrict__ 
         bounds(t, nfull, ragged);
     }
 }
+
+// ---- the packed 5-bit shadow of f32 rows and its scan ("5-bit shadow") ------------------------------
+// Codes c = rint(x / s5), |c| <= 15, s5 = max|x| / 15; a5 is the int8 shadow's a_r with these codes.  The query is
+// k_q6_query's (planes and state words unchanged), so with ||c|| <= 15 sqrt(dim)
+//
+//     | S_r - (s5_r / 8) t2 I_r | <= a5_r Q + s5_r 15 sqrt(dim) e =: w,   I_r = sum_i 8 c_ri (256 d_hi,i + d_lo,i)   (****)
+//
+// |8 c| <= 120 fits int8 and a plane's sum stays below 2^31 at dim 1024 (120 * 127 * 1024).  w is twice the 6-bit
+// shadow's, which the threshold over the lower bounds alone does not survive: the caller raises it to the k-th exact
+// score of a thousand candidates before the survivor pass (k_exact_threshold below).
+// Layout (q5_fields in ssw_common.h): the 6-bit shadow's tiles, lanes, k-steps and slots; a lane owns 5 dim / 128 words of
+// the tile, the pair of k-steps 2 p, 2 p + 1 its words 5 p .. 5 p + 4; word wi of lane l is at q6_word_offset(l, wi): every
+// wave load instruction reads 1 KiB contiguous, five of them a tile at dim 512, ten at dim 1024.  Dims 256 and 768 have
+// 2.5 and 7.5 such loads and no 5-bit shadow.
+// 10 KiB a request of a wave at both dims.  Swept at 10^8 x 512 rows (profiles/prune5_shape_sweep.txt, host wall ms of a
+// whole call, medians of 12 with the shapes alternating): one block a CU 5.510 with one tile and 5.498 with two -- level,
+// the ranges overlap -- two blocks a CU 5.656 and 5.664, behind both.  Dim 1024 has the one shape (scan_tiles).
+constexpr int Q5_BLOCKS_PER_CU = 1;
+constexpr int q5_default_tiles(int C) { return C == 2 ? 2 : 1; }
+
+// 15 sqrt(dim), rounded up
+__host__ __device__ constexpr double q5_code_norm(int dim) { return dim == 512 ? 339.4112550 : 480.0; }
+
+// one wave per row (grid-strided).  The row's codes in natural order go through the wave's LDS line as in k_q6_build;
+// then every lane ORs the fields of its 4C codes (q5_fields) into the row's 4 * WPL packed words in LDS, word g * WPL + wi
+// being word wi of the lane of group g, and the words go to their places in the tile.
+template <int C>
+__global__ __launch_bounds__(256) void k_q5_build(const float *__restrict__ X, int64_t n, unsigned char *__restrict__ codes,
+                                                  float *__restrict__ scale, float *__restrict__ err) {
+    constexpr int dim = 256 * C, KS = dim / 64, WPL = 5 * KS / 2;  // words a lane of the tile owns
+    constexpr size_t TILE_BYTES = (size_t)16 * dim * 5 / 8;
+    __shared__ unsigned packed_row[4][4 * WPL];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < n; r += (int64_t)gridDim.x * 4) {
+        const float4 *src = reinterpret_cast<const float4 *>(X + r * dim) + lane * C;
+        float x[4 * C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const float4 v = src[c];
+            x[4 * c] = v.x, x[4 * c + 1] = v.y, x[4 * c + 2] = v.z, x[4 * c + 3] = v.w;
+        }
+        unsigned packed[C];
+        q8_quantise_row<C, 15>(x, r, lane, packed, scale, err);
+        __builtin_amdgcn_wave_barrier();  // the previous row's reads of the words are issued (LDS is in order per wave)
+        for (int w = lane; w < 4 * WPL; w += 64) packed_row[wave][w] = 0u;
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int t = 0; t < 4 * C; ++t) {
+            const unsigned c5 = (packed[t >> 2] >> (8 * (t & 3))) & 0x1fu;  // the code of element 4C lane + t, five bits
+            int u, g, j;
+            q6_slot(4 * C * lane + t, &u, &g, &j);
+            Q5Field f[3];
+            const int nf = q5_fields(u, j, f);
+#pragma unroll
+            for (int i = 0; i < 3; ++i)  // (unrolled: the fields stay in registers)
+                if (i < nf)
+                    atomicOr(&packed_row[wave][g * WPL + f[i].word],
+                             ((c5 >> f[i].from) & ((1u << f[i].bits) - 1u)) << (8 * f[i].byte + f[i].lo));
+        }
+        __builtin_amdgcn_wave_barrier();
+        unsigned char *tile = codes + (size_t)(r >> 4) * TILE_BYTES;
+        for (int w = lane; w < 4 * WPL; w += 64)
+            *reinterpret_cast<unsigned *>(tile + q6_word_offset(16 * (w / WPL) + (int)(r & 15), w % WPL)) = packed_row[wave][w];
+    }
+}
+
+// lb of every row into scores[r]: k_q6_bounds' loop and epilogue (two register sets in turn, the next group's codes and
+// constants requested before the current group's products, counted waits, one loop exit, the last n % (16 T) rows as one
+// clamped group for one wave; a tile past the last one is the last one again and nothing is stored for it or for a row
+// >= n) over NL = 5 C / 2 loads a tile.  Unpack, per five words = 32 codes = two k-steps of a lane: five v_and_b32 with
+// 0xf8f8f8f8 give 20 operand bytes 8 c; the three spill words x0, x1, x2 are put together from the low bits (the map at
+// q5_fields), no sign extension.  Two v_mfma_i32_16x16x64_i8 a pair: {m0, m1, m2, x0} with the query operand of k-step
+// 2 p, {m3, m4, x1, x2} with that of 2 p + 1.
+// DEBUG (lab hook only): I_r goes to dbg_I[r] as well.
+template <int C, int T, bool DEBUG>
+__global__ __launch_bounds__(256) void k_q5_bounds(const u32x4 *__restrict__ codes, const float *__restrict__ scale,
+                                                   const float *__restrict__ err, const u32x4 *__restrict__ planes,
+                                                   const unsigned *__restrict__ st, float *__restrict__ scores, int64_t n,
+                                                   int64_t *__restrict__ dbg_I) {
+    static_assert(C == 2 || C == 4, "dims 512 and 1024");
+    constexpr int dim = 256 * C, KS = dim / 64, NL = 5 * C / 2, G = 16 * T;  // NL 1-KiB loads a tile
+    constexpr unsigned TILE_VECS = NL * 64;
+    const int lane = threadIdx.x & 63;
+    const int col = lane & 15, quad = lane >> 4;
+    const int64_t gwave = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t nwaves = (int64_t)gridDim.x * 4;
+    const int64_t nfull = n / G;
+    const int ragged = (int)(n % G);
+    i32x4 qp[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) qp[ks] = __builtin_bit_cast(i32x4, planes[ks * 64 + lane]);
+    const double t2q = (double)__uint_as_float(st[4]) * 0.125;  // exact: the sums are of 8 c
+    const double wQ = (double)__uint_as_float(st[1]) * MQ_INFLATE;
+    const double wE = (double)__uint_as_float(st[3]) * q5_code_norm(dim) * MQ_INFLATE;
+    struct Set {
+        u32x4 c[T][NL];
+        float s[T][4], a[T][4];
+    };
+    // tile0: the group's first tile; last_tile: none beyond it is read.  Every code load is non-temporal, the ragged
+    // group's too, with the builtin called without a condition (k_q6_bounds' note on what `nt ? .. : *p` lost).
+    auto load = [&](Set &d, int64_t tile0, int64_t last_tile) {
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const int64_t tile = tile0 + t < last_tile ? tile0 + t : last_tile;  // wave-uniform
+            const u32x4 *base = codes + tile * (int64_t)TILE_VECS + lane;
+#pragma unroll
+            for (int l = 0; l < NL; ++l) d.c[t][l] = __builtin_nontemporal_load(base + l * 64);
+        }
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const int64_t tile = tile0 + t < last_tile ? tile0 + t : last_tile;
+            const float4 sv = *reinterpret_cast<const float4 *>(scale + tile * 16 + 4 * quad);
+            const float4 av = *reinterpret_cast<const float4 *>(err + tile * 16 + 4 * quad);
+            d.s[t][0] = sv.x, d.s[t][1] = sv.y, d.s[t][2] = sv.z, d.s[t][3] = sv.w;
+            d.a[t][0] = av.x, d.a[t][1] = av.y, d.a[t][2] = av.z, d.a[t][3] = av.w;
+        }
+        __builtin_amdgcn_sched_barrier(0);  // as in k_q8_bounds: the requests stay ahead of the products
+    };
+    // the bounds of the first `rows` rows of group g from a set that has arrived (rows == G: whole stores)
+    auto bounds = [&](const Set &d, int64_t g, int rows) {
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            unsigned w[4 * NL];
+#pragma unroll
+            for (int l = 0; l < NL; ++l) w[4 * l] = d.c[t][l].x, w[4 * l + 1] = d.c[t][l].y, w[4 * l + 2] = d.c[t][l].z, w[4 * l + 3] = d.c[t][l].w;
+            i32x4 acc = {0, 0, 0, 0};
+#pragma unroll
+            for (int p = 0; p < KS / 2; ++p) {
+                const unsigned w0 = w[5 * p], w1 = w[5 * p + 1], w2 = w[5 * p + 2], w3 = w[5 * p + 3], w4 = w[5 * p + 4];
+                const unsigned x0 = ((w0 & 0x07070707u) << 5) | ((w1 & 0x03030303u) << 3);
+                const unsigned x1 = ((w2 & 0x07070707u) << 5) | ((w3 & 0x03030303u) << 3);
+                const unsigned x2 = ((w4 & 0x07070707u) << 5) | ((w1 & 0x04040404u) << 2) | ((w3 & 0x04040404u) << 1);
+                const i32x4 a0 = {(int)(w0 & 0xf8f8f8f8u), (int)(w1 & 0xf8f8f8f8u), (int)(w2 & 0xf8f8f8f8u), (int)x0};
+                const i32x4 a1 = {(int)(w3 & 0xf8f8f8f8u), (int)(w4 & 0xf8f8f8f8u), (int)x1, (int)x2};
+                acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, qp[2 * p], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, qp[2 * p + 1], acc, 0, 0, 0);
+            }
+            float out[4];
+            double I[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int lo = dpp_i<DPP_XOR1>(acc[i]);  // column 1's sum, for the lanes of column 0
+                I[i] = (double)acc[i] * 256.0 + (double)lo;  // exact: |I| < 2^39 at dim 1024
+                const double sd = (double)d.s[t][i];
+                const double wv = (double)d.a[t][i] * wQ + sd * wE;
+                double lb = sd * t2q * I[i] - wv;
+                lb -= fabs(lb) * 0x1p-50 + PAD_ABS;
+                out[i] = __double2float_rd(lb);
+            }
+            const int r0 = t * 16 + 4 * quad;  // of the lane's four rows in the group
+            if (col == 0) {
+                if (rows == G) {
+                    *reinterpret_cast<float4 *>(scores + g * G + r0) = make_float4(out[0], out[1], out[2], out[3]);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        if (r0 + i < rows) (scores + g * G)[r0 + i] = out[i];
+                }
+                if constexpr (DEBUG) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        if (r0 + i < rows) (dbg_I + g * G)[r0 + i] = (int64_t)I[i];
+                }
+            }
+        }
+    };
+    if (gwave < nfull) {
+        const int64_t last = nfull * T - 1;
+        Set a, b;
+        int64_t g = gwave;
+        load(a, g * T, last);
+        for (;;) {
+            // a wave without a next group requests its last one once more (cache hits) and writes nothing for it
+            const int64_t g1 = g + nwaves < nfull ? g + nwaves : g;
+            load(b, g1 * T, last);
+            bounds(a, g, G);
+            const int64_t g2 = g1 + nwaves < nfull ? g1 + nwaves : g1;
+            load(a, g2 * T, last);
+            bounds(b, g1, g1 != g ? G : 0);
+            if (g2 == g1) break;
+            g = g2;
+        }
+    }
+    if (ragged != 0 && gwave == nfull % nwaves) {
+        Set t;
+        load(t, nfull * T, (n - 1) >> 4);
+        bounds(t, nfull, ragged);
+    }
+}
+
+// ---- the exact threshold of the 5-bit path ---------------------------------------------------------------------------
+// The threshold selection over the lower bounds ran for kc = min(SSW_MAX_TOPK, max(1024, 4 k)) keys instead of k.  Their
+// rows are scored exactly and T_x = the k-th largest of those scores: k distinct rows, none excluded, score at least
+// T_x, so the k-th best score of the index is >= T_x and a row with ub < max(T_lb, T_x) cannot be among the k best.
+__global__ __launch_bounds__(256) void k_candidate_rows(const uint64_t *__restrict__ keys, const int32_t *__restrict__ sel_count,
+                                                        int32_t kc, int64_t n, int64_t *__restrict__ rows_out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= kc) return;
+    // a selection that overflowed leaves no keys to trust: row 0 throughout (k_exact_threshold leaves it alone)
+    const int count = sel_count[1] != 0 ? 0 : max(0, min(sel_count[0], kc));
+    // composite_key's low word (select.hip): 0xffffffff - row
+    const uint64_t key = i < count ? keys[i] : count > 0 ? keys[0] : 0xffffffffull;
+    const int64_t row = (int64_t)(0xffffffffu - (uint32_t)key);
+    rows_out[i] = row < n ? row : 0;  // (never beyond the rows, whatever the keys hold)
+}
+
+constexpr int TX_THREADS = 1024, TX_KEYS = SSW_MAX_TOPK;
+static_assert((TX_KEYS & (TX_KEYS - 1)) == 0 && TX_KEYS >= TX_THREADS, "a power of two");
+
+// One block.  The ordinal keys of the candidates' exact scores (0 for a NaN score and beyond the count: below every
+// score's key, -inf's included) are sorted descending in LDS (bitonic over P = the power of two >= kc keys); T_x's key
+// is the k-th, if it is a score's.
+__global__ __launch_bounds__(TX_THREADS) void k_exact_threshold(uint64_t *__restrict__ keys,
+                                                                const int32_t *__restrict__ sel_count,
+                                                                const float *__restrict__ vals, int32_t k, int32_t kc,
+                                                                int32_t P) {
+    __shared__ uint32_t ord[TX_KEYS];
+    if (sel_count[0] < k || sel_count[1] != 0) return;  // the selection failed: the caller falls back
+    const int count = min(sel_count[0], kc);  // >= k >= 1 here
+    for (int i = threadIdx.x; i < P; i += TX_THREADS) {
+        const float v = i < count ? vals[i] : NAN;
+        ord[i] = v != v ? 0u : f32_to_ord(v);
+    }
+    __syncthreads();
+    for (int size = 2; size <= P; size <<= 1)
+        for (int j = size >> 1; j > 0; j >>= 1) {
+            for (int i = threadIdx.x; i < P; i += TX_THREADS) {
+                const int partner = i ^ j;
+                if (partner > i) {
+                    const uint32_t a = ord[i], b = ord[partner];
+                    const bool descending = (i & size) == 0;
+                    if (descending ? a < b : a > b) ord[i] = b, ord[partner] = a;
+                }
+            }
+            __syncthreads();
+        }
+    if (threadIdx.x == 0) {
+        const uint32_t tx = ord[k - 1];  // 0: fewer than k scores that are not NaN, T_x = -inf
+        const uint64_t key = keys[k - 1];
+        if (tx > (uint32_t)(key >> 32)) keys[k - 1] = ((uint64_t)tx << 32) | (key & 0xffffffffull);
+    }
+}
 }  // namespace
 
 bool q8_dim_supported(int32_t dim) { return dim == 256 || dim == 512 || dim == 1024; }
@@ -1230,17 +1472,21 @@ static void dispatch_dim(int C, F f) {
     f(Int<4>{});
 }
 
-// The launch shape of the three tile scans on the matrix core, by TileScan (ssw_tune_prune_scan_mq, ssw_tune_prune6_scan,
-// ssw_tune_prune6_scan_mq; lab build only): four-wave blocks per CU, and 16-row tiles of one request (0: the scan's
+// The launch shape of the four tile scans on the matrix core, by TileScan (ssw_tune_prune_scan_mq, ssw_tune_prune6_scan,
+// ssw_tune_prune6_scan_mq, ssw_tune_prune5_scan; lab build only): four-wave blocks per CU, and 16-row tiles of one request (0: the scan's
 // default for C)
 struct ScanTune {
     int blocks_per_cu;
     int tiles;
 };
-constexpr int SCAN_BLOCKS_PER_CU[3] = {MQ_BLOCKS_PER_CU, Q6_BLOCKS_PER_CU, Q6MQ_BLOCKS_PER_CU};
-static SSW_TUNABLE ScanTune g_scan_tune[3] = {{SCAN_BLOCKS_PER_CU[0], 0}, {SCAN_BLOCKS_PER_CU[1], 0}, {SCAN_BLOCKS_PER_CU[2], 0}};
+constexpr int SCAN_BLOCKS_PER_CU[4] = {MQ_BLOCKS_PER_CU, Q6_BLOCKS_PER_CU, Q6MQ_BLOCKS_PER_CU, Q5_BLOCKS_PER_CU};
+static SSW_TUNABLE ScanTune g_scan_tune[4] = {{SCAN_BLOCKS_PER_CU[0], 0}, {SCAN_BLOCKS_PER_CU[1], 0}, {SCAN_BLOCKS_PER_CU[2], 0},
+                                              {SCAN_BLOCKS_PER_CU[3], 0}};
 constexpr int scan_default_tiles(TileScan scan, int C) {
-    return scan == SCAN_Q8_MQ ? mq_default_tiles(C) : scan == SCAN_Q6 ? q6_default_tiles(C) : q6mq_default_tiles(C);
+    return scan == SCAN_Q8_MQ ? mq_default_tiles(C)
+           : scan == SCAN_Q6  ? q6_default_tiles(C)
+           : scan == SCAN_Q5  ? q5_default_tiles(C)
+                              : q6mq_default_tiles(C);
 }
 
 static int scan_tiles(const ScanTune &tune, int default_tiles, int C) {
@@ -1508,6 +1754,99 @@ ssw_status launch_q6_bounds_mq(const unsigned char *codes, const float *scale, c
         hipLaunchKernelGGL((k_q6_bounds_mq<c.value, t.value, d.value>), dim3((unsigned)grid), dim3(256), 0, stream, cd, scale,
                            err, pl, mq, (int)w, side, stride, own, n, dbg_I);
     });
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+// ---- the packed 5-bit shadow ----------------------------------------------------------------------------------------
+bool q5_dim_supported(int32_t dim) { return dim == 512 || dim == 1024; }
+int64_t q5_padded_rows(int64_t n) { return (n + 15) / 16 * 16; }
+size_t q5_code_bytes(int64_t n, int32_t dim) { return (size_t)q5_padded_rows(n) * (size_t)dim * 5 / 8; }
+
+// codes / scale / err: q5_code_bytes and q5_padded_rows floats each; the rows past n of the last tile get zeros
+ssw_status launch_q5_build(const void *X, int32_t dtype, int64_t n, int32_t dim, unsigned char *codes, float *scale,
+                           float *err, hipStream_t stream) {
+    if (n <= 0) return SSW_OK;
+    if (!q5_dim_supported(dim) || dtype != SSW_DTYPE_F32) {
+        set_error("q5_build: dim=%d, dtype=%d unsupported", dim, dtype);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    const int64_t np = q5_padded_rows(n);
+    const size_t tile_bytes = (size_t)16 * dim * 5 / 8;
+    if (np != n) {
+        SSW_HIP_TRY(hipMemsetAsync(codes + q5_code_bytes(n, dim) - tile_bytes, 0, tile_bytes, stream));
+        SSW_HIP_TRY(hipMemsetAsync(scale + np - 16, 0, 16 * sizeof(float), stream));
+        SSW_HIP_TRY(hipMemsetAsync(err + np - 16, 0, 16 * sizeof(float), stream));
+    }
+    const dim3 grid((unsigned)std::min<int64_t>((n + 3) / 4, (int64_t)1 << 20)), block(256);
+    const float *Xf = static_cast<const float *>(X);
+    if (dim == 512) hipLaunchKernelGGL(k_q5_build<2>, grid, block, 0, stream, Xf, n, codes, scale, err);
+    else hipLaunchKernelGGL(k_q5_build<4>, grid, block, 0, stream, Xf, n, codes, scale, err);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+// f(Int<C>, Int<T>, DEBUG) for the instance of k_q5_bounds that scan_shape's T and the caller's debug output ask for,
+// by dispatch_scan's rule: the product has one instance per dim, at the default T and without DEBUG; the lab build has
+// T = 1 and 2 at dim 512 and T = 1 at dim 1024, each with and without DEBUG
+template <class F>
+static void dispatch_q5(int C, int T, bool debug, F f) {
+#ifdef SSW_DEBUG_HOOKS
+    auto with_debug = [&](auto c, auto t) { debug ? f(c, t, std::true_type{}) : f(c, t, std::false_type{}); };
+    if (C == 4) return with_debug(Int<4>{}, Int<1>{});
+    if (T == 2) return with_debug(Int<2>{}, Int<2>{});
+    with_debug(Int<2>{}, Int<1>{});
+#else
+    (void)T, (void)debug;
+    if (C == 4) return f(Int<4>{}, Int<q5_default_tiles(4)>{}, std::false_type{});
+    f(Int<2>{}, Int<q5_default_tiles(2)>{}, std::false_type{});
+#endif
+}
+
+ssw_status launch_q5_bounds(const unsigned char *codes, const float *scale, const float *err, const int8_t *planes,
+                            const unsigned *st, float *scores, int64_t n, int32_t dim, int64_t *dbg_I, int device,
+                            hipStream_t stream) {
+    if (n <= 0) return SSW_OK;
+    if (!q5_dim_supported(dim)) {
+        set_error("q5_bounds: dim=%d unsupported", dim);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    int grid = 1, T = 1;
+    scan_shape(SCAN_Q5, dim, device, n, &grid, &T);
+    const u32x4 *cd = reinterpret_cast<const u32x4 *>(codes), *pl = reinterpret_cast<const u32x4 *>(planes);
+    dispatch_q5(dim / 256, T, dbg_I != nullptr, [&](auto c, auto t, auto d) {
+        hipLaunchKernelGGL((k_q5_bounds<c.value, t.value, d.value>), dim3((unsigned)grid), dim3(256), 0, stream, cd, scale, err,
+                           pl, st, scores, n, dbg_I);
+    });
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+ssw_status launch_survivors_q5(const float *lb, const float *err, const float *scale, const unsigned *mx, int64_t n, int32_t dim,
+                               const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *slot_state,
+                               int64_t *rows, int64_t cap, int device, hipStream_t stream) {
+    hipLaunchKernelGGL(k_survivors_mq, survivor_grid(device, n), dim3(256), 0, stream, lb, err, scale, mx, n,
+                       q5_code_norm(dim), keys, sel_count, k, slot_state, rows, cap);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+ssw_status launch_candidate_rows(const uint64_t *keys, const int32_t *sel_count, int32_t kc, int64_t n, int64_t *rows_out,
+                                 hipStream_t stream) {
+    hipLaunchKernelGGL(k_candidate_rows, dim3((unsigned)((kc + 255) / 256)), dim3(256), 0, stream, keys, sel_count, kc, n, rows_out);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+ssw_status launch_exact_threshold(uint64_t *keys, const int32_t *sel_count, const float *vals, int32_t k, int32_t kc,
+                                  hipStream_t stream) {
+    if (k < 1 || kc < k || kc > TX_KEYS) {
+        set_error("exact_threshold: k=%d, kc=%d outside [1, %d]", k, kc, TX_KEYS);
+        return SSW_ERR_INVALID;
+    }
+    int P = TX_THREADS;
+    while (P < kc) P <<= 1;
+    hipLaunchKernelGGL(k_exact_threshold, dim3(1), dim3(TX_THREADS), 0, stream, keys, sel_count, vals, k, kc, P);
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
 }

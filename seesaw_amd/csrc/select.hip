@@ -817,7 +817,9 @@ ssw_status launch_select_topk(SelectWorkspace &ws, const float *values, int64_t 
         set_error("topk: %lld images exceed the 32-bit id space of one shard", (long long)m);
         return SSW_ERR_UNSUPPORTED;
     }
-    SSW_TRY(exchange_fits(dest.target ? *dest.target : ws.xchg, k));
+    // (a selection that writes no message -- the pruned scan's threshold selection, which on the 5-bit path asks for more
+    // keys than the caller's k -- is not held to an attached target's k_max: final_outputs gives it no target at all)
+    if (dest.target || dest.message) SSW_TRY(exchange_fits(dest.target ? *dest.target : ws.xchg, k));
     const uint32_t *excl = ws.excl_dirty ? ws.excl_bits : nullptr;
     unsigned char *packed = nullptr;
     FinalExchange xg = final_outputs(ws, dest, &packed);

@@ -221,9 +221,9 @@ ssw_status launch_rescore_survivors(const void *X, int32_t dtype, const float *q
                                     int64_t stride, float *own, int64_t n, int32_t dim, int device, hipStream_t stream);
 int rescore_survivors_waves(int device, int64_t cap);
 ssw_status launch_mark_uncertified(const unsigned *slot_state, int64_t cap, uint64_t *msg_last_word, hipStream_t stream);
-// the three tile scans on the int8 matrix core: launch_q8_bounds_mq, launch_q6_bounds, launch_q6_bounds_mq; scan_shape:
+// the tile scans on the int8 matrix core: launch_q8_bounds_mq, launch_q6_bounds, launch_q6_bounds_mq, launch_q5_bounds; scan_shape:
 // blocks and 16-row tiles per request of the launch the scan's launcher would make
-enum TileScan { SCAN_Q8_MQ, SCAN_Q6, SCAN_Q6_MQ };
+enum TileScan { SCAN_Q8_MQ, SCAN_Q6, SCAN_Q6_MQ, SCAN_Q5 };  // SCAN_Q5: launch_q5_bounds (below)
 void scan_shape(TileScan scan, int32_t dim, int device, int64_t n, int *out_blocks, int *out_tiles);
 // the packed 6-bit shadow of f32 or f16 rows (prune.hip, "6-bit shadow"): tiles of 16 rows, 3 dim / 4 bytes a row, buffers
 // padded to whole tiles.  q6_slot / q6_element / q6_word_offset are the ONE placement of an element's code: k-step u, lane
@@ -254,6 +254,54 @@ ssw_status launch_q6_query_mq(const float *qb_dev, int32_t dim, int32_t w, unsig
 ssw_status launch_q6_bounds_mq(const unsigned char *codes, const float *scale, const float *err, const int8_t *planes,
                                const unsigned *mq, int32_t w, float *side, int64_t stride, float *own, int64_t n,
                                int32_t dim, int64_t *dbg_I, int device, hipStream_t stream);
+// the packed 5-bit shadow of f32 rows at dim 512 and 1024 (prune.hip, "5-bit shadow"): tiles of 16 rows, 5 dim / 8 bytes a
+// row, buffers padded to whole tiles.  Lanes, k-steps and slots are the 6-bit shadow's (q6_slot / q6_element: the lane
+// of row r and element i is 16 g + r % 16), and so is the place of a lane's word in the tile (q6_word_offset).  Two
+// k-steps u = 2 p, 2 p + 1 share the lane's five words 5 p .. 5 p + 4 (w0 .. w4): the upper five bits of their 20 bytes
+// are 20 codes, the low three bits hold the other 12.  q5_fields is the ONE placement of a code's bits, shared by the
+// builder and the lab hook and mirrored by the tests' numpy twin; k_q5_bounds' unpack is its inverse:
+//   k-step 2 p:     slots 0 .. 11 = bits 7:3 of w0, w1, w2;  slot 12 + b = (w0 & 7) << 2 | (w1 & 3) of byte b
+//   k-step 2 p + 1: slots 0 .. 7 = bits 7:3 of w3, w4;  slot 8 + b = (w2 & 7) << 2 | (w3 & 3);
+//                   slot 12 + b = (w4 & 7) << 2 | (w1 >> 2 & 1) << 1 | (w3 >> 2 & 1)
+// A field: code bits [from, from + bits) sit at bits [lo, lo + bits) of byte `byte` of the lane's word `word`.
+struct Q5Field {
+    int word, byte, lo, bits, from;
+};
+__host__ __device__ inline int q5_fields(int u, int j, Q5Field (&f)[3]) {
+    const int w = 5 * (u >> 1), b = j & 3;
+    if ((u & 1) == 0) {
+        if (j < 12) return f[0] = Q5Field{w + (j >> 2), b, 3, 5, 0}, 1;
+        return f[0] = Q5Field{w, b, 0, 3, 2}, f[1] = Q5Field{w + 1, b, 0, 2, 0}, 2;
+    }
+    if (j < 8) return f[0] = Q5Field{w + 3 + (j >> 2), b, 3, 5, 0}, 1;
+    if (j < 12) return f[0] = Q5Field{w + 2, b, 0, 3, 2}, f[1] = Q5Field{w + 3, b, 0, 2, 0}, 2;
+    return f[0] = Q5Field{w + 4, b, 0, 3, 2}, f[1] = Q5Field{w + 1, b, 2, 1, 1}, f[2] = Q5Field{w + 3, b, 2, 1, 0}, 3;
+}
+bool q5_dim_supported(int32_t dim);
+int64_t q5_padded_rows(int64_t n);
+size_t q5_code_bytes(int64_t n, int32_t dim);
+// X: f32 rows in natural order (dtype must be SSW_DTYPE_F32)
+ssw_status launch_q5_build(const void *X, int32_t dtype, int64_t n, int32_t dim, unsigned char *codes, float *scale,
+                           float *err, hipStream_t stream);
+// the query's operand and state words are the 6-bit scan's (launch_q6_query); dbg_I (lab hook only, else NULL): [n] the
+// exact integer sums of 8 c with 256 d_hi + d_lo
+ssw_status launch_q5_bounds(const unsigned char *codes, const float *scale, const float *err, const int8_t *planes,
+                            const unsigned *st, float *scores, int64_t n, int32_t dim, int64_t *dbg_I, int device,
+                            hipStream_t stream);
+// k_survivors_mq with the 5-bit code norm: the threshold is the k-th key of `keys`, which launch_exact_threshold raised
+ssw_status launch_survivors_q5(const float *lb, const float *err, const float *scale, const unsigned *mx, int64_t n, int32_t dim,
+                               const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *slot_state,
+                               int64_t *rows, int64_t cap, int device, hipStream_t stream);
+// The exact threshold of the 5-bit path (prune.hip, "exact threshold").  keys / sel_count: what a threshold selection of
+// kc >= k keys over the lower bounds left (an index without an image map: the low word of a key names its row).
+// candidate_rows: rows_out[i] = the row of key i for i < the number of keys, of key 0 (row 0 without keys) beyond, kc
+// entries below n, for launch_score_rows.  exact_threshold: with vals[i] the exact scores of those rows, T_x = the k-th largest
+// of the first min(count, kc) that are not NaN (-inf if fewer than k are left) and keys[k - 1]'s score word becomes
+// max(T_lb, T_x) in the key domain.  Nothing is changed when the selection failed (fewer than k keys or an overflow).
+ssw_status launch_candidate_rows(const uint64_t *keys, const int32_t *sel_count, int32_t kc, int64_t n, int64_t *rows_out,
+                                 hipStream_t stream);
+ssw_status launch_exact_threshold(uint64_t *keys, const int32_t *sel_count, const float *vals, int32_t k, int32_t kc,
+                                  hipStream_t stream);
 // rows between natural order and the index.  to_h16: n rows of natural-order f32 (src_f32) or binary16 (src_h16, the
 // other NULL) -> rows [0, n) of dst in the f16 layout, rounded to nearest even.  gather: rows (rows_or_null[i], or
 // first_row + i when it is NULL) of an index matrix of element type dtype -> n natural-order f32 rows of out.

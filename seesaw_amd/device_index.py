@@ -500,6 +500,8 @@ class DeviceIndex:
         A dim-768 index (CLIP ViT-L/14) has the 6-bit shadow alone, 584 bytes a row: `shadow` and `shadow_bytes`
         ((n + 15) // 16 * 16 * 584) are that shadow's, and single queries and pruned batches scan it from 2^20 rows
         on, f32 or float16; below that every call is the full-precision one.
+        An f32 index of dim 512 or 1024 without an image map and of at least 25 M rows: `shadow` is the packed 5-bit
+        shadow single queries scan there, 5 dim / 8 + 8 bytes a row of (n + 15) // 16 * 16 rows in `shadow_bytes`.
         `completions=True` adds the two words of ssw_index_prune_completions (the six above stay what they were for
         callers that compare the whole dict): `completions`: full scans that completed a partial score buffer or slab
         for a reader; `rescored_rows`: rows the second-stage readers (`rescore_avg`, `gather_scores`, `topk_batch_avg`)

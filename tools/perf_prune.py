@@ -14,13 +14,16 @@ query.  Prints per size: host wall ms per call (median, and the spread min .. ma
 both forms returned the same images, scores and best rows.  This mode keeps every index on the int8 shadow at every size
 (ssw_tune_prune6(0)).
 
---three-way (how MIN_ROWS (6-bit single call, f32) and, with --dtype float16, MIN_ROWS (6-bit single call, f16) of csrc/index_prune.hip are chosen):
-full scan / int8 shadow / packed 6-bit shadow in turn in one process, two warm-up rounds, then 20 rounds, each a
+--three-way (how MIN_ROWS (6-bit single call, f32), MIN_ROWS_Q5 and, with --dtype float16, MIN_ROWS (6-bit single call, f16) of
+csrc/index_prune.hip are chosen):
+full scan / int8 shadow / packed 6-bit shadow and, on f32 rows of dim 512 or 1024, a fourth column, the packed 5-bit
+shadow with its exact threshold, in turn in one process, two warm-up rounds, then 20 rounds, each a
 different query; per size one JSON line with the median and the spread (max - min) of the host wall ms of each form, the
-6-bit survivors, whether all three returned the same bytes, and under "shadows" which shadow each form's first call
-built, from the growth of prune_stats' shadow_bytes ("none", "int8" or "6-bit"; a form that built another shadow than
-its name says ends the run).  Where the two shadows do not fit beside the rows together, the int8 rounds and the 6-bit
-rounds run one after the other on two indexes of the same rows, each alternating with the full scan.
+6-bit and the 5-bit survivors, whether all forms returned the same bytes, and under "shadows" which shadow each form's first call
+built, from the growth of prune_stats' shadow_bytes ("none", "int8", "6-bit" or "5-bit"; a form that built another shadow than
+its name says ends the run).  Where the shadows do not fit beside the rows together, the int8 rounds and the 6-bit (and
+5-bit) rounds run one after the other on two indexes of the same rows, each alternating with the full scan; the 6-bit and
+the 5-bit call always alternate on one index.
 
 --dim D (default 512): the width of the index.  --dim 768 (how MIN_ROWS (6-bit single call, dim 768, f32) and MIN_ROWS (6-bit single call, dim 768, f16) are
 chosen): that dim has the 6-bit shadow alone, so the run is always the rounds of --three-way with two forms, full scan /
@@ -64,15 +67,18 @@ def main():
     def set_form(form):
         _lib.call("ssw_tune_prune", 0 if form == "full" else 1, 1, -1)
         _lib.call("ssw_tune_prune6", 1 if form == "q6" else 0, 1)
+        _lib.call("ssw_tune_prune5", 1 if form == "q5" else 0, 1)
 
     dtype = np.dtype(args.dtype)
     six_only = dim == 768  # no int8 shadow at this dim
-    built_by = {"full": "none", "int8": "int8", "q6": "6-bit"}
+    five = dim in (512, 1024) and dtype == np.float32  # the fourth column
+    built_by = {"full": "none", "int8": "int8", "q6": "6-bit", "q5": "5-bit"}
 
     def rounds(n, forms, wall, surv, shadows):
         """warm-up and timed rounds over `forms` on a fresh index; -> all forms returned the same bytes"""
         idx = DeviceIndex.synthetic(n, dim, seed=2024, dtype=dtype)
-        grows = {0: "none", n * (dim + 8): "int8", (n + 15) // 16 * 16 * (dim * 3 // 4 + 8): "6-bit"}
+        grows = {0: "none", n * (dim + 8): "int8", (n + 15) // 16 * 16 * (dim * 3 // 4 + 8): "6-bit",
+                 (n + 15) // 16 * 16 * (dim * 5 // 8 + 8): "5-bit"}
         same = True
         try:
             for form in forms:  # builds the shadows, untimed
@@ -91,8 +97,8 @@ def main():
                     out[form] = idx.topk(q, args.k)
                     if i >= 0:
                         wall.setdefault(form, []).append(1e3 * (time.perf_counter() - t0))
-                        if form == "q6":
-                            surv.append(int(stats(idx)[2]))
+                        if form in ("q6", "q5"):
+                            surv.setdefault(form, []).append(int(stats(idx)[2]))
                 for form in forms[1:]:
                     same = same and all(np.array_equal(np.asarray(a).view(np.uint8), np.asarray(b).view(np.uint8))
                                         for a, b in zip(out[forms[0]], out[form]))
@@ -103,17 +109,20 @@ def main():
     def three_way(n):
         import torch
         total = torch.cuda.mem_get_info(0)[1]
-        together = six_only or n * (dim * dtype.itemsize + (dim + 8) + (dim * 3 // 4 + 8) + 8) + (5 << 30) < total
-        wall, surv, shadows = {}, [], {}
+        q5_bytes = dim * 5 // 8 + 8 if five else 0
+        together = six_only or n * (dim * dtype.itemsize + (dim + 8) + (dim * 3 // 4 + 8) + q5_bytes + 8) + (5 << 30) < total
+        wall, surv, shadows = {}, {}, {}
+        packed = ["q6", "q5"] if five else ["q6"]
         if six_only:
             same, fallbacks = rounds(n, ["full", "q6"], wall, surv, shadows)
         elif together:
-            same, fallbacks = rounds(n, ["full", "int8", "q6"], wall, surv, shadows)
+            same, fallbacks = rounds(n, ["full", "int8"] + packed, wall, surv, shadows)
         else:
             wall_b = {}
             same_a, fa = rounds(n, ["full", "int8"], wall, surv, shadows)
-            same_b, fb = rounds(n, ["full", "q6"], wall_b, surv, shadows)
-            wall["q6"], wall["full_beside_q6"] = wall_b["q6"], wall_b["full"]
+            same_b, fb = rounds(n, ["full"] + packed, wall_b, surv, shadows)
+            wall["full_beside_q6"] = wall_b.pop("full")
+            wall.update(wall_b)
             same, fallbacks = same_a and same_b, fa + fb
         res = {"rows": n, "dtype": args.dtype, "k": args.k, "one_index": bool(together), "shadows": shadows}
         if dim != 512:
@@ -121,8 +130,9 @@ def main():
         for form, v in wall.items():
             res[form + "_ms_median"] = round(float(np.median(v)), 3)
             res[form + "_ms_spread"] = round(float(np.max(v) - np.min(v)), 3)
-        res.update({"q6_survivors_min_median_max": [int(np.min(surv)), int(np.median(surv)), int(np.max(surv))],
-                    "fallbacks": fallbacks, "identical": bool(same)})
+        for form, v in surv.items():
+            res[form + "_survivors_min_median_max"] = [int(np.min(v)), int(np.median(v)), int(np.max(v))]
+        res.update({"fallbacks": fallbacks, "identical": bool(same)})
         print(json.dumps(res), flush=True)
 
     with _lib.debug_hooks():
@@ -133,8 +143,10 @@ def main():
             finally:
                 _lib.call("ssw_tune_prune", 1, -1, -1)
                 _lib.call("ssw_tune_prune6", 1, -1)
+                _lib.call("ssw_tune_prune5", 1, -1)
             return
         _lib.call("ssw_tune_prune6", 0, -1)
+        _lib.call("ssw_tune_prune5", 0, -1)
         for rows in args.rows:
             n = int(rows)
             idx = DeviceIndex.synthetic(n, dim, seed=2024, dtype=np.dtype(args.dtype))
@@ -186,6 +198,7 @@ def main():
                 _lib.call("ssw_tune_prune", 1, -1, -1)
                 idx.close()
         _lib.call("ssw_tune_prune6", 1, -1)
+        _lib.call("ssw_tune_prune5", 1, -1)
 
 
 if __name__ == "__main__":
