@@ -16,7 +16,7 @@ enum ShadowKind { SHADOW_Q8, SHADOW_Q6, SHADOW_Q5 };
 struct Shadow {
     unsigned char *codes = nullptr;               // int8: [n, dim] codes; 6-bit: q6_code_bytes(n, dim), tiles of 16 rows;
                                                   // 5-bit: q5_code_bytes(n, dim), tiles of 16 rows
-    float *scale = nullptr, *err = nullptr;       // s_r, a_r: [n]; 6-bit, 5-bit: [q6_padded_rows(n)]
+    float *scale = nullptr, *err = nullptr;       // s_r, a_r: [n]; 6-bit, 5-bit: [packed_padded_rows(n)]
     unsigned *max = nullptr;                      // [SHADOW_MAX_WORDS] the largest finite a_r, s_r (launch_shadow_max)
     bool stale = true;                            // the rows changed since the shadow was built
     bool refused = false;                         // too little free memory at the last attempt (until the rows change)

@@ -105,9 +105,11 @@ struct ShadowDesc {
 };
 static const ShadowDesc SHADOW[3] = {
     {q8_dim_supported, [](int64_t n, int32_t dim) { return (size_t)n * dim; }, [](int64_t n) { return n; }, launch_q8_build, false},
-    {q6_dim_supported, q6_code_bytes, q6_padded_rows, launch_q6_build, true},
-    {q5_dim_supported, q5_code_bytes, q5_padded_rows, launch_q5_build, true},  // the 6-bit query's words and operand
+    {q6_dim_supported, q6_code_bytes, packed_padded_rows, launch_q6_build, true},
+    {q5_dim_supported, q5_code_bytes, packed_padded_rows, launch_q5_build, true},  // the 6-bit query's words and operand
 };
+
+static int code_bits(ShadowKind kind) { return kind == SHADOW_Q8 ? 8 : kind == SHADOW_Q6 ? 6 : 5; }  // of launch_survivors_mq
 
 static bool prune_forced_off() {
     static const bool v = getenv("SSW_TOPK_FULL_SCAN") != nullptr;  // A/B: every top-k runs the full f32 scan
@@ -249,12 +251,8 @@ ssw_status ssw::prune_survivors(ssw_index *idx, ShadowKind kind, int32_t k, int6
     const unsigned seq = next_seq(p.seq);
     int32_t *host_dev = nullptr;
     SSW_HIP_TRY(hipHostGetDevicePointer((void **)&host_dev, p.host, 0));
-    if (kind == SHADOW_Q5) {
-        SSW_TRY(launch_survivors_q5(idx->scores, s.err, s.scale, s.max, idx->n, idx->dim, idx->ws.out_keys, idx->ws.out_count, k,
-                                    p.state6, p.surv_rows, cap, idx->device, idx->stream));
-        SSW_TRY(launch_prune_publish_mq(p.state6, 1, cap, host_dev, seq, idx->stream));
-    } else if (kind == SHADOW_Q6) {
-        SSW_TRY(launch_survivors_mq(idx->scores, s.err, s.scale, s.max, idx->n, idx->dim, true, idx->ws.out_keys,
+    if (kind != SHADOW_Q8) {
+        SSW_TRY(launch_survivors_mq(idx->scores, s.err, s.scale, s.max, idx->n, idx->dim, code_bits(kind), idx->ws.out_keys,
                                     idx->ws.out_count, k, p.state6, p.surv_rows, cap, idx->device, idx->stream));
         SSW_TRY(launch_prune_publish_mq(p.state6, 1, cap, host_dev, seq, idx->stream));
     } else {
@@ -429,7 +427,7 @@ ssw_status ssw::prune_bounds_mq(ssw_index *idx, int w, int32_t *dbg_hi, int32_t 
 ssw_status ssw::prune_survivors_slot(ssw_index *idx, int w, int j, int32_t k, int64_t cap) {
     PruneBatchState &pb = idx->prune_batch;
     const Shadow &s = idx->prune.sh[pb.kind];
-    return launch_survivors_mq(chunk_slab(idx, w, j), s.err, s.scale, s.max, idx->n, idx->dim, pb.kind == SHADOW_Q6,
+    return launch_survivors_mq(chunk_slab(idx, w, j), s.err, s.scale, s.max, idx->n, idx->dim, code_bits(pb.kind),
                                idx->ws.out_keys, idx->ws.out_count, k, pb.mq + j * Q8_MQ_WORDS, pb.surv_rows + (int64_t)j * SURV_CAP, cap, idx->device,
                                idx->stream);
 }
@@ -493,8 +491,8 @@ ssw_status ssw_index_prune_stats(ssw_index *idx, int64_t *out6) {
     out6[2] = p.last;
     out6[3] = p.queries;
     out6[4] = p.fallbacks;
-    out6[5] = (q8.codes ? idx->n * (idx->dim + 8) : 0) + (q6.codes ? q6_padded_rows(idx->n) * (idx->dim * 3 / 4 + 8) : 0) +
-              (q5.codes ? q5_padded_rows(idx->n) * (idx->dim * 5 / 8 + 8) : 0);
+    out6[5] = (q8.codes ? idx->n * (idx->dim + 8) : 0) + (q6.codes ? packed_padded_rows(idx->n) * (idx->dim * 3 / 4 + 8) : 0) +
+              (q5.codes ? packed_padded_rows(idx->n) * (idx->dim * 5 / 8 + 8) : 0);
     return SSW_OK;
 }
 

@@ -579,6 +579,29 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 // 127 sqrt(dim), rounded up
 __host__ __device__ constexpr double mq_code_norm(int dim) { return dim == 256 ? 2032.0 : dim == 512 ? 2873.6819588 : 4064.0; }
 
+// A slot's constants of (**) and its kin from its state words: the factor on the integer sum (t2 times the shadow's
+// `factor`, a power of two: exact) and the two factors of the width w = a_r wQ + s_r wE, with the shadow's code norm.
+// The scans (tile_scan) and the survivor pass (k_survivors_mq) form the same w from them.
+struct SlotBound {
+    double t2q, wQ, wE;
+};
+__device__ __forceinline__ SlotBound slot_bound(const unsigned *st, double factor, double code_norm) {
+    return {(double)__uint_as_float(st[4]) * factor, (double)__uint_as_float(st[1]) * MQ_INFLATE,
+            (double)__uint_as_float(st[3]) * code_norm * MQ_INFLATE};
+}
+
+// THE certificate of the matrix-core scans: the lower bound of row r's score from its exact integer sum I and its
+// constants s_r, a_r, lb = s t2q I - (a wQ + s wE) in double, padded downwards by its own rounding (relative) and by
+// underflow (PAD_ABS), and rounded down to float.  Every tile scan's epilogue is this function.  (k_q8_bounds forms
+// s A - a Q from a float sum A, another expression: it keeps its own.)
+__device__ __forceinline__ float certified_lb(double I, float s, float a, const SlotBound &b) {
+    const double sd = (double)s;
+    const double wv = (double)a * b.wQ + sd * b.wE;
+    double lb = sd * b.t2q * I - wv;
+    lb -= fabs(lb) * 0x1p-50 + PAD_ABS;
+    return __double2float_rd(lb);
+}
+
 // One query into its two code planes and its state words, by one block of 256 threads.  code_at(i, p) is where the
 // code of element i in plane p (0 hi, 1 lo) goes: the caller's operand layout.
 template <class CodeAt>
@@ -651,134 +674,62 @@ __global__ __launch_bounds__(256) void k_q8_query_mq(const float *__restrict__ q
     mq_quantise_query(qb + (size_t)b * dim, dim, b == w - 1 ? q_last : nullptr, mq + b * MQ_WORDS, code_at);
 }
 
-// lb of every row for every query of the chunk: query j's into slab j (j + 1 < w: side + j * stride, the last: own).
-// C = dim / 256; a wave takes groups of T tiles of 16 consecutive rows, grid-strided, and keeps two register sets in
-// turn as k_q8_bounds does: the next group's codes and constants are requested before the current group's MFMAs, the
-// waits inside the loop are counted ones, the loop has one exit, and the last n % (16 T) rows are one clamped group
-// for one wave after it.  Result map of the 16x16 product: lane l holds query l & 15 and rows 4 (l >> 4) .. + 3 of the
-// tile, so it loads those rows' s and a with one 16-byte load each and writes its four bounds with one 16-byte store.
-// DEBUG (lab hook only): the integer sums go to dbg_hi / dbg_lo [query][n] as well.
-template <int C, int T, bool DEBUG>
-__global__ __launch_bounds__(256) void k_q8_bounds_mq(const int8_t *__restrict__ codes, const float *__restrict__ scale,
-                                                      const float *__restrict__ err, const u32x4 *__restrict__ planes,
-                                                      const unsigned *__restrict__ mq, int w, float *__restrict__ side,
-                                                      int64_t stride, float *__restrict__ own, int64_t n,
-                                                      int32_t *__restrict__ dbg_hi, int32_t *__restrict__ dbg_lo) {
-    constexpr int dim = 256 * C, KS = dim / 64, G = 16 * T;
-    const int lane = threadIdx.x & 63;
-    const int col = lane & 15, quad = lane >> 4;
-    const int64_t gwave = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t nwaves = (int64_t)gridDim.x * 4;
-    const int64_t nfull = n / G;
-    const int ragged = (int)(n % G);
-    i32x4 qh[KS], ql[KS];
+// One v_mfma_i32_16x16x64_i8 per query plane of a k-step: the row operand a with the PLANES operands of the k-step
+template <int PLANES>
+__device__ __forceinline__ void mq_products(i32x4 a, const i32x4 (&q)[PLANES], i32x4 (&acc)[PLANES]) {
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-        qh[ks] = __builtin_bit_cast(i32x4, planes[(ks * 2) * 64 + lane]);
-        ql[ks] = __builtin_bit_cast(i32x4, planes[(ks * 2 + 1) * 64 + lane]);
-    }
-    const bool live = col < w;
-    float *__restrict__ slab = col + 1 < w ? side + (int64_t)col * stride : own;
-    const unsigned *st = mq + (live ? col : 0) * MQ_WORDS;
-    const double t2d = (double)__uint_as_float(st[4]);
-    const double wQ = (double)__uint_as_float(st[1]) * MQ_INFLATE;
-    const double wE = (double)__uint_as_float(st[3]) * mq_code_norm(dim) * MQ_INFLATE;
-    const unsigned lane_byte = (unsigned)(col * dim + 16 * quad);  // of the lane's 16 codes of k-step 0 in a tile
-    struct Set {
-        u32x4 c[T][KS];
-        float s[T][4], a[T][4];
-    };
-    auto load = [&](Set &d, int64_t g) {
-        const int8_t *base = codes + g * (int64_t)(G * dim);  // wave-uniform
-#pragma unroll
-        for (int t = 0; t < T; ++t)
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
-                d.c[t][ks] = __builtin_nontemporal_load(
-                    reinterpret_cast<const u32x4 *>(base + (lane_byte + (unsigned)(t * 16 * dim + ks * 64))));
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-            const float4 sv = *reinterpret_cast<const float4 *>(scale + g * G + t * 16 + 4 * quad);
-            const float4 av = *reinterpret_cast<const float4 *>(err + g * G + t * 16 + 4 * quad);
-            d.s[t][0] = sv.x, d.s[t][1] = sv.y, d.s[t][2] = sv.z, d.s[t][3] = sv.w;
-            d.a[t][0] = av.x, d.a[t][1] = av.y, d.a[t][2] = av.z, d.a[t][3] = av.w;
-        }
-        __builtin_amdgcn_sched_barrier(0);  // as in k_q8_bounds: the requests stay ahead of the products
-    };
-    // the bounds of the first `rows` rows of group g from a set that has arrived (rows == G: whole stores)
-    auto bounds = [&](const Set &d, int64_t g, int rows) {
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-            i32x4 hi = {0, 0, 0, 0}, lo = {0, 0, 0, 0};
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const i32x4 a = __builtin_bit_cast(i32x4, d.c[t][ks]);
-                hi = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, qh[ks], hi, 0, 0, 0);
-                lo = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, ql[ks], lo, 0, 0, 0);
-            }
-            float out[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const double I = (double)hi[i] * 256.0 + (double)lo[i];  // exact
-                const double sd = (double)d.s[t][i];
-                const double wv = (double)d.a[t][i] * wQ + sd * wE;
-                double lb = sd * t2d * I - wv;
-                lb -= fabs(lb) * 0x1p-50 + PAD_ABS;
-                out[i] = __double2float_rd(lb);
-            }
-            const int r0 = t * 16 + 4 * quad;  // of the lane's four rows in the group
-            if (rows == G) {
-                if (live) *reinterpret_cast<float4 *>(slab + g * G + r0) = make_float4(out[0], out[1], out[2], out[3]);
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (live && r0 + i < rows) (slab + g * G)[r0 + i] = out[i];
-            }
-            if constexpr (DEBUG) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (live && r0 + i < rows) {
-                        (dbg_hi + (int64_t)col * n + g * G)[r0 + i] = hi[i];
-                        (dbg_lo + (int64_t)col * n + g * G)[r0 + i] = lo[i];
-                    }
-            }
-        }
-    };
-    if (gwave < nfull) {
-        Set a, b;
-        int64_t g = gwave;
-        load(a, g);
-        for (;;) {
-            // a wave without a next group requests its last one once more (cache hits) and writes nothing for it
-            const int64_t g1 = g + nwaves < nfull ? g + nwaves : g;
-            load(b, g1);
-            bounds(a, g, G);
-            const int64_t g2 = g1 + nwaves < nfull ? g1 + nwaves : g1;
-            load(a, g2);
-            bounds(b, g1, g1 != g ? G : 0);
-            if (g2 == g1) break;
-            g = g2;
-        }
-    }
-    if (ragged != 0 && gwave == nfull % nwaves) {
-        Set t;
-        const int8_t *base = codes + nfull * (int64_t)(G * dim);
-#pragma unroll
-        for (int tt = 0; tt < T; ++tt) {
-            const unsigned row = (unsigned)min(tt * 16 + col, ragged - 1);  // nothing beyond row n - 1
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
-                t.c[tt][ks] = *reinterpret_cast<const u32x4 *>(base + (row * (unsigned)dim + (unsigned)(ks * 64 + 16 * quad)));
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int r = min(tt * 16 + 4 * quad + i, ragged - 1);
-                t.s[tt][i] = (scale + nfull * G)[r];
-                t.a[tt][i] = (err + nfull * G)[r];
-            }
-        }
-        bounds(t, nfull, ragged);
-    }
+    for (int p = 0; p < PLANES; ++p) acc[p] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, q[p], acc[p], 0, 0, 0);
 }
+
+// Codes policy of tile_scan (below): the int8 shadow's rows, (**).  A tile is 16 consecutive rows in row-major order;
+// lane l loads the 16 bytes at 64 ks + 16 (l >> 4) of row l & 15 for every k-step ks, which are the MFMA's row operand
+// as they are (no unpack).  The buffers are NOT padded to whole tiles: the group after the last full one is loaded row
+// by row, every row index clamped to the last row (nothing beyond row n - 1 is read), codes and constants alike.
+template <int C>
+struct Q8Rows {
+    static_assert(C == 1 || C == 2 || C == 4, "dims 256, 512 and 1024");
+    static constexpr int dim = 256 * C, KS = dim / 64;
+    static constexpr int NL = KS;           // 16-byte words a lane holds of a tile
+    static constexpr bool PADDED = false;   // the ragged group goes through load_clamped
+    static constexpr double FACTOR = 1.0;   // on t2: the sums are of c
+    static constexpr double CODE_NORM = mq_code_norm(dim);
+    typedef int8_t Elem;
+    // tile t of a full group whose first tile is tile0: every tile of it exists
+    __device__ static __forceinline__ int64_t tile(int64_t tile0, int t, int64_t) { return tile0 + t; }
+    __device__ static __forceinline__ void load_tile(u32x4 (&c)[NL], const int8_t *__restrict__ codes, int64_t tile0, int t,
+                                                     int64_t, int lane) {
+        const int8_t *base = codes + tile0 * (int64_t)(16 * dim);                     // wave-uniform
+        const unsigned lane_byte = (unsigned)((lane & 15) * dim + 16 * (lane >> 4));  // of the lane's 16 codes of k-step 0
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+            c[ks] = __builtin_nontemporal_load(
+                reinterpret_cast<const u32x4 *>(base + (lane_byte + (unsigned)(t * 16 * dim + ks * 64))));
+    }
+    // tile t of the ragged group of `ragged` rows, whose first tile is tile0 (plain loads, as they have always been: at
+    // most one group a launch; the full groups' loads above are the non-temporal ones)
+    __device__ static __forceinline__ void load_clamped(u32x4 (&c)[NL], float (&s)[4], float (&a)[4],
+                                                        const int8_t *__restrict__ codes, const float *__restrict__ scale,
+                                                        const float *__restrict__ err, int64_t tile0, int t, int ragged,
+                                                        int lane) {
+        const int col = lane & 15, quad = lane >> 4;
+        const int8_t *base = codes + tile0 * (int64_t)(16 * dim);
+        const unsigned row = (unsigned)min(t * 16 + col, ragged - 1);
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+            c[ks] = *reinterpret_cast<const u32x4 *>(base + (row * (unsigned)dim + (unsigned)(ks * 64 + 16 * quad)));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int r = min(t * 16 + 4 * quad + i, ragged - 1);
+            s[i] = (scale + tile0 * 16)[r];
+            a[i] = (err + tile0 * 16)[r];
+        }
+    }
+    template <int PLANES>
+    __device__ static __forceinline__ void products(const u32x4 (&c)[NL], const i32x4 (&q)[KS][PLANES], i32x4 (&acc)[PLANES]) {
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) mq_products(__builtin_bit_cast(i32x4, c[ks]), q[ks], acc);
+    }
+};
 
 // k_survivors for one slot of a chunk: the width is w of (**), from the slot's state and the row's scale beside its
 // err; the list and the counter are the slot's.  A failed selection or a flagged query collects nothing and leaves
@@ -795,10 +746,9 @@ __global__ __launch_bounds__(256) void k_survivors_mq(const float *__restrict__ 
     }
     if (st[2] != 0u) return;
     const float T = ord_to_f32((uint32_t)(keys[k - 1] >> 32));
-    const double wQ = (double)__uint_as_float(st[1]) * MQ_INFLATE;
-    const double wE = (double)__uint_as_float(st[3]) * code_norm * MQ_INFLATE;
-    const double w_max = ((double)__uint_as_float(mx[0]) * wQ + (double)__uint_as_float(mx[1]) * wE) * WMAX_INFLATE;
-    survivor_pass<true>(lb, err, scale, n, T, wQ, wE, w_max, &st[0], rows, cap);
+    const SlotBound b = slot_bound(st, 1.0, code_norm);  // (its factor on the sums is not used here)
+    const double w_max = ((double)__uint_as_float(mx[0]) * b.wQ + (double)__uint_as_float(mx[1]) * b.wE) * WMAX_INFLATE;
+    survivor_pass<true>(lb, err, scale, n, T, b.wQ, b.wE, w_max, &st[0], rows, cap);
 }
 
 // every slot's answer in one launch: host_block[1 + j] = survivors or -1, j < w, released under host_block[0] = seq
@@ -934,129 +884,53 @@ __device__ __forceinline__ int dpp_i(int v) {
     return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true);
 }
 
-// lb of every row into scores[r].  C = dim / 256; a wave takes groups of T tiles, grid-strided, with k_q8_bounds_mq's
-// loop: two register sets in turn, the next group's codes and constants requested before the current group's
-// products, counted waits, one loop exit, and the last n % (16 T) rows as one clamped group for one wave after it
-// (the code and constant buffers are padded to whole tiles; a tile past the last one is the last one again and
-// nothing is stored for it or for a row >= n).
-// Unpack, per 16 codes = one k-step of a lane (ISA of <2, 2>: 3 v_and_b32 with 0xfcfcfcfc for the three operand words
-// 4c, and for the fourth 3 v_and_b32 with 0x03030303, 3 v_lshlrev_b32 and 1 v_or3_b32): 10 VALU instructions, no sign
-// extension.  Then ONE v_mfma_i32_16x16x64_i8 a k-step: result lane l holds rows 4 (l >> 4) .. + 3
-// of the tile for column l & 15, the hi sums in column 0 and the lo sums in column 1, which lane l & 15 == 0 fetches with
-// one DPP move each; those four lanes do the double epilogue and one 16-byte store.
-// DEBUG (lab hook only): I_r goes to dbg_I[r] as well.
-template <int C, int T, bool DEBUG>
-__global__ __launch_bounds__(256) void k_q6_bounds(const u32x4 *__restrict__ codes, const float *__restrict__ scale,
-                                                   const float *__restrict__ err, const u32x4 *__restrict__ planes,
-                                                   const unsigned *__restrict__ st, float *__restrict__ scores, int64_t n,
-                                                   int64_t *__restrict__ dbg_I) {
-    constexpr int dim = 256 * C, KS = dim / 64, NL = 3 * C, G = 16 * T;  // NL 1-KiB loads a tile
-    constexpr unsigned TILE_VECS = NL * 64;
-    const int lane = threadIdx.x & 63;
-    const int col = lane & 15, quad = lane >> 4;
-    const int64_t gwave = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t nwaves = (int64_t)gridDim.x * 4;
-    const int64_t nfull = n / G;
-    const int ragged = (int)(n % G);
-    i32x4 qp[KS];
+// What the two packed shadows share as Codes policies of tile_scan: NL contiguous 1-KiB wave loads a tile (word l of
+// lane `lane` is the u32x4 at l * 64 + lane of the tile), code and constant buffers padded to whole tiles, so the
+// ragged group is loaded as a full one with a tile past the last one read as the last one again.
+template <int NL_>
+struct PackedTiles {
+    static constexpr int NL = NL_;  // 16-byte words a lane holds of a tile
+    static constexpr bool PADDED = true;
+    typedef u32x4 Elem;
+    // tile t of a group whose first tile is tile0; none beyond last_tile is read (wave-uniform)
+    __device__ static __forceinline__ int64_t tile(int64_t tile0, int t, int64_t last_tile) {
+        return tile0 + t < last_tile ? tile0 + t : last_tile;
+    }
+    __device__ static __forceinline__ void load_tile(u32x4 (&c)[NL], const u32x4 *__restrict__ codes, int64_t tile0, int t,
+                                                     int64_t last_tile, int lane) {
+        const u32x4 *base = codes + tile(tile0, t, last_tile) * (int64_t)(NL * 64) + lane;
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) qp[ks] = __builtin_bit_cast(i32x4, planes[ks * 64 + lane]);
-    const double t2q = (double)__uint_as_float(st[4]) * 0.25;  // exact: the sums are of 4 c
-    const double wQ = (double)__uint_as_float(st[1]) * MQ_INFLATE;
-    const double wE = (double)__uint_as_float(st[3]) * q6_code_norm(dim) * MQ_INFLATE;
-    struct Set {
-        u32x4 c[T][NL];
-        float s[T][4], a[T][4];
-    };
-    // tile0: the group's first tile; last_tile: none beyond it is read.  Every code load is non-temporal, the ragged
-    // group's too, as in k_q8_bounds: with `nt ? __builtin_nontemporal_load(p) : *p` here the two arms were merged into
-    // one load before the constant got in, the hint was lost (no `nt` on any global_load_dwordx4 of the kernel) and the
-    // scan ran at the default policy's HBM rate.
-    auto load = [&](Set &d, int64_t tile0, int64_t last_tile) {
+        for (int l = 0; l < NL; ++l) c[l] = __builtin_nontemporal_load(base + l * 64);
+    }
+    // the lane's words, a dword each
+    __device__ static __forceinline__ void words(const u32x4 (&c)[NL], unsigned (&w)[4 * NL]) {
 #pragma unroll
-        for (int t = 0; t < T; ++t) {
-            const int64_t tile = tile0 + t < last_tile ? tile0 + t : last_tile;  // wave-uniform
-            const u32x4 *base = codes + tile * (int64_t)TILE_VECS + lane;
+        for (int l = 0; l < NL; ++l) w[4 * l] = c[l].x, w[4 * l + 1] = c[l].y, w[4 * l + 2] = c[l].z, w[4 * l + 3] = c[l].w;
+    }
+};
+
+// Codes policy of tile_scan: the packed 6-bit shadow, (***): three words a k-step.
+// Unpack, per 16 codes = one k-step of a lane (ISA of k_q6_bounds<2, 2>: 3 v_and_b32 with 0xfcfcfcfc for the three
+// operand words 4c, and for the fourth 3 v_and_b32 with 0x03030303, 3 v_lshlrev_b32 and 1 v_or3_b32): 10 VALU
+// instructions, no sign extension.  Then one v_mfma_i32_16x16x64_i8 a query plane.
+template <int C>
+struct Q6Tiles : PackedTiles<3 * C> {
+    static constexpr int dim = 256 * C, KS = dim / 64, NL = 3 * C;
+    static constexpr double FACTOR = 0.25;  // on t2, exact: the sums are of 4 c
+    static constexpr double CODE_NORM = q6_code_norm(dim);
+    template <int PLANES>
+    __device__ static __forceinline__ void products(const u32x4 (&c)[NL], const i32x4 (&q)[KS][PLANES], i32x4 (&acc)[PLANES]) {
+        unsigned w[4 * NL];
+        PackedTiles<NL>::words(c, w);
 #pragma unroll
-            for (int l = 0; l < NL; ++l) d.c[t][l] = __builtin_nontemporal_load(base + l * 64);
-        }
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-            const int64_t tile = tile0 + t < last_tile ? tile0 + t : last_tile;
-            const float4 sv = *reinterpret_cast<const float4 *>(scale + tile * 16 + 4 * quad);
-            const float4 av = *reinterpret_cast<const float4 *>(err + tile * 16 + 4 * quad);
-            d.s[t][0] = sv.x, d.s[t][1] = sv.y, d.s[t][2] = sv.z, d.s[t][3] = sv.w;
-            d.a[t][0] = av.x, d.a[t][1] = av.y, d.a[t][2] = av.z, d.a[t][3] = av.w;
-        }
-        __builtin_amdgcn_sched_barrier(0);  // as in k_q8_bounds: the requests stay ahead of the products
-    };
-    // the bounds of the first `rows` rows of group g from a set that has arrived (rows == G: whole stores)
-    auto bounds = [&](const Set &d, int64_t g, int rows) {
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-            unsigned w[4 * NL];
-#pragma unroll
-            for (int l = 0; l < NL; ++l) w[4 * l] = d.c[t][l].x, w[4 * l + 1] = d.c[t][l].y, w[4 * l + 2] = d.c[t][l].z, w[4 * l + 3] = d.c[t][l].w;
-            i32x4 acc = {0, 0, 0, 0};
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const unsigned w0 = w[3 * ks], w1 = w[3 * ks + 1], w2 = w[3 * ks + 2];
-                const i32x4 a = {(int)(w0 & 0xfcfcfcfcu), (int)(w1 & 0xfcfcfcfcu), (int)(w2 & 0xfcfcfcfcu),
-                                 (int)(((w0 & 0x03030303u) << 6) | ((w1 & 0x03030303u) << 4) | ((w2 & 0x03030303u) << 2))};
-                acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, qp[ks], acc, 0, 0, 0);
-            }
-            float out[4];
-            double I[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int lo = dpp_i<DPP_XOR1>(acc[i]);  // column 1's sum, for the lanes of column 0
-                I[i] = (double)acc[i] * 256.0 + (double)lo;  // exact: |I| < 2^33 at dim 1024
-                const double sd = (double)d.s[t][i];
-                const double wv = (double)d.a[t][i] * wQ + sd * wE;
-                double lb = sd * t2q * I[i] - wv;
-                lb -= fabs(lb) * 0x1p-50 + PAD_ABS;
-                out[i] = __double2float_rd(lb);
-            }
-            const int r0 = t * 16 + 4 * quad;  // of the lane's four rows in the group
-            if (col == 0) {
-                if (rows == G) {
-                    *reinterpret_cast<float4 *>(scores + g * G + r0) = make_float4(out[0], out[1], out[2], out[3]);
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        if (r0 + i < rows) (scores + g * G)[r0 + i] = out[i];
-                }
-                if constexpr (DEBUG) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        if (r0 + i < rows) (dbg_I + g * G)[r0 + i] = (int64_t)I[i];
-                }
-            }
-        }
-    };
-    if (gwave < nfull) {
-        const int64_t last = nfull * T - 1;
-        Set a, b;
-        int64_t g = gwave;
-        load(a, g * T, last);
-        for (;;) {
-            // a wave without a next group requests its last one once more (cache hits) and writes nothing for it
-            const int64_t g1 = g + nwaves < nfull ? g + nwaves : g;
-            load(b, g1 * T, last);
-            bounds(a, g, G);
-            const int64_t g2 = g1 + nwaves < nfull ? g1 + nwaves : g1;
-            load(a, g2 * T, last);
-            bounds(b, g1, g1 != g ? G : 0);
-            if (g2 == g1) break;
-            g = g2;
+        for (int ks = 0; ks < KS; ++ks) {
+            const unsigned w0 = w[3 * ks], w1 = w[3 * ks + 1], w2 = w[3 * ks + 2];
+            const i32x4 a = {(int)(w0 & 0xfcfcfcfcu), (int)(w1 & 0xfcfcfcfcu), (int)(w2 & 0xfcfcfcfcu),
+                             (int)(((w0 & 0x03030303u) << 6) | ((w1 & 0x03030303u) << 4) | ((w2 & 0x03030303u) << 2))};
+            mq_products(a, q[ks], acc);
         }
     }
-    if (ragged != 0 && gwave == nfull % nwaves) {
-        Set t;
-        load(t, nfull * T, (n - 1) >> 4);
-        bounds(t, nfull, ragged);
-    }
-}
+};
 
 // ---- a chunk of up to 16 queries on the 6-bit shadow ("Pruned batch on the 6-bit shadow") ---------
 // k_q6_bounds multiplies 14 of the 16 query columns by zeros; here every column is a query of the chunk, (***) holds per
@@ -1085,130 +959,6 @@ constexpr int Q6MQ_BLOCKS_PER_CU = 1;
 // 12 KiB a wave at every dim, the request k_q6_bounds had when this was set; one tile at dim 512 is behind two at nq = 16
 // (profiles/q6_shape_batch_thresholds.txt); dim 768 (C = 3): one tile, 9 KiB
 constexpr int q6mq_default_tiles(int C) { return 4 / C; }
-
-// lb of every row for every query of the chunk: query j's into slab j (j + 1 < w: side + j * stride, the last: own).
-// The tile loads (NL contiguous 1-KiB loads a tile, a tile past last_tile read as last_tile again) and the unpack are
-// k_q6_bounds'; the two accumulators, the two MFMAs a k-step and the result map are k_q8_bounds_mq's: lane l holds query
-// l & 15 and rows 4 (l >> 4) .. + 3 of the tile and writes its four bounds with one 16-byte store into its slot's slab.
-// The loop is theirs: two register sets in turn, the next group's codes and constants requested before the current
-// group's products, one exit, the last n % (16 T) rows as one clamped group for one wave, nothing stored for a row >= n
-// or by the lanes of a slot >= w.  The epilogue is (***) in double, per slot.
-// DEBUG (lab hook only): I_r of query j goes to dbg_I[j * n + r] as well.
-template <int C, int T, bool DEBUG>
-__global__ __launch_bounds__(256) void k_q6_bounds_mq(const u32x4 *__restrict__ codes, const float *__restrict__ scale,
-                                                      const float *__restrict__ err, const u32x4 *__restrict__ planes,
-                                                      const unsigned *__restrict__ mq, int w, float *__restrict__ side,
-                                                      int64_t stride, float *__restrict__ own, int64_t n,
-                                                      int64_t *__restrict__ dbg_I) {
-    constexpr int dim = 256 * C, KS = dim / 64, NL = 3 * C, G = 16 * T;  // NL 1-KiB loads a tile
-    constexpr unsigned TILE_VECS = NL * 64;
-    const int lane = threadIdx.x & 63;
-    const int col = lane & 15, quad = lane >> 4;
-    const int64_t gwave = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t nwaves = (int64_t)gridDim.x * 4;
-    const int64_t nfull = n / G;
-    const int ragged = (int)(n % G);
-    i32x4 qh[KS], ql[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-        qh[ks] = __builtin_bit_cast(i32x4, planes[(ks * 2) * 64 + lane]);
-        ql[ks] = __builtin_bit_cast(i32x4, planes[(ks * 2 + 1) * 64 + lane]);
-    }
-    const bool live = col < w;
-    float *__restrict__ slab = col + 1 < w ? side + (int64_t)col * stride : own;
-    const unsigned *st = mq + (live ? col : 0) * MQ_WORDS;
-    const double t2q = (double)__uint_as_float(st[4]) * 0.25;  // exact: the sums are of 4 c
-    const double wQ = (double)__uint_as_float(st[1]) * MQ_INFLATE;
-    const double wE = (double)__uint_as_float(st[3]) * q6_code_norm(dim) * MQ_INFLATE;
-    struct Set {
-        u32x4 c[T][NL];
-        float s[T][4], a[T][4];
-    };
-    // tile0: the group's first tile; last_tile: none beyond it is read.  Every code load is non-temporal, the ragged
-    // group's too, with the builtin called without a condition: k_q6_bounds' note on what `nt ? .. : *p` lost.
-    auto load = [&](Set &d, int64_t tile0, int64_t last_tile) {
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-            const int64_t tile = tile0 + t < last_tile ? tile0 + t : last_tile;  // wave-uniform
-            const u32x4 *base = codes + tile * (int64_t)TILE_VECS + lane;
-#pragma unroll
-            for (int l = 0; l < NL; ++l) d.c[t][l] = __builtin_nontemporal_load(base + l * 64);
-        }
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-            const int64_t tile = tile0 + t < last_tile ? tile0 + t : last_tile;
-            const float4 sv = *reinterpret_cast<const float4 *>(scale + tile * 16 + 4 * quad);
-            const float4 av = *reinterpret_cast<const float4 *>(err + tile * 16 + 4 * quad);
-            d.s[t][0] = sv.x, d.s[t][1] = sv.y, d.s[t][2] = sv.z, d.s[t][3] = sv.w;
-            d.a[t][0] = av.x, d.a[t][1] = av.y, d.a[t][2] = av.z, d.a[t][3] = av.w;
-        }
-        __builtin_amdgcn_sched_barrier(0);  // as in k_q8_bounds: the requests stay ahead of the products
-    };
-    // the bounds of the first `rows` rows of group g from a set that has arrived (rows == G: whole stores)
-    auto bounds = [&](const Set &d, int64_t g, int rows) {
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-            unsigned wd[4 * NL];
-#pragma unroll
-            for (int l = 0; l < NL; ++l) wd[4 * l] = d.c[t][l].x, wd[4 * l + 1] = d.c[t][l].y, wd[4 * l + 2] = d.c[t][l].z, wd[4 * l + 3] = d.c[t][l].w;
-            i32x4 hi = {0, 0, 0, 0}, lo = {0, 0, 0, 0};
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const unsigned w0 = wd[3 * ks], w1 = wd[3 * ks + 1], w2 = wd[3 * ks + 2];
-                const i32x4 a = {(int)(w0 & 0xfcfcfcfcu), (int)(w1 & 0xfcfcfcfcu), (int)(w2 & 0xfcfcfcfcu),
-                                 (int)(((w0 & 0x03030303u) << 6) | ((w1 & 0x03030303u) << 4) | ((w2 & 0x03030303u) << 2))};
-                hi = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, qh[ks], hi, 0, 0, 0);
-                lo = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, ql[ks], lo, 0, 0, 0);
-            }
-            float out[4];
-            double I[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                I[i] = (double)hi[i] * 256.0 + (double)lo[i];  // exact: |I| < 2^33 at dim 1024
-                const double sd = (double)d.s[t][i];
-                const double wv = (double)d.a[t][i] * wQ + sd * wE;
-                double lb = sd * t2q * I[i] - wv;
-                lb -= fabs(lb) * 0x1p-50 + PAD_ABS;
-                out[i] = __double2float_rd(lb);
-            }
-            const int r0 = t * 16 + 4 * quad;  // of the lane's four rows in the group
-            if (rows == G) {
-                if (live) *reinterpret_cast<float4 *>(slab + g * G + r0) = make_float4(out[0], out[1], out[2], out[3]);
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (live && r0 + i < rows) (slab + g * G)[r0 + i] = out[i];
-            }
-            if constexpr (DEBUG) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (live && r0 + i < rows) (dbg_I + (int64_t)col * n + g * G)[r0 + i] = (int64_t)I[i];
-            }
-        }
-    };
-    if (gwave < nfull) {
-        const int64_t last = nfull * T - 1;
-        Set a, b;
-        int64_t g = gwave;
-        load(a, g * T, last);
-        for (;;) {
-            // a wave without a next group requests its last one once more (cache hits) and writes nothing for it
-            const int64_t g1 = g + nwaves < nfull ? g + nwaves : g;
-            load(b, g1 * T, last);
-            bounds(a, g, G);
-            const int64_t g2 = g1 + nwaves < nfull ? g1 + nwaves : g1;
-            load(a, g2 * T, last);
-            bounds(b, g1, g1 != g ? G : 0);
-            if (g2 == g1) break;
-            g = g2;
-        }
-    }
-    if (ragged != 0 && gwave == nfull % nwaves) {
-        Set t;
-        load(t, nfull * T, (n - 1) >> 4);
-        bounds(t, nfull, ragged);
-    }
-}
 
 // ---- the packed 5-bit shadow of f32 rows and its scan ("5-bit shadow") ------------------------------
 // Codes c = rint(x / s5), |c| <= 15, s5 = max|x| / 15; a5 is the int8 shadow's a_r with these codes.  The query is
@@ -1275,102 +1025,178 @@ __global__ __launch_bounds__(256) void k_q5_build(const float *__restrict__ X, i
     }
 }
 
-// lb of every row into scores[r]: k_q6_bounds' loop and epilogue (two register sets in turn, the next group's codes and
-// constants requested before the current group's products, counted waits, one loop exit, the last n % (16 T) rows as one
-// clamped group for one wave; a tile past the last one is the last one again and nothing is stored for it or for a row
-// >= n) over NL = 5 C / 2 loads a tile.  Unpack, per five words = 32 codes = two k-steps of a lane: five v_and_b32 with
-// 0xf8f8f8f8 give 20 operand bytes 8 c; the three spill words x0, x1, x2 are put together from the low bits (the map at
-// q5_fields), no sign extension.  Two v_mfma_i32_16x16x64_i8 a pair: {m0, m1, m2, x0} with the query operand of k-step
-// 2 p, {m3, m4, x1, x2} with that of 2 p + 1.
-// DEBUG (lab hook only): I_r goes to dbg_I[r] as well.
-template <int C, int T, bool DEBUG>
-__global__ __launch_bounds__(256) void k_q5_bounds(const u32x4 *__restrict__ codes, const float *__restrict__ scale,
-                                                   const float *__restrict__ err, const u32x4 *__restrict__ planes,
-                                                   const unsigned *__restrict__ st, float *__restrict__ scores, int64_t n,
-                                                   int64_t *__restrict__ dbg_I) {
+// Codes policy of tile_scan: the packed 5-bit shadow, (****): five words a pair of k-steps, NL = 5 C / 2 loads a tile.
+// Unpack, per five words = 32 codes = two k-steps of a lane: five v_and_b32 with 0xf8f8f8f8 give 20 operand bytes 8 c;
+// the three spill words x0, x1, x2 are put together from the low bits (the map at q5_fields), no sign extension.  Two
+// MFMAs a pair and query plane: {m0, m1, m2, x0} with the query operand of k-step 2 p, {m3, m4, x1, x2} with that of
+// 2 p + 1.
+template <int C>
+struct Q5Tiles : PackedTiles<5 * C / 2> {
     static_assert(C == 2 || C == 4, "dims 512 and 1024");
-    constexpr int dim = 256 * C, KS = dim / 64, NL = 5 * C / 2, G = 16 * T;  // NL 1-KiB loads a tile
-    constexpr unsigned TILE_VECS = NL * 64;
+    static constexpr int dim = 256 * C, KS = dim / 64, NL = 5 * C / 2;
+    static constexpr double FACTOR = 0.125;  // on t2, exact: the sums are of 8 c
+    static constexpr double CODE_NORM = q5_code_norm(dim);
+    template <int PLANES>
+    __device__ static __forceinline__ void products(const u32x4 (&c)[NL], const i32x4 (&q)[KS][PLANES], i32x4 (&acc)[PLANES]) {
+        unsigned w[4 * NL];
+        PackedTiles<NL>::words(c, w);
+#pragma unroll
+        for (int p = 0; p < KS / 2; ++p) {
+            const unsigned w0 = w[5 * p], w1 = w[5 * p + 1], w2 = w[5 * p + 2], w3 = w[5 * p + 3], w4 = w[5 * p + 4];
+            const unsigned x0 = ((w0 & 0x07070707u) << 5) | ((w1 & 0x03030303u) << 3);
+            const unsigned x1 = ((w2 & 0x07070707u) << 5) | ((w3 & 0x03030303u) << 3);
+            const unsigned x2 = ((w4 & 0x07070707u) << 5) | ((w1 & 0x04040404u) << 2) | ((w3 & 0x04040404u) << 1);
+            const i32x4 a0 = {(int)(w0 & 0xf8f8f8f8u), (int)(w1 & 0xf8f8f8f8u), (int)(w2 & 0xf8f8f8f8u), (int)x0};
+            const i32x4 a1 = {(int)(w3 & 0xf8f8f8f8u), (int)(w4 & 0xf8f8f8f8u), (int)x1, (int)x2};
+            mq_products(a0, q[2 * p], acc);
+            mq_products(a1, q[2 * p + 1], acc);
+        }
+    }
+};
+
+// ---- the tile scan: one skeleton for the four shadow scans on the int8 matrix core ---------------------------------------
+// Where the lab hooks' DEBUG instances put a row's integer sums: I_r as int64, or the two plane sums as int32
+struct DebugSum {
+    int64_t *__restrict__ I;
+    __device__ __forceinline__ void put(int64_t at, int, int, double sum) const { I[at] = (int64_t)sum; }
+};
+struct DebugPlanes {
+    int32_t *__restrict__ hi, *__restrict__ lo;
+    __device__ __forceinline__ void put(int64_t at, int h, int l, double) const { hi[at] = h, lo[at] = l; }
+};
+
+// Out policy: ONE query (k_q6_bounds, k_q5_bounds).  The operand (k_q6_query) has one plane: the hi codes in column 0,
+// the lo codes in column 1 and zeros elsewhere, so 14 of the 16 result columns are products with zeros.  Result lane l
+// holds rows 4 (l >> 4) .. + 3 of the tile for column l & 15; the lanes of column 0 fetch column 1's sum with one DPP
+// move each, do the double epilogue and store into scores.  Debug: I_r goes to dbg.I[r].
+struct OneQuery {
+    static constexpr int PLANES = 1;
+    static constexpr bool ONE_TEST = true;  // four lanes of a wave store: one test around everything (tile_scan)
+    const unsigned *state;                  // the kernel's arguments: the query's state words (a slot's, MQ_WORDS),
+    float *scores;
+    DebugSum dbg;
+    __device__ __forceinline__ const unsigned *st(int) const { return state; }
+    __device__ __forceinline__ float *dst(int) const { return scores; }
+    __device__ __forceinline__ bool stores(int col) const { return col == 0; }
+    __device__ __forceinline__ int64_t dbg_at(int, int64_t r) const { return r; }
+    // the two plane sums of the lane's row i
+    __device__ __forceinline__ void sums(const i32x4 (&acc)[1], int i, int *hi, int *lo) const {
+        *hi = acc[0][i];
+        *lo = dpp_i<DPP_XOR1>(acc[0][i]);  // column 1's sum, for the lanes of column 0
+    }
+};
+
+// Out policy: a CHUNK of w <= 16 queries (k_q8_bounds_mq, k_q6_bounds_mq).  The operand has two planes a k-step (hi, lo:
+// k_q8_query_mq, k_q6_query_mq) and every result column is a query: lane l holds query l & 15 and rows 4 (l >> 4) .. + 3
+// of the tile in two accumulators and stores into its slot's slab (query j's is slab j: side + j * stride for
+// j + 1 < w, the last one `own`); the lanes of a slot >= w store nothing.  Debug: the sums of query j's row r go to
+// element j * n + r of the arrays of Debug.
+template <class Debug>
+struct Chunk {
+    static constexpr int PLANES = 2;
+    static constexpr bool ONE_TEST = false;  // most lanes store: every store on its own test
+    const unsigned *mq;                      // the kernel's arguments
+    int w;
+    float *side;
+    int64_t stride;
+    float *own;
+    int64_t n;
+    Debug dbg;
+    __device__ __forceinline__ const unsigned *st(int col) const { return mq + (col < w ? col : 0) * MQ_WORDS; }
+    __device__ __forceinline__ float *dst(int col) const { return col + 1 < w ? side + (int64_t)col * stride : own; }
+    __device__ __forceinline__ bool stores(int col) const { return col < w; }
+    __device__ __forceinline__ int64_t dbg_at(int col, int64_t r) const { return (int64_t)col * n + r; }
+    __device__ __forceinline__ void sums(const i32x4 (&acc)[2], int i, int *hi, int *lo) const {
+        *hi = acc[0][i];
+        *lo = acc[1][i];
+    }
+};
+
+// THE scan of a shadow on the matrix core: lb of every row, for the query or queries of `out`.  C = dim / 256; a wave
+// takes groups of T tiles of 16 consecutive rows, grid-strided.  Two register sets (a, b) take turns as in k_q8_bounds:
+// while one group is multiplied the next group's codes AND its rows' constants are in flight, so the only waits inside
+// the loop are counted ones for the group that was requested an iteration earlier.  The loop has one exit and no branch
+// around a request: a path with fewer loads outstanding would make the compiler's wait counts conservative on every
+// path.  The last n % (16 T) rows are one clamped group of their own, after the loop, for one wave: nothing is stored
+// for a row >= n.  Result map of the 16x16 product: lane l holds column l & 15 and rows 4 (l >> 4) .. + 3 of the tile, so
+// it loads those rows' s and a with one 16-byte load each and writes its four bounds with one 16-byte store.
+// Codes: the shadow's layout and unpack (Q8Rows, Q6Tiles, Q5Tiles); Out: what the 16 columns are (OneQuery, Chunk).
+// DEBUG (lab hooks only): the integer sums go to out.dbg as well.
+template <template <int> class CodesOf, class Out, int C, int T, bool DEBUG>
+__device__ __forceinline__ void tile_scan(const typename CodesOf<C>::Elem *__restrict__ codes, const float *__restrict__ scale,
+                                          const float *__restrict__ err, const u32x4 *__restrict__ planes, int64_t n,
+                                          const Out out) {
+    typedef CodesOf<C> Codes;
+    constexpr int KS = Codes::KS, NL = Codes::NL, P = Out::PLANES, G = 16 * T;
     const int lane = threadIdx.x & 63;
     const int col = lane & 15, quad = lane >> 4;
     const int64_t gwave = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t nwaves = (int64_t)gridDim.x * 4;
-    const int64_t nfull = n / G;
-    const int ragged = (int)(n % G);
-    i32x4 qp[KS];
+    const int64_t nfull = n / G;      // groups of G rows
+    const int ragged = (int)(n % G);  // rows of the group after them
+    // the query operand: plane p of k-step ks is the u32x4 at (ks * P + p) * 64 + lane
+    i32x4 q[KS][P];
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) qp[ks] = __builtin_bit_cast(i32x4, planes[ks * 64 + lane]);
-    const double t2q = (double)__uint_as_float(st[4]) * 0.125;  // exact: the sums are of 8 c
-    const double wQ = (double)__uint_as_float(st[1]) * MQ_INFLATE;
-    const double wE = (double)__uint_as_float(st[3]) * q5_code_norm(dim) * MQ_INFLATE;
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+        for (int p = 0; p < P; ++p) q[ks][p] = __builtin_bit_cast(i32x4, planes[(ks * P + p) * 64 + lane]);
+    const bool each = Out::ONE_TEST || out.stores(col);  // (see the stores)
+    float *__restrict__ dst = out.dst(col);
+    const SlotBound sb = slot_bound(out.st(col), Codes::FACTOR, Codes::CODE_NORM);
     struct Set {
         u32x4 c[T][NL];
         float s[T][4], a[T][4];
     };
-    // tile0: the group's first tile; last_tile: none beyond it is read.  Every code load is non-temporal, the ragged
-    // group's too, with the builtin called without a condition (k_q6_bounds' note on what `nt ? .. : *p` lost).
+    // all requests of a group.  tile0: its first tile; last_tile: a padded shadow reads none beyond it.  Every code load
+    // is non-temporal (Codes::load_tile), with the builtin called without a condition: with
+    // `nt ? __builtin_nontemporal_load(p) : *p` the two arms were merged into one load before the constant got in, the
+    // hint was lost (no `nt` on any global_load_dwordx4 of the kernel) and the scan ran at the default policy's HBM rate.
     auto load = [&](Set &d, int64_t tile0, int64_t last_tile) {
 #pragma unroll
-        for (int t = 0; t < T; ++t) {
-            const int64_t tile = tile0 + t < last_tile ? tile0 + t : last_tile;  // wave-uniform
-            const u32x4 *base = codes + tile * (int64_t)TILE_VECS + lane;
-#pragma unroll
-            for (int l = 0; l < NL; ++l) d.c[t][l] = __builtin_nontemporal_load(base + l * 64);
-        }
+        for (int t = 0; t < T; ++t) Codes::load_tile(d.c[t], codes, tile0, t, last_tile, lane);
 #pragma unroll
         for (int t = 0; t < T; ++t) {
-            const int64_t tile = tile0 + t < last_tile ? tile0 + t : last_tile;
+            const int64_t tile = Codes::tile(tile0, t, last_tile);
             const float4 sv = *reinterpret_cast<const float4 *>(scale + tile * 16 + 4 * quad);
             const float4 av = *reinterpret_cast<const float4 *>(err + tile * 16 + 4 * quad);
             d.s[t][0] = sv.x, d.s[t][1] = sv.y, d.s[t][2] = sv.z, d.s[t][3] = sv.w;
             d.a[t][0] = av.x, d.a[t][1] = av.y, d.a[t][2] = av.z, d.a[t][3] = av.w;
         }
-        __builtin_amdgcn_sched_barrier(0);  // as in k_q8_bounds: the requests stay ahead of the products
+        // left alone the scheduler sinks these requests into the products that follow, to reuse the registers of the
+        // set being consumed: the next group would be requested half a group late
+        __builtin_amdgcn_sched_barrier(0);
     };
     // the bounds of the first `rows` rows of group g from a set that has arrived (rows == G: whole stores)
     auto bounds = [&](const Set &d, int64_t g, int rows) {
 #pragma unroll
         for (int t = 0; t < T; ++t) {
-            unsigned w[4 * NL];
+            i32x4 acc[P];
 #pragma unroll
-            for (int l = 0; l < NL; ++l) w[4 * l] = d.c[t][l].x, w[4 * l + 1] = d.c[t][l].y, w[4 * l + 2] = d.c[t][l].z, w[4 * l + 3] = d.c[t][l].w;
-            i32x4 acc = {0, 0, 0, 0};
-#pragma unroll
-            for (int p = 0; p < KS / 2; ++p) {
-                const unsigned w0 = w[5 * p], w1 = w[5 * p + 1], w2 = w[5 * p + 2], w3 = w[5 * p + 3], w4 = w[5 * p + 4];
-                const unsigned x0 = ((w0 & 0x07070707u) << 5) | ((w1 & 0x03030303u) << 3);
-                const unsigned x1 = ((w2 & 0x07070707u) << 5) | ((w3 & 0x03030303u) << 3);
-                const unsigned x2 = ((w4 & 0x07070707u) << 5) | ((w1 & 0x04040404u) << 2) | ((w3 & 0x04040404u) << 1);
-                const i32x4 a0 = {(int)(w0 & 0xf8f8f8f8u), (int)(w1 & 0xf8f8f8f8u), (int)(w2 & 0xf8f8f8f8u), (int)x0};
-                const i32x4 a1 = {(int)(w3 & 0xf8f8f8f8u), (int)(w4 & 0xf8f8f8f8u), (int)x1, (int)x2};
-                acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, qp[2 * p], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, qp[2 * p + 1], acc, 0, 0, 0);
-            }
-            float out[4];
+            for (int p = 0; p < P; ++p) acc[p] = i32x4{0, 0, 0, 0};
+            Codes::products(d.c[t], q, acc);
+            float lb[4];
+            int hi[4], lo[4];
             double I[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const int lo = dpp_i<DPP_XOR1>(acc[i]);  // column 1's sum, for the lanes of column 0
-                I[i] = (double)acc[i] * 256.0 + (double)lo;  // exact: |I| < 2^39 at dim 1024
-                const double sd = (double)d.s[t][i];
-                const double wv = (double)d.a[t][i] * wQ + sd * wE;
-                double lb = sd * t2q * I[i] - wv;
-                lb -= fabs(lb) * 0x1p-50 + PAD_ABS;
-                out[i] = __double2float_rd(lb);
+                out.sums(acc, i, &hi[i], &lo[i]);
+                I[i] = (double)hi[i] * 256.0 + (double)lo[i];  // exact: |I| < 2^39 at dim 1024
+                lb[i] = certified_lb(I[i], d.s[t][i], d.a[t][i], sb);
             }
             const int r0 = t * 16 + 4 * quad;  // of the lane's four rows in the group
-            if (col == 0) {
+            // Out::ONE_TEST: one test of the lane stands around all its stores; else each store has it beside the row's
+            if (!Out::ONE_TEST || out.stores(col)) {
                 if (rows == G) {
-                    *reinterpret_cast<float4 *>(scores + g * G + r0) = make_float4(out[0], out[1], out[2], out[3]);
+                    if (each) *reinterpret_cast<float4 *>(dst + g * G + r0) = make_float4(lb[0], lb[1], lb[2], lb[3]);
                 } else {
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
-                        if (r0 + i < rows) (scores + g * G)[r0 + i] = out[i];
+                        if (each && r0 + i < rows) (dst + g * G)[r0 + i] = lb[i];
                 }
                 if constexpr (DEBUG) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
-                        if (r0 + i < rows) (dbg_I + g * G)[r0 + i] = (int64_t)I[i];
+                        if (each && r0 + i < rows) out.dbg.put(out.dbg_at(col, g * G + r0 + i), hi[i], lo[i], I[i]);
                 }
             }
         }
@@ -1394,9 +1220,56 @@ __global__ __launch_bounds__(256) void k_q5_bounds(const u32x4 *__restrict__ cod
     }
     if (ragged != 0 && gwave == nfull % nwaves) {
         Set t;
-        load(t, nfull * T, (n - 1) >> 4);
+        if constexpr (Codes::PADDED) {
+            load(t, nfull * T, (n - 1) >> 4);
+        } else {
+#pragma unroll
+            for (int tt = 0; tt < T; ++tt)
+                Codes::load_clamped(t.c[tt], t.s[tt], t.a[tt], codes, scale, err, nfull * T, tt, ragged, lane);
+        }
         bounds(t, nfull, ragged);
     }
+}
+
+// The four kernels: a shadow's Codes and the Out of one query or of a chunk.  dbg_*: lab hooks only (DEBUG), else NULL.
+// lb of every row for every query of the chunk into the slot's slab, on the int8 shadow
+template <int C, int T, bool DEBUG>
+__global__ __launch_bounds__(256) void k_q8_bounds_mq(const int8_t *__restrict__ codes, const float *__restrict__ scale,
+                                                      const float *__restrict__ err, const u32x4 *__restrict__ planes,
+                                                      const unsigned *__restrict__ mq, int w, float *__restrict__ side,
+                                                      int64_t stride, float *__restrict__ own, int64_t n,
+                                                      int32_t *__restrict__ dbg_hi, int32_t *__restrict__ dbg_lo) {
+    tile_scan<Q8Rows, Chunk<DebugPlanes>, C, T, DEBUG>(codes, scale, err, planes, n,
+                                                       {mq, w, side, stride, own, n, {dbg_hi, dbg_lo}});
+}
+
+// lb of every row into scores[r], on the packed 6-bit shadow
+template <int C, int T, bool DEBUG>
+__global__ __launch_bounds__(256) void k_q6_bounds(const u32x4 *__restrict__ codes, const float *__restrict__ scale,
+                                                   const float *__restrict__ err, const u32x4 *__restrict__ planes,
+                                                   const unsigned *__restrict__ st, float *__restrict__ scores, int64_t n,
+                                                   int64_t *__restrict__ dbg_I) {
+    tile_scan<Q6Tiles, OneQuery, C, T, DEBUG>(codes, scale, err, planes, n, {st, scores, {dbg_I}});
+}
+
+// lb of every row for every query of the chunk into the slot's slab, on the packed 6-bit shadow
+template <int C, int T, bool DEBUG>
+__global__ __launch_bounds__(256) void k_q6_bounds_mq(const u32x4 *__restrict__ codes, const float *__restrict__ scale,
+                                                      const float *__restrict__ err, const u32x4 *__restrict__ planes,
+                                                      const unsigned *__restrict__ mq, int w, float *__restrict__ side,
+                                                      int64_t stride, float *__restrict__ own, int64_t n,
+                                                      int64_t *__restrict__ dbg_I) {
+    tile_scan<Q6Tiles, Chunk<DebugSum>, C, T, DEBUG>(codes, scale, err, planes, n,
+                                                     {mq, w, side, stride, own, n, {dbg_I}});
+}
+
+// lb of every row into scores[r], on the packed 5-bit shadow
+template <int C, int T, bool DEBUG>
+__global__ __launch_bounds__(256) void k_q5_bounds(const u32x4 *__restrict__ codes, const float *__restrict__ scale,
+                                                   const float *__restrict__ err, const u32x4 *__restrict__ planes,
+                                                   const unsigned *__restrict__ st, float *__restrict__ scores, int64_t n,
+                                                   int64_t *__restrict__ dbg_I) {
+    tile_scan<Q5Tiles, OneQuery, C, T, DEBUG>(codes, scale, err, planes, n, {st, scores, {dbg_I}});
 }
 
 // ---- the exact threshold of the 5-bit path ---------------------------------------------------------------------------
@@ -1513,25 +1386,45 @@ void tune_tile_scan(TileScan scan, int blocks_per_cu, int tiles) {
 }
 #endif
 
+// the C = dim / 256 a tile scan has instances of: its shadow's dims
+constexpr bool scan_has_dim(TileScan scan, int C) {
+    return scan == SCAN_Q8_MQ ? C != 3 : scan == SCAN_Q5 ? C == 2 || C == 4 : true;
+}
+
 // f(Int<C>, Int<T>, DEBUG) for the instance of tile scan S that scan_shape's T and the caller's debug output ask for.
-// The product has one instance per C, at the scan's default T and without DEBUG; the lab build has every T with
-// T * C <= 4 (scan_tiles), each with and without DEBUG.
+// The product has one instance per C of scan_has_dim, at the scan's default T and without DEBUG; the lab build has
+// every T with T * C <= 4 (scan_tiles), each with and without DEBUG.  (A C without instances: the caller has refused it.)
 template <TileScan S, class F>
 static void dispatch_scan(int C, int T, bool debug, F f) {
-    dispatch_dim<S != SCAN_Q8_MQ>(C, [&](auto c) {
+    auto at = [&](auto c) {
+        if constexpr (scan_has_dim(S, c.value)) {
 #ifdef SSW_DEBUG_HOOKS
-        auto with_debug = [&](auto t) { debug ? f(c, t, std::true_type{}) : f(c, t, std::false_type{}); };
-        if constexpr (c.value == 1)
-            if (T == 4) return with_debug(Int<4>{});
-        if constexpr (c.value <= 2)
-            if (T == 2) return with_debug(Int<2>{});
-        with_debug(Int<1>{});
+            auto with_debug = [&](auto t) { debug ? f(c, t, std::true_type{}) : f(c, t, std::false_type{}); };
+            if constexpr (c.value == 1)
+                if (T == 4) return with_debug(Int<4>{});
+            if constexpr (c.value <= 2)
+                if (T == 2) return with_debug(Int<2>{});
+            with_debug(Int<1>{});
 #else
-        (void)T, (void)debug;
-        f(c, Int<scan_default_tiles(S, c.value)>{}, std::false_type{});
+            (void)T, (void)debug;
+            f(c, Int<scan_default_tiles(S, c.value)>{}, std::false_type{});
 #endif
-    });
+        }
+    };
+    C == 1 ? at(Int<1>{}) : C == 2 ? at(Int<2>{}) : C == 3 ? at(Int<3>{}) : at(Int<4>{});
 }
+
+// What the four launchers of the tile scans share: grid and T from scan_shape, then launch(grid, Int<C>, Int<T>, DEBUG)
+// for the instance (the launcher has checked dim and n > 0)
+template <TileScan S, class Launch>
+static ssw_status launch_tile_scan(int32_t dim, int device, int64_t n, bool debug, Launch launch) {
+    int grid = 1, T = 1;
+    scan_shape(S, dim, device, n, &grid, &T);
+    dispatch_scan<S>(dim / 256, T, debug, [&](auto c, auto t, auto d) { launch(dim3((unsigned)grid), c, t, d); });
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+static const u32x4 *as_u32x4(const void *p) { return static_cast<const u32x4 *>(p); }
 
 ssw_status launch_q8_build(const void *X, int32_t dtype, int64_t n, int32_t dim, unsigned char *codes, float *scale,
                            float *err, hipStream_t stream) {
@@ -1643,24 +1536,20 @@ ssw_status launch_q8_bounds_mq(const unsigned char *codes, const float *scale, c
         set_error("q8_bounds_mq: dim=%d, w=%d unsupported", dim, w);
         return SSW_ERR_UNSUPPORTED;
     }
-    int grid = 1, T = 1;
-    scan_shape(SCAN_Q8_MQ, dim, device, n, &grid, &T);
-    const int8_t *cd = reinterpret_cast<const int8_t *>(codes);
-    const u32x4 *pl = reinterpret_cast<const u32x4 *>(planes);
-    dispatch_scan<SCAN_Q8_MQ>(dim / 256, T, dbg_hi != nullptr, [&](auto c, auto t, auto d) {
-        hipLaunchKernelGGL((k_q8_bounds_mq<c.value, t.value, d.value>), dim3((unsigned)grid), dim3(256), 0, stream, cd, scale,
-                           err, pl, mq, (int)w, side, stride, own, n, dbg_hi, dbg_lo);
+    return launch_tile_scan<SCAN_Q8_MQ>(dim, device, n, dbg_hi != nullptr, [&](dim3 grid, auto c, auto t, auto d) {
+        hipLaunchKernelGGL((k_q8_bounds_mq<c.value, t.value, d.value>), grid, dim3(256), 0, stream,
+                           reinterpret_cast<const int8_t *>(codes), scale, err, as_u32x4(planes), mq, (int)w, side, stride, own,
+                           n, dbg_hi, dbg_lo);
     });
-    SSW_HIP_TRY(hipGetLastError());
-    return SSW_OK;
 }
 
-// six: the bounds, err, scale and mx are the 6-bit shadow's (width (***)), else the int8 shadow's (width (**))
+// code_bits: the bounds, err, scale and mx are the int8 (8: width (**)), the 6-bit (6: (***)) or the 5-bit shadow's (5: (****))
 ssw_status launch_survivors_mq(const float *lb, const float *err, const float *scale, const unsigned *mx, int64_t n, int32_t dim,
-                               bool six, const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *slot_state,
+                               int code_bits, const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *slot_state,
                                int64_t *rows, int64_t cap, int device, hipStream_t stream) {
-    hipLaunchKernelGGL(k_survivors_mq, survivor_grid(device, n), dim3(256), 0, stream, lb, err, scale, mx, n,
-                       six ? q6_code_norm(dim) : mq_code_norm(dim), keys, sel_count, k, slot_state, rows, cap);
+    const double code_norm = code_bits == 8 ? mq_code_norm(dim) : code_bits == 6 ? q6_code_norm(dim) : q5_code_norm(dim);
+    hipLaunchKernelGGL(k_survivors_mq, survivor_grid(device, n), dim3(256), 0, stream, lb, err, scale, mx, n, code_norm, keys,
+                       sel_count, k, slot_state, rows, cap);
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
 }
@@ -1673,11 +1562,23 @@ ssw_status launch_prune_publish_mq(const unsigned *mq, int32_t w, int64_t cap, i
 }
 
 // ---- the packed 6-bit shadow ----------------------------------------------------------------------------------------
-int64_t q6_padded_rows(int64_t n) { return (n + 15) / 16 * 16; }
-size_t q6_code_bytes(int64_t n, int32_t dim) { return (size_t)q6_padded_rows(n) * (size_t)dim * 3 / 4; }
+int64_t packed_padded_rows(int64_t n) { return (n + 15) / 16 * 16; }
+size_t q6_code_bytes(int64_t n, int32_t dim) { return (size_t)packed_padded_rows(n) * (size_t)dim * 3 / 4; }
 size_t q6_plane_bytes(int32_t dim) { return (size_t)(dim / 64) * 64 * 16; }
 
-// codes / scale / err: q6_code_bytes and q6_padded_rows floats each; the rows past n of the last tile get zeros
+// zeros for the rows past n of a packed shadow's last tile, ahead of its builder: code_bytes of codes in tiles of
+// tile_bytes, packed_padded_rows floats of scale and err
+static ssw_status zero_last_tile(unsigned char *codes, size_t code_bytes, size_t tile_bytes, float *scale, float *err, int64_t n,
+                                 hipStream_t stream) {
+    const int64_t np = packed_padded_rows(n);
+    if (np == n) return SSW_OK;
+    SSW_HIP_TRY(hipMemsetAsync(codes + code_bytes - tile_bytes, 0, tile_bytes, stream));
+    SSW_HIP_TRY(hipMemsetAsync(scale + np - 16, 0, 16 * sizeof(float), stream));
+    SSW_HIP_TRY(hipMemsetAsync(err + np - 16, 0, 16 * sizeof(float), stream));
+    return SSW_OK;
+}
+
+// codes / scale / err: q6_code_bytes and packed_padded_rows floats each; the rows past n of the last tile get zeros
 ssw_status launch_q6_build(const void *X, int32_t dtype, int64_t n, int32_t dim, unsigned char *codes, float *scale,
                            float *err, hipStream_t stream) {
     if (n <= 0) return SSW_OK;
@@ -1685,13 +1586,7 @@ ssw_status launch_q6_build(const void *X, int32_t dtype, int64_t n, int32_t dim,
         set_error("q6_build: dim=%d, dtype=%d unsupported", dim, dtype);
         return SSW_ERR_UNSUPPORTED;
     }
-    const int64_t np = q6_padded_rows(n);
-    const size_t tile_bytes = (size_t)16 * dim * 3 / 4;
-    if (np != n) {
-        SSW_HIP_TRY(hipMemsetAsync(codes + q6_code_bytes(n, dim) - tile_bytes, 0, tile_bytes, stream));
-        SSW_HIP_TRY(hipMemsetAsync(scale + np - 16, 0, 16 * sizeof(float), stream));
-        SSW_HIP_TRY(hipMemsetAsync(err + np - 16, 0, 16 * sizeof(float), stream));
-    }
+    SSW_TRY(zero_last_tile(codes, q6_code_bytes(n, dim), (size_t)16 * dim * 3 / 4, scale, err, n, stream));
     const dim3 grid((unsigned)std::min<int64_t>((n + 3) / 4, (int64_t)1 << 20)), block(256);
     dispatch_dim<true>(dim / 256, [&](auto c) {
         if (dtype == SSW_DTYPE_F16)
@@ -1719,15 +1614,10 @@ ssw_status launch_q6_bounds(const unsigned char *codes, const float *scale, cons
         set_error("q6_bounds: dim=%d unsupported", dim);
         return SSW_ERR_UNSUPPORTED;
     }
-    int grid = 1, T = 1;
-    scan_shape(SCAN_Q6, dim, device, n, &grid, &T);
-    const u32x4 *cd = reinterpret_cast<const u32x4 *>(codes), *pl = reinterpret_cast<const u32x4 *>(planes);
-    dispatch_scan<SCAN_Q6>(dim / 256, T, dbg_I != nullptr, [&](auto c, auto t, auto d) {
-        hipLaunchKernelGGL((k_q6_bounds<c.value, t.value, d.value>), dim3((unsigned)grid), dim3(256), 0, stream, cd, scale, err,
-                           pl, st, scores, n, dbg_I);
+    return launch_tile_scan<SCAN_Q6>(dim, device, n, dbg_I != nullptr, [&](dim3 grid, auto c, auto t, auto d) {
+        hipLaunchKernelGGL((k_q6_bounds<c.value, t.value, d.value>), grid, dim3(256), 0, stream, as_u32x4(codes), scale, err,
+                           as_u32x4(planes), st, scores, n, dbg_I);
     });
-    SSW_HIP_TRY(hipGetLastError());
-    return SSW_OK;
 }
 
 // ---- a chunk of up to 16 queries on the 6-bit shadow ------------------------------------------------------------------
@@ -1747,23 +1637,17 @@ ssw_status launch_q6_bounds_mq(const unsigned char *codes, const float *scale, c
         set_error("q6_bounds_mq: dim=%d, w=%d unsupported", dim, w);
         return SSW_ERR_UNSUPPORTED;
     }
-    int grid = 1, T = 1;
-    scan_shape(SCAN_Q6_MQ, dim, device, n, &grid, &T);
-    const u32x4 *cd = reinterpret_cast<const u32x4 *>(codes), *pl = reinterpret_cast<const u32x4 *>(planes);
-    dispatch_scan<SCAN_Q6_MQ>(dim / 256, T, dbg_I != nullptr, [&](auto c, auto t, auto d) {
-        hipLaunchKernelGGL((k_q6_bounds_mq<c.value, t.value, d.value>), dim3((unsigned)grid), dim3(256), 0, stream, cd, scale,
-                           err, pl, mq, (int)w, side, stride, own, n, dbg_I);
+    return launch_tile_scan<SCAN_Q6_MQ>(dim, device, n, dbg_I != nullptr, [&](dim3 grid, auto c, auto t, auto d) {
+        hipLaunchKernelGGL((k_q6_bounds_mq<c.value, t.value, d.value>), grid, dim3(256), 0, stream, as_u32x4(codes), scale, err,
+                           as_u32x4(planes), mq, (int)w, side, stride, own, n, dbg_I);
     });
-    SSW_HIP_TRY(hipGetLastError());
-    return SSW_OK;
 }
 
 // ---- the packed 5-bit shadow ----------------------------------------------------------------------------------------
 bool q5_dim_supported(int32_t dim) { return dim == 512 || dim == 1024; }
-int64_t q5_padded_rows(int64_t n) { return (n + 15) / 16 * 16; }
-size_t q5_code_bytes(int64_t n, int32_t dim) { return (size_t)q5_padded_rows(n) * (size_t)dim * 5 / 8; }
+size_t q5_code_bytes(int64_t n, int32_t dim) { return (size_t)packed_padded_rows(n) * (size_t)dim * 5 / 8; }
 
-// codes / scale / err: q5_code_bytes and q5_padded_rows floats each; the rows past n of the last tile get zeros
+// codes / scale / err: q5_code_bytes and packed_padded_rows floats each; the rows past n of the last tile get zeros
 ssw_status launch_q5_build(const void *X, int32_t dtype, int64_t n, int32_t dim, unsigned char *codes, float *scale,
                            float *err, hipStream_t stream) {
     if (n <= 0) return SSW_OK;
@@ -1771,36 +1655,13 @@ ssw_status launch_q5_build(const void *X, int32_t dtype, int64_t n, int32_t dim,
         set_error("q5_build: dim=%d, dtype=%d unsupported", dim, dtype);
         return SSW_ERR_UNSUPPORTED;
     }
-    const int64_t np = q5_padded_rows(n);
-    const size_t tile_bytes = (size_t)16 * dim * 5 / 8;
-    if (np != n) {
-        SSW_HIP_TRY(hipMemsetAsync(codes + q5_code_bytes(n, dim) - tile_bytes, 0, tile_bytes, stream));
-        SSW_HIP_TRY(hipMemsetAsync(scale + np - 16, 0, 16 * sizeof(float), stream));
-        SSW_HIP_TRY(hipMemsetAsync(err + np - 16, 0, 16 * sizeof(float), stream));
-    }
+    SSW_TRY(zero_last_tile(codes, q5_code_bytes(n, dim), (size_t)16 * dim * 5 / 8, scale, err, n, stream));
     const dim3 grid((unsigned)std::min<int64_t>((n + 3) / 4, (int64_t)1 << 20)), block(256);
     const float *Xf = static_cast<const float *>(X);
     if (dim == 512) hipLaunchKernelGGL(k_q5_build<2>, grid, block, 0, stream, Xf, n, codes, scale, err);
     else hipLaunchKernelGGL(k_q5_build<4>, grid, block, 0, stream, Xf, n, codes, scale, err);
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
-}
-
-// f(Int<C>, Int<T>, DEBUG) for the instance of k_q5_bounds that scan_shape's T and the caller's debug output ask for,
-// by dispatch_scan's rule: the product has one instance per dim, at the default T and without DEBUG; the lab build has
-// T = 1 and 2 at dim 512 and T = 1 at dim 1024, each with and without DEBUG
-template <class F>
-static void dispatch_q5(int C, int T, bool debug, F f) {
-#ifdef SSW_DEBUG_HOOKS
-    auto with_debug = [&](auto c, auto t) { debug ? f(c, t, std::true_type{}) : f(c, t, std::false_type{}); };
-    if (C == 4) return with_debug(Int<4>{}, Int<1>{});
-    if (T == 2) return with_debug(Int<2>{}, Int<2>{});
-    with_debug(Int<2>{}, Int<1>{});
-#else
-    (void)T, (void)debug;
-    if (C == 4) return f(Int<4>{}, Int<q5_default_tiles(4)>{}, std::false_type{});
-    f(Int<2>{}, Int<q5_default_tiles(2)>{}, std::false_type{});
-#endif
 }
 
 ssw_status launch_q5_bounds(const unsigned char *codes, const float *scale, const float *err, const int8_t *planes,
@@ -1811,24 +1672,10 @@ ssw_status launch_q5_bounds(const unsigned char *codes, const float *scale, cons
         set_error("q5_bounds: dim=%d unsupported", dim);
         return SSW_ERR_UNSUPPORTED;
     }
-    int grid = 1, T = 1;
-    scan_shape(SCAN_Q5, dim, device, n, &grid, &T);
-    const u32x4 *cd = reinterpret_cast<const u32x4 *>(codes), *pl = reinterpret_cast<const u32x4 *>(planes);
-    dispatch_q5(dim / 256, T, dbg_I != nullptr, [&](auto c, auto t, auto d) {
-        hipLaunchKernelGGL((k_q5_bounds<c.value, t.value, d.value>), dim3((unsigned)grid), dim3(256), 0, stream, cd, scale, err,
-                           pl, st, scores, n, dbg_I);
+    return launch_tile_scan<SCAN_Q5>(dim, device, n, dbg_I != nullptr, [&](dim3 grid, auto c, auto t, auto d) {
+        hipLaunchKernelGGL((k_q5_bounds<c.value, t.value, d.value>), grid, dim3(256), 0, stream, as_u32x4(codes), scale, err,
+                           as_u32x4(planes), st, scores, n, dbg_I);
     });
-    SSW_HIP_TRY(hipGetLastError());
-    return SSW_OK;
-}
-
-ssw_status launch_survivors_q5(const float *lb, const float *err, const float *scale, const unsigned *mx, int64_t n, int32_t dim,
-                               const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *slot_state,
-                               int64_t *rows, int64_t cap, int device, hipStream_t stream) {
-    hipLaunchKernelGGL(k_survivors_mq, survivor_grid(device, n), dim3(256), 0, stream, lb, err, scale, mx, n,
-                       q5_code_norm(dim), keys, sel_count, k, slot_state, rows, cap);
-    SSW_HIP_TRY(hipGetLastError());
-    return SSW_OK;
 }
 
 ssw_status launch_candidate_rows(const uint64_t *keys, const int32_t *sel_count, int32_t kc, int64_t n, int64_t *rows_out,

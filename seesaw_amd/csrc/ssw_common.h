@@ -205,9 +205,10 @@ ssw_status launch_q8_query_mq(const float *qb_dev, int32_t dim, int32_t w, unsig
 ssw_status launch_q8_bounds_mq(const unsigned char *codes, const float *scale, const float *err, const int8_t *planes,
                                const unsigned *mq, int32_t w, float *side, int64_t stride, float *own, int64_t n,
                                int32_t dim, int32_t *dbg_hi, int32_t *dbg_lo, int device, hipStream_t stream);
-// six: lb, err, scale and mx are the 6-bit shadow's (launch_q6_bounds_mq), else the int8 shadow's
+// code_bits: lb, err, scale and mx are the int8 shadow's (8), the 6-bit shadow's (6: launch_q6_bounds, launch_q6_bounds_mq) or
+// the 5-bit shadow's (5: launch_q5_bounds, with the k-th key of `keys` raised by launch_exact_threshold)
 ssw_status launch_survivors_mq(const float *lb, const float *err, const float *scale, const unsigned *mx, int64_t n, int32_t dim,
-                               bool six, const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *slot_state,
+                               int code_bits, const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *slot_state,
                                int64_t *rows, int64_t cap, int device, hipStream_t stream);
 ssw_status launch_prune_publish_mq(const unsigned *mq, int32_t w, int64_t cap, int32_t *host_block, unsigned seq,
                                    hipStream_t stream);
@@ -235,7 +236,7 @@ __host__ __device__ inline int q6_element(int u, int g, int j) { return 64 * u +
 __host__ __device__ inline size_t q6_word_offset(int lane, int wi) {
     return (size_t)(wi >> 2) * 1024 + (size_t)lane * 16 + (size_t)(wi & 3) * 4;
 }
-int64_t q6_padded_rows(int64_t n);
+int64_t packed_padded_rows(int64_t n);  // of both packed shadows: n rounded up to whole tiles
 size_t q6_code_bytes(int64_t n, int32_t dim);
 size_t q6_plane_bytes(int32_t dim);
 // X: f32 rows in natural order, or binary16 rows in the f16 index's lane-interleaved layout (dtype: SSW_DTYPE_*)
@@ -278,7 +279,6 @@ __host__ __device__ inline int q5_fields(int u, int j, Q5Field (&f)[3]) {
     return f[0] = Q5Field{w + 4, b, 0, 3, 2}, f[1] = Q5Field{w + 1, b, 2, 1, 1}, f[2] = Q5Field{w + 3, b, 2, 1, 0}, 3;
 }
 bool q5_dim_supported(int32_t dim);
-int64_t q5_padded_rows(int64_t n);
 size_t q5_code_bytes(int64_t n, int32_t dim);
 // X: f32 rows in natural order (dtype must be SSW_DTYPE_F32)
 ssw_status launch_q5_build(const void *X, int32_t dtype, int64_t n, int32_t dim, unsigned char *codes, float *scale,
@@ -288,10 +288,6 @@ ssw_status launch_q5_build(const void *X, int32_t dtype, int64_t n, int32_t dim,
 ssw_status launch_q5_bounds(const unsigned char *codes, const float *scale, const float *err, const int8_t *planes,
                             const unsigned *st, float *scores, int64_t n, int32_t dim, int64_t *dbg_I, int device,
                             hipStream_t stream);
-// k_survivors_mq with the 5-bit code norm: the threshold is the k-th key of `keys`, which launch_exact_threshold raised
-ssw_status launch_survivors_q5(const float *lb, const float *err, const float *scale, const unsigned *mx, int64_t n, int32_t dim,
-                               const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *slot_state,
-                               int64_t *rows, int64_t cap, int device, hipStream_t stream);
 // The exact threshold of the 5-bit path (prune.hip, "exact threshold").  keys / sel_count: what a threshold selection of
 // kc >= k keys over the lower bounds left (an index without an image map: the low word of a key names its row).
 // candidate_rows: rows_out[i] = the row of key i for i < the number of keys, of key 0 (row 0 without keys) beyond, kc
