@@ -767,14 +767,18 @@ typedef struct ssw_clip ssw_clip;
  * image, patch, t_hidden, t_layers, t_heads, t_mlp, t_max_positions, vocab, eos_token_id,
  * projection_dim, float layer_norm_eps, int32 reserved) followed by the f32 tensors of a
  * transformers.CLIPModel state_dict in the order seesaw_amd/models/clip.py::pack_clip_weights
- * writes them.  GEMM weights are converted to bf16 on the device. */
+ * writes them.  GEMM weights are converted to bf16 on the device.
+ * Served: head dim 64, hidden / MLP sizes multiples of 128 and hidden <= 1024, an image tower of at most 272 tokens
+ * ((image / patch)^2 + 1; any patch size that divides the image: ViT-B/32, ViT-B/16, ViT-L/14 at 224 pixels), a text
+ * tower of at most 80 positions.  Anything else is SSW_ERR_UNSUPPORTED, decided before any device call. */
 ssw_status ssw_clip_create(int32_t device, const void *weight_blob, size_t bytes, ssw_clip **out);
 ssw_status ssw_clip_destroy(ssw_clip *clip);
 /* pixel_values [b, 3, image, image] f32 (already CLIP-normalised) -> [b, projection_dim] f32;
  * normalize != 0 L2-normalises every row (HGFaceWrapper). */
 ssw_status ssw_clip_embed_image(ssw_clip *clip, const float *nchw_host, int32_t b, int32_t normalize,
                                 float *out_host);
-/* same with device pointers, enqueued on hip_stream (NULL: the handle's stream), no sync. */
+/* same with device pointers, enqueued on hip_stream (NULL: the handle's stream), no sync.  At most 1024 images a call,
+ * fewer for an image tower above 80 tokens: as many as make 1024 * 80 token rows (ViT-B/16: 415, ViT-L/14: 318). */
 ssw_status ssw_clip_embed_image_dev(ssw_clip *clip, void *hip_stream, const float *nchw_dev, int32_t b,
                                     int32_t normalize, float *out_dev);
 /* tiles [b, image, image, 3] uint8 (HWC, as cut by the multiscale tiler): batch_tx's
@@ -792,7 +796,8 @@ ssw_status ssw_clip_sync(ssw_clip *clip);
  * (SSW_CLIP_BF16_STREAM=1 sets option 0, SSW_CLIP_UNFUSED_ATTN=1 option 3).  Waits for the handle's stream first.
  *   SSW_CLIP_OPT_IMAGE_ROWS_BF16 (0): residual rows of the image tower in bf16 instead of the default f32 rows (SURVEY 8
  *       a-12's arithmetic) -- the precision / throughput choice of an ingest job: 6 % more tiles per second for 4x the score
- *       error (1.5e-3 against 4e-4 on a unit query, tests/test_clip_gpu.py retrieval test); both forms meet the parity bar;
+ *       error (1.5e-3 against 4e-4 on a unit query, tests/test_clip_gpu.py retrieval test); both forms meet the parity bar,
+ *       also at ViT-L/14's 24 layers (max |delta| of a unit vector's component 1.6e-3 against 4.0e-4 with f32 rows);
  *   SSW_CLIP_OPT_TEXT_ROWS_BF16 (1): residual rows of the text tower's batched path in bf16 (default f32);
  *   SSW_CLIP_OPT_FULL_LAST_LAYER (4): the image tower's last layer over every row (as the reference's model runs it)
  *       instead of for the pooled rows only -- the embedding reads the first row of an image and nothing else, so the
@@ -802,13 +807,18 @@ ssw_status ssw_clip_sync(ssw_clip *clip);
  *       residual row are the full layer's bit for bit, but the products on B rows select other tile kernels and split
  *       K over workgroups, so sums are taken in another order and a bf16 hidden value may round the other way;
  *   SSW_CLIP_OPT_ATTN_DIRECT (2), SSW_CLIP_OPT_ATTN_OUT_UNFUSED (3): earlier kernel forms of the image tower's attention
- *       (fragments straight from memory; attention and out-projection as two launches) kept for A/B measurements.
+ *       (fragments straight from memory; attention and out-projection as two launches) kept for A/B measurements;
+ *   SSW_CLIP_OPT_ATTN_LONG (6): attention_long, the kernel of sequences above 80 tokens (ViT-B/16: 197, ViT-L/14: 257), for
+ *       shorter sequences too.  Like option 2 it acts only where attention is a launch of its own (the text tower's tile
+ *       path; the image tower with option 3 or at widths the fused launch does not serve).  Same arithmetic, same bits:
+ *       kept for that comparison (tests/test_clip_variants_gpu.py).  Number 5 stays unknown to ssw_clip_set_option.
  * Not part of the reference's interface (its precision choice is `.half()` on the whole model, embeddings.py:433-435). */
 #define SSW_CLIP_OPT_IMAGE_ROWS_BF16 0
 #define SSW_CLIP_OPT_TEXT_ROWS_BF16 1
 #define SSW_CLIP_OPT_ATTN_DIRECT 2
 #define SSW_CLIP_OPT_ATTN_OUT_UNFUSED 3
 #define SSW_CLIP_OPT_FULL_LAST_LAYER 4
+#define SSW_CLIP_OPT_ATTN_LONG 6
 ssw_status ssw_clip_set_option(ssw_clip *clip, int32_t option, int32_t value);
 
 #ifdef __cplusplus

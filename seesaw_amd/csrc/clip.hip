@@ -1,4 +1,5 @@
-// clip.hip -- CLIP ViT-B/32 image and text towers, bf16 MFMA forward (gfx950 / MI355X)
+// clip.hip -- CLIP image and text towers (ViT-B/32; ViT-B/16 and ViT-L/14 through attention_long and the general patch
+// gather), bf16 MFMA forward (gfx950 / MI355X)
 //
 // Replaces the reference's calls into transformers.CLIPModel:
 //   get_text_features   seesaw/models/embeddings.py:441-455 (HGWrapper.from_string)
@@ -512,6 +513,151 @@ __global__ __launch_bounds__(128) void attention_rows64(const bf16 *__restrict__
     }
 }
 
+// Sequences above ATT_MAX_S tokens (ViT-B/16: 197, ViT-L/14: 257), up to ATT_LONG_MAX_S = 17 key tiles.  The arithmetic
+// of a query tile is attention_mfma's to the instruction -- the same K / Q fragments into the same two MFMA k-steps a key
+// tile, scale, mask, maximum and sum in-lane over (j, r) ascending then across xor 16 and xor 32, __expf, normalised
+// before the bf16 rounding, P through a per-wave LDS tile, out^T = V^T P^T over key steps of 32 ascending with the V^T
+// fragments out of ds_read_b64_tr_b16 -- so at S <= 80 it gives attention_mfma's bits (SSW_CLIP_OPT_ATTN_LONG).  What
+// differs is the shape of the work: a workgroup is one (image, head) pair, K and V of the head are staged in LDS once
+// (coalesced 128-byte rows, 8 lanes a row: K in the GEMM's swizzled rows as attention_rows64, V with attention_mfma's
+// v_off), and the waves loop over the query tiles, tile i on wave i % NW.  A whole row of scores is NT f32x4 a lane (68
+// VGPRs at NT = 17) and stays in registers: no running maximum.  The K fragments (136 VGPRs if held) are read per key
+// tile out of LDS instead, 16 bytes a lane; Q fragments come straight from memory, two loads a tile.
+// LDS: (2 KP * 64 + NW * 16 * (KP + 8)) * 2 bytes -- NT 17: 72 + 74 = 146 KiB, one workgroup of eight waves a CU;
+// NT 13: 56 + 58 = 114 KiB, one a CU; NT 4 / 5 (four waves, comparison only): 25 / 37 KiB.
+constexpr int ATT_LONG_MAX_S = 272;
+
+template <int NT>
+__global__ __launch_bounds__((NT <= 5 ? 4 : 8) * 64) void attention_long(const bf16 *__restrict__ qkv, bf16 *__restrict__ out,
+                                                                         int S, int D, int H, float scale, int causal) {
+    constexpr int KP = ((NT * 16 + 31) / 32) * 32;  // keys padded to the MFMA K step, as attention_mfma
+    constexpr int LDP = KP + 8;                     // P rows: an odd number of 16-byte chunks
+    constexpr int NW = NT <= 5 ? 4 : 8;             // waves per workgroup
+    constexpr int NCH = (KP * 8 + NW * 64 - 1) / (NW * 64);  // 16-byte chunks of K (and of V) per thread
+    __shared__ __attribute__((aligned(16))) bf16 sK[KP * 64];       // [key][64 head dims], 16-byte chunks swizzled (g_off)
+    __shared__ __attribute__((aligned(16))) bf16 sV[KP * 64];       // [key][64 head dims], 32-byte chunks swizzled (v_off)
+    __shared__ __attribute__((aligned(16))) bf16 sP[NW][16 * LDP];  // one 16-row tile per wave
+    auto g_off = [](int row, int c16) { return row * 64 + ((c16 ^ ((row >> 1) & 7)) << 3); };
+    auto v_off = [](int key, int c32) { return key * 64 + ((c32 ^ (((key >> 1) & 1) | (((key >> 3) & 1) << 1))) << 4); };
+    const int t = threadIdx.x, lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int b = blockIdx.x / H, h = blockIdx.x % H;
+    const int fr = lane & 15, fq = lane >> 4;
+    const bf16 *base = qkv + (int64_t)b * S * 3 * D + h * 64;
+
+    // K and V rows of this head, whole workgroup; keys >= S are zero (their scores are masked, their P columns zero)
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        const int ch = t + c * NW * 64, key = ch >> 3, c16 = ch & 7;
+        if (ch < KP * 8) {
+            bf16x8 kr, vr;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) kr[j] = vr[j] = (bf16)0.f;
+            if (key < S) {
+                const bf16 *r = base + (int64_t)key * 3 * D + c16 * 8;
+                kr = *reinterpret_cast<const bf16x8 *>(r + D);
+                vr = *reinterpret_cast<const bf16x8 *>(r + 2 * D);
+            }
+            *reinterpret_cast<bf16x8 *>(&sK[g_off(key, c16)]) = kr;
+            *reinterpret_cast<bf16x8 *>(&sV[v_off(key, c16 >> 1) + (c16 & 1) * 8]) = vr;
+        }
+    }
+    __syncthreads();
+    bf16 *pt = sP[wave];
+    // a wave whose first tile is past S leaves here as a whole wave (the transposed reads need all 64 lanes)
+    for (int i = wave; i * 16 < S; i += NW) {  // query tile, wave-uniform
+        f32x4 sc[NT];
+        const int qrow = min(i * 16 + fr, S - 1);
+        bf16x8 qf[2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+            qf[ks] = *reinterpret_cast<const bf16x8 *>(base + (int64_t)qrow * 3 * D + ks * 32 + fq * 8);
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            sc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                const bf16x8 kf = *reinterpret_cast<const bf16x8 *>(&sK[g_off(j * 16 + fr, ks * 4 + fq)]);
+                sc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[ks], sc[j], 0, 0, 0);
+            }
+        }
+        // this lane holds scores[query = 16 i + fr][key = 16 j + 4 fq + r]
+        const int q = i * 16 + fr;
+        float mx = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int key = j * 16 + fq * 4 + r;
+                float v = sc[j][r] * scale;
+                if (key >= S || (causal && key > q)) v = -INFINITY;
+                sc[j][r] = v;
+                mx = fmaxf(mx, v);
+            }
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        float sum = 0.f;
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float e = __expf(sc[j][r] - mx);  // key 0 is never masked, so mx is finite
+                sc[j][r] = e;
+                sum += e;
+            }
+        sum += __shfl_xor(sum, 16, 64);
+        sum += __shfl_xor(sum, 32, 64);
+        const float inv = 1.f / sum;
+        // P (bf16) -> this wave's LDS tile [16 queries][KP keys]; the previous tile's reads of it are this wave's own
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            bf16x4 pv;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) pv[r] = to_bf16(sc[j][r] * inv);
+            *reinterpret_cast<bf16x4 *>(&pt[fr * LDP + j * 16 + fq * 4]) = pv;
+        }
+        if (KP > NT * 16) {
+            bf16x4 z;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) z[r] = (bf16)0.f;
+            *reinterpret_cast<bf16x4 *>(&pt[fr * LDP + NT * 16 + fq * 4]) = z;
+        }
+        __builtin_amdgcn_wave_barrier();  // (the wave's LDS accesses complete in order; keep the compiler to that order too)
+        // out^T tile = V^T P^T : o[dt][r] = out[query fr][d = 16 dt + 4 fq + r]
+        f32x4 o[4];
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < KP / 32; ++ks) {
+            const bf16x8 pa = *reinterpret_cast<const bf16x8 *>(&pt[fr * LDP + ks * 32 + fq * 8]);
+            // V^T fragment as in attention_mfma: two transposed reads of 4 keys x 16 dims
+            const int kq = ks * 32 + 8 * fq + (fr >> 2), dp = (fr & 3) * 4;
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) {
+                typedef __attribute__((ext_vector_type(4))) short s16x4;
+                typedef __attribute__((address_space(3))) s16x4 *lds_s16x4;
+                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(&sV[v_off(kq, dt) + dp]));
+                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(&sV[v_off(kq + 4, dt) + dp]));
+                typedef __attribute__((ext_vector_type(8))) short s16x8;
+                const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+                const bf16x8 vb = __builtin_bit_cast(bf16x8, both);
+                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vb, pa, o[dt], 0, 0, 0);
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (q < S) {
+            bf16 *orow = out + ((int64_t)b * S + q) * D + h * 64 + fq * 4;
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) {
+                bf16x4 ov;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) ov[r] = to_bf16(o[dt][r]);
+                *reinterpret_cast<bf16x4 *>(orow + dt * 16) = ov;
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------
 // skinny linear: out[R <= 32, N] = epilogue(LN?(X)[R, K] W[N, K]^T) for the handful of rows a single text query has.
 // The tile kernels above give such a product to N/128 workgroups that each walk all of K (a [8 x 2048] x [2048 x 512]
@@ -879,6 +1025,35 @@ __global__ void im2col_patches_u8(const uint8_t *__restrict__ tiles, bf16 *__res
     }
 }
 
+// Any patch size (ViT-L/14: 14): the two gathers above want 8 consecutive pixels of a patch row, 16-byte aligned.  Here a
+// thread is one output element: column c * patch^2 + py * patch + px as above, the row padded with zero columns to `ld`
+// (the next multiple of 64, the GEMM's K step: 588 -> 640), which the padded patch weight matches.  Scalar loads: the
+// gather is 150 KB a tile against the tower's tens of GFLOP.  U8 = the tiler's HWC bytes with batch_tx's arithmetic.
+template <bool U8>
+__global__ void im2col_patches_any(const void *__restrict__ src, bf16 *__restrict__ out, int B, int img, int patch, int ld,
+                                   float m0, float m1, float m2, float s0, float s1, float s2) {
+    const int g = img / patch;
+    const int pp = patch * patch;
+    const int64_t total = (int64_t)B * g * g * ld;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int col = (int)(i % ld);
+        const int64_t r = i / ld;
+        const int p = (int)(r % (g * g));
+        const int b = (int)(r / (g * g));
+        float v = 0.f;
+        if (col < 3 * pp) {
+            const int c = col / pp, py = (col % pp) / patch, pxx = col % patch;
+            const int y = (p / g) * patch + py, x = (p % g) * patch + pxx;
+            const float mean = c == 0 ? m0 : c == 1 ? m1 : m2, stdv = c == 0 ? s0 : c == 1 ? s1 : s2;
+            if (U8)
+                v = ((float)static_cast<const uint8_t *>(src)[(((int64_t)b * img + y) * img + x) * 3 + c] / 255.0f - mean) / stdv;
+            else
+                v = static_cast<const float *>(src)[(((int64_t)b * 3 + c) * img + y) * img + x];
+        }
+        out[i] = to_bf16(v);
+    }
+}
+
 __global__ void text_embed(const int *__restrict__ ids, const float *__restrict__ tok, const float *__restrict__ pos,
                            float *__restrict__ hidden, int B, int L, int D) {
     const int64_t total = (int64_t)B * L * D;
@@ -1186,7 +1361,8 @@ struct ssw_clip {
     int64_t rows_key = -1;  // what `rows` holds: (B << 32 | stride) of the image tower's pooled-row list, -1 = something else
     // ssw_clip_set_option: bit 0 = bf16 residual rows in the image tower's tile path, bit 1 = bf16 rows in the text tower's,
     // bit 2 = the tile path's attention with its K / Q fragments straight from memory (attention_mfma) for S <= 64 too,
-    // bit 3 = attention and out-projection as two launches (round 3's layer) where attn_out.hip's one launch applies
+    // bit 3 = attention and out-projection as two launches (round 3's layer) where attn_out.hip's one launch applies,
+    // bit 6 = attention_long for S <= 80 too, where attention is a launch of its own
     int flags = 0;
     // The lab build's tap (ssw_clip_debug_tap).  Declared in BOTH builds so that a handle has one layout whichever library
     // created it (a product-made handle handed to the lab build's tap wrote past the allocation); the product
@@ -1197,6 +1373,12 @@ struct ssw_clip {
 };
 
 namespace {
+
+// columns of a row of c->patches and of c->patch_w: 3 patch^2 padded to the GEMM's K step of 64 (a multiple of it already
+// when patch % 8 == 0; patch 14: 588 -> 640).  seesaw_amd/models/clip.py::patch_columns is the same number.
+inline int patch_cols(int patch) { return (3 * patch * patch + 63) / 64 * 64; }
+// token rows of the image tower
+inline int vision_tokens(const Header &h) { return (h.image / h.patch) * (h.image / h.patch) + 1; }
 
 ssw_status dmalloc(ssw_clip *c, void **p, size_t bytes) {
     SSW_HIP_TRY(hipMalloc(p, bytes + 64));
@@ -1331,7 +1513,7 @@ ssw_status reserve(ssw_clip *c, int64_t batch) {
     const int64_t Tv = (int64_t)(h.image / h.patch) * (h.image / h.patch) + 1;
     const int64_t rows = batch * std::max<int64_t>(Tv, h.t_maxpos);
     const int64_t D = std::max(h.v_hidden, h.t_hidden), Mm = std::max(h.v_mlp, h.t_mlp);
-    const int64_t pcols = 3LL * h.patch * h.patch;
+    const int64_t pcols = patch_cols(h.patch);
     SSW_HIP_TRY(hipMalloc((void **)&c->hidden, rows * D * sizeof(float)));
     SSW_HIP_TRY(hipMalloc((void **)&c->hidden2, rows * D * sizeof(float)));
     SSW_HIP_TRY(hipMalloc((void **)&c->pooled, batch * D * sizeof(float)));
@@ -1420,6 +1602,14 @@ ssw_status tap_layer_rows(ssw_clip *c, const Tower &tw, int l, int causal, int64
 #else
 #define SSW_TAP(l, f32p, bf16p)
 #endif
+
+// the smallest instance that holds S (<= ATT_LONG_MAX_S, ssw_clip_create's condition)
+void launch_attention_long(hipStream_t s, const bf16 *qkv, bf16 *att, int n_heads, int S, int D, int H, float scale, int causal) {
+    if (S <= 64) hipLaunchKernelGGL(attention_long<4>, dim3(n_heads), dim3(256), 0, s, qkv, att, S, D, H, scale, causal);
+    else if (S <= 80) hipLaunchKernelGGL(attention_long<5>, dim3(n_heads), dim3(256), 0, s, qkv, att, S, D, H, scale, causal);
+    else if (S <= 208) hipLaunchKernelGGL(attention_long<13>, dim3(n_heads), dim3(512), 0, s, qkv, att, S, D, H, scale, causal);
+    else hipLaunchKernelGGL(attention_long<17>, dim3(n_heads), dim3(512), 0, s, qkv, att, S, D, H, scale, causal);
+}
 
 ssw_status run_tower(ssw_clip *c, const Tower &tw, int B, int S, int causal) {
     hipStream_t s = c->stream;
@@ -1560,7 +1750,9 @@ ssw_status run_tower(ssw_clip *c, const Tower &tw, int B, int S, int causal) {
         // (one wave per pair with four tiles, attention_mfma<4, 4>: 21.6 us per layer against 17.1 -- measured, not kept)
         static const bool direct_env = getenv("SSW_CLIP_ATTN_DIRECT") != nullptr;  // A/B: fragments straight from memory
         const bool direct_frags = direct_env || (c->flags & 4) != 0;
-        if (S <= 64 && !one_tile_waves && !direct_frags)
+        if (S > ATT_MAX_S || (c->flags & 64) != 0)
+            launch_attention_long(s, c->qkv, c->att, n_heads, S, D, tw.H, att_scale, causal);
+        else if (S <= 64 && !one_tile_waves && !direct_frags)
             hipLaunchKernelGGL(attention_rows64, dim3(n_heads), dim3(128), 0, s, c->qkv, c->att, S, D, tw.H, att_scale, causal);
         else if (S <= 64 && !one_tile_waves)
             hipLaunchKernelGGL((attention_mfma<4, 2>), dim3(n_heads), dim3(128), 0, s, c->qkv, c->att, S, D, tw.H, att_scale,
@@ -1646,13 +1838,19 @@ ssw_status pool_and_project(ssw_clip *c, const Tower &tw, int B, int D, int norm
 // costs 12.2-12.3 us a tile at 200-256 tiles a call and 10.4-10.8 from 384 on (tile-count rounding of the 256-row GEMM
 // tiles, launch ramps); 1024 tiles are ~2 GB of activations of the 288.
 constexpr int HOST_CHUNK = 1024;
+// HOST_CHUNK is the count for a tower of at most ATT_MAX_S tokens; a longer image tower gets as many tiles as make the same
+// number of token rows (ViT-L/14: 318), so the workspace and every row index stay where ViT-B/32 has them.  A tile's
+// vector does not depend on the chunk: no product of the image tower chooses its form by the row count.
+inline int image_chunk(const Header &h) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>(HOST_CHUNK, (int64_t)HOST_CHUNK * ATT_MAX_S / vision_tokens(h)));
+}
 
 // c->patches holds the im2col'ed bf16 patches of B images
 ssw_status image_forward_from_patches(ssw_clip *c, int B, int normalize, float *out_dev) {
     hipStream_t s = c->stream;
     const Header &h = c->hdr;
     const int g = h.image / h.patch, T = g * g + 1, D = h.v_hidden;
-    const int pcols = 3 * h.patch * h.patch;
+    const int pcols = patch_cols(h.patch);
     SSW_TRY(gemm<EPI_F32>(s, c->patches, c->patch_w, nullptr, nullptr, c->patch_out, B * (T - 1), D, pcols));
     // cls / patch rows + position embedding, then the pre-LayerNorm = the stack's input row, in one pass: bf16 copy and
     // statistics for layer 0's QKV, and the f32 row into c->hidden unless the stack keeps its rows in bf16
@@ -1674,15 +1872,24 @@ ssw_status image_forward_from_patches(ssw_clip *c, int B, int normalize, float *
 
 ssw_status image_forward(ssw_clip *c, const float *pixels_dev, int B, int normalize, float *out_dev) {
     const Header &h = c->hdr;
-    hipLaunchKernelGGL(im2col_patches, dim3(2048), dim3(256), 0, c->stream, pixels_dev, c->patches, B, h.image, h.patch);
+    if (h.patch % 8 == 0)
+        hipLaunchKernelGGL(im2col_patches, dim3(2048), dim3(256), 0, c->stream, pixels_dev, c->patches, B, h.image, h.patch);
+    else
+        hipLaunchKernelGGL(im2col_patches_any<false>, dim3(2048), dim3(256), 0, c->stream, (const void *)pixels_dev, c->patches, B,
+                           h.image, h.patch, patch_cols(h.patch), 0.f, 0.f, 0.f, 1.f, 1.f, 1.f);
     return image_forward_from_patches(c, B, normalize, out_dev);
 }
 
 // CLIP's pixel statistics (make_clip_transform, embeddings.py:405-419; batch_tx, multiscale_tools.py:176-179)
 ssw_status image_forward_u8(ssw_clip *c, const uint8_t *tiles_dev, int B, int normalize, float *out_dev) {
     const Header &h = c->hdr;
-    hipLaunchKernelGGL(im2col_patches_u8, dim3(2048), dim3(256), 0, c->stream, tiles_dev, c->patches, B, h.image, h.patch,
-                       0.48145466f, 0.4578275f, 0.40821073f, 0.26862954f, 0.26130258f, 0.27577711f);
+    if (h.patch % 8 == 0)
+        hipLaunchKernelGGL(im2col_patches_u8, dim3(2048), dim3(256), 0, c->stream, tiles_dev, c->patches, B, h.image, h.patch,
+                           0.48145466f, 0.4578275f, 0.40821073f, 0.26862954f, 0.26130258f, 0.27577711f);
+    else
+        hipLaunchKernelGGL(im2col_patches_any<true>, dim3(2048), dim3(256), 0, c->stream, (const void *)tiles_dev, c->patches, B,
+                           h.image, h.patch, patch_cols(h.patch), 0.48145466f, 0.4578275f, 0.40821073f, 0.26862954f,
+                           0.26130258f, 0.27577711f);
     return image_forward_from_patches(c, B, normalize, out_dev);
 }
 
@@ -1710,7 +1917,8 @@ extern "C" {
 
 ssw_status ssw_clip_set_option(ssw_clip *c, int32_t option, int32_t value) {
     SSW_REQUIRE(c != nullptr, "clip is NULL");
-    SSW_REQUIRE(option >= 0 && option <= 4, "ssw_clip_set_option: option %d unknown (SSW_CLIP_OPT_*)", option);
+    SSW_REQUIRE((option >= 0 && option <= 4) || option == SSW_CLIP_OPT_ATTN_LONG,
+                "ssw_clip_set_option: option %d unknown (SSW_CLIP_OPT_*)", option);
     DeviceGuard guard(c->device);
     SSW_HIP_TRY(hipStreamSynchronize(c->stream));  // a forward in flight keeps the form it started with
     if (value) c->flags |= 1 << option;
@@ -1767,9 +1975,10 @@ ssw_status ssw_clip_create(int32_t device, const void *weight_blob, size_t bytes
     const int g = h.patch > 0 ? h.image / h.patch : 0;
     const int Tv = g * g + 1;
     if (h.v_hidden % 128 || h.t_hidden % 128 || h.v_mlp % 128 || h.t_mlp % 128 || h.proj % 4 ||
-        (3 * h.patch * h.patch) % 64 || h.v_hidden / h.v_heads != 64 || h.t_hidden / h.t_heads != 64 ||
-        Tv > ATT_MAX_S || h.t_maxpos > ATT_MAX_S || h.v_hidden > 1024 || h.t_hidden > 1024 || h.proj > 1024) {
-        set_error("clip: configuration outside what the kernels support (head_dim 64, <= 80 tokens, dims %% 128)");
+        h.patch <= 0 || h.image <= 0 || h.image % h.patch || h.v_hidden / h.v_heads != 64 || h.t_hidden / h.t_heads != 64 ||
+        Tv > ATT_LONG_MAX_S || h.t_maxpos > ATT_MAX_S || h.v_hidden > 1024 || h.t_hidden > 1024 || h.proj > 1024) {
+        set_error("clip: configuration outside what the kernels support (head_dim 64, dims %% 128 and <= 1024, image tower <= %d "
+                  "tokens with a patch size that divides the image, text tower <= %d positions)", ATT_LONG_MAX_S, ATT_MAX_S);
         return SSW_ERR_UNSUPPORTED;
     }
     DeviceGuard guard(device);
@@ -1793,7 +2002,7 @@ ssw_status ssw_clip_create(int32_t device, const void *weight_blob, size_t bytes
     size_t big = (size_t)h.vocab * h.t_hidden;
     big = std::max(big, (size_t)3 * h.v_hidden * h.v_hidden);
     big = std::max(big, (size_t)h.v_mlp * h.v_hidden);
-    big = std::max(big, (size_t)h.v_hidden * 3 * h.patch * h.patch);
+    big = std::max(big, (size_t)h.v_hidden * patch_cols(h.patch));
     float *scratch = nullptr;
     if (hipMalloc((void **)&scratch, big * sizeof(float)) != hipSuccess) {
         set_error("clip: scratch allocation failed");
@@ -1804,7 +2013,23 @@ ssw_status ssw_clip_create(int32_t device, const void *weight_blob, size_t bytes
         c->vis.D = h.v_hidden; c->vis.L = h.v_layers; c->vis.H = h.v_heads; c->vis.M = h.v_mlp; c->vis.T = Tv;
         c->txt.D = h.t_hidden; c->txt.L = h.t_layers; c->txt.H = h.t_heads; c->txt.M = h.t_mlp; c->txt.T = h.t_maxpos;
         if ((st = upload_f32(c, cur, end, h.v_hidden, &c->cls)) != SSW_OK) break;
-        if ((st = upload_bf16(c, cur, end, (size_t)h.v_hidden * 3 * h.patch * h.patch, &c->patch_w, scratch)) != SSW_OK) break;
+        {   // the patch weight [v_hidden][3 patch^2], its rows padded with zero columns to patch_cols (the blob is not padded)
+            const size_t pc = (size_t)3 * h.patch * h.patch, ld = patch_cols(h.patch), n = (size_t)h.v_hidden * pc;
+            if (cur + n > end) {
+                set_error("clip: weight blob truncated");
+                st = SSW_ERR_INVALID;
+                break;
+            }
+            if (ld == pc) {
+                if ((st = upload_bf16(c, cur, end, n, &c->patch_w, scratch)) != SSW_OK) break;
+            } else {
+                std::vector<float> padded((size_t)h.v_hidden * ld, 0.f);
+                for (size_t r = 0; r < (size_t)h.v_hidden; ++r) memcpy(padded.data() + r * ld, cur + r * pc, pc * sizeof(float));
+                const float *p = padded.data();
+                if ((st = upload_bf16(c, p, p + padded.size(), padded.size(), &c->patch_w, scratch)) != SSW_OK) break;
+                cur += n;
+            }
+        }
         if ((st = upload_f32(c, cur, end, (size_t)Tv * h.v_hidden, &c->vpos)) != SSW_OK) break;
         if ((st = upload_f32(c, cur, end, h.v_hidden, &c->pre_w)) != SSW_OK) break;
         if ((st = upload_f32(c, cur, end, h.v_hidden, &c->pre_b)) != SSW_OK) break;
@@ -1830,7 +2055,7 @@ ssw_status ssw_clip_embed_image(ssw_clip *c, const float *nchw_host, int32_t b, 
     SSW_REQUIRE(c && nchw_host && out_host && b > 0, "bad argument");
     DeviceGuard guard(c->device);
     const Header &h = c->hdr;
-    const int chunk = HOST_CHUNK;
+    const int chunk = image_chunk(h);
     SSW_TRY(reserve(c, std::min<int64_t>(b, chunk)));
     const size_t per = (size_t)3 * h.image * h.image;
     for (int b0 = 0; b0 < b; b0 += chunk) {
@@ -1850,8 +2075,7 @@ ssw_status ssw_clip_embed_tiles_u8(ssw_clip *c, const uint8_t *tiles_hwc_host, i
     SSW_REQUIRE(c && tiles_hwc_host && out_host && b > 0, "bad argument");
     DeviceGuard guard(c->device);
     const Header &h = c->hdr;
-    SSW_REQUIRE(h.patch % 8 == 0, "clip: patch size %d is not a multiple of 8", h.patch);
-    const int chunk = HOST_CHUNK;
+    const int chunk = image_chunk(h);
     SSW_TRY(reserve(c, std::min<int64_t>(b, chunk)));
     const size_t per = (size_t)3 * h.image * h.image;  // bytes per tile; c->pixels (f32) is 4x that
     for (int b0 = 0; b0 < b; b0 += chunk) {
@@ -1870,7 +2094,7 @@ ssw_status ssw_clip_embed_image_dev(ssw_clip *c, void *hip_stream, const float *
                                     int32_t normalize, float *out_dev) {
     SSW_REQUIRE(c && nchw_dev && out_dev && b > 0, "bad argument");
     DeviceGuard guard(c->device);
-    SSW_REQUIRE(b <= 1024, "clip: at most 1024 images per device-side call");
+    SSW_REQUIRE(b <= image_chunk(c->hdr), "clip: at most %d images per device-side call", image_chunk(c->hdr));
     SSW_TRY(reserve(c, b));
     hipStream_t saved = c->stream;
     if (hip_stream) c->stream = (hipStream_t)hip_stream;

@@ -173,7 +173,7 @@ class InferenceActor:
         out = []
         for s in range(0, len(tiles), self.batch_size):
             out.append(self.model.embed_tiles_u8(np.stack(tiles[s:s + self.batch_size]), normalize=True))
-        vecs = np.concatenate(out) if out else np.zeros((0, 512), np.float32)
+        vecs = np.concatenate(out) if out else np.zeros((0, getattr(self.model, "projection_dim", 512)), np.float32)
         return batch_df.drop(["tile"], axis=1).assign(vectors=list(vecs))
 
 

@@ -1,4 +1,4 @@
-"""CLIP ViT-B/32 on the GPU: weight packing + ctypes front of the ssw_clip_* entry points.
+"""CLIP (ViT-B/32, ViT-B/16, ViT-L/14) on the GPU: weight packing + ctypes front of the ssw_clip_* entry points.
 
 The reference loads `transformers.CLIPModel.from_pretrained(<local dir>)` and calls
 `get_text_features` / `get_image_features` (seesaw/models/embeddings.py:427-455,
@@ -18,6 +18,12 @@ _LAYER_KEYS = ["layer_norm1.weight", "layer_norm1.bias", "self_attn.q_proj.weigh
                "self_attn.k_proj.weight", "self_attn.k_proj.bias", "self_attn.v_proj.weight", "self_attn.v_proj.bias",
                "self_attn.out_proj.weight", "self_attn.out_proj.bias", "layer_norm2.weight", "layer_norm2.bias",
                "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias"]
+
+
+def patch_columns(patch_size: int) -> int:
+    """Columns of a gathered patch row on the device: 3 patch^2 padded with zero columns to the next multiple of 64
+    (csrc/clip.hip, patch_cols; patch 14: 588 -> 640).  The blob is not padded: ssw_clip_create pads the patch weight."""
+    return -(-3 * patch_size * patch_size // 64) * 64
 
 
 def pack_clip_weights(state_dict, config) -> np.ndarray:
@@ -60,6 +66,7 @@ class ClipModel:
         self._h = ctypes.c_void_p()
         hdr = struct.unpack("<8s6i7iifi", blob[:72].tobytes())
         self.image_size, self.patch_size = hdr[5], hdr[6]
+        self.vision_hidden, self.text_hidden = hdr[1], hdr[7]
         self.max_positions, self.vocab_size, self.eos_token_id, self.projection_dim = hdr[11], hdr[12], hdr[13], hdr[14]
         _lib.call("ssw_clip_create", int(device), ctypes.c_void_p(blob.ctypes.data), ctypes.c_size_t(blob.nbytes),
                   ctypes.byref(self._h))
@@ -69,12 +76,14 @@ class ClipModel:
         return cls(pack_clip_weights(hf_model.state_dict(), hf_model.config), device=device)
 
     @classmethod
-    def random_init(cls, seed: int = 1234, device: int = 0) -> "ClipModel":
-        """BASELINE.json: 'random-init CLIP weights' -- transformers.CLIPModel(CLIPConfig()) under a seed."""
+    def random_init(cls, seed: int = 1234, device: int = 0, config=None) -> "ClipModel":
+        """BASELINE.json: 'random-init CLIP weights' -- transformers.CLIPModel(CLIPConfig()) under a seed.
+        `config`: a transformers.CLIPConfig of another variant (ViT-B/16, ViT-L/14); default ViT-B/32."""
         import torch
         import transformers
         torch.manual_seed(seed)
-        return cls.from_hf(transformers.CLIPModel(transformers.CLIPConfig()).eval(), device=device)
+        cfg = transformers.CLIPConfig() if config is None else config
+        return cls.from_hf(transformers.CLIPModel(cfg).eval(), device=device)
 
     def close(self):
         if self._h:
@@ -113,6 +122,7 @@ class ClipModel:
 
     # ssw_clip_set_option (include/seesaw_hip.h): per-handle form of the towers' tile path
     OPT_IMAGE_ROWS_BF16, OPT_TEXT_ROWS_BF16, OPT_ATTN_DIRECT, OPT_ATTN_OUT_UNFUSED, OPT_FULL_LAST_LAYER = 0, 1, 2, 3, 4
+    OPT_ATTN_LONG = 6  # the long-sequence attention kernel for towers of <= 80 tokens too (5 is not an option)
 
     def set_option(self, option: int, value: bool):
         _lib.call("ssw_clip_set_option", self._h, int(option), int(bool(value)))
