@@ -482,9 +482,16 @@ ssw_status ssw_index_profile_read(ssw_index *idx, float *out_ms, int32_t cap, in
  * rows of it -- and raise the threshold to the k-th exact score of max(1024, 4 k) candidates before the survivors are
  * listed; such an index builds no 6-bit shadow for single queries (a pruned batch still builds its own), [0] reports
  * the 5-bit shadow and [5] includes its bytes.  Refused for memory, it leaves the 6-bit and then the int8 path.
+ * The same calls scan the two-stage form of those 5-bit codes instead where the library's constant for it admits the
+ * index ("Two-stage 4 + 1-bit shadow"): a 4-bit plane every row is scanned on and a 1-bit plane read
+ * only for the rows that scan leaves, 5 dim / 8 + 16 bytes a row in all; such an index builds no packed 5-bit shadow, [0]
+ * reports the two-stage shadow and [5] includes its bytes; refused for memory, it leaves the 5-bit path.
  * out6: [0] shadow 0 none / 1 current / 2 stale / 3 refused (memory), [1] 1 = the next top-k with a query is pruned,
  * [2] survivors of the last pruned call (-1 = it fell back), [3] pruned calls, [4] fallbacks, [5] shadow bytes. */
 ssw_status ssw_index_prune_stats(ssw_index *idx, int64_t *out6);
+/* the two-stage shadow's own counters: out3 [0] rows the first stage left in the last such call, [1] calls so far whose
+ * second stage walked every row because the first left more than its list admits (dense), [2] two-stage calls so far. */
+ssw_status ssw_index_prune_coarse_stats(ssw_index *idx, int64_t *out3);
 /* what the readers of a partial score buffer or slab cost: out2 [0] full scans launched to complete one (by a reader of
  * the whole buffer, by a second-stage call over more than 2^18 rows, before the rows change), [1] rows scored by gather
  * instead -- the candidates' tile total of ssw_index_rescore_avg, the rows of ssw_index_gather_scores, the k x T list

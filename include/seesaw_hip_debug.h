@@ -126,6 +126,32 @@ ssw_status ssw_debug_prune6_survivors(ssw_index *idx, float threshold, int32_t k
  *   ssw_debug_prune5_bounds, against a threshold written by hand (the product raises the selection's k-th key to the
  *   exact threshold first); arguments and outputs as ssw_debug_prune_survivors. */
 ssw_status ssw_tune_prune5(int32_t enable, int64_t min_rows);
+/* The two-stage 4 + 1-bit shadow (csrc/prune.hip; tests/test_prune41_gpu.py).
+ * ssw_tune_prune41: enable 0 = no index takes the two-stage path; min_rows >= 0 = the smallest index whose single queries
+ *   take it, < 0 = the product's constant again; coarse_cap in [0, 2^23] = the first-stage survivors above which the
+ *   refine walks every row instead of the list (dense), any other value = 2^23.
+ * ssw_tune_prune41_scan / ssw_debug_prune41_scan_shape: the launch shape of k_q4_bounds, as ssw_tune_prune5_scan.
+ * ssw_debug_prune41_shadow: builds the shadow if it is missing or stale and copies out, for rows [first_row, first_row +
+ *   n_rows): the nibbles h [n_rows, dim] in natural element order (by q4_nibble, the builder's placement function), the
+ *   fine plane's words [n_rows, dim / 32], s5, a5 and a4.  NULL outputs are skipped.
+ * ssw_debug_prune41_stage1: k_q41_query + k_q4_bounds for one host query: out_H [n], out_lb4 [n], out_Qe [4] as
+ *   ssw_debug_prune6_bounds, out_sumD [2] = the sums of the hi and lo code planes.
+ * ssw_debug_prune41_survivors1: k_survivors_q4 over those bounds against a threshold written by hand, with `blocks`
+ *   blocks (0 = the product's grid): *out_count = the counter, out_rows [min(count, rows_cap)] the list.
+ * ssw_debug_prune41_refine: k_q41_refine over the list `rows` [m] given by hand (repeats allowed), against a threshold
+ *   written by hand; with m above the coarse cap the kernel walks every row instead and the outputs are per row.
+ *   out_lb5 / out_B: per entry (per row when dense); *out_survivors and out_surv_rows [min(survivors, SURV_CAP)]. */
+ssw_status ssw_tune_prune41(int32_t enable, int64_t min_rows, int64_t coarse_cap);
+ssw_status ssw_tune_prune41_scan(int32_t blocks_per_cu, int32_t tiles);
+ssw_status ssw_debug_prune41_scan_shape(ssw_index *idx, int32_t *out_blocks, int32_t *out_tiles);
+ssw_status ssw_debug_prune41_shadow(ssw_index *idx, int64_t first_row, int64_t n_rows, uint8_t *out_h, uint32_t *out_fine,
+                                    float *out_s5, float *out_a5, float *out_a4);
+ssw_status ssw_debug_prune41_stage1(ssw_index *idx, const float *q_host, int32_t *out_H, float *out_lb4, float *out_Qe,
+                                    int32_t *out_sumD);
+ssw_status ssw_debug_prune41_survivors1(ssw_index *idx, float threshold, int32_t k, int32_t blocks, int64_t rows_cap,
+                                        int64_t *out_count, uint32_t *out_rows);
+ssw_status ssw_debug_prune41_refine(ssw_index *idx, const uint32_t *rows, int64_t m, float threshold, int32_t k,
+                                    float *out_lb5, int32_t *out_B, int64_t *out_survivors, int64_t *out_surv_rows);
 ssw_status ssw_tune_prune5_scan(int32_t blocks_per_cu, int32_t tiles);
 ssw_status ssw_debug_prune5_scan_shape(ssw_index *idx, int32_t *out_blocks, int32_t *out_tiles);
 ssw_status ssw_debug_prune5_shadow(ssw_index *idx, int64_t first_row, int64_t n_rows, int8_t *out_codes, float *out_scale,
@@ -187,7 +213,8 @@ ssw_status ssw_debug_prune6_survivors_mq(ssw_index *idx, int32_t nq, int32_t slo
                                          int64_t *out_collected, int64_t *out_rows);
 
 /* The pruned batch that stays on the device (seesaw_hip.h, ssw_index_topk_batch_dev_pruned; csrc/rescore_dev.hip).
- * ssw_tune_surv_cap: the survivors a slot of that entry may have and still be certified, 1 .. 2^18; any other value =
+ * ssw_tune_surv_cap: the survivors a slot of that entry may have and still be certified (and the final survivors of a
+ *   single query on the two-stage 4 + 1-bit shadow, ssw_tune_prune41), 1 .. 2^18; any other value =
  *   the product's 2^18.  Governs that entry and the hook below only.
  * ssw_debug_rescore_survivors: k_rescore_survivors alone, through the product's launch function, on the index's own
  *   chunk buffers (dim 256 / 512 / 1024; no shadow is needed).  nq <= 16 host queries [nq, dim]; slot j's state words

@@ -164,6 +164,7 @@ _SIGNATURES = {
     "ssw_index_profile_read": (c_i32, [c_void_p, c_void_p, c_i32, c_i32_p]),
     "ssw_index_prune_stats": (c_i32, [c_void_p, c_i64_p]),
     "ssw_index_prune_completions": (c_i32, [c_void_p, c_i64_p]),
+    "ssw_index_prune_coarse_stats": (c_i32, [c_void_p, c_i64_p]),
 }
 
 
@@ -200,6 +201,14 @@ _DEBUG_SIGNATURES = {
     "ssw_debug_prune5_bounds": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ssw_debug_prune5_survivors": (c_i32, [c_void_p, ctypes.c_float, c_i32, c_i32, c_i32, c_i64, c_i32_p, c_i64_p,
                                            c_void_p]),
+    "ssw_tune_prune41": (c_i32, [c_i32, c_i64, c_i64]),
+    "ssw_tune_prune41_scan": (c_i32, [c_i32, c_i32]),
+    "ssw_debug_prune41_scan_shape": (c_i32, [c_void_p, c_i32_p, c_i32_p]),
+    "ssw_debug_prune41_shadow": (c_i32, [c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ssw_debug_prune41_stage1": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ssw_debug_prune41_survivors1": (c_i32, [c_void_p, ctypes.c_float, c_i32, c_i32, c_i64, c_i64_p, c_void_p]),
+    "ssw_debug_prune41_refine": (c_i32, [c_void_p, c_void_p, c_i64, ctypes.c_float, c_i32, c_void_p, c_void_p, c_i64_p,
+                                         c_void_p]),
     "ssw_tune_prune6_batch": (c_i32, [c_i64]),
     "ssw_tune_prune6_scan_mq": (c_i32, [c_i32, c_i32]),
     "ssw_debug_prune6_scan_mq_shape": (c_i32, [c_void_p, c_i32_p, c_i32_p]),

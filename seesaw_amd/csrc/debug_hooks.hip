@@ -943,6 +943,160 @@ ssw_status ssw_debug_prune5_survivors(ssw_index *idx, float threshold, int32_t k
     return SSW_OK;
 }
 
+// ---- the two-stage 4 + 1-bit shadow (prune.hip, "two-stage 4 + 1-bit shadow"; tests/test_prune41_gpu.py) -------------
+static ssw_status require_shadow41(ssw_index *idx, const char *who) {
+    SSW_REQUIRE(prune41_eligible(idx),
+                "the index takes no two-stage shadow (ssw_tune_prune41, rows, dim, dtype, image map, borrowed or escaped rows)");
+    return require_shadow(idx, who, SHADOW_Q41);
+}
+
+ssw_status ssw_debug_prune41_scan_shape(ssw_index *idx, int32_t *out_blocks, int32_t *out_tiles) {
+    SSW_REQUIRE(idx != nullptr && out_blocks != nullptr && out_tiles != nullptr, "NULL argument");
+    SSW_REQUIRE(q5_dim_supported(idx->dim), "dim=%d has no two-stage shadow scan", idx->dim);
+    int blocks = 0, tiles = 0;
+    scan_shape(SCAN_Q4, idx->dim, idx->device, idx->n, &blocks, &tiles);
+    *out_blocks = blocks;
+    *out_tiles = tiles;
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_prune41_shadow(ssw_index *idx, int64_t first_row, int64_t n_rows, uint8_t *out_h, uint32_t *out_fine,
+                                    float *out_s5, float *out_a5, float *out_a4) {
+    SSW_REQUIRE(idx != nullptr, "idx is NULL");
+    SSW_REQUIRE(first_row >= 0 && n_rows >= 0 && first_row + n_rows <= idx->n, "rows [%lld, +%lld) outside [0, %lld)",
+                (long long)first_row, (long long)n_rows, (long long)idx->n);
+    DeviceGuard guard(idx->device);
+    SSW_TRY(require_shadow41(idx, "prune41_shadow"));
+    if (n_rows == 0) return SSW_OK;
+    const Shadow &s = idx->prune.sh[SHADOW_Q41];
+    const int dim = idx->dim;
+    const size_t tile_bytes = (size_t)16 * dim / 2, fw = (size_t)dim / 32;
+    const int64_t tile0 = first_row >> 4, tile1 = (first_row + n_rows - 1) >> 4;
+    std::vector<unsigned char> packed(out_h ? (size_t)(tile1 - tile0 + 1) * tile_bytes : 0);
+    if (out_h)
+        SSW_HIP_TRY(hipMemcpyAsync(packed.data(), s.codes + (size_t)tile0 * tile_bytes, packed.size(), hipMemcpyDeviceToHost,
+                                   idx->stream));
+    if (out_fine)
+        SSW_HIP_TRY(hipMemcpyAsync(out_fine, s.fine + (size_t)first_row * fw, (size_t)n_rows * fw * sizeof(uint32_t),
+                                   hipMemcpyDeviceToHost, idx->stream));
+    const float *src[3] = {s.scale, s.err, s.err4};
+    float *dst[3] = {out_s5, out_a5, out_a4};
+    for (int t = 0; t < 3; ++t)
+        if (dst[t])
+            SSW_HIP_TRY(hipMemcpyAsync(dst[t], src[t] + first_row, (size_t)n_rows * sizeof(float), hipMemcpyDeviceToHost,
+                                       idx->stream));
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+    if (!out_h) return SSW_OK;
+    for (int64_t r = first_row; r < first_row + n_rows; ++r) {
+        const unsigned char *tile = packed.data() + (size_t)((r >> 4) - tile0) * tile_bytes;
+        for (int i = 0; i < dim; ++i) {
+            int u, g, j, word, byte, shift;
+            q6_slot(i, &u, &g, &j);
+            q4_nibble(u, j, &word, &byte, &shift);
+            out_h[(size_t)(r - first_row) * dim + i] =
+                (uint8_t)((tile[q6_word_offset(16 * g + (int)(r & 15), word) + (size_t)byte] >> shift) & 15u);
+        }
+    }
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_prune41_stage1(ssw_index *idx, const float *q_host, int32_t *out_H, float *out_lb4, float *out_Qe,
+                                    int32_t *out_sumD) {
+    SSW_REQUIRE(idx != nullptr && q_host != nullptr, "NULL argument");
+    DeviceGuard guard(idx->device);
+    SSW_TRY(require_shadow41(idx, "prune41_stage1"));
+    PruneState &p = idx->prune;
+    unsigned st[Q8_MQ_WORDS] = {};
+    SSW_TRY(idx->q_stage.push(idx->q_dev, q_host, (size_t)idx->dim * sizeof(float), idx->stream));
+    SSW_TRY(prune_bounds(idx, SHADOW_Q41, idx->q_dev, nullptr));  // as in scan_for_topk: readers complete the buffer with q_last
+    if (out_H)
+        SSW_HIP_TRY(hipMemcpyAsync(out_H, p.sh[SHADOW_Q41].H, (size_t)idx->n * sizeof(int32_t), hipMemcpyDeviceToHost, idx->stream));
+    if (out_lb4)
+        SSW_HIP_TRY(hipMemcpyAsync(out_lb4, idx->scores, (size_t)idx->n * sizeof(float), hipMemcpyDeviceToHost, idx->stream));
+    SSW_HIP_TRY(hipMemcpyAsync(st, p.state6, sizeof(st), hipMemcpyDeviceToHost, idx->stream));
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+    if (out_Qe) {
+        memcpy(out_Qe, &st[1], 4);      // Q
+        memcpy(out_Qe + 1, &st[3], 4);  // e
+        memcpy(out_Qe + 2, &st[4], 4);  // t2
+        out_Qe[3] = (float)st[2];       // 1 = the query cannot be bounded
+    }
+    if (out_sumD) out_sumD[0] = (int32_t)st[6], out_sumD[1] = (int32_t)st[7];
+    return SSW_OK;
+}
+
+// the counters the two stages add to, and the "selection failed" word, as k_q41_query leaves them
+static ssw_status reset_stage_words(ssw_index *idx) {
+    unsigned *st = idx->prune.state6;
+    SSW_HIP_TRY(hipMemsetAsync(st, 0, sizeof(unsigned), idx->stream));
+    SSW_HIP_TRY(hipMemsetAsync(st + 5, 0, sizeof(unsigned), idx->stream));
+    SSW_HIP_TRY(hipMemsetAsync(idx->prune.cstate, 0, Q41_STATE_WORDS * sizeof(unsigned), idx->stream));
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_prune41_survivors1(ssw_index *idx, float threshold, int32_t k, int32_t blocks, int64_t rows_cap,
+                                        int64_t *out_count, uint32_t *out_rows) {
+    SSW_REQUIRE(idx != nullptr && out_count != nullptr, "NULL argument");
+    SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
+    SSW_REQUIRE(blocks >= 0 && blocks <= 65536, "blocks=%d outside [0, 65536]", blocks);
+    SSW_REQUIRE(rows_cap >= 0 && (rows_cap == 0 || out_rows != nullptr), "out_rows is NULL");
+    SSW_REQUIRE(idx->scores_partial && shadow_current(idx, SHADOW_Q41), "no bounds in the buffer: ssw_debug_prune41_stage1 first");
+    DeviceGuard guard(idx->device);
+    SSW_TRY(ensure_ws(idx));
+    SSW_TRY(reset_stage_words(idx));
+    SSW_TRY(stand_in_threshold(idx, threshold, k, k, 0));
+    SSW_TRY(prune41_stage1(idx, k, blocks));
+    unsigned count = 0u;
+    SSW_HIP_TRY(hipMemcpyAsync(&count, idx->prune.cstate, sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
+    SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+    const int64_t m = std::min<int64_t>(std::min<int64_t>(count, COARSE_CAP), rows_cap);
+    if (m > 0) SSW_HIP_TRY(hipMemcpy(out_rows, idx->prune.coarse_rows, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    *out_count = (int64_t)count;
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_prune41_refine(ssw_index *idx, const uint32_t *rows, int64_t m, float threshold, int32_t k,
+                                    float *out_lb5, int32_t *out_B, int64_t *out_survivors, int64_t *out_surv_rows) {
+    SSW_REQUIRE(idx != nullptr && out_lb5 != nullptr && out_B != nullptr && out_survivors != nullptr, "NULL argument");
+    SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
+    SSW_REQUIRE(m >= 0 && m <= COARSE_CAP && (m == 0 || rows != nullptr), "m=%lld outside [0, %lld]", (long long)m, (long long)COARSE_CAP);
+    SSW_REQUIRE(idx->scores_partial && shadow_current(idx, SHADOW_Q41), "no bounds in the buffer: ssw_debug_prune41_stage1 first");
+    DeviceGuard guard(idx->device);
+    SSW_TRY(ensure_ws(idx));
+    PruneState &p = idx->prune;
+    const bool dense = m > prune41_coarse_cap();
+    const int64_t entries = dense ? idx->n : m;
+    float *lb5 = nullptr;
+    int32_t *B = nullptr;
+    auto run = [&]() -> ssw_status {
+        SSW_HIP_TRY(hipMalloc((void **)&lb5, (size_t)std::max<int64_t>(entries, 1) * sizeof(float)));
+        SSW_HIP_TRY(hipMalloc((void **)&B, (size_t)std::max<int64_t>(entries, 1) * sizeof(int32_t)));
+        SSW_TRY(reset_stage_words(idx));
+        SSW_TRY(stand_in_threshold(idx, threshold, k, k, 0));
+        const unsigned count = (unsigned)m;
+        if (m > 0) SSW_HIP_TRY(hipMemcpy(p.coarse_rows, rows, (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice));
+        SSW_HIP_TRY(hipMemcpy(p.cstate, &count, sizeof(unsigned), hipMemcpyHostToDevice));
+        SSW_TRY(prune41_refine(idx, k, nullptr, SURV_CAP, lb5, B));
+        unsigned found = 0u;
+        SSW_HIP_TRY(hipMemcpyAsync(&found, p.state6, sizeof(unsigned), hipMemcpyDeviceToHost, idx->stream));
+        SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+        if (entries > 0) {
+            SSW_HIP_TRY(hipMemcpy(out_lb5, lb5, (size_t)entries * sizeof(float), hipMemcpyDeviceToHost));
+            SSW_HIP_TRY(hipMemcpy(out_B, B, (size_t)entries * sizeof(int32_t), hipMemcpyDeviceToHost));
+        }
+        const int64_t got = std::min<int64_t>(found, SURV_CAP);
+        if (got > 0 && out_surv_rows)
+            SSW_HIP_TRY(hipMemcpy(out_surv_rows, p.surv_rows, (size_t)got * sizeof(int64_t), hipMemcpyDeviceToHost));
+        *out_survivors = (int64_t)found;
+        return SSW_OK;
+    };
+    const ssw_status rc = run();
+    if (rc != SSW_OK) (void)hipStreamSynchronize(idx->stream);
+    (void)hipFree(lb5);
+    (void)hipFree(B);
+    return rc;
+}
+
 ssw_status ssw_debug_prune6_scan_shape(ssw_index *idx, int32_t *out_blocks, int32_t *out_tiles) {
     SSW_REQUIRE(idx != nullptr && out_blocks != nullptr && out_tiles != nullptr, "NULL argument");
     SSW_REQUIRE(q6_dim_supported(idx->dim), "dim=%d has no shadow scan", idx->dim);

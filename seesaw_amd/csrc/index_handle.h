@@ -12,25 +12,34 @@ constexpr int64_t SMALL_ROWS = 65536;               // and the small scan kernel
 // single queries scan instead on an index of enough rows, and the packed 5-bit one that single queries on a still larger
 // f32 index without an image map scan instead of that (index_prune.hip, MIN_ROWS, MIN_ROWS_Q5).  Each is built lazily by
 // the first top-k with a query that wants it after the rows last changed
-enum ShadowKind { SHADOW_Q8, SHADOW_Q6, SHADOW_Q5 };
+// SHADOW_Q41: the 5-bit codes as a 4-bit plane every row is scanned on and a 1-bit plane read for the survivors of that
+// scan alone (prune.hip, "two-stage 4 + 1-bit shadow"); where it applies (MIN_ROWS_Q41) no packed 5-bit shadow is built
+enum ShadowKind { SHADOW_Q8, SHADOW_Q6, SHADOW_Q5, SHADOW_Q41 };
 struct Shadow {
     unsigned char *codes = nullptr;               // int8: [n, dim] codes; 6-bit: q6_code_bytes(n, dim), tiles of 16 rows;
                                                   // 5-bit: q5_code_bytes(n, dim), tiles of 16 rows
     float *scale = nullptr, *err = nullptr;       // s_r, a_r: [n]; 6-bit, 5-bit: [packed_padded_rows(n)]
-    unsigned *max = nullptr;                      // [SHADOW_MAX_WORDS] the largest finite a_r, s_r (launch_shadow_max)
+    unsigned *max = nullptr;                      // [SHADOW_MAX_WORDS] the largest finite a_r, s_r (launch_shadow_max);
+                                                  // SHADOW_Q41: of a4_r, s5_r (the first stage's width)
+    // SHADOW_Q41 only: codes is the coarse plane (q41_coarse_bytes), scale / err are s5 / a5, and beside them
+    float *err4 = nullptr;                        // a4_r [packed_padded_rows(n)]
+    int32_t *H = nullptr;                         // [packed_padded_rows(n)] the last first-stage scan's integer sums
+    unsigned *fine = nullptr;                     // the fine plane (q41_fine_bytes)
     bool stale = true;                            // the rows changed since the shadow was built
     bool refused = false;                         // too little free memory at the last attempt (until the rows change)
     void free() {
-        for (void *p : {(void *)codes, (void *)scale, (void *)err}) (void)hipFree(p);
+        for (void *p : {(void *)codes, (void *)scale, (void *)err, (void *)err4, (void *)H, (void *)fine}) (void)hipFree(p);
         codes = nullptr;
-        scale = err = nullptr;
+        scale = err = err4 = nullptr;
+        H = nullptr;
+        fine = nullptr;
         stale = true;
     }
 };
 
 // the shadows and the buffers of one pruned call
 struct PruneState {
-    Shadow sh[3];                                  // by ShadowKind
+    Shadow sh[4];                                  // by ShadowKind
     unsigned *state = nullptr;                     // [4] device words (ssw_common.h, launch_q8_query)
     int64_t *surv_rows = nullptr;                  // [SURV_CAP]
     float *surv_scores = nullptr;                  // [SURV_CAP]
@@ -44,6 +53,11 @@ struct PruneState {
     // a single query on the 6-bit or the 5-bit shadow
     unsigned *state6 = nullptr;                    // [Q8_MQ_WORDS] the query's words, a slot's of the chunk
     int8_t *planes6 = nullptr;                     // q6_plane_bytes(dim): the query's operand
+    // a single query on the two-stage shadow, beside those
+    unsigned *cstate = nullptr;                    // [Q41_STATE_WORDS] the first stage's counter, the dense flag
+    uint32_t *coarse_rows = nullptr;               // [COARSE_CAP] the first stage's survivors
+    int32_t *D41 = nullptr;                        // [dim] the query's 256 d_hi + d_lo in natural order
+    int64_t coarse_last = 0, dense_refines = 0, two_stage_calls = 0;  // ssw_index_prune_coarse_stats
     void free_shadow() {
         for (Shadow &s : sh) s.free();
     }
@@ -52,7 +66,8 @@ struct PruneState {
             s.free();
             (void)hipFree(s.max);
         }
-        for (void *p : {(void *)state, (void *)surv_rows, (void *)surv_scores, (void *)q_last, (void *)state6, (void *)planes6})
+        for (void *p : {(void *)state, (void *)surv_rows, (void *)surv_scores, (void *)q_last, (void *)state6, (void *)planes6,
+                        (void *)cstate, (void *)coarse_rows, (void *)D41})
             (void)hipFree(p);
         if (host) (void)hipHostFree(host);
         if (ev) (void)hipEventDestroy(ev);
@@ -231,6 +246,10 @@ bool prune_eligible(const ssw_index *idx);
 bool prune_batch_eligible(const ssw_index *idx);
 bool prune6_eligible(const ssw_index *idx);
 bool prune5_eligible(const ssw_index *idx);
+bool prune41_eligible(const ssw_index *idx);
+int64_t prune41_coarse_cap();
+ssw_status prune41_stage1(ssw_index *idx, int32_t k, int blocks);
+ssw_status prune41_refine(ssw_index *idx, int32_t k, const uint32_t *list_or_null, int64_t cap, float *dbg_lb5, int32_t *dbg_B);
 ssw_status prune_exact_threshold(ssw_index *idx, int32_t k, int32_t kc);
 ssw_status ensure_shadow(ssw_index *idx, ShadowKind kind, bool *ready);
 ssw_status rows_changing(ssw_index *idx);

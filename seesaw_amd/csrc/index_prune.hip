@@ -1,5 +1,5 @@
-// index_prune.hip -- the certified pre-scan of the index's top-k: when it applies, the int8, the packed 6-bit and the packed
-// 5-bit shadow of the rows, and the steps of one pruned query and of one pruned chunk of a batch (kernels: prune.hip).  The handle:
+// index_prune.hip -- the certified pre-scan of the index's top-k: when it applies, the int8, the packed 6-bit, the packed
+// 5-bit and the two-stage 4 + 1-bit shadow of the rows, and the steps of one pruned query and of one pruned chunk of a batch (kernels: prune.hip).  The handle:
 // index_handle.h.
 #include <algorithm>
 
@@ -82,34 +82,75 @@ constexpr int64_t MIN_ROWS[2][2][2][2] = {
 // 1.539 at 25 M (spreads 0.071 together), 2.350 / 1.905 at 2^25, 3.408 / 2.972 at 50 M, 6.335 / 5.377 at 100 M (0.165):
 // ahead by more than both spreads at every size of the sweep, so the entry is its smallest.
 constexpr int64_t MIN_ROWS_Q5 = 25000000;
+// ---- SHADOW_Q41 ----
+// The calls that take the 5-bit shadow scan the two-stage 4 + 1-bit shadow instead on an index of at least this many rows
+// (264 instead of 328 bytes a row read by the scan at dim 512, a refine pass over the first stage's survivors; prune.hip,
+// "two-stage 4 + 1-bit shadow"), and such an index builds no packed 5-bit shadow.  One entry under the rule above
+// MIN_ROWS_Q5, against the 5-bit call, over the same sizes; never below 25 M rows.
+// Measured (profiles/prune41_sweep.txt, tools/perf_prune.py --two-stage, host wall ms a call, 5-bit / two-stage, medians of
+// 20, spreads together in brackets): 1.563 / 1.435 at 25 M (0.067), 2.090 / 1.934 at 2^25 (0.157), 2.825 / 2.701 at 50 M
+// (0.250), 5.890 / 4.946 at 100 M (0.224).  The two-stage call is ahead at every size, but at 2^25 and 50 M rows by no more
+// than the spreads, so the rule admits 100 M rows alone (profiles/prune41_*_kernel_stats.txt, 10^8 rows: the scan saves
+// 0.74 ms a launch and the two passes over the first stage's 1.5 M survivors cost 0.23 ms more than k_survivors_mq).  A second
+// run of the sweep (the same file): 1.553 / 1.447 (0.065), 2.078 / 1.953 (0.133), 2.779 / 2.647 (0.071), 5.435 / 4.950
+// (0.113) -- 2^25 rows inside the spreads again, 50 M outside them this time; a size has to clear in both.
+constexpr int64_t MIN_ROWS_Q41 = 100000000;
 constexpr int64_t PRUNE_RESERVE = (int64_t)4 << 30;   // free device memory the shadow must leave
 static SSW_TUNABLE bool g_prune = true;               // ssw_tune_prune
 static SSW_TUNABLE bool g_prune6 = true;              // ssw_tune_prune6
 static SSW_TUNABLE bool g_prune5 = true;              // ssw_tune_prune5
 static SSW_TUNABLE int64_t g_prune5_min_rows = -1;     // >= 0: this many rows instead of MIN_ROWS_Q5
+static SSW_TUNABLE bool g_prune41 = true;             // ssw_tune_prune41
+static SSW_TUNABLE int64_t g_prune41_min_rows = -1;    // >= 0: this many rows instead of MIN_ROWS_Q41
+static SSW_TUNABLE int64_t g_coarse_cap = COARSE_CAP;  // first-stage survivors the refine walks as a list; more: dense
 static SSW_TUNABLE int64_t g_prune6_min_rows = -1;     // >= 0: this many rows for both dtypes instead
 static SSW_TUNABLE int64_t g_prune_min_rows = -1;      // >= 0: this many rows for both dtypes instead
 static SSW_TUNABLE int64_t g_prune6_batch_min_rows = -1;  // ssw_tune_prune6_batch: >= 0: the batch's, for both dtypes
 static SSW_TUNABLE int64_t g_prune_reserve = PRUNE_RESERVE;
-static SSW_TUNABLE int64_t g_surv_cap_dev = SURV_CAP;  // ssw_tune_surv_cap: of ssw_index_topk_batch_dev_pruned only
+static SSW_TUNABLE int64_t g_surv_cap_dev = SURV_CAP;  // ssw_tune_surv_cap: of ssw_index_topk_batch_dev_pruned, and of the
+                                                       // two-stage single call's final survivors (scan_for_topk)
 
 // what differs between the shadows where they are made: the dims, the sizes of the codes and of the two constant
-// arrays, the builder, and whether a single query on it needs its own state words and operand (state6, planes6)
+// arrays, what the shadow holds beside them, the builder (into the shadow's buffers), the constant whose maximum the
+// survivor pass pre-tests with, and whether a single query on it needs its own state words and operand (state6, planes6)
 struct ShadowDesc {
     bool (*dim_ok)(int32_t dim);
     size_t (*code_bytes)(int64_t n, int32_t dim);
     int64_t (*const_rows)(int64_t n);
-    ssw_status (*build)(const void *X, int32_t dtype, int64_t n, int32_t dim, unsigned char *codes, float *scale, float *err,
-                        hipStream_t stream);
+    size_t (*extra_bytes)(int64_t n, int32_t dim);  // NULL: codes, scale and err are all of it
+    ssw_status (*build)(const void *X, int32_t dtype, int64_t n, int32_t dim, const Shadow &s, hipStream_t stream);
+    float *Shadow::*width_err;                      // a_r of the bounds the survivor pass reads first (launch_shadow_max)
     bool query_operand;
 };
-static const ShadowDesc SHADOW[3] = {
-    {q8_dim_supported, [](int64_t n, int32_t dim) { return (size_t)n * dim; }, [](int64_t n) { return n; }, launch_q8_build, false},
-    {q6_dim_supported, q6_code_bytes, packed_padded_rows, launch_q6_build, true},
-    {q5_dim_supported, q5_code_bytes, packed_padded_rows, launch_q5_build, true},  // the 6-bit query's words and operand
+// the two-stage shadow beside its coarse plane, s5 and a5: a4 and H (a word a row each) and the fine plane
+static size_t q41_extra_bytes(int64_t n, int32_t dim) {
+    return (size_t)packed_padded_rows(n) * (sizeof(float) + sizeof(int32_t)) + q41_fine_bytes(n, dim);
+}
+// ... and the buffers of a call on it: the first stage's list, its state words, the query's D
+static size_t q41_call_bytes(int32_t dim) {
+    return (size_t)COARSE_CAP * sizeof(uint32_t) + Q41_STATE_WORDS * sizeof(unsigned) + (size_t)dim * sizeof(int32_t);
+}
+#define SSW_PLAIN_BUILD(launch)                                                                                  \
+    [](const void *X, int32_t dtype, int64_t n, int32_t dim, const Shadow &s, hipStream_t stream) -> ssw_status { \
+        return launch(X, dtype, n, dim, s.codes, s.scale, s.err, stream);                                        \
+    }
+static const ShadowDesc SHADOW[4] = {
+    {q8_dim_supported, [](int64_t n, int32_t dim) { return (size_t)n * dim; }, [](int64_t n) { return n; }, nullptr,
+     SSW_PLAIN_BUILD(launch_q8_build), &Shadow::err, false},
+    {q6_dim_supported, q6_code_bytes, packed_padded_rows, nullptr, SSW_PLAIN_BUILD(launch_q6_build), &Shadow::err, true},
+    // (the 6-bit query's words and operand)
+    {q5_dim_supported, q5_code_bytes, packed_padded_rows, nullptr, SSW_PLAIN_BUILD(launch_q5_build), &Shadow::err, true},
+    // codes: the coarse plane; the first stage's width is a4's, the refine reads a5 and s5 of the rows it bounds
+    {q5_dim_supported, q41_coarse_bytes, packed_padded_rows, q41_extra_bytes,
+     [](const void *X, int32_t dtype, int64_t n, int32_t dim, const Shadow &s, hipStream_t stream) -> ssw_status {
+         return launch_q41_build(X, dtype, n, dim, s.codes, s.fine, s.scale, s.err, s.err4, stream);
+     },
+     &Shadow::err4, true},
 };
+#undef SSW_PLAIN_BUILD
 
-static int code_bits(ShadowKind kind) { return kind == SHADOW_Q8 ? 8 : kind == SHADOW_Q6 ? 6 : 5; }  // of launch_survivors_mq
+// of launch_survivors_mq (the two-stage shadow's own passes: prune41_stage1, prune41_refine)
+static int code_bits(ShadowKind kind) { return kind == SHADOW_Q8 ? 8 : kind == SHADOW_Q6 ? 6 : 5; }
 
 static bool prune_forced_off() {
     static const bool v = getenv("SSW_TOPK_FULL_SCAN") != nullptr;  // A/B: every top-k runs the full f32 scan
@@ -121,12 +162,14 @@ static bool prune_forced_off() {
 // on the int8 shadow, or at dim 768, which has none, on the plain batch) and ssw_tune_prune6_batch's the 6-bit batch's
 static int64_t prune_min_rows(const ssw_index *idx, ShadowKind kind, bool batch) {
     if (kind == SHADOW_Q5) return g_prune5_min_rows >= 0 ? g_prune5_min_rows : MIN_ROWS_Q5;  // ssw_tune_prune5's alone
+    if (kind == SHADOW_Q41) return g_prune41_min_rows >= 0 ? g_prune41_min_rows : MIN_ROWS_Q41;  // ssw_tune_prune41's alone
     const int64_t lab = kind == SHADOW_Q8 ? g_prune_min_rows : batch ? g_prune6_batch_min_rows : g_prune6_min_rows;
     return lab >= 0 ? lab : MIN_ROWS[kind][batch][idx->dim == 768][idx->dtype == SSW_DTYPE_F16];
 }
 
 static bool prune_eligible_on(const ssw_index *idx, ShadowKind kind, bool batch) {
-    return g_prune && (kind != SHADOW_Q6 || g_prune6) && (kind != SHADOW_Q5 || g_prune5) && !prune_forced_off() &&
+    return g_prune && (kind != SHADOW_Q6 || g_prune6) && (kind != SHADOW_Q5 || g_prune5) && (kind != SHADOW_Q41 || g_prune41) &&
+           !prune_forced_off() &&
            idx->owns_X && !idx->rows_escaped && idx->n >= prune_min_rows(idx, kind, batch) && idx->n_images > 0 &&
            SHADOW[kind].dim_ok(idx->dim);
 }
@@ -135,6 +178,11 @@ static bool prune_eligible_on(const ssw_index *idx, ShadowKind kind, bool batch)
 bool ssw::prune5_eligible(const ssw_index *idx) {
     return prune_eligible_on(idx, SHADOW_Q5, false) && idx->dtype == SSW_DTYPE_F32 && !idx->has_map;
 }
+// the two-stage shadow: the calls and indexes of the 5-bit shadow (its own switch and row count)
+bool ssw::prune41_eligible(const ssw_index *idx) {
+    return prune_eligible_on(idx, SHADOW_Q41, false) && idx->dtype == SSW_DTYPE_F32 && !idx->has_map;
+}
+int64_t ssw::prune41_coarse_cap() { return g_coarse_cap; }
 bool ssw::prune_eligible(const ssw_index *idx) { return prune_eligible_on(idx, SHADOW_Q8, false); }
 bool ssw::prune_batch_eligible(const ssw_index *idx) { return prune_eligible_on(idx, SHADOW_Q8, true); }
 bool ssw::prune6_eligible(const ssw_index *idx) { return prune_eligible_on(idx, SHADOW_Q6, false); }
@@ -188,14 +236,23 @@ ssw_status ssw::ensure_shadow(ssw_index *idx, ShadowKind kind, bool *ready) {
     if (s.refused) return SSW_OK;
     if (!s.codes) {
         const size_t codes = desc.code_bytes(idx->n, idx->dim), consts = (size_t)desc.const_rows(idx->n) * sizeof(float);
+        const bool two = desc.extra_bytes != nullptr;  // the two-stage shadow: its planes, and the buffers of a call on it
+        const size_t extra = two ? desc.extra_bytes(idx->n, idx->dim) + (p.coarse_rows ? 0 : q41_call_bytes(idx->dim)) : 0;
         bool fits = false;
-        SSW_TRY(shadow_fits(idx, codes + 2 * consts, &fits));
+        SSW_TRY(shadow_fits(idx, codes + 2 * consts + extra, &fits));
         if (!fits) {
             s.refused = true;
             return SSW_OK;
         }
-        if (hipMalloc((void **)&s.codes, codes) != hipSuccess || hipMalloc((void **)&s.scale, consts) != hipSuccess ||
-            hipMalloc((void **)&s.err, consts) != hipSuccess) {
+        bool got = hipMalloc((void **)&s.codes, codes) == hipSuccess && hipMalloc((void **)&s.scale, consts) == hipSuccess &&
+                   hipMalloc((void **)&s.err, consts) == hipSuccess;
+        if (got && two)
+            got = hipMalloc((void **)&s.err4, consts) == hipSuccess && hipMalloc((void **)&s.H, consts) == hipSuccess &&
+                  hipMalloc((void **)&s.fine, q41_fine_bytes(idx->n, idx->dim)) == hipSuccess &&
+                  (p.cstate || hipMalloc((void **)&p.cstate, Q41_STATE_WORDS * sizeof(unsigned)) == hipSuccess) &&
+                  (p.coarse_rows || hipMalloc((void **)&p.coarse_rows, (size_t)COARSE_CAP * sizeof(uint32_t)) == hipSuccess) &&
+                  (p.D41 || hipMalloc((void **)&p.D41, (size_t)idx->dim * sizeof(int32_t)) == hipSuccess);
+        if (!got) {  // (a call buffer that was had stays for the next attempt: each is under its own test)
             (void)hipGetLastError();
             s.free();
             s.refused = true;
@@ -211,8 +268,8 @@ ssw_status ssw::ensure_shadow(ssw_index *idx, ShadowKind kind, bool *ready) {
         SSW_HIP_TRY(hipMemsetAsync(p.planes6, 0, q6_plane_bytes(idx->dim), idx->stream));
     }
     if (!s.max) SSW_HIP_TRY(hipMalloc((void **)&s.max, SHADOW_MAX_WORDS * sizeof(unsigned)));
-    SSW_TRY(desc.build(idx->X, idx->dtype, idx->n, idx->dim, s.codes, s.scale, s.err, idx->stream));
-    SSW_TRY(launch_shadow_max(s.err, s.scale, idx->n, s.max, idx->device, idx->stream));
+    SSW_TRY(desc.build(idx->X, idx->dtype, idx->n, idx->dim, s, idx->stream));
+    SSW_TRY(launch_shadow_max(s.*desc.width_err, s.scale, idx->n, s.max, idx->device, idx->stream));
     s.stale = false;
     *ready = true;
     return SSW_OK;
@@ -224,7 +281,11 @@ ssw_status ssw::ensure_shadow(ssw_index *idx, ShadowKind kind, bool *ready) {
 ssw_status ssw::prune_bounds(ssw_index *idx, ShadowKind kind, const float *q_dev, int64_t *dbg_I) {
     PruneState &p = idx->prune;
     const Shadow &s = p.sh[kind];
-    if (kind == SHADOW_Q5) {
+    if (kind == SHADOW_Q41) {  // the first stage: lb4 into the buffer, H beside the shadow (dbg_I: not this scan's)
+        SSW_TRY(launch_q41_query(q_dev, idx->dim, p.state6, p.planes6, p.q_last, p.D41, p.cstate, idx->stream));
+        SSW_TRY(launch_q4_bounds(s.codes, s.scale, s.err4, p.planes6, p.state6, idx->scores, s.H, idx->n, idx->dim, idx->device,
+                                 idx->stream));
+    } else if (kind == SHADOW_Q5) {
         SSW_TRY(launch_q6_query(q_dev, idx->dim, p.state6, p.planes6, p.q_last, idx->stream));
         SSW_TRY(launch_q5_bounds(s.codes, s.scale, s.err, p.planes6, p.state6, idx->scores, idx->n, idx->dim, dbg_I,
                                  idx->device, idx->stream));
@@ -251,7 +312,12 @@ ssw_status ssw::prune_survivors(ssw_index *idx, ShadowKind kind, int32_t k, int6
     const unsigned seq = next_seq(p.seq);
     int32_t *host_dev = nullptr;
     SSW_HIP_TRY(hipHostGetDevicePointer((void **)&host_dev, p.host, 0));
-    if (kind != SHADOW_Q8) {
+    if (kind == SHADOW_Q41) {
+        // both stages on the device, no wait between them: the first stage's survivors, then their 5-bit bounds
+        SSW_TRY(prune41_stage1(idx, k, 0));
+        SSW_TRY(prune41_refine(idx, k, nullptr, cap, nullptr, nullptr));
+        SSW_TRY(launch_prune_publish_q41(p.state6, p.cstate, cap, host_dev, seq, idx->stream));
+    } else if (kind != SHADOW_Q8) {
         SSW_TRY(launch_survivors_mq(idx->scores, s.err, s.scale, s.max, idx->n, idx->dim, code_bits(kind), idx->ws.out_keys,
                                     idx->ws.out_count, k, p.state6, p.surv_rows, cap, idx->device, idx->stream));
         SSW_TRY(launch_prune_publish_mq(p.state6, 1, cap, host_dev, seq, idx->stream));
@@ -262,7 +328,32 @@ ssw_status ssw::prune_survivors(ssw_index *idx, ShadowKind kind, int32_t k, int6
     if (sleep_ev_or_null) SSW_HIP_TRY(hipEventSynchronize(sleep_ev_or_null));
     SSW_TRY(wait_host_seq(idx->stream, reinterpret_cast<const unsigned *>(p.host), seq));
     *out_m = __atomic_load_n(p.host + 1, __ATOMIC_ACQUIRE);
+    if (kind == SHADOW_Q41) {
+        p.coarse_last = __atomic_load_n(p.host + 2, __ATOMIC_ACQUIRE);
+        p.dense_refines += __atomic_load_n(p.host + 3, __ATOMIC_ACQUIRE) != 0 ? 1 : 0;
+        ++p.two_stage_calls;
+    }
     return SSW_OK;
+}
+
+// The two device steps of the two-stage shadow's survivors, which the lab hooks drive one at a time as well; lb4 of the
+// kept query is in the buffer and H beside the shadow (prune_bounds).  Stage 1: the rows whose coarse upper bound reaches
+// the k-th key, into the 32-bit list.  blocks: 0 = the pass's own grid (lab hook: one block walks many stages).
+ssw_status ssw::prune41_stage1(ssw_index *idx, int32_t k, int blocks) {
+    PruneState &p = idx->prune;
+    const Shadow &s = p.sh[SHADOW_Q41];
+    return launch_survivors_q4(idx->scores, s.err4, s.scale, s.max, idx->n, idx->dim, idx->ws.out_keys, idx->ws.out_count, k,
+                               p.state6, p.cstate, p.coarse_rows, COARSE_CAP, blocks, idx->device, idx->stream);
+}
+// Refine: the 5-bit bound of the listed rows (the first stage's list, or the lab hook's), or of every row when the list
+// holds more than the coarse cap; its survivors into surv_rows, counted in state6[0]
+ssw_status ssw::prune41_refine(ssw_index *idx, int32_t k, const uint32_t *list_or_null, int64_t cap, float *dbg_lb5,
+                               int32_t *dbg_B) {
+    PruneState &p = idx->prune;
+    const Shadow &s = p.sh[SHADOW_Q41];
+    return launch_q41_refine(s.H, s.fine, s.scale, s.err, p.D41, idx->ws.out_keys, k, p.state6, p.cstate,
+                             list_or_null ? list_or_null : p.coarse_rows, std::min(g_coarse_cap, COARSE_CAP), idx->n, idx->dim,
+                             p.surv_rows, cap, dbg_lb5, dbg_B, idx->device, idx->stream);
 }
 
 // The exact threshold of the 5-bit path, between the threshold selection of kc keys and the survivor pass, all on the
@@ -290,13 +381,21 @@ ssw_status ssw::prune_exact_threshold(ssw_index *idx, int32_t k, int32_t kc) {
 // refusal for memory falls through to the 6-bit and then the int8 shadow).  Its bounds are twice as wide, so its
 // threshold selection runs for kc = min(SSW_MAX_TOPK, max(1024, 4 k)) keys and prune_exact_threshold raises the k-th key
 // to the k-th exact score of those candidates before the survivor pass, on the device; everything after is the same.
+// Ahead of it, where prune41_eligible says so, comes the two-stage form of the same codes (and then no packed 5-bit shadow
+// is built; a refusal for memory falls through to it): the scan bounds every row on the 4-bit plane, the selection and
+// the exact threshold run as for the 5-bit shadow, and prune_survivors enqueues both survivor stages (prune41_stage1,
+// prune41_refine) ahead of the one host wait; what it publishes are the rows that survive the 5-bit bound.
 ssw_status ssw::scan_for_topk(ssw_index *idx, const float *q_dev, int32_t k, bool *out_candidates) {
     *out_candidates = false;
     bool ready = false;
-    ShadowKind kind = SHADOW_Q5;
+    ShadowKind kind = SHADOW_Q41;
     const bool k_ok = k >= 1 && k <= SSW_MAX_TOPK && (idx->ws.xchg.msg_out == nullptr || k <= idx->ws.xchg.k_max);
     const int32_t kc = std::min<int32_t>(SSW_MAX_TOPK, std::max<int32_t>(1024, 4 * std::min<int32_t>(k, SSW_MAX_TOPK)));
-    if (k_ok && prune5_eligible(idx)) SSW_TRY(ensure_shadow(idx, kind, &ready));
+    if (k_ok && prune41_eligible(idx)) SSW_TRY(ensure_shadow(idx, kind, &ready));
+    if (k_ok && !ready && prune5_eligible(idx)) {
+        kind = SHADOW_Q5;
+        SSW_TRY(ensure_shadow(idx, kind, &ready));
+    }
     if (k_ok && !ready && prune6_eligible(idx)) {
         kind = SHADOW_Q6;
         SSW_TRY(ensure_shadow(idx, kind, &ready));
@@ -312,12 +411,15 @@ ssw_status ssw::scan_for_topk(ssw_index *idx, const float *q_dev, int32_t k, boo
         SSW_TRY(prune_bounds(idx, kind, q_dev, nullptr));
         SSW_HIP_TRY(hipEventRecord(p.ev, idx->stream));
         // threshold: the ordinary selection over the lower bounds, with the exclusions, without a message or host result
-        SSW_TRY(do_select(idx, idx->scores, kind == SHADOW_Q5 ? kc : k, SelectDest{nullptr, 0u, false}, idx->stream));
+        const bool exact_t = kind == SHADOW_Q5 || kind == SHADOW_Q41;  // the wide bounds: kc keys, the exact threshold
+        SSW_TRY(do_select(idx, idx->scores, exact_t ? kc : k, SelectDest{nullptr, 0u, false}, idx->stream));
         // (ahead of the host wait; the survivor pass reads the selection's keys and count, not these words)
         if (!idx->has_map) SSW_TRY(select_reset_state(idx->ws, idx->stream));
-        if (kind == SHADOW_Q5) SSW_TRY(prune_exact_threshold(idx, k, kc));
+        if (exact_t) SSW_TRY(prune_exact_threshold(idx, k, kc));
         int32_t m = -1;
-        SSW_TRY(prune_survivors(idx, kind, k, SURV_CAP, p.ev, &m));  // sleep through the shadow scan, spin on the rest
+        // (the two-stage path's final survivors are held to ssw_tune_surv_cap's value in the lab build: SURV_CAP unless set)
+        const int64_t cap = kind == SHADOW_Q41 ? std::min<int64_t>(SURV_CAP, g_surv_cap_dev) : SURV_CAP;
+        SSW_TRY(prune_survivors(idx, kind, k, cap, p.ev, &m));  // sleep through the shadow scan, spin on the rest
         p.last = m;
         ++p.queries;
         if (m < 0) {
@@ -482,17 +584,27 @@ ssw_status ssw_index_prune_stats(ssw_index *idx, int64_t *out6) {
     const PruneState &p = idx->prune;
     // the state of the shadow single queries use: the 6-bit one where it applies and was not refused
     // (a dim-768 index has no other: there a refusal is the 6-bit shadow's)
-    const Shadow &q8 = p.sh[SHADOW_Q8], &q6 = p.sh[SHADOW_Q6], &q5 = p.sh[SHADOW_Q5];
+    const Shadow &q8 = p.sh[SHADOW_Q8], &q6 = p.sh[SHADOW_Q6], &q5 = p.sh[SHADOW_Q5], &q41 = p.sh[SHADOW_Q41];
     const bool six = prune6_eligible(idx) && (!q6.refused || !q8_dim_supported(idx->dim));
     const bool five = prune5_eligible(idx) && !q5.refused;  // ... and before it the 5-bit one, on the same terms
-    const Shadow &s = five ? q5 : six ? q6 : q8;
+    const bool two = prune41_eligible(idx) && !q41.refused;  // ... and before that the two-stage one
+    const Shadow &s = two ? q41 : five ? q5 : six ? q6 : q8;
     out6[0] = s.codes ? (s.stale ? 2 : 1) : (s.refused ? 3 : 0);
-    out6[1] = prune_eligible(idx) || six || five ? 1 : 0;
+    out6[1] = prune_eligible(idx) || six || five || two ? 1 : 0;
     out6[2] = p.last;
     out6[3] = p.queries;
     out6[4] = p.fallbacks;
     out6[5] = (q8.codes ? idx->n * (idx->dim + 8) : 0) + (q6.codes ? packed_padded_rows(idx->n) * (idx->dim * 3 / 4 + 8) : 0) +
-              (q5.codes ? packed_padded_rows(idx->n) * (idx->dim * 5 / 8 + 8) : 0);
+              (q5.codes ? packed_padded_rows(idx->n) * (idx->dim * 5 / 8 + 8) : 0) +
+              (q41.codes ? packed_padded_rows(idx->n) * (idx->dim * 5 / 8 + 16) : 0);  // both planes, s5, a5, a4, H
+    return SSW_OK;
+}
+
+ssw_status ssw_index_prune_coarse_stats(ssw_index *idx, int64_t *out3) {
+    SSW_REQUIRE(idx != nullptr && out3 != nullptr, "NULL argument");
+    out3[0] = idx->prune.coarse_last;
+    out3[1] = idx->prune.dense_refines;
+    out3[2] = idx->prune.two_stage_calls;
     return SSW_OK;
 }
 
@@ -530,6 +642,18 @@ ssw_status ssw_tune_prune6(int32_t enable, int64_t min_rows) {
 ssw_status ssw_tune_prune5(int32_t enable, int64_t min_rows) {
     g_prune5 = enable != 0;
     g_prune5_min_rows = min_rows < 0 ? -1 : min_rows;  // < 0: MIN_ROWS_Q5 again
+    return SSW_OK;
+}
+
+ssw_status ssw_tune_prune41(int32_t enable, int64_t min_rows, int64_t coarse_cap) {
+    g_prune41 = enable != 0;
+    g_prune41_min_rows = min_rows < 0 ? -1 : min_rows;  // < 0: MIN_ROWS_Q41 again
+    g_coarse_cap = coarse_cap >= 0 && coarse_cap <= COARSE_CAP ? coarse_cap : COARSE_CAP;
+    return SSW_OK;
+}
+
+ssw_status ssw_tune_prune41_scan(int32_t blocks_per_cu, int32_t tiles) {
+    tune_tile_scan(SCAN_Q4, blocks_per_cu, tiles);
     return SSW_OK;
 }
 

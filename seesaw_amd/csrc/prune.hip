@@ -51,9 +51,11 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 // elements to lanes and slots) -> their codes, slot i in byte i % 4 of packed[i / 4], and the row's s_r and a_r, which
 // lane 0 writes.  The codes and s_r do not depend on the assignment; a_r's double sums are taken in its order.
 // LEVELS: the largest |code|, 127 for the int8 shadow, 31 for the packed 6-bit one (k_q6_build).
+// s_out / ok_out (k_q41_build only, else NULL): the row's s_r and whether the row can be bounded, in every lane.
 template <int C, int LEVELS = 127>
 __device__ __forceinline__ void q8_quantise_row(const float (&x)[4 * C], int64_t r, int lane, unsigned (&packed)[C],
-                                                float *__restrict__ scale, float *__restrict__ err) {
+                                                float *__restrict__ scale, float *__restrict__ err,
+                                                float *s_out = nullptr, bool *ok_out = nullptr) {
     constexpr int dim = 256 * C;
     constexpr float LV = (float)LEVELS;
     float m = 0.0f;
@@ -67,6 +69,8 @@ __device__ __forceinline__ void q8_quantise_row(const float (&x)[4 * C], int64_t
     for (int off = 1; off < 64; off <<= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
     const bool ok = __all(finite) && (m == 0.0f || (m >= MIN_ABS && m <= MAX_ABS));
     const float s = (ok && m > 0.0f) ? m / LV : 0.0f;
+    if (s_out) *s_out = s;
+    if (ok_out) *ok_out = ok;
     double e2 = 0.0, x2 = 0.0, c2 = 0.0;
 #pragma unroll
     for (int c = 0; c < C; ++c) packed[c] = 0u;
@@ -397,6 +401,9 @@ __device__ __forceinline__ double surv_ub(double l, double w) {
 constexpr double WMAX_INFLATE = 1.0 + 0x1p-30;  // on w_max: a different fma contraction of the two ub's cannot matter
 constexpr int SURV_UNROLL = 4;                  // 16-byte loads of lb a lane keeps in flight
 constexpr int SURV_STAGE = 1024;                // survivors a block collects in LDS before it takes its place in the list
+// FLUSH (survivor_pass): a block adds at most 4 waves x SURV_UNROLL steps x 256 rows between two looks at its stage, and
+// the last n % 4 rows after the last look
+constexpr int SURV_FLUSH_STAGE = SURV_STAGE + 4 * SURV_UNROLL * 256 + 4;
 
 // The survivor pass of both kernels below: the rows with !(ub < T), their number added to *counter and the first cap of
 // them listed in rows (any order).  MQ: the width is e wA + s wS ((**) / (***)), else e wA.
@@ -413,16 +420,21 @@ constexpr int SURV_STAGE = 1024;                // survivors a block collects in
 // no longer fits the stage goes to the global counter directly, as before, and so does every wave-step of the block
 // after it (once a claim has failed the stage is closed).  Count and set are the same; only the order of the list,
 // which was the atomics' already, differs.
-template <bool MQ>
+// FLUSH (the first stage of the two-stage path, millions of survivors: a closed stage would leave most of the pass to
+// atomics on the one global counter): the block looks at its stage before every round of SURV_UNROLL steps, all waves
+// together, and once more than SURV_STAGE rows are staged it claims their place in the list with ONE global atomic,
+// writes them out and starts the stage again.  The stage has room for a whole round beyond that mark, so no claim fails
+// and nothing goes to the global counter directly.  Rows are 32-bit (Row = uint32_t), the list's type.
+template <bool MQ, bool FLUSH = false, class Row = int64_t>
 __device__ __forceinline__ void survivor_pass(const float *__restrict__ lb, const float *__restrict__ err,
                                               const float *__restrict__ scale, int64_t n, float T, double wA, double wS,
-                                              double w_max, unsigned *__restrict__ counter, int64_t *__restrict__ rows,
+                                              double w_max, unsigned *__restrict__ counter, Row *__restrict__ rows,
                                               int64_t cap) {
     const int lane = threadIdx.x & 63;
     const uint64_t below = (1ull << lane) - 1ull;
     const int64_t stride = (int64_t)gridDim.x * 1024;
     const double Td = (double)T;
-    __shared__ int64_t stage[SURV_STAGE];
+    __shared__ Row stage[FLUSH ? SURV_FLUSH_STAGE : SURV_STAGE];
     __shared__ unsigned staged, first_failed, stage_base;
     if (threadIdx.x == 0) staged = 0u, first_failed = 0xffffffffu;
     __syncthreads();
@@ -472,10 +484,12 @@ __device__ __forceinline__ void survivor_pass(const float *__restrict__ lb, cons
         int direct = 0;
         if (lane == 0) {
             slot = atomicAdd(&staged, total);
-            if (slot + total > (unsigned)SURV_STAGE) {
-                atomicMin(&first_failed, slot);
-                slot = atomicAdd(counter, total);
-                direct = 1;
+            if constexpr (!FLUSH) {
+                if (slot + total > (unsigned)SURV_STAGE) {
+                    atomicMin(&first_failed, slot);
+                    slot = atomicAdd(counter, total);
+                    direct = 1;
+                }
             }
         }
         slot = __shfl(slot, 0, 64);
@@ -484,8 +498,8 @@ __device__ __forceinline__ void survivor_pass(const float *__restrict__ lb, cons
         for (int t = 0; t < 4; ++t) {
             const int64_t at = (int64_t)slot + __popcll(ballot[t] & below);
             if (keep[t]) {
-                if (!direct) stage[at] = r0 + t;
-                else if (at < cap) rows[at] = r0 + t;
+                if (!direct) stage[at] = (Row)(r0 + t);
+                else if (at < cap) rows[at] = (Row)(r0 + t);
             }
             slot += (unsigned)__popcll(ballot[t]);
         }
@@ -493,7 +507,30 @@ __device__ __forceinline__ void survivor_pass(const float *__restrict__ lb, cons
     // the whole groups of four rows: a wave takes 256 rows a step, SURV_UNROLL steps a stride apart at a time, their loads
     // requested together (wave-uniform loop; no scalar path beside the loads, which would make the waits conservative)
     const int64_t n4 = n & ~(int64_t)3;
-    for (int64_t base0 = (int64_t)blockIdx.x * 1024 + (threadIdx.x & ~63u) * 4; base0 < n4; base0 += SURV_UNROLL * stride) {
+    // the staged rows into the list behind one claim on the global counter (whole block; FLUSH: the stage starts again)
+    auto flush = [&](unsigned count) {
+        if (threadIdx.x == 0) stage_base = atomicAdd(counter, count);
+        __syncthreads();
+        for (unsigned i = threadIdx.x; i < count; i += 256) {
+            const int64_t at = (int64_t)stage_base + i;
+            if (at < cap) rows[at] = stage[i];
+        }
+        if constexpr (FLUSH) {
+            __syncthreads();
+            if (threadIdx.x == 0) staged = 0u;
+            __syncthreads();
+        }
+    };
+    // FLUSH: the loop is the block's (wave 0's base decides), so that every wave reaches the barriers; a wave past the
+    // rows has r0 >= n4 throughout and does nothing
+    for (int64_t base0 = (int64_t)blockIdx.x * 1024 + (threadIdx.x & ~63u) * 4;
+         base0 - (FLUSH ? (int64_t)((threadIdx.x & ~63u) * 4) : 0) < n4; base0 += SURV_UNROLL * stride) {
+        if constexpr (FLUSH) {
+            __syncthreads();
+            const unsigned have = staged;  // (block-uniform: read between two barriers)
+            __syncthreads();
+            if (have > (unsigned)SURV_STAGE) flush(have);
+        }
         float4 lv[SURV_UNROLL];
 #pragma unroll
         for (int u = 0; u < SURV_UNROLL; ++u) {
@@ -519,12 +556,7 @@ __device__ __forceinline__ void survivor_pass(const float *__restrict__ lb, cons
     __syncthreads();
     const unsigned mine = min(staged, first_failed);  // <= SURV_STAGE: where the first claim that did not fit began
     if (mine == 0u) return;
-    if (threadIdx.x == 0) stage_base = atomicAdd(counter, mine);
-    __syncthreads();
-    for (unsigned i = threadIdx.x; i < mine; i += 256) {
-        const int64_t at = (int64_t)stage_base + i;
-        if (at < cap) rows[at] = stage[i];
-    }
+    flush(mine);
 }
 
 // the rows whose upper bound reaches T = the k-th key of the threshold selection over the lower bounds.
@@ -1072,6 +1104,8 @@ struct DebugPlanes {
 struct OneQuery {
     static constexpr int PLANES = 1;
     static constexpr bool ONE_TEST = true;  // four lanes of a wave store: one test around everything (tile_scan)
+    static constexpr bool STORE_H = false;  // (OneQueryH below)
+    __device__ __forceinline__ double adjust(double I) const { return I; }
     const unsigned *state;                  // the kernel's arguments: the query's state words (a slot's, MQ_WORDS),
     float *scores;
     DebugSum dbg;
@@ -1095,6 +1129,8 @@ template <class Debug>
 struct Chunk {
     static constexpr int PLANES = 2;
     static constexpr bool ONE_TEST = false;  // most lanes store: every store on its own test
+    static constexpr bool STORE_H = false;
+    __device__ __forceinline__ double adjust(double I) const { return I; }
     const unsigned *mq;                      // the kernel's arguments
     int w;
     float *side;
@@ -1120,7 +1156,8 @@ struct Chunk {
 // path.  The last n % (16 T) rows are one clamped group of their own, after the loop, for one wave: nothing is stored
 // for a row >= n.  Result map of the 16x16 product: lane l holds column l & 15 and rows 4 (l >> 4) .. + 3 of the tile, so
 // it loads those rows' s and a with one 16-byte load each and writes its four bounds with one 16-byte store.
-// Codes: the shadow's layout and unpack (Q8Rows, Q6Tiles, Q5Tiles); Out: what the 16 columns are (OneQuery, Chunk).
+// Codes: the shadow's layout and unpack (Q8Rows, Q6Tiles, Q5Tiles; Q4Tiles further down); Out: what the 16 columns are
+// (OneQuery, Chunk; OneQueryH further down: Out::adjust turns the integer sum into the bound's, Out::STORE_H keeps it).
 // DEBUG (lab hooks only): the integer sums go to out.dbg as well.
 template <template <int> class CodesOf, class Out, int C, int T, bool DEBUG>
 __device__ __forceinline__ void tile_scan(const typename CodesOf<C>::Elem *__restrict__ codes, const float *__restrict__ scale,
@@ -1181,7 +1218,7 @@ __device__ __forceinline__ void tile_scan(const typename CodesOf<C>::Elem *__res
             for (int i = 0; i < 4; ++i) {
                 out.sums(acc, i, &hi[i], &lo[i]);
                 I[i] = (double)hi[i] * 256.0 + (double)lo[i];  // exact: |I| < 2^39 at dim 1024
-                lb[i] = certified_lb(I[i], d.s[t][i], d.a[t][i], sb);
+                lb[i] = certified_lb(out.adjust(I[i]), d.s[t][i], d.a[t][i], sb);
             }
             const int r0 = t * 16 + 4 * quad;  // of the lane's four rows in the group
             // Out::ONE_TEST: one test of the lane stands around all its stores; else each store has it beside the row's
@@ -1192,6 +1229,10 @@ __device__ __forceinline__ void tile_scan(const typename CodesOf<C>::Elem *__res
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
                         if (each && r0 + i < rows) (dst + g * G)[r0 + i] = lb[i];
+                }
+                if constexpr (Out::STORE_H) {  // the lane's four H beside its four bounds (the array is padded to whole tiles)
+                    const i32x4 h4 = {hi[0] * 256 + lo[0], hi[1] * 256 + lo[1], hi[2] * 256 + lo[2], hi[3] * 256 + lo[3]};
+                    if (rows == G || r0 < rows) *reinterpret_cast<i32x4 *>(out.H + g * G + r0) = h4;
                 }
                 if constexpr (DEBUG) {
 #pragma unroll
@@ -1272,6 +1313,295 @@ __global__ __launch_bounds__(256) void k_q5_bounds(const u32x4 *__restrict__ cod
     tile_scan<Q5Tiles, OneQuery, C, T, DEBUG>(codes, scale, err, planes, n, {st, scores, {dbg_I}});
 }
 
+// ---- the two-stage 4 + 1-bit shadow of f32 rows ("Two-stage 4 + 1-bit shadow") ----------------------
+// Codes, s5 and a5 are q8_quantise_row<C, 15>'s, the 5-bit shadow's.  Write u = c + 16 in [1, 31], h = u >> 1 in [0, 15],
+// b = u & 1, so c = 2 h + b - 16.  With D_i = 256 d_hi,i + d_lo,i and the query state of k_q6_query:
+//
+// COARSE bound (first stage, every row, the 4-bit plane alone):
+//     x = s5 (2 h - 15.5) + r4,     a4_r >= ||r4|| (+ a5's rounding terms; summed in double with SAFETY as a5 is)
+//     | S_r - (s5_r / 2) t2 J_r | <= a4_r Q + s5_r 15.5 sqrt(dim) e =: w4
+//     J_r = sum_i (4 h_ri - 31) D_i = 4 H_r - 31 sum D,     H_r = sum_i h_ri D_i = 256 H_hi + H_lo
+// The operand bytes are the nibbles h themselves (0 .. 15); |H| <= 15 * 1024 * 32639 < 2^31 is one int32 a row, which the
+// scan keeps; J is formed exactly in double and goes through certified_lb with FACTOR 0.5 and the code norm 15.5 sqrt(dim).
+// Zero rows, rows with a non-finite element and unboundable queries keep the builders' conventions (a = +inf, lb = -inf;
+// the flagged query takes the full scan).
+//
+// FINE bound (second stage, the first stage's survivors only): B_r = sum_i b_ri D_i (|B| < 2^25) and
+//     I_r = sum_i 8 c_ri D_i = 8 (2 H_r + B_r - 16 sum D)
+// is k_q5_bounds' integer sum, exactly, so certified_lb(I_r, s5_r, a5_r, slot_bound(st, 0.125, q5_code_norm(dim))) is that
+// kernel's lower bound bit for bit, and everything downstream of it is the 5-bit path's.
+// Layout: q4_nibble (ssw_common.h) for the coarse plane, a tile of 16 rows = NL = 2 C wave loads of 1 KiB; the fine plane
+// row-major, dim / 32 words a row.
+constexpr int Q4_BLOCKS_PER_CU = 1;
+constexpr int q4_default_tiles(int C) { return C == 2 ? 2 : 1; }  // 8 KiB a request of a wave at both dims
+
+// 15.5 sqrt(dim), rounded up
+__host__ __device__ constexpr double q4_code_norm(int dim) { return dim == 512 ? 350.7249635 : 496.0; }
+
+// one wave per row (grid-strided), as k_q5_build: the codes and s5, a5 from q8_quantise_row<C, 15> with that kernel's
+// assignment of elements to lanes (bit-identical constants); a4 from the same sums with 2 h - 15.5 in the code's place;
+// every lane ORs its nibbles (q4_nibble) and its fifth bits into the row's words in LDS, which go to their places.
+template <int C>
+__global__ __launch_bounds__(256) void k_q41_build(const float *__restrict__ X, int64_t n, unsigned char *__restrict__ coarse,
+                                                   unsigned *__restrict__ fine, float *__restrict__ scale,
+                                                   float *__restrict__ err, float *__restrict__ err4) {
+    constexpr int dim = 256 * C, KS = dim / 64, WPL = 2 * KS, FW = dim / 32;  // words a lane owns; fine words a row
+    constexpr size_t TILE_BYTES = (size_t)16 * dim / 2;
+    __shared__ unsigned packed_row[4][4 * WPL + FW];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < n; r += (int64_t)gridDim.x * 4) {
+        const float4 *src = reinterpret_cast<const float4 *>(X + r * dim) + lane * C;
+        float x[4 * C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const float4 v = src[c];
+            x[4 * c] = v.x, x[4 * c + 1] = v.y, x[4 * c + 2] = v.z, x[4 * c + 3] = v.w;
+        }
+        unsigned packed[C];
+        float s = 0.0f;
+        bool ok = false;
+        q8_quantise_row<C, 15>(x, r, lane, packed, scale, err, &s, &ok);
+        __builtin_amdgcn_wave_barrier();  // the previous row's reads of the words are issued (LDS is in order per wave)
+        for (int w = lane; w < 4 * WPL + FW; w += 64) packed_row[wave][w] = 0u;
+        __builtin_amdgcn_wave_barrier();
+        double e2 = 0.0, x2 = 0.0, c2 = 0.0;
+#pragma unroll
+        for (int t = 0; t < 4 * C; ++t) {
+            const int ci = (int)(int8_t)(packed[t >> 2] >> (8 * (t & 3)));
+            const unsigned uu = (unsigned)(ci + 16), h = uu >> 1, b = uu & 1u;
+            const int i = 4 * C * lane + t;
+            int u, g, j, word, byte, shift;
+            q6_slot(i, &u, &g, &j);
+            q4_nibble(u, j, &word, &byte, &shift);
+            atomicOr(&packed_row[wave][g * WPL + word], h << (8 * byte + shift));
+            atomicOr(&packed_row[wave][4 * WPL + (i >> 5)], b << (i & 31));
+            const double mid = 2.0 * (double)h - 15.5;  // s * mid is exact in double; so is its difference to x
+            const double d = (double)x[t] - (double)s * mid;
+            e2 += d * d;
+            if (ok) x2 += (double)x[t] * (double)x[t];
+            c2 += mid * mid;
+        }
+        e2 = wave_sum_d(e2);
+        x2 = wave_sum_d(x2);
+        c2 = wave_sum_d(c2);
+        if (lane == 0) {
+            const double g = (double)dim * 0x1p-24 / (1.0 - (double)dim * 0x1p-24);
+            const double a = SAFETY * (sqrt(e2) + g * sqrt(x2) + g * (double)s * sqrt(c2));
+            err4[r] = ok ? __double2float_ru(a) : INFINITY;
+        }
+        __builtin_amdgcn_wave_barrier();
+        unsigned char *tile = coarse + (size_t)(r >> 4) * TILE_BYTES;
+        for (int w = lane; w < 4 * WPL; w += 64)
+            *reinterpret_cast<unsigned *>(tile + q6_word_offset(16 * (w / WPL) + (int)(r & 15), w % WPL)) = packed_row[wave][w];
+        if (lane < FW) fine[r * FW + lane] = packed_row[wave][4 * WPL + lane];
+    }
+}
+
+// k_q6_query, then: the sums of the two code planes as integers into st[6], st[7], D in natural order, and the first
+// stage's counter and dense flag reset
+__global__ __launch_bounds__(256) void k_q41_query(const float *__restrict__ q, int dim, unsigned *__restrict__ st,
+                                                   int8_t *__restrict__ planes, float *__restrict__ q_keep,
+                                                   int32_t *__restrict__ D, unsigned *__restrict__ cstate) {
+    auto code_at = [&](int i, int p) -> int8_t * {
+        int u, g, j;
+        q6_slot(i, &u, &g, &j);
+        return planes + ((size_t)(u * 64 + g * 16 + p) * 16 + j);
+    };
+    mq_quantise_query(q, dim, q_keep, st, code_at);
+    __syncthreads();  // (each thread reads back the codes it wrote itself: the same i)
+    __shared__ int sums[2][4];
+    int sh = 0, sl = 0;
+    for (int i = threadIdx.x; i < dim; i += 256) {
+        const int hi = *code_at(i, 0), lo = *code_at(i, 1);
+        D[i] = 256 * hi + lo;
+        sh += hi, sl += lo;
+    }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) sh += __shfl_xor(sh, off, 64), sl += __shfl_xor(sl, off, 64);
+    if ((threadIdx.x & 63) == 0) sums[0][threadIdx.x >> 6] = sh, sums[1][threadIdx.x >> 6] = sl;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        st[6] = (unsigned)(sums[0][0] + sums[0][1] + sums[0][2] + sums[0][3]);
+        st[7] = (unsigned)(sums[1][0] + sums[1][1] + sums[1][2] + sums[1][3]);
+        for (int i = 0; i < Q41_STATE_WORDS; ++i) cstate[i] = 0u;
+    }
+}
+
+// Codes policy of tile_scan: the coarse plane.  Unpack, per two words = 16 nibbles = one k-step of a lane: two v_and_b32
+// with 0x0f0f0f0f and two shift-and-mask give the four operand words; no sign, no offset (the epilogue has it).
+template <int C>
+struct Q4Tiles : PackedTiles<2 * C> {
+    static_assert(C == 2 || C == 4, "dims 512 and 1024");
+    static constexpr int dim = 256 * C, KS = dim / 64, NL = 2 * C;
+    static constexpr double FACTOR = 0.5;  // on t2, exact: the sums are of 4 h - 31
+    static constexpr double CODE_NORM = q4_code_norm(dim);
+    template <int PLANES>
+    __device__ static __forceinline__ void products(const u32x4 (&c)[NL], const i32x4 (&q)[KS][PLANES], i32x4 (&acc)[PLANES]) {
+        unsigned w[4 * NL];
+        PackedTiles<NL>::words(c, w);
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const unsigned w0 = w[2 * ks], w1 = w[2 * ks + 1];
+            const i32x4 a = {(int)(w0 & 0x0f0f0f0fu), (int)((w0 >> 4) & 0x0f0f0f0fu), (int)(w1 & 0x0f0f0f0fu),
+                             (int)((w1 >> 4) & 0x0f0f0f0fu)};
+            mq_products(a, q[ks], acc);
+        }
+    }
+};
+
+// Out policy: OneQuery on the coarse plane.  The integer sum of a row is H; the bound takes J = 4 H - 31 sum D (`off`,
+// exact in double), and the lane stores its four H beside its four bounds with one 16-byte store.
+struct OneQueryH : OneQuery {
+    static constexpr bool STORE_H = true;
+    int32_t *H;
+    double off;
+    __device__ __forceinline__ double adjust(double I) const { return 4.0 * I - off; }
+};
+
+// lb4 of every row into scores[r] and H_r into H[r], on the coarse plane
+template <int C, int T, bool DEBUG>
+__global__ __launch_bounds__(256) void k_q4_bounds(const u32x4 *__restrict__ codes, const float *__restrict__ scale,
+                                                   const float *__restrict__ err4, const u32x4 *__restrict__ planes,
+                                                   const unsigned *__restrict__ st, float *__restrict__ scores,
+                                                   int32_t *__restrict__ H, int64_t n) {
+    const double off = 31.0 * ((double)(int)st[6] * 256.0 + (double)(int)st[7]);
+    tile_scan<Q4Tiles, OneQueryH, C, T, DEBUG>(codes, scale, err4, planes, n, OneQueryH{{st, scores, {nullptr}}, H, off});
+}
+
+// the first stage's survivors: k_survivors_mq's pass over the coarse bounds with the coarse width, into the 32-bit list
+// behind cstate[0], a block's stage flushed and used again (survivor_pass, FLUSH)
+__global__ __launch_bounds__(256) void k_survivors_q4(const float *__restrict__ lb, const float *__restrict__ err4,
+                                                      const float *__restrict__ scale, const unsigned *__restrict__ mx,
+                                                      int64_t n, double code_norm, const uint64_t *__restrict__ keys,
+                                                      const int32_t *__restrict__ sel_count, int32_t k,
+                                                      unsigned *__restrict__ st, unsigned *__restrict__ cstate,
+                                                      uint32_t *__restrict__ rows, int64_t cap) {
+    if (sel_count[0] < k || sel_count[1] != 0) {
+        if (threadIdx.x == 0) st[5] = 1u;  // every block writes the same word
+        return;
+    }
+    if (st[2] != 0u) return;
+    const float T = ord_to_f32((uint32_t)(keys[k - 1] >> 32));
+    const SlotBound b = slot_bound(st, 1.0, code_norm);
+    const double w_max = ((double)__uint_as_float(mx[0]) * b.wQ + (double)__uint_as_float(mx[1]) * b.wE) * WMAX_INFLATE;
+    survivor_pass<true, true, uint32_t>(lb, err4, scale, n, T, b.wQ, b.wE, w_max, &cstate[0], rows, cap);
+}
+
+constexpr int REFINE_UNROLL = 4;  // rows a group of lanes has in flight
+
+// The second stage.  A group of LPR = dim / 32 lanes takes a row: lane j of the group holds D of the row's fine word j in
+// 32 registers for the whole launch, so a row costs one 4-byte load a lane, 32 multiply-adds and a reduction over the
+// group.  The rows are the first stage's list -- or, when it holds more than coarse_cap, every row of the index (dense:
+// lb5 is a bound of any row, so the test below alone decides).  Survivors: survivor_pass' own test with the 5-bit width,
+// collected in a block's stage as there (a claim that does not fit goes to the global counter).  The grid does not depend
+// on the count, which is read here.  DEBUG (lab hook): lb5 and B per entry.
+template <int C, bool DEBUG>
+__global__ __launch_bounds__(256) void k_q41_refine(const int32_t *__restrict__ H, const unsigned *__restrict__ fine,
+                                                    const float *__restrict__ scale, const float *__restrict__ err,
+                                                    const int32_t *__restrict__ D, const uint64_t *__restrict__ keys,
+                                                    int32_t k, unsigned *__restrict__ st, unsigned *__restrict__ cstate,
+                                                    const uint32_t *__restrict__ list, int64_t coarse_cap, int64_t n,
+                                                    int64_t *__restrict__ rows, int64_t cap, float *__restrict__ dbg_lb5,
+                                                    int32_t *__restrict__ dbg_B) {
+    constexpr int dim = 256 * C, LPR = dim / 32, RPW = 64 / LPR;  // lanes a row, rows a wave-step
+    if (st[5] != 0u || st[2] != 0u) return;  // the selection failed or the query cannot be bounded: the full scan
+    const int64_t found = (int64_t)cstate[0];
+    const bool dense = found > coarse_cap;
+    const int64_t m = dense ? n : found;
+    if (blockIdx.x == 0 && threadIdx.x == 0) cstate[1] = dense ? 1u : 0u;
+    const int lane = threadIdx.x & 63, j = lane % LPR, sub = lane / LPR;
+    int Dj[32];
+#pragma unroll
+    for (int t = 0; t < 32; ++t) Dj[t] = D[32 * j + t];
+    const double Td = (double)ord_to_f32((uint32_t)(keys[k - 1] >> 32));
+    const SlotBound sb = slot_bound(st, 0.125, q5_code_norm(dim));  // k_q5_bounds' and, for the width, k_survivors_mq's
+    const double sumD = (double)(int)st[6] * 256.0 + (double)(int)st[7];
+    __shared__ int64_t stage[SURV_STAGE];
+    __shared__ unsigned staged, first_failed, stage_base;
+    if (threadIdx.x == 0) staged = 0u, first_failed = 0xffffffffu;
+    __syncthreads();
+    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
+    constexpr int STEP = RPW * REFINE_UNROLL;  // entries a wave takes at a time
+    for (int64_t e0 = wave * STEP; e0 < m; e0 += nwaves * STEP) {
+        int64_t r[REFINE_UNROLL];
+        bool have[REFINE_UNROLL];
+#pragma unroll
+        for (int v = 0; v < REFINE_UNROLL; ++v) {
+            const int64_t e = e0 + v * RPW + sub;
+            have[v] = e < m;
+            r[v] = !have[v] ? 0 : dense ? e : (int64_t)list[e];
+            if (r[v] >= n) r[v] = 0, have[v] = false;  // (never beyond the rows, whatever the list holds)
+        }
+        unsigned fw[REFINE_UNROLL];
+        int h[REFINE_UNROLL];
+        float s[REFINE_UNROLL], a[REFINE_UNROLL];
+#pragma unroll
+        for (int v = 0; v < REFINE_UNROLL; ++v) {
+            fw[v] = fine[r[v] * LPR + j];
+            h[v] = H[r[v]];
+            s[v] = scale[r[v]];
+            a[v] = err[r[v]];
+        }
+#pragma unroll
+        for (int v = 0; v < REFINE_UNROLL; ++v) {
+            int B = 0;
+#pragma unroll
+            for (int t = 0; t < 32; ++t) B += (int)((fw[v] >> t) & 1u) * Dj[t];
+#pragma unroll
+            for (int off = 1; off < LPR; off <<= 1) B += __shfl_xor(B, off, 64);
+            const double I = 8.0 * (2.0 * (double)h[v] + (double)B - 16.0 * sumD);  // exact: |I| < 2^39
+            const float lb5 = certified_lb(I, s[v], a[v], sb);
+            const double l = (double)lb5, w = (double)a[v] * sb.wQ + (double)s[v] * sb.wE;
+            const bool keep = have[v] && j == 0 && (!(surv_ub(l, w) < Td) || !(lb5 > -INFINITY));
+            if constexpr (DEBUG) {
+                const int64_t e = e0 + v * RPW + sub;
+                if (e < m && j == 0) dbg_lb5[e] = lb5, dbg_B[e] = B;
+            }
+            const uint64_t ballot = __ballot(keep);
+            if (ballot == 0ull) continue;
+            const unsigned total = (unsigned)__popcll(ballot);
+            unsigned slot = 0u;
+            int direct = 0;
+            if (lane == 0) {
+                slot = atomicAdd(&staged, total);
+                if (slot + total > (unsigned)SURV_STAGE) {
+                    atomicMin(&first_failed, slot);
+                    slot = atomicAdd(&st[0], total);
+                    direct = 1;
+                }
+            }
+            slot = __shfl(slot, 0, 64);
+            direct = __shfl(direct, 0, 64);
+            const int64_t at = (int64_t)slot + __popcll(ballot & ((1ull << lane) - 1ull));
+            if (keep) {
+                if (!direct) stage[at] = r[v];
+                else if (at < cap) rows[at] = r[v];
+            }
+        }
+    }
+    __syncthreads();
+    const unsigned mine = min(staged, first_failed);
+    if (mine == 0u) return;
+    if (threadIdx.x == 0) stage_base = atomicAdd(&st[0], mine);
+    __syncthreads();
+    for (unsigned i = threadIdx.x; i < mine; i += 256) {
+        const int64_t at = (int64_t)stage_base + i;
+        if (at < cap) rows[at] = stage[i];
+    }
+}
+
+// k_prune_publish_mq for the one slot, with the first stage's count and the dense flag for the host's counters
+__global__ void k_prune_publish_q41(const unsigned *__restrict__ st, const unsigned *__restrict__ cstate, int64_t cap,
+                                    int32_t *__restrict__ host_block, unsigned seq) {
+    if (threadIdx.x != 0) return;
+    const bool fall = st[5] != 0u || st[2] != 0u || (int64_t)st[0] > cap;
+    host_block[1] = fall ? -1 : (int32_t)st[0];
+    host_block[2] = (int32_t)min(cstate[0], 0x7fffffffu);
+    host_block[3] = (int32_t)cstate[1];
+    __threadfence_system();
+    __hip_atomic_store(reinterpret_cast<unsigned *>(host_block), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // ---- the exact threshold of the 5-bit path ---------------------------------------------------------------------------
 // The threshold selection over the lower bounds ran for kc = min(SSW_MAX_TOPK, max(1024, 4 k)) keys instead of k.  Their
 // rows are scored exactly and T_x = the k-th largest of those scores: k distinct rows, none excluded, score at least
@@ -1345,20 +1675,21 @@ static void dispatch_dim(int C, F f) {
     f(Int<4>{});
 }
 
-// The launch shape of the four tile scans on the matrix core, by TileScan (ssw_tune_prune_scan_mq, ssw_tune_prune6_scan,
-// ssw_tune_prune6_scan_mq, ssw_tune_prune5_scan; lab build only): four-wave blocks per CU, and 16-row tiles of one request (0: the scan's
+// The launch shape of the five tile scans on the matrix core, by TileScan (ssw_tune_prune_scan_mq, ssw_tune_prune6_scan,
+// ssw_tune_prune6_scan_mq, ssw_tune_prune5_scan, ssw_tune_prune41_scan; lab build only): four-wave blocks per CU, and 16-row tiles of one request (0: the scan's
 // default for C)
 struct ScanTune {
     int blocks_per_cu;
     int tiles;
 };
-constexpr int SCAN_BLOCKS_PER_CU[4] = {MQ_BLOCKS_PER_CU, Q6_BLOCKS_PER_CU, Q6MQ_BLOCKS_PER_CU, Q5_BLOCKS_PER_CU};
-static SSW_TUNABLE ScanTune g_scan_tune[4] = {{SCAN_BLOCKS_PER_CU[0], 0}, {SCAN_BLOCKS_PER_CU[1], 0}, {SCAN_BLOCKS_PER_CU[2], 0},
-                                              {SCAN_BLOCKS_PER_CU[3], 0}};
+constexpr int SCAN_BLOCKS_PER_CU[5] = {MQ_BLOCKS_PER_CU, Q6_BLOCKS_PER_CU, Q6MQ_BLOCKS_PER_CU, Q5_BLOCKS_PER_CU, Q4_BLOCKS_PER_CU};
+static SSW_TUNABLE ScanTune g_scan_tune[5] = {{SCAN_BLOCKS_PER_CU[0], 0}, {SCAN_BLOCKS_PER_CU[1], 0}, {SCAN_BLOCKS_PER_CU[2], 0},
+                                              {SCAN_BLOCKS_PER_CU[3], 0}, {SCAN_BLOCKS_PER_CU[4], 0}};
 constexpr int scan_default_tiles(TileScan scan, int C) {
     return scan == SCAN_Q8_MQ ? mq_default_tiles(C)
            : scan == SCAN_Q6  ? q6_default_tiles(C)
            : scan == SCAN_Q5  ? q5_default_tiles(C)
+           : scan == SCAN_Q4  ? q4_default_tiles(C)
                               : q6mq_default_tiles(C);
 }
 
@@ -1388,18 +1719,22 @@ void tune_tile_scan(TileScan scan, int blocks_per_cu, int tiles) {
 
 // the C = dim / 256 a tile scan has instances of: its shadow's dims
 constexpr bool scan_has_dim(TileScan scan, int C) {
-    return scan == SCAN_Q8_MQ ? C != 3 : scan == SCAN_Q5 ? C == 2 || C == 4 : true;
+    return scan == SCAN_Q8_MQ ? C != 3 : scan == SCAN_Q5 || scan == SCAN_Q4 ? C == 2 || C == 4 : true;
 }
 
 // f(Int<C>, Int<T>, DEBUG) for the instance of tile scan S that scan_shape's T and the caller's debug output ask for.
 // The product has one instance per C of scan_has_dim, at the scan's default T and without DEBUG; the lab build has
-// every T with T * C <= 4 (scan_tiles), each with and without DEBUG.  (A C without instances: the caller has refused it.)
+// every T with T * C <= 4 (scan_tiles), each with and without DEBUG (SCAN_Q4: without).  (A C without instances: the caller has refused it.)
 template <TileScan S, class F>
 static void dispatch_scan(int C, int T, bool debug, F f) {
     auto at = [&](auto c) {
         if constexpr (scan_has_dim(S, c.value)) {
 #ifdef SSW_DEBUG_HOOKS
-            auto with_debug = [&](auto t) { debug ? f(c, t, std::true_type{}) : f(c, t, std::false_type{}); };
+            // (k_q4_bounds keeps its integer sums for the refine in every launch: it has no DEBUG instance)
+            auto with_debug = [&](auto t) {
+                if constexpr (S == SCAN_Q4) f(c, t, std::false_type{});
+                else debug ? f(c, t, std::true_type{}) : f(c, t, std::false_type{});
+            };
             if constexpr (c.value == 1)
                 if (T == 4) return with_debug(Int<4>{});
             if constexpr (c.value <= 2)
@@ -1676,6 +2011,97 @@ ssw_status launch_q5_bounds(const unsigned char *codes, const float *scale, cons
         hipLaunchKernelGGL((k_q5_bounds<c.value, t.value, d.value>), grid, dim3(256), 0, stream, as_u32x4(codes), scale, err,
                            as_u32x4(planes), st, scores, n, dbg_I);
     });
+}
+
+// ---- the two-stage 4 + 1-bit shadow ---------------------------------------------------------------------------------
+size_t q41_coarse_bytes(int64_t n, int32_t dim) { return (size_t)packed_padded_rows(n) * (size_t)dim / 2; }
+size_t q41_fine_bytes(int64_t n, int32_t dim) { return (size_t)packed_padded_rows(n) * (size_t)dim / 8; }
+
+ssw_status launch_q41_build(const void *X, int32_t dtype, int64_t n, int32_t dim, unsigned char *coarse, unsigned *fine,
+                            float *scale, float *err, float *err4, hipStream_t stream) {
+    if (n <= 0) return SSW_OK;
+    if (!q5_dim_supported(dim) || dtype != SSW_DTYPE_F32) {
+        set_error("q41_build: dim=%d, dtype=%d unsupported", dim, dtype);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    SSW_TRY(zero_last_tile(coarse, q41_coarse_bytes(n, dim), (size_t)16 * dim / 2, scale, err, n, stream));
+    const int64_t np = packed_padded_rows(n);
+    if (np != n) {
+        SSW_HIP_TRY(hipMemsetAsync(err4 + np - 16, 0, 16 * sizeof(float), stream));
+        SSW_HIP_TRY(hipMemsetAsync(fine + (np - 16) * (dim / 32), 0, (size_t)16 * dim / 8, stream));
+    }
+    const dim3 grid((unsigned)std::min<int64_t>((n + 3) / 4, (int64_t)1 << 20)), block(256);
+    const float *Xf = static_cast<const float *>(X);
+    if (dim == 512) hipLaunchKernelGGL(k_q41_build<2>, grid, block, 0, stream, Xf, n, coarse, fine, scale, err, err4);
+    else hipLaunchKernelGGL(k_q41_build<4>, grid, block, 0, stream, Xf, n, coarse, fine, scale, err, err4);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+ssw_status launch_q41_query(const float *q_dev, int32_t dim, unsigned *st, int8_t *planes, float *q_keep, int32_t *D,
+                            unsigned *cstate, hipStream_t stream) {
+    hipLaunchKernelGGL(k_q41_query, dim3(1), dim3(256), 0, stream, q_dev, (int)dim, st, planes, q_keep, D, cstate);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+ssw_status launch_q4_bounds(const unsigned char *coarse, const float *scale, const float *err4, const int8_t *planes,
+                            const unsigned *st, float *scores, int32_t *H, int64_t n, int32_t dim, int device,
+                            hipStream_t stream) {
+    if (n <= 0) return SSW_OK;
+    if (!q5_dim_supported(dim)) {
+        set_error("q4_bounds: dim=%d unsupported", dim);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    return launch_tile_scan<SCAN_Q4>(dim, device, n, false, [&](dim3 grid, auto c, auto t, auto d) {
+        hipLaunchKernelGGL((k_q4_bounds<c.value, t.value, d.value>), grid, dim3(256), 0, stream, as_u32x4(coarse), scale, err4,
+                           as_u32x4(planes), st, scores, H, n);
+    });
+}
+
+ssw_status launch_survivors_q4(const float *lb4, const float *err4, const float *scale, const unsigned *mx, int64_t n,
+                               int32_t dim, const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *st,
+                               unsigned *cstate, uint32_t *rows32, int64_t list_cap, int blocks, int device,
+                               hipStream_t stream) {
+    const dim3 grid = blocks > 0 ? dim3((unsigned)blocks) : survivor_grid(device, n);
+    hipLaunchKernelGGL(k_survivors_q4, grid, dim3(256), 0, stream, lb4, err4, scale, mx, n, q4_code_norm(dim), keys, sel_count, k,
+                       st, cstate, rows32, list_cap);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+ssw_status launch_q41_refine(const int32_t *H, const unsigned *fine, const float *scale, const float *err, const int32_t *D,
+                             const uint64_t *keys, int32_t k, unsigned *st, unsigned *cstate, const uint32_t *rows32,
+                             int64_t coarse_cap, int64_t n, int32_t dim, int64_t *rows, int64_t cap, float *dbg_lb5,
+                             int32_t *dbg_B, int device, hipStream_t stream) {
+    if (n <= 0) return SSW_OK;
+    if (!q5_dim_supported(dim)) {
+        set_error("q41_refine: dim=%d unsupported", dim);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    // without the count: enough waves to hide the gathers' latency, no more blocks than a dense pass has steps
+    const int64_t step = (int64_t)4 * (64 / (dim / 32)) * REFINE_UNROLL;  // rows a block takes at a time
+    int64_t grid = (int64_t)num_cus(device) * 8;
+    if (grid > (n + step - 1) / step) grid = (n + step - 1) / step;
+    auto launch = [&](auto c, auto d) {
+        hipLaunchKernelGGL((k_q41_refine<c.value, d.value>), dim3((unsigned)grid), dim3(256), 0, stream, H, fine, scale, err, D,
+                           keys, k, st, cstate, rows32, coarse_cap, n, rows, cap, dbg_lb5, dbg_B);
+    };
+    auto with_dim = [&](auto d) { dim == 512 ? launch(Int<2>{}, d) : launch(Int<4>{}, d); };
+#ifdef SSW_DEBUG_HOOKS
+    if (dbg_lb5 != nullptr) with_dim(std::true_type{});
+    else
+#endif
+        with_dim(std::false_type{});
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+ssw_status launch_prune_publish_q41(const unsigned *st, const unsigned *cstate, int64_t cap, int32_t *host_block,
+                                    unsigned seq, hipStream_t stream) {
+    hipLaunchKernelGGL(k_prune_publish_q41, dim3(1), dim3(64), 0, stream, st, cstate, cap, host_block, seq);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
 }
 
 ssw_status launch_candidate_rows(const uint64_t *keys, const int32_t *sel_count, int32_t kc, int64_t n, int64_t *rows_out,

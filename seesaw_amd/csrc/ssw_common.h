@@ -224,7 +224,7 @@ int rescore_survivors_waves(int device, int64_t cap);
 ssw_status launch_mark_uncertified(const unsigned *slot_state, int64_t cap, uint64_t *msg_last_word, hipStream_t stream);
 // the tile scans on the int8 matrix core: launch_q8_bounds_mq, launch_q6_bounds, launch_q6_bounds_mq, launch_q5_bounds; scan_shape:
 // blocks and 16-row tiles per request of the launch the scan's launcher would make
-enum TileScan { SCAN_Q8_MQ, SCAN_Q6, SCAN_Q6_MQ, SCAN_Q5 };  // SCAN_Q5: launch_q5_bounds (below)
+enum TileScan { SCAN_Q8_MQ, SCAN_Q6, SCAN_Q6_MQ, SCAN_Q5, SCAN_Q4 };  // SCAN_Q5: launch_q5_bounds, SCAN_Q4: launch_q4_bounds (below)
 void scan_shape(TileScan scan, int32_t dim, int device, int64_t n, int *out_blocks, int *out_tiles);
 // the packed 6-bit shadow of f32 or f16 rows (prune.hip, "6-bit shadow"): tiles of 16 rows, 3 dim / 4 bytes a row, buffers
 // padded to whole tiles.  q6_slot / q6_element / q6_word_offset are the ONE placement of an element's code: k-step u, lane
@@ -298,6 +298,49 @@ ssw_status launch_candidate_rows(const uint64_t *keys, const int32_t *sel_count,
                                  hipStream_t stream);
 ssw_status launch_exact_threshold(uint64_t *keys, const int32_t *sel_count, const float *vals, int32_t k, int32_t kc,
                                   hipStream_t stream);
+// The two-plane 5-bit shadow of f32 rows at dim 512 and 1024 (prune.hip, "two-stage 4 + 1-bit shadow").  The codes c, s5
+// and a5 are the 5-bit shadow's; with u = c + 16 the COARSE plane holds h = u >> 1 (a nibble) of every element in tiles of
+// 16 rows, dim / 2 bytes a row, and the FINE plane b = u & 1 row-major, dim / 8 bytes a row (bit i & 31 of the row's word
+// i >> 5 is b of natural element i).  Lanes, k-steps and slots of the coarse plane are the 6-bit shadow's (q6_slot), and
+// so is the place of a lane's word in the tile (q6_word_offset); a lane owns two words a k-step.  q4_nibble is the ONE
+// placement of a nibble, shared by the builder and the lab hook and mirrored by the tests' numpy twin: slot j of k-step u
+// sits at bits [shift, shift + 4) of byte `byte` of the lane's word `word`, so that w & 0x0f0f0f0f and (w >> 4) &
+// 0x0f0f0f0f of the two words are the matrix core's four operand words of the k-step.
+__host__ __device__ inline void q4_nibble(int u, int j, int *word, int *byte, int *shift) {
+    *word = 2 * u + (j >> 3), *byte = j & 3, *shift = 4 * ((j >> 2) & 1);
+}
+constexpr int64_t COARSE_CAP = (int64_t)1 << 23;  // rows of the first stage's survivor list; more: the dense refine
+constexpr int Q41_STATE_WORDS = 4;                // [0] first-stage survivors, [1] 1 = the last refine was dense
+size_t q41_coarse_bytes(int64_t n, int32_t dim);
+size_t q41_fine_bytes(int64_t n, int32_t dim);
+// coarse / fine: the two planes; scale, err, err4: s5, a5 and a4 >= ||x - s5 (2 h - 15.5)|| (+ the rounding terms of a5),
+// packed_padded_rows floats each; the rows past n of the last tile get zeros
+ssw_status launch_q41_build(const void *X, int32_t dtype, int64_t n, int32_t dim, unsigned char *coarse, unsigned *fine,
+                            float *scale, float *err, float *err4, hipStream_t stream);
+// launch_q6_query, and beside it: the sums of the two code planes into st[6], st[7] (int32), D_i = 256 d_hi,i + d_lo,i in
+// natural order into D [dim], and cstate's Q41_STATE_WORDS words zeroed
+ssw_status launch_q41_query(const float *q_dev, int32_t dim, unsigned *st, int8_t *planes, float *q_keep, int32_t *D,
+                            unsigned *cstate, hipStream_t stream);
+// the first stage: lb4 of every row into scores and H_r = sum_i h_ri D_i into H [packed_padded_rows]
+ssw_status launch_q4_bounds(const unsigned char *coarse, const float *scale, const float *err4, const int8_t *planes,
+                            const unsigned *st, float *scores, int32_t *H, int64_t n, int32_t dim, int device,
+                            hipStream_t stream);
+// its survivors against the k-th key of `keys` (raised by launch_exact_threshold): the first `list_cap` into rows32 (any
+// order), their number into cstate[0]; a failed selection sets st[5].  No host wait.  blocks: 0 = the pass's own grid
+ssw_status launch_survivors_q4(const float *lb4, const float *err4, const float *scale, const unsigned *mx, int64_t n,
+                               int32_t dim, const uint64_t *keys, const int32_t *sel_count, int32_t k, unsigned *st,
+                               unsigned *cstate, uint32_t *rows32, int64_t list_cap, int blocks, int device,
+                               hipStream_t stream);
+// the second stage: for the listed rows -- or, with cstate[0] > coarse_cap, for every row (dense) -- the 5-bit scan's own
+// lower bound lb5 from H, the fine plane, s5 and a5, and the survivors of k_survivors_mq's test with the 5-bit width into
+// rows (cap) and st[0].  dbg_lb5 / dbg_B (lab hook only, else NULL): per list entry (per row when dense)
+ssw_status launch_q41_refine(const int32_t *H, const unsigned *fine, const float *scale, const float *err, const int32_t *D,
+                             const uint64_t *keys, int32_t k, unsigned *st, unsigned *cstate, const uint32_t *rows32,
+                             int64_t coarse_cap, int64_t n, int32_t dim, int64_t *rows, int64_t cap, float *dbg_lb5,
+                             int32_t *dbg_B, int device, hipStream_t stream);
+// launch_prune_publish_mq for one slot, with the first stage's count and the dense flag in host_block[2], [3]
+ssw_status launch_prune_publish_q41(const unsigned *st, const unsigned *cstate, int64_t cap, int32_t *host_block,
+                                    unsigned seq, hipStream_t stream);
 // rows between natural order and the index.  to_h16: n rows of natural-order f32 (src_f32) or binary16 (src_h16, the
 // other NULL) -> rows [0, n) of dst in the f16 layout, rounded to nearest even.  gather: rows (rows_or_null[i], or
 // first_row + i when it is NULL) of an index matrix of element type dtype -> n natural-order f32 rows of out.

@@ -502,6 +502,8 @@ class DeviceIndex:
         on, f32 or float16; below that every call is the full-precision one.
         An f32 index of dim 512 or 1024 without an image map and of at least 25 M rows: `shadow` is the packed 5-bit
         shadow single queries scan there, 5 dim / 8 + 8 bytes a row of (n + 15) // 16 * 16 rows in `shadow_bytes`.
+        From 100 M rows such an index holds the two-stage form of those codes instead (a 4-bit plane scanned for every
+        row, a 1-bit plane read for that scan's survivors), 5 dim / 8 + 16 bytes a row, and no packed 5-bit shadow.
         `completions=True` adds the two words of ssw_index_prune_completions (the six above stay what they were for
         callers that compare the whole dict): `completions`: full scans that completed a partial score buffer or slab
         for a reader; `rescored_rows`: rows the second-stage readers (`rescore_avg`, `gather_scores`, `topk_batch_avg`)

@@ -5,6 +5,7 @@
                                [--warmup-pairs 2]
     python tools/perf_prune.py --three-way [--rows ...] [--k 100] [--dtype float32|float16]
     python tools/perf_prune.py --dim 768 [--rows ...] [--k 100] [--dtype float32|float16]
+    python tools/perf_prune.py --two-stage [--rows ...] [--k 100] [--dim 512|1024] [--scan41 BLOCKS TILES]
 
 For each index size: a synthetic N x 512 index of f32 or binary16 rows, one first top-k (builds the int8 shadow, timed
 on its own), `warmup-pairs` untimed pairs, then `reps` pairs of top-k calls with the pruning switched off and on in turn
@@ -24,6 +25,12 @@ built, from the growth of prune_stats' shadow_bytes ("none", "int8", "6-bit" or 
 its name says ends the run).  Where the shadows do not fit beside the rows together, the int8 rounds and the 6-bit (and
 5-bit) rounds run one after the other on two indexes of the same rows, each alternating with the full scan; the 6-bit and
 the 5-bit call always alternate on one index.
+
+--two-stage (how MIN_ROWS_Q41 of csrc/index_prune.hip is chosen; f32 rows of dim 512 or 1024): full scan / packed 5-bit
+shadow / two-stage 4 + 1-bit shadow in turn on one index, the rounds and the JSON line of --three-way with the columns
+"q5" and "q41", and beside them the first stage's survivors of the two-stage calls (min, median, max) and the dense
+refines.  --scan41 sets k_q4_bounds' launch shape (four-wave blocks a CU, 16-row tiles a request) for the run and the
+line carries it.
 
 --dim D (default 512): the width of the index.  --dim 768 (how MIN_ROWS (6-bit single call, dim 768, f32) and MIN_ROWS (6-bit single call, dim 768, f16) are
 chosen): that dim has the 6-bit shadow alone, so the run is always the rounds of --three-way with two forms, full scan /
@@ -50,6 +57,8 @@ def main():
     ap.add_argument("--warmup-pairs", type=int, default=2)
     ap.add_argument("--three-way", action="store_true")
     ap.add_argument("--dim", type=int, choices=(256, 512, 768, 1024), default=512)
+    ap.add_argument("--two-stage", action="store_true")
+    ap.add_argument("--scan41", type=int, nargs=2, metavar=("BLOCKS", "TILES"))
     args = ap.parse_args()
     from seesaw_amd import _lib
     from seesaw_amd.device_index import DeviceIndex
@@ -68,17 +77,24 @@ def main():
         _lib.call("ssw_tune_prune", 0 if form == "full" else 1, 1, -1)
         _lib.call("ssw_tune_prune6", 1 if form == "q6" else 0, 1)
         _lib.call("ssw_tune_prune5", 1 if form == "q5" else 0, 1)
+        _lib.call("ssw_tune_prune41", 1 if form == "q41" else 0, 1, -1)
 
     dtype = np.dtype(args.dtype)
     six_only = dim == 768  # no int8 shadow at this dim
     five = dim in (512, 1024) and dtype == np.float32  # the fourth column
-    built_by = {"full": "none", "int8": "int8", "q6": "6-bit", "q5": "5-bit"}
+    built_by = {"full": "none", "int8": "int8", "q6": "6-bit", "q5": "5-bit", "q41": "two-stage"}
+    coarse = []  # the first stage's survivors of the timed two-stage calls
+
+    def coarse_stats(idx):
+        out = np.zeros(3, dtype=np.int64)
+        _lib.call("ssw_index_prune_coarse_stats", idx._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
+        return out
 
     def rounds(n, forms, wall, surv, shadows):
         """warm-up and timed rounds over `forms` on a fresh index; -> all forms returned the same bytes"""
         idx = DeviceIndex.synthetic(n, dim, seed=2024, dtype=dtype)
         grows = {0: "none", n * (dim + 8): "int8", (n + 15) // 16 * 16 * (dim * 3 // 4 + 8): "6-bit",
-                 (n + 15) // 16 * 16 * (dim * 5 // 8 + 8): "5-bit"}
+                 (n + 15) // 16 * 16 * (dim * 5 // 8 + 8): "5-bit", (n + 15) // 16 * 16 * (dim * 5 // 8 + 16): "two-stage"}
         same = True
         try:
             for form in forms:  # builds the shadows, untimed
@@ -97,11 +113,15 @@ def main():
                     out[form] = idx.topk(q, args.k)
                     if i >= 0:
                         wall.setdefault(form, []).append(1e3 * (time.perf_counter() - t0))
-                        if form in ("q6", "q5"):
+                        if form in ("q6", "q5", "q41"):
                             surv.setdefault(form, []).append(int(stats(idx)[2]))
+                        if form == "q41":
+                            coarse.append(int(coarse_stats(idx)[0]))
                 for form in forms[1:]:
                     same = same and all(np.array_equal(np.asarray(a).view(np.uint8), np.asarray(b).view(np.uint8))
                                         for a, b in zip(out[forms[0]], out[form]))
+            if "q41" in forms:
+                shadows["dense_refines"] = int(coarse_stats(idx)[1])
             return same, int(stats(idx)[4])
         finally:
             idx.close()
@@ -113,7 +133,9 @@ def main():
         together = six_only or n * (dim * dtype.itemsize + (dim + 8) + (dim * 3 // 4 + 8) + q5_bytes + 8) + (5 << 30) < total
         wall, surv, shadows = {}, {}, {}
         packed = ["q6", "q5"] if five else ["q6"]
-        if six_only:
+        if args.two_stage:
+            same, fallbacks = rounds(n, ["full", "q5", "q41"], wall, surv, shadows)
+        elif six_only:
             same, fallbacks = rounds(n, ["full", "q6"], wall, surv, shadows)
         elif together:
             same, fallbacks = rounds(n, ["full", "int8"] + packed, wall, surv, shadows)
@@ -132,21 +154,34 @@ def main():
             res[form + "_ms_spread"] = round(float(np.max(v) - np.min(v)), 3)
         for form, v in surv.items():
             res[form + "_survivors_min_median_max"] = [int(np.min(v)), int(np.median(v)), int(np.max(v))]
+        if args.two_stage:
+            res["q41_first_stage_min_median_max"] = [int(np.min(coarse)), int(np.median(coarse)), int(np.max(coarse))]
+            res["dense_refines"] = shadows.pop("dense_refines")
+            if args.scan41:
+                res["scan41_blocks_tiles"] = list(args.scan41)
+            coarse.clear()
         res.update({"fallbacks": fallbacks, "identical": bool(same)})
         print(json.dumps(res), flush=True)
 
     with _lib.debug_hooks():
-        if args.three_way or six_only:
+        if args.two_stage and not five:
+            raise SystemExit("--two-stage: f32 rows of dim 512 or 1024 only")
+        if args.three_way or six_only or args.two_stage:
             try:
+                if args.scan41:
+                    _lib.call("ssw_tune_prune41_scan", args.scan41[0], args.scan41[1])
                 for rows in args.rows:
                     three_way(int(rows))
             finally:
                 _lib.call("ssw_tune_prune", 1, -1, -1)
                 _lib.call("ssw_tune_prune6", 1, -1)
                 _lib.call("ssw_tune_prune5", 1, -1)
+                _lib.call("ssw_tune_prune41", 1, -1, -1)
+                _lib.call("ssw_tune_prune41_scan", 0, 0)
             return
         _lib.call("ssw_tune_prune6", 0, -1)
         _lib.call("ssw_tune_prune5", 0, -1)
+        _lib.call("ssw_tune_prune41", 0, -1, -1)
         for rows in args.rows:
             n = int(rows)
             idx = DeviceIndex.synthetic(n, dim, seed=2024, dtype=np.dtype(args.dtype))
@@ -199,6 +234,7 @@ def main():
                 idx.close()
         _lib.call("ssw_tune_prune6", 1, -1)
         _lib.call("ssw_tune_prune5", 1, -1)
+        _lib.call("ssw_tune_prune41", 1, -1, -1)
 
 
 if __name__ == "__main__":
