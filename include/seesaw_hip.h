@@ -794,6 +794,31 @@ ssw_status ssw_clip_embed_image_dev(ssw_clip *clip, void *hip_stream, const floa
  * InferenceActor.__call__ (multiscale_tools.py:187-202). */
 ssw_status ssw_clip_embed_tiles_u8(ssw_clip *clip, const uint8_t *tiles_hwc_host, int32_t b, int32_t normalize,
                                    float *out_host);
+/* Decoded images -> the vectors of their multiscale tiles, pyramid and tiling on the device (csrc/tiler.hip).  Replaces,
+ * for a batch of images, pyramid + rescale + strided_tiling + generate_multiscale_tiling
+ * (seesaw/indices/multiscale/multiscale_tools.py:16-117), batch_tx (:167-183) and InferenceActor.__call__ (:187-202).
+ *   images_hwc_concat_host: the images' RGB bytes, [h, w, 3] uint8 each, rows tight; image i starts at byte
+ *     image_offsets[i] (image_offsets[0] = 0, image_offsets[n_images] = the buffer's size; starts that are multiples of
+ *     8 save a device copy for a level of the source's own size).  image_hw[i] = {height, width}, each in 1 .. 16384.
+ *   level_wh[level_first[i] .. level_first[i + 1]) = {width, height} of image i's pyramid levels, in the order their tiles
+ *     are wanted.  The CALLER names them (seesaw_amd ... multiscale_tools.multiscale_plan: np.geomspace and math.floor
+ *     are Python's); every side is at least the tower's image size, the tile size.
+ * A level is PIL.Image.resize(size, BILINEAR) of the source, byte for byte (Pillow's 8-bit resample is integer
+ * arithmetic: 22-bit fixed-point coefficients, horizontal pass to uint8, then vertical pass); a level of the source's
+ * own size is the source.  Tiles per level: for i in (0, 1), for j in (0, 1), the row-major (h' / tile) x (w' / tile) grid
+ * of the level shifted by x = i tile / 2, y = j tile / 2.  The tiles are never materialised: the patch gather reads them
+ * in place, with batch_tx's arithmetic as in ssw_clip_embed_tiles_u8, and a tile's vector is the one that entry gives
+ * for the same bytes.  out_vectors_host [out_cap_tiles, projection_dim] f32 receives the vectors in tile order, image
+ * after image; *out_n_tiles their count (also set when out_cap_tiles is too small).
+ * Refused with SSW_ERR_INVALID before any device call, the message naming the value: a level side below the tile size,
+ * a source or level side outside 1 .. 16384, out_cap_tiles below the count (the message holds the count), offsets that
+ * do not hold their image, and a call whose sources, levels, intermediate rows and tables exceed
+ * SSW_CLIP_TILER_ARENA_BYTES (hand over fewer images).  The handle stays usable. */
+#define SSW_CLIP_TILER_ARENA_BYTES ((int64_t)1 << 30)
+ssw_status ssw_clip_embed_multiscale_u8(ssw_clip *clip, const uint8_t *images_hwc_concat_host, int32_t n_images,
+                                        const int64_t *image_offsets, const int32_t *image_hw, const int32_t *level_first,
+                                        const int32_t *level_wh, int32_t normalize, float *out_vectors_host,
+                                        int64_t out_cap_tiles, int64_t *out_n_tiles);
 /* input_ids [b, seq_len] int32 (BOS ... EOS [pad]); the feature is taken at the first EOS. */
 ssw_status ssw_clip_embed_text(ssw_clip *clip, const int32_t *ids_host, int32_t b, int32_t seq_len,
                                int32_t normalize, float *out_host);

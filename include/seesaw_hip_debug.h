@@ -283,6 +283,18 @@ ssw_status ssw_clip_debug_tap(ssw_clip *clip, int32_t tower, int32_t layer);
 ssw_status ssw_clip_debug_tap_read(ssw_clip *clip, float *out_host_or_null, int64_t cap_floats, int64_t *out_rows,
                                    int32_t *out_dim);
 
+/* The device-side tile pyramid (csrc/tiler.hip) seen from outside, through the product's planner, job table and
+ * kernels (tests/test_device_tiling_gpu.py).  resize: one image [src_h, src_w, 3] uint8 -> the level [dst_h, dst_w, 3]
+ * (any size from 1 x 1 on: no tile is cut) back on the host, rows tight.  multiscale_tiles: the arguments of
+ * ssw_clip_embed_multiscale_u8 without `normalize`; returns the uint8 tiles [n, tile, tile, 3] the gather would read
+ * instead of their vectors. */
+ssw_status ssw_debug_resize_u8(ssw_clip *clip, const uint8_t *src_hwc_host, int32_t src_w, int32_t src_h, int32_t dst_w,
+                               int32_t dst_h, uint8_t *out_hwc_host);
+ssw_status ssw_debug_clip_multiscale_tiles(ssw_clip *clip, const uint8_t *images_hwc_concat_host, int32_t n_images,
+                                           const int64_t *image_offsets, const int32_t *image_hw,
+                                           const int32_t *level_first, const int32_t *level_wh, uint8_t *out_tiles_host,
+                                           int64_t out_cap_tiles, int64_t *out_n_tiles);
+
 #ifdef __cplusplus
 }
 #endif

@@ -139,6 +139,8 @@ _SIGNATURES = {
     "ssw_clip_embed_image_dev": (c_i32, [c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_void_p]),
     "ssw_clip_embed_text": (c_i32, [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p]),
     "ssw_clip_embed_tiles_u8": (c_i32, [c_void_p, c_void_p, c_i32, c_i32, c_void_p]),
+    "ssw_clip_embed_multiscale_u8": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_i32,
+                                             c_void_p, c_i64, c_i64_p]),
     "ssw_clip_sync": (c_i32, [c_void_p]),
     "ssw_clip_set_option": (c_i32, [c_void_p, c_i32, c_i32]),
     "ssw_wm_build_symmetric": (c_i32, [c_i32, c_i64, c_i64, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_i64)]),
@@ -226,6 +228,9 @@ _DEBUG_SIGNATURES = {
     "ssw_debug_attn_out_stamps": (c_i32, [c_void_p, c_i32]),
     "ssw_clip_debug_tap": (c_i32, [c_void_p, c_i32, c_i32]),
     "ssw_clip_debug_tap_read": (c_i32, [c_void_p, c_void_p, c_i64, c_i64_p, c_i32_p]),
+    "ssw_debug_resize_u8": (c_i32, [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_i32, c_void_p]),
+    "ssw_debug_clip_multiscale_tiles": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_i64, c_i64_p]),
 }
 
 

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "ssw_common.h"
+#include "tiler.h"
 
 namespace ssw {
 namespace {
@@ -990,7 +991,42 @@ __global__ void im2col_patches(const float *__restrict__ px, bf16 *__restrict__ 
 // uint8 HWC tiles [B,224,224,3] (what the tiler produces, multiscale_tools.py:45-71) -> patches bf16,
 // with batch_tx's arithmetic fused in (multiscale_tools.py:167-183: x / 255, then (x - mean) / std in
 // f32): the f32 NCHW tensor is never materialised and the host hands over a quarter of the bytes.
-__global__ void im2col_patches_u8(const uint8_t *__restrict__ tiles, bf16 *__restrict__ out, int B, int img, int patch,
+// Where the tiles' bytes are is the Src policy's business: DenseTiles = [B, img, img, 3] as the host tiler stacks them,
+// LevelTiles = in place inside the pyramid levels of tiler.hip, through a descriptor per tile -- the 224 x 224 x 3 tile is
+// then never materialised.  Both give the same bf16 bits for the same pixels: the arithmetic below is the only copy.
+__device__ __forceinline__ float clip_norm_u8(uint8_t px, float mean, float stdv) { return ((float)px / 255.0f - mean) / stdv; }
+
+struct DenseTiles {
+    static constexpr bool in_levels = false;
+    const uint8_t *tiles;
+    int img;
+    __device__ __forceinline__ const uint8_t *row(int b, int y) const { return tiles + ((int64_t)b * img + y) * img * 3; }
+    __device__ __forceinline__ float value(int b, int c, int y, int x, float mean, float stdv) const {
+        return clip_norm_u8(row(b, y)[x * 3 + c], mean, stdv);
+    }
+};
+struct LevelTiles {  // (aligned form: level bases and pitches are multiples of 8 bytes, x0 of 8 pixels)
+    static constexpr bool in_levels = true;
+    const uint8_t *arena;
+    const TileDesc *tile;
+    __device__ __forceinline__ const uint8_t *row(int b, int y) const {
+        const TileDesc t = tile[b];
+        return arena + t.base + (int64_t)(t.y0 + y) * t.pitch + (int64_t)t.x0 * 3;
+    }
+    __device__ __forceinline__ float value(int b, int c, int y, int x, float mean, float stdv) const {
+        return clip_norm_u8(row(b, y)[x * 3 + c], mean, stdv);
+    }
+};
+struct PlanarF32 {  // [B, 3, img, img] f32, already normalised (ssw_clip_embed_image)
+    const float *px;
+    int img;
+    __device__ __forceinline__ float value(int b, int c, int y, int x, float, float) const {
+        return px[(((int64_t)b * 3 + c) * img + y) * img + x];
+    }
+};
+
+template <class Src>
+__global__ void im2col_patches_u8(const Src tiles, bf16 *__restrict__ out, int B, int img, int patch,
                                   float m0, float m1, float m2, float s0, float s1, float s2) {
     const int g = img / patch;
     const int pp = patch * patch;
@@ -1005,7 +1041,7 @@ __global__ void im2col_patches_u8(const uint8_t *__restrict__ tiles, bf16 *__res
         const int p = (int)(r % (g * g));
         const int b = (int)(r / (g * g));
         const int y = (p / g) * patch + py, x = (p % g) * patch + xg * 8;
-        const uint64_t *src = reinterpret_cast<const uint64_t *>(tiles + (((int64_t)b * img + y) * img + x) * 3);
+        const uint64_t *src = reinterpret_cast<const uint64_t *>(tiles.row(b, y) + x * 3);
         const uint64_t w0 = src[0], w1 = src[1], w2 = src[2];  // 8 pixels x RGB = 24 bytes
         uint8_t px[24];
 #pragma unroll
@@ -1019,7 +1055,7 @@ __global__ void im2col_patches_u8(const uint8_t *__restrict__ tiles, bf16 *__res
         for (int c = 0; c < 3; ++c) {
             bf16x8 o;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = to_bf16(((float)px[3 * j + c] / 255.0f - mean[c]) / stdv[c]);
+            for (int j = 0; j < 8; ++j) o[j] = to_bf16(clip_norm_u8(px[3 * j + c], mean[c], stdv[c]));
             *reinterpret_cast<bf16x8 *>(row + c * pp) = o;
         }
     }
@@ -1028,9 +1064,10 @@ __global__ void im2col_patches_u8(const uint8_t *__restrict__ tiles, bf16 *__res
 // Any patch size (ViT-L/14: 14): the two gathers above want 8 consecutive pixels of a patch row, 16-byte aligned.  Here a
 // thread is one output element: column c * patch^2 + py * patch + px as above, the row padded with zero columns to `ld`
 // (the next multiple of 64, the GEMM's K step: 588 -> 640), which the padded patch weight matches.  Scalar loads: the
-// gather is 150 KB a tile against the tower's tens of GFLOP.  U8 = the tiler's HWC bytes with batch_tx's arithmetic.
-template <bool U8>
-__global__ void im2col_patches_any(const void *__restrict__ src, bf16 *__restrict__ out, int B, int img, int patch, int ld,
+// gather is 150 KB a tile against the tower's tens of GFLOP.  Src::value is the element: PlanarF32 = the f32 NCHW tensor,
+// DenseTiles / LevelTiles = the tiler's HWC bytes with batch_tx's arithmetic (nothing here wants an alignment).
+template <class Src>
+__global__ void im2col_patches_any(const Src src, bf16 *__restrict__ out, int B, int img, int patch, int ld,
                                    float m0, float m1, float m2, float s0, float s1, float s2) {
     const int g = img / patch;
     const int pp = patch * patch;
@@ -1045,14 +1082,24 @@ __global__ void im2col_patches_any(const void *__restrict__ src, bf16 *__restric
             const int c = col / pp, py = (col % pp) / patch, pxx = col % patch;
             const int y = (p / g) * patch + py, x = (p % g) * patch + pxx;
             const float mean = c == 0 ? m0 : c == 1 ? m1 : m2, stdv = c == 0 ? s0 : c == 1 ? s1 : s2;
-            if (U8)
-                v = ((float)static_cast<const uint8_t *>(src)[(((int64_t)b * img + y) * img + x) * 3 + c] / 255.0f - mean) / stdv;
-            else
-                v = static_cast<const float *>(src)[(((int64_t)b * 3 + c) * img + y) * img + x];
+            v = src.value(b, c, y, x, mean, stdv);
         }
         out[i] = to_bf16(v);
     }
 }
+
+#ifdef SSW_DEBUG_HOOKS
+// lab build only (ssw_debug_clip_multiscale_tiles): the tiles the gathers above read in place, written out densely
+__global__ void debug_tiles_from_levels(const LevelTiles tiles, uint8_t *__restrict__ out, int B, int img) {
+    const int row_bytes = img * 3;
+    const int64_t total = (int64_t)B * img * row_bytes;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int xb = (int)(i % row_bytes);
+        const int64_t r = i / row_bytes;
+        out[i] = tiles.row((int)(r / img), (int)(r % img))[xb];
+    }
+}
+#endif
 
 __global__ void text_embed(const int *__restrict__ ids, const float *__restrict__ tok, const float *__restrict__ pos,
                            float *__restrict__ hidden, int B, int L, int D) {
@@ -1370,6 +1417,10 @@ struct ssw_clip {
     int tap_layer = -1, tap_tower = 0;  // the residual rows behind this layer of this tower (0 image, 1 text) ...
     float *tap_buf = nullptr;           // ... as f32 [tap_rows][tap_dim]
     int64_t tap_rows = 0, tap_dim = 0, tap_cap = 0;
+    // the device-side tile pyramid's arena (tiler.h): a call's sources, levels and tables; grows on demand up to
+    // TILER_ARENA_MAX_BYTES
+    uint8_t *tiler_arena = nullptr;
+    int64_t tiler_cap = 0;
 };
 
 namespace {
@@ -1377,6 +1428,12 @@ namespace {
 // columns of a row of c->patches and of c->patch_w: 3 patch^2 padded to the GEMM's K step of 64 (a multiple of it already
 // when patch % 8 == 0; patch 14: 588 -> 640).  seesaw_amd/models/clip.py::patch_columns is the same number.
 inline int patch_cols(int patch) { return (3 * patch * patch + 63) / 64 * 64; }
+// The 8-pixel gather (im2col_patches_u8) serves a tower whose patch size is a multiple of 8.  Dense tiles need no more
+// (img = a multiple of the patch); tiles read in place from pyramid levels start at multiples of half the image size
+// (the strided tiling's shifts), so there that half has to be a multiple of 8 as well: ViT-B/32 and ViT-B/16 (112) yes.
+inline bool aligned_gather(const Header &h, bool in_levels = false) {
+    return h.patch % 8 == 0 && (!in_levels || (h.image / 2) % 8 == 0);
+}
 // token rows of the image tower
 inline int vision_tokens(const Header &h) { return (h.image / h.patch) * (h.image / h.patch) + 1; }
 
@@ -1874,22 +1931,25 @@ ssw_status image_forward(ssw_clip *c, const float *pixels_dev, int B, int normal
     const Header &h = c->hdr;
     if (h.patch % 8 == 0)
         hipLaunchKernelGGL(im2col_patches, dim3(2048), dim3(256), 0, c->stream, pixels_dev, c->patches, B, h.image, h.patch);
-    else
-        hipLaunchKernelGGL(im2col_patches_any<false>, dim3(2048), dim3(256), 0, c->stream, (const void *)pixels_dev, c->patches, B,
-                           h.image, h.patch, patch_cols(h.patch), 0.f, 0.f, 0.f, 1.f, 1.f, 1.f);
+    else {
+        const PlanarF32 pixels{pixels_dev, h.image};
+        hipLaunchKernelGGL(im2col_patches_any<PlanarF32>, dim3(2048), dim3(256), 0, c->stream, pixels, c->patches, B, h.image,
+                           h.patch, patch_cols(h.patch), 0.f, 0.f, 0.f, 1.f, 1.f, 1.f);
+    }
     return image_forward_from_patches(c, B, normalize, out_dev);
 }
 
 // CLIP's pixel statistics (make_clip_transform, embeddings.py:405-419; batch_tx, multiscale_tools.py:176-179)
-ssw_status image_forward_u8(ssw_clip *c, const uint8_t *tiles_dev, int B, int normalize, float *out_dev) {
+// `tiles`: where the B tiles' bytes are (DenseTiles / LevelTiles).  The aligned gather reads 8 pixels with 8-byte loads.
+template <class Src>
+ssw_status image_forward_u8(ssw_clip *c, const Src tiles, int B, int normalize, float *out_dev) {
     const Header &h = c->hdr;
-    if (h.patch % 8 == 0)
-        hipLaunchKernelGGL(im2col_patches_u8, dim3(2048), dim3(256), 0, c->stream, tiles_dev, c->patches, B, h.image, h.patch,
+    if (aligned_gather(h, Src::in_levels))
+        hipLaunchKernelGGL(im2col_patches_u8<Src>, dim3(2048), dim3(256), 0, c->stream, tiles, c->patches, B, h.image, h.patch,
                            0.48145466f, 0.4578275f, 0.40821073f, 0.26862954f, 0.26130258f, 0.27577711f);
     else
-        hipLaunchKernelGGL(im2col_patches_any<true>, dim3(2048), dim3(256), 0, c->stream, (const void *)tiles_dev, c->patches, B,
-                           h.image, h.patch, patch_cols(h.patch), 0.48145466f, 0.4578275f, 0.40821073f, 0.26862954f,
-                           0.26130258f, 0.27577711f);
+        hipLaunchKernelGGL(im2col_patches_any<Src>, dim3(2048), dim3(256), 0, c->stream, tiles, c->patches, B, h.image, h.patch,
+                           patch_cols(h.patch), 0.48145466f, 0.4578275f, 0.40821073f, 0.26862954f, 0.26130258f, 0.27577711f);
     return image_forward_from_patches(c, B, normalize, out_dev);
 }
 
@@ -1909,6 +1969,37 @@ ssw_status text_forward(ssw_clip *c, const int *ids_dev, int B, int L, int norma
     hipLaunchKernelGGL(eos_rows, dim3((B + 255) / 256), dim3(256), 0, s, ids_dev, B, L, h.eos, c->rows);
     c->rows_key = -1;
     return pool_and_project(c, c->txt, B, D, normalize, out_dev);
+}
+
+// ---- device-side tile pyramid (tiler.hip) ----
+ssw_status reserve_tiler(ssw_clip *c, int64_t bytes) {
+    if (bytes <= c->tiler_cap) return SSW_OK;
+    SSW_HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->tiler_arena) (void)hipFree(c->tiler_arena);
+    c->tiler_arena = nullptr;
+    c->tiler_cap = 0;
+    constexpr int64_t grain = (int64_t)64 << 20;  // grow in steps: calls of a pipeline differ by a few levels
+    const int64_t cap = std::min(TILER_ARENA_MAX_BYTES, (bytes + grain - 1) / grain * grain);
+    SSW_HIP_TRY(hipMalloc((void **)&c->tiler_arena, (size_t)cap));
+    c->tiler_cap = cap;
+    return SSW_OK;
+}
+
+// The plan's host tables and the caller's images are pageable memory handed to asynchronous copies: whatever way a call
+// ends, the stream is drained before they go.
+struct DrainOnExit {
+    hipStream_t s;
+    ~DrainOnExit() { (void)hipStreamSynchronize(s); }
+};
+
+// the levels of a planned call: arena, upload, the two resample launches (every refusal was tiler_plan's, before this)
+ssw_status build_levels(ssw_clip *c, const uint8_t *images_host, const TilerPlan &plan) {
+    SSW_TRY(reserve_tiler(c, plan.arena_bytes));
+    return tiler_run(c->stream, c->tiler_arena, images_host, plan);
+}
+
+inline LevelTiles level_tiles(const ssw_clip *c, const TilerPlan &plan, int64_t first) {
+    return LevelTiles{c->tiler_arena, reinterpret_cast<const TileDesc *>(c->tiler_arena + plan.tiles_off) + first};
 }
 
 }  // namespace
@@ -1960,6 +2051,7 @@ ssw_status ssw_clip_destroy(ssw_clip *c) {
                     (void *)c->out, (void *)c->ids, (void *)c->rows, (void *)c->stats_a, (void *)c->stats_b, (void *)c->splitk})
         (void)hipFree(p);
     if (c->tap_buf) (void)hipFree(c->tap_buf);  // (allocated by the lab build's tap only; either build's destroy frees it)
+    if (c->tiler_arena) (void)hipFree(c->tiler_arena);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return SSW_OK;
@@ -2082,13 +2174,88 @@ ssw_status ssw_clip_embed_tiles_u8(ssw_clip *c, const uint8_t *tiles_hwc_host, i
         const int nb = std::min(chunk, b - b0);
         SSW_HIP_TRY(hipMemcpyAsync(c->pixels, tiles_hwc_host + (size_t)b0 * per, (size_t)nb * per, hipMemcpyHostToDevice,
                                    c->stream));
-        SSW_TRY(image_forward_u8(c, reinterpret_cast<const uint8_t *>(c->pixels), nb, normalize, c->out));
+        const DenseTiles tiles{reinterpret_cast<const uint8_t *>(c->pixels), h.image};
+        SSW_TRY(image_forward_u8(c, tiles, nb, normalize, c->out));
         SSW_HIP_TRY(hipMemcpyAsync(out_host + (size_t)b0 * h.proj, c->out, (size_t)nb * h.proj * sizeof(float),
                                    hipMemcpyDeviceToHost, c->stream));
         SSW_HIP_TRY(hipStreamSynchronize(c->stream));
     }
     return SSW_OK;
 }
+
+ssw_status ssw_clip_embed_multiscale_u8(ssw_clip *c, const uint8_t *images_hwc_concat_host, int32_t n_images,
+                                        const int64_t *image_offsets, const int32_t *image_hw, const int32_t *level_first,
+                                        const int32_t *level_wh, int32_t normalize, float *out_vectors_host,
+                                        int64_t out_cap_tiles, int64_t *out_n_tiles) {
+    SSW_REQUIRE(c && images_hwc_concat_host && out_vectors_host && out_n_tiles, "bad argument");
+    const Header &h = c->hdr;
+    TilerPlan plan;
+    SSW_TRY(tiler_plan(h.image, h.image, n_images, image_offsets, image_hw, level_first, level_wh, &plan));
+    const int64_t total = (int64_t)plan.tiles.size();
+    *out_n_tiles = total;
+    SSW_REQUIRE(total <= out_cap_tiles, "multiscale: the call makes %lld tiles, out_cap_tiles is %lld", (long long)total,
+                (long long)out_cap_tiles);
+    DeviceGuard guard(c->device);
+    const int chunk = image_chunk(h);
+    SSW_TRY(reserve(c, std::min<int64_t>(total, chunk)));
+    DrainOnExit drain{c->stream};
+    SSW_TRY(build_levels(c, images_hwc_concat_host, plan));
+    for (int64_t b0 = 0; b0 < total; b0 += chunk) {  // (a chunk boundary may fall inside an image: tiles are just rows of the list)
+        const int nb = (int)std::min<int64_t>(chunk, total - b0);
+        SSW_TRY(image_forward_u8(c, level_tiles(c, plan, b0), nb, normalize, c->out));
+        SSW_HIP_TRY(hipMemcpyAsync(out_vectors_host + (size_t)b0 * h.proj, c->out, (size_t)nb * h.proj * sizeof(float),
+                                   hipMemcpyDeviceToHost, c->stream));
+        SSW_HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return SSW_OK;
+}
+
+#ifdef SSW_DEBUG_HOOKS
+ssw_status ssw_debug_resize_u8(ssw_clip *c, const uint8_t *src_hwc_host, int32_t src_w, int32_t src_h, int32_t dst_w,
+                               int32_t dst_h, uint8_t *out_hwc_host) {
+    SSW_REQUIRE(c && src_hwc_host && out_hwc_host, "bad argument");
+    const int64_t offsets[2] = {0, (int64_t)std::max(src_w, 0) * std::max(src_h, 0) * 3};
+    const int32_t hw[2] = {src_h, src_w}, first[2] = {0, 1}, wh[2] = {dst_w, dst_h};
+    TilerPlan plan;
+    SSW_TRY(tiler_plan(c->hdr.image, 1, 1, offsets, hw, first, wh, &plan));
+    DeviceGuard guard(c->device);
+    DrainOnExit drain{c->stream};
+    SSW_TRY(build_levels(c, src_hwc_host, plan));
+    SSW_HIP_TRY(hipMemcpy2DAsync(out_hwc_host, (size_t)dst_w * 3, c->tiler_arena + plan.level_base[0], (size_t)plan.level_pitch[0],
+                                 (size_t)dst_w * 3, (size_t)dst_h, hipMemcpyDeviceToHost, c->stream));
+    SSW_HIP_TRY(hipStreamSynchronize(c->stream));
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_clip_multiscale_tiles(ssw_clip *c, const uint8_t *images_hwc_concat_host, int32_t n_images,
+                                           const int64_t *image_offsets, const int32_t *image_hw, const int32_t *level_first,
+                                           const int32_t *level_wh, uint8_t *out_tiles_host, int64_t out_cap_tiles,
+                                           int64_t *out_n_tiles) {
+    SSW_REQUIRE(c && images_hwc_concat_host && out_tiles_host && out_n_tiles, "bad argument");
+    const Header &h = c->hdr;
+    TilerPlan plan;
+    SSW_TRY(tiler_plan(h.image, h.image, n_images, image_offsets, image_hw, level_first, level_wh, &plan));
+    const int64_t total = (int64_t)plan.tiles.size();
+    *out_n_tiles = total;
+    SSW_REQUIRE(total <= out_cap_tiles, "multiscale: the call makes %lld tiles, out_cap_tiles is %lld", (long long)total,
+                (long long)out_cap_tiles);
+    DeviceGuard guard(c->device);
+    const int chunk = image_chunk(h);
+    SSW_TRY(reserve(c, std::min<int64_t>(total, chunk)));
+    DrainOnExit drain{c->stream};
+    SSW_TRY(build_levels(c, images_hwc_concat_host, plan));
+    const size_t per = (size_t)3 * h.image * h.image;  // bytes a tile; c->pixels holds a chunk of them (it is sized for f32)
+    for (int64_t b0 = 0; b0 < total; b0 += chunk) {
+        const int nb = (int)std::min<int64_t>(chunk, total - b0);
+        hipLaunchKernelGGL(debug_tiles_from_levels, dim3(2048), dim3(256), 0, c->stream, level_tiles(c, plan, b0),
+                           reinterpret_cast<uint8_t *>(c->pixels), nb, h.image);
+        SSW_HIP_TRY(hipGetLastError());
+        SSW_HIP_TRY(hipMemcpyAsync(out_tiles_host + (size_t)b0 * per, c->pixels, (size_t)nb * per, hipMemcpyDeviceToHost, c->stream));
+        SSW_HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return SSW_OK;
+}
+#endif
 
 ssw_status ssw_clip_embed_image_dev(ssw_clip *c, void *hip_stream, const float *nchw_dev, int32_t b,
                                     int32_t normalize, float *out_dev) {

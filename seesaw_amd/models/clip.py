@@ -113,6 +113,75 @@ class ClipModel:
                   ctypes.c_void_p(out.ctypes.data))
         return out
 
+    # What a call's sources, levels, intermediate rows and tables may take of the device (include/seesaw_hip.h,
+    # SSW_CLIP_TILER_ARENA_BYTES); embed_multiscale_u8 splits its list so that every call stays under it.
+    TILER_ARENA_BYTES = 1 << 30
+
+    def tiler_bytes(self, shape, level_sizes) -> int:
+        """An upper bound of what one [h, w, 3] image with these (w', h') levels takes of the arena (csrc/tiler.hip,
+        tiler_plan): the source; per level its rows (pitch rounded up to 8 bytes) and the horizontal pass's intermediate
+        rows, whether or not that pass runs; the tables -- (2 ceil(in / out) + 3) int32 coefficients an output row or
+        column, two 56-byte jobs a level, a 24-byte descriptor a tile."""
+        h, w, t = int(shape[0]), int(shape[1]), self.image_size
+        total = h * w * 3 + 8
+        for (lw, lh) in level_sizes:
+            lw, lh = max(int(lw), 1), max(int(lh), 1)
+            total += (lh + h) * (-(-lw * 3 // 8) * 8) + 16
+            total += 4 * (lw * (2 * -(-w // lw) + 3) + lh * (2 * -(-h // lh) + 3)) + 2 * 56 + 24
+            total += 24 * 4 * (lw // t) * (lh // t)
+        return total
+
+    def embed_multiscale_u8(self, images, plans, normalize: bool = True) -> np.ndarray:
+        """Decoded images -> the vectors of their multiscale tiles, pyramid and tiling on the device
+        (ssw_clip_embed_multiscale_u8).  images: list of [h, w, 3] uint8 arrays; plans: per image what
+        multiscale_tools.multiscale_plan returned -- (levels, meta), levels with columns w, h -- or just the list of
+        (w', h') level sizes.  -> [total tiles, projection_dim] f32 in tile order, image after image: row i belongs to
+        row i of the concatenated meta frames."""
+        if len(images) != len(plans):
+            raise ValueError(f"{len(images)} images, {len(plans)} plans")
+        arrays, sizes = [], []
+        for i, (im, plan) in enumerate(zip(images, plans)):
+            if not isinstance(im, np.ndarray) or im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError(f"image {i}: want a uint8 array [h, w, 3], got "
+                                 f"{getattr(im, 'dtype', type(im).__name__)} {getattr(im, 'shape', '')}")
+            levels = plan[0] if isinstance(plan, tuple) else plan
+            if hasattr(levels, "columns"):
+                levels = list(zip(levels["w"].tolist(), levels["h"].tolist()))
+            arrays.append(np.ascontiguousarray(im))
+            sizes.append([(int(w), int(h)) for (w, h) in levels])
+        out, group, used = [], [], 0
+        for i in range(len(arrays)):
+            need = self.tiler_bytes(arrays[i].shape, sizes[i])
+            if group and used + need > self.TILER_ARENA_BYTES:
+                out.append(self._embed_multiscale_call([arrays[j] for j in group], [sizes[j] for j in group], normalize))
+                group, used = [], 0
+            group.append(i)
+            used += need
+        if group:
+            out.append(self._embed_multiscale_call([arrays[j] for j in group], [sizes[j] for j in group], normalize))
+        return np.concatenate(out) if out else np.zeros((0, self.projection_dim), np.float32)
+
+    def _embed_multiscale_call(self, arrays, sizes, normalize):
+        t, half = self.image_size, self.image_size // 2
+        offsets = [0]
+        for a in arrays:  # starts on multiples of 8 bytes: a level of the source's own size is then read in place
+            offsets.append(-(-(offsets[-1] + a.size) // 8) * 8)
+        buf = np.empty(max(offsets[-1], 1), np.uint8)
+        for a, o in zip(arrays, offsets):
+            buf[o:o + a.size] = a.reshape(-1)
+        offsets = np.asarray(offsets, np.int64)
+        hw = np.asarray([a.shape[:2] for a in arrays], np.int32).reshape(-1, 2)
+        first = np.cumsum([0] + [len(s) for s in sizes]).astype(np.int32)
+        wh = np.asarray([s for ls in sizes for s in ls], np.int32).reshape(-1, 2)
+        cap = sum(max(h - sy, 0) // t * (max(w - sx, 0) // t) for ls in sizes for (w, h) in ls for sx in (0, half)
+                  for sy in (0, half))
+        out = np.empty((max(cap, 1), self.projection_dim), np.float32)
+        n = ctypes.c_int64(0)
+        _lib.call("ssw_clip_embed_multiscale_u8", self._h, ctypes.c_void_p(buf.ctypes.data), len(arrays),
+                  ctypes.c_void_p(offsets.ctypes.data), ctypes.c_void_p(hw.ctypes.data), ctypes.c_void_p(first.ctypes.data),
+                  ctypes.c_void_p(wh.ctypes.data), int(normalize), ctypes.c_void_p(out.ctypes.data), cap, ctypes.byref(n))
+        return out[:n.value]
+
     def embed_image_dev(self, pixels_ptr: int, b: int, out_ptr: int, normalize: bool = True, stream_ptr: int = 0):
         _lib.call("ssw_clip_embed_image_dev", self._h, ctypes.c_void_p(stream_ptr) if stream_ptr else None,
                   ctypes.c_void_p(pixels_ptr), int(b), int(normalize), ctypes.c_void_p(out_ptr))
