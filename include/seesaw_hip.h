@@ -97,7 +97,8 @@ ssw_status ssw_index_destroy(ssw_index *idx);
  * set_excluded, topk_dev, select_deep_dev, result_ptrs, topk_fetch, gather_scores, set_tile_meta, rescore_avg,
  * rescore_avg_f64, profile, profile_read, prune_stats / prune_completions ("not pruned"), ssw_labelprop_scores_to_index,
  * ssw_labelprop_round; ssw_index_device_ptrs hands out the view's score buffer and a NULL row pointer;
- * ssw_index_score_rows, ssw_index_gather_rows and ssw_fb_set_data_from_index take VIEW rows and translate them.
+ * ssw_index_score_rows, ssw_index_gather_rows and ssw_fb_set_data_from_index take VIEW rows and translate them;
+ * ssw_index_coarse_mean reads a view as its SOURCE through the row table (and refuses one as its destination).
  * Refused on a view with SSW_ERR_UNSUPPORTED (the message says "view") before anything is touched: upload, upload_f16,
  * download, fill_random, set_row2image, every *_batch* entry, topk_slot_deep_dev, stage2_avg_batch_dev, both exchange
  * target setters, ssw_knn_build, ssw_xlx, ssw_fb_set_pseudo_sample_from_index, and a view of a view.
@@ -132,6 +133,27 @@ ssw_status ssw_index_download(ssw_index *idx, float *host_rows, int64_t first_ro
 /* fill the whole index on the device with the counter-based synthetic generator
  * (unit-norm rows; bit-identical to oracle.synth_rows(seed, global_first_row+i)). */
 ssw_status ssw_index_fill_random(ssw_index *idx, uint64_t seed, int64_t global_first_row);
+
+/* The coarse (one vector per image) rows out of a resident multiscale index, on the device: infer_coarse_embedding of
+ * the reference (seesaw/indices/coarse/preprocessor.py:11-19: the rows with zoom_level == max_zoom_level,
+ * groupby("dbidx").vectors.mean(), / np.maximum(norm, 1e-6)), the one way it builds a CoarseIndex (from_fine_grained,
+ * preprocessor.py:22-52).  keep_host [src n_rows]: != 0 marks a kept row; images_host [m]: positions in src's image map,
+ * strictly ascending.  Row i of dst becomes, for image images_host[i] with kept rows r_1 < ... < r_c:
+ *   s = x[r_1] + ... + x[r_c] in double in ascending row order (binary16 rows widened exactly), mean = s / c,
+ *   dst[i] = (float)(mean / max(||mean||, 1e-6)), norm and divisions in double, ONE rounding to f32 (an f16 dst rounds
+ *   that f32 to binary16, nearest even).
+ * An image's row depends on its own kept rows alone: not on m, on the other listed images or on the device.
+ * src: needs an image map (else SSW_ERR_UNSUPPORTED); f32, f16 or a view (keep_host and images_host are then in the
+ * VIEW's numbering).  dst: an index of n_rows == m and src's dim on src's device, of either dtype, not a view
+ * (SSW_ERR_UNSUPPORTED, the message says "view"), not src and not src's parent.  The work is enqueued on src's stream
+ * and the call returns when it is done; dst's rows then count as changed exactly as after ssw_index_upload (its shadows
+ * are stale, its score buffer is completed first and is not partial).
+ * SSW_ERR_INVALID, like every refusal decided on the host before anything is enqueued: positions not strictly ascending
+ * or outside the map, a listed image without a kept row, dst of another shape or device, a NULL pointer.
+ * Device memory: n_rows mask bytes and 8 m bytes of positions for the duration of the call, nothing afterwards.
+ * ssw_index_profile(src) records one event pair around the kernel. */
+ssw_status ssw_index_coarse_mean(ssw_index *src, const uint8_t *keep_host, const int64_t *images_host, int64_t m,
+                                 ssw_index *dst);
 
 /* row -> image map (vector_meta.dbidx of the reference, multiscale_index.py:192):
  * host array [n_rows] int32, non-decreasing, values are *positions* 0..n_images-1 of

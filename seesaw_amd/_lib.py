@@ -59,6 +59,7 @@ _SIGNATURES = {
     "ssw_index_upload_f16": (c_i32, [c_void_p, c_void_p, c_i64, c_i64]),
     "ssw_index_download": (c_i32, [c_void_p, c_void_p, c_i64, c_i64]),
     "ssw_index_fill_random": (c_i32, [c_void_p, c_u64, c_i64]),
+    "ssw_index_coarse_mean": (c_i32, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
     "ssw_index_set_row2image": (c_i32, [c_void_p, c_void_p, c_i64]),
     "ssw_index_scan": (c_i32, [c_void_p, c_void_p, c_void_p]),
     "ssw_index_scan_dev": (c_i32, [c_void_p, c_void_p]),

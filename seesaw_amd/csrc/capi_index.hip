@@ -496,6 +496,68 @@ ssw_status ssw_index_download(ssw_index *idx, float *host_rows, int64_t first_ro
     return SSW_OK;
 }
 
+// the coarse index's rows out of a multiscale index (coarse.hip): every refusal is decided on the host, from the handle's
+// host mirror of the image map and the caller's mask, before anything is enqueued
+ssw_status ssw_index_coarse_mean(ssw_index *src, const uint8_t *keep_host, const int64_t *images_host, int64_t m,
+                                 ssw_index *dst) {
+    SSW_REQUIRE(src != nullptr && dst != nullptr && keep_host != nullptr && (m == 0 || images_host != nullptr), "NULL argument");
+    if (!src->has_map) {
+        set_error("ssw_index_coarse_mean: the source index has no image map (ssw_index_set_row2image)");
+        return SSW_ERR_UNSUPPORTED;
+    }
+    SSW_TRY(refuse_view(dst, "ssw_index_coarse_mean (dst)"));
+    SSW_REQUIRE(dst != src && dst != src->parent, "ssw_index_coarse_mean: dst holds the rows src reads");
+    SSW_REQUIRE(m >= 0 && dst->n == m && dst->dim == src->dim,
+                "ssw_index_coarse_mean: dst is [%lld, %d], need [%lld, %d] (one row a listed image, the source's dim)",
+                (long long)dst->n, dst->dim, (long long)m, src->dim);
+    SSW_REQUIRE(dst->device == src->device, "ssw_index_coarse_mean: dst is on device %d, src on device %d", dst->device,
+                src->device);
+    for (int64_t i = 0; i < m; ++i) {
+        const int64_t p = images_host[i];
+        SSW_REQUIRE(p >= 0 && p < src->n_images, "ssw_index_coarse_mean: image position %lld outside [0, %lld)", (long long)p,
+                    (long long)src->n_images);
+        SSW_REQUIRE(i == 0 || p > images_host[i - 1], "ssw_index_coarse_mean: positions must be strictly ascending (entry %lld)",
+                    (long long)i);
+        int64_t r = src->row_start_host[(size_t)p];
+        const int64_t r1 = src->row_start_host[(size_t)p + 1];
+        while (r < r1 && keep_host[r] == 0) ++r;
+        SSW_REQUIRE(r < r1, "ssw_index_coarse_mean: image position %lld has no kept row", (long long)p);
+    }
+    if (m == 0) return SSW_OK;
+    DeviceGuard guard(src->device);
+    SSW_TRY(rows_changing(dst));
+    if (dst->stream != src->stream) SSW_HIP_TRY(hipStreamSynchronize(dst->stream));  // whatever still reads dst's rows
+    hipStream_t s = src->stream;
+    // staged for this call alone: the mask (a byte a source row) and the listed positions
+    unsigned char *d_keep = nullptr;
+    int64_t *d_images = nullptr;
+    if (hipMalloc((void **)&d_keep, (size_t)std::max<int64_t>(src->n, 1)) != hipSuccess ||
+        hipMalloc((void **)&d_images, (size_t)m * sizeof(int64_t)) != hipSuccess) {
+        (void)hipFree(d_keep);
+        set_error("ssw_index_coarse_mean: hipMalloc of the %lld mask bytes and %lld positions failed", (long long)src->n,
+                  (long long)m);
+        return SSW_ERR_NOMEM;
+    }
+    ssw_status rc = SSW_OK;
+    hipError_t e = hipMemcpyAsync(d_keep, keep_host, (size_t)src->n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_images, images_host, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)  // (ssw_index_profile(src): one event pair around the kernel)
+        rc = profiled(src, [&] {
+            return launch_coarse_mean(src->X, src->dtype, src->parent ? src->row_src : nullptr, d_keep, src->row_start,
+                                      d_images, m, src->dim, dst->X, dst->dtype, src->device, s);
+        });
+    const hipError_t e2 = hipStreamSynchronize(s);  // the staging is freed below; dst's stream finds the rows written
+    if (e == hipSuccess) e = e2;
+    (void)hipFree(d_keep);
+    (void)hipFree(d_images);
+    if (rc != SSW_OK) return rc;
+    if (e != hipSuccess) {
+        set_error("ssw_index_coarse_mean: %s", hipGetErrorString(e));
+        return SSW_ERR_HIP;
+    }
+    return SSW_OK;
+}
+
 ssw_status ssw_index_fill_random(ssw_index *idx, uint64_t seed, int64_t global_first_row) {
     SSW_REQUIRE(idx != nullptr, "idx is NULL");
     SSW_TRY(refuse_view(idx, "ssw_index_fill_random"));

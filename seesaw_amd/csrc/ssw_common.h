@@ -348,6 +348,15 @@ ssw_status launch_rows_to_h16(const float *src_f32, const uint16_t *src_h16, int
                               hipStream_t stream);
 ssw_status launch_gather_rows(const void *X, int32_t dtype, const int64_t *rows_or_null, int64_t first_row, int64_t n,
                               int32_t dim, float *out, hipStream_t stream);
+// coarse.hip: out row i (i < m) = the normalised mean of the KEPT rows of image images[i] -- the rows r of
+// [row_start[images[i]], row_start[images[i] + 1]) with keep[r] != 0, at least one -- summed in double in ascending row
+// order, / count, / max(its double norm, 1e-6), rounded once to f32 (see coarse.hip).  X: f32 rows in natural order, or
+// binary16 rows in the f16 index's layout (src_dtype); row_src_or_null: X is read through a view's row table and keep /
+// row_start are in the view's numbering.  out: [m, dim] f32, or binary16 in the index layout (dst_dtype).  keep [rows],
+// row_start and images [m] are device pointers.  An image's row depends on its own kept rows alone.
+ssw_status launch_coarse_mean(const void *X, int32_t src_dtype, const int32_t *row_src_or_null, const unsigned char *keep,
+                              const int64_t *row_start, const int64_t *images, int64_t m, int32_t dim, void *out,
+                              int32_t dst_dtype, int device, hipStream_t stream);
 #ifdef SSW_DEBUG_HOOKS
 void tune_scan(int variant, int blocks_per_cu);
 void tune_scan_batch(int max_width, int blocks_per_cu);

@@ -62,7 +62,20 @@ def view_rows(row_start: np.ndarray, positions: np.ndarray):
     return parent_rows, start
 
 
+def kept_images(row_start: np.ndarray, keep: np.ndarray) -> np.ndarray:
+    """positions (int64, ascending) of the images with at least one kept row: image p holds the rows
+    [row_start[p], row_start[p + 1]) and `keep[r] != 0` marks a kept row -- `coarse_mean`'s default `images`"""
+    row_start = np.asarray(row_start, dtype=np.int64)
+    keep = np.asarray(keep).reshape(-1)
+    if keep.shape[0] != row_start[-1]:
+        raise ValueError(f"keep has {keep.shape[0]} entries for {int(row_start[-1])} rows")
+    kept_before = np.concatenate(([0], np.cumsum(keep != 0, dtype=np.int64)))
+    return np.flatnonzero(kept_before[row_start[1:]] > kept_before[row_start[:-1]]).astype(np.int64)
+
+
 class DeviceIndex:
+    _row_start: Optional[np.ndarray] = None  # int64 [n_images + 1] host mirror of the image map, None without one
+
     def __init__(self, n_rows: int, dim: int = 512, device: int = 0, dev_ptr: int = 0, dtype=np.float32):
         self._h = ctypes.c_void_p()
         self.n_rows = int(n_rows)
@@ -109,12 +122,14 @@ class DeviceIndex:
         if row2image is None:
             _lib.call("ssw_index_set_row2image", self._h, None, 0)
             self.n_images = self.n_rows
+            self._row_start = None
             return
         r2i = np.ascontiguousarray(row2image, dtype=np.int32)
         assert r2i.shape == (self.n_rows,)
         n_images = int(r2i[-1]) + 1 if self.n_rows else 0
         _lib.call("ssw_index_set_row2image", self._h, _ptr(r2i), n_images)
         self.n_images = n_images
+        self._row_start = np.concatenate(([0], np.cumsum(np.bincount(r2i, minlength=n_images)))).astype(np.int64)
 
     # -- zero-copy subset views -------------------------------------------------------
     is_view = False  # a view scans its member rows in place, out of `parent`'s matrix
@@ -142,7 +157,35 @@ class DeviceIndex:
         v.is_view, v.parent = True, self
         v.parent_rows = np.empty(v.n_rows, dtype=np.int64)
         _lib.call("ssw_index_view_rows", v._h, _ptr(v.parent_rows))
+        if self._row_start is not None:  # the view's own image map: its members' tile counts
+            v._row_start = np.concatenate(([0], np.cumsum(self._row_start[pos + 1] - self._row_start[pos]))).astype(np.int64)
         return v
+
+    # -- the coarse index's rows ------------------------------------------------------
+    def coarse_mean(self, keep, images=None, dtype=np.float32) -> "DeviceIndex":
+        """one row per image out of this index's resident rows (ssw_index_coarse_mean; infer_coarse_embedding of the
+        reference, seesaw/indices/coarse/preprocessor.py:11-19): the mean of the image's KEPT rows (`keep[r] != 0`, one
+        entry a row of this index) summed in float64 in row order, divided by max(its norm, 1e-6), rounded once to f32
+        -> a new owning DeviceIndex of `len(images)` rows and storage `dtype`, without an image map, on this index's
+        device.  `images`: positions in this index's image map, strictly ascending, each with a kept row; None: every
+        image that has one.  Works on an f32 or float16 index and on a view (keep and images in the view's numbering);
+        the rows never leave the device.  A row depends on its own image's kept rows alone."""
+        if self._row_start is None and images is None:  # (with a list the library refuses: it owns that message)
+            raise ValueError("coarse_mean needs an index with an image map (set_row2image)")
+        keep =np.ascontiguousarray(np.asarray(keep).reshape(-1) != 0, dtype=np.uint8)
+        if keep.shape[0] != self.n_rows:
+            raise ValueError(f"keep has {keep.shape[0]} entries, the index has {self.n_rows} rows")
+        pos = kept_images(self._row_start, keep) if images is None else \
+            np.ascontiguousarray(np.asarray(images).reshape(-1), dtype=np.int64)
+        if pos.shape[0] == 0:
+            raise ValueError("coarse_mean: no image to derive a row for (no kept row, or an empty list)")
+        out = DeviceIndex(pos.shape[0], self.dim, device=self.device, dtype=dtype)
+        try:
+            _lib.call("ssw_index_coarse_mean", self._h, _ptr(keep), _ptr(pos), pos.shape[0], out._h)
+        except Exception:
+            out.close()
+            raise
+        return out
 
     def close(self):
         if self._h:

@@ -31,11 +31,13 @@ def _positions_of(sorted_dbidx: np.ndarray, ids) -> np.ndarray:
 
 class CoarseIndex(AccessMethod):
     def __init__(self, embedding, vectors: np.ndarray, vector_meta: pd.DataFrame, path: str = None,
-                 device: int = 0, vector_dtype: str = "float32", _view_of=None):
+                 device: int = 0, vector_dtype: str = "float32", _view_of=None, _device_index=None):
         """vector_dtype="float16": the resident matrix is binary16 and `self.vectors` holds the widened rounded rows
         (what every host-side expression then reads is what the device scans).  `_view_of` (subset_view): (the parent's
         DeviceIndex, the member images' positions in it) -- the device index is then a view of the parent's resident
-        rows, not an upload of `vectors`"""
+        rows, not an upload of `vectors`.  `_device_index` (MultiscaleIndex.coarse_index): an owning DeviceIndex that
+        already holds these rows in `vector_dtype` on `device` -- it becomes this index's, nothing is uploaded, and
+        `vectors` is its download"""
         self.path = path
         self.embedding = embedding
         self.vector_dtype = _vector_dtype(vector_dtype)
@@ -46,7 +48,12 @@ class CoarseIndex(AccessMethod):
         self._dbidx = dbidx
         self.all_indices = FrozenBitMap(dbidx)
         self.device = device
-        if _view_of is not None:
+        if _device_index is not None:
+            assert _view_of is None and not _device_index.is_view
+            assert (_device_index.n_rows, _device_index.dim) == self.vectors.shape and \
+                _device_index.dtype == self.vector_dtype and _device_index.device == device
+            self._dev = _device_index
+        elif _view_of is not None:
             self._dev = _view_of[0].view(_view_of[1])
             assert self._dev.n_rows == self.vectors.shape[0]
         else:

@@ -236,7 +236,8 @@ class MultiscaleIndex(AccessMethod):
         else:
             vectors = np.load(f"{index_path}/vectors.npy", mmap_mode="r")
             meta = pd.read_parquet(f"{index_path}/vector_meta.parquet").reset_index(drop=True)
-        meta = meta[["dbidx", "zoom_level", "x1", "y1", "x2", "y2"]]
+        # (max_zoom_level, where the tiler wrote it: what coarse_index / from_fine_grained select the coarse rows by)
+        meta = meta[["dbidx", "zoom_level", "x1", "y1", "x2", "y2"] + [c for c in ("max_zoom_level",) if c in meta]]
         return MultiscaleIndex(embedding=embedding, vectors=np.asarray(vectors), vector_meta=meta,
                                vec_index=None, path=index_path,
                                excluded=info.get("excluded", None) if exclude is None else exclude, device=device,
@@ -454,6 +455,20 @@ class MultiscaleIndex(AccessMethod):
     def get_data(self, dbidx) -> pd.DataFrame:
         vmeta = self.vector_meta[self.vector_meta.dbidx == dbidx]
         return vmeta.assign(vectors=list(self.vectors[vmeta.index]))
+
+    def coarse_index(self, vector_dtype=None):
+        """the CoarseIndex of this index's images, in memory (seesaw/indices/coarse/preprocessor.py:11-19 without the
+        round trip through disk): one row per image that has a row at its max_zoom_level -- the normalised mean of those
+        rows -- derived on the device from the resident rows (DeviceIndex.coarse_mean) into a DeviceIndex the coarse
+        index then owns.  Nothing is uploaded; the host `vectors` are one download of the m x dim result; the embedding
+        is shared.  `vector_dtype` defaults to this index's.  On a subset_view index the result is an owning coarse
+        index of the subset."""
+        from ..coarse.coarse_index import CoarseIndex
+        from ..coarse.preprocessor import infer_coarse_embedding
+        dt = self.vector_dtype if vector_dtype is None else vector_dtype
+        meta, dev = infer_coarse_embedding(self, vector_dtype=dt)
+        return CoarseIndex(embedding=self.embedding, vectors=dev.download(), vector_meta=meta, device=self.device,
+                           vector_dtype=dt, _device_index=dev)
 
     def subset(self, indices: BitMap) -> AccessMethod:
         mask = np.isin(self._row_dbidx, np.asarray(indices, dtype=np.int64))
