@@ -727,6 +727,25 @@ ssw_status ssw_fb_fit(ssw_fb *fb, const ssw_fb_objective *obj, float *w_inout, i
  * 0 when the host drove one evaluation at a time (larger sets; or env SSW_FB_HOST_DRIVER).  Both walk the same
  * path bit for bit. */
 ssw_status ssw_fb_last_fit_on_device(const ssw_fb *fb, int32_t *out);
+/* ssw_fb_fit for nfit engines at once: the call site it replaces nfit times is the LBFGS of multi_reg.py:156 stepped
+ * at basic_trainer.py:59-63 (opt.step(closure)), taken once per session of a group that refines in lock step.  Slot s fits objs[s] on
+ * fbs[s] from row s of W_inout ([nfit][dim + 1]; a slot without intercept uses the first dim entries) with max_iter[s]
+ * and lr[s], and ends with the bits ssw_fb_fit returns for the same inputs: weights, iterations, evaluations, loss.
+ * Every slot that ssw_fb_fit would run as one launch gets one workgroup of ONE launch (k_fb_fit_wg_batch, grid = those
+ * slots), on its own engine's buffers and completion word; one launch may mix objectives and set sizes, and more slots
+ * than compute units queue.  Each engine's pending uploads stay on its own stream: the launch, on the first such
+ * slot's stream, waits for an event recorded on every other slot's.  The host then waits for every slot's completion
+ * word as ssw_fb_fit waits for one.  The slots ssw_fb_fit drives from the host (more than 1024 rows, SSW_FB_RANKREG,
+ * env SSW_FB_HOST_DRIVER) go through ssw_fb_fit afterwards, one by one; ssw_fb_last_fit_on_device tells per handle.
+ * Refused before anything is queued (SSW_ERR_INVALID): nfit < 1, a NULL or repeated handle, handles of different
+ * device or dim, max_iter < 1, a non-finite start weight.
+ * A slot whose loss or weights diverged gets SSW_ERR_NUMERIC in out_status, keeps its row of W_inout as it came, and
+ * ssw_fb_batch_error(fbs[s]) is the message ssw_fb_fit would have left ("" for a slot that is SSW_OK); the other
+ * slots are not concerned and the call returns SSW_OK.  out_iters, out_evals, out_final_loss ([nfit]) may be NULL. */
+ssw_status ssw_fb_fit_batch(ssw_fb *const *fbs, const ssw_fb_objective *objs, int32_t nfit, float *W_inout,
+                            const int32_t *max_iter, const float *lr, int32_t *out_iters, int32_t *out_evals,
+                            float *out_final_loss, int32_t *out_status);
+const char *ssw_fb_batch_error(const ssw_fb *fb);
 /* forget the installed rows, targets, query and X'LX (the allocations stay): lets one engine serve the scorers the
  * loops build anew every refine (LogisticRegressionPT(...) per round, loops/pseudo_lr.py:33, log_reg.py:22) without
  * an allocate / free cycle per round. */

@@ -125,6 +125,8 @@ _SIGNATURES = {
     "ssw_fb_scores": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p]),
     "ssw_fb_fit": (c_i32, [c_void_p, c_void_p, c_void_p, c_i32, ctypes.c_float, c_i32_p, c_i32_p, c_void_p]),
     "ssw_fb_last_fit_on_device": (c_i32, [c_void_p, c_i32_p]),
+    "ssw_fb_fit_batch": (c_i32, [c_void_pp, c_void_p, c_i32, c_f32_p, c_i32_p, c_f32_p, c_i32_p, c_i32_p, c_f32_p, c_i32_p]),
+    "ssw_fb_batch_error": (ctypes.c_char_p, [c_void_p]),
     "ssw_fb_reset": (c_i32, [c_void_p]),
     "ssw_np_permutation_prefix": (c_i32, [c_void_p, c_i32_p, c_i64, c_i64, c_void_p]),
     "ssw_np_permutation_prefix_dev": (c_i32, [c_i32, c_void_p, c_i32_p, c_i64, c_i64, c_void_p]),

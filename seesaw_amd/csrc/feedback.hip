@@ -18,6 +18,10 @@
 // terms.  Two drivers over the same arithmetic (bit-identical fits, tests/test_feedback_gpu.py):
 //   * n <= 1024 rows (every feedback session): k_fb_fit_wg -- the whole optimizer.step(closure), i.e. L-BFGS
 //     direction updates, strong-Wolfe line search and all closure evaluations, in ONE launch of one workgroup;
+//     k_fb_fit_wg_batch (ssw_fb_fit_batch) is that workgroup once per session of a group that refines in lock step,
+//     S fits in one launch and one host wait: the call site it replaces S times is the LBFGS of
+//     seesaw/loops/multi_reg.py:156 stepped by seesaw/basic_trainer.py:59-63 (opt.step(closure)), which the
+//     reference runs once per session and spreads over Ray actors;
 //   * larger sets (PseudoLR's 10 000 pseudo-labelled rows) and the rank objective: the host walks the same
 //     state machine and launches one evaluation at a time = 3-4 small kernels on rows that already sit in HBM:
 //       fb_logits   z = Xc w (+ b)                        wave per row, coalesced 16-B loads
@@ -32,6 +36,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 #include "ssw_common.h"
@@ -1594,9 +1599,12 @@ __device__ __noinline__ void fit_driver_step(double *base, int dim_) {
     if (lane == 0) *S.drv = D;
 }
 
-template <int FIT_EPL>
-__global__ __launch_bounds__(1024) void k_fb_fit_wg(FitWgArgs a_in, FbW w0v) {
-    extern __shared__ double fit_lds[];
+// The body both fit kernels run, from the LDS set-up to the publish by wave 0.  Nothing in it (nor in fit_eval_*,
+// fit_driver_step, fb_final_body) reads blockIdx / gridDim or a global scratch word: a workgroup touches its LDS and
+// the buffers its FitWgArgs name, so any number of them run side by side.  ARG_W: the start vector may sit in the
+// argument segment (`w0v`, the single launch); without it `w0_or_null` is set.
+template <int FIT_EPL, bool ARG_W>
+__device__ __forceinline__ void fit_wg_body(double *fit_lds, const FitWgArgs &a_in, const FbW *w0v) {
     const int c = threadIdx.x, lane = c & 63, wave = c >> 6;
     const int dim = a_in.dim, n = a_in.n, Pd = dim + 1;
     const FitLds S = fit_lds_map(fit_lds, dim);
@@ -1618,7 +1626,10 @@ __global__ __launch_bounds__(1024) void k_fb_fit_wg(FitWgArgs a_in, FbW w0v) {
     for (int k = c; k < 1040; k += 1024) S.gout[k] = 0.f;  // the driver reads it FIT_EPL * 64 wide
     for (int k = c; k < VS; k += 1024) {
         float x0 = 0.f;
-        if (k < a_in.P) x0 = a_in.w0_or_null ? a_in.w0_or_null[k] : w0v.v[k < FB_ARG_FLOATS ? k : 0];
+        if (k < a_in.P) {
+            if constexpr (ARG_W) x0 = a_in.w0_or_null ? a_in.w0_or_null[k] : w0v->v[k < FB_ARG_FLOATS ? k : 0];
+            else x0 = a_in.w0_or_null[k];
+        }
         S.vx[k] = x0;
         S.vd[k] = 0.f;
         S.vg[k] = 0.f;
@@ -1680,6 +1691,26 @@ __global__ __launch_bounds__(1024) void k_fb_fit_wg(FitWgArgs a_in, FbW w0v) {
     }
 }
 
+template <int FIT_EPL>
+__global__ __launch_bounds__(1024) void k_fb_fit_wg(FitWgArgs a_in, FbW w0v) {
+    extern __shared__ double fit_lds[];
+    fit_wg_body<FIT_EPL, true>(fit_lds, a_in, &w0v);
+}
+
+// k_fb_fit_wg_batch: S independent fits side by side -- the LBFGS of multi_reg.py:156, stepped at
+// basic_trainer.py:59-63, taken S times, once per session of a lock-step group -- in one launch and one host wait.  Block b is k_fb_fit_wg for entry b of `table`: its own engine's rows, targets,
+// coefficients, history and mapped result words with that engine's sequence number, so it publishes exactly as the
+// single launch does and no two blocks share a byte.  The start vector comes through w0_or_null (a row of a device
+// table of [nfit][dim + 1] floats).  n, P, label_mode, onepass, max_iter and lr are block-uniform loads: one launch
+// mixes objectives and set sizes.  The LDS allocation is the largest any slot needs (`stage` is the last region: a
+// larger allocation moves nothing); at 160 KB that is one workgroup a compute unit, further slots queue.
+template <int FIT_EPL>
+__global__ __launch_bounds__(1024) void k_fb_fit_wg_batch(const FitWgArgs *__restrict__ table) {
+    extern __shared__ double fit_lds[];
+    const FitWgArgs a_in = table[blockIdx.x];
+    fit_wg_body<FIT_EPL, false>(fit_lds, a_in, nullptr);
+}
+
 }  // namespace
 }  // namespace ssw
 
@@ -1731,6 +1762,13 @@ struct ssw_fb {
     float rank_factor = 0.f;   // 1 / total_pairs of the installed targets (SSW_FB_RANKREG)
     float *hist = nullptr;     // [2, FIT_HISTORY, 1024] L-BFGS history of the single-launch fit
     bool last_fit_on_device = false;
+    // ssw_fb_fit_batch: the engine of a launch's first slot lends the argument and start-vector tables
+    FitWgArgs *batch_tab = nullptr;  // [batch_cap]
+    float *batch_w = nullptr;        // [batch_cap, dim + 1]
+    int batch_cap = 0;
+    PinnedStage batch_tab_stage, batch_w_stage;
+    hipEvent_t batch_ev = nullptr;   // "this engine's uploads are queued", for the launch stream to wait on
+    std::string batch_error;         // this engine's slot of the last batch: the message ssw_fb_fit would have set, or empty
 };
 
 static ssw_status fb_reserve(ssw_fb *fb, int64_t n) {
@@ -2382,6 +2420,11 @@ ssw_status ssw_fb_destroy(ssw_fb *fb) {
     (void)hipFree(fb->out);
     (void)hipFree(fb->loss_dev);
     (void)hipFree(fb->hist);
+    fb->batch_tab_stage.release();
+    fb->batch_w_stage.release();
+    (void)hipFree(fb->batch_tab);
+    (void)hipFree(fb->batch_w);
+    if (fb->batch_ev) (void)hipEventDestroy(fb->batch_ev);
     if (fb->loss_host) (void)hipHostFree(fb->loss_host);
     if (fb->out_host) (void)hipHostFree(fb->out_host);
     if (fb->w_host) (void)hipHostFree(fb->w_host);
@@ -2677,12 +2720,91 @@ ssw_status ssw_fb_scores(ssw_fb *fb, const float *w_host, int32_t has_bias, floa
     return SSW_OK;
 }
 
+// ---- the one-launch fit's host side, shared by ssw_fb_fit and ssw_fb_fit_batch ----------------------------------
+static int fb_fit_params(const ssw_fb *fb, const ssw_fb_objective *obj) {
+    return fb->dim + ((obj->kind == SSW_FB_LOGREG && obj->fit_intercept) ? 1 : 0);
+}
+
+// a labelled set one workgroup reaches; every other fit is driven from the host, one evaluation at a time
+static bool fb_fit_wg_eligible(const ssw_fb *fb, const ssw_fb_objective *obj) {
+    return fb->n <= FIT_WG_MAX_ROWS && fb->dim + 1 <= 1024 && obj->kind != SSW_FB_RANKREG && !getenv("SSW_FB_HOST_DRIVER");
+}
+
+// the arguments of one fit workgroup after fb_prepare (`dev`, `pw`, `pairwise_active` are its outputs); takes the
+// engine's next sequence number.  w0_or_null is the caller's.
+static void fb_fit_wg_fill(ssw_fb *fb, const ssw_fb_objective *obj, const FbObjDev &dev, float pw, bool pairwise_active,
+                           int max_iter, float lr, FitWgArgs *out) {
+    FitWgArgs a;
+    memset(&a, 0, sizeof(a));
+    a.X = fb->X; a.y = fb->y; a.coef = fb->coef;
+    a.qhat = fb->has_q ? fb->qhat : nullptr;
+    a.xlx = fb->has_xlx ? fb->xlx : nullptr;
+    a.hist_dirs = fb->hist;
+    a.hist_stps = fb->hist + (size_t)FIT_HISTORY * 1024;
+    a.out_w = fb->out_host_dev + 1;
+    a.out_loss = fb->loss_host_dev;
+    a.out_counts = reinterpret_cast<int *>(fb->flag_host_dev) + 4;
+    a.done_flag = fb->flag_host_dev;
+    a.seqno = ++fb->seqno;
+    a.n = (int)fb->n; a.dim = fb->dim; a.P = fb_fit_params(fb, obj);
+    const bool pairwise = obj->kind == SSW_FB_MULTIREG && obj->loss_type != SSW_FB_LOSS_CE;
+    a.label_mode = !pairwise ? 0 : !pairwise_active ? 3 : obj->loss_type == SSW_FB_LOSS_PAIRWISE_LOGISTIC ? 2 : 1;
+    a.pw = pw; a.margin = obj->margin; a.max_iter = max_iter; a.lr = lr; a.obj = dev;
+    a.onepass = a.label_mode == 0 && fb->dim == FIT_OP_DIM && fb->n >= 1 && !getenv("SSW_FB_TWO_PASS");  // the variable is the tests' A/B switch
+    *out = a;
+}
+
+// the 160 KB dynamic-LDS attribute of the fit kernel `kern` (batch: k_fb_fit_wg_batch), once per (device, kernel)
+static ssw_status fb_fit_wg_attr(const void *kern, int device, int dim, bool batch) {
+    static bool attr_done[64][4] = {};
+    const int dslot = device >= 0 && device < 64 ? device : -1, kslot = (dim + 1 <= 9 * 64 ? 0 : 1) + (batch ? 2 : 0);
+    if (dslot < 0 || !attr_done[dslot][kslot]) {
+        SSW_HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        if (dslot >= 0) attr_done[dslot][kslot] = true;
+    }
+    return SSW_OK;
+}
+
+// bounded spin on the engine's completion word; false = not seen (the caller synchronises the launch stream)
+static bool fb_fit_wg_spin(const ssw_fb *fb, unsigned want) {
+    if (getenv("SSW_FB_NO_SPIN")) return false;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned it = 0;; ++it) {
+        if (__atomic_load_n(fb->flag_host, __ATOMIC_ACQUIRE) == want) return true;
+        if ((it & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) return false;
+    }
+}
+
+// what a finished fit workgroup left in the engine's mapped words: bookkeeping, the divergence checks, the weights
+static ssw_status fb_fit_wg_collect(ssw_fb *fb, int P, float *w_inout, int32_t *out_iters, int32_t *out_evals,
+                                    float *out_final_loss) {
+    const int *counts = reinterpret_cast<const int *>(fb->flag_host) + 4;
+    fb->last_iters = counts[0];
+    fb->last_evals = counts[1];
+    fb->last_fit_on_device = true;
+    if (counts[2] != 0) {
+        set_error("feedback: loss diverged -- regression training failed with a nan");
+        return SSW_ERR_NUMERIC;  // logistic_regression.py:398-401
+    }
+    for (int i = 0; i < P; ++i) {
+        if (!std::isfinite(fb->out_host[1 + i])) {
+            set_error("feedback: weights diverged");
+            return SSW_ERR_NUMERIC;
+        }
+        w_inout[i] = fb->out_host[1 + i];
+    }
+    if (out_iters) *out_iters = counts[0];
+    if (out_evals) *out_evals = counts[1];
+    if (out_final_loss) *out_final_loss = (float)fb->loss_host[0];
+    return SSW_OK;
+}
+
 ssw_status ssw_fb_fit(ssw_fb *fb, const ssw_fb_objective *obj, float *w_inout, int32_t max_iter, float lr,
                       int32_t *out_iters, int32_t *out_evals, float *out_final_loss) {
     SSW_REQUIRE(fb && obj && w_inout, "NULL argument");
     SSW_REQUIRE(max_iter >= 1, "max_iter < 1");
     DeviceGuard guard(fb->device);
-    const int P = fb->dim + ((obj->kind == SSW_FB_LOGREG && obj->fit_intercept) ? 1 : 0);
+    const int P = fb_fit_params(fb, obj);
     Evaluator E;
     E.fb = fb;
     E.o = obj;
@@ -2694,24 +2816,10 @@ ssw_status ssw_fb_fit(ssw_fb *fb, const ssw_fb_objective *obj, float *w_inout, i
     fb->last_evals = 0;
     fb->last_fit_on_device = false;
     // ---- the whole step(closure) in one launch (k_fb_fit_wg) when the labelled set fits one workgroup's reach
-    if (fb->n <= FIT_WG_MAX_ROWS && fb->dim + 1 <= 1024 && obj->kind != SSW_FB_RANKREG && !getenv("SSW_FB_HOST_DRIVER")) {
+    if (fb_fit_wg_eligible(fb, obj)) {
         for (int i = 0; i < P; ++i) SSW_REQUIRE(std::isfinite(w_inout[i]), "initial weight %d is not finite", i);
         FitWgArgs a;
-        memset(&a, 0, sizeof(a));
-        a.X = fb->X; a.y = fb->y; a.coef = fb->coef;
-        a.qhat = fb->has_q ? fb->qhat : nullptr;
-        a.xlx = fb->has_xlx ? fb->xlx : nullptr;
-        a.hist_dirs = fb->hist;
-        a.hist_stps = fb->hist + (size_t)FIT_HISTORY * 1024;
-        a.out_w = fb->out_host_dev + 1;
-        a.out_loss = fb->loss_host_dev;
-        a.out_counts = reinterpret_cast<int *>(fb->flag_host_dev) + 4;
-        a.done_flag = fb->flag_host_dev;
-        a.seqno = ++fb->seqno;
-        a.n = (int)fb->n; a.dim = fb->dim; a.P = P;
-        const bool pairwise = obj->kind == SSW_FB_MULTIREG && obj->loss_type != SSW_FB_LOSS_CE;
-        a.label_mode = !pairwise ? 0 : !E.pairwise_active ? 3 : obj->loss_type == SSW_FB_LOSS_PAIRWISE_LOGISTIC ? 2 : 1;
-        a.pw = E.pw; a.margin = obj->margin; a.max_iter = max_iter; a.lr = lr; a.obj = E.dev;
+        fb_fit_wg_fill(fb, obj, E.dev, E.pw, E.pairwise_active, max_iter, lr, &a);
         FbW w0v;
         memset(&w0v, 0, sizeof(w0v));
         if (fb->dim + 1 <= FB_ARG_FLOATS) {
@@ -2722,48 +2830,14 @@ ssw_status ssw_fb_fit(ssw_fb *fb, const ssw_fb_objective *obj, float *w_inout, i
             SSW_HIP_TRY(hipMemcpyAsync(fb->w, fb->w_host, (size_t)(fb->dim + 1) * sizeof(float), hipMemcpyHostToDevice, fb->stream));
             a.w0_or_null = fb->w;
         }
-        a.onepass = a.label_mode == 0 && fb->dim == FIT_OP_DIM && fb->n >= 1 && !getenv("SSW_FB_TWO_PASS");  // the variable is the tests' A/B switch
         const size_t lds = fit_wg_lds_bytes(fb->dim, a.onepass != 0);
         auto kern = fb->dim + 1 <= 9 * 64 ? k_fb_fit_wg<9> : k_fb_fit_wg<16>;
-        // the attribute is per device: one flag per (device, kernel)
-        static bool attr_done[64][2] = {};
-        const int dslot = fb->device >= 0 && fb->device < 64 ? fb->device : -1, kslot = fb->dim + 1 <= 9 * 64 ? 0 : 1;
-        if (dslot < 0 || !attr_done[dslot][kslot]) {
-            SSW_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            if (dslot >= 0) attr_done[dslot][kslot] = true;
-        }
+        SSW_TRY(fb_fit_wg_attr(reinterpret_cast<const void *>(kern), fb->device, fb->dim, false));
         hipLaunchKernelGGL(kern, dim3(1), dim3(1024), lds, fb->stream, a, w0v);
         SSW_HIP_TRY(hipGetLastError());
-        {
-            const unsigned want = fb->seqno;
-            bool seen = false;
-            if (!getenv("SSW_FB_NO_SPIN")) {
-                const auto t0 = std::chrono::steady_clock::now();
-                for (unsigned it = 0;; ++it) {
-                    if (__atomic_load_n(fb->flag_host, __ATOMIC_ACQUIRE) == want) {
-                        seen = true;
-                        break;
-                    }
-                    if ((it & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-                }
-            }
-            if (!seen) SSW_HIP_TRY(hipStreamSynchronize(fb->stream));
-        }
+        if (!fb_fit_wg_spin(fb, fb->seqno)) SSW_HIP_TRY(hipStreamSynchronize(fb->stream));
+        SSW_TRY(fb_fit_wg_collect(fb, P, w_inout, out_iters, out_evals, out_final_loss));
         const int *counts = reinterpret_cast<const int *>(fb->flag_host) + 4;
-        fb->last_iters = counts[0];
-        fb->last_evals = counts[1];
-        fb->last_fit_on_device = true;
-        if (counts[2] != 0) {
-            set_error("feedback: loss diverged -- regression training failed with a nan");
-            return SSW_ERR_NUMERIC;  // logistic_regression.py:398-401
-        }
-        for (int i = 0; i < P; ++i) {
-            if (!std::isfinite(fb->out_host[1 + i])) {
-                set_error("feedback: weights diverged");
-                return SSW_ERR_NUMERIC;
-            }
-            w_inout[i] = fb->out_host[1 + i];
-        }
         if (getenv("SSW_FB_TIMING"))
             fprintf(stderr, "fit (one launch): n=%lld iters=%d evals=%d total %.1f us, prepare %.1f; kernel %.1f us = logits %.1f + "
                     "labels %.1f + gradient %.1f + final %.1f + driver %.1f (%.0f MHz)\n", (long long)fb->n, counts[0], counts[1],
@@ -2776,9 +2850,6 @@ ssw_status ssw_fb_fit(ssw_fb *fb, const ssw_fb_objective *obj, float *w_inout, i
         if (getenv("SSW_FB_TIMING") && counts[11])
             fprintf(stderr, "   one pass (SSW_FIT_STAMPS build), cycles per evaluation: %.0f, %.0f, %.0f\n",
                     16.0 * counts[11] / counts[1], 16.0 * counts[12] / counts[1], 16.0 * counts[13] / counts[1]);
-        if (out_iters) *out_iters = counts[0];
-        if (out_evals) *out_evals = counts[1];
-        if (out_final_loss) *out_final_loss = (float)fb->loss_host[0];
         return SSW_OK;
     }
     Vec x(E.P, 0.f);
@@ -2807,6 +2878,137 @@ ssw_status ssw_fb_fit(ssw_fb *fb, const ssw_fb_objective *obj, float *w_inout, i
     if (out_final_loss) *out_final_loss = (float)loss;
     return SSW_OK;
 }
+
+// ---- S sessions' fits in one launch (k_fb_fit_wg_batch) ----------------------------------------
+static ssw_status fb_batch_reserve(ssw_fb *fb, int nfit) {
+    if (nfit <= fb->batch_cap) return SSW_OK;
+    SSW_HIP_TRY(hipStreamSynchronize(fb->stream));
+    (void)hipFree(fb->batch_tab);
+    (void)hipFree(fb->batch_w);
+    fb->batch_tab = nullptr;
+    fb->batch_w = nullptr;
+    fb->batch_cap = 0;
+    int cap = 16;
+    while (cap < nfit) cap <<= 1;
+    SSW_HIP_TRY(hipMalloc((void **)&fb->batch_tab, (size_t)cap * sizeof(FitWgArgs)));
+    SSW_HIP_TRY(hipMalloc((void **)&fb->batch_w, (size_t)cap * (fb->dim + 1) * sizeof(float)));
+    fb->batch_cap = cap;
+    return SSW_OK;
+}
+
+ssw_status ssw_fb_fit_batch(ssw_fb *const *fbs, const ssw_fb_objective *objs, int32_t nfit, float *W_inout,
+                            const int32_t *max_iter, const float *lr, int32_t *out_iters, int32_t *out_evals,
+                            float *out_final_loss, int32_t *out_status) {
+    // ---- refusals, before anything is queued
+    SSW_REQUIRE(nfit >= 1, "nfit < 1");
+    SSW_REQUIRE(fbs && objs && W_inout && max_iter && lr && out_status, "NULL argument");
+    for (int s = 0; s < nfit; ++s) {
+        SSW_REQUIRE(fbs[s] != nullptr, "slot %d: NULL handle", s);
+        for (int t = 0; t < s; ++t) SSW_REQUIRE(fbs[t] != fbs[s], "slots %d and %d share one handle", t, s);
+        SSW_REQUIRE(fbs[s]->device == fbs[0]->device, "slot %d: device %d, slot 0 is on device %d", s, fbs[s]->device,
+                    fbs[0]->device);
+        SSW_REQUIRE(fbs[s]->dim == fbs[0]->dim, "slot %d: dim %d, slot 0 has dim %d", s, fbs[s]->dim, fbs[0]->dim);
+        SSW_REQUIRE(max_iter[s] >= 1, "slot %d: max_iter < 1", s);
+    }
+    const int dim = fbs[0]->dim, Pd = dim + 1;
+    for (int s = 0; s < nfit; ++s) {
+        const int P = fb_fit_params(fbs[s], &objs[s]);
+        for (int i = 0; i < P; ++i)
+            SSW_REQUIRE(std::isfinite(W_inout[(size_t)s * Pd + i]), "slot %d: initial weight %d is not finite", s, i);
+    }
+    DeviceGuard guard(fbs[0]->device);
+    std::vector<int> slots;  // the slots one workgroup each serves; the others go through ssw_fb_fit afterwards
+    for (int s = 0; s < nfit; ++s) {
+        fbs[s]->batch_error.clear();
+        out_status[s] = SSW_OK;
+        if (fb_fit_wg_eligible(fbs[s], &objs[s])) slots.push_back(s);
+    }
+    const int nwg = (int)slots.size();
+    if (nwg > 0) {
+        ssw_fb *lead = fbs[slots[0]];  // its stream takes the launch, its tables the arguments
+        // every engine queues its own uploads (fb_prepare: the coefficients; before it the rows, targets and query of
+        // its set_* calls) on its own stream, without a wait
+        std::vector<FbObjDev> dev((size_t)nwg);
+        std::vector<float> pw((size_t)nwg);
+        std::vector<char> active((size_t)nwg);
+        for (int b = 0; b < nwg; ++b) {
+            ssw_fb *fb = fbs[slots[b]];
+            bool pa = false;
+            SSW_TRY(fb_prepare(fb, &objs[slots[b]], &dev[b], &pw[b], &pa));
+            active[b] = pa;
+            fb->last_evals = 0;
+            fb->last_fit_on_device = false;
+        }
+        SSW_TRY(fb_batch_reserve(lead, nwg));
+        std::vector<FitWgArgs> tab((size_t)nwg);
+        std::vector<float> w0((size_t)nwg * Pd, 0.f);
+        size_t lds = 0;
+        for (int b = 0; b < nwg; ++b) {
+            const int s = slots[b];
+            fb_fit_wg_fill(fbs[s], &objs[s], dev[b], pw[b], active[b] != 0, max_iter[s], lr[s], &tab[b]);
+            tab[b].w0_or_null = lead->batch_w + (size_t)b * Pd;
+            memcpy(&w0[(size_t)b * Pd], &W_inout[(size_t)s * Pd], (size_t)tab[b].P * sizeof(float));
+            lds = std::max(lds, fit_wg_lds_bytes(dim, tab[b].onepass != 0));
+        }
+        SSW_TRY(lead->batch_tab_stage.push(lead->batch_tab, tab.data(), tab.size() * sizeof(FitWgArgs), lead->stream));
+        SSW_TRY(lead->batch_w_stage.push(lead->batch_w, w0.data(), w0.size() * sizeof(float), lead->stream));
+        for (int b = 1; b < nwg; ++b) {  // the launch is ordered behind every slot's uploads
+            ssw_fb *fb = fbs[slots[b]];
+            if (!fb->batch_ev) SSW_HIP_TRY(hipEventCreateWithFlags(&fb->batch_ev, hipEventDisableTiming));
+            SSW_HIP_TRY(hipEventRecord(fb->batch_ev, fb->stream));
+            SSW_HIP_TRY(hipStreamWaitEvent(lead->stream, fb->batch_ev, 0));
+        }
+        auto kern = dim + 1 <= 9 * 64 ? k_fb_fit_wg_batch<9> : k_fb_fit_wg_batch<16>;
+        SSW_TRY(fb_fit_wg_attr(reinterpret_cast<const void *>(kern), lead->device, dim, true));
+        hipLaunchKernelGGL(kern, dim3(nwg), dim3(1024), lds, lead->stream, (const FitWgArgs *)lead->batch_tab);
+        SSW_HIP_TRY(hipGetLastError());
+        for (int b = 0; b < nwg; ++b) {
+            if (!fb_fit_wg_spin(fbs[slots[b]], tab[b].seqno)) {
+                SSW_HIP_TRY(hipStreamSynchronize(lead->stream));  // every workgroup has published
+                break;
+            }
+        }
+        std::vector<float> row((size_t)Pd);
+        for (int b = 0; b < nwg; ++b) {
+            const int s = slots[b];
+            float *Ws = &W_inout[(size_t)s * Pd];
+            memcpy(row.data(), Ws, (size_t)Pd * sizeof(float));
+            const ssw_status st = fb_fit_wg_collect(fbs[s], tab[b].P, row.data(), out_iters ? &out_iters[s] : nullptr,
+                                                    out_evals ? &out_evals[s] : nullptr,
+                                                    out_final_loss ? &out_final_loss[s] : nullptr);
+            if (st == SSW_OK) {
+                memcpy(Ws, row.data(), (size_t)Pd * sizeof(float));
+            } else {  // SSW_ERR_NUMERIC: this slot's row stays as it came, the others are not concerned
+                out_status[s] = st;
+                fbs[s]->batch_error = ssw_last_error();
+            }
+        }
+    }
+    // ---- the slots the single call drives from the host: through it, one after another
+    size_t next_wg = 0;
+    std::vector<float> row((size_t)Pd);
+    for (int s = 0; s < nfit; ++s) {
+        if (next_wg < slots.size() && slots[next_wg] == s) {
+            ++next_wg;
+            continue;
+        }
+        float *Ws = &W_inout[(size_t)s * Pd];
+        memcpy(row.data(), Ws, (size_t)Pd * sizeof(float));
+        const ssw_status st = ssw_fb_fit(fbs[s], &objs[s], row.data(), max_iter[s], lr[s], out_iters ? &out_iters[s] : nullptr,
+                                         out_evals ? &out_evals[s] : nullptr, out_final_loss ? &out_final_loss[s] : nullptr);
+        if (st == SSW_OK) {
+            memcpy(Ws, row.data(), (size_t)Pd * sizeof(float));
+        } else if (st == SSW_ERR_NUMERIC) {
+            out_status[s] = st;
+            fbs[s]->batch_error = ssw_last_error();
+        } else {
+            return st;
+        }
+    }
+    return SSW_OK;
+}
+
+const char *ssw_fb_batch_error(const ssw_fb *fb) { return fb ? fb->batch_error.c_str() : ""; }
 
 // ---- MultiRegModule (multi_reg_neg loop): two-output objective -------------------------------
 ssw_status ssw_fb_set_targets2(ssw_fb *fb, const float *y2_host, const float *sample_weight_or_null) {

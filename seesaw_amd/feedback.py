@@ -152,6 +152,53 @@ class FeedbackEngine:
         return w, {"n_iter": iters.value, "func_evals": evals.value, "loss": float(loss.value),
                    "on_device": bool(on_dev.value)}
 
+    @staticmethod
+    def _fit_batch_raw(engines, objs, W, max_iters, lrs):
+        """ssw_fb_fit_batch on W [nfit, dim + 1] f32 in place; returns (iters, evals, loss, status), one entry a slot"""
+        nfit = len(engines)
+        assert W.dtype == np.float32 and W.flags.c_contiguous
+        handles = (ctypes.c_void_p * max(nfit, 1))(*[e._h for e in engines])
+        obj_arr = (FbObjective * max(nfit, 1))(*objs)
+        mi = np.ascontiguousarray(max_iters, dtype=np.int32).reshape(-1)
+        lr = np.ascontiguousarray(lrs, dtype=np.float32).reshape(-1)
+        iters, evals = np.zeros(max(nfit, 1), np.int32), np.zeros(max(nfit, 1), np.int32)
+        loss, status = np.zeros(max(nfit, 1), np.float32), np.zeros(max(nfit, 1), np.int32)
+        as_f32 = lambda a: a.ctypes.data_as(_lib.c_f32_p)  # noqa: E731
+        as_i32 = lambda a: a.ctypes.data_as(_lib.c_i32_p)  # noqa: E731
+        _lib.call("ssw_fb_fit_batch", handles, ctypes.cast(obj_arr, ctypes.c_void_p), nfit, as_f32(W), as_i32(mi),
+                  as_f32(lr), as_i32(iters), as_i32(evals), as_f32(loss), as_i32(status))
+        return iters, evals, loss, status
+
+    @staticmethod
+    def fit_batch(engines, objs, w0s, max_iters, lrs):
+        """`[e.fit(o, w0, max_iter=m, lr=l) for e, o, w0, m, l in zip(...)]` in one launch and one host wait
+        (ssw_fb_fit_batch: a workgroup per engine, each on its own engine's buffers), entry by entry the bits of the
+        single calls.  Returns one entry per slot: `(w, info)`, or -- for a slot whose loss or weights diverged -- the
+        SeesawHipError `fit` would have raised (the other slots have their results).  Engines must be distinct and of
+        one dim and device; a slot `fit` would drive from the host is run through it after the launch."""
+        engines, objs = list(engines), list(objs)
+        nfit = len(engines)
+        if not (len(objs) == len(w0s) == len(max_iters) == len(lrs) == nfit):
+            raise ValueError("fit_batch: engines, objs, w0s, max_iters and lrs must have one entry per slot")
+        dim = max((e.dim for e in engines), default=0)  # engines of unequal dim are refused by the library, by name
+        W = np.zeros((max(nfit, 1), dim + 1), dtype=np.float32)
+        for s, w0 in enumerate(w0s):
+            w0 = np.asarray(w0, dtype=np.float32).reshape(-1)
+            W[s, :w0.shape[0]] = w0
+        iters, evals, loss, status = FeedbackEngine._fit_batch_raw(engines, objs, W, max_iters, lrs)
+        out = []
+        for s, (eng, obj) in enumerate(zip(engines, objs)):
+            if status[s] != _lib.SSW_OK:
+                msg = _lib.load().ssw_fb_batch_error(eng._h)
+                out.append(_lib.SeesawHipError(int(status[s]), msg.decode("utf-8", "replace") if msg else ""))
+                continue
+            P = eng.dim + (1 if (obj.kind == _lib.SSW_FB_LOGREG and obj.fit_intercept) else 0)
+            on_dev = ctypes.c_int32(0)
+            _lib.call("ssw_fb_last_fit_on_device", eng._h, ctypes.byref(on_dev))
+            out.append((W[s, :P].copy(), {"n_iter": int(iters[s]), "func_evals": int(evals[s]), "loss": float(loss[s]),
+                                          "on_device": bool(on_dev.value)}))
+        return out
+
     # ---- two linear outputs (MultiRegModule, loops/multi_reg_neg.py) ---------------------
     def set_targets2(self, y2: np.ndarray, sample_weight: Optional[np.ndarray] = None):
         y2 = np.ascontiguousarray(np.asarray(y2), dtype=np.float32)

@@ -63,9 +63,8 @@ class RegModule:
     def forward(self, X, y=None):
         return np.asarray(X, dtype=np.float32) @ self.weight
 
-    def fit(self, X, y, matchdf, index=None, rows=None):
-        """X [n, dim] labelled tile vectors (or index + rows to gather them on the device),
-        y [n] in {0,1}, matchdf with a `dbidx` column (sample weight = 1 / #vectors of the image)."""
+    def _stage(self, X, y, matchdf, index=None, rows=None):
+        """the data and targets of one fit onto this module's engine (queued on the engine's stream, no wait)"""
         n = len(y)
         if n > 0:
             # 1 / (vectors of the same image): matchdf.groupby('dbidx').size() merged back (multi_reg.py:163-165)
@@ -85,14 +84,44 @@ class RegModule:
         else:  # regularisers only (multi_reg.py:171-172 `dl = None`)
             self._engine.set_data(np.zeros((0, self.dim), np.float32), center=False)
             self._engine.set_targets(np.zeros(0))
-        try:
-            w, info = self._engine.fit(self._objective(), self.weight, max_iter=self.max_iter, lr=self.lr)
-        except _lib.SeesawHipError as e:
-            raise AssertionError(f"regression training failed: {e}") from e
+
+    def _finish(self, w, info):
+        """take a fit's result; `w` may be the SeesawHipError of a fit that diverged"""
+        if isinstance(w, _lib.SeesawHipError):
+            raise AssertionError(f"regression training failed: {w}") from w
         assert not np.isnan(w).any()
         self.weight = w
         self.info_ = info
         return [{"k": "total_loss", "loss": info["loss"]}]
+
+    def fit(self, X, y, matchdf, index=None, rows=None):
+        """X [n, dim] labelled tile vectors (or index + rows to gather them on the device),
+        y [n] in {0,1}, matchdf with a `dbidx` column (sample weight = 1 / #vectors of the image)."""
+        self._stage(X, y, matchdf, index=index, rows=rows)
+        try:
+            w, info = self._engine.fit(self._objective(), self.weight, max_iter=self.max_iter, lr=self.lr)
+        except _lib.SeesawHipError as e:
+            w, info = e, None
+        return self._finish(w, info)
+
+    @staticmethod
+    def fit_batch(models, staged):
+        """`[m.fit(*a) for m, a in zip(models, staged)]` with ONE engine call (FeedbackEngine.fit_batch): every model
+        stages its `(X, y, matchdf, index, rows)` on its own engine, the fits run side by side, every model takes its
+        result.  Returns one entry per model: what `fit` returns, or the AssertionError it would have raised -- raising
+        is the caller's, after the other models have their weights."""
+        models = list(models)
+        for m, args in zip(models, staged):
+            m._stage(*args)
+        res = FeedbackEngine.fit_batch([m._engine for m in models], [m._objective() for m in models],
+                                       [m.weight for m in models], [m.max_iter for m in models], [m.lr for m in models])
+        out = []
+        for m, r in zip(models, res):
+            try:
+                out.append(m._finish(r, None) if isinstance(r, _lib.SeesawHipError) else m._finish(*r))
+            except AssertionError as e:
+                out.append(e)
+        return out
 
 
 class MultiReg(PointBased):
@@ -113,7 +142,8 @@ class MultiReg(PointBased):
         else:
             self.curr_vec = self.curr_qvec
 
-    def refine(self, change=None):
+    def _labelled(self):
+        """rows of the labelled tiles, their targets, and the image of each (getXy()'s columns)"""
         arrays = getattr(self.q, "_matched_arrays", None)
         if arrays is not None and hasattr(self.q.index, "_row_dbidx"):  # getXy()'s columns without the frame
             rows, miou = arrays()
@@ -123,17 +153,46 @@ class MultiReg(PointBased):
             matchdf = self.q.getXy()
             rows = matchdf.index.values
             y = matchdf.ys.values
+        return rows, y, matchdf
+
+    def _model(self):
         assert self.curr_qvec is not None
         o = self.options
-        model = RegModule(dim=self.q.index.vectors.shape[1], xlx_matrix=self.xlx_matrix, qvec=self.curr_qvec,
-                          label_loss_type=o["label_loss_type"], rank_loss_margin=o["rank_loss_margin"],
-                          reg_data_lambda=o["reg_data_lambda"], reg_norm_lambda=o["reg_norm_lambda"],
-                          use_qvec_norm=o["use_qvec_norm"], reg_query_lambda=o["reg_query_lambda"],
-                          verbose=o["verbose"], max_iter=int(o["max_iter"]), pos_weight=o["pos_weight"], lr=o["lr"],
-                          engine=self._engine)
+        return RegModule(dim=self.q.index.vectors.shape[1], xlx_matrix=self.xlx_matrix, qvec=self.curr_qvec,
+                         label_loss_type=o["label_loss_type"], rank_loss_margin=o["rank_loss_margin"],
+                         reg_data_lambda=o["reg_data_lambda"], reg_norm_lambda=o["reg_norm_lambda"],
+                         use_qvec_norm=o["use_qvec_norm"], reg_query_lambda=o["reg_query_lambda"],
+                         verbose=o["verbose"], max_iter=int(o["max_iter"]), pos_weight=o["pos_weight"], lr=o["lr"],
+                         engine=self._engine)
+
+    def _fit_args(self):
+        rows, y, matchdf = self._labelled()
         dev = getattr(self.q.index, "_dev", None)
         if dev is not None:  # labelled rows are gathered out of the resident index, no upload
-            model.fit(None, y, matchdf, index=dev, rows=rows)
-        else:
-            model.fit(self.q.index.vectors[rows], y, matchdf)
+            return (None, y, matchdf, dev, rows)
+        return (self.q.index.vectors[rows], y, matchdf, None, None)
+
+    def refine(self, change=None):
+        args = self._fit_args()
+        model = self._model()
+        model.fit(*args)
         self.curr_vec = model.get_coeff()
+
+    @classmethod
+    def refine_batch(cls, loops):
+        """`for l in loops: l.refine()` with one batched fit: every loop stages on its own engine, one
+        RegModule.fit_batch follows, every `curr_vec` is set.  A loop whose fit raised surfaces its AssertionError
+        after the other loops have got their vectors."""
+        loops = list(loops)
+        if not loops:
+            return
+        staged = [l._fit_args() for l in loops]
+        models = [l._model() for l in loops]
+        failed = None
+        for l, m, r in zip(loops, models, RegModule.fit_batch(models, staged)):
+            if isinstance(r, AssertionError):
+                failed = failed or r
+                continue
+            l.curr_vec = m.get_coeff()
+        if failed is not None:
+            raise failed

@@ -246,6 +246,130 @@ class Session:
         self._last_change = [(idx, 1 if idx in delta_accepted else 0) for idx in delta_seen.union(delta_accepted)]
 
 
+class SessionGroup:
+    """Several sessions driven in lock step: `next()` then `refine()` for all of them, with the work the sessions
+    have in common done once.  The reference spreads sessions over Ray actors (`parallel_run`, `make_bench_actors`);
+    here one process serves them, so a round's two halves are batched instead:
+
+    * `next()`: the sessions whose loop would answer through `LoopBase._next_batch_curr_vec` (a `PointBased` loop, or
+      any loop whose start policy has not fired) and that share one index object and the same `batch_size`,
+      `shortlist_size`, `agg_method` and `aug_larger` are served by ONE `index.query_batch` -- one pass over the rows;
+      every other session calls its own `next()`.
+    * `refine()`: every session's start-policy gate runs as in `LoopBase.refine_external`; the started `MultiReg`
+      loops go through ONE `MultiReg.refine_batch` -- one launch, one host wait; every other loop through its own
+      `refine_external`.
+
+    Every session ends each call in the state its own `next()` / `refine()` would have left: `returned`, `timing`
+    (the shared call's time for each member), `acc_indices`, `acc_activations`, the log, `curr_vec` -- bit for bit.
+    `prune` is passed on to `query_batch`."""
+
+    def __init__(self, sessions, prune: bool = False):
+        self.sessions = list(sessions)
+        self.prune = bool(prune)
+
+    # ---- which sessions go together ---------------------------------------------------------------------------
+    @staticmethod
+    def batch_vector(loop):
+        """the vector `loop.next_batch_external()` would hand to `_next_batch_curr_vec`, or None when the loop
+        answers another way"""
+        from .loops.loop_base import LoopBase
+        from .loops.point_based import PointBased
+        cls = type(loop)
+        if cls.next_batch_external is not LoopBase.next_batch_external or \
+                cls._next_batch_curr_vec is not LoopBase._next_batch_curr_vec:
+            return None
+        if not loop.started:
+            return loop.curr_qvec
+        if isinstance(loop, PointBased) and cls.next_batch is PointBased.next_batch:
+            return loop.curr_vec
+        return None
+
+    def query_groups(self):
+        """[(session positions, ...)]: the positions that share one `query_batch`, in session order; a session that
+        answers on its own is a group of one"""
+        groups, by_key = [], {}
+        for i, s in enumerate(self.sessions):
+            p = s.loop.params
+            if self.batch_vector(s.loop) is None:
+                groups.append([i])
+                continue
+            key = (id(s.loop.q.index), p.batch_size, p.shortlist_size, p.agg_method, p.aug_larger)
+            if key not in by_key:
+                by_key[key] = []
+                groups.append(by_key[key])
+            by_key[key].append(i)
+        return [tuple(g) for g in groups]
+
+    def fit_groups(self):
+        """([positions that refine through one MultiReg.refine_batch, ...], [positions that refine on their own]),
+        for loops that have started; the gate is `refine()`'s"""
+        from .loops.loop_base import LoopBase
+        from .loops.multi_reg import MultiReg
+        batched, alone = {}, []
+        for i, s in enumerate(self.sessions):
+            loop = s.loop
+            cls = type(loop)
+            if isinstance(loop, MultiReg) and cls.refine is MultiReg.refine and \
+                    cls.refine_external is LoopBase.refine_external and loop.started:
+                batched.setdefault((loop._engine.dim, loop._engine.device), []).append(i)
+            else:
+                alone.append(i)
+        return [tuple(g) for g in batched.values()], alone
+
+    # ---- the two halves of a round ----------------------------------------------------------------------------
+    def next(self):
+        """`[s.next() for s in sessions]`"""
+        out = [None] * len(self.sessions)
+        for group in self.query_groups():
+            if len(group) == 1:
+                out[group[0]] = self.sessions[group[0]].next()
+                continue
+            members = [self.sessions[i] for i in group]
+            vectors = []
+            for s in members:
+                s._log("next.start")
+                print("start met. next batch from custom method..." if s.loop.started
+                      else "start not yet met. next batch using default...")
+                vec = self.batch_vector(s.loop)
+                assert not np.isnan(vec).any(), f"NaN in query vector {vec=}"
+                vectors.append(vec)
+            start = time.time()
+            p = members[0].loop.params
+            results = members[0].loop.q.index.query_batch(
+                topk=p.batch_size, vectors=vectors, excludes=[s.loop.q.returned for s in members], prune=self.prune,
+                shortlist_size=p.shortlist_size, agg_method=p.agg_method, aug_larger=p.aug_larger)
+            elapsed = time.time() - start
+            for i, s, r in zip(group, members, results):
+                s.loop.q.returned.update(np.asarray(r["dbidxs"], dtype=np.int64))
+                s.timing.append(elapsed)
+                s.acc_indices.append(r["dbidxs"])
+                s.acc_activations.append(r["activations"])
+                s._log("next.end")
+                out[i] = r["dbidxs"]
+        return out
+
+    def refine(self):
+        """`for s in sessions: s.refine()`"""
+        from .loops.multi_reg import MultiReg
+        for s in self.sessions:  # the gate of LoopBase.refine_external
+            if not s.loop.started and isinstance(s.loop, MultiReg):
+                s.loop.started = s.loop._start_condition()
+        batched, alone = self.fit_groups()
+        for group in batched:
+            members = [self.sessions[i] for i in group]
+            if len(members) == 1:
+                alone.append(group[0])
+                continue
+            for s in members:
+                s._log("refine.start")
+                print("start condition met... refinining custom method...")
+            MultiReg.refine_batch([s.loop for s in members])
+            for s in members:
+                s._log("refine.end")
+        for i in sorted(alone):
+            self.sessions[i].refine()
+
+
 def make_session(gdm, p: SessionParams, b: BenchParams = None):
     ds = gdm.get_dataset(p.index_spec.d_name)
     if p.index_spec.c_name is not None:
