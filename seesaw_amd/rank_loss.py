@@ -2,7 +2,7 @@
 
 `ref_pairwise_rank_loss` / `ref_pairwise_logistic_loss` with aggregate='sum' and
 `ref_pairwise_rank_loss_gradient` go through ssw_rank_pairwise -- the very kernel the MultiReg fit evaluates
-every closure call (csrc/feedback.hip, k_fb_pairwise)."""
+every closure call (csrc/feedback_eval.hip, k_fb_pairwise)."""
 from __future__ import annotations
 
 import ctypes
