@@ -675,6 +675,27 @@ ssw_status ssw_fb_lossgrad2(ssw_fb *fb, const float *W_host, float reg_norm_lamb
                             float *out_loss, float *out_grad, float *out_parts5_or_null);
 ssw_status ssw_fb_fit2(ssw_fb *fb, float *W_inout, float reg_norm_lambda, float reg_query_lambda, int32_t max_iter,
                        float lr, int32_t *out_iters, int32_t *out_evals, float *out_final_loss);
+/* ssw_fb_lossgrad2 with the whole evaluation on the device (opt-in): replaces one call of MultiRegModule._step
+ * (seesaw/loops/multi_reg_module.py:64-128) including F.normalize, its chain rule and the two regularisers, which
+ * ssw_fb_lossgrad2 forms on the host.  Same outputs; the operation order is ssw_fb_lossgrad2's, the values differ from
+ * it only where the device library's logf / coshf / sinhf differ from the host's. */
+ssw_status ssw_fb_lossgrad2_dev(ssw_fb *fb, const float *W_host, float reg_norm_lambda, float reg_query_lambda,
+                                float *out_loss, float *out_grad, float *out_parts5_or_null);
+/* ssw_fb_fit2 over that device evaluation for nfit engines at once (opt-in; nfit = 1 is the single fit): the call
+ * site it replaces nfit times is the LBFGS of seesaw/loops/multi_reg_module.py:142 stepped at basic_trainer.py:59-63
+ * (opt.step(closure)), once per multi_reg_neg session of a group that refines in lock step.  Slot s fits fbs[s] from
+ * row s of W_inout ([nfit][2 dim]) with reg_norm_lambda[s], reg_query_lambda[s], max_iter[s], lr[s].  Every slot of
+ * 0 to 1024 rows gets one workgroup of ONE launch (k_fb_fit2_wg_batch; 0 rows: the regularisers alone); a larger set,
+ * or env SSW_FB_HOST_DRIVER, is driven from the host afterwards, one device evaluation and one wait at a time.  Both
+ * drivers walk the same path bit for bit (weights, iterations, evaluations, loss); ssw_fb_last_fit_on_device tells per
+ * handle.  Stream and event ordering between the engines, the per-slot SSW_ERR_NUMERIC (row untouched, message in
+ * ssw_fb_batch_error, the call returns SSW_OK) and the optional outputs are ssw_fb_fit_batch's.
+ * Refused before anything is queued (SSW_ERR_INVALID): nfit < 1, a NULL or repeated handle, handles of different
+ * device or dim, 2 dim > 1024, max_iter < 1, a non-finite start weight, a slot with rows but without
+ * ssw_fb_set_targets2, a slot without ssw_fb_set_query. */
+ssw_status ssw_fb_fit2_batch(ssw_fb *const *fbs, int32_t nfit, float *W_inout, const float *reg_norm_lambda,
+                             const float *reg_query_lambda, const int32_t *max_iter, const float *lr,
+                             int32_t *out_iters, int32_t *out_evals, float *out_final_loss, int32_t *out_status);
 
 ssw_status ssw_fb_create(int32_t device, int32_t dim, ssw_fb **out);
 ssw_status ssw_fb_destroy(ssw_fb *fb);

@@ -120,6 +120,8 @@ _SIGNATURES = {
     "ssw_fb_set_targets2": (c_i32, [c_void_p, c_void_p, c_void_p]),
     "ssw_fb_lossgrad2": (c_i32, [c_void_p, c_void_p, ctypes.c_float, ctypes.c_float, c_void_p, c_void_p, c_void_p]),
     "ssw_fb_fit2": (c_i32, [c_void_p, c_void_p, ctypes.c_float, ctypes.c_float, c_i32, ctypes.c_float, c_void_p, c_void_p, c_void_p]),
+    "ssw_fb_lossgrad2_dev": (c_i32, [c_void_p, c_void_p, ctypes.c_float, ctypes.c_float, c_void_p, c_void_p, c_void_p]),
+    "ssw_fb_fit2_batch": (c_i32, [c_void_pp, c_i32, c_f32_p, c_f32_p, c_f32_p, c_i32_p, c_f32_p, c_i32_p, c_i32_p, c_f32_p, c_i32_p]),
     "ssw_fb_get_mean": (c_i32, [c_void_p, c_void_p]),
     "ssw_fb_lossgrad": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ssw_fb_scores": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p]),

@@ -27,6 +27,9 @@ struct FitWgArgs {
     int max_iter;
     float lr;
     ssw::FbObjDev obj;
+    // k_fb_fit2_wg (two outputs): y = two target planes `plane2` floats apart, coef = the sample weights, dim2 = the
+    // rows' width; dim = 2 dim2 - 1 and P = 2 dim2 are what the driver step sees (2 dim2 parameters, no unused slot)
+    int dim2, plane2;
 };
 
 struct ssw_fb {
@@ -45,6 +48,7 @@ struct ssw_fb {
     // two-output objective (ssw_fb_*2): planes of cap floats / [2][nslabs(cap)][dim] partial gradients
     float *y2 = nullptr, *sw2 = nullptr, *z2 = nullptr, *r2 = nullptr, *itemv = nullptr, *itemh = nullptr;
     float *partial2 = nullptr, *nw2 = nullptr;
+    float *w2 = nullptr;       // [2 dim + 2] raw weights of a device evaluation, then the two row norms (fb_eval2_dev)
     float *out2_host = nullptr, *out2_host_dev = nullptr;  // mapped pinned [2 + 2 dim]
     int64_t cap2 = 0;
     bool has_targets2 = false;
@@ -96,6 +100,7 @@ struct Evaluator {
     bool pairwise_active;
     int P;
     bool two = false;            // the two-output objective (fb_eval2) instead of fb_eval
+    bool two_dev = false;        // ... evaluated entirely on the device (fb_eval2_dev)
     float l_norm2 = 0.f, l_query2 = 0.f;
     ssw_status status = SSW_OK;
     bool eval(const std::vector<float> &x, double t, const std::vector<float> &d, double *f, std::vector<float> *g);
@@ -112,6 +117,8 @@ ssw_status fb_center(ssw_fb *fb, int center);
 ssw_status fb_prepare(ssw_fb *fb, const ssw_fb_objective *o, FbObjDev *dev, float *pw_out, bool *pairwise_active);
 ssw_status fb_eval(ssw_fb *fb, const ssw_fb_objective *o, const FbObjDev &dev, float pw, bool pairwise_active, int P);
 ssw_status fb_eval2(ssw_fb *fb, float l_norm, float l_query, float *parts5);
+ssw_status fb_eval2_dev(ssw_fb *fb, float l_norm, float l_query, float *parts5);  // the same with no host arithmetic
+ssw_status fb2_dev_reserve(ssw_fb *fb);
 void launch_fb_logits(ssw_fb *fb, int has_bias);  // k_fb_logits: fb->z = fb->X fb->w (+ b)
 void launch_fb_pairwise(int logistic, const float *z, const float *y, const float *coef, float margin, int n,
                         double *item_loss, float *r, hipStream_t stream);
@@ -127,6 +134,9 @@ bool fb_fit_wg_spin(const ssw_fb *fb, unsigned want);
 ssw_status fb_fit_wg_collect(ssw_fb *fb, int P, float *w_inout, int32_t *out_iters, int32_t *out_evals,
                              float *out_final_loss);
 ssw_status fb_batch_reserve(ssw_fb *fb, int nfit);
+bool fb_fit2_wg_eligible(const ssw_fb *fb);
+void fb_fit2_wg_fill(ssw_fb *fb, float l_norm, float l_query, int max_iter, float lr, const float *w0_dev, FitWgArgs *out);
+ssw_status fb_fit2_wg_launch(ssw_fb *lead, const FitWgArgs *tab_host, int nwg);  // nwg = 1: tab_host[0] by value
 
 // feedback_lbfgs.hip: torch.optim.LBFGS.step(closure) driven from the host
 extern double g_fit_eval_s;  // diagnostic (SSW_FB_TIMING): seconds of the last fit spent inside closure evaluations

@@ -11,6 +11,8 @@
 //                    network for the host's dot products (vdot of feedback_lbfgs.hip  |  fit_driver_step)
 //   last step        FbFinalLds + fb_final_body     (k_fb_final  |  fit_eval_final)
 //   line search      cubic_interpolate_dev          (strong_wolfe  |  fit_driver_step)
+//   two outputs      fb2_row_terms, fb2_item_tree, fb2_norm_body, fb2_tail_body + Fb2Lds
+//                    (k_fb2_logits_elem, k_fb2_reduce, k_fb2_norm, k_fb2_final_dev  |  fit2_eval_*)
 // and the plain data those take (FbW, FbObjDev, the slab and argument-segment sizes).  A change here changes both
 // drivers at once; an expression of this kind written a second time somewhere else breaks the contract.  Every
 // translation unit that includes this file is compiled with -ffp-contract=off (Makefile, NOCONTRACT): the host and the
@@ -395,6 +397,158 @@ __device__ __forceinline__ void fb_final_body(float g, const float wc, const dou
             parts[1] = (float)p_data;
             parts[2] = (float)p_query;
             parts[3] = (float)data_loss;
+        }
+    }
+}
+
+// ---- the two-output objective, one closure evaluation of MultiRegModule._step entirely on the device
+// (seesaw/loops/multi_reg_module.py:64-128).  Two drivers take it: the host-driven device evaluation (k_fb2_norm,
+// k_fb2_logits_elem, k_fb_grad, k_fb2_final_dev of feedback_eval.hip) and the one-launch fit (k_fb_fit2_wg,
+// feedback_fit_wg.hip).  The data part is fb2_row_terms per row, k_fb_grad's slab chains and fb2_item_tree; the
+// O(dim) part is fb2_norm_body before the logits and fb2_tail_body after the gradient.  The O(dim) part keeps the
+// operation order of fb_eval2's host tail (sums over k sequential in f32, the total ((labels + loss_norm) + lq0) + lq1),
+// so it differs from ssw_fb_fit2 only where the device library's logf / coshf / sinhf differ from the host's.
+struct Fb2Lds {     // all in LDS
+    float *W;       // [2 dim] the raw weights of this evaluation
+    float *nw;      // [2 dim] rows of W over max(|row|, 1e-12)  (F.normalize)
+    float *g;       // [2 dim] d labels / d nw: the slab sums of both gradient planes
+    float *qh;      // [dim]   unit query
+    float *sc;      // [8]     |W_0|, |W_1|, nw_0.q, nw_1.q, nw_0.G_0, nw_1.G_1
+    float *rv, *rh; // [1024]  fb2_item_tree's scratch
+};
+
+// One row's label terms from its two logits (a: target, b: confusion class), all f32 as in the reference: the
+// vertical BCE pair, the horizontal CE where the row carries a label, d loss / d logit, times the sample weight
+__device__ __forceinline__ void fb2_row_terms(float a, float b, float y0, float y1, float s, float *r0, float *r1,
+                                              float *item_v, float *item_h) {
+    // binary_cross_entropy_with_logits: (1 - y) z - log_sigmoid(z), log_sigmoid(z) = min(z, 0) - log1p(exp(-|z|))
+    const float ls0 = fminf(a, 0.f) - log1pf(expf(-fabsf(a))), ls1 = fminf(b, 0.f) - log1pf(expf(-fabsf(b)));
+    const float vert = ((1.f - y0) * a - ls0) + ((1.f - y1) * b - ls1);
+    const float sg0 = 1.f / (1.f + expf(-a)), sg1 = 1.f / (1.f + expf(-b));
+    float g0 = sg0 - y0, g1 = sg1 - y1, hor = 0.f;
+    const float near = y0 + y1;
+    if (near > 0.f) {  // cross_entropy with probability targets on the rows that carry any label
+        const float m = fmaxf(a, b);
+        const float lse = m + logf(expf(a - m) + expf(b - m));
+        hor = -(y0 * (a - lse) + y1 * (b - lse));
+        g0 += near * expf(a - lse) - y0;
+        g1 += near * expf(b - lse) - y1;
+    }
+    *r0 = s * g0;
+    *r1 = s * g1;
+    *item_v = s * vert;
+    *item_h = s * hor;
+}
+
+// sums of the per-row vertical / horizontal losses: thread t brings its own rows' sums (rows t, t + 1024, ...), a
+// 1024-wide LDS tree adds them.  Afterwards rv[0] / rh[0] hold the totals (a barrier has passed).
+__device__ __forceinline__ void fb2_item_tree(float v, float h, float *rv, float *rh) {
+    const int t = threadIdx.x;
+    rv[t] = v;
+    rh[t] = h;
+    __syncthreads();
+    for (int off = 512; off >= 1; off >>= 1) {
+        if (t < off) {
+            rv[t] += rv[t + off];
+            rh[t] += rh[t + off];
+        }
+        __syncthreads();
+    }
+}
+
+// sum of dim terms in k order, f32: term4(j) returns terms 4 j .. 4 j + 3.  The terms of 32 k are formed (their LDS loads
+// in flight together) before the sequential additions take them, instead of an LDS round trip per element; measured
+// 4 % of a one-launch fit at 390 rows (2.26 -> 2.16 ms).  The additions and their order are the plain loop's.
+template <class Term4>
+__device__ __forceinline__ float fb2_seq_sum(int dim, Term4 term4) {
+    const int q = dim / 4;
+    float s = 0.f;
+    for (int j0 = 0; j0 < q; j0 += 8) {
+        float4 v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = term4(min(j0 + u, q - 1));
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (j0 + u < q) {
+                s += v[u].x;
+                s += v[u].y;
+                s += v[u].z;
+                s += v[u].w;
+            }
+    }
+    return s;
+}
+__device__ __forceinline__ float4 fb2_ld4(const float *p, int j) { return reinterpret_cast<const float4 *>(p)[j]; }
+
+// row norms and normalised rows of L.W into L.sc[0..1] / L.nw.  One thread per row walks the sum of squares in k
+// order (thread 0 and thread 64: two waves, side by side).  Ends behind a barrier only for the thread's own nw[t].
+// (Every Fb2Lds array is 16-byte aligned and dim is a multiple of 4.)
+__device__ __forceinline__ void fb2_norm_body(const Fb2Lds &L, int dim) {
+    const int t = threadIdx.x;
+    if (t == 0 || t == 64) {
+        const int c = t >> 6;
+        const float *w = L.W + c * dim;
+        const float ss = fb2_seq_sum(dim, [&](int j) {
+            const float4 a = fb2_ld4(w, j);
+            return make_float4(a.x * a.x, a.y * a.y, a.z * a.z, a.w * a.w);
+        });
+        L.sc[c] = sqrtf(ss);
+    }
+    __syncthreads();
+    if (t < 2 * dim) L.nw[t] = L.W[t] / fmaxf(L.sc[t / dim], 1e-12f);  // F.normalize's eps
+}
+
+// The regularisers and the chain rule through the normalisation, from L.nw, L.sc[0..1], L.g, L.qh and the label
+// sums: out[0] = (float) total, out[1 .. 1 + 2 dim) = d total / d W, *out_loss = total; parts5 (or null) =
+// loss_norm, loss_queryreg, loss_queryreg2, vertical, horizontal.  The values are formed as f32 the way the
+// reference's tensors are (see the comment on the one-output regularisers in fb_final_body).  L.nw / L.g / L.sc[0..1]
+// must be visible to the workgroup on entry.
+__device__ __forceinline__ void fb2_tail_body(const Fb2Lds &L, int dim, float l_norm, float l_query, float vsum,
+                                              float hsum, float *out, double *out_loss, float *parts5) {
+    const int t = threadIdx.x;
+    if (t < 256 && (t & 63) == 0) {  // four sequential sums over k, a wave each
+        const int c = (t >> 6) & 1;
+        const float *nw = L.nw + c * dim, *g = L.g + c * dim;
+        const float hq = 0.5f * l_query;
+        float s;
+        if (t < 128) {
+            s = fb2_seq_sum(dim, [&](int j) {
+                const float4 a = fb2_ld4(nw, j), b = fb2_ld4(L.qh, j);
+                return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w);
+            });
+        } else {
+            s = fb2_seq_sum(dim, [&](int j) {
+                const float4 a = fb2_ld4(nw, j), b = fb2_ld4(L.qh, j), c4 = fb2_ld4(g, j);
+                return make_float4(a.x * (c4.x - hq * b.x), a.y * (c4.y - hq * b.y), a.z * (c4.z - hq * b.z),
+                                   a.w * (c4.w - hq * b.w));
+            });
+        }
+        L.sc[2 + (t >> 6)] = s;
+    }
+    __syncthreads();
+    if (t < 2 * dim) {
+        // G = d total / d nw_c ; d nw / d W = (I - nw nw') / |W|
+        const int c = t / dim, k = t - c * dim;
+        const float nrm = L.sc[c], dotg = L.sc[4 + c];
+        const float lg = logf(nrm);
+        const float den = fmaxf(nrm, 1e-12f);
+        const float radial = l_norm * sinhf(lg) / den;  // d [l_norm (cosh(log |W|) - 1)] / d|W|, times d|W|/dW = nw
+        const float G = L.g[t] - 0.5f * l_query * L.qh[k];
+        out[1 + t] = (G - L.nw[t] * dotg) / den + radial * L.nw[t];
+    }
+    if (t == 0) {
+        float loss_norm = 0.f, lq[2];
+        for (int c = 0; c < 2; ++c) {
+            loss_norm += coshf(logf(L.sc[c])) - 1.f;
+            lq[c] = l_query * ((1.f - L.sc[2 + c]) / 2.f);
+        }
+        loss_norm *= l_norm;
+        const float labels = vsum + hsum;
+        const float total = ((labels + loss_norm) + lq[0]) + lq[1];
+        out[0] = total;
+        *out_loss = (double)total;
+        if (parts5) {
+            parts5[0] = loss_norm; parts5[1] = lq[0]; parts5[2] = lq[1]; parts5[3] = vsum; parts5[4] = hsum;
         }
     }
 }

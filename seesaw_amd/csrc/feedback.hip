@@ -10,6 +10,9 @@
 //       sum_i sw_i item_i + l_norm (cosh(log w.w) - 1) + l_data w'(X'LX)w + l_query (1 - w^.q^)/2,
 //       item = BCE (balanced re-weighting :90-105) | pairwise hinge (:106-112, rank_loss.py:63-95)
 //              | pairwise logistic (:113-119, rank_loss.py:34-61)
+//   MultiRegModule (the multi_reg_neg loop's two-output scorer)   seesaw/loops/multi_reg_module.py:40-165
+//       two logits a row from the L2-normalised rows of W [2, dim]; vertical BCE pair + horizontal CE on the labelled
+//       rows + l_norm sum_c (cosh(log |W_c|) - 1) + l_query sum_c (1 - w^_c.q^)/2, all f32
 //   torch.optim.LBFGS(line_search_fn="strong_wolfe") closure loop   seesaw/basic_trainer.py:11-69
 //
 // The reference evaluates the closure through Python autograd (with anomaly detection on)
@@ -29,6 +32,16 @@
 //       fb_elem     per-item BCE loss + dL/dz             elementwise
 //       fb_grad     partial g = Xc' r per 32-row slab     thread per column, coalesced
 //       fb_final    fixed-order reduction of the partials + regulariser terms -> [loss, grad]
+// The two-output objective has three forms.  ssw_fb_fit2 / ssw_fb_lossgrad2 (the default, its bits kept): the host
+// drives, and per evaluation the data part runs on the device (k_fb2_logits_elem, k_fb_grad twice, k_fb2_reduce) and the
+// O(dim) part -- F.normalize, its chain rule, the two regularisers -- on the host.  Opt-in, ssw_fb_lossgrad2_dev /
+// ssw_fb_fit2_batch: the O(dim) part on the device too (fb2_norm_body / fb2_tail_body of fb_math.h, in the host
+// tail's operation order; only logf / coshf / sinhf are the device library's), under two drivers that return
+// bit-identical fits (tests/test_fit2_device_gpu.py):
+//   * n <= 1024 rows: k_fb_fit2_wg -- the whole step(closure) in one launch, fit_driver_step<16> around new evaluation
+//     phases; k_fb_fit2_wg_batch is that workgroup once per engine, S sessions' fits in one launch and one host wait;
+//   * larger sets, or SSW_FB_HOST_DRIVER: lbfgs_host over fb_eval2_dev -- one copy of W, k_fb2_norm, k_fb2_logits_elem,
+//     k_fb_grad twice, k_fb2_final_dev and one wait per evaluation, no host arithmetic.
 // Bound: issue / launch latency, not HBM -- nothing here is GEMM-shaped enough for MFMA.  Compiled with
 // -ffp-contract=off (Makefile), like the four files below: the host driver and the device driver must round alike,
 // and the expressions that are meant to be fused say fmaf.
@@ -36,8 +49,10 @@
 // The engine's sources:
 //   fb_math.h            the arithmetic both drivers share, and nothing else -- the bit-identity contract
 //   fb_handle.h          struct ssw_fb, FitWgArgs, Evaluator, the host functions that cross the files below
-//   feedback_eval.hip    data-preparation and per-evaluation kernels; fb_reserve, fb_center, fb_prepare, fb_eval, fb_eval2
-//   feedback_fit_wg.hip  k_fb_fit_wg / k_fb_fit_wg_batch, their LDS map, phases and driver step, and their host side
+//   feedback_eval.hip    data-preparation and per-evaluation kernels; fb_reserve, fb_center, fb_prepare, fb_eval, fb_eval2,
+//                        fb_eval2_dev
+//   feedback_fit_wg.hip  k_fb_fit_wg / k_fb_fit_wg_batch, their LDS map, phases and driver step, and their host side;
+//                        k_fb_fit2_wg / k_fb_fit2_wg_batch on the same driver step
 //   feedback_lbfgs.hip   the host L-BFGS: strong_wolfe, lbfgs_host
 //   feedback.hip         the C entry points (ssw_fb_*, ssw_rank_pairwise): no kernel, no device code
 #include <algorithm>
@@ -76,7 +91,7 @@ ssw_status ssw_fb_destroy(ssw_fb *fb) {
     (void)hipFree(fb->partial);
     (void)hipFree(fb->gsum);
     (void)hipFree(fb->rankg);
-    for (float *p2 : {fb->y2, fb->sw2, fb->z2, fb->r2, fb->itemv, fb->itemh, fb->partial2, fb->nw2}) (void)hipFree(p2);
+    for (float *p2 : {fb->y2, fb->sw2, fb->z2, fb->r2, fb->itemv, fb->itemh, fb->partial2, fb->nw2, fb->w2}) (void)hipFree(p2);
     if (fb->out2_host) (void)hipHostFree(fb->out2_host);
     (void)hipFree(fb->colsum);
     (void)hipFree(fb->w);
@@ -632,6 +647,139 @@ ssw_status ssw_fb_fit2(ssw_fb *fb, float *W_inout, float reg_norm_lambda, float 
     fb->last_evals = 0;
     fb->last_fit_on_device = false;
     return fb_fit_host(E, E.P, -1, W_inout, max_iter, lr, out_iters, out_evals, out_final_loss);
+}
+
+// ---- the two-output objective evaluated and fitted entirely on the device (opt-in) ---------------
+ssw_status ssw_fb_lossgrad2_dev(ssw_fb *fb, const float *W_host, float reg_norm_lambda, float reg_query_lambda,
+                                float *out_loss, float *out_grad, float *out_parts5_or_null) {
+    SSW_REQUIRE(fb && W_host && out_loss && out_grad, "NULL argument");
+    DeviceGuard guard(fb->device);
+    SSW_REQUIRE(2 * fb->dim <= 1024, "feedback: the two-output objective takes dim <= 512, got %d", fb->dim);
+    memcpy(fb->w_host, W_host, (size_t)2 * fb->dim * sizeof(float));
+    SSW_TRY(fb_eval2_dev(fb, reg_norm_lambda, reg_query_lambda, out_parts5_or_null));
+    *out_loss = (float)fb->loss_host[0];
+    memcpy(out_grad, fb->out_host + 1, (size_t)2 * fb->dim * sizeof(float));
+    return SSW_OK;
+}
+
+// the host-driven fit over the device evaluation: the driver k_fb_fit2_wg is pinned on, and the path of the sets
+// one workgroup does not reach
+static ssw_status fb_fit2_host_dev(ssw_fb *fb, float *W_inout, float l_norm, float l_query, int32_t max_iter, float lr,
+                                   int32_t *out_iters, int32_t *out_evals, float *out_final_loss) {
+    Evaluator E;
+    E.fb = fb;
+    E.o = nullptr;
+    E.P = 2 * fb->dim;
+    E.two = true;
+    E.two_dev = true;
+    E.l_norm2 = l_norm;
+    E.l_query2 = l_query;
+    E.pw = 1.f;
+    E.pairwise_active = false;
+    memset(&E.dev, 0, sizeof(E.dev));
+    fb->last_evals = 0;
+    fb->last_fit_on_device = false;
+    return fb_fit_host(E, E.P, -1, W_inout, max_iter, lr, out_iters, out_evals, out_final_loss);
+}
+
+ssw_status ssw_fb_fit2_batch(ssw_fb *const *fbs, int32_t nfit, float *W_inout, const float *reg_norm_lambda,
+                             const float *reg_query_lambda, const int32_t *max_iter, const float *lr, int32_t *out_iters,
+                             int32_t *out_evals, float *out_final_loss, int32_t *out_status) {
+    // ---- refusals, before anything is queued
+    SSW_REQUIRE(nfit >= 1, "nfit < 1");
+    SSW_REQUIRE(fbs && W_inout && reg_norm_lambda && reg_query_lambda && max_iter && lr && out_status, "NULL argument");
+    for (int s = 0; s < nfit; ++s) {
+        SSW_REQUIRE(fbs[s] != nullptr, "slot %d: NULL handle", s);
+        for (int t = 0; t < s; ++t) SSW_REQUIRE(fbs[t] != fbs[s], "slots %d and %d share one handle", t, s);
+        SSW_REQUIRE(fbs[s]->device == fbs[0]->device, "slot %d: device %d, slot 0 is on device %d", s, fbs[s]->device,
+                    fbs[0]->device);
+        SSW_REQUIRE(fbs[s]->dim == fbs[0]->dim, "slot %d: dim %d, slot 0 has dim %d", s, fbs[s]->dim, fbs[0]->dim);
+        SSW_REQUIRE(max_iter[s] >= 1, "slot %d: max_iter < 1", s);
+    }
+    const int dim = fbs[0]->dim, P = 2 * dim;
+    SSW_REQUIRE(P <= 1024, "feedback: the two-output objective takes dim <= 512, got %d", dim);
+    for (int s = 0; s < nfit; ++s) {
+        const ssw_fb *fb = fbs[s];
+        SSW_REQUIRE(fb->n == 0 || (fb->has_targets2 && fb->cap2 >= fb->cap),
+                    "slot %d: ssw_fb_set_targets2 has not been called for these rows", s);
+        SSW_REQUIRE(fb->has_q, "slot %d: the two-output objective needs ssw_fb_set_query first", s);
+        for (int i = 0; i < P; ++i)
+            SSW_REQUIRE(std::isfinite(W_inout[(size_t)s * P + i]), "slot %d: initial weight %d is not finite", s, i);
+    }
+    DeviceGuard guard(fbs[0]->device);
+    std::vector<int> slots;  // the slots one workgroup each serves; the others are driven from the host afterwards
+    for (int s = 0; s < nfit; ++s) {
+        fbs[s]->batch_error.clear();
+        out_status[s] = SSW_OK;
+        if (fb_fit2_wg_eligible(fbs[s])) slots.push_back(s);
+    }
+    // one slot's result, formed on a copy of the slot's row (as in ssw_fb_fit_batch)
+    std::vector<float> row((size_t)P);
+    auto fit_slot = [&](int s, auto &&fit) -> ssw_status {
+        float *Ws = &W_inout[(size_t)s * P];
+        memcpy(row.data(), Ws, (size_t)P * sizeof(float));
+        const ssw_status st = fit(row.data(), out_iters ? &out_iters[s] : nullptr, out_evals ? &out_evals[s] : nullptr,
+                                  out_final_loss ? &out_final_loss[s] : nullptr);
+        if (st == SSW_OK) {
+            memcpy(Ws, row.data(), (size_t)P * sizeof(float));
+        } else if (st == SSW_ERR_NUMERIC) {
+            out_status[s] = st;
+            fbs[s]->batch_error = ssw_last_error();
+        } else {
+            return st;
+        }
+        return SSW_OK;
+    };
+    const int nwg = (int)slots.size();
+    if (nwg > 0) {
+        ssw_fb *lead = fbs[slots[0]];  // its stream takes the launch, its tables the arguments and start vectors
+        const int wrow = 2 * (dim + 1);  // the start-vector table's rows are dim + 1 wide: a slot's 2 dim floats take two
+        SSW_TRY(fb_batch_reserve(lead, 2 * nwg));
+        std::vector<FitWgArgs> tab((size_t)nwg);
+        std::vector<float> w0((size_t)nwg * wrow, 0.f);
+        for (int b = 0; b < nwg; ++b) {
+            const int s = slots[b];
+            fbs[s]->last_evals = 0;
+            fbs[s]->last_fit_on_device = false;
+            fb_fit2_wg_fill(fbs[s], reg_norm_lambda[s], reg_query_lambda[s], max_iter[s], lr[s],
+                            lead->batch_w + (size_t)b * wrow, &tab[b]);
+            memcpy(&w0[(size_t)b * wrow], &W_inout[(size_t)s * P], (size_t)P * sizeof(float));
+        }
+        if (nwg > 1) SSW_TRY(lead->batch_tab_stage.push(lead->batch_tab, tab.data(), tab.size() * sizeof(FitWgArgs), lead->stream));
+        SSW_TRY(lead->batch_w_stage.push(lead->batch_w, w0.data(), w0.size() * sizeof(float), lead->stream));
+        for (int b = 1; b < nwg; ++b) {  // the launch is ordered behind every slot's uploads
+            ssw_fb *fb = fbs[slots[b]];
+            if (!fb->batch_ev) SSW_HIP_TRY(hipEventCreateWithFlags(&fb->batch_ev, hipEventDisableTiming));
+            SSW_HIP_TRY(hipEventRecord(fb->batch_ev, fb->stream));
+            SSW_HIP_TRY(hipStreamWaitEvent(lead->stream, fb->batch_ev, 0));
+        }
+        SSW_TRY(fb_fit2_wg_launch(lead, tab.data(), nwg));
+        for (int b = 0; b < nwg; ++b) {
+            if (!fb_fit_wg_spin(fbs[slots[b]], tab[b].seqno)) {
+                SSW_HIP_TRY(hipStreamSynchronize(lead->stream));  // every workgroup has published
+                break;
+            }
+        }
+        for (int b = 0; b < nwg; ++b) {
+            const int s = slots[b];
+            SSW_TRY(fit_slot(s, [&](float *w, int32_t *iters, int32_t *evals, float *final_loss) {
+                return fb_fit_wg_collect(fbs[s], P, w, iters, evals, final_loss);
+            }));
+        }
+    }
+    // ---- the slots driven from the host, one evaluation at a time on the device: one after another
+    size_t next_wg = 0;
+    for (int s = 0; s < nfit; ++s) {
+        if (next_wg < slots.size() && slots[next_wg] == s) {
+            ++next_wg;
+            continue;
+        }
+        SSW_TRY(fit_slot(s, [&](float *w, int32_t *iters, int32_t *evals, float *final_loss) {
+            return fb_fit2_host_dev(fbs[s], w, reg_norm_lambda[s], reg_query_lambda[s], max_iter[s], lr[s], iters, evals,
+                                    final_loss);
+        }));
+    }
+    return SSW_OK;
 }
 
 ssw_status ssw_fb_reset(ssw_fb *fb) {

@@ -238,26 +238,14 @@ __global__ __launch_bounds__(256) void k_fb2_logits_elem(const float *__restrict
         b += __shfl_xor(b, off, 64);
     }
     if (lane != 0) return;
-    const float y0 = y2[row], y1 = y2[plane + row], s = sw[row];
-    // binary_cross_entropy_with_logits: (1 - y) z - log_sigmoid(z), log_sigmoid(z) = min(z, 0) - log1p(exp(-|z|))
-    const float ls0 = fminf(a, 0.f) - log1pf(expf(-fabsf(a))), ls1 = fminf(b, 0.f) - log1pf(expf(-fabsf(b)));
-    const float vert = ((1.f - y0) * a - ls0) + ((1.f - y1) * b - ls1);
-    const float sg0 = 1.f / (1.f + expf(-a)), sg1 = 1.f / (1.f + expf(-b));
-    float g0 = sg0 - y0, g1 = sg1 - y1, hor = 0.f;
-    const float near = y0 + y1;
-    if (near > 0.f) {  // cross_entropy with probability targets on the rows that carry any label
-        const float m = fmaxf(a, b);
-        const float lse = m + logf(expf(a - m) + expf(b - m));
-        hor = -(y0 * (a - lse) + y1 * (b - lse));
-        g0 += near * expf(a - lse) - y0;
-        g1 += near * expf(b - lse) - y1;
-    }
+    float r0, r1, iv, ih;
+    fb2_row_terms(a, b, y2[row], y2[plane + row], sw[row], &r0, &r1, &iv, &ih);
     z2[row] = a;
     z2[plane + row] = b;
-    r2[row] = s * g0;
-    r2[plane + row] = s * g1;
-    item_v[row] = s * vert;
-    item_h[row] = s * hor;
+    r2[row] = r0;
+    r2[plane + row] = r1;
+    item_v[row] = iv;
+    item_h[row] = ih;
 }
 
 // The slab sums (slab_column_sum, fb_math.h) ahead of k_fb_final, over several workgroups, for sets of thousands of
@@ -307,20 +295,55 @@ __global__ __launch_bounds__(1024) void k_fb2_reduce(const float *__restrict__ p
         v += item_v[i];
         h += item_h[i];
     }
-    rv[t] = v;
-    rh[t] = h;
-    __syncthreads();
-    for (int off = 512; off >= 1; off >>= 1) {
-        if (t < off) {
-            rv[t] += rv[t + off];
-            rh[t] += rh[t + off];
-        }
-        __syncthreads();
-    }
+    fb2_item_tree(v, h, rv, rh);
     if (t == 0) {
         out[0] = rv[0];
         out[1] = rh[0];
     }
+    __threadfence_system();
+    __syncthreads();
+    if (t == 0) __hip_atomic_store(done_flag, seqno, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// ---- the two-output evaluation with its O(dim) part on the device too (fb_eval2_dev): k_fb2_norm in front of
+// k_fb2_logits_elem / k_fb_grad, k_fb2_final_dev in place of k_fb2_reduce and fb_eval2's host tail.  The bodies are
+// fb_math.h's (fb2_norm_body, fb2_item_tree, fb2_tail_body), the ones k_fb_fit2_wg runs.
+// wn [2 dim + 2]: raw weights in, then |W_0|, |W_1| out; nw [2 dim] out
+__global__ __launch_bounds__(1024) void k_fb2_norm(float *__restrict__ wn, int dim, float *__restrict__ nw) {
+    __shared__ __align__(16) float sW[1024], snw[1024], ssc[8];
+    const int t = threadIdx.x;
+    if (t < 2 * dim) sW[t] = wn[t];
+    __syncthreads();
+    const Fb2Lds L{sW, snw, nullptr, nullptr, ssc, nullptr, nullptr};
+    fb2_norm_body(L, dim);
+    if (t < 2 * dim) nw[t] = snw[t];
+    if (t < 2) wn[2 * dim + t] = ssc[t];
+}
+
+// out[0] = (float) loss, out[1 .. 1 + 2 dim) = d loss / d W, out[1 + 2 dim ..) = parts5, *out_loss; then the flag
+__global__ __launch_bounds__(1024) void k_fb2_final_dev(const float *__restrict__ partial /* [2][nslabs_cap][dim] */,
+                                                        int64_t partial_plane, int nslabs, const float *__restrict__ item_v,
+                                                        const float *__restrict__ item_h, int64_t n, int dim,
+                                                        const float *__restrict__ wn, const float *__restrict__ nw,
+                                                        const float *__restrict__ qhat, float l_norm, float l_query,
+                                                        float *__restrict__ out, double *__restrict__ out_loss,
+                                                        unsigned *__restrict__ done_flag, unsigned seqno) {
+    __shared__ __align__(16) float snw[1024], sg[1024], sqh[512], ssc[8], rv[1024], rh[1024];
+    const int t = threadIdx.x;
+    if (t < 2 * dim) {
+        snw[t] = nw[t];
+        sg[t] = slab_column_sum(partial + (t / dim) * partial_plane + (t % dim), nslabs, dim);
+    }
+    if (t < dim) sqh[t] = qhat[t];
+    if (t < 2) ssc[t] = wn[2 * dim + t];
+    float v = 0.f, h = 0.f;
+    for (int64_t i = t; i < n; i += 1024) {
+        v += item_v[i];
+        h += item_h[i];
+    }
+    fb2_item_tree(v, h, rv, rh);
+    const Fb2Lds L{nullptr, snw, sg, sqh, ssc, rv, rh};  // the tail reads the normalised rows and their norms only
+    fb2_tail_body(L, dim, l_norm, l_query, rv[0], rh[0], out, out_loss, out + 1 + 2 * dim);
     __threadfence_system();
     __syncthreads();
     if (t == 0) __hip_atomic_store(done_flag, seqno, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -631,6 +654,13 @@ ssw_status fb2_reserve(ssw_fb *fb) {
     return SSW_OK;
 }
 
+// the device copies of the raw and the normalised weights (fb_eval2_dev, the one-launch fit's start vector)
+ssw_status fb2_dev_reserve(ssw_fb *fb) {
+    if (!fb->w2) SSW_HIP_TRY(hipMalloc((void **)&fb->w2, (size_t)(2 * fb->dim + 2) * sizeof(float)));
+    if (!fb->nw2) SSW_HIP_TRY(hipMalloc((void **)&fb->nw2, (size_t)2 * fb->dim * sizeof(float)));
+    return SSW_OK;
+}
+
 // One evaluation of MultiRegModule._step (multi_reg_module.py:64-128) at the raw weights W = fb->w_host [2, dim]:
 // the data part (logits, per-row losses, X' r per output) on the device; the O(dim) part -- F.normalize and its
 // chain rule, the norm and query regularisers -- here, in f32 like the reference's tensors.
@@ -714,6 +744,39 @@ ssw_status fb_eval2(ssw_fb *fb, float l_norm, float l_query, float *parts5) {
     if (parts5) {
         parts5[0] = loss_norm; parts5[1] = lq[0]; parts5[2] = lq[1]; parts5[3] = vsum; parts5[4] = hsum;
     }
+    fb->last_evals++;
+    return SSW_OK;
+}
+
+// fb_eval2 with nothing left on the host: one copy of the raw weights, the launches below, one wait.  Results as
+// fb_eval2 leaves them (fb->loss_host[0], fb->out_host[1 .. 1 + 2 dim)); parts5 optional.  A set of 0 rows is
+// regulariser-only: k_fb2_norm and k_fb2_final_dev alone.
+ssw_status fb_eval2_dev(ssw_fb *fb, float l_norm, float l_query, float *parts5) {
+    hipStream_t s = fb->stream;
+    const int64_t n = fb->n;
+    const int dim = fb->dim;
+    SSW_REQUIRE(fb->has_q, "feedback: the two-output objective needs ssw_fb_set_query first");
+    SSW_REQUIRE(n == 0 || (fb->has_targets2 && fb->cap2 >= fb->cap),
+                "feedback: ssw_fb_set_targets2 has not been called for these rows");
+    SSW_TRY(fb2_dev_reserve(fb));
+    SSW_HIP_TRY(hipMemcpyAsync(fb->w2, fb->w_host, (size_t)2 * dim * sizeof(float), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_fb2_norm, dim3(1), dim3(1024), 0, s, fb->w2, dim, fb->nw2);
+    const int nslabs = (int)((n + FB_SLAB - 1) / FB_SLAB);
+    const int64_t plane = fb->cap2, pplane = ((fb->cap2 + FB_SLAB - 1) / FB_SLAB) * dim;
+    if (n > 0) {
+        hipLaunchKernelGGL(k_fb2_logits_elem, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, fb->X, fb->nw2, n, dim, plane,
+                           fb->y2, fb->sw2, fb->z2, fb->r2, fb->itemv, fb->itemh);
+        const int tx = dim < 256 ? dim : 256;
+        for (int c = 0; c < 2; ++c)
+            hipLaunchKernelGGL(k_fb_grad, dim3((unsigned)nslabs, (unsigned)((dim + tx - 1) / tx)), dim3(tx), 0, s, fb->X,
+                               fb->r2 + c * plane, n, dim, fb->partial2 + c * pplane);
+    }
+    hipLaunchKernelGGL(k_fb2_final_dev, dim3(1), dim3(1024), 0, s, n > 0 ? fb->partial2 : (const float *)nullptr, pplane, nslabs,
+                       fb->itemv, fb->itemh, n, dim, fb->w2, fb->nw2, fb->qhat, l_norm, l_query, fb->out_host_dev,
+                       fb->loss_host_dev, fb->flag_host_dev, ++fb->seqno);
+    SSW_HIP_TRY(hipGetLastError());
+    if (!fb_fit_wg_spin(fb, fb->seqno)) SSW_HIP_TRY(hipStreamSynchronize(s));
+    if (parts5) memcpy(parts5, fb->out_host + 1 + 2 * dim, 5 * sizeof(float));
     fb->last_evals++;
     return SSW_OK;
 }

@@ -943,6 +943,254 @@ __global__ __launch_bounds__(1024) void k_fb_fit_wg_batch(const FitWgArgs *__res
     fit_wg_body<FIT_EPL, false>(fit_lds, a_in, nullptr);
 }
 
+// ---- the two-output objective's whole fit in one launch ------------------------------------------
+// k_fb_fit2_wg / k_fb_fit2_wg_batch: k_fb_fit_wg for MultiRegModule's objective (multi_reg_module.py:64-128; the
+// LBFGS of multi_reg_module.py:142 stepped at basic_trainer.py:59-63).  The driver is fit_driver_step<16> as it
+// stands: 16 x 64 = 1024 vector elements hold the 2 dim <= 1024 parameters exactly, the driver sees them as
+// "dim + 1 parameters with intercept" (a.dim = 2 dim2 - 1, a.P = 2 dim2), so no slot is zeroed -- lbfgs_host with
+// E.P = 2 dim and zero_slot = -1 on the other side.  Only the evaluation phases are new; what they compute is
+// fb_math.h's (fb2_norm_body, fb2_row_terms, fb2_item_tree, fb2_tail_body) in the order of the per-evaluation
+// kernels: k_fb2_logits_elem's lane chains and butterfly, k_fb_grad's slab chains, k_fb2_reduce's slab and item sums.
+//
+// LDS map: FitLds at the 1024 stride (fit_lds_map(base, FIT2_MAP_DIM)), whose regions serve as
+//     sw_  raw weights of the evaluation [2 dim2]        gout  loss + gradient [1 + 2 dim2]
+//     zl / rl  d loss / d logit, planes 0 / 1            yl / cl  targets, planes 0 / 1
+//     item  the per-row vertical [0, 1024) and horizontal [1024, 2048) losses as floats       qh  unit query
+// and behind them, in `stage`:
+//     sample weights [1024] | normalised weights [1024] | label gradient [1024] | scalars [16] |
+//     slab partials [FIT_ROUND_SLABS][2][dim2] (after the gradient: the item tree's 2 x 1024 floats)
+constexpr int FIT2_MAP_DIM = 1023;  // any dim of the 16 x 64 vector stride
+constexpr size_t FIT2_STAGE_FLOATS = 3 * 1024 + 16 + (size_t)FIT_ROUND_SLABS * 1024;
+constexpr size_t FIT2_LDS_BYTES = FIT_LDS_DOUBLES * sizeof(double) +
+                                  (1024 + 1040 + 4 * FIT_WG_MAX_ROWS + 1024 + 7 * 1024 + FIT2_STAGE_FLOATS) * sizeof(float);
+static_assert(FIT2_LDS_BYTES <= 160 * 1024, "k_fb_fit2_wg's LDS map outgrew the 160 KB attribute");
+static_assert(FIT_ROUND_SLABS * 1024 >= 2 * 1024, "the item tree borrows the slab partials' region");
+static_assert(FIT_WG_MAX_ROWS == 1024, "one row a thread in the item sums; two float planes in FitLds::item");
+
+struct Fit2Lds {
+    float *sw;     // [FIT_WG_MAX_ROWS] sample weights
+    float *nw;     // [1024] normalised weights
+    float *glab;   // [1024] d labels / d nw
+    float *sc;     // [16]
+    float *part;   // [FIT_ROUND_SLABS][2][dim2]
+    float *iv, *ih;  // [FIT_WG_MAX_ROWS] per-row losses
+};
+__device__ __forceinline__ Fit2Lds fit2_lds_map(const FitLds &S) {
+    Fit2Lds T;
+    T.sw = S.stage;
+    T.nw = T.sw + 1024;
+    T.glab = T.nw + 1024;
+    T.sc = T.glab + 1024;
+    T.part = T.sc + 16;
+    T.iv = reinterpret_cast<float *>(S.item);
+    T.ih = T.iv + FIT_WG_MAX_ROWS;
+    return T;
+}
+__device__ __forceinline__ Fb2Lds fit2_math_lds(const FitLds &S, const Fit2Lds &T) {
+    return Fb2Lds{S.sw_, T.nw, T.glab, S.qh, T.sc, T.part, T.part + 1024};
+}
+
+__device__ __noinline__ void fit2_eval_norm(double *base) {
+    const FitLds S = fit_lds_map(base, FIT2_MAP_DIM);
+    const Fit2Lds T = fit2_lds_map(S);
+    fb2_norm_body(fit2_math_lds(S, T), S.args->dim2);
+}
+
+// two logits a row from both normalised weight rows (a wave takes four rows at a time, their loads in flight
+// together; per row k_fb2_logits_elem's lane chains and xor butterfly), then lanes 0-3 one row's label terms each
+__device__ __noinline__ void fit2_eval_logits_labels(double *base) {
+    const FitLds S = fit_lds_map(base, FIT2_MAP_DIM);
+    const Fit2Lds T = fit2_lds_map(S);
+    const FitWgArgs &a = *S.args;
+    const int c = threadIdx.x, lane = c & 63, wave = c >> 6;
+    const int n = a.n, dim = a.dim2;
+    const float4 *w0 = reinterpret_cast<const float4 *>(T.nw), *w1 = reinterpret_cast<const float4 *>(T.nw + dim);
+    for (int row0 = wave * 4; row0 < n; row0 += 64) {
+        fit_g4ptr x4[4];
+        float pa[4], pb[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            x4[u] = (fit_g4ptr)(a.X + (int64_t)(row0 + u < n ? row0 + u : row0) * dim);
+            pa[u] = 0.f;
+            pb[u] = 0.f;
+        }
+        for (int k = lane; k < dim / 4; k += 64) {
+            fit_v4f xv[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) xv[u] = x4[u][k];
+            const float4 p = w0[k], q = w1[k];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                float s_ = pa[u], t_ = pb[u];
+                s_ = fmaf(xv[u].x, p.x, s_); s_ = fmaf(xv[u].y, p.y, s_); s_ = fmaf(xv[u].z, p.z, s_); s_ = fmaf(xv[u].w, p.w, s_);
+                t_ = fmaf(xv[u].x, q.x, t_); t_ = fmaf(xv[u].y, q.y, t_); t_ = fmaf(xv[u].z, q.z, t_); t_ = fmaf(xv[u].w, q.w, t_);
+                pa[u] = s_;
+                pb[u] = t_;
+            }
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                pa[u] += __shfl_xor(pa[u], off, 64);
+                pb[u] += __shfl_xor(pb[u], off, 64);
+            }
+        }
+        const float za = lane == 0 ? pa[0] : lane == 1 ? pa[1] : lane == 2 ? pa[2] : pa[3];
+        const float zb = lane == 0 ? pb[0] : lane == 1 ? pb[1] : lane == 2 ? pb[2] : pb[3];
+        const int row = row0 + lane;
+        if (lane < 4 && row < n)
+            fb2_row_terms(za, zb, S.yl[row], S.cl[row], T.sw[row], &S.zl[row], &S.rl[row], &T.iv[row], &T.ih[row]);
+    }
+}
+
+// both gradient planes in one pass over the rows: fit_eval_grad's schedule (four adjacent columns a thread, thread
+// group grp the slab s0 + grp of a round, quarters of eight rows on two register sets) with two chains a column --
+// k_fb_grad's ordered chain per plane and slab, the slab sums added in slab order (k_fb2_reduce).  Leaves T.glab.
+__device__ __noinline__ void fit2_eval_grad(double *base) {
+    const FitLds S = fit_lds_map(base, FIT2_MAP_DIM);
+    const Fit2Lds T = fit2_lds_map(S);
+    const FitWgArgs &a = *S.args;
+    const int c = threadIdx.x;
+    const int n = a.n, dim = a.dim2;
+    const float *r0l = S.zl, *r1l = S.rl;
+    float *part = T.part;
+    float gcol = 0.f;
+    const int dq = dim / 4;
+    const int groups = min(FIT_ROUND_SLABS, 1024 / dq);
+    const int grp = c / dq, cq = c - grp * dq;
+    const int nslabs = (n + FB_SLAB - 1) / FB_SLAB;
+    const int pc = c < 2 * dim ? c / dim : 0, kc = c - pc * dim;  // this thread's plane and column in the slab sums
+    for (int s0 = 0; s0 < nslabs; s0 += groups) {
+        const int sl = s0 + grp;
+        if (grp < groups && sl < nslabs) {
+            const int r0 = sl * FB_SLAB;
+            const int cnt = min(r0 + FB_SLAB, n) - r0;
+            float4 p = make_float4(0.f, 0.f, 0.f, 0.f), q = make_float4(0.f, 0.f, 0.f, 0.f);
+            static_assert(FB_SLAB == 32, "four quarters of eight rows");
+            fit_v4f xq[2][8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) xq[0][i] = *(fit_g4ptr)(a.X + (int64_t)(r0 + (i < cnt ? i : 0)) * dim + 4 * cq);
+#pragma unroll
+            for (int qd = 0; qd < 4; ++qd) {
+                const int h = qd * 8;
+                if (qd + 1 < 4) {
+#pragma unroll
+                    for (int i = 0; i < 8; ++i)
+                        xq[(qd + 1) & 1][i] =
+                            *(fit_g4ptr)(a.X + (int64_t)(r0 + (h + 8 + i < cnt ? h + 8 + i : 0)) * dim + 4 * cq);
+                }
+#pragma unroll
+                for (int i = 0; i < 8; ++i)
+                    if (h + i < cnt) {
+                        const float ri = r0l[r0 + h + i], si = r1l[r0 + h + i];
+                        const fit_v4f xv = xq[qd & 1][i];
+                        p.x = fmaf(ri, xv.x, p.x); p.y = fmaf(ri, xv.y, p.y); p.z = fmaf(ri, xv.z, p.z); p.w = fmaf(ri, xv.w, p.w);
+                        q.x = fmaf(si, xv.x, q.x); q.y = fmaf(si, xv.y, q.y); q.z = fmaf(si, xv.z, q.z); q.w = fmaf(si, xv.w, q.w);
+                    }
+            }
+            *reinterpret_cast<float4 *>(part + (size_t)(2 * grp) * dim + 4 * cq) = p;
+            *reinterpret_cast<float4 *>(part + (size_t)(2 * grp + 1) * dim + 4 * cq) = q;
+        }
+        __syncthreads();
+        if (c < 2 * dim)
+            for (int j = 0; j < groups && s0 + j < nslabs; ++j) gcol += part[(size_t)(2 * j + pc) * dim + kc];
+        __syncthreads();
+    }
+    if (c < 2 * dim) T.glab[c] = gcol;
+}
+
+// the item sums and the O(dim) tail into gout / loss_slot
+__device__ __noinline__ void fit2_eval_final(double *base) {
+    const FitLds S = fit_lds_map(base, FIT2_MAP_DIM);
+    const Fit2Lds T = fit2_lds_map(S);
+    const FitWgArgs &a = *S.args;
+    const int c = threadIdx.x;
+    const Fb2Lds L = fit2_math_lds(S, T);
+    float v = 0.f, h = 0.f;
+    if (c < a.n) {  // k_fb2_reduce's `for (i = t; i < n; i += 1024)` at n <= 1024
+        v += T.iv[c];
+        h += T.ih[c];
+    }
+    fb2_item_tree(v, h, L.rv, L.rh);
+    fb2_tail_body(L, a.dim2, a.obj.l_norm, a.obj.l_query, L.rv[0], L.rh[0], S.gout, S.loss_slot, nullptr);
+}
+
+__device__ __forceinline__ void fit2_wg_body(double *fit_lds, const FitWgArgs &a_in) {
+    const int c = threadIdx.x, lane = c & 63, wave = c >> 6;
+    const int dim = a_in.dim2, n = a_in.n, P = 2 * dim;
+    const FitLds S = fit_lds_map(fit_lds, FIT2_MAP_DIM);
+    const Fit2Lds T = fit2_lds_map(S);
+    if (c == 0) {
+        *S.args = a_in;
+        FitDriver z0;
+        memset(&z0, 0, sizeof(z0));
+        z0.H_diag = 1.0;  // st = ST_INIT = 0
+        *S.drv = z0;
+        S.ctl[0] = 0.0;
+        for (int i = 0; i < 8; ++i) S.tk[i] = 0;
+    }
+    for (int i = c; i < n; i += 1024) {
+        S.yl[i] = a_in.y[i];
+        S.cl[i] = a_in.y[(size_t)a_in.plane2 + i];
+        T.sw[i] = a_in.coef[i];
+    }
+    if (c < dim) S.qh[c] = a_in.qhat[c];
+    for (int k = c; k < 1040; k += 1024) S.gout[k] = 0.f;  // the driver reads it 16 x 64 wide
+    {
+        const float x0 = c < P ? a_in.w0_or_null[c] : 0.f;
+        S.vx[c] = x0;
+        S.vd[c] = 0.f;
+        S.vg[c] = 0.f;
+        S.vpg[c] = 0.f;
+        S.vgp[c] = 0.f;
+        S.vb0[c] = 0.f;
+        S.vb1[c] = 0.f;
+        S.sw_[c] = x0 + (float)0.0 * 0.f;  // the first closure call: f(x + 0 d)
+    }
+    const unsigned long long t_kernel0 = wall_clock64();
+    for (;;) {
+        __syncthreads();  // the set-up, or the driver's sw_ and ctl, are published
+        if (S.ctl[0] != 0.0) break;
+        fit2_eval_norm(fit_lds);
+        __syncthreads();
+        if (n > 0) {
+            fit2_eval_logits_labels(fit_lds);
+            __syncthreads();
+        }
+        fit2_eval_grad(fit_lds);  // no slab at n = 0: the label gradient is 0
+        __syncthreads();
+        fit2_eval_final(fit_lds);
+        __syncthreads();
+        if (wave == 0) fit_driver_step<16>(fit_lds, FIT2_MAP_DIM);
+    }
+    if (wave == 0) {  // every wave is here; wave 0 publishes as fit_wg_body does
+        const FitDriver &D = *S.drv;
+        for (int k = lane; k < P; k += 64) a_in.out_w[k] = S.vx[k];
+        if (lane == 0) {
+            a_in.out_counts[0] = D.n_iter;
+            a_in.out_counts[1] = D.evals;
+            a_in.out_counts[2] = D.status;
+            for (int i = 3; i < 14; ++i) a_in.out_counts[i] = 0;
+            a_in.out_counts[7] = (int)(wall_clock64() - t_kernel0);
+            *a_in.out_loss = D.loss;
+        }
+        __threadfence_system();
+        if (lane == 0) __hip_atomic_store(a_in.done_flag, a_in.seqno, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+__global__ __launch_bounds__(1024) void k_fb_fit2_wg(FitWgArgs a_in) {
+    extern __shared__ double fit_lds[];
+    fit2_wg_body(fit_lds, a_in);
+}
+// one workgroup per table entry, each on its own engine's buffers and completion word (cf. k_fb_fit_wg_batch)
+__global__ __launch_bounds__(1024) void k_fb_fit2_wg_batch(const FitWgArgs *__restrict__ table) {
+    extern __shared__ double fit_lds[];
+    const FitWgArgs a_in = table[blockIdx.x];
+    fit2_wg_body(fit_lds, a_in);
+}
+
 // the 160 KB dynamic-LDS attribute of the fit kernel `kern` (batch: k_fb_fit_wg_batch), once per (device, kernel)
 ssw_status fb_fit_wg_attr(const void *kern, int device, int dim, bool batch) {
     static bool attr_done[64][4] = {};
@@ -1056,6 +1304,49 @@ ssw_status fb_batch_reserve(ssw_fb *fb, int nfit) {
     SSW_HIP_TRY(hipMalloc((void **)&fb->batch_tab, (size_t)cap * sizeof(FitWgArgs)));
     SSW_HIP_TRY(hipMalloc((void **)&fb->batch_w, (size_t)cap * (fb->dim + 1) * sizeof(float)));
     fb->batch_cap = cap;
+    return SSW_OK;
+}
+
+// ---- the two-output fit's host side (ssw_fb_fit2_batch) ------------------------------------------
+bool fb_fit2_wg_eligible(const ssw_fb *fb) {
+    return fb->n <= FIT_WG_MAX_ROWS && 2 * fb->dim <= 1024 && !getenv("SSW_FB_HOST_DRIVER");
+}
+
+// the arguments of one k_fb_fit2_wg workgroup; takes the engine's next sequence number.  w0_dev: [2 dim] on the device
+void fb_fit2_wg_fill(ssw_fb *fb, float l_norm, float l_query, int max_iter, float lr, const float *w0_dev, FitWgArgs *out) {
+    FitWgArgs a;
+    memset(&a, 0, sizeof(a));
+    a.X = fb->X; a.y = fb->y2; a.coef = fb->sw2;
+    a.qhat = fb->qhat;
+    a.w0_or_null = w0_dev;
+    a.hist_dirs = fb->hist;
+    a.hist_stps = fb->hist + (size_t)FIT_HISTORY * 1024;
+    a.out_w = fb->out_host_dev + 1;
+    a.out_loss = fb->loss_host_dev;
+    a.out_counts = reinterpret_cast<int *>(fb->flag_host_dev) + 4;
+    a.done_flag = fb->flag_host_dev;
+    a.seqno = ++fb->seqno;
+    a.n = (int)fb->n; a.dim2 = fb->dim; a.plane2 = (int)fb->cap2;
+    a.dim = 2 * fb->dim - 1; a.P = 2 * fb->dim;  // the driver step's view: 2 dim parameters, none unused
+    a.max_iter = max_iter; a.lr = lr;
+    a.obj.l_norm = l_norm; a.obj.l_query = l_query;
+    *out = a;
+}
+
+ssw_status fb_fit2_wg_launch(ssw_fb *lead, const FitWgArgs *tab_host, int nwg) {
+    static bool attr_done[64][2] = {};
+    const bool batch = nwg > 1;
+    const void *kern = batch ? reinterpret_cast<const void *>(k_fb_fit2_wg_batch) : reinterpret_cast<const void *>(k_fb_fit2_wg);
+    const int dslot = lead->device >= 0 && lead->device < 64 ? lead->device : -1;
+    if (dslot < 0 || !attr_done[dslot][batch]) {
+        SSW_HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        if (dslot >= 0) attr_done[dslot][batch] = true;
+    }
+    if (batch)
+        hipLaunchKernelGGL(k_fb_fit2_wg_batch, dim3(nwg), dim3(1024), FIT2_LDS_BYTES, lead->stream, (const FitWgArgs *)lead->batch_tab);
+    else
+        hipLaunchKernelGGL(k_fb_fit2_wg, dim3(1), dim3(1024), FIT2_LDS_BYTES, lead->stream, tab_host[0]);
+    SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
 }
 

@@ -22,7 +22,8 @@ double g_fit_eval_s = 0;
 bool Evaluator::eval(const std::vector<float> &x, double t, const std::vector<float> &d, double *f, std::vector<float> *g) {
     for (int i = 0; i < P; ++i) fb->w_host[i] = x[i] + (float)t * d[i];
     const auto t0 = std::chrono::steady_clock::now();
-    status = two ? fb_eval2(fb, l_norm2, l_query2, nullptr) : fb_eval(fb, o, dev, pw, pairwise_active, P);
+    status = two ? (two_dev ? fb_eval2_dev(fb, l_norm2, l_query2, nullptr) : fb_eval2(fb, l_norm2, l_query2, nullptr))
+                 : fb_eval(fb, o, dev, pw, pairwise_active, P);
     g_fit_eval_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (status != SSW_OK) return false;
     *f = fb->loss_host[0];

@@ -219,6 +219,65 @@ class FeedbackEngine:
                   ctypes.byref(loss), _p(grad), _p(parts))
         return float(loss.value), grad, parts
 
+    def lossgrad2_dev(self, W: np.ndarray, reg_norm_lambda: float, reg_query_lambda: float):
+        """`lossgrad2` with the whole evaluation on the device (ssw_fb_lossgrad2_dev): same outputs, the values within
+        the device library's logf / coshf / sinhf of it"""
+        W = np.ascontiguousarray(np.asarray(W), dtype=np.float32)
+        assert W.shape == (2, self.dim)
+        loss = ctypes.c_float(0)
+        grad = np.empty((2, self.dim), dtype=np.float32)
+        parts = np.empty(5, dtype=np.float32)
+        _lib.call("ssw_fb_lossgrad2_dev", self._h, _p(W), float(reg_norm_lambda), float(reg_query_lambda),
+                  ctypes.byref(loss), _p(grad), _p(parts))
+        return float(loss.value), grad, parts
+
+    @staticmethod
+    def fit2_batch(engines, W0s, reg_norm_lambdas, reg_query_lambdas, max_iters, lrs):
+        """The two-output fit over the device evaluation for several engines in one launch and one host wait
+        (ssw_fb_fit2_batch; one engine = the single device fit).  Returns one entry per slot: `(W [2, dim], info)`, or
+        -- for a slot whose loss or weights diverged -- the SeesawHipError a single fit would have raised (the other
+        slots have their results).  Engines must be distinct and of one dim and device; a slot of more than 1024 rows
+        is driven from the host after the launch, one device evaluation at a time (`info["on_device"]` is False)."""
+        engines = list(engines)
+        nfit = len(engines)
+        if not (len(W0s) == len(reg_norm_lambdas) == len(reg_query_lambdas) == len(max_iters) == len(lrs) == nfit):
+            raise ValueError("fit2_batch: every argument must have one entry per slot")
+        dim = max((e.dim for e in engines), default=0)  # engines of unequal dim are refused by the library, by name
+        W = np.zeros((max(nfit, 1), 2, dim), dtype=np.float32)
+        for s, W0 in enumerate(W0s):
+            W0 = np.asarray(W0, dtype=np.float32)
+            assert W0.shape == (2, engines[s].dim)
+            W[s, :, :W0.shape[1]] = W0
+        handles = (ctypes.c_void_p * max(nfit, 1))(*[e._h for e in engines])
+        ln = np.ascontiguousarray(reg_norm_lambdas, dtype=np.float32).reshape(-1)
+        lq = np.ascontiguousarray(reg_query_lambdas, dtype=np.float32).reshape(-1)
+        mi = np.ascontiguousarray(max_iters, dtype=np.int32).reshape(-1)
+        lr = np.ascontiguousarray(lrs, dtype=np.float32).reshape(-1)
+        iters, evals = np.zeros(max(nfit, 1), np.int32), np.zeros(max(nfit, 1), np.int32)
+        loss, status = np.zeros(max(nfit, 1), np.float32), np.zeros(max(nfit, 1), np.int32)
+        as_f32 = lambda a: a.ctypes.data_as(_lib.c_f32_p)  # noqa: E731
+        as_i32 = lambda a: a.ctypes.data_as(_lib.c_i32_p)  # noqa: E731
+        _lib.call("ssw_fb_fit2_batch", handles, nfit, as_f32(W), as_f32(ln), as_f32(lq), as_i32(mi), as_f32(lr),
+                  as_i32(iters), as_i32(evals), as_f32(loss), as_i32(status))
+        out = []
+        for s, eng in enumerate(engines):
+            if status[s] != _lib.SSW_OK:
+                msg = _lib.load().ssw_fb_batch_error(eng._h)
+                out.append(_lib.SeesawHipError(int(status[s]), msg.decode("utf-8", "replace") if msg else ""))
+                continue
+            on_dev = ctypes.c_int32(0)
+            _lib.call("ssw_fb_last_fit_on_device", eng._h, ctypes.byref(on_dev))
+            out.append((W[s].copy(), {"n_iter": int(iters[s]), "func_evals": int(evals[s]), "loss": float(loss[s]),
+                                      "on_device": bool(on_dev.value)}))
+        return out
+
+    def fit2_dev(self, W0: np.ndarray, reg_norm_lambda: float, reg_query_lambda: float, max_iter: int, lr: float = 1.0):
+        """`fit2` over the device evaluation: the whole fit in one launch for sets of up to 1024 rows"""
+        (r,) = FeedbackEngine.fit2_batch([self], [W0], [reg_norm_lambda], [reg_query_lambda], [max_iter], [lr])
+        if isinstance(r, _lib.SeesawHipError):
+            raise r
+        return r
+
     def fit2(self, W0: np.ndarray, reg_norm_lambda: float, reg_query_lambda: float, max_iter: int, lr: float = 1.0):
         W = np.array(np.asarray(W0), dtype=np.float32)
         assert W.shape == (2, self.dim)

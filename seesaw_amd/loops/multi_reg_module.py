@@ -3,6 +3,8 @@
 Row 0 of the weight matrix is the target query, row 1 the "confusion" class the user marked as not-the-target; the
 logits use the L2-normalised rows.  The reference is an nn.Module whose closure torch.optim.LBFGS re-evaluates through
 autograd; here `fit` hands the objective to the HIP feedback engine (ssw_fb_fit2) and the weights come back.
+With `fit_on_device=True` the evaluation runs entirely on the device and a fit of up to 1024 rows is one launch
+(ssw_fb_fit2_batch); `fit_batch` runs several modules' fits in that one launch.
 """
 from __future__ import annotations
 
@@ -35,7 +37,8 @@ def _dataloader_draws(n: int):
 
 class MultiRegModule:
     def __init__(self, *, qvec, qvec2=None, reg_norm_lambda, reg_query_lambda, verbose=False, max_iter=100, lr=1.0,
-                 dim: int = None, device: int = 0, engine: FeedbackEngine = None, weight0: np.ndarray = None):
+                 dim: int = None, device: int = 0, engine: FeedbackEngine = None, weight0: np.ndarray = None,
+                 fit_on_device: bool = False):
         qvec = np.asarray(qvec, dtype=np.float32).reshape(-1)
         qn = float(np.linalg.norm(qvec))
         assert not math.isclose(qn, 0.0)
@@ -47,6 +50,7 @@ class MultiRegModule:
         self.reg_query_lambda, self.reg_norm_lambda = float(reg_query_lambda), float(reg_norm_lambda)
         self._engine = engine or FeedbackEngine(self.dim, device=device)
         self._engine.set_query(self.qvec)
+        self.fit_on_device = bool(fit_on_device)
         self.info_ = None
 
     def get_coeff(self):
@@ -74,20 +78,51 @@ class MultiRegModule:
 
     def lossgrad(self, W=None):
         """one closure evaluation on the installed rows (tests / diagnostics)"""
-        return self._engine.lossgrad2(self.weight if W is None else W, self.reg_norm_lambda, self.reg_query_lambda)
+        f = self._engine.lossgrad2_dev if self.fit_on_device else self._engine.lossgrad2
+        return f(self.weight if W is None else W, self.reg_norm_lambda, self.reg_query_lambda)
 
-    def fit(self, X, y, matchdf, index=None, rows=None):
+    def _stage(self, X, y, matchdf, index=None, rows=None):
+        """the rows and targets of one fit onto this module's engine, and the reference's generator draws"""
         n = len(y)
         if n == 0:  # the reference's _step has no label term to evaluate without rows and raises (multi_reg_module.py:110)
             raise AssertionError("MultiRegModule.fit needs at least one labelled vector")
         self._install(X, y, matchdf, index=index, rows=rows)
         _dataloader_draws(n)
-        try:
-            W, info = self._engine.fit2(self.weight, self.reg_norm_lambda, self.reg_query_lambda, max_iter=self.max_iter,
-                                        lr=self.lr)
-        except _lib.SeesawHipError as e:
-            raise AssertionError(f"regression training failed: {e}") from e
+
+    def _finish(self, W, info):
+        """take a fit's result; `W` may be the SeesawHipError of a fit that diverged"""
+        if isinstance(W, _lib.SeesawHipError):
+            raise AssertionError(f"regression training failed: {W}") from W
         assert not np.isnan(W).any()
         self.weight = W
         self.info_ = info
         return [{"k": "loss", "loss": info["loss"]}]
+
+    def fit(self, X, y, matchdf, index=None, rows=None):
+        self._stage(X, y, matchdf, index=index, rows=rows)
+        fit2 = self._engine.fit2_dev if self.fit_on_device else self._engine.fit2
+        try:
+            W, info = fit2(self.weight, self.reg_norm_lambda, self.reg_query_lambda, max_iter=self.max_iter, lr=self.lr)
+        except _lib.SeesawHipError as e:
+            W, info = e, None
+        return self._finish(W, info)
+
+    @staticmethod
+    def fit_batch(models):
+        """The fits of several modules built with `fit_on_device=True`, each already staged (`_stage`), with ONE engine
+        call (FeedbackEngine.fit2_batch): every module ends as its own `fit` would have left it.  Staging is the
+        caller's because the reference's generator draws interleave: a module's start weights, then its loader's
+        draws, then the next module's.  Returns one entry per module: what `fit` returns, or the AssertionError it
+        would have raised."""
+        models = list(models)
+        assert all(m.fit_on_device for m in models), "fit_batch serves modules that opted in to the device fit"
+        res = FeedbackEngine.fit2_batch([m._engine for m in models], [m.weight for m in models],
+                                        [m.reg_norm_lambda for m in models], [m.reg_query_lambda for m in models],
+                                        [m.max_iter for m in models], [m.lr for m in models])
+        out = []
+        for m, r in zip(models, res):
+            try:
+                out.append(m._finish(r, None) if isinstance(r, _lib.SeesawHipError) else m._finish(*r))
+            except AssertionError as e:
+                out.append(e)
+        return out

@@ -19,6 +19,9 @@ class MultiRegNeg(PointBased):
         if self.options.get("matrix_options") is not None:
             self.xlx_matrix = get_weight_matrix_from_index(q.index, self.options["matrix_options"], xlx_matrix=True)
         self.confusion_vec = None
+        # opt-in: the fit's closure evaluated entirely on the device, a session-sized fit in one launch, and a
+        # SessionGroup refines such loops together; absent or false is the host-tailed fit (ssw_fb_fit2)
+        self.fit_on_device = bool(self.options.get("fit_on_device", False))
         self._engine = FeedbackEngine(q.index.vectors.shape[1], device=getattr(q.index, "device", 0))
 
     def set_text_vec(self, tvec):
@@ -28,7 +31,7 @@ class MultiRegNeg(PointBased):
         else:
             self.curr_vec = self.curr_qvec
 
-    def refine(self, change=None):
+    def _fit_args(self):
         matchdf = self.q.getXy(target_description=None)
         rows = matchdf.index.values
         y = matchdf.ys.values
@@ -43,18 +46,53 @@ class MultiRegNeg(PointBased):
         ys = np.stack([y, yconf], axis=1).astype("float32")
         assert ys.shape[0] == y.shape[0] and ys.shape[1] == 2
         print(f"{ys.sum(axis=0)=}")
-        assert self.curr_qvec is not None
-        o = self.options
-        model = MultiRegModule(qvec=self.curr_qvec, reg_norm_lambda=o["reg_norm_lambda"],
-                               reg_query_lambda=o["reg_query_lambda"], verbose=o["verbose"], max_iter=int(o["max_iter"]),
-                               lr=o["lr"], dim=self.q.index.vectors.shape[1], engine=self._engine)
         dev = getattr(self.q.index, "_dev", None)
         if dev is not None:  # labelled rows are gathered out of the resident index, no upload
-            model.fit(None, ys, matchdf, index=dev, rows=rows)
-        else:
-            model.fit(self.q.index.vectors[rows], ys, matchdf)
+            return (None, ys, matchdf, dev, rows)
+        return (self.q.index.vectors[rows], ys, matchdf, None, None)
+
+    def _model(self):
+        assert self.curr_qvec is not None
+        o = self.options
+        return MultiRegModule(qvec=self.curr_qvec, reg_norm_lambda=o["reg_norm_lambda"],
+                              reg_query_lambda=o["reg_query_lambda"], verbose=o["verbose"], max_iter=int(o["max_iter"]),
+                              lr=o["lr"], dim=self.q.index.vectors.shape[1], engine=self._engine,
+                              fit_on_device=self.fit_on_device)
+
+    def refine(self, change=None):
+        args = self._fit_args()
+        model = self._model()
+        model.fit(*args)
         self.curr_vec = model.get_coeff()
         self.confusion_vec = model.get_confusion_coeff()
+
+    @classmethod
+    def refine_batch(cls, loops):
+        """`for l in loops: l.refine()` for loops that opted in (`fit_on_device`), with one batched fit
+        (MultiRegModule.fit_batch): loop by loop the labels are read, the module is built and staged on the loop's own
+        engine -- the order of the log lines and of the generator draws of the single calls -- then one launch fits
+        them all and every `curr_vec` / `confusion_vec` is set.  A loop whose fit raised surfaces its AssertionError
+        after the other loops have got their vectors.  (`next_batch` with `vector2` stays per session: batching the
+        two-vector query is out of scope here.)"""
+        loops = list(loops)
+        if not loops:
+            return
+        models = []
+        for l in loops:
+            assert l.fit_on_device, "refine_batch serves loops that opted in to the device fit"
+            args = l._fit_args()
+            m = l._model()
+            m._stage(*args)
+            models.append(m)
+        failed = None
+        for l, m, r in zip(loops, models, MultiRegModule.fit_batch(models)):
+            if isinstance(r, AssertionError):
+                failed = failed or r
+                continue
+            l.curr_vec = m.get_coeff()
+            l.confusion_vec = m.get_confusion_coeff()
+        if failed is not None:
+            raise failed
 
     def next_batch(self):
         dim = self.q.index.vectors.shape[1]

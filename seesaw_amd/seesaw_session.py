@@ -256,8 +256,12 @@ class SessionGroup:
       `shortlist_size`, `agg_method` and `aug_larger` are served by ONE `index.query_batch` -- one pass over the rows;
       every other session calls its own `next()`.
     * `refine()`: every session's start-policy gate runs as in `LoopBase.refine_external`; the started `MultiReg`
-      loops go through ONE `MultiReg.refine_batch` -- one launch, one host wait; every other loop through its own
-      `refine_external`.
+      loops go through ONE `MultiReg.refine_batch` -- one launch, one host wait -- and the started `MultiRegNeg` loops
+      whose options say `fit_on_device` through ONE `MultiRegNeg.refine_batch`, a launch of their own; every other
+      loop, a `MultiRegNeg` that did not opt in included, through its own `refine_external`.  The batches refine
+      first, the remaining sessions after them in session order: loops that draw from torch's global generator (every
+      `MultiRegNeg` refine draws its start weights) keep the draws of the one-by-one order when the opted-in loops
+      stand before the others in `sessions`.  `MultiRegNeg`'s `next()` with `vector2` stays per session.
 
     Every session ends each call in the state its own `next()` / `refine()` would have left: `returned`, `timing`
     (the shared call's time for each member), `acc_indices`, `acc_activations`, the log, `curr_vec` -- bit for bit.
@@ -301,17 +305,22 @@ class SessionGroup:
         return [tuple(g) for g in groups]
 
     def fit_groups(self):
-        """([positions that refine through one MultiReg.refine_batch, ...], [positions that refine on their own]),
-        for loops that have started; the gate is `refine()`'s"""
+        """([positions that refine through one refine_batch, ...], [positions that refine on their own]), for loops
+        that have started; the gate is `refine()`'s.  A group holds `MultiReg` loops, or `MultiRegNeg` loops that opted
+        in with `fit_on_device` -- never both: the two objectives take launches of their own -- of one (dim, device)."""
         from .loops.loop_base import LoopBase
         from .loops.multi_reg import MultiReg
+        from .loops.multi_reg_neg import MultiRegNeg
         batched, alone = {}, []
         for i, s in enumerate(self.sessions):
             loop = s.loop
             cls = type(loop)
-            if isinstance(loop, MultiReg) and cls.refine is MultiReg.refine and \
-                    cls.refine_external is LoopBase.refine_external and loop.started:
-                batched.setdefault((loop._engine.dim, loop._engine.device), []).append(i)
+            own_gate = cls.refine_external is LoopBase.refine_external and loop.started
+            if isinstance(loop, MultiReg) and cls.refine is MultiReg.refine and own_gate:
+                batched.setdefault((MultiReg, loop._engine.dim, loop._engine.device), []).append(i)
+            elif isinstance(loop, MultiRegNeg) and cls.refine is MultiRegNeg.refine and own_gate and \
+                    getattr(loop, "fit_on_device", False):
+                batched.setdefault((MultiRegNeg, loop._engine.dim, loop._engine.device), []).append(i)
             else:
                 alone.append(i)
         return [tuple(g) for g in batched.values()], alone
@@ -351,8 +360,10 @@ class SessionGroup:
     def refine(self):
         """`for s in sessions: s.refine()`"""
         from .loops.multi_reg import MultiReg
+        from .loops.multi_reg_neg import MultiRegNeg
         for s in self.sessions:  # the gate of LoopBase.refine_external
-            if not s.loop.started and isinstance(s.loop, MultiReg):
+            if not s.loop.started and (isinstance(s.loop, MultiReg) or
+                                       (isinstance(s.loop, MultiRegNeg) and getattr(s.loop, "fit_on_device", False))):
                 s.loop.started = s.loop._start_condition()
         batched, alone = self.fit_groups()
         for group in batched:
@@ -363,7 +374,7 @@ class SessionGroup:
             for s in members:
                 s._log("refine.start")
                 print("start condition met... refinining custom method...")
-            MultiReg.refine_batch([s.loop for s in members])
+            type(members[0].loop).refine_batch([s.loop for s in members])
             for s in members:
                 s._log("refine.end")
         for i in sorted(alone):
