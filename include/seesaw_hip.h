@@ -348,6 +348,36 @@ ssw_status ssw_index_topk_batch_avg_pruned(ssw_index *idx, const float *q_host, 
                                            int64_t *out_images, float *out_scores, int64_t *out_best_rows,
                                            float *out_avg_scores, int64_t *out_avg_rows, int32_t *out_counts);
 
+/* The SECOND STAGE of a batch of TWO-VECTOR queries (`query(vector=, vector2=)`, seesaw/indices/multiscale/
+ * multiscale_index.py:341-352: `scores = vectors[ilocs] @ vector`, `scores -= vectors[ilocs] @ vector2`, then
+ * rescore_candidates), for nq queries in ONE launch (k_pair_score, csrc/rescore.hip; DESIGN.md section 4, "Batched
+ * two-vector query").  image_positions_host [nq, k] / counts_host [nq]: query b's candidates are its first counts_host[b]
+ * entries (positions as ssw_index_topk_batch returns them, any order).  For query b and slot c < counts_host[b] the tiles
+ * of that image are scored straight from the index rows, each row read once: v = the bits of ssw_index_scan(q_host[b]),
+ * v2 = the bits of ssw_index_score_rows(q2_host[b]), d = v - v2 in f32, and aggregated:
+ *   agg = SSW_AGG_AVG:   as ssw_index_rescore_avg aggregates the resident scores of q_host[b] with minus_scores = v2
+ *                        (aug_larger: its codes, 0 / 1 / 2, optionally + 4);
+ *   agg = SSW_AGG_PLAIN: the image's first tile with the highest non-NaN d (rescore_candidates' plain_score branch); an
+ *                        image whose every d is NaN gives its first row, score NaN.  aug_larger is ignored.
+ * out_scores / out_best_rows [nq, k]: entry [b, c] for c < counts_host[b]; entries from counts_host[b] on are LEFT AS
+ * THEY WERE.  Host data in, host data out: one copy up (both query blocks, the positions, the counts), one launch, one
+ * copy down, one host wait, on the handle's stream; the staging blocks are allocated by the first call and grown by a
+ * larger one (ssw_index_destroy frees them).
+ * Refused on the host before anything is enqueued: a view (SSW_ERR_UNSUPPORTED, the message says "view"); agg =
+ * SSW_AGG_AVG on an index without tile meta, dim other than 256 / 512 / 768 / 1024, an image of more than 2048 tiles
+ * anywhere in the index (SSW_ERR_UNSUPPORTED); nq outside [1, 65535], k outside [1, SSW_MAX_TOPK], a bad agg or
+ * aug_larger, no image map, a count outside [0, k], a listed position outside the index, NULL arguments
+ * (SSW_ERR_INVALID); a non-finite component in either query block (SSW_ERR_NUMERIC).
+ * State afterwards is the state before, as for ssw_index_stage2_avg_batch_dev: the score buffer (partial or complete,
+ * with its kept query), the result buffers, the installed exclusion set and the counters of ssw_index_prune_stats /
+ * ssw_index_prune_completions stay as they were, so it follows a plain and a pruned first stage alike and never causes
+ * a completing full scan. */
+#define SSW_AGG_PLAIN 0
+#define SSW_AGG_AVG 1
+ssw_status ssw_index_stage2_pair_batch(ssw_index *idx, const float *q_host, const float *q2_host, int32_t nq,
+                                       const int64_t *image_positions_host, const int32_t *counts_host, int32_t k,
+                                       int32_t agg, int32_t aug_larger, float *out_scores, int64_t *out_best_rows);
+
 /* merge several sorted key lists (e.g. the all-gathered per-shard top-k of a
  * row-sharded index; keys as in ssw_index_result_ptrs but with GLOBAL image ids
  * added by the caller via id_offsets) into the global top-k.  All pointers device. */

@@ -163,6 +163,8 @@ _SIGNATURES = {
                                               c_void_p, c_void_p, c_void_p]),
     "ssw_index_stage2_avg_batch_dev": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_i64,
                                                c_i64, c_void_p]),
+    "ssw_index_stage2_pair_batch": (c_i32, [c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_i32, c_i32,
+                                            c_void_p, c_void_p]),
     "ssw_comm_unique_id": (c_i32, [c_void_p]),
     "ssw_comm_create": (c_i32, [c_i32, c_void_p, c_i32, c_i32, ctypes.POINTER(c_void_p)]),
     "ssw_comm_destroy": (c_i32, [c_void_p]),

@@ -264,6 +264,7 @@ ssw_status ssw_index_destroy(ssw_index *idx) {
     idx->prune.release();
     idx->batch.release();
     idx->prune_batch.release();
+    idx->pair.release();
     if (idx->owns_X) (void)hipFree(idx->X);
     (void)hipFree(idx->xfer);
     (void)hipFree(idx->scores);

@@ -4,6 +4,7 @@
 // the side slabs; the selection then runs slab by slab through the single-query path (topk_enqueue / topk_collect).
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 
 #include "index_handle.h"
 
@@ -529,6 +530,100 @@ extern "C" ssw_status ssw_index_stage2_avg_batch_dev(ssw_index *idx, const float
         a.image_offset = image_offset, a.row_offset = row_offset;
         a.out = dev_out + (size_t)b * 2 * k_max;
         SSW_TRY(launch_avg_score_owner(idx->X, idx->dtype, idx->dim, a, idx->stream));
+    }
+    return SSW_OK;
+}
+
+// The second stage of a batch of two-vector queries on this handle (k_pair_score, rescore.hip): host data in, host data
+// out, ONE copy up, ONE launch, ONE copy down, ONE host wait.  Like the entry above it reads the rows, the image map and
+// (avg) the tile meta and nothing else.
+extern "C" ssw_status ssw_index_stage2_pair_batch(ssw_index *idx, const float *q_host, const float *q2_host, int32_t nq,
+                                                  const int64_t *image_positions_host, const int32_t *counts_host,
+                                                  int32_t k, int32_t agg, int32_t aug_larger, float *out_scores,
+                                                  int64_t *out_best_rows) {
+    SSW_REQUIRE(idx != nullptr, "idx is NULL");
+    SSW_TRY(refuse_view(idx, "ssw_index_stage2_pair_batch"));  // k_pair_score scores tiles from the matrix by row
+    SSW_REQUIRE(nq >= 1 && nq <= 65535, "nq=%d outside [1, 65535]", nq);
+    SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
+    SSW_REQUIRE(agg == SSW_AGG_PLAIN || agg == SSW_AGG_AVG, "agg=%d is not 0 (plain_score) or 1 (avg_score)", agg);
+    SSW_REQUIRE(q_host && q2_host && image_positions_host && counts_host && out_scores && out_best_rows, "NULL argument");
+    SSW_REQUIRE(idx->has_map, "stage2_pair_batch needs ssw_index_set_row2image first");
+    if (agg == SSW_AGG_AVG) {
+        SSW_TRY(check_aug_code(aug_larger));
+        if (!idx->tile_boxes || !idx->tile_zoom) {
+            set_error("stage2_pair_batch: the avg_score aggregation needs ssw_index_set_tile_meta first");
+            return SSW_ERR_UNSUPPORTED;
+        }
+    }
+    if (idx->dim != 256 && idx->dim != 512 && idx->dim != 768 && idx->dim != 1024) {
+        set_error("stage2_pair_batch: dim=%d unsupported", idx->dim);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    const int64_t max_tiles = max_image_tiles(idx);
+    if (max_tiles > SSW_RESCORE_MAX_TILES) {
+        set_error("stage2_pair_batch: the index has an image with %lld tiles, more than the %d the kernel takes",
+                  (long long)max_tiles, SSW_RESCORE_MAX_TILES);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    for (int32_t b = 0; b < nq; ++b) {
+        SSW_REQUIRE(counts_host[b] >= 0 && counts_host[b] <= k, "counts[%d]=%d outside [0, k=%d]", b, counts_host[b], k);
+        for (int32_t c = 0; c < counts_host[b]; ++c) {
+            const int64_t p = image_positions_host[(size_t)b * k + c];
+            SSW_REQUIRE(p >= 0 && p < idx->n_images, "image position %lld (query %d, slot %d) outside [0, %lld)",
+                        (long long)p, b, c, (long long)idx->n_images);
+        }
+    }
+    SSW_TRY(check_query_batch(idx, q_host, nq));
+    SSW_TRY(check_query_batch(idx, q2_host, nq));
+    DeviceGuard guard(idx->device);
+    // the block: [positions i64 nq k | q f32 nq dim | q2 f32 nq dim | counts i32 nq] [rows i64 nq k | scores f32 nq k],
+    // the query blocks (read as float4) and the outputs on 16-byte boundaries
+    const size_t slots = (size_t)nq * k, qbytes = (size_t)nq * idx->dim * sizeof(float);
+    const size_t off_q = (slots * 8 + 15) & ~(size_t)15, off_q2 = off_q + qbytes, off_cnt = off_q2 + qbytes;
+    const size_t in_bytes = (off_cnt + (size_t)nq * 4 + 15) & ~(size_t)15;
+    const size_t off_score = in_bytes + slots * 8, total = off_score + slots * 4;
+    PairStage &ps = idx->pair;
+    hipStream_t s = idx->stream;
+    if (total > ps.cap) {
+        SSW_HIP_TRY(hipStreamSynchronize(s));
+        ps.release();
+        size_t cap = (size_t)1 << 16;
+        while (cap < total) cap <<= 1;
+        if (hipHostMalloc((void **)&ps.host, cap) != hipSuccess || hipMalloc((void **)&ps.dev, cap) != hipSuccess) {
+            (void)hipGetLastError();
+            ps.release();
+            set_error("stage2_pair_batch: no memory for the %zu-byte staging blocks", cap);
+            return SSW_ERR_NOMEM;
+        }
+        ps.cap = cap;
+    }
+    memcpy(ps.host, image_positions_host, slots * 8);
+    memcpy(ps.host + off_q, q_host, qbytes);
+    memcpy(ps.host + off_q2, q2_host, qbytes);
+    memcpy(ps.host + off_cnt, counts_host, (size_t)nq * 4);
+    SSW_HIP_TRY(hipMemcpyAsync(ps.dev, ps.host, in_bytes, hipMemcpyHostToDevice, s));
+    PairScoreArgs a;
+    a.qb = reinterpret_cast<const float *>(ps.dev + off_q);
+    a.q2b = reinterpret_cast<const float *>(ps.dev + off_q2);
+    a.boxes = idx->tile_boxes;
+    a.zoom = idx->tile_zoom;
+    a.row_start = idx->row_start;
+    a.n_images = idx->n_images;
+    a.pos = reinterpret_cast<const int64_t *>(ps.dev);
+    a.counts = reinterpret_cast<const int32_t *>(ps.dev + off_cnt);
+    a.nq = nq, a.k = k, a.max_tiles = (int32_t)max_tiles, a.aug = agg == SSW_AGG_AVG ? aug_larger : 0;
+    a.avg = agg == SSW_AGG_AVG;
+    a.out_row = reinterpret_cast<int64_t *>(ps.dev + in_bytes);
+    a.out_score = reinterpret_cast<float *>(ps.dev + off_score);
+    SSW_TRY(launch_pair_score(idx->X, idx->dtype, idx->dim, a, s));
+    SSW_HIP_TRY(hipMemcpyAsync(ps.host + in_bytes, ps.dev + in_bytes, total - in_bytes, hipMemcpyDeviceToHost, s));
+    SSW_HIP_TRY(hipStreamSynchronize(s));
+    const int64_t *rows = reinterpret_cast<const int64_t *>(ps.host + in_bytes);
+    const float *scores = reinterpret_cast<const float *>(ps.host + off_score);
+    for (int32_t b = 0; b < nq; ++b) {  // slots at or past the count stay the caller's
+        const size_t o = (size_t)b * k, m = (size_t)counts_host[b];
+        memcpy(out_scores + o, scores + o, m * 4);
+        memcpy(out_best_rows + o, rows + o, m * 8);
     }
     return SSW_OK;
 }

@@ -116,6 +116,19 @@ struct BatchState {
     }
 };
 
+// ssw_index_stage2_pair_batch: one pinned host block and its device mirror, [inputs | outputs] of one call; allocated
+// by the first call, grown by a larger one
+struct PairStage {
+    unsigned char *host = nullptr, *dev = nullptr;
+    size_t cap = 0;
+    void release() {
+        if (host) (void)hipHostFree(host);
+        (void)hipFree(dev);
+        host = dev = nullptr;
+        cap = 0;
+    }
+};
+
 struct ssw_index {
     int device = 0;
     int64_t n = 0;
@@ -178,6 +191,7 @@ struct ssw_index {
     bool scores_partial = false;
     BatchState batch;
     PruneBatchState prune_batch;
+    PairStage pair;
     // profiling of the scan kernel
     bool profiling = false;
     std::vector<hipEvent_t> ev;  // pairs

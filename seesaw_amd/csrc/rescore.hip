@@ -305,6 +305,91 @@ __global__ __launch_bounds__(RS_THREADS) void k_avg_score_owner(
     });
 }
 
+// The second stage of a batch of TWO-VECTOR queries (the `vector2` form of MultiscaleIndex.query; DESIGN.md section 4,
+// "Batched two-vector query").  grid (k, nq): workgroup (c, b) takes candidate image pos[b * k + c] of query b; a slot
+// at or past counts[b] writes nothing and touches no row, box or row_start.  Like the owner kernel it needs no score
+// buffer: wave w scores tiles w, w + 4, ... straight from the index rows, two rows in flight, each row loaded ONCE for
+// both fragments -- v the scan's bits for qb[b], v2 launch_score_rows' bits for q2b[b] -- and keeps d = v - v2, one f32
+// subtraction (numpy's gather_scores(rows) - score_rows(vector2, rows)).
+//   AVG:   d goes to sscore and the shared aggregation does the rest: launch_avg_score with the minus form on a handle
+//          whose resident scores are qb[b]'s.
+//   plain: the first tile attaining the maximum of the non-NaN d (np.lexsort((arange, -s, dbidx)) in
+//          rescore_candidates' plain branch); an image whose every d is NaN gives its first row and that row's d.
+//          No dynamic LDS, no box and no zoom level is read.
+// out_score / out_row [nq, k].
+template <class R, int C, bool AVG>
+__global__ __launch_bounds__(RS_THREADS) void k_pair_score(
+    const typename R::T *__restrict__ X, const float *__restrict__ qb, const float *__restrict__ q2b,
+    const float4 *__restrict__ boxes, const int32_t *__restrict__ zoom, const int64_t *__restrict__ row_start,
+    int64_t n_images, const int64_t *__restrict__ pos, const int32_t *__restrict__ counts, int k, int aug,
+    float *__restrict__ out_score, int64_t *__restrict__ out_row) {
+    constexpr int WAVES = RS_THREADS / 64;
+    const int c = blockIdx.x, b = blockIdx.y;
+    if (c >= counts[b]) return;
+    const size_t slot = (size_t)b * k + c;
+    const int64_t p = pos[slot];
+    if (p < 0 || p >= n_images) return;  // (the host refused such a list: the LDS is sized for this index's images only)
+    const int64_t r0 = row_start[p];
+    const int T = (int)(row_start[p + 1] - r0);
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const rows::Frag<C> qf = rows::load_query<C>(qb + (size_t)b * (C * 256), lane);
+    const rows::Frag<C> q2f = rows::load_query<C>(q2b + (size_t)b * (C * 256), lane);
+    AvgLds<float> l = {};
+    if constexpr (AVG) {
+        l = avg_lds<float>(T);
+        avg_score_fill<float, false>(l, boxes, zoom, nullptr, nullptr, r0, T);
+    }
+    // plain: this wave's first maximum among its tiles (ascending), every lane the same; wave 0 also keeps tile 0's d
+    float bv = 0.f, d_first = 0.f;
+    int bi = -1;
+    for (int i = w; i < T; i += 2 * WAVES) {
+        const int i1 = i + WAVES;
+        const bool two = i1 < T;
+        const rows::Frag<C> x0 = R::template load<C>(X, r0 + i, lane);
+        const rows::Frag<C> x1 = R::template load<C>(X, r0 + (two ? i1 : i), lane);
+        const float d0 = __fsub_rn(rows::wave_sum(rows::lane_partial<C>(x0, qf)), rows::wave_sum(rows::lane_partial<C>(x0, q2f)));
+        const float d1 = __fsub_rn(rows::wave_sum(rows::lane_partial<C>(x1, qf)), rows::wave_sum(rows::lane_partial<C>(x1, q2f)));
+        if constexpr (AVG) {
+            if (lane == 0) {
+                l.sscore[i] = d0;
+                if (two) l.sscore[i1] = d1;
+            }
+        } else {
+            if (i == 0) d_first = d0;
+            if (d0 == d0 && (bi < 0 || d0 > bv)) bv = d0, bi = i;
+            if (two && d1 == d1 && (bi < 0 || d1 > bv)) bv = d1, bi = i1;
+        }
+    }
+    if constexpr (AVG) {
+        avg_score_from_lds<float>(l, T, aug, [&](float score, int tile) {
+            out_score[slot] = score;
+            out_row[slot] = r0 + tile;
+        });
+    } else {
+        __shared__ float wave_v[WAVES + 1];  // [WAVES]: tile 0's d
+        __shared__ int wave_i[WAVES];
+        if (lane == 0) {
+            wave_v[w] = bv;
+            wave_i[w] = bi;
+            if (w == 0) wave_v[WAVES] = d_first;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            float v = 0.f;
+            int t = -1;
+            for (int j = 0; j < WAVES; ++j) {  // the highest d; among equals the lowest tile
+                const int tj = wave_i[j];
+                if (tj < 0) continue;
+                const float vj = wave_v[j];
+                if (t < 0 || vj > v || (vj == v && tj < t)) v = vj, t = tj;
+            }
+            out_score[slot] = t >= 0 ? v : wave_v[WAVES];
+            out_row[slot] = r0 + (t >= 0 ? t : 0);
+        }
+    }
+}
+
 // The rows the aggregation above is about to read, as a list the gather scoring can take: candidate c's tiles at
 // rows_out[cand_off[c] ..).  One workgroup a candidate.
 __global__ __launch_bounds__(RS_THREADS) void k_candidate_tiles(const int64_t *__restrict__ row_start,
@@ -415,6 +500,41 @@ ssw_status launch_avg_score_owner(const void *X, int32_t dtype, int32_t dim, con
     }
 #undef SSW_AVG_OWNER
     set_error("avg_score_owner: dim=%d unsupported", dim);
+    return SSW_ERR_UNSUPPORTED;
+}
+
+template <class R, int C, bool AVG>
+static ssw_status launch_pair_score_t(const void *X, const PairScoreArgs &a, hipStream_t stream) {
+    size_t lds = 0;
+    if constexpr (AVG)
+        SSW_TRY(avg_score_lds(reinterpret_cast<const void *>(k_pair_score<R, C, true>), a.max_tiles, sizeof(float), &lds));
+    hipLaunchKernelGGL((k_pair_score<R, C, AVG>), dim3((unsigned)a.k, (unsigned)a.nq), dim3(RS_THREADS), lds, stream,
+                       static_cast<const typename R::T *>(X), a.qb, a.q2b, reinterpret_cast<const float4 *>(a.boxes), a.zoom,
+                       a.row_start, a.n_images, a.pos, a.counts, (int)a.k, (int)a.aug, a.out_score, a.out_row);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+ssw_status launch_pair_score(const void *X, int32_t dtype, int32_t dim, const PairScoreArgs &a, hipStream_t stream) {
+    if (a.nq <= 0 || a.k <= 0) return SSW_OK;
+    if (a.max_tiles > SSW_RESCORE_MAX_TILES) {  // both aggregations: the entry's one limit
+        set_error("pair_score: an image with %d tiles exceeds the %d the kernel takes", a.max_tiles, SSW_RESCORE_MAX_TILES);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    const bool h16 = dtype == SSW_DTYPE_F16;
+#define SSW_PAIR_SCORE(C)                                                                          \
+    return h16 ? (a.avg ? launch_pair_score_t<rows::H16Rows, C, true>(X, a, stream)                \
+                        : launch_pair_score_t<rows::H16Rows, C, false>(X, a, stream))              \
+               : (a.avg ? launch_pair_score_t<rows::F32Rows, C, true>(X, a, stream)                \
+                        : launch_pair_score_t<rows::F32Rows, C, false>(X, a, stream))
+    switch (dim) {
+        case 256: SSW_PAIR_SCORE(1);
+        case 512: SSW_PAIR_SCORE(2);
+        case 768: SSW_PAIR_SCORE(3);
+        case 1024: SSW_PAIR_SCORE(4);
+    }
+#undef SSW_PAIR_SCORE
+    set_error("pair_score: dim=%d unsupported", dim);
     return SSW_ERR_UNSUPPORTED;
 }
 

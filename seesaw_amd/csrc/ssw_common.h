@@ -569,6 +569,25 @@ struct AvgOwnerArgs {
     uint64_t *out;
 };
 ssw_status launch_avg_score_owner(const void *X, int32_t dtype, int32_t dim, const AvgOwnerArgs &args, hipStream_t stream);
+// the second stage of a batch of two-vector queries (k_pair_score): grid (k, nq); workgroup (c, b), c < counts[b], scores
+// the tiles of image pos[b * k + c] straight from the rows X for qb + b * dim and for q2b + b * dim, takes the
+// difference and aggregates it -- avg: as launch_avg_score with the minus form (aug: its code), plain: the first tile
+// with the highest non-NaN difference.  out_score / out_row [nq, k]; slots at or past counts[b] are not written.
+// boxes / zoom may be NULL for plain.  max_tiles = the most tiles of any image of the index.
+struct PairScoreArgs {
+    const float *qb, *q2b;  // [nq, dim] device
+    const float *boxes;
+    const int32_t *zoom;
+    const int64_t *row_start;
+    int64_t n_images;
+    const int64_t *pos;     // [nq, k] device
+    const int32_t *counts;  // [nq] device
+    int32_t nq, k, max_tiles, aug;
+    bool avg;
+    float *out_score;
+    int64_t *out_row;
+};
+ssw_status launch_pair_score(const void *X, int32_t dtype, int32_t dim, const PairScoreArgs &args, hipStream_t stream);
 // the rows those two launches read, as row lists for launch_score_rows: candidate c's tiles at rows_out[cand_off[c] ..)
 // (the candidates' tile total entries); slot c's at rows_out[c * max_tiles ..), padded with rows of the index to
 // k * max_tiles entries in all

@@ -398,6 +398,39 @@ class DeviceIndex:
         return [(imgs[b, :c].copy(), scs[b, :c].copy(), rows[b, :c].copy(), avg_scs[b, :c].copy(), avg_rows[b, :c].copy())
                 for b, c in enumerate(cnt.tolist())]
 
+    AGG_PLAIN, AGG_AVG = 0, 1  # ssw_index_stage2_pair_batch's `agg`
+
+    def stage2_pair(self, Q: np.ndarray, Q2: np.ndarray, positions: np.ndarray, counts: np.ndarray, agg: str,
+                    aug_larger: str = "all", aug_weight: str = "level_max", out=None):
+        """the second stage of a batch of two-vector queries in one launch (ssw_index_stage2_pair_batch): for query b
+        and each of its first `counts[b]` candidate images `positions[b, :]` (int64 [nq, k], any order), the image's
+        tiles are scored from the index rows for Q[b] and Q2[b] and the differences aggregated -- agg "avg_score" (any
+        agg_method other than "plain_score"): what `rescore_avg(pos, aug_larger, score_rows(Q2[b], rows), aug_weight)`
+        returns while Q[b]'s scores are resident; "plain_score": the first tile with the highest non-NaN
+        `gather_scores(rows) - score_rows(Q2[b], rows)`.  -> (scores f32 [nq, k], best rows int64 [nq, k]); entries from
+        counts[b] on are `out`'s (a pair of such arrays to write into) or unspecified.  The handle's scores, results,
+        exclusion set and prune counters are not touched."""
+        Q, Q2 = self._queries(Q), self._queries(Q2)
+        nq = Q.shape[0]
+        pos = np.ascontiguousarray(positions, dtype=np.int64)
+        cnt = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+        if Q2.shape != Q.shape or pos.ndim != 2 or pos.shape[0] != nq or cnt.shape[0] != nq:
+            raise ValueError(f"stage2_pair: Q {Q.shape}, Q2 {Q2.shape}, positions {pos.shape}, counts {cnt.shape} disagree")
+        k = pos.shape[1]
+        if out is None:
+            scores, rows = np.empty((nq, k), dtype=np.float32), np.empty((nq, k), dtype=np.int64)
+        else:
+            scores, rows = out
+            assert scores.dtype == np.float32 and rows.dtype == np.int64 and scores.shape == rows.shape == (nq, k) \
+                and scores.flags.c_contiguous and rows.flags.c_contiguous
+        if agg == "plain_score":
+            code, aug = self.AGG_PLAIN, 0
+        else:
+            code, aug = self.AGG_AVG, self.AUG_LARGER[aug_larger] | {"level_max": 0, "cont_weighted": 4}[aug_weight]
+        _lib.call("ssw_index_stage2_pair_batch", self._h, _ptr(Q), _ptr(Q2), nq, _ptr(pos), _ptr(cnt), k, code, aug,
+                  _ptr(scores), _ptr(rows))
+        return scores, rows
+
     def rescore_avg_f64(self, dev_scores_ptr: int, image_positions: np.ndarray, aug_larger: str,
                         aug_weight: str = "level_max"):
         """rescore_avg over float64 tile scores resident on the device (one per index row, e.g. the label-propagation

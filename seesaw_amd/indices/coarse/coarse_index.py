@@ -104,12 +104,12 @@ class CoarseIndex(AccessMethod):
         return {"dbidxs": ret, "nextstartk": len(exclude) + ret.shape[0],
                 "activations": ActivationFrames(boxes, ret, np.asarray(scores))}
 
-    def query_batch(self, *, topk, vectors, excludes=None, prune=False, **kwargs):
+    def query_batch(self, *, topk, vectors, excludes=None, prune=False, vectors2=None, **kwargs):
         """one `DeviceIndex.topk_batch` call for the vectors that are given: the list of dicts `query` returns, entry by
         entry identical to it (on a subset_view index a loop over `query`: a view has no batched scan).  A `None`
         vector (random order) and a query whose exclude set covers the whole index
         keep going through `query`.  `prune` is `DeviceIndex.topk_batch`'s: the same results from the shared int8
-        pre-scan on an index large enough for it."""
+        pre-scan on an index large enough for it.  `vectors2` is dropped: `query` ignores `vector2`."""
         vectors = list(vectors)
         excludes = [None] * len(vectors) if excludes is None else list(excludes)
         if len(excludes) != len(vectors):

@@ -84,15 +84,23 @@ class AccessMethod:
     # subset(BitMap of dbidxs) -> AccessMethod over those images only
     subset = _not_here("subset")
 
-    def query_batch(self, *, topk, vectors, excludes=None, **kwargs):
+    def query_batch(self, *, topk, vectors, excludes=None, vectors2=None, **kwargs):
         """`[query(vector=v, topk=topk, exclude=e, **kwargs) for v, e in zip(vectors, excludes)]`.  `excludes` is None
-        or one exclude set (or None) per vector.  This default asks one query at a time; an index whose device path
-        scores several queries in one pass over its rows overrides it (CoarseIndex)."""
+        or one exclude set (or None) per vector.  `vectors2` is None or one second vector (or None) per vector: entry i
+        is then `query(vector=v, vector2=vectors2[i], ...)`, the keyword passed only where the entry is not None.  This
+        default asks one query at a time; an index whose device path scores several queries in one pass over its rows
+        overrides it (CoarseIndex)."""
         vectors = list(vectors)
         excludes = [None] * len(vectors) if excludes is None else list(excludes)
         if len(excludes) != len(vectors):
             raise ValueError(f"excludes has {len(excludes)} entries for {len(vectors)} vectors")
-        return [self.query(topk=topk, vector=v, exclude=e, **kwargs) for v, e in zip(vectors, excludes)]
+        if vectors2 is None:
+            return [self.query(topk=topk, vector=v, exclude=e, **kwargs) for v, e in zip(vectors, excludes)]
+        vectors2 = list(vectors2)
+        if len(vectors2) != len(vectors):
+            raise ValueError(f"vectors2 has {len(vectors2)} entries for {len(vectors)} vectors")
+        return [self.query(topk=topk, vector=v, exclude=e, **({} if v2 is None else {"vector2": v2}), **kwargs)
+                for v, e, v2 in zip(vectors, excludes, vectors2)]
 
     def get_knng_path(self, name: str = None) -> str:
         """directory of a named k-NN graph of this index (`forward.parquet` inside)"""

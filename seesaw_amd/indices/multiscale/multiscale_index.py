@@ -144,6 +144,26 @@ def rescore_candidates(fullmeta: pd.DataFrame, topk: int, **kwargs):
     return {"dbidxs": dbidxs[top].astype("int"), "activations": [activations[i] for i in top]}
 
 
+def plain_pair_result(vector_meta: pd.DataFrame, row_start: np.ndarray, positions: np.ndarray, scores: np.ndarray,
+                      rows: np.ndarray, topk: int):
+    """the end of rescore_candidates' plain_score branch for candidates whose per-image work is done already
+    (`DeviceIndex.stage2_pair`): `positions` ascending -- the order the frames are walked in -- with every image's
+    score (the highest non-NaN tile score, f32) and the row of the first tile attaining it -> the `topk` frames by
+    `np.argsort(-score.astype(f64), kind="stable")`, each activation the one-row frame `fullmeta.iloc[[i]][_ACT_COLS]`
+    would be, indexed by the tile's place among the candidates' rows laid end to end."""
+    positions = np.asarray(positions, dtype=np.int64)
+    scores = np.asarray(scores, dtype=np.float32)
+    rows = np.asarray(rows, dtype=np.int64)
+    top = np.argsort(-scores.astype(np.float64), kind="stable")[:topk]
+    first = np.asarray(row_start, dtype=np.int64)[positions]
+    tiles = np.asarray(row_start, dtype=np.int64)[positions + 1] - first
+    place = np.concatenate(([0], np.cumsum(tiles)[:-1])) + (rows - first)  # fullmeta's index after reset_index
+    # one take of the winners' rows out of the (large) meta frame, then the one-row frames out of that small one
+    frame = vector_meta.iloc[rows[top]].assign(score=scores[top])[_ACT_COLS]
+    frame.index = pd.Index(place[top].astype(np.int64))
+    return {"dbidxs": frame.dbidx.values.astype("int"), "activations": [frame.iloc[[j]] for j in range(top.shape[0])]}
+
+
 class _Candidates:
     """what _query_prelim hands to the second stage: the reference's two-column frame (dbidx, max_score) as plain
     arrays plus the image positions and best rows that came back with the selection; `.df` builds the DataFrame
@@ -332,14 +352,14 @@ class MultiscaleIndex(AccessMethod):
         return np.concatenate([np.arange(self._row_start[p], self._row_start[p + 1]) for p in positions]) \
             if positions.size else np.zeros(0, dtype=np.int64)
 
-    def query_batch(self, *, topk, vectors, excludes=None, prune=False, **kwargs):
+    def query_batch(self, *, topk, vectors, excludes=None, prune=False, vectors2=None, **kwargs):
         """`[query(vector=v, topk=topk, exclude=e, **kwargs) for v, e in zip(vectors, excludes)]`, entry by entry
         identical to it (on a subset_view index exactly that loop: a view has no batched scan),
         with the rows read once per chunk of up to 16 queries: `plain_score` ends in
         `DeviceIndex.topk_batch`, every other agg_method in `DeviceIndex.topk_batch_avg`, whose second stage reads each
         query's own score slab while the chunk is alive (one k = the largest shortlist of the batch; each query keeps
         its own first min(shortlist_size, included) candidates).  Entries that keep going through `query`: no vector,
-        an exclude set that covers the index, and the whole call when `vector2` is given, when the index has no tile
+        an exclude set that covers the index, and the whole call when the single `vector2` is given, when the index has no tile
         geometry on the device (the host-side `rescore_candidates` path) or holds an image of more tiles than the
         kernel takes.  Afterwards `_resident_q` names the query whose scores are resident.
         `prune` is `DeviceIndex.topk_batch`'s and `DeviceIndex.topk_batch_avg`'s: the same results from the shared int8
@@ -347,27 +367,46 @@ class MultiscaleIndex(AccessMethod):
         candidates.  It is consumed here: the entries that keep going through `query` never see it.  Without it a
         batch scans in full precision: on an index large enough for the single `query` to be pruned (>= 2^22 rows) a
         small batch is slower per query than the loop (at 2^22 f32 rows it crosses over between nq = 4 and 8, while
-        the pruned batch is ahead from nq = 2: DESIGN.md section 10, "Pruned two-stage query").  The `vector2` form remains a follow-up (the sharded index batches its first stage:
-        `ShardedMultiscaleIndex`)."""
+        the pruned batch is ahead from nq = 2: DESIGN.md section 10, "Pruned two-stage query").
+        `vectors2`: None, or one second vector (or None) per vector -- entry i is then `query(vector=v, vector2=
+        vectors2[i], ...)`, dbidxs, activation boxes and activation scores (bit for bit) alike.  The whole batch,
+        single-vector entries included, still shares ONE first stage (`topk_batch`; `topk_batch_avg` only where a
+        single-vector entry needs its second stage), and ONE `DeviceIndex.stage2_pair` launch then scores both vectors
+        on the tiles of every two-vector entry's candidates and aggregates the differences; the avg entries finish in
+        `_avg_result`, the plain ones in `plain_pair_result`.  It reads no score buffer, so it is the same behind the
+        plain and the pruned first stage.  The single `vector2=` keyword keeps its meaning (the per-query loop).
+        (The sharded index batches its first stage and its avg second stage, `ShardedMultiscaleIndex`; its two-vector
+        entries loop: the owner-side form of `stage2_pair` remains a follow-up.)"""
         vectors = list(vectors)
         excludes = [None] * len(vectors) if excludes is None else list(excludes)
         if len(excludes) != len(vectors):
             raise ValueError(f"excludes has {len(excludes)} entries for {len(vectors)} vectors")
+        if vectors2 is not None:
+            vectors2 = list(vectors2)
+            if len(vectors2) != len(vectors):
+                raise ValueError(f"vectors2 has {len(vectors2)} entries for {len(vectors)} vectors")
+            if kwargs.get("vector2") is not None:
+                raise ValueError("give `vector2` (one for the whole call) or `vectors2` (one per vector), not both")
+            if all(v2 is None for v2 in vectors2):
+                vectors2 = None
         plain = kwargs.get("agg_method") == "plain_score"
-        on_device = plain or (self._has_tile_meta and
-                              int(np.diff(self._row_start).max(initial=0)) <= DeviceIndex.RESCORE_MAX_TILES)
-        if kwargs.get("vector2") is not None or not on_device or "shortlist_size" not in kwargs or getattr(self._dev, "is_view", False):
-            return super().query_batch(topk=topk, vectors=vectors, excludes=excludes, **kwargs)
+        tiles_fit = int(np.diff(self._row_start).max(initial=0)) <= DeviceIndex.RESCORE_MAX_TILES
+        on_device = plain or (self._has_tile_meta and tiles_fit)
+        if kwargs.get("vector2") is not None or not on_device or "shortlist_size" not in kwargs \
+                or getattr(self._dev, "is_view", False) or (vectors2 is not None and not tiles_fit):
+            return super().query_batch(topk=topk, vectors=vectors, excludes=excludes, vectors2=vectors2, **kwargs)
         shortlist_size = kwargs["shortlist_size"]
         if shortlist_size is None:
             shortlist_size = topk * 5
         n = self._dbidx.shape[0]
         out = [None] * len(vectors)
+        second = [None] * len(vectors) if vectors2 is None else vectors2
         excl_pos = [None if v is None else self._excluded_positions(e) for v, e in zip(vectors, excludes)]
         batch = [i for i, v in enumerate(vectors) if v is not None and excl_pos[i].shape[0] < n]
         for i in range(len(vectors)):
             if i not in batch:
-                out[i] = self.query(topk=topk, vector=vectors[i], exclude=excludes[i], **kwargs)
+                out[i] = self.query(topk=topk, vector=vectors[i], exclude=excludes[i],
+                                    **({} if second[i] is None else {"vector2": second[i]}), **kwargs)
         if not batch:
             return out
         if shortlist_size < topk * 5:
@@ -377,19 +416,41 @@ class MultiscaleIndex(AccessMethod):
         # one k for the launch; every query keeps its own min(shortlist_size, included) candidates
         ks = [min(int(shortlist_size), n - excl_pos[i].shape[0]) for i in batch]
         excluded = [excl_pos[i] for i in batch]
-        if plain:
-            for i, k_i, (pos, scores, best_rows) in zip(batch, ks, self._dev.topk_batch(Q, max(ks), excluded=excluded,
-                                                                                  prune=prune)):
-                cand = _Candidates(self._dbidx[pos[:k_i]], scores[:k_i], pos[:k_i], best_rows[:k_i])
-                out[i] = self._activations_from_best(cand, topk)
-        else:
-            aug_weight = kwargs.get("aug_weight", "level_max")
+        aug_weight = kwargs.get("aug_weight", "level_max")
+        if not plain:
             assert aug_weight in ("level_max", "cont_weighted"), aug_weight  # score_frame2's `assert False`
+        # ONE first stage for the whole batch; its own second stage only where a single-vector entry needs it
+        if plain or all(second[i] is not None for i in batch):
+            res = self._dev.topk_batch(Q, max(ks), excluded=excluded, prune=prune)
+        else:
             res = self._dev.topk_batch_avg(Q, max(ks), kwargs["aug_larger"], excluded=excluded, aug_weight=aug_weight,
                                            prune=prune)
-            for i, k_i, (pos, _, _, avg_scores, avg_rows) in zip(batch, ks, res):
-                order = np.argsort(pos[:k_i])  # rescore_candidates walks the frames in ascending dbidx order
-                out[i] = self._avg_result(pos[:k_i][order], avg_scores[:k_i][order], avg_rows[:k_i][order], topk)
+        pairs = []  # (entry, its candidates' positions ascending: the order rescore_candidates walks the frames in)
+        for i, k_i, r in zip(batch, ks, res):
+            pos = r[0]
+            if second[i] is not None:
+                pairs.append((i, np.sort(pos[:k_i])))
+            elif plain:
+                cand = _Candidates(self._dbidx[pos[:k_i]], r[1][:k_i], pos[:k_i], r[2][:k_i])
+                out[i] = self._activations_from_best(cand, topk)
+            else:
+                order = np.argsort(pos[:k_i])
+                out[i] = self._avg_result(pos[:k_i][order], r[3][:k_i][order], r[4][:k_i][order], topk)
+        if pairs:  # ONE launch for every two-vector entry: both vectors scored on the candidates' tiles
+            counts = np.array([p.shape[0] for _, p in pairs], dtype=np.int32)
+            positions = np.zeros((len(pairs), int(counts.max())), dtype=np.int64)
+            for j, (_, p) in enumerate(pairs):
+                positions[j, :p.shape[0]] = p
+            Q1 = np.stack([np.asarray(vectors[i], dtype=np.float32).reshape(-1) for i, _ in pairs])
+            Q2 = np.stack([np.asarray(second[i], dtype=np.float32).reshape(-1) for i, _ in pairs])
+            scores, rows = self._dev.stage2_pair(Q1, Q2, positions, counts, "plain_score" if plain else "avg_score",
+                                                 aug_larger="all" if plain else kwargs["aug_larger"], aug_weight=aug_weight)
+            for j, (i, p) in enumerate(pairs):
+                m = p.shape[0]
+                if plain:
+                    out[i] = plain_pair_result(self.vector_meta, self._row_start, p, scores[j, :m], rows[j, :m], topk)
+                else:
+                    out[i] = self._avg_result(p, scores[j, :m], rows[j, :m], topk)
         self._resident_q = Q[-1].copy()
         return out
 

@@ -362,7 +362,7 @@ class ShardedMultiscaleIndex(MultiscaleIndex):
     # (`vector2`, an index without tile meta, a shard factory without the batched methods).
     query_batch = AccessMethod.query_batch
 
-    def _query_batch_sharded(self, *, topk, vectors, excludes=None, prune=False, **kwargs):
+    def _query_batch_sharded(self, *, topk, vectors, excludes=None, prune=False, vectors2=None, **kwargs):
         """`index.query_batch`: `[query(vector=v, topk=topk, exclude=e, **kwargs) for v, e in zip(vectors, excludes)]`,
         entry by entry identical to it.  Without `vector2` every rank reads its rows once per chunk of up
         to 16 queries (`DeviceShard.select_batch`) and the ranks exchange once per group of `n_slots` queries: one
@@ -388,6 +388,8 @@ class ShardedMultiscaleIndex(MultiscaleIndex):
         excludes = [None] * len(vectors) if excludes is None else list(excludes)
         if len(excludes) != len(vectors):
             raise ValueError(f"excludes has {len(excludes)} entries for {len(vectors)} vectors")
+        if vectors2 is not None and any(v2 is not None for v2 in vectors2):  # a per-entry `vector2`: the loop, as above
+            return AccessMethod.query_batch(self, topk=topk, vectors=vectors, excludes=excludes, vectors2=vectors2, **kwargs)
         served = kwargs.get("vector2") is None and "shortlist_size" in kwargs and hasattr(self._shard_factory, "select_batch")
         avg = kwargs.get("agg_method") != "plain_score"
         if avg:  # the second stage too: on the owners, one launch and one more exchange a group

@@ -72,8 +72,8 @@ class MultiRegNeg(PointBased):
         (MultiRegModule.fit_batch): loop by loop the labels are read, the module is built and staged on the loop's own
         engine -- the order of the log lines and of the generator draws of the single calls -- then one launch fits
         them all and every `curr_vec` / `confusion_vec` is set.  A loop whose fit raised surfaces its AssertionError
-        after the other loops have got their vectors.  (`next_batch` with `vector2` stays per session: batching the
-        two-vector query is out of scope here.)"""
+        after the other loops have got their vectors.  (The matching `next()` of a group: `SessionGroup.next`, through
+        `query_batch(vectors2=...)`.)"""
         loops = list(loops)
         if not loops:
             return

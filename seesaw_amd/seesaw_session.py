@@ -254,14 +254,16 @@ class SessionGroup:
     * `next()`: the sessions whose loop would answer through `LoopBase._next_batch_curr_vec` (a `PointBased` loop, or
       any loop whose start policy has not fired) and that share one index object and the same `batch_size`,
       `shortlist_size`, `agg_method` and `aug_larger` are served by ONE `index.query_batch` -- one pass over the rows;
-      every other session calls its own `next()`.
+      a started `MultiRegNeg` whose `next_batch` is the class's own joins that group with `vector = curr_vec` and
+      `vector2 = confusion_vec if discount_neg else zeros(dim)` (`query_batch(vectors2=...)`: one more launch for all
+      of them); every other session calls its own `next()`.
     * `refine()`: every session's start-policy gate runs as in `LoopBase.refine_external`; the started `MultiReg`
       loops go through ONE `MultiReg.refine_batch` -- one launch, one host wait -- and the started `MultiRegNeg` loops
       whose options say `fit_on_device` through ONE `MultiRegNeg.refine_batch`, a launch of their own; every other
       loop, a `MultiRegNeg` that did not opt in included, through its own `refine_external`.  The batches refine
       first, the remaining sessions after them in session order: loops that draw from torch's global generator (every
       `MultiRegNeg` refine draws its start weights) keep the draws of the one-by-one order when the opted-in loops
-      stand before the others in `sessions`.  `MultiRegNeg`'s `next()` with `vector2` stays per session.
+      stand before the others in `sessions`.
 
     Every session ends each call in the state its own `next()` / `refine()` would have left: `returned`, `timing`
     (the shared call's time for each member), `acc_indices`, `acc_activations`, the log, `curr_vec` -- bit for bit.
@@ -286,7 +288,24 @@ class SessionGroup:
             return loop.curr_qvec
         if isinstance(loop, PointBased) and cls.next_batch is PointBased.next_batch:
             return loop.curr_vec
+        if SessionGroup._asks_with_two_vectors(loop):
+            return loop.curr_vec  # with `batch_vector2`: the two-vector query
         return None
+
+    @staticmethod
+    def _asks_with_two_vectors(loop):
+        """a started `MultiRegNeg` whose `next_batch` is the class's own and that carries what that method reads
+        (`options`, `confusion_vec`: a loop made without `MultiRegNeg.__init__` has neither and answers on its own)"""
+        from .loops.multi_reg_neg import MultiRegNeg
+        return loop.started and isinstance(loop, MultiRegNeg) and type(loop).next_batch is MultiRegNeg.next_batch and \
+            hasattr(loop, "confusion_vec") and getattr(loop, "options", None) is not None
+
+    @staticmethod
+    def batch_vector2(loop):
+        """the `vector2` a started `MultiRegNeg.next_batch` asks with (None: the loop asks with one vector)"""
+        if SessionGroup.batch_vector(loop) is None or not SessionGroup._asks_with_two_vectors(loop):
+            return None
+        return loop.confusion_vec if loop.options["discount_neg"] else np.zeros(loop.q.index.vectors.shape[1])
 
     def query_groups(self):
         """[(session positions, ...)]: the positions that share one `query_batch`, in session order; a session that
@@ -334,19 +353,23 @@ class SessionGroup:
                 out[group[0]] = self.sessions[group[0]].next()
                 continue
             members = [self.sessions[i] for i in group]
-            vectors = []
+            vectors, vectors2 = [], []
             for s in members:
                 s._log("next.start")
                 print("start met. next batch from custom method..." if s.loop.started
                       else "start not yet met. next batch using default...")
                 vec = self.batch_vector(s.loop)
-                assert not np.isnan(vec).any(), f"NaN in query vector {vec=}"
+                vec2 = self.batch_vector2(s.loop)
+                if vec2 is None:  # (`_next_batch_curr_vec`'s check; `MultiRegNeg.next_batch` has none)
+                    assert not np.isnan(vec).any(), f"NaN in query vector {vec=}"
                 vectors.append(vec)
+                vectors2.append(vec2)
             start = time.time()
             p = members[0].loop.params
+            pair = {"vectors2": vectors2} if any(v2 is not None for v2 in vectors2) else {}
             results = members[0].loop.q.index.query_batch(
                 topk=p.batch_size, vectors=vectors, excludes=[s.loop.q.returned for s in members], prune=self.prune,
-                shortlist_size=p.shortlist_size, agg_method=p.agg_method, aug_larger=p.aug_larger)
+                shortlist_size=p.shortlist_size, agg_method=p.agg_method, aug_larger=p.aug_larger, **pair)
             elapsed = time.time() - start
             for i, s, r in zip(group, members, results):
                 s.loop.q.returned.update(np.asarray(r["dbidxs"], dtype=np.int64))
