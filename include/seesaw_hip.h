@@ -630,6 +630,52 @@ ssw_status ssw_labelprop_round(ssw_lp *lp, ssw_index *index, int32_t propagate, 
                                int32_t mask_labeled, const int64_t *excluded_images, int64_t n_excluded, int32_t k,
                                int64_t *out_images, float *out_scores, int64_t *out_best_rows, int32_t *out_count,
                                int32_t *out_sweeps, int32_t *out_converged);
+/* ssw_labelprop_round for n_slots graph handles over ONE index in one call: the lock-step round of several graph loops
+ * (SessionGroup.refine -> KnnProp2.refine_batch).  lps [n_slots]: distinct handles on the index's device, each with a
+ * prior installed and n == the index's rows.  Per slot j: propagate[j], its labels label_ids / label_vals
+ * [label_offsets[j], label_offsets[j + 1]) of the packed arrays, reg_lambda[j], eps[j], max_iter[j], and its excluded
+ * images packed with offsets as in ssw_index_topk_batch (excluded_offsets NULL: nobody excludes).  mask_labeled and k
+ * hold for the whole call.  Outputs [n_slots, k] row-major (row j filled up to out_counts[j]), out_counts / out_sweeps /
+ * out_converged / out_status [n_slots] (images, scores, best rows, sweeps and converged may be NULL).
+ * Contract: for every slot the outputs are the bits ssw_labelprop_round(lps[j], index, slot j's arguments) returns,
+ * and the handle is left as that call leaves it -- iterates, kept levels and block maxima, installed labels, result,
+ * sweeps hint and ssw_labelprop_last_run_info [0], [1], [4], [5] -- so a later single or batched call on any of the
+ * handles continues from there, incrementally.  A slot's failure (e.g. SSW_ERR_NUMERIC when its values left the bounds)
+ * is out_status[j] with the message in ssw_labelprop_batch_error(lps[j]); the other slots are not affected and the call
+ * returns SSW_OK.
+ * Routing, decided on the host before anything is enqueued for the slot:
+ *   incremental slots (propagate, valid tracked state, unchanged reg_lambda / eps / max_iter, unique ids, a non-empty
+ *     change of at most n / 8 labels, SSW_LP_NO_INCREMENTAL unset) take the BATCHED PASS: one device table of per-slot
+ *     descriptors, the pass's kernels launched once for the chunk with the slot on blockIdx.y -- 3 + 3 x (the deepest kept
+ *     level) launches whatever the number of slots -- the last of which writes slot j's f32 scores into slab j of the
+ *     index's batch slabs and leaves the slot's control block in the slot's pinned memory;
+ *   prior slots (propagate == 0) enqueue ssw_labelprop_prior_as_result's work without a wait and join the batched scores
+ *     and selection with iterate 0; unchanged slots (the same labels) join with the kept result;
+ *   everything else (a first full propagation, other parameters, duplicate ids, too large a change, max_iter == 0) runs
+ *     the single round inside the call, one slot after another.  A batched FIRST propagation is out of scope.
+ * The selections of a chunk's slots follow back to back, each over its slab into its own pinned block under its own
+ * sequence word, and the host waits ONCE a chunk.  After that wait: a slot whose fast selection overflowed (mass ties) is
+ * selected again on the deep path from its slab; an incremental slot whose frontier overflowed or that needs more sweeps
+ * than were kept is finished by the single path's continuation (full sweeps) and gets its own scores and selection.
+ * More than 16 slots: several chunks in the one call.
+ * Streams: the call runs on lps[0]'s stream; it first waits for the index (ssw_index_sync) and every other handle's
+ * stream, and returns with everything complete.  The index's score buffer holds some slot's scores afterwards and is
+ * complete (no resident query describes it).
+ * Errors before any device work, leaving every handle and the index untouched (SSW_ERR_INVALID): NULL or duplicate
+ * handles, a device or row-count mismatch, a handle without a prior, k outside [1, SSW_MAX_TOPK], a label id or an
+ * excluded image out of range in any slot, decreasing offsets.  A view index: SSW_ERR_UNSUPPORTED ("view").
+ * out_stats4 (may be NULL): [0] slots that took the batched pass, [1] kernel launches of that pass up to and including
+ * the scores kernel (selections excluded), [2] host waits of the call, [3] slots finished on the single path or by the
+ * continuation.  ssw_labelprop_last_run_info of a batched slot: [2] = the launches of its chunk's pass, [3] = 1 (the
+ * chunk's wait), [6] / [7] = nanoseconds of the CALL from entry until the chunk was enqueued / waited for the chunk. */
+ssw_status ssw_labelprop_round_batch(ssw_lp *const *lps, int32_t n_slots, ssw_index *index, const int32_t *propagate,
+                                     const int64_t *label_ids, const double *label_vals, const int64_t *label_offsets,
+                                     const double *reg_lambda, const double *eps, const int32_t *max_iter,
+                                     int32_t mask_labeled, const int64_t *excluded_images, const int64_t *excluded_offsets,
+                                     int32_t k, int64_t *out_images, float *out_scores, int64_t *out_best_rows,
+                                     int32_t *out_counts, int32_t *out_sweeps, int32_t *out_converged, int32_t *out_status,
+                                     int64_t *out_stats4);
+const char *ssw_labelprop_batch_error(const ssw_lp *lp);
 /* device address of the [n] f64 result of the last propagation (valid until the next run on this handle). */
 ssw_status ssw_labelprop_device_scores(ssw_lp *lp, const double **out_dev_scores);
 

@@ -114,6 +114,10 @@ _SIGNATURES = {
     "ssw_labelprop_device_scores": (c_i32, [c_void_p, ctypes.POINTER(c_void_p)]),
     "ssw_labelprop_round": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i64, ctypes.c_double, ctypes.c_double, c_i32,
                                     c_i32, c_void_p, c_i64, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ssw_labelprop_round_batch": (c_i32, [c_void_pp, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ssw_labelprop_batch_error": (ctypes.c_char_p, [c_void_p]),
     "ssw_xlx": (c_i32, [c_void_p, c_void_p, c_void_p]),
     "ssw_knn_build": (c_i32, [c_void_p, c_i32, ctypes.c_uint64, c_void_p, c_void_p, c_void_p]),
     "ssw_fb_set_xlx": (c_i32, [c_void_p, c_void_p]),

@@ -284,6 +284,7 @@ ssw_status ssw_index_destroy(ssw_index *idx) {
     idx->rows_stage.release();
     if (idx->res_host) (void)hipHostFree(idx->res_host);
     if (idx->small_host) (void)hipHostFree(idx->small_host);
+    if (idx->slot_host) (void)hipHostFree(idx->slot_host);
     idx->q2_stage.release();
     if (idx->own_stream) (void)hipStreamDestroy(idx->own_stream);
     delete idx;

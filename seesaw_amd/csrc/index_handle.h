@@ -173,6 +173,9 @@ struct ssw_index {
     unsigned small_seq = 0;
     unsigned res_pending_seq = 0;  // != 0: the selection in flight publishes into res_host under this sequence number
     unsigned small_pending_seq = 0;  // the same for the small form, into small_host
+    // batched graph round (index_enqueue_topk_slot): BATCH_MAX_WIDTH pinned, device-visible blocks, one a slot of a chunk,
+    // [excluded ids SMALL_EXCL_CAP i64][packed result]; each slot's selection publishes into its own block
+    unsigned char *slot_host = nullptr;
     float *q2_dev = nullptr;  // second query vector (score_rows)
     ssw::PinnedStage q2_stage;
     // tile geometry + staging of the avg_score aggregation (rescore.hip)

@@ -244,6 +244,96 @@ ssw_status index_collect_topk(ssw_index *idx, hipStream_t on_stream, int32_t k, 
     return topk_collect(idx, idx->scores, on_stream, k, out_images, out_scores, out_best_rows, out_count);
 }
 
+// ---- the same two halves once per slot of a chunk (ssw_labelprop_round_batch): the selections of a chunk's slots are
+// enqueued back to back on one stream, each over its own score slab, and each publishes into its own pinned block
+// under its own sequence word, so the host waits once for the chunk -- on the word of the slot enqueued last
+constexpr size_t SLOT_EXCL_BYTES = (size_t)SMALL_EXCL_CAP * sizeof(int64_t);
+constexpr size_t SLOT_BYTES = SLOT_EXCL_BYTES + 16 + (size_t)SSW_MAX_TOPK * 12;
+
+ssw_status index_round_slabs(ssw_index *idx, int w, int *out_w, float **slabs) {
+    SSW_REQUIRE(idx != nullptr && out_w != nullptr && slabs != nullptr && w >= 1, "NULL argument");
+    if (w > BATCH_MAX_WIDTH) w = BATCH_MAX_WIDTH;
+    SSW_TRY(batch_buffers(idx, w, false, &w));
+    for (int j = 0; j < w; ++j) slabs[j] = chunk_slab(idx, w, j);
+    *out_w = w;
+    return SSW_OK;
+}
+
+ssw_status index_enqueue_topk_slot(ssw_index *idx, hipStream_t on_stream, int slot, const float *slab,
+                                   const int64_t *excluded_images, int64_t n_excluded, int32_t k, unsigned *out_seq) {
+    SSW_REQUIRE(idx != nullptr && out_seq != nullptr && slot >= 0 && slot < BATCH_MAX_WIDTH, "bad slot");
+    SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
+    SSW_REQUIRE(n_excluded == 0 || excluded_images != nullptr, "excluded_images is NULL");
+    *out_seq = 0;
+    if (idx->n_images == 0) return SSW_OK;
+    if (!idx->slot_host) {
+        SSW_HIP_TRY(hipHostMalloc((void **)&idx->slot_host, (size_t)BATCH_MAX_WIDTH * SLOT_BYTES,
+                                  hipHostMallocMapped | hipHostMallocCoherent));
+        memset(idx->slot_host, 0, (size_t)BATCH_MAX_WIDTH * SLOT_BYTES);
+    }
+    unsigned char *block = idx->slot_host + (size_t)slot * SLOT_BYTES, *dev_view = nullptr;
+    SSW_HIP_TRY(hipHostGetDevicePointer((void **)&dev_view, block, 0));
+    SSW_TRY(check_excluded(idx, excluded_images, 0, n_excluded));
+    SSW_TRY(ensure_ws(idx));
+    const unsigned seq = next_seq(idx->small_seq);
+    if (small_path_ok(idx, n_excluded)) {  // the form the single call takes on this index: one launch, ids read in place
+        if (idx->ws.excl_dirty) SSW_TRY(select_set_excluded(idx->ws, idx->n_images, nullptr, 0, on_stream));
+        if (n_excluded > 0) memcpy(block, excluded_images, (size_t)n_excluded * sizeof(int64_t));
+        SSW_TRY(launch_select_small(idx->ws, slab, idx->has_map ? idx->row_start : nullptr, idx->n_images,
+                                    reinterpret_cast<const int64_t *>(dev_view), n_excluded, k, dev_view + SLOT_EXCL_BYTES,
+                                    seq, on_stream));
+    } else {
+        SSW_TRY(install_excluded(idx, excluded_images, n_excluded, on_stream));
+        SelectDest dest;
+        dest.host_packed = dev_view + SLOT_EXCL_BYTES;
+        dest.seq = seq;
+        SSW_TRY(do_select(idx, slab, k, dest, on_stream));
+    }
+    *out_seq = seq;
+    return SSW_OK;
+}
+
+// the chunk's one wait: on the word of the slot whose selection was enqueued last
+ssw_status index_wait_topk_slot(ssw_index *idx, hipStream_t on_stream, int slot, unsigned seq) {
+    SSW_REQUIRE(idx != nullptr && idx->slot_host != nullptr && slot >= 0 && slot < BATCH_MAX_WIDTH && seq != 0, "bad slot");
+    const unsigned char *res = idx->slot_host + (size_t)slot * SLOT_BYTES + SLOT_EXCL_BYTES;
+    return wait_host_seq(on_stream, reinterpret_cast<const unsigned *>(res) + 3, seq);
+}
+
+// Collect half.  *reran: the fast selection had reported overflow (massive ties) and the slot was selected again on the
+// deep path, from its slab -- the per-image maxima in the workspace are a later slot's by now -- behind one more wait.
+// The excluded set is installed again for it: a later slot's is in the workspace as well.
+ssw_status index_collect_topk_slot(ssw_index *idx, hipStream_t on_stream, int slot, unsigned seq, const float *slab,
+                                   const int64_t *excluded_images, int64_t n_excluded, int32_t k, int64_t *out_images,
+                                   float *out_scores, int64_t *out_best_rows, int32_t *out_count, bool *reran) {
+    SSW_REQUIRE(idx != nullptr && out_count != nullptr && slot >= 0 && slot < BATCH_MAX_WIDTH, "bad slot");
+    *out_count = 0;
+    if (reran) *reran = false;
+    if (idx->n_images == 0 || seq == 0) return SSW_OK;
+    unsigned char *res = idx->slot_host + (size_t)slot * SLOT_BYTES + SLOT_EXCL_BYTES;
+    SSW_TRY(wait_host_seq(on_stream, reinterpret_cast<const unsigned *>(res) + 3, seq));
+    const int32_t *hdr = reinterpret_cast<const int32_t *>(res);
+    if (!small_path_ok(idx, n_excluded) && hdr[1] != 0) {
+        unsigned char *dev_view = nullptr;
+        SSW_HIP_TRY(hipHostGetDevicePointer((void **)&dev_view, res, 0));
+        SSW_TRY(install_excluded(idx, excluded_images, n_excluded, on_stream));
+        if (idx->has_map)
+            SSW_TRY(launch_image_max(slab, idx->row_start, idx->n_images, idx->ws.img_score, idx->ws.img_best, on_stream));
+        SelectDest dest;
+        dest.host_packed = dev_view;
+        dest.seq = next_seq(idx->small_seq);
+        SSW_TRY(do_select_deep(idx, slab, k, dest, on_stream));
+        SSW_TRY(wait_host_seq(on_stream, reinterpret_cast<const unsigned *>(res) + 3, dest.seq));
+        if (reran) *reran = true;
+    }
+    if (hdr[2] != k) {
+        set_error("topk slot %d: k=%d does not match the k=%d of the selection that produced the result", slot, k, hdr[2]);
+        return SSW_ERR_INVALID;
+    }
+    decode_packed(res, k, out_images, out_scores, out_best_rows, out_count);
+    return SSW_OK;
+}
+
 int index_device(const ssw_index *idx) { return idx ? idx->device : -1; }
 int32_t index_dtype(const ssw_index *idx) { return idx ? idx->dtype : SSW_DTYPE_F32; }
 const void *index_matrix(const ssw_index *idx, int64_t *n_rows, int32_t *dim) {

@@ -52,6 +52,18 @@ struct LpState {           // device-resident control block
     int pad[3];
 };
 
+// The last step of a row, ONE text for the full sweeps, the incremental pass and its batched form: `sum` holds the row's
+// products, each formed once and added in ascending position; then lambda * prior joins, the divide, the reference's
+// bounds (label_propagation.py:36-40) and the label clamp.
+__device__ __forceinline__ double lp_row_value(double sum, double lambda, double prior, double wsum, double low_bound,
+                                               double high_bound, bool is_label, double label, int *violation) {
+    const double weighted = __dadd_rn(sum, __dmul_rn(lambda, prior));
+    double v = weighted / __dadd_rn(wsum, lambda);
+    if (!(v >= low_bound) || !(v <= high_bound)) *violation = 1;
+    if (is_label) v = label;
+    return v;
+}
+
 __global__ __launch_bounds__(LP_BLOCK) void k_lp_sweep(
     int64_t n, const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
     const double *__restrict__ data, const double *__restrict__ wsum,
@@ -108,10 +120,8 @@ __global__ __launch_bounds__(LP_BLOCK) void k_lp_sweep(
     }
     double d2 = 0.0;
     if (row < n) {
-        const double weighted = __dadd_rn(sum, __dmul_rn(lambda, e_prior));
-        double v = weighted / __dadd_rn(e_wsum, lambda);
-        if (!(v >= low_bound) || !(v <= high_bound)) st->bound_violation = 1;
-        if (e_is_label) v = e_label;
+        const double v = lp_row_value(sum, lambda, e_prior, e_wsum, low_bound, high_bound, e_is_label != 0, e_label,
+                                      &st->bound_violation);
         f_new[row] = v;
         const double d = __dadd_rn(v, -e_old);
         d2 = __dmul_rn(d, d);
@@ -212,10 +222,9 @@ __global__ __launch_bounds__(LP_BLOCK) void k_lp_sweep_fused(
     for (int g = 0; g < LP_GROUPS; ++g) {
         const int64_t row = r0 + (int64_t)g * LP_BLOCK + t;
         if (row < n) {
-            const double weighted = __dadd_rn(sum[g], __dmul_rn(lambda, prior[row]));
-            double v = weighted / __dadd_rn(wsum[row], lambda);
-            if (!(v >= low_bound) || !(v <= high_bound)) st->bound_violation = 1;
-            if (is_label[row]) v = label_val[row];
+            const bool lab = is_label[row] != 0;
+            const double v = lp_row_value(sum[g], lambda, prior[row], wsum[row], low_bound, high_bound, lab,
+                                          lab ? label_val[row] : 0.0, &st->bound_violation);
             f_new[row] = v;
             const double d = __dadd_rn(v, -f_old[row]);
             d2 = fmax(d2, __dmul_rn(d, d));
@@ -284,9 +293,41 @@ struct LpInc {
     double level_max[8];      // per sweep: max over ALL blocks of 256 nodes of (F[k] - F[k-1])^2
 };
 
+// Every kernel of the pass is a __device__ body with two __global__ forms: the single call's, which takes the handle's
+// arrays as arguments, and the batched call's (ssw_labelprop_round_batch, suffix _b), which takes a device table of
+// per-slot descriptors and uses blockIdx.y as the slot.  The bodies walk their lists in strides of gridDim.x, so no
+// result depends on the grid either form is launched with.
+constexpr int LP_KEEP = 8;  // == ssw_lp::KEEP
+struct LpSlot {
+    // the slot's own graph, iterates and frontier state (device pointers of its handle)
+    const int64_t *indptr, *ht_indptr;
+    const int32_t *indices, *ht_indices;
+    const double *data, *wsum, *prior;
+    double *f[LP_KEEP], *bmax[LP_KEEP];
+    unsigned char *is_label;
+    double *label_val;
+    uint32_t *stamp, *bstamp;
+    int32_t *mem, *blk;
+    int64_t *ids_out;   // the handle's list of installed labels
+    double *vals_out;
+    // this call: the packed label lists, the control block and its pinned copy, the slot's score slab
+    const int64_t *ch_ids, *all_ids;
+    const double *set_vals, *all_vals;
+    struct LpInc *ctl, *host_copy;
+    const int32_t *perm;           // NULL: the handle is in original node order
+    float *out;
+    double lambda, lo, hi, eps;
+    int64_t n;
+    int n_set, n_unset, n_all, cap;
+    int levels;                    // kept levels: the sweeps this slot takes part in (0: no incremental pass)
+    int fixed_result;              // >= 0: the scores come from this iterate (prior / unchanged slots), no control block
+    int mask_labeled;
+    uint32_t ep;
+};
+
 // the label changes of an incremental call: ids [0, n_set) become labelled with vals, ids [n_set, n_set + n_unset) lose
 // their label; every changed node enters the frontier list
-__global__ void k_inc_seed(const int64_t *__restrict__ ids, const double *__restrict__ vals, int n_set, int n_unset,
+__device__ __forceinline__ void inc_seed_body(const int64_t *__restrict__ ids, const double *__restrict__ vals, int n_set, int n_unset,
                            const double *__restrict__ prior, double *__restrict__ f0, unsigned char *__restrict__ is_label,
                            double *__restrict__ label_val, uint32_t *__restrict__ stamp, uint32_t ep, int32_t *__restrict__ mem,
                            const int64_t *__restrict__ all_ids, const double *__restrict__ all_vals, int n_all,
@@ -309,13 +350,27 @@ __global__ void k_inc_seed(const int64_t *__restrict__ ids, const double *__rest
     stamp[r] = ep;   // (the changed ids are distinct)
     mem[i] = (int32_t)r;
 }
+__global__ void k_inc_seed(const int64_t *__restrict__ ids, const double *__restrict__ vals, int n_set, int n_unset,
+                           const double *__restrict__ prior, double *__restrict__ f0, unsigned char *__restrict__ is_label,
+                           double *__restrict__ label_val, uint32_t *__restrict__ stamp, uint32_t ep, int32_t *__restrict__ mem,
+                           const int64_t *__restrict__ all_ids, const double *__restrict__ all_vals, int n_all,
+                           int64_t *__restrict__ ids_out, double *__restrict__ vals_out) {
+    inc_seed_body(ids, vals, n_set, n_unset, prior, f0, is_label, label_val, stamp, ep, mem, all_ids, all_vals, n_all, ids_out,
+                  vals_out);
+}
+__global__ void k_inc_seed_b(const LpSlot *__restrict__ tab) {
+    const LpSlot &d = tab[blockIdx.y];
+    if ((int)(blockIdx.x * blockDim.x) >= max(d.n_set + d.n_unset, d.n_all)) return;  // (a slot with shorter lists)
+    inc_seed_body(d.ch_ids, d.set_vals, d.n_set, d.n_unset, d.prior, d.f[0], d.is_label, d.label_val, d.stamp, d.ep, d.mem,
+                  d.all_ids, d.all_vals, d.n_all, d.ids_out, d.vals_out);
+}
 
 // frontier of sweep k: the rows whose sums read a value that changed in sweep k - 1, i.e. the in-neighbours (rows of the
 // TRANSPOSED pattern) of the nodes that entered the list one sweep earlier.  A wave per source node (hub rows hold
 // thousands of entries), first touch by atomic exchange on the node's stamp; the order of the list does not matter.
-__global__ __launch_bounds__(256) void k_inc_expand(int k, const int64_t *__restrict__ ht_indptr, const int32_t *__restrict__ ht_indices,
-                                                    uint32_t *__restrict__ stamp, uint32_t ep, int32_t *__restrict__ mem, int cap,
-                                                    LpInc *__restrict__ ctl) {
+__device__ __forceinline__ void inc_expand_body(int k, const int64_t *__restrict__ ht_indptr, const int32_t *__restrict__ ht_indices,
+                                                uint32_t *__restrict__ stamp, uint32_t ep, int32_t *__restrict__ mem, int cap,
+                                                LpInc *__restrict__ ctl) {
     const int lane = threadIdx.x & 63;
     const int lo = k >= 2 ? ctl->m[k - 2] : 0, hi = ctl->m[k - 1];
     const int nwaves = gridDim.x * 4;
@@ -331,6 +386,17 @@ __global__ __launch_bounds__(256) void k_inc_expand(int k, const int64_t *__rest
         }
     }
 }
+__global__ __launch_bounds__(256) void k_inc_expand(int k, const int64_t *__restrict__ ht_indptr, const int32_t *__restrict__ ht_indices,
+                                                    uint32_t *__restrict__ stamp, uint32_t ep, int32_t *__restrict__ mem, int cap,
+                                                    LpInc *__restrict__ ctl) {
+    inc_expand_body(k, ht_indptr, ht_indices, stamp, ep, mem, cap, ctl);
+}
+// (a slot with fewer kept levels than the chunk's deepest leaves the later sweeps at once: here and in the two below)
+__global__ __launch_bounds__(256) void k_inc_expand_b(int k, const LpSlot *__restrict__ tab) {
+    const LpSlot &d = tab[blockIdx.y];
+    if (k > d.levels) return;
+    inc_expand_body(k, d.ht_indptr, d.ht_indices, d.stamp, d.ep, d.mem, d.cap, d.ctl);
+}
 
 // Sweep k over the listed rows: a wave takes FOUR rows at a time, 16 lanes a row (a row of this graph holds ~12 entries;
 // hub rows hold thousands and keep their 16 lanes busy for more trips while the other three groups idle).  A group takes
@@ -338,13 +404,13 @@ __global__ __launch_bounds__(256) void k_inc_expand(int k, const int64_t *__rest
 // formed once and parked in the group's 1 KB of LDS -- then the group's first lane adds them in ascending position: the
 // order of the full sweeps and of scipy's csr_matvec.  Rows that are new in this sweep also enter their block of 256
 // nodes in the block list (first touch by the block's stamp).
-__global__ __launch_bounds__(256) void k_inc_rows(int k, const int32_t *__restrict__ mem, int cap, const int64_t *__restrict__ indptr,
-                                                  const int32_t *__restrict__ indices, const double *__restrict__ data,
-                                                  const double *__restrict__ wsum, const double *__restrict__ prior,
-                                                  const double *__restrict__ f_old, double *__restrict__ f_new,
-                                                  const unsigned char *__restrict__ is_label, const double *__restrict__ label_val,
-                                                  double lambda, double low_bound, double high_bound, uint32_t *__restrict__ bstamp,
-                                                  uint32_t ep, int32_t *__restrict__ blk, LpInc *__restrict__ ctl) {
+__device__ __forceinline__ void inc_rows_body(int k, const int32_t *__restrict__ mem, int cap, const int64_t *__restrict__ indptr,
+                                              const int32_t *__restrict__ indices, const double *__restrict__ data,
+                                              const double *__restrict__ wsum, const double *__restrict__ prior,
+                                              const double *__restrict__ f_old, double *__restrict__ f_new,
+                                              const unsigned char *__restrict__ is_label, const double *__restrict__ label_val,
+                                              double lambda, double low_bound, double high_bound, uint32_t *__restrict__ bstamp,
+                                              uint32_t ep, int32_t *__restrict__ blk, LpInc *__restrict__ ctl) {
     __shared__ double prod[4][4][128];
     const int lane = threadIdx.x & 63, g = lane >> 4, gl = lane & 15;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -391,22 +457,35 @@ __global__ __launch_bounds__(256) void k_inc_rows(int k, const int32_t *__restri
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
         if (live && gl == 0) {
-            const double weighted = __dadd_rn(sum, __dmul_rn(lambda, prior[row]));
-            double v = weighted / __dadd_rn(wsum[row], lambda);
-            if (!(v >= low_bound) || !(v <= high_bound)) ctl->bound_violation = 1;
-            if (is_label[row]) v = label_val[row];
-            f_new[row] = v;
+            const bool lab = is_label[row] != 0;
+            f_new[row] = lp_row_value(sum, lambda, prior[row], wsum[row], low_bound, high_bound, lab, lab ? label_val[row] : 0.0,
+                                      &ctl->bound_violation);
         }
     }
+}
+__global__ __launch_bounds__(256) void k_inc_rows(int k, const int32_t *__restrict__ mem, int cap, const int64_t *__restrict__ indptr,
+                                                  const int32_t *__restrict__ indices, const double *__restrict__ data,
+                                                  const double *__restrict__ wsum, const double *__restrict__ prior,
+                                                  const double *__restrict__ f_old, double *__restrict__ f_new,
+                                                  const unsigned char *__restrict__ is_label, const double *__restrict__ label_val,
+                                                  double lambda, double low_bound, double high_bound, uint32_t *__restrict__ bstamp,
+                                                  uint32_t ep, int32_t *__restrict__ blk, LpInc *__restrict__ ctl) {
+    inc_rows_body(k, mem, cap, indptr, indices, data, wsum, prior, f_old, f_new, is_label, label_val, lambda, low_bound, high_bound,
+                  bstamp, ep, blk, ctl);
+}
+__global__ __launch_bounds__(256) void k_inc_rows_b(int k, const LpSlot *__restrict__ tab) {
+    const LpSlot &d = tab[blockIdx.y];
+    if (k > d.levels) return;
+    inc_rows_body(k, d.mem, d.cap, d.indptr, d.indices, d.data, d.wsum, d.prior, d.f[k - 1], d.f[k], d.is_label, d.label_val,
+                  d.lambda, d.lo, d.hi, d.bstamp, d.ep, d.blk, d.ctl);
 }
 
 // max over a block of 256 nodes of (f_new - f_old)^2.  blk == nullptr: every block (a full sweep's pass; skipped once
 // the run has converged); otherwise the blocks of the incremental call's list (all touched so far)
-__global__ __launch_bounds__(256) void k_lp_blockmax(const int32_t *__restrict__ blk, const LpInc *__restrict__ ctl, int64_t n,
-                                                     const double *__restrict__ f_new, const double *__restrict__ f_old,
-                                                     double *__restrict__ bmax, const LpState *__restrict__ st_or_null) {
+__device__ __forceinline__ void lp_blockmax_body(const int32_t *__restrict__ blk, const LpInc *__restrict__ ctl, int64_t n,
+                                                 const double *__restrict__ f_new, const double *__restrict__ f_old,
+                                                 double *__restrict__ bmax) {
     __shared__ double red[4];
-    if (st_or_null && st_or_null->done) return;  // a sweep enqueued past convergence wrote nothing
     const int count = blk ? ctl->blocks : (int)gridDim.x;
     for (int q = blockIdx.x; q < count; q += gridDim.x) {
         const int64_t b = blk ? (int64_t)blk[q] : (int64_t)q;
@@ -424,15 +503,25 @@ __global__ __launch_bounds__(256) void k_lp_blockmax(const int32_t *__restrict__
         __syncthreads();
     }
 }
+__global__ __launch_bounds__(256) void k_lp_blockmax(const int32_t *__restrict__ blk, const LpInc *__restrict__ ctl, int64_t n,
+                                                     const double *__restrict__ f_new, const double *__restrict__ f_old,
+                                                     double *__restrict__ bmax, const LpState *__restrict__ st_or_null) {
+    if (st_or_null && st_or_null->done) return;  // a sweep enqueued past convergence wrote nothing
+    lp_blockmax_body(blk, ctl, n, f_new, f_old, bmax);
+}
+__global__ __launch_bounds__(256) void k_lp_blockmax_b(int k, const LpSlot *__restrict__ tab) {
+    const LpSlot &d = tab[blockIdx.y];
+    if (k > d.levels) return;
+    lp_blockmax_body(d.blk, d.ctl, d.n, d.f[k], d.f[k - 1], d.bmax[k]);
+}
 
 // per kept sweep (blockIdx.x + 1): the maximum over all its blocks
 struct LpBmaxPtrs {
     const double *p[8];
 };
-__global__ __launch_bounds__(1024) void k_lp_levelmax(LpBmaxPtrs bm, int64_t nb, LpInc *__restrict__ ctl) {
+__device__ __forceinline__ void lp_levelmax_body(const double *__restrict__ bmax, int64_t nb, LpInc *__restrict__ ctl) {
     __shared__ double red[16];
     const int k = blockIdx.x + 1;
-    const double *bmax = bm.p[k];
     double m = 0.0;
     for (int64_t i = threadIdx.x; i < nb; i += 1024) m = fmax(m, bmax[i]);
 #pragma unroll
@@ -444,6 +533,14 @@ __global__ __launch_bounds__(1024) void k_lp_levelmax(LpBmaxPtrs bm, int64_t nb,
         ctl->level_max[k] = m;
     }
 }
+__global__ __launch_bounds__(1024) void k_lp_levelmax(LpBmaxPtrs bm, int64_t nb, LpInc *__restrict__ ctl) {
+    lp_levelmax_body(bm.p[blockIdx.x + 1], nb, ctl);
+}
+__global__ __launch_bounds__(1024) void k_lp_levelmax_b(const LpSlot *__restrict__ tab) {
+    const LpSlot &d = tab[blockIdx.y];
+    if ((int)blockIdx.x + 1 > d.levels) return;
+    lp_levelmax_body(d.bmax[blockIdx.x + 1], (d.n + 255) / 256, d.ctl);
+}
 
 // The tail of a fused round (ssw_labelprop_round): the incremental pass's answer is iterate conv - 1, conv = the first
 // sweep whose maximum over all blocks is below eps (the host's rule, lp_run_tracked) -- decided HERE from the control
@@ -453,9 +550,7 @@ __global__ __launch_bounds__(1024) void k_lp_levelmax(LpBmaxPtrs bm, int64_t nb,
 struct LpFPtrs {
     const double *p[8];
 };
-__global__ void k_lp_scores_sel(LpFPtrs fp, const LpInc *__restrict__ ctl, int levels, double eps,
-                                const unsigned char *__restrict__ is_label_or_null, const int32_t *__restrict__ perm_or_null,
-                                int64_t n, float *__restrict__ out, LpInc *__restrict__ host_copy) {
+__device__ __forceinline__ int lp_scores_conv(const LpInc *__restrict__ ctl, int levels, double eps, LpInc *__restrict__ host_copy) {
     int conv = 0;
     if (!ctl->overflow && !ctl->bound_violation)
         for (int k = 1; k <= levels; ++k)
@@ -469,12 +564,46 @@ __global__ void k_lp_scores_sel(LpFPtrs fp, const LpInc *__restrict__ ctl, int l
         *host_copy = c;
         __threadfence_system();
     }
-    if (!conv) return;
-    const double *__restrict__ f = fp.p[conv - 1];
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    return conv;
+}
+// element i of the f32 scores the selection reads: labelled nodes at -inf, through the node order where the handle has one
+__device__ __forceinline__ void lp_score_store(const double *__restrict__ f, const unsigned char *__restrict__ is_label_or_null,
+                                               const int32_t *__restrict__ perm_or_null, int64_t n, float *__restrict__ out, int64_t i) {
     if (i >= n) return;
     const int64_t r = perm_or_null ? (int64_t)perm_or_null[i] : i;
     out[i] = (is_label_or_null && is_label_or_null[r]) ? -INFINITY : (float)f[r];
+}
+// ... one element a thread
+__device__ __forceinline__ void lp_scores_write(const double *__restrict__ f, const unsigned char *__restrict__ is_label_or_null,
+                                                const int32_t *__restrict__ perm_or_null, int64_t n, float *__restrict__ out) {
+    lp_score_store(f, is_label_or_null, perm_or_null, n, out, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+__global__ void k_lp_scores_sel(LpFPtrs fp, const LpInc *__restrict__ ctl, int levels, double eps,
+                                const unsigned char *__restrict__ is_label_or_null, const int32_t *__restrict__ perm_or_null,
+                                int64_t n, float *__restrict__ out, LpInc *__restrict__ host_copy) {
+    const int conv = lp_scores_conv(ctl, levels, eps, host_copy);
+    if (!conv) return;
+    lp_scores_write(fp.p[conv - 1], is_label_or_null, perm_or_null, n, out);
+}
+// Batched form: slot blockIdx.y's scores into ITS slab.  A slot that joined the chunk without an incremental pass (the
+// prior ranks, or the labels did not change) names its iterate in the descriptor and has no control block.  A workgroup
+// writes LP_SCORES_B_PER_THREAD x 256 elements: what it reads first -- the descriptor, then the control block, then the
+// iterate's address -- is a chain of dependent loads that one element a thread does not pay for (measured at 1.56 M
+// nodes x 16 slots: 160 us with one element a thread, docs/EXPERIMENTS.md "Batched graph round").
+constexpr int LP_SCORES_B_PER_THREAD = 8;
+__global__ __launch_bounds__(256) void k_lp_scores_sel_b(const LpSlot *__restrict__ tab) {
+    const LpSlot &d = tab[blockIdx.y];
+    int res = d.fixed_result;
+    if (res < 0) {
+        const int conv = lp_scores_conv(d.ctl, d.levels, d.eps, d.host_copy);
+        if (!conv) return;
+        res = conv - 1;
+    }
+    const double *__restrict__ f = d.f[res];
+    const unsigned char *__restrict__ lab = d.mask_labeled ? d.is_label : (const unsigned char *)nullptr;
+    const int64_t base = (int64_t)blockIdx.x * (LP_SCORES_B_PER_THREAD * 256) + threadIdx.x;
+#pragma unroll
+    for (int u = 0; u < LP_SCORES_B_PER_THREAD; ++u) lp_score_store(f, lab, d.perm, d.n, d.out, base + (int64_t)u * 256);
 }
 
 __global__ void k_lp_clear_labels(unsigned char *is_label, const int64_t *ids, int64_t n_labels) {
@@ -590,10 +719,7 @@ __global__ void k_lp_scores_f32_perm(const double *__restrict__ f, const unsigne
 
 __global__ void k_lp_scores_f32_perm_or_plain(const double *__restrict__ f, const unsigned char *__restrict__ is_label_or_null,
                                               const int32_t *__restrict__ perm_or_null, int64_t n, float *__restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int64_t r = perm_or_null ? (int64_t)perm_or_null[i] : i;
-    out[i] = (is_label_or_null && is_label_or_null[r]) ? -INFINITY : (float)f[r];
+    lp_scores_write(f, is_label_or_null, perm_or_null, n, out);
 }
 
 __global__ void k_lp_gather(const double *__restrict__ f, const int64_t *__restrict__ rows, int64_t m,
@@ -669,7 +795,13 @@ struct ssw_lp {
     // what the last propagation did (ssw_labelprop_last_run_info)
     int64_t info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     LpInc *round_host = nullptr;  // pinned, device-mapped: the control block as the fused round's scores kernel saw it
+    // ssw_labelprop_round_batch: the handle of a call's first slot lends the descriptor table of a chunk (pinned host
+    // copy + device copy, LP_BATCH_CHUNK entries); every slot's handle keeps the message of its own status
+    LpSlot *tab_host = nullptr, *tab_dev = nullptr;
+    std::string batch_error;
 };
+static_assert(LP_KEEP == ssw_lp::KEEP, "LpSlot holds one pointer per kept iterate");
+constexpr int LP_BATCH_CHUNK = 16;  // slots of one chunk of ssw_labelprop_round_batch: the index's batch slabs (index_round_slabs)
 
 // the rest of a feedback round behind the propagation (ssw_labelprop_round): f32 scores into the index + the selection
 struct LpRoundTail {
@@ -714,6 +846,8 @@ ssw_status ssw_labelprop_destroy(ssw_lp *lp) {
     (void)hipFree(lp->inc_dev);
     if (lp->inc_host) (void)hipHostFree(lp->inc_host);
     if (lp->round_host) (void)hipHostFree(lp->round_host);
+    if (lp->tab_host) (void)hipHostFree(lp->tab_host);
+    (void)hipFree(lp->tab_dev);
     (void)hipFree(lp->is_label);
     (void)hipFree(lp->g_rows);
     (void)hipFree(lp->g_vals);
@@ -1215,17 +1349,25 @@ static ssw_status lp_reserve_labels(ssw_lp *lp, const std::vector<int64_t> &ids)
     return SSW_OK;
 }
 
-static ssw_status lp_run_tracked(ssw_lp *lp, const int64_t *label_ids, const double *label_vals, int64_t n_labels,
-                                 double reg_lambda, double eps, int32_t max_iter, LpState *st_out, LpRoundTail *tail = nullptr) {
-    SSW_REQUIRE(reg_lambda >= 0.0, "reg_lambda < 0");
-    SSW_REQUIRE(max_iter >= 0, "max_iter < 0");
-    SSW_REQUIRE(n_labels == 0 || (label_ids && label_vals), "NULL labels");
-    for (int64_t i = 0; i < n_labels; ++i)
-        SSW_REQUIRE(label_ids[i] >= 0 && label_ids[i] < lp->n, "label id %lld out of range", (long long)label_ids[i]);
-    const int64_t n = lp->n, nb = (n + 255) / 256;
-    hipStream_t s = lp->stream;
-    const double lo = lp->prior_lo, hi = lp->prior_hi;
-    const auto t_entry = std::chrono::steady_clock::now();
+// ---- a tracked run in its parts, shared by the single driver (lp_run_tracked) and the batched one
+// (ssw_labelprop_round_batch): the plan, made on the host before anything is enqueued; the staging of an incremental
+// pass; the reading of its control block; the full sweeps that start or continue a run.
+struct LpPlan {
+    enum Route {
+        CORE,         // duplicate ids or max_iter == 0: the untracked path (lp_run_core)
+        UNCHANGED,    // the same labels: the kept iterates are the answer
+        INCREMENTAL,  // the incremental pass over the kept iterates
+        FULL          // full sweeps from the prior (a first run, other parameters, too large a change, switched off)
+    } route = FULL;
+    std::vector<int64_t> ids;   // the labels in device positions, ascending
+    std::vector<double> vals;
+    std::vector<int64_t> set_ids, unset_ids;  // INCREMENTAL: labels set (new, or another value) and labels removed
+    std::vector<double> set_vals;
+};
+
+// Changes nothing on the handle but its id-mapping scratch.  The arguments have been checked (lp_check_tracked_args).
+static void lp_plan(ssw_lp *lp, const int64_t *label_ids, const double *label_vals, int64_t n_labels, double reg_lambda,
+                    double eps, int32_t max_iter, LpPlan &pl) {
     // the labels in device positions, ascending; duplicate ids (numpy: the last assignment wins) take the untracked path
     const int64_t *mapped = lp_map_ids(lp, label_ids, n_labels);
     std::vector<std::pair<int64_t, double>> lab((size_t)n_labels);
@@ -1234,22 +1376,22 @@ static ssw_status lp_run_tracked(ssw_lp *lp, const int64_t *label_ids, const dou
     bool unique = true;
     for (size_t i = 1; i < lab.size(); ++i) unique = unique && lab[i].first != lab[i - 1].first;
     const bool inc_off = getenv("SSW_LP_NO_INCREMENTAL") != nullptr;  // A/B and tests: every call runs the full sweeps (read per call)
-    if (!unique || max_iter == 0)
-        return lp_run_core(lp, nullptr, true, nullptr, label_ids, label_vals, n_labels, reg_lambda, eps, max_iter, st_out);
-    std::vector<int64_t> ids((size_t)n_labels);
-    std::vector<double> vals((size_t)n_labels);
-    for (size_t i = 0; i < lab.size(); ++i) ids[i] = lab[i].first, vals[i] = lab[i].second;
-    SSW_TRY(lp_reserve_labels(lp, ids));
-    ssw_lp::Track &tk = lp->trk;
-    LpState st;
-    memset(&st, 0, sizeof(st));
-
-    bool inc = !inc_off && lp->ht_indptr != nullptr && tk.valid && tk.lambda == reg_lambda && tk.eps == eps && tk.max_iter == max_iter && tk.levels >= 1;
-    int continue_from = 0;  // > 0: the incremental pass brought iterates 0 .. continue_from up to date without converging
+    if (!unique || max_iter == 0) {
+        pl.route = LpPlan::CORE;
+        return;
+    }
+    pl.ids.resize((size_t)n_labels);
+    pl.vals.resize((size_t)n_labels);
+    for (size_t i = 0; i < lab.size(); ++i) pl.ids[i] = lab[i].first, pl.vals[i] = lab[i].second;
+    const std::vector<int64_t> &ids = pl.ids;
+    const std::vector<double> &vals = pl.vals;
+    const ssw_lp::Track &tk = lp->trk;
+    const bool inc = !inc_off && lp->ht_indptr != nullptr && tk.valid && tk.lambda == reg_lambda && tk.eps == eps && tk.max_iter == max_iter && tk.levels >= 1;
+    pl.route = LpPlan::FULL;
     if (inc) {
         // ---- what changed: labels set (new, or another value) and labels removed
-        std::vector<int64_t> set_ids, unset_ids;
-        std::vector<double> set_vals;
+        std::vector<int64_t> &set_ids = pl.set_ids, &unset_ids = pl.unset_ids;
+        std::vector<double> &set_vals = pl.set_vals;
         size_t a = 0, b = 0;
         while (a < ids.size() || b < tk.ids.size()) {
             if (b == tk.ids.size() || (a < ids.size() && ids[a] < tk.ids[b])) {
@@ -1261,51 +1403,157 @@ static ssw_status lp_run_tracked(ssw_lp *lp, const int64_t *label_ids, const dou
                 ++a, ++b;
             }
         }
-        if (set_ids.empty() && unset_ids.empty()) {  // the same labels: the kept iterates ARE the answer
-            st.sweeps = tk.sweeps, st.done = 1, st.result_buf = tk.result;
-            lp->last_result = tk.result;
-            lp->info[0] = 1, lp->info[1] = st.sweeps, lp->info[2] = 0, lp->info[3] = 0, lp->info[4] = 0, lp->info[5] = tk.levels;
-            *st_out = st;
-            return SSW_OK;
-        }
-        // ---- frontier on the device: the changed labels seed the row list; sweep k first extends it by the in-neighbours
-        // of the rows that joined one sweep earlier, then recomputes every listed row and the maxima of the touched blocks;
-        // the nested sets make ONE list serve every sweep by its prefix.  Nothing but the label lists is uploaded.
-        const int64_t n_set = (int64_t)set_ids.size(), n_unset = (int64_t)unset_ids.size();
-        if (n_set + n_unset > lp->cap_rows) inc = false;
-        if (inc) {
-            if (++lp->epoch == 0) {  // (wrapped)
-                SSW_HIP_TRY(hipMemsetAsync(lp->stamp, 0, (size_t)n * sizeof(uint32_t), s));
-                SSW_HIP_TRY(hipMemsetAsync(lp->bstamp, 0, (size_t)nb * sizeof(uint32_t), s));
-                lp->epoch = 1;
-            }
-            const uint32_t ep = lp->epoch;
-            // one packed upload: [set ids | unset ids | set values | all ids | all values], then the control block
-            const int64_t o_ch = 0, o_sv = n_set + n_unset, o_ids = o_sv + n_set, o_vals = o_ids + n_labels, words = o_vals + n_labels + 64;
-            SSW_TRY(lp_inc_reserve(lp, words));
-            int64_t *hb = lp->inc_host;
-            for (int64_t i = 0; i < n_set; ++i) hb[o_ch + i] = set_ids[(size_t)i];
-            for (int64_t i = 0; i < n_unset; ++i) hb[o_ch + n_set + i] = unset_ids[(size_t)i];
-            memcpy(hb + o_sv, set_vals.data(), (size_t)n_set * sizeof(double));
-            memcpy(hb + o_ids, ids.data(), (size_t)n_labels * sizeof(int64_t));
-            memcpy(hb + o_vals, vals.data(), (size_t)n_labels * sizeof(double));
-            const int64_t o_ctl = o_vals + n_labels;  // the control block travels with the lists (64 words of slack hold its 128 bytes)
-            LpInc *hctl = reinterpret_cast<LpInc *>(hb + o_ctl);
-            memset(hctl, 0, sizeof(LpInc));
-            hctl->total = (int)(n_set + n_unset);
-            hctl->m[0] = (int)(n_set + n_unset);
-            SSW_HIP_TRY(hipMemcpyAsync(lp->inc_dev, hb, (size_t)(o_ctl + 16) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-            int64_t *db = lp->inc_dev;
-            LpInc *dctl = reinterpret_cast<LpInc *>(db + o_ctl);
-            hipLaunchKernelGGL(k_inc_seed, dim3((unsigned)((std::max<int64_t>(n_set + n_unset, n_labels) + 255) / 256)), dim3(256), 0, s,
-                               db + o_ch, reinterpret_cast<const double *>(db + o_sv), (int)n_set, (int)n_unset, lp->prior, lp->f[0],
-                               lp->is_label, lp->label_val, lp->stamp, ep, lp->mem, db + o_ids,
-                               reinterpret_cast<const double *>(db + o_vals), (int)n_labels, lp->ids, lp->vals);
-            // from here on the device holds THESE labels: whatever happens below (an error return included), the kept
-            // state describes them or nothing -- it is valid again only where a branch says so
-            const int kept_levels = tk.levels;
-            tk.valid = false;
-            tk.ids = ids, tk.vals = vals;
+        if (set_ids.empty() && unset_ids.empty()) pl.route = LpPlan::UNCHANGED;  // the same labels: the kept iterates ARE the answer
+        else if ((int64_t)(set_ids.size() + unset_ids.size()) <= lp->cap_rows) pl.route = LpPlan::INCREMENTAL;
+    }
+}
+
+// what every tracked entry checks before it plans
+static ssw_status lp_check_tracked_args(const ssw_lp *lp, const int64_t *label_ids, const double *label_vals, int64_t n_labels,
+                                        double reg_lambda, int32_t max_iter) {
+    SSW_REQUIRE(reg_lambda >= 0.0, "reg_lambda < 0");
+    SSW_REQUIRE(max_iter >= 0, "max_iter < 0");
+    SSW_REQUIRE(n_labels == 0 || (label_ids && label_vals), "NULL labels");
+    for (int64_t i = 0; i < n_labels; ++i)
+        SSW_REQUIRE(label_ids[i] >= 0 && label_ids[i] < lp->n, "label id %lld out of range", (long long)label_ids[i]);
+    return SSW_OK;
+}
+
+// LpPlan::UNCHANGED: nothing is enqueued
+static void lp_unchanged_result(ssw_lp *lp, LpState *st_out) {
+    const ssw_lp::Track &tk = lp->trk;
+    LpState st;
+    memset(&st, 0, sizeof(st));
+    st.sweeps = tk.sweeps, st.done = 1, st.result_buf = tk.result;
+    lp->last_result = tk.result;
+    lp->info[0] = 1, lp->info[1] = st.sweeps, lp->info[2] = 0, lp->info[3] = 0, lp->info[4] = 0, lp->info[5] = tk.levels;
+    *st_out = st;
+}
+
+// An incremental pass as it stands on the device after lp_inc_stage: where the packed lists and the control block are
+struct LpIncStage {
+    const int64_t *ch_ids = nullptr, *all_ids = nullptr;   // device: [set ids | unset ids], every label's id
+    const double *set_vals = nullptr, *all_vals = nullptr;  // device: the set labels' values, every label's value
+    LpInc *dctl = nullptr, *hctl = nullptr;                 // the control block: device, and where it was staged (pinned)
+    int n_set = 0, n_unset = 0, n_labels = 0;
+    int levels = 0;                                         // the kept levels the pass updates
+    uint32_t ep = 0;
+};
+
+// LpPlan::INCREMENTAL, first half: a fresh epoch, ONE packed upload -- [set ids | unset ids | set values | all ids | all
+// values], then the control block -- and the handle's host state moved to "the device holds THESE labels": whatever
+// happens afterwards (an error return included), the kept state describes them or nothing; it is valid again only where
+// lp_inc_outcome says so.  The caller launches the seed kernel (which refreshes lp->ids / lp->vals) and the sweeps.
+// ---- frontier on the device: the changed labels seed the row list; sweep k first extends it by the in-neighbours
+// of the rows that joined one sweep earlier, then recomputes every listed row and the maxima of the touched blocks;
+// the nested sets make ONE list serve every sweep by its prefix.  Nothing but the label lists is uploaded.
+static ssw_status lp_inc_stage(ssw_lp *lp, const LpPlan &pl, LpIncStage &sg) {
+    const int64_t n = lp->n, nb = (n + 255) / 256;
+    hipStream_t s = lp->stream;
+    ssw_lp::Track &tk = lp->trk;
+    const int64_t n_set = (int64_t)pl.set_ids.size(), n_unset = (int64_t)pl.unset_ids.size(), n_labels = (int64_t)pl.ids.size();
+    if (++lp->epoch == 0) {  // (wrapped)
+        SSW_HIP_TRY(hipMemsetAsync(lp->stamp, 0, (size_t)n * sizeof(uint32_t), s));
+        SSW_HIP_TRY(hipMemsetAsync(lp->bstamp, 0, (size_t)nb * sizeof(uint32_t), s));
+        lp->epoch = 1;
+    }
+    const int64_t o_ch = 0, o_sv = n_set + n_unset, o_ids = o_sv + n_set, o_vals = o_ids + n_labels, words = o_vals + n_labels + 64;
+    SSW_TRY(lp_inc_reserve(lp, words));
+    int64_t *hb = lp->inc_host;
+    for (int64_t i = 0; i < n_set; ++i) hb[o_ch + i] = pl.set_ids[(size_t)i];
+    for (int64_t i = 0; i < n_unset; ++i) hb[o_ch + n_set + i] = pl.unset_ids[(size_t)i];
+    memcpy(hb + o_sv, pl.set_vals.data(), (size_t)n_set * sizeof(double));
+    memcpy(hb + o_ids, pl.ids.data(), (size_t)n_labels * sizeof(int64_t));
+    memcpy(hb + o_vals, pl.vals.data(), (size_t)n_labels * sizeof(double));
+    const int64_t o_ctl = o_vals + n_labels;  // the control block travels with the lists (64 words of slack hold its 128 bytes)
+    LpInc *hctl = reinterpret_cast<LpInc *>(hb + o_ctl);
+    memset(hctl, 0, sizeof(LpInc));
+    hctl->total = (int)(n_set + n_unset);
+    hctl->m[0] = (int)(n_set + n_unset);
+    SSW_HIP_TRY(hipMemcpyAsync(lp->inc_dev, hb, (size_t)(o_ctl + 16) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    int64_t *db = lp->inc_dev;
+    sg.ch_ids = db + o_ch, sg.all_ids = db + o_ids;
+    sg.set_vals = reinterpret_cast<const double *>(db + o_sv), sg.all_vals = reinterpret_cast<const double *>(db + o_vals);
+    sg.dctl = reinterpret_cast<LpInc *>(db + o_ctl), sg.hctl = hctl;
+    sg.n_set = (int)n_set, sg.n_unset = (int)n_unset, sg.n_labels = (int)n_labels;
+    sg.levels = tk.levels, sg.ep = lp->epoch;
+    tk.valid = false;
+    tk.ids = pl.ids, tk.vals = pl.vals;
+    lp->n_labels_installed = n_labels;
+    return SSW_OK;
+}
+
+// LpPlan::INCREMENTAL, second half: what the pass's control block says.  *finished: the pass converged within the kept
+// levels -- *st_out and the handle are the call's result.  Otherwise the caller goes on with lp_full_sweeps from
+// *continue_from: 0 after an overflow (the change reaches more than n / 8 rows: rows beyond the list were not recomputed,
+// so the kept iterates are no longer a run's -- start over from the labels just installed), else the kept levels (the new
+// labels need more sweeps than were kept: iterates 0 .. levels ARE the new run's, every row either unchanged or
+// recomputed).  A value outside the bounds is SSW_ERR_NUMERIC.
+static ssw_status lp_inc_outcome(ssw_lp *lp, const LpInc &rctl, const LpIncStage &sg, double eps, int64_t launches,
+                                 LpState *st_out, bool *finished, int *continue_from) {
+    ssw_lp::Track &tk = lp->trk;
+    *finished = false;
+    *continue_from = 0;
+    if (rctl.overflow) return SSW_OK;
+    if (rctl.bound_violation) {
+        tk.valid = false;
+        set_error("label propagation: averaged scores left [%g, %g] (label_propagation.py:39-40)", lp->prior_lo, lp->prior_hi);
+        return SSW_ERR_NUMERIC;
+    }
+    int64_t rows_total = 0;
+    for (int k = 1; k <= sg.levels; ++k) rows_total += rctl.m[k];
+    int conv = 0;
+    for (int k = 1; k <= sg.levels && !conv; ++k)
+        if (rctl.level_max[k] < eps) conv = k;
+    if (conv) {
+        LpState st;
+        memset(&st, 0, sizeof(st));
+        st.sweeps = conv, st.done = 1, st.result_buf = conv - 1;
+        tk.valid = true, tk.levels = sg.levels;
+        tk.sweeps = conv, tk.result = conv - 1;
+        lp->last_result = conv - 1;
+        lp->sweeps_hint = conv;
+        lp->info[0] = 1, lp->info[1] = conv, lp->info[2] = launches, lp->info[3] = 1, lp->info[4] = rows_total,
+        lp->info[5] = tk.levels;
+        *st_out = st;
+        *finished = true;
+        return SSW_OK;
+    }
+    *continue_from = sg.levels;
+    return SSW_OK;
+}
+
+static ssw_status lp_full_sweeps(ssw_lp *lp, const LpPlan &pl, double reg_lambda, double eps, int32_t max_iter, int continue_from,
+                                 LpState *st_out);
+
+static ssw_status lp_run_tracked(ssw_lp *lp, const int64_t *label_ids, const double *label_vals, int64_t n_labels,
+                                 double reg_lambda, double eps, int32_t max_iter, LpState *st_out, LpRoundTail *tail = nullptr) {
+    SSW_TRY(lp_check_tracked_args(lp, label_ids, label_vals, n_labels, reg_lambda, max_iter));
+    const int64_t n = lp->n, nb = (n + 255) / 256;
+    hipStream_t s = lp->stream;
+    const double lo = lp->prior_lo, hi = lp->prior_hi;
+    const auto t_entry = std::chrono::steady_clock::now();
+    LpPlan pl;
+    lp_plan(lp, label_ids, label_vals, n_labels, reg_lambda, eps, max_iter, pl);
+    if (pl.route == LpPlan::CORE)
+        return lp_run_core(lp, nullptr, true, nullptr, label_ids, label_vals, n_labels, reg_lambda, eps, max_iter, st_out);
+    SSW_TRY(lp_reserve_labels(lp, pl.ids));
+    ssw_lp::Track &tk = lp->trk;
+    if (pl.route == LpPlan::UNCHANGED) {
+        lp_unchanged_result(lp, st_out);
+        return SSW_OK;
+    }
+    int continue_from = 0;  // > 0: the incremental pass brought iterates 0 .. continue_from up to date without converging
+    if (pl.route == LpPlan::INCREMENTAL) {
+        {
+            LpIncStage sg;
+            SSW_TRY(lp_inc_stage(lp, pl, sg));
+            const uint32_t ep = sg.ep;
+            LpInc *dctl = sg.dctl, *hctl = sg.hctl;
+            hipLaunchKernelGGL(k_inc_seed, dim3((unsigned)((std::max<int64_t>(sg.n_set + sg.n_unset, sg.n_labels) + 255) / 256)), dim3(256), 0, s,
+                               sg.ch_ids, sg.set_vals, sg.n_set, sg.n_unset, lp->prior, lp->f[0],
+                               lp->is_label, lp->label_val, lp->stamp, ep, lp->mem, sg.all_ids,
+                               sg.all_vals, sg.n_labels, lp->ids, lp->vals);
             LpBmaxPtrs bm;
             for (int k = 0; k < ssw_lp::KEEP; ++k) bm.p[k] = lp->bmax[k];
             for (int k = 1; k <= tk.levels; ++k) {
@@ -1319,7 +1567,6 @@ static ssw_status lp_run_tracked(ssw_lp *lp, const int64_t *label_ids, const dou
             }
             hipLaunchKernelGGL(k_lp_levelmax, dim3((unsigned)tk.levels), dim3(1024), 0, s, bm, nb, dctl);
             SSW_HIP_TRY(hipGetLastError());
-            lp->n_labels_installed = n_labels;  // (k_inc_seed refreshed lp->ids / lp->vals)
             LpInc rctl;
             if (tail) {
                 // fused round: the scores kernel picks the converged iterate itself and leaves the control block in pinned
@@ -1354,42 +1601,29 @@ static ssw_status lp_run_tracked(ssw_lp *lp, const int64_t *label_ids, const dou
                 lp->info[7] = (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_wait0).count();
                 memcpy(&rctl, hctl, sizeof(LpInc));
             }
-            LpState dst;
-            memset(&dst, 0, sizeof(dst));
-            dst.bound_violation = rctl.bound_violation;
-            if (rctl.overflow) {
-                // the change reaches more than n / 8 rows: rows beyond the list were not recomputed, so the kept iterates
-                // are no longer a run's -- start over with the full sweeps (from the labels just installed)
-                inc = false;
-            } else if (dst.bound_violation) {
-                tk.valid = false;
-                set_error("label propagation: averaged scores left [%g, %g] (label_propagation.py:39-40)", lo, hi);
-                return SSW_ERR_NUMERIC;
-            } else {
-                int64_t rows_total = 0;
-                for (int k = 1; k <= tk.levels; ++k) rows_total += rctl.m[k];
-                int conv = 0;
-                for (int k = 1; k <= tk.levels && !conv; ++k)
-                    if (rctl.level_max[k] < eps) conv = k;
-                if (conv) {
-                    st.sweeps = conv, st.done = 1, st.result_buf = conv - 1;
-                    tk.valid = true, tk.levels = kept_levels;
-                    tk.sweeps = conv, tk.result = conv - 1;
-                    lp->last_result = conv - 1;
-                    lp->sweeps_hint = conv;
-                    lp->info[0] = 1, lp->info[1] = conv, lp->info[2] = 2 + 3 * (int64_t)tk.levels, lp->info[3] = 1, lp->info[4] = rows_total,
-                    lp->info[5] = tk.levels;
-                    *st_out = st;
-                    return SSW_OK;
-                }
-                // the new labels need more sweeps than were kept: iterates 0 .. levels ARE the new run's (every row either
-                // unchanged or recomputed), so the full sweeps below continue from sweep levels + 1
-                continue_from = tk.levels;
-            }
+            bool finished = false;
+            SSW_TRY(lp_inc_outcome(lp, rctl, sg, eps, 2 + 3 * (int64_t)sg.levels, st_out, &finished, &continue_from));
+            if (finished) return SSW_OK;
         }
     }
+    return lp_full_sweeps(lp, pl, reg_lambda, eps, max_iter, continue_from, st_out);
+}
 
-    // ---- full sweeps, every iterate and its block maxima kept (the state the next call updates)
+// ---- full sweeps, every iterate and its block maxima kept (the state the next call updates): from the installed prior
+// and pl's labels (continue_from == 0: a first run, or an incremental pass that overflowed its frontier), or from
+// iterate continue_from of an incremental pass that did not converge within the kept levels.  The one continuation of
+// both drivers.
+static ssw_status lp_full_sweeps(ssw_lp *lp, const LpPlan &pl, double reg_lambda, double eps, int32_t max_iter, int continue_from,
+                                 LpState *st_out) {
+    const int64_t n = lp->n, nb = (n + 255) / 256;
+    hipStream_t s = lp->stream;
+    const double lo = lp->prior_lo, hi = lp->prior_hi;
+    const std::vector<int64_t> &ids = pl.ids;
+    const std::vector<double> &vals = pl.vals;
+    const int64_t n_labels = (int64_t)ids.size();
+    ssw_lp::Track &tk = lp->trk;
+    LpState st;
+    memset(&st, 0, sizeof(st));
     tk.valid = false;
     if (continue_from > 0) {
         LpState init;
@@ -1627,6 +1861,14 @@ ssw_status ssw_labelprop_scores_to_index(ssw_lp *lp, ssw_index *index, int32_t m
     return SSW_OK;
 }
 
+static ssw_status lp_round_run(ssw_lp *lp, ssw_index *index, float *scores, int32_t propagate, const int64_t *label_ids,
+                               const double *label_vals, int64_t n_labels, double reg_lambda, double eps, int32_t max_iter,
+                               int32_t mask_labeled, const int64_t *excluded_images, int64_t n_excluded, int32_t k,
+                               int64_t *out_images, float *out_scores, int64_t *out_best_rows, int32_t *out_count,
+                               int32_t *out_sweeps, int32_t *out_converged);
+static ssw_status lp_scores_and_select(ssw_lp *lp, ssw_index *index, float *scores, int32_t mask_labeled,
+                                       const int64_t *excluded_images, int64_t n_excluded, int32_t k, int64_t *out_images,
+                                       float *out_scores, int64_t *out_best_rows, int32_t *out_count);
 
 /* One feedback round of a graph loop in ONE call (KnnProp2.refine + next_batch, seesaw/loops/graph_based.py:73-121;
  * LabelPropagationRanker2.update, research/knn_methods.py:176-199):
@@ -1658,6 +1900,18 @@ ssw_status ssw_labelprop_round(ssw_lp *lp, ssw_index *index, int32_t propagate, 
                     (long long)excluded_images[i], (long long)n_images);
     SSW_TRY(ssw_index_sync(index));  // nothing of the index's own stream still touches the score buffer / the workspace
     DeviceGuard guard(lp->device);
+    return lp_round_run(lp, index, (float *)scores, propagate, label_ids, label_vals, n_labels, reg_lambda, eps, max_iter,
+                        mask_labeled, excluded_images, n_excluded, k, out_images, out_scores, out_best_rows, out_count, out_sweeps,
+                        out_converged);
+}
+
+// The round itself, on lp->stream: arguments checked, the index's own stream idle, the device set.  `scores`: the index's
+// own score buffer.  The single call, and inside ssw_labelprop_round_batch every slot that is not batched.
+static ssw_status lp_round_run(ssw_lp *lp, ssw_index *index, float *scores, int32_t propagate, const int64_t *label_ids,
+                               const double *label_vals, int64_t n_labels, double reg_lambda, double eps, int32_t max_iter,
+                               int32_t mask_labeled, const int64_t *excluded_images, int64_t n_excluded, int32_t k,
+                               int64_t *out_images, float *out_scores, int64_t *out_best_rows, int32_t *out_count,
+                               int32_t *out_sweeps, int32_t *out_converged) {
     SSW_TRY(lp_session_buffers(lp));
     LpRoundTail tail;
     tail.index = index, tail.index_scores = (float *)scores, tail.mask_labeled = mask_labeled != 0;
@@ -1676,13 +1930,360 @@ ssw_status ssw_labelprop_round(ssw_lp *lp, ssw_index *index, int32_t propagate, 
     if (tail.valid) return SSW_OK;
     // the propagation took another path (a session's first run, more sweeps than were kept, ...): its answer is
     // lp->f[lp->last_result] by now -- scores and selection behind it, one more wait
+    return lp_scores_and_select(lp, index, scores, mask_labeled, excluded_images, n_excluded, k, out_images, out_scores,
+                                out_best_rows, out_count);
+}
+
+// lp->f[lp->last_result] -> the index's own score buffer, the selection over it, its wait
+static ssw_status lp_scores_and_select(ssw_lp *lp, ssw_index *index, float *scores, int32_t mask_labeled,
+                                       const int64_t *excluded_images, int64_t n_excluded, int32_t k, int64_t *out_images,
+                                       float *out_scores, int64_t *out_best_rows, int32_t *out_count) {
+    const int64_t n = lp->n;
     hipLaunchKernelGGL(k_lp_scores_f32_perm_or_plain, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, lp->stream,
                        lp->f[lp->last_result], mask_labeled ? lp->is_label : (const unsigned char *)nullptr, (const int32_t *)lp->perm, n,
-                       (float *)scores);
+                       scores);
     SSW_HIP_TRY(hipGetLastError());
     SSW_TRY(index_enqueue_topk_resident(index, lp->stream, excluded_images, n_excluded, k));
     return index_collect_topk(index, lp->stream, k, out_images, out_scores, out_best_rows, out_count);
 }
+
+// ---- ssw_labelprop_round_batch ---------------------------------------------------------------------------------------
+// every handle of a call works on the call's stream while the call lasts, so the single path's code -- a slot that is
+// not batched, a continuation -- runs inside the call unchanged
+struct LpStreamLoan {
+    std::vector<std::pair<ssw_lp *, hipStream_t>> own;
+    LpStreamLoan(ssw_lp *const *lps, int32_t S, hipStream_t call_stream) {
+        for (int32_t j = 0; j < S; ++j) {
+            own.push_back({lps[j], lps[j]->stream});
+            lps[j]->stream = call_stream;
+        }
+    }
+    ~LpStreamLoan() {
+        for (auto &o : own) o.first->stream = o.second;
+    }
+};
+
+static int64_t lp_ns_since(std::chrono::steady_clock::time_point t0) {
+    return (int64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+}
+
+ssw_status ssw_labelprop_round_batch(ssw_lp *const *lps, int32_t n_slots, ssw_index *index, const int32_t *propagate,
+                                     const int64_t *label_ids, const double *label_vals, const int64_t *label_offsets,
+                                     const double *reg_lambda, const double *eps, const int32_t *max_iter,
+                                     int32_t mask_labeled, const int64_t *excluded_images, const int64_t *excluded_offsets,
+                                     int32_t k, int64_t *out_images, float *out_scores, int64_t *out_best_rows,
+                                     int32_t *out_counts, int32_t *out_sweeps, int32_t *out_converged, int32_t *out_status,
+                                     int64_t *out_stats4) {
+    // ---- validation: everything below is decided on the host before any device work
+    SSW_REQUIRE(index != nullptr, "NULL argument");
+    SSW_TRY(refuse_view(index, "ssw_labelprop_round_batch"));  // like every batched entry: the chunk's slabs are the index's batch slabs
+    SSW_REQUIRE(n_slots >= 1, "n_slots=%d < 1", n_slots);
+    SSW_REQUIRE(lps && propagate && label_offsets && reg_lambda && eps && max_iter && out_counts && out_status, "NULL argument");
+    SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
+    const int32_t S = n_slots;
+    int64_t n = 0, n_images = 0;
+    int32_t D = 0;
+    SSW_TRY(ssw_index_shape(index, &n, &D, &n_images));
+    for (int32_t j = 0; j < S; ++j) {
+        SSW_REQUIRE(lps[j] != nullptr, "slot %d: NULL handle", j);
+        for (int32_t i = 0; i < j; ++i) SSW_REQUIRE(lps[i] != lps[j], "slots %d and %d name the same handle", i, j);
+        SSW_REQUIRE(lps[j]->device == index_device(index), "slot %d: the index lives on device %d, the graph on device %d", j,
+                    index_device(index), lps[j]->device);
+        SSW_REQUIRE(lps[j]->n == n, "slot %d: the index has %lld rows, the graph %lld nodes", j, (long long)n, (long long)lps[j]->n);
+        SSW_REQUIRE(lps[j]->prior_installed, "slot %d: no prior installed (ssw_labelprop_set_prior)", j);
+    }
+    SSW_REQUIRE(label_offsets[0] >= 0, "label_offsets[0]=%lld < 0", (long long)label_offsets[0]);
+    for (int32_t j = 0; j < S; ++j) SSW_REQUIRE(label_offsets[j] <= label_offsets[j + 1], "label_offsets decrease at slot %d", j);
+    SSW_REQUIRE(label_offsets[S] == label_offsets[0] || (label_ids && label_vals), "NULL labels");
+    for (int32_t j = 0; j < S; ++j)
+        for (int64_t i = label_offsets[j]; i < label_offsets[j + 1]; ++i)
+            SSW_REQUIRE(label_ids[i] >= 0 && label_ids[i] < n, "slot %d: label id %lld out of range", j, (long long)label_ids[i]);
+    if (excluded_offsets) {
+        SSW_REQUIRE(excluded_offsets[0] >= 0, "excluded_offsets[0]=%lld < 0", (long long)excluded_offsets[0]);
+        for (int32_t j = 0; j < S; ++j)
+            SSW_REQUIRE(excluded_offsets[j] <= excluded_offsets[j + 1], "excluded_offsets decrease at slot %d", j);
+        SSW_REQUIRE(excluded_offsets[S] == excluded_offsets[0] || excluded_images != nullptr, "excluded_images is NULL");
+        for (int32_t j = 0; j < S; ++j)
+            for (int64_t i = excluded_offsets[j]; i < excluded_offsets[j + 1]; ++i)
+                SSW_REQUIRE(excluded_images[i] >= 0 && excluded_images[i] < n_images, "slot %d: excluded image %lld outside [0, %lld)",
+                            j, (long long)excluded_images[i], (long long)n_images);
+    }
+    auto excl_of = [&](int32_t j, int64_t *n_ex) -> const int64_t * {
+        *n_ex = excluded_offsets ? excluded_offsets[j + 1] - excluded_offsets[j] : 0;
+        return *n_ex > 0 ? excluded_images + excluded_offsets[j] : nullptr;
+    };
+    int64_t stats[4] = {0, 0, 0, 0};
+    for (int32_t j = 0; j < S; ++j) {
+        out_counts[j] = 0, out_status[j] = SSW_OK;
+        if (out_sweeps) out_sweeps[j] = 0;
+        if (out_converged) out_converged[j] = 0;
+        lps[j]->batch_error.clear();
+    }
+    const auto t_entry = std::chrono::steady_clock::now();
+
+    // ---- streams: the call runs on its first handle's stream; the index and every other handle are idle before anything
+    // is enqueued, and the call ends with everything complete
+    void *scores_v = nullptr;
+    SSW_TRY(ssw_index_device_ptrs(index, nullptr, &scores_v));  // (completes a partial score buffer, as the single round does)
+    float *scores = (float *)scores_v;
+    SSW_TRY(ssw_index_sync(index));
+    DeviceGuard guard(lps[0]->device);
+    hipStream_t s = lps[0]->stream;
+    for (int32_t j = 1; j < S; ++j) SSW_HIP_TRY(hipStreamSynchronize(lps[j]->stream));
+    LpStreamLoan loan(lps, S, s);
+    ssw_lp *host = lps[0];  // lends the descriptor table
+    if (!host->tab_host) {
+        SSW_HIP_TRY(hipHostMalloc((void **)&host->tab_host, LP_BATCH_CHUNK * sizeof(LpSlot), hipHostMallocDefault));
+        SSW_HIP_TRY(hipMalloc((void **)&host->tab_dev, LP_BATCH_CHUNK * sizeof(LpSlot)));
+    }
+    int W = 1;
+    float *slabs[LP_BATCH_CHUNK];
+    SSW_TRY(index_round_slabs(index, std::min<int32_t>(S, LP_BATCH_CHUNK), &W, slabs));
+
+    auto fail = [&](int32_t j, ssw_status rc) {  // a slot's own status and message; the other slots are not affected
+        out_status[j] = rc;
+        out_counts[j] = 0;
+        const char *msg = ssw_last_error();
+        lps[j]->batch_error = msg ? msg : "";
+    };
+    auto outs = [&](int32_t j, int64_t **im, float **sc, int64_t **br) {
+        const size_t o = (size_t)j * (size_t)k;
+        *im = out_images ? out_images + o : nullptr, *sc = out_scores ? out_scores + o : nullptr;
+        *br = out_best_rows ? out_best_rows + o : nullptr;
+    };
+
+    enum Kind { SINGLE, FIXED, INC };
+    struct Member {  // a slot that joined its chunk's batched scores and selection
+        int32_t j;
+        Kind kind;
+        LpPlan plan;
+        LpIncStage sg;
+        LpState st;
+        unsigned seq;       // the sequence word of its selection (0: none in flight)
+        int continue_from;  // an incremental member that was not finished by its pass: where lp_full_sweeps starts
+    };
+    for (int32_t c0 = 0; c0 < S; c0 += W) {
+        const int w = std::min<int32_t>(W, S - c0);
+        for (int i = 0; i < w; ++i) slabs[i] = nullptr;
+        SSW_TRY(index_round_slabs(index, w, &W, slabs));  // (this chunk's slabs: a narrower last chunk ends in the handle's buffer too)
+        std::vector<Member> members;
+        members.reserve((size_t)w);
+        // ---- routing, slot by slot, before anything is enqueued for the slot; a slot that is not batched runs the single
+        // path right here, one after another
+        for (int32_t j = c0; j < c0 + w; ++j) {
+            ssw_lp *lp = lps[j];
+            const int64_t n_lab = label_offsets[j + 1] - label_offsets[j];
+            const int64_t *ids_j = n_lab > 0 ? label_ids + label_offsets[j] : nullptr;
+            const double *vals_j = n_lab > 0 ? label_vals + label_offsets[j] : nullptr;
+            if (ssw_status rc = lp_session_buffers(lp); rc != SSW_OK) {
+                fail(j, rc);
+                continue;
+            }
+            Member mb;
+            mb.j = j, mb.kind = SINGLE, mb.seq = 0, mb.continue_from = 0;
+            memset(&mb.st, 0, sizeof(mb.st));
+            if (!propagate[j]) {
+                // the prior ranks (no negative label yet): its work goes onto the call's stream without a wait, and the
+                // slot joins the batched scores and selection with its result fixed to iterate 0
+                lp->info[0] = 3, lp->info[1] = 0, lp->info[2] = 3, lp->info[3] = 0, lp->info[4] = 0, lp->info[5] = 0, lp->info[6] = 0, lp->info[7] = 0;
+                if (ssw_status rc = lp_prior_as_result(lp, ids_j, n_lab, false); rc != SSW_OK) {
+                    fail(j, rc);
+                    continue;
+                }
+                mb.kind = FIXED;
+            } else if (lp_check_tracked_args(lp, ids_j, vals_j, n_lab, reg_lambda[j], max_iter[j]) == SSW_OK) {
+                lp_plan(lp, ids_j, vals_j, n_lab, reg_lambda[j], eps[j], max_iter[j], mb.plan);
+                if (mb.plan.route == LpPlan::UNCHANGED || mb.plan.route == LpPlan::INCREMENTAL) {
+                    if (ssw_status rc = lp_reserve_labels(lp, mb.plan.ids); rc != SSW_OK) {
+                        fail(j, rc);
+                        continue;
+                    }
+                }
+                if (mb.plan.route == LpPlan::UNCHANGED) {
+                    lp_unchanged_result(lp, &mb.st);
+                    mb.kind = FIXED;
+                } else if (mb.plan.route == LpPlan::INCREMENTAL) {
+                    if (ssw_status rc = lp_inc_stage(lp, mb.plan, mb.sg); rc != SSW_OK) {
+                        fail(j, rc);
+                        continue;
+                    }
+                    mb.kind = INC;
+                }
+            }
+            if (mb.kind == SINGLE) {  // a first full propagation, other parameters, duplicate ids, too large a change, max_iter == 0, bad arguments
+                int64_t n_ex = 0, *im, *br;
+                float *sc;
+                const int64_t *ex = excl_of(j, &n_ex);
+                outs(j, &im, &sc, &br);
+                int32_t sw = 0, cv = 0;
+                const ssw_status rc = lp_round_run(lp, index, scores, 1, ids_j, vals_j, n_lab, reg_lambda[j], eps[j], max_iter[j],
+                                                   mask_labeled, ex, n_ex, k, im, sc, br, out_counts + j, &sw, &cv);
+                if (rc != SSW_OK) fail(j, rc);
+                if (out_sweeps) out_sweeps[j] = sw;
+                if (out_converged) out_converged[j] = cv;
+                stats[3] += 1;
+                stats[2] += lp->info[3] + 1;
+                continue;
+            }
+            members.push_back(std::move(mb));
+        }
+        if (members.empty()) continue;
+        // ---- the batched pass: the incremental members first in the table, then the fixed ones; ONE table upload, the
+        // kernels with the slot on blockIdx.y
+        std::stable_sort(members.begin(), members.end(), [](const Member &a, const Member &b) { return (a.kind == INC) > (b.kind == INC); });
+        int n_inc = 0, max_levels = 0, seed_items = 1;
+        for (size_t m = 0; m < members.size(); ++m) {
+            Member &mb = members[m];
+            ssw_lp *lp = lps[mb.j];
+            LpSlot &d = host->tab_host[m];
+            memset(&d, 0, sizeof(d));
+            d.indptr = lp->indptr, d.ht_indptr = lp->ht_indptr, d.indices = lp->indices, d.ht_indices = lp->ht_indices;
+            d.data = lp->data, d.wsum = lp->wsum, d.prior = lp->prior;
+            for (int q = 0; q < LP_KEEP; ++q) d.f[q] = lp->f[q], d.bmax[q] = lp->bmax[q];
+            d.is_label = lp->is_label, d.label_val = lp->label_val;
+            d.stamp = lp->stamp, d.bstamp = lp->bstamp, d.mem = lp->mem, d.blk = lp->blk;
+            d.ids_out = lp->ids, d.vals_out = lp->vals;
+            d.perm = lp->perm;
+            d.out = slabs[mb.j - c0];
+            d.lambda = reg_lambda[mb.j], d.lo = lp->prior_lo, d.hi = lp->prior_hi, d.eps = eps[mb.j];
+            d.n = n, d.cap = lp->cap_rows, d.mask_labeled = mask_labeled != 0;
+            d.fixed_result = -1;
+            if (mb.kind == INC) {
+                d.ch_ids = mb.sg.ch_ids, d.all_ids = mb.sg.all_ids, d.set_vals = mb.sg.set_vals, d.all_vals = mb.sg.all_vals;
+                d.ctl = mb.sg.dctl;
+                d.n_set = mb.sg.n_set, d.n_unset = mb.sg.n_unset, d.n_all = mb.sg.n_labels, d.levels = mb.sg.levels, d.ep = mb.sg.ep;
+                SSW_HIP_TRY(hipHostGetDevicePointer((void **)&d.host_copy, lp->round_host, 0));
+                lp->round_host->m[8] = -1;
+                ++n_inc;
+                max_levels = std::max(max_levels, mb.sg.levels);
+                seed_items = std::max(seed_items, std::max(mb.sg.n_set + mb.sg.n_unset, mb.sg.n_labels));
+            } else {
+                d.fixed_result = lp->last_result;
+            }
+        }
+        const unsigned nm = (unsigned)members.size();
+        SSW_HIP_TRY(hipMemcpyAsync(host->tab_dev, host->tab_host, nm * sizeof(LpSlot), hipMemcpyHostToDevice, s));
+        const LpSlot *tab = host->tab_dev;
+        const int64_t nb = (n + 255) / 256;
+        int64_t launches = 0;
+        if (n_inc > 0) {
+            // the frontier lists of a round are short; the chunk shares the grid the single pass gives one handle
+            const unsigned g_expand = (unsigned)std::max(64, 1024 / n_inc), g_rows = (unsigned)std::max(128, 2048 / n_inc);
+            const unsigned g_bmax = (unsigned)std::min<int64_t>(nb, std::max(128, 2048 / n_inc));
+            hipLaunchKernelGGL(k_inc_seed_b, dim3((unsigned)((seed_items + 255) / 256), (unsigned)n_inc), dim3(256), 0, s, tab);
+            for (int q = 1; q <= max_levels; ++q) {
+                hipLaunchKernelGGL(k_inc_expand_b, dim3(g_expand, (unsigned)n_inc), dim3(256), 0, s, q, tab);
+                hipLaunchKernelGGL(k_inc_rows_b, dim3(g_rows, (unsigned)n_inc), dim3(256), 0, s, q, tab);
+                hipLaunchKernelGGL(k_lp_blockmax_b, dim3(g_bmax, (unsigned)n_inc), dim3(256), 0, s, q, tab);
+            }
+            hipLaunchKernelGGL(k_lp_levelmax_b, dim3((unsigned)max_levels, (unsigned)n_inc), dim3(1024), 0, s, tab);
+            launches += 2 + 3 * (int64_t)max_levels;
+        }
+        hipLaunchKernelGGL(k_lp_scores_sel_b, dim3((unsigned)((nb + LP_SCORES_B_PER_THREAD - 1) / LP_SCORES_B_PER_THREAD), nm),
+                           dim3(256), 0, s, tab);
+        launches += 1;
+        SSW_HIP_TRY(hipGetLastError());
+        stats[0] += n_inc, stats[1] += launches;
+        // ---- the selections, back to back: each over its slot's slab, into its slot's pinned block
+        for (Member &mb : members) {
+            int64_t n_ex = 0;
+            const int64_t *ex = excl_of(mb.j, &n_ex);
+            if (ssw_status rc = index_enqueue_topk_slot(index, s, mb.j - c0, slabs[mb.j - c0], ex, n_ex, k, &mb.seq); rc != SSW_OK)
+                fail(mb.j, rc);
+        }
+        // ---- ONE wait for the chunk: on the word of the selection enqueued last (everything before it on the stream is
+        // complete by then, the control blocks in pinned memory included)
+        const int64_t ns_enqueued = lp_ns_since(t_entry);
+        const auto t_wait0 = std::chrono::steady_clock::now();
+        {
+            int64_t last_seq_member = -1;
+            for (size_t m = 0; m < members.size(); ++m)
+                if (members[m].seq != 0) last_seq_member = (int64_t)m;
+            if (last_seq_member >= 0) {
+                Member &mb = members[(size_t)last_seq_member];
+                SSW_TRY(index_wait_topk_slot(index, s, mb.j - c0, mb.seq));
+            } else {
+                SSW_HIP_TRY(hipStreamSynchronize(s));  // (an index without images, or every selection refused)
+            }
+            stats[2] += 1;
+        }
+        const int64_t ns_waited = lp_ns_since(t_wait0);
+        // ---- results: the members whose answer is in their slab first -- a deep rerun reads the slab, and a continuation
+        // below takes the handle's own score buffer, the last slab of the chunk
+        std::vector<Member *> later;
+        for (Member &mb : members) {
+            ssw_lp *lp = lps[mb.j];
+            if (out_status[mb.j] != SSW_OK) continue;
+            if (mb.kind == INC) {
+                LpInc rctl;
+                memcpy(&rctl, lp->round_host, sizeof(LpInc));
+                if (rctl.m[8] < 0) {  // (the word the kernel always writes did not arrive: should not happen -- wait the plain way)
+                    SSW_HIP_TRY(hipStreamSynchronize(s));
+                    stats[2] += 1;
+                    memcpy(&rctl, lp->round_host, sizeof(LpInc));
+                    if (rctl.m[8] < 0) {
+                        set_error("labelprop round batch: the scores kernel did not publish slot %d's control block", mb.j);
+                        fail(mb.j, SSW_ERR_HIP);
+                        continue;
+                    }
+                }
+                bool finished = false;
+                const ssw_status rc = lp_inc_outcome(lp, rctl, mb.sg, eps[mb.j], launches, &mb.st, &finished, &mb.continue_from);
+                lp->info[6] = ns_enqueued, lp->info[7] = ns_waited;
+                if (rc != SSW_OK) {
+                    fail(mb.j, rc);
+                    continue;
+                }
+                if (!finished) {  // (its selection ran on a slab the scores kernel did not write: the result is void)
+                    later.push_back(&mb);
+                    continue;
+                }
+            }
+            int64_t n_ex = 0, *im, *br;
+            float *sc;
+            const int64_t *ex = excl_of(mb.j, &n_ex);
+            outs(mb.j, &im, &sc, &br);
+            bool reran = false;
+            if (ssw_status rc = index_collect_topk_slot(index, s, mb.j - c0, mb.seq, slabs[mb.j - c0], ex, n_ex, k, im, sc, br,
+                                                        out_counts + mb.j, &reran);
+                rc != SSW_OK) {
+                fail(mb.j, rc);
+                continue;
+            }
+            if (reran) stats[2] += 1;
+            if (out_sweeps) out_sweeps[mb.j] = mb.st.sweeps;
+            if (out_converged) out_converged[mb.j] = mb.st.done;
+        }
+        // ---- incremental members whose pass overflowed its frontier or did not converge within the kept levels: the
+        // continuation of the single path, then their own scores and selection
+        for (Member *mbp : later) {
+            Member &mb = *mbp;
+            ssw_lp *lp = lps[mb.j];
+            int64_t n_ex = 0, *im, *br;
+            float *sc;
+            const int64_t *ex = excl_of(mb.j, &n_ex);
+            outs(mb.j, &im, &sc, &br);
+            stats[3] += 1;
+            ssw_status rc = lp_full_sweeps(lp, mb.plan, reg_lambda[mb.j], eps[mb.j], max_iter[mb.j], mb.continue_from, &mb.st);
+            if (rc == SSW_OK) {
+                // (info[3] of a continued run counts the pass's wait, which was the chunk's here, beside its own; the
+                // selection below waits once more)
+                stats[2] += mb.continue_from > 0 ? lp->info[3] : lp->info[3] + 1;
+                rc = lp_scores_and_select(lp, index, scores, mask_labeled, ex, n_ex, k, im, sc, br, out_counts + mb.j);
+            }
+            if (rc != SSW_OK) {
+                fail(mb.j, rc);
+                continue;
+            }
+            if (out_sweeps) out_sweeps[mb.j] = mb.st.sweeps;
+            if (out_converged) out_converged[mb.j] = mb.st.done;
+        }
+    }
+    if (out_stats4) memcpy(out_stats4, stats, sizeof(stats));
+    return SSW_OK;
+}
+
+const char *ssw_labelprop_batch_error(const ssw_lp *lp) { return lp ? lp->batch_error.c_str() : ""; }
 
 ssw_status ssw_xlx(ssw_index *index, ssw_lp *lap, double *out_host) {
     SSW_REQUIRE(index != nullptr && lap != nullptr && out_host != nullptr, "NULL argument");

@@ -128,6 +128,18 @@ ssw_status index_enqueue_topk_resident(ssw_index *idx, hipStream_t on_stream, co
                                        int32_t k);
 ssw_status index_collect_topk(ssw_index *idx, hipStream_t on_stream, int32_t k, int64_t *out_images, float *out_scores,
                               int64_t *out_best_rows, int32_t *out_count);
+// ... and once per slot of a chunk (ssw_labelprop_round_batch).  index_round_slabs: the score slabs of a chunk of up to
+// w (<= 16) slots -- *out_w is the width the side buffer could be grown to, slabs[j] slot j's slab; the last one is the
+// handle's own score buffer.  index_enqueue_topk_slot: install_excluded + the ordinary selection over `slab`, which
+// publishes into the slot's own pinned block under *out_seq.  index_collect_topk_slot: the wait on that word, the deep
+// rerun from the slab when the fast selection overflowed (*reran), the decode.
+ssw_status index_round_slabs(ssw_index *idx, int w, int *out_w, float **slabs);
+ssw_status index_enqueue_topk_slot(ssw_index *idx, hipStream_t on_stream, int slot, const float *slab,
+                                   const int64_t *excluded_images, int64_t n_excluded, int32_t k, unsigned *out_seq);
+ssw_status index_wait_topk_slot(ssw_index *idx, hipStream_t on_stream, int slot, unsigned seq);  // the wait alone
+ssw_status index_collect_topk_slot(ssw_index *idx, hipStream_t on_stream, int slot, unsigned seq, const float *slab,
+                                   const int64_t *excluded_images, int64_t n_excluded, int32_t k, int64_t *out_images,
+                                   float *out_scores, int64_t *out_best_rows, int32_t *out_count, bool *reran);
 int index_device(const ssw_index *idx);
 // element type of the resident matrix (SSW_DTYPE_*), its device pointer and shape, for the entries that read it through
 // a handle without index_handle.h (feedback gathers; k-NN and X'LX refuse an f16 matrix)

@@ -341,6 +341,24 @@ class MultiscaleIndex(AccessMethod):
         keep = np.isfinite(scores)
         return _Candidates(self._dbidx[pos[keep]], scores[keep], pos[keep], best_rows[keep])
 
+    def topk_after_update_batch(self, models, idxs, labels, *, topk_dbidx, exclude_dbidxs):
+        """`[topk_after_update(m, i, l, topk_dbidx=topk_dbidx, exclude_dbidx=e) for m, i, l, e in zip(...)]` for several
+        graph models over THIS index in one device call (LabelPropagationRanker2.update_and_select_batch): one
+        `_Candidates` a slot, or the exception that slot's own call would have raised"""
+        excl = [self._excluded_positions(e) for e in exclude_dbidxs]
+        self._resident_q = None
+        outs = type(models[0]).update_and_select_batch(models, idxs, labels, self._dev, excluded=excl,
+                                                       k=max(1, min(int(topk_dbidx), self._dbidx.shape[0])))
+        cands = []
+        for r in outs:
+            if isinstance(r, Exception):
+                cands.append(r)
+                continue
+            pos, scores, best_rows = r
+            keep = np.isfinite(scores)
+            cands.append(_Candidates(self._dbidx[pos[keep]], scores[keep], pos[keep], best_rows[keep]))
+        return cands
+
     def _activations_from_best(self, candidate_df: pd.DataFrame, topk: int):
         rows = np.asarray(candidate_df.attrs["best_rows"][:topk], dtype=np.int64)
         scores = np.asarray(candidate_df.max_score)[:topk]

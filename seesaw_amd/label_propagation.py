@@ -168,6 +168,71 @@ class LabelPropagation:
         c = cnt.value
         return imgs[:c].copy(), scs[:c].copy(), rows[:c].copy()
 
+    @staticmethod
+    def pack_round_batch(label_ids, label_values, excluded):
+        """the packed arrays of ssw_labelprop_round_batch from per-slot lists: (ids int64, vals float64, label offsets
+        int64 [S + 1], excluded int64, excluded offsets int64 [S + 1]); slot j owns [offsets[j], offsets[j + 1]) of each.
+        An excluded entry may be None (nobody excluded)."""
+        S = len(label_ids)
+        assert len(label_values) == S and len(excluded) == S
+        ids = [np.ascontiguousarray(a, dtype=np.int64).reshape(-1) for a in label_ids]
+        vals = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in label_values]
+        for a, b in zip(ids, vals):
+            assert a.shape == b.shape
+        exs = [np.zeros(0, dtype=np.int64) if e is None else np.ascontiguousarray(e, dtype=np.int64).reshape(-1) for e in excluded]
+        off = np.zeros(S + 1, dtype=np.int64)
+        np.cumsum([a.shape[0] for a in ids], out=off[1:])
+        ex_off = np.zeros(S + 1, dtype=np.int64)
+        np.cumsum([e.shape[0] for e in exs], out=ex_off[1:])
+        cat = lambda parts, dt: np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(0, dtype=dt)  # noqa: E731
+        return cat(ids, np.int64), cat(vals, np.float64), off, cat(exs, np.int64), ex_off
+
+    last_batch_stats = None  # round_batch: (batched slots, launches of the batched pass, host waits, slots on the single path)
+
+    @staticmethod
+    def round_batch(lps, device_index, *, propagate, label_ids, label_values, mask_labeled: bool, excluded, k: int):
+        """`[lp.round(device_index, propagate=p, label_ids=i, label_values=v, mask_labeled=..., excluded=e, k=k) for ...]`
+        in ONE C-ABI call (ssw_labelprop_round_batch): per-slot lists in, per slot the triple `round` returns -- or, in
+        its place, the SeesawHipError that slot's `round` would have raised -- out.  The slots whose propagation is an
+        incremental update share one pass of kernels and one host wait a chunk of 16; every handle is left as its own
+        `round` leaves it (`last_sweeps`, `last_converged`, and with `collect_run_info` the run info).  The stats of the
+        call are kept in `LabelPropagation.last_batch_stats` and on every handle as `last_batch_stats`."""
+        lps = list(lps)
+        S = len(lps)
+        assert S >= 1 and len(propagate) == S
+        ids, vals, off, ex, ex_off = LabelPropagation.pack_round_batch(label_ids, label_values, excluded)
+        k = int(k)
+        handles = (ctypes.c_void_p * S)(*[lp._h for lp in lps])
+        prop = np.ascontiguousarray([int(bool(p)) for p in propagate], dtype=np.int32)
+        lam = np.ascontiguousarray([lp.reg_lambda for lp in lps], dtype=np.float64)
+        eps = np.ascontiguousarray([float(lp.epsilon) for lp in lps], dtype=np.float64)
+        mit = np.ascontiguousarray([lp.max_iter for lp in lps], dtype=np.int32)
+        imgs, scs, rows = np.empty((S, k), dtype=np.int64), np.empty((S, k), dtype=np.float32), np.empty((S, k), dtype=np.int64)
+        cnt, sweeps, conv, status = (np.zeros(S, dtype=np.int32) for _ in range(4))
+        stats = np.zeros(4, dtype=np.int64)
+        _lib.call("ssw_labelprop_round_batch", handles, S, device_index._h, _p(prop), _p(ids), _p(vals), _p(off), _p(lam), _p(eps),
+                  _p(mit), int(bool(mask_labeled)), _p(ex), _p(ex_off), k, _p(imgs), _p(scs), _p(rows), _p(cnt), _p(sweeps),
+                  _p(conv), _p(status), _p(stats))
+        LabelPropagation.last_batch_stats = tuple(int(x) for x in stats)
+        out = []
+        for j, lp in enumerate(lps):
+            lp.last_batch_stats = LabelPropagation.last_batch_stats
+            if status[j] != _lib.SSW_OK:
+                msg = _lib.load().ssw_labelprop_batch_error(lp._h)
+                out.append(_lib.SeesawHipError(int(status[j]), msg.decode("utf-8", "replace") if msg else ""))
+                continue
+            if propagate[j]:
+                lp.last_sweeps, lp.last_converged = int(sweeps[j]), bool(conv[j])
+                if not lp.last_converged:
+                    print(f"warning: did not converge after {lp.last_sweeps} iterations")
+                elif lp.verbose > 0:
+                    print(f"prop. converged after {lp.last_sweeps} iterations")
+            if lp.collect_run_info:
+                lp._read_run_info()
+            c = int(cnt[j])
+            out.append((imgs[j, :c].copy(), scs[j, :c].copy(), rows[j, :c].copy()))
+        return out
+
     def _read_run_info(self):
         """what the propagation just did on the device (ssw_labelprop_last_run_info): consecutive fit_resident calls
         are incremental -- only rows within k hops of a changed label are recomputed for sweep k, bit-identical results"""
@@ -176,6 +241,7 @@ class LabelPropagation:
         self.last_mode = int(info[0])              # 0 full sweeps, 1 incremental update, 2 incremental pass continued by full sweeps
         self.last_incremental = self.last_mode == 1
         self.last_launches, self.last_host_syncs, self.last_rows_recomputed = int(info[2]), int(info[3]), int(info[4])
+        self.last_kept_levels = int(info[5])       # iterates kept for the next call's incremental pass
         self.last_frontier_us, self.last_device_wait_us = info[6] / 1e3, info[7] / 1e3
 
     def prior_as_result(self, label_ids):

@@ -180,3 +180,34 @@ class KnnProp2(LoopBase):
             self._pending = (cand, len(q.returned), p.shortlist_size, getattr(model, "_labels_stamp", 0))
         else:
             model.update(idxs, labels)
+
+    @classmethod
+    def refine_batch(cls, loops):
+        """`for l in loops: l.refine()` for loops over ONE index whose refine takes the fused round (SessionGroup.
+        propagation_groups): every loop's labels are read as its own refine reads them, ONE
+        `index.topk_after_update_batch` follows -- the incremental propagations share one pass of kernels and one host
+        wait -- and every `_pending` is set as the loop's own refine sets it, so the next `next_batch()` takes the
+        shortlist without a device selection.  A loop whose round raised surfaces its error after the other loops
+        have got their shortlists."""
+        loops = list(loops)
+        if not loops:
+            return
+        index, size = loops[0].q.index, loops[0].params.shortlist_size
+        models, all_idxs, all_labels, excludes = [], [], [], []
+        for l in loops:
+            assert l.q.index is index and l.params.shortlist_size == size
+            pos, neg = l.q.getXy(get_positions=True)
+            all_idxs.append(np.concatenate([pos, neg]))
+            all_labels.append(np.concatenate([np.ones_like(pos), np.zeros_like(neg)]))
+            models.append(l.state.knn_model)
+            excludes.append(l.q.returned)
+            l._pending = None
+        cands = index.topk_after_update_batch(models, all_idxs, all_labels, topk_dbidx=size, exclude_dbidxs=excludes)
+        failed = None
+        for l, m, c in zip(loops, models, cands):
+            if isinstance(c, Exception):
+                failed = failed or c
+                continue
+            l._pending = (c, len(l.q.returned), size, getattr(m, "_labels_stamp", 0))
+        if failed is not None:
+            raise failed

@@ -176,6 +176,35 @@ class LabelPropagationRanker2(BaseLabelPropagationRanker):
         self._current_scores = None
         return out
 
+    @staticmethod
+    def update_and_select_batch(models, idxs, labels, device_index, *, excluded, k):
+        """`[m.update_and_select(i, l, device_index, excluded=e, k=k) for m, i, l, e in zip(...)]` with the host
+        bookkeeping of each model run in turn and ONE device call for all of them (LabelPropagation.round_batch).
+        One entry a model: its (image positions, scores, best rows), or the SeesawHipError its own call would have
+        raised."""
+        models = list(models)
+        ids_all, vals_all, prop = [], [], []
+        for m, i, l in zip(models, idxs, labels):
+            m.update_labels(i, l)
+            m._refresh_has_negative()
+            ids = m._sorted_label_ids()
+            if m._has_negative:
+                print(" propagating")
+                vals = m.labels.reshape(-1)[ids]
+            else:
+                print(" no negatives yet, skipping propagation")
+                vals = np.zeros(ids.shape[0])
+            ids_all.append(ids)
+            vals_all.append(vals)
+            prop.append(m._has_negative)
+        outs = LabelPropagation.round_batch([m.lp for m in models], device_index, propagate=prop, label_ids=ids_all,
+                                            label_values=vals_all, mask_labeled=True, excluded=list(excluded), k=k)
+        for m, r in zip(models, outs):
+            if not isinstance(r, Exception):
+                m._resident = True
+                m._current_scores = None
+        return outs
+
     def _no_negatives_yet(self):
         # the reference serves the prior until a negative label exists; here the prior is in the graph handle already
         # (set_prior): it becomes the resident result with the labelled nodes marked, so these rounds select and

@@ -5,6 +5,7 @@ Interface of seesaw/seesaw_session.py:12-245 (`set_text`, `next`, `update_state`
 """
 from __future__ import annotations
 
+import os
 import time
 
 import numpy as np
@@ -259,7 +260,9 @@ class SessionGroup:
       of them); every other session calls its own `next()`.
     * `refine()`: every session's start-policy gate runs as in `LoopBase.refine_external`; the started `MultiReg`
       loops go through ONE `MultiReg.refine_batch` -- one launch, one host wait -- and the started `MultiRegNeg` loops
-      whose options say `fit_on_device` through ONE `MultiRegNeg.refine_batch`, a launch of their own; every other
+      whose options say `fit_on_device` through ONE `MultiRegNeg.refine_batch`, a launch of their own; the started
+      `KnnProp2` loops of one index and shortlist size (`propagation_groups`, from `MIN_PROPAGATION_GROUP` members on)
+      through ONE `KnnProp2.refine_batch` -- their propagations, scores and selections in one device call; every other
       loop, a `MultiRegNeg` that did not opt in included, through its own `refine_external`.  The batches refine
       first, the remaining sessions after them in session order: loops that draw from torch's global generator (every
       `MultiRegNeg` refine draws its start weights) keep the draws of the one-by-one order when the opted-in loops
@@ -344,6 +347,40 @@ class SessionGroup:
                 alone.append(i)
         return [tuple(g) for g in batched.values()], alone
 
+    # A group of graph loops goes through KnnProp2.refine_batch from this many members on.  Read from
+    # profiles/round_batch_ab.txt (tools/perf_round_batch.py, 1.56 M nodes): per session-round the batched round takes
+    # 87.4 [5.2] us against the loop's 105.9 [3.5] at 3 sessions -- ahead by more than both spreads -- and 105.9 [6.5]
+    # against 108.7 [5.0] at 2, which is not.
+    MIN_PROPAGATION_GROUP = 3
+
+    def propagation_groups(self):
+        """[(session positions, ...)]: the started `KnnProp2` loops that refine through one `KnnProp2.refine_batch`,
+        grouped by (index object, shortlist_size), in session order.  A member's `refine` and `refine_external` are the
+        class's own, its model `can_fuse_round()`, its index holds its rows on the device (`_dev`) and is not a subset
+        view (no batched entry takes one); SSW_NO_FUSED_ROUND empties the list.  A `PseudoLR`'s inner graph loop is not
+        a session's loop and stays on its own path.  Groups of one are listed too; `refine()` leaves them alone."""
+        from .loops.graph_based import KnnProp2
+        from .loops.loop_base import LoopBase
+        if os.environ.get("SSW_NO_FUSED_ROUND"):
+            return []
+        by_key = {}
+        for i, s in enumerate(self.sessions):
+            loop = s.loop
+            cls = type(loop)
+            if not (isinstance(loop, KnnProp2) and loop.started and cls.refine is KnnProp2.refine and
+                    cls.refine_external is LoopBase.refine_external):
+                continue
+            index = loop.q.index
+            dev = getattr(index, "_dev", None)
+            if dev is None or getattr(dev, "is_view", False) or getattr(index, "is_view", False) or \
+                    not callable(getattr(index, "topk_after_update_batch", None)):
+                continue
+            model = getattr(getattr(loop, "state", None), "knn_model", None)
+            if not getattr(model, "can_fuse_round", lambda: False)():
+                continue
+            by_key.setdefault((id(index), loop.params.shortlist_size), []).append(i)
+        return [tuple(g) for g in by_key.values()]
+
     # ---- the two halves of a round ----------------------------------------------------------------------------
     def next(self):
         """`[s.next() for s in sessions]`"""
@@ -382,13 +419,18 @@ class SessionGroup:
 
     def refine(self):
         """`for s in sessions: s.refine()`"""
+        from .loops.graph_based import KnnProp2
         from .loops.multi_reg import MultiReg
         from .loops.multi_reg_neg import MultiRegNeg
         for s in self.sessions:  # the gate of LoopBase.refine_external
-            if not s.loop.started and (isinstance(s.loop, MultiReg) or
+            if not s.loop.started and (isinstance(s.loop, (MultiReg, KnnProp2)) or
                                        (isinstance(s.loop, MultiRegNeg) and getattr(s.loop, "fit_on_device", False))):
                 s.loop.started = s.loop._start_condition()
         batched, alone = self.fit_groups()
+        for group in self.propagation_groups():  # graph loops of one index: one batched round, from the minimum size on
+            if len(group) >= max(2, self.MIN_PROPAGATION_GROUP):
+                batched.append(group)
+                alone = [i for i in alone if i not in group]
         for group in batched:
             members = [self.sessions[i] for i in group]
             if len(members) == 1:
