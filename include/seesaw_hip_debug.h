@@ -276,6 +276,26 @@ ssw_status ssw_debug_attn_out_run(int32_t B, int32_t S, const uint16_t *qkv_bf16
  * attention, after the product, after the stores, end; 8 + 2p / 9 + 2p = head pair p staged / computed */
 ssw_status ssw_debug_attn_out_stamps(uint64_t *out, int32_t n_words);
 
+/* ONE launch of one of the towers' attention kernels (csrc/clip.hip) on the caller's operands, with the launch shape
+ * run_tower gives it (tests/test_attention_gpu.py holds each to an f64 softmax).  form: 0 attention_mfma<4>,
+ * 1 attention_mfma<4, 2>, 2 attention_mfma<5>, 3 attention_rows64, 4 launch_attention_long (its own choice of
+ * instance), 5 attn_pooled_rows (out is [B, D]: row 0 of every sequence; non-causal only).  qkv [qkv_rows_alloc, 3 D]
+ * bf16 (q | k | v; rows_alloc >= B S), out [out_rows_alloc, D] bf16: both buffers travel whole, up and -- after the one
+ * launch on the default stream -- down, so the rows past B S (past B for form 5) are guards the caller fills and reads
+ * back.  SSW_ERR_UNSUPPORTED, with nothing launched and out untouched: S < 1, S > 64 (forms 0, 1, 3, 5), S > 80
+ * (form 2), S > 272 (form 4), D != 64 H, causal with form 5. */
+ssw_status ssw_debug_attention_run(int32_t form, int32_t B, int32_t S, int32_t D, int32_t H, int32_t causal, float scale,
+                                   const uint16_t *qkv_bf16, int64_t qkv_rows_alloc, uint16_t *out_bf16_inout,
+                                   int64_t out_rows_alloc);
+/* The text tower's fused attention + out-projection of a short query (skinny_attn_out<1> for B L <= 16 rows, <2> for
+ * 17 .. 32; more is SSW_ERR_UNSUPPORTED): qkv [B L, 1536] bf16, Wo [512, 512] bf16 as nn.Linear holds it, bias [512],
+ * residual [B L, 512] f32, out [B L, 512] f32 is uploaded, written by the one launch and returned.  On the device 32
+ * rows of 0xFF bytes follow the qkv, residual and out rows: a read past the rows shows as NaN in the output, a write
+ * past them is SSW_ERR_NUMERIC. */
+ssw_status ssw_debug_skinny_attn_out_run(int32_t B, int32_t L, int32_t causal, float scale, const uint16_t *qkv_bf16,
+                                         const uint16_t *Wo_bf16, const float *bias, const float *residual,
+                                         float *out_f32_inout);
+
 /* Keep the residual rows behind transformer layer `layer` of tower `tower` (0 image, 1 text; layer -1 = off) of the
  * handle's next forward passes, as f32 [rows][hidden]; ssw_clip_debug_tap_read waits for the stream and returns them
  * (tests/test_clip_gpu.py compares every layer with transformers' output_hidden_states). */

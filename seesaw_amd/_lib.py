@@ -237,6 +237,10 @@ _DEBUG_SIGNATURES = {
     "ssw_debug_attn_out_run": (c_i32, [c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        ctypes.c_float]),
     "ssw_debug_attn_out_stamps": (c_i32, [c_void_p, c_i32]),
+    "ssw_debug_attention_run": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_float, c_void_p, c_i64, c_void_p,
+                                        c_i64]),
+    "ssw_debug_skinny_attn_out_run": (c_i32, [c_i32, c_i32, c_i32, ctypes.c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p]),
     "ssw_clip_debug_tap": (c_i32, [c_void_p, c_i32, c_i32]),
     "ssw_clip_debug_tap_read": (c_i32, [c_void_p, c_void_p, c_i64, c_i64_p, c_i32_p]),
     "ssw_debug_resize_u8": (c_i32, [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_i32, c_void_p]),

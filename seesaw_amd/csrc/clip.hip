@@ -2039,6 +2039,112 @@ ssw_status ssw_clip_debug_tap_read(ssw_clip *c, float *out_host, int64_t cap_flo
     }
     return SSW_OK;
 }
+
+// ---- one attention kernel on the caller's operands (tests/test_attention_gpu.py) -------------------------------------
+// The launch shapes are run_tower's; nothing here is reachable from the product.
+namespace {
+struct DebugBufs {
+    std::vector<void *> ptrs;
+    ~DebugBufs() {
+        for (void *p : ptrs) (void)hipFree(p);
+    }
+    // host == NULL: every byte 0xFF (bf16 and f32 NaN patterns)
+    ssw_status up(const void *host, size_t bytes, void **dev) {
+        *dev = nullptr;
+        SSW_HIP_TRY(hipMalloc(dev, bytes ? bytes : 16));
+        ptrs.push_back(*dev);
+        if (host) SSW_HIP_TRY(hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice));
+        else SSW_HIP_TRY(hipMemset(*dev, 0xFF, bytes ? bytes : 16));
+        return SSW_OK;
+    }
+};
+#define SSW_UNSUPPORTED_IF(cond, ...)     \
+    do {                                  \
+        if (cond) {                       \
+            ssw::set_error(__VA_ARGS__);  \
+            return SSW_ERR_UNSUPPORTED;   \
+        }                                 \
+    } while (0)
+}  // namespace
+
+ssw_status ssw_debug_attention_run(int32_t form, int32_t B, int32_t S, int32_t D, int32_t H, int32_t causal, float scale,
+                                   const uint16_t *qkv_bf16, int64_t qkv_rows_alloc, uint16_t *out_bf16_inout,
+                                   int64_t out_rows_alloc) {
+    SSW_REQUIRE(form >= 0 && form <= 5, "ssw_debug_attention_run: form %d unknown (0 .. 5)", form);
+    SSW_REQUIRE(qkv_bf16 && out_bf16_inout && B >= 1 && B <= 4096 && H >= 1 && D >= 1, "ssw_debug_attention_run: bad arguments");
+    static const int max_s[6] = {64, 64, ATT_MAX_S, 64, ATT_LONG_MAX_S, 64};
+    SSW_UNSUPPORTED_IF(S < 1, "ssw_debug_attention_run: S=%d < 1", S);
+    SSW_UNSUPPORTED_IF(S > max_s[form], "ssw_debug_attention_run: form %d holds S <= %d, got %d", form, max_s[form], S);
+    SSW_UNSUPPORTED_IF(D != 64 * H || H > 64, "ssw_debug_attention_run: D=%d is not 64 x H=%d (head_dim 64)", D, H);
+    SSW_UNSUPPORTED_IF(causal && form == 5, "ssw_debug_attention_run: attn_pooled_rows has no causal form");
+    const int64_t R = (int64_t)B * S, out_rows = form == 5 ? B : R;
+    SSW_REQUIRE(qkv_rows_alloc >= R && out_rows_alloc >= out_rows && qkv_rows_alloc <= (1 << 20) && out_rows_alloc <= (1 << 20),
+                "ssw_debug_attention_run: %lld qkv rows / %lld out rows allocated, the call needs %lld / %lld",
+                (long long)qkv_rows_alloc, (long long)out_rows_alloc, (long long)R, (long long)out_rows);
+    DebugBufs d;
+    void *qkv_v, *out_v;
+    const size_t out_bytes = (size_t)out_rows_alloc * D * 2;
+    SSW_TRY(d.up(qkv_bf16, (size_t)qkv_rows_alloc * 3 * D * 2, &qkv_v));
+    SSW_TRY(d.up(out_bf16_inout, out_bytes, &out_v));
+    const bf16 *qkv = (const bf16 *)qkv_v;
+    bf16 *out = (bf16 *)out_v;
+    const int n_heads = B * H, cz = causal ? 1 : 0;
+    hipStream_t s = nullptr;
+    switch (form) {
+    case 0: hipLaunchKernelGGL(attention_mfma<4>, dim3(n_heads), dim3(256), 0, s, qkv, out, S, D, H, scale, cz); break;
+    case 1: hipLaunchKernelGGL((attention_mfma<4, 2>), dim3(n_heads), dim3(128), 0, s, qkv, out, S, D, H, scale, cz); break;
+    case 2: hipLaunchKernelGGL(attention_mfma<5>, dim3(n_heads), dim3(320), 0, s, qkv, out, S, D, H, scale, cz); break;
+    case 3: hipLaunchKernelGGL(attention_rows64, dim3(n_heads), dim3(128), 0, s, qkv, out, S, D, H, scale, cz); break;
+    case 4: launch_attention_long(s, qkv, out, n_heads, S, D, H, scale, cz); break;
+    default: hipLaunchKernelGGL(attn_pooled_rows, dim3(n_heads), dim3(64), 0, s, qkv, out, S, D, H, scale); break;
+    }
+    SSW_HIP_TRY(hipGetLastError());
+    SSW_HIP_TRY(hipDeviceSynchronize());
+    SSW_HIP_TRY(hipMemcpy(out_bf16_inout, out, out_bytes, hipMemcpyDeviceToHost));
+    return SSW_OK;
+}
+
+ssw_status ssw_debug_skinny_attn_out_run(int32_t B, int32_t L, int32_t causal, float scale, const uint16_t *qkv_bf16,
+                                         const uint16_t *Wo_bf16, const float *bias, const float *residual,
+                                         float *out_f32_inout) {
+    constexpr int D = 512, GUARD = 32;
+    SSW_REQUIRE(qkv_bf16 && Wo_bf16 && bias && residual && out_f32_inout, "ssw_debug_skinny_attn_out_run: NULL argument");
+    SSW_UNSUPPORTED_IF(B < 1 || L < 1 || (int64_t)B * L > SK_MAX_ROWS,
+                       "ssw_debug_skinny_attn_out_run: B=%d x L=%d rows, the kernel holds 1 .. %d", B, L, SK_MAX_ROWS);
+    const int R = B * L;
+    const size_t qkv_bytes = (size_t)R * 3 * D * 2, out_bytes = (size_t)R * D * 4, guard_bytes = (size_t)GUARD * D * 4;
+    DebugBufs d;
+    void *qkv, *wo, *b, *res, *out;
+    // GUARD rows of 0xFF behind the qkv, residual and out rows: an over-read is a NaN in the output, an over-write is
+    // found below
+    SSW_TRY(d.up(nullptr, qkv_bytes + (size_t)GUARD * 3 * D * 2, &qkv));
+    SSW_HIP_TRY(hipMemcpy(qkv, qkv_bf16, qkv_bytes, hipMemcpyHostToDevice));
+    SSW_TRY(d.up(Wo_bf16, (size_t)D * D * 2, &wo));
+    SSW_TRY(d.up(bias, (size_t)D * 4, &b));
+    SSW_TRY(d.up(nullptr, out_bytes + guard_bytes, &res));
+    SSW_HIP_TRY(hipMemcpy(res, residual, out_bytes, hipMemcpyHostToDevice));
+    SSW_TRY(d.up(nullptr, out_bytes + guard_bytes, &out));
+    SSW_HIP_TRY(hipMemcpy(out, out_f32_inout, out_bytes, hipMemcpyHostToDevice));
+    hipStream_t s = nullptr;
+    if (R <= 16)
+        hipLaunchKernelGGL(skinny_attn_out<1>, dim3(D / 16), dim3(256), 0, s, (const bf16 *)qkv, (const bf16 *)wo, (const float *)b,
+                           (const float *)res, (float *)out, R, L, scale, causal ? 1 : 0);
+    else
+        hipLaunchKernelGGL(skinny_attn_out<2>, dim3(D / 16), dim3(256), 0, s, (const bf16 *)qkv, (const bf16 *)wo, (const float *)b,
+                           (const float *)res, (float *)out, R, L, scale, causal ? 1 : 0);
+    SSW_HIP_TRY(hipGetLastError());
+    SSW_HIP_TRY(hipDeviceSynchronize());
+    SSW_HIP_TRY(hipMemcpy(out_f32_inout, out, out_bytes, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> guard((size_t)GUARD * D);
+    SSW_HIP_TRY(hipMemcpy(guard.data(), (const char *)out + out_bytes, guard_bytes, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < guard.size(); ++i)
+        if (guard[i] != 0xFFFFFFFFu) {
+            ssw::set_error("ssw_debug_skinny_attn_out_run: the kernel wrote row %d of %d (column %d)", R + (int)(i / D), R, (int)(i % D));
+            return SSW_ERR_NUMERIC;
+        }
+    return SSW_OK;
+}
+#undef SSW_UNSUPPORTED_IF
 #endif
 
 ssw_status ssw_clip_destroy(ssw_clip *c) {
