@@ -898,6 +898,46 @@ ssw_status ssw_lknn_destroy(ssw_lknn *h);
 ssw_status ssw_lknn_top_sum(ssw_lknn *h, const double *numer_host, const double *denom_host, const int32_t *top_ids_desc,
                             int32_t K, double *out_values_or_null, int64_t *out_best_idx, double *out_best_value);
 
+/* The device-resident model: LKNNModel's state (numerators, denominators, gamma: f64 [n]; which nodes are seen) kept on
+ * the handle, in buffers of its own -- ssw_lknn_top_sum keeps working on the same handle and does not touch them.
+ *
+ * Order.  Wherever nodes are ranked here the order is total: score descending, node id ascending, seen nodes left out,
+ * score = (numerators + gamma) / (denominators + 1) with one rounding per operation.  Whenever the K + D + 1 highest
+ * unseen scores are pairwise distinct, every result below equals LKNNModel's bit for bit.  Under exact ties the host
+ * model's order comes from np.argpartition and is unspecified; this one is the order just defined, whatever the launch
+ * shape.
+ *
+ * state_init: numerators = denominators = 0, no node seen, gamma installed (finite values; one 8 n-byte upload).
+ * set_gamma:  LKNNModel.with_gamma -- replaces gamma, keeps counts and seen marks (one 8 n-byte upload). */
+ssw_status ssw_lknn_state_init(ssw_lknn *h, const double *gamma_host);
+ssw_status ssw_lknn_set_gamma(ssw_lknn *h, const double *gamma_host);
+/* LKNNModel.condition_ for m <= 4096 answers, applied in order: every distinct neighbour j of ids[t] (the handle's table)
+ * gets numerators[j] += ys[t], denominators[j] += 1, then ids[t] is marked seen.  Checked on the host before anything
+ * is enqueued: ids in range, ys 0 or 1, no id seen already, none twice in the call -- otherwise SSW_ERR_INVALID and the
+ * state is as before.  Enqueue only: the host waits for nothing but an earlier call's staging copy still in flight. */
+ssw_status ssw_lknn_condition(ssw_lknn *h, const int64_t *ids, const int32_t *ys, int32_t m);
+/* One planning step, one host wait, nothing of size n copied to the device.
+ * lookahead 2: numer = numerators + gamma (-inf at seen nodes), denom = denominators + 1, the L = K + D best unseen
+ *   nodes selected in the same pass over the state, then ssw_lknn_top_sum's kernels on them: np.nanargmax(value) and
+ *   its value; out_values (optional) [n] all values, out_list (optional) [K + D] the selected nodes, best first.
+ *   1 <= K <= 128, K + D <= 192, K + D <= the number of unseen nodes: otherwise SSW_ERR_INVALID before any launch.
+ * lookahead 1 (K ignored): the first index of the largest score among the unseen nodes, and that score; out_values
+ *   (optional) the scores, -inf at seen nodes; out_list is not written. */
+ssw_status ssw_lknn_step(ssw_lknn *h, int32_t K, int32_t lookahead, int64_t *out_best_idx, double *out_best_value,
+                         double *out_values_or_null, int32_t *out_list_or_null);
+/* the k <= 192 best unseen nodes, best first, with their scores; *out_count = min(k, unseen nodes).  One host wait. */
+ssw_status ssw_lknn_top_remaining(ssw_lknn *h, int32_t k, int32_t *out_ids, double *out_scores, int32_t *out_count);
+/* predict_proba: the score of m <= 4096 nodes, seen or not */
+ssw_status ssw_lknn_predict(ssw_lknn *h, const int64_t *ids, int32_t m, double *out_scores);
+/* the state copied back ([n] each; any pointer may be NULL): tests and debugging */
+ssw_status ssw_lknn_state_fetch(ssw_lknn *h, double *numerators, double *denominators, double *gamma, uint8_t *seen_u8);
+/* of the last ssw_lknn_step or ssw_lknn_top_remaining: [0] kernel launches, [1] host waits, [2] bytes copied host ->
+ * device, [3] bytes copied device -> host */
+ssw_status ssw_lknn_step_info(ssw_lknn *h, int64_t *out4);
+/* out_ms2 (optional): device-event times in ms of the last step's [0] selection (state pass + merge levels) and [1]
+ * look-ahead kernel, -1 where that step was not timed; then steps from now on are timed (enable != 0) or not. */
+ssw_status ssw_lknn_step_times(ssw_lknn *h, int32_t enable, double *out_ms2_or_null);
+
 /* ------------------------------------------------------------------------- */
 /* CLIP ViT-B/32 image / text towers (bf16 MFMA forward)                       */
 /* replaces: transformers.CLIPModel.get_text_features                          */

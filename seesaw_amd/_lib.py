@@ -141,6 +141,15 @@ _SIGNATURES = {
     "ssw_lknn_create": (c_i32, [c_i32, c_i64, c_i32, c_void_p, c_void_pp]),
     "ssw_lknn_destroy": (c_i32, [c_void_p]),
     "ssw_lknn_top_sum": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p]),
+    "ssw_lknn_state_init": (c_i32, [c_void_p, c_void_p]),
+    "ssw_lknn_set_gamma": (c_i32, [c_void_p, c_void_p]),
+    "ssw_lknn_condition": (c_i32, [c_void_p, c_void_p, c_void_p, c_i32]),
+    "ssw_lknn_step": (c_i32, [c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ssw_lknn_top_remaining": (c_i32, [c_void_p, c_i32, c_void_p, c_void_p, c_void_p]),
+    "ssw_lknn_predict": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p]),
+    "ssw_lknn_state_fetch": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ssw_lknn_step_info": (c_i32, [c_void_p, c_void_p]),
+    "ssw_lknn_step_times": (c_i32, [c_void_p, c_i32, c_void_p]),
     "ssw_rank_pairwise": (c_i32, [c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_i32, ctypes.c_float, c_void_p, c_void_p]),
     "ssw_clip_create": (c_i32, [c_i32, c_void_p, ctypes.c_size_t, c_void_pp]),
     "ssw_clip_destroy": (c_i32, [c_void_p]),

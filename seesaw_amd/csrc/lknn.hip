@@ -19,6 +19,8 @@
 // formed in numpy's pairwise order for a contiguous row of K <= 128 doubles (8 running sums over the elements
 // 0..8 floor(K/8), combined ((0+1)+(2+3))+((4+5)+(6+7)), then the tail one by one; plain left-to-right below
 // 8 elements).  Divisions and the final combination are single IEEE operations, as numpy's elementwise ops.
+#include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "ssw_common.h"
@@ -201,6 +203,210 @@ __global__ __launch_bounds__(LK_THREADS) void k_lknn_argmax(const double *__rest
     }
 }
 
+// ---- the device-resident model (ssw_lknn_state_init .. ssw_lknn_step) ------------------------------------------------
+// The state of LKNNModel (numerators, denominators, gamma: f64 [n]; seen: u8 [n]) stays in HBM.  A planning step forms
+// numer = numerators + gamma (-inf at seen nodes), denom = denominators + 1 and score = numer / denom in ONE pass over it
+// (25 n bytes read, the 16 n bytes of numer / denom written for k_lknn_top_sum) and selects, in the same pass, the exact
+// L = K + D best unseen nodes under the total order (score descending, node id ascending).
+//
+// The selection is a hierarchy of comparisons on whole keys -- nothing is binned by value (the prior is 0.1 +- 1e-6: every
+// key shares its sign, exponent and leading mantissa bits, so a histogram of the high bits would put all nodes into one
+// bin).  A workgroup keeps its best 256 candidates sorted in the lower half of a 512-entry LDS array (LkTop); candidates
+// come 256 at a time, one a thread; those that beat the L-th best so far are appended to the upper half, and when the
+// next 256 might not fit a bitonic sort orders all 512 and empties the upper half (sort and truncate).  Candidates that
+// do not beat the L-th best cannot be in the result, so dropping them changes nothing; how many sorts a workgroup runs
+// depends on the order the scores arrive in, between one and -- scores rising along the slice -- one per 256 candidates.
+//   k_lknn_select: a workgroup reduces its slice of LK_SLICE rows to its own best L;
+//   k_lknn_merge:  a workgroup reduces up to LK_FAN such lists to one, the same way; levels repeat until one list is
+//                  left, which the last level writes as node ids (and scores) in order.
+// A key is unique (the id breaks every tie), so the result is the same for any slice length, fan-in or grid, and for
+// any order in which the LDS atomic hands out places in the upper half.
+constexpr int LK_SLICE = 2048;  // rows of one workgroup of k_lknn_select
+constexpr int LK_FAN = 32;      // lists one workgroup of k_lknn_merge reduces
+constexpr int LK_SORT = 2 * LK_THREADS;
+constexpr unsigned LK_EMPTY = 0xffffffffu;  // id of an empty entry (key 0): after every node
+static_assert(LK_MAX_LIST <= LK_THREADS, "a workgroup's list is the sorted lower half");
+
+// ascending unsigned order == ascending order of the doubles (-0 and +0 compare equal in numpy: one key)
+__device__ inline unsigned long long score_key(double s) {
+    if (s == 0.0) s = 0.0;
+    const unsigned long long u = (unsigned long long)__double_as_longlong(s);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
+__device__ inline bool lk_before(unsigned long long ka, unsigned ia, unsigned long long kb, unsigned ib) {
+    return ka > kb || (ka == kb && ia < ib);
+}
+
+// a workgroup's best candidates: k / id [0, 256) sorted best first (empty entries last), [256, 256 + fill) appended since
+struct LkTop {
+    unsigned long long k[LK_SORT];
+    unsigned id[LK_SORT];
+    int fill;
+};
+
+__device__ inline void lk_clear_upper(LkTop &s) {
+    s.k[LK_THREADS + threadIdx.x] = 0ull, s.id[LK_THREADS + threadIdx.x] = LK_EMPTY;
+    if (threadIdx.x == 0) s.fill = 0;
+    __syncthreads();
+}
+
+__device__ inline void lk_init(LkTop &s) {
+    s.k[threadIdx.x] = 0ull, s.id[threadIdx.x] = LK_EMPTY;
+    lk_clear_upper(s);
+}
+
+// the bitonic sort of all LK_SORT entries, best first, then the upper half emptied.  Whole workgroup.
+__device__ inline void lk_flush(LkTop &s) {
+    const int t = threadIdx.x;
+    __syncthreads();  // the appends
+    for (int size = 2; size <= LK_SORT; size <<= 1)
+        for (int stride = size >> 1; stride >= 1; stride >>= 1) {
+            const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
+            const unsigned long long ka = s.k[lo], kb = s.k[hi];
+            const unsigned ia = s.id[lo], ib = s.id[hi];
+            const bool in_order = (lo & size) == 0;  // this run is to come out best first, the next one reversed
+            if (in_order ? lk_before(kb, ib, ka, ia) : lk_before(ka, ia, kb, ib)) {
+                s.k[lo] = kb, s.id[lo] = ib;
+                s.k[hi] = ka, s.id[hi] = ia;
+            }
+            __syncthreads();
+        }
+    lk_clear_upper(s);
+}
+
+// every thread of the workgroup offers one candidate (id LK_EMPTY: none).  fill: the thread's copy of s.fill, the same
+// in all threads.  The L-th best so far (an empty entry while there are fewer) is read from the lower half, which only
+// lk_flush changes; the barrier inside the count separates that from this call's appends.
+__device__ inline void lk_offer(LkTop &s, int L, unsigned long long key, unsigned id, int &fill) {
+    const bool beats = id != LK_EMPTY && lk_before(key, id, s.k[L - 1], s.id[L - 1]);
+    const int count = __syncthreads_count(beats);
+    if (count == 0) return;
+    if (fill + count > LK_THREADS) {
+        lk_flush(s);
+        fill = 0;
+    }
+    if (beats) {
+        const int at = LK_THREADS + atomicAdd(&s.fill, 1);
+        s.k[at] = key, s.id[at] = id;
+    }
+    fill += count;
+}
+
+__global__ __launch_bounds__(LK_THREADS) void k_lknn_select(int64_t n, int L, const double *__restrict__ numerators,
+                                                            const double *__restrict__ denominators,
+                                                            const double *__restrict__ gamma,
+                                                            const unsigned char *__restrict__ seen,
+                                                            double *__restrict__ numer, double *__restrict__ denom,
+                                                            unsigned long long *__restrict__ out_keys,
+                                                            unsigned *__restrict__ out_ids) {
+    __shared__ LkTop top;
+    const int t = threadIdx.x;
+    lk_init(top);
+    int fill = 0;
+    const int64_t first = (int64_t)blockIdx.x * LK_SLICE;
+    const int64_t last = first + LK_SLICE < n ? first + LK_SLICE : n;
+    for (int64_t c = first; c < last; c += LK_THREADS) {
+        const int64_t i = c + t;
+        unsigned long long key = 0ull;
+        unsigned id = LK_EMPTY;
+        if (i < last) {
+            const bool gone = seen[i] != 0;
+            const double nu = gone ? -INFINITY : __dadd_rn(numerators[i], gamma[i]);
+            const double de = __dadd_rn(denominators[i], 1.0);
+            numer[i] = nu;
+            denom[i] = de;
+            if (!gone) key = score_key(__ddiv_rn(nu, de)), id = (unsigned)i;
+        }
+        lk_offer(top, L, key, id, fill);
+    }
+    lk_flush(top);
+    if (t < L) {
+        out_keys[(size_t)blockIdx.x * LK_MAX_LIST + t] = top.k[t];
+        out_ids[(size_t)blockIdx.x * LK_MAX_LIST + t] = top.id[t];
+    }
+}
+
+// final_ids != NULL (the last level, one workgroup): the list as node ids, with numer / denom of each as its score
+__global__ __launch_bounds__(LK_THREADS) void k_lknn_merge(int n_lists, int L, const unsigned long long *__restrict__ in_keys,
+                                                           const unsigned *__restrict__ in_ids,
+                                                           unsigned long long *__restrict__ out_keys,
+                                                           unsigned *__restrict__ out_ids, int32_t *__restrict__ final_ids,
+                                                           double *__restrict__ final_scores,
+                                                           const double *__restrict__ numer,
+                                                           const double *__restrict__ denom) {
+    __shared__ LkTop top;
+    const int t = threadIdx.x;
+    lk_init(top);
+    int fill = 0;
+    const int first = blockIdx.x * LK_FAN;
+    const int lists = first + LK_FAN < n_lists ? LK_FAN : n_lists - first;
+    const int entries = lists * L;  // of this workgroup's lists, list after list
+    for (int c = 0; c < entries; c += LK_THREADS) {
+        const int e = c + t;
+        unsigned long long key = 0ull;
+        unsigned id = LK_EMPTY;
+        if (e < entries) {
+            const size_t at = (size_t)(first + e / L) * LK_MAX_LIST + e % L;
+            key = in_keys[at], id = in_ids[at];
+        }
+        lk_offer(top, L, key, id, fill);
+    }
+    lk_flush(top);
+    if (t >= L) return;
+    if (final_ids) {
+        const unsigned id = top.id[t];
+        final_ids[t] = (int32_t)id;
+        final_scores[t] = id == LK_EMPTY ? -INFINITY : __ddiv_rn(numer[id], denom[id]);
+    } else {
+        out_keys[(size_t)blockIdx.x * LK_MAX_LIST + t] = top.k[t];
+        out_ids[(size_t)blockIdx.x * LK_MAX_LIST + t] = top.id[t];
+    }
+}
+
+// the one-step branch: value = score, -inf at seen nodes (k_lknn_argmax then is np.nanargmax)
+__global__ __launch_bounds__(LK_THREADS) void k_lknn_score(int64_t n, const double *__restrict__ numerators,
+                                                           const double *__restrict__ denominators,
+                                                           const double *__restrict__ gamma,
+                                                           const unsigned char *__restrict__ seen, double *__restrict__ value) {
+    const int64_t i = (int64_t)blockIdx.x * LK_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const double nu = seen[i] ? -INFINITY : __dadd_rn(numerators[i], gamma[i]);
+    value[i] = __ddiv_rn(nu, __dadd_rn(denominators[i], 1.0));
+}
+
+// predict_proba of a few nodes: (numerators + gamma) / (denominators + 1), seen or not
+__global__ void k_lknn_gather_score(int m, const int32_t *__restrict__ ids, const double *__restrict__ numerators,
+                                    const double *__restrict__ denominators, const double *__restrict__ gamma,
+                                    double *__restrict__ out) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= m) return;
+    const int id = ids[t];
+    out[t] = __ddiv_rn(__dadd_rn(numerators[id], gamma[id]), __dadd_rn(denominators[id], 1.0));
+}
+
+// condition_ for m answers in order, one workgroup of LK_MAX_D lanes: lane d owns neighbour d of the answered node.  A
+// neighbour listed twice in a row counts once (numpy's `numerators[neighbors] = num + y`); rows are ascending.
+__global__ __launch_bounds__(LK_MAX_D) void k_lknn_condition(int m, int D, const int32_t *__restrict__ pairs /* [m] (id, y) */,
+                                                             const int32_t *__restrict__ nbr, double *__restrict__ numerators,
+                                                             double *__restrict__ denominators,
+                                                             unsigned char *__restrict__ seen) {
+    const int d = threadIdx.x;
+    for (int t = 0; t < m; ++t) {
+        const int64_t id = pairs[2 * t];
+        const double y = (double)pairs[2 * t + 1];
+        if (d < D) {
+            const int j = nbr[id * D + d];
+            if (d == 0 || nbr[id * D + d - 1] != j) {
+                numerators[j] = __dadd_rn(numerators[j], y);
+                denominators[j] = __dadd_rn(denominators[j], 1.0);
+            }
+        }
+        if (d == 0) seen[id] = 1;
+        __syncthreads();  // the next answer may touch the same neighbours
+    }
+}
+
 }  // namespace
 }  // namespace ssw
 
@@ -218,7 +424,27 @@ struct ssw_lknn {
     long long *blk_i = nullptr;
     int argmax_blocks = 0;
     hipStream_t stream = nullptr;
+    // the device-resident model (ssw_lknn_state_init): its own buffers, numer / denom above stay the staging of a step
+    bool has_state = false;
+    double *numerators = nullptr, *denominators = nullptr, *gamma = nullptr;  // [n]
+    unsigned char *seen = nullptr;                                            // [n]
+    std::vector<unsigned char> seen_host;  // the marks once more, for the refusals of ssw_lknn_condition
+    int64_t n_seen = 0;
+    int n_slices = 0;                      // workgroups of k_lknn_select
+    unsigned long long *keys_a = nullptr, *keys_b = nullptr;  // [n_slices] / [ceil(n_slices / LK_FAN)] lists of LK_MAX_LIST
+    unsigned *ids_a = nullptr, *ids_b = nullptr;
+    double *list_scores = nullptr;         // [LK_MAX_LIST]
+    int32_t *small_ids = nullptr;          // [LK_MAX_ANSWERS, 2]: the answers of a condition call, the ids of a predict call
+    double *small_out = nullptr;           // [LK_MAX_ANSWERS]
+    PinnedStage small_stage;
+    unsigned char *pinned = nullptr;       // block results, list ids and list scores of a step
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around the selection and the look-ahead (ssw_lknn_step_times)
+    bool timing = false;
+    int timed = 0;                         // of the last call: 1 = the selection was timed, 2 = the look-ahead too
+    int64_t info[4] = {0, 0, 0, 0};        // of the last step: launches, host waits, bytes up, bytes down
 };
+
+static constexpr int LK_MAX_ANSWERS = 4096;  // answers of one ssw_lknn_condition, nodes of one ssw_lknn_predict
 
 extern "C" {
 
@@ -227,8 +453,14 @@ ssw_status ssw_lknn_destroy(ssw_lknn *h) {
     DeviceGuard guard(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (void *p : {(void *)h->nbr, (void *)h->numer, (void *)h->denom, (void *)h->value, (void *)h->rank_in_list,
-                    (void *)h->list_ids, (void *)h->blk_v, (void *)h->blk_i})
+                    (void *)h->list_ids, (void *)h->blk_v, (void *)h->blk_i, (void *)h->numerators, (void *)h->denominators,
+                    (void *)h->gamma, (void *)h->seen, (void *)h->keys_a, (void *)h->keys_b, (void *)h->ids_a, (void *)h->ids_b,
+                    (void *)h->list_scores, (void *)h->small_ids, (void *)h->small_out})
         (void)hipFree(p);
+    h->small_stage.release();
+    if (h->pinned) (void)hipHostFree(h->pinned);
+    for (hipEvent_t e : h->ev)
+        if (e) (void)hipEventDestroy(e);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return SSW_OK;
@@ -309,6 +541,295 @@ ssw_status ssw_lknn_top_sum(ssw_lknn *h, const double *numer_host, const double 
     }
     if (out_best_idx) *out_best_idx = best;
     if (out_best_value) *out_best_value = bval;
+    return SSW_OK;
+}
+
+}  // extern "C"
+
+// ---- the device-resident model ---------------------------------------------------------------------------------------
+namespace {
+
+ssw_status check_gamma(const ssw_lknn *h, const double *gamma_host) {
+    for (int64_t i = 0; i < h->n; ++i)
+        SSW_REQUIRE(std::isfinite(gamma_host[i]), "lknn: gamma of node %lld is not finite", (long long)i);
+    return SSW_OK;
+}
+
+void free_state(ssw_lknn *h) {
+    for (void **p : {(void **)&h->numerators, (void **)&h->denominators, (void **)&h->gamma, (void **)&h->seen, (void **)&h->keys_a,
+                     (void **)&h->keys_b, (void **)&h->ids_a, (void **)&h->ids_b, (void **)&h->list_scores, (void **)&h->small_ids,
+                     (void **)&h->small_out}) {
+        (void)hipFree(*p);
+        *p = nullptr;
+    }
+    if (h->pinned) (void)hipHostFree(h->pinned);
+    h->pinned = nullptr;
+    h->has_state = false;
+}
+
+// the places of a step's small results in the pinned block
+size_t pinned_blk_i(const ssw_lknn *h) { return (size_t)h->argmax_blocks * 8; }
+size_t pinned_list_ids(const ssw_lknn *h) { return (size_t)h->argmax_blocks * 16; }
+size_t pinned_list_scores(const ssw_lknn *h) { return pinned_list_ids(h) + LK_MAX_LIST * 4; }
+size_t pinned_bytes(const ssw_lknn *h) { return pinned_list_scores(h) + LK_MAX_LIST * 8; }
+
+// the state pass and the merge levels: afterwards numer / denom hold the step's operands and list_ids / list_scores the
+// L best unseen nodes, best first.  L <= the number of unseen nodes (the callers check).  Enqueue only.
+ssw_status enqueue_select(ssw_lknn *h, int L) {
+    hipStream_t s = h->stream;
+    hipLaunchKernelGGL(k_lknn_select, dim3((unsigned)h->n_slices), dim3(LK_THREADS), 0, s, h->n, L, h->numerators, h->denominators,
+                       h->gamma, h->seen, h->numer, h->denom, h->keys_a, h->ids_a);
+    ++h->info[0];
+    int lists = h->n_slices;
+    bool from_a = true;
+    do {
+        const int out = (lists + LK_FAN - 1) / LK_FAN;
+        const bool last = out == 1;
+        hipLaunchKernelGGL(k_lknn_merge, dim3((unsigned)out), dim3(LK_THREADS), 0, s, lists, L, from_a ? h->keys_a : h->keys_b,
+                           from_a ? h->ids_a : h->ids_b, from_a ? h->keys_b : h->keys_a, from_a ? h->ids_b : h->ids_a,
+                           last ? h->list_ids : (int32_t *)nullptr, h->list_scores, h->numer, h->denom);
+        ++h->info[0];
+        lists = out;
+        from_a = !from_a;
+    } while (lists > 1);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+ssw_status copy_down(ssw_lknn *h, void *dst, const void *src, size_t bytes) {
+    SSW_HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
+    h->info[3] += (int64_t)bytes;
+    return SSW_OK;
+}
+
+ssw_status wait(ssw_lknn *h) {
+    SSW_HIP_TRY(hipStreamSynchronize(h->stream));
+    ++h->info[1];
+    return SSW_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+ssw_status ssw_lknn_state_init(ssw_lknn *h, const double *gamma_host) {
+    SSW_REQUIRE(h && gamma_host, "NULL argument");
+    SSW_TRY(check_gamma(h, gamma_host));
+    DeviceGuard guard(h->device);
+    const int64_t n = h->n;
+    if (!h->has_state) {
+        h->n_slices = (int)((n + LK_SLICE - 1) / LK_SLICE);
+        const size_t lists_b = (size_t)(h->n_slices + LK_FAN - 1) / LK_FAN;
+        bool ok = hipMalloc((void **)&h->numerators, (size_t)n * 8) == hipSuccess &&
+                  hipMalloc((void **)&h->denominators, (size_t)n * 8) == hipSuccess &&
+                  hipMalloc((void **)&h->gamma, (size_t)n * 8) == hipSuccess &&
+                  hipMalloc((void **)&h->seen, (size_t)n) == hipSuccess &&
+                  hipMalloc((void **)&h->keys_a, (size_t)h->n_slices * LK_MAX_LIST * 8) == hipSuccess &&
+                  hipMalloc((void **)&h->ids_a, (size_t)h->n_slices * LK_MAX_LIST * 4) == hipSuccess &&
+                  hipMalloc((void **)&h->keys_b, lists_b * LK_MAX_LIST * 8) == hipSuccess &&
+                  hipMalloc((void **)&h->ids_b, lists_b * LK_MAX_LIST * 4) == hipSuccess &&
+                  hipMalloc((void **)&h->list_scores, LK_MAX_LIST * 8) == hipSuccess &&
+                  hipMalloc((void **)&h->small_ids, LK_MAX_ANSWERS * 8) == hipSuccess &&
+                  hipMalloc((void **)&h->small_out, LK_MAX_ANSWERS * 8) == hipSuccess &&
+                  hipHostMalloc((void **)&h->pinned, pinned_bytes(h), hipHostMallocDefault) == hipSuccess;
+        for (hipEvent_t &e : h->ev)
+            if (ok && !e) ok = hipEventCreate(&e) == hipSuccess;
+        if (!ok) {
+            free_state(h);
+            set_error("lknn: allocation of the resident state failed");
+            return SSW_ERR_NOMEM;
+        }
+        h->has_state = true;
+    }
+    hipStream_t s = h->stream;
+    SSW_HIP_TRY(hipMemsetAsync(h->numerators, 0, (size_t)n * 8, s));
+    SSW_HIP_TRY(hipMemsetAsync(h->denominators, 0, (size_t)n * 8, s));
+    SSW_HIP_TRY(hipMemsetAsync(h->seen, 0, (size_t)n, s));
+    SSW_HIP_TRY(hipMemcpyAsync(h->gamma, gamma_host, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    SSW_HIP_TRY(hipStreamSynchronize(s));  // gamma_host is the caller's again
+    h->seen_host.assign((size_t)n, 0);
+    h->n_seen = 0;
+    return SSW_OK;
+}
+
+ssw_status ssw_lknn_set_gamma(ssw_lknn *h, const double *gamma_host) {
+    SSW_REQUIRE(h && gamma_host, "NULL argument");
+    SSW_REQUIRE(h->has_state, "lknn: no resident state (ssw_lknn_state_init)");
+    SSW_TRY(check_gamma(h, gamma_host));
+    DeviceGuard guard(h->device);
+    SSW_HIP_TRY(hipMemcpyAsync(h->gamma, gamma_host, (size_t)h->n * 8, hipMemcpyHostToDevice, h->stream));
+    SSW_HIP_TRY(hipStreamSynchronize(h->stream));
+    return SSW_OK;
+}
+
+ssw_status ssw_lknn_condition(ssw_lknn *h, const int64_t *ids, const int32_t *ys, int32_t m) {
+    SSW_REQUIRE(h && (m == 0 || (ids && ys)), "NULL argument");
+    SSW_REQUIRE(h->has_state, "lknn: no resident state (ssw_lknn_state_init)");
+    SSW_REQUIRE(m >= 0 && m <= LK_MAX_ANSWERS, "lknn: %d answers in one call (at most %d)", m, LK_MAX_ANSWERS);
+    if (m == 0) return SSW_OK;
+    // every refusal comes before the first change: a node of this call carries the mark 2 until all have passed
+    int bad = -1;
+    const char *why = nullptr;
+    for (int t = 0; t < m && bad < 0; ++t) {
+        if (ids[t] < 0 || ids[t] >= h->n) bad = t, why = "is outside the graph";
+        else if (ys[t] != 0 && ys[t] != 1) bad = t, why = "has a label that is neither 0 nor 1";
+        else if (h->seen_host[(size_t)ids[t]] == 1) bad = t, why = "has been answered before";
+        else if (h->seen_host[(size_t)ids[t]] == 2) bad = t, why = "is repeated in the call";
+        else h->seen_host[(size_t)ids[t]] = 2;
+    }
+    for (int t = 0; t < (bad < 0 ? m : bad); ++t) h->seen_host[(size_t)ids[t]] = bad < 0 ? 1 : 0;
+    SSW_REQUIRE(bad < 0, "lknn: answer %d (node %lld) %s", bad, (long long)ids[bad], why);
+    h->n_seen += m;
+    std::vector<int32_t> pairs((size_t)m * 2);
+    for (int t = 0; t < m; ++t) pairs[2 * t] = (int32_t)ids[t], pairs[2 * t + 1] = ys[t];
+    DeviceGuard guard(h->device);
+    SSW_TRY(h->small_stage.push(h->small_ids, pairs.data(), pairs.size() * 4, h->stream));
+    hipLaunchKernelGGL(k_lknn_condition, dim3(1), dim3(LK_MAX_D), 0, h->stream, (int)m, h->D, h->small_ids, h->nbr, h->numerators,
+                       h->denominators, h->seen);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+ssw_status ssw_lknn_step(ssw_lknn *h, int32_t K, int32_t lookahead, int64_t *out_best_idx, double *out_best_value,
+                         double *out_values_or_null, int32_t *out_list_or_null) {
+    SSW_REQUIRE(h, "NULL argument");
+    SSW_REQUIRE(h->has_state, "lknn: no resident state (ssw_lknn_state_init)");
+    SSW_REQUIRE(lookahead == 1 || lookahead == 2, "lknn: lookahead=%d (1 or 2)", lookahead);
+    const int64_t n = h->n, unseen = n - h->n_seen;
+    const int L = K + h->D;
+    if (lookahead == 2) {
+        SSW_REQUIRE(K >= 1 && K <= 128, "lknn: K=%d outside [1, 128] (the row sum follows numpy's order for one 128-element block)", K);
+        SSW_REQUIRE(L <= LK_MAX_LIST, "lknn: K + D = %d exceeds %d", L, LK_MAX_LIST);
+        SSW_REQUIRE(L <= unseen, "lknn: K + D = %d exceeds the %lld unseen nodes", L, (long long)unseen);
+    } else {
+        SSW_REQUIRE(unseen >= 1, "lknn: no unseen node is left");
+    }
+    DeviceGuard guard(h->device);
+    hipStream_t s = h->stream;
+    h->info[0] = h->info[1] = h->info[2] = h->info[3] = 0;
+    h->timed = 0;
+    const unsigned row_blocks = (unsigned)((n + LK_THREADS - 1) / LK_THREADS);
+    if (lookahead == 2) {
+        if (h->timing) SSW_HIP_TRY(hipEventRecord(h->ev[0], s));
+        SSW_TRY(enqueue_select(h, L));
+        if (h->timing) SSW_HIP_TRY(hipEventRecord(h->ev[1], s));
+        hipLaunchKernelGGL(k_lknn_mark, dim3(1), dim3(LK_THREADS), 0, s, h->rank_in_list, h->list_ids, L);
+        if (h->timing) SSW_HIP_TRY(hipEventRecord(h->ev[2], s));
+        hipLaunchKernelGGL(k_lknn_top_sum, dim3(row_blocks), dim3(LK_THREADS), 0, s, n, h->D, (int)K, L, h->nbr, h->numer, h->denom,
+                           h->list_ids, h->rank_in_list, h->value);
+        if (h->timing) SSW_HIP_TRY(hipEventRecord(h->ev[3], s));
+        hipLaunchKernelGGL(k_lknn_unmark, dim3(1), dim3(LK_THREADS), 0, s, h->rank_in_list, h->list_ids, L);
+        h->info[0] += 3;
+        h->timed = h->timing ? 3 : 0;
+    } else {
+        hipLaunchKernelGGL(k_lknn_score, dim3(row_blocks), dim3(LK_THREADS), 0, s, n, h->numerators, h->denominators, h->gamma,
+                           h->seen, h->value);
+        ++h->info[0];
+    }
+    hipLaunchKernelGGL(k_lknn_argmax, dim3(h->argmax_blocks), dim3(LK_THREADS), 0, s, h->value, n, h->blk_v, h->blk_i);
+    ++h->info[0];
+    SSW_HIP_TRY(hipGetLastError());
+    const double *bv = (const double *)h->pinned;
+    const long long *bi = (const long long *)(h->pinned + pinned_blk_i(h));
+    SSW_TRY(copy_down(h, h->pinned, h->blk_v, (size_t)h->argmax_blocks * 8));
+    SSW_TRY(copy_down(h, h->pinned + pinned_blk_i(h), h->blk_i, (size_t)h->argmax_blocks * 8));
+    if (out_list_or_null && lookahead == 2) SSW_TRY(copy_down(h, h->pinned + pinned_list_ids(h), h->list_ids, (size_t)L * 4));
+    if (out_values_or_null) SSW_TRY(copy_down(h, out_values_or_null, h->value, (size_t)n * 8));
+    SSW_TRY(wait(h));
+    if (out_list_or_null && lookahead == 2) memcpy(out_list_or_null, h->pinned + pinned_list_ids(h), (size_t)L * 4);
+    long long best = -1;
+    double bval = 0.0;
+    for (int b = 0; b < h->argmax_blocks; ++b) {
+        if (bi[b] < 0) continue;
+        if (best < 0 || bv[b] > bval || (bv[b] == bval && bi[b] < best)) {
+            best = bi[b];
+            bval = bv[b];
+        }
+    }
+    if (out_best_idx) *out_best_idx = best;
+    if (out_best_value) *out_best_value = bval;
+    return SSW_OK;
+}
+
+ssw_status ssw_lknn_top_remaining(ssw_lknn *h, int32_t k, int32_t *out_ids, double *out_scores, int32_t *out_count) {
+    SSW_REQUIRE(h && out_ids && out_scores && out_count, "NULL argument");
+    SSW_REQUIRE(h->has_state, "lknn: no resident state (ssw_lknn_state_init)");
+    SSW_REQUIRE(k >= 1 && k <= LK_MAX_LIST, "lknn: top_remaining k=%d outside [1, %d]", k, LK_MAX_LIST);
+    const int64_t unseen = h->n - h->n_seen;
+    const int L = (int)std::min<int64_t>(k, unseen);
+    h->info[0] = h->info[1] = h->info[2] = h->info[3] = 0;
+    h->timed = 0;
+    *out_count = L;
+    if (L == 0) return SSW_OK;
+    DeviceGuard guard(h->device);
+    if (h->timing) SSW_HIP_TRY(hipEventRecord(h->ev[0], h->stream));
+    SSW_TRY(enqueue_select(h, L));
+    if (h->timing) SSW_HIP_TRY(hipEventRecord(h->ev[1], h->stream));
+    h->timed = h->timing ? 1 : 0;
+    SSW_TRY(copy_down(h, h->pinned + pinned_list_ids(h), h->list_ids, (size_t)L * 4));
+    SSW_TRY(copy_down(h, h->pinned + pinned_list_scores(h), h->list_scores, (size_t)L * 8));
+    SSW_TRY(wait(h));
+    memcpy(out_ids, h->pinned + pinned_list_ids(h), (size_t)L * 4);
+    memcpy(out_scores, h->pinned + pinned_list_scores(h), (size_t)L * 8);
+    return SSW_OK;
+}
+
+ssw_status ssw_lknn_predict(ssw_lknn *h, const int64_t *ids, int32_t m, double *out_scores) {
+    SSW_REQUIRE(h && (m == 0 || (ids && out_scores)), "NULL argument");
+    SSW_REQUIRE(h->has_state, "lknn: no resident state (ssw_lknn_state_init)");
+    SSW_REQUIRE(m >= 0 && m <= LK_MAX_ANSWERS, "lknn: %d nodes in one call (at most %d)", m, LK_MAX_ANSWERS);
+    if (m == 0) return SSW_OK;
+    std::vector<int32_t> ids32((size_t)m);
+    for (int t = 0; t < m; ++t) {
+        SSW_REQUIRE(ids[t] >= 0 && ids[t] < h->n, "lknn: node %lld is outside the graph", (long long)ids[t]);
+        ids32[t] = (int32_t)ids[t];
+    }
+    DeviceGuard guard(h->device);
+    SSW_TRY(h->small_stage.push(h->small_ids, ids32.data(), ids32.size() * 4, h->stream));
+    hipLaunchKernelGGL(k_lknn_gather_score, dim3((unsigned)((m + LK_THREADS - 1) / LK_THREADS)), dim3(LK_THREADS), 0, h->stream, (int)m,
+                       h->small_ids, h->numerators, h->denominators, h->gamma, h->small_out);
+    SSW_HIP_TRY(hipGetLastError());
+    SSW_HIP_TRY(hipMemcpyAsync(out_scores, h->small_out, (size_t)m * 8, hipMemcpyDeviceToHost, h->stream));
+    SSW_HIP_TRY(hipStreamSynchronize(h->stream));
+    return SSW_OK;
+}
+
+ssw_status ssw_lknn_state_fetch(ssw_lknn *h, double *numerators, double *denominators, double *gamma, uint8_t *seen_u8) {
+    SSW_REQUIRE(h, "NULL argument");
+    SSW_REQUIRE(h->has_state, "lknn: no resident state (ssw_lknn_state_init)");
+    DeviceGuard guard(h->device);
+    hipStream_t s = h->stream;
+    const size_t n = (size_t)h->n;
+    if (numerators) SSW_HIP_TRY(hipMemcpyAsync(numerators, h->numerators, n * 8, hipMemcpyDeviceToHost, s));
+    if (denominators) SSW_HIP_TRY(hipMemcpyAsync(denominators, h->denominators, n * 8, hipMemcpyDeviceToHost, s));
+    if (gamma) SSW_HIP_TRY(hipMemcpyAsync(gamma, h->gamma, n * 8, hipMemcpyDeviceToHost, s));
+    if (seen_u8) SSW_HIP_TRY(hipMemcpyAsync(seen_u8, h->seen, n, hipMemcpyDeviceToHost, s));
+    SSW_HIP_TRY(hipStreamSynchronize(s));
+    return SSW_OK;
+}
+
+ssw_status ssw_lknn_step_info(ssw_lknn *h, int64_t *out4) {
+    SSW_REQUIRE(h && out4, "NULL argument");
+    for (int j = 0; j < 4; ++j) out4[j] = h->info[j];
+    return SSW_OK;
+}
+
+ssw_status ssw_lknn_step_times(ssw_lknn *h, int32_t enable, double *out_ms2_or_null) {
+    SSW_REQUIRE(h, "NULL argument");
+    SSW_REQUIRE(h->has_state, "lknn: no resident state (ssw_lknn_state_init)");
+    if (out_ms2_or_null) {
+        out_ms2_or_null[0] = out_ms2_or_null[1] = -1.0;
+        float ms = 0.f;
+        if (h->timed & 1) {
+            SSW_HIP_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+            out_ms2_or_null[0] = ms;
+        }
+        if (h->timed & 2) {
+            SSW_HIP_TRY(hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
+            out_ms2_or_null[1] = ms;
+        }
+    }
+    h->timing = enable != 0;
     return SSW_OK;
 }
 

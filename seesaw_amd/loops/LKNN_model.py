@@ -5,7 +5,9 @@ three host arrays (numerators, denominators, gamma) over the nodes and the CSR n
 label touches one row of neighbours.  What is expensive in the reference -- the look-ahead value of every node,
 an N x (K + 2D) argsort per planning step -- runs on the GPU (`top_sum`, ssw_lknn_top_sum).  The descending order of the
 scores is sorted in full only where the scores are new as a whole (from_dataset, with_gamma: once per text query);
-after an answer (condition_) the handful of changed nodes is merged back into it."""
+after an answer (condition_) the handful of changed nodes is merged back into it.
+
+DeviceLKNNModel (below) is the same model with its state resident on the device and no order kept at all."""
 from __future__ import annotations
 
 import ctypes
@@ -238,9 +240,155 @@ class LKNNModel(ProbabilityModel):
         return (int(best_i.value), float(best_v.value), values) if return_values else (int(best_i.value), float(best_v.value))
 
 
+class DeviceLKNNModel(ProbabilityModel):
+    """LKNNModel with its state on the device (interactive_options["model_on_device"]): numerators, denominators, gamma
+    and the seen marks live on an ssw_lknn handle; an answer is one enqueued kernel (ssw_lknn_condition), a planning
+    step one call with one host wait (ssw_lknn_step).  The host keeps the dataset (seen bitmap, idx2label) and nothing of
+    size N: no sorted order, no score array.  The object is mutable: with_gamma and condition_ change it in place, so the
+    recursive planner's condition() is not offered -- implementation='vectorized' only.
+
+    Nodes are ranked by (score descending, node id ascending).  Whenever the K + D + 1 highest unseen scores are pairwise
+    distinct -- the jittered prior sees to that -- picks, values and value vectors equal LKNNModel's bit for bit."""
+    device_resident = True
+    KERNEL_MAX_K, KERNEL_MAX_D, KERNEL_MAX_LIST = LKNNModel.KERNEL_MAX_K, LKNNModel.KERNEL_MAX_D, LKNNModel.KERNEL_MAX_LIST
+    MAX_CALL = 4096  # answers of one ssw_lknn_condition, nodes of one ssw_lknn_predict
+
+    def __init__(self, dataset: Dataset, owner: "_Handle", n: int, degree: int, device: int):
+        super().__init__(dataset)
+        self._owner, self.n, self.degree, self.device = owner, n, degree, device
+
+    @staticmethod
+    def from_dataset(dataset: Dataset, weight_matrix: sp.csr_array, gamma: np.ndarray, device: int = 0):
+        if getattr(weight_matrix, "format", None) != "csr":
+            raise ValueError("the device-resident L-KNN model needs a CSR weight matrix")
+        if len(dataset.idx2label) != 0:
+            raise ValueError("the device-resident L-KNN model starts from a dataset without labels")
+        n = weight_matrix.shape[0]
+        deltas = np.diff(weight_matrix.indptr)
+        if n == 0 or not (deltas == deltas[0]).all() or not 1 <= int(deltas[0]) <= DeviceLKNNModel.KERNEL_MAX_D:
+            raise ValueError("the device-resident L-KNN model needs a regular graph (the same number of neighbours for every "
+                             f"node) of degree 1..{DeviceLKNNModel.KERNEL_MAX_D}; this one has {int(deltas.min()) if n else 0}.."
+                             f"{int(deltas.max()) if n else 0} neighbours a node; there is no host fallback")
+        degree = int(deltas[0])
+        gamma = DeviceLKNNModel._checked_gamma(gamma, n)
+        nbr = np.ascontiguousarray(np.sort(weight_matrix.indices.reshape(-1, degree)), dtype=np.int32)
+        h = ctypes.c_void_p()
+        _lib.call("ssw_lknn_create", int(device), n, degree, ctypes.c_void_p(nbr.ctypes.data), ctypes.byref(h))
+        owner = _Handle(h)
+        _lib.call("ssw_lknn_state_init", h, ctypes.c_void_p(gamma.ctypes.data))
+        return DeviceLKNNModel(dataset, owner, n, degree, int(device))
+
+    @staticmethod
+    def _checked_gamma(gamma, n):
+        gamma = np.ascontiguousarray(gamma, dtype=np.float64)
+        assert gamma.shape == (n,)
+        assert ((0 < gamma) & (gamma < 1)).all(), "this could fail by chance, decrase var. or fix properly by applying sigmoid"
+        return gamma
+
+    @property
+    def _h(self):
+        if self._owner is None:
+            raise RuntimeError("this DeviceLKNNModel is closed")
+        return self._owner.h
+
+    def close(self):
+        if self._owner is not None:
+            self._owner.close()
+            self._owner = None
+
+    # ---- conditioning -------------------------------------------------------------------------
+    def condition(self, idx, y):
+        raise NotImplementedError("the device-resident model is conditioned in place (condition_); the recursive planner "
+                                  "(implementation='loop') needs the host LKNNModel")
+
+    def probability_bound(self, n):
+        raise NotImplementedError("pruning is not served by the device-resident model")
+
+    def with_gamma(self, new_gamma: np.ndarray) -> "DeviceLKNNModel":
+        """replaces gamma IN PLACE (one upload), keeps counts and seen marks; returns self"""
+        gamma = self._checked_gamma(new_gamma, self.n)
+        _lib.call("ssw_lknn_set_gamma", self._h, ctypes.c_void_p(gamma.ctypes.data))
+        return self
+
+    def condition_(self, idx, y):
+        self.condition_many_([(idx, y)])
+
+    def condition_many_(self, pairs):
+        """the answers [(idx, y), ...] in order, one enqueued call per 4096 of them (a refused call changes nothing)"""
+        pairs = [(int(i), int(y)) for i, y in pairs]
+        for a in range(0, len(pairs), self.MAX_CALL):
+            part = pairs[a:a + self.MAX_CALL]
+            ids = np.array([i for i, _ in part], dtype=np.int64)
+            ys = np.array([y for _, y in part], dtype=np.int32)
+            _lib.call("ssw_lknn_condition", self._h, ctypes.c_void_p(ids.ctypes.data), ctypes.c_void_p(ys.ctypes.data), len(part))
+            for i, y in part:
+                self.dataset = self.dataset.with_label(i, y)
+
+    # ---- queries ------------------------------------------------------------------------------
+    def step(self, K: int, lookahead: int, return_values: bool = False, return_list: bool = False):
+        """one planning step (ssw_lknn_step).  lookahead 2: LKNNModel.top_sum(K); lookahead 1: the most probable unseen
+        node and its score.  -> (best index, best value[, all values][, the K + D selected nodes])"""
+        values = np.empty(self.n, dtype=np.float64) if return_values else None
+        chosen = np.empty(K + self.degree, dtype=np.int32) if return_list and lookahead == 2 else None
+        best_i, best_v = ctypes.c_int64(-1), ctypes.c_double(0.0)
+        _lib.call("ssw_lknn_step", self._h, int(K), int(lookahead), ctypes.byref(best_i), ctypes.byref(best_v),
+                  None if values is None else ctypes.c_void_p(values.ctypes.data),
+                  None if chosen is None else ctypes.c_void_p(chosen.ctypes.data))
+        out = (int(best_i.value), float(best_v.value))
+        if return_values:
+            out += (values,)
+        if return_list:
+            out += (chosen,)
+        return out
+
+    def top_sum(self, K: int, return_values: bool = False):
+        return self.step(K, 2, return_values=return_values)
+
+    def top_k_remaining(self, top_k: int) -> Tuple[np.ndarray, np.ndarray]:
+        if not 1 <= top_k <= self.KERNEL_MAX_LIST:
+            raise ValueError(f"top_k={top_k}: the device-resident model lists 1..{self.KERNEL_MAX_LIST} nodes")
+        ids, scores = np.empty(top_k, dtype=np.int32), np.empty(top_k, dtype=np.float64)
+        count = ctypes.c_int32(0)
+        _lib.call("ssw_lknn_top_remaining", self._h, int(top_k), ctypes.c_void_p(ids.ctypes.data),
+                  ctypes.c_void_p(scores.ctypes.data), ctypes.byref(count))
+        return ids[:count.value].astype(np.int64), scores[:count.value]
+
+    def predict_proba(self, idxs) -> np.ndarray:
+        idxs = np.ascontiguousarray(np.asarray(idxs, dtype=np.int64).reshape(-1))
+        out = np.empty(idxs.shape[0], dtype=np.float64)
+        for a in range(0, idxs.shape[0], self.MAX_CALL):
+            m = min(self.MAX_CALL, idxs.shape[0] - a)
+            _lib.call("ssw_lknn_predict", self._h, ctypes.c_void_p(idxs[a:].ctypes.data), m, ctypes.c_void_p(out[a:].ctypes.data))
+        return out
+
+    def state(self) -> dict:
+        """the resident state copied back: numerators, denominators, gamma (f64 [N]), seen (bool [N])"""
+        num, den, gam = (np.empty(self.n, dtype=np.float64) for _ in range(3))
+        seen = np.empty(self.n, dtype=np.uint8)
+        _lib.call("ssw_lknn_state_fetch", self._h, *(ctypes.c_void_p(a.ctypes.data) for a in (num, den, gam, seen)))
+        return dict(numerators=num, denominators=den, gamma=gam, seen=seen.astype(bool))
+
+    def step_info(self) -> dict:
+        out = np.zeros(4, dtype=np.int64)
+        _lib.call("ssw_lknn_step_info", self._h, ctypes.c_void_p(out.ctypes.data))
+        return dict(launches=int(out[0]), host_waits=int(out[1]), bytes_to_device=int(out[2]), bytes_to_host=int(out[3]))
+
+    def step_times(self, enable: bool = True):
+        """(selection ms, look-ahead ms) of the last step from device events, None where it was not timed; steps from now
+        on are timed or not"""
+        out = np.zeros(2, dtype=np.float64)
+        _lib.call("ssw_lknn_step_times", self._h, int(bool(enable)), ctypes.c_void_p(out.ctypes.data))
+        return None if out[0] < 0 else (float(out[0]), float(out[1]))
+
+
 class _Handle:
     def __init__(self, h):
         self.h = h
+
+    def close(self):
+        if self.h is not None:
+            h, self.h = self.h, None
+            _lib.call("ssw_lknn_destroy", h)
 
     def __del__(self):
         try:

@@ -1,6 +1,8 @@
 """ActiveSearch / LKNNSearch loops (seesaw/loops/active_search.py:32-223): the next image is chosen by planning over
 the L-KNN model instead of by the current query vector.  ActiveSearch plans with efficient non-myopic search (the
-vectorised two-step look-ahead runs on the GPU); LKNNSearch greedily takes the most probable remaining node."""
+vectorised two-step look-ahead runs on the GPU); LKNNSearch greedily takes the most probable remaining node.
+interactive_options["model_on_device"] = True keeps the model's state on the device (DeviceLKNNModel): set_text_vec
+uploads gamma once, next_batch is one step call, refine one condition call; absent or false, the host LKNNModel runs."""
 from __future__ import annotations
 
 import math
@@ -12,8 +14,33 @@ from ..calibration import FixedCalibrator
 from ..research.active_search.common import Dataset
 from ..research.active_search.efficient_nonmyopic_search import efficient_nonmyopic_search
 from .graph_based import get_label_prop
-from .LKNN_model import LKNNModel, initial_gamma_array
+from .LKNN_model import DeviceLKNNModel, LKNNModel, initial_gamma_array
 from .loop_base import LoopBase
+
+
+def _model_class(opts, planner: bool):
+    """interactive_options["model_on_device"]: the model whose state stays on the device (DeviceLKNNModel).  What it
+    cannot serve is refused here, at construction, not met half way through a session."""
+    if not opts.get("model_on_device", False):
+        return LKNNModel
+    if planner:
+        if opts["implementation"] != "vectorized":
+            raise ValueError(f"model_on_device serves implementation='vectorized' only, not {opts['implementation']!r}")
+        if opts["pruning_on"]:
+            raise ValueError("model_on_device does not serve pruning_on=True")
+        if opts["reward_horizon"] > DeviceLKNNModel.KERNEL_MAX_K + 1:
+            raise ValueError(f"model_on_device serves a reward_horizon of at most {DeviceLKNNModel.KERNEL_MAX_K + 1}, "
+                             f"not {opts['reward_horizon']}")
+    return DeviceLKNNModel
+
+
+def _condition_all(model, answers):
+    """the answers [(node, y), ...] in order: one enqueued call on the device model, one condition_ each on the host model"""
+    if isinstance(model, DeviceLKNNModel):
+        model.condition_many_(answers)
+    else:
+        for idx, y in answers:
+            model.condition_(idx, y)
 
 
 def _vector_position(index, dbidx) -> int:
@@ -42,8 +69,9 @@ class ActiveSearch(LoopBase):
         else:
             assert self.gamma["mode"] == "fixed"
             initial_gamma = initial_gamma_array(self.gamma["value"], n)
-        self.prob_model = LKNNModel.from_dataset(Dataset.from_vectors(q.index.vectors), gamma=initial_gamma,
-                                                 weight_matrix=weight_matrix, device=getattr(q.index, "device", 0) or 0)
+        self.prob_model = _model_class(opts, planner=True).from_dataset(
+            Dataset.from_vectors(q.index.vectors), gamma=initial_gamma, weight_matrix=weight_matrix,
+            device=getattr(q.index, "device", 0) or 0)
         self.dataset = self.prob_model.dataset
         self.pruned_fractions = []
         self.refine_not_called_before = True
@@ -84,8 +112,7 @@ class ActiveSearch(LoopBase):
             translated = [(int(i), 1) for i in pos] + [(int(i), 0) for i in neg]
         else:
             translated = [(_vector_position(self.q.index, idx), y) for idx, y in change]
-        for idx, y in translated:
-            self.prob_model.condition_(idx, y)
+        _condition_all(self.prob_model, translated)
         self.refine_not_called_before = False
 
 
@@ -101,8 +128,9 @@ class LKNNSearch(LoopBase):
             gamma_mean = opts["gamma"]
         n = q.index.vectors.shape[0]
         self.use_clip_as_gamma = opts["use_clip_as_gamma"]
-        self.prob_model = LKNNModel.from_dataset(Dataset.from_vectors(q.index.vectors), gamma=initial_gamma_array(gamma_mean, n),
-                                                 weight_matrix=weight_matrix, device=getattr(q.index, "device", 0) or 0)
+        self.prob_model = _model_class(opts, planner=False).from_dataset(
+            Dataset.from_vectors(q.index.vectors), gamma=initial_gamma_array(gamma_mean, n), weight_matrix=weight_matrix,
+            device=getattr(q.index, "device", 0) or 0)
         self.dataset = self.prob_model.dataset
 
     @staticmethod
@@ -127,5 +155,5 @@ class LKNNSearch(LoopBase):
     def refine(self, change=None):
         assert change is not None
         print(f"updating model with {change=}")
-        for idx, y in change:
-            self.prob_model.condition_(_vector_position(self.q.index, idx), y)
+        translated = [(_vector_position(self.q.index, idx), y) for idx, y in change]
+        _condition_all(self.prob_model, translated)

@@ -59,6 +59,9 @@ def _opt_expected_utility_helper(*, i: int, lookahead_limit: int, t: int, model:
 
 def _opt_expected_utility_helper_lknn2(*, i: int, lookahead_limit: int, t: int, model, pruning_on: bool):
     assert i == 0 and lookahead_limit <= 2 and t >= lookahead_limit
+    if getattr(model, "device_resident", False):  # DeviceLKNNModel: either depth is one ssw_lknn_step call
+        best, value = model.step(K=t - 1, lookahead=lookahead_limit)
+        return Result(value=value, index=best, pruned_fraction=0.0)
     assert ((0 < model.gamma) & (model.gamma < 1)).all()
     assert (model.numerators <= model.denominators).all()
     if lookahead_limit == 2:
