@@ -315,6 +315,12 @@ ssw_status ssw_debug_clip_multiscale_tiles(ssw_clip *clip, const uint8_t *images
                                            const int32_t *level_first, const int32_t *level_wh, uint8_t *out_tiles_host,
                                            int64_t out_cap_tiles, int64_t *out_n_tiles);
 
+/* The f64 loss of the engine's last evaluation (ssw_fb_lossgrad, ssw_fb_lossgrad2, ssw_fb_lossgrad2_dev), which those
+ * entries round to f32 on the way out.  The fit drivers compare the f64 value (L-BFGS stops on |loss - prev_loss| <
+ * 1e-9), so a restatement of the driver around the engine's own evaluation needs it (tests/test_fit_driver_gpu.py).
+ * Host code only: reads the word the evaluation left, launches nothing.  After a fit it holds that fit's last word. */
+ssw_status ssw_debug_fb_last_loss(const ssw_fb *fb, double *out);
+
 #ifdef __cplusplus
 }
 #endif

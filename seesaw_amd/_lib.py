@@ -255,6 +255,7 @@ _DEBUG_SIGNATURES = {
     "ssw_debug_resize_u8": (c_i32, [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_i32, c_void_p]),
     "ssw_debug_clip_multiscale_tiles": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                 c_i64, c_i64_p]),
+    "ssw_debug_fb_last_loss": (c_i32, [c_void_p, c_f64_p]),
 }
 
 

@@ -4,6 +4,7 @@
 #endif
 #include <algorithm>
 
+#include "fb_handle.h"
 #include "index_handle.h"
 
 // ---------------------------------------------------------------------------------------
@@ -1104,6 +1105,15 @@ ssw_status ssw_debug_prune6_scan_shape(ssw_index *idx, int32_t *out_blocks, int3
     scan_shape(SCAN_Q6, idx->dim, idx->device, idx->n, &blocks, &tiles);
     *out_blocks = blocks;
     *out_tiles = tiles;
+    return SSW_OK;
+}
+
+// The f64 loss of the engine's last one-output evaluation (fb_eval leaves it in loss_host[0]; ssw_fb_lossgrad hands out
+// its f32 rounding, the fit drivers compare this value).  Host code only: fb_handle.h is included for the handle's
+// layout, none of fb_math.h's arithmetic is instantiated here.
+ssw_status ssw_debug_fb_last_loss(const ssw_fb *fb, double *out) {
+    SSW_REQUIRE(fb != nullptr && out != nullptr, "NULL argument");
+    *out = fb->loss_host[0];
     return SSW_OK;
 }
 
