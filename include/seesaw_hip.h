@@ -938,6 +938,47 @@ ssw_status ssw_lknn_step_info(ssw_lknn *h, int64_t *out4);
  * look-ahead kernel, -1 where that step was not timed; then steps from now on are timed (enable != 0) or not. */
 ssw_status ssw_lknn_step_times(ssw_lknn *h, int32_t enable, double *out_ms2_or_null);
 
+/* Several handles' planning steps in ONE pass of kernels with ONE host wait -- S sessions that plan together share the
+ * launches and the wait (ssw_lknn_step alone: 3-8 launches and a wait each).  hs: n_slots <= SSW_LKNN_MAX_BATCH distinct
+ * handles with resident state, of one device, one n and one D; K, lookahead: [n_slots].
+ * Contract: slot j returns the bits ssw_lknn_step(hs[j], K[j], lookahead[j], ...) returns -- out_best_idx[j],
+ * out_best_value[j], out_values[j] ([n], NaN pattern included; the array or any entry may be NULL) and, of a lookahead-2
+ * slot, the first K[j] + D entries of row j of out_lists ([n_slots][192]; may be NULL; the rest of a row is not written)
+ * -- and like it leaves the model state (numerators, denominators, gamma, seen) untouched.
+ * Per-slot refusals: whatever ssw_lknn_step would refuse for that handle (lookahead not 1 or 2, K outside [1, 128], K + D
+ * above 192 or above the slot's unseen nodes, no unseen node left) is out_status[j] (SSW_ERR_INVALID) with that call's
+ * message in ssw_lknn_batch_error(hs[j]), decided on the host before anything is enqueued for the slot; its outputs are
+ * index -1, value 0.  The other slots run and the call returns SSW_OK; a slot that is SSW_OK has "" as its batch error.
+ * The pass: one device table of per-slot descriptors (the slot's own state and staging buffers, K, L -- no new O(n)
+ * allocation), every kernel launched once with the slot on blockIdx.y and running the single kernel's body: for the
+ * lookahead-2 slots the state pass with the selection, the merge levels, mark, look-ahead, unmark; for the lookahead-1
+ * slots the score kernel; for all the block argmax and a finish kernel, one workgroup a slot, that reduces the block
+ * results on the device by the host loop's rule (largest non-NaN value, lowest index among equals: a total order, so the
+ * reduction order does not matter).  The number of launches does not depend on n_slots (1.56 M nodes: 3 + 3 + 2, one
+ * more with lookahead-1 slots present); 16 bytes a slot come back, plus the lists and value vectors asked for.
+ * Streams: the pass runs on hs[0]'s stream after waiting on an event recorded on every other handle's stream -- answers
+ * enqueued with ssw_lknn_condition are seen -- and the call returns with everything complete.  The descriptor table and
+ * the pinned result block belong to hs[0], grow on demand and are freed with it.
+ * Whole-call refusals (SSW_ERR_INVALID, nothing enqueued, every handle untouched): n_slots outside
+ * [1, SSW_LKNN_MAX_BATCH], NULL arrays, a NULL or repeated handle, a handle without resident state, handles of
+ * different device, n or D.
+ * out_stats4 (may be NULL): [0] kernel launches, [1] host waits (1; 0 when every slot was refused), [2] bytes copied host
+ * -> device (the table), [3] bytes copied device -> host.  ssw_lknn_step_info of hs[0] and of every slot that ran
+ * reports the same four; with timing enabled on hs[0], ssw_lknn_step_times(hs[0], ...) reports the pass's selection and
+ * look-ahead phases (all slots together).
+ *
+ * ssw_lknn_top_remaining_batch: slot j returns the bits of ssw_lknn_top_remaining(hs[j], k[j], ...) in row j of out_ids /
+ * out_scores ([n_slots][192] each) with out_counts[j] = min(k[j], unseen nodes) entries; a slot without an unseen node
+ * has count 0 and enqueues nothing; k[j] outside [1, 192] is that slot's refusal.  Same pass (state pass, merge levels,
+ * one kernel that gathers the lists), same streams, same whole-call refusals, one host wait. */
+#define SSW_LKNN_MAX_BATCH 256
+ssw_status ssw_lknn_step_batch(ssw_lknn *const *hs, int32_t n_slots, const int32_t *K, const int32_t *lookahead,
+                               int64_t *out_best_idx, double *out_best_value, double *const *out_values_or_null,
+                               int32_t *out_lists_or_null, int32_t *out_status, int64_t *out_stats4_or_null);
+ssw_status ssw_lknn_top_remaining_batch(ssw_lknn *const *hs, int32_t n_slots, const int32_t *k, int32_t *out_ids,
+                                        double *out_scores, int32_t *out_counts, int32_t *out_status);
+const char *ssw_lknn_batch_error(const ssw_lknn *h);
+
 /* ------------------------------------------------------------------------- */
 /* CLIP ViT-B/32 image / text towers (bf16 MFMA forward)                       */
 /* replaces: transformers.CLIPModel.get_text_features                          */

@@ -150,6 +150,10 @@ _SIGNATURES = {
     "ssw_lknn_state_fetch": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ssw_lknn_step_info": (c_i32, [c_void_p, c_void_p]),
     "ssw_lknn_step_times": (c_i32, [c_void_p, c_i32, c_void_p]),
+    "ssw_lknn_step_batch": (c_i32, [c_void_pp, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_pp, c_void_p, c_void_p,
+                                    c_void_p]),
+    "ssw_lknn_top_remaining_batch": (c_i32, [c_void_pp, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ssw_lknn_batch_error": (ctypes.c_char_p, [c_void_p]),
     "ssw_rank_pairwise": (c_i32, [c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_i32, ctypes.c_float, c_void_p, c_void_p]),
     "ssw_clip_create": (c_i32, [c_i32, c_void_p, ctypes.c_size_t, c_void_pp]),
     "ssw_clip_destroy": (c_i32, [c_void_p]),

@@ -82,25 +82,34 @@ struct RowSum {
     }
 };
 
-__global__ void k_lknn_mark(int32_t *__restrict__ rank_in_list, const int32_t *__restrict__ list_ids, int L) {
+// Every kernel body below is a __device__ function: the single kernels hand it their arguments, the *_batch kernels (at
+// the end of the namespace) the fields of their slot's descriptor -- one body, the same bits.  blockIdx.x / threadIdx.x
+// mean the same in both; the slot of a batch kernel is blockIdx.y.
+__device__ __forceinline__ void lk_mark_body(int32_t *__restrict__ rank_in_list, const int32_t *__restrict__ list_ids, int L) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j < L) rank_in_list[list_ids[j]] = j;
 }
 
-__global__ void k_lknn_unmark(int32_t *__restrict__ rank_in_list, const int32_t *__restrict__ list_ids, int L) {
+__device__ __forceinline__ void lk_unmark_body(int32_t *__restrict__ rank_in_list, const int32_t *__restrict__ list_ids, int L) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j < L) rank_in_list[list_ids[j]] = -1;
 }
 
+__global__ void k_lknn_mark(int32_t *__restrict__ rank_in_list, const int32_t *__restrict__ list_ids, int L) {
+    lk_mark_body(rank_in_list, list_ids, L);
+}
+
+__global__ void k_lknn_unmark(int32_t *__restrict__ rank_in_list, const int32_t *__restrict__ list_ids, int L) {
+    lk_unmark_body(rank_in_list, list_ids, L);
+}
+
 // numer: numerators + gamma (-inf for labelled nodes); denom: denominators + 1
-__global__ __launch_bounds__(LK_THREADS) void k_lknn_top_sum(int64_t n, int D, int K, int L,
-                                                             const int32_t *__restrict__ nbr /* [n, D] ascending */,
-                                                             const double *__restrict__ numer,
-                                                             const double *__restrict__ denom,
-                                                             const int32_t *__restrict__ list_ids /* [L] score desc */,
-                                                             const int32_t *__restrict__ rank_in_list,
-                                                             double *__restrict__ out) {
-    __shared__ double lscore[LK_MAX_LIST];
+// lscore: the workgroup's [LK_MAX_LIST] doubles of LDS
+__device__ __forceinline__ void lk_top_sum_body(double *lscore, int64_t n, int D, int K, int L,
+                                                const int32_t *__restrict__ nbr /* [n, D] ascending */,
+                                                const double *__restrict__ numer, const double *__restrict__ denom,
+                                                const int32_t *__restrict__ list_ids /* [L] score desc */,
+                                                const int32_t *__restrict__ rank_in_list, double *__restrict__ out) {
     for (int j = threadIdx.x; j < L; j += LK_THREADS) {
         const int id = list_ids[j];
         lscore[j] = numer[id] / denom[id];
@@ -166,11 +175,21 @@ __global__ __launch_bounds__(LK_THREADS) void k_lknn_top_sum(int64_t n, int D, i
     out[i] = __dadd_rn(__dmul_rn(s, __dadd_rn(1.0, e1)), __dmul_rn(__dadd_rn(1.0, -s), e0));
 }
 
+__global__ __launch_bounds__(LK_THREADS) void k_lknn_top_sum(int64_t n, int D, int K, int L,
+                                                             const int32_t *__restrict__ nbr /* [n, D] ascending */,
+                                                             const double *__restrict__ numer,
+                                                             const double *__restrict__ denom,
+                                                             const int32_t *__restrict__ list_ids /* [L] score desc */,
+                                                             const int32_t *__restrict__ rank_in_list,
+                                                             double *__restrict__ out) {
+    __shared__ double lscore[LK_MAX_LIST];
+    lk_top_sum_body(lscore, n, D, K, L, nbr, numer, denom, list_ids, rank_in_list, out);
+}
+
 // np.nanargmax: the first index of the largest non-NaN value
-__global__ __launch_bounds__(LK_THREADS) void k_lknn_argmax(const double *__restrict__ v, int64_t n,
-                                                            double *__restrict__ best_v, long long *__restrict__ best_i) {
-    __shared__ double sv[LK_THREADS];
-    __shared__ long long si[LK_THREADS];
+// sv / si: the workgroup's [LK_THREADS] entries of LDS each
+__device__ __forceinline__ void lk_argmax_body(double *sv, long long *si, const double *__restrict__ v, int64_t n,
+                                               double *__restrict__ best_v, long long *__restrict__ best_i) {
     double bv = -INFINITY;
     long long bi = -1;
     for (int64_t i = (int64_t)blockIdx.x * LK_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * LK_THREADS) {
@@ -201,6 +220,13 @@ __global__ __launch_bounds__(LK_THREADS) void k_lknn_argmax(const double *__rest
         best_v[blockIdx.x] = sv[0];
         best_i[blockIdx.x] = si[0];
     }
+}
+
+__global__ __launch_bounds__(LK_THREADS) void k_lknn_argmax(const double *__restrict__ v, int64_t n,
+                                                            double *__restrict__ best_v, long long *__restrict__ best_i) {
+    __shared__ double sv[LK_THREADS];
+    __shared__ long long si[LK_THREADS];
+    lk_argmax_body(sv, si, v, n, best_v, best_i);
 }
 
 // ---- the device-resident model (ssw_lknn_state_init .. ssw_lknn_step) ------------------------------------------------
@@ -293,14 +319,11 @@ __device__ inline void lk_offer(LkTop &s, int L, unsigned long long key, unsigne
     fill += count;
 }
 
-__global__ __launch_bounds__(LK_THREADS) void k_lknn_select(int64_t n, int L, const double *__restrict__ numerators,
-                                                            const double *__restrict__ denominators,
-                                                            const double *__restrict__ gamma,
-                                                            const unsigned char *__restrict__ seen,
-                                                            double *__restrict__ numer, double *__restrict__ denom,
-                                                            unsigned long long *__restrict__ out_keys,
-                                                            unsigned *__restrict__ out_ids) {
-    __shared__ LkTop top;
+__device__ __forceinline__ void lk_select_body(LkTop &top, int64_t n, int L, const double *__restrict__ numerators,
+                                               const double *__restrict__ denominators, const double *__restrict__ gamma,
+                                               const unsigned char *__restrict__ seen, double *__restrict__ numer,
+                                               double *__restrict__ denom, unsigned long long *__restrict__ out_keys,
+                                               unsigned *__restrict__ out_ids) {
     const int t = threadIdx.x;
     lk_init(top);
     int fill = 0;
@@ -327,15 +350,23 @@ __global__ __launch_bounds__(LK_THREADS) void k_lknn_select(int64_t n, int L, co
     }
 }
 
-// final_ids != NULL (the last level, one workgroup): the list as node ids, with numer / denom of each as its score
-__global__ __launch_bounds__(LK_THREADS) void k_lknn_merge(int n_lists, int L, const unsigned long long *__restrict__ in_keys,
-                                                           const unsigned *__restrict__ in_ids,
-                                                           unsigned long long *__restrict__ out_keys,
-                                                           unsigned *__restrict__ out_ids, int32_t *__restrict__ final_ids,
-                                                           double *__restrict__ final_scores,
-                                                           const double *__restrict__ numer,
-                                                           const double *__restrict__ denom) {
+__global__ __launch_bounds__(LK_THREADS) void k_lknn_select(int64_t n, int L, const double *__restrict__ numerators,
+                                                            const double *__restrict__ denominators,
+                                                            const double *__restrict__ gamma,
+                                                            const unsigned char *__restrict__ seen,
+                                                            double *__restrict__ numer, double *__restrict__ denom,
+                                                            unsigned long long *__restrict__ out_keys,
+                                                            unsigned *__restrict__ out_ids) {
     __shared__ LkTop top;
+    lk_select_body(top, n, L, numerators, denominators, gamma, seen, numer, denom, out_keys, out_ids);
+}
+
+// final_ids != NULL (the last level, one workgroup): the list as node ids, with numer / denom of each as its score
+__device__ __forceinline__ void lk_merge_body(LkTop &top, int n_lists, int L, const unsigned long long *__restrict__ in_keys,
+                                              const unsigned *__restrict__ in_ids, unsigned long long *__restrict__ out_keys,
+                                              unsigned *__restrict__ out_ids, int32_t *__restrict__ final_ids,
+                                              double *__restrict__ final_scores, const double *__restrict__ numer,
+                                              const double *__restrict__ denom) {
     const int t = threadIdx.x;
     lk_init(top);
     int fill = 0;
@@ -364,15 +395,32 @@ __global__ __launch_bounds__(LK_THREADS) void k_lknn_merge(int n_lists, int L, c
     }
 }
 
+__global__ __launch_bounds__(LK_THREADS) void k_lknn_merge(int n_lists, int L, const unsigned long long *__restrict__ in_keys,
+                                                           const unsigned *__restrict__ in_ids,
+                                                           unsigned long long *__restrict__ out_keys,
+                                                           unsigned *__restrict__ out_ids, int32_t *__restrict__ final_ids,
+                                                           double *__restrict__ final_scores,
+                                                           const double *__restrict__ numer,
+                                                           const double *__restrict__ denom) {
+    __shared__ LkTop top;
+    lk_merge_body(top, n_lists, L, in_keys, in_ids, out_keys, out_ids, final_ids, final_scores, numer, denom);
+}
+
 // the one-step branch: value = score, -inf at seen nodes (k_lknn_argmax then is np.nanargmax)
-__global__ __launch_bounds__(LK_THREADS) void k_lknn_score(int64_t n, const double *__restrict__ numerators,
-                                                           const double *__restrict__ denominators,
-                                                           const double *__restrict__ gamma,
-                                                           const unsigned char *__restrict__ seen, double *__restrict__ value) {
+__device__ __forceinline__ void lk_score_body(int64_t n, const double *__restrict__ numerators,
+                                              const double *__restrict__ denominators, const double *__restrict__ gamma,
+                                              const unsigned char *__restrict__ seen, double *__restrict__ value) {
     const int64_t i = (int64_t)blockIdx.x * LK_THREADS + threadIdx.x;
     if (i >= n) return;
     const double nu = seen[i] ? -INFINITY : __dadd_rn(numerators[i], gamma[i]);
     value[i] = __ddiv_rn(nu, __dadd_rn(denominators[i], 1.0));
+}
+
+__global__ __launch_bounds__(LK_THREADS) void k_lknn_score(int64_t n, const double *__restrict__ numerators,
+                                                           const double *__restrict__ denominators,
+                                                           const double *__restrict__ gamma,
+                                                           const unsigned char *__restrict__ seen, double *__restrict__ value) {
+    lk_score_body(n, numerators, denominators, gamma, seen, value);
 }
 
 // predict_proba of a few nodes: (numerators + gamma) / (denominators + 1), seen or not
@@ -405,6 +453,131 @@ __global__ __launch_bounds__(LK_MAX_D) void k_lknn_condition(int m, int D, const
         if (d == 0) seen[id] = 1;
         __syncthreads();  // the next answer may touch the same neighbours
     }
+}
+
+// ---- several handles' steps in one pass (ssw_lknn_step_batch, ssw_lknn_top_remaining_batch) --------------------------
+// One descriptor a slot, in a device table; every kernel of the pass is launched once with the slot on blockIdx.y and
+// runs the single kernel's body on the slot's own buffers.  The table holds the lookahead-2 slots first: the selection,
+// mark, look-ahead and unmark kernels cover those, k_lknn_score_batch the lookahead-1 slots behind them, the block
+// argmax and the finish all of them.
+struct LkSlot {
+    const double *numerators, *denominators, *gamma;
+    const unsigned char *seen;
+    const int32_t *nbr;
+    double *numer, *denom, *value;
+    int32_t *rank_in_list, *list_ids;
+    double *list_scores;
+    unsigned long long *keys_a, *keys_b;
+    unsigned *ids_a, *ids_b;
+    double *blk_v;
+    long long *blk_i;
+    int32_t K, L;        // L: entries of the slot's list (K + D of a step, min(k, unseen) of a top_remaining)
+    int32_t slot;        // the caller's slot: where the results go in the result block
+    int32_t want_list;   // the finish copies list_ids (1) and list_scores too (2) into the result block
+};
+
+// the result block of a pass (device and pinned host copy alike), for `cap` slots: the picks, then the lists
+struct LkBest {
+    double value;
+    long long index;
+};
+__host__ __device__ inline size_t lk_res_ids(int cap) { return (size_t)cap * sizeof(LkBest); }
+__host__ __device__ inline size_t lk_res_scores(int cap) { return lk_res_ids(cap) + (size_t)cap * LK_MAX_LIST * 4; }
+__host__ __device__ inline size_t lk_res_bytes(int cap) { return lk_res_scores(cap) + (size_t)cap * LK_MAX_LIST * 8; }
+
+__global__ __launch_bounds__(LK_THREADS) void k_lknn_select_batch(const LkSlot *__restrict__ tab, int64_t n) {
+    __shared__ LkTop top;
+    const LkSlot &d = tab[blockIdx.y];
+    lk_select_body(top, n, d.L, d.numerators, d.denominators, d.gamma, d.seen, d.numer, d.denom, d.keys_a, d.ids_a);
+}
+
+// from_a: this level reads the slot's keys_a / ids_a and writes the others; last: it writes list_ids / list_scores
+__global__ __launch_bounds__(LK_THREADS) void k_lknn_merge_batch(const LkSlot *__restrict__ tab, int n_lists, int from_a,
+                                                                 int last) {
+    __shared__ LkTop top;
+    const LkSlot &d = tab[blockIdx.y];
+    lk_merge_body(top, n_lists, d.L, from_a ? d.keys_a : d.keys_b, from_a ? d.ids_a : d.ids_b, from_a ? d.keys_b : d.keys_a,
+                  from_a ? d.ids_b : d.ids_a, last ? d.list_ids : (int32_t *)nullptr, d.list_scores, d.numer, d.denom);
+}
+
+__global__ void k_lknn_mark_batch(const LkSlot *__restrict__ tab) {
+    const LkSlot &d = tab[blockIdx.y];
+    lk_mark_body(d.rank_in_list, d.list_ids, d.L);
+}
+
+__global__ void k_lknn_unmark_batch(const LkSlot *__restrict__ tab) {
+    const LkSlot &d = tab[blockIdx.y];
+    lk_unmark_body(d.rank_in_list, d.list_ids, d.L);
+}
+
+__global__ __launch_bounds__(LK_THREADS) void k_lknn_top_sum_batch(const LkSlot *__restrict__ tab, int64_t n, int D) {
+    __shared__ double lscore[LK_MAX_LIST];
+    const LkSlot &d = tab[blockIdx.y];
+    lk_top_sum_body(lscore, n, D, d.K, d.L, d.nbr, d.numer, d.denom, d.list_ids, d.rank_in_list, d.value);
+}
+
+// tab: the first lookahead-1 slot's descriptor
+__global__ __launch_bounds__(LK_THREADS) void k_lknn_score_batch(const LkSlot *__restrict__ tab, int64_t n) {
+    const LkSlot &d = tab[blockIdx.y];
+    lk_score_body(n, d.numerators, d.denominators, d.gamma, d.seen, d.value);
+}
+
+__global__ __launch_bounds__(LK_THREADS) void k_lknn_argmax_batch(const LkSlot *__restrict__ tab, int64_t n) {
+    __shared__ double sv[LK_THREADS];
+    __shared__ long long si[LK_THREADS];
+    const LkSlot &d = tab[blockIdx.y];
+    lk_argmax_body(sv, si, d.value, n, d.blk_v, d.blk_i);
+}
+
+// the lists of a slot into the result block: ids (want_list >= 1) and scores (want_list == 2).  L <= LK_THREADS.
+__device__ inline void lk_collect(const LkSlot &d, unsigned char *__restrict__ res, int cap) {
+    const int t = threadIdx.x;
+    if (t >= d.L || d.want_list == 0) return;
+    ((int32_t *)(res + lk_res_ids(cap)))[(size_t)d.slot * LK_MAX_LIST + t] = d.list_ids[t];
+    if (d.want_list == 2) ((double *)(res + lk_res_scores(cap)))[(size_t)d.slot * LK_MAX_LIST + t] = d.list_scores[t];
+}
+
+// One workgroup a slot: the n_blocks partial results of k_lknn_argmax_batch reduced by the rule the single call's host
+// loop applies to them -- the largest value, the lowest index among equal values; a partial without a candidate (index
+// -1) never wins; none at all gives (0.0, -1).  (value descending, index ascending) is a total order of the partials, so
+// the winner is the same element whatever the order of the reduction.
+__global__ __launch_bounds__(LK_THREADS) void k_lknn_finish_batch(const LkSlot *__restrict__ tab, int n_blocks,
+                                                                  unsigned char *__restrict__ res, int cap) {
+    __shared__ double sv[LK_THREADS];
+    __shared__ long long si[LK_THREADS];
+    const LkSlot &d = tab[blockIdx.y];
+    const int t = threadIdx.x;
+    double bv = 0.0;
+    long long bi = -1;
+    for (int b = t; b < n_blocks; b += LK_THREADS) {
+        const long long oi = d.blk_i[b];
+        const double ov = d.blk_v[b];
+        if (oi < 0) continue;
+        if (bi < 0 || ov > bv || (ov == bv && oi < bi)) bv = ov, bi = oi;
+    }
+    sv[t] = bv;
+    si[t] = bi;
+    __syncthreads();
+    for (int s = LK_THREADS / 2; s >= 1; s >>= 1) {
+        if (t < s) {
+            const double ov = sv[t + s];
+            const long long oi = si[t + s];
+            if (oi >= 0 && (si[t] < 0 || ov > sv[t] || (ov == sv[t] && oi < si[t]))) sv[t] = ov, si[t] = oi;
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        LkBest *best = (LkBest *)res;
+        best[d.slot].value = si[0] < 0 ? 0.0 : sv[0];
+        best[d.slot].index = si[0];
+    }
+    lk_collect(d, res, cap);
+}
+
+// top_remaining: nothing but the lists to bring home
+__global__ __launch_bounds__(LK_THREADS) void k_lknn_collect_batch(const LkSlot *__restrict__ tab, unsigned char *__restrict__ res,
+                                                                   int cap) {
+    lk_collect(tab[blockIdx.y], res, cap);
 }
 
 }  // namespace
@@ -442,6 +615,15 @@ struct ssw_lknn {
     bool timing = false;
     int timed = 0;                         // of the last call: 1 = the selection was timed, 2 = the look-ahead too
     int64_t info[4] = {0, 0, 0, 0};        // of the last step: launches, host waits, bytes up, bytes down
+    // ssw_lknn_step_batch / ssw_lknn_top_remaining_batch: the handle of a call's first slot lends the descriptor table
+    // and the result block (device + pinned host copy), batch_cap slots each, grown on demand; every slot's handle has
+    // the event the pass waits on and keeps the message of its own status
+    LkSlot *batch_tab = nullptr;
+    unsigned char *batch_res = nullptr, *batch_pinned = nullptr;
+    int batch_cap = 0;
+    PinnedStage batch_stage;
+    hipEvent_t batch_ev = nullptr;
+    std::string batch_error;
 };
 
 static constexpr int LK_MAX_ANSWERS = 4096;  // answers of one ssw_lknn_condition, nodes of one ssw_lknn_predict
@@ -459,6 +641,11 @@ ssw_status ssw_lknn_destroy(ssw_lknn *h) {
         (void)hipFree(p);
     h->small_stage.release();
     if (h->pinned) (void)hipHostFree(h->pinned);
+    (void)hipFree(h->batch_tab);
+    (void)hipFree(h->batch_res);
+    h->batch_stage.release();
+    if (h->batch_pinned) (void)hipHostFree(h->batch_pinned);
+    if (h->batch_ev) (void)hipEventDestroy(h->batch_ev);
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -608,6 +795,26 @@ ssw_status wait(ssw_lknn *h) {
     return SSW_OK;
 }
 
+// what a step refuses for this handle, decided on the host (ssw_lknn_step and a slot of ssw_lknn_step_batch alike)
+ssw_status check_step(const ssw_lknn *h, int32_t K, int32_t lookahead) {
+    SSW_REQUIRE(lookahead == 1 || lookahead == 2, "lknn: lookahead=%d (1 or 2)", lookahead);
+    const int64_t unseen = h->n - h->n_seen;
+    const int L = K + h->D;
+    if (lookahead == 2) {
+        SSW_REQUIRE(K >= 1 && K <= 128, "lknn: K=%d outside [1, 128] (the row sum follows numpy's order for one 128-element block)", K);
+        SSW_REQUIRE(L <= LK_MAX_LIST, "lknn: K + D = %d exceeds %d", L, LK_MAX_LIST);
+        SSW_REQUIRE(L <= unseen, "lknn: K + D = %d exceeds the %lld unseen nodes", L, (long long)unseen);
+    } else {
+        SSW_REQUIRE(unseen >= 1, "lknn: no unseen node is left");
+    }
+    return SSW_OK;
+}
+
+ssw_status check_top_remaining(int32_t k) {
+    SSW_REQUIRE(k >= 1 && k <= LK_MAX_LIST, "lknn: top_remaining k=%d outside [1, %d]", k, LK_MAX_LIST);
+    return SSW_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -694,16 +901,9 @@ ssw_status ssw_lknn_step(ssw_lknn *h, int32_t K, int32_t lookahead, int64_t *out
                          double *out_values_or_null, int32_t *out_list_or_null) {
     SSW_REQUIRE(h, "NULL argument");
     SSW_REQUIRE(h->has_state, "lknn: no resident state (ssw_lknn_state_init)");
-    SSW_REQUIRE(lookahead == 1 || lookahead == 2, "lknn: lookahead=%d (1 or 2)", lookahead);
-    const int64_t n = h->n, unseen = n - h->n_seen;
+    SSW_TRY(check_step(h, K, lookahead));
+    const int64_t n = h->n;
     const int L = K + h->D;
-    if (lookahead == 2) {
-        SSW_REQUIRE(K >= 1 && K <= 128, "lknn: K=%d outside [1, 128] (the row sum follows numpy's order for one 128-element block)", K);
-        SSW_REQUIRE(L <= LK_MAX_LIST, "lknn: K + D = %d exceeds %d", L, LK_MAX_LIST);
-        SSW_REQUIRE(L <= unseen, "lknn: K + D = %d exceeds the %lld unseen nodes", L, (long long)unseen);
-    } else {
-        SSW_REQUIRE(unseen >= 1, "lknn: no unseen node is left");
-    }
     DeviceGuard guard(h->device);
     hipStream_t s = h->stream;
     h->info[0] = h->info[1] = h->info[2] = h->info[3] = 0;
@@ -754,7 +954,7 @@ ssw_status ssw_lknn_step(ssw_lknn *h, int32_t K, int32_t lookahead, int64_t *out
 ssw_status ssw_lknn_top_remaining(ssw_lknn *h, int32_t k, int32_t *out_ids, double *out_scores, int32_t *out_count) {
     SSW_REQUIRE(h && out_ids && out_scores && out_count, "NULL argument");
     SSW_REQUIRE(h->has_state, "lknn: no resident state (ssw_lknn_state_init)");
-    SSW_REQUIRE(k >= 1 && k <= LK_MAX_LIST, "lknn: top_remaining k=%d outside [1, %d]", k, LK_MAX_LIST);
+    SSW_TRY(check_top_remaining(k));
     const int64_t unseen = h->n - h->n_seen;
     const int L = (int)std::min<int64_t>(k, unseen);
     h->info[0] = h->info[1] = h->info[2] = h->info[3] = 0;
@@ -832,5 +1032,224 @@ ssw_status ssw_lknn_step_times(ssw_lknn *h, int32_t enable, double *out_ms2_or_n
     h->timing = enable != 0;
     return SSW_OK;
 }
+
+}  // extern "C"
+
+// ---- several handles' steps in one pass ---------------------------------------------------------------------------------
+namespace {
+
+constexpr int LK_MAX_BATCH = SSW_LKNN_MAX_BATCH;
+
+// the whole-call refusals of both batched entries; nothing is read through a handle before every handle is known non-NULL
+ssw_status check_batch(ssw_lknn *const *hs, int32_t n_slots, bool arrays) {
+    SSW_REQUIRE(n_slots >= 1 && n_slots <= LK_MAX_BATCH, "lknn batch: n_slots=%d outside [1, %d]", n_slots, LK_MAX_BATCH);
+    SSW_REQUIRE(hs != nullptr && arrays, "NULL argument");
+    for (int j = 0; j < n_slots; ++j) SSW_REQUIRE(hs[j] != nullptr, "lknn batch: handle %d is NULL", j);
+    for (int j = 0; j < n_slots; ++j) {
+        for (int i = 0; i < j; ++i) SSW_REQUIRE(hs[i] != hs[j], "lknn batch: handle %d repeats handle %d", j, i);
+        SSW_REQUIRE(hs[j]->has_state, "lknn batch: handle %d has no resident state (ssw_lknn_state_init)", j);
+        SSW_REQUIRE(hs[j]->device == hs[0]->device && hs[j]->n == hs[0]->n && hs[j]->D == hs[0]->D,
+                    "lknn batch: handle %d (device %d, n=%lld, D=%d) differs from handle 0 (device %d, n=%lld, D=%d)", j,
+                    hs[j]->device, (long long)hs[j]->n, hs[j]->D, hs[0]->device, (long long)hs[0]->n, hs[0]->D);
+    }
+    return SSW_OK;
+}
+
+void refuse_slot(ssw_lknn *h, ssw_status rc, int32_t *out_status) {
+    *out_status = rc;
+    const char *msg = ssw_last_error();
+    h->batch_error = msg ? msg : "";
+}
+
+LkSlot describe(ssw_lknn *h, int slot, int K, int L, int want_list) {
+    LkSlot d;
+    d.numerators = h->numerators, d.denominators = h->denominators, d.gamma = h->gamma, d.seen = h->seen, d.nbr = h->nbr;
+    d.numer = h->numer, d.denom = h->denom, d.value = h->value;
+    d.rank_in_list = h->rank_in_list, d.list_ids = h->list_ids, d.list_scores = h->list_scores;
+    d.keys_a = h->keys_a, d.keys_b = h->keys_b, d.ids_a = h->ids_a, d.ids_b = h->ids_b;
+    d.blk_v = h->blk_v, d.blk_i = h->blk_i;
+    d.K = K, d.L = L, d.slot = slot, d.want_list = want_list;
+    return d;
+}
+
+// the first handle's table and result block for n_slots slots; the table goes up; the pass waits for every other
+// handle's stream (answers enqueued there must be seen)
+ssw_status begin_pass(ssw_lknn *const *hs, int32_t n_slots, const std::vector<LkSlot> &tab) {
+    ssw_lknn *h0 = hs[0];
+    if (n_slots > h0->batch_cap) {  // nothing of an earlier pass is in flight: every pass ends with a wait
+        (void)hipFree(h0->batch_tab);
+        (void)hipFree(h0->batch_res);
+        if (h0->batch_pinned) (void)hipHostFree(h0->batch_pinned);
+        h0->batch_tab = nullptr, h0->batch_res = nullptr, h0->batch_pinned = nullptr, h0->batch_cap = 0;
+        int cap = 16;
+        while (cap < n_slots) cap <<= 1;
+        SSW_HIP_TRY(hipMalloc((void **)&h0->batch_tab, (size_t)cap * sizeof(LkSlot)));
+        SSW_HIP_TRY(hipMalloc((void **)&h0->batch_res, lk_res_bytes(cap)));
+        SSW_HIP_TRY(hipHostMalloc((void **)&h0->batch_pinned, lk_res_bytes(cap), hipHostMallocDefault));
+        h0->batch_cap = cap;
+    }
+    for (int j = 1; j < n_slots; ++j) {
+        if (!hs[j]->batch_ev) SSW_HIP_TRY(hipEventCreateWithFlags(&hs[j]->batch_ev, hipEventDisableTiming));
+        SSW_HIP_TRY(hipEventRecord(hs[j]->batch_ev, hs[j]->stream));
+        SSW_HIP_TRY(hipStreamWaitEvent(h0->stream, hs[j]->batch_ev, 0));
+    }
+    h0->info[0] = h0->info[1] = h0->info[2] = h0->info[3] = 0;
+    h0->timed = 0;
+    SSW_TRY(h0->batch_stage.push(h0->batch_tab, tab.data(), tab.size() * sizeof(LkSlot), h0->stream));
+    h0->info[2] += (int64_t)(tab.size() * sizeof(LkSlot));
+    return SSW_OK;
+}
+
+// the state pass and the merge levels of the table's first n2 slots (enqueue_select, slot on blockIdx.y)
+ssw_status enqueue_select_batch(ssw_lknn *h0, int n2) {
+    hipStream_t s = h0->stream;
+    hipLaunchKernelGGL(k_lknn_select_batch, dim3((unsigned)h0->n_slices, (unsigned)n2), dim3(LK_THREADS), 0, s, h0->batch_tab, h0->n);
+    ++h0->info[0];
+    int lists = h0->n_slices;
+    bool from_a = true;
+    do {
+        const int out = (lists + LK_FAN - 1) / LK_FAN;
+        hipLaunchKernelGGL(k_lknn_merge_batch, dim3((unsigned)out, (unsigned)n2), dim3(LK_THREADS), 0, s, h0->batch_tab, lists,
+                           from_a ? 1 : 0, out == 1 ? 1 : 0);
+        ++h0->info[0];
+        lists = out;
+        from_a = !from_a;
+    } while (lists > 1);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+ssw_status ssw_lknn_step_batch(ssw_lknn *const *hs, int32_t n_slots, const int32_t *K, const int32_t *lookahead,
+                               int64_t *out_best_idx, double *out_best_value, double *const *out_values_or_null,
+                               int32_t *out_lists_or_null, int32_t *out_status, int64_t *out_stats4_or_null) {
+    SSW_TRY(check_batch(hs, n_slots, K && lookahead && out_best_idx && out_best_value && out_status));
+    ssw_lknn *h0 = hs[0];
+    const int64_t n = h0->n;
+    // per slot, on the host: refused, or a descriptor -- the lookahead-2 slots first
+    std::vector<LkSlot> tab, ones;
+    for (int j = 0; j < n_slots; ++j) {
+        hs[j]->batch_error.clear();
+        out_status[j] = SSW_OK;
+        out_best_idx[j] = -1, out_best_value[j] = 0.0;
+        const ssw_status rc = check_step(hs[j], K[j], lookahead[j]);
+        if (rc != SSW_OK) {
+            refuse_slot(hs[j], rc, &out_status[j]);
+            continue;
+        }
+        if (lookahead[j] == 2) tab.push_back(describe(hs[j], j, K[j], K[j] + hs[j]->D, out_lists_or_null ? 1 : 0));
+        else ones.push_back(describe(hs[j], j, K[j], 0, 0));
+    }
+    const int n2 = (int)tab.size(), n1 = (int)ones.size(), active = n2 + n1;
+    tab.insert(tab.end(), ones.begin(), ones.end());
+    if (out_stats4_or_null) out_stats4_or_null[0] = out_stats4_or_null[1] = out_stats4_or_null[2] = out_stats4_or_null[3] = 0;
+    if (active == 0) return SSW_OK;
+    DeviceGuard guard(h0->device);
+    SSW_TRY(begin_pass(hs, n_slots, tab));
+    hipStream_t s = h0->stream;
+    const unsigned row_blocks = (unsigned)((n + LK_THREADS - 1) / LK_THREADS);
+    if (n2) {
+        if (h0->timing) SSW_HIP_TRY(hipEventRecord(h0->ev[0], s));
+        SSW_TRY(enqueue_select_batch(h0, n2));
+        if (h0->timing) SSW_HIP_TRY(hipEventRecord(h0->ev[1], s));
+        hipLaunchKernelGGL(k_lknn_mark_batch, dim3(1, (unsigned)n2), dim3(LK_THREADS), 0, s, h0->batch_tab);
+        if (h0->timing) SSW_HIP_TRY(hipEventRecord(h0->ev[2], s));
+        hipLaunchKernelGGL(k_lknn_top_sum_batch, dim3(row_blocks, (unsigned)n2), dim3(LK_THREADS), 0, s, h0->batch_tab, n, h0->D);
+        if (h0->timing) SSW_HIP_TRY(hipEventRecord(h0->ev[3], s));
+        hipLaunchKernelGGL(k_lknn_unmark_batch, dim3(1, (unsigned)n2), dim3(LK_THREADS), 0, s, h0->batch_tab);
+        h0->info[0] += 3;
+        h0->timed = h0->timing ? 3 : 0;
+    }
+    if (n1) {
+        hipLaunchKernelGGL(k_lknn_score_batch, dim3(row_blocks, (unsigned)n1), dim3(LK_THREADS), 0, s, h0->batch_tab + n2, n);
+        ++h0->info[0];
+    }
+    hipLaunchKernelGGL(k_lknn_argmax_batch, dim3((unsigned)h0->argmax_blocks, (unsigned)active), dim3(LK_THREADS), 0, s, h0->batch_tab, n);
+    hipLaunchKernelGGL(k_lknn_finish_batch, dim3(1, (unsigned)active), dim3(LK_THREADS), 0, s, h0->batch_tab, h0->argmax_blocks,
+                       h0->batch_res, h0->batch_cap);
+    h0->info[0] += 2;
+    SSW_HIP_TRY(hipGetLastError());
+    const int cap = h0->batch_cap;
+    SSW_TRY(copy_down(h0, h0->batch_pinned, h0->batch_res, (size_t)n_slots * sizeof(LkBest)));
+    if (out_lists_or_null && n2)
+        SSW_TRY(copy_down(h0, h0->batch_pinned + lk_res_ids(cap), h0->batch_res + lk_res_ids(cap), (size_t)n_slots * LK_MAX_LIST * 4));
+    if (out_values_or_null)
+        for (const LkSlot &d : tab)
+            if (out_values_or_null[d.slot]) SSW_TRY(copy_down(h0, out_values_or_null[d.slot], d.value, (size_t)n * 8));
+    SSW_TRY(wait(h0));
+    const LkBest *best = (const LkBest *)h0->batch_pinned;
+    const int32_t *lists = (const int32_t *)(h0->batch_pinned + lk_res_ids(cap));
+    for (const LkSlot &d : tab) {
+        out_best_idx[d.slot] = best[d.slot].index;
+        out_best_value[d.slot] = best[d.slot].value;
+        if (out_lists_or_null && d.L) memcpy(out_lists_or_null + (size_t)d.slot * LK_MAX_LIST, lists + (size_t)d.slot * LK_MAX_LIST, (size_t)d.L * 4);
+        ssw_lknn *h = hs[d.slot];
+        if (h != h0) {
+            for (int q = 0; q < 4; ++q) h->info[q] = h0->info[q];
+            h->timed = 0;
+        }
+    }
+    if (out_stats4_or_null)
+        for (int q = 0; q < 4; ++q) out_stats4_or_null[q] = h0->info[q];
+    return SSW_OK;
+}
+
+ssw_status ssw_lknn_top_remaining_batch(ssw_lknn *const *hs, int32_t n_slots, const int32_t *k, int32_t *out_ids,
+                                        double *out_scores, int32_t *out_counts, int32_t *out_status) {
+    SSW_TRY(check_batch(hs, n_slots, k && out_ids && out_scores && out_counts && out_status));
+    ssw_lknn *h0 = hs[0];
+    std::vector<LkSlot> tab;
+    for (int j = 0; j < n_slots; ++j) {
+        hs[j]->batch_error.clear();
+        out_status[j] = SSW_OK;
+        out_counts[j] = 0;
+        const ssw_status rc = check_top_remaining(k[j]);
+        if (rc != SSW_OK) {
+            refuse_slot(hs[j], rc, &out_status[j]);
+            continue;
+        }
+        const int L = (int)std::min<int64_t>(k[j], hs[j]->n - hs[j]->n_seen);
+        out_counts[j] = L;
+        if (L == 0) {  // as the single call: nothing to do, and that is what its info says
+            hs[j]->info[0] = hs[j]->info[1] = hs[j]->info[2] = hs[j]->info[3] = 0;
+            hs[j]->timed = 0;
+            continue;
+        }
+        tab.push_back(describe(hs[j], j, 0, L, 2));
+    }
+    const int active = (int)tab.size();
+    if (active == 0) return SSW_OK;
+    DeviceGuard guard(h0->device);
+    SSW_TRY(begin_pass(hs, n_slots, tab));
+    hipStream_t s = h0->stream;
+    if (h0->timing) SSW_HIP_TRY(hipEventRecord(h0->ev[0], s));
+    SSW_TRY(enqueue_select_batch(h0, active));
+    if (h0->timing) SSW_HIP_TRY(hipEventRecord(h0->ev[1], s));
+    h0->timed = h0->timing ? 1 : 0;
+    hipLaunchKernelGGL(k_lknn_collect_batch, dim3(1, (unsigned)active), dim3(LK_THREADS), 0, s, h0->batch_tab, h0->batch_res, h0->batch_cap);
+    ++h0->info[0];
+    SSW_HIP_TRY(hipGetLastError());
+    const int cap = h0->batch_cap;
+    SSW_TRY(copy_down(h0, h0->batch_pinned + lk_res_ids(cap), h0->batch_res + lk_res_ids(cap), (size_t)n_slots * LK_MAX_LIST * 4));
+    SSW_TRY(copy_down(h0, h0->batch_pinned + lk_res_scores(cap), h0->batch_res + lk_res_scores(cap), (size_t)n_slots * LK_MAX_LIST * 8));
+    SSW_TRY(wait(h0));
+    const int32_t *ids = (const int32_t *)(h0->batch_pinned + lk_res_ids(cap));
+    const double *scores = (const double *)(h0->batch_pinned + lk_res_scores(cap));
+    for (const LkSlot &d : tab) {
+        memcpy(out_ids + (size_t)d.slot * LK_MAX_LIST, ids + (size_t)d.slot * LK_MAX_LIST, (size_t)d.L * 4);
+        memcpy(out_scores + (size_t)d.slot * LK_MAX_LIST, scores + (size_t)d.slot * LK_MAX_LIST, (size_t)d.L * 8);
+        ssw_lknn *h = hs[d.slot];
+        if (h != h0) {
+            for (int q = 0; q < 4; ++q) h->info[q] = h0->info[q];
+            h->timed = 0;
+        }
+    }
+    return SSW_OK;
+}
+
+const char *ssw_lknn_batch_error(const ssw_lknn *h) { return h ? h->batch_error.c_str() : ""; }
 
 }  // extern "C"

@@ -353,6 +353,80 @@ class DeviceLKNNModel(ProbabilityModel):
                   ctypes.c_void_p(scores.ctypes.data), ctypes.byref(count))
         return ids[:count.value].astype(np.int64), scores[:count.value]
 
+    # ---- several models in one call ------------------------------------------------------------
+    MAX_BATCH = 256  # SSW_LKNN_MAX_BATCH
+    last_batch_stats = None  # of the last step_batch: launches, host_waits, bytes_to_device, bytes_to_host
+
+    @staticmethod
+    def _handles(models):
+        hs = (ctypes.c_void_p * len(models))(*[m._h for m in models])
+        return hs
+
+    @staticmethod
+    def _slot_error(model, status):
+        msg = _lib.load().ssw_lknn_batch_error(model._h)
+        return _lib.SeesawHipError(int(status), msg.decode("utf-8", "replace") if msg else "")
+
+    @staticmethod
+    def step_batch(models, Ks, lookaheads, return_values: bool = False, return_list: bool = False):
+        """`[m.step(K, lookahead, ...) for m, K, lookahead in zip(models, Ks, lookaheads)]` in one call with one host wait
+        (ssw_lknn_step_batch): one entry per model, what `step` returns or the SeesawHipError it would have raised.  The
+        models are distinct and share device, node count and degree (otherwise the call raises and nothing ran)."""
+        models = list(models)
+        S = len(models)
+        Ks = np.ascontiguousarray([int(k) for k in Ks], dtype=np.int32)
+        lookaheads = np.ascontiguousarray([int(a) for a in lookaheads], dtype=np.int32)
+        assert Ks.shape == (S,) and lookaheads.shape == (S,)
+        hs = DeviceLKNNModel._handles(models)
+        values = [np.empty(m.n, dtype=np.float64) for m in models] if return_values else None
+        value_ptrs = (ctypes.c_void_p * S)(*[v.ctypes.data for v in values]) if return_values else None
+        lists = np.full((S, DeviceLKNNModel.KERNEL_MAX_LIST), -1, dtype=np.int32) if return_list else None
+        best_i, best_v = np.full(S, -1, dtype=np.int64), np.zeros(S, dtype=np.float64)
+        status, stats = np.zeros(S, dtype=np.int32), np.zeros(4, dtype=np.int64)
+        _lib.call("ssw_lknn_step_batch", hs, S, ctypes.c_void_p(Ks.ctypes.data), ctypes.c_void_p(lookaheads.ctypes.data),
+                  ctypes.c_void_p(best_i.ctypes.data), ctypes.c_void_p(best_v.ctypes.data), value_ptrs,
+                  None if lists is None else ctypes.c_void_p(lists.ctypes.data), ctypes.c_void_p(status.ctypes.data),
+                  ctypes.c_void_p(stats.ctypes.data))
+        DeviceLKNNModel.last_batch_stats = dict(launches=int(stats[0]), host_waits=int(stats[1]), bytes_to_device=int(stats[2]),
+                                                bytes_to_host=int(stats[3]))
+        out = []
+        for j, m in enumerate(models):
+            if status[j] != _lib.SSW_OK:
+                out.append(DeviceLKNNModel._slot_error(m, status[j]))
+                continue
+            entry = (int(best_i[j]), float(best_v[j]))
+            if return_values:
+                entry += (values[j],)
+            if return_list:
+                entry += (lists[j, :int(Ks[j]) + m.degree].copy() if lookaheads[j] == 2 else None,)
+            out.append(entry)
+        return out
+
+    @staticmethod
+    def top_k_remaining_batch(models, top_ks):
+        """`[m.top_k_remaining(k) for m, k in zip(models, top_ks)]` in one call with one host wait
+        (ssw_lknn_top_remaining_batch): one entry per model, (ids, scores) or the error that call would have raised"""
+        models = list(models)
+        S = len(models)
+        ks = np.ascontiguousarray([int(k) for k in top_ks], dtype=np.int32)
+        assert ks.shape == (S,)
+        hs = DeviceLKNNModel._handles(models)
+        ids = np.empty((S, DeviceLKNNModel.KERNEL_MAX_LIST), dtype=np.int32)
+        scores = np.empty((S, DeviceLKNNModel.KERNEL_MAX_LIST), dtype=np.float64)
+        counts, status = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int32)
+        _lib.call("ssw_lknn_top_remaining_batch", hs, S, ctypes.c_void_p(ks.ctypes.data), ctypes.c_void_p(ids.ctypes.data),
+                  ctypes.c_void_p(scores.ctypes.data), ctypes.c_void_p(counts.ctypes.data), ctypes.c_void_p(status.ctypes.data))
+        out = []
+        for j, m in enumerate(models):
+            if status[j] != _lib.SSW_OK:
+                if not 1 <= ks[j] <= DeviceLKNNModel.KERNEL_MAX_LIST:  # what top_k_remaining raises before the library is asked
+                    out.append(ValueError(f"top_k={int(ks[j])}: the device-resident model lists 1..{DeviceLKNNModel.KERNEL_MAX_LIST} nodes"))
+                else:
+                    out.append(DeviceLKNNModel._slot_error(m, status[j]))
+                continue
+            out.append((ids[j, :counts[j]].astype(np.int64), scores[j, :counts[j]].copy()))
+        return out
+
     def predict_proba(self, idxs) -> np.ndarray:
         idxs = np.ascontiguousarray(np.asarray(idxs, dtype=np.int64).reshape(-1))
         out = np.empty(idxs.shape[0], dtype=np.float64)

@@ -12,7 +12,7 @@ import scipy.sparse as sp
 
 from ..calibration import FixedCalibrator
 from ..research.active_search.common import Dataset
-from ..research.active_search.efficient_nonmyopic_search import efficient_nonmyopic_search
+from ..research.active_search.efficient_nonmyopic_search import efficient_nonmyopic_search, efficient_nonmyopic_search_batch
 from .graph_based import get_label_prop
 from .LKNN_model import DeviceLKNNModel, LKNNModel, initial_gamma_array
 from .loop_base import LoopBase
@@ -92,9 +92,7 @@ class ActiveSearch(LoopBase):
 
     def next_batch(self):
         opts = self.params.interactive_options
-        remaining = opts["max_steps"] - len(self.q.returned) if opts["adjust_horizon"] else math.inf
-        horizon = int(min(opts["reward_horizon"], remaining))
-        assert horizon > 0, "need a non-negative horizon for reward to be defined"
+        horizon = self._horizon()
         res = efficient_nonmyopic_search(self.prob_model, reward_horizon=horizon, lookahead_limit=min(2, horizon),
                                          pruning_on=opts["pruning_on"], implementation=opts["implementation"])
         print(f"{res.index=}, {res.value=}")
@@ -103,6 +101,41 @@ class ActiveSearch(LoopBase):
         ans = {"dbidxs": abs_idx, "activations": None}
         self.q.returned.update(ans["dbidxs"])
         return ans
+
+    def _horizon(self):
+        opts = self.params.interactive_options
+        remaining = opts["max_steps"] - len(self.q.returned) if opts["adjust_horizon"] else math.inf
+        horizon = int(min(opts["reward_horizon"], remaining))
+        assert horizon > 0, "need a non-negative horizon for reward to be defined"
+        return horizon
+
+    @classmethod
+    def next_batch_group(cls, loops):
+        """`[l.next_batch() for l in loops]` with ONE planning call (ssw_lknn_step_batch) for loops whose models are
+        DeviceLKNNModels of one device, node count and degree: every loop's horizon is worked out (and asserted) on the
+        host first, then one call plans for all, then every loop prints, records and returns as its own `next_batch`.
+        A loop whose slot the library refused surfaces its error after the other loops have been served."""
+        loops = list(loops)
+        if not loops:
+            return []
+        horizons = [l._horizon() for l in loops]
+        results = efficient_nonmyopic_search_batch([l.prob_model for l in loops], horizons, [min(2, t) for t in horizons],
+                                                   return_errors=True)
+        out, failed = [], None
+        for l, res in zip(loops, results):
+            if isinstance(res, Exception):
+                failed = failed or res
+                out.append(None)
+                continue
+            print(f"{res.index=}, {res.value=}")
+            l.pruned_fractions.append(res.pruned_fraction)
+            abs_idx = l.q.index.vector_meta["dbidx"].iloc[np.array([int(res.index)])].values
+            ans = {"dbidxs": abs_idx, "activations": None}
+            l.q.returned.update(ans["dbidxs"])
+            out.append(ans)
+        if failed is not None:
+            raise failed
+        return out
 
     def refine(self, change=None):
         assert change is not None
@@ -151,6 +184,31 @@ class LKNNSearch(LoopBase):
         ans = {"dbidxs": abs_idx, "activations": None}
         self.q.returned.update(ans["dbidxs"])
         return ans
+
+    @classmethod
+    def next_batch_group(cls, loops):
+        """`[l.next_batch() for l in loops]` with ONE ssw_lknn_top_remaining_batch call for loops whose models are
+        DeviceLKNNModels of one device, node count and degree.  A loop whose slot failed surfaces its error after the
+        other loops have been served."""
+        loops = list(loops)
+        if not loops:
+            return []
+        entries = DeviceLKNNModel.top_k_remaining_batch([l.prob_model for l in loops], [1] * len(loops))
+        out, failed = [], None
+        for l, entry in zip(loops, entries):
+            if isinstance(entry, Exception):
+                failed = failed or entry
+                out.append(None)
+                continue
+            vec_idx, _ = entry
+            print(f"{vec_idx=}")
+            abs_idx = l.q.index.vector_meta["dbidx"].iloc[vec_idx].values
+            ans = {"dbidxs": abs_idx, "activations": None}
+            l.q.returned.update(ans["dbidxs"])
+            out.append(ans)
+        if failed is not None:
+            raise failed
+        return out
 
     def refine(self, change=None):
         assert change is not None

@@ -85,3 +85,23 @@ def efficient_nonmyopic_search(model: ProbabilityModel, *, reward_horizon: int, 
     assert implementation == "loop", implementation
     return _opt_expected_utility_helper(i=0, lookahead_limit=lookahead_limit, t=reward_horizon, model=model,
                                         pruning_on=pruning_on)
+
+
+def efficient_nonmyopic_search_batch(models, reward_horizons, lookahead_limits, return_errors: bool = False):
+    """`efficient_nonmyopic_search(model, reward_horizon=..., lookahead_limit=..., pruning_on=False,
+    implementation='vectorized')` for several device-resident models in ONE ssw_lknn_step_batch call: a list of Result.
+    The single function's assertions run for every member before the call; a member the library refuses raises its
+    error (the first such member's) after the call -- or, with return_errors, has that error as its entry."""
+    models, reward_horizons, lookahead_limits = list(models), list(reward_horizons), list(lookahead_limits)
+    assert len(models) == len(reward_horizons) == len(lookahead_limits)
+    for model, reward_horizon, lookahead_limit in zip(models, reward_horizons, lookahead_limits):
+        assert getattr(model, "device_resident", False), "the batched search serves device-resident models only"
+        assert reward_horizon > 0
+        assert 1 <= lookahead_limit <= 2, "implementation assumes at most 1 lookahead (pruning)"
+        assert lookahead_limit <= reward_horizon
+    entries = type(models[0]).step_batch(models, [t - 1 for t in reward_horizons], lookahead_limits)
+    for entry in entries:
+        if isinstance(entry, Exception) and not return_errors:
+            raise entry
+    return [entry if isinstance(entry, Exception) else Result(value=entry[1], index=entry[0], pruned_fraction=0.0)
+            for entry in entries]

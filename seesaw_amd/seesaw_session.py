@@ -257,7 +257,9 @@ class SessionGroup:
       `shortlist_size`, `agg_method` and `aug_larger` are served by ONE `index.query_batch` -- one pass over the rows;
       a started `MultiRegNeg` whose `next_batch` is the class's own joins that group with `vector = curr_vec` and
       `vector2 = confusion_vec if discount_neg else zeros(dim)` (`query_batch(vectors2=...)`: one more launch for all
-      of them); every other session calls its own `next()`.
+      of them); the started `ActiveSearch` / `LKNNSearch` loops whose model is on the device (`planning_groups`, from the
+      `MIN_LKNN_GROUP` / `MIN_ACTIVE_SEARCH_GROUP` members on; `None` = never) plan through ONE `next_batch_group` -- one pass of kernels,
+      one host wait -- before the other sessions; every other session calls its own `next()`.
     * `refine()`: every session's start-policy gate runs as in `LoopBase.refine_external`; the started `MultiReg`
       loops go through ONE `MultiReg.refine_batch` -- one launch, one host wait -- and the started `MultiRegNeg` loops
       whose options say `fit_on_device` through ONE `MultiRegNeg.refine_batch`, a launch of their own; the started
@@ -381,12 +383,75 @@ class SessionGroup:
             by_key.setdefault((id(index), loop.params.shortlist_size), []).append(i)
         return [tuple(g) for g in by_key.values()]
 
+    # A group of active-search loops plans through `next_batch_group` from this many members on; None: never.  Per loop
+    # class, read from profiles/lknn_step_batch_ab.txt (tools/perf_lknn_batch.py): the smallest S at which the batch is
+    # ahead of the loop of single calls by more than both interquartile ranges at EVERY measured graph size (3000, 50 000,
+    # 200 000 and 1.56 M nodes; us per session-step, median [interquartile range], loop against batch).
+    # lknn at 2 sessions: 77.0 [1.6] / 56.7 [1.9] at 3000 nodes, 78.3 [2.1] / 57.1 [1.6], 83.7 [1.1] / 57.6 [1.1] and
+    # 97.3 [1.5] / 72.1 [1.8] at 1.56 M -- the launches and the wait shared; 102.0 / 40.3 at 16 sessions.
+    MIN_LKNN_GROUP = 2
+    # active_search (horizon 5) at 2 sessions: 116.5 [3.4] / 81.9 [6.4] at 3000 nodes, 141.9 [1.0] / 105.1 [3.2],
+    # 233.1 [2.8] / 199.2 [3.0] and, at 1.56 M nodes, 1582.2 [3.3] / 1574.2 [7.3]: ahead by 8.0 against a spread of 7.3, the
+    # narrowest case of the sweep -- there the look-ahead kernel is 1.44 of the 1.58 ms and takes S times as long for S
+    # slots, so what the batch saves (8 us a step at 2 sessions, 19 at 4, 52 at 16) is the launches and the wait alone.
+    MIN_ACTIVE_SEARCH_GROUP = 2
+
+    def min_planning_group(self, loop):
+        """the smallest group of `loop`'s class that `next()` serves through `next_batch_group` (None: none)"""
+        from .loops.active_search import LKNNSearch
+        return self.MIN_LKNN_GROUP if type(loop) is LKNNSearch else self.MIN_ACTIVE_SEARCH_GROUP
+
+    def planning_groups(self):
+        """[(session positions, ...)]: the started loops that are exactly an `ActiveSearch` or an `LKNNSearch`, whose
+        `next_batch` and `next_batch_external` are the class's own and whose `prob_model` is a `DeviceLKNNModel`, grouped
+        by (class, device, node count, degree) in session order -- what one `next_batch_group` can serve.  Groups of one
+        are listed too; `next()` serves a group from `min_planning_group` members on."""
+        from .loops.active_search import ActiveSearch, LKNNSearch
+        from .loops.LKNN_model import DeviceLKNNModel
+        from .loops.loop_base import LoopBase
+        by_key = {}
+        for i, s in enumerate(self.sessions):
+            loop = s.loop
+            cls = type(loop)
+            if cls not in (ActiveSearch, LKNNSearch) or not loop.started or \
+                    cls.next_batch_external is not LoopBase.next_batch_external:
+                continue
+            model = getattr(loop, "prob_model", None)
+            if not isinstance(model, DeviceLKNNModel):
+                continue
+            by_key.setdefault((cls, model.device, model.n, model.degree), []).append(i)
+        return [tuple(g) for g in by_key.values()]
+
+    def _next_planned(self, group, out):
+        """one `next_batch_group` for the sessions of `group`, with `Session.next`'s bookkeeping for each"""
+        members = [self.sessions[i] for i in group]
+        for s in members:
+            s._log("next.start")
+            print("start met. next batch from custom method...")
+        start = time.time()
+        results = type(members[0].loop).next_batch_group([s.loop for s in members])
+        elapsed = time.time() - start
+        for i, s, r in zip(group, members, results):
+            s.timing.append(elapsed)
+            s.acc_indices.append(r["dbidxs"])
+            s.acc_activations.append(r["activations"])
+            s._log("next.end")
+            out[i] = r["dbidxs"]
+
     # ---- the two halves of a round ----------------------------------------------------------------------------
     def next(self):
         """`[s.next() for s in sessions]`"""
         out = [None] * len(self.sessions)
+        planned = set()
+        for group in self.planning_groups():
+            least = self.min_planning_group(self.sessions[group[0]].loop)
+            if least is not None and len(group) >= max(2, least):
+                self._next_planned(group, out)
+                planned.update(group)
         for group in self.query_groups():
             if len(group) == 1:
+                if group[0] in planned:
+                    continue
                 out[group[0]] = self.sessions[group[0]].next()
                 continue
             members = [self.sessions[i] for i in group]
