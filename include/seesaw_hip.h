@@ -96,11 +96,12 @@ ssw_status ssw_index_destroy(ssw_index *idx);
  * Work on a view: shape, dtype, set_stream, sync, scan, scan_dev, load_scores, topk (small and general form),
  * set_excluded, topk_dev, select_deep_dev, result_ptrs, topk_fetch, gather_scores, set_tile_meta, rescore_avg,
  * rescore_avg_f64, profile, profile_read, prune_stats / prune_completions ("not pruned"), ssw_labelprop_scores_to_index,
- * ssw_labelprop_round; ssw_index_device_ptrs hands out the view's score buffer and a NULL row pointer;
+ * ssw_labelprop_round, and the batched entries of its own, ssw_index_view_scan_batch / _view_topk_batch /
+ * _view_topk_batch_avg; ssw_index_device_ptrs hands out the view's score buffer and a NULL row pointer;
  * ssw_index_score_rows, ssw_index_gather_rows and ssw_fb_set_data_from_index take VIEW rows and translate them;
  * ssw_index_coarse_mean reads a view as its SOURCE through the row table (and refuses one as its destination).
  * Refused on a view with SSW_ERR_UNSUPPORTED (the message says "view") before anything is touched: upload, upload_f16,
- * download, fill_random, set_row2image, every *_batch* entry, topk_slot_deep_dev, stage2_avg_batch_dev, both exchange
+ * download, fill_random, set_row2image, every *_batch* entry without `view_` in its name, topk_slot_deep_dev, stage2_avg_batch_dev, both exchange
  * target setters, ssw_knn_build, ssw_xlx, ssw_fb_set_pseudo_sample_from_index, and a view of a view.
  * Lifetime: the parent counts its live views; ssw_index_destroy(parent) with live views is SSW_ERR_INVALID and leaves
  * the parent intact.  Destroy the views first.  A view's members are the rows the parent's image map gave those images
@@ -347,6 +348,27 @@ ssw_status ssw_index_topk_batch_avg_pruned(ssw_index *idx, const float *q_host, 
                                            const int64_t *excluded_offsets, int32_t k, int32_t aug_larger,
                                            int64_t *out_images, float *out_scores, int64_t *out_best_rows,
                                            float *out_avg_scores, int64_t *out_avg_rows, int32_t *out_counts);
+
+/* The batched scan, top-k and two-stage top-k of a VIEW (ssw_index_create_view): ssw_index_scan_batch,
+ * ssw_index_topk_batch and ssw_index_topk_batch_avg over the member rows, read in place out of the parent's matrix
+ * ONCE per chunk of queries (the multi-query scan with the view's row table, 4 more bytes a row a chunk).  Signatures,
+ * validation, per-query exclusion lists, chunk widths, the deep rerun on mass ties, out_counts, the side buffer and the
+ * errors are those of the plain entries; a view of fewer than 65 536 rows is served by one single-query scan of the
+ * view per query.  Query b's outputs are the bits of the view's ssw_index_scan / ssw_index_topk (/ ssw_index_rescore_avg
+ * over the view's own tile meta) for q[b], which are those of a copied subset index of the member rows.  There is no
+ * pruned form: a view holds no shadow.  State afterwards: that of ssw_index_topk on the view with the last query --
+ * its resident scores are the last query's and are not partial.  The side slabs and the query block belong to the view
+ * handle and go with it in ssw_index_destroy; the parent is read only, and sees nothing of the call.
+ * Each entry takes a view only: any other handle is SSW_ERR_INVALID (the message names the entry), as are NULL
+ * arguments, before anything is touched.  The plain entries keep refusing a view. */
+ssw_status ssw_index_view_scan_batch(ssw_index *view, const float *q_host, int32_t nq, float *out_scores_host);
+ssw_status ssw_index_view_topk_batch(ssw_index *view, const float *q_host, int32_t nq, const int64_t *excluded_images,
+                                     const int64_t *excluded_offsets, int32_t k, int64_t *out_images, float *out_scores,
+                                     int64_t *out_best_rows, int32_t *out_counts);
+ssw_status ssw_index_view_topk_batch_avg(ssw_index *view, const float *q_host, int32_t nq, const int64_t *excluded_images,
+                                         const int64_t *excluded_offsets, int32_t k, int32_t aug_larger,
+                                         int64_t *out_images, float *out_scores, int64_t *out_best_rows,
+                                         float *out_avg_scores, int64_t *out_avg_rows, int32_t *out_counts);
 
 /* The SECOND STAGE of a batch of TWO-VECTOR queries (`query(vector=, vector2=)`, seesaw/indices/multiscale/
  * multiscale_index.py:341-352: `scores = vectors[ilocs] @ vector`, `scores -= vectors[ilocs] @ vector2`, then

@@ -75,6 +75,11 @@ _SIGNATURES = {
                                          c_void_p, c_void_p, c_void_p, c_void_p]),
     "ssw_index_topk_batch_avg_pruned": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_i32, c_void_p,
                                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ssw_index_view_scan_batch": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p]),
+    "ssw_index_view_topk_batch": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p, c_void_p,
+                                          c_void_p, c_void_p]),
+    "ssw_index_view_topk_batch_avg": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_i32, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ssw_index_set_excluded": (c_i32, [c_void_p, c_void_p, c_i64]),
     "ssw_index_topk_dev": (c_i32, [c_void_p, c_void_p, c_i32]),
     "ssw_index_set_tile_meta": (c_i32, [c_void_p, c_void_p, c_void_p]),

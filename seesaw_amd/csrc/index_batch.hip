@@ -1,4 +1,5 @@
-// index_batch.hip -- several queries in one pass over the index's rows (scan.hip: batch_scores_kernel): the batched scan
+// index_batch.hip -- several queries in one pass over the index's rows (scan.hip: batch_scores_kernel; over the member
+// rows of a view: view_batch_kernel, through the ssw_index_view_* entries): the batched scan
 // and the batched top-k, plain, pruned and two-stage, on one driver.  The handle: index_handle.h.  A batch is cut into chunks of the widest kernel form the shape and the side buffer allow, the remainder into
 // narrower ones and at last single queries.  A chunk's last query scores into the handle's own buffer, the others into
 // the side slabs; the selection then runs slab by slab through the single-query path (topk_enqueue / topk_collect).
@@ -47,13 +48,15 @@ ssw_status ssw::batch_buffers(ssw_index *idx, int w, bool with_queries, int *out
 
 // the chunk width to use for nq queries: limited by the shape, by nq and by what the side buffer could be grown to
 static ssw_status batch_width(ssw_index *idx, int32_t nq, int *out_w) {
-    int w = scan_batch_max_width(idx->n, idx->dim, idx->dtype);
+    int w = idx->parent ? scan_view_batch_max_width(idx->n, idx->dim, idx->dtype)
+                        : scan_batch_max_width(idx->n, idx->dim, idx->dtype);
     if (w > BATCH_MAX_WIDTH) w = BATCH_MAX_WIDTH;
     while (w > nq) w >>= 1;
     return batch_buffers(idx, w, false, out_w);
 }
 
-// queries [w, dim] (host), w >= 2 -> one launch that fills chunk_slab(w, j) with the scores of query j
+// queries [w, dim] (host), w >= 2 -> one launch that fills chunk_slab(w, j) with the scores of query j; on a view (only
+// the ssw_index_view_* entries come here with one) over its member rows in the parent's matrix
 static ssw_status do_scan_chunk(ssw_index *idx, const float *q_host, int w) {
     BatchState &bt = idx->batch;
     float *slab[BATCH_MAX_WIDTH];
@@ -61,6 +64,9 @@ static ssw_status do_scan_chunk(ssw_index *idx, const float *q_host, int w) {
     SSW_TRY(bt.qb_stage.push(bt.qb_dev, q_host, (size_t)w * idx->dim * sizeof(float), idx->stream));
     idx->scores_partial = false;
     return profiled(idx, [&] {
+        if (idx->parent)
+            return launch_scan_view_batch(idx->X, idx->dtype, bt.qb_dev, idx->row_src, slab, w, idx->n, idx->dim, idx->device,
+                                          idx->stream);
         return launch_scan_batch(idx->X, idx->dtype, bt.qb_dev, slab, w, idx->n, idx->dim, idx->device, idx->stream);
     });
 }
@@ -77,8 +83,19 @@ static ssw_status check_query_batch(const ssw_index *idx, const float *q_host, i
     return SSW_OK;
 }
 
-extern "C" ssw_status ssw_index_scan_batch(ssw_index *idx, const float *q_host, int32_t nq, float *out_scores_host) {
-    SSW_TRY(refuse_view(idx, "ssw_index_scan_batch"));  // a view has no batched scan: the chunk kernels walk the matrix by row number
+// The batched entries come in two sets.  The plain ones refuse a view (refuse_view), as every entry that walks the matrix
+// by row number does; the ssw_index_view_* ones take a view and nothing else.  `view`: the call is one of the latter,
+// named `who`.  Behind the gate one driver serves both: batch_width and do_scan_chunk pick the view's kernels by the
+// handle, the single scans go through launch_index_scan, and the rest works on the handle's own buffers.
+static ssw_status view_gate(const ssw_index *idx, bool view, const char *who) {
+    if (!view) return refuse_view(idx, who);
+    SSW_REQUIRE(idx == nullptr || idx->parent != nullptr,
+                "%s: the index is not a view (ssw_index_create_view); the entry without `view_` takes it", who);
+    return SSW_OK;
+}
+
+static ssw_status scan_batch_run(ssw_index *idx, const float *q_host, int32_t nq, float *out_scores_host, bool view) {
+    SSW_TRY(view_gate(idx, view, view ? "ssw_index_view_scan_batch" : "ssw_index_scan_batch"));
     SSW_REQUIRE(nq >= 1, "nq=%d < 1", nq);
     SSW_REQUIRE(idx != nullptr && q_host != nullptr, "NULL argument");
     SSW_TRY(check_query_batch(idx, q_host, nq));
@@ -106,6 +123,14 @@ extern "C" ssw_status ssw_index_scan_batch(ssw_index *idx, const float *q_host, 
     }
     SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
     return SSW_OK;
+}
+
+extern "C" ssw_status ssw_index_scan_batch(ssw_index *idx, const float *q_host, int32_t nq, float *out_scores_host) {
+    return scan_batch_run(idx, q_host, nq, out_scores_host, false);
+}
+
+extern "C" ssw_status ssw_index_view_scan_batch(ssw_index *idx, const float *q_host, int32_t nq, float *out_scores_host) {
+    return scan_batch_run(idx, q_host, nq, out_scores_host, true);
 }
 
 // ---- the second stage of a batch (ssw_index_topk_batch_avg) -----------------------------------------------------------
@@ -220,15 +245,18 @@ static ssw_status prune_scan_chunk(ssw_index *idx, const BatchExcluded &excl, in
     return SSW_OK;
 }
 
-// The four batched top-k entries.  `pruned`: a chunk's slabs get their scores from the certified pre-scan (if the index
+// The four batched top-k entries and the two of a view (`view`: view_gate; never `pruned`, a view holds no shadow).
+// `pruned`: a chunk's slabs get their scores from the certified pre-scan (if the index
 // is not eligible or its shadow is refused: from the plain scan, and the prune counters stay as they are).  With `avg`,
 // every query's selection is followed by the aggregation over its own slab; a pruned slab is exact on its survivors
 // only, so the tiles of the selected images are rescored into it first (exact_tiles_of_result).
 static ssw_status topk_batch_run(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
                                  const int64_t *excluded_offsets, int32_t k, int64_t *out_images, float *out_scores,
-                                 int64_t *out_best_rows, int32_t *out_counts, const AvgStage *avg, bool pruned) {
-    SSW_TRY(refuse_view(idx, avg ? (pruned ? "ssw_index_topk_batch_avg_pruned" : "ssw_index_topk_batch_avg")
-                                 : (pruned ? "ssw_index_topk_batch_pruned" : "ssw_index_topk_batch")));  // no batched scan of a view
+                                 int64_t *out_best_rows, int32_t *out_counts, const AvgStage *avg, bool pruned,
+                                 bool view = false) {
+    SSW_TRY(view_gate(idx, view, view ? (avg ? "ssw_index_view_topk_batch_avg" : "ssw_index_view_topk_batch")
+                                 : avg ? (pruned ? "ssw_index_topk_batch_avg_pruned" : "ssw_index_topk_batch_avg")
+                                       : (pruned ? "ssw_index_topk_batch_pruned" : "ssw_index_topk_batch")));
     SSW_REQUIRE(nq >= 1, "nq=%d < 1", nq);
     SSW_REQUIRE(idx != nullptr && q_host != nullptr && out_counts != nullptr, "NULL argument");
     SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
@@ -328,6 +356,13 @@ ssw_status ssw_index_topk_batch_pruned(ssw_index *idx, const float *q_host, int3
                           out_counts, nullptr, true);
 }
 
+ssw_status ssw_index_view_topk_batch(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
+                                     const int64_t *excluded_offsets, int32_t k, int64_t *out_images, float *out_scores,
+                                     int64_t *out_best_rows, int32_t *out_counts) {
+    return topk_batch_run(idx, q_host, nq, excluded_images, excluded_offsets, k, out_images, out_scores, out_best_rows,
+                          out_counts, nullptr, false, true);
+}
+
 }  // extern "C"
 
 // ---- the batched top-k that stays on the device: every query's message into a slot of the batch exchange target ------
@@ -388,7 +423,7 @@ static ssw_status prune_scan_chunk_dev(ssw_index *idx, const BatchExcluded &excl
 // call is ssw_index_topk_batch_dev).
 static ssw_status topk_batch_dev_run(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
                                      const int64_t *excluded_offsets, int32_t k, int32_t first_slot, bool pruned) {
-    // a view has no batched scan: the chunk kernels walk the matrix by row number
+    // a view has no exchange target to write into, so the batch that stays on the device has no view form
     SSW_TRY(refuse_view(idx, pruned ? "ssw_index_topk_batch_dev_pruned" : "ssw_index_topk_batch_dev"));
     SSW_REQUIRE(nq >= 1, "nq=%d < 1", nq);
     SSW_REQUIRE(idx != nullptr && q_host != nullptr, "NULL argument");
@@ -632,8 +667,9 @@ extern "C" ssw_status ssw_index_stage2_pair_batch(ssw_index *idx, const float *q
 static ssw_status topk_batch_avg(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
                                  const int64_t *excluded_offsets, int32_t k, int32_t aug_larger, int64_t *out_images,
                                  float *out_scores, int64_t *out_best_rows, float *out_avg_scores, int64_t *out_avg_rows,
-                                 int32_t *out_counts, bool pruned) {
-    SSW_TRY(refuse_view(idx, pruned ? "ssw_index_topk_batch_avg_pruned" : "ssw_index_topk_batch_avg"));
+                                 int32_t *out_counts, bool pruned, bool view = false) {
+    SSW_TRY(view_gate(idx, view, view ? "ssw_index_view_topk_batch_avg"
+                                      : pruned ? "ssw_index_topk_batch_avg_pruned" : "ssw_index_topk_batch_avg"));
     SSW_REQUIRE(nq >= 1, "nq=%d < 1", nq);
     SSW_REQUIRE(idx && q_host && out_counts && out_avg_scores && out_avg_rows, "NULL argument");
     SSW_TRY(check_avg_args(idx, aug_larger, "topk_batch_avg"));
@@ -643,7 +679,7 @@ static ssw_status topk_batch_avg(ssw_index *idx, const float *q_host, int32_t nq
                 SSW_RESCORE_MAX_TILES);
     const AvgStage avg{aug_larger, out_avg_scores, out_avg_rows};
     return topk_batch_run(idx, q_host, nq, excluded_images, excluded_offsets, k, out_images, out_scores, out_best_rows,
-                          out_counts, &avg, pruned);
+                          out_counts, &avg, pruned, view);
 }
 
 extern "C" {
@@ -662,6 +698,14 @@ ssw_status ssw_index_topk_batch_avg_pruned(ssw_index *idx, const float *q_host, 
                                            float *out_avg_scores, int64_t *out_avg_rows, int32_t *out_counts) {
     return topk_batch_avg(idx, q_host, nq, excluded_images, excluded_offsets, k, aug_larger, out_images, out_scores,
                           out_best_rows, out_avg_scores, out_avg_rows, out_counts, true);
+}
+
+ssw_status ssw_index_view_topk_batch_avg(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
+                                         const int64_t *excluded_offsets, int32_t k, int32_t aug_larger,
+                                         int64_t *out_images, float *out_scores, int64_t *out_best_rows,
+                                         float *out_avg_scores, int64_t *out_avg_rows, int32_t *out_counts) {
+    return topk_batch_avg(idx, q_host, nq, excluded_images, excluded_offsets, k, aug_larger, out_images, out_scores,
+                          out_best_rows, out_avg_scores, out_avg_rows, out_counts, false, true);
 }
 
 }  // extern "C"

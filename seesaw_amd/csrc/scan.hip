@@ -476,6 +476,97 @@ __global__ __launch_bounds__(256) void view_small_kernel(const typename R::T *__
     }
 }
 
+// multi-query form: slab b, row j = <X[row_src[j], :], Q[b, :]>.  batch_scores_kernel's schedule and arithmetic line for
+// line (persistent grid, 64-row batches, groups of U rows, nt loads, register double buffer, T groups unrolled between
+// scheduling barriers, dot_frag, group_reduce<V, true>, the B x B register / lane transpose, one 256-byte store a slab);
+// only the rows come as in view_scores_kernel: one coalesced row_src load per 64-row batch, requested a batch ahead,
+// lanes past the view's last row clamped to it, a group's U sources taken out by load_view_group.  Slab b holds the bits
+// view_scores_kernel writes for query b.  It is a kernel of its own, not an instance of a body shared with
+// batch_scores_kernel: behind a shared inlined body that kernel's instances no longer compiled to what they compile to
+// alone ("Batched scan of a view").  A change to either loop belongs in both.  Two more live
+// registers than batch_scores_kernel (src, src_next): scan_view_batch_max_width.
+template <class R, int C, int U, int B, bool NT>
+__global__ __launch_bounds__(256) void view_batch_kernel(const typename R::T *__restrict__ X,
+                                                        const float *__restrict__ q,  // [B, 256*C]
+                                                        const int32_t *__restrict__ row_src, ScoreSlabs<B> out, int n) {
+    constexpr int V = U * B;
+    static_assert(V <= 64 && (B & (B - 1)) == 0 && (U & (U - 1)) == 0, "U*B (row, query) partials share one wave-wide reduce");
+    constexpr int GPB = 64 / U;  // groups per batch
+    constexpr int T = B <= 4 ? B : 4;  // groups unrolled per trip
+    const int lane = threadIdx.x & 63;
+    const int gwave = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int nwaves = gridDim.x * 4;
+    const int nbatches = (n + 63) >> 6;
+    const int last = n - 1;
+    if (gwave >= nbatches) return;
+
+    RowFrag<C> qf[B];
+#pragma unroll
+    for (int b = 0; b < B; ++b) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) qf[b].v[c] = reinterpret_cast<const float4 *>(q)[(b * C + c) * 64 + lane];
+    }
+
+    const int my_run = lane / V;
+    int src = row_src[min((gwave << 6) + lane, last)];
+    Group<R, C, U> cur, nxt;
+    load_view_group<R, C, U, NT>(cur, X, src, 0, lane);
+    for (int bt = gwave; bt < nbatches; bt += nwaves) {
+        const int row0 = bt << 6;
+        const int nb = bt + nwaves;
+        const int next0 = (nb < nbatches ? nb : bt) << 6;  // no next batch: re-touch own rows
+        const int src_next = row_src[min(next0 + lane, last)];
+        float o[B];
+#pragma unroll
+        for (int t = 0; t < B; ++t) o[t] = 0.0f;
+#pragma unroll 1
+        for (int s = 0; s < GPB / T; ++s) {
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                const int g = s * T + t;
+                const bool more = g + 1 < GPB;
+                load_view_group<R, C, U, NT>(nxt, X, more ? src : src_next, more ? (g + 1) * U : 0, lane);
+                __builtin_amdgcn_sched_barrier(0);
+                float acc[V];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const RowFrag<C> x = R::widen(cur.r[u]);
+#pragma unroll
+                    for (int b = 0; b < B; ++b) acc[b * U + u] = dot_frag<C>(x, qf[b]);
+                }
+                const float v = group_reduce<V, true>(acc, lane);
+                const bool mine = my_run == s / (B / T);
+#pragma unroll
+                for (int j = 0; j < B / T; ++j) {
+                    const bool here = (B == T) || (s % (B / T)) == j;  // wave-uniform
+                    unsigned m = (mine && here) ? 0xffffffffu : 0u;
+                    asm volatile("" : "+v"(m));
+                    o[t + T * j] = pick(m, o[t + T * j], v);
+                }
+                cur = nxt;
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        // register t <-> query bits of the lane
+#pragma unroll
+        for (int off = 1; off < B; off <<= 1) {
+            const unsigned m = lane_bit_mask(lane, U * off);  // (my_q & off) != 0
+#pragma unroll
+            for (int i = 0; i < B; ++i) {
+                if ((i & off) != 0) continue;
+                const float got = __shfl_xor(pick(m, o[i + off], o[i]), U * off, 64);
+                o[i] = pick(m, o[i], got);
+                o[i + off] = pick(m, got, o[i + off]);
+            }
+        }
+        if (row0 + lane < n) {
+#pragma unroll
+            for (int b = 0; b < B; ++b) out.p[b][row0 + lane] = o[b];
+        }
+        src = src_next;
+    }
+}
+
 // scores of an explicit list of rows, same summation order as the full scan (one wave per
 // row, plain butterfly) -- stage-2 rescoring against a second vector
 // (multiscale_index.py:347-349).
@@ -640,9 +731,10 @@ constexpr const ScanBatchWidths *scan_batch_widths(int32_t dim) {
 SSW_TUNABLE int g_scan_batch_max = -1;  // tuning hook (ssw_tune_scan_batch): -1 = the product's widths
 SSW_TUNABLE int g_scan_batch_blocks_per_cu = SCAN_BATCH_BLOCKS_PER_CU;  // the same hook: four-wave blocks per CU
 
+// row_src: the rows are a view's (view_batch_kernel), n its rows; NULL: the matrix's own (batch_scores_kernel)
 template <class R, int C, int U, int B>
-ssw_status launch_scan_batch_t(const void *Xv, const float *qb, float *const *slabs, int64_t n, int device,
-                               hipStream_t stream) {
+ssw_status launch_scan_batch_t(const void *Xv, const float *qb, const int32_t *row_src, float *const *slabs, int64_t n,
+                               int device, hipStream_t stream) {
     const typename R::T *X = static_cast<const typename R::T *>(Xv);
     ScoreSlabs<B> out;
     for (int b = 0; b < B; ++b) out.p[b] = slabs[b];
@@ -652,8 +744,12 @@ ssw_status launch_scan_batch_t(const void *Xv, const float *qb, float *const *sl
     const int64_t need = (nbatches + 3) / 4;
     if (grid > need) grid = need;
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL((batch_scores_kernel<R, C, U, B, true>), dim3((unsigned)grid), dim3(256), 0, stream, X, qb,
-                       out, (int)n);
+    if (row_src)
+        hipLaunchKernelGGL((view_batch_kernel<R, C, U, B, true>), dim3((unsigned)grid), dim3(256), 0, stream, X, qb,
+                           row_src, out, (int)n);
+    else
+        hipLaunchKernelGGL((batch_scores_kernel<R, C, U, B, true>), dim3((unsigned)grid), dim3(256), 0, stream, X, qb,
+                           out, (int)n);
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
 }
@@ -786,19 +882,20 @@ int scan_batch_max_width(int64_t n, int32_t dim, int32_t dtype) {
     return h16 ? w->f16 : w->f32;
 }
 
-// slabs[b][i] = <X[i,:], qb[b,:]> for b < nb (a power of two, 2 <= nb <= scan_batch_max_width): the bits of launch_scan
-// per query
-ssw_status launch_scan_batch(const void *X, int32_t dtype, const float *qb_dev, float *const *slabs, int32_t nb,
-                             int64_t n, int32_t dim, int device, hipStream_t stream) {
-    if (n <= 0) return SSW_OK;
-    if (nb < 2 || nb > scan_batch_max_width(n, dim, dtype)) {
-        set_error("scan_batch: a batch of %d queries over %lld rows of dim %d has no kernel", nb, (long long)n, dim);
-        return SSW_ERR_UNSUPPORTED;
-    }
+// The same for a view of n rows.  A width whose view_batch_kernel instance used scratch would be narrowed here; none
+// does: every instance holds two registers more than batch_scores_kernel's and stays at its occupancy, the 16-wide ones
+// at dim 768 and f16 dim 512 past 256 registers as theirs are (profiles/view_batch_resource_usage.txt), so the widths
+// are the matrix's own.
+int scan_view_batch_max_width(int64_t n, int32_t dim, int32_t dtype) { return scan_batch_max_width(n, dim, dtype); }
+
+namespace {
+// the instance of a width nb the callers below have checked: over the matrix's own rows (row_src NULL) or a view's
+ssw_status scan_batch_dispatch(const void *X, int32_t dtype, const float *qb_dev, const int32_t *row_src,
+                               float *const *slabs, int32_t nb, int64_t n, int32_t dim, int device, hipStream_t stream) {
     const bool h16 = dtype == SSW_DTYPE_F16;
     // <row format, chunks, rows a group, width>.  Rows a group: launch_scan's value at the dim, halved where U * B would
     // pass the 64 partials of one reduce (dim 256) or the registers ask for it.
-#define SSW_BATCH_ARGS (X, qb_dev, slabs, n, device, stream)
+#define SSW_BATCH_ARGS (X, qb_dev, row_src, slabs, n, device, stream)
     switch (dim) {
         case 256:
             switch (nb) {
@@ -865,6 +962,33 @@ ssw_status launch_scan_batch(const void *X, int32_t dtype, const float *qb_dev, 
 #undef SSW_BATCH_ARGS
     set_error("scan_batch: width %d has no kernel in this build", nb);
     return SSW_ERR_UNSUPPORTED;
+}
+}  // namespace
+
+// slabs[b][i] = <X[i,:], qb[b,:]> for b < nb (a power of two, 2 <= nb <= scan_batch_max_width): the bits of launch_scan
+// per query
+ssw_status launch_scan_batch(const void *X, int32_t dtype, const float *qb_dev, float *const *slabs, int32_t nb,
+                             int64_t n, int32_t dim, int device, hipStream_t stream) {
+    if (n <= 0) return SSW_OK;
+    if (nb < 2 || nb > scan_batch_max_width(n, dim, dtype)) {
+        set_error("scan_batch: a batch of %d queries over %lld rows of dim %d has no kernel", nb, (long long)n, dim);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    return scan_batch_dispatch(X, dtype, qb_dev, nullptr, slabs, nb, n, dim, device, stream);
+}
+
+// slabs[b][j] = <X[row_src[j],:], qb[b,:]> for j < n_view, b < nb (a power of two, 2 <= nb <= scan_view_batch_max_width):
+// the bits of launch_scan_view per query.  row_src [n_view] i32 (device), every entry a row of X
+ssw_status launch_scan_view_batch(const void *X, int32_t dtype, const float *qb_dev, const int32_t *row_src,
+                                  float *const *slabs, int32_t nb, int64_t n_view, int32_t dim, int device,
+                                  hipStream_t stream) {
+    if (n_view <= 0) return SSW_OK;
+    if (row_src == nullptr || nb < 2 || nb > scan_view_batch_max_width(n_view, dim, dtype)) {
+        set_error("scan_view_batch: a batch of %d queries over a view of %lld rows of dim %d has no kernel", nb,
+                  (long long)n_view, dim);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    return scan_batch_dispatch(X, dtype, qb_dev, row_src, slabs, nb, n_view, dim, device, stream);
 }
 
 ssw_status launch_score_rows(const void *X, int32_t dtype, const float *q_dev, const int64_t *rows_dev, int64_t n,

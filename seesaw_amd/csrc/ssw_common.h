@@ -187,6 +187,13 @@ ssw_status launch_scan_view(const void *X, int32_t dtype, const float *q_dev, co
 int scan_batch_max_width(int64_t n, int32_t dim, int32_t dtype);
 ssw_status launch_scan_batch(const void *X, int32_t dtype, const float *qb_dev, float *const *slabs, int32_t nb,
                              int64_t n, int32_t dim, int device, hipStream_t stream);
+// the multi-query form over a view's rows: slabs[b][j] = dot(X[row_src[j],:], qb_dev[b,:]) for j < n_view, per query the
+// bits of launch_scan_view.  nb at most scan_view_batch_max_width(n_view, dim, dtype): scan_batch_max_width, narrowed
+// where the view instance of a width is not built
+int scan_view_batch_max_width(int64_t n_view, int32_t dim, int32_t dtype);
+ssw_status launch_scan_view_batch(const void *X, int32_t dtype, const float *qb_dev, const int32_t *row_src,
+                                  float *const *slabs, int32_t nb, int64_t n_view, int32_t dim, int device,
+                                  hipStream_t stream);
 // prune.hip: the int8 shadow of an index (rows of element type dtype: f32, or binary16 in the layout above, taken as
 // their widened values) and the certified pre-scan of the exact top-k (see prune.hip).
 // query state words: [0] survivors, [1] Q = ||q|| rounded up (f32 bits), [2] 1 = the query cannot be bounded

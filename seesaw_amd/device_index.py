@@ -142,8 +142,9 @@ class DeviceIndex:
         (ssw_index_create_view): no rows are copied, the view holds a 4-byte row table, its own score buffer, selection
         workspace and image map, and returns what `from_numpy(X[rows], row2image=compact)` returns, bit for bit.  It
         sees this index's current rows and keeps it alive; `close()` of this index is refused while a view is open.
-        What reads or writes the matrix by row number (upload, download, the batched entries, knn, ...) raises on a
-        view; `score_rows` / `gather_rows` take the view's rows.  Close views before their parent: `__del__` cannot
+        What reads or writes the matrix by row number (upload, download, `scores_batch` / `topk_batch` and the other
+        batched entries, knn, ...) raises on a view; a view batches through `view_scores_batch`, `view_topk_batch` and
+        `view_topk_batch_avg`; `score_rows` / `gather_rows` take the view's rows.  Close views before their parent: `__del__` cannot
         raise, so a parent that is collected while a view is still open (interpreter shutdown, a reference cycle) keeps
         its device memory until the process ends -- the refusal is silent there."""
         pos = np.ascontiguousarray(image_positions, dtype=np.int64).reshape(-1)
@@ -319,6 +320,33 @@ class DeviceIndex:
                   _ptr(offsets), k, _ptr(imgs), _ptr(scs), _ptr(rows), _ptr(cnt))
         return [(imgs[b, :c].copy(), scs[b, :c].copy(), rows[b, :c].copy()) for b, c in enumerate(cnt.tolist())]
 
+    # -- the same on a view: the member rows read once per chunk of queries, in place ----
+    def view_scores_batch(self, Q: np.ndarray) -> np.ndarray:
+        """`scores_batch` of a view (ssw_index_view_scan_batch): [nq, n_rows] f32, row b the bits of `scores(Q[b])` --
+        those of `parent.scores(Q[b])[parent_rows]` -- from one pass over the member rows per chunk of queries.  The
+        resident scores are then those of the last query.  Raises on an index that is not a view."""
+        Q = self._queries(Q)
+        out = np.empty((Q.shape[0], self.n_rows), dtype=np.float32)
+        _lib.call("ssw_index_view_scan_batch", self._h, _ptr(Q), Q.shape[0], _ptr(out))
+        return out
+
+    def view_topk_batch(self, Q: np.ndarray, k: int, excluded=None):
+        """`topk_batch` of a view (ssw_index_view_topk_batch): `[topk(Q[b], k, excluded[b]) for b]`, bit for bit, with
+        the member rows read out of the parent's matrix once per chunk of queries; what `topk_batch` of the copied
+        subset returns.  `excluded` as there.  There is no pruned form: a view holds no shadow.  The view is left as
+        after the last query's topk.  Raises on an index that is not a view."""
+        k = int(k)
+        Q = self._queries(Q)
+        nq = Q.shape[0]
+        ids, offsets = self._excluded_batch(excluded, nq)
+        imgs = np.empty((nq, k), dtype=np.int64)
+        scs = np.empty((nq, k), dtype=np.float32)
+        rows = np.empty((nq, k), dtype=np.int64)
+        cnt = np.zeros(nq, dtype=np.int32)
+        _lib.call("ssw_index_view_topk_batch", self._h, _ptr(Q), nq, _ptr(ids), _ptr(offsets), k, _ptr(imgs), _ptr(scs),
+                  _ptr(rows), _ptr(cnt))
+        return [(imgs[b, :c].copy(), scs[b, :c].copy(), rows[b, :c].copy()) for b, c in enumerate(cnt.tolist())]
+
     def load_scores(self, scores: np.ndarray):
         """overwrite the resident per-row scores (f32; -inf rows are never selected)."""
         s = np.ascontiguousarray(scores, dtype=np.float32)
@@ -394,6 +422,27 @@ class DeviceIndex:
         cnt = np.zeros(nq, dtype=np.int32)
         _lib.call("ssw_index_topk_batch_avg_pruned" if prune else "ssw_index_topk_batch_avg", self._h, _ptr(Q), nq,
                   _ptr(ids), _ptr(offsets), k, aug, _ptr(imgs),
+                  _ptr(scs), _ptr(rows), _ptr(avg_scs), _ptr(avg_rows), _ptr(cnt))
+        return [(imgs[b, :c].copy(), scs[b, :c].copy(), rows[b, :c].copy(), avg_scs[b, :c].copy(), avg_rows[b, :c].copy())
+                for b, c in enumerate(cnt.tolist())]
+
+    def view_topk_batch_avg(self, Q: np.ndarray, k: int, aug_larger: str, excluded=None, aug_weight: str = "level_max"):
+        """`topk_batch_avg` of a view (ssw_index_view_topk_batch_avg): both stages for a batch over the member rows,
+        the second over the view's own image map and tile meta; a list of (images, scores, rows, avg_scores, avg_rows)
+        as there, what `topk_batch_avg` of the copied subset returns.  No pruned form.  Raises on an index that is not a
+        view."""
+        k = int(k)
+        Q = self._queries(Q)
+        nq = Q.shape[0]
+        ids, offsets = self._excluded_batch(excluded, nq)
+        aug = self.AUG_LARGER[aug_larger] | {"level_max": 0, "cont_weighted": 4}[aug_weight]
+        imgs = np.empty((nq, k), dtype=np.int64)
+        scs = np.empty((nq, k), dtype=np.float32)
+        rows = np.empty((nq, k), dtype=np.int64)
+        avg_scs = np.empty((nq, k), dtype=np.float32)
+        avg_rows = np.empty((nq, k), dtype=np.int64)
+        cnt = np.zeros(nq, dtype=np.int32)
+        _lib.call("ssw_index_view_topk_batch_avg", self._h, _ptr(Q), nq, _ptr(ids), _ptr(offsets), k, aug, _ptr(imgs),
                   _ptr(scs), _ptr(rows), _ptr(avg_scs), _ptr(avg_rows), _ptr(cnt))
         return [(imgs[b, :c].copy(), scs[b, :c].copy(), rows[b, :c].copy(), avg_scs[b, :c].copy(), avg_rows[b, :c].copy())
                 for b, c in enumerate(cnt.tolist())]

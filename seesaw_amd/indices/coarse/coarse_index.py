@@ -105,8 +105,10 @@ class CoarseIndex(AccessMethod):
                 "activations": ActivationFrames(boxes, ret, np.asarray(scores))}
 
     def query_batch(self, *, topk, vectors, excludes=None, prune=False, vectors2=None, **kwargs):
-        """one `DeviceIndex.topk_batch` call for the vectors that are given: the list of dicts `query` returns, entry by
-        entry identical to it (on a subset_view index a loop over `query`: a view has no batched scan).  A `None`
+        """one `DeviceIndex.topk_batch` call for the vectors that are given (on a subset_view index one
+        `DeviceIndex.view_topk_batch` call: the member rows read in place, once a chunk of queries; `prune` is consumed
+        and means that plain view batch; a call with `vectors2` or `vector2` stays the loop over `query` there, as on a
+        multiscale view index): the list of dicts `query` returns, entry by entry identical to it.  A `None`
         vector (random order) and a query whose exclude set covers the whole index
         keep going through `query`.  `prune` is `DeviceIndex.topk_batch`'s: the same results from the shared int8
         pre-scan on an index large enough for it.  `vectors2` is dropped: `query` ignores `vector2`."""
@@ -114,7 +116,8 @@ class CoarseIndex(AccessMethod):
         excludes = [None] * len(vectors) if excludes is None else list(excludes)
         if len(excludes) != len(vectors):
             raise ValueError(f"excludes has {len(excludes)} entries for {len(vectors)} vectors")
-        if getattr(self._dev, "is_view", False):
+        is_view = getattr(self._dev, "is_view", False)
+        if is_view and (vectors2 is not None or kwargs.get("vector2") is not None):  # as on a multiscale view: the loop
             return [self.query(topk=topk, vector=v, exclude=e, **kwargs) for v, e in zip(vectors, excludes)]
         out = [None] * len(vectors)
         n = self._dbidx.shape[0]
@@ -127,7 +130,10 @@ class CoarseIndex(AccessMethod):
             Q = np.stack([np.asarray(vectors[i], dtype=np.float32).reshape(-1) for i in batch])
             # one k for the launch; every query keeps its own min(topk, included) results
             ks = [min(int(topk), n - excl_pos[i].shape[0]) for i in batch]
-            res = self._dev.topk_batch(Q, max(ks), excluded=[excl_pos[i] for i in batch], prune=prune)
+            if is_view:
+                res = self._dev.view_topk_batch(Q, max(ks), excluded=[excl_pos[i] for i in batch])
+            else:
+                res = self._dev.topk_batch(Q, max(ks), excluded=[excl_pos[i] for i in batch], prune=prune)
             for i, k_i, (pos, scores, _) in zip(batch, ks, res):
                 ret = self._dbidx[pos[:k_i]]
                 assert ret.shape[0] == k_i

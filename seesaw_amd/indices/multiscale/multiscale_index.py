@@ -372,9 +372,12 @@ class MultiscaleIndex(AccessMethod):
 
     def query_batch(self, *, topk, vectors, excludes=None, prune=False, vectors2=None, **kwargs):
         """`[query(vector=v, topk=topk, exclude=e, **kwargs) for v, e in zip(vectors, excludes)]`, entry by entry
-        identical to it (on a subset_view index exactly that loop: a view has no batched scan),
+        identical to it,
         with the rows read once per chunk of up to 16 queries: `plain_score` ends in
-        `DeviceIndex.topk_batch`, every other agg_method in `DeviceIndex.topk_batch_avg`, whose second stage reads each
+        `DeviceIndex.topk_batch`, every other agg_method in `DeviceIndex.topk_batch_avg` (on a subset_view index in
+        `DeviceIndex.view_topk_batch` / `view_topk_batch_avg`: the member rows read in place, once a chunk; `prune` is
+        consumed there and means that plain view batch, and a call with `vectors2` is the loop over `query` -- no
+        `stage2_pair` takes a view), whose second stage reads each
         query's own score slab while the chunk is alive (one k = the largest shortlist of the batch; each query keeps
         its own first min(shortlist_size, included) candidates).  Entries that keep going through `query`: no vector,
         an exclude set that covers the index, and the whole call when the single `vector2` is given, when the index has no tile
@@ -410,8 +413,9 @@ class MultiscaleIndex(AccessMethod):
         plain = kwargs.get("agg_method") == "plain_score"
         tiles_fit = int(np.diff(self._row_start).max(initial=0)) <= DeviceIndex.RESCORE_MAX_TILES
         on_device = plain or (self._has_tile_meta and tiles_fit)
+        is_view = getattr(self._dev, "is_view", False)  # batches through the view_* entries; its two-vector entries loop
         if kwargs.get("vector2") is not None or not on_device or "shortlist_size" not in kwargs \
-                or getattr(self._dev, "is_view", False) or (vectors2 is not None and not tiles_fit):
+                or (vectors2 is not None and (is_view or not tiles_fit)):
             return super().query_batch(topk=topk, vectors=vectors, excludes=excludes, vectors2=vectors2, **kwargs)
         shortlist_size = kwargs["shortlist_size"]
         if shortlist_size is None:
@@ -439,7 +443,10 @@ class MultiscaleIndex(AccessMethod):
             assert aug_weight in ("level_max", "cont_weighted"), aug_weight  # score_frame2's `assert False`
         # ONE first stage for the whole batch; its own second stage only where a single-vector entry needs it
         if plain or all(second[i] is not None for i in batch):
-            res = self._dev.topk_batch(Q, max(ks), excluded=excluded, prune=prune)
+            res = self._dev.view_topk_batch(Q, max(ks), excluded=excluded) if is_view else \
+                self._dev.topk_batch(Q, max(ks), excluded=excluded, prune=prune)
+        elif is_view:
+            res = self._dev.view_topk_batch_avg(Q, max(ks), kwargs["aug_larger"], excluded=excluded, aug_weight=aug_weight)
         else:
             res = self._dev.topk_batch_avg(Q, max(ks), kwargs["aug_larger"], excluded=excluded, aug_weight=aug_weight,
                                            prune=prune)

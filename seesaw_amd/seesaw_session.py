@@ -359,7 +359,7 @@ class SessionGroup:
         """[(session positions, ...)]: the started `KnnProp2` loops that refine through one `KnnProp2.refine_batch`,
         grouped by (index object, shortlist_size), in session order.  A member's `refine` and `refine_external` are the
         class's own, its model `can_fuse_round()`, its index holds its rows on the device (`_dev`) and is not a subset
-        view (no batched entry takes one); SSW_NO_FUSED_ROUND empties the list.  A `PseudoLR`'s inner graph loop is not
+        view (the batched round, ssw_labelprop_round_batch, takes none); SSW_NO_FUSED_ROUND empties the list.  A `PseudoLR`'s inner graph loop is not
         a session's loop and stays on its own path.  Groups of one are listed too; `refine()` leaves them alone."""
         from .loops.graph_based import KnnProp2
         from .loops.loop_base import LoopBase
