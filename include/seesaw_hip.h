@@ -97,11 +97,11 @@ ssw_status ssw_index_destroy(ssw_index *idx);
  * set_excluded, topk_dev, select_deep_dev, result_ptrs, topk_fetch, gather_scores, set_tile_meta, rescore_avg,
  * rescore_avg_f64, profile, profile_read, prune_stats / prune_completions ("not pruned"), ssw_labelprop_scores_to_index,
  * ssw_labelprop_round, and the batched entries of its own, ssw_index_view_scan_batch / _view_topk_batch /
- * _view_topk_batch_avg; ssw_index_device_ptrs hands out the view's score buffer and a NULL row pointer;
+ * _view_topk_batch_avg, and across views of one parent ssw_index_views_topk_batch / _avg; ssw_index_device_ptrs hands out the view's score buffer and a NULL row pointer;
  * ssw_index_score_rows, ssw_index_gather_rows and ssw_fb_set_data_from_index take VIEW rows and translate them;
  * ssw_index_coarse_mean reads a view as its SOURCE through the row table (and refuses one as its destination).
  * Refused on a view with SSW_ERR_UNSUPPORTED (the message says "view") before anything is touched: upload, upload_f16,
- * download, fill_random, set_row2image, every *_batch* entry without `view_` in its name, topk_slot_deep_dev, stage2_avg_batch_dev, both exchange
+ * download, fill_random, set_row2image, every *_batch* entry without `view_` or `views_` in its name, topk_slot_deep_dev, stage2_avg_batch_dev, both exchange
  * target setters, ssw_knn_build, ssw_xlx, ssw_fb_set_pseudo_sample_from_index, and a view of a view.
  * Lifetime: the parent counts its live views; ssw_index_destroy(parent) with live views is SSW_ERR_INVALID and leaves
  * the parent intact.  Destroy the views first.  A view's members are the rows the parent's image map gave those images
@@ -369,6 +369,36 @@ ssw_status ssw_index_view_topk_batch_avg(ssw_index *view, const float *q_host, i
                                          const int64_t *excluded_offsets, int32_t k, int32_t aug_larger,
                                          int64_t *out_images, float *out_scores, int64_t *out_best_rows,
                                          float *out_avg_scores, int64_t *out_avg_rows, int32_t *out_counts);
+
+/* Top-k across VIEWS of one parent in one call: ns slots, slot s = (views[s], q[s]).  Sessions on category subsets
+ * each hold a view of a few thousand rows, where ssw_index_topk is launches and a host wait rather than bytes; here a
+ * chunk of up to 16 slots is ONE upload (slot table and queries), ONE scan launch for the slots of fewer than 65 537
+ * rows and one for the larger ones (csrc/scan.hip, "S VIEWS of one parent": a flat list of row blocks over all slots,
+ * no padding to the largest view), the slots' selections back to back on the PARENT's stream -- each its view's own
+ * selection, with that view's image map and exclusion list -- with `_avg` each followed by the second stage over the
+ * slot's scores and that view's tile meta, and ONE host wait.  ns above 16 is served in chunks of 16.
+ * q_host [ns, dim]; excluded_images / excluded_offsets as in ssw_index_topk_batch, slot s's ids in views[s]'s OWN
+ * image numbering; outputs [ns, k] and out_counts [ns] as there.  A view may fill several slots.  Slot s's outputs are
+ * bit for bit those of ssw_index_topk(views[s], q[s], slot s's exclusions, k) -- and of ssw_index_rescore_avg after it
+ * over the returned images -- as are the scores it leaves behind.  There is no pruned form: a view holds no shadow.
+ * Refused with SSW_ERR_INVALID before anything is touched or enqueued (the message names the entry): a handle that is
+ * not a view, views of different parents, k outside [1, SSW_MAX_TOPK], a NULL argument, an excluded image outside
+ * its view; `_avg` also refuses a view without tile meta.  The plain *_batch* entries keep refusing a view, and the
+ * ssw_index_view_* entries keep taking one view alone.
+ * State afterwards: every view is left as after ssw_index_topk with the query of its LAST slot in the call -- its
+ * resident scores are that query's, complete, and its result buffers (ssw_index_result_ptrs) hold that slot's
+ * selection (after a deep rerun on mass ties: the rerun slot's).  A view's earlier slots of a chunk score into its
+ * side slabs (those of ssw_index_view_topk_batch, grown as that entry grows them); the slot table lives on the parent
+ * and goes with it.  The call runs on the parent's stream and returns with it idle; a view's own stream is waited for
+ * first if it still holds work.  The parent's rows are read only. */
+ssw_status ssw_index_views_topk_batch(ssw_index *const *views, const float *q_host, int32_t ns,
+                                      const int64_t *excluded_images, const int64_t *excluded_offsets, int32_t k,
+                                      int64_t *out_images, float *out_scores, int64_t *out_best_rows, int32_t *out_counts);
+ssw_status ssw_index_views_topk_batch_avg(ssw_index *const *views, const float *q_host, int32_t ns,
+                                          const int64_t *excluded_images, const int64_t *excluded_offsets, int32_t k,
+                                          int32_t aug_larger, int64_t *out_images, float *out_scores,
+                                          int64_t *out_best_rows, float *out_avg_scores, int64_t *out_avg_rows,
+                                          int32_t *out_counts);
 
 /* The SECOND STAGE of a batch of TWO-VECTOR queries (`query(vector=, vector2=)`, seesaw/indices/multiscale/
  * multiscale_index.py:341-352: `scores = vectors[ilocs] @ vector`, `scores -= vectors[ilocs] @ vector2`, then

@@ -265,6 +265,7 @@ ssw_status ssw_index_destroy(ssw_index *idx) {
     idx->batch.release();
     idx->prune_batch.release();
     idx->pair.release();
+    idx->views_batch.release();
     if (idx->owns_X) (void)hipFree(idx->X);
     (void)hipFree(idx->xfer);
     (void)hipFree(idx->scores);

@@ -1,5 +1,6 @@
 // index_batch.hip -- several queries in one pass over the index's rows (scan.hip: batch_scores_kernel; over the member
-// rows of a view: view_batch_kernel, through the ssw_index_view_* entries): the batched scan
+// rows of a view: view_batch_kernel, through the ssw_index_view_* entries; over several views of one parent, a query
+// each: the multi-view kernels, through the ssw_index_views_* entries at the end of the file): the batched scan
 // and the batched top-k, plain, pruned and two-stage, on one driver.  The handle: index_handle.h.  A batch is cut into chunks of the widest kernel form the shape and the side buffer allow, the remainder into
 // narrower ones and at last single queries.  A chunk's last query scores into the handle's own buffer, the others into
 // the side slabs; the selection then runs slab by slab through the single-query path (topk_enqueue / topk_collect).
@@ -706,6 +707,195 @@ ssw_status ssw_index_view_topk_batch_avg(ssw_index *idx, const float *q_host, in
                                          float *out_avg_scores, int64_t *out_avg_rows, int32_t *out_counts) {
     return topk_batch_avg(idx, q_host, nq, excluded_images, excluded_offsets, k, aug_larger, out_images, out_scores,
                           out_best_rows, out_avg_scores, out_avg_rows, out_counts, false, true);
+}
+
+}  // extern "C"
+
+// ---- top-k across VIEWS of one parent: ssw_index_views_topk_batch / _avg ------------------------------------------------
+// ns slots, slot s = (views[s], query s).  Sessions on category subsets hold views of a few thousand rows each: their
+// top-k is launches and a wait, not bytes, and the batched entries above cannot share either across handles.  Here a
+// chunk of up to VIEWS_MAX_SLOTS slots is ONE upload (the slot table and the queries in one block), the multi-view scan
+// (scan.hip: one launch a form), the slots' selections back to back on the PARENT's stream -- each the selection its
+// view's own ssw_index_topk runs (index_enqueue_topk_slot: the view's image map, workspace and exclusions), publishing
+// into a pinned block of the view's -- with `avg` each followed by the aggregation over the slot's slab and the view's
+// tile meta, and ONE host wait.  A view that fills several slots of a chunk scores its occurrences into its own chunk
+// slabs (index_round_slabs): its last occurrence into its resident buffer, the earlier ones into its side slabs.
+namespace {
+struct ViewsChunk {
+    int w = 0;
+    int occ[VIEWS_MAX_SLOTS];      // the slot's occurrence number among the slots of its view in the chunk
+    float *slab[VIEWS_MAX_SLOTS];  // where the slot's scores go
+    unsigned seq[VIEWS_MAX_SLOTS];
+};
+}  // namespace
+
+// the slabs of a chunk's slots: per distinct view as many as the chunk holds occurrences of it
+static ssw_status views_chunk_slabs(ssw_index *const *views, ViewsChunk &c, const char *who) {
+    for (int j = 0; j < c.w; ++j) {
+        int count = 0, before = 0;
+        for (int i = 0; i < c.w; ++i) {
+            if (views[i] != views[j]) continue;
+            ++count;
+            if (i < j) ++before;
+        }
+        c.occ[j] = before;
+        if (before > 0) continue;  // the view's first occurrence sets its buffers up
+        ssw_index *v = views[j];
+        if (hipStreamQuery(v->stream) != hipSuccess) {  // (work of the view's own entries that did not end in a wait)
+            (void)hipGetLastError();
+            SSW_HIP_TRY(hipStreamSynchronize(v->stream));
+        }
+        SSW_TRY(ensure_ws(v));
+        float *slabs[BATCH_MAX_WIDTH];
+        int got = 0;
+        SSW_TRY(index_round_slabs(v, count, &got, slabs));
+        if (got != count) {
+            set_error("%s: no device memory for the %d score slabs of a view of %lld rows", who, count, (long long)v->n);
+            return SSW_ERR_NOMEM;
+        }
+        for (int i = j, o = 0; i < c.w; ++i)
+            if (views[i] == v) c.slab[i] = slabs[o++];
+        v->scores_partial = false;
+    }
+    return SSW_OK;
+}
+
+static ssw_status views_topk_batch_run(ssw_index *const *views, const float *q_host, int32_t ns,
+                                       const int64_t *excluded_images, const int64_t *excluded_offsets, int32_t k,
+                                       int64_t *out_images, float *out_scores, int64_t *out_best_rows, int32_t *out_counts,
+                                       const AvgStage *avg, const char *who) {
+    // every refusal before anything is touched or enqueued
+    SSW_REQUIRE(ns >= 1, "%s: ns=%d < 1", who, ns);
+    SSW_REQUIRE(views != nullptr && q_host != nullptr && out_counts != nullptr, "%s: NULL argument", who);
+    for (int32_t s = 0; s < ns; ++s) {
+        SSW_REQUIRE(views[s] != nullptr, "%s: views[%d] is NULL", who, s);
+        SSW_REQUIRE(views[s]->parent != nullptr, "%s: views[%d] is not a view (ssw_index_create_view)", who, s);
+        SSW_REQUIRE(views[s]->parent == views[0]->parent, "%s: views[%d] is a view of another parent than views[0]", who, s);
+    }
+    SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "%s: k=%d outside [1, %d]", who, k, SSW_MAX_TOPK);
+    const BatchExcluded excl{excluded_images, excluded_offsets};
+    if (excl.offsets) {
+        SSW_REQUIRE(excl.offsets[0] >= 0, "%s: excluded_offsets[0]=%lld < 0", who, (long long)excl.offsets[0]);
+        for (int32_t s = 0; s < ns; ++s)
+            SSW_REQUIRE(excl.offsets[s] <= excl.offsets[s + 1], "%s: excluded_offsets decrease at slot %d", who, s);
+        SSW_REQUIRE(excl.offsets[ns] == excl.offsets[0] || excl.images != nullptr, "%s: excluded_images is NULL", who);
+        for (int32_t s = 0; s < ns; ++s)  // each slot's ids in its own view's numbering
+            SSW_TRY(check_excluded(views[s], excl.images, excl.offsets[s], excl.offsets[s + 1]));
+    }
+    ssw_index *parent = views[0]->parent;
+    const int32_t dim = parent->dim;
+    if (dim != 256 && dim != 512 && dim != 768 && dim != 1024) {
+        set_error("%s: dim=%d unsupported", who, dim);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    if (avg) {
+        for (int32_t s = 0; s < ns; ++s) {
+            SSW_TRY(check_avg_args(views[s], avg->aug, who));
+            SSW_REQUIRE(max_image_tiles(views[s]) <= SSW_RESCORE_MAX_TILES,
+                        "%s: views[%d] has an image with %lld tiles, more than the %d the kernel keeps in LDS", who, s,
+                        (long long)views[s]->max_image_tiles, SSW_RESCORE_MAX_TILES);
+        }
+    }
+    SSW_TRY(check_query_batch(parent, q_host, ns));
+    for (int32_t s = 0; s < ns; ++s) out_counts[s] = 0;
+
+    DeviceGuard guard(parent->device);
+    hipStream_t stream = parent->stream;
+    ViewsBatchState &vb = parent->views_batch;
+    const size_t q_bytes = (size_t)dim * sizeof(float), block_bytes = sizeof(ViewSlotTable) + VIEWS_MAX_SLOTS * q_bytes;
+    if (!vb.dev) SSW_HIP_TRY(hipMalloc((void **)&vb.dev, block_bytes));
+    vb.host.resize(block_bytes);
+    if (avg) SSW_TRY(ensure_avg_buffers(parent));
+    BatchState &pbt = parent->batch;  // (its second-stage arrays alone: row j is slot j of the chunk)
+
+    for (int32_t b = 0; b < ns; b += VIEWS_MAX_SLOTS) {
+        ViewsChunk c;
+        c.w = std::min<int32_t>(VIEWS_MAX_SLOTS, ns - b);
+        ssw_index *const *cv = views + b;
+        SSW_TRY(views_chunk_slabs(cv, c, who));
+        // the block: the table, then the chunk's queries (16-byte aligned behind it: the kernels read them as float4)
+        static_assert(sizeof(ViewSlotTable) % 16 == 0, "the queries behind the table are read as float4");
+        ViewSlotTable *tab = reinterpret_cast<ViewSlotTable *>(vb.host.data());
+        memset(tab, 0, sizeof(ViewSlotTable));
+        const float *q_dev = reinterpret_cast<const float *>(vb.dev + sizeof(ViewSlotTable));
+        for (int j = 0; j < c.w; ++j) {
+            tab->slot[j].row_src = cv[j]->row_src;
+            tab->slot[j].q = q_dev + (size_t)j * dim;
+            tab->slot[j].out = c.slab[j];
+            tab->slot[j].n = (int32_t)cv[j]->n;
+        }
+        ViewsScanPlan plan;
+        SSW_TRY(plan_scan_views(tab, c.w, dim, parent->device, &plan));
+        memcpy(vb.host.data() + sizeof(ViewSlotTable), q_host + (size_t)b * dim, (size_t)c.w * q_bytes);
+        SSW_TRY(vb.stage.push(vb.dev, vb.host.data(), sizeof(ViewSlotTable) + (size_t)c.w * q_bytes, stream));
+        SSW_TRY(profiled(parent, [&] {
+            return launch_scan_views(parent->X, parent->dtype, reinterpret_cast<const ViewSlotTable *>(vb.dev), plan, dim,
+                                     stream);
+        }));
+        int last = -1;
+        for (int j = 0; j < c.w; ++j) {
+            int64_t n_ex = 0;
+            const int64_t *ex = excl.of(b + j, &n_ex);
+            ssw_index *v = cv[j];
+            SSW_TRY(index_enqueue_topk_slot(v, stream, c.occ[j], c.slab[j], ex, n_ex, k, &c.seq[j]));
+            if (c.seq[j] != 0) last = j;
+            if (avg)  // over the result the selection just ahead on the stream leaves in the view's workspace
+                SSW_TRY(launch_avg_score_keys(v->tile_boxes, v->tile_zoom, c.slab[j], v->row_start, v->n_images,
+                                              v->ws.out_keys, v->ws.out_count, k, (int32_t)v->max_image_tiles, avg->aug,
+                                              pbt.avg_score + (size_t)j * k, pbt.avg_row + (size_t)j * k, stream));
+        }
+        // the chunk's ONE wait: with a second stage on its copies, else on the word of the selection enqueued last
+        if (avg) {
+            const size_t o = (size_t)b * k, m = (size_t)c.w * k;
+            SSW_HIP_TRY(hipMemcpyAsync(avg->out_scores + o, pbt.avg_score, m * sizeof(float), hipMemcpyDeviceToHost, stream));
+            SSW_HIP_TRY(hipMemcpyAsync(avg->out_rows + o, pbt.avg_row, m * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+            SSW_HIP_TRY(hipStreamSynchronize(stream));
+        } else if (last >= 0) {
+            SSW_TRY(index_wait_topk_slot(cv[last], stream, c.occ[last], c.seq[last]));
+        }
+        for (int j = 0; j < c.w; ++j) {
+            int64_t n_ex = 0;
+            const int64_t *ex = excl.of(b + j, &n_ex);
+            const size_t o = (size_t)(b + j) * k;
+            ssw_index *v = cv[j];
+            bool reran = false;
+            SSW_TRY(index_collect_topk_slot(v, stream, c.occ[j], c.seq[j], c.slab[j], ex, n_ex, k,
+                                            out_images ? out_images + o : nullptr, out_scores ? out_scores + o : nullptr,
+                                            out_best_rows ? out_best_rows + o : nullptr, out_counts + b + j, &reran));
+            if (avg && reran) {  // mass ties: the deep rerun's result replaces the one the aggregation read
+                SSW_TRY(launch_avg_score_keys(v->tile_boxes, v->tile_zoom, c.slab[j], v->row_start, v->n_images,
+                                              v->ws.out_keys, v->ws.out_count, k, (int32_t)v->max_image_tiles, avg->aug,
+                                              pbt.avg_score + (size_t)j * k, pbt.avg_row + (size_t)j * k, stream));
+                SSW_HIP_TRY(hipMemcpyAsync(avg->out_scores + o, pbt.avg_score + (size_t)j * k, (size_t)k * sizeof(float),
+                                           hipMemcpyDeviceToHost, stream));
+                SSW_HIP_TRY(hipMemcpyAsync(avg->out_rows + o, pbt.avg_row + (size_t)j * k, (size_t)k * sizeof(int64_t),
+                                           hipMemcpyDeviceToHost, stream));
+                SSW_HIP_TRY(hipStreamSynchronize(stream));
+            }
+        }
+    }
+    return SSW_OK;
+}
+
+extern "C" {
+
+ssw_status ssw_index_views_topk_batch(ssw_index *const *views, const float *q_host, int32_t ns,
+                                      const int64_t *excluded_images, const int64_t *excluded_offsets, int32_t k,
+                                      int64_t *out_images, float *out_scores, int64_t *out_best_rows, int32_t *out_counts) {
+    return views_topk_batch_run(views, q_host, ns, excluded_images, excluded_offsets, k, out_images, out_scores,
+                                out_best_rows, out_counts, nullptr, "ssw_index_views_topk_batch");
+}
+
+ssw_status ssw_index_views_topk_batch_avg(ssw_index *const *views, const float *q_host, int32_t ns,
+                                          const int64_t *excluded_images, const int64_t *excluded_offsets, int32_t k,
+                                          int32_t aug_larger, int64_t *out_images, float *out_scores,
+                                          int64_t *out_best_rows, float *out_avg_scores, int64_t *out_avg_rows,
+                                          int32_t *out_counts) {
+    const char *who = "ssw_index_views_topk_batch_avg";
+    SSW_REQUIRE(out_avg_scores != nullptr && out_avg_rows != nullptr, "%s: NULL argument", who);
+    const AvgStage avg{aug_larger, out_avg_scores, out_avg_rows};
+    return views_topk_batch_run(views, q_host, ns, excluded_images, excluded_offsets, k, out_images, out_scores,
+                                out_best_rows, out_counts, &avg, who);
 }
 
 }  // extern "C"

@@ -129,6 +129,19 @@ struct PairStage {
     }
 };
 
+// ssw_index_views_topk_batch, on the PARENT of the views: one chunk's block [ViewSlotTable | its queries, VIEWS_MAX_SLOTS x
+// dim f32] on the device, put together in `host` and sent with one copy; allocated by the first call
+struct ViewsBatchState {
+    unsigned char *dev = nullptr;
+    std::vector<unsigned char> host;
+    ssw::PinnedStage stage;
+    void release() {
+        (void)hipFree(dev);
+        dev = nullptr;
+        stage.release();
+    }
+};
+
 struct ssw_index {
     int device = 0;
     int64_t n = 0;
@@ -195,6 +208,7 @@ struct ssw_index {
     BatchState batch;
     PruneBatchState prune_batch;
     PairStage pair;
+    ViewsBatchState views_batch;
     // profiling of the scan kernel
     bool profiling = false;
     std::vector<hipEvent_t> ev;  // pairs

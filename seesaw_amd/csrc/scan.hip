@@ -45,6 +45,7 @@
 //
 // Grid: persistent, (#CUs x resident blocks per CU) blocks of 256 threads; waves
 // stride over the batches.
+#include <algorithm>
 #include <cstdlib>
 
 #include "ssw_common.h"
@@ -567,6 +568,120 @@ __global__ __launch_bounds__(256) void view_batch_kernel(const typename R::T *__
     }
 }
 
+// ---- S VIEWS of one parent in one launch: slot s = (view_s, query_s), ViewSlotTable (ssw_common.h) -----------------------
+// Sessions on category subsets each hold a view of a few thousand rows: their scans are launch-bound, and one launch
+// for all of them is what a round can share.  Views differ in size by orders of magnitude, so the grid is not
+// (largest view) x S: the work is a FLAT list of row blocks over all slots.  The host writes, per form, the running sum
+// of the slots' block counts into the table; a workgroup finds its slot by counting the sums at or below its block
+// number -- 15 compares on the SALU over entries that arrive with scalar loads, wave-uniform, no divergence -- and
+// takes its block number within the slot from the sum before it.  From there on a workgroup is one of the single view
+// kernels above: the slot's query through LDS once a workgroup (small form), the wave's row sources from one coalesced
+// row_src load, row addresses by load_view_group's lane reads, dot_frag / group_reduce<U> in the same group order -- so
+// every score is the bits view.topk's scan gives that row, whatever the other slots are.
+// Two forms, as launch_view_t has them; a call with slots of both kinds takes one launch of each:
+//   * views_small_kernel: view_small_kernel's shape.  `steps` is one value for the launch, chosen from the rows of all
+//     its slots (plan_scan_views), since sixteen views of 14 k rows are 230 k rows and need no 7 200 workgroups.
+//   * views_stream_kernel: view_scores_kernel's shape.  A slot gets the persistent grid that kernel would get alone, and
+//     its waves stride over its 64-row batches with the sources requested a batch ahead, non-temporal loads.
+// (The names carry neither "scan" nor "score_rows": tests/test_index_f16_cpu.py pins the kernels so named.)
+// Both are compiled without the packed-f32 instructions: dot_frag's two chains become scalar fmas, which are the same
+// values, and the kernels do not depend on the packed forms being right in every encoding.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SSW_NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define SSW_NO_PACKED_F32  // (the host pass knows no such feature)
+#endif
+
+__device__ __forceinline__ int views_slot_of(const int32_t *__restrict__ end, int block) {
+    int s = 0;
+#pragma unroll
+    for (int i = 0; i < VIEWS_MAX_SLOTS - 1; ++i) s += block >= end[i] ? 1 : 0;  // (block < end[VIEWS_MAX_SLOTS - 1])
+    return __builtin_amdgcn_readfirstlane(s);
+}
+
+template <class R, int C, int U>
+__global__ SSW_NO_PACKED_F32 __launch_bounds__(256) void views_small_kernel(const typename R::T *__restrict__ X,
+                                                         const ViewSlotTable *__restrict__ tab, int steps) {
+    __shared__ float4 ql[C * 64];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int s = views_slot_of(tab->end_small, (int)blockIdx.x);
+    const int block = (int)blockIdx.x - (s ? tab->end_small[s - 1] : 0);
+    const int32_t *__restrict__ row_src = tab->slot[s].row_src;
+    const float *__restrict__ q = tab->slot[s].q;
+    float *__restrict__ scores = tab->slot[s].out;
+    const int n = tab->slot[s].n;
+    const int last = n - 1;
+    const int row_base = (block * 4 + wave) * U * steps;
+    const int src = row_src[min(row_base + lane, last)];
+    for (int i = threadIdx.x; i < C * 64; i += 256) ql[i] = reinterpret_cast<const float4 *>(q)[i];
+    Group<R, C, U> cur, nxt;
+    load_view_group<R, C, U, false>(cur, X, src, 0, lane);
+    __syncthreads();
+    RowFrag<C> qf;
+#pragma unroll
+    for (int c = 0; c < C; ++c) qf.v[c] = ql[c * 64 + lane];
+    for (int g = 0; g < steps; ++g) {
+        const int row0 = row_base + g * U;
+        if (row0 >= n) break;
+        if (g + 1 < steps) load_view_group<R, C, U, false>(nxt, X, src, (g + 1) * U, lane);
+        float acc[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) acc[u] = dot_frag<C>(R::widen(cur.r[u]), qf);
+        const float v = group_reduce<U>(acc, lane);
+        if (lane < U && row0 + lane < n) scores[row0 + lane] = v;
+        cur = nxt;
+    }
+}
+
+template <class R, int C, int U, bool NT>
+__global__ SSW_NO_PACKED_F32 __launch_bounds__(256) void views_stream_kernel(const typename R::T *__restrict__ X,
+                                                          const ViewSlotTable *__restrict__ tab) {
+    constexpr int GPB = 64 / U;  // groups per batch
+    const int lane = threadIdx.x & 63;
+    const int s = views_slot_of(tab->end_stream, (int)blockIdx.x);
+    const int first = s ? tab->end_stream[s - 1] : 0;
+    const int32_t *__restrict__ row_src = tab->slot[s].row_src;
+    const float *__restrict__ q = tab->slot[s].q;
+    float *__restrict__ scores = tab->slot[s].out;
+    const int n = tab->slot[s].n;
+    // the slot's own persistent grid: its workgroups' waves stride over its batches
+    const int gwave = ((int)blockIdx.x - first) * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int nwaves = (tab->end_stream[s] - first) * 4;
+    const int nbatches = (n + 63) >> 6;
+    const int last = n - 1;
+    if (gwave >= nbatches) return;
+
+    RowFrag<C> qf;
+#pragma unroll
+    for (int c = 0; c < C; ++c) qf.v[c] = reinterpret_cast<const float4 *>(q)[c * 64 + lane];
+
+    const int my_group = lane / U;
+    int src = row_src[min((gwave << 6) + lane, last)];
+    Group<R, C, U> cur, nxt;
+    load_view_group<R, C, U, NT>(cur, X, src, 0, lane);
+    for (int b = gwave; b < nbatches; b += nwaves) {
+        const int row0 = b << 6;
+        const int nb = b + nwaves;
+        const int next0 = (nb < nbatches ? nb : b) << 6;  // no next batch: re-touch own rows
+        const int src_next = row_src[min(next0 + lane, last)];
+        float out = 0.0f;
+#pragma unroll 2
+        for (int g = 0; g < GPB; ++g) {
+            const bool more = g + 1 < GPB;
+            load_view_group<R, C, U, NT>(nxt, X, more ? src : src_next, more ? (g + 1) * U : 0, lane);
+            float acc[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) acc[u] = dot_frag<C>(R::widen(cur.r[u]), qf);
+            const float v = group_reduce<U>(acc, lane);
+            out = (my_group == g) ? v : out;
+            cur = nxt;
+        }
+        if (row0 + lane < n) scores[row0 + lane] = out;
+        src = src_next;
+    }
+}
+
 // scores of an explicit list of rows, same summation order as the full scan (one wave per
 // row, plain butterfly) -- stage-2 rescoring against a second vector
 // (multiscale_index.py:347-349).
@@ -867,6 +982,96 @@ ssw_status launch_scan_view(const void *X, int32_t dtype, const float *q_dev, co
         }
     }
     set_error("scan: dim=%d unsupported (need a multiple of 256, <= 1024)", dim);
+    return SSW_ERR_UNSUPPORTED;
+}
+
+// ---- the multi-view form (views_small_kernel / views_stream_kernel) -----------------------------------------------------
+namespace {
+constexpr int views_small_u(int C) { return C <= 2 ? 8 : 4; }  // launch_view_t's SU
+constexpr int VIEWS_SMALL_BLOCKS_PER_CU = 8;  // the small form's launch aims at no more workgroups than this a CU
+
+template <class R, int C, int U>
+ssw_status launch_views_t(const void *Xv, const ViewSlotTable *tab, const ViewsScanPlan &p, hipStream_t stream) {
+    const typename R::T *X = static_cast<const typename R::T *>(Xv);
+    constexpr int SU = views_small_u(C);
+    if (p.grid_small > 0) {
+        hipLaunchKernelGGL((views_small_kernel<R, C, SU>), dim3((unsigned)p.grid_small), dim3(256), 0, stream, X, tab,
+                           (int)p.steps);
+        SSW_HIP_TRY(hipGetLastError());
+    }
+    if (p.grid_stream > 0) {
+        hipLaunchKernelGGL((views_stream_kernel<R, C, U, true>), dim3((unsigned)p.grid_stream), dim3(256), 0, stream, X,
+                           tab);
+        SSW_HIP_TRY(hipGetLastError());
+    }
+    return SSW_OK;
+}
+}  // namespace
+
+// The host half: slot[0 .. ns) of *t are filled in (n at least 1); this writes both lists of block sums and the launch
+// shapes.  A slot takes the form launch_view_t gives a view of its size alone.  Small form: a wave takes U * steps
+// rows, U * steps <= 64 (one register holds a wave's sources); steps is 1 -- the single kernel's value over the whole
+// small range -- until the slots' rows together would pass VIEWS_SMALL_BLOCKS_PER_CU workgroups a CU, then as many as
+// keep the launch there.  The scores do not depend on it: a row's sum is formed within its own row.  Streaming form:
+// per slot the grid launch_view_t launches.
+ssw_status plan_scan_views(ViewSlotTable *t, int32_t ns, int32_t dim, int device, ViewsScanPlan *plan) {
+    if (t == nullptr || plan == nullptr || ns < 1 || ns > VIEWS_MAX_SLOTS) {
+        set_error("scan_views: %d slots outside [1, %d]", ns, VIEWS_MAX_SLOTS);
+        return SSW_ERR_INVALID;
+    }
+    if (dim != 256 && dim != 512 && dim != 768 && dim != 1024) {
+        set_error("scan_views: dim=%d unsupported (need a multiple of 256, <= 1024)", dim);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    const int C = dim >> 8, SU = views_small_u(C);
+    int64_t small_rows = 0;
+    for (int s = 0; s < ns; ++s) {
+        const int64_t n = t->slot[s].n;
+        if (n < 1 || n >= (int64_t)0x7fff0000 || !t->slot[s].row_src || !t->slot[s].q || !t->slot[s].out) {
+            set_error("scan_views: slot %d is not filled in (n=%lld)", s, (long long)n);
+            return SSW_ERR_INVALID;
+        }
+        if (n <= SCAN_SMALL_ROWS) small_rows += n;
+    }
+    const int64_t cus = num_cus(device);
+    const int64_t per_step = 4 * SU, target = std::max<int64_t>(cus, 1) * VIEWS_SMALL_BLOCKS_PER_CU;
+    int64_t steps = (small_rows + per_step * target - 1) / (per_step * target);
+    steps = std::min<int64_t>(std::max<int64_t>(steps, 1), 64 / SU);
+    const int64_t stream_cap = std::max<int64_t>(cus, 1) * (C == 2 ? 1 : 2);  // launch_view_t's residency
+    int64_t small = 0, stream = 0;
+    for (int s = 0; s < VIEWS_MAX_SLOTS; ++s) {
+        const int64_t n = s < ns ? t->slot[s].n : 0;
+        if (n > SCAN_SMALL_ROWS) stream += std::min((((n + 63) >> 6) + 3) / 4, stream_cap);
+        else if (n > 0) small += (n + per_step * steps - 1) / (per_step * steps);
+        t->end_small[s] = (int32_t)small;
+        t->end_stream[s] = (int32_t)stream;
+    }
+    plan->grid_small = (int32_t)small;
+    plan->grid_stream = (int32_t)stream;
+    plan->steps = (int32_t)steps;
+    return SSW_OK;
+}
+
+// one launch a form over the table on the device (plan_scan_views' table, uploaded); the rows a group of the streaming
+// form are launch_scan_view's
+ssw_status launch_scan_views(const void *X, int32_t dtype, const ViewSlotTable *tab, const ViewsScanPlan &plan,
+                             int32_t dim, hipStream_t stream) {
+    if (dtype == SSW_DTYPE_F16) {
+        switch (dim) {
+            case 256: return launch_views_t<H16Rows, 1, 16>(X, tab, plan, stream);
+            case 512: return launch_views_t<H16Rows, 2, 4>(X, tab, plan, stream);
+            case 768: return launch_views_t<H16Rows, 3, 4>(X, tab, plan, stream);
+            case 1024: return launch_views_t<H16Rows, 4, 4>(X, tab, plan, stream);
+        }
+    } else {
+        switch (dim) {
+            case 256: return launch_views_t<F32Rows, 1, 8>(X, tab, plan, stream);
+            case 512: return launch_views_t<F32Rows, 2, 2>(X, tab, plan, stream);
+            case 768: return launch_views_t<F32Rows, 3, 2>(X, tab, plan, stream);
+            case 1024: return launch_views_t<F32Rows, 4, 2>(X, tab, plan, stream);
+        }
+    }
+    set_error("scan_views: dim=%d unsupported (need a multiple of 256, <= 1024)", dim);
     return SSW_ERR_UNSUPPORTED;
 }
 

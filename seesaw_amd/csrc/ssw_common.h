@@ -194,6 +194,30 @@ int scan_view_batch_max_width(int64_t n_view, int32_t dim, int32_t dtype);
 ssw_status launch_scan_view_batch(const void *X, int32_t dtype, const float *qb_dev, const int32_t *row_src,
                                   float *const *slabs, int32_t nb, int64_t n_view, int32_t dim, int device,
                                   hipStream_t stream);
+// the multi-VIEW form: ns <= VIEWS_MAX_SLOTS slots, slot s a (view, query) pair over ONE parent matrix X, scored in one
+// launch a form -- slot[s].out[j] = dot(X[slot[s].row_src[j],:], slot[s].q) for j < slot[s].n, per slot the bits of
+// launch_scan_view.  The table lives on the device; the host fills slot[0 .. ns) and plan_scan_views fills the rest: the
+// work of a form is a flat list of row blocks over all slots, end_*[s] the list position one past slot s's last block
+// (slots of the other form, and entries from ns on, take no blocks), so no block is launched for padding however
+// much the views differ in size.
+constexpr int VIEWS_MAX_SLOTS = 16;
+struct ViewSlot {
+    const int32_t *row_src;  // [n] device: the parent row of each row of the view
+    const float *q;          // [dim] device
+    float *out;              // [n] device: the slot's score slab
+    int32_t n, pad;
+};
+struct ViewSlotTable {
+    int32_t end_small[VIEWS_MAX_SLOTS], end_stream[VIEWS_MAX_SLOTS];
+    ViewSlot slot[VIEWS_MAX_SLOTS];
+};
+struct ViewsScanPlan {
+    int32_t grid_small = 0, grid_stream = 0;  // workgroups of each form (0: no slot of that form)
+    int32_t steps = 1;                        // small form: groups of rows a wave takes
+};
+ssw_status plan_scan_views(ViewSlotTable *table_host, int32_t ns, int32_t dim, int device, ViewsScanPlan *plan);
+ssw_status launch_scan_views(const void *X, int32_t dtype, const ViewSlotTable *table_dev, const ViewsScanPlan &plan,
+                             int32_t dim, hipStream_t stream);
 // prune.hip: the int8 shadow of an index (rows of element type dtype: f32, or binary16 in the layout above, taken as
 // their widened values) and the certified pre-scan of the exact top-k (see prune.hip).
 // query state words: [0] survivors, [1] Q = ||q|| rounded up (f32 bits), [2] 1 = the query cannot be bounded

@@ -447,6 +447,64 @@ class DeviceIndex:
         return [(imgs[b, :c].copy(), scs[b, :c].copy(), rows[b, :c].copy(), avg_scs[b, :c].copy(), avg_rows[b, :c].copy())
                 for b, c in enumerate(cnt.tolist())]
 
+    # -- across views of one parent: slot s = (views[s], Q[s]), a chunk of 16 slots one scan launch and one wait ----
+    @staticmethod
+    def _view_slots(views, Q, excluded):
+        """the arguments of the `views_*` calls, checked on the host: -> (handles, Q [ns, dim], ids, offsets)"""
+        views = list(views)
+        if not views:
+            raise ValueError("views must hold at least one view")
+        for s, v in enumerate(views):
+            if not isinstance(v, DeviceIndex) or not v.is_view:
+                raise ValueError(f"views[{s}] is not a view (DeviceIndex.view)")
+            if v.parent is not views[0].parent:
+                raise ValueError(f"views[{s}] is a view of another parent than views[0]")
+        Q = views[0]._queries(Q)
+        if Q.shape[0] != len(views):
+            raise ValueError(f"{Q.shape[0]} queries for {len(views)} views: one query a slot")
+        ids, offsets = DeviceIndex._excluded_batch(excluded, len(views))
+        handles = (ctypes.c_void_p * len(views))(*[v._h for v in views])
+        return handles, Q, ids, offsets
+
+    @staticmethod
+    def views_topk_batch(views, Q: np.ndarray, k: int, excluded=None):
+        """`[views[s].topk(Q[s], k, excluded[s]) for s]`, bit for bit, for views of ONE parent
+        (ssw_index_views_topk_batch): the slots of a chunk of 16 are scored by one launch out of the parent's matrix
+        (two when views on both sides of 65 536 rows share it), their selections follow back to back and the host waits
+        once a chunk.  A view may fill several slots; `excluded[s]` is in `views[s]`'s own image numbering.  Every view
+        is left as after the `topk` of its last slot.  No pruned form.  Raises ValueError on anything but views of one
+        parent and one query a view."""
+        k = int(k)
+        handles, Q, ids, offsets = DeviceIndex._view_slots(views, Q, excluded)
+        ns = Q.shape[0]
+        imgs = np.empty((ns, k), dtype=np.int64)
+        scs = np.empty((ns, k), dtype=np.float32)
+        rows = np.empty((ns, k), dtype=np.int64)
+        cnt = np.zeros(ns, dtype=np.int32)
+        _lib.call("ssw_index_views_topk_batch", handles, _ptr(Q), ns, _ptr(ids), _ptr(offsets), k, _ptr(imgs), _ptr(scs),
+                  _ptr(rows), _ptr(cnt))
+        return [(imgs[b, :c].copy(), scs[b, :c].copy(), rows[b, :c].copy()) for b, c in enumerate(cnt.tolist())]
+
+    @staticmethod
+    def views_topk_batch_avg(views, Q: np.ndarray, k: int, aug_larger: str, excluded=None, aug_weight: str = "level_max"):
+        """`views_topk_batch` with the second stage behind every slot's selection (ssw_index_views_topk_batch_avg), over
+        the slot's scores and its view's own tile meta: a list of (images, scores, rows, avg_scores, avg_rows), slot s
+        what `views[s].view_topk_batch_avg(Q[s:s + 1], ...)` returns."""
+        k = int(k)
+        handles, Q, ids, offsets = DeviceIndex._view_slots(views, Q, excluded)
+        ns = Q.shape[0]
+        aug = DeviceIndex.AUG_LARGER[aug_larger] | {"level_max": 0, "cont_weighted": 4}[aug_weight]
+        imgs = np.empty((ns, k), dtype=np.int64)
+        scs = np.empty((ns, k), dtype=np.float32)
+        rows = np.empty((ns, k), dtype=np.int64)
+        avg_scs = np.empty((ns, k), dtype=np.float32)
+        avg_rows = np.empty((ns, k), dtype=np.int64)
+        cnt = np.zeros(ns, dtype=np.int32)
+        _lib.call("ssw_index_views_topk_batch_avg", handles, _ptr(Q), ns, _ptr(ids), _ptr(offsets), k, aug, _ptr(imgs),
+                  _ptr(scs), _ptr(rows), _ptr(avg_scs), _ptr(avg_rows), _ptr(cnt))
+        return [(imgs[b, :c].copy(), scs[b, :c].copy(), rows[b, :c].copy(), avg_scs[b, :c].copy(), avg_rows[b, :c].copy())
+                for b, c in enumerate(cnt.tolist())]
+
     AGG_PLAIN, AGG_AVG = 0, 1  # ssw_index_stage2_pair_batch's `agg`
 
     def stage2_pair(self, Q: np.ndarray, Q2: np.ndarray, positions: np.ndarray, counts: np.ndarray, agg: str,

@@ -143,6 +143,40 @@ class CoarseIndex(AccessMethod):
                           "activations": ActivationFrames(boxes, ret, np.asarray(scores[:k_i]))}
         return out
 
+    @staticmethod
+    def query_batch_views(indexes, *, topk, vectors, excludes=None, **kwargs):
+        """`[ix.query(topk=topk, vector=v, exclude=e) for ix, v, e in zip(indexes, vectors, excludes)]`, entry by entry
+        identical to it, for `subset_view` indexes of ONE parent through ONE `DeviceIndex.views_topk_batch`: a chunk of
+        16 entries one scan launch over the parent's rows and one host wait.  A `None` vector, an exclude set that
+        covers the index and an index that is not a view keep going through `query`.  `shortlist_size`, `agg_method`
+        and `aug_larger` are accepted and unused, as `query` takes them."""
+        indexes, vectors = list(indexes), list(vectors)
+        excludes = [None] * len(vectors) if excludes is None else list(excludes)
+        if not (len(indexes) == len(vectors) == len(excludes)):
+            raise ValueError(f"{len(indexes)} indexes, {len(vectors)} vectors and {len(excludes)} excludes: one of each an entry")
+        if len({id(ix._dev.parent) for ix in indexes if getattr(ix._dev, "is_view", False)}) > 1:
+            raise ValueError("query_batch_views: the indexes are views of different parents")
+        out, batch, excl_pos = [None] * len(vectors), [], {}
+        for i, (ix, v, e) in enumerate(zip(indexes, vectors, excludes)):
+            excl_pos[i] = _positions_of(ix._dbidx, np.asarray(BitMap() if e is None else e, dtype=np.int64))
+            if v is not None and getattr(ix._dev, "is_view", False) and excl_pos[i].shape[0] < ix._dbidx.shape[0]:
+                batch.append(i)
+            else:
+                out[i] = ix.query(topk=topk, vector=v, exclude=e, **kwargs)
+        if batch:
+            Q = np.stack([np.asarray(vectors[i], dtype=np.float32).reshape(-1) for i in batch])
+            ks = [min(int(topk), indexes[i]._dbidx.shape[0] - excl_pos[i].shape[0]) for i in batch]
+            res = DeviceIndex.views_topk_batch([indexes[i]._dev for i in batch], Q, max(ks),
+                                               excluded=[excl_pos[i] for i in batch])
+            for i, k_i, (pos, scores, _) in zip(batch, ks, res):
+                ret = indexes[i]._dbidx[pos[:k_i]]
+                assert ret.shape[0] == k_i
+                boxes = np.tile(np.array([[0, 0, 224, 224]], dtype=np.int64), (ret.shape[0], 1))
+                n_excl = 0 if excludes[i] is None else len(excludes[i])
+                out[i] = {"dbidxs": ret, "nextstartk": n_excl + ret.shape[0],
+                          "activations": ActivationFrames(boxes, ret, np.asarray(scores[:k_i]))}
+        return out
+
     def new_query(self):
         return CoarseQuery(self)
 

@@ -479,6 +479,62 @@ class MultiscaleIndex(AccessMethod):
         self._resident_q = Q[-1].copy()
         return out
 
+    @staticmethod
+    def query_batch_views(indexes, *, topk, vectors, excludes=None, shortlist_size, agg_method, aug_larger, **kwargs):
+        """`[ix.query(vector=v, topk=topk, exclude=e, shortlist_size=..., agg_method=..., aug_larger=...) for ix, v, e in
+        zip(indexes, vectors, excludes)]`, entry by entry identical to it (dbidxs, activation boxes, score bits), for
+        `subset_view` indexes of ONE parent: `plain_score` ends in ONE `DeviceIndex.views_topk_batch`, every other
+        agg_method in ONE `DeviceIndex.views_topk_batch_avg` -- a chunk of 16 entries one scan launch over the parent's
+        matrix and one host wait, each entry selected and aggregated over its own index's image map and tile meta.  An
+        index may stand in several entries.  Entries that keep going through their own `query`: no vector, an exclude
+        set that covers the index, an index that is not a view or lacks what the device second stage needs.  There is
+        no `prune` and no second vector here.  Every index's `_resident_q` afterwards names its last entry's vector."""
+        indexes, vectors = list(indexes), list(vectors)
+        excludes = [None] * len(vectors) if excludes is None else list(excludes)
+        if not (len(indexes) == len(vectors) == len(excludes)):
+            raise ValueError(f"{len(indexes)} indexes, {len(vectors)} vectors and {len(excludes)} excludes: one of each an entry")
+        parents = {id(ix._dev.parent) for ix in indexes if getattr(ix._dev, "is_view", False)}
+        if len(parents) > 1:
+            raise ValueError("query_batch_views: the indexes are views of different parents")
+        plain = agg_method == "plain_score"
+        own = dict(shortlist_size=shortlist_size, agg_method=agg_method, aug_larger=aug_larger, **kwargs)
+        sl = topk * 5 if shortlist_size is None else shortlist_size
+        out, batch, excl_pos = [None] * len(vectors), [], {}
+        for i, (ix, v, e) in enumerate(zip(indexes, vectors, excludes)):
+            ok = v is not None and getattr(ix._dev, "is_view", False) and \
+                (plain or (ix._has_tile_meta and int(np.diff(ix._row_start).max(initial=0)) <= DeviceIndex.RESCORE_MAX_TILES))
+            if ok:
+                excl_pos[i] = ix._excluded_positions(e)
+                ok = excl_pos[i].shape[0] < ix._dbidx.shape[0]
+            if ok:
+                batch.append(i)
+            else:
+                out[i] = ix.query(topk=topk, vector=v, exclude=e, **own)
+        if not batch:
+            return out
+        if sl < topk * 5:
+            print(f"Warning: shortlist_size parameter {sl} is small compared to topk param {topk}, "
+                  "you may consider increasing it")
+        Q = np.stack([np.asarray(vectors[i], dtype=np.float32).reshape(-1) for i in batch])
+        # one k for the call; every entry keeps its own min(shortlist_size, included) candidates
+        ks = [min(int(sl), indexes[i]._dbidx.shape[0] - excl_pos[i].shape[0]) for i in batch]
+        devs, excluded = [indexes[i]._dev for i in batch], [excl_pos[i] for i in batch]
+        if plain:
+            res = DeviceIndex.views_topk_batch(devs, Q, max(ks), excluded=excluded)
+        else:
+            aug_weight = kwargs.get("aug_weight", "level_max")
+            assert aug_weight in ("level_max", "cont_weighted"), aug_weight  # score_frame2's `assert False`
+            res = DeviceIndex.views_topk_batch_avg(devs, Q, max(ks), aug_larger, excluded=excluded, aug_weight=aug_weight)
+        for j, (i, k_i, r) in enumerate(zip(batch, ks, res)):
+            ix, pos = indexes[i], r[0][:k_i]
+            if plain:
+                out[i] = ix._activations_from_best(_Candidates(ix._dbidx[pos], r[1][:k_i], pos, r[2][:k_i]), topk)
+            else:
+                order = np.argsort(pos)
+                out[i] = ix._avg_result(pos[order], r[3][:k_i][order], r[4][:k_i][order], topk)
+            ix._resident_q = Q[j].copy()
+        return out
+
     def query(self, *, vector, vector2=None, topk, shortlist_size, exclude=None, force_exact=False, **kwargs):
         if shortlist_size is None:
             shortlist_size = topk * 5

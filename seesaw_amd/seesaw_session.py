@@ -257,7 +257,9 @@ class SessionGroup:
       `shortlist_size`, `agg_method` and `aug_larger` are served by ONE `index.query_batch` -- one pass over the rows;
       a started `MultiRegNeg` whose `next_batch` is the class's own joins that group with `vector = curr_vec` and
       `vector2 = confusion_vec if discount_neg else zeros(dim)` (`query_batch(vectors2=...)`: one more launch for all
-      of them); the started `ActiveSearch` / `LKNNSearch` loops whose model is on the device (`planning_groups`, from the
+      of them); the groups among these whose indexes are `subset_view`s of one parent (`view_groups`, from
+      `MIN_VIEW_GROUP` members on; `None` = never) are served together by ONE `query_batch_views` -- one scan launch and
+      one host wait a chunk of 16 sessions, whichever views they are on; the started `ActiveSearch` / `LKNNSearch` loops whose model is on the device (`planning_groups`, from the
       `MIN_LKNN_GROUP` / `MIN_ACTIVE_SEARCH_GROUP` members on; `None` = never) plan through ONE `next_batch_group` -- one pass of kernels,
       one host wait -- before the other sessions; every other session calls its own `next()`.
     * `refine()`: every session's start-policy gate runs as in `LoopBase.refine_external`; the started `MultiReg`
@@ -327,6 +329,60 @@ class SessionGroup:
                 groups.append(by_key[key])
             by_key[key].append(i)
         return [tuple(g) for g in groups]
+
+    # A merged group of sessions on views of one parent goes through `query_batch_views` from this many members on; None:
+    # never.  It is the smallest S at which the one call is ahead of the loop of `view.topk` by more than both
+    # interquartile ranges in profiles/views_batch_ab.txt (tools/perf_views_batch.py); until that file holds a
+    # measurement that says so the constant stays None and `next()` keeps today's route.
+    MIN_VIEW_GROUP = None
+
+    def view_groups(self):
+        """[(session positions, ...)]: the groups of `query_groups()` that ONE `query_batch_views` can serve together,
+        merged -- those whose index is a `subset_view` (its `_dev` a view) of one parent device index, of one index
+        class, with the same `batch_size`, `shortlist_size`, `agg_method` and `aug_larger`, and none of whose members
+        asks with a second vector -- in session order.  Sessions on different views of one parent are groups of one to
+        `query_groups()`, which keys on the index object; here they stand together.  Merged groups of one are listed
+        too; `next()` serves a group from `MIN_VIEW_GROUP` members on, and never with `prune`."""
+        by_key = {}
+        for group in self.query_groups():
+            first = self.sessions[group[0]].loop
+            dev = getattr(first.q.index, "_dev", None)
+            if not getattr(dev, "is_view", False) or not callable(getattr(first.q.index, "query_batch_views", None)):
+                continue
+            if any(self.batch_vector(self.sessions[i].loop) is None or self.batch_vector2(self.sessions[i].loop) is not None
+                   for i in group):
+                continue
+            p = first.params
+            key = (id(dev.parent), type(first.q.index), p.batch_size, p.shortlist_size, p.agg_method, p.aug_larger)
+            by_key.setdefault(key, []).extend(group)
+        return [tuple(sorted(g)) for g in by_key.values()]
+
+    def _next_views(self, group, out):
+        """one `query_batch_views` for the sessions of `group`, with the bookkeeping `next()` does for a query group"""
+        members = [self.sessions[i] for i in group]
+        vectors = []
+        for s in members:
+            s._log("next.start")
+            print("start met. next batch from custom method..." if s.loop.started
+                  else "start not yet met. next batch using default...")
+            vec = self.batch_vector(s.loop)
+            assert not np.isnan(vec).any(), f"NaN in query vector {vec=}"
+            vectors.append(vec)
+        start = time.time()
+        p = members[0].loop.params
+        indexes = [s.loop.q.index for s in members]
+        # (an index that stands in several slots: each slot excludes what its own session has been shown)
+        results = type(indexes[0]).query_batch_views(
+            indexes, topk=p.batch_size, vectors=vectors, excludes=[s.loop.q.returned for s in members],
+            shortlist_size=p.shortlist_size, agg_method=p.agg_method, aug_larger=p.aug_larger)
+        elapsed = time.time() - start
+        for i, s, r in zip(group, members, results):
+            s.loop.q.returned.update(np.asarray(r["dbidxs"], dtype=np.int64))
+            s.timing.append(elapsed)
+            s.acc_indices.append(r["dbidxs"])
+            s.acc_activations.append(r["activations"])
+            s._log("next.end")
+            out[i] = r["dbidxs"]
 
     def fit_groups(self):
         """([positions that refine through one refine_batch, ...], [positions that refine on their own]), for loops
@@ -448,7 +504,14 @@ class SessionGroup:
             if least is not None and len(group) >= max(2, least):
                 self._next_planned(group, out)
                 planned.update(group)
+        if self.MIN_VIEW_GROUP is not None and not self.prune:  # views of one parent: one call for all their sessions
+            for group in self.view_groups():
+                if len(group) >= max(2, self.MIN_VIEW_GROUP):
+                    self._next_views(group, out)
+                    planned.update(group)
         for group in self.query_groups():
+            if group[0] in planned and len(group) > 1:  # (served whole: view_groups merges whole query groups)
+                continue
             if len(group) == 1:
                 if group[0] in planned:
                     continue
