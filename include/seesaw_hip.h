@@ -602,6 +602,25 @@ ssw_status ssw_index_prune_coarse_stats(ssw_index *idx, int64_t *out3);
  * entries of the two-stage batch. */
 ssw_status ssw_index_prune_completions(ssw_index *idx, int64_t *out2);
 
+/* Chunk selection: with the setting on (default 0), the batched entries that score a chunk of up to 16 slots select all
+ * of its slots in ONE set of launches whose number does not depend on the slot count -- one for slots of at most 8192
+ * images, four for larger ones -- and wait for the host once, instead of one selection a slot.  Taken by the unpruned
+ * chunks of two or more queries of ssw_index_topk_batch / _avg and ssw_index_view_topk_batch / _avg (the handle's
+ * setting), by ssw_index_views_topk_batch / _avg (the PARENT's setting) and by ssw_labelprop_round_batch (the index's).
+ * Results are bit for bit those with the setting off.  Slot by slot the per-slot selection still runs where the chunk
+ * form does not apply: 2^24 images or more, more distinct excluded ids than 4096 - k, an attached exchange target, no
+ * memory for the chunk workspace; a slot whose top is more than 8192 tied images reruns on the deep path.  Not taken by
+ * the pruned entries, ssw_index_topk_batch_dev* or the L-KNN batch.  The handle's installed exclusion set
+ * (ssw_index_set_excluded) is neither read nor changed by a chunk-selected slot, unless the slot reruns on the deep path;
+ * a slot sent to the per-slot selection, and a deep rerun, install their own set as the calls with the setting off do.
+ * Memory: the first use adds per slot 144 KiB plus, for an index of more than 8192 images with an image map, 8 bytes an
+ * image (freed by ssw_index_destroy).
+ * ssw_index_chunk_select_stats, counts since the handle was made: [0] chunks selected together, [1] slots in them,
+ * [2] of those the slots that took the second histogram level (counted when a slot's result is collected), [3] slots sent to the per-slot selection, [4] deep
+ * reruns of chunk-selected slots, [5] launches enqueued by the chunk form. */
+ssw_status ssw_index_set_chunk_select(ssw_index *idx, int32_t on);
+ssw_status ssw_index_chunk_select_stats(ssw_index *idx, int64_t *out6);
+
 /* ------------------------------------------------------------------------- */
 /* k-NN-graph label propagation                                               */
 /* replaces: LabelPropagation.fit_transform  seesaw/label_propagation.py:45-79 */

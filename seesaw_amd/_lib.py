@@ -200,6 +200,8 @@ _SIGNATURES = {
     "ssw_index_prune_stats": (c_i32, [c_void_p, c_i64_p]),
     "ssw_index_prune_completions": (c_i32, [c_void_p, c_i64_p]),
     "ssw_index_prune_coarse_stats": (c_i32, [c_void_p, c_i64_p]),
+    "ssw_index_set_chunk_select": (c_i32, [c_void_p, c_i32]),
+    "ssw_index_chunk_select_stats": (c_i32, [c_void_p, c_i64_p]),
 }
 
 

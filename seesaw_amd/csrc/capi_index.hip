@@ -266,6 +266,7 @@ ssw_status ssw_index_destroy(ssw_index *idx) {
     idx->prune_batch.release();
     idx->pair.release();
     idx->views_batch.release();
+    idx->chunk.release();
     if (idx->owns_X) (void)hipFree(idx->X);
     (void)hipFree(idx->xfer);
     (void)hipFree(idx->scores);
@@ -583,6 +584,7 @@ ssw_status ssw_index_set_row2image(ssw_index *idx, const int32_t *row2image_host
         select_free(idx->ws);
         idx->ws_ready = false;
     }
+    idx->chunk.release();  // (sized by the image count)
     (void)hipFree(idx->row_start);
     idx->row_start = nullptr;
     idx->row_start_host.clear();

@@ -246,6 +246,45 @@ static ssw_status prune_scan_chunk(ssw_index *idx, const BatchExcluded &excl, in
     return SSW_OK;
 }
 
+// The selections of an unpruned chunk of w >= 2 queries [b, b + w) with chunk selection on (ssw_index_set_chunk_select):
+// ONE set of launches for the slots the chunk form takes (index_enqueue_topk_chunk), with `avg` every slot's aggregation
+// over the device result its selection left, and ONE host wait -- on the second stage's copies, else on the slots'
+// words.  A slot that reran deep repeats its aggregation from the handle's result buffers.
+static ssw_status select_chunk_of_batch(ssw_index *idx, const BatchExcluded &excl, int32_t b, int w, int32_t k,
+                                        int64_t *out_images, float *out_scores, int64_t *out_best_rows, int32_t *out_counts,
+                                        const AvgStage *avg) {
+    BatchState &bt = idx->batch;
+    ChunkTopkReq reqs[BATCH_MAX_WIDTH];
+    for (int j = 0; j < w; ++j) {
+        reqs[j].idx = idx, reqs[j].slot = j, reqs[j].slab = chunk_slab(idx, w, j), reqs[j].k = k;
+        reqs[j].excluded_images = excl.of(b + j, &reqs[j].n_excluded);
+    }
+    auto avg_of = [&](int j, const uint64_t *keys, const int32_t *count) {
+        return launch_avg_score_keys(idx->tile_boxes, idx->tile_zoom, reqs[j].slab, idx->row_start, idx->n_images, keys, count,
+                                     k, (int32_t)idx->max_image_tiles, avg->aug, bt.avg_score + (size_t)j * k,
+                                     bt.avg_row + (size_t)j * k, idx->stream);
+    };
+    const std::function<ssw_status(int)> after = [&](int j) { return avg_of(j, reqs[j].dev_keys, reqs[j].dev_count); };
+    SSW_TRY(index_enqueue_topk_chunk(idx, reqs, w, idx->stream, avg ? &after : nullptr));
+    if (avg) SSW_TRY(collect_avg(idx, avg, b, w, k));
+    for (int j = 0; j < w; ++j) {
+        const size_t o = (size_t)(b + j) * k;
+        bool reran = false;
+        SSW_TRY(index_collect_topk_chunk(idx, idx->stream, reqs[j], out_images ? out_images + o : nullptr,
+                                         out_scores ? out_scores + o : nullptr, out_best_rows ? out_best_rows + o : nullptr,
+                                         out_counts + b + j, &reran));
+        if (avg && reran) {
+            SSW_TRY(avg_of(j, idx->ws.out_keys, idx->ws.out_count));
+            SSW_HIP_TRY(hipMemcpyAsync(avg->out_scores + o, bt.avg_score + (size_t)j * k, (size_t)k * sizeof(float),
+                                       hipMemcpyDeviceToHost, idx->stream));
+            SSW_HIP_TRY(hipMemcpyAsync(avg->out_rows + o, bt.avg_row + (size_t)j * k, (size_t)k * sizeof(int64_t),
+                                       hipMemcpyDeviceToHost, idx->stream));
+            SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
+        }
+    }
+    return SSW_OK;
+}
+
 // The four batched top-k entries and the two of a view (`view`: view_gate; never `pruned`, a view holds no shadow).
 // `pruned`: a chunk's slabs get their scores from the certified pre-scan (if the index
 // is not eligible or its shadow is refused: from the plain scan, and the prune counters stay as they are).  With `avg`,
@@ -314,6 +353,11 @@ static ssw_status topk_batch_run(ssw_index *idx, const float *q_host, int32_t nq
             w = 1;
             SSW_TRY(stage_query(idx, q));
             SSW_TRY(do_scan(idx, idx->q_dev));
+        }
+        if (!pruned && w >= 2 && idx->chunk.on && idx->n_images > 0) {
+            SSW_TRY(select_chunk_of_batch(idx, excl, b, w, k, out_images, out_scores, out_best_rows, out_counts, avg));
+            b += w;
+            continue;
         }
         for (int j = 0; j < w; ++j) {
             int64_t n_ex = 0;
@@ -833,7 +877,24 @@ static ssw_status views_topk_batch_run(ssw_index *const *views, const float *q_h
                                      stream);
         }));
         int last = -1;
-        for (int j = 0; j < c.w; ++j) {
+        // chunk selection on the parent: the slots' selections in ONE set of launches (index_enqueue_topk_chunk), each
+        // aggregation over the device result its slot's selection left; the collect below waits on the slots' words
+        const bool chunked = parent->chunk.on;
+        ChunkTopkReq reqs[VIEWS_MAX_SLOTS];
+        if (chunked) {
+            for (int j = 0; j < c.w; ++j) {
+                reqs[j].idx = cv[j], reqs[j].slot = c.occ[j], reqs[j].slab = c.slab[j], reqs[j].k = k;
+                reqs[j].excluded_images = excl.of(b + j, &reqs[j].n_excluded);
+            }
+            const std::function<ssw_status(int)> after = [&](int j) {
+                ssw_index *v = cv[j];
+                return launch_avg_score_keys(v->tile_boxes, v->tile_zoom, c.slab[j], v->row_start, v->n_images,
+                                             reqs[j].dev_keys, reqs[j].dev_count, k, (int32_t)v->max_image_tiles, avg->aug,
+                                             pbt.avg_score + (size_t)j * k, pbt.avg_row + (size_t)j * k, stream);
+            };
+            SSW_TRY(index_enqueue_topk_chunk(parent, reqs, c.w, stream, avg ? &after : nullptr));
+        }
+        for (int j = 0; j < c.w && !chunked; ++j) {
             int64_t n_ex = 0;
             const int64_t *ex = excl.of(b + j, &n_ex);
             ssw_index *v = cv[j];
@@ -859,9 +920,14 @@ static ssw_status views_topk_batch_run(ssw_index *const *views, const float *q_h
             const size_t o = (size_t)(b + j) * k;
             ssw_index *v = cv[j];
             bool reran = false;
-            SSW_TRY(index_collect_topk_slot(v, stream, c.occ[j], c.seq[j], c.slab[j], ex, n_ex, k,
-                                            out_images ? out_images + o : nullptr, out_scores ? out_scores + o : nullptr,
-                                            out_best_rows ? out_best_rows + o : nullptr, out_counts + b + j, &reran));
+            if (chunked)
+                SSW_TRY(index_collect_topk_chunk(parent, stream, reqs[j], out_images ? out_images + o : nullptr,
+                                                 out_scores ? out_scores + o : nullptr,
+                                                 out_best_rows ? out_best_rows + o : nullptr, out_counts + b + j, &reran));
+            else
+                SSW_TRY(index_collect_topk_slot(v, stream, c.occ[j], c.seq[j], c.slab[j], ex, n_ex, k,
+                                                out_images ? out_images + o : nullptr, out_scores ? out_scores + o : nullptr,
+                                                out_best_rows ? out_best_rows + o : nullptr, out_counts + b + j, &reran));
             if (avg && reran) {  // mass ties: the deep rerun's result replaces the one the aggregation read
                 SSW_TRY(launch_avg_score_keys(v->tile_boxes, v->tile_zoom, c.slab[j], v->row_start, v->n_images,
                                               v->ws.out_keys, v->ws.out_count, k, (int32_t)v->max_image_tiles, avg->aug,

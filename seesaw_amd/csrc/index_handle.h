@@ -142,6 +142,24 @@ struct ViewsBatchState {
     }
 };
 
+// chunk selection (ssw_index_set_chunk_select; index_topk.hip, index_enqueue_topk_chunk): the setting, the counters of
+// ssw_index_chunk_select_stats and the handle's chunk workspace -- `slots` parts of select_chunk_slot_bytes each, one a
+// slot of a chunk: histograms, state, candidates, device results and (with_map) per-image maxima.  Allocated zeroed at
+// first use and left zero by the kernels; `dirty` after a failed enqueue: cleared again before the next one
+struct ChunkSelectState {
+    bool on = false;
+    int64_t stats[6] = {0, 0, 0, 0, 0, 0};
+    unsigned char *ws = nullptr;
+    int slots = 0;
+    bool with_map = false, dirty = false, refused = false;
+    void release() {
+        (void)hipFree(ws);
+        ws = nullptr;
+        slots = 0;
+        refused = false;
+    }
+};
+
 struct ssw_index {
     int device = 0;
     int64_t n = 0;
@@ -209,6 +227,7 @@ struct ssw_index {
     PruneBatchState prune_batch;
     PairStage pair;
     ViewsBatchState views_batch;
+    ChunkSelectState chunk;
     // profiling of the scan kernel
     bool profiling = false;
     std::vector<hipEvent_t> ev;  // pairs

@@ -250,6 +250,15 @@ ssw_status index_collect_topk(ssw_index *idx, hipStream_t on_stream, int32_t k, 
 constexpr size_t SLOT_EXCL_BYTES = (size_t)SMALL_EXCL_CAP * sizeof(int64_t);
 constexpr size_t SLOT_BYTES = SLOT_EXCL_BYTES + 16 + (size_t)SSW_MAX_TOPK * 12;
 
+static ssw_status ensure_slot_host(ssw_index *idx) {
+    if (!idx->slot_host) {
+        SSW_HIP_TRY(hipHostMalloc((void **)&idx->slot_host, (size_t)BATCH_MAX_WIDTH * SLOT_BYTES,
+                                  hipHostMallocMapped | hipHostMallocCoherent));
+        memset(idx->slot_host, 0, (size_t)BATCH_MAX_WIDTH * SLOT_BYTES);
+    }
+    return SSW_OK;
+}
+
 ssw_status index_round_slabs(ssw_index *idx, int w, int *out_w, float **slabs) {
     SSW_REQUIRE(idx != nullptr && out_w != nullptr && slabs != nullptr && w >= 1, "NULL argument");
     if (w > BATCH_MAX_WIDTH) w = BATCH_MAX_WIDTH;
@@ -266,11 +275,7 @@ ssw_status index_enqueue_topk_slot(ssw_index *idx, hipStream_t on_stream, int sl
     SSW_REQUIRE(n_excluded == 0 || excluded_images != nullptr, "excluded_images is NULL");
     *out_seq = 0;
     if (idx->n_images == 0) return SSW_OK;
-    if (!idx->slot_host) {
-        SSW_HIP_TRY(hipHostMalloc((void **)&idx->slot_host, (size_t)BATCH_MAX_WIDTH * SLOT_BYTES,
-                                  hipHostMallocMapped | hipHostMallocCoherent));
-        memset(idx->slot_host, 0, (size_t)BATCH_MAX_WIDTH * SLOT_BYTES);
-    }
+    SSW_TRY(ensure_slot_host(idx));
     unsigned char *block = idx->slot_host + (size_t)slot * SLOT_BYTES, *dev_view = nullptr;
     SSW_HIP_TRY(hipHostGetDevicePointer((void **)&dev_view, block, 0));
     SSW_TRY(check_excluded(idx, excluded_images, 0, n_excluded));
@@ -331,6 +336,168 @@ ssw_status index_collect_topk_slot(ssw_index *idx, hipStream_t on_stream, int sl
         return SSW_ERR_INVALID;
     }
     decode_packed(res, k, out_images, out_scores, out_best_rows, out_count);
+    return SSW_OK;
+}
+
+// ---- the chunk-level pair (ssw_common.h): every request of a chunk that the chunk form takes in ONE set of launches ----
+bool index_chunk_select_on(const ssw_index *idx) { return idx != nullptr && idx->chunk.on; }
+
+// the handle's chunk workspace for slots [0, slots), with per-image maxima if with_map; false: it could not be had (the
+// handle's requests take the per-slot selection then, and no later call tries again until the image map changes).  The
+// zeros the kernels count on are put there ON `stream`, ahead of the chunk's kernels: a memset on the null stream is not
+// ordered with a non-blocking stream's work and could land on the first chunk's per-image maxima
+// Which stream the next chunk comes on may differ (the handle's own, a parent's, a graph handle's): every driver ends
+// its call with all its slots' words waited for or with a stream synchronisation (ssw_labelprop_round_batch, whose
+// deferred or failed members are never collected, waits on every member's word in its one wait), so the
+// kernels of one chunk have left the workspace before another stream's chunk can start on it.
+static bool ensure_chunk_ws(ssw_index *idx, int slots, bool with_map, hipStream_t stream) {
+    ChunkSelectState &cs = idx->chunk;
+    if (cs.refused) return false;
+    const size_t part = select_chunk_slot_bytes(idx->n_images, with_map || cs.with_map);
+    if (cs.ws == nullptr || cs.slots < slots || (with_map && !cs.with_map)) {
+        if (cs.ws != nullptr && hipStreamSynchronize(stream) != hipSuccess) return false;
+        const int keep = std::max(cs.slots, slots);
+        const bool map = with_map || cs.with_map;
+        cs.release();
+        if (hipMalloc((void **)&cs.ws, part * keep) != hipSuccess || hipMemsetAsync(cs.ws, 0, part * keep, stream) != hipSuccess) {
+            (void)hipGetLastError();
+            cs.release();
+            cs.refused = true;
+            return false;
+        }
+        cs.slots = keep;
+        cs.with_map = map;
+        cs.dirty = false;
+    }
+    if (cs.dirty) {  // an enqueue failed half way: the kernels did not leave their zeros behind
+        if (hipStreamSynchronize(stream) != hipSuccess || hipMemsetAsync(cs.ws, 0, part * cs.slots, stream) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+        cs.dirty = false;
+    }
+    return true;
+}
+
+ssw_status index_enqueue_topk_chunk(ssw_index *owner, ChunkTopkReq *reqs, int n, hipStream_t on_stream,
+                                    const std::function<ssw_status(int)> *after) {
+    // every refusal before anything is touched
+    SSW_REQUIRE(owner != nullptr && reqs != nullptr && n >= 1 && n <= SELECT_CHUNK_SLOTS, "topk chunk: %d requests outside [1, %d]",
+                n, SELECT_CHUNK_SLOTS);
+    for (int i = 0; i < n; ++i) {
+        const ChunkTopkReq &r = reqs[i];
+        SSW_REQUIRE(r.idx != nullptr && r.slot >= 0 && r.slot < BATCH_MAX_WIDTH, "topk chunk: bad slot in request %d", i);
+        SSW_REQUIRE(r.idx->device == owner->device, "topk chunk: request %d is on another device", i);
+        SSW_REQUIRE(r.k >= 1 && r.k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", r.k, SSW_MAX_TOPK);
+        SSW_REQUIRE(r.n_excluded == 0 || r.excluded_images != nullptr, "excluded_images is NULL");
+        SSW_REQUIRE(r.idx->n_images == 0 || r.slab != nullptr, "topk chunk: request %d has no score slab", i);
+        for (int j = 0; j < i; ++j)
+            SSW_REQUIRE(reqs[j].idx != r.idx || reqs[j].slot != r.slot, "topk chunk: requests %d and %d share a slot", j, i);
+        SSW_TRY(check_excluded(r.idx, r.excluded_images, 0, r.n_excluded));
+    }
+    // the form of each request; the sorted, distinct ids of the ones the chunk form takes
+    static thread_local std::vector<int64_t> ids[SELECT_CHUNK_SLOTS];
+    bool general[SELECT_CHUNK_SLOTS];
+    for (int i = 0; i < n; ++i) {
+        ChunkTopkReq &r = reqs[i];
+        ssw_index *idx = r.idx;
+        r.seq = 0, r.route = 0, r.dev_keys = nullptr, r.dev_count = nullptr;
+        general[i] = false;
+        if (idx->n_images == 0) continue;
+        SSW_TRY(ensure_ws(idx));  // (the per-slot selection and the deep rerun work in it)
+        SSW_TRY(ensure_slot_host(idx));
+        r.route = 2;
+        if (idx->ws.xchg.msg_out != nullptr) continue;  // (the per-slot selection writes the attached message)
+        ids[i].assign(r.excluded_images, r.excluded_images + r.n_excluded);
+        if (!std::is_sorted(ids[i].begin(), ids[i].end())) std::sort(ids[i].begin(), ids[i].end());
+        ids[i].erase(std::unique(ids[i].begin(), ids[i].end()), ids[i].end());
+        if (small_path_ok(idx, r.n_excluded)) r.route = 1;
+        else if (select_chunk_general_ok(idx->n_images) && (int64_t)ids[i].size() <= select_chunk_excl_cap(r.k))
+            r.route = 1, general[i] = true;
+    }
+    for (int i = 0; i < n; ++i) {  // the workspace of each handle, for the slots and the forms its requests need
+        if (reqs[i].route != 1) continue;
+        ssw_index *idx = reqs[i].idx;
+        int slots = 0;
+        bool with_map = false;
+        for (int j = 0; j < n; ++j) {
+            if (reqs[j].idx != idx || reqs[j].route != 1) continue;
+            slots = std::max(slots, reqs[j].slot + 1);
+            with_map = with_map || (general[j] && idx->has_map);
+        }
+        if (!ensure_chunk_ws(idx, slots, with_map, on_stream))
+            for (int j = 0; j < n; ++j)
+                if (reqs[j].idx == idx) reqs[j].route = reqs[j].route == 1 ? 2 : reqs[j].route;
+    }
+    // the table: the general-form slots first
+    ChunkTable tab;
+    int order[SELECT_CHUNK_SLOTS], n_general = 0, n_total = 0;
+    for (int pass = 0; pass < 2; ++pass)
+        for (int i = 0; i < n; ++i)
+            if (reqs[i].route == 1 && general[i] == (pass == 0)) {
+                order[n_total++] = i;
+                if (pass == 0) ++n_general;
+            }
+    for (int m = 0; m < n_total; ++m) {
+        ChunkTopkReq &r = reqs[order[m]];
+        ssw_index *idx = r.idx;
+        ChunkSlot &d = tab.s[m];
+        const bool gen = general[order[m]];
+        unsigned char *block = idx->slot_host + (size_t)r.slot * SLOT_BYTES, *dev_view = nullptr;
+        SSW_HIP_TRY(hipHostGetDevicePointer((void **)&dev_view, block, 0));
+        const std::vector<int64_t> &ex = ids[order[m]];
+        if (!ex.empty()) memcpy(block, ex.data(), ex.size() * sizeof(int64_t));
+        select_chunk_carve(idx->chunk.ws + (size_t)r.slot * select_chunk_slot_bytes(idx->n_images, idx->chunk.with_map),
+                           idx->n_images, idx->chunk.with_map, &d);
+        d.slab = r.slab;
+        d.row_start = idx->has_map ? idx->row_start : nullptr;
+        d.excl_ids = reinterpret_cast<const int64_t *>(dev_view);
+        d.packed = dev_view + SLOT_EXCL_BYTES;
+        d.n_images = (int32_t)idx->n_images, d.k = r.k, d.n_excl = (int32_t)ex.size(), d.small = gen ? 0 : 1;
+        d.seq = r.seq = next_seq(idx->small_seq);
+        r.dev_keys = d.out_keys, r.dev_count = d.out_count;
+    }
+    int64_t *stats = owner->chunk.stats;
+    if (n_total > 0) {
+        int launches = 0;
+        const ssw_status st = launch_select_chunk(tab, n_general, n_total, owner->device, on_stream, &launches);
+        if (st != SSW_OK) {
+            for (int m = 0; m < n_total; ++m) reqs[order[m]].idx->chunk.dirty = true, reqs[order[m]].seq = 0;
+            return st;
+        }
+        stats[0] += 1, stats[1] += n_total, stats[5] += launches;
+        if (after)
+            for (int m = 0; m < n_total; ++m) SSW_TRY((*after)(order[m]));
+    }
+    for (int i = 0; i < n; ++i) {  // the others one by one, each followed by what reads its result on the device
+        ChunkTopkReq &r = reqs[i];
+        if (r.route != 2) continue;
+        stats[3] += 1;
+        SSW_TRY(index_enqueue_topk_slot(r.idx, on_stream, r.slot, r.slab, r.excluded_images, r.n_excluded, r.k, &r.seq));
+        r.dev_keys = r.idx->ws.out_keys, r.dev_count = r.idx->ws.out_count;
+        if (after) SSW_TRY((*after)(i));
+    }
+    return SSW_OK;
+}
+
+ssw_status index_collect_topk_chunk(ssw_index *owner, hipStream_t on_stream, const ChunkTopkReq &req, int64_t *out_images,
+                                    float *out_scores, int64_t *out_best_rows, int32_t *out_count, bool *reran) {
+    SSW_REQUIRE(owner != nullptr && req.idx != nullptr && out_count != nullptr, "NULL argument");
+    *out_count = 0;
+    if (reran) *reran = false;
+    if (req.route == 0 || req.seq == 0) return SSW_OK;
+    bool deep = false;
+    if (req.route == 1) {  // header word 1 of a chunk-selected slot: overflow | second level taken << 1
+        unsigned char *res = req.idx->slot_host + (size_t)req.slot * SLOT_BYTES + SLOT_EXCL_BYTES;
+        SSW_TRY(wait_host_seq(on_stream, reinterpret_cast<const unsigned *>(res) + 3, req.seq));
+        int32_t *hdr = reinterpret_cast<int32_t *>(res);
+        if (hdr[1] & 2) owner->chunk.stats[2] += 1;
+        hdr[1] &= 1;
+    }
+    SSW_TRY(index_collect_topk_slot(req.idx, on_stream, req.slot, req.seq, req.slab, req.excluded_images, req.n_excluded,
+                                    req.k, out_images, out_scores, out_best_rows, out_count, &deep));
+    if (deep && req.route == 1) owner->chunk.stats[4] += 1;
+    if (reran) *reran = deep;
     return SSW_OK;
 }
 
@@ -415,6 +582,18 @@ ssw_status ssw_index_topk(ssw_index *idx, const float *q_host, const int64_t *ex
     else SSW_TRY(ensure_full_scores(idx));
     SSW_TRY(topk_enqueue(idx, q_host, idx->scores, idx->stream, excluded_images, n_excluded, k));
     return topk_collect(idx, idx->scores, idx->stream, k, out_images, out_scores, out_best_rows, out_count);
+}
+
+ssw_status ssw_index_set_chunk_select(ssw_index *idx, int32_t on) {
+    SSW_REQUIRE(idx != nullptr, "idx is NULL");
+    idx->chunk.on = on != 0;
+    return SSW_OK;
+}
+
+ssw_status ssw_index_chunk_select_stats(ssw_index *idx, int64_t *out6) {
+    SSW_REQUIRE(idx != nullptr && out6 != nullptr, "NULL argument");
+    memcpy(out6, idx->chunk.stats, sizeof(idx->chunk.stats));
+    return SSW_OK;
 }
 
 #ifdef SSW_DEBUG_HOOKS

@@ -2185,7 +2185,23 @@ ssw_status ssw_labelprop_round_batch(ssw_lp *const *lps, int32_t n_slots, ssw_in
         SSW_HIP_TRY(hipGetLastError());
         stats[0] += n_inc, stats[1] += launches;
         // ---- the selections, back to back: each over its slot's slab, into its slot's pinned block
+        // (with chunk selection on the index, ssw_index_set_chunk_select: the members' selections in ONE set of launches)
+        const bool chunked = index_chunk_select_on(index);
+        std::vector<ChunkTopkReq> reqs(chunked ? members.size() : 0);
+        if (chunked) {
+            for (size_t m = 0; m < members.size(); ++m) {
+                const Member &mb = members[m];
+                reqs[m].idx = index, reqs[m].slot = mb.j - c0, reqs[m].slab = slabs[mb.j - c0], reqs[m].k = k;
+                reqs[m].excluded_images = excl_of(mb.j, &reqs[m].n_excluded);
+            }
+            const ssw_status rc = index_enqueue_topk_chunk(index, reqs.data(), (int)reqs.size(), s, nullptr);
+            for (size_t m = 0; m < members.size(); ++m) {
+                members[m].seq = reqs[m].seq;
+                if (rc != SSW_OK) fail(members[m].j, rc);
+            }
+        }
         for (Member &mb : members) {
+            if (chunked) break;
             int64_t n_ex = 0;
             const int64_t *ex = excl_of(mb.j, &n_ex);
             if (ssw_status rc = index_enqueue_topk_slot(index, s, mb.j - c0, slabs[mb.j - c0], ex, n_ex, k, &mb.seq); rc != SSW_OK)
@@ -2202,6 +2218,10 @@ ssw_status ssw_labelprop_round_batch(ssw_lp *const *lps, int32_t n_slots, ssw_in
             if (last_seq_member >= 0) {
                 Member &mb = members[(size_t)last_seq_member];
                 SSW_TRY(index_wait_topk_slot(index, s, mb.j - c0, mb.seq));
+                // (a chunk's slots end in one kernel, a workgroup each: every word, so that the chunk workspace is at rest
+                // even where a member below is never collected)
+                for (size_t m = 0; chunked && m < members.size(); ++m)
+                    if (members[m].seq != 0) SSW_TRY(index_wait_topk_slot(index, s, members[m].j - c0, members[m].seq));
             } else {
                 SSW_HIP_TRY(hipStreamSynchronize(s));  // (an index without images, or every selection refused)
             }
@@ -2244,8 +2264,10 @@ ssw_status ssw_labelprop_round_batch(ssw_lp *const *lps, int32_t n_slots, ssw_in
             const int64_t *ex = excl_of(mb.j, &n_ex);
             outs(mb.j, &im, &sc, &br);
             bool reran = false;
-            if (ssw_status rc = index_collect_topk_slot(index, s, mb.j - c0, mb.seq, slabs[mb.j - c0], ex, n_ex, k, im, sc, br,
-                                                        out_counts + mb.j, &reran);
+            if (ssw_status rc = chunked ? index_collect_topk_chunk(index, s, reqs[(size_t)(&mb - members.data())], im, sc, br,
+                                                                   out_counts + mb.j, &reran)
+                                        : index_collect_topk_slot(index, s, mb.j - c0, mb.seq, slabs[mb.j - c0], ex, n_ex, k, im,
+                                                                  sc, br, out_counts + mb.j, &reran);
                 rc != SSW_OK) {
                 fail(mb.j, rc);
                 continue;

@@ -46,6 +46,13 @@ constexpr int64_t SAMPLE_FROM = (int64_t)1 << 24;
 constexpr int64_t SAMPLE_R = 64;
 constexpr int SAMPLE_RANK = 48;
 constexpr int SAMPLE_MAX_K = 1024;
+// chunk selection: a general-form slot picks rank k + n_excl instead of striking the excluded images out of its
+// histograms, so fewer than k + n_excl candidates lie above its last bin and that bin has FINAL_CAP - (k + n_excl - 1)
+// entries of room before the slot overflows into the deep rerun.  The single form leaves its bin FINAL_CAP - k, at its
+// largest k FINAL_CAP - SSW_MAX_TOPK; the chunk form never leaves less: k + n_excl <= SSW_MAX_TOPK, that is at most
+// CHUNK_RANK_MAX - k distinct excluded ids.  A slot with more takes the per-slot selection.
+constexpr int CHUNK_RANK_MAX = SSW_MAX_TOPK;
+static_assert(CHUNK_RANK_MAX <= FINAL_CAP / 2, "half of the final sort stays free for the last bin");
 SSW_TUNABLE bool g_select_sampled = true;  // ssw_tune_topk bit 1
 enum StateSlot : int {
     ST_B1 = 0, ST_ABOVE1, ST_CNT1, ST_B2, ST_ABOVE2, ST_CNT2, ST_MODE, ST_NCAND, ST_OVERFLOW, ST_K,
@@ -653,6 +660,366 @@ int grid_for(int64_t m, int device) {
     return (int)g;
 }
 
+// ---- chunk selection: every slot of a chunk (ChunkTable, in the kernel-argument segment) in the same launches ----------
+// General form, four launches whatever the slot count, slots on blockIdx.y:
+//   k_chunk_level1 : per-image maximum (image map) or the slab itself, tallied straight into the LDS histogram of the top
+//                    12 key bits; the slot's LAST workgroup to flush -- an atomic ticket in the slot's state words --
+//                    picks the bin of rank k + n_excl, so there is no pick launch;
+//   k_chunk_level2 : the next 12 bits inside that bin where level 1 left more than LEVEL2_FROM, its last workgroup picks;
+//   k_chunk_collect: keys at or above the prefix into the slot's candidate block;
+//   k_chunk_final  : one workgroup a slot (blockIdx.x), small-form slots included.
+// Exclusions never reach a bitmap: the histograms and the collect pass ignore them, the pick takes rank k + n_excl (the
+// k-th image that is not excluded has overall rank <= k + n_excl, so it and everything above it is a candidate), and
+// the final kernel strikes the candidates whose image a binary search finds in the slot's sorted id list, held in LDS.
+// Zeroing: every kernel leaves what it has consumed zero -- the pick its histogram, the final kernel the state words --
+// so a chunk starts on the zeros the allocation or the chunk before left; there is no memset.
+constexpr int ST_TICKET1 = 10, ST_TICKET2 = 11;  // state words beside StateSlot's
+constexpr int CHUNK_MAP_IMAGES_PER_WG = 1024;    // level 1 with an image map reads ~13 rows an image
+constexpr int CHUNK_IMAGES_PER_WG = 4096;        // without: as grid_for
+constexpr int CHUNK_AUX_WORDS = FINAL_CAP;       // LDS behind the sort's buffers: best rows (small) / excluded ids
+constexpr size_t CHUNK_FINAL_LDS_BYTES = FINAL_LDS_BYTES + (size_t)CHUNK_AUX_WORDS * sizeof(uint32_t);
+static_assert(CHUNK_RANK_MAX <= CHUNK_AUX_WORDS && SELECT_SMALL_IMAGES <= CHUNK_AUX_WORDS, "the ids / best rows fit");
+static_assert(sizeof(ChunkTable) <= 3072, "the table travels in the kernel-argument segment");
+
+__device__ __forceinline__ uint32_t load_agent(const uint32_t *p) {  // past this CU's vector cache
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// k_pick on the 256 threads of the workgroup that flushed last: 16 bins a thread, and the histogram zeroed behind it
+template <int LEVEL>
+__device__ __forceinline__ void chunk_pick(uint32_t *__restrict__ hist, uint32_t *__restrict__ state, uint32_t kk,
+                                           uint32_t *sums, int t) {
+    uint32_t h[16], local = 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        h[j] = load_agent(hist + 16 * t + j);
+        local += h[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 16; ++j) hist[16 * t + j] = 0u;
+    __syncthreads();  // (sums is the histogram's LDS: every flush has been read)
+    sums[t] = local;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {  // inclusive suffix sum, from the top bin downwards
+        const uint32_t v = (t + d < 256) ? sums[t + d] : 0u;
+        __syncthreads();
+        sums[t] += v;
+        __syncthreads();
+    }
+    const uint32_t total = sums[0], above_t = sums[t] - local;
+    uint32_t b = 0, above = 0, cnt = 0;
+    bool found = false;
+    if (total < kk) {  // fewer than kk elements in all: everything is a candidate
+        if (t == 0) {
+            found = true;
+            cnt = h[0];
+            above = total - h[0];
+        }
+    } else if (above_t < kk && kk <= above_t + local) {
+        uint32_t c = above_t;
+#pragma unroll
+        for (int j = 15; j >= 0; --j) {
+            if (!found && c + h[j] >= kk) {
+                found = true;
+                b = 16 * t + j;
+                above = c;
+                cnt = h[j];
+            }
+            c += h[j];
+        }
+    }
+    if (!found) return;
+    if (LEVEL == 1) {
+        state[ST_B1] = b;
+        state[ST_ABOVE1] = above;
+        state[ST_CNT1] = cnt;
+        state[ST_MODE] = (above + cnt > (uint32_t)LEVEL2_FROM) ? 1u : 0u;
+    } else {
+        state[ST_B2] = b;
+        state[ST_ABOVE2] = above;
+        state[ST_CNT2] = cnt;
+        if (state[ST_ABOVE1] + above + cnt > (uint32_t)FINAL_CAP) state[ST_OVERFLOW] = 1u;
+    }
+}
+
+// the flush of a workgroup's LDS histogram, and whether this workgroup was the last of the slot's nblk to flush
+__device__ __forceinline__ bool chunk_flush_last(const uint32_t *lh, uint32_t *__restrict__ hist, uint32_t *ticket,
+                                                 unsigned nblk, uint32_t *flag, int t) {
+    __syncthreads();
+    for (int i = t; i < NBINS; i += 256) {
+        const uint32_t c = lh[i];
+        if (c) atomicAdd(&hist[i], c);
+    }
+    __threadfence();
+    __syncthreads();
+    if (t == 0) *flag = (atomicAdd(ticket, 1u) == nblk - 1u) ? 1u : 0u;
+    __syncthreads();
+    const bool last = *flag != 0u;
+    if (last) __threadfence();
+    return last;
+}
+
+__device__ __forceinline__ unsigned chunk_blocks(int64_t n, int per_wg) {
+    const int64_t b = (n + per_wg - 1) / per_wg;
+    return (unsigned)(b < (int64_t)gridDim.x ? b : (int64_t)gridDim.x);
+}
+
+__global__ __launch_bounds__(256) void k_chunk_level1(const ChunkTable tab) {
+    __shared__ uint32_t lh[NBINS];
+    __shared__ uint32_t flag;
+    const ChunkSlot &d = tab.s[blockIdx.y];
+    const int t = threadIdx.x;
+    const int64_t n = d.n_images;
+    const int64_t *__restrict__ row_start = d.row_start;
+    const float *__restrict__ slab = d.slab;
+    const unsigned nblk = chunk_blocks(n, row_start ? CHUNK_MAP_IMAGES_PER_WG : CHUNK_IMAGES_PER_WG);
+    if (blockIdx.x >= nblk) return;
+    for (int i = t; i < NBINS; i += 256) lh[i] = 0;
+    __syncthreads();
+    const int64_t stride = (int64_t)nblk * 256;
+    if (row_start != nullptr) {  // k_image_max and the tally in one pass; eight rows in flight
+        float *__restrict__ img_score = d.img_score;
+        uint32_t *__restrict__ img_best = d.img_best;
+        for (int64_t m = (int64_t)blockIdx.x * 256 + t; m < n; m += stride) {
+            const int64_t r0 = row_start[m], r1 = row_start[m + 1];
+            float best = -INFINITY;
+            int64_t br = r0;
+            for (int64_t r = r0; r < r1; r += 8) {
+                float sc[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) sc[u] = slab[min(r + u, r1 - 1)];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    if (r + u < r1 && sc[u] > best) {  // strict: lowest row wins ties
+                        best = sc[u];
+                        br = r + u;
+                    }
+                }
+            }
+            img_score[m] = best;
+            img_best[m] = (uint32_t)br;
+            atomicAdd(&lh[f32_to_ord(best) >> 20], 1u);
+        }
+    } else {  // 16-byte loads, two in flight per thread (the slabs are 16-byte aligned)
+        const float4 *v4 = reinterpret_cast<const float4 *>(slab);
+        const int64_t n4 = n >> 2;
+        for (int64_t j = (int64_t)blockIdx.x * 256 + t; j < n4; j += 2 * stride) {
+            const int64_t j2 = j + stride;
+            const float4 a = v4[j];
+            const float4 b = v4[j2 < n4 ? j2 : j];
+            atomicAdd(&lh[f32_to_ord(a.x) >> 20], 1u);
+            atomicAdd(&lh[f32_to_ord(a.y) >> 20], 1u);
+            atomicAdd(&lh[f32_to_ord(a.z) >> 20], 1u);
+            atomicAdd(&lh[f32_to_ord(a.w) >> 20], 1u);
+            if (j2 < n4) {
+                atomicAdd(&lh[f32_to_ord(b.x) >> 20], 1u);
+                atomicAdd(&lh[f32_to_ord(b.y) >> 20], 1u);
+                atomicAdd(&lh[f32_to_ord(b.z) >> 20], 1u);
+                atomicAdd(&lh[f32_to_ord(b.w) >> 20], 1u);
+            }
+        }
+        for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * 256 + t; i < n; i += stride)
+            atomicAdd(&lh[f32_to_ord(slab[i]) >> 20], 1u);
+    }
+    uint32_t *state = d.hist + 2 * NBINS;
+    if (!chunk_flush_last(lh, d.hist, state + ST_TICKET1, nblk, &flag, t)) return;
+    chunk_pick<1>(d.hist, state, (uint32_t)(d.k + d.n_excl), lh, t);
+}
+
+__global__ __launch_bounds__(256) void k_chunk_level2(const ChunkTable tab) {
+    __shared__ uint32_t lh[NBINS];
+    __shared__ uint32_t flag;
+    const ChunkSlot &d = tab.s[blockIdx.y];
+    uint32_t *state = d.hist + 2 * NBINS;
+    if (state[ST_MODE] == 0) return;  // level 1 was enough
+    const int t = threadIdx.x;
+    const int64_t n = d.n_images;
+    const unsigned nblk = chunk_blocks(n, CHUNK_IMAGES_PER_WG);
+    if (blockIdx.x >= nblk) return;
+    const uint32_t b1 = state[ST_B1];
+    for (int i = t; i < NBINS; i += 256) lh[i] = 0;
+    __syncthreads();
+    const float *__restrict__ values = d.row_start ? d.img_score : d.slab;
+    const int64_t stride = (int64_t)nblk * 256;
+    auto tally = [&](float v) {
+        const uint32_t key = f32_to_ord(v);
+        if ((key >> 20) == b1) atomicAdd(&lh[(key >> 8) & 0xfffu], 1u);
+    };
+    const float4 *v4 = reinterpret_cast<const float4 *>(values);
+    const int64_t n4 = n >> 2;
+    for (int64_t j = (int64_t)blockIdx.x * 256 + t; j < n4; j += 2 * stride) {
+        const int64_t j2 = j + stride;
+        const float4 a = v4[j];
+        const float4 b = v4[j2 < n4 ? j2 : j];
+        tally(a.x);
+        tally(a.y);
+        tally(a.z);
+        tally(a.w);
+        if (j2 < n4) {
+            tally(b.x);
+            tally(b.y);
+            tally(b.z);
+            tally(b.w);
+        }
+    }
+    for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * 256 + t; i < n; i += stride) tally(values[i]);
+    uint32_t *hist2 = d.hist + NBINS;
+    if (!chunk_flush_last(lh, hist2, state + ST_TICKET2, nblk, &flag, t)) return;
+    chunk_pick<2>(hist2, state, (uint32_t)(d.k + d.n_excl) - state[ST_ABOVE1], lh, t);
+}
+
+__global__ __launch_bounds__(256) void k_chunk_collect(const ChunkTable tab) {
+    const ChunkSlot &d = tab.s[blockIdx.y];
+    const int64_t n = d.n_images;
+    const unsigned nblk = chunk_blocks(n, CHUNK_IMAGES_PER_WG);
+    if (blockIdx.x >= nblk) return;
+    uint32_t *state = d.hist + 2 * NBINS;
+    uint64_t *__restrict__ cand = d.cand;
+    const uint32_t mode = state[ST_MODE];
+    const uint32_t prefix = mode ? ((state[ST_B1] << 12) | state[ST_B2]) : state[ST_B1];
+    const int shift = mode ? 8 : 20;
+    const float *__restrict__ values = d.row_start ? d.img_score : d.slab;
+    const int64_t stride = (int64_t)nblk * 256;
+    auto take = [&](float v, int64_t i) {
+        const uint32_t key = f32_to_ord(v);
+        if ((key >> shift) >= prefix) {
+            const uint32_t slot = atomicAdd(&state[ST_NCAND], 1u);
+            if (slot < (uint32_t)FINAL_CAP) cand[slot] = ((uint64_t)key << 32) | (uint64_t)(0xffffffffu - (uint32_t)i);
+        }
+    };
+    const float4 *v4 = reinterpret_cast<const float4 *>(values);
+    const int64_t n4 = n >> 2;
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n4; j += 4 * stride) {
+        float4 a[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t ju = j + u * stride;
+            a[u] = v4[ju < n4 ? ju : j];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t ju = j + u * stride;
+            if (ju < n4) {
+                take(a[u].x, 4 * ju);
+                take(a[u].y, 4 * ju + 1);
+                take(a[u].z, 4 * ju + 2);
+                take(a[u].w, 4 * ju + 3);
+            }
+        }
+    }
+    for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) take(values[i], i);
+}
+
+// One workgroup a slot.  Small form: k_final's values_all branch -- every image's key into LDS (the per-image maximum
+// taken here, its best row kept in LDS beside the keys), the excluded ids struck out by position.  General form: the
+// slot's candidates into LDS, its sorted id list beside them, every candidate whose image the list holds struck out.
+// Then select_sorted_desc, the packed block (header word 1: overflow | second level taken << 1), the device results the
+// second stage reads, the state words left zero, and the release of the slot's sequence word.
+__global__ __launch_bounds__(1024) void k_chunk_final(const ChunkTable tab) {
+    extern __shared__ uint64_t s[];  // FINAL_CAP entries + FINAL_CAP / 2 for the halvings + CHUNK_AUX_WORDS u32
+    uint32_t *aux = reinterpret_cast<uint32_t *>(s + FINAL_CAP + FINAL_CAP / 2);
+    const ChunkSlot &d = tab.s[blockIdx.x];
+    const int t = threadIdx.x;
+    const int k = d.k, n_excl = d.n_excl;
+    const int64_t *__restrict__ excl_ids = d.excl_ids;
+    const int64_t *__restrict__ row_start = d.row_start;
+    const bool small = d.small != 0;
+    uint32_t *state = small ? nullptr : d.hist + 2 * NBINS;
+    int n = 0, ovf = 0, mode = 0;
+    if (small) {
+        n = d.n_images;
+        const float *__restrict__ slab = d.slab;
+        for (int i = t; i < n; i += 1024) {
+            float v;
+            if (row_start != nullptr) {  // k_image_max, here; eight rows in flight
+                const int64_t r0 = row_start[i], r1 = row_start[i + 1];
+                float best = -INFINITY;
+                int64_t br = r0;
+                for (int64_t r = r0; r < r1; r += 8) {
+                    float sc[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) sc[u] = slab[min(r + u, r1 - 1)];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        if (r + u < r1 && sc[u] > best) {  // strict: lowest row wins ties
+                            best = sc[u];
+                            br = r + u;
+                        }
+                    }
+                }
+                aux[i] = (uint32_t)br;
+                v = best;
+            } else {
+                v = slab[i];
+            }
+            s[i] = composite_key(v, i);
+        }
+        __syncthreads();
+        for (int j = t; j < n_excl; j += 1024) s[excl_ids[j]] = 0ull;  // ids range-checked by the host
+    } else {
+        const uint32_t ncand = state[ST_NCAND];
+        ovf = (state[ST_OVERFLOW] != 0 || ncand > (uint32_t)FINAL_CAP) ? 1 : 0;
+        mode = (int)state[ST_MODE];
+        n = (int)min(ncand, (uint32_t)FINAL_CAP);
+        const uint64_t *__restrict__ cand = d.cand;
+        for (int i = t; i < n; i += 1024) s[i] = cand[i];
+        for (int j = t; j < n_excl; j += 1024) aux[j] = (uint32_t)excl_ids[j];
+        __syncthreads();
+        if (n_excl > 0) {
+            for (int i = t; i < n; i += 1024) {
+                const uint32_t id = 0xffffffffu - (uint32_t)(s[i] & 0xffffffffull);
+                int lo = 0, hi = n_excl;  // the first entry >= id
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (aux[mid] < id) lo = mid + 1;
+                    else hi = mid;
+                }
+                if (lo < n_excl && aux[lo] == id) s[i] = 0ull;
+            }
+        }
+    }
+    int p = 64;
+    while (p < n) p <<= 1;
+    int c = 64;  // keys wanted, rounded up to a block of the selection
+    while (c < k) c <<= 1;
+    c = min(c, p);
+    for (int i = n + t; i < p; i += 1024) s[i] = 0ull;  // below every real key
+    __syncthreads();
+    const uint64_t *res = select_sorted_desc(s, p, c, t);
+    const int kk = min(k, c);
+    unsigned char *packed = d.packed;
+    uint64_t *pk_keys = reinterpret_cast<uint64_t *>(packed + 16);
+    uint32_t *pk_best = reinterpret_cast<uint32_t *>(packed + 16 + (size_t)k * 8);
+    uint64_t *__restrict__ keys_out = d.out_keys;
+    uint32_t *__restrict__ best_out = d.out_best;
+    const uint32_t *__restrict__ img_best = d.img_best;
+    for (int i = t; i < kk; i += 1024) {
+        const uint64_t key = res[i];
+        const bool last = key != 0ull && (i + 1 == kk || res[i + 1] == 0ull);
+        if (last || (i == 0 && key == 0ull)) {
+            const int out = key != 0ull ? i + 1 : 0;
+            d.out_count[0] = out;
+            d.out_count[1] = ovf;
+            int32_t *hdr = reinterpret_cast<int32_t *>(packed);
+            hdr[0] = out;
+            hdr[1] = ovf | (mode << 1);
+            hdr[2] = k;
+        }
+        if (key == 0ull) continue;
+        const uint32_t id = 0xffffffffu - (uint32_t)(key & 0xffffffffull);
+        const uint32_t br = row_start == nullptr ? id : small ? aux[id] : img_best[id];
+        keys_out[i] = key;
+        pk_keys[i] = key;
+        best_out[i] = br;
+        pk_best[i] = br;
+    }
+    if (!small && t < ST_WORDS) state[t] = 0u;  // (every read of them is above the selection's barriers)
+    __threadfence_system();  // the packed block is host memory: release everything, then the word the host spins on
+    __syncthreads();
+    if (t == 0)
+        __hip_atomic_store(reinterpret_cast<unsigned *>(packed) + 3, d.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 }  // namespace
 
 #ifdef SSW_DEBUG_HOOKS
@@ -1006,6 +1373,88 @@ ssw_status launch_merge_msgs(const uint64_t *msgs, int32_t world, int32_t k_max,
                              hipStream_t stream) {
     return launch_merge_msgs_batch(msgs, world, (int64_t)(with_best ? 2 : 1) * k_max + 1, 1, k_max, with_best, k, keys_out,
                                    count_out, flags_out, flags_seen, stream);
+}
+
+// ---- chunk selection: the workspace layout and the launches ------------------------------------------------------------
+static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+constexpr size_t CHUNK_HIST_BYTES = (size_t)(2 * NBINS + ST_WORDS) * sizeof(uint32_t);
+
+size_t select_chunk_slot_bytes(int64_t n_images, bool with_map) {
+    size_t b = align256(CHUNK_HIST_BYTES) + align256((size_t)FINAL_CAP * 8) + align256((size_t)SSW_MAX_TOPK * 8) + 256 +
+               align256((size_t)SSW_MAX_TOPK * 4);
+    if (with_map) b += 2 * align256((size_t)n_images * 4 + 16);
+    return b;
+}
+
+void select_chunk_carve(unsigned char *part, int64_t n_images, bool with_map, ChunkSlot *d) {
+    d->hist = reinterpret_cast<uint32_t *>(part);
+    part += align256(CHUNK_HIST_BYTES);
+    d->cand = reinterpret_cast<uint64_t *>(part);
+    part += align256((size_t)FINAL_CAP * 8);
+    d->out_keys = reinterpret_cast<uint64_t *>(part);
+    part += align256((size_t)SSW_MAX_TOPK * 8);
+    d->out_count = reinterpret_cast<int32_t *>(part);
+    part += 256;
+    d->out_best = reinterpret_cast<uint32_t *>(part);
+    part += align256((size_t)SSW_MAX_TOPK * 4);
+    if (with_map) {
+        d->img_score = reinterpret_cast<float *>(part);
+        part += align256((size_t)n_images * 4 + 16);
+        d->img_best = reinterpret_cast<uint32_t *>(part);
+    }
+}
+
+int64_t select_chunk_excl_cap(int32_t k) { return std::max<int64_t>(0, (int64_t)CHUNK_RANK_MAX - k); }
+
+bool select_chunk_general_ok(int64_t n_images) { return n_images > SELECT_SMALL_IMAGES && n_images < SAMPLE_FROM; }
+
+ssw_status launch_select_chunk(const ChunkTable &tab, int n_general, int n_total, int device, hipStream_t stream,
+                               int *launches) {
+    *launches = 0;
+    if (n_general < 0 || n_total < n_general || n_total < 1 || n_total > SELECT_CHUNK_SLOTS) {
+        set_error("select_chunk: %d general slots of %d outside a chunk of %d", n_general, n_total, SELECT_CHUNK_SLOTS);
+        return SSW_ERR_INVALID;
+    }
+    int64_t g1 = 1, g2 = 1;
+    for (int j = 0; j < n_total; ++j) {
+        const ChunkSlot &d = tab.s[j];
+        const bool general = j < n_general;
+        const int64_t excl_cap = general ? select_chunk_excl_cap(d.k) : (int64_t)CHUNK_AUX_WORDS;
+        if (d.k < 1 || d.k > SSW_MAX_TOPK || d.seq == 0 || d.n_excl < 0 || d.n_excl > excl_cap || (d.small != 0) == general ||
+            (general ? !select_chunk_general_ok(d.n_images) : d.n_images < 1 || d.n_images > SELECT_SMALL_IMAGES) ||
+            (general && d.row_start != nullptr && (d.img_score == nullptr || d.img_best == nullptr)) ||
+            (general && (d.hist == nullptr || d.cand == nullptr)) || d.slab == nullptr || d.packed == nullptr ||
+            d.out_keys == nullptr || d.out_count == nullptr || d.out_best == nullptr ||
+            (d.n_excl > 0 && d.excl_ids == nullptr)) {
+            set_error("select_chunk: slot %d (n_images=%d k=%d n_excl=%d) outside the chunk form", j, d.n_images, d.k,
+                      d.n_excl);
+            return SSW_ERR_INVALID;
+        }
+        if (general) {
+            const int64_t cap = (int64_t)num_cus(device) * 8;
+            const int per1 = d.row_start ? CHUNK_MAP_IMAGES_PER_WG : CHUNK_IMAGES_PER_WG;
+            g1 = std::max(g1, std::min(cap, (d.n_images + (int64_t)per1 - 1) / per1));
+            g2 = std::max(g2, std::min(cap, (d.n_images + (int64_t)CHUNK_IMAGES_PER_WG - 1) / CHUNK_IMAGES_PER_WG));
+        }
+    }
+    static bool lds_done[64] = {false};
+    int dev = 0;
+    SSW_HIP_TRY(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || !lds_done[dev]) {
+        SSW_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_chunk_final),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)CHUNK_FINAL_LDS_BYTES));
+        if (dev >= 0 && dev < 64) lds_done[dev] = true;
+    }
+    if (n_general > 0) {
+        hipLaunchKernelGGL(k_chunk_level1, dim3((unsigned)g1, (unsigned)n_general), dim3(256), 0, stream, tab);
+        hipLaunchKernelGGL(k_chunk_level2, dim3((unsigned)g2, (unsigned)n_general), dim3(256), 0, stream, tab);
+        hipLaunchKernelGGL(k_chunk_collect, dim3((unsigned)g2, (unsigned)n_general), dim3(256), 0, stream, tab);
+        *launches += 3;
+    }
+    hipLaunchKernelGGL(k_chunk_final, dim3((unsigned)n_total), dim3(1024), CHUNK_FINAL_LDS_BYTES, stream, tab);
+    *launches += 1;
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
 }
 
 ssw_status launch_gather_f32(const float *src, const int64_t *idx_dev, int64_t n, float *dst,

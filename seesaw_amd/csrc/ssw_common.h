@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -140,6 +141,32 @@ ssw_status index_wait_topk_slot(ssw_index *idx, hipStream_t on_stream, int slot,
 ssw_status index_collect_topk_slot(ssw_index *idx, hipStream_t on_stream, int slot, unsigned seq, const float *slab,
                                    const int64_t *excluded_images, int64_t n_excluded, int32_t k, int64_t *out_images,
                                    float *out_scores, int64_t *out_best_rows, int32_t *out_count, bool *reran);
+// ... and for a whole chunk at once (chunk selection, ssw_index_set_chunk_select): up to 16 requests, each a slot of its
+// own handle over its own slab with its own exclusions, all on one stream.  index_enqueue_topk_chunk validates every
+// request before it touches anything, selects the requests the chunk form takes (select.hip, "chunk selection") in one
+// set of launches and the others through index_enqueue_topk_slot, and records the route in each request; `after(i)`,
+// if given, is called once request i's selection is on the stream and before another selection can take the device
+// result buffers it left in dev_keys / dev_count (the second stage is enqueued there).  index_collect_topk_chunk is the
+// collect half of one request: the wait on its word, the deep rerun of a flagged slot, the decode.  `owner` holds the
+// counters of ssw_index_chunk_select_stats.
+struct ChunkTopkReq {
+    ssw_index *idx = nullptr;
+    int slot = 0;
+    const float *slab = nullptr;
+    const int64_t *excluded_images = nullptr;
+    int64_t n_excluded = 0;
+    int32_t k = 0;
+    // set by the enqueue half
+    unsigned seq = 0;
+    int route = 0;  // 0: nothing in flight (an index without images), 1: the chunk form, 2: the per-slot selection
+    const uint64_t *dev_keys = nullptr;
+    const int32_t *dev_count = nullptr;
+};
+bool index_chunk_select_on(const ssw_index *idx);
+ssw_status index_enqueue_topk_chunk(ssw_index *owner, ChunkTopkReq *reqs, int n, hipStream_t on_stream,
+                                    const std::function<ssw_status(int)> *after);
+ssw_status index_collect_topk_chunk(ssw_index *owner, hipStream_t on_stream, const ChunkTopkReq &req, int64_t *out_images,
+                                    float *out_scores, int64_t *out_best_rows, int32_t *out_count, bool *reran);
 int index_device(const ssw_index *idx);
 // element type of the resident matrix (SSW_DTYPE_*), its device pointer and shape, for the entries that read it through
 // a handle without index_handle.h (feedback gathers; k-NN and X'LX refuse an f16 matrix)
@@ -575,6 +602,38 @@ ssw_status launch_merge_msgs_batch(const uint64_t *msgs, int32_t world, int64_t 
                                    long long *flags_out, long long *flags_seen, hipStream_t stream);
 ssw_status launch_gather_f32(const float *src, const int64_t *idx_dev, int64_t n, float *dst,
                              hipStream_t stream);
+
+// ---- chunk selection (select.hip, "chunk selection"): the top-k of every slot of a chunk in a number of launches that
+// does not depend on the slot count.  One descriptor a slot, the table in the kernel-argument segment (no upload).
+constexpr int SELECT_CHUNK_SLOTS = 16;
+struct ChunkSlot {
+    const float *slab = nullptr;          // the slot's row scores (image scores without an image map)
+    const int64_t *row_start = nullptr;   // [n_images + 1], or NULL: row = image
+    float *img_score = nullptr;           // [n_images] general form with an image map only
+    uint32_t *img_best = nullptr;
+    uint32_t *hist = nullptr;             // general form: [2 x 4096 bins | 16 state words], zero between selections
+    uint64_t *cand = nullptr;             // general form: [8192]
+    const int64_t *excl_ids = nullptr;    // sorted, distinct (device view of the slot's pinned block)
+    unsigned char *packed = nullptr;      // the slot's pinned result block (device view)
+    uint64_t *out_keys = nullptr;         // [SSW_MAX_TOPK] device results, as SelectWorkspace's
+    int32_t *out_count = nullptr;         // [2]
+    uint32_t *out_best = nullptr;         // [SSW_MAX_TOPK]
+    int32_t n_images = 0, k = 0, n_excl = 0, small = 0;
+    unsigned seq = 0, pad_ = 0;
+};
+struct ChunkTable {
+    ChunkSlot s[SELECT_CHUNK_SLOTS];      // the general-form slots first
+};
+// bytes of one slot's part of a chunk workspace: [hist | cand | out_keys | out_count | out_best], then with_map the
+// per-image maxima; chunk_slot_carve points a descriptor's workspace fields into such a part
+size_t select_chunk_slot_bytes(int64_t n_images, bool with_map);
+void select_chunk_carve(unsigned char *part, int64_t n_images, bool with_map, ChunkSlot *d);
+// the most distinct excluded ids a general-form slot of a chunk takes at this k (select.hip, beside SAMPLE_MAX_K)
+int64_t select_chunk_excl_cap(int32_t k);
+bool select_chunk_general_ok(int64_t n_images);  // SELECT_SMALL_IMAGES < n_images < the sampled threshold's range
+// n_general general-form slots at tab.s[0, n_general), small-form ones behind them up to n_total; *launches: enqueued
+ssw_status launch_select_chunk(const ChunkTable &tab, int n_general, int n_total, int device, hipStream_t stream,
+                               int *launches);
 
 constexpr int SSW_RANK_MAX_ITEMS = 65536;    // rank.hip: items of one counting launch (O(n^2) compares)
 

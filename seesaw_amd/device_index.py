@@ -701,6 +701,32 @@ class DeviceIndex:
             st.update(completions=int(more[0]), rescored_rows=int(more[1]))
         return st
 
+    # -- chunk selection ---------------------------------------------------------------
+    _CHUNK_SELECT_STATS = ("chunks", "slots", "second_level", "per_slot", "deep_reruns", "launches")
+    _chunk_select = False  # a handle starts with the setting off
+
+    @property
+    def chunk_select(self) -> bool:
+        """the batched entries select all slots of a chunk of up to 16 in ONE set of launches (one for slots of at most
+        8192 images, four above) behind one host wait, instead of one selection a slot (ssw_index_set_chunk_select;
+        default off).  Read by `topk_batch` / `topk_batch_avg` and `view_topk_batch` / `_avg` on this handle, by
+        `views_topk_batch` / `_avg` on the PARENT of the views, by `LabelPropagation.round_batch` on its index.
+        Results are bit for bit those with the setting off"""
+        return self._chunk_select
+
+    @chunk_select.setter
+    def chunk_select(self, on: bool):
+        _lib.call("ssw_index_set_chunk_select", self._h, int(bool(on)))
+        self._chunk_select = bool(on)
+
+    def chunk_select_stats(self) -> dict:
+        """counts since the handle was made (ssw_index_chunk_select_stats): `chunks` selected together, `slots` in them,
+        `second_level`: of those the slots that took the second histogram level, `per_slot`: slots sent to the per-slot
+        selection, `deep_reruns` of chunk-selected slots (mass ties), `launches` the chunk form enqueued"""
+        out = np.zeros(6, dtype=np.int64)
+        _lib.call("ssw_index_chunk_select_stats", self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
+        return dict(zip(self._CHUNK_SELECT_STATS, (int(v) for v in out)))
+
     # -- profiling --------------------------------------------------------------------
     def profile(self, enable: bool):
         _lib.call("ssw_index_profile", self._h, int(bool(enable)))

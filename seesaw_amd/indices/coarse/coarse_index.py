@@ -31,7 +31,8 @@ def _positions_of(sorted_dbidx: np.ndarray, ids) -> np.ndarray:
 
 class CoarseIndex(AccessMethod):
     def __init__(self, embedding, vectors: np.ndarray, vector_meta: pd.DataFrame, path: str = None,
-                 device: int = 0, vector_dtype: str = "float32", _view_of=None, _device_index=None):
+                 device: int = 0, vector_dtype: str = "float32", _view_of=None, _device_index=None,
+                 chunk_select: bool = False):
         """vector_dtype="float16": the resident matrix is binary16 and `self.vectors` holds the widened rounded rows
         (what every host-side expression then reads is what the device scans).  `_view_of` (subset_view): (the parent's
         DeviceIndex, the member images' positions in it) -- the device index is then a view of the parent's resident
@@ -58,6 +59,8 @@ class CoarseIndex(AccessMethod):
             assert self._dev.n_rows == self.vectors.shape[0]
         else:
             self._dev = DeviceIndex.from_numpy(self.vectors, device=device, dtype=self.vector_dtype)
+        if chunk_select:  # index_options={"chunk_select": True}: DeviceIndex.chunk_select
+            self._dev.chunk_select = True
 
     def __len__(self):
         return len(self.all_indices)
@@ -71,7 +74,7 @@ class CoarseIndex(AccessMethod):
 
     @staticmethod
     def from_path(index_path: str, *, use_vec_index=False, exclude=None, device: int = 0, vector_dtype: str = "float32",
-                  **_):
+                  chunk_select: bool = False, **_):
         """<index>/vectors.npy [N,512] f32 + <index>/vector_meta.parquet (dbidx, ...) + info.json."""
         index_path = resolve_path(index_path)
         info = json.load(open(f"{index_path}/info.json"))
@@ -81,7 +84,7 @@ class CoarseIndex(AccessMethod):
         meta = pd.read_parquet(f"{index_path}/vector_meta.parquet")
         assert meta.dbidx.is_monotonic_increasing, "sanity check"
         return CoarseIndex(embedding=embedding, vectors=np.asarray(vectors), vector_meta=meta,
-                           path=index_path, device=device, vector_dtype=vector_dtype)
+                           path=index_path, device=device, vector_dtype=vector_dtype, chunk_select=chunk_select)
 
     def query(self, *, topk, vector=None, exclude=None, startk=None, **kwargs):
         exclude = BitMap() if exclude is None else exclude

@@ -191,7 +191,7 @@ class MultiscaleIndex(AccessMethod):
 
     def __init__(self, *, embedding, vectors: np.ndarray, vector_meta: pd.DataFrame, vec_index=None,
                  min_zoom_level=1, path: str = None, excluded: BitMap = None, device: int = 0,
-                 vector_dtype: str = "float32", _view_of=None):
+                 vector_dtype: str = "float32", _view_of=None, chunk_select: bool = False):
         """vector_dtype="float16": the resident matrix is binary16 (half the HBM) and `self.vectors` holds the widened
         rounded rows, so every host-side expression (`index.vectors[rows]` of the fitting loops) reads the numbers the
         device scans.  `_view_of` (subset_view): (the parent's DeviceIndex, the member images' positions in it) -- the
@@ -225,6 +225,8 @@ class MultiscaleIndex(AccessMethod):
         self._resident_q = None
         self._view_of = _view_of
         self._init_device()
+        if chunk_select and self._dev is not None:  # index_options={"chunk_select": True}: DeviceIndex.chunk_select
+            self._dev.chunk_select = True
 
     def _init_device(self):
         """the whole matrix into HBM (a sharded index overrides this with its own slice); for subset_view's index a
@@ -242,7 +244,7 @@ class MultiscaleIndex(AccessMethod):
     # ---- construction -----------------------------------------------------------------
     @staticmethod
     def from_path(index_path: str, *, use_vec_index=True, exclude=None, device: int = 0, vector_dtype: str = "float32",
-                  **options):
+                  chunk_select: bool = False, **options):
         """<index>/info.json {"constructor", "model", ...} plus either the reference's
         <index>/vectors.sorted.cached parquet (as create_multiscale_index writes it) or
         <index>/vectors.npy [N,512] f32 + <index>/vector_meta.parquet; rows sorted by dbidx."""
@@ -261,7 +263,7 @@ class MultiscaleIndex(AccessMethod):
         return MultiscaleIndex(embedding=embedding, vectors=np.asarray(vectors), vector_meta=meta,
                                vec_index=None, path=index_path,
                                excluded=info.get("excluded", None) if exclude is None else exclude, device=device,
-                               vector_dtype=vector_dtype)
+                               vector_dtype=vector_dtype, chunk_select=chunk_select)
 
     def get_knng(self, path=None):
         from ...knn_graph import KNNGraph

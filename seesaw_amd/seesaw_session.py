@@ -279,6 +279,12 @@ class SessionGroup:
     def __init__(self, sessions, prune: bool = False):
         self.sessions = list(sessions)
         self.prune = bool(prune)
+        if self.CHUNK_SELECT:  # the device indexes of the group's sessions, and of views their parents
+            for s in self.sessions:
+                dev = s.loop.q.index._dev  # (None: a sharded index holds no whole-matrix device index)
+                for d in (dev, dev.parent if dev is not None else None):
+                    if d is not None:
+                        d.chunk_select = True
 
     # ---- which sessions go together ---------------------------------------------------------------------------
     @staticmethod
@@ -335,6 +341,11 @@ class SessionGroup:
     # interquartile ranges in profiles/views_batch_ab.txt (tools/perf_views_batch.py); until that file holds a
     # measurement that says so the constant stays None and `next()` keeps today's route.
     MIN_VIEW_GROUP = None
+
+    # True: the group's device indexes select a chunk's slots together (`DeviceIndex.chunk_select`).  It becomes True
+    # only where profiles/chunk_select_ab.txt (tools/perf_chunk_select.py) shows the chunk form ahead of the per-slot
+    # selections by more than both interquartile ranges at every size of `topk_batch` and of the graph round.
+    CHUNK_SELECT = None
 
     def view_groups(self):
         """[(session positions, ...)]: the groups of `query_groups()` that ONE `query_batch_views` can serve together,

@@ -3,7 +3,7 @@
 views_stream_kernel) against the loop of `view.topk` it stands in for, in one process on one GPU (DESIGN.md section 4,
 "Top-k across views of one parent").  SessionGroup.MIN_VIEW_GROUP is read from this tool's output.
 
-    python tools/perf_views_batch.py [--reps 31] [--k 50] [--dtypes float32 float16]
+    python tools/perf_views_batch.py [--reps 31] [--k 50] [--dtypes float32 float16] [--chunk-select]
 
 Parent: 120 000 images x 13 tiles = 1.56 M rows at dim 512.  Views: sixteen seeded random sets of 1 109 images
 (14 417 rows: an LVIS category); `mixed` replaces the first of them by a view of 96 154 images (1.25 M rows, the
@@ -62,7 +62,7 @@ def case(tag, parent, views, args):
         scan_ms = parent.profile_read()
         parent.profile(False)
         out = {"case": tag, "parent_rows": parent.n_rows, "view_rows": [int(v.n_rows) for v in views[:2]], "dim": parent.dim,
-               "dtype": parent.dtype.name, "k": args.k, "slots": s, "reps": args.reps}
+               "dtype": parent.dtype.name, "k": args.k, "slots": s, "reps": args.reps, "chunk_select": bool(parent.chunk_select)}
         stat = {}
         for name in names:
             q1, med, q3 = np.percentile(us[name], [25, 50, 75])
@@ -80,6 +80,8 @@ def main():
     ap.add_argument("--reps", type=int, default=31)
     ap.add_argument("--k", type=int, default=50)
     ap.add_argument("--dtypes", nargs="+", default=["float32", "float16"])
+    ap.add_argument("--chunk-select", action="store_true",
+                    help="the parent's chunk selection on (DeviceIndex.chunk_select): the call selects its slots together")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -89,6 +91,7 @@ def main():
     for name in args.dtypes:
         parent = DeviceIndex.synthetic(n_images * tiles, 512, seed=4, dtype=np.dtype(name))
         parent.set_row2image(np.repeat(np.arange(n_images), tiles).astype(np.int32))
+        parent.chunk_select = args.chunk_select
         rng = np.random.default_rng(11)
         small = [parent.view(np.sort(rng.choice(n_images, 1109, replace=False))) for _ in range(max(SLOTS))]
         large = parent.view(np.sort(rng.choice(n_images, 96_154, replace=False)))
