@@ -1043,6 +1043,10 @@ ssw_status select_alloc(SelectWorkspace &ws, int64_t n_rows, int64_t n_images, b
     SSW_TRY(dev_alloc(&ws.excl_bits, words));
     SSW_HIP_TRY(hipMemset(ws.excl_bits, 0, words * 4));
     SSW_HIP_TRY(hipMemset(ws.out_count, 0, 16));
+    // The memsets run on the null stream and the handles' streams are non-blocking, so nothing orders them with the
+    // first selection: the zeros could land on the bits k_excl_delta had just set, and that selection returned an
+    // excluded image.  Once a handle: wait until they are done before anything is enqueued on the workspace.
+    SSW_HIP_TRY(hipDeviceSynchronize());
     (void)n_rows;
     return SSW_OK;
 }

@@ -11,55 +11,9 @@ a parent without a map, in the slots of one `views_topk_batch` chunk (`test_gene
 import numpy as np
 import pytest
 
+from tests._chunk_select_helpers import DIM, STATS, _index, _on_off, _reference, _same  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-DIM = 256
-STATS = ("chunks", "slots", "second_level", "per_slot", "deep_reruns", "launches")
-
-
-def _reference(scores, row_start, excluded, k):
-    """per-image maximum (lowest row on ties), excluded images removed, (score descending, image ascending), first k"""
-    n_images = row_start.shape[0] - 1
-    best = np.maximum.reduceat(scores, row_start[:-1])
-    image = np.repeat(np.arange(n_images), np.diff(row_start))
-    rows = np.minimum.reduceat(np.where(scores == best[image], np.arange(scores.shape[0]), scores.shape[0]), row_start[:-1])
-    keep = np.ones(n_images, dtype=bool)
-    keep[np.asarray(excluded, dtype=np.int64)] = False
-    ids = np.nonzero(keep)[0]
-    ids = ids[np.lexsort((ids, -best[ids].astype(np.float64)))][:k]
-    return ids, best[ids], rows[ids]
-
-
-def _same(got, want, where):
-    assert len(got) == len(want), where
-    for s, (g, w) in enumerate(zip(got, want)):
-        for a, b in zip(g, w):
-            a, b = np.asarray(a), np.asarray(b)
-            assert a.shape == b.shape, (where, s, "count")
-            assert a.tobytes() == b.tobytes(), (where, s)
-
-
-def _index(rng, n_images, tiles, has_map, dtype, X=None):
-    from seesaw_amd.device_index import DeviceIndex
-    counts = np.full(n_images, tiles[0]) if tiles[0] == tiles[1] else rng.integers(tiles[0], tiles[1] + 1, n_images)
-    n = int(counts.sum())
-    if X is None:
-        X = rng.standard_normal((n, DIM)).astype(np.float32)
-    row2image = np.repeat(np.arange(n_images, dtype=np.int32), counts)
-    idx = DeviceIndex.from_numpy(X, row2image=row2image if has_map else None, dtype=dtype)
-    row_start = np.concatenate(([0], np.cumsum(counts))) if has_map else np.arange(n + 1)
-    return idx, row_start
-
-
-def _on_off(idx, call):
-    """`call()` with the setting off, then on: (off, on, the counters' change over the on call)"""
-    idx.chunk_select = False
-    off = call()
-    idx.chunk_select = True
-    before = idx.chunk_select_stats()
-    on = call()
-    after = idx.chunk_select_stats()
-    return off, on, {key: after[key] - before[key] for key in STATS}
 
 
 @pytest.mark.parametrize("dtype", ["float32", "float16"])
