@@ -62,7 +62,10 @@ typedef struct ssw_index ssw_index;
 
 /* dev_vectors_or_null: borrow an existing device matrix (row-major, 16-byte
  * aligned, must outlive the handle); NULL -> the handle allocates n_rows*dim*4
- * bytes itself.  dim must be a multiple of 256 and <= 1024 (CLIP: 512). */
+ * bytes itself.  dim must be a multiple of 256 and <= 1024 (CLIP: 512), or one
+ * of 384, 640, 896, 1152, 1280: those are served by the scan family alone (scan, top-k, score_rows, gathers, the batched
+ * and the view forms); the pruning shadows, the k-NN build, fill_random, coarse_mean, views_topk_batch, stage2_pair and
+ * the *_dev sharded entries return SSW_ERR_UNSUPPORTED for them. */
 ssw_status ssw_index_create(int32_t device, int64_t n_rows, int32_t dim,
                             const float *dev_vectors_or_null, ssw_index **out);
 /* Element type of the resident matrix.  SSW_DTYPE_F16 stores every element as IEEE binary16, rounded to nearest

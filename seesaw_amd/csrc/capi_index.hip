@@ -107,6 +107,13 @@ ssw_status ssw::refuse_view(const ssw_index *idx, const char *who) {
     return SSW_ERR_UNSUPPORTED;
 }
 
+ssw_status ssw::refuse_dims128(const ssw_index *idx, const char *who) {
+    if (!idx || !scan_dims128(idx->dim)) return SSW_OK;
+    set_error("%s: dim=%d unsupported: the dims that are no multiple of 256 up to 1024 are served by the scan family "
+              "alone (scan, top-k, score_rows, the batched and the view forms)", who, idx->dim);
+    return SSW_ERR_UNSUPPORTED;
+}
+
 const int32_t *ssw::index_view_rows(const ssw_index *idx) { return idx && idx->parent ? idx->row_src_host.data() : nullptr; }
 
 ssw_status ssw::do_scan(ssw_index *idx, const float *q_dev) {
@@ -195,8 +202,8 @@ ssw_status ssw_index_create_typed(int32_t device, int64_t n_rows, int32_t dim, i
         set_error("index: an f16 index keeps its rows in a private layout and cannot borrow a device matrix");
         return SSW_ERR_UNSUPPORTED;
     }
-    if (dim <= 0 || dim % 256 != 0 || dim > 1024) {
-        set_error("index: dim=%d unsupported (need a multiple of 256, <= 1024)", dim);
+    if (!scan_dim_supported(dim)) {
+        set_error("index: dim=%d unsupported (" SSW_SCAN_DIMS_TEXT ")", dim);
         return SSW_ERR_UNSUPPORTED;
     }
     if (n_rows >= (int64_t)0x7fff0000) {
@@ -510,6 +517,7 @@ ssw_status ssw_index_coarse_mean(ssw_index *src, const uint8_t *keep_host, const
         return SSW_ERR_UNSUPPORTED;
     }
     SSW_TRY(refuse_view(dst, "ssw_index_coarse_mean (dst)"));
+    SSW_TRY(refuse_dims128(src, "ssw_index_coarse_mean"));  // k_coarse_mean's lanes sum whole chunks (coarse.hip)
     SSW_REQUIRE(dst != src && dst != src->parent, "ssw_index_coarse_mean: dst holds the rows src reads");
     SSW_REQUIRE(m >= 0 && dst->n == m && dst->dim == src->dim,
                 "ssw_index_coarse_mean: dst is [%lld, %d], need [%lld, %d] (one row a listed image, the source's dim)",
@@ -565,6 +573,7 @@ ssw_status ssw_index_coarse_mean(ssw_index *src, const uint8_t *keep_host, const
 ssw_status ssw_index_fill_random(ssw_index *idx, uint64_t seed, int64_t global_first_row) {
     SSW_REQUIRE(idx != nullptr, "idx is NULL");
     SSW_TRY(refuse_view(idx, "ssw_index_fill_random"));
+    SSW_TRY(refuse_dims128(idx, "ssw_index_fill_random"));  // k_fill_random writes whole chunks (rng.hip)
     DeviceGuard guard(idx->device);
     SSW_TRY(rows_changing(idx));
     SSW_TRY(launch_fill_random(idx->X, idx->dtype, idx->n, idx->dim, seed, global_first_row, idx->stream));

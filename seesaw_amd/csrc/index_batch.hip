@@ -470,6 +470,8 @@ static ssw_status topk_batch_dev_run(ssw_index *idx, const float *q_host, int32_
                                      const int64_t *excluded_offsets, int32_t k, int32_t first_slot, bool pruned) {
     // a view has no exchange target to write into, so the batch that stays on the device has no view form
     SSW_TRY(refuse_view(idx, pruned ? "ssw_index_topk_batch_dev_pruned" : "ssw_index_topk_batch_dev"));
+    // the sharded entries rescore on the owners with rescore_rows.h's whole-chunk fragments
+    SSW_TRY(refuse_dims128(idx, pruned ? "ssw_index_topk_batch_dev_pruned" : "ssw_index_topk_batch_dev"));
     SSW_REQUIRE(nq >= 1, "nq=%d < 1", nq);
     SSW_REQUIRE(idx != nullptr && q_host != nullptr, "NULL argument");
     SSW_TRY(check_batch_target(idx, k, first_slot, nq, "topk_batch_dev"));
@@ -572,6 +574,7 @@ extern "C" ssw_status ssw_index_stage2_avg_batch_dev(ssw_index *idx, const float
                                                      int32_t k, int32_t aug_larger, int64_t image_offset,
                                                      int64_t row_offset, uint64_t *dev_out) {
     SSW_TRY(refuse_view(idx, "ssw_index_stage2_avg_batch_dev"));  // k_avg_score_owner scores tiles from the matrix by row
+    SSW_TRY(refuse_dims128(idx, "ssw_index_stage2_avg_batch_dev"));
     SSW_REQUIRE(nq >= 1, "nq=%d < 1", nq);
     SSW_REQUIRE(k >= 1 && k <= k_max && k_max <= SSW_MAX_TOPK, "k=%d outside [1, k_max=%d], k_max at most %d", k, k_max,
                 SSW_MAX_TOPK);
@@ -623,6 +626,7 @@ extern "C" ssw_status ssw_index_stage2_pair_batch(ssw_index *idx, const float *q
                                                   int64_t *out_best_rows) {
     SSW_REQUIRE(idx != nullptr, "idx is NULL");
     SSW_TRY(refuse_view(idx, "ssw_index_stage2_pair_batch"));  // k_pair_score scores tiles from the matrix by row
+    SSW_TRY(refuse_dims128(idx, "ssw_index_stage2_pair_batch"));  // ... with rescore_rows.h's whole-chunk fragments
     SSW_REQUIRE(nq >= 1 && nq <= 65535, "nq=%d outside [1, 65535]", nq);
     SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
     SSW_REQUIRE(agg == SSW_AGG_PLAIN || agg == SSW_AGG_AVG, "agg=%d is not 0 (plain_score) or 1 (avg_score)", agg);

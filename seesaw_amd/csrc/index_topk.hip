@@ -521,6 +521,7 @@ ssw_status ssw_index_set_excluded(ssw_index *idx, const int64_t *excluded_images
 
 ssw_status ssw_index_topk_dev(ssw_index *idx, const float *q_dev, int32_t k) {
     SSW_REQUIRE(idx != nullptr, "idx is NULL");
+    SSW_TRY(refuse_dims128(idx, "ssw_index_topk_dev"));  // the row-sharded query: its second stage has no such instances
     DeviceGuard guard(idx->device);
     bool candidates = false;
     if (q_dev) SSW_TRY(scan_for_topk(idx, q_dev, k, &candidates));

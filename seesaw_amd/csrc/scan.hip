@@ -68,6 +68,7 @@ struct F32Rows {
     typedef float T;
     template <int C>
     using Frag = RowFrag<C>;
+    static constexpr bool TAIL = false;  // every chunk is a whole one: dim = 256 * C
 
     template <int C, bool NT>
     static __device__ __forceinline__ RowFrag<C> load(const float *__restrict__ X, int row, int lane) {
@@ -102,6 +103,7 @@ struct H16Rows {
     typedef uint16_t T;
     template <int C>
     using Frag = HalfFrag<C>;
+    static constexpr bool TAIL = false;
 
     template <int C, bool NT>
     static __device__ __forceinline__ HalfFrag<C> load(const uint16_t *__restrict__ X, int row, int lane) {
@@ -135,9 +137,202 @@ struct H16Rows {
         return r;
     }
     static __device__ __forceinline__ float4 group4(const uint16_t *row, int e, int dim) {
-        return widen_h16x4(*reinterpret_cast<const u32x2 *>(row + h16_group_pos(e, dim >> 8)));
+        return widen_h16x4(*reinterpret_cast<const u32x2 *>(row + h16_row_pos(e, dim)));
     }
 };
+
+#ifdef SSW_SCAN_DIMS128  // (the formats of scan_dims128.o alone: see the note above launch_scan)
+// ---- rows whose LAST chunk is a half one: dim = 256 * (C - 1) + 128 (384, 640, 896, 1152) --------------------------
+// No padding is stored.  A fragment still holds C chunks; the half chunk is loaded by lanes 0-31 alone (one coalesced
+// 512-byte wave instruction for f32 rows, 256 bytes for f16 rows) and lanes 32-63 hold +0.0 for it, in the query's
+// fragment too (load_query below).  A lane's chains start at +0.0 and fma(0, 0, a) == a, so dot_frag<C> gives every lane
+// the partial it has for the row and the query zero-padded to 256 * C elements: the scores are the bits of the scan of
+// the padded rows at dim 256 * C.  The kernels are the ones above and below, unchanged: only the format differs.
+// Tail form (2), the streaming kernels' (load_group): ONE full-width load brings the half chunks of two rows, lanes 0-31
+// row a's and lanes 32-63 row b's, and v_permlane32_swap against a register of zeros makes both fragments of form (1) out
+// of it: `lo` keeps lanes 0-31 and has +0.0 above, `hi` has the upper half in lanes 0-31 and +0.0 above.
+__device__ __forceinline__ void split_halves(unsigned t, unsigned &lo, unsigned &hi) {
+    const auto r = __builtin_amdgcn_permlane32_swap(t, 0u, false, false);  // t's lanes 32-63 <-> the zeros' lanes 0-31
+    lo = r[0];
+    hi = r[1];
+}
+__device__ __forceinline__ void split_halves(unsigned t, float &lo, float &hi) {
+    unsigned l, h;
+    split_halves(t, l, h);
+    lo = __uint_as_float(l);
+    hi = __uint_as_float(h);
+}
+
+struct F32TailRows {
+    typedef float T;
+    template <int C>
+    using Frag = RowFrag<C>;
+    static constexpr bool TAIL = true;
+    // tail form (2) where it was the faster one: the single scan at dims 384 and 1152 (6.58 against 6.40, 6.90 against
+    // 6.68 TB/s; within the spread at 640 and 896), no width of the batched scan (dim 384: 0.463 against 0.447 ms a query)
+    template <int C>
+    static constexpr bool pair_scan() { return C == 2 || C == 5; }
+    static constexpr bool PAIR_BATCH = false;
+
+    template <int C, bool NT>
+    static __device__ __forceinline__ RowFrag<C> load(const float *__restrict__ X, int row, int lane) {
+        RowFrag<C> r;
+        const float4 *p = reinterpret_cast<const float4 *>(X) + (int64_t)row * (C * 64 - 32) + lane;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            if (c == C - 1 && lane >= 32) {  // past the row's end: never read
+                r.v[c] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            } else if (NT) {
+                const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(p + c * 64));
+                r.v[c] = make_float4(v.x, v.y, v.z, v.w);
+            } else {
+                r.v[c] = p[c * 64];
+            }
+        }
+        return r;
+    }
+    // the fragments of TWO rows, their half chunks with one full-width instruction (lanes 0-31 row_a's, lanes 32-63
+    // row_b's: split_halves).  Lane l's chunk C - 1 is elements 256 * (C - 1) + 4 * l .. +3 of its row or +0.0, as above.
+    template <int C, bool NT>
+    static __device__ __forceinline__ void load2(const float *__restrict__ X, int row_a, int row_b, int lane,
+                                                 RowFrag<C> &a, RowFrag<C> &b) {
+        const int row[2] = {row_a, row_b};
+        RowFrag<C> *const f[2] = {&a, &b};
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const float4 *p = reinterpret_cast<const float4 *>(X) + (int64_t)row[i] * (C * 64 - 32) + lane;
+#pragma unroll
+            for (int c = 0; c < C - 1; ++c) {
+                if (NT) {
+                    const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(p + c * 64));
+                    f[i]->v[c] = make_float4(v.x, v.y, v.z, v.w);
+                } else {
+                    f[i]->v[c] = p[c * 64];
+                }
+            }
+        }
+        const f32x4 *t = reinterpret_cast<const f32x4 *>(X) + (int64_t)(lane < 32 ? row_a : row_b) * (C * 64 - 32) +
+                         (C - 1) * 64 + (lane & 31);
+        f32x4 v;
+        if (NT) v = __builtin_nontemporal_load(t);
+        else v = *t;
+        split_halves(__float_as_uint(v.x), a.v[C - 1].x, b.v[C - 1].x);
+        split_halves(__float_as_uint(v.y), a.v[C - 1].y, b.v[C - 1].y);
+        split_halves(__float_as_uint(v.z), a.v[C - 1].z, b.v[C - 1].z);
+        split_halves(__float_as_uint(v.w), a.v[C - 1].w, b.v[C - 1].w);
+    }
+    template <int C>
+    static __device__ __forceinline__ const RowFrag<C> &widen(const RowFrag<C> &f) { return f; }
+    static __device__ __forceinline__ float4 group4(const float *row, int e, int dim) {
+        return reinterpret_cast<const float4 *>(row)[e >> 2];
+    }
+};
+
+// binary16: the first 256 * (C - 1) elements lane-interleaved as a row of C - 1 chunks (h16_group_pos(e, C - 1)), the
+// half chunk's 128 elements behind them in natural order -- lane l < 32 has its 8-byte group at byte 512 * (C - 1) + 8 * l
+// (ssw_common.h, h16_row_pos)
+struct H16TailRows {
+    typedef uint16_t T;
+    template <int C>
+    using Frag = HalfFrag<C>;
+    static constexpr bool TAIL = true;
+    // tail form (2) where it was the faster one: the single scan at dims 384 and 640 (6.18 against 3.52, 5.50 against
+    // 5.21 TB/s; the slower one at 896 and 1152: 5.79 against 5.86, 5.85 against 6.18), every width of the batched scan
+    // (ms a query at 16 queries: 0.496 / 0.632 / 0.816 / 0.957 against 0.641 / 0.745 / 0.895 / 1.039)
+    template <int C>
+    static constexpr bool pair_scan() { return C <= 3; }
+    static constexpr bool PAIR_BATCH = true;
+
+    // the C - 1 whole chunks of lane l: its 8 * (C - 1) contiguous bytes
+    template <int C, bool NT>
+    static __device__ __forceinline__ void load_body(HalfFrag<C> &r, const unsigned char *row_p, int lane) {
+        constexpr int C0 = C - 1;
+        const unsigned char *p = row_p + lane * (C0 * 8);
+        if constexpr (C0 % 2 == 0) {  // rows are multiples of 256 bytes: the body is 16-byte aligned as in H16Rows
+            const u32x4 *p4 = reinterpret_cast<const u32x4 *>(p);
+#pragma unroll
+            for (int i = 0; i < C0 / 2; ++i) {
+                u32x4 v;
+                if constexpr (NT) v = __builtin_nontemporal_load(p4 + i);
+                else v = p4[i];
+                r.w[2 * i] = u32x2{v.x, v.y};
+                r.w[2 * i + 1] = u32x2{v.z, v.w};
+            }
+        } else {
+            const u32x2 *p2 = reinterpret_cast<const u32x2 *>(p);
+#pragma unroll
+            for (int c = 0; c < C0; ++c) {
+                if constexpr (NT) r.w[c] = __builtin_nontemporal_load(p2 + c);
+                else r.w[c] = p2[c];
+            }
+        }
+    }
+    template <int C, bool NT>
+    static __device__ __forceinline__ HalfFrag<C> load(const uint16_t *__restrict__ X, int row, int lane) {
+        constexpr int C0 = C - 1;
+        HalfFrag<C> r;
+        const unsigned char *row_p = reinterpret_cast<const unsigned char *>(X) + (int64_t)row * (C0 * 512 + 256);
+        load_body<C, NT>(r, row_p, lane);
+        if (lane < 32) {
+            const u32x2 *t = reinterpret_cast<const u32x2 *>(row_p + C0 * 512) + lane;
+            if constexpr (NT) r.w[C0] = __builtin_nontemporal_load(t);
+            else r.w[C0] = *t;
+        } else {
+            r.w[C0] = u32x2{0u, 0u};  // widens to +0.0
+        }
+        return r;
+    }
+    // two rows, their half chunks with one full-width (512-byte) instruction: F32TailRows::load2
+    template <int C, bool NT>
+    static __device__ __forceinline__ void load2(const uint16_t *__restrict__ X, int row_a, int row_b, int lane,
+                                                 HalfFrag<C> &a, HalfFrag<C> &b) {
+        constexpr int C0 = C - 1;
+        const unsigned char *base = reinterpret_cast<const unsigned char *>(X);
+        load_body<C, NT>(a, base + (int64_t)row_a * (C0 * 512 + 256), lane);
+        load_body<C, NT>(b, base + (int64_t)row_b * (C0 * 512 + 256), lane);
+        const u32x2 *t = reinterpret_cast<const u32x2 *>(base + (int64_t)(lane < 32 ? row_a : row_b) * (C0 * 512 + 256) +
+                                                         C0 * 512) + (lane & 31);
+        u32x2 v;
+        if constexpr (NT) v = __builtin_nontemporal_load(t);
+        else v = *t;
+        unsigned ax, ay, bx, by;
+        split_halves(v.x, ax, bx);
+        split_halves(v.y, ay, by);
+        a.w[C0] = u32x2{ax, ay};
+        b.w[C0] = u32x2{bx, by};
+    }
+    template <int C>
+    static __device__ __forceinline__ RowFrag<C> widen(const HalfFrag<C> &f) {
+        RowFrag<C> r;
+#pragma unroll
+        for (int c = 0; c < C; ++c) r.v[c] = widen_h16x4(f.w[c]);
+        return r;
+    }
+    static __device__ __forceinline__ float4 group4(const uint16_t *row, int e, int dim) {
+        return widen_h16x4(*reinterpret_cast<const u32x2 *>(row + h16_row_pos(e, dim)));
+    }
+};
+
+#endif
+
+// Lane l's fragment of the f32 query at q (global memory, or the workgroup's copy in LDS): the float4 at element
+// 256 * c + 4 * l of every chunk; behind a half chunk lanes 32-63 hold +0.0 and read nothing (the query ends there).
+// query_float4: the float4s of one query of the format, the distance between the queries of a batch.
+// The kernels call it for the formats with a half chunk alone and keep their own loop for whole chunks: with the one call
+// for both, which is the same values, the compiler schedules the instances of dims 256-1024 differently (their loads come
+// in another order), and those instances stay what was measured.
+template <class R, int C>
+constexpr int query_float4() { return R::TAIL ? C * 64 - 32 : C * 64; }
+template <class R, int C>
+__device__ __forceinline__ RowFrag<C> load_query(const float4 *q, int lane) {
+    RowFrag<C> f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        if (R::TAIL && c == C - 1 && lane >= 32) f.v[c] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        else f.v[c] = q[c * 64 + lane];
+    }
+    return f;
+}
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -196,11 +391,28 @@ struct Group {
     typename R::template Frag<C> r[U];
 };
 
-template <class R, int C, int U, bool NT>
+// PAIR (the streaming kernels, where tail_paired says so): rows with a half chunk are loaded two at a time, the two half
+// chunks with one full-width instruction (R::load2); a group of one row is loaded as everywhere else.
+// tail_paired: which instances take that form (2) -- those where it beat form (1) by more than the run-to-run spread at
+// 12.5 M rows (profiles/dims128_sweep.txt, the formats' PAIR_* below); every instance has one form.
+template <bool PAIR>
+struct TailPair {};  // load_group's / load_view_group's last argument: the form as a tag
+template <class R, int C, bool BATCH>
+constexpr bool tail_paired() {
+    if constexpr (R::TAIL) return BATCH ? R::PAIR_BATCH : R::template pair_scan<C>();
+    else return false;
+}
+template <class R, int C, int U, bool NT, bool PAIR = false>
 __device__ __forceinline__ void load_group(Group<R, C, U> &g, const typename R::T *__restrict__ X,
-                                           int first_row, int last, int lane) {
+                                           int first_row, int last, int lane, TailPair<PAIR> = {}) {
+    if constexpr (PAIR && U % 2 == 0) {
 #pragma unroll
-    for (int u = 0; u < U; ++u) g.r[u] = R::template load<C, NT>(X, min(first_row + u, last), lane);
+        for (int u = 0; u < U; u += 2)
+            R::template load2<C, NT>(X, min(first_row + u, last), min(first_row + u + 1, last), lane, g.r[u], g.r[u + 1]);
+    } else {
+#pragma unroll
+        for (int u = 0; u < U; ++u) g.r[u] = R::template load<C, NT>(X, min(first_row + u, last), lane);
+    }
 }
 
 template <class R, int C, int U, bool NT>
@@ -218,12 +430,16 @@ __global__ __launch_bounds__(256) void scan_scores_kernel(const typename R::T *_
     if (gwave >= nbatches) return;
 
     RowFrag<C> qf;
+    if constexpr (R::TAIL) {
+        qf = load_query<R, C>(reinterpret_cast<const float4 *>(q), lane);
+    } else {
 #pragma unroll
-    for (int c = 0; c < C; ++c) qf.v[c] = reinterpret_cast<const float4 *>(q)[c * 64 + lane];
+        for (int c = 0; c < C; ++c) qf.v[c] = reinterpret_cast<const float4 *>(q)[c * 64 + lane];
+    }
 
     const int my_group = lane / U;
     Group<R, C, U> cur, nxt;
-    load_group<R, C, U, NT>(cur, X, gwave << 6, last, lane);
+    load_group<R, C, U, NT>(cur, X, gwave << 6, last, lane, TailPair<tail_paired<R, C, false>()>{});
     for (int b = gwave; b < nbatches; b += nwaves) {
         const int row0 = b << 6;
         const int nb = b + nwaves;
@@ -233,7 +449,7 @@ __global__ __launch_bounds__(256) void scan_scores_kernel(const typename R::T *_
         for (int g = 0; g < GPB; ++g) {
             // request group g+1 (or the first group of this wave's next batch) ...
             const int nrow = (g + 1 < GPB) ? row0 + (g + 1) * U : next0;
-            load_group<R, C, U, NT>(nxt, X, nrow, last, lane);
+            load_group<R, C, U, NT>(nxt, X, nrow, last, lane, TailPair<tail_paired<R, C, false>()>{});
             // ... then finish group g
             float acc[U];
 #pragma unroll
@@ -283,13 +499,17 @@ __global__ __launch_bounds__(256) void batch_scores_kernel(const typename R::T *
     RowFrag<C> qf[B];
 #pragma unroll
     for (int b = 0; b < B; ++b) {
+        if constexpr (R::TAIL) {
+            qf[b] = load_query<R, C>(reinterpret_cast<const float4 *>(q) + b * query_float4<R, C>(), lane);
+        } else {
 #pragma unroll
-        for (int c = 0; c < C; ++c) qf[b].v[c] = reinterpret_cast<const float4 *>(q)[(b * C + c) * 64 + lane];
+            for (int c = 0; c < C; ++c) qf[b].v[c] = reinterpret_cast<const float4 *>(q)[(b * C + c) * 64 + lane];
+        }
     }
 
     const int my_run = lane / V;
     Group<R, C, U> cur, nxt;
-    load_group<R, C, U, NT>(cur, X, gwave << 6, last, lane);
+    load_group<R, C, U, NT>(cur, X, gwave << 6, last, lane, TailPair<tail_paired<R, C, true>()>{});
     for (int bt = gwave; bt < nbatches; bt += nwaves) {
         const int row0 = bt << 6;
         const int nb = bt + nwaves;
@@ -308,7 +528,7 @@ __global__ __launch_bounds__(256) void batch_scores_kernel(const typename R::T *
             for (int t = 0; t < T; ++t) {
                 const int g = s * T + t;
                 const int nrow = (g + 1 < GPB) ? row0 + (g + 1) * U : next0;
-                load_group<R, C, U, NT>(nxt, X, nrow, last, lane);
+                load_group<R, C, U, NT>(nxt, X, nrow, last, lane, TailPair<tail_paired<R, C, true>()>{});
                 __builtin_amdgcn_sched_barrier(0);
                 float acc[V];
 #pragma unroll
@@ -366,11 +586,15 @@ __global__ __launch_bounds__(256) void scan_small_kernel(const typename R::T *__
     const int row_base = (blockIdx.x * 4 + wave) * U * steps;
     Group<R, C, U> cur, nxt;
     load_group<R, C, U, false>(cur, X, row_base, last, lane);
-    for (int i = threadIdx.x; i < C * 64; i += 256) ql[i] = reinterpret_cast<const float4 *>(q)[i];
+    for (int i = threadIdx.x; i < query_float4<R, C>(); i += 256) ql[i] = reinterpret_cast<const float4 *>(q)[i];
     __syncthreads();
     RowFrag<C> qf;
+    if constexpr (R::TAIL) {
+        qf = load_query<R, C>(ql, lane);
+    } else {
 #pragma unroll
-    for (int c = 0; c < C; ++c) qf.v[c] = ql[c * 64 + lane];
+        for (int c = 0; c < C; ++c) qf.v[c] = ql[c * 64 + lane];
+    }
     for (int g = 0; g < steps; ++g) {
         const int row0 = row_base + g * U;
         if (row0 >= n) break;
@@ -391,11 +615,18 @@ __global__ __launch_bounds__(256) void scan_small_kernel(const typename R::T *__
 // kernels.  Lanes past the view's last row clamp to it, as load_group does with `last`.  dot_frag / group_reduce<U> and
 // the group order are the unmapped kernels': a view's score is the BITS the parent's scan gives the same row.
 // (The names carry neither "scan" nor "score_rows": tests/test_index_f16_cpu.py pins the kernels so named.)
-template <class R, int C, int U, bool NT>
+template <class R, int C, int U, bool NT, bool PAIR = false>
 __device__ __forceinline__ void load_view_group(Group<R, C, U> &g, const typename R::T *__restrict__ X, int src,
-                                                int first_lane, int lane) {
+                                                int first_lane, int lane, TailPair<PAIR> = {}) {
+    if constexpr (PAIR && U % 2 == 0) {  // load_group's
 #pragma unroll
-    for (int u = 0; u < U; ++u) g.r[u] = R::template load<C, NT>(X, __builtin_amdgcn_readlane(src, first_lane + u), lane);
+        for (int u = 0; u < U; u += 2)
+            R::template load2<C, NT>(X, __builtin_amdgcn_readlane(src, first_lane + u),
+                                     __builtin_amdgcn_readlane(src, first_lane + u + 1), lane, g.r[u], g.r[u + 1]);
+    } else {
+#pragma unroll
+        for (int u = 0; u < U; ++u) g.r[u] = R::template load<C, NT>(X, __builtin_amdgcn_readlane(src, first_lane + u), lane);
+    }
 }
 
 // streaming form: scan_scores_kernel's schedule (persistent grid, 64-row batches, groups of U, register double buffer,
@@ -414,13 +645,17 @@ __global__ __launch_bounds__(256) void view_scores_kernel(const typename R::T *_
     if (gwave >= nbatches) return;
 
     RowFrag<C> qf;
+    if constexpr (R::TAIL) {
+        qf = load_query<R, C>(reinterpret_cast<const float4 *>(q), lane);
+    } else {
 #pragma unroll
-    for (int c = 0; c < C; ++c) qf.v[c] = reinterpret_cast<const float4 *>(q)[c * 64 + lane];
+        for (int c = 0; c < C; ++c) qf.v[c] = reinterpret_cast<const float4 *>(q)[c * 64 + lane];
+    }
 
     const int my_group = lane / U;
     int src = row_src[min((gwave << 6) + lane, last)];
     Group<R, C, U> cur, nxt;
-    load_view_group<R, C, U, NT>(cur, X, src, 0, lane);
+    load_view_group<R, C, U, NT>(cur, X, src, 0, lane, TailPair<tail_paired<R, C, false>()>{});
     for (int b = gwave; b < nbatches; b += nwaves) {
         const int row0 = b << 6;
         const int nb = b + nwaves;
@@ -431,7 +666,8 @@ __global__ __launch_bounds__(256) void view_scores_kernel(const typename R::T *_
         for (int g = 0; g < GPB; ++g) {
             // request group g+1 (or the first group of this wave's next batch) ...
             const bool more = g + 1 < GPB;
-            load_view_group<R, C, U, NT>(nxt, X, more ? src : src_next, more ? (g + 1) * U : 0, lane);
+            load_view_group<R, C, U, NT>(nxt, X, more ? src : src_next, more ? (g + 1) * U : 0, lane,
+                                         TailPair<tail_paired<R, C, false>()>{});
             // ... then finish group g
             float acc[U];
 #pragma unroll
@@ -457,13 +693,17 @@ __global__ __launch_bounds__(256) void view_small_kernel(const typename R::T *__
     const int last = n - 1;
     const int row_base = (blockIdx.x * 4 + wave) * U * steps;
     const int src = row_src[min(row_base + lane, last)];
-    for (int i = threadIdx.x; i < C * 64; i += 256) ql[i] = reinterpret_cast<const float4 *>(q)[i];
+    for (int i = threadIdx.x; i < query_float4<R, C>(); i += 256) ql[i] = reinterpret_cast<const float4 *>(q)[i];
     Group<R, C, U> cur, nxt;
     load_view_group<R, C, U, false>(cur, X, src, 0, lane);
     __syncthreads();
     RowFrag<C> qf;
+    if constexpr (R::TAIL) {
+        qf = load_query<R, C>(ql, lane);
+    } else {
 #pragma unroll
-    for (int c = 0; c < C; ++c) qf.v[c] = ql[c * 64 + lane];
+        for (int c = 0; c < C; ++c) qf.v[c] = ql[c * 64 + lane];
+    }
     for (int g = 0; g < steps; ++g) {
         const int row0 = row_base + g * U;
         if (row0 >= n) break;
@@ -504,14 +744,18 @@ __global__ __launch_bounds__(256) void view_batch_kernel(const typename R::T *__
     RowFrag<C> qf[B];
 #pragma unroll
     for (int b = 0; b < B; ++b) {
+        if constexpr (R::TAIL) {
+            qf[b] = load_query<R, C>(reinterpret_cast<const float4 *>(q) + b * query_float4<R, C>(), lane);
+        } else {
 #pragma unroll
-        for (int c = 0; c < C; ++c) qf[b].v[c] = reinterpret_cast<const float4 *>(q)[(b * C + c) * 64 + lane];
+            for (int c = 0; c < C; ++c) qf[b].v[c] = reinterpret_cast<const float4 *>(q)[(b * C + c) * 64 + lane];
+        }
     }
 
     const int my_run = lane / V;
     int src = row_src[min((gwave << 6) + lane, last)];
     Group<R, C, U> cur, nxt;
-    load_view_group<R, C, U, NT>(cur, X, src, 0, lane);
+    load_view_group<R, C, U, NT>(cur, X, src, 0, lane, TailPair<tail_paired<R, C, true>()>{});
     for (int bt = gwave; bt < nbatches; bt += nwaves) {
         const int row0 = bt << 6;
         const int nb = bt + nwaves;
@@ -526,7 +770,8 @@ __global__ __launch_bounds__(256) void view_batch_kernel(const typename R::T *__
             for (int t = 0; t < T; ++t) {
                 const int g = s * T + t;
                 const bool more = g + 1 < GPB;
-                load_view_group<R, C, U, NT>(nxt, X, more ? src : src_next, more ? (g + 1) * U : 0, lane);
+                load_view_group<R, C, U, NT>(nxt, X, more ? src : src_next, more ? (g + 1) * U : 0, lane,
+                                             TailPair<tail_paired<R, C, true>()>{});
                 __builtin_amdgcn_sched_barrier(0);
                 float acc[V];
 #pragma unroll
@@ -694,8 +939,12 @@ __global__ __launch_bounds__(256) void score_rows_kernel(const typename R::T *__
     const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (w >= n) return;
     RowFrag<C> qf;
+    if constexpr (R::TAIL) {
+        qf = load_query<R, C>(reinterpret_cast<const float4 *>(q), lane);
+    } else {
 #pragma unroll
-    for (int c = 0; c < C; ++c) qf.v[c] = reinterpret_cast<const float4 *>(q)[c * 64 + lane];
+        for (int c = 0; c < C; ++c) qf.v[c] = reinterpret_cast<const float4 *>(q)[c * 64 + lane];
+    }
     const RowFrag<C> x = R::widen(R::template load<C, false>(X, (int)rows[w], lane));
     float v = dot_frag<C>(x, qf);
 #pragma unroll
@@ -788,7 +1037,7 @@ ssw_status launch_scan_t(const void *Xv, const float *q, float *scores, int64_t 
     }
     int blocks_per_cu[16];
     blocks_per_cu[dev_slot] = max_blocks_per_cu[dev_slot];
-    const int cap = g_scan_blocks_per_cu < 0 ? (C == 2 ? 1 : 2) : g_scan_blocks_per_cu;
+    const int cap = g_scan_blocks_per_cu < 0 ? (C == 2 && !R::TAIL ? 1 : 2) : g_scan_blocks_per_cu;  // one: dim 512 alone
     if (cap >= 1 && cap < blocks_per_cu[dev_slot]) blocks_per_cu[dev_slot] = cap;
     if (n >= (int64_t)0x7fff0000) {
         set_error("scan: n=%lld rows exceeds the 2^31 row limit of one index shard", (long long)n);
@@ -889,6 +1138,12 @@ ssw_status launch_score_rows_t(const void *Xv, const float *q_dev, const int64_t
 
 }  // namespace
 
+// This file is compiled twice.  scan.o holds every entry point and the instances of dims 256, 512, 768 and 1024, exactly
+// as before.  scan_dims128.o (-DSSW_SCAN_DIMS128, the section at the end of the file) holds the instances of the dims
+// that are multiples of 128 -- the same kernel templates over F32TailRows / H16TailRows, and five whole chunks at dim
+// 1280 -- compiled without the packed-f32 instructions (Makefile): dot_frag's two chains become scalar fmas there, the
+// same values.  The entry points below hand those dims over.
+#ifndef SSW_SCAN_DIMS128
 // Variants differ in schedule only (rows per group, load policy); numerics are identical.  A binary16 row is half the
 // bytes of an f32 row, so the f16 schedule takes twice the rows per group (one 4-wave block per CU at dim 512 for both).
 ssw_status launch_scan(const void *X, int32_t dtype, const float *q_dev, float *scores, int64_t n, int32_t dim,
@@ -923,9 +1178,11 @@ ssw_status launch_scan(const void *X, int32_t dtype, const float *q_dev, float *
             case 1024: return launch_scan_t<F32Rows, 4, 2, true>(X, q_dev, scores, n, device, stream);
         }
     }
-    set_error("scan: dim=%d unsupported (need a multiple of 256, <= 1024)", dim);
+    if (scan_dims128(dim)) return launch_scan_dims128(X, dtype, q_dev, scores, n, dim, device, stream);
+    set_error("scan: dim=%d unsupported (" SSW_SCAN_DIMS_TEXT ")", dim);
     return SSW_ERR_UNSUPPORTED;
 }
+#endif
 
 namespace {
 // the view's scan in the default schedule of launch_scan_t: small form up to SCAN_SMALL_ROWS rows (inclusive: the
@@ -947,7 +1204,7 @@ ssw_status launch_view_t(const void *Xv, const float *q, const int32_t *row_src,
         return SSW_OK;
     }
     const int64_t nbatches = (n + 63) >> 6;
-    int64_t grid = (int64_t)num_cus(device) * (C == 2 ? 1 : 2);  // launch_scan_t's residency
+    int64_t grid = (int64_t)num_cus(device) * (C == 2 && !R::TAIL ? 1 : 2);  // launch_scan_t's residency
     const int64_t need = (nbatches + 3) / 4;
     if (grid > need) grid = need;
     hipLaunchKernelGGL((view_scores_kernel<R, C, U, true>), dim3((unsigned)grid), dim3(256), 0, stream, X, q, row_src,
@@ -957,6 +1214,7 @@ ssw_status launch_view_t(const void *Xv, const float *q, const int32_t *row_src,
 }
 }  // namespace
 
+#ifndef SSW_SCAN_DIMS128
 // scores[j] = <X[row_src[j], :], q> for j < n_view: the bits launch_scan gives row row_src[j].  row_src [n_view] i32
 // (device), every entry a row of X; the rows per group are launch_scan's defaults.
 ssw_status launch_scan_view(const void *X, int32_t dtype, const float *q_dev, const int32_t *row_src, float *scores,
@@ -981,7 +1239,8 @@ ssw_status launch_scan_view(const void *X, int32_t dtype, const float *q_dev, co
             case 1024: return launch_view_t<F32Rows, 4, 2>(X, q_dev, row_src, scores, n_view, device, stream);
         }
     }
-    set_error("scan: dim=%d unsupported (need a multiple of 256, <= 1024)", dim);
+    if (scan_dims128(dim)) return launch_scan_view_dims128(X, dtype, q_dev, row_src, scores, n_view, dim, device, stream);
+    set_error("scan: dim=%d unsupported (" SSW_SCAN_DIMS_TEXT ")", dim);
     return SSW_ERR_UNSUPPORTED;
 }
 
@@ -1019,7 +1278,7 @@ ssw_status plan_scan_views(ViewSlotTable *t, int32_t ns, int32_t dim, int device
         set_error("scan_views: %d slots outside [1, %d]", ns, VIEWS_MAX_SLOTS);
         return SSW_ERR_INVALID;
     }
-    if (dim != 256 && dim != 512 && dim != 768 && dim != 1024) {
+    if (dim != 256 && dim != 512 && dim != 768 && dim != 1024) {  // (the multi-view kernels have no half-chunk instances)
         set_error("scan_views: dim=%d unsupported (need a multiple of 256, <= 1024)", dim);
         return SSW_ERR_UNSUPPORTED;
     }
@@ -1079,6 +1338,7 @@ ssw_status launch_scan_views(const void *X, int32_t dtype, const ViewSlotTable *
 // from the streaming kernel's range on; 1 = every query goes through launch_scan.  A width asked for through the lab
 // hook is clamped to the widest instance of the shape, so that a chunk is never refused in the middle of a batch.
 int scan_batch_max_width(int64_t n, int32_t dim, int32_t dtype) {
+    if (scan_dims128(dim)) return scan_batch_max_width_dims128(n, dim, dtype);
     const ScanBatchWidths *w = scan_batch_widths(dim);
     if (w == nullptr || n < SCAN_SMALL_ROWS || n >= (int64_t)0x7fff0000) return 1;
     const bool h16 = dtype == SSW_DTYPE_F16;
@@ -1098,6 +1358,7 @@ namespace {
 ssw_status scan_batch_dispatch(const void *X, int32_t dtype, const float *qb_dev, const int32_t *row_src,
                                float *const *slabs, int32_t nb, int64_t n, int32_t dim, int device, hipStream_t stream) {
     const bool h16 = dtype == SSW_DTYPE_F16;
+    if (scan_dims128(dim)) return launch_scan_batch_dims128(X, dtype, qb_dev, row_src, slabs, nb, n, dim, device, stream);
     // <row format, chunks, rows a group, width>.  Rows a group: launch_scan's value at the dim, halved where U * B would
     // pass the 64 partials of one reduce (dim 256) or the registers ask for it.
 #define SSW_BATCH_ARGS (X, qb_dev, row_src, slabs, n, device, stream)
@@ -1199,6 +1460,7 @@ ssw_status launch_scan_view_batch(const void *X, int32_t dtype, const float *qb_
 ssw_status launch_score_rows(const void *X, int32_t dtype, const float *q_dev, const int64_t *rows_dev, int64_t n,
                              int32_t dim, float *out, hipStream_t stream) {
     if (n <= 0) return SSW_OK;
+    if (scan_dims128(dim)) return launch_score_rows_dims128(X, dtype, q_dev, rows_dev, n, dim, out, stream);
     if (dtype == SSW_DTYPE_F16) return launch_score_rows_t<H16Rows>(X, q_dev, rows_dev, n, dim, out, stream);
     return launch_score_rows_t<F32Rows>(X, q_dev, rows_dev, n, dim, out, stream);
 }
@@ -1242,7 +1504,7 @@ __global__ __launch_bounds__(256) void k_rows_to_h16(const float *__restrict__ s
     u32x2 w;
     if constexpr (FROM_F32) w = round_h16x4(reinterpret_cast<const float4 *>(src_f32 + r * dim)[e >> 2]);
     else w = reinterpret_cast<const u32x2 *>(src_h16 + r * dim)[e >> 2];
-    *reinterpret_cast<u32x2 *>(dst + r * dim + h16_group_pos(e, dim >> 8)) = w;
+    *reinterpret_cast<u32x2 *>(dst + r * dim + h16_row_pos(e, dim)) = w;
 }
 
 // one 128-thread block per row, one thread per 4-element group
@@ -1259,7 +1521,7 @@ __global__ void k_gather_rows(const typename R::T *__restrict__ X, const int64_t
 ssw_status launch_rows_to_h16(const float *src_f32, const uint16_t *src_h16, int64_t n, int32_t dim, uint16_t *dst,
                               hipStream_t stream) {
     if (n <= 0) return SSW_OK;
-    if (dim <= 0 || dim % 256 != 0 || dim > 1024) {
+    if (!scan_dim_supported(dim)) {
         set_error("rows_to_h16: dim=%d unsupported", dim);
         return SSW_ERR_UNSUPPORTED;
     }
@@ -1298,5 +1560,140 @@ void tune_scan_batch(int max_width, int blocks_per_cu) {
     g_scan_batch_blocks_per_cu = (blocks_per_cu >= 1 && blocks_per_cu <= 8) ? blocks_per_cu : SCAN_BATCH_BLOCKS_PER_CU;
 }
 #endif
+
+#else  // SSW_SCAN_DIMS128: the instances of dims 384, 640, 896, 1152 and 1280 (scan_dims128.o)
+
+// Rows a group and blocks a CU, chosen as launch_scan chose them: by the bytes a wave keeps in flight (one group), inside
+// the 4 to 10 KiB a group listed below (dims 512 to 1024 keep 4 to 8 KiB), f16 rows taking twice the rows of f32 rows; measured as chosen, not swept
+// ("Dims that are multiples of 128").
+//   dim    chunks      f32 U  f16 U  bytes a group   blocks a CU
+//   384    1 + half      4      8      6 KiB          2 (one, dim 512's residency, read 1.99 TB/s on f16 rows)
+//   640    2 + half      2      4      5 KiB          2
+//   896    3 + half      2      4      7 KiB          2
+//   1152   4 + half      2      4      9 KiB          2
+//   1280   5             2      4     10 KiB          2
+// At two rows of dim 384 a wave would have 3 KiB in flight, less than any dim before it; four rows are dim 768's 6 KiB.
+// At dims 1152 and 1280 one row a group would halve what a wave asks for at a time to under dim 768's, and the two
+// fragment sets of two rows are 80 registers: no pressure.  The small kernels take launch_scan_t's rows a step.
+#define SSW_DIMS128_SHAPES(F, ...)                                              \
+    switch (dim) {                                                              \
+        case 384: return h16 ? F<H16TailRows, 2, 8> __VA_ARGS__ : F<F32TailRows, 2, 4> __VA_ARGS__;  \
+        case 640: return h16 ? F<H16TailRows, 3, 4> __VA_ARGS__ : F<F32TailRows, 3, 2> __VA_ARGS__;  \
+        case 896: return h16 ? F<H16TailRows, 4, 4> __VA_ARGS__ : F<F32TailRows, 4, 2> __VA_ARGS__;  \
+        case 1152: return h16 ? F<H16TailRows, 5, 4> __VA_ARGS__ : F<F32TailRows, 5, 2> __VA_ARGS__; \
+        case 1280: return h16 ? F<H16Rows, 5, 4> __VA_ARGS__ : F<F32Rows, 5, 2> __VA_ARGS__;         \
+    }
+
+namespace {
+template <class R, int C, int U>
+ssw_status scan_nt(const void *X, const float *q, float *scores, int64_t n, int device, hipStream_t stream) {
+    return launch_scan_t<R, C, U, true>(X, q, scores, n, device, stream);
+}
+template <class R, int C, int U>
+ssw_status score_rows_of(const void *Xv, const float *q_dev, const int64_t *rows_dev, int64_t n, float *out,
+                         hipStream_t stream) {
+    const typename R::T *X = static_cast<const typename R::T *>(Xv);
+    hipLaunchKernelGGL((score_rows_kernel<R, C>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, X, q_dev, rows_dev,
+                       n, out);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+}  // namespace
+
+ssw_status launch_scan_dims128(const void *X, int32_t dtype, const float *q_dev, float *scores, int64_t n, int32_t dim,
+                               int device, hipStream_t stream) {
+    const bool h16 = dtype == SSW_DTYPE_F16;
+    SSW_DIMS128_SHAPES(scan_nt, (X, q_dev, scores, n, device, stream))
+    set_error("scan: dim=%d unsupported (" SSW_SCAN_DIMS_TEXT ")", dim);
+    return SSW_ERR_UNSUPPORTED;
+}
+
+ssw_status launch_scan_view_dims128(const void *X, int32_t dtype, const float *q_dev, const int32_t *row_src,
+                                    float *scores, int64_t n_view, int32_t dim, int device, hipStream_t stream) {
+    const bool h16 = dtype == SSW_DTYPE_F16;
+    SSW_DIMS128_SHAPES(launch_view_t, (X, q_dev, row_src, scores, n_view, device, stream))
+    set_error("scan: dim=%d unsupported (" SSW_SCAN_DIMS_TEXT ")", dim);
+    return SSW_ERR_UNSUPPORTED;
+}
+
+ssw_status launch_score_rows_dims128(const void *X, int32_t dtype, const float *q_dev, const int64_t *rows_dev, int64_t n,
+                                     int32_t dim, float *out, hipStream_t stream) {
+    const bool h16 = dtype == SSW_DTYPE_F16;
+    SSW_DIMS128_SHAPES(score_rows_of, (X, q_dev, rows_dev, n, out, stream))
+    set_error("score_rows: dim=%d unsupported", dim);
+    return SSW_ERR_UNSUPPORTED;
+}
+#undef SSW_DIMS128_SHAPES
+
+// The batch widths: the instances whose code objects use no scratch (profiles/dims128_resource_usage.txt), which is
+// scan_batch_widths' rule.  A lane holds B * C float4 of queries: five chunks end at a width of 8, as four do.  The
+// product's width is the widest one built.  f16 rows at dims 384 and 640 have no sixteen-wide instance: they take dim
+// 512's and dim 768's 8, whose sixteen-wide f16 instances were the slower ones (profiles/batch_dims_sweep.txt).  None of
+// the new widths has a sweep of its own yet.
+int scan_batch_max_width_dims128(int64_t n, int32_t dim, int32_t dtype) {
+    if (n < SCAN_SMALL_ROWS || n >= (int64_t)0x7fff0000) return 1;
+    return (dim == 384 || dim == 640) && dtype != SSW_DTYPE_F16 ? 16 : 8;  // the widest instance below
+}
+
+// <row format, chunks, rows a group, width>: launch_scan_dims128's rows a group up to a width of 4 (dim 384: dim 512's two
+// and four, which keep U * B within the 64 partials of one reduce at a width of 16), halved from the width at which the
+// dim with as many whole chunks halves them (scan_batch_dispatch)
+ssw_status launch_scan_batch_dims128(const void *X, int32_t dtype, const float *qb_dev, const int32_t *row_src,
+                                     float *const *slabs, int32_t nb, int64_t n, int32_t dim, int device,
+                                     hipStream_t stream) {
+    const bool h16 = dtype == SSW_DTYPE_F16;
+#define SSW_BATCH_WIDTH(B, R16, R32, C, U16, U32)                                                                      \
+    case B:                                                                                                            \
+        return h16 ? launch_scan_batch_t<R16, C, U16, B>(X, qb_dev, row_src, slabs, n, device, stream)                 \
+                   : launch_scan_batch_t<R32, C, U32, B>(X, qb_dev, row_src, slabs, n, device, stream)
+    switch (dim) {
+        case 384:
+            switch (nb) {
+                SSW_BATCH_WIDTH(2, H16TailRows, F32TailRows, 2, 4, 2);
+                SSW_BATCH_WIDTH(4, H16TailRows, F32TailRows, 2, 4, 2);
+                SSW_BATCH_WIDTH(8, H16TailRows, F32TailRows, 2, 4, 2);
+                case 16:  // (f32 rows alone)
+                    if (!h16) return launch_scan_batch_t<F32TailRows, 2, 2, 16>(X, qb_dev, row_src, slabs, n, device, stream);
+                    break;
+            }
+            break;
+        case 640:
+            switch (nb) {
+                SSW_BATCH_WIDTH(2, H16TailRows, F32TailRows, 3, 4, 2);
+                SSW_BATCH_WIDTH(4, H16TailRows, F32TailRows, 3, 4, 2);
+                SSW_BATCH_WIDTH(8, H16TailRows, F32TailRows, 3, 4, 2);
+                case 16:
+                    if (!h16) return launch_scan_batch_t<F32TailRows, 3, 1, 16>(X, qb_dev, row_src, slabs, n, device, stream);
+                    break;
+            }
+            break;
+        case 896:
+            switch (nb) {
+                SSW_BATCH_WIDTH(2, H16TailRows, F32TailRows, 4, 4, 2);
+                SSW_BATCH_WIDTH(4, H16TailRows, F32TailRows, 4, 4, 2);
+                SSW_BATCH_WIDTH(8, H16TailRows, F32TailRows, 4, 2, 1);
+            }
+            break;
+        case 1152:
+            switch (nb) {
+                SSW_BATCH_WIDTH(2, H16TailRows, F32TailRows, 5, 4, 2);
+                SSW_BATCH_WIDTH(4, H16TailRows, F32TailRows, 5, 4, 2);
+                SSW_BATCH_WIDTH(8, H16TailRows, F32TailRows, 5, 2, 1);
+            }
+            break;
+        case 1280:
+            switch (nb) {
+                SSW_BATCH_WIDTH(2, H16Rows, F32Rows, 5, 4, 2);
+                SSW_BATCH_WIDTH(4, H16Rows, F32Rows, 5, 4, 2);
+                SSW_BATCH_WIDTH(8, H16Rows, F32Rows, 5, 2, 1);
+            }
+            break;
+    }
+#undef SSW_BATCH_WIDTH
+    set_error("scan_batch: width %d at dim %d has no kernel in this build", nb, dim);
+    return SSW_ERR_UNSUPPORTED;
+}
+
+#endif  // SSW_SCAN_DIMS128
 
 }  // namespace ssw

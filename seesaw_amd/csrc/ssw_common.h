@@ -178,6 +178,10 @@ const void *index_matrix(const ssw_index *idx, int64_t *n_rows, int32_t *dim);
 // index that is not a view; index_matrix then reports the PARENT's row count.
 ssw_status refuse_view(const ssw_index *idx, const char *who);
 const int32_t *index_view_rows(const ssw_index *idx);
+// The one refusal of every entry whose kernels read rows as whole 256-element chunks alone, on an index of one of the
+// dims of scan_dims128 below (SSW_ERR_UNSUPPORTED, the message names `who` and the dim); made before anything is
+// enqueued.
+ssw_status refuse_dims128(const ssw_index *idx, const char *who);
 
 // ---- the f16 index's row layout ---------------------------------------------------------------------------------
 // A row of dim = 256*C binary16 elements is stored LANE-INTERLEAVED: the 4*C elements scan lane l works on
@@ -185,6 +189,21 @@ const int32_t *index_view_rows(const ssw_index *idx);
 // byte 8*c inside them.  A row stays dim*2 contiguous bytes; at dim 512 a lane reads its part with one 16-byte load.
 // Position (in elements) of the 4-element group that starts at natural element e (e % 4 == 0) of a row:
 __host__ __device__ inline int h16_group_pos(int e, int C) { return ((e & 255) >> 2) * 4 * C + (e >> 8) * 4; }
+// The dims the scan serves: 256 * C for C <= 4 and, from whole chunks and a HALF one, 384, 640, 896 and 1152 (dim =
+// 256 * C0 + 128), and 1280 (five whole chunks).  scan_dims128: the second group (scan.hip, scan_dims128.o).  No
+// padding is stored for a half chunk: an f32 row is dim floats in natural order; an f16 row keeps the lane-interleaved
+// layout above for its first 256 * C0 elements (as a row of C0 chunks) and the half chunk's 128 elements follow in
+// natural order, so lane l < 32 finds its 8-byte group at byte 512 * C0 + 8 * l.  h16_row_pos: the position (in
+// elements) of the group from natural element e in a row of any served dim.
+#define SSW_SCAN_DIMS_TEXT "need 256, 512, 768 or 1024, or 384, 640, 896, 1152 or 1280"
+inline bool scan_dims128(int32_t dim) { return dim == 384 || dim == 640 || dim == 896 || dim == 1152 || dim == 1280; }
+inline bool scan_dim_supported(int32_t dim) {
+    return (dim > 0 && dim % 256 == 0 && dim <= 1024) || scan_dims128(dim);
+}
+__host__ __device__ inline int h16_row_pos(int e, int dim) {
+    const int C0 = dim >> 8;
+    return e < (C0 << 8) ? h16_group_pos(e, C0) : e;
+}
 // A 4-element group of binary16 is one u32x2.  Widening is exact (v_cvt_f32_f16; the code objects keep f16 denormals,
 // .amdhsa_float_denorm_mode_16_64 3); rounding is to nearest even with subnormals kept and overflow to +-inf
 // (v_cvt_f16_f32: numpy's astype(float16)).
@@ -221,6 +240,17 @@ int scan_view_batch_max_width(int64_t n_view, int32_t dim, int32_t dtype);
 ssw_status launch_scan_view_batch(const void *X, int32_t dtype, const float *qb_dev, const int32_t *row_src,
                                   float *const *slabs, int32_t nb, int64_t n_view, int32_t dim, int device,
                                   hipStream_t stream);
+// the same five entries for the dims of scan_dims128, which the entries above hand over (scan.hip, scan_dims128.o)
+ssw_status launch_scan_dims128(const void *X, int32_t dtype, const float *q_dev, float *scores, int64_t n, int32_t dim,
+                               int device, hipStream_t stream);
+ssw_status launch_score_rows_dims128(const void *X, int32_t dtype, const float *q_dev, const int64_t *rows_dev, int64_t n,
+                                     int32_t dim, float *out, hipStream_t stream);
+ssw_status launch_scan_view_dims128(const void *X, int32_t dtype, const float *q_dev, const int32_t *row_src,
+                                    float *scores, int64_t n_view, int32_t dim, int device, hipStream_t stream);
+int scan_batch_max_width_dims128(int64_t n, int32_t dim, int32_t dtype);
+ssw_status launch_scan_batch_dims128(const void *X, int32_t dtype, const float *qb_dev, const int32_t *row_src_or_null,
+                                     float *const *slabs, int32_t nb, int64_t n, int32_t dim, int device,
+                                     hipStream_t stream);
 // the multi-VIEW form: ns <= VIEWS_MAX_SLOTS slots, slot s a (view, query) pair over ONE parent matrix X, scored in one
 // launch a form -- slot[s].out[j] = dot(X[slot[s].row_src[j],:], slot[s].q) for j < slot[s].n, per slot the bits of
 // launch_scan_view.  The table lives on the device; the host fills slot[0 .. ns) and plan_scan_views fills the rest: the
