@@ -63,8 +63,10 @@ typedef struct ssw_index ssw_index;
 /* dev_vectors_or_null: borrow an existing device matrix (row-major, 16-byte
  * aligned, must outlive the handle); NULL -> the handle allocates n_rows*dim*4
  * bytes itself.  dim must be a multiple of 256 and <= 1024 (CLIP: 512), or one
- * of 384, 640, 896, 1152, 1280: those are served by the scan family alone (scan, top-k, score_rows, gathers, the batched
- * and the view forms); the pruning shadows, the k-NN build, fill_random, coarse_mean, views_topk_batch, stage2_pair and
+ * of 384, 640, 896, 1152, 1280: those are served by the scan family alone
+ * (scan, top-k, score_rows, gathers, the batched and the view forms) and, up
+ * to dim 1152, by the packed 6-bit pruning shadow; the other pruning shadows,
+ * the k-NN build, fill_random, coarse_mean, views_topk_batch, stage2_pair and
  * the *_dev sharded entries return SSW_ERR_UNSUPPORTED for them. */
 ssw_status ssw_index_create(int32_t device, int64_t n_rows, int32_t dim,
                             const float *dev_vectors_or_null, ssw_index **out);
@@ -584,6 +586,9 @@ ssw_status ssw_index_profile_read(ssw_index *idx, float *out_ms, int32_t cap, in
  * rows on, f32 or f16, single queries and pruned batches alike (the smallest size measured; the pruned call is ahead of
  * the full scan at every one); it never gets an int8 shadow, and below that count, or when the shadow is refused for
  * memory, every call is the full-precision one.  [0] and [5] then report that shadow.
+ * Dims 384, 640, 896 and 1152: the same, 3 dim / 4 + 8 = 296 / 488 / 680 / 872 bytes a row, from 2^18 .. 2^22 rows on by
+ * dim, row format and call (csrc/index_prune.hip, MIN_ROWS_DIMS128), at dim 1152 up to 12.5 M rows (MAX_ROWS_DIMS128: above
+ * it too many calls have more survivors than the list holds); dim 1280 has no entry and stays unpruned.
  * From 25 M rows on, single queries on an f32 index of dim 512 or 1024 that has no image map at the time of the call
  * scan a packed 5-bit shadow instead of the 6-bit one -- 5 dim / 8 + 8 = 328 bytes a row at dim 512, (n + 15) / 16 * 16
  * rows of it -- and raise the threshold to the k-th exact score of max(1024, 4 k) candidates before the survivors are

@@ -610,6 +610,7 @@ ssw_status ssw_debug_prune6_shadow(ssw_index *idx, int64_t first_row, int64_t n_
     const Shadow &s = idx->prune.sh[SHADOW_Q6];
     const int dim = idx->dim;
     const size_t tile_bytes = (size_t)16 * dim * 3 / 4;
+    const int words = 3 * dim / 64;  // a lane owns of a tile (q6_word_offset: the tail load of dims 384, 640, 896, 1152)
     const int64_t tile0 = first_row >> 4, tile1 = (first_row + n_rows - 1) >> 4;
     std::vector<unsigned char> packed(out_codes ? (size_t)(tile1 - tile0 + 1) * tile_bytes : 0);
     if (out_codes)
@@ -631,11 +632,11 @@ ssw_status ssw_debug_prune6_shadow(ssw_index *idx, int64_t first_row, int64_t n_
             const int lane = 16 * g + (int)(r & 15);
             int c;
             if (j < 12) {
-                c = (int8_t)tile[q6_word_offset(lane, 3 * u + j / 4) + (size_t)(j % 4)] >> 2;  // arithmetic: sign kept
+                c = (int8_t)tile[q6_word_offset(lane, 3 * u + j / 4, words) + (size_t)(j % 4)] >> 2;  // arithmetic: sign kept
             } else {
                 unsigned bits = 0u;
                 for (int part = 0; part < 3; ++part)
-                    bits = (bits << 2) | (tile[q6_word_offset(lane, 3 * u + part) + (size_t)(j - 12)] & 3u);
+                    bits = (bits << 2) | (tile[q6_word_offset(lane, 3 * u + part, words) + (size_t)(j - 12)] & 3u);
                 c = (int)(bits ^ 32u) - 32;  // six bits, two's complement
             }
             out_codes[(size_t)(r - first_row) * dim + i] = (int8_t)c;
@@ -869,7 +870,7 @@ ssw_status ssw_debug_prune5_shadow(ssw_index *idx, int64_t first_row, int64_t n_
             const int nf = q5_fields(u, j, f);
             unsigned bits = 0u;
             for (int t = 0; t < nf; ++t)
-                bits |= ((tile[q6_word_offset(lane, f[t].word) + (size_t)f[t].byte] >> f[t].lo) & ((1u << f[t].bits) - 1u)) << f[t].from;
+                bits |= ((tile[q6_word_offset(lane, f[t].word, 5 * dim / 128) + (size_t)f[t].byte] >> f[t].lo) & ((1u << f[t].bits) - 1u)) << f[t].from;
             out_codes[(size_t)(r - first_row) * dim + i] = (int8_t)((int)(bits ^ 16u) - 16);  // five bits, two's complement
         }
     }
@@ -995,7 +996,7 @@ ssw_status ssw_debug_prune41_shadow(ssw_index *idx, int64_t first_row, int64_t n
             q6_slot(i, &u, &g, &j);
             q4_nibble(u, j, &word, &byte, &shift);
             out_h[(size_t)(r - first_row) * dim + i] =
-                (uint8_t)((tile[q6_word_offset(16 * g + (int)(r & 15), word) + (size_t)byte] >> shift) & 15u);
+                (uint8_t)((tile[q6_word_offset(16 * g + (int)(r & 15), word, dim / 32) + (size_t)byte] >> shift) & 15u);
         }
     }
     return SSW_OK;

@@ -12,7 +12,7 @@ using namespace ssw;
 // survivors exactly; the score buffer then holds exact scores for the survivors and lower bounds elsewhere
 // (scores_partial) until a consumer that reads all of it materialises the full scan of the kept query; the second-stage
 // readers make exact the rows they read (rescore_rows) and leave it partial.
-constexpr int64_t NO_SHADOW = INT64_MAX;  // the int8 shadow at dim 768: no such shadow (q8_dim_supported)
+constexpr int64_t NO_SHADOW = INT64_MAX;  // the int8 shadow at dim 768 and at the dims of q6_dims128: no such shadow (q8_dim_supported)
 // The rows from which a call is pruned on a shadow: [ShadowKind][single call, batch][dim 256 / 512 / 1024, dim 768]
 // [f32, f16 rows].  The two row formats are measured separately and need not stay equal.
 constexpr int64_t MIN_ROWS[2][2][2][2] = {
@@ -72,6 +72,56 @@ constexpr int64_t MIN_ROWS[2][2][2][2] = {
       // (0.019); 50 M rows: 0.651 against 24.837 and 1.615 against 28.876.  f16, 2^20 rows: 0.110 against 0.336 (0.005)
       // and 0.138 against 0.385 (0.008).
       {(int64_t)1 << 20, (int64_t)1 << 20}}}};
+// ---- SHADOW_Q6 at the dims of q6_dims128 ----
+// Dims 384, 640, 896, 1152 and 1280 have the 6-bit shadow alone, as dim 768 has (296, 488, 680, 872 and 968 bytes a row
+// against 4 dim of f32 and 2 dim of f16 rows), so a pruned call's alternative is the full scan or the plain batch, and the
+// int8 entries are NO_SHADOW (prune_min_rows).  [single call, batch][dim 384, 640, 896, 1152, 1280][f32, f16 rows]: entries
+// of their own under the rule above, governed by ssw_tune_prune6 / ssw_tune_prune6_batch alone.
+// Measured on Gaussian rows normalised to unit length, the pruned call and its alternative alternating in one process:
+// single call tools/perf_prune.py --dim D (profiles/prune6_dims128_sweep.txt, ms a call, full / 6-bit, medians of 20),
+// batch tools/perf_prune_batch.py --dim D --nq 16 4 (profiles/prune6_dims128_batch.txt, ms a query, plain / pruned, medians
+// of 5; an entry has to clear at both widths).  Sizes: 2^18, 2^20, 2^22 and 12.5 M rows at every dim, 2^24 and 2^25 at dims
+// 384 to 1152, 2^23 at dims 896 and 1152, and at dim 896 50 M f32 rows and 2^26 and 100 M f16 rows, about what one device
+// holds beside the shadow; 2^19 and 2^21 rows were not measured.  Each entry is the smallest measured size from which the
+// pruned call is ahead by more than both spreads, there and at every larger measured size up to the dim's MAX_ROWS_DIMS128.
+// The survivors grow with the dim and the rows (medians at 12.5 M rows: 10 700, 40 100, 105 700 and 224 900 at dims
+// 384 .. 1152), and a call whose survivors pass SURV_CAP = 2^18 pays the shadow scan and then the full scan.  An index of
+// more rows than its dim's entry here is therefore not pruned, single call or batch, f32 or f16 rows (the survivors do not
+// depend on the dtype): the largest measured size that clears the rule above, NO_MAX where every measured size does.
+// Dims 384 and 640: 13 700 and 55 300 survivors at 2^25 rows, 1.995 against 7.968 and 2.851 against 12.683 ms a call.
+// Dim 896: no call fell back up to 2^26 rows (203 800 survivors, at most 238 600); at 100 M f16 rows, the most a device
+// holds, 231 800 (at most 254 500), no single call and 10 of 280 batch queries fell back and the pruned forms stay ahead:
+// 10.971 against 30.227 ms a call, 3.304 against 7.694 ms a query at nq = 16 (spreads 3.752 together).
+// Dim 1152: 12.5 M rows (2.094 against 8.487 ms a call; 2 of 224 batch queries fell back, 0.528 against 1.846 ms a query,
+// spreads 0.527).  At 2^24 rows 8 of 23 single calls and 90 of 280 batch queries fell back: the single call's median is
+// ahead (2.844 against 11.244) inside a spread of 11.017, the nq = 16 batch is behind (4.679 against 2.257 f32, 2.413
+// against 1.631 f16); at 2^25 rows every call fell back (27.244 against 22.491 ms a call, 23.204 against 3.221 a query).
+// Dim 1280: every call of 12.5 M rows fell back (11.434 against 9.482 ms f32, 9.889 against 7.921 f16; batch 9.729 against
+// 1.442 ms a query) and nothing between 2^22 rows, where it is ahead (0.953 against 3.187 ms), and there was measured; its
+// MIN_ROWS entries are NO_SHADOW, so a dim-1280 index is pruned by the lab switches alone and this entry is never read.
+constexpr int64_t NO_MAX = INT64_MAX;
+constexpr int64_t MAX_ROWS_DIMS128[5] = {NO_MAX, NO_MAX, NO_MAX, 12500000, NO_MAX};
+constexpr int64_t MIN_ROWS_DIMS128[2][5][2] = {
+    {// single call
+     {(int64_t)1 << 20,   // 384 f32: 0.148 against 0.280 (spreads 0.079); at 2^18 0.099 against 0.108, inside them
+      (int64_t)1 << 22},  // 384 f16: 0.332 against 0.569 (0.043); at 2^20 ahead by 0.021 with spreads of 0.024
+     {(int64_t)1 << 18,   // 640 f32: 0.113 against 0.146 (0.027), the smallest size of the sweep
+      (int64_t)1 << 20},  // 640 f16: 0.187 against 0.300 (0.032); level at 2^18
+     {(int64_t)1 << 18,   // 896 f32: 0.137 against 0.182 (0.023)
+      (int64_t)1 << 20},  // 896 f16: 0.242 against 0.378 (0.026); behind at 2^18
+     {(int64_t)1 << 18,   // 1152 f32: 0.168 against 0.219 (0.018); up to MAX_ROWS_DIMS128
+      (int64_t)1 << 20},  // 1152 f16: 0.308 against 0.447 (0.042); behind at 2^18
+     {NO_SHADOW, NO_SHADOW}},
+    {// the pruned batch against the plain batch, nq = 16 / nq = 4
+     {(int64_t)1 << 22,   // 384 f32: 0.144 against 0.241 / 0.194 against 0.602; behind at 2^20 and nq = 16
+      (int64_t)1 << 22},  // 384 f16: 0.142 against 0.227 / 0.192 against 0.376; behind at 2^20 and nq = 16
+     {(int64_t)1 << 20,   // 640 f32: 0.111 against 0.142 (0.008) / 0.130 against 0.251
+      (int64_t)1 << 22},  // 640 f16: 0.161 against 0.297 / 0.229 against 0.545; level at 2^20 and nq = 16
+     {(int64_t)1 << 20,   // 896 f32: 0.126 against 0.165 (0.007) / 0.156 against 0.333
+      (int64_t)1 << 20},  // 896 f16: 0.116 against 0.124 (0.003) / 0.147 against 0.205 (0.015)
+     {(int64_t)1 << 20,   // 1152 f32: 0.164 against 0.190 (0.005) / 0.194 against 0.417
+      (int64_t)1 << 22},  // 1152 f16: 0.241 against 0.447 / 0.359 against 0.893; level at 2^20 and nq = 16
+     {NO_SHADOW, NO_SHADOW}}};
 // ---- SHADOW_Q5 ----
 // Single queries on an f32 index of dim 512 or 1024 without an image map and of at least this many rows scan the packed
 // 5-bit shadow (328 instead of 392 bytes a row at dim 512) and raise the threshold to the k-th exact score of a
@@ -164,13 +214,25 @@ static int64_t prune_min_rows(const ssw_index *idx, ShadowKind kind, bool batch)
     if (kind == SHADOW_Q5) return g_prune5_min_rows >= 0 ? g_prune5_min_rows : MIN_ROWS_Q5;  // ssw_tune_prune5's alone
     if (kind == SHADOW_Q41) return g_prune41_min_rows >= 0 ? g_prune41_min_rows : MIN_ROWS_Q41;  // ssw_tune_prune41's alone
     const int64_t lab = kind == SHADOW_Q8 ? g_prune_min_rows : batch ? g_prune6_batch_min_rows : g_prune6_min_rows;
-    return lab >= 0 ? lab : MIN_ROWS[kind][batch][idx->dim == 768][idx->dtype == SSW_DTYPE_F16];
+    if (lab >= 0) return lab;
+    const bool f16 = idx->dtype == SSW_DTYPE_F16;
+    if (q6_dims128(idx->dim))  // 384, 640, 896, 1152, 1280 -> 0 .. 4; no int8 shadow
+        return kind == SHADOW_Q8 ? NO_SHADOW : MIN_ROWS_DIMS128[batch][idx->dim == 1280 ? 4 : idx->dim / 256 - 1][f16];
+    return MIN_ROWS[kind][batch][idx->dim == 768][f16];
+}
+
+// MAX_ROWS_DIMS128's entry for the index: the 6-bit shadow's alone; the lab build's row count in ssw_tune_prune6 lifts it,
+// as it replaces the entry of MIN_ROWS_DIMS128 (the tools measure past the bound with it)
+static int64_t prune_max_rows(const ssw_index *idx, ShadowKind kind) {
+    if (kind != SHADOW_Q6 || !q6_dims128(idx->dim) || g_prune6_min_rows >= 0) return INT64_MAX;
+    return MAX_ROWS_DIMS128[idx->dim == 1280 ? 4 : idx->dim / 256 - 1];
 }
 
 static bool prune_eligible_on(const ssw_index *idx, ShadowKind kind, bool batch) {
     return g_prune && (kind != SHADOW_Q6 || g_prune6) && (kind != SHADOW_Q5 || g_prune5) && (kind != SHADOW_Q41 || g_prune41) &&
            !prune_forced_off() &&
-           idx->owns_X && !idx->rows_escaped && idx->n >= prune_min_rows(idx, kind, batch) && idx->n_images > 0 &&
+           idx->owns_X && !idx->rows_escaped && idx->n >= prune_min_rows(idx, kind, batch) &&
+           idx->n <= prune_max_rows(idx, kind) && idx->n_images > 0 &&
            SHADOW[kind].dim_ok(idx->dim);
 }
 // the 5-bit shadow: single queries on f32 rows of an index that has no image map at the time of the call (its exact
@@ -583,7 +645,7 @@ ssw_status ssw_index_prune_stats(ssw_index *idx, int64_t *out6) {
     SSW_REQUIRE(idx != nullptr && out6 != nullptr, "NULL argument");
     const PruneState &p = idx->prune;
     // the state of the shadow single queries use: the 6-bit one where it applies and was not refused
-    // (a dim-768 index has no other: there a refusal is the 6-bit shadow's)
+    // (an index of dim 768 or of a dim of q6_dims128 has no other: there a refusal is the 6-bit shadow's)
     const Shadow &q8 = p.sh[SHADOW_Q8], &q6 = p.sh[SHADOW_Q6], &q5 = p.sh[SHADOW_Q5], &q41 = p.sh[SHADOW_Q41];
     const bool six = prune6_eligible(idx) && (!q6.refused || !q8_dim_supported(idx->dim));
     const bool five = prune5_eligible(idx) && !q5.refused;  // ... and before it the 5-bit one, on the same terms

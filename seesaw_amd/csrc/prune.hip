@@ -52,16 +52,18 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 // lane 0 writes.  The codes and s_r do not depend on the assignment; a_r's double sums are taken in its order.
 // LEVELS: the largest |code|, 127 for the int8 shadow, 31 for the packed 6-bit one (k_q6_build).
 // s_out / ok_out (k_q41_build only, else NULL): the row's s_r and whether the row can be bounded, in every lane.
-template <int C, int LEVELS = 127>
-__device__ __forceinline__ void q8_quantise_row(const float (&x)[4 * C], int64_t r, int lane, unsigned (&packed)[C],
-                                                float *__restrict__ scale, float *__restrict__ err,
-                                                float *s_out = nullptr, bool *ok_out = nullptr) {
-    constexpr int dim = 256 * C;
+// quantise_row: the same for E elements a lane of a row of 64 E (E = 4 C, or 2 H for a dim of 128 H: the last word of
+// packed is half full where E % 4 == 2); q8_quantise_row<C> is quantise_row<4 C>.
+template <int E, int LEVELS>
+__device__ __forceinline__ void quantise_row(const float (&x)[E], int64_t r, int lane, unsigned (&packed)[(E + 3) / 4],
+                                             float *__restrict__ scale, float *__restrict__ err,
+                                             float *s_out = nullptr, bool *ok_out = nullptr) {
+    constexpr int dim = 64 * E;
     constexpr float LV = (float)LEVELS;
     float m = 0.0f;
     bool finite = true;
 #pragma unroll
-    for (int i = 0; i < 4 * C; ++i) {
+    for (int i = 0; i < E; ++i) {
         finite = finite && isfinite(x[i]);
         m = fmaxf(m, fabsf(x[i]));
     }
@@ -73,9 +75,9 @@ __device__ __forceinline__ void q8_quantise_row(const float (&x)[4 * C], int64_t
     if (ok_out) *ok_out = ok;
     double e2 = 0.0, x2 = 0.0, c2 = 0.0;
 #pragma unroll
-    for (int c = 0; c < C; ++c) packed[c] = 0u;
+    for (int c = 0; c < (E + 3) / 4; ++c) packed[c] = 0u;
 #pragma unroll
-    for (int i = 0; i < 4 * C; ++i) {
+    for (int i = 0; i < E; ++i) {
         float q = s > 0.0f ? rintf(x[i] / s) : 0.0f;
         q = fminf(fmaxf(q, -LV), LV);
         const int ci = (int)q;
@@ -96,6 +98,12 @@ __device__ __forceinline__ void q8_quantise_row(const float (&x)[4 * C], int64_t
         scale[r] = s;
         err[r] = ok ? __double2float_ru(a) : INFINITY;
     }
+}
+template <int C, int LEVELS = 127>
+__device__ __forceinline__ void q8_quantise_row(const float (&x)[4 * C], int64_t r, int lane, unsigned (&packed)[C],
+                                                float *__restrict__ scale, float *__restrict__ err,
+                                                float *s_out = nullptr, bool *ok_out = nullptr) {
+    quantise_row<4 * C, LEVELS>(x, r, lane, packed, scale, err, s_out, ok_out);
 }
 
 // f32 rows: lane l converts the 4C elements 4C*l .. 4C*l + 4C - 1 (natural order, C = dim / 256)
@@ -815,7 +823,10 @@ __global__ __launch_bounds__(256) void k_scatter_scores(const int64_t *__restric
 // which owns 3 dim / 64 words of the tile; k-step u = i / 64 takes its words 3u .. 3u + 2, slot j = i % 16: slots 0 ..
 // 11 are the upper six bits of those twelve bytes, slot 12 + b is spread over the low two bits of byte b of the three
 // words (code bits 5:4, 3:2, 1:0).  Word wi of lane l is the four bytes at (wi / 4) * 1024 + 16 l + 4 (wi % 4) of the
-// tile: every wave load instruction reads 1 KiB contiguous.  The state words are a slot's of the chunk (MQ_WORDS).
+// tile: every wave load instruction reads 1 KiB contiguous.  At dims 384, 640, 896 and 1152 a lane's 3 dim / 64 words
+// end in half a 16-byte word: its last two words are the eight bytes at (3 dim / 256) * 1024 + 8 l, ONE 512-byte wave
+// load after the whole ones (q6_word_offset with the words a lane; Q6TilesH below); dim 1280 is fifteen whole loads.
+// The state words are a slot's of the chunk (MQ_WORDS).
 // Query operand: k-step u, lane l: the u32x4 at u * 64 + l holds the hi plane's codes of elements 64 u + 16 (l >> 4) + j
 // in column 0 (l & 15 == 0), the lo plane's in column 1, zeros elsewhere (written once, when the buffer is made).
 constexpr int Q6_BLOCKS_PER_CU = 1;
@@ -828,14 +839,16 @@ constexpr int q6_default_tiles(int C) { return C == 1 ? 2 : 1; }
 
 // 31 sqrt(dim), rounded up
 __host__ __device__ constexpr double q6_code_norm(int dim) {
-    return dim == 256 ? 496.0 : dim == 512 ? 701.4499270 : dim == 768 ? 859.0972006 : 992.0;
+    return dim == 256 ? 496.0 : dim == 512 ? 701.4499270 : dim == 768 ? 859.0972006 : dim == 1024 ? 992.0
+           : dim == 384 ? 607.4734563 : dim == 640 ? 784.2448598 : dim == 896 ? 927.9310320
+           : dim == 1152 ? 1052.1748905 : 1109.0897169;  // (1280)
 }
 
 // The tile assembly both builders share: cl is the wave's LDS line with the codes of row r in natural element order,
 // one byte each; lane l assembles words l, l + 64, .. of the row's 12 dim / 64 and stores each at its place in the tile.
-template <int C>
+template <int dim>
 __device__ __forceinline__ void q6_store_row(const int8_t *cl, int64_t r, int lane, unsigned char *__restrict__ codes) {
-    constexpr int dim = 256 * C, KS = dim / 64, WPL = 3 * KS;  // words a lane of the tile owns
+    constexpr int KS = dim / 64, WPL = 3 * KS;  // words a lane of the tile owns
     constexpr size_t TILE_BYTES = (size_t)16 * dim * 3 / 4;
     unsigned char *tile = codes + (size_t)(r >> 4) * TILE_BYTES;
     for (int w = lane; w < 4 * WPL; w += 64) {
@@ -846,7 +859,7 @@ __device__ __forceinline__ void q6_store_row(const int8_t *cl, int64_t r, int la
             const int main_c = cl[q6_element(u, g, 4 * part + b)], low_c = cl[q6_element(u, g, 12 + b)];
             word |= ((((unsigned)main_c & 0x3fu) << 2) | (((unsigned)low_c >> (4 - 2 * part)) & 3u)) << (8 * b);
         }
-        *reinterpret_cast<unsigned *>(tile + q6_word_offset(16 * g + (int)(r & 15), wi)) = word;
+        *reinterpret_cast<unsigned *>(tile + q6_word_offset(16 * g + (int)(r & 15), wi, WPL)) = word;
     }
 }
 
@@ -873,7 +886,7 @@ __global__ __launch_bounds__(256) void k_q6_build(const float *__restrict__ X, i
 #pragma unroll
         for (int c = 0; c < C; ++c) line[wave][lane * C + c] = packed[c];
         __builtin_amdgcn_wave_barrier();
-        q6_store_row<C>(cl, r, lane, codes);
+        q6_store_row<256 * C>(cl, r, lane, codes);
     }
 }
 
@@ -897,7 +910,76 @@ __global__ __launch_bounds__(256) void k_q6_build_h16(const uint16_t *__restrict
 #pragma unroll
         for (int c = 0; c < C; ++c) line[wave][64 * c + lane] = packed[c];
         __builtin_amdgcn_wave_barrier();
-        q6_store_row<C>(cl, r, lane, codes);
+        q6_store_row<256 * C>(cl, r, lane, codes);
+    }
+}
+
+// ---- the builders at dim = 128 H for H = 3, 5, 7, 9 (a half chunk after the whole ones) and H = 10 (dim 1280) ------------
+// One wave a row through its LDS line as above, 2 H elements a lane (quantise_row<2 H, 31>), the line in 16-bit words of
+// two codes.  f32 rows: pair j of lane l is the natural elements 128 j + 2 l, + 1, so a wave's load of a pair is 512
+// contiguous bytes and its codes are word 64 j + l of the line.
+template <int H>
+__global__ __launch_bounds__(256) void k_q6_build_dims128(const float *__restrict__ X, int64_t n,
+                                                          unsigned char *__restrict__ codes, float *__restrict__ scale,
+                                                          float *__restrict__ err) {
+    constexpr int dim = 128 * H;
+    __shared__ unsigned short line[4][64 * H];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int8_t *cl = reinterpret_cast<const int8_t *>(line[wave]);
+    for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < n; r += (int64_t)gridDim.x * 4) {
+        const float2 *src = reinterpret_cast<const float2 *>(X + r * dim) + lane;
+        float x[2 * H];
+#pragma unroll
+        for (int j = 0; j < H; ++j) {
+            const float2 v = src[64 * j];
+            x[2 * j] = v.x, x[2 * j + 1] = v.y;
+        }
+        unsigned packed[(H + 1) / 2];
+        quantise_row<2 * H, 31>(x, r, lane, packed, scale, err);
+        __builtin_amdgcn_wave_barrier();  // as in k_q6_build
+#pragma unroll
+        for (int j = 0; j < H; ++j) line[wave][64 * j + lane] = (unsigned short)(packed[j >> 1] >> (16 * (j & 1)));
+        __builtin_amdgcn_wave_barrier();
+        q6_store_row<dim>(cl, r, lane, codes);
+    }
+}
+
+// The same from binary16 rows in the f16 index's layout (ssw_common.h, h16_row_pos): the C0 = H / 2 whole chunks are
+// lane-interleaved as a row of C0 chunks (lane l: its 8 C0 bytes at 8 C0 l, chunk c of them the natural elements
+// 256 c + 4 l .. + 3, words 128 c + 2 l, + 1 of the line), and for odd H the half chunk follows in natural order: lane l
+// takes its elements 256 C0 + 2 l, + 1 (four bytes at 512 C0 + 4 l, word 128 C0 + l of the line), so all 64 lanes hold
+// 2 H elements.  A lane's part of the whole chunks is only 8-byte aligned for odd C0: one 8-byte load a chunk.
+template <int H>
+__global__ __launch_bounds__(256) void k_q6_build_h16_dims128(const uint16_t *__restrict__ X, int64_t n,
+                                                              unsigned char *__restrict__ codes, float *__restrict__ scale,
+                                                              float *__restrict__ err) {
+    constexpr int dim = 128 * H, C0 = H / 2;
+    __shared__ unsigned short line[4][64 * H];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int8_t *cl = reinterpret_cast<const int8_t *>(line[wave]);
+    for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < n; r += (int64_t)gridDim.x * 4) {
+        const unsigned char *row = reinterpret_cast<const unsigned char *>(X + r * dim);
+        float x[2 * H];
+#pragma unroll
+        for (int c = 0; c < C0; ++c) {
+            const float4 v = widen_h16x4(*reinterpret_cast<const u32x2 *>(row + (size_t)lane * 8 * C0 + 8 * c));
+            x[4 * c] = v.x, x[4 * c + 1] = v.y, x[4 * c + 2] = v.z, x[4 * c + 3] = v.w;
+        }
+        if constexpr (H % 2 != 0) {
+            const float4 v = widen_h16x4(u32x2{*reinterpret_cast<const unsigned *>(row + 512 * C0 + 4 * lane), 0u});
+            x[4 * C0] = v.x, x[4 * C0 + 1] = v.y;
+        }
+        unsigned packed[(H + 1) / 2];
+        quantise_row<2 * H, 31>(x, r, lane, packed, scale, err);
+        __builtin_amdgcn_wave_barrier();  // as in k_q6_build
+#pragma unroll
+        for (int c = 0; c < C0; ++c) {
+            line[wave][128 * c + 2 * lane] = (unsigned short)packed[c];
+            line[wave][128 * c + 2 * lane + 1] = (unsigned short)(packed[c] >> 16);
+        }
+        if constexpr (H % 2 != 0) line[wave][128 * C0 + lane] = (unsigned short)packed[C0];
+        __builtin_amdgcn_wave_barrier();
+        q6_store_row<dim>(cl, r, lane, codes);
     }
 }
 
@@ -941,10 +1023,23 @@ struct PackedTiles {
     }
 };
 
-// Codes policy of tile_scan: the packed 6-bit shadow, (***): three words a k-step.
-// Unpack, per 16 codes = one k-step of a lane (ISA of k_q6_bounds<2, 2>: 3 v_and_b32 with 0xfcfcfcfc for the three
+// The ONE unpack of the packed 6-bit shadow, of both Codes policies below, over a lane's 3 KS words: three words a k-step.
+// Per 16 codes = one k-step of a lane (ISA of k_q6_bounds<2, 2>: 3 v_and_b32 with 0xfcfcfcfc for the three
 // operand words 4c, and for the fourth 3 v_and_b32 with 0x03030303, 3 v_lshlrev_b32 and 1 v_or3_b32): 10 VALU
 // instructions, no sign extension.  Then one v_mfma_i32_16x16x64_i8 a query plane.
+template <int KS, int NL, int PLANES>
+__device__ __forceinline__ void q6_products(const u32x4 (&c)[NL], const i32x4 (&q)[KS][PLANES], i32x4 (&acc)[PLANES]) {
+    unsigned w[4 * NL];
+    PackedTiles<NL>::words(c, w);
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        const unsigned w0 = w[3 * ks], w1 = w[3 * ks + 1], w2 = w[3 * ks + 2];
+        const i32x4 a = {(int)(w0 & 0xfcfcfcfcu), (int)(w1 & 0xfcfcfcfcu), (int)(w2 & 0xfcfcfcfcu),
+                         (int)(((w0 & 0x03030303u) << 6) | ((w1 & 0x03030303u) << 4) | ((w2 & 0x03030303u) << 2))};
+        mq_products(a, q[ks], acc);
+    }
+}
+// Codes policy of tile_scan: the packed 6-bit shadow at dim = 256 C, (***).
 template <int C>
 struct Q6Tiles : PackedTiles<3 * C> {
     static constexpr int dim = 256 * C, KS = dim / 64, NL = 3 * C;
@@ -952,15 +1047,33 @@ struct Q6Tiles : PackedTiles<3 * C> {
     static constexpr double CODE_NORM = q6_code_norm(dim);
     template <int PLANES>
     __device__ static __forceinline__ void products(const u32x4 (&c)[NL], const i32x4 (&q)[KS][PLANES], i32x4 (&acc)[PLANES]) {
-        unsigned w[4 * NL];
-        PackedTiles<NL>::words(c, w);
+        q6_products<KS, NL, PLANES>(c, q, acc);
+    }
+};
+
+// Codes policy of tile_scan: the packed 6-bit shadow at dim = 128 H (H = 3, 5, 7, 9, 10: q6_dims128), (***) unchanged.
+// KS = 2 H k-steps of three words: a lane owns 6 H words of the tile, 3 H / 2 whole 16-byte words (1-KiB wave loads) and,
+// for odd H, two more in ONE 512-byte wave load after them (q6_word_offset): NL = ceil(3 H / 2) registers of four words
+// a tile, the last one half used.
+template <int H>
+struct Q6TilesH : PackedTiles<(3 * H + 1) / 2> {
+    static constexpr int dim = 128 * H, KS = 2 * H, NL = (3 * H + 1) / 2, NF = 3 * H / 2;  // NF: whole words a lane
+    static constexpr double FACTOR = 0.25;
+    static constexpr double CODE_NORM = q6_code_norm(dim);
+    // (both loads non-temporal with the builtin called without a condition: see `load` in tile_scan)
+    __device__ static __forceinline__ void load_tile(u32x4 (&c)[NL], const u32x4 *__restrict__ codes, int64_t tile0, int t,
+                                                     int64_t last_tile, int lane) {
+        const u32x4 *tile = codes + PackedTiles<NL>::tile(tile0, t, last_tile) * (int64_t)(96 * H);  // 1536 H bytes a tile
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const unsigned w0 = w[3 * ks], w1 = w[3 * ks + 1], w2 = w[3 * ks + 2];
-            const i32x4 a = {(int)(w0 & 0xfcfcfcfcu), (int)(w1 & 0xfcfcfcfcu), (int)(w2 & 0xfcfcfcfcu),
-                             (int)(((w0 & 0x03030303u) << 6) | ((w1 & 0x03030303u) << 4) | ((w2 & 0x03030303u) << 2))};
-            mq_products(a, q[ks], acc);
+        for (int l = 0; l < NF; ++l) c[l] = __builtin_nontemporal_load(tile + l * 64 + lane);
+        if constexpr (NF != NL) {
+            const u32x2 tail = __builtin_nontemporal_load(reinterpret_cast<const u32x2 *>(tile + NF * 64) + lane);
+            c[NF] = u32x4{tail.x, tail.y, 0u, 0u};
         }
+    }
+    template <int PLANES>
+    __device__ static __forceinline__ void products(const u32x4 (&c)[NL], const i32x4 (&q)[KS][PLANES], i32x4 (&acc)[PLANES]) {
+        q6_products<KS, NL, PLANES>(c, q, acc);
     }
 };
 
@@ -1053,7 +1166,7 @@ __global__ __launch_bounds__(256) void k_q5_build(const float *__restrict__ X, i
         __builtin_amdgcn_wave_barrier();
         unsigned char *tile = codes + (size_t)(r >> 4) * TILE_BYTES;
         for (int w = lane; w < 4 * WPL; w += 64)
-            *reinterpret_cast<unsigned *>(tile + q6_word_offset(16 * (w / WPL) + (int)(r & 15), w % WPL)) = packed_row[wave][w];
+            *reinterpret_cast<unsigned *>(tile + q6_word_offset(16 * (w / WPL) + (int)(r & 15), w % WPL, WPL)) = packed_row[wave][w];
     }
 }
 
@@ -1217,7 +1330,7 @@ __device__ __forceinline__ void tile_scan(const typename CodesOf<C>::Elem *__res
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 out.sums(acc, i, &hi[i], &lo[i]);
-                I[i] = (double)hi[i] * 256.0 + (double)lo[i];  // exact: |I| < 2^39 at dim 1024
+                I[i] = (double)hi[i] * 256.0 + (double)lo[i];  // exact: |I| < 2^39 up to dim 1280
                 lb[i] = certified_lb(out.adjust(I[i]), d.s[t][i], d.a[t][i], sb);
             }
             const int r0 = t * 16 + 4 * quad;  // of the lane's four rows in the group
@@ -1284,23 +1397,23 @@ __global__ __launch_bounds__(256) void k_q8_bounds_mq(const int8_t *__restrict__
                                                        {mq, w, side, stride, own, n, {dbg_hi, dbg_lo}});
 }
 
-// lb of every row into scores[r], on the packed 6-bit shadow
-template <int C, int T, bool DEBUG>
+// lb of every row into scores[r], on the packed 6-bit shadow (Codes: Q6Tiles of C = dim / 256, or Q6TilesH of C = dim / 128)
+template <int C, int T, bool DEBUG, template <int> class Codes = Q6Tiles>
 __global__ __launch_bounds__(256) void k_q6_bounds(const u32x4 *__restrict__ codes, const float *__restrict__ scale,
                                                    const float *__restrict__ err, const u32x4 *__restrict__ planes,
                                                    const unsigned *__restrict__ st, float *__restrict__ scores, int64_t n,
                                                    int64_t *__restrict__ dbg_I) {
-    tile_scan<Q6Tiles, OneQuery, C, T, DEBUG>(codes, scale, err, planes, n, {st, scores, {dbg_I}});
+    tile_scan<Codes, OneQuery, C, T, DEBUG>(codes, scale, err, planes, n, {st, scores, {dbg_I}});
 }
 
-// lb of every row for every query of the chunk into the slot's slab, on the packed 6-bit shadow
-template <int C, int T, bool DEBUG>
+// lb of every row for every query of the chunk into the slot's slab, on the packed 6-bit shadow (Codes: as above)
+template <int C, int T, bool DEBUG, template <int> class Codes = Q6Tiles>
 __global__ __launch_bounds__(256) void k_q6_bounds_mq(const u32x4 *__restrict__ codes, const float *__restrict__ scale,
                                                       const float *__restrict__ err, const u32x4 *__restrict__ planes,
                                                       const unsigned *__restrict__ mq, int w, float *__restrict__ side,
                                                       int64_t stride, float *__restrict__ own, int64_t n,
                                                       int64_t *__restrict__ dbg_I) {
-    tile_scan<Q6Tiles, Chunk<DebugSum>, C, T, DEBUG>(codes, scale, err, planes, n,
+    tile_scan<Codes, Chunk<DebugSum>, C, T, DEBUG>(codes, scale, err, planes, n,
                                                      {mq, w, side, stride, own, n, {dbg_I}});
 }
 
@@ -1392,7 +1505,7 @@ __global__ __launch_bounds__(256) void k_q41_build(const float *__restrict__ X, 
         __builtin_amdgcn_wave_barrier();
         unsigned char *tile = coarse + (size_t)(r >> 4) * TILE_BYTES;
         for (int w = lane; w < 4 * WPL; w += 64)
-            *reinterpret_cast<unsigned *>(tile + q6_word_offset(16 * (w / WPL) + (int)(r & 15), w % WPL)) = packed_row[wave][w];
+            *reinterpret_cast<unsigned *>(tile + q6_word_offset(16 * (w / WPL) + (int)(r & 15), w % WPL, WPL)) = packed_row[wave][w];
         if (lane < FW) fine[r * FW + lane] = packed_row[wave][4 * WPL + lane];
     }
 }
@@ -1658,8 +1771,9 @@ __global__ __launch_bounds__(TX_THREADS) void k_exact_threshold(uint64_t *__rest
 
 bool q8_dim_supported(int32_t dim) { return dim == 256 || dim == 512 || dim == 1024; }
 // the packed 6-bit shadow also takes dim 768 (C = 3): its matrix-core scans work in k-steps of 64 elements, where
-// k_q8_bounds' lanes-per-row map needs 4 % C == 0
-bool q6_dim_supported(int32_t dim) { return q8_dim_supported(dim) || dim == 768; }
+// k_q8_bounds' lanes-per-row map needs 4 % C == 0; and the dims of q6_dims128, on the tile layout with a 512-byte tail
+// load (Q6TilesH)
+bool q6_dim_supported(int32_t dim) { return q8_dim_supported(dim) || dim == 768 || q6_dims128(dim); }
 
 // ---- run-time shapes -> template instances ----------------------------------------------------------------------------
 template <int N>
@@ -1701,7 +1815,8 @@ static int scan_tiles(const ScanTune &tune, int default_tiles, int C) {
 }
 
 void scan_shape(TileScan scan, int32_t dim, int device, int64_t n, int *out_blocks, int *out_tiles) {
-    const int T = scan_tiles(g_scan_tune[scan], scan_default_tiles(scan, dim / 256), dim / 256);
+    // (the 6-bit scans at a dim of q6_dims128: one tile, 4.5 to 15 KiB a request, the only instances there are)
+    const int T = q6_dims128(dim) ? 1 : scan_tiles(g_scan_tune[scan], scan_default_tiles(scan, dim / 256), dim / 256);
     const int64_t need = ((n + 16 * T - 1) / (16 * T) + 3) / 4;
     int64_t grid = (int64_t)num_cus(device) * g_scan_tune[scan].blocks_per_cu;
     if (grid > need) grid = need;
@@ -1760,6 +1875,29 @@ static ssw_status launch_tile_scan(int32_t dim, int device, int64_t n, bool debu
     return SSW_OK;
 }
 static const u32x4 *as_u32x4(const void *p) { return static_cast<const u32x4 *>(p); }
+
+// f(Int<H>) for H = dim / 128 of a dim of q6_dims128
+template <class F>
+static void dispatch_dims128(int H, F f) {
+    H == 3 ? f(Int<3>{}) : H == 5 ? f(Int<5>{}) : H == 7 ? f(Int<7>{}) : H == 9 ? f(Int<9>{}) : f(Int<10>{});
+}
+// launch_tile_scan for the two 6-bit scans at such a dim: launch(grid, Int<H>, DEBUG) for the instance on Q6TilesH, which
+// has T = 1 alone (the product: without DEBUG)
+template <TileScan S, class Launch>
+static ssw_status launch_tile_scan_dims128(int32_t dim, int device, int64_t n, bool debug, Launch launch) {
+    int grid = 1, T = 1;
+    scan_shape(S, dim, device, n, &grid, &T);
+    dispatch_dims128(dim / 128, [&](auto h) {
+#ifdef SSW_DEBUG_HOOKS
+        debug ? launch(dim3((unsigned)grid), h, std::true_type{}) : launch(dim3((unsigned)grid), h, std::false_type{});
+#else
+        (void)debug;
+        launch(dim3((unsigned)grid), h, std::false_type{});
+#endif
+    });
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
 
 ssw_status launch_q8_build(const void *X, int32_t dtype, int64_t n, int32_t dim, unsigned char *codes, float *scale,
                            float *err, hipStream_t stream) {
@@ -1923,6 +2061,18 @@ ssw_status launch_q6_build(const void *X, int32_t dtype, int64_t n, int32_t dim,
     }
     SSW_TRY(zero_last_tile(codes, q6_code_bytes(n, dim), (size_t)16 * dim * 3 / 4, scale, err, n, stream));
     const dim3 grid((unsigned)std::min<int64_t>((n + 3) / 4, (int64_t)1 << 20)), block(256);
+    if (q6_dims128(dim)) {
+        dispatch_dims128(dim / 128, [&](auto h) {
+            if (dtype == SSW_DTYPE_F16)
+                hipLaunchKernelGGL(k_q6_build_h16_dims128<h.value>, grid, block, 0, stream, static_cast<const uint16_t *>(X), n,
+                                   codes, scale, err);
+            else
+                hipLaunchKernelGGL(k_q6_build_dims128<h.value>, grid, block, 0, stream, static_cast<const float *>(X), n, codes,
+                                   scale, err);
+        });
+        SSW_HIP_TRY(hipGetLastError());
+        return SSW_OK;
+    }
     dispatch_dim<true>(dim / 256, [&](auto c) {
         if (dtype == SSW_DTYPE_F16)
             hipLaunchKernelGGL(k_q6_build_h16<c.value>, grid, block, 0, stream, static_cast<const uint16_t *>(X), n, codes, scale, err);
@@ -1949,6 +2099,11 @@ ssw_status launch_q6_bounds(const unsigned char *codes, const float *scale, cons
         set_error("q6_bounds: dim=%d unsupported", dim);
         return SSW_ERR_UNSUPPORTED;
     }
+    if (q6_dims128(dim))
+        return launch_tile_scan_dims128<SCAN_Q6>(dim, device, n, dbg_I != nullptr, [&](dim3 grid, auto h, auto d) {
+            hipLaunchKernelGGL((k_q6_bounds<h.value, 1, d.value, Q6TilesH>), grid, dim3(256), 0, stream, as_u32x4(codes), scale,
+                               err, as_u32x4(planes), st, scores, n, dbg_I);
+        });
     return launch_tile_scan<SCAN_Q6>(dim, device, n, dbg_I != nullptr, [&](dim3 grid, auto c, auto t, auto d) {
         hipLaunchKernelGGL((k_q6_bounds<c.value, t.value, d.value>), grid, dim3(256), 0, stream, as_u32x4(codes), scale, err,
                            as_u32x4(planes), st, scores, n, dbg_I);
@@ -1972,6 +2127,11 @@ ssw_status launch_q6_bounds_mq(const unsigned char *codes, const float *scale, c
         set_error("q6_bounds_mq: dim=%d, w=%d unsupported", dim, w);
         return SSW_ERR_UNSUPPORTED;
     }
+    if (q6_dims128(dim))
+        return launch_tile_scan_dims128<SCAN_Q6_MQ>(dim, device, n, dbg_I != nullptr, [&](dim3 grid, auto h, auto d) {
+            hipLaunchKernelGGL((k_q6_bounds_mq<h.value, 1, d.value, Q6TilesH>), grid, dim3(256), 0, stream, as_u32x4(codes),
+                               scale, err, as_u32x4(planes), mq, (int)w, side, stride, own, n, dbg_I);
+        });
     return launch_tile_scan<SCAN_Q6_MQ>(dim, device, n, dbg_I != nullptr, [&](dim3 grid, auto c, auto t, auto d) {
         hipLaunchKernelGGL((k_q6_bounds_mq<c.value, t.value, d.value>), grid, dim3(256), 0, stream, as_u32x4(codes), scale, err,
                            as_u32x4(planes), mq, (int)w, side, stride, own, n, dbg_I);

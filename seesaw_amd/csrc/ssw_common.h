@@ -279,7 +279,8 @@ ssw_status launch_scan_views(const void *X, int32_t dtype, const ViewSlotTable *
 // their widened values) and the certified pre-scan of the exact top-k (see prune.hip).
 // query state words: [0] survivors, [1] Q = ||q|| rounded up (f32 bits), [2] 1 = the query cannot be bounded
 bool q8_dim_supported(int32_t dim);
-// the dims of the packed 6-bit shadow's builders and scans: those of the int8 shadow and 768, which has no int8 shadow
+// the dims of the packed 6-bit shadow's builders and scans: those of the int8 shadow, and 768 and the scan's dims of
+// scan_dims128 (384, 640, 896, 1152, 1280), which have no int8 shadow
 bool q6_dim_supported(int32_t dim);
 ssw_status launch_q8_build(const void *X, int32_t dtype, int64_t n, int32_t dim, unsigned char *codes, float *scale,
                            float *err, hipStream_t stream);
@@ -330,12 +331,22 @@ void scan_shape(TileScan scan, int32_t dim, int device, int64_t n, int *out_bloc
 // padded to whole tiles.  q6_slot / q6_element / q6_word_offset are the ONE placement of an element's code: k-step u, lane
 // group g (the lane of row r is 16 g + r % 16) and slot j of the lane's 16 codes of that k-step; slot j < 12 is the upper
 // six bits of byte j % 4 of the lane's word 3 u + j / 4, slot 12 + b the low two bits of byte b of words 3 u .. 3 u + 2
-// (code bits 5:4, 3:2, 1:0); word wi of lane l sits at q6_word_offset(l, wi) in the tile.
+// (code bits 5:4, 3:2, 1:0); word wi of lane l sits at q6_word_offset(l, wi, words) in the tile, `words` the words a
+// lane owns of it (3 dim / 64 for the 6-bit shadow).  A tile is words / 4 contiguous 1-KiB wave loads, a 16-byte word
+// a lane each; where words % 4 == 2 (dims 384, 640, 896 and 1152: 18, 30, 42 and 54 words) ONE 512-byte wave load
+// follows them, lane l's last two words at (words / 4) * 1024 + 8 l.  A tile is 256 * words bytes with no padding,
+// every load is aligned to its size and every wave load contiguous.  Every caller passes its count: the 5-bit shadow's
+// (5 dim / 128) and the two-stage shadow's planes' are multiples of four at their dims, so they have no such tail.
 __host__ __device__ inline void q6_slot(int i, int *u, int *g, int *j) { *u = i >> 6, *g = (i & 63) >> 4, *j = i & 15; }
 __host__ __device__ inline int q6_element(int u, int g, int j) { return 64 * u + 16 * g + j; }
-__host__ __device__ inline size_t q6_word_offset(int lane, int wi) {
+__host__ __device__ inline size_t q6_word_offset(int lane, int wi, int words) {
+    if ((words & 3) != 0 && (wi >> 2) == (words >> 2))  // the two words of the tail load
+        return (size_t)(words >> 2) * 1024 + (size_t)lane * 8 + (size_t)(wi & 3) * 4;
     return (size_t)(wi >> 2) * 1024 + (size_t)lane * 16 + (size_t)(wi & 3) * 4;
 }
+// the dims of the 6-bit shadow that are no multiple of 256 or lie beyond 1024: the scan's dims of scan_dims128, served
+// by the instances parametrised by H = dim / 128 (prune.hip, Q6TilesH)
+inline bool q6_dims128(int32_t dim) { return scan_dims128(dim); }
 int64_t packed_padded_rows(int64_t n);  // of both packed shadows: n rounded up to whole tiles
 size_t q6_code_bytes(int64_t n, int32_t dim);
 size_t q6_plane_bytes(int32_t dim);

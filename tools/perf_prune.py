@@ -34,8 +34,9 @@ line carries it.
 
 --dim D (default 512): the width of the index.  --dim 768 (how MIN_ROWS (6-bit single call, dim 768, f32) and MIN_ROWS (6-bit single call, dim 768, f16) are
 chosen): that dim has the 6-bit shadow alone, so the run is always the rounds of --three-way with two forms, full scan /
-packed 6-bit shadow, and the JSON line has no int8 column; it carries "dim".  Every other dim prints what it printed
-before the option existed."""
+packed 6-bit shadow, and the JSON line has no int8 column; it carries "dim".  The same holds for --dim 384, 640, 896, 1152
+and 1280 (MIN_ROWS_DIMS128, single call), whose rows tools/_gaussian_index.py draws (the device's fill has no such dims).
+Every other dim prints what it printed before the option existed."""
 import argparse
 import ctypes
 import json
@@ -46,6 +47,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _gaussian_index import DIMS128, make_index  # noqa: E402  (tools/ is the script's directory)
 
 
 def main():
@@ -56,7 +58,7 @@ def main():
     ap.add_argument("--dtype", choices=("float32", "float16"), default="float32")
     ap.add_argument("--warmup-pairs", type=int, default=2)
     ap.add_argument("--three-way", action="store_true")
-    ap.add_argument("--dim", type=int, choices=(256, 512, 768, 1024), default=512)
+    ap.add_argument("--dim", type=int, choices=(256, 512, 768, 1024) + DIMS128, default=512)
     ap.add_argument("--two-stage", action="store_true")
     ap.add_argument("--scan41", type=int, nargs=2, metavar=("BLOCKS", "TILES"))
     args = ap.parse_args()
@@ -80,7 +82,7 @@ def main():
         _lib.call("ssw_tune_prune41", 1 if form == "q41" else 0, 1, -1)
 
     dtype = np.dtype(args.dtype)
-    six_only = dim == 768  # no int8 shadow at this dim
+    six_only = dim == 768 or dim in DIMS128  # no int8 shadow at these dims
     five = dim in (512, 1024) and dtype == np.float32  # the fourth column
     built_by = {"full": "none", "int8": "int8", "q6": "6-bit", "q5": "5-bit", "q41": "two-stage"}
     coarse = []  # the first stage's survivors of the timed two-stage calls
@@ -92,7 +94,7 @@ def main():
 
     def rounds(n, forms, wall, surv, shadows):
         """warm-up and timed rounds over `forms` on a fresh index; -> all forms returned the same bytes"""
-        idx = DeviceIndex.synthetic(n, dim, seed=2024, dtype=dtype)
+        idx = make_index(n, dim, dtype)
         grows = {0: "none", n * (dim + 8): "int8", (n + 15) // 16 * 16 * (dim * 3 // 4 + 8): "6-bit",
                  (n + 15) // 16 * 16 * (dim * 5 // 8 + 8): "5-bit", (n + 15) // 16 * 16 * (dim * 5 // 8 + 16): "two-stage"}
         same = True

@@ -20,7 +20,8 @@ for memory ran the plain batch and is reported as `"resident": false`.
 --dim D (default 512): the width of the index.  --dim 768 (how MIN_ROWS (6-bit batch, dim 768, f32 and f16) are chosen): that
 dim has the 6-bit shadow alone, so --shadow is taken as `six` whatever was given, the comparison is the 6-bit batch
 against the plain batch and the pruned singles, there is no int8 column, and the
-JSON line carries "dim".  Every other dim prints what it printed before the option existed."""
+JSON line carries "dim"; so at --dim 384, 640, 896, 1152 and 1280 (MIN_ROWS_DIMS128, batch; rows: tools/_gaussian_index.py).
+Every other dim prints what it printed before the option existed."""
 import argparse
 import ctypes
 import json
@@ -31,6 +32,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _gaussian_index import DIMS128, make_index  # noqa: E402  (tools/ is the script's directory)
 
 
 def main():
@@ -46,13 +48,12 @@ def main():
     ap.add_argument("--blocks", type=int, default=-1)
     ap.add_argument("--tiles6", type=int, default=-1)
     ap.add_argument("--blocks6", type=int, default=-1)
-    ap.add_argument("--dim", type=int, choices=(256, 512, 768, 1024), default=512)
+    ap.add_argument("--dim", type=int, choices=(256, 512, 768, 1024) + DIMS128, default=512)
     args = ap.parse_args()
     dim = args.dim
-    if dim == 768:
+    if dim == 768 or dim in DIMS128:
         args.shadow = "six"
     from seesaw_amd import _lib
-    from seesaw_amd.device_index import DeviceIndex
     forms = {"int8": ["int8"], "six": ["six"], "both": ["int8", "six"]}[args.shadow]
 
     def stats(idx):
@@ -80,7 +81,7 @@ def main():
         _lib.call("ssw_tune_prune6_scan_mq", args.blocks6, args.tiles6)
         for rows in args.rows:
             n = int(rows)
-            idx = DeviceIndex.synthetic(n, dim, seed=2024, dtype=np.dtype(args.dtype))
+            idx = make_index(n, dim, np.dtype(args.dtype))
             try:
                 _lib.call("ssw_tune_prune", 1, 1, -1)
                 _lib.call("ssw_tune_prune6_batch", 1)
