@@ -254,6 +254,35 @@ ssw_status ssw_index_topk_batch_pruned(ssw_index *idx, const float *q_host, int3
                                        const int64_t *excluded_offsets, int32_t k, int64_t *out_images,
                                        float *out_scores, int64_t *out_best_rows, int32_t *out_counts);
 
+/* ssw_index_topk_batch for hundreds of queries, scored on the fp16 matrix cores (index_mc.hip; DESIGN.md section 4,
+ * "Large-batch top-k on the matrix cores"): arguments and results exactly as ssw_index_topk_batch, every query's row the
+ * bits of ssw_index_topk for it.  The rows -- f32 or f16, with or without an image map -- are read in place ONCE per
+ * group of up to 1024 queries: strips of rows are rounded to fp16 into LDS and multiplied with the group's fp16 queries
+ * (v_mfma_f32_16x16x32_f16), rising per-query thresholds keep M = 4 k candidates (64 <= M <= 512) a query, and one
+ * workgroup a query rescores them with the scan's arithmetic, orders, maps to images, strikes out the excluded and
+ * certifies the list against the fp16 path's error bound.  A query that is not certified, or whose candidate buffer
+ * overflowed, is answered by ONE ssw_index_topk_batch call for all such queries after the groups; k > 128 sends the
+ * whole call there, as does an index whose largest element lies outside [2^-40, 2^40].  The certificate therefore
+ * decides who pays for the plain batch, never what is returned.  One host wait per group, plus the plain batch's own.
+ * Served: dims 256, 512, 768 and 1024.  Refused with SSW_ERR_UNSUPPORTED before anything is enqueued: a view (the
+ * message says "view"), any other dim (the message names it), nq outside [1, 65535].  A non-finite query component is
+ * SSW_ERR_NUMERIC before anything is enqueued; so is an index that holds a NaN or no finite non-zero element (found by
+ * one pass over the rows, made once per state of the rows and kept in the handle; the passes that make the shadows
+ * stale make it stale).  NULL pointers, k outside [1, SSW_MAX_TOPK], decreasing offsets and excluded ids out of range
+ * are SSW_ERR_INVALID.
+ * State afterwards: that of a pruned top-k of the last query -- the query is kept and the resident scores are completed
+ * by their first reader.  The prune counters stay as they are.
+ * Memory: allocated by the first call, grown by a larger one, freed with the handle -- 32 KiB of candidate buffer a
+ * query of a group (32 MiB at 1024), the group's queries in f32 and fp16, its results, and 4 bytes a strip of 128 rows
+ * (64 from dim 768 on).  SSW_ERR_NOMEM leaves the handle usable.  Opt-in: nothing dispatches to it silently.
+ * ssw_index_topk_batch_mc_stats: out8 = {calls, queries, queries proven, queries sent to the plain batch because not
+ * certified, because of an overflow, calls diverted whole because k > 128, strips multiplied (per group), candidate
+ * entries appended}, since the handle was made. */
+ssw_status ssw_index_topk_batch_mc(ssw_index *idx, const float *q_host, int32_t nq, const int64_t *excluded_images,
+                                   const int64_t *excluded_offsets, int32_t k, int64_t *out_images, float *out_scores,
+                                   int64_t *out_best_rows, int32_t *out_counts);
+ssw_status ssw_index_topk_batch_mc_stats(ssw_index *idx, int64_t *out8);
+
 /* device-resident form used by bench.py and the sharded index: q_dev [dim] f32;
  * the excluded set is whatever the last ssw_index_set_excluded installed; results
  * stay on the device in the handle's result buffers (ssw_index_result_ptrs).

@@ -71,6 +71,9 @@ _SIGNATURES = {
                                      c_void_p]),
     "ssw_index_topk_batch_pruned": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p, c_void_p,
                                             c_void_p, c_void_p]),
+    "ssw_index_topk_batch_mc": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p,
+                                        c_void_p]),
+    "ssw_index_topk_batch_mc_stats": (c_i32, [c_void_p, c_i64_p]),
     "ssw_index_topk_batch_avg": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p]),
     "ssw_index_topk_batch_avg_pruned": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_i32, c_void_p,

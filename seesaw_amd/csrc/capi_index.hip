@@ -274,6 +274,7 @@ ssw_status ssw_index_destroy(ssw_index *idx) {
     idx->pair.release();
     idx->views_batch.release();
     idx->chunk.release();
+    idx->mc.release();
     if (idx->owns_X) (void)hipFree(idx->X);
     (void)hipFree(idx->xfer);
     (void)hipFree(idx->scores);

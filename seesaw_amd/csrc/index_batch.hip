@@ -72,7 +72,7 @@ static ssw_status do_scan_chunk(ssw_index *idx, const float *q_host, int w) {
     });
 }
 
-static ssw_status check_query_batch(const ssw_index *idx, const float *q_host, int32_t nq) {
+ssw_status ssw::check_query_batch(const ssw_index *idx, const float *q_host, int32_t nq) {
     for (int32_t b = 0; b < nq; ++b) {
         for (int i = 0; i < idx->dim; ++i) {
             if (!std::isfinite(q_host[(size_t)b * idx->dim + i])) {
@@ -207,6 +207,9 @@ static ssw_status check_excluded_offsets(const ssw_index *idx, const BatchExclud
         SSW_REQUIRE(ex.offsets[b] <= ex.offsets[b + 1], "excluded_offsets decrease at query %d", b);
     SSW_REQUIRE(ex.offsets[nq] == ex.offsets[0] || ex.images != nullptr, "excluded_images is NULL");
     return check_excluded(idx, ex.images, ex.offsets[0], ex.offsets[nq]);
+}
+ssw_status ssw::check_excluded_lists(const ssw_index *idx, const int64_t *images, const int64_t *offsets, int32_t nq) {
+    return check_excluded_offsets(idx, BatchExcluded{images, offsets}, nq);
 }
 
 // The scores of a pruned chunk: ONE pass over the shadow prune_batch_shadow chose bounds its w queries [b, b + w), already

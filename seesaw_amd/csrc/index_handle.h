@@ -58,8 +58,13 @@ struct PruneState {
     uint32_t *coarse_rows = nullptr;               // [COARSE_CAP] the first stage's survivors
     int32_t *D41 = nullptr;                        // [dim] the query's 256 d_hi + d_lo in natural order
     int64_t coarse_last = 0, dense_refines = 0, two_stage_calls = 0;  // ssw_index_prune_coarse_stats
+    // the rows' largest |element| and an upper bound of their largest norm (index_mc.hip): derived from the rows like a
+    // shadow, so they go stale where the shadows do -- rows_changing and free_shadow, and nowhere else
+    float rows_maxabs = 0.f, rows_maxnorm = 0.f;
+    bool rows_stats_stale = true;
     void free_shadow() {
         for (Shadow &s : sh) s.free();
+        rows_stats_stale = true;
     }
     void release() {
         for (Shadow &s : sh) {
@@ -160,6 +165,29 @@ struct ChunkSelectState {
     }
 };
 
+// large-batch top-k on the matrix cores (ssw_index_topk_batch_mc, index_mc.hip): the workspace of one group of up to
+// MC_GROUP queries and the counters of ssw_index_topk_batch_mc_stats.  Allocated by the first call, grown by a larger one
+struct McState {
+    int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned *maxima = nullptr;        // [2] the stats pass's words
+    int32_t *perm = nullptr;           // [perm_strips] the seeded order the strips are dealt to the levels in
+    int64_t perm_strips = 0;
+    unsigned char *in_dev = nullptr;   // one upload a group: [queries f32 | excluded offsets i64 | excluded ids i64]
+    size_t in_cap = 0;
+    ssw::PinnedStage in_stage;
+    // per group, sized for q_cap (padded) queries and k_cap results each
+    unsigned char *grp = nullptr;      // [Qh | norms | thr | cnt | kept | overflow | buffers]
+    unsigned char *res_dev = nullptr, *res_host = nullptr;  // [images | rows | scores | counts | flags | appended]
+    int q_cap = 0, k_cap = 0;
+    void release() {
+        for (void *p : {(void *)maxima, (void *)perm, (void *)in_dev, (void *)grp, (void *)res_dev}) (void)hipFree(p);
+        if (res_host) (void)hipHostFree(res_host);
+        in_stage.release();
+        maxima = nullptr, perm = nullptr, in_dev = grp = res_dev = res_host = nullptr;
+        perm_strips = 0, in_cap = 0, q_cap = k_cap = 0;
+    }
+};
+
 struct ssw_index {
     int device = 0;
     int64_t n = 0;
@@ -228,6 +256,7 @@ struct ssw_index {
     PairStage pair;
     ViewsBatchState views_batch;
     ChunkSelectState chunk;
+    McState mc;
     // profiling of the scan kernel
     bool profiling = false;
     std::vector<hipEvent_t> ev;  // pairs
@@ -321,6 +350,8 @@ ssw_status rescore_survivors_chunk(ssw_index *idx, int w, int64_t cap);
 int64_t slab_stride(const ssw_index *idx);
 float *chunk_slab(ssw_index *idx, int w, int j);
 ssw_status batch_buffers(ssw_index *idx, int w, bool with_queries, int *out_w);
+ssw_status check_query_batch(const ssw_index *idx, const float *q_host, int32_t nq);
+ssw_status check_excluded_lists(const ssw_index *idx, const int64_t *images, const int64_t *offsets, int32_t nq);
 
 }  // namespace ssw
 #pragma GCC visibility pop

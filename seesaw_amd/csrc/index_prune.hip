@@ -256,6 +256,7 @@ static bool prune6_batch_eligible(const ssw_index *idx) {
 ssw_status ssw::rows_changing(ssw_index *idx) {
     SSW_TRY(ensure_full_scores(idx));
     for (Shadow &s : idx->prune.sh) s.stale = true, s.refused = false;
+    idx->prune.rows_stats_stale = true;
     return SSW_OK;
 }
 

@@ -299,7 +299,7 @@ class DeviceIndex:
         _lib.call("ssw_index_scan_batch", self._h, _ptr(Q), Q.shape[0], _ptr(out))
         return out
 
-    def topk_batch(self, Q: np.ndarray, k: int, excluded=None, prune: bool = False):
+    def topk_batch(self, Q: np.ndarray, k: int, excluded=None, prune: bool = False, matrix_core: bool = False):
         """`[topk(Q[b], k, excluded[b]) for b]` with the rows read once per chunk of queries (ssw_index_topk_batch):
         a list of (images, scores, rows), bit for bit what the single calls return.  `excluded` is None or a sequence of
         nq iterables of image positions, each of which may be None.  The handle is left as after the last query's topk.
@@ -307,7 +307,14 @@ class DeviceIndex:
         -- from 25 M rows the packed 6-bit one single queries scan there, below that (or where that one is refused for
         memory) the int8 one; at dim 768 the 6-bit one from 2^20 rows and no other -- bounds a chunk of up to 16 queries
         and only each query's survivors are scored exactly -- the same results; `prune_stats` counts every query.  Any
-        other index takes the plain batch."""
+        other index takes the plain batch.
+        `matrix_core=True` (ssw_index_topk_batch_mc), for hundreds of queries: the rows are read in place once per
+        group of up to 1024 queries and multiplied with them in fp16 on the matrix cores; each query keeps 4 k
+        candidates, which are rescored exactly and certified, and a query that is not certified goes through the plain
+        batch -- the same results; `matrix_core_stats` counts.  Dims 256, 512, 768 and 1024, f32 or float16 rows; a view
+        and any other dim raise.  Not together with `prune`."""
+        if prune and matrix_core:
+            raise ValueError("topk_batch: prune=True and matrix_core=True are two different routes; choose one")
         k = int(k)
         Q = self._queries(Q)
         nq = Q.shape[0]
@@ -316,9 +323,20 @@ class DeviceIndex:
         scs = np.empty((nq, k), dtype=np.float32)
         rows = np.empty((nq, k), dtype=np.int64)
         cnt = np.zeros(nq, dtype=np.int32)
-        _lib.call("ssw_index_topk_batch_pruned" if prune else "ssw_index_topk_batch", self._h, _ptr(Q), nq, _ptr(ids),
-                  _ptr(offsets), k, _ptr(imgs), _ptr(scs), _ptr(rows), _ptr(cnt))
+        entry = "ssw_index_topk_batch_mc" if matrix_core else "ssw_index_topk_batch_pruned" if prune else "ssw_index_topk_batch"
+        _lib.call(entry, self._h, _ptr(Q), nq, _ptr(ids), _ptr(offsets), k, _ptr(imgs), _ptr(scs), _ptr(rows), _ptr(cnt))
         return [(imgs[b, :c].copy(), scs[b, :c].copy(), rows[b, :c].copy()) for b, c in enumerate(cnt.tolist())]
+
+    _MATRIX_CORE_STATS = ("calls", "queries", "proven", "uncertified", "overflowed", "diverted_calls", "strips", "appended")
+
+    def matrix_core_stats(self) -> dict:
+        """counters of `topk_batch(matrix_core=True)` since the handle was made (ssw_index_topk_batch_mc_stats): calls,
+        queries, queries proven, queries sent to the plain batch because not certified (`uncertified`) or because their
+        candidate buffer overflowed (`overflowed`), calls diverted whole because k > 128, strips of rows multiplied
+        (counted once a group of queries) and candidate entries appended"""
+        out = np.zeros(8, dtype=np.int64)
+        _lib.call("ssw_index_topk_batch_mc_stats", self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
+        return dict(zip(self._MATRIX_CORE_STATS, out.tolist()))
 
     # -- the same on a view: the member rows read once per chunk of queries, in place ----
     def view_scores_batch(self, Q: np.ndarray) -> np.ndarray:

@@ -107,14 +107,18 @@ class CoarseIndex(AccessMethod):
         return {"dbidxs": ret, "nextstartk": len(exclude) + ret.shape[0],
                 "activations": ActivationFrames(boxes, ret, np.asarray(scores))}
 
-    def query_batch(self, *, topk, vectors, excludes=None, prune=False, vectors2=None, **kwargs):
+    def query_batch(self, *, topk, vectors, excludes=None, prune=False, vectors2=None, matrix_core=False, **kwargs):
         """one `DeviceIndex.topk_batch` call for the vectors that are given (on a subset_view index one
         `DeviceIndex.view_topk_batch` call: the member rows read in place, once a chunk of queries; `prune` is consumed
         and means that plain view batch; a call with `vectors2` or `vector2` stays the loop over `query` there, as on a
         multiscale view index): the list of dicts `query` returns, entry by entry identical to it.  A `None`
         vector (random order) and a query whose exclude set covers the whole index
         keep going through `query`.  `prune` is `DeviceIndex.topk_batch`'s: the same results from the shared int8
-        pre-scan on an index large enough for it.  `vectors2` is dropped: `query` ignores `vector2`."""
+        pre-scan on an index large enough for it.  `vectors2` is dropped: `query` ignores `vector2`.
+        `matrix_core` is `DeviceIndex.topk_batch`'s too (hundreds of queries against the rows in one pass on the matrix
+        cores, the same results); with `vectors2` or on a view index it is a ValueError before anything runs."""
+        if matrix_core and (vectors2 is not None or getattr(self._dev, "is_view", False)):
+            raise ValueError("query_batch: matrix_core=True takes neither vectors2 nor a view index")
         vectors = list(vectors)
         excludes = [None] * len(vectors) if excludes is None else list(excludes)
         if len(excludes) != len(vectors):
@@ -136,7 +140,8 @@ class CoarseIndex(AccessMethod):
             if is_view:
                 res = self._dev.view_topk_batch(Q, max(ks), excluded=[excl_pos[i] for i in batch])
             else:
-                res = self._dev.topk_batch(Q, max(ks), excluded=[excl_pos[i] for i in batch], prune=prune)
+                res = self._dev.topk_batch(Q, max(ks), excluded=[excl_pos[i] for i in batch], prune=prune,
+                                           matrix_core=matrix_core)
             for i, k_i, (pos, scores, _) in zip(batch, ks, res):
                 ret = self._dbidx[pos[:k_i]]
                 assert ret.shape[0] == k_i

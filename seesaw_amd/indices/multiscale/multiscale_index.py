@@ -372,7 +372,7 @@ class MultiscaleIndex(AccessMethod):
         return np.concatenate([np.arange(self._row_start[p], self._row_start[p + 1]) for p in positions]) \
             if positions.size else np.zeros(0, dtype=np.int64)
 
-    def query_batch(self, *, topk, vectors, excludes=None, prune=False, vectors2=None, **kwargs):
+    def query_batch(self, *, topk, vectors, excludes=None, prune=False, vectors2=None, matrix_core=False, **kwargs):
         """`[query(vector=v, topk=topk, exclude=e, **kwargs) for v, e in zip(vectors, excludes)]`, entry by entry
         identical to it,
         with the rows read once per chunk of up to 16 queries: `plain_score` ends in
@@ -399,7 +399,14 @@ class MultiscaleIndex(AccessMethod):
         `_avg_result`, the plain ones in `plain_pair_result`.  It reads no score buffer, so it is the same behind the
         plain and the pruned first stage.  The single `vector2=` keyword keeps its meaning (the per-query loop).
         (The sharded index batches its first stage and its avg second stage, `ShardedMultiscaleIndex`; its two-vector
-        entries loop: the owner-side form of `stage2_pair` remains a follow-up.)"""
+        entries loop: the owner-side form of `stage2_pair` remains a follow-up.)
+        `matrix_core` is `DeviceIndex.topk_batch`'s (hundreds of queries against the rows in one pass on the matrix
+        cores, the same results) and reaches it where the call ends there: `plain_score` without second vectors on an
+        index that is not a view.  With any other agg_method, `vectors2` / `vector2` or a view index it is a ValueError
+        before anything runs."""
+        if matrix_core and (kwargs.get("agg_method") != "plain_score" or vectors2 is not None
+                            or kwargs.get("vector2") is not None or getattr(self._dev, "is_view", False)):
+            raise ValueError("query_batch: matrix_core=True serves plain_score alone, without vectors2 and not on a view index")
         vectors = list(vectors)
         excludes = [None] * len(vectors) if excludes is None else list(excludes)
         if len(excludes) != len(vectors):
@@ -446,7 +453,7 @@ class MultiscaleIndex(AccessMethod):
         # ONE first stage for the whole batch; its own second stage only where a single-vector entry needs it
         if plain or all(second[i] is not None for i in batch):
             res = self._dev.view_topk_batch(Q, max(ks), excluded=excluded) if is_view else \
-                self._dev.topk_batch(Q, max(ks), excluded=excluded, prune=prune)
+                self._dev.topk_batch(Q, max(ks), excluded=excluded, prune=prune, matrix_core=matrix_core)
         elif is_view:
             res = self._dev.view_topk_batch_avg(Q, max(ks), kwargs["aug_larger"], excluded=excluded, aug_weight=aug_weight)
         else:
