@@ -228,6 +228,28 @@ ssw_status ssw_debug_rescore_survivors(ssw_index *idx, const float *q_host, int3
                                        const int64_t *counts, const int32_t *fail_bits, float *out_slabs_host,
                                        int32_t *out_waves);
 
+/* The large-batch top-k on the matrix cores (seesaw_hip.h, ssw_index_topk_batch_mc; csrc/index_mc.hip) seen stage by
+ * stage, for tests/test_topk_mc_certificate_gpu.py.  ONE group of nq <= 1024 host queries and k <= 128 goes through the
+ * product's run_group -- rows_stats, k_mc_prep, launch_candidates, k_mc_compact, launch_finish, no exclusions, the
+ * index's own image map -- and what the device holds is copied out.  All out pointers are HOST memory; any may be NULL.
+ * mode 1: prep and the first level's candidate launch alone, nothing compacted: out_cnt [nq] = each query's counter (it
+ *   passes 4096 where entries were dropped), out_scores / out_rows [nq, 4096] = the first min(cnt, 4096) entries of its
+ *   buffer, unsorted, as (fp16-path score, row).  On an index of <= 4096 - 128 rows that is every (query, row) once.
+ * mode 0: every level and the finish: out_thr [nq] = the final thresholds (fp16-path units, -inf = never raised),
+ *   out_cnt [nq] and out_scores / out_rows [nq, M] = the <= M kept entries, best first, out_flags [nq] = 0 proven, 1 not
+ *   certified, 2 overflowed, out_bE [nq, 2] = b and E as k_mc_finish evaluated them.
+ * Both: out_meta [6] = scale, scale_q, maxabs_x, maxnorm, maxabs_q, M; out_levels [levels_cap] = the level bounds in
+ *   strips and *out_n_levels their number; out_perm [strips] = the order the strips are dealt in (a strip is 128 rows at
+ *   dim <= 512, 64 above).
+ * Refusals are the product's (a view, a dim that is no multiple of 256, non-finite queries); k > 128, and rows or
+ * queries whose largest element lies outside [2^-40, 2^40], which the product answers with the plain batch, are
+ * SSW_ERR_UNSUPPORTED here.  The handle is left as after the product call (partial, the last query kept); the counters
+ * of ssw_index_topk_batch_mc_stats do not move. */
+ssw_status ssw_debug_mc_candidates(ssw_index *idx, const float *q_host, int32_t nq, int32_t k, int32_t mode,
+                                   float *out_meta, int64_t *out_levels, int32_t levels_cap, int32_t *out_n_levels,
+                                   int32_t *out_perm, float *out_thr, uint32_t *out_cnt, float *out_scores,
+                                   int64_t *out_rows, int32_t *out_flags, float *out_bE);
+
 /* Kernel A/B harness for the towers' bf16 GEMM (C[M,N] = A[M,K] W[N,K]^T + epilogue `epi`, see
  * csrc/gemm_bf16.hip): runs `variant` on seeded operands, reports ms per launch over `iters`
  * launches and the max |difference| to variant 0.  Not part of the reference's interface. */

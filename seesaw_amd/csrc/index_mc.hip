@@ -330,6 +330,7 @@ struct McFinishArgs {
     int64_t *out_images, *out_rows;
     float *out_scores;
     int32_t *out_counts, *out_flags;  // flag 0: proven, 1: not certified, 2: its buffer overflowed
+    float *out_bE;                    // [nq][2] b and E as evaluated below; NULL in the product (the lab hook's view)
 };
 
 template <class Rw, int C>
@@ -411,6 +412,7 @@ __global__ __launch_bounds__(256) void k_mc_finish(const typename Rw::T *__restr
         const bool proven = !bad && (all_rows || (rank == a.k && s_k - E > b));
         a.out_counts[q] = rank;
         a.out_flags[q] = a.ovf[q] ? 2 : (proven ? 0 : 1);
+        if (a.out_bE) a.out_bE[2 * q] = b, a.out_bE[2 * q + 1] = E;
     }
 }
 
@@ -588,11 +590,49 @@ void launch_finish(const ssw_index *idx, int nq, const McFinishArgs &a) {
 #undef MC_CASE
 }
 
+// What the lab build's hook (ssw_debug_mc_candidates, at the foot of this file) reads out of a group's device state; the
+// product passes none.  Every pointer is host memory and may be NULL.  mode 1: the state behind the first level's
+// candidate launch, before any compaction (`stride` = MC_CAP entries a query), and run_group returns there; mode 0: the
+// state the finish saw (`stride` = M entries a query).
+struct McProbe {
+    int mode = 0;
+    float *meta = nullptr;       // [6] scale, scale_q, maxabs_x, maxnorm, maxabs_q, M
+    int64_t *levels = nullptr;   // [levels_cap] the level bounds in strips
+    int32_t levels_cap = 0, *n_levels = nullptr, *perm = nullptr;  // perm [strips]
+    float *thr = nullptr;        // [nq]
+    uint32_t *cnt = nullptr;     // [nq] as the device holds it: above MC_CAP after an overflowing launch (mode 1)
+    float *scores = nullptr;     // [nq, stride] fp16-path scores of the first min(cnt, stride) entries
+    int64_t *rows = nullptr;     // [nq, stride] their rows
+    int32_t *flags = nullptr;    // [nq] mode 0
+    float *bE = nullptr;         // [nq, 2] mode 0: b and E as k_mc_finish evaluated them
+    float *bE_dev = nullptr;     // the device words behind bE (the hook's)
+};
+
+// a group's thresholds, counts and buffer entries, unpacked for the probe (after the stream has been waited for)
+ssw_status probe_read(const McProbe &pr, int nq, int stride, const float *thr, const unsigned *cnt, const uint64_t *buf) {
+    if (pr.thr) SSW_HIP_TRY(hipMemcpy(pr.thr, thr, (size_t)nq * 4, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> c((size_t)nq);
+    SSW_HIP_TRY(hipMemcpy(c.data(), cnt, (size_t)nq * 4, hipMemcpyDeviceToHost));
+    if (pr.cnt) std::copy(c.begin(), c.end(), pr.cnt);
+    if (!pr.scores && !pr.rows) return SSW_OK;
+    std::vector<uint64_t> keys((size_t)nq * stride);
+    SSW_HIP_TRY(hipMemcpy2D(keys.data(), (size_t)stride * 8, buf, (size_t)MC_CAP * 8, (size_t)stride * 8, (size_t)nq,
+                            hipMemcpyDeviceToHost));
+    for (int q = 0; q < nq; ++q)
+        for (uint32_t e = 0; e < std::min<uint32_t>(c[(size_t)q], (uint32_t)stride); ++e) {
+            const uint64_t key = keys[(size_t)q * stride + e];
+            if (pr.scores) pr.scores[(size_t)q * stride + e] = ord_to_f32((uint32_t)(key >> 32));
+            if (pr.rows) pr.rows[(size_t)q * stride + e] = (int64_t)(0xFFFFFFFFu - (uint32_t)key);
+        }
+    return SSW_OK;
+}
+
 // one group of nq <= MC_GROUP queries [q0, q0 + nq) of the call: everything up to its results in the caller's arrays;
 // failed: the call's queries that the plain batch has to answer
 ssw_status run_group(ssw_index *idx, const float *q_host, int32_t q0, int32_t nq, const int64_t *ex_images,
                      const int64_t *ex_offsets, int32_t k, int M, float scale, int64_t *out_images, float *out_scores,
-                     int64_t *out_best_rows, int32_t *out_counts, std::vector<int32_t> &failed) {
+                     int64_t *out_best_rows, int32_t *out_counts, std::vector<int32_t> &failed,
+                     const McProbe *probe = nullptr) {
     McState &mc = idx->mc;
     const int D = idx->dim, R = strip_rows(D);
     const float *Q = q_host + (size_t)q0 * D;
@@ -631,10 +671,23 @@ ssw_status run_group(ssw_index *idx, const float *q_host, int32_t q0, int32_t nq
     const float *Qf = reinterpret_cast<const float *>(mc.in_dev);
     hipLaunchKernelGGL(k_mc_prep, dim3(qp / 4), dim3(256), 0, s, Qf, (int)nq, qp, D, scale_q, Qh, qnorm, thr, cnt, kept, ovf,
                        appended);
+    const std::vector<int64_t> bounds = level_bounds(strips, R, M);
+    if (probe) {
+        const float meta[6] = {scale, scale_q, idx->prune.rows_maxabs, idx->prune.rows_maxnorm, maxabs_q, (float)M};
+        if (probe->meta) std::copy(meta, meta + 6, probe->meta);
+        if (probe->n_levels) *probe->n_levels = (int32_t)bounds.size();
+        for (size_t l = 0; probe->levels && l < bounds.size() && l < (size_t)probe->levels_cap; ++l) probe->levels[l] = bounds[l];
+        if (probe->perm) SSW_HIP_TRY(hipMemcpy(probe->perm, mc.perm, (size_t)strips * 4, hipMemcpyDeviceToHost));
+    }
     int64_t s0 = 0;
-    for (const int64_t s1 : level_bounds(strips, R, M)) {
+    for (const int64_t s1 : bounds) {
         if (s1 <= s0) continue;
         SSW_TRY(launch_candidates(idx, scale, mc.perm + s0, s1 - s0, Qh, qp / MC_QT, thr, cnt, buf));
+        if (probe && probe->mode == 1) {  // the candidate kernel's raw output
+            SSW_HIP_TRY(hipGetLastError());
+            SSW_HIP_TRY(hipStreamSynchronize(s));
+            return probe_read(*probe, nq, MC_CAP, thr, cnt, buf);
+        }
         hipLaunchKernelGGL(k_mc_compact, dim3(nq), dim3(256), 0, s, buf, cnt, kept, thr, ovf, appended, M);
         s0 = s1;
     }
@@ -650,10 +703,16 @@ ssw_status run_group(ssw_index *idx, const float *q_host, int32_t q0, int32_t nq
     a.out_images = reinterpret_cast<int64_t *>(mc.res_dev + L.images), a.out_rows = reinterpret_cast<int64_t *>(mc.res_dev + L.rows);
     a.out_scores = reinterpret_cast<float *>(mc.res_dev + L.scores);
     a.out_counts = reinterpret_cast<int32_t *>(mc.res_dev + L.counts), a.out_flags = reinterpret_cast<int32_t *>(mc.res_dev + L.flags);
+    a.out_bE = probe ? probe->bE_dev : nullptr;
     launch_finish(idx, nq, a);
     SSW_HIP_TRY(hipGetLastError());
     SSW_HIP_TRY(hipMemcpyAsync(mc.res_host, mc.res_dev, L.res_bytes, hipMemcpyDeviceToHost, s));
     SSW_HIP_TRY(hipStreamSynchronize(s));  // the group's one wait
+    if (probe) {
+        SSW_TRY(probe_read(*probe, nq, M, thr, cnt, buf));
+        if (probe->flags) memcpy(probe->flags, mc.res_host + L.flags, (size_t)nq * 4);
+        if (probe->bE && probe->bE_dev) SSW_HIP_TRY(hipMemcpy(probe->bE, probe->bE_dev, (size_t)nq * 8, hipMemcpyDeviceToHost));
+    }
     mc.stats[6] += strips;
     mc.stats[7] += (int64_t) * reinterpret_cast<const unsigned long long *>(mc.res_host + L.appended);
     const int64_t *r_img = reinterpret_cast<const int64_t *>(mc.res_host + L.images);
@@ -674,6 +733,16 @@ ssw_status run_group(ssw_index *idx, const float *q_host, int32_t q0, int32_t nq
         if (out_best_rows) memcpy(out_best_rows + o, r_row + g, m * 8);
         if (out_scores) memcpy(out_scores + o, r_sc + g, m * 4);
     }
+    return SSW_OK;
+}
+
+// the state a pruned call leaves: the last query kept, the score buffer for the first reader to complete
+ssw_status leave_last_query(ssw_index *idx, const float *q_host, int32_t nq) {
+    const size_t D = (size_t)idx->dim;
+    PruneState &p = idx->prune;
+    if (!p.q_last) SSW_HIP_TRY(hipMalloc((void **)&p.q_last, D * sizeof(float)));
+    SSW_TRY(idx->q_stage.push(p.q_last, q_host + (size_t)(nq - 1) * D, D * sizeof(float), idx->stream));
+    idx->scores_partial = true;
     return SSW_OK;
 }
 
@@ -743,12 +812,7 @@ extern "C" ssw_status ssw_index_topk_batch_mc(ssw_index *idx, const float *q_hos
             if (out_scores) memcpy(out_scores + o, &sc[f * k], m * 4);
         }
     }
-    // the state a pruned call leaves: the last query kept, the score buffer for the first reader to complete
-    PruneState &p = idx->prune;
-    if (!p.q_last) SSW_HIP_TRY(hipMalloc((void **)&p.q_last, D * sizeof(float)));
-    SSW_TRY(idx->q_stage.push(p.q_last, q_host + (size_t)(nq - 1) * D, D * sizeof(float), idx->stream));
-    idx->scores_partial = true;
-    return SSW_OK;
+    return leave_last_query(idx, q_host, nq);
 }
 
 extern "C" ssw_status ssw_index_topk_batch_mc_stats(ssw_index *idx, int64_t *out8) {
@@ -756,3 +820,51 @@ extern "C" ssw_status ssw_index_topk_batch_mc_stats(ssw_index *idx, int64_t *out
     for (int i = 0; i < 8; ++i) out8[i] = idx->mc.stats[i];
     return SSW_OK;
 }
+
+#ifdef SSW_DEBUG_HOOKS
+// include/seesaw_hip_debug.h: one group through run_group with a probe
+extern "C" ssw_status ssw_debug_mc_candidates(ssw_index *idx, const float *q_host, int32_t nq, int32_t k, int32_t mode,
+                                              float *out_meta, int64_t *out_levels, int32_t levels_cap, int32_t *out_n_levels,
+                                              int32_t *out_perm, float *out_thr, uint32_t *out_cnt, float *out_scores,
+                                              int64_t *out_rows, int32_t *out_flags, float *out_bE) {
+    const char *who = "ssw_debug_mc_candidates";
+    SSW_TRY(refuse_view(idx, who));
+    SSW_TRY(refuse_dims128(idx, who));
+    SSW_REQUIRE(idx != nullptr && q_host != nullptr, "NULL argument");
+    if (idx->dim != 256 && idx->dim != 512 && idx->dim != 768 && idx->dim != 1024) {
+        set_error("%s: dim=%d unsupported", who, idx->dim);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    if (nq < 1 || nq > MC_GROUP || k < 1 || k > MC_MAX_K || (mode != 0 && mode != 1)) {
+        set_error("%s: nq=%d outside [1, %d], k=%d outside [1, %d] or mode=%d not 0 or 1", who, nq, MC_GROUP, k, MC_MAX_K, mode);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    SSW_TRY(check_query_batch(idx, q_host, nq));
+    McState &mc = idx->mc;
+    DeviceGuard guard(idx->device);
+    SSW_TRY(rows_stats(idx));
+    const float maxabs = idx->prune.rows_maxabs;
+    float maxabs_q = 0.f;
+    for (size_t i = 0; i < (size_t)nq * idx->dim; ++i) maxabs_q = std::max(maxabs_q, std::fabs(q_host[i]));
+    if (!(maxabs >= MC_MIN_ABS && maxabs <= MC_MAX_ABS && maxabs_q >= MC_MIN_ABS && maxabs_q <= MC_MAX_ABS)) {
+        set_error("%s: no bound at this magnitude of the rows or the queries (the product takes the plain batch)", who);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    int M = 64;
+    while (M < 4 * k) M <<= 1;
+    McProbe pr;
+    pr.mode = mode, pr.meta = out_meta, pr.levels = out_levels, pr.levels_cap = levels_cap, pr.n_levels = out_n_levels;
+    pr.perm = out_perm, pr.thr = out_thr, pr.cnt = out_cnt, pr.scores = out_scores, pr.rows = out_rows;
+    pr.flags = out_flags, pr.bE = out_bE;
+    if (mode == 0) SSW_HIP_TRY(hipMalloc((void **)&pr.bE_dev, (size_t)nq * 8));
+    int64_t stats[8];
+    std::copy(mc.stats, mc.stats + 8, stats);  // the counters are the product calls' alone
+    std::vector<int32_t> failed, counts((size_t)nq, 0);
+    ssw_status st = run_group(idx, q_host, 0, nq, nullptr, nullptr, k, M, pow2_scale(maxabs), nullptr, nullptr, nullptr,
+                              counts.data(), failed, &pr);
+    std::copy(stats, stats + 8, mc.stats);
+    (void)hipFree(pr.bE_dev);
+    if (st != SSW_OK) return st;
+    return leave_last_query(idx, q_host, nq);
+}
+#endif
