@@ -212,6 +212,23 @@ ssw_status ssw_debug_prune6_survivors_mq(ssw_index *idx, int32_t nq, int32_t slo
                                          int32_t sel_count, int32_t sel_overflow, int64_t cap, int32_t *out_published,
                                          int64_t *out_collected, int64_t *out_rows);
 
+/* The pruned batch's chunk on the packed 5-bit shadow (csrc/prune.hip, "a chunk of up to 16 queries on the 5-bit
+ * shadow"; tests/test_prune5_batch_gpu.py): what ssw_index_topk_batch_pruned runs on an index whose single queries scan
+ * the 5-bit shadow (ssw_tune_prune5) and that holds no 6-bit shadow.
+ * ssw_tune_prune5_batch: min_rows >= 0 = the smallest such index whose pruned batches scan the 5-bit shadow (never below
+ *   the single call's count, ssw_tune_prune5); < 0 = the product's constant again (25 M rows).
+ * ssw_debug_prune5_bounds_mq: k_q6_query_mq + k_q5_bounds_mq; arguments and outputs as ssw_debug_prune6_bounds_mq, on the
+ *   5-bit shadow (built if missing or stale), out_I = the exact integer sums of 8 c with 256 d_hi + d_lo.
+ * ssw_debug_prune5_survivors_mq: k_survivors_mq with the 5-bit code norm for one slot of the chunk the last
+ *   ssw_debug_prune5_bounds_mq bounded, against the hand-written threshold kept for the slot as the batch keeps its
+ *   selection's keys, then k_prune_publish_mq; arguments and outputs as ssw_debug_prune_survivors. */
+ssw_status ssw_tune_prune5_batch(int64_t min_rows);
+ssw_status ssw_debug_prune5_bounds_mq(ssw_index *idx, const float *q_host, int32_t nq, int64_t *out_I, float *out_lb,
+                                      float *out_Qe, int8_t *out_codes);
+ssw_status ssw_debug_prune5_survivors_mq(ssw_index *idx, int32_t nq, int32_t slot, float threshold, int32_t k,
+                                         int32_t sel_count, int32_t sel_overflow, int64_t cap, int32_t *out_published,
+                                         int64_t *out_collected, int64_t *out_rows);
+
 /* The pruned batch that stays on the device (seesaw_hip.h, ssw_index_topk_batch_dev_pruned; csrc/rescore_dev.hip).
  * ssw_tune_surv_cap: the survivors a slot of that entry may have and still be certified (and the final survivors of a
  *   single query on the two-stage 4 + 1-bit shadow, ssw_tune_prune41), 1 .. 2^18; any other value =

@@ -255,7 +255,11 @@ _DEBUG_SIGNATURES = {
     "ssw_debug_prune6_bounds_mq": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ssw_debug_prune6_survivors_mq": (c_i32, [c_void_p, c_i32, c_i32, ctypes.c_float, c_i32, c_i32, c_i32, c_i64, c_i32_p,
                                               c_i64_p, c_void_p]),
-    "ssw_debug_mc_candidates": (c_i32, [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_i32, c_i32_p,
+    "ssw_tune_prune5_batch": (c_i32, [c_i64]),
+    "ssw_debug_prune5_bounds_mq": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ssw_debug_prune5_survivors_mq": (c_i32, [c_void_p, c_i32, c_i32, ctypes.c_float, c_i32, c_i32, c_i32, c_i64, c_i32_p,
+                                              c_i64_p, c_void_p]),
+    "ssw_debug_mc_candidates":(c_i32, [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_void_p, c_void_p, c_i32, c_i32_p,
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ssw_tune_gemm": (c_i32, [c_i32]),
     "ssw_debug_gemm": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_void_p, c_void_p]),

@@ -431,16 +431,20 @@ ssw_status ssw_debug_prune_scan_mq_shape(ssw_index *idx, int32_t *out_blocks, in
 }
 
 static ssw_status require_shadow6(ssw_index *idx, const char *who);
+static ssw_status require_shadow5(ssw_index *idx, const char *who);
 
-// the chunk's buffers for nq queries staged from the host, for the hooks below; six: on the 6-bit shadow
-static ssw_status debug_chunk_ready(ssw_index *idx, int32_t nq, bool six = false) {
-    if (six) {
+// the chunk's buffers for nq queries staged from the host, for the hooks below, on the shadow `kind`
+static ssw_status debug_chunk_ready(ssw_index *idx, int32_t nq, ShadowKind kind = SHADOW_Q8) {
+    if (kind == SHADOW_Q5) {
+        SSW_REQUIRE(prune5_batch_eligible(idx), "the index's batches take no 5-bit shadow (ssw_tune_prune5_batch, rows)");
+        SSW_TRY(require_shadow5(idx, "prune5_bounds_mq"));
+    } else if (kind == SHADOW_Q6) {
         SSW_TRY(require_shadow6(idx, "prune6_bounds_mq"));
     } else {
         SSW_REQUIRE(prune_batch_eligible(idx), "the index is not pruned (ssw_tune_prune, dim, borrowed or escaped rows)");
         SSW_TRY(require_shadow(idx, "prune_bounds_mq"));
     }
-    idx->prune_batch.kind = six ? SHADOW_Q6 : SHADOW_Q8;  // what prune_batch_shadow would have left
+    idx->prune_batch.kind = kind;  // what prune_batch_shadow would have left
     SSW_TRY(ensure_ws(idx));
     int w = 0;
     SSW_TRY(batch_buffers(idx, nq, true, &w));
@@ -739,12 +743,16 @@ ssw_status ssw_debug_prune6_scan_mq_shape(ssw_index *idx, int32_t *out_blocks, i
     return SSW_OK;
 }
 
-ssw_status ssw_debug_prune6_bounds_mq(ssw_index *idx, const float *q_host, int32_t nq, int64_t *out_I, float *out_lb,
-                                      float *out_Qe, int8_t *out_codes) {
+}  // extern "C"
+
+// k_q6_query_mq and the bounds pass of a chunk on the packed shadow `kind`, 6-bit or 5-bit: the two differ in the shadow
+// and its kernel alone (prune_bounds_mq)
+static ssw_status debug_packed_bounds_mq(ssw_index *idx, ShadowKind kind, const float *q_host, int32_t nq, int64_t *out_I,
+                                         float *out_lb, float *out_Qe, int8_t *out_codes) {
     SSW_REQUIRE(idx != nullptr && q_host != nullptr, "NULL argument");
     SSW_REQUIRE(nq >= 1 && nq <= Q8_MQ_WIDTH, "nq=%d outside [1, %d]", nq, Q8_MQ_WIDTH);
     DeviceGuard guard(idx->device);
-    SSW_TRY(debug_chunk_ready(idx, nq, true));
+    SSW_TRY(debug_chunk_ready(idx, nq, kind));
     PruneBatchState &pb = idx->prune_batch;
     const size_t dim = (size_t)idx->dim, cells = (size_t)nq * idx->n;
     int64_t *dbg = nullptr;
@@ -787,24 +795,26 @@ ssw_status ssw_debug_prune6_bounds_mq(ssw_index *idx, const float *q_host, int32
     return SSW_OK;
 }
 
-ssw_status ssw_debug_prune6_survivors_mq(ssw_index *idx, int32_t nq, int32_t slot, float threshold, int32_t k,
-                                         int32_t sel_count, int32_t sel_overflow, int64_t cap, int32_t *out_published,
-                                         int64_t *out_collected, int64_t *out_rows) {
+// k_survivors_mq of one slot of such a chunk against a threshold written by hand, and the publish
+static ssw_status debug_packed_survivors_mq(ssw_index *idx, ShadowKind kind, int32_t nq, int32_t slot, float threshold,
+                                            int32_t k, int32_t sel_count, int32_t sel_overflow, int64_t cap,
+                                            int32_t *out_published, int64_t *out_collected, int64_t *out_rows) {
     SSW_REQUIRE(idx != nullptr && out_published != nullptr && out_collected != nullptr, "NULL argument");
     SSW_REQUIRE(nq >= 1 && nq <= Q8_MQ_WIDTH && slot >= 0 && slot < nq, "slot=%d outside the chunk of %d", slot, nq);
     SSW_REQUIRE(k >= 1 && k <= SSW_MAX_TOPK, "k=%d outside [1, %d]", k, SSW_MAX_TOPK);
     SSW_REQUIRE(cap >= 0 && cap <= SURV_CAP, "cap=%lld outside [0, %lld]", (long long)cap, (long long)SURV_CAP);
     SSW_REQUIRE(cap == 0 || out_rows != nullptr, "out_rows is NULL");
     PruneBatchState &pb = idx->prune_batch;
-    SSW_REQUIRE(idx->scores_partial && pb.kind == SHADOW_Q6 && shadow_current(idx, SHADOW_Q6) && pb.slots >= nq &&
+    SSW_REQUIRE(idx->scores_partial && pb.kind == kind && shadow_current(idx, kind) && pb.slots >= nq &&
                     idx->batch.side_slabs >= nq - 1,
-                "no bounds of such a chunk in the buffers: ssw_debug_prune6_bounds_mq first");
+                "no bounds of such a chunk in the buffers: ssw_debug_prune%d_bounds_mq first", kind == SHADOW_Q5 ? 5 : 6);
     DeviceGuard guard(idx->device);
     SSW_TRY(ensure_ws(idx));
     unsigned *st = pb.mq + slot * Q8_MQ_WORDS;
     SSW_HIP_TRY(hipMemsetAsync(st, 0, sizeof(unsigned), idx->stream));      // the counter and the "selection failed"
     SSW_HIP_TRY(hipMemsetAsync(st + 5, 0, sizeof(unsigned), idx->stream));  // word k_q6_query_mq resets
     SSW_TRY(stand_in_threshold(idx, threshold, k, sel_count, sel_overflow));
+    if (kind == SHADOW_Q5) SSW_TRY(prune_slot_candidates(idx, slot, k));  // the slot's pass reads the keys kept for it
     SSW_TRY(prune_survivors_slot(idx, nq, slot, k, cap));
     int32_t m[Q8_MQ_WIDTH];
     SSW_TRY(prune_publish_mq(idx, nq, cap, nullptr, m));
@@ -817,6 +827,33 @@ ssw_status ssw_debug_prune6_survivors_mq(ssw_index *idx, int32_t nq, int32_t slo
     *out_published = m[slot];
     *out_collected = (int64_t)collected;
     return SSW_OK;
+}
+
+extern "C" {
+
+ssw_status ssw_debug_prune6_bounds_mq(ssw_index *idx, const float *q_host, int32_t nq, int64_t *out_I, float *out_lb,
+                                      float *out_Qe, int8_t *out_codes) {
+    return debug_packed_bounds_mq(idx, SHADOW_Q6, q_host, nq, out_I, out_lb, out_Qe, out_codes);
+}
+
+ssw_status ssw_debug_prune6_survivors_mq(ssw_index *idx, int32_t nq, int32_t slot, float threshold, int32_t k,
+                                         int32_t sel_count, int32_t sel_overflow, int64_t cap, int32_t *out_published,
+                                         int64_t *out_collected, int64_t *out_rows) {
+    return debug_packed_survivors_mq(idx, SHADOW_Q6, nq, slot, threshold, k, sel_count, sel_overflow, cap, out_published,
+                                     out_collected, out_rows);
+}
+
+// ---- the pruned batch's chunk on the 5-bit shadow (prune.hip, k_q5_bounds_mq; tests/test_prune5_batch_gpu.py) -----------
+ssw_status ssw_debug_prune5_bounds_mq(ssw_index *idx, const float *q_host, int32_t nq, int64_t *out_I, float *out_lb,
+                                      float *out_Qe, int8_t *out_codes) {
+    return debug_packed_bounds_mq(idx, SHADOW_Q5, q_host, nq, out_I, out_lb, out_Qe, out_codes);
+}
+
+ssw_status ssw_debug_prune5_survivors_mq(ssw_index *idx, int32_t nq, int32_t slot, float threshold, int32_t k,
+                                         int32_t sel_count, int32_t sel_overflow, int64_t cap, int32_t *out_published,
+                                         int64_t *out_collected, int64_t *out_rows) {
+    return debug_packed_survivors_mq(idx, SHADOW_Q5, nq, slot, threshold, k, sel_count, sel_overflow, cap, out_published,
+                                     out_collected, out_rows);
 }
 
 // ---- the packed 5-bit shadow of single queries (prune.hip, "5-bit shadow"; tests/test_prune5_gpu.py) ----------------

@@ -222,12 +222,21 @@ static ssw_status prune_scan_chunk(ssw_index *idx, const BatchExcluded &excl, in
     pb.dev_w = 0;  // the state words are this chunk's from here on
     SSW_TRY(prune_bounds_mq(idx, w, nullptr, nullptr));
     SSW_HIP_TRY(hipEventRecord(p.ev, idx->stream));
+    // the 5-bit shadow's wide bounds: kc keys a slot, kept for the slot, and the chunk's exact threshold (index_prune.hip,
+    // prune_exact_threshold_mq) between the last selection and the survivor passes -- no host wait is added
+    const bool exact_t = pb.kind == SHADOW_Q5;
+    const int32_t kc = prune_candidates(k);
     for (int j = 0; j < w; ++j) {  // threshold and survivors of each query, in stream order
         int64_t n_ex = 0;
         const int64_t *ex = excl.of(b + j, &n_ex);
         SSW_TRY(install_excluded(idx, ex, n_ex, idx->stream));
-        SSW_TRY(do_select(idx, chunk_slab(idx, w, j), k, SelectDest{nullptr, 0u, false}, idx->stream));
-        SSW_TRY(prune_survivors_slot(idx, w, j, k, SURV_CAP));
+        SSW_TRY(do_select(idx, chunk_slab(idx, w, j), exact_t ? kc : k, SelectDest{nullptr, 0u, false}, idx->stream));
+        if (exact_t) SSW_TRY(prune_slot_candidates(idx, j, kc));
+        else SSW_TRY(prune_survivors_slot(idx, w, j, k, SURV_CAP));
+    }
+    if (exact_t) {
+        SSW_TRY(prune_exact_threshold_mq(idx, w, k, kc));
+        for (int j = 0; j < w; ++j) SSW_TRY(prune_survivors_slot(idx, w, j, k, SURV_CAP));
     }
     SSW_TRY(prune_publish_mq(idx, w, SURV_CAP, p.ev, m));  // sleep through the shadow scan, spin on the rest
     for (int j = 0; j < w; ++j) {
@@ -312,7 +321,7 @@ static ssw_status topk_batch_run(ssw_index *idx, const float *q_host, int32_t nq
     if (avg && nq == 1) pruned = false;  // the single call below prunes by itself, on whichever shadow applies
     if (pruned) {
         bool ready = false;
-        if (idx->ws.xchg.msg_out == nullptr) SSW_TRY(prune_batch_shadow(idx, &ready));
+        if (idx->ws.xchg.msg_out == nullptr) SSW_TRY(prune_batch_shadow(idx, &ready, true));
         if (ready) SSW_TRY(batch_buffers(idx, std::min<int32_t>(nq, Q8_MQ_WIDTH), true, &W));
         pruned = ready && idx->batch.qb_dev;
     }

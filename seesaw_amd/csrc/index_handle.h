@@ -87,9 +87,13 @@ struct PruneBatchState {
     int64_t *surv_rows = nullptr;  // [slots][SURV_CAP]
     float *surv_scores = nullptr;  // [slots][SURV_CAP]
     int slots = 0;
-    // the shadow that bounds the chunk (prune_batch_shadow): the packed 6-bit one, else the int8 one.  The state words,
-    // the planes and the slabs hold one chunk at a time, so only one shadow ever serves them
+    // the shadow that bounds the chunk (prune_batch_shadow): the packed 5-bit one, the packed 6-bit one, else the int8
+    // one.  The state words, the planes and the slabs hold one chunk at a time, so only one shadow ever serves them
     ShadowKind kind = SHADOW_Q8;
+    // a chunk on the 5-bit shadow: what each slot's threshold selection left, for the chunk's exact threshold and the
+    // slot's survivor pass (prune_slot_candidates)
+    uint64_t *keys = nullptr;      // [Q8_MQ_WIDTH][SSW_MAX_TOPK]
+    int32_t *counts = nullptr;     // [Q8_MQ_WIDTH][2]: count, overflow
     int32_t *host = nullptr;       // pinned, mapped: [seq, survivors or -1 of each slot]
     unsigned seq = 0;
     // the last chunk of ssw_index_topk_batch_dev_pruned, for ssw_index_prune_batch_dev_read: its width (0: the words
@@ -97,7 +101,8 @@ struct PruneBatchState {
     int dev_w = 0;
     int64_t dev_cap = 0;
     void release() {
-        for (void *p : {(void *)mq, (void *)planes, (void *)surv_rows, (void *)surv_scores}) (void)hipFree(p);
+        for (void *p : {(void *)mq, (void *)planes, (void *)surv_rows, (void *)surv_scores, (void *)keys, (void *)counts})
+            (void)hipFree(p);
         if (host) (void)hipHostFree(host);
     }
 };
@@ -337,8 +342,12 @@ ssw_status prune_survivors(ssw_index *idx, ShadowKind kind, int32_t k, int64_t c
                            int32_t *out_m);
 ssw_status scan_for_topk(ssw_index *idx, const float *q_dev, int32_t k, bool *out_candidates);
 ssw_status ensure_prune_batch(ssw_index *idx, int w, int *out_w);
-ssw_status prune_batch_shadow(ssw_index *idx, bool *ready);
+bool prune5_batch_eligible(const ssw_index *idx);
+ssw_status prune_batch_shadow(ssw_index *idx, bool *ready, bool five_ok = false);
 ssw_status prune_bounds_mq(ssw_index *idx, int w, int32_t *dbg_hi, int32_t *dbg_lo, int64_t *dbg_I = nullptr);
+int32_t prune_candidates(int32_t k);
+ssw_status prune_slot_candidates(ssw_index *idx, int j, int32_t kc);
+ssw_status prune_exact_threshold_mq(ssw_index *idx, int w, int32_t k, int32_t kc);
 ssw_status prune_survivors_slot(ssw_index *idx, int w, int j, int32_t k, int64_t cap);
 ssw_status prune_publish_mq(ssw_index *idx, int w, int64_t cap, hipEvent_t sleep_ev_or_null, int32_t *out_m);
 ssw_status rescore_rows(ssw_index *idx, const float *q_dev, const int64_t *rows_dev, float *vals_dev, int64_t m, float *dst,

@@ -132,6 +132,10 @@ constexpr int64_t MIN_ROWS_DIMS128[2][5][2] = {
 // 1.539 at 25 M (spreads 0.071 together), 2.350 / 1.905 at 2^25, 3.408 / 2.972 at 50 M, 6.335 / 5.377 at 100 M (0.165):
 // ahead by more than both spreads at every size of the sweep, so the entry is its smallest.
 constexpr int64_t MIN_ROWS_Q5 = 25000000;
+// A pruned batch on such an index bounds its chunks on the 5-bit shadow as well, unless the index already holds a 6-bit
+// shadow (prune_batch_shadow; DESIGN.md section 4, "Pruned batch on the 5-bit shadow"): the single call's entry, so that
+// the batch and the single queries of one index share one shadow.
+constexpr int64_t MIN_ROWS_Q5_BATCH = MIN_ROWS_Q5;
 // ---- SHADOW_Q41 ----
 // The calls that take the 5-bit shadow scan the two-stage 4 + 1-bit shadow instead on an index of at least this many rows
 // (264 instead of 328 bytes a row read by the scan at dim 512, a refine pass over the first stage's survivors; prune.hip,
@@ -150,6 +154,7 @@ static SSW_TUNABLE bool g_prune = true;               // ssw_tune_prune
 static SSW_TUNABLE bool g_prune6 = true;              // ssw_tune_prune6
 static SSW_TUNABLE bool g_prune5 = true;              // ssw_tune_prune5
 static SSW_TUNABLE int64_t g_prune5_min_rows = -1;     // >= 0: this many rows instead of MIN_ROWS_Q5
+static SSW_TUNABLE int64_t g_prune5_batch_min_rows = -1;  // ssw_tune_prune5_batch: >= 0: instead of MIN_ROWS_Q5_BATCH
 static SSW_TUNABLE bool g_prune41 = true;             // ssw_tune_prune41
 static SSW_TUNABLE int64_t g_prune41_min_rows = -1;    // >= 0: this many rows instead of MIN_ROWS_Q41
 static SSW_TUNABLE int64_t g_coarse_cap = COARSE_CAP;  // first-stage survivors the refine walks as a list; more: dense
@@ -239,6 +244,10 @@ static bool prune_eligible_on(const ssw_index *idx, ShadowKind kind, bool batch)
 // threshold reads rows out of the selection's keys); an index with a map keeps the 6-bit or int8 path
 bool ssw::prune5_eligible(const ssw_index *idx) {
     return prune_eligible_on(idx, SHADOW_Q5, false) && idx->dtype == SSW_DTYPE_F32 && !idx->has_map;
+}
+// ... and its pruned batches, from the batch's own row count on (never below the single call's, as prune6_batch_eligible)
+bool ssw::prune5_batch_eligible(const ssw_index *idx) {
+    return prune5_eligible(idx) && idx->n >= (g_prune5_batch_min_rows >= 0 ? g_prune5_batch_min_rows : MIN_ROWS_Q5_BATCH);
 }
 // the two-stage shadow: the calls and indexes of the 5-bit shadow (its own switch and row count)
 bool ssw::prune41_eligible(const ssw_index *idx) {
@@ -453,7 +462,7 @@ ssw_status ssw::scan_for_topk(ssw_index *idx, const float *q_dev, int32_t k, boo
     bool ready = false;
     ShadowKind kind = SHADOW_Q41;
     const bool k_ok = k >= 1 && k <= SSW_MAX_TOPK && (idx->ws.xchg.msg_out == nullptr || k <= idx->ws.xchg.k_max);
-    const int32_t kc = std::min<int32_t>(SSW_MAX_TOPK, std::max<int32_t>(1024, 4 * std::min<int32_t>(k, SSW_MAX_TOPK)));
+    const int32_t kc = prune_candidates(k);
     if (k_ok && prune41_eligible(idx)) SSW_TRY(ensure_shadow(idx, kind, &ready));
     if (k_ok && !ready && prune5_eligible(idx)) {
         kind = SHADOW_Q5;
@@ -509,8 +518,8 @@ ssw_status ssw::rescore_rows(ssw_index *idx, const float *q_dev, const int64_t *
     return SSW_OK;
 }
 
-// ---- the pruned batch: ONE pass over the int8 or the 6-bit shadow bounds a chunk of up to 16 queries (prune.hip,
-// "Pruned batch") ----
+// ---- the pruned batch: ONE pass over the int8, the 6-bit or the 5-bit shadow bounds a chunk of up to 16 queries
+// (prune.hip, "Pruned batch") ----
 static_assert(BATCH_MAX_WIDTH == Q8_MQ_WIDTH, "a chunk of the pruned batch uses the batch's slabs");
 
 // the state of a chunk of w queries; the survivor lists may only be had for fewer slots: *out_w
@@ -524,6 +533,9 @@ ssw_status ssw::ensure_prune_batch(ssw_index *idx, int w, int *out_w) {
                                   hipHostMallocMapped | hipHostMallocCoherent));
         memset(pb.host, 0, (1 + Q8_MQ_WIDTH) * sizeof(int32_t));
     }
+    if (pb.kind == SHADOW_Q5 && !pb.keys)
+        SSW_HIP_TRY(hipMalloc((void **)&pb.keys, (size_t)Q8_MQ_WIDTH * SSW_MAX_TOPK * sizeof(uint64_t)));
+    if (pb.kind == SHADOW_Q5 && !pb.counts) SSW_HIP_TRY(hipMalloc((void **)&pb.counts, (size_t)Q8_MQ_WIDTH * 2 * sizeof(int32_t)));
     while (pb.slots < w) {  // grow; on failure keep halving the width
         SSW_HIP_TRY(hipStreamSynchronize(idx->stream));
         (void)hipFree(pb.surv_rows);
@@ -555,10 +567,18 @@ ssw_status ssw::ensure_prune_batch(ssw_index *idx, int w, int *out_w) {
 // where the 6-bit shadow is refused for memory, the int8 one under prune_batch_eligible.  prune_batch.kind remembers
 // the choice for the steps below.  *ready false: the batch is the plain one -- at dim 768, which has no int8 fallback,
 // whenever the index is below the batch's 6-bit constant or the 6-bit shadow was refused.
-ssw_status ssw::prune_batch_shadow(ssw_index *idx, bool *ready) {
+// five_ok (the host-waiting batch, ssw_index_topk_batch_pruned / _avg_pruned): ahead of those comes the 5-bit shadow single
+// queries scan, where prune5_batch_eligible says so, the index holds no 6-bit shadow (current, or stale and rebuilt in
+// place: either serves the batch without another allocation) and the 5-bit one is ready or fits.  So an index that
+// serves single queries and batches holds ONE packed shadow, whichever came first; a 5-bit shadow refused for memory
+// falls through to the rule above.  The entries that stay on the device keep the shadows they had.
+ssw_status ssw::prune_batch_shadow(ssw_index *idx, bool *ready, bool five_ok) {
     *ready = false;
-    ShadowKind kind = SHADOW_Q6;
-    if (prune6_batch_eligible(idx)) SSW_TRY(ensure_shadow(idx, kind, ready));
+    ShadowKind kind = SHADOW_Q5;
+    const bool holds6 = idx->prune.sh[SHADOW_Q6].codes && prune6_batch_eligible(idx);  // ... and the batch may scan it
+    if (five_ok && prune5_batch_eligible(idx) && !holds6) SSW_TRY(ensure_shadow(idx, kind, ready));
+    if (!*ready) kind = SHADOW_Q6;
+    if (!*ready && prune6_batch_eligible(idx)) SSW_TRY(ensure_shadow(idx, kind, ready));
     if (!*ready && prune_batch_eligible(idx)) {
         kind = SHADOW_Q8;
         SSW_TRY(ensure_shadow(idx, kind, ready));
@@ -570,12 +590,16 @@ ssw_status ssw::prune_batch_shadow(ssw_index *idx, bool *ready) {
 // The two device steps of a chunk that the lab hooks drive as well; the shadow prune_batch.kind names and the chunk's
 // buffers are ready and the w queries are in batch.qb_dev.  Lower bounds of query j into slab j; the handle's buffer
 // (the last query's slab) is partial from here on and q_last is the last query.  dbg_hi / dbg_lo: of the int8 chunk,
-// dbg_I: of the 6-bit chunk (lab hooks only).
+// dbg_I: of the 6-bit or the 5-bit chunk (lab hooks only).
 ssw_status ssw::prune_bounds_mq(ssw_index *idx, int w, int32_t *dbg_hi, int32_t *dbg_lo, int64_t *dbg_I) {
     PruneState &p = idx->prune;
     PruneBatchState &pb = idx->prune_batch;
     const Shadow &s = p.sh[pb.kind];
-    if (pb.kind == SHADOW_Q6) {
+    if (pb.kind == SHADOW_Q5) {  // the 6-bit chunk's query operand and state words
+        SSW_TRY(launch_q6_query_mq(idx->batch.qb_dev, idx->dim, w, pb.mq, pb.planes, p.q_last, idx->stream));
+        SSW_TRY(launch_q5_bounds_mq(s.codes, s.scale, s.err, pb.planes, pb.mq, w, idx->batch.side, slab_stride(idx),
+                                    idx->scores, idx->n, idx->dim, dbg_I, idx->device, idx->stream));
+    } else if (pb.kind == SHADOW_Q6) {
         SSW_TRY(launch_q6_query_mq(idx->batch.qb_dev, idx->dim, w, pb.mq, pb.planes, p.q_last, idx->stream));
         SSW_TRY(launch_q6_bounds_mq(s.codes, s.scale, s.err, pb.planes, pb.mq, w, idx->batch.side, slab_stride(idx),
                                     idx->scores, idx->n, idx->dim, dbg_I, idx->device, idx->stream));
@@ -588,13 +612,36 @@ ssw_status ssw::prune_bounds_mq(ssw_index *idx, int w, int32_t *dbg_hi, int32_t 
     return SSW_OK;
 }
 
-// the survivors of slot j against the keys the last selection left, into the slot's list (no publish)
+// The exact threshold of a chunk on the 5-bit shadow: prune_exact_threshold for every slot, all on the device.  The
+// slots' selections share one workspace, so after slot j's selection of kc keys prune_slot_candidates lists the keys' rows
+// in the slot's survivor list (free until its survivor pass) and keeps the keys and the count for the slot; after the
+// last slot's, prune_exact_threshold_mq scores every slot's candidates for its own query in ONE launch (the list's
+// scores) and raises every slot's k-th key in one more.
+int32_t ssw::prune_candidates(int32_t k) {
+    return std::min<int32_t>(SSW_MAX_TOPK, std::max<int32_t>(1024, 4 * std::min<int32_t>(k, SSW_MAX_TOPK)));
+}
+ssw_status ssw::prune_slot_candidates(ssw_index *idx, int j, int32_t kc) {
+    PruneBatchState &pb = idx->prune_batch;
+    return launch_candidate_rows_slot(idx->ws.out_keys, idx->ws.out_count, kc, idx->n, pb.surv_rows + (int64_t)j * SURV_CAP,
+                                      pb.keys + (size_t)j * SSW_MAX_TOPK, pb.counts + 2 * j, idx->stream);
+}
+ssw_status ssw::prune_exact_threshold_mq(ssw_index *idx, int w, int32_t k, int32_t kc) {
+    PruneBatchState &pb = idx->prune_batch;
+    SSW_TRY(launch_score_candidates(static_cast<const float *>(idx->X), idx->batch.qb_dev, pb.surv_rows, SURV_CAP, kc, w,
+                                    pb.surv_scores, idx->n, idx->dim, idx->device, idx->stream));
+    return launch_exact_threshold_mq(pb.keys, pb.counts, pb.surv_scores, SURV_CAP, w, k, kc, idx->stream);
+}
+
+// the survivors of slot j against the keys the last selection left -- on the 5-bit shadow: the keys kept for the slot,
+// its k-th raised by prune_exact_threshold_mq -- into the slot's list (no publish)
 ssw_status ssw::prune_survivors_slot(ssw_index *idx, int w, int j, int32_t k, int64_t cap) {
     PruneBatchState &pb = idx->prune_batch;
     const Shadow &s = idx->prune.sh[pb.kind];
+    const bool kept = pb.kind == SHADOW_Q5;
     return launch_survivors_mq(chunk_slab(idx, w, j), s.err, s.scale, s.max, idx->n, idx->dim, code_bits(pb.kind),
-                               idx->ws.out_keys, idx->ws.out_count, k, pb.mq + j * Q8_MQ_WORDS, pb.surv_rows + (int64_t)j * SURV_CAP, cap, idx->device,
-                               idx->stream);
+                               kept ? pb.keys + (size_t)j * SSW_MAX_TOPK : idx->ws.out_keys,
+                               kept ? pb.counts + 2 * j : idx->ws.out_count, k, pb.mq + j * Q8_MQ_WORDS,
+                               pb.surv_rows + (int64_t)j * SURV_CAP, cap, idx->device, idx->stream);
 }
 
 // every slot's count (or -1) of the chunk -> out_m[w]; ONE host wait: a sleep on sleep_ev_or_null first, then a spin
@@ -705,6 +752,11 @@ ssw_status ssw_tune_prune6(int32_t enable, int64_t min_rows) {
 ssw_status ssw_tune_prune5(int32_t enable, int64_t min_rows) {
     g_prune5 = enable != 0;
     g_prune5_min_rows = min_rows < 0 ? -1 : min_rows;  // < 0: MIN_ROWS_Q5 again
+    return SSW_OK;
+}
+
+ssw_status ssw_tune_prune5_batch(int64_t min_rows) {
+    g_prune5_batch_min_rows = min_rows < 0 ? -1 : min_rows;  // < 0: MIN_ROWS_Q5_BATCH again
     return SSW_OK;
 }
 

@@ -1426,6 +1426,28 @@ __global__ __launch_bounds__(256) void k_q5_bounds(const u32x4 *__restrict__ cod
     tile_scan<Q5Tiles, OneQuery, C, T, DEBUG>(codes, scale, err, planes, n, {st, scores, {dbg_I}});
 }
 
+// ---- a chunk of up to 16 queries on the 5-bit shadow ("Pruned batch on the 5-bit shadow") ---------
+// lb5 of every row for every query of the chunk into the slot's slab: Q5Tiles' rows as one MFMA operand, the chunk's
+// queries (k_q6_query_mq: k_q6_query's planes and state words a slot) as the other, so the 14 columns k_q5_bounds
+// multiplies by zeros are queries here and (****) holds per slot.  A pair of k-steps of a tile is unpacked ONCE into the
+// two operand groups {m0, m1, m2, x0} and {m3, m4, x1, x2} (eight registers, live for four MFMAs: each group meets the hi
+// and the lo plane of its k-step), so the pass costs k_q5_bounds' code loads and unpack with four MFMAs a pair instead of
+// two.  Registers a lane at dim 512 / 1024: the query operand 64 / 128 (two planes of KS k-steps, loaded once a launch),
+// two sets of a request's codes 2 x 40 and of its rows' constants 2 x 8 T, two accumulators of four.
+// Tiles in flight: 10 KiB a request of a wave at both dims, k_q5_bounds' shape (Q5_BLOCKS_PER_CU, q5_default_tiles) --
+// the loads and the unpack are that kernel's, and 16 MFMAs a 5-KiB tile are far from binding.  No other shape was swept.
+constexpr int Q5MQ_BLOCKS_PER_CU = Q5_BLOCKS_PER_CU;
+constexpr int q5mq_default_tiles(int C) { return q5_default_tiles(C); }
+
+template <int C, int T, bool DEBUG>
+__global__ __launch_bounds__(256) void k_q5_bounds_mq(const u32x4 *__restrict__ codes, const float *__restrict__ scale,
+                                                      const float *__restrict__ err, const u32x4 *__restrict__ planes,
+                                                      const unsigned *__restrict__ mq, int w, float *__restrict__ side,
+                                                      int64_t stride, float *__restrict__ own, int64_t n,
+                                                      int64_t *__restrict__ dbg_I) {
+    tile_scan<Q5Tiles, Chunk<DebugSum>, C, T, DEBUG>(codes, scale, err, planes, n, {mq, w, side, stride, own, n, {dbg_I}});
+}
+
 // ---- the two-stage 4 + 1-bit shadow of f32 rows ("Two-stage 4 + 1-bit shadow") ----------------------
 // Codes, s5 and a5 are q8_quantise_row<C, 15>'s, the 5-bit shadow's.  Write u = c + 16 in [1, 31], h = u >> 1 in [0, 15],
 // b = u & 1, so c = 2 h + b - 16.  With D_i = 256 d_hi,i + d_lo,i and the query state of k_q6_query:
@@ -1719,10 +1741,8 @@ __global__ void k_prune_publish_q41(const unsigned *__restrict__ st, const unsig
 // The threshold selection over the lower bounds ran for kc = min(SSW_MAX_TOPK, max(1024, 4 k)) keys instead of k.  Their
 // rows are scored exactly and T_x = the k-th largest of those scores: k distinct rows, none excluded, score at least
 // T_x, so the k-th best score of the index is >= T_x and a row with ub < max(T_lb, T_x) cannot be among the k best.
-__global__ __launch_bounds__(256) void k_candidate_rows(const uint64_t *__restrict__ keys, const int32_t *__restrict__ sel_count,
-                                                        int32_t kc, int64_t n, int64_t *__restrict__ rows_out) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= kc) return;
+__device__ __forceinline__ void candidate_row(const uint64_t *__restrict__ keys, const int32_t *__restrict__ sel_count,
+                                              int32_t kc, int64_t n, int64_t *__restrict__ rows_out, int i) {
     // a selection that overflowed leaves no keys to trust: row 0 throughout (k_exact_threshold leaves it alone)
     const int count = sel_count[1] != 0 ? 0 : max(0, min(sel_count[0], kc));
     // composite_key's low word (select.hip): 0xffffffff - row
@@ -1731,16 +1751,35 @@ __global__ __launch_bounds__(256) void k_candidate_rows(const uint64_t *__restri
     rows_out[i] = row < n ? row : 0;  // (never beyond the rows, whatever the keys hold)
 }
 
+__global__ __launch_bounds__(256) void k_candidate_rows(const uint64_t *__restrict__ keys, const int32_t *__restrict__ sel_count,
+                                                        int32_t kc, int64_t n, int64_t *__restrict__ rows_out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= kc) return;
+    candidate_row(keys, sel_count, kc, n, rows_out, i);
+}
+
+// The same for one slot of a chunk, whose selection's keys and count the next slot's selection overwrites: they are kept
+// beside the rows -- the kc keys into keep_keys, [count, overflow] into keep_count -- for k_exact_threshold_mq and the
+// slot's survivor pass, which run after every slot's selection.
+__global__ __launch_bounds__(256) void k_candidate_rows_slot(const uint64_t *__restrict__ keys,
+                                                             const int32_t *__restrict__ sel_count, int32_t kc, int64_t n,
+                                                             int64_t *__restrict__ rows_out, uint64_t *__restrict__ keep_keys,
+                                                             int32_t *__restrict__ keep_count) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= kc) return;
+    candidate_row(keys, sel_count, kc, n, rows_out, i);
+    keep_keys[i] = keys[i];
+    if (i < 2) keep_count[i] = sel_count[i];
+}
+
 constexpr int TX_THREADS = 1024, TX_KEYS = SSW_MAX_TOPK;
 static_assert((TX_KEYS & (TX_KEYS - 1)) == 0 && TX_KEYS >= TX_THREADS, "a power of two");
 
 // One block.  The ordinal keys of the candidates' exact scores (0 for a NaN score and beyond the count: below every
 // score's key, -inf's included) are sorted descending in LDS (bitonic over P = the power of two >= kc keys); T_x's key
 // is the k-th, if it is a score's.
-__global__ __launch_bounds__(TX_THREADS) void k_exact_threshold(uint64_t *__restrict__ keys,
-                                                                const int32_t *__restrict__ sel_count,
-                                                                const float *__restrict__ vals, int32_t k, int32_t kc,
-                                                                int32_t P) {
+__device__ __forceinline__ void exact_threshold(uint64_t *__restrict__ keys, const int32_t *__restrict__ sel_count,
+                                                const float *__restrict__ vals, int32_t k, int32_t kc, int32_t P) {
     __shared__ uint32_t ord[TX_KEYS];
     if (sel_count[0] < k || sel_count[1] != 0) return;  // the selection failed: the caller falls back
     const int count = min(sel_count[0], kc);  // >= k >= 1 here
@@ -1767,6 +1806,23 @@ __global__ __launch_bounds__(TX_THREADS) void k_exact_threshold(uint64_t *__rest
         if (tx > (uint32_t)(key >> 32)) keys[k - 1] = ((uint64_t)tx << 32) | (key & 0xffffffffull);
     }
 }
+
+__global__ __launch_bounds__(TX_THREADS) void k_exact_threshold(uint64_t *__restrict__ keys,
+                                                                const int32_t *__restrict__ sel_count,
+                                                                const float *__restrict__ vals, int32_t k, int32_t kc,
+                                                                int32_t P) {
+    exact_threshold(keys, sel_count, vals, k, kc, P);
+}
+
+// One block a slot of a chunk, slot j = blockIdx.y: the keys and the count k_candidate_rows_slot kept for it (TX_KEYS keys
+// and two words a slot) and the exact scores of its candidates at vals + j * vals_stride
+__global__ __launch_bounds__(TX_THREADS) void k_exact_threshold_mq(uint64_t *__restrict__ keys,
+                                                                   const int32_t *__restrict__ sel_count,
+                                                                   const float *__restrict__ vals, int64_t vals_stride,
+                                                                   int32_t k, int32_t kc, int32_t P) {
+    const int j = blockIdx.y;
+    exact_threshold(keys + (size_t)j * TX_KEYS, sel_count + 2 * j, vals + (int64_t)j * vals_stride, k, kc, P);
+}
 }  // namespace
 
 bool q8_dim_supported(int32_t dim) { return dim == 256 || dim == 512 || dim == 1024; }
@@ -1789,21 +1845,23 @@ static void dispatch_dim(int C, F f) {
     f(Int<4>{});
 }
 
-// The launch shape of the five tile scans on the matrix core, by TileScan (ssw_tune_prune_scan_mq, ssw_tune_prune6_scan,
-// ssw_tune_prune6_scan_mq, ssw_tune_prune5_scan, ssw_tune_prune41_scan; lab build only): four-wave blocks per CU, and 16-row tiles of one request (0: the scan's
-// default for C)
+// The launch shape of the six tile scans on the matrix core, by TileScan (ssw_tune_prune_scan_mq, ssw_tune_prune6_scan,
+// ssw_tune_prune6_scan_mq, ssw_tune_prune5_scan, ssw_tune_prune41_scan; lab build only; SCAN_Q5_MQ has no such entry and
+// keeps its defaults): four-wave blocks per CU, and 16-row tiles of one request (0: the scan's default for C)
 struct ScanTune {
     int blocks_per_cu;
     int tiles;
 };
-constexpr int SCAN_BLOCKS_PER_CU[5] = {MQ_BLOCKS_PER_CU, Q6_BLOCKS_PER_CU, Q6MQ_BLOCKS_PER_CU, Q5_BLOCKS_PER_CU, Q4_BLOCKS_PER_CU};
-static SSW_TUNABLE ScanTune g_scan_tune[5] = {{SCAN_BLOCKS_PER_CU[0], 0}, {SCAN_BLOCKS_PER_CU[1], 0}, {SCAN_BLOCKS_PER_CU[2], 0},
-                                              {SCAN_BLOCKS_PER_CU[3], 0}, {SCAN_BLOCKS_PER_CU[4], 0}};
+constexpr int SCAN_BLOCKS_PER_CU[6] = {MQ_BLOCKS_PER_CU, Q6_BLOCKS_PER_CU, Q6MQ_BLOCKS_PER_CU, Q5_BLOCKS_PER_CU, Q4_BLOCKS_PER_CU,
+                                       Q5MQ_BLOCKS_PER_CU};
+static SSW_TUNABLE ScanTune g_scan_tune[6] = {{SCAN_BLOCKS_PER_CU[0], 0}, {SCAN_BLOCKS_PER_CU[1], 0}, {SCAN_BLOCKS_PER_CU[2], 0},
+                                              {SCAN_BLOCKS_PER_CU[3], 0}, {SCAN_BLOCKS_PER_CU[4], 0}, {SCAN_BLOCKS_PER_CU[5], 0}};
 constexpr int scan_default_tiles(TileScan scan, int C) {
     return scan == SCAN_Q8_MQ ? mq_default_tiles(C)
            : scan == SCAN_Q6  ? q6_default_tiles(C)
            : scan == SCAN_Q5  ? q5_default_tiles(C)
            : scan == SCAN_Q4  ? q4_default_tiles(C)
+           : scan == SCAN_Q5_MQ ? q5mq_default_tiles(C)
                               : q6mq_default_tiles(C);
 }
 
@@ -1834,7 +1892,7 @@ void tune_tile_scan(TileScan scan, int blocks_per_cu, int tiles) {
 
 // the C = dim / 256 a tile scan has instances of: its shadow's dims
 constexpr bool scan_has_dim(TileScan scan, int C) {
-    return scan == SCAN_Q8_MQ ? C != 3 : scan == SCAN_Q5 || scan == SCAN_Q4 ? C == 2 || C == 4 : true;
+    return scan == SCAN_Q8_MQ ? C != 3 : scan == SCAN_Q5 || scan == SCAN_Q4 || scan == SCAN_Q5_MQ ? C == 2 || C == 4 : true;
 }
 
 // f(Int<C>, Int<T>, DEBUG) for the instance of tile scan S that scan_shape's T and the caller's debug output ask for.
@@ -2173,6 +2231,21 @@ ssw_status launch_q5_bounds(const unsigned char *codes, const float *scale, cons
     });
 }
 
+// the chunk of w <= 16 queries on it: mq and planes are launch_q6_query_mq's, the slabs launch_q8_bounds_mq's
+ssw_status launch_q5_bounds_mq(const unsigned char *codes, const float *scale, const float *err, const int8_t *planes,
+                               const unsigned *mq, int32_t w, float *side, int64_t stride, float *own, int64_t n,
+                               int32_t dim, int64_t *dbg_I, int device, hipStream_t stream) {
+    if (n <= 0) return SSW_OK;
+    if (!q5_dim_supported(dim) || w < 1 || w > MQ_WIDTH) {
+        set_error("q5_bounds_mq: dim=%d, w=%d unsupported", dim, w);
+        return SSW_ERR_UNSUPPORTED;
+    }
+    return launch_tile_scan<SCAN_Q5_MQ>(dim, device, n, dbg_I != nullptr, [&](dim3 grid, auto c, auto t, auto d) {
+        hipLaunchKernelGGL((k_q5_bounds_mq<c.value, t.value, d.value>), grid, dim3(256), 0, stream, as_u32x4(codes), scale, err,
+                           as_u32x4(planes), mq, (int)w, side, stride, own, n, dbg_I);
+    });
+}
+
 // ---- the two-stage 4 + 1-bit shadow ---------------------------------------------------------------------------------
 size_t q41_coarse_bytes(int64_t n, int32_t dim) { return (size_t)packed_padded_rows(n) * (size_t)dim / 2; }
 size_t q41_fine_bytes(int64_t n, int32_t dim) { return (size_t)packed_padded_rows(n) * (size_t)dim / 8; }
@@ -2280,6 +2353,28 @@ ssw_status launch_exact_threshold(uint64_t *keys, const int32_t *sel_count, cons
     int P = TX_THREADS;
     while (P < kc) P <<= 1;
     hipLaunchKernelGGL(k_exact_threshold, dim3(1), dim3(TX_THREADS), 0, stream, keys, sel_count, vals, k, kc, P);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+ssw_status launch_candidate_rows_slot(const uint64_t *keys, const int32_t *sel_count, int32_t kc, int64_t n, int64_t *rows_out,
+                                      uint64_t *keep_keys, int32_t *keep_count, hipStream_t stream) {
+    hipLaunchKernelGGL(k_candidate_rows_slot, dim3((unsigned)((kc + 255) / 256)), dim3(256), 0, stream, keys, sel_count, kc, n,
+                       rows_out, keep_keys, keep_count);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
+}
+
+ssw_status launch_exact_threshold_mq(uint64_t *keys, const int32_t *sel_count, const float *vals, int64_t vals_stride, int32_t w,
+                                     int32_t k, int32_t kc, hipStream_t stream) {
+    if (k < 1 || kc < k || kc > TX_KEYS || w < 1 || w > MQ_WIDTH) {
+        set_error("exact_threshold_mq: k=%d, kc=%d outside [1, %d] or w=%d", k, kc, TX_KEYS, w);
+        return SSW_ERR_INVALID;
+    }
+    int P = TX_THREADS;
+    while (P < kc) P <<= 1;
+    hipLaunchKernelGGL(k_exact_threshold_mq, dim3(1, (unsigned)w), dim3(TX_THREADS), 0, stream, keys, sel_count, vals,
+                       vals_stride, k, kc, P);
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
 }

@@ -55,6 +55,38 @@ __global__ __launch_bounds__(256) void k_rescore_survivors(const typename R::T *
     }
 }
 
+// The candidates of a chunk's exact threshold (prune.hip, "the exact threshold"; f32 rows): grid (blocks, w), slot j =
+// blockIdx.y scores the kc rows at lists + j * list_stride for its own query into vals + j * list_stride, a wave a row,
+// two rows in flight.  No state word is read: a slot whose selection failed lists row 0 throughout and its threshold
+// kernel ignores the scores.  An entry that is no row of the index scores NaN, which the threshold kernel skips.
+template <int C>
+__global__ __launch_bounds__(256) void k_score_candidates(const float *__restrict__ X, const float *__restrict__ qb,
+                                                          const int64_t *__restrict__ lists, int64_t list_stride, int32_t kc,
+                                                          float *__restrict__ vals, int64_t n) {
+    const int j = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int64_t gwave = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t nwaves = (int64_t)gridDim.x * 4;
+    if (gwave >= kc) return;
+    const int64_t *rows = lists + (int64_t)j * list_stride;
+    float *out = vals + (int64_t)j * list_stride;
+    const Frag<C> qf = load_query<C>(qb + (int64_t)j * (C * 256), lane);
+    for (int64_t i = gwave; i < kc; i += RESCORE_IN_FLIGHT * nwaves) {
+        const int64_t i1 = i + nwaves;
+        const bool two = i1 < kc;
+        const int64_t r0 = rows[i], r1 = rows[two ? i1 : i];  // wave-uniform
+        const bool ok0 = (uint64_t)r0 < (uint64_t)n, ok1 = (uint64_t)r1 < (uint64_t)n;
+        const Frag<C> x0 = F32Rows::load<C>(X, ok0 ? r0 : 0, lane);
+        const Frag<C> x1 = F32Rows::load<C>(X, ok1 ? r1 : 0, lane);
+        const float v0 = wave_sum(lane_partial<C>(x0, qf));
+        const float v1 = wave_sum(lane_partial<C>(x1, qf));
+        if (lane == 0) {
+            out[i] = ok0 ? v0 : NAN;
+            if (two) out[i1] = ok1 ? v1 : NAN;
+        }
+    }
+}
+
 // the last word of a slot's exchange message (count | flags << 32, written by the selection that has just run on the
 // stream) gets bit 33 when the slot's certificate failed: "this rank's scores for this query are bounds"
 __global__ void k_mark_uncertified(const unsigned *__restrict__ st, int64_t cap, unsigned long long *__restrict__ word) {
@@ -108,6 +140,20 @@ ssw_status launch_rescore_survivors(const void *X, int32_t dtype, const float *q
     if (dtype == SSW_DTYPE_F16)
         return launch_t<H16Rows>(X, qb_dev, mq, lists, list_stride, cap, w, side, stride, own, n, dim, device, stream);
     return launch_t<F32Rows>(X, qb_dev, mq, lists, list_stride, cap, w, side, stride, own, n, dim, device, stream);
+}
+
+ssw_status launch_score_candidates(const float *X, const float *qb_dev, const int64_t *lists, int64_t list_stride, int32_t kc,
+                                   int32_t w, float *vals, int64_t n, int32_t dim, int device, hipStream_t stream) {
+    if (n <= 0 || w <= 0 || kc <= 0) return SSW_OK;
+    if (w > Q8_MQ_WIDTH || kc > list_stride || (dim != 512 && dim != 1024)) {
+        set_error("score_candidates: w=%d, kc=%d of %lld, dim=%d", w, kc, (long long)list_stride, dim);
+        return SSW_ERR_INVALID;
+    }
+    const dim3 grid((unsigned)rescore_blocks(device, kc), (unsigned)w), block(256);
+    if (dim == 512) hipLaunchKernelGGL(k_score_candidates<2>, grid, block, 0, stream, X, qb_dev, lists, list_stride, kc, vals, n);
+    else hipLaunchKernelGGL(k_score_candidates<4>, grid, block, 0, stream, X, qb_dev, lists, list_stride, kc, vals, n);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
 }
 
 ssw_status launch_mark_uncertified(const unsigned *slot_state, int64_t cap, uint64_t *msg_last_word, hipStream_t stream) {

@@ -322,10 +322,16 @@ ssw_status launch_rescore_survivors(const void *X, int32_t dtype, const float *q
                                     const int64_t *lists, int64_t list_stride, int64_t cap, int32_t w, float *side,
                                     int64_t stride, float *own, int64_t n, int32_t dim, int device, hipStream_t stream);
 int rescore_survivors_waves(int device, int64_t cap);
+// the exact scores (launch_scan's bits) of kc listed rows of every slot j < w of a chunk in ONE launch: the rows at
+// lists + j * list_stride (each below n; any other entry scores NaN) for query qb_dev + j * dim into vals + j * list_stride.
+// f32 rows at dims 512 and 1024: the exact threshold of a chunk on the 5-bit shadow
+ssw_status launch_score_candidates(const float *X, const float *qb_dev, const int64_t *lists, int64_t list_stride, int32_t kc,
+                                   int32_t w, float *vals, int64_t n, int32_t dim, int device, hipStream_t stream);
 ssw_status launch_mark_uncertified(const unsigned *slot_state, int64_t cap, uint64_t *msg_last_word, hipStream_t stream);
 // the tile scans on the int8 matrix core: launch_q8_bounds_mq, launch_q6_bounds, launch_q6_bounds_mq, launch_q5_bounds; scan_shape:
 // blocks and 16-row tiles per request of the launch the scan's launcher would make
-enum TileScan { SCAN_Q8_MQ, SCAN_Q6, SCAN_Q6_MQ, SCAN_Q5, SCAN_Q4 };  // SCAN_Q5: launch_q5_bounds, SCAN_Q4: launch_q4_bounds (below)
+// SCAN_Q5: launch_q5_bounds, SCAN_Q4: launch_q4_bounds, SCAN_Q5_MQ: launch_q5_bounds_mq (below)
+enum TileScan { SCAN_Q8_MQ, SCAN_Q6, SCAN_Q6_MQ, SCAN_Q5, SCAN_Q4, SCAN_Q5_MQ };
 void scan_shape(TileScan scan, int32_t dim, int device, int64_t n, int *out_blocks, int *out_tiles);
 // the packed 6-bit shadow of f32 or f16 rows (prune.hip, "6-bit shadow"): tiles of 16 rows, 3 dim / 4 bytes a row, buffers
 // padded to whole tiles.  q6_slot / q6_element / q6_word_offset are the ONE placement of an element's code: k-step u, lane
@@ -399,6 +405,11 @@ ssw_status launch_q5_build(const void *X, int32_t dtype, int64_t n, int32_t dim,
 ssw_status launch_q5_bounds(const unsigned char *codes, const float *scale, const float *err, const int8_t *planes,
                             const unsigned *st, float *scores, int64_t n, int32_t dim, int64_t *dbg_I, int device,
                             hipStream_t stream);
+// the chunk of w <= 16 queries on the 5-bit shadow (prune.hip): mq and planes are launch_q6_query_mq's, the slabs
+// launch_q8_bounds_mq's; dbg_I (lab hook only, else NULL): [w, n] the exact integer sums of 8 c with 256 d_hi + d_lo
+ssw_status launch_q5_bounds_mq(const unsigned char *codes, const float *scale, const float *err, const int8_t *planes,
+                               const unsigned *mq, int32_t w, float *side, int64_t stride, float *own, int64_t n,
+                               int32_t dim, int64_t *dbg_I, int device, hipStream_t stream);
 // The exact threshold of the 5-bit path (prune.hip, "exact threshold").  keys / sel_count: what a threshold selection of
 // kc >= k keys over the lower bounds left (an index without an image map: the low word of a key names its row).
 // candidate_rows: rows_out[i] = the row of key i for i < the number of keys, of key 0 (row 0 without keys) beyond, kc
@@ -409,6 +420,14 @@ ssw_status launch_candidate_rows(const uint64_t *keys, const int32_t *sel_count,
                                  hipStream_t stream);
 ssw_status launch_exact_threshold(uint64_t *keys, const int32_t *sel_count, const float *vals, int32_t k, int32_t kc,
                                   hipStream_t stream);
+// The same for a chunk, whose slots' selections share one workspace.  candidate_rows_slot: launch_candidate_rows, and the
+// selection's kc keys and [count, overflow] copied to keep_keys / keep_count for the slot.  exact_threshold_mq: ONE launch
+// for slots j < w over the kept keys (keys + j * SSW_MAX_TOPK), counts (sel_count + 2 j) and vals + j * vals_stride
+// (rescore_dev.hip, launch_score_candidates).
+ssw_status launch_candidate_rows_slot(const uint64_t *keys, const int32_t *sel_count, int32_t kc, int64_t n, int64_t *rows_out,
+                                      uint64_t *keep_keys, int32_t *keep_count, hipStream_t stream);
+ssw_status launch_exact_threshold_mq(uint64_t *keys, const int32_t *sel_count, const float *vals, int64_t vals_stride, int32_t w,
+                                     int32_t k, int32_t kc, hipStream_t stream);
 // The two-plane 5-bit shadow of f32 rows at dim 512 and 1024 (prune.hip, "two-stage 4 + 1-bit shadow").  The codes c, s5
 // and a5 are the 5-bit shadow's; with u = c + 16 the COARSE plane holds h = u >> 1 (a nibble) of every element in tiles of
 // 16 rows, dim / 2 bytes a row, and the FINE plane b = u & 1 row-major, dim / 8 bytes a row (bit i & 31 of the row's word

@@ -305,7 +305,9 @@ class DeviceIndex:
         nq iterables of image positions, each of which may be None.  The handle is left as after the last query's topk.
         `prune=True` (ssw_index_topk_batch_pruned): on an index whose single `topk` is pruned, one pass over a shadow
         -- from 25 M rows the packed 6-bit one single queries scan there, below that (or where that one is refused for
-        memory) the int8 one; at dim 768 the 6-bit one from 2^20 rows and no other -- bounds a chunk of up to 16 queries
+        memory) the int8 one; at dim 768 the 6-bit one from 2^20 rows and no other; on an f32 index of dim 512 or 1024
+        without an image map, from 25 M rows, the packed 5-bit one single queries scan there, unless the index already
+        holds a 6-bit one -- bounds a chunk of up to 16 queries
         and only each query's survivors are scored exactly -- the same results; `prune_stats` counts every query.  Any
         other index takes the plain batch.
         `matrix_core=True` (ssw_index_topk_batch_mc), for hundreds of queries: the rows are read in place once per
