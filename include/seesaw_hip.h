@@ -1099,11 +1099,14 @@ typedef struct ssw_clip ssw_clip;
 
 /* weight_blob: 72-byte header ("SSWCLIP1", then int32 v_hidden, v_layers, v_heads, v_mlp,
  * image, patch, t_hidden, t_layers, t_heads, t_mlp, t_max_positions, vocab, eos_token_id,
- * projection_dim, float layer_norm_eps, int32 reserved) followed by the f32 tensors of a
+ * projection_dim, float layer_norm_eps, int32 activation: 0 quick-GELU, 1 GELU 0.5 x (1 + erf(x / sqrt 2)), any
+ * other code SSW_ERR_INVALID) followed by the f32 tensors of a
  * transformers.CLIPModel state_dict in the order seesaw_amd/models/clip.py::pack_clip_weights
  * writes them.  GEMM weights are converted to bf16 on the device.
- * Served: head dim 64, hidden / MLP sizes multiples of 128 and hidden <= 1024, an image tower of at most 272 tokens
- * ((image / patch)^2 + 1; any patch size that divides the image: ViT-B/32, ViT-B/16, ViT-L/14 at 224 pixels), a text
+ * Served: head dim 64 (the image tower: also 80, 88, 104), hidden / MLP sizes multiples of 128, hidden <= 1664,
+ * projection <= 1280, an image tower of at most 272 tokens ((image / patch)^2 + 1; any patch size that divides the
+ * image: ViT-B/32, ViT-B/16, ViT-L/14, OpenCLIP ViT-H/14, ViT-bigG/14 at 224 pixels; ViT-g/14's
+ * shapes are accepted, its head dim 88 is tested as a kernel only), a text
  * tower of at most 80 positions.  Anything else is SSW_ERR_UNSUPPORTED, decided before any device call. */
 ssw_status ssw_clip_create(int32_t device, const void *weight_blob, size_t bytes, ssw_clip **out);
 ssw_status ssw_clip_destroy(ssw_clip *clip);

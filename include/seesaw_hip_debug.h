@@ -318,11 +318,12 @@ ssw_status ssw_debug_attn_out_stamps(uint64_t *out, int32_t n_words);
 /* ONE launch of one of the towers' attention kernels (csrc/clip.hip) on the caller's operands, with the launch shape
  * run_tower gives it (tests/test_attention_gpu.py holds each to an f64 softmax).  form: 0 attention_mfma<4>,
  * 1 attention_mfma<4, 2>, 2 attention_mfma<5>, 3 attention_rows64, 4 launch_attention_long (its own choice of
- * instance), 5 attn_pooled_rows (out is [B, D]: row 0 of every sequence; non-causal only).  qkv [qkv_rows_alloc, 3 D]
+ * instance), 5 attn_pooled_rows (out is [B, D]: row 0 of every sequence; non-causal only), 6 launch_attention_hd
+ * (attention_hd: D = 80 H, 88 H or 104 H, S <= 272, non-causal only; tests/test_clip_openclip_gpu.py).  qkv [qkv_rows_alloc, 3 D]
  * bf16 (q | k | v; rows_alloc >= B S), out [out_rows_alloc, D] bf16: both buffers travel whole, up and -- after the one
  * launch on the default stream -- down, so the rows past B S (past B for form 5) are guards the caller fills and reads
  * back.  SSW_ERR_UNSUPPORTED, with nothing launched and out untouched: S < 1, S > 64 (forms 0, 1, 3, 5), S > 80
- * (form 2), S > 272 (form 4), D != 64 H, causal with form 5. */
+ * (form 2), S > 272 (forms 4, 6), D != 64 H (forms 0 .. 5), D / H not 80, 88 or 104 (form 6), causal with form 5 or 6. */
 ssw_status ssw_debug_attention_run(int32_t form, int32_t B, int32_t S, int32_t D, int32_t H, int32_t causal, float scale,
                                    const uint16_t *qkv_bf16, int64_t qkv_rows_alloc, uint16_t *out_bf16_inout,
                                    int64_t out_rows_alloc);

@@ -34,10 +34,12 @@ typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 enum Epilogue { EPI_F32 = 0, EPI_BF16_BIAS = 1, EPI_BF16_BIAS_GELU = 2, EPI_F32_BIAS_RESIDUAL = 3, EPI_BF16_LN = 4, EPI_BF16_LN_GELU = 5,
-                EPI_F32_BIAS_RESIDUAL_STATS = 6, EPI_BF16_STREAM_STATS = 7 };  // as gemm_bf16.hip
+                EPI_F32_BIAS_RESIDUAL_STATS = 6, EPI_BF16_STREAM_STATS = 7, EPI_BF16_BIAS_ERF = 8, EPI_BF16_LN_ERF = 9 };  // as gemm_bf16.hip
 
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 __device__ __forceinline__ bf16 to_bf16(float x) { return (bf16)x; }
+// the exact GELU of OpenCLIP's ViT-H/14 and bigG/14 (torch's nn.GELU()), as gemm_bf16.hip's
+__device__ __forceinline__ float erf_gelu_f32(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678f)); }
 
 // ---------------------------------------------------------------------------------------
 // LayerNorm over the last dim (one wave per row), f32 in -> bf16 or f32 out.
@@ -45,7 +47,8 @@ __device__ __forceinline__ bf16 to_bf16(float x) { return (bf16)x; }
 // ---------------------------------------------------------------------------------------
 // One wave per row; the row (D <= 1024 floats = 4 float4 per lane) stays in registers, so x is
 // read once with 16-byte loads and mean / variance / normalise are a single pass.
-template <typename OutT>
+// NV: float4 per lane -- 4 for every width up to 1024, 7 for the rows up to 1664 of ViT-H/14 and bigG/14 (ROW_NV_WIDE).
+template <typename OutT, int NV = 4>
 __global__ __launch_bounds__(256) void layernorm_rows(const float *__restrict__ x, const int *__restrict__ row_index,
                                                       int n_rows, int D, const float *__restrict__ w,
                                                       const float *__restrict__ b, float eps, OutT *__restrict__ out) {
@@ -54,10 +57,10 @@ __global__ __launch_bounds__(256) void layernorm_rows(const float *__restrict__ 
     if (r >= n_rows) return;
     const float4 *xr = reinterpret_cast<const float4 *>(x + (int64_t)(row_index ? row_index[r] : r) * D);
     const int nv = D >> 2;  // float4 per row (D % 4 == 0)
-    float4 v[4];
+    float4 v[NV];
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < NV; ++i) {
         const int c = lane + 64 * i;
         v[i] = c < nv ? xr[c] : make_float4(0.f, 0.f, 0.f, 0.f);
         s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
@@ -67,7 +70,7 @@ __global__ __launch_bounds__(256) void layernorm_rows(const float *__restrict__ 
     const float mean = s / (float)D;
     float q = 0.f;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < NV; ++i) {
         if (lane + 64 * i < nv) {
             const float dx = v[i].x - mean, dy = v[i].y - mean, dz = v[i].z - mean, dw = v[i].w - mean;
             q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
@@ -79,7 +82,7 @@ __global__ __launch_bounds__(256) void layernorm_rows(const float *__restrict__ 
     const float4 *w4 = reinterpret_cast<const float4 *>(w), *b4 = reinterpret_cast<const float4 *>(b);
     OutT *o = out + (int64_t)r * D;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < NV; ++i) {
         const int c = lane + 64 * i;
         if (c < nv) {
             const float4 ww = w4[c], bb = b4[c];
@@ -99,7 +102,7 @@ __global__ __launch_bounds__(256) void layernorm_rows(const float *__restrict__ 
 // LN = true: y = LayerNorm(x) with (w, b) is the row (x is consumed); LN = false: y = x.
 // With `pos` given, x is the patch embedding's output and the row is put together here, the image tower's input:
 // token 0 of an image = cls + pos[0], token 1 + p = x[image * (T - 1) + p] + pos[1 + p].  y_out may be null (bf16 stream).
-template <bool LN>
+template <bool LN, int NV = 4>
 __global__ __launch_bounds__(256) void stack_input_rows(const float *__restrict__ x, int n_rows, int D,
                                                         const float *__restrict__ w, const float *__restrict__ b,
                                                         float eps, float *__restrict__ y_out, bf16 *__restrict__ y_bf16,
@@ -117,10 +120,10 @@ __global__ __launch_bounds__(256) void stack_input_rows(const float *__restrict_
         pr = reinterpret_cast<const float4 *>(pos + (int64_t)tk * D);
     }
     const int nv = D >> 2;
-    float4 v[4];
+    float4 v[NV];
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < NV; ++i) {
         const int c = lane + 64 * i;
         v[i] = c < nv ? xr[c] : make_float4(0.f, 0.f, 0.f, 0.f);
         if (pr && c < nv) {
@@ -135,7 +138,7 @@ __global__ __launch_bounds__(256) void stack_input_rows(const float *__restrict_
         const float mean = s / (float)D;
         float q = 0.f;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < NV; ++i) {
             if (lane + 64 * i < nv) {
                 const float dx = v[i].x - mean, dy = v[i].y - mean, dz = v[i].z - mean, dw = v[i].w - mean;
                 q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
@@ -147,7 +150,7 @@ __global__ __launch_bounds__(256) void stack_input_rows(const float *__restrict_
         const float4 *w4 = reinterpret_cast<const float4 *>(w), *b4 = reinterpret_cast<const float4 *>(b);
         s = 0.f;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < NV; ++i) {
             const int c = lane + 64 * i;
             if (c < nv) {
                 const float4 ww = w4[c], bb = b4[c];
@@ -161,7 +164,7 @@ __global__ __launch_bounds__(256) void stack_input_rows(const float *__restrict_
     }
     float q2 = 0.f;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) q2 += (v[i].x * v[i].x + v[i].y * v[i].y) + (v[i].z * v[i].z + v[i].w * v[i].w);
+    for (int i = 0; i < NV; ++i) q2 += (v[i].x * v[i].x + v[i].y * v[i].y) + (v[i].z * v[i].z + v[i].w * v[i].w);
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
         s += __shfl_xor(s, off, 64);
@@ -170,7 +173,7 @@ __global__ __launch_bounds__(256) void stack_input_rows(const float *__restrict_
     float4 *yo = reinterpret_cast<float4 *>(y_out + (int64_t)r * D);
     bf16x4 *yb = reinterpret_cast<bf16x4 *>(y_bf16 + (int64_t)r * D);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < NV; ++i) {
         const int c = lane + 64 * i;
         if (c < nv) {
             if (LN && y_out) yo[c] = v[i];
@@ -659,6 +662,154 @@ __global__ __launch_bounds__((NT <= 5 ? 4 : 8) * 64) void attention_long(const b
     }
 }
 
+// Head dims other than 64 (OpenCLIP ViT-H/14: 80, ViT-g/14: 88, ViT-bigG/14: 104), non-causal, S <= ATT_LONG_MAX_S.
+// The shape of the work is attention_long's -- a workgroup per (image, head), K and V of the head staged in LDS once, the
+// waves loop over the query tiles, a whole row of scores in registers, no running maximum -- but widened to 112 padded
+// columns that layout is 193 KB.  What goes is the P tile: the k index of an MFMA is only a summation label
+// (skinny_attn_out), so k-slot 4 c + r of lane group fq in key PAIR p is key 32 p + 16 c + 4 fq + r, which is where the
+// lane's softmaxed scores already are; the V^T operand is read to match (the two transposed reads of a fragment take keys
+// 32 p + 4 fq .. and 32 p + 16 + 4 fq ..).  P is rounded to bf16 in registers and never touches LDS; behind the staging
+// barrier the waves do not meet again.
+//   HD = 8 * C8, and C8 (10, 11, 13) is no multiple of 4: the reduction of Q K^T runs over ceil(HD / 32) k-steps of 32
+//   whose 8-column fragment chunks past C8 are zero IN REGISTERS for both operands (a chunk is wholly a head's own or
+//   wholly padding, so nothing is read past the head's columns, neither in qkv nor in an LDS row).
+//   K rows in LDS: C8 chunks rounded up to an odd count KC (176 / 176 / 208 B), so the 16 rows a quarter wave reads with
+//   ds_read_b128 start on 16 different bank quads; the pad chunk is written zero.
+//   V rows in LDS: ND = ceil(HD / 16) output tiles, rounded up to VC = 2 * odd chunks (160 / 224 / 224 B), so the eight
+//   32-byte pieces a half wave's transposed read takes lie on disjoint banks; columns HD .. are written zero, so the half
+//   tile of 88 and 104 multiplies zeros, and its store is masked: a lane writes its four columns only if they are below HD.
+// LDS, NT = 17 (S <= 272, eight waves): 16 NT KC + 32 ceil(NT / 2) VC chunks of 16 B -- HD 80: 93 952 B, 88: 112 384 B,
+// 104: 121 088 B, one workgroup a CU as attention_long<17>; NT = 5 (S <= 80, four waves): 29 440 / 35 584 / 38 144 B.
+template <int HD, int NT>
+__global__ __launch_bounds__((NT <= 5 ? 4 : 8) * 64) void attention_hd(const bf16 *__restrict__ qkv, bf16 *__restrict__ out,
+                                                                       int S, int D, int H, float scale) {
+    static_assert(HD % 8 == 0 && HD > 64 && HD <= 128, "head dims of whole 16-byte chunks");
+    constexpr int C8 = HD / 8;                        // 16-byte chunks of a head's row
+    constexpr int KC = (C8 & 1) ? C8 : C8 + 1;        // chunks of a K row in LDS
+    constexpr int KS = (HD + 31) / 32;                // k-steps of Q K^T
+    constexpr int ND = (HD + 15) / 16;                // output tiles
+    constexpr int VC = (ND & 1) ? 2 * ND : 2 * ND + 2;  // chunks of a V row in LDS
+    constexpr int NW = NT <= 5 ? 4 : 8;               // waves per workgroup
+    constexpr int NP = (NT + 1) / 2;                  // key pairs: the k-steps of V^T P^T
+    constexpr int KR = NT * 16, VR = NP * 32;         // K / V rows held
+    __shared__ __attribute__((aligned(16))) bf16 sK[KR * KC * 8];
+    __shared__ __attribute__((aligned(16))) bf16 sV[VR * VC * 8];
+    const int t = threadIdx.x, lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int b = blockIdx.x / H, h = blockIdx.x % H;
+    const int fr = lane & 15, fq = lane >> 4;
+    const bf16 *base = qkv + (int64_t)b * S * 3 * D + h * HD;
+    bf16x8 zero8;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) zero8[j] = (bf16)0.f;
+
+    // K and V rows of this head, whole workgroup: keys >= S and the pad chunks are zero
+#pragma unroll 4
+    for (int ch = t; ch < KR * KC; ch += NW * 64) {
+        const int key = ch / KC, c = ch % KC;
+        bf16x8 kr = zero8;
+        if (key < S && c < C8) kr = *reinterpret_cast<const bf16x8 *>(base + (int64_t)key * 3 * D + D + c * 8);
+        *reinterpret_cast<bf16x8 *>(&sK[ch * 8]) = kr;
+    }
+#pragma unroll 4
+    for (int ch = t; ch < VR * VC; ch += NW * 64) {
+        const int key = ch / VC, c = ch % VC;
+        bf16x8 vr = zero8;
+        if (key < S && c < C8) vr = *reinterpret_cast<const bf16x8 *>(base + (int64_t)key * 3 * D + 2 * D + c * 8);
+        *reinterpret_cast<bf16x8 *>(&sV[ch * 8]) = vr;
+    }
+    __syncthreads();
+    // a wave whose first tile is past S leaves here as a whole wave (the transposed reads need all 64 lanes)
+    for (int i = wave; i * 16 < S; i += NW) {  // query tile, wave-uniform
+        const int qrow = min(i * 16 + fr, S - 1);
+        bf16x8 qf[KS];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const int c8 = ks * 4 + fq;
+            qf[ks] = zero8;
+            if (c8 < C8) qf[ks] = *reinterpret_cast<const bf16x8 *>(base + (int64_t)qrow * 3 * D + c8 * 8);
+        }
+        f32x4 sc[NT];
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            sc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const int c8 = ks * 4 + fq;
+                bf16x8 kf = zero8;
+                if (c8 < C8) kf = *reinterpret_cast<const bf16x8 *>(&sK[((j * 16 + fr) * KC + c8) * 8]);
+                sc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[ks], sc[j], 0, 0, 0);
+            }
+            // the scheduler may run K fragments four tiles ahead of their MFMAs, not all NT: fully hoisted, the NT = 17
+            // instances spilled
+            if (NT > 5 && (j & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+        }
+        // this lane holds scores[query = 16 i + fr][key = 16 j + 4 fq + r]
+        float mx = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float v = sc[j][r] * scale;
+                if (j * 16 + fq * 4 + r >= S) v = -INFINITY;
+                sc[j][r] = v;
+                mx = fmaxf(mx, v);
+            }
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        float sum = 0.f;
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float e = __expf(sc[j][r] - mx);  // key 0 is never masked, so mx is finite
+                sc[j][r] = e;
+                sum += e;
+            }
+        sum += __shfl_xor(sum, 16, 64);
+        sum += __shfl_xor(sum, 32, 64);
+        const float inv = 1.f / sum;
+        // out^T tile = V^T P^T : o[dt][r] = out[query fr][d = 16 dt + 4 fq + r]
+        f32x4 o[ND];
+#pragma unroll
+        for (int dt = 0; dt < ND; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            // P^T operand from the scores where they are: k-slot 4 c + r = key 32 p + 16 c + 4 fq + r (normalised, then bf16)
+            bf16x8 pb;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int j = 2 * p + (e >> 2);
+                pb[e] = j < NT ? to_bf16(sc[j < NT ? j : 0][e & 3] * inv) : to_bf16(0.f);
+            }
+            // V^T fragment to match: in a 16-lane group lane 4 q + x supplies key row 32 p + 4 fq + q (+ 16), dims 4 x ..
+            const int kq = p * 32 + 4 * fq + (fr >> 2), dp = (fr & 3) * 4;
+#pragma unroll
+            for (int dt = 0; dt < ND; ++dt) {
+                typedef __attribute__((ext_vector_type(4))) short s16x4;
+                typedef __attribute__((address_space(3))) s16x4 *lds_s16x4;
+                typedef __attribute__((ext_vector_type(8))) short s16x8;
+                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(&sV[kq * VC * 8 + dt * 16 + dp]));
+                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(&sV[(kq + 16) * VC * 8 + dt * 16 + dp]));
+                const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, both), pb, o[dt], 0, 0, 0);
+            }
+            if (NT > 5 && (p & 1) == 1) __builtin_amdgcn_sched_barrier(0);  // (V fragments at most two key pairs ahead)
+        }
+        const int q = i * 16 + fr;
+        if (q < S) {
+            bf16 *orow = out + ((int64_t)b * S + q) * D + h * HD + fq * 4;
+#pragma unroll
+            for (int dt = 0; dt < ND; ++dt) {
+                bf16x4 ov;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) ov[r] = to_bf16(o[dt][r]);
+                if (dt * 16 + fq * 4 < HD) *reinterpret_cast<bf16x4 *>(orow + dt * 16) = ov;  // (HD % 4 == 0: four columns in or out)
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------
 // skinny linear: out[R <= 32, N] = epilogue(LN?(X)[R, K] W[N, K]^T) for the handful of rows a single text query has.
 // The tile kernels above give such a product to N/128 workgroups that each walk all of K (a [8 x 2048] x [2048 x 512]
@@ -669,7 +820,7 @@ __global__ __launch_bounds__((NT <= 5 ? 4 : 8) * 64) void attention_long(const b
 // arithmetic, eight lanes a row) is redone by every workgroup from the f32 residual stream -- R x D floats out of L2,
 // under the latency of the W loads -- instead of being a launch of its own.  Epilogues are gemm_bf16.hip's.
 // ---------------------------------------------------------------------------------------
-enum { SK_F32 = 0, SK_BF16_BIAS = 1, SK_BF16_BIAS_GELU = 2, SK_F32_BIAS_RESIDUAL = 3 };
+enum { SK_F32 = 0, SK_BF16_BIAS = 1, SK_BF16_BIAS_GELU = 2, SK_F32_BIAS_RESIDUAL = 3, SK_BF16_BIAS_ERF = 4 };  // 4: exact GELU
 constexpr int SK_MAX_ROWS = 32;
 
 template <int CTRL>
@@ -812,8 +963,12 @@ __global__ __launch_bounds__(64 * NW) void skinny_linear(const void *__restrict_
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = v[e] / (1.f + __expf(-1.702f * v[e]));  // quick_gelu
     }
+    if (EPI == SK_BF16_BIAS_ERF) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = erf_gelu_f32(v[e]);
+    }
     v += res_v;
-    if (EPI == SK_BF16_BIAS || EPI == SK_BF16_BIAS_GELU) {
+    if (EPI == SK_BF16_BIAS || EPI == SK_BF16_BIAS_GELU || EPI == SK_BF16_BIAS_ERF) {
         bf16x4 ov;
 #pragma unroll
         for (int e = 0; e < 4; ++e) ov[e] = to_bf16(v[e]);
@@ -1114,10 +1269,11 @@ __global__ void text_embed(const int *__restrict__ ids, const float *__restrict_
 
 // out[b, :] = x[b, :] @ Wp^T  (Wp [P, D] bf16), optional L2 normalisation; one workgroup per row,
 // one wave per output column (16-byte bf16 loads, wave reduction)
+template <int CAP>  // D, P <= CAP
 __global__ __launch_bounds__(256) void project_rows(const float *__restrict__ x, const bf16 *__restrict__ Wp, int D,
                                                     int P, int normalize, float *__restrict__ out) {
-    __shared__ float sx[1024];
-    __shared__ float so[1024];
+    __shared__ float sx[CAP];
+    __shared__ float so[CAP];
     __shared__ float red[4];
     const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
     for (int c = t; c < D; c += 256) sx[c] = x[(int64_t)b * D + c];
@@ -1379,7 +1535,7 @@ struct Header {
     int32_t t_hidden, t_layers, t_heads, t_mlp, t_maxpos, vocab, eos;
     int32_t proj;
     float ln_eps;
-    int32_t reserved;
+    int32_t activation;  // fc1's: 0 = quick-GELU x sigmoid(1.702 x), 1 = GELU 0.5 x (1 + erf(x / sqrt 2))
 };
 
 }  // namespace
@@ -1525,7 +1681,10 @@ ssw_status load_tower(ssw_clip *c, Tower &tw, const float *&cur, const float *en
         const float *wc = w.data(), *bc = b.data();
         SSW_TRY(upload_bf16(c, wc, wc + w.size(), w.size(), &ly.wqkv, scratch));
         SSW_TRY(upload_f32(c, bc, bc + b.size(), b.size(), &ly.bqkv));
-        SSW_TRY(fold_layernorm(c, w.data(), ln1w_h, ln1b_h, b.data(), 3 * D, D, &ly.wqkv_ln, &ly.c1qkv, &ly.c2qkv, scratch));
+        // (a width run_tower never folds -- ln_folds -- needs no folded copies: 2 GB of them on bigG/14's image tower)
+        const bool folds = D % 256 == 0 && D <= 2048;
+        if (folds)
+            SSW_TRY(fold_layernorm(c, w.data(), ln1w_h, ln1b_h, b.data(), 3 * D, D, &ly.wqkv_ln, &ly.c1qkv, &ly.c2qkv, scratch));
         SSW_TRY(upload_bf16(c, cur, end, D * D, &ly.wo, scratch));
         if (attn_outproj_supports(1, (int)D, tw.H)) {
             SSW_TRY(dmalloc(c, (void **)&ly.wo_pk, D * D * sizeof(bf16)));
@@ -1540,7 +1699,7 @@ ssw_status load_tower(ssw_clip *c, Tower &tw, const float *&cur, const float *en
             set_error("clip: weight blob truncated");
             return SSW_ERR_INVALID;
         }
-        SSW_TRY(fold_layernorm(c, cur, ln2w_h, ln2b_h, cur + M * D, M, D, &ly.w1_ln, &ly.c1fc1, &ly.c2fc1, scratch));
+        if (folds) SSW_TRY(fold_layernorm(c, cur, ln2w_h, ln2b_h, cur + M * D, M, D, &ly.w1_ln, &ly.c1fc1, &ly.c2fc1, scratch));
         SSW_TRY(upload_bf16(c, cur, end, M * D, &ly.w1, scratch));
         SSW_TRY(upload_f32(c, cur, end, M, &ly.b1));
         SSW_TRY(upload_bf16(c, cur, end, D * M, &ly.w2, scratch));
@@ -1630,9 +1789,11 @@ bool unfused_ln_forced() {
     static const bool v = getenv("SSW_CLIP_UNFUSED_LN") != nullptr;  // A/B: the round-2 seven-launch layer
     return v;
 }
+// does a tower of this width run its LayerNorms folded into the QKV / fc1 products (five launches a layer)?
+bool ln_folds(int D) { return !unfused_ln_forced() && D % 256 == 0 && D <= 2048; }
 // does this tower's tile path keep its residual rows in bf16?
 bool bf16_rows(const ssw_clip *c, const Tower &tw, int causal) {
-    return !unfused_ln_forced() && tw.D % 256 == 0 && (causal ? (c->flags & 2) != 0 : (c->flags & 1) != 0);
+    return ln_folds(tw.D) && (causal ? (c->flags & 2) != 0 : (c->flags & 1) != 0);
 }
 
 #ifdef SSW_DEBUG_HOOKS
@@ -1668,6 +1829,46 @@ void launch_attention_long(hipStream_t s, const bf16 *qkv, bf16 *att, int n_head
     else hipLaunchKernelGGL(attention_long<17>, dim3(n_heads), dim3(512), 0, s, qkv, att, S, D, H, scale, causal);
 }
 
+// the one-wave-a-row kernels: four float4 a lane up to 1024 columns (every tower before ViT-H/14), seven up to CLIP_MAX_DIM
+constexpr int CLIP_MAX_DIM = 1664, CLIP_MAX_PROJ = 1280, ROW_NV_WIDE = 7;
+static_assert(ROW_NV_WIDE * 256 >= CLIP_MAX_DIM, "a wide row fits a wave's registers");
+template <typename OutT>
+void launch_layernorm_rows(hipStream_t s, const float *x, const int *row_index, int n_rows, int D, const float *w,
+                           const float *b, float eps, OutT *out) {
+    if (D <= 1024)
+        hipLaunchKernelGGL(layernorm_rows<OutT>, dim3((n_rows + 3) / 4), dim3(256), 0, s, x, row_index, n_rows, D, w, b, eps, out);
+    else
+        hipLaunchKernelGGL((layernorm_rows<OutT, ROW_NV_WIDE>), dim3((n_rows + 3) / 4), dim3(256), 0, s, x, row_index, n_rows,
+                           D, w, b, eps, out);
+}
+template <bool LN>
+void launch_stack_input_rows(hipStream_t s, const float *x, int n_rows, int D, const float *w, const float *b, float eps,
+                             float *y_out, bf16 *y_bf16, float *stats, const float *cls = nullptr,
+                             const float *pos = nullptr, int T = 1) {
+    const int np = D / 128 > 0 ? D / 128 : 1;
+    if (D <= 1024)
+        hipLaunchKernelGGL(stack_input_rows<LN>, dim3((n_rows + 3) / 4), dim3(256), 0, s, x, n_rows, D, w, b, eps, y_out,
+                           y_bf16, stats, np, cls, pos, T);
+    else
+        hipLaunchKernelGGL((stack_input_rows<LN, ROW_NV_WIDE>), dim3((n_rows + 3) / 4), dim3(256), 0, s, x, n_rows, D, w, b,
+                           eps, y_out, y_bf16, stats, np, cls, pos, T);
+}
+
+// head dims 80 / 88 / 104 (non-causal, S <= ATT_LONG_MAX_S): attention_hd's smallest instance that holds S
+inline bool attention_hd_serves(int head_dim) { return head_dim == 80 || head_dim == 88 || head_dim == 104; }
+template <int HD>
+void launch_attention_hd_of(hipStream_t s, const bf16 *qkv, bf16 *att, int n_heads, int S, int D, int H, float scale) {
+    if (S <= ATT_MAX_S) hipLaunchKernelGGL((attention_hd<HD, 5>), dim3(n_heads), dim3(256), 0, s, qkv, att, S, D, H, scale);
+    else hipLaunchKernelGGL((attention_hd<HD, 17>), dim3(n_heads), dim3(512), 0, s, qkv, att, S, D, H, scale);
+}
+void launch_attention_hd(hipStream_t s, const bf16 *qkv, bf16 *att, int n_heads, int S, int D, int H, float scale) {
+    switch (D / H) {
+    case 80: launch_attention_hd_of<80>(s, qkv, att, n_heads, S, D, H, scale); break;
+    case 88: launch_attention_hd_of<88>(s, qkv, att, n_heads, S, D, H, scale); break;
+    default: launch_attention_hd_of<104>(s, qkv, att, n_heads, S, D, H, scale); break;
+    }
+}
+
 ssw_status run_tower(ssw_clip *c, const Tower &tw, int B, int S, int causal) {
     hipStream_t s = c->stream;
     const int R = B * S, D = tw.D, M = tw.M;
@@ -1691,7 +1892,10 @@ ssw_status run_tower(ssw_clip *c, const Tower &tw, int B, int S, int causal) {
             hipLaunchKernelGGL(skinny_attn_out<2>, dim3(D / 16), dim3(256), 0, s, c->qkv, ly.wo, ly.bo, h, h2, R, S,
                                att_scale, causal);
         }
-        launch_skinny<SK_BF16_BIAS_GELU, true>(s, h2, nullptr, ly.ln2w, ly.ln2b, eps, ly.w1, ly.b1, nullptr, c->h1, R, M, D);
+        if (c->hdr.activation == 1)
+            launch_skinny<SK_BF16_BIAS_ERF, true>(s, h2, nullptr, ly.ln2w, ly.ln2b, eps, ly.w1, ly.b1, nullptr, c->h1, R, M, D);
+        else
+            launch_skinny<SK_BF16_BIAS_GELU, true>(s, h2, nullptr, ly.ln2w, ly.ln2b, eps, ly.w1, ly.b1, nullptr, c->h1, R, M, D);
         launch_skinny<SK_F32_BIAS_RESIDUAL, false>(s, c->h1, nullptr, nullptr, nullptr, eps, ly.w2, ly.b2, h2, h, R, D, M);
         SSW_TAP(l, h, nullptr);
     }
@@ -1699,7 +1903,13 @@ ssw_status run_tower(ssw_clip *c, const Tower &tw, int B, int S, int causal) {
     // ssw_common.h): the out-projection / fc2 epilogues leave, next to the f32 residual row, its bf16 copy (c->xn) and
     // its partial statistics; QKV / fc1 multiply that copy by gamma (.) W and apply mean / rstd in their epilogue.
     // c->xn and stats_in arrive filled by whoever produced c->hidden (stack_input_rows).
-    const bool unfused_ln = unfused_ln_forced();
+    // LayerNorm as launches of its own (seven a layer): forced, or a width the folded products do not take -- their
+    // statistics are read as float4 = two 128-column partial pairs, at most sixteen pairs a row (gemm_bf16.hip,
+    // ln_row_request), so D % 256 == 0 and D <= 2048.  ViT-H/14 (1280) and bigG/14's text tower (1280) are folded;
+    // bigG/14's image tower (1664 = 13 x 128) and ViT-g/14's (1408 = 11 x 128) run this form, as 384 and 640 do.
+    const bool unfused_ln = !ln_folds(D);
+    const bool erf_gelu = c->hdr.activation == 1;  // fc1's epilogue: 0.5 x (1 + erf(x / sqrt 2)) instead of quick-GELU
+    const int epi_ln_act = erf_gelu ? EPI_BF16_LN_ERF : EPI_BF16_LN_GELU;
     // the residual stream of the tile path in bf16: the producers' bf16 copy IS the stream (read, added to, written back
     // in place by EPI_BF16_STREAM_STATS), the f32 row and its 30 MB + 30 MB a product at B = 200 are gone
     // Measured against transformers' f32 towers (tools/clip_stream_error.py, 26 images): min cosine 0.999994 -> 0.999952,
@@ -1713,7 +1923,7 @@ ssw_status run_tower(ssw_clip *c, const Tower &tw, int B, int S, int causal) {
     // Round 6 experiment (SSW_XCD_AFFINITY=1, A/B only): the QKV product deals CONTIGUOUS runs of row tiles to the XCDs and the
     // fused attention launch puts an image's workgroup on the XCD that produced its qkv rows (what it measured)
     static const bool xcd_affinity_env = getenv("SSW_XCD_AFFINITY") != nullptr;
-    const bool xcd_affinity = xcd_affinity_env && !causal && !unfused_ln && D % 256 == 0 && (c->flags & 8) == 0 &&
+    const bool xcd_affinity = xcd_affinity_env && !causal && !unfused_ln && (c->flags & 8) == 0 &&
                               attn_outproj_supports(S, D, tw.H);
     for (int l = 0; l < tw.L && !skinny; ++l) {
         const Layer &ly = tw.layers[l];
@@ -1722,9 +1932,8 @@ ssw_status run_tower(ssw_clip *c, const Tower &tw, int B, int S, int causal) {
         cons.inv_dim = 1.0f / (float)D;
         cons.eps = eps;
         prod.xcopy = c->xn;
-        if (unfused_ln || D % 256 != 0) {
-            hipLaunchKernelGGL(layernorm_rows<bf16>, dim3((R + 3) / 4), dim3(256), 0, s, h, (const int *)nullptr, R, D,
-                               ly.ln1w, ly.ln1b, eps, c->xn);
+        if (unfused_ln) {
+            launch_layernorm_rows<bf16>(s, h, nullptr, R, D, ly.ln1w, ly.ln1b, eps, c->xn);
             SSW_TRY(gemm<EPI_BF16_BIAS>(s, c->xn, ly.wqkv, ly.bqkv, nullptr, c->qkv, R, 3 * D, D));
         } else {
             cons.stats_in = st_h;
@@ -1737,7 +1946,7 @@ ssw_status run_tower(ssw_clip *c, const Tower &tw, int B, int S, int causal) {
         const float att_scale = 1.0f / sqrtf((float)(D / tw.H));
         // round 4: attention + out-projection + residual + statistics of the image tower in one launch, a workgroup per
         // image (attn_out.hip); the fc1 product then reads two partial pairs a row instead of D / 128
-        const bool fused_attn = !unfused_ln && D % 256 == 0 && !causal && (c->flags & 8) == 0 &&
+        const bool fused_attn = !unfused_ln && !causal && (c->flags & 8) == 0 &&
                                 attn_outproj_supports(S, D, tw.H) && ly.wo_pk != nullptr;
         if (fused_attn) {
             // The last layer on the pooled rows only: the final LayerNorm and the projection read the first row of
@@ -1770,7 +1979,7 @@ ssw_status run_tower(ssw_clip *c, const Tower &tw, int B, int S, int causal) {
                 SSW_TRY(launch_gemm_bf16_ln(EPI_F32_BIAS_RESIDUAL_STATS, s, att_p, ly.wo, ly.bo, h, h2, B, D, D, prod));
                 cons.np_in = np;
                 cons.stats_in = st_h;
-                SSW_TRY(launch_gemm_bf16_ln(EPI_BF16_LN_GELU, s, c->att, ly.w1_ln, ly.c2fc1, nullptr, c->h1, B, M, D, cons));
+                SSW_TRY(launch_gemm_bf16_ln(epi_ln_act, s, c->att, ly.w1_ln, ly.c2fc1, nullptr, c->h1, B, M, D, cons));
                 SSW_TRY(launch_gemm_splitk_f32(s, c->h1, ly.w2, ly.b2, h2, h, partials, B, D, M, 8));
                 c->pooled_compact = true;
                 c->stream_in_xn = false;  // the pooled rows are f32 rows of hidden whatever the stream's precision
@@ -1788,13 +1997,13 @@ ssw_status run_tower(ssw_clip *c, const Tower &tw, int B, int S, int causal) {
                 hipLaunchKernelGGL(gather_pooled_rows, dim3(B), dim3(256), 0, s, bf16_stream ? (const float *)nullptr : h2, c->xn, st_h2,
                                    B, S, D, 2, res_p, c->att, st_h);
                 cons.stats_in = st_h;
-                SSW_TRY(launch_gemm_bf16_ln(EPI_BF16_LN_GELU, s, c->att, ly.w1_ln, ly.c2fc1, nullptr, c->h1, B, M, D, cons));
+                SSW_TRY(launch_gemm_bf16_ln(epi_ln_act, s, c->att, ly.w1_ln, ly.c2fc1, nullptr, c->h1, B, M, D, cons));
                 SSW_TRY(launch_gemm_splitk_f32(s, c->h1, ly.w2, ly.b2, res_p, h, reinterpret_cast<float *>(c->qkv), B, D, M, 8));
                 c->pooled_compact = true;
                 c->stream_in_xn = false;  // the pooled rows are f32 rows of hidden whatever the stream's precision
                 continue;
             }
-            SSW_TRY(launch_gemm_bf16_ln(EPI_BF16_LN_GELU, s, c->xn, ly.w1_ln, ly.c2fc1, nullptr, c->h1, R, M, D, cons));
+            SSW_TRY(launch_gemm_bf16_ln(epi_ln_act, s, c->xn, ly.w1_ln, ly.c2fc1, nullptr, c->h1, R, M, D, cons));
             prod.stats_out = st_h;
             if (bf16_stream)
                 SSW_TRY(launch_gemm_bf16_ln(EPI_BF16_STREAM_STATS, s, c->h1, ly.w2, ly.b2, nullptr, nullptr, R, D, M, prod));
@@ -1807,7 +2016,9 @@ ssw_status run_tower(ssw_clip *c, const Tower &tw, int B, int S, int causal) {
         // (one wave per pair with four tiles, attention_mfma<4, 4>: 21.6 us per layer against 17.1 -- measured, not kept)
         static const bool direct_env = getenv("SSW_CLIP_ATTN_DIRECT") != nullptr;  // A/B: fragments straight from memory
         const bool direct_frags = direct_env || (c->flags & 4) != 0;
-        if (S > ATT_MAX_S || (c->flags & 64) != 0)
+        if (D / tw.H != 64)  // (the image tower only, 80 / 88 / 104: ssw_clip_create's condition)
+            launch_attention_hd(s, c->qkv, c->att, n_heads, S, D, tw.H, att_scale);
+        else if (S > ATT_MAX_S || (c->flags & 64) != 0)
             launch_attention_long(s, c->qkv, c->att, n_heads, S, D, tw.H, att_scale, causal);
         else if (S <= 64 && !one_tile_waves && !direct_frags)
             hipLaunchKernelGGL(attention_rows64, dim3(n_heads), dim3(128), 0, s, c->qkv, c->att, S, D, tw.H, att_scale, causal);
@@ -1820,11 +2031,10 @@ ssw_status run_tower(ssw_clip *c, const Tower &tw, int B, int S, int causal) {
         else
             hipLaunchKernelGGL(attention_mfma<5>, dim3(n_heads), dim3(320), 0, s, c->qkv, c->att, S, D, tw.H, att_scale,
                                causal);
-        if (unfused_ln || D % 256 != 0) {
+        if (unfused_ln) {
             SSW_TRY(gemm<EPI_F32_BIAS_RESIDUAL>(s, c->att, ly.wo, ly.bo, h, h2, R, D, D));
-            hipLaunchKernelGGL(layernorm_rows<bf16>, dim3((R + 3) / 4), dim3(256), 0, s, h2, (const int *)nullptr, R, D,
-                               ly.ln2w, ly.ln2b, eps, c->xn);
-            SSW_TRY(gemm<EPI_BF16_BIAS_GELU>(s, c->xn, ly.w1, ly.b1, nullptr, c->h1, R, M, D));
+            launch_layernorm_rows<bf16>(s, h2, nullptr, R, D, ly.ln2w, ly.ln2b, eps, c->xn);
+            SSW_TRY(launch_gemm_bf16_nt(erf_gelu ? EPI_BF16_BIAS_ERF : EPI_BF16_BIAS_GELU, s, c->xn, ly.w1, ly.b1, nullptr, c->h1, R, M, D));
             SSW_TRY(gemm<EPI_F32_BIAS_RESIDUAL>(s, c->h1, ly.w2, ly.b2, h2, h, R, D, M));
         } else if (bf16_stream) {
             c->stream_in_xn = true;
@@ -1832,7 +2042,7 @@ ssw_status run_tower(ssw_clip *c, const Tower &tw, int B, int S, int causal) {
             SSW_TRY(launch_gemm_bf16_ln(EPI_BF16_STREAM_STATS, s, c->att, ly.wo, ly.bo, nullptr, nullptr, R, D, D, prod));
             cons.stats_in = st_h2;
             cons.c1 = ly.c1fc1;
-            SSW_TRY(launch_gemm_bf16_ln(EPI_BF16_LN_GELU, s, c->xn, ly.w1_ln, ly.c2fc1, nullptr, c->h1, R, M, D, cons));
+            SSW_TRY(launch_gemm_bf16_ln(epi_ln_act, s, c->xn, ly.w1_ln, ly.c2fc1, nullptr, c->h1, R, M, D, cons));
             prod.stats_out = st_h;
             SSW_TRY(launch_gemm_bf16_ln(EPI_BF16_STREAM_STATS, s, c->h1, ly.w2, ly.b2, nullptr, nullptr, R, D, M, prod));
         } else {
@@ -1855,7 +2065,7 @@ ssw_status run_tower(ssw_clip *c, const Tower &tw, int B, int S, int causal) {
             else SSW_TRY(launch_gemm_bf16_ln(EPI_F32_BIAS_RESIDUAL_STATS, s, c->att, ly.wo, ly.bo, h, h2, R, D, D, prod));
             cons.stats_in = st_h2;
             cons.c1 = ly.c1fc1;
-            SSW_TRY(launch_gemm_bf16_ln(EPI_BF16_LN_GELU, s, c->xn, ly.w1_ln, ly.c2fc1, nullptr, c->h1, R, M, D, cons));
+            SSW_TRY(launch_gemm_bf16_ln(epi_ln_act, s, c->xn, ly.w1_ln, ly.c2fc1, nullptr, c->h1, R, M, D, cons));
             prod.stats_out = st_h;
             if (sp_2 > 1) SSW_TRY(launch_gemm_splitk_stats(s, c->h1, ly.w2, ly.b2, h2, h, c->splitk, R, D, M, sp_2, prod));
             else SSW_TRY(launch_gemm_bf16_ln(EPI_F32_BIAS_RESIDUAL_STATS, s, c->h1, ly.w2, ly.b2, h2, h, R, D, M, prod));
@@ -1877,14 +2087,15 @@ ssw_status pool_and_project(ssw_clip *c, const Tower &tw, int B, int D, int norm
                                     out_dev, B, h.proj, D);
         if (normalize) hipLaunchKernelGGL(l2norm_rows, dim3((B + 3) / 4), dim3(256), 0, s, out_dev, B, h.proj);
     } else if (h.proj % 128 == 0 && D % 64 == 0) {
-        hipLaunchKernelGGL(layernorm_rows<bf16>, dim3((B + 3) / 4), dim3(256), 0, s, c->hidden, c->rows, B, D,
-                           tw.lnf_w, tw.lnf_b, h.ln_eps, c->xn);
+        launch_layernorm_rows<bf16>(s, c->hidden, c->rows, B, D, tw.lnf_w, tw.lnf_b, h.ln_eps, c->xn);
         SSW_TRY(gemm<EPI_F32>(s, c->xn, tw.proj, nullptr, nullptr, out_dev, B, h.proj, D));
         if (normalize) hipLaunchKernelGGL(l2norm_rows, dim3((B + 3) / 4), dim3(256), 0, s, out_dev, B, h.proj);
     } else {
-        hipLaunchKernelGGL(layernorm_rows<float>, dim3((B + 3) / 4), dim3(256), 0, s, c->hidden, c->rows, B, D,
-                           tw.lnf_w, tw.lnf_b, h.ln_eps, c->pooled);
-        hipLaunchKernelGGL(project_rows, dim3(B), dim3(256), 0, s, c->pooled, tw.proj, D, h.proj, normalize, out_dev);
+        launch_layernorm_rows<float>(s, c->hidden, c->rows, B, D, tw.lnf_w, tw.lnf_b, h.ln_eps, c->pooled);
+        if (D <= 1024 && h.proj <= 1024)
+            hipLaunchKernelGGL(project_rows<1024>, dim3(B), dim3(256), 0, s, c->pooled, tw.proj, D, h.proj, normalize, out_dev);
+        else
+            hipLaunchKernelGGL(project_rows<CLIP_MAX_DIM>, dim3(B), dim3(256), 0, s, c->pooled, tw.proj, D, h.proj, normalize, out_dev);
     }
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
@@ -1912,9 +2123,8 @@ ssw_status image_forward_from_patches(ssw_clip *c, int B, int normalize, float *
     // cls / patch rows + position embedding, then the pre-LayerNorm = the stack's input row, in one pass: bf16 copy and
     // statistics for layer 0's QKV, and the f32 row into c->hidden unless the stack keeps its rows in bf16
     // (round 3: putting the rows together was a launch and a 30-MB round trip of its own at B = 200)
-    hipLaunchKernelGGL(stack_input_rows<true>, dim3((B * T + 3) / 4), dim3(256), 0, s, c->patch_out, B * T, D, c->pre_w,
-                       c->pre_b, h.ln_eps, bf16_rows(c, c->vis, 0) ? (float *)nullptr : c->hidden, c->xn, c->stats_a,
-                       D / 128 > 0 ? D / 128 : 1, c->cls, c->vpos, T);
+    launch_stack_input_rows<true>(s, c->patch_out, B * T, D, c->pre_w, c->pre_b, h.ln_eps,
+                                  bf16_rows(c, c->vis, 0) ? (float *)nullptr : c->hidden, c->xn, c->stats_a, c->cls, c->vpos, T);
     SSW_TRY(run_tower(c, c->vis, B, T, 0));
     {   // the pooled rows' list depends on (B, stride) only: a launch (~5 us of a small forward) the first time, none after
         const int stride = c->pooled_compact ? 1 : T;
@@ -1962,9 +2172,7 @@ ssw_status text_forward(ssw_clip *c, const int *ids_dev, int B, int L, int norma
     const int D = h.t_hidden;
     hipLaunchKernelGGL(text_embed, dim3(1024), dim3(256), 0, s, ids_dev, c->tok, c->tpos, c->hidden, B, L, D);
     if (!(skinny_rows(B * L, D, c->txt.M) && c->txt.H * 64 == D))  // the tile path wants the row's bf16 copy + statistics
-        hipLaunchKernelGGL(stack_input_rows<false>, dim3((B * L + 3) / 4), dim3(256), 0, s, c->hidden, B * L, D,
-                           (const float *)nullptr, (const float *)nullptr, h.ln_eps, c->hidden, c->xn, c->stats_a,
-                           D / 128 > 0 ? D / 128 : 1);
+        launch_stack_input_rows<false>(s, c->hidden, B * L, D, nullptr, nullptr, h.ln_eps, c->hidden, c->xn, c->stats_a);
     SSW_TRY(run_tower(c, c->txt, B, L, 1));
     hipLaunchKernelGGL(eos_rows, dim3((B + 255) / 256), dim3(256), 0, s, ids_dev, B, L, h.eos, c->rows);
     c->rows_key = -1;
@@ -2070,12 +2278,18 @@ struct DebugBufs {
 ssw_status ssw_debug_attention_run(int32_t form, int32_t B, int32_t S, int32_t D, int32_t H, int32_t causal, float scale,
                                    const uint16_t *qkv_bf16, int64_t qkv_rows_alloc, uint16_t *out_bf16_inout,
                                    int64_t out_rows_alloc) {
-    SSW_REQUIRE(form >= 0 && form <= 5, "ssw_debug_attention_run: form %d unknown (0 .. 5)", form);
+    SSW_REQUIRE(form >= 0 && form <= 6, "ssw_debug_attention_run: form %d unknown (0 .. 6)", form);
     SSW_REQUIRE(qkv_bf16 && out_bf16_inout && B >= 1 && B <= 4096 && H >= 1 && D >= 1, "ssw_debug_attention_run: bad arguments");
-    static const int max_s[6] = {64, 64, ATT_MAX_S, 64, ATT_LONG_MAX_S, 64};
+    static const int max_s[7] = {64, 64, ATT_MAX_S, 64, ATT_LONG_MAX_S, 64, ATT_LONG_MAX_S};
     SSW_UNSUPPORTED_IF(S < 1, "ssw_debug_attention_run: S=%d < 1", S);
     SSW_UNSUPPORTED_IF(S > max_s[form], "ssw_debug_attention_run: form %d holds S <= %d, got %d", form, max_s[form], S);
-    SSW_UNSUPPORTED_IF(D != 64 * H || H > 64, "ssw_debug_attention_run: D=%d is not 64 x H=%d (head_dim 64)", D, H);
+    if (form == 6) {
+        SSW_UNSUPPORTED_IF(H > 64 || D % H != 0 || !attention_hd_serves(D / H),
+                           "ssw_debug_attention_run: form 6 wants D = 80, 88 or 104 x H, got D=%d H=%d", D, H);
+        SSW_UNSUPPORTED_IF(causal, "ssw_debug_attention_run: attention_hd has no causal form");
+    } else {
+        SSW_UNSUPPORTED_IF(D != 64 * H || H > 64, "ssw_debug_attention_run: D=%d is not 64 x H=%d (head_dim 64)", D, H);
+    }
     SSW_UNSUPPORTED_IF(causal && form == 5, "ssw_debug_attention_run: attn_pooled_rows has no causal form");
     const int64_t R = (int64_t)B * S, out_rows = form == 5 ? B : R;
     SSW_REQUIRE(qkv_rows_alloc >= R && out_rows_alloc >= out_rows && qkv_rows_alloc <= (1 << 20) && out_rows_alloc <= (1 << 20),
@@ -2096,6 +2310,7 @@ ssw_status ssw_debug_attention_run(int32_t form, int32_t B, int32_t S, int32_t D
     case 2: hipLaunchKernelGGL(attention_mfma<5>, dim3(n_heads), dim3(320), 0, s, qkv, out, S, D, H, scale, cz); break;
     case 3: hipLaunchKernelGGL(attention_rows64, dim3(n_heads), dim3(128), 0, s, qkv, out, S, D, H, scale, cz); break;
     case 4: launch_attention_long(s, qkv, out, n_heads, S, D, H, scale, cz); break;
+    case 6: launch_attention_hd(s, qkv, out, n_heads, S, D, H, scale); break;
     default: hipLaunchKernelGGL(attn_pooled_rows, dim3(n_heads), dim3(64), 0, s, qkv, out, S, D, H, scale); break;
     }
     SSW_HIP_TRY(hipGetLastError());
@@ -2172,11 +2387,16 @@ ssw_status ssw_clip_create(int32_t device, const void *weight_blob, size_t bytes
     SSW_REQUIRE(memcmp(h.magic, "SSWCLIP1", 8) == 0, "clip: bad blob magic");
     const int g = h.patch > 0 ? h.image / h.patch : 0;
     const int Tv = g * g + 1;
-    if (h.v_hidden % 128 || h.t_hidden % 128 || h.v_mlp % 128 || h.t_mlp % 128 || h.proj % 4 ||
-        h.patch <= 0 || h.image <= 0 || h.image % h.patch || h.v_hidden / h.v_heads != 64 || h.t_hidden / h.t_heads != 64 ||
-        Tv > ATT_LONG_MAX_S || h.t_maxpos > ATT_MAX_S || h.v_hidden > 1024 || h.t_hidden > 1024 || h.proj > 1024) {
-        set_error("clip: configuration outside what the kernels support (head_dim 64, dims %% 128 and <= 1024, image tower <= %d "
-                  "tokens with a patch size that divides the image, text tower <= %d positions)", ATT_LONG_MAX_S, ATT_MAX_S);
+    SSW_REQUIRE(h.activation == 0 || h.activation == 1, "clip: activation code %d unknown (0 quick-GELU, 1 GELU)", h.activation);
+    const bool heads_ok = h.v_heads > 0 && h.t_heads > 0 && h.v_hidden % h.v_heads == 0 && h.t_hidden == 64 * h.t_heads &&
+                          (h.v_hidden == 64 * h.v_heads || attention_hd_serves(h.v_hidden / h.v_heads));
+    if (h.v_hidden % 128 || h.t_hidden % 128 || h.v_mlp % 128 || h.t_mlp % 128 || h.proj % 4 || h.v_hidden <= 0 || h.t_hidden <= 0 ||
+        h.v_mlp <= 0 || h.t_mlp <= 0 || h.proj <= 0 || h.patch <= 0 || h.image <= 0 || h.image % h.patch || !heads_ok ||
+        Tv > ATT_LONG_MAX_S || h.t_maxpos > ATT_MAX_S || h.v_hidden > CLIP_MAX_DIM || h.t_hidden > CLIP_MAX_DIM ||
+        h.proj > CLIP_MAX_PROJ) {
+        set_error("clip: configuration outside what the kernels support (head_dim 64, or 80 / 88 / 104 in the image tower; dims %% 128 "
+                  "and <= %d, projection <= %d; image tower <= %d tokens with a patch size that divides the image, text tower "
+                  "<= %d positions)", CLIP_MAX_DIM, CLIP_MAX_PROJ, ATT_LONG_MAX_S, ATT_MAX_S);
         return SSW_ERR_UNSUPPORTED;
     }
     DeviceGuard guard(device);
@@ -2201,6 +2421,9 @@ ssw_status ssw_clip_create(int32_t device, const void *weight_blob, size_t bytes
     big = std::max(big, (size_t)3 * h.v_hidden * h.v_hidden);
     big = std::max(big, (size_t)h.v_mlp * h.v_hidden);
     big = std::max(big, (size_t)h.v_hidden * patch_cols(h.patch));
+    big = std::max(big, (size_t)3 * h.t_hidden * h.t_hidden);
+    big = std::max(big, (size_t)h.t_mlp * h.t_hidden);
+    big = std::max(big, (size_t)h.proj * std::max(h.v_hidden, h.t_hidden));
     float *scratch = nullptr;
     if (hipMalloc((void **)&scratch, big * sizeof(float)) != hipSuccess) {
         set_error("clip: scratch allocation failed");

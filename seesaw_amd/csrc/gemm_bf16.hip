@@ -76,10 +76,18 @@ __device__ __forceinline__ void epi_store(V *p, V v) {
 // bf16 copy of the new residual row and its partial LayerNorm statistics for the next product; 7: the same with the
 // residual stream itself held in bf16 (read from and written back to GemmLn::xcopy, no f32 row)
 enum Epilogue { EPI_F32 = 0, EPI_BF16_BIAS = 1, EPI_BF16_BIAS_GELU = 2, EPI_F32_BIAS_RESIDUAL = 3, EPI_BF16_LN = 4,
-                EPI_BF16_LN_GELU = 5, EPI_F32_BIAS_RESIDUAL_STATS = 6, EPI_BF16_STREAM_STATS = 7 };
-constexpr bool epi_ln(int e) { return e == EPI_BF16_LN || e == EPI_BF16_LN_GELU; }
-constexpr bool epi_bf16_out(int e) { return e == EPI_BF16_BIAS || e == EPI_BF16_BIAS_GELU || epi_ln(e); }
-constexpr bool epi_gelu(int e) { return e == EPI_BF16_BIAS_GELU || e == EPI_BF16_LN_GELU; }
+                EPI_BF16_LN_GELU = 5, EPI_F32_BIAS_RESIDUAL_STATS = 6, EPI_BF16_STREAM_STATS = 7,
+                EPI_BF16_BIAS_ERF = 8, EPI_BF16_LN_ERF = 9,  // 8 / 9: 2 / 5 with the exact GELU 0.5 x (1 + erf(x / sqrt 2))
+                // 4 / 5 / 9 for rows of 9 .. 16 partial-statistics pairs (chosen by launch_gemm_bf16_ln from np_in, never by a caller)
+                EPI_BF16_LN_W = 10, EPI_BF16_LN_GELU_W = 11, EPI_BF16_LN_ERF_W = 12 };
+constexpr bool epi_ln_wide(int e) { return e == EPI_BF16_LN_W || e == EPI_BF16_LN_GELU_W || e == EPI_BF16_LN_ERF_W; }
+constexpr int epi_ln_quads(int e) { return epi_ln_wide(e) ? 8 : 4; }
+constexpr bool epi_ln(int e) { return e == EPI_BF16_LN || e == EPI_BF16_LN_GELU || e == EPI_BF16_LN_ERF || epi_ln_wide(e); }
+constexpr bool epi_bf16_out(int e) { return e == EPI_BF16_BIAS || e == EPI_BF16_BIAS_GELU || e == EPI_BF16_BIAS_ERF || epi_ln(e); }
+constexpr bool epi_gelu(int e) { return e == EPI_BF16_BIAS_GELU || e == EPI_BF16_LN_GELU || e == EPI_BF16_LN_GELU_W; }
+constexpr bool epi_erf(int e) { return e == EPI_BF16_BIAS_ERF || e == EPI_BF16_LN_ERF || e == EPI_BF16_LN_ERF_W; }
+// torch's nn.GELU() (OpenCLIP ViT-H/14, bigG/14): erff is ocml's, a few ulp -- far below the bf16 rounding behind it
+__device__ __forceinline__ float erf_gelu_f32(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678f)); }
 constexpr bool epi_residual(int e) { return e == EPI_F32_BIAS_RESIDUAL || e == EPI_F32_BIAS_RESIDUAL_STATS; }
 constexpr bool epi_stats(int e) { return e == EPI_F32_BIAS_RESIDUAL_STATS || e == EPI_BF16_STREAM_STATS; }
 
@@ -108,6 +116,10 @@ __device__ __forceinline__ void epilogue_store(f32x4 v, int64_t o, int col, cons
 #pragma unroll
         for (int r = 0; r < 4; ++r)  // quick_gelu: x * sigmoid(1.702 x), v_exp + v_rcp
             v[r] *= __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.702f * 1.44269504f * v[r]));
+    }
+    if constexpr (epi_erf(EPI)) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = erf_gelu_f32(v[r]);
     }
     if constexpr (epi_residual(EPI)) v += *reinterpret_cast<const f32x4 *>(residual + o);
     if constexpr (EPI == EPI_BF16_STREAM_STATS) {  // the stream's own element: read here, replaced below by this thread
@@ -154,31 +166,41 @@ __device__ __forceinline__ f32x4 epilogue_value(f32x4 v, float mean, float rstd,
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] *= __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.702f * 1.44269504f * v[r]));
     }
+    if constexpr (epi_erf(EPI)) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = erf_gelu_f32(v[r]);
+    }
     return v;
 }
 
 // LayerNorm statistics of a tile's rows, AHEAD of the K loop (round 4): thread t < rows asks for row m0 + t's np_in
-// partial pairs (np_in even, <= 8: four float4 requests, the last ones repeated when there are fewer), adds them in
+// partial pairs (np_in even, <= 8: four float4 requests, the last ones repeated when there are fewer; <= 16 and eight
+// requests in the wide epilogues), adds them in
 // ascending order -- the order the producing epilogues' partials have always been added in -- and leaves mean / rstd
 // in ln_lds[2 t], [2 t + 1]; the K loop's first barrier publishes them.  The loads go out before the ring's first
 // pieces and are waited for behind them, so the wait is the first stage's own.  (They used to be parked in the idle
 // staging bytes and summed BEHIND the loop: two barriers and an LDS round trip per tile in the exposed epilogue,
 // 1.6 us of QKV's 44.3 and 1.9 of fc1's 62.5 at 10 000 rows.)
+// NQ: float4 requests a row -- 4 (np_in <= 8, rows up to 1024 wide) in every epilogue but the wide ones (epi_ln_quads),
+// which take 8 (np_in <= 16: the 1280-wide rows of ViT-H/14 and of bigG/14's text tower) in instantiations of their own.
+template <int NQ>
 struct LnRowPre {
-    f32x4 v[4];
+    f32x4 v[NQ];
 };
-__device__ __forceinline__ LnRowPre ln_row_request(const GemmLn &ln, int row) {
-    LnRowPre r;
+template <int NQ>
+__device__ __forceinline__ LnRowPre<NQ> ln_row_request(const GemmLn &ln, int row) {
+    LnRowPre<NQ> r;
     const f32x4 *p = reinterpret_cast<const f32x4 *>(ln.stats_in + (int64_t)row * ln.np_in * 2);
     const int last = ln.np_in / 2 - 1;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) r.v[k] = p[min(k, last)];
+    for (int k = 0; k < NQ; ++k) r.v[k] = p[min(k, last)];
     return r;
 }
-__device__ __forceinline__ void ln_row_finish(const GemmLn &ln, const LnRowPre &r, float *dst2) {
+template <int NQ>
+__device__ __forceinline__ void ln_row_finish(const GemmLn &ln, const LnRowPre<NQ> &r, float *dst2) {
     float sm = 0.f, sq = 0.f;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < NQ; ++k) {
         if (2 * k < ln.np_in) {
             sm += r.v[k][0];
             sq += r.v[k][1];
@@ -339,8 +361,9 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt(const bf16 *__restrict__ A, 
                 float v = acc[i][j][r] + bv;
                 const int64_t o = (int64_t)row * N + col;
                 if (EPI == EPI_BF16_BIAS_GELU) v = v / (1.f + __expf(-1.702f * v));  // quick_gelu
+                if (EPI == EPI_BF16_BIAS_ERF) v = erf_gelu_f32(v);
                 if (EPI == EPI_F32_BIAS_RESIDUAL) v += residual[o];
-                if (EPI == EPI_BF16_BIAS || EPI == EPI_BF16_BIAS_GELU)
+                if (EPI == EPI_BF16_BIAS || EPI == EPI_BF16_BIAS_GELU || EPI == EPI_BF16_BIAS_ERF)
                     reinterpret_cast<bf16 *>(Cout)[o] = to_bf16(v);
                 else
                     reinterpret_cast<float *>(Cout)[o] = v;
@@ -468,11 +491,11 @@ __global__ __launch_bounds__(TM * WN) void gemm_glds(const bf16 *__restrict__ A,
     float *const ln_lds = reinterpret_cast<float *>(smem + DEPTH * STAGE);  // [TM][2] statistics / [WN][TM][2] partials
     // LayerNorm-folded variants: thread t < TM requests the partial sums of row m0 + t NOW (ordinary loads, ahead of the
     // ring's first pieces) and turns them into the row's mean / rstd once the first stages are on their way (LnRowPre)
-    LnRowPre ln_pre;
+    LnRowPre<epi_ln_quads(EPI)> ln_pre;
     f32x4 ln_cpre = f32x4{0.f, 0.f, 0.f, 0.f};  // threads 0-31: c1 of 4 of the tile's 128 columns, 32-63: c2
     float *const ln_c = ln_lds + 2 * TM;         // [2][128] behind the statistics
     if constexpr (epi_ln(EPI) && !(SSW_ABL_LN & 1)) {
-        if (t < TM) ln_pre = ln_row_request(ln, min(m0 + t, M - 1));
+        if (t < TM) ln_pre = ln_row_request<epi_ln_quads(EPI)>(ln, min(m0 + t, M - 1));
         ln_cpre = *reinterpret_cast<const f32x4 *>(((t & 32) ? bias : ln.c1) + n0 + (t & 31) * 4);
     }
 
@@ -954,12 +977,12 @@ __global__ __launch_bounds__(512) void gemm_256(const bf16 *__restrict__ A, cons
         for (int i = 0; i < 8; ++i) acc[i][j] = bv;
     }
     float *const ln_lds = reinterpret_cast<float *>(smem + 2 * T256_STAGE);  // [256][2] row statistics
-    LnRowPre ln_pre;  // as in gemm_glds: row m0 + t's partial pairs, requested now, summed once the first tiles are on their way
+    LnRowPre<epi_ln_quads(EPI)> ln_pre;  // as in gemm_glds: row m0 + t's partial pairs, requested now, summed once the first tiles are on their way
     f32x4 ln_cpre = f32x4{0.f, 0.f, 0.f, 0.f};  // threads 0-63: c1 of 4 of the tile's 256 columns, 64-127: c2
     float *const ln_c = ln_lds + 2 * 256;        // [2][256] behind the statistics
     if constexpr (epi_ln(EPI)) {
         ln_cpre = *reinterpret_cast<const f32x4 *>(((t & 64) ? bias : ln.c1) + n0 + (t & 63) * 4);
-        if (t < 256) ln_pre = ln_row_request(ln, min(m0 + t, M - 1));
+        if (t < 256) ln_pre = ln_row_request<epi_ln_quads(EPI)>(ln, min(m0 + t, M - 1));
     }
     const int frag0 = fr * 128 + ((fq ^ (fr >> 1)) << 4);
     const int a_frag = wr * T256_HALF + frag0;                                        // + i * 2048, i = 0..7
@@ -1220,7 +1243,7 @@ ssw_status launch_gemm_bf16_nt(int epi, hipStream_t s, const void *A_, const voi
         return SSW_ERR_UNSUPPORTED;
     }
 #ifdef SSW_DEBUG_HOOKS  // the four-wave experiment (gemm_pw4.hip) is part of the lab build only
-    if (g_gemm_variant >= 20 && g_gemm_variant <= 23 && gemm_pw4_supports(M, N, K)) {
+    if (g_gemm_variant >= 20 && g_gemm_variant <= 23 && epi != EPI_BF16_BIAS_ERF && gemm_pw4_supports(M, N, K)) {  // (no erf epilogue there)
         static const int bn_of[4] = {0, 256, 192, 128};
         int bn = bn_of[g_gemm_variant - 20];
         if (bn != 0 && N % bn != 0) bn = 0;
@@ -1232,6 +1255,7 @@ ssw_status launch_gemm_bf16_nt(int epi, hipStream_t s, const void *A_, const voi
         case EPI_F32: return launch_epi<EPI_F32>(s, A, W, bias, res, C, M, N, K);
         case EPI_BF16_BIAS: return launch_epi<EPI_BF16_BIAS>(s, A, W, bias, res, C, M, N, K);
         case EPI_BF16_BIAS_GELU: return launch_epi<EPI_BF16_BIAS_GELU>(s, A, W, bias, res, C, M, N, K);
+        case EPI_BF16_BIAS_ERF: return launch_epi<EPI_BF16_BIAS_ERF>(s, A, W, bias, res, C, M, N, K);
         case EPI_F32_BIAS_RESIDUAL: return launch_epi<EPI_F32_BIAS_RESIDUAL>(s, A, W, bias, res, C, M, N, K);
     }
     set_error("gemm_bf16_nt: unknown epilogue %d", epi);
@@ -1248,10 +1272,17 @@ ssw_status launch_gemm_bf16_ln(int epi, hipStream_t s, const void *A_, const voi
     switch (epi) {
         case EPI_BF16_LN:
         case EPI_BF16_LN_GELU:
-            if (!ln.stats_in || !ln.c1 || !bias || ln.np_in <= 0 || ln.np_in > 8 || (ln.np_in & 1)) {
-                set_error("gemm_bf16_ln: the LayerNorm-folded product needs statistics (an even number of partial pairs, <= 8), c1 and c2");
+        case EPI_BF16_LN_ERF:
+            if (!ln.stats_in || !ln.c1 || !bias || ln.np_in <= 0 || ln.np_in > 16 || (ln.np_in & 1)) {
+                set_error("gemm_bf16_ln: the LayerNorm-folded product needs statistics (an even number of partial pairs, <= 16), c1 and c2");
                 return SSW_ERR_INVALID;
             }
+            if (ln.np_in > 8) {  // rows wider than 1024: eight float4 requests a row, instantiations of their own
+                if (epi == EPI_BF16_LN) return launch_epi_ln<EPI_BF16_LN_W>(s, A, W, bias, res, C, M, N, K, ln);
+                if (epi == EPI_BF16_LN_GELU) return launch_epi_ln<EPI_BF16_LN_GELU_W>(s, A, W, bias, res, C, M, N, K, ln);
+                return launch_epi_ln<EPI_BF16_LN_ERF_W>(s, A, W, bias, res, C, M, N, K, ln);
+            }
+            if (epi == EPI_BF16_LN_ERF) return launch_epi_ln<EPI_BF16_LN_ERF>(s, A, W, bias, res, C, M, N, K, ln);
             return epi == EPI_BF16_LN ? launch_epi_ln<EPI_BF16_LN>(s, A, W, bias, res, C, M, N, K, ln)
                                       : launch_epi_ln<EPI_BF16_LN_GELU>(s, A, W, bias, res, C, M, N, K, ln);
         case EPI_F32_BIAS_RESIDUAL_STATS:
@@ -1292,7 +1323,9 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(const float *__restrict__
 // the producers' epilogue (EPI_F32_BIAS_RESIDUAL_STATS) behind a split-K product: a row per workgroup, four columns a
 // thread -- partial products added in ascending order, + bias + residual -> the f32 row, its bf16 copy, and the (sum,
 // sum of squares) of each 128-column tile (32 threads: a butterfly inside the half wave) for the next product's LayerNorm
-__global__ __launch_bounds__(256) void k_splitk_reduce_stats(const float *__restrict__ part, int splits, int M, int N,
+// THREADS: 256 for rows up to 1024 columns, 512 up to 2048
+template <int THREADS = 256>
+__global__ __launch_bounds__(THREADS) void k_splitk_reduce_stats(const float *__restrict__ part, int splits, int M, int N,
                                                              const float *__restrict__ bias, const float *__restrict__ residual,
                                                              float *__restrict__ out, bf16 *__restrict__ xcopy,
                                                              float *__restrict__ stats_out) {
@@ -1366,13 +1399,17 @@ int splitk_choice(int M, int N, int K, int cus) {
 }
 ssw_status launch_gemm_splitk_stats(hipStream_t s, const void *A, const void *W, const float *bias, const float *residual,
                                     float *out, float *partials, int M, int N, int K, int splits, const GemmLn &ln) {
-    if (N % BN != 0 || N > 1024 || !bias || !residual || !ln.xcopy || !ln.stats_out) {
+    if (N % BN != 0 || N > 2048 || !bias || !residual || !ln.xcopy || !ln.stats_out) {
         set_error("gemm_splitk_stats: N=%d unsupported or a NULL operand", N);
         return SSW_ERR_UNSUPPORTED;
     }
     SSW_TRY(launch_gemm_splitk_partials(s, A, W, partials, M, N, K, splits));
-    hipLaunchKernelGGL(k_splitk_reduce_stats, dim3(M), dim3(256), 0, s, partials, splits, M, N, bias, residual, out, ln.xcopy,
-                       ln.stats_out);
+    if (N <= 1024)
+        hipLaunchKernelGGL(k_splitk_reduce_stats<256>, dim3(M), dim3(256), 0, s, partials, splits, M, N, bias, residual, out,
+                           ln.xcopy, ln.stats_out);
+    else
+        hipLaunchKernelGGL(k_splitk_reduce_stats<512>, dim3(M), dim3(512), 0, s, partials, splits, M, N, bias, residual, out,
+                           ln.xcopy, ln.stats_out);
     SSW_HIP_TRY(hipGetLastError());
     return SSW_OK;
 }

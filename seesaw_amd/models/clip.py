@@ -1,4 +1,10 @@
-"""CLIP (ViT-B/32, ViT-B/16, ViT-L/14) on the GPU: weight packing + ctypes front of the ssw_clip_* entry points.
+"""CLIP (ViT-B/32, ViT-B/16, ViT-L/14; OpenCLIP ViT-H/14 and ViT-bigG/14 as transformers.CLIPModel) on the GPU:
+weight packing + ctypes front of the ssw_clip_* entry points.  (ViT-g/14's shapes, 1408 wide with heads of 88, are
+accepted; only its attention kernel is tested, no tower of that width.)
+
+Served: image towers up to 1664 wide with heads of 64, 80, 88 or 104 columns and at most 272 tokens; text towers up to
+1664 wide with heads of 64 and at most 80 positions; projections up to 1280; hidden_act "quick_gelu" or "gelu" (the
+same in both towers).  Anything else is refused by pack_clip_weights or ssw_clip_create.
 
 The reference loads `transformers.CLIPModel.from_pretrained(<local dir>)` and calls
 `get_text_features` / `get_image_features` (seesaw/models/embeddings.py:427-455,
@@ -20,6 +26,10 @@ _LAYER_KEYS = ["layer_norm1.weight", "layer_norm1.bias", "self_attn.q_proj.weigh
                "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias"]
 
 
+# the header's last word: fc1's activation (csrc/clip.hip, Header::activation)
+ACTIVATION_CODES = {"quick_gelu": 0, "gelu": 1}
+
+
 def patch_columns(patch_size: int) -> int:
     """Columns of a gathered patch row on the device: 3 patch^2 padded with zero columns to the next multiple of 64
     (csrc/clip.hip, patch_cols; patch 14: 588 -> 640).  The blob is not padded: ssw_clip_create pads the patch weight."""
@@ -29,11 +39,15 @@ def patch_columns(patch_size: int) -> int:
 def pack_clip_weights(state_dict, config) -> np.ndarray:
     """transformers.CLIPModel state_dict + CLIPConfig -> the flat blob ssw_clip_create reads."""
     v, t = config.vision_config, config.text_config
-    assert v.hidden_act == "quick_gelu" and t.hidden_act == "quick_gelu", "only quick_gelu CLIP variants"
+    if v.hidden_act != t.hidden_act:
+        raise ValueError(f"the towers' activations differ (vision {v.hidden_act!r}, text {t.hidden_act!r}): "
+                         "the blob carries one for both")
+    if v.hidden_act not in ACTIVATION_CODES:
+        raise ValueError(f"hidden_act {v.hidden_act!r} is not served: {sorted(ACTIVATION_CODES)}")
     header = struct.pack("<8s6i7iifi", b"SSWCLIP1", v.hidden_size, v.num_hidden_layers, v.num_attention_heads,
                          v.intermediate_size, v.image_size, v.patch_size, t.hidden_size, t.num_hidden_layers,
                          t.num_attention_heads, t.intermediate_size, t.max_position_embeddings, t.vocab_size,
-                         t.eos_token_id, config.projection_dim, float(v.layer_norm_eps), 0)
+                         t.eos_token_id, config.projection_dim, float(v.layer_norm_eps), ACTIVATION_CODES[v.hidden_act])
     assert len(header) == 72
 
     def get(name):
@@ -65,6 +79,8 @@ class ClipModel:
         blob = np.ascontiguousarray(blob, dtype=np.uint8)
         self._h = ctypes.c_void_p()
         hdr = struct.unpack("<8s6i7iifi", blob[:72].tobytes())
+        if hdr[16] not in ACTIVATION_CODES.values():
+            raise ValueError(f"clip blob: activation code {hdr[16]} unknown (0 quick_gelu, 1 gelu)")
         self.image_size, self.patch_size = hdr[5], hdr[6]
         self.vision_hidden, self.text_hidden = hdr[1], hdr[7]
         self.max_positions, self.vocab_size, self.eos_token_id, self.projection_dim = hdr[11], hdr[12], hdr[13], hdr[14]

@@ -2,7 +2,7 @@
 random-init weights (GPU box), with f32 and with bf16 residual rows -- tools/clip_stream_error.py's measurement for the
 towers of tools/perf_clip_variants.py.
 
-  python tools/clip_variants_error.py [--tiles 6]
+  python tools/clip_variants_error.py [--tiles 6] [--models b16,l14[,h14]]
 Prints min cosine and max |delta| of the unit vectors: four lines.  The bar is 0.999 / 5e-3.
 """
 import argparse
@@ -24,8 +24,9 @@ def unit(x):
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--tiles", type=int, default=6)
+ap.add_argument("--models", default="b16,l14", help="of tools/perf_clip_variants.py's MODELS; h14 = ViT-H/14 at 32 layers")
 args = ap.parse_args()
-for name in ("b16", "l14"):
+for name in args.models.split(","):
     torch.manual_seed(1234)
     hf = transformers.CLIPModel(config(name)).eval()
     ours = ClipModel.from_hf(hf)

@@ -1,7 +1,7 @@
-"""Image tower forward of ViT-B/32, ViT-B/16 and ViT-L/14 at 200 tiles a call (GPU box), full depth, seeded random-init
-weights, no HF forward.
+"""Image tower forward of ViT-B/32, ViT-B/16 and ViT-L/14 (and, on request, OpenCLIP ViT-H/14 and bigG/14) at 200 tiles a
+call (GPU box), full depth, seeded random-init weights, no HF forward.
 
-  python tools/perf_clip_variants.py [--models b32,b16,l14] [--tiles 200] [--reps 30] [--text]
+  python tools/perf_clip_variants.py [--models b32,b16,l14[,h14,bigg14]] [--tiles 200] [--reps 30] [--text]
 Per model: the median of `reps` timed calls (each a device-side forward that ends in a synchronise, after 3 warm-up calls)
 with min / max and the interquartile spread, tiles/s, and the fraction of the 2.5 PFLOP/s dense bf16 peak priced at the
 model's own FLOP count per tile (the reference model's: every row through every layer, as DESIGN does for ViT-B/32).
@@ -22,7 +22,12 @@ MODELS = {
     "b32": ("ViT-B/32", 32, 768, 12, 3072, 12, 512, 8, 2048, 512),
     "b16": ("ViT-B/16", 16, 768, 12, 3072, 12, 512, 8, 2048, 512),
     "l14": ("ViT-L/14", 14, 1024, 16, 4096, 24, 768, 12, 3072, 768),
+    # OpenCLIP's (hidden_act "gelu"): the image tower at full depth; the text tower, which this tool does not time unless
+    # --text is given, keeps its widths at 2 layers so that the f32 blob stays a host-memory-sized thing
+    "h14": ("ViT-H/14", 14, 1280, 16, 5120, 32, 1024, 16, 4096, 1024),
+    "bigg14": ("ViT-bigG/14", 14, 1664, 16, 8192, 48, 1280, 20, 5120, 1280),
 }
+OPENCLIP = ("h14", "bigg14")
 
 
 def tile_flops(patch, D, M, L, P, image=224):
@@ -35,10 +40,12 @@ def tile_flops(patch, D, M, L, P, image=224):
 def config(name):
     import transformers
     _, patch, vh, vn, vm, vl, th, tn, tm, proj = MODELS[name]
+    extra_t = dict(num_hidden_layers=2, hidden_act="gelu") if name in OPENCLIP else {}
+    extra_v = dict(hidden_act="gelu") if name in OPENCLIP else {}
     return transformers.CLIPConfig(
-        text_config=dict(hidden_size=th, num_attention_heads=tn, intermediate_size=tm),
+        text_config=dict(hidden_size=th, num_attention_heads=tn, intermediate_size=tm, **extra_t),
         vision_config=dict(hidden_size=vh, num_attention_heads=vn, intermediate_size=vm, num_hidden_layers=vl,
-                           patch_size=patch),
+                           patch_size=patch, **extra_v),
         projection_dim=proj)
 
 
@@ -90,7 +97,8 @@ def main():
             for _ in range(5):
                 m.embed_text(ids)
             tt = np.sort(np.array([_timed(lambda: m.embed_text(ids)) for _ in range(50)]))
-            print(f"{args.label}{title}: one text query (1 x 9 tokens, hidden {th}, host call to host result): median "
+            depth = " at 2 LAYERS, not the model's depth" if name in OPENCLIP else ""
+            print(f"{args.label}{title}: one text query (1 x 9 tokens, hidden {th}{depth}, host call to host result): median "
                   f"{np.median(tt) * 1e3:.3f} ms (min {tt[0] * 1e3:.3f}, max {tt[-1] * 1e3:.3f})", flush=True)
         m.close()
         del x, out
