@@ -1107,7 +1107,17 @@ typedef struct ssw_clip ssw_clip;
  * projection <= 1280, an image tower of at most 272 tokens ((image / patch)^2 + 1; any patch size that divides the
  * image: ViT-B/32, ViT-B/16, ViT-L/14, OpenCLIP ViT-H/14, ViT-bigG/14 at 224 pixels; ViT-g/14's
  * shapes are accepted, its head dim 88 is tested as a kernel only), a text
- * tower of at most 80 positions.  Anything else is SSW_ERR_UNSUPPORTED, decided before any device call. */
+ * tower of at most 80 positions.  Anything else is SSW_ERR_UNSUPPORTED, decided before any device call.
+ * A transformers.SiglipModel comes as a blob of its own: magic "SSWSIGL1", the same 72 bytes (eos_token_id unused;
+ * projection_dim = the text head's width = the image tower's; activation also 2, the tanh GELU
+ * 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3)))), then int32 pooling-head heads, int32 0: 80 bytes, followed by the
+ * f32 tensors in pack_siglip_weights' order, unpadded.  The magic implies: no class token ((image / patch)^2 tokens), a
+ * patch bias, no pre-LayerNorm, the attention-pooling head behind post_layernorm and no image projection; an unmasked
+ * text tower pooled at the last position given, its head with a bias.  Served: head dims 64, 72, 80, 88, 104 in both
+ * towers, hidden sizes multiples of 128, the image tower <= 1152 wide with <= 16 pooling heads and <= 272 tokens, any MLP
+ * width (padded to 128 on the device), <= 64 text positions; the refusal names the offending value.
+ * The u8 entries below normalise with CLIP's pixel mean / std for either magic; SigLIP checkpoints are trained with
+ * mean = std = 0.5, so feed them through ssw_clip_embed_image(_dev) with pixels the caller has normalised. */
 ssw_status ssw_clip_create(int32_t device, const void *weight_blob, size_t bytes, ssw_clip **out);
 ssw_status ssw_clip_destroy(ssw_clip *clip);
 /* pixel_values [b, 3, image, image] f32 (already CLIP-normalised) -> [b, projection_dim] f32;

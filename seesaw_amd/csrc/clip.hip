@@ -34,7 +34,8 @@ typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 enum Epilogue { EPI_F32 = 0, EPI_BF16_BIAS = 1, EPI_BF16_BIAS_GELU = 2, EPI_F32_BIAS_RESIDUAL = 3, EPI_BF16_LN = 4, EPI_BF16_LN_GELU = 5,
-                EPI_F32_BIAS_RESIDUAL_STATS = 6, EPI_BF16_STREAM_STATS = 7, EPI_BF16_BIAS_ERF = 8, EPI_BF16_LN_ERF = 9 };  // as gemm_bf16.hip
+                EPI_F32_BIAS_RESIDUAL_STATS = 6, EPI_BF16_STREAM_STATS = 7, EPI_BF16_BIAS_ERF = 8, EPI_BF16_LN_ERF = 9,
+                EPI_BF16_BIAS_TANH = 13, EPI_BF16_LN_TANH = 14 };  // as gemm_bf16.hip
 
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 __device__ __forceinline__ bf16 to_bf16(float x) { return (bf16)x; }
@@ -102,6 +103,8 @@ __global__ __launch_bounds__(256) void layernorm_rows(const float *__restrict__ 
 // LN = true: y = LayerNorm(x) with (w, b) is the row (x is consumed); LN = false: y = x.
 // With `pos` given, x is the patch embedding's output and the row is put together here, the image tower's input:
 // token 0 of an image = cls + pos[0], token 1 + p = x[image * (T - 1) + p] + pos[1 + p].  y_out may be null (bf16 stream).
+// Without `cls` (SigLIP: no class token, no pre-LayerNorm) the T rows of an image are its patches, row r = x[r] + pos[r % T];
+// the patch convolution's bias is the same for every row and is added to `pos` once, by ssw_clip_create.
 template <bool LN, int NV = 4>
 __global__ __launch_bounds__(256) void stack_input_rows(const float *__restrict__ x, int n_rows, int D,
                                                         const float *__restrict__ w, const float *__restrict__ b,
@@ -116,7 +119,7 @@ __global__ __launch_bounds__(256) void stack_input_rows(const float *__restrict_
     const float4 *pr = nullptr;
     if (pos) {
         const int tk = r % T, img = r / T;
-        xr = reinterpret_cast<const float4 *>(tk == 0 ? cls : x + ((int64_t)img * (T - 1) + tk - 1) * D);
+        if (cls) xr = reinterpret_cast<const float4 *>(tk == 0 ? cls : x + ((int64_t)img * (T - 1) + tk - 1) * D);
         pr = reinterpret_cast<const float4 *>(pos + (int64_t)tk * D);
     }
     const int nv = D >> 2;
@@ -176,7 +179,7 @@ __global__ __launch_bounds__(256) void stack_input_rows(const float *__restrict_
     for (int i = 0; i < NV; ++i) {
         const int c = lane + 64 * i;
         if (c < nv) {
-            if (LN && y_out) yo[c] = v[i];
+            if ((LN || pr) && y_out) yo[c] = v[i];
             bf16x4 h;
             h[0] = (bf16)v[i].x; h[1] = (bf16)v[i].y; h[2] = (bf16)v[i].z; h[3] = (bf16)v[i].w;
             yb[c] = h;
@@ -1500,9 +1503,226 @@ __global__ __launch_bounds__(64) void attn_pooled_rows(const bf16 *__restrict__ 
     }
 }
 
-__global__ void cls_rows(int B, int T, int *__restrict__ rows) {
+// `offset`: 0 = the class token's row of an image; L - 1 = the last position given of a SigLIP text
+__global__ void cls_rows(int B, int T, int *__restrict__ rows, int offset = 0) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < B) rows[b] = b * T;
+    if (b < B) rows[b] = b * T + offset;
+}
+
+// x[b, :] += bias (SigLIP's text head is a Linear with bias; the projection products carry none)
+__global__ void add_row_bias(float *__restrict__ x, const float *__restrict__ bias, int B, int P) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B * P; i += gridDim.x * blockDim.x) x[i] += bias[i % P];
+}
+
+// ---------------------------------------------------------------------------------------
+// SigLIP's pooling head (SiglipMultiheadAttentionPoolingHead): one learned probe row attends over the T tokens of an
+// image behind post_layernorm.  As transformers writes it that is a K and a V projection of every token, 2 T W^2
+// multiply-adds an image for one output row.  The probe is a constant, so the query q = Wq probe + bq and, per head,
+// the row u_h = (1 / sqrt hd) Wk_h^T q_h are too: the logit of token t in head h is x^_t . u_h (+ q_h . bk_h, the same
+// for every token, gone in the softmax), and the head's output is Wv_h (sum_t P_th x^_t) + bv_h since sum_t P_th = 1.
+// What is left per image is two skinny products with the T normalised rows -- map_pool -- and one W x W product with
+// the H pooled rows -- map_value.  post_layernorm's affine part leaves the loop as well: with x~ = (x - mean) rstd,
+// x^ = gamma x~ + beta, the logits are x~ . (gamma u_h) + const_h and sum_t P_th x^_t = gamma (sum_t P_th x~_t) + beta,
+// so ssw_clip_create stores U = gamma (.) u (f32, heads padded with zero rows to 16) and gamma / beta are applied to the
+// 16 pooled rows at the end.
+//
+// map_pool: one workgroup of eight waves per image, the residual rows read ONCE, in strips of 32 tokens:
+//   1. wave w normalises rows 4 w .. 4 w + 3 of the strip (layernorm_rows's two passes over registers), leaves them as
+//      bf16 in the strip's LDS tile, and forms their 16 logits with f32 FMAs from the registers it holds them in (U in LDS,
+//      16 bytes a lane; the four rows share every read of it); a transposing butterfly (7 shuffles a head) adds the lane
+//      partials of the four rows at once.  f32, not the bf16 MFMA: a logit of a peaked pooling (probe x 32) is tens in
+//      magnitude, bf16 operands put ~2^-9 of that on it and the softmax turns that into percents on the weights.
+//   2. every wave: running maximum and sum of head fr (flash-attention's rescaling, in-lane over the lane's 8 tokens, then
+//      xor 16 / 32), P = exp(logit - max) as bf16 in registers; rows past T hold a logit of -inf, pad heads get P = 0.
+//      Z^T += X~^T P : v_mfma_f32_16x16x32_bf16, the strip's 32 tokens are the k-step, the 16 heads the N; the X~^T
+//      fragments come out of ds_read_b64_tr_b16 (rows of W + 16 bf16: 32 B mod 64, attention_hd's V rows).  A wave owns
+//      the column tiles w, w + 8, ..: nine f32x4 accumulators at W = 1152, Z (16 x 1152 f32) spread over the workgroup.
+//   At the end a lane holds Z[head fr][4 consecutive columns]: / sum, * gamma + beta, one 16-byte store.
+// LDS: 64 W + 64 (W + 16) + 2048 bytes: 150 528 at W = 1152 (MAP_MAX_DIM; 1280 would be 166 912 > 160 KiB).
+// ---------------------------------------------------------------------------------------
+constexpr int MAP_HEADS = 16, MAP_STRIP = 32, MAP_NV = 5, MAP_MAX_DIM = 1152, MAP_TILES = MAP_MAX_DIM / 16 / 8;
+static_assert(MAP_NV * 256 >= MAP_MAX_DIM, "a row fits a wave's registers");
+inline size_t map_pool_lds(int W) { return (size_t)MAP_HEADS * W * 4 + (size_t)MAP_STRIP * (W + 16) * 2 + MAP_STRIP * MAP_HEADS * 4; }
+
+template <bool BF16IN>
+__global__ __launch_bounds__(512) void map_pool(const void *__restrict__ xin, const float *__restrict__ U,
+                                                const float *__restrict__ gamma, const float *__restrict__ beta, float eps,
+                                                int T, int W, int H, float *__restrict__ Z) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char map_lds[];
+    const int LDX = W + 16, nv = W >> 2, ntile = W >> 4;
+    float *sU = reinterpret_cast<float *>(map_lds);                                                  // [16][W]
+    bf16 *sX = reinterpret_cast<bf16 *>(map_lds + (size_t)MAP_HEADS * W * 4);                        // [32][W + 16]
+    float *sL = reinterpret_cast<float *>(map_lds + (size_t)MAP_HEADS * W * 4 + (size_t)MAP_STRIP * LDX * 2);  // [32][16]
+    const int t = threadIdx.x, lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int fr = lane & 15, fq = lane >> 4;
+    const int64_t row0 = (int64_t)blockIdx.x * T;
+    for (int i = t; i < MAP_HEADS * nv; i += 512) reinterpret_cast<float4 *>(sU)[i] = reinterpret_cast<const float4 *>(U)[i];
+    f32x4 acc[MAP_TILES];
+#pragma unroll
+    for (int i = 0; i < MAP_TILES; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const bool head_live = fr < H;
+    float m_run = -INFINITY, l_run = 0.f;
+    __syncthreads();
+    for (int t0 = 0; t0 < T; t0 += MAP_STRIP) {
+        // ---- 1. this wave's four rows: normalise, park as bf16, logits ----
+        float4 v[4][MAP_NV];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int row = t0 + wave * 4 + j;
+            const bool live = row < T;  // wave-uniform
+            float s = 0.f;
+#pragma unroll
+            for (int i = 0; i < MAP_NV; ++i) {
+                const int c = lane + 64 * i;
+                v[j][i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (live && c < nv) {
+                    if (BF16IN) {
+                        const bf16x4 hb = *reinterpret_cast<const bf16x4 *>(reinterpret_cast<const bf16 *>(xin) + (row0 + row) * W + 4 * c);
+                        v[j][i] = make_float4((float)hb[0], (float)hb[1], (float)hb[2], (float)hb[3]);
+                    } else {
+                        v[j][i] = *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(xin) + (row0 + row) * W + 4 * c);
+                    }
+                }
+                s += (v[j][i].x + v[j][i].y) + (v[j][i].z + v[j][i].w);
+            }
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+            const float mean = s / (float)W;
+            float q = 0.f;
+#pragma unroll
+            for (int i = 0; i < MAP_NV; ++i) {
+                if (lane + 64 * i < nv) {
+                    const float dx = v[j][i].x - mean, dy = v[j][i].y - mean, dz = v[j][i].z - mean, dw = v[j][i].w - mean;
+                    q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+                }
+            }
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) q += __shfl_xor(q, off, 64);
+            const float rstd = live ? rsqrtf(q / (float)W + eps) : 0.f;  // rows past T: zeros in the tile
+#pragma unroll
+            for (int i = 0; i < MAP_NV; ++i) {
+                const int c = lane + 64 * i;
+                if (c < nv) {
+                    v[j][i].x = (v[j][i].x - mean) * rstd; v[j][i].y = (v[j][i].y - mean) * rstd;
+                    v[j][i].z = (v[j][i].z - mean) * rstd; v[j][i].w = (v[j][i].w - mean) * rstd;
+                    bf16x4 hb;
+                    hb[0] = to_bf16(v[j][i].x); hb[1] = to_bf16(v[j][i].y); hb[2] = to_bf16(v[j][i].z); hb[3] = to_bf16(v[j][i].w);
+                    *reinterpret_cast<bf16x4 *>(&sX[(wave * 4 + j) * LDX + 4 * c]) = hb;
+                }
+            }
+        }
+#pragma unroll 2
+        for (int h = 0; h < MAP_HEADS; ++h) {
+            float a[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int i = 0; i < MAP_NV; ++i) {
+                const int c = lane + 64 * i;
+                const float4 u = c < nv ? reinterpret_cast<const float4 *>(sU)[h * nv + c] : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    a[j] = fmaf(v[j][i].x, u.x, fmaf(v[j][i].y, u.y, fmaf(v[j][i].z, u.z, fmaf(v[j][i].w, u.w, a[j]))));
+            }
+            // the four rows' lane partials added at once: afterwards lane l holds the whole sum of row l & 3
+            const bool o1 = lane & 1, o2 = lane & 2;
+            float b0 = (o1 ? a[1] : a[0]) + __shfl_xor(o1 ? a[0] : a[1], 1, 64);
+            float b1 = (o1 ? a[3] : a[2]) + __shfl_xor(o1 ? a[2] : a[3], 1, 64);
+            float d = (o2 ? b1 : b0) + __shfl_xor(o2 ? b0 : b1, 2, 64);
+#pragma unroll
+            for (int off = 4; off <= 32; off <<= 1) d += __shfl_xor(d, off, 64);
+            if (lane < 4) sL[(wave * 4 + lane) * MAP_HEADS + h] = t0 + wave * 4 + lane < T ? d : -INFINITY;
+        }
+        __syncthreads();
+        // ---- 2. head fr's softmax state over the strip's tokens 8 fq .. 8 fq + 7 (the same arithmetic in every wave) ----
+        float lg[8], mx = -INFINITY;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            lg[e] = sL[(8 * fq + e) * MAP_HEADS + fr];
+            mx = fmaxf(mx, lg[e]);
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float m_new = fmaxf(m_run, mx);        // finite: token t0 is live
+        const float alpha = __expf(m_run - m_new);  // first strip: exp(-inf) = 0 on accumulators that are zero
+        float ps = 0.f;
+        bf16x8 pb;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float p = head_live ? __expf(lg[e] - m_new) : 0.f;  // rows past T: exp(-inf) = 0
+            ps += p;
+            pb[e] = to_bf16(p);
+        }
+        ps += __shfl_xor(ps, 16, 64);
+        ps += __shfl_xor(ps, 32, 64);
+        l_run = l_run * alpha + ps;
+        m_run = m_new;
+        // X~^T fragment as attention_long's V^T: in a 16-lane group lane 4 q + x supplies token row 8 fq + q (+ 4), columns 4 x ..
+        const int kq = 8 * fq + (fr >> 2), dp = (fr & 3) * 4;
+#pragma unroll
+        for (int i = 0; i < MAP_TILES; ++i) {
+            const int jt = wave + 8 * i;
+            if (jt < ntile) {  // wave-uniform
+                typedef __attribute__((ext_vector_type(4))) short s16x4;
+                typedef __attribute__((address_space(3))) s16x4 *lds_s16x4;
+                typedef __attribute__((ext_vector_type(8))) short s16x8;
+                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(&sX[kq * LDX + jt * 16 + dp]));
+                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(&sX[(kq + 4) * LDX + jt * 16 + dp]));
+                const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+                acc[i] *= alpha;
+                acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, both), pb, acc[i], 0, 0, 0);
+            }
+        }
+        __syncthreads();  // the next strip overwrites the tile and the logits
+    }
+    // acc[i][r] = sum_t P[t][head fr] x~[t][16 jt + 4 fq + r]
+    if (!head_live) return;
+    const float inv = 1.f / l_run;
+    float *zrow = Z + ((int64_t)blockIdx.x * MAP_HEADS + fr) * W;
+#pragma unroll
+    for (int i = 0; i < MAP_TILES; ++i) {
+        const int col = (wave + 8 * i) * 16 + 4 * fq;
+        if (col < W) {
+            const f32x4 g = *reinterpret_cast<const f32x4 *>(gamma + col), bb = *reinterpret_cast<const f32x4 *>(beta + col);
+            *reinterpret_cast<f32x4 *>(zrow + col) = acc[i] * inv * g + bb;
+        }
+    }
+}
+
+// map_value: the value projection of every head's OWN pooled row, o[b][h hd + j] = Wv[h hd + j] . z[b][h] + bv[h hd + j]:
+// H products [B x W] [W x hd] whose left operand differs by head, as one grouped launch -- workgroup (feature tile of 16
+// inside a head, head, 16 images), four waves that split K = W by k-steps of 32 (skinny_linear's shape: the W fragment
+// straight from memory, 16 bytes a lane; the z rows are the other operand, rounded to bf16 as every product's input),
+// partial tiles added through LDS in wave order.  hd need not be a multiple of 16 (72 = 4.5 tiles): a tile's rows past the
+// head are clamped reads whose stores are masked, as are the images past B.
+__global__ __launch_bounds__(256) void map_value(const float *__restrict__ Z, const bf16 *__restrict__ Wv,
+                                                 const float *__restrict__ bv, int B, int W, int hd, bf16 *__restrict__ out) {
+    __shared__ f32x4 part[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fr = lane & 15, fq = lane >> 4;
+    const int jt = blockIdx.x, h = blockIdx.y, b0 = blockIdx.z * 16;
+    const bf16 *wrow = Wv + (int64_t)(h * hd + min(jt * 16 + fr, hd - 1)) * W;
+    const float *zrow = Z + ((int64_t)min(b0 + fr, B - 1) * MAP_HEADS + h) * W;
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int ks = wave; ks < W / 32; ks += 4) {
+        const int k0 = ks * 32 + fq * 8;
+        const bf16x8 wf = *reinterpret_cast<const bf16x8 *>(wrow + k0);
+        const float4 z0 = *reinterpret_cast<const float4 *>(zrow + k0), z1 = *reinterpret_cast<const float4 *>(zrow + k0 + 4);
+        bf16x8 zb;
+        zb[0] = to_bf16(z0.x); zb[1] = to_bf16(z0.y); zb[2] = to_bf16(z0.z); zb[3] = to_bf16(z0.w);
+        zb[4] = to_bf16(z1.x); zb[5] = to_bf16(z1.y); zb[6] = to_bf16(z1.z); zb[7] = to_bf16(z1.w);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, zb, acc, 0, 0, 0);  // lane: o[image fr][feature 4 fq + r]
+    }
+    part[wave][lane] = acc;
+    __syncthreads();
+    const int j0 = jt * 16 + fq * 4;  // (hd % 4 == 0: the lane's four features are in the head or out of it)
+    if (wave != 0 || b0 + fr >= B || j0 >= hd) return;
+    f32x4 v = part[0][lane];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) v += part[w][lane];
+    v += *reinterpret_cast<const f32x4 *>(bv + h * hd + j0);
+    bf16x4 ov;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) ov[r] = to_bf16(v[r]);
+    *reinterpret_cast<bf16x4 *>(out + (int64_t)(b0 + fr) * W + h * hd + j0) = ov;
 }
 
 }  // namespace
@@ -1524,8 +1744,10 @@ struct Layer {
 
 struct Tower {
     int D = 0, L = 0, H = 0, M = 0, T = 0;
+    int Mb = 0;  // the MLP width in the blob; M is it padded to the GEMM's 128 columns (SigLIP so400m: 4304 -> 4352)
     std::vector<Layer> layers;
     float *lnf_w = nullptr, *lnf_b = nullptr;
+    const float *lnf_w_host = nullptr;  // the final LayerNorm's weight inside the caller's blob (ssw_clip_create only)
     bf16 *proj = nullptr;
 };
 
@@ -1535,7 +1757,15 @@ struct Header {
     int32_t t_hidden, t_layers, t_heads, t_mlp, t_maxpos, vocab, eos;
     int32_t proj;
     float ln_eps;
-    int32_t activation;  // fc1's: 0 = quick-GELU x sigmoid(1.702 x), 1 = GELU 0.5 x (1 + erf(x / sqrt 2))
+    int32_t activation;  // fc1's: 0 = quick-GELU x sigmoid(1.702 x), 1 = GELU 0.5 x (1 + erf(x / sqrt 2)); SSWSIGL1 only: 2 = tanh GELU
+};
+// A SigLIP blob (magic SSWSIGL1): the same fields -- `eos` is unused, `proj` is the text head's width and the image
+// tower's own -- and two more words.  What the magic implies: no class token, a patch bias, no pre-LayerNorm, the pooling
+// head behind the image tower; a bidirectional text tower pooled at the last position given, its head with a bias.
+struct SiglipHeader {
+    Header h;
+    int32_t pool_heads;  // heads of the pooling head's attention (transformers: the image tower's)
+    int32_t reserved;    // 0
 };
 
 }  // namespace
@@ -1549,6 +1779,13 @@ struct ssw_clip {
     // vision extras
     bf16 *patch_w = nullptr;
     float *cls = nullptr, *vpos = nullptr, *pre_w = nullptr, *pre_b = nullptr;
+    // SigLIP (magic SSWSIGL1): the pooling head -- U = gamma (.) u [16][W] (map_pool), the value / out projections, its
+    // LayerNorm and MLP -- and the text head's bias
+    bool siglip = false;
+    int pool_heads = 0, pool_mlp = 0;
+    float *map_u = nullptr, *map_bv = nullptr, *map_bo = nullptr, *map_lnw = nullptr, *map_lnb = nullptr, *map_b1 = nullptr,
+          *map_b2 = nullptr, *head_b = nullptr;
+    bf16 *map_wv = nullptr, *map_wo = nullptr, *map_w1 = nullptr, *map_w2 = nullptr;
     // text extras
     float *tok = nullptr, *tpos = nullptr;
     // workspace (sized for `cap_rows` token rows)
@@ -1590,8 +1827,9 @@ inline int patch_cols(int patch) { return (3 * patch * patch + 63) / 64 * 64; }
 inline bool aligned_gather(const Header &h, bool in_levels = false) {
     return h.patch % 8 == 0 && (!in_levels || (h.image / 2) % 8 == 0);
 }
-// token rows of the image tower
-inline int vision_tokens(const Header &h) { return (h.image / h.patch) * (h.image / h.patch) + 1; }
+// fc1's epilogue by the header's activation code: quick-GELU, exact GELU, tanh GELU
+inline int act_epi_bias(int activation) { return activation == 2 ? EPI_BF16_BIAS_TANH : activation == 1 ? EPI_BF16_BIAS_ERF : EPI_BF16_BIAS_GELU; }
+inline int act_epi_ln(int activation) { return activation == 2 ? EPI_BF16_LN_TANH : activation == 1 ? EPI_BF16_LN_ERF : EPI_BF16_LN_GELU; }
 
 ssw_status dmalloc(ssw_clip *c, void **p, size_t bytes) {
     SSW_HIP_TRY(hipMalloc(p, bytes + 64));
@@ -1657,6 +1895,48 @@ ssw_status fold_layernorm(ssw_clip *c, const float *W, const float *gamma, const
     return SSW_OK;
 }
 
+// An MLP of the blob -- fc1 [Mb, D], its bias [Mb], fc2 [D, Mb], its bias [D] -- as the GEMMs want it: fc1's rows and bias
+// and fc2's columns padded with zeros to M, a multiple of 128 (SigLIP so400m: 4304 -> 4352).  Every activation served
+// maps 0 to 0, so the pad columns of fc1's output are exact zeros against fc2's zero columns.  The blob is not padded.
+struct MlpHost {
+    const float *w1, *b1, *w2, *b2;
+    std::vector<float> padded;
+};
+ssw_status mlp_from_blob(const float *&cur, const float *end, size_t D, size_t Mb, size_t M, MlpHost &m) {
+    if (cur + Mb * D + Mb + D * Mb + D > end) {
+        set_error("clip: weight blob truncated");
+        return SSW_ERR_INVALID;
+    }
+    m.w1 = cur;
+    m.b1 = m.w1 + Mb * D;
+    m.w2 = m.b1 + Mb;
+    m.b2 = m.w2 + D * Mb;
+    cur = m.b2 + D;
+    if (M != Mb) {
+        m.padded.assign(M * D + M + D * M, 0.f);
+        float *w1 = m.padded.data(), *b1 = w1 + M * D, *w2 = b1 + M;
+        memcpy(w1, m.w1, Mb * D * sizeof(float));
+        memcpy(b1, m.b1, Mb * sizeof(float));
+        for (size_t r = 0; r < D; ++r) memcpy(w2 + r * M, m.w2 + r * Mb, Mb * sizeof(float));
+        m.w1 = w1;
+        m.b1 = b1;
+        m.w2 = w2;
+    }
+    return SSW_OK;
+}
+ssw_status upload_mlp(ssw_clip *c, const MlpHost &m, size_t D, size_t M, bf16 **w1, float **b1, bf16 **w2, float **b2,
+                      float *scratch) {
+    const float *p = m.w1;
+    SSW_TRY(upload_bf16(c, p, p + M * D, M * D, w1, scratch));
+    p = m.b1;
+    SSW_TRY(upload_f32(c, p, p + M, M, b1));
+    p = m.w2;
+    SSW_TRY(upload_bf16(c, p, p + D * M, D * M, w2, scratch));
+    p = m.b2;
+    SSW_TRY(upload_f32(c, p, p + D, D, b2));
+    return SSW_OK;
+}
+
 // q, k, v weights/biases are consecutive in the blob; fuse them into one [3D, D] operand
 ssw_status load_tower(ssw_clip *c, Tower &tw, const float *&cur, const float *end, float *scratch) {
     const size_t D = tw.D, M = tw.M;
@@ -1695,19 +1975,61 @@ ssw_status load_tower(ssw_clip *c, Tower &tw, const float *&cur, const float *en
         const float *ln2w_h = cur, *ln2b_h = cur + D;
         SSW_TRY(upload_f32(c, cur, end, D, &ly.ln2w));
         SSW_TRY(upload_f32(c, cur, end, D, &ly.ln2b));
-        if (cur + M * D + M > end) {
-            set_error("clip: weight blob truncated");
-            return SSW_ERR_INVALID;
-        }
-        if (folds) SSW_TRY(fold_layernorm(c, cur, ln2w_h, ln2b_h, cur + M * D, M, D, &ly.w1_ln, &ly.c1fc1, &ly.c2fc1, scratch));
-        SSW_TRY(upload_bf16(c, cur, end, M * D, &ly.w1, scratch));
-        SSW_TRY(upload_f32(c, cur, end, M, &ly.b1));
-        SSW_TRY(upload_bf16(c, cur, end, D * M, &ly.w2, scratch));
-        SSW_TRY(upload_f32(c, cur, end, D, &ly.b2));
+        MlpHost mlp;
+        SSW_TRY(mlp_from_blob(cur, end, D, tw.Mb, M, mlp));
+        if (folds) SSW_TRY(fold_layernorm(c, mlp.w1, ln2w_h, ln2b_h, mlp.b1, M, D, &ly.w1_ln, &ly.c1fc1, &ly.c2fc1, scratch));
+        SSW_TRY(upload_mlp(c, mlp, D, M, &ly.w1, &ly.b1, &ly.w2, &ly.b2, scratch));
     }
+    tw.lnf_w_host = cur;
     SSW_TRY(upload_f32(c, cur, end, D, &tw.lnf_w));
     SSW_TRY(upload_f32(c, cur, end, D, &tw.lnf_b));
     return SSW_OK;
+}
+
+// SigLIP's pooling head, behind the image tower's post_layernorm (gamma: Tower::lnf_w_host): probe [W],
+// in_proj_weight [3W, W], in_proj_bias [3W], out_proj, layernorm, mlp.  The probe's side of the attention is folded here,
+// once, in f64 (map_pool's comment): q = Wq probe + bq, u_h = (1 / sqrt hd) Wk_h^T q_h, U = gamma (.) u, heads padded with zero
+// rows to 16.  Wq, Wk and both their biases are not uploaded: the key bias moves every logit of a head by the same q_h . bk_h.
+ssw_status load_pooling_head(ssw_clip *c, const float *&cur, const float *end, float *scratch) {
+    const size_t W = c->vis.D, H = c->pool_heads, hd = W / H;
+    const float *gamma = c->vis.lnf_w_host;  // post_layernorm.weight
+    if (cur + W + 3 * W * W + 3 * W > end) {
+        set_error("clip: weight blob truncated");
+        return SSW_ERR_INVALID;
+    }
+    const float *probe = cur, *w_in = cur + W, *b_in = w_in + 3 * W * W;
+    std::vector<double> q(W);
+    for (size_t n = 0; n < W; ++n) {
+        double a = b_in[n];
+        for (size_t k = 0; k < W; ++k) a += (double)w_in[n * W + k] * (double)probe[k];
+        q[n] = a;
+    }
+    std::vector<double> u(W);
+    std::vector<float> U((size_t)MAP_HEADS * W, 0.f);
+    const double scale = 1.0 / std::sqrt((double)hd);
+    for (size_t h = 0; h < H; ++h) {
+        std::fill(u.begin(), u.end(), 0.0);
+        for (size_t j = 0; j < hd; ++j) {
+            const float *wk = w_in + (W + h * hd + j) * W;
+            const double qj = q[h * hd + j];
+            for (size_t k = 0; k < W; ++k) u[k] += qj * (double)wk[k];
+        }
+        for (size_t k = 0; k < W; ++k) U[h * W + k] = (float)(scale * u[k] * (double)gamma[k]);
+    }
+    const float *p = U.data();
+    SSW_TRY(upload_f32(c, p, p + U.size(), U.size(), &c->map_u));
+    p = w_in + 2 * W * W;
+    SSW_TRY(upload_bf16(c, p, p + W * W, W * W, &c->map_wv, scratch));
+    p = b_in + 2 * W;
+    SSW_TRY(upload_f32(c, p, p + W, W, &c->map_bv));
+    cur = b_in + 3 * W;
+    SSW_TRY(upload_bf16(c, cur, end, W * W, &c->map_wo, scratch));
+    SSW_TRY(upload_f32(c, cur, end, W, &c->map_bo));
+    SSW_TRY(upload_f32(c, cur, end, W, &c->map_lnw));
+    SSW_TRY(upload_f32(c, cur, end, W, &c->map_lnb));
+    MlpHost mlp;
+    SSW_TRY(mlp_from_blob(cur, end, W, c->vis.Mb, c->pool_mlp, mlp));
+    return upload_mlp(c, mlp, W, c->pool_mlp, &c->map_w1, &c->map_b1, &c->map_w2, &c->map_b2, scratch);
 }
 
 template <int EPI>
@@ -1726,19 +2048,20 @@ ssw_status reserve(ssw_clip *c, int64_t batch) {
                     (void *)c->out, (void *)c->ids, (void *)c->rows, (void *)c->stats_a, (void *)c->stats_b, (void *)c->splitk})
         (void)hipFree(p);
     const Header &h = c->hdr;
-    const int64_t Tv = (int64_t)(h.image / h.patch) * (h.image / h.patch) + 1;
-    const int64_t rows = batch * std::max<int64_t>(Tv, h.t_maxpos);
-    const int64_t D = std::max(h.v_hidden, h.t_hidden), Mm = std::max(h.v_mlp, h.t_mlp);
+    const int64_t Tv = c->vis.T, g2 = (int64_t)(h.image / h.patch) * (h.image / h.patch);
+    // (SigLIP: map_pool leaves 16 pooled rows an image in hidden2)
+    const int64_t rows = batch * std::max<int64_t>(std::max<int64_t>(Tv, h.t_maxpos), c->siglip ? MAP_HEADS : 1);
+    const int64_t D = std::max(h.v_hidden, h.t_hidden), Mm = std::max(c->vis.M, c->txt.M);
     const int64_t pcols = patch_cols(h.patch);
     SSW_HIP_TRY(hipMalloc((void **)&c->hidden, rows * D * sizeof(float)));
     SSW_HIP_TRY(hipMalloc((void **)&c->hidden2, rows * D * sizeof(float)));
     SSW_HIP_TRY(hipMalloc((void **)&c->pooled, batch * D * sizeof(float)));
-    SSW_HIP_TRY(hipMalloc((void **)&c->patch_out, batch * (Tv - 1) * h.v_hidden * sizeof(float)));
+    SSW_HIP_TRY(hipMalloc((void **)&c->patch_out, batch * g2 * h.v_hidden * sizeof(float)));
     SSW_HIP_TRY(hipMalloc((void **)&c->xn, rows * D * sizeof(bf16)));
     SSW_HIP_TRY(hipMalloc((void **)&c->qkv, rows * 3 * D * sizeof(bf16)));
     SSW_HIP_TRY(hipMalloc((void **)&c->att, rows * D * sizeof(bf16)));
     SSW_HIP_TRY(hipMalloc((void **)&c->h1, rows * Mm * sizeof(bf16)));
-    SSW_HIP_TRY(hipMalloc((void **)&c->patches, batch * (Tv - 1) * pcols * sizeof(bf16)));
+    SSW_HIP_TRY(hipMalloc((void **)&c->patches, batch * g2 * pcols * sizeof(bf16)));
     SSW_HIP_TRY(hipMalloc((void **)&c->pixels, batch * 3LL * h.image * h.image * sizeof(float)));
     SSW_HIP_TRY(hipMalloc((void **)&c->out, batch * h.proj * sizeof(float)));
     SSW_HIP_TRY(hipMalloc((void **)&c->ids, batch * h.t_maxpos * sizeof(int)));
@@ -1854,8 +2177,9 @@ void launch_stack_input_rows(hipStream_t s, const float *x, int n_rows, int D, c
                            eps, y_out, y_bf16, stats, np, cls, pos, T);
 }
 
-// head dims 80 / 88 / 104 (non-causal, S <= ATT_LONG_MAX_S): attention_hd's smallest instance that holds S
-inline bool attention_hd_serves(int head_dim) { return head_dim == 80 || head_dim == 88 || head_dim == 104; }
+// head dims 72 (SigLIP so400m, both towers) / 80 / 88 / 104 (non-causal, S <= ATT_LONG_MAX_S): attention_hd's smallest
+// instance that holds S
+inline bool attention_hd_serves(int head_dim) { return head_dim == 72 || head_dim == 80 || head_dim == 88 || head_dim == 104; }
 template <int HD>
 void launch_attention_hd_of(hipStream_t s, const bf16 *qkv, bf16 *att, int n_heads, int S, int D, int H, float scale) {
     if (S <= ATT_MAX_S) hipLaunchKernelGGL((attention_hd<HD, 5>), dim3(n_heads), dim3(256), 0, s, qkv, att, S, D, H, scale);
@@ -1863,6 +2187,7 @@ void launch_attention_hd_of(hipStream_t s, const bf16 *qkv, bf16 *att, int n_hea
 }
 void launch_attention_hd(hipStream_t s, const bf16 *qkv, bf16 *att, int n_heads, int S, int D, int H, float scale) {
     switch (D / H) {
+    case 72: launch_attention_hd_of<72>(s, qkv, att, n_heads, S, D, H, scale); break;
     case 80: launch_attention_hd_of<80>(s, qkv, att, n_heads, S, D, H, scale); break;
     case 88: launch_attention_hd_of<88>(s, qkv, att, n_heads, S, D, H, scale); break;
     default: launch_attention_hd_of<104>(s, qkv, att, n_heads, S, D, H, scale); break;
@@ -1874,7 +2199,9 @@ ssw_status run_tower(ssw_clip *c, const Tower &tw, int B, int S, int causal) {
     const int R = B * S, D = tw.D, M = tw.M;
     const float eps = c->hdr.ln_eps;
     float *h = c->hidden, *h2 = c->hidden2;
-    const bool skinny = skinny_rows(R, D, M) && tw.H * 64 == D;  // skinny_attn_out: 8 heads of 64
+    // `causal` names the tower (1 = text) for everything below; the attention mask is CLIP's text tower's only
+    const int mask = causal && !c->siglip;
+    const bool skinny = skinny_rows(R, D, M) && tw.H * 64 == D && !c->siglip;  // skinny_attn_out: 8 heads of 64; no tanh GELU there
     for (int l = 0; l < tw.L && skinny; ++l) {
         const Layer &ly = tw.layers[l];
         launch_skinny<SK_BF16_BIAS, true>(s, h, nullptr, ly.ln1w, ly.ln1b, eps, ly.wqkv, ly.bqkv, nullptr, c->qkv, R,
@@ -1883,14 +2210,14 @@ ssw_status run_tower(ssw_clip *c, const Tower &tw, int B, int S, int causal) {
         static const bool two_launches = getenv("SSW_CLIP_NO_FUSED_ATTN") != nullptr;  // A/B: attention as its own launch
         if (two_launches) {
             hipLaunchKernelGGL(attention_mfma<4>, dim3(B * tw.H), dim3(256), 0, s, c->qkv, c->att, S, D, tw.H, att_scale,
-                               causal);
+                               mask);
             launch_skinny<SK_F32_BIAS_RESIDUAL, false>(s, c->att, nullptr, nullptr, nullptr, eps, ly.wo, ly.bo, h, h2, R, D, D);
         } else if (R <= 16) {
             hipLaunchKernelGGL(skinny_attn_out<1>, dim3(D / 16), dim3(256), 0, s, c->qkv, ly.wo, ly.bo, h, h2, R, S,
-                               att_scale, causal);
+                               att_scale, mask);
         } else {
             hipLaunchKernelGGL(skinny_attn_out<2>, dim3(D / 16), dim3(256), 0, s, c->qkv, ly.wo, ly.bo, h, h2, R, S,
-                               att_scale, causal);
+                               att_scale, mask);
         }
         if (c->hdr.activation == 1)
             launch_skinny<SK_BF16_BIAS_ERF, true>(s, h2, nullptr, ly.ln2w, ly.ln2b, eps, ly.w1, ly.b1, nullptr, c->h1, R, M, D);
@@ -1908,8 +2235,7 @@ ssw_status run_tower(ssw_clip *c, const Tower &tw, int B, int S, int causal) {
     // ln_row_request), so D % 256 == 0 and D <= 2048.  ViT-H/14 (1280) and bigG/14's text tower (1280) are folded;
     // bigG/14's image tower (1664 = 13 x 128) and ViT-g/14's (1408 = 11 x 128) run this form, as 384 and 640 do.
     const bool unfused_ln = !ln_folds(D);
-    const bool erf_gelu = c->hdr.activation == 1;  // fc1's epilogue: 0.5 x (1 + erf(x / sqrt 2)) instead of quick-GELU
-    const int epi_ln_act = erf_gelu ? EPI_BF16_LN_ERF : EPI_BF16_LN_GELU;
+    const int epi_ln_act = act_epi_ln(c->hdr.activation);  // fc1's epilogue: quick-GELU, the exact GELU or the tanh GELU
     // the residual stream of the tile path in bf16: the producers' bf16 copy IS the stream (read, added to, written back
     // in place by EPI_BF16_STREAM_STATS), the f32 row and its 30 MB + 30 MB a product at B = 200 are gone
     // Measured against transformers' f32 towers (tools/clip_stream_error.py, 26 images): min cosine 0.999994 -> 0.999952,
@@ -1955,7 +2281,8 @@ ssw_status run_tower(ssw_clip *c, const Tower &tw, int B, int S, int causal) {
             // last attention runs row 0's query against the image's keys (attn_pooled_rows), the out-projection on those B
             // rows (split over K like the last fc2).  SSW_CLIP_OPT_FULL_LAST_LAYER runs every row as the reference's model does.
             const bool full_last_layer = (c->flags & 16) != 0;
-            bool pooled_only = l == tw.L - 1 && !full_last_layer && S >= 8 && M % 512 == 0;  // (S: the partial products borrow the qkv buffer)
+            // (S: the partial products borrow the qkv buffer; SigLIP's pooling head reads every row of the last layer)
+            bool pooled_only = l == tw.L - 1 && !full_last_layer && S >= 8 && M % 512 == 0 && !c->siglip;
 #ifdef SSW_DEBUG_HOOKS
             if (c->tap_layer == l && c->tap_tower == 0) pooled_only = false;  // the tap wants every row of this layer
 #endif
@@ -2016,25 +2343,25 @@ ssw_status run_tower(ssw_clip *c, const Tower &tw, int B, int S, int causal) {
         // (one wave per pair with four tiles, attention_mfma<4, 4>: 21.6 us per layer against 17.1 -- measured, not kept)
         static const bool direct_env = getenv("SSW_CLIP_ATTN_DIRECT") != nullptr;  // A/B: fragments straight from memory
         const bool direct_frags = direct_env || (c->flags & 4) != 0;
-        if (D / tw.H != 64)  // (the image tower only, 80 / 88 / 104: ssw_clip_create's condition)
+        if (D / tw.H != 64)  // (72 / 80 / 88 / 104, in a tower without a mask: ssw_clip_create's condition)
             launch_attention_hd(s, c->qkv, c->att, n_heads, S, D, tw.H, att_scale);
         else if (S > ATT_MAX_S || (c->flags & 64) != 0)
-            launch_attention_long(s, c->qkv, c->att, n_heads, S, D, tw.H, att_scale, causal);
+            launch_attention_long(s, c->qkv, c->att, n_heads, S, D, tw.H, att_scale, mask);
         else if (S <= 64 && !one_tile_waves && !direct_frags)
-            hipLaunchKernelGGL(attention_rows64, dim3(n_heads), dim3(128), 0, s, c->qkv, c->att, S, D, tw.H, att_scale, causal);
+            hipLaunchKernelGGL(attention_rows64, dim3(n_heads), dim3(128), 0, s, c->qkv, c->att, S, D, tw.H, att_scale, mask);
         else if (S <= 64 && !one_tile_waves)
             hipLaunchKernelGGL((attention_mfma<4, 2>), dim3(n_heads), dim3(128), 0, s, c->qkv, c->att, S, D, tw.H, att_scale,
-                               causal);
+                               mask);
         else if (S <= 64)
             hipLaunchKernelGGL(attention_mfma<4>, dim3(n_heads), dim3(256), 0, s, c->qkv, c->att, S, D, tw.H, att_scale,
-                               causal);
+                               mask);
         else
             hipLaunchKernelGGL(attention_mfma<5>, dim3(n_heads), dim3(320), 0, s, c->qkv, c->att, S, D, tw.H, att_scale,
-                               causal);
+                               mask);
         if (unfused_ln) {
             SSW_TRY(gemm<EPI_F32_BIAS_RESIDUAL>(s, c->att, ly.wo, ly.bo, h, h2, R, D, D));
             launch_layernorm_rows<bf16>(s, h2, nullptr, R, D, ly.ln2w, ly.ln2b, eps, c->xn);
-            SSW_TRY(launch_gemm_bf16_nt(erf_gelu ? EPI_BF16_BIAS_ERF : EPI_BF16_BIAS_GELU, s, c->xn, ly.w1, ly.b1, nullptr, c->h1, R, M, D));
+            SSW_TRY(launch_gemm_bf16_nt(act_epi_bias(c->hdr.activation), s, c->xn, ly.w1, ly.b1, nullptr, c->h1, R, M, D));
             SSW_TRY(gemm<EPI_F32_BIAS_RESIDUAL>(s, c->h1, ly.w2, ly.b2, h2, h, R, D, M));
         } else if (bf16_stream) {
             c->stream_in_xn = true;
@@ -2109,17 +2436,57 @@ constexpr int HOST_CHUNK = 1024;
 // HOST_CHUNK is the count for a tower of at most ATT_MAX_S tokens; a longer image tower gets as many tiles as make the same
 // number of token rows (ViT-L/14: 318), so the workspace and every row index stay where ViT-B/32 has them.  A tile's
 // vector does not depend on the chunk: no product of the image tower chooses its form by the row count.
-inline int image_chunk(const Header &h) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>(HOST_CHUNK, (int64_t)HOST_CHUNK * ATT_MAX_S / vision_tokens(h)));
+inline int image_chunk(const ssw_clip *c) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>(HOST_CHUNK, (int64_t)HOST_CHUNK * ATT_MAX_S / c->vis.T));
+}
+
+// SigLIP's image tower behind its last layer: post_layernorm and the probe's attention over the T tokens (map_pool), the
+// heads' value projections (map_value), then B-row products on the kernels the towers already have: out_proj (split over
+// K, no residual), the head's LayerNorm, fc1 with the activation, fc2 + the residual, straight into out_dev.
+ssw_status siglip_pool(ssw_clip *c, int B, int normalize, float *out_dev) {
+    hipStream_t s = c->stream;
+    const Tower &tw = c->vis;
+    const int W = tw.D, T = tw.T, H = c->pool_heads, M = c->pool_mlp;
+    const float eps = c->hdr.ln_eps;
+    float *Z = c->hidden2;  // [B][16][W]: free behind the stack (reserve: at least 16 rows an image)
+    const size_t lds = map_pool_lds(W);  // (above 64 KB: ssw_clip_create has raised the kernels' limit on this device)
+    if (c->stream_in_xn)
+        hipLaunchKernelGGL(map_pool<true>, dim3(B), dim3(512), lds, s, (const void *)c->xn, c->map_u, tw.lnf_w, tw.lnf_b, eps, T, W, H, Z);
+    else
+        hipLaunchKernelGGL(map_pool<false>, dim3(B), dim3(512), lds, s, (const void *)c->hidden, c->map_u, tw.lnf_w, tw.lnf_b, eps, T, W, H, Z);
+    const int hd = W / H;
+    hipLaunchKernelGGL(map_value, dim3((hd + 15) / 16, H, (B + 15) / 16), dim3(256), 0, s, Z, c->map_wv, c->map_bv, B, W, hd, c->att);
+    int splits = 1;  // out_proj is a tile or two of rows: split over K as the last layer's fc2 (the same split for every B)
+    for (int sp : {8, 6, 4, 3, 2})
+        if (W / 64 % sp == 0) {
+            splits = sp;
+            break;
+        }
+    float *y = c->pooled;  // the attention's output row: the residual of the head's MLP
+    SSW_TRY(launch_gemm_splitk_f32(s, c->att, c->map_wo, c->map_bo, nullptr, y, c->splitk, B, W, W, splits));
+    launch_layernorm_rows<bf16>(s, y, nullptr, B, W, c->map_lnw, c->map_lnb, eps, c->xn);
+    SSW_TRY(launch_gemm_bf16_nt(act_epi_bias(c->hdr.activation), s, c->xn, c->map_w1, c->map_b1, nullptr, c->h1, B, M, W));
+    SSW_TRY(gemm<EPI_F32_BIAS_RESIDUAL>(s, c->h1, c->map_w2, c->map_b2, y, out_dev, B, W, M));
+    if (normalize) hipLaunchKernelGGL(l2norm_rows, dim3((B + 3) / 4), dim3(256), 0, s, out_dev, B, W);
+    SSW_HIP_TRY(hipGetLastError());
+    return SSW_OK;
 }
 
 // c->patches holds the im2col'ed bf16 patches of B images
 ssw_status image_forward_from_patches(ssw_clip *c, int B, int normalize, float *out_dev) {
     hipStream_t s = c->stream;
     const Header &h = c->hdr;
-    const int g = h.image / h.patch, T = g * g + 1, D = h.v_hidden;
+    const int g = h.image / h.patch, T = c->vis.T, D = h.v_hidden;
     const int pcols = patch_cols(h.patch);
-    SSW_TRY(gemm<EPI_F32>(s, c->patches, c->patch_w, nullptr, nullptr, c->patch_out, B * (T - 1), D, pcols));
+    SSW_TRY(gemm<EPI_F32>(s, c->patches, c->patch_w, nullptr, nullptr, c->patch_out, B * g * g, D, pcols));
+    if (c->siglip) {
+        // no class token, no pre-LayerNorm: patch rows + (position embedding + patch bias) are the stack's input; behind the
+        // stack every token goes through post_layernorm into the pooling head
+        launch_stack_input_rows<false>(s, c->patch_out, B * T, D, nullptr, nullptr, h.ln_eps,
+                                       bf16_rows(c, c->vis, 0) ? (float *)nullptr : c->hidden, c->xn, c->stats_a, nullptr, c->vpos, T);
+        SSW_TRY(run_tower(c, c->vis, B, T, 0));
+        return siglip_pool(c, B, normalize, out_dev);
+    }
     // cls / patch rows + position embedding, then the pre-LayerNorm = the stack's input row, in one pass: bf16 copy and
     // statistics for layer 0's QKV, and the f32 row into c->hidden unless the stack keeps its rows in bf16
     // (round 3: putting the rows together was a launch and a 30-MB round trip of its own at B = 200)
@@ -2171,11 +2538,19 @@ ssw_status text_forward(ssw_clip *c, const int *ids_dev, int B, int L, int norma
     const Header &h = c->hdr;
     const int D = h.t_hidden;
     hipLaunchKernelGGL(text_embed, dim3(1024), dim3(256), 0, s, ids_dev, c->tok, c->tpos, c->hidden, B, L, D);
-    if (!(skinny_rows(B * L, D, c->txt.M) && c->txt.H * 64 == D))  // the tile path wants the row's bf16 copy + statistics
+    if (!(skinny_rows(B * L, D, c->txt.M) && c->txt.H * 64 == D && !c->siglip))  // the tile path wants the row's bf16 copy + statistics
         launch_stack_input_rows<false>(s, c->hidden, B * L, D, nullptr, nullptr, h.ln_eps, c->hidden, c->xn, c->stats_a);
     SSW_TRY(run_tower(c, c->txt, B, L, 1));
-    hipLaunchKernelGGL(eos_rows, dim3((B + 255) / 256), dim3(256), 0, s, ids_dev, B, L, h.eos, c->rows);
     c->rows_key = -1;
+    if (c->siglip) {  // pooled at the last position given, whatever its token; the head is a Linear with bias
+        hipLaunchKernelGGL(cls_rows, dim3((B + 255) / 256), dim3(256), 0, s, B, L, c->rows, L - 1);
+        SSW_TRY(pool_and_project(c, c->txt, B, D, 0, out_dev));
+        hipLaunchKernelGGL(add_row_bias, dim3(64), dim3(256), 0, s, out_dev, c->head_b, B, h.proj);
+        if (normalize) hipLaunchKernelGGL(l2norm_rows, dim3((B + 3) / 4), dim3(256), 0, s, out_dev, B, h.proj);
+        SSW_HIP_TRY(hipGetLastError());
+        return SSW_OK;
+    }
+    hipLaunchKernelGGL(eos_rows, dim3((B + 255) / 256), dim3(256), 0, s, ids_dev, B, L, h.eos, c->rows);
     return pool_and_project(c, c->txt, B, D, normalize, out_dev);
 }
 
@@ -2285,7 +2660,7 @@ ssw_status ssw_debug_attention_run(int32_t form, int32_t B, int32_t S, int32_t D
     SSW_UNSUPPORTED_IF(S > max_s[form], "ssw_debug_attention_run: form %d holds S <= %d, got %d", form, max_s[form], S);
     if (form == 6) {
         SSW_UNSUPPORTED_IF(H > 64 || D % H != 0 || !attention_hd_serves(D / H),
-                           "ssw_debug_attention_run: form 6 wants D = 80, 88 or 104 x H, got D=%d H=%d", D, H);
+                           "ssw_debug_attention_run: form 6 wants D = 72, 80, 88 or 104 x H, got D=%d H=%d", D, H);
         SSW_UNSUPPORTED_IF(causal, "ssw_debug_attention_run: attention_hd has no causal form");
     } else {
         SSW_UNSUPPORTED_IF(D != 64 * H || H > 64, "ssw_debug_attention_run: D=%d is not 64 x H=%d (head_dim 64)", D, H);
@@ -2384,13 +2759,42 @@ ssw_status ssw_clip_create(int32_t device, const void *weight_blob, size_t bytes
     SSW_REQUIRE(bytes > sizeof(Header), "clip: blob too small");
     Header h;
     memcpy(&h, weight_blob, sizeof(Header));
-    SSW_REQUIRE(memcmp(h.magic, "SSWCLIP1", 8) == 0, "clip: bad blob magic");
+    const bool siglip = memcmp(h.magic, "SSWSIGL1", 8) == 0;
+    SSW_REQUIRE(siglip || memcmp(h.magic, "SSWCLIP1", 8) == 0, "clip: bad blob magic");
+    SiglipHeader sh{};
+    if (siglip) {
+        SSW_REQUIRE(bytes > sizeof(SiglipHeader), "clip: blob too small");
+        memcpy(&sh, weight_blob, sizeof(SiglipHeader));
+    }
     const int g = h.patch > 0 ? h.image / h.patch : 0;
-    const int Tv = g * g + 1;
-    SSW_REQUIRE(h.activation == 0 || h.activation == 1, "clip: activation code %d unknown (0 quick-GELU, 1 GELU)", h.activation);
-    const bool heads_ok = h.v_heads > 0 && h.t_heads > 0 && h.v_hidden % h.v_heads == 0 && h.t_hidden == 64 * h.t_heads &&
-                          (h.v_hidden == 64 * h.v_heads || attention_hd_serves(h.v_hidden / h.v_heads));
-    if (h.v_hidden % 128 || h.t_hidden % 128 || h.v_mlp % 128 || h.t_mlp % 128 || h.proj % 4 || h.v_hidden <= 0 || h.t_hidden <= 0 ||
+    const int Tv = g * g + (siglip ? 0 : 1);
+    SSW_REQUIRE(h.activation == 0 || h.activation == 1 || (siglip && h.activation == 2),
+                "clip: activation code %d unknown (0 quick-GELU, 1 GELU; SigLIP blobs: 2 tanh GELU)", h.activation);
+    auto head_dim_ok = [](int hidden, int heads) { return hidden == 64 * heads || attention_hd_serves(hidden / heads); };
+    if (siglip) {  // what only a SigLIP blob can ask for, refused with the offending value
+        auto refuse = [](const char *what, int got, const char *served) {
+            set_error("clip: SigLIP %s %d is outside what the kernels serve (%s)", what, got, served);
+            return SSW_ERR_UNSUPPORTED;
+        };
+        if (h.patch <= 0 || h.image <= 0) return refuse("patch size", h.patch, "a positive patch and image size");
+        if (h.v_heads <= 0 || h.v_hidden <= 0 || h.v_hidden % h.v_heads)
+            return refuse("image head count", h.v_heads, "a positive divisor of the image tower's width");
+        if (h.t_heads <= 0 || h.t_hidden <= 0 || h.t_hidden % h.t_heads)
+            return refuse("text head count", h.t_heads, "a positive divisor of the text tower's width");
+        if (Tv > ATT_LONG_MAX_S) return refuse("image token count", Tv, "at most 272");
+        if (h.image % h.patch) return refuse("image size", h.image, "a multiple of the patch size");
+        if (!head_dim_ok(h.v_hidden, h.v_heads)) return refuse("image head dim", h.v_hidden / h.v_heads, "64, 72, 80, 88, 104");
+        if (!head_dim_ok(h.t_hidden, h.t_heads)) return refuse("text head dim", h.t_hidden / h.t_heads, "64, 72, 80, 88, 104");
+        if (sh.pool_heads < 1 || sh.pool_heads > MAP_HEADS || h.v_hidden % sh.pool_heads || h.v_hidden / sh.pool_heads % 8)
+            return refuse("pooling head count", sh.pool_heads, "1 .. 16 heads of a multiple of 8 columns");
+        if (h.v_hidden > MAP_MAX_DIM) return refuse("image tower width", h.v_hidden, "the pooling head holds at most 1152");
+        if (h.t_maxpos > 64) return refuse("text position count", h.t_maxpos, "at most 64");
+        if (h.proj != h.v_hidden) return refuse("text head width", h.proj, "the image tower's width: the towers share one space");
+    }
+    const bool heads_ok = h.v_heads > 0 && h.t_heads > 0 && h.v_hidden % h.v_heads == 0 && h.t_hidden % h.t_heads == 0 &&
+                          (siglip ? head_dim_ok(h.t_hidden, h.t_heads) : h.t_hidden == 64 * h.t_heads) &&
+                          head_dim_ok(h.v_hidden, h.v_heads);
+    if (h.v_hidden % 128 || h.t_hidden % 128 || (!siglip && (h.v_mlp % 128 || h.t_mlp % 128)) || h.proj % 4 || h.v_hidden <= 0 || h.t_hidden <= 0 ||
         h.v_mlp <= 0 || h.t_mlp <= 0 || h.proj <= 0 || h.patch <= 0 || h.image <= 0 || h.image % h.patch || !heads_ok ||
         Tv > ATT_LONG_MAX_S || h.t_maxpos > ATT_MAX_S || h.v_hidden > CLIP_MAX_DIM || h.t_hidden > CLIP_MAX_DIM ||
         h.proj > CLIP_MAX_PROJ) {
@@ -2408,21 +2812,33 @@ ssw_status ssw_clip_create(int32_t device, const void *weight_blob, size_t bytes
     if (!c) return SSW_ERR_NOMEM;
     c->device = device;
     c->hdr = h;
+    c->siglip = siglip;
+    c->pool_heads = sh.pool_heads;
     c->flags = clip_flags_from_env();
+    if (siglip) {  // map_pool's strip tile and U take more than the 64 KB of LDS a kernel gets unasked
+        const int lds_max = (int)map_pool_lds(MAP_MAX_DIM);
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(map_pool<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void *>(map_pool<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess) {
+            delete c;
+            set_error("clip: map_pool's %d bytes of LDS are refused by device %d", lds_max, device);
+            return SSW_ERR_HIP;
+        }
+    }
     auto bail = [&](ssw_status s) {
         ssw_clip_destroy(c);
         return s;
     };
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return bail(SSW_ERR_HIP);
-    const float *cur = reinterpret_cast<const float *>(reinterpret_cast<const char *>(weight_blob) + sizeof(Header));
+    const float *cur = reinterpret_cast<const float *>(reinterpret_cast<const char *>(weight_blob) +
+                                                       (siglip ? sizeof(SiglipHeader) : sizeof(Header)));
     const float *end = reinterpret_cast<const float *>(reinterpret_cast<const char *>(weight_blob) + bytes);
     // scratch large enough for the biggest single tensor (token embedding or a fused qkv)
     size_t big = (size_t)h.vocab * h.t_hidden;
     big = std::max(big, (size_t)3 * h.v_hidden * h.v_hidden);
-    big = std::max(big, (size_t)h.v_mlp * h.v_hidden);
+    big = std::max(big, (size_t)((h.v_mlp + 127) / 128 * 128) * h.v_hidden);
     big = std::max(big, (size_t)h.v_hidden * patch_cols(h.patch));
     big = std::max(big, (size_t)3 * h.t_hidden * h.t_hidden);
-    big = std::max(big, (size_t)h.t_mlp * h.t_hidden);
+    big = std::max(big, (size_t)((h.t_mlp + 127) / 128 * 128) * h.t_hidden);
     big = std::max(big, (size_t)h.proj * std::max(h.v_hidden, h.t_hidden));
     float *scratch = nullptr;
     if (hipMalloc((void **)&scratch, big * sizeof(float)) != hipSuccess) {
@@ -2431,9 +2847,12 @@ ssw_status ssw_clip_create(int32_t device, const void *weight_blob, size_t bytes
     }
     ssw_status st = SSW_OK;
     do {
-        c->vis.D = h.v_hidden; c->vis.L = h.v_layers; c->vis.H = h.v_heads; c->vis.M = h.v_mlp; c->vis.T = Tv;
-        c->txt.D = h.t_hidden; c->txt.L = h.t_layers; c->txt.H = h.t_heads; c->txt.M = h.t_mlp; c->txt.T = h.t_maxpos;
-        if ((st = upload_f32(c, cur, end, h.v_hidden, &c->cls)) != SSW_OK) break;
+        c->vis.D = h.v_hidden; c->vis.L = h.v_layers; c->vis.H = h.v_heads; c->vis.Mb = h.v_mlp; c->vis.T = Tv;
+        c->txt.D = h.t_hidden; c->txt.L = h.t_layers; c->txt.H = h.t_heads; c->txt.Mb = h.t_mlp; c->txt.T = h.t_maxpos;
+        c->vis.M = (h.v_mlp + 127) / 128 * 128;  // (a CLIP blob's are multiples of 128 already)
+        c->txt.M = (h.t_mlp + 127) / 128 * 128;
+        c->pool_mlp = c->vis.M;
+        if (!siglip && (st = upload_f32(c, cur, end, h.v_hidden, &c->cls)) != SSW_OK) break;
         {   // the patch weight [v_hidden][3 patch^2], its rows padded with zero columns to patch_cols (the blob is not padded)
             const size_t pc = (size_t)3 * h.patch * h.patch, ld = patch_cols(h.patch), n = (size_t)h.v_hidden * pc;
             if (cur + n > end) {
@@ -2451,15 +2870,32 @@ ssw_status ssw_clip_create(int32_t device, const void *weight_blob, size_t bytes
                 cur += n;
             }
         }
-        if ((st = upload_f32(c, cur, end, (size_t)Tv * h.v_hidden, &c->vpos)) != SSW_OK) break;
-        if ((st = upload_f32(c, cur, end, h.v_hidden, &c->pre_w)) != SSW_OK) break;
-        if ((st = upload_f32(c, cur, end, h.v_hidden, &c->pre_b)) != SSW_OK) break;
+        if (siglip) {  // the patch bias, the same for every token, goes into the position embedding
+            const size_t W = h.v_hidden, n = (size_t)Tv * W;
+            if (cur + W + n > end) {
+                set_error("clip: weight blob truncated");
+                st = SSW_ERR_INVALID;
+                break;
+            }
+            std::vector<float> pos(n);
+            for (size_t i = 0; i < n; ++i) pos[i] = cur[W + i] + cur[i % W];
+            cur += W + n;
+            const float *p = pos.data();
+            if ((st = upload_f32(c, p, p + n, n, &c->vpos)) != SSW_OK) break;
+        } else {
+            if ((st = upload_f32(c, cur, end, (size_t)Tv * h.v_hidden, &c->vpos)) != SSW_OK) break;
+            if ((st = upload_f32(c, cur, end, h.v_hidden, &c->pre_w)) != SSW_OK) break;
+            if ((st = upload_f32(c, cur, end, h.v_hidden, &c->pre_b)) != SSW_OK) break;
+        }
         if ((st = load_tower(c, c->vis, cur, end, scratch)) != SSW_OK) break;
-        if ((st = upload_bf16(c, cur, end, (size_t)h.proj * h.v_hidden, &c->vis.proj, scratch)) != SSW_OK) break;
+        if (siglip) {
+            if ((st = load_pooling_head(c, cur, end, scratch)) != SSW_OK) break;
+        } else if ((st = upload_bf16(c, cur, end, (size_t)h.proj * h.v_hidden, &c->vis.proj, scratch)) != SSW_OK) break;
         if ((st = upload_f32(c, cur, end, (size_t)h.vocab * h.t_hidden, &c->tok)) != SSW_OK) break;
         if ((st = upload_f32(c, cur, end, (size_t)h.t_maxpos * h.t_hidden, &c->tpos)) != SSW_OK) break;
         if ((st = load_tower(c, c->txt, cur, end, scratch)) != SSW_OK) break;
         if ((st = upload_bf16(c, cur, end, (size_t)h.proj * h.t_hidden, &c->txt.proj, scratch)) != SSW_OK) break;
+        if (siglip && (st = upload_f32(c, cur, end, h.proj, &c->head_b)) != SSW_OK) break;
         if (cur != end) {
             set_error("clip: %zu unread floats at the end of the weight blob", (size_t)(end - cur));
             st = SSW_ERR_INVALID;
@@ -2476,7 +2912,7 @@ ssw_status ssw_clip_embed_image(ssw_clip *c, const float *nchw_host, int32_t b, 
     SSW_REQUIRE(c && nchw_host && out_host && b > 0, "bad argument");
     DeviceGuard guard(c->device);
     const Header &h = c->hdr;
-    const int chunk = image_chunk(h);
+    const int chunk = image_chunk(c);
     SSW_TRY(reserve(c, std::min<int64_t>(b, chunk)));
     const size_t per = (size_t)3 * h.image * h.image;
     for (int b0 = 0; b0 < b; b0 += chunk) {
@@ -2496,7 +2932,7 @@ ssw_status ssw_clip_embed_tiles_u8(ssw_clip *c, const uint8_t *tiles_hwc_host, i
     SSW_REQUIRE(c && tiles_hwc_host && out_host && b > 0, "bad argument");
     DeviceGuard guard(c->device);
     const Header &h = c->hdr;
-    const int chunk = image_chunk(h);
+    const int chunk = image_chunk(c);
     SSW_TRY(reserve(c, std::min<int64_t>(b, chunk)));
     const size_t per = (size_t)3 * h.image * h.image;  // bytes per tile; c->pixels (f32) is 4x that
     for (int b0 = 0; b0 < b; b0 += chunk) {
@@ -2525,7 +2961,7 @@ ssw_status ssw_clip_embed_multiscale_u8(ssw_clip *c, const uint8_t *images_hwc_c
     SSW_REQUIRE(total <= out_cap_tiles, "multiscale: the call makes %lld tiles, out_cap_tiles is %lld", (long long)total,
                 (long long)out_cap_tiles);
     DeviceGuard guard(c->device);
-    const int chunk = image_chunk(h);
+    const int chunk = image_chunk(c);
     SSW_TRY(reserve(c, std::min<int64_t>(total, chunk)));
     DrainOnExit drain{c->stream};
     SSW_TRY(build_levels(c, images_hwc_concat_host, plan));
@@ -2569,7 +3005,7 @@ ssw_status ssw_debug_clip_multiscale_tiles(ssw_clip *c, const uint8_t *images_hw
     SSW_REQUIRE(total <= out_cap_tiles, "multiscale: the call makes %lld tiles, out_cap_tiles is %lld", (long long)total,
                 (long long)out_cap_tiles);
     DeviceGuard guard(c->device);
-    const int chunk = image_chunk(h);
+    const int chunk = image_chunk(c);
     SSW_TRY(reserve(c, std::min<int64_t>(total, chunk)));
     DrainOnExit drain{c->stream};
     SSW_TRY(build_levels(c, images_hwc_concat_host, plan));
@@ -2590,7 +3026,7 @@ ssw_status ssw_clip_embed_image_dev(ssw_clip *c, void *hip_stream, const float *
                                     int32_t normalize, float *out_dev) {
     SSW_REQUIRE(c && nchw_dev && out_dev && b > 0, "bad argument");
     DeviceGuard guard(c->device);
-    SSW_REQUIRE(b <= image_chunk(c->hdr), "clip: at most %d images per device-side call", image_chunk(c->hdr));
+    SSW_REQUIRE(b <= image_chunk(c), "clip: at most %d images per device-side call", image_chunk(c));
     SSW_TRY(reserve(c, b));
     hipStream_t saved = c->stream;
     if (hip_stream) c->stream = (hipStream_t)hip_stream;
@@ -2606,7 +3042,7 @@ ssw_status ssw_clip_embed_text(ssw_clip *c, const int32_t *ids_host, int32_t b, 
     SSW_REQUIRE(seq_len >= 1 && seq_len <= h.t_maxpos, "clip: sequence length %d outside [1, %d]", seq_len, h.t_maxpos);
     for (int64_t i = 0; i < (int64_t)b * seq_len; ++i)
         SSW_REQUIRE(ids_host[i] >= 0 && ids_host[i] < h.vocab, "clip: token id %d outside the vocabulary", ids_host[i]);
-    if (h.eos != 2)  // legacy configs pool at argmax(ids), which always exists
+    if (h.eos != 2 && !c->siglip)  // legacy configs pool at argmax(ids), which always exists; SigLIP pools the last position
         for (int r = 0; r < b; ++r) {
             bool found = false;
             for (int j = 0; j < seq_len && !found; ++j) found = ids_host[(int64_t)r * seq_len + j] == h.eos;

@@ -79,15 +79,26 @@ enum Epilogue { EPI_F32 = 0, EPI_BF16_BIAS = 1, EPI_BF16_BIAS_GELU = 2, EPI_F32_
                 EPI_BF16_LN_GELU = 5, EPI_F32_BIAS_RESIDUAL_STATS = 6, EPI_BF16_STREAM_STATS = 7,
                 EPI_BF16_BIAS_ERF = 8, EPI_BF16_LN_ERF = 9,  // 8 / 9: 2 / 5 with the exact GELU 0.5 x (1 + erf(x / sqrt 2))
                 // 4 / 5 / 9 for rows of 9 .. 16 partial-statistics pairs (chosen by launch_gemm_bf16_ln from np_in, never by a caller)
-                EPI_BF16_LN_W = 10, EPI_BF16_LN_GELU_W = 11, EPI_BF16_LN_ERF_W = 12 };
-constexpr bool epi_ln_wide(int e) { return e == EPI_BF16_LN_W || e == EPI_BF16_LN_GELU_W || e == EPI_BF16_LN_ERF_W; }
+                EPI_BF16_LN_W = 10, EPI_BF16_LN_GELU_W = 11, EPI_BF16_LN_ERF_W = 12,
+                // 13 / 14 / 15: 2 / 5 / 11 with SigLIP's tanh GELU 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3)))
+                EPI_BF16_BIAS_TANH = 13, EPI_BF16_LN_TANH = 14, EPI_BF16_LN_TANH_W = 15 };
+constexpr bool epi_ln_wide(int e) { return e == EPI_BF16_LN_W || e == EPI_BF16_LN_GELU_W || e == EPI_BF16_LN_ERF_W || e == EPI_BF16_LN_TANH_W; }
 constexpr int epi_ln_quads(int e) { return epi_ln_wide(e) ? 8 : 4; }
-constexpr bool epi_ln(int e) { return e == EPI_BF16_LN || e == EPI_BF16_LN_GELU || e == EPI_BF16_LN_ERF || epi_ln_wide(e); }
-constexpr bool epi_bf16_out(int e) { return e == EPI_BF16_BIAS || e == EPI_BF16_BIAS_GELU || e == EPI_BF16_BIAS_ERF || epi_ln(e); }
+constexpr bool epi_ln(int e) { return e == EPI_BF16_LN || e == EPI_BF16_LN_GELU || e == EPI_BF16_LN_ERF || e == EPI_BF16_LN_TANH || epi_ln_wide(e); }
+constexpr bool epi_bf16_out(int e) {
+    return e == EPI_BF16_BIAS || e == EPI_BF16_BIAS_GELU || e == EPI_BF16_BIAS_ERF || e == EPI_BF16_BIAS_TANH || epi_ln(e);
+}
 constexpr bool epi_gelu(int e) { return e == EPI_BF16_BIAS_GELU || e == EPI_BF16_LN_GELU || e == EPI_BF16_LN_GELU_W; }
 constexpr bool epi_erf(int e) { return e == EPI_BF16_BIAS_ERF || e == EPI_BF16_LN_ERF || e == EPI_BF16_LN_ERF_W; }
 // torch's nn.GELU() (OpenCLIP ViT-H/14, bigG/14): erff is ocml's, a few ulp -- far below the bf16 rounding behind it
 __device__ __forceinline__ float erf_gelu_f32(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678f)); }
+constexpr bool epi_tanh(int e) { return e == EPI_BF16_BIAS_TANH || e == EPI_BF16_LN_TANH || e == EPI_BF16_LN_TANH_W; }
+// torch's GELU(approximate="tanh") (SigLIP's gelu_pytorch_tanh): 0.5 (1 + tanh z) = sigmoid(2 z), z = sqrt(2 / pi) (x + 0.044715 x^3),
+// so it is quick-GELU's v_exp + v_rcp with a cubic in front (an overflowing cube gives sigmoid 0 or 1, as tanh does)
+__device__ __forceinline__ float tanh_gelu_f32(float x) {
+    const float z2 = 1.5957691216f * (x + 0.044715f * x * x * x);  // 2 z
+    return x * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.44269504f * z2));
+}
 constexpr bool epi_residual(int e) { return e == EPI_F32_BIAS_RESIDUAL || e == EPI_F32_BIAS_RESIDUAL_STATS; }
 constexpr bool epi_stats(int e) { return e == EPI_F32_BIAS_RESIDUAL_STATS || e == EPI_BF16_STREAM_STATS; }
 
@@ -120,6 +131,10 @@ __device__ __forceinline__ void epilogue_store(f32x4 v, int64_t o, int col, cons
     if constexpr (epi_erf(EPI)) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = erf_gelu_f32(v[r]);
+    }
+    if constexpr (epi_tanh(EPI)) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = tanh_gelu_f32(v[r]);
     }
     if constexpr (epi_residual(EPI)) v += *reinterpret_cast<const f32x4 *>(residual + o);
     if constexpr (EPI == EPI_BF16_STREAM_STATS) {  // the stream's own element: read here, replaced below by this thread
@@ -169,6 +184,10 @@ __device__ __forceinline__ f32x4 epilogue_value(f32x4 v, float mean, float rstd,
     if constexpr (epi_erf(EPI)) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = erf_gelu_f32(v[r]);
+    }
+    if constexpr (epi_tanh(EPI)) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = tanh_gelu_f32(v[r]);
     }
     return v;
 }
@@ -362,8 +381,9 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt(const bf16 *__restrict__ A, 
                 const int64_t o = (int64_t)row * N + col;
                 if (EPI == EPI_BF16_BIAS_GELU) v = v / (1.f + __expf(-1.702f * v));  // quick_gelu
                 if (EPI == EPI_BF16_BIAS_ERF) v = erf_gelu_f32(v);
+                if (EPI == EPI_BF16_BIAS_TANH) v = tanh_gelu_f32(v);
                 if (EPI == EPI_F32_BIAS_RESIDUAL) v += residual[o];
-                if (EPI == EPI_BF16_BIAS || EPI == EPI_BF16_BIAS_GELU || EPI == EPI_BF16_BIAS_ERF)
+                if (epi_bf16_out(EPI))
                     reinterpret_cast<bf16 *>(Cout)[o] = to_bf16(v);
                 else
                     reinterpret_cast<float *>(Cout)[o] = v;
@@ -1243,7 +1263,8 @@ ssw_status launch_gemm_bf16_nt(int epi, hipStream_t s, const void *A_, const voi
         return SSW_ERR_UNSUPPORTED;
     }
 #ifdef SSW_DEBUG_HOOKS  // the four-wave experiment (gemm_pw4.hip) is part of the lab build only
-    if (g_gemm_variant >= 20 && g_gemm_variant <= 23 && epi != EPI_BF16_BIAS_ERF && gemm_pw4_supports(M, N, K)) {  // (no erf epilogue there)
+    if (g_gemm_variant >= 20 && g_gemm_variant <= 23 && epi != EPI_BF16_BIAS_ERF && epi != EPI_BF16_BIAS_TANH &&
+        gemm_pw4_supports(M, N, K)) {  // (no erf / tanh epilogue there)
         static const int bn_of[4] = {0, 256, 192, 128};
         int bn = bn_of[g_gemm_variant - 20];
         if (bn != 0 && N % bn != 0) bn = 0;
@@ -1256,6 +1277,7 @@ ssw_status launch_gemm_bf16_nt(int epi, hipStream_t s, const void *A_, const voi
         case EPI_BF16_BIAS: return launch_epi<EPI_BF16_BIAS>(s, A, W, bias, res, C, M, N, K);
         case EPI_BF16_BIAS_GELU: return launch_epi<EPI_BF16_BIAS_GELU>(s, A, W, bias, res, C, M, N, K);
         case EPI_BF16_BIAS_ERF: return launch_epi<EPI_BF16_BIAS_ERF>(s, A, W, bias, res, C, M, N, K);
+        case EPI_BF16_BIAS_TANH: return launch_epi<EPI_BF16_BIAS_TANH>(s, A, W, bias, res, C, M, N, K);
         case EPI_F32_BIAS_RESIDUAL: return launch_epi<EPI_F32_BIAS_RESIDUAL>(s, A, W, bias, res, C, M, N, K);
     }
     set_error("gemm_bf16_nt: unknown epilogue %d", epi);
@@ -1273,6 +1295,7 @@ ssw_status launch_gemm_bf16_ln(int epi, hipStream_t s, const void *A_, const voi
         case EPI_BF16_LN:
         case EPI_BF16_LN_GELU:
         case EPI_BF16_LN_ERF:
+        case EPI_BF16_LN_TANH:
             if (!ln.stats_in || !ln.c1 || !bias || ln.np_in <= 0 || ln.np_in > 16 || (ln.np_in & 1)) {
                 set_error("gemm_bf16_ln: the LayerNorm-folded product needs statistics (an even number of partial pairs, <= 16), c1 and c2");
                 return SSW_ERR_INVALID;
@@ -1280,9 +1303,11 @@ ssw_status launch_gemm_bf16_ln(int epi, hipStream_t s, const void *A_, const voi
             if (ln.np_in > 8) {  // rows wider than 1024: eight float4 requests a row, instantiations of their own
                 if (epi == EPI_BF16_LN) return launch_epi_ln<EPI_BF16_LN_W>(s, A, W, bias, res, C, M, N, K, ln);
                 if (epi == EPI_BF16_LN_GELU) return launch_epi_ln<EPI_BF16_LN_GELU_W>(s, A, W, bias, res, C, M, N, K, ln);
+                if (epi == EPI_BF16_LN_TANH) return launch_epi_ln<EPI_BF16_LN_TANH_W>(s, A, W, bias, res, C, M, N, K, ln);
                 return launch_epi_ln<EPI_BF16_LN_ERF_W>(s, A, W, bias, res, C, M, N, K, ln);
             }
             if (epi == EPI_BF16_LN_ERF) return launch_epi_ln<EPI_BF16_LN_ERF>(s, A, W, bias, res, C, M, N, K, ln);
+            if (epi == EPI_BF16_LN_TANH) return launch_epi_ln<EPI_BF16_LN_TANH>(s, A, W, bias, res, C, M, N, K, ln);
             return epi == EPI_BF16_LN ? launch_epi_ln<EPI_BF16_LN>(s, A, W, bias, res, C, M, N, K, ln)
                                       : launch_epi_ln<EPI_BF16_LN_GELU>(s, A, W, bias, res, C, M, N, K, ln);
         case EPI_F32_BIAS_RESIDUAL_STATS:

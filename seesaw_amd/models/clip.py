@@ -6,6 +6,11 @@ Served: image towers up to 1664 wide with heads of 64, 80, 88 or 104 columns and
 1664 wide with heads of 64 and at most 80 positions; projections up to 1280; hidden_act "quick_gelu" or "gelu" (the
 same in both towers).  Anything else is refused by pack_clip_weights or ssw_clip_create.
 
+transformers.SiglipModel (config.model_type "siglip") is served through a blob of its own, magic SSWSIGL1
+(pack_siglip_weights): image towers up to 1152 wide and 272 tokens without a class token, with the attention-pooling head
+(at most 16 heads) and no projection; bidirectional text towers of at most 64 positions pooled at the last position given;
+heads of 64, 72, 80, 88 or 104 columns in both towers; hidden_act "gelu_pytorch_tanh" as well; any MLP width.
+
 The reference loads `transformers.CLIPModel.from_pretrained(<local dir>)` and calls
 `get_text_features` / `get_image_features` (seesaw/models/embeddings.py:427-455,
 seesaw/models/model.py:50-63).  Here the same state_dict is flattened into one blob and the
@@ -28,6 +33,11 @@ _LAYER_KEYS = ["layer_norm1.weight", "layer_norm1.bias", "self_attn.q_proj.weigh
 
 # the header's last word: fc1's activation (csrc/clip.hip, Header::activation)
 ACTIVATION_CODES = {"quick_gelu": 0, "gelu": 1}
+
+
+# a SigLIP blob's header carries the tanh GELU as code 2; an SSWCLIP1 header with that code stays refused
+SIGLIP_ACTIVATION_CODES = {"quick_gelu": 0, "gelu": 1, "gelu_pytorch_tanh": 2}
+_HEADER, _SIGLIP_HEADER = "<8s6i7iifi", "<8s6i7iifi2i"  # 72 / 80 bytes
 
 
 def patch_columns(patch_size: int) -> int:
@@ -74,13 +84,64 @@ def pack_clip_weights(state_dict, config) -> np.ndarray:
     return blob
 
 
+def _flat(state_dict, name):
+    x = state_dict[name]
+    x = x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+    return np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+
+
+def pack_siglip_weights(state_dict, config) -> np.ndarray:
+    """transformers.SiglipModel state_dict + SiglipConfig -> the SSWSIGL1 blob ssw_clip_create reads: an 80-byte header
+    (the SSWCLIP1 fields, then the pooling head's head count and a zero word) and every parameter but logit_scale /
+    logit_bias as f32, unpadded.  What the magic implies (no class token, a patch bias, no pre-LayerNorm, the pooling
+    head, an unmasked text tower pooled at the last position, a text head with bias) is not in the header."""
+    v, t = config.vision_config, config.text_config
+    if v.hidden_act != t.hidden_act:
+        raise ValueError(f"the towers' activations differ (vision {v.hidden_act!r}, text {t.hidden_act!r}): "
+                         "the blob carries one for both")
+    if v.hidden_act not in SIGLIP_ACTIVATION_CODES:
+        raise ValueError(f"hidden_act {v.hidden_act!r} is not served: {sorted(SIGLIP_ACTIVATION_CODES)}")
+    if not getattr(v, "vision_use_head", True):
+        raise ValueError("a SigLIP image tower without its pooling head is not served")
+    proj = getattr(t, "projection_size", None) or t.hidden_size
+    header = struct.pack(_SIGLIP_HEADER, b"SSWSIGL1", v.hidden_size, v.num_hidden_layers, v.num_attention_heads,
+                         v.intermediate_size, v.image_size, v.patch_size, t.hidden_size, t.num_hidden_layers,
+                         t.num_attention_heads, t.intermediate_size, t.max_position_embeddings, t.vocab_size, 0, proj,
+                         float(v.layer_norm_eps), SIGLIP_ACTIVATION_CODES[v.hidden_act], v.num_attention_heads, 0)
+    assert len(header) == 80
+
+    def get(name):
+        return _flat(state_dict, name)
+
+    ve, head = "vision_model.embeddings.", "vision_model.head."
+    parts = [get(ve + "patch_embedding.weight"), get(ve + "patch_embedding.bias"), get(ve + "position_embedding.weight")]
+    for i in range(v.num_hidden_layers):
+        parts += [get(f"vision_model.encoder.layers.{i}.{k}") for k in _LAYER_KEYS]
+    parts += [get("vision_model.post_layernorm.weight"), get("vision_model.post_layernorm.bias"), get(head + "probe"),
+              get(head + "attention.in_proj_weight"), get(head + "attention.in_proj_bias"),
+              get(head + "attention.out_proj.weight"), get(head + "attention.out_proj.bias"),
+              get(head + "layernorm.weight"), get(head + "layernorm.bias")]
+    parts += [get(head + k) for k in _LAYER_KEYS[-4:]]  # mlp.fc1 / fc2
+    parts += [get("text_model.embeddings.token_embedding.weight"), get("text_model.embeddings.position_embedding.weight")]
+    for i in range(t.num_hidden_layers):
+        parts += [get(f"text_model.encoder.layers.{i}.{k}") for k in _LAYER_KEYS]
+    parts += [get("text_model.final_layer_norm.weight"), get("text_model.final_layer_norm.bias"),
+              get("text_model.head.weight"), get("text_model.head.bias")]
+    body = np.concatenate(parts)
+    blob = np.empty(80 + body.nbytes, dtype=np.uint8)
+    blob[:80] = np.frombuffer(header, dtype=np.uint8)
+    blob[80:] = body.view(np.uint8)
+    return blob
+
+
 class ClipModel:
     def __init__(self, blob: np.ndarray, device: int = 0):
         blob = np.ascontiguousarray(blob, dtype=np.uint8)
         self._h = ctypes.c_void_p()
-        hdr = struct.unpack("<8s6i7iifi", blob[:72].tobytes())
-        if hdr[16] not in ACTIVATION_CODES.values():
-            raise ValueError(f"clip blob: activation code {hdr[16]} unknown (0 quick_gelu, 1 gelu)")
+        self.is_siglip = blob[:8].tobytes() == b"SSWSIGL1"
+        hdr = struct.unpack(_HEADER, blob[:72].tobytes())
+        if hdr[16] not in (SIGLIP_ACTIVATION_CODES if self.is_siglip else ACTIVATION_CODES).values():
+            raise ValueError(f"clip blob: activation code {hdr[16]} unknown (0 quick_gelu, 1 gelu; SSWSIGL1 only: 2 tanh gelu)")
         self.image_size, self.patch_size = hdr[5], hdr[6]
         self.vision_hidden, self.text_hidden = hdr[1], hdr[7]
         self.max_positions, self.vocab_size, self.eos_token_id, self.projection_dim = hdr[11], hdr[12], hdr[13], hdr[14]
@@ -89,17 +150,19 @@ class ClipModel:
 
     @classmethod
     def from_hf(cls, hf_model, device: int = 0) -> "ClipModel":
-        return cls(pack_clip_weights(hf_model.state_dict(), hf_model.config), device=device)
+        pack = pack_siglip_weights if getattr(hf_model.config, "model_type", "clip") == "siglip" else pack_clip_weights
+        return cls(pack(hf_model.state_dict(), hf_model.config), device=device)
 
     @classmethod
     def random_init(cls, seed: int = 1234, device: int = 0, config=None) -> "ClipModel":
         """BASELINE.json: 'random-init CLIP weights' -- transformers.CLIPModel(CLIPConfig()) under a seed.
-        `config`: a transformers.CLIPConfig of another variant (ViT-B/16, ViT-L/14); default ViT-B/32."""
+        `config`: a transformers.CLIPConfig of another variant (ViT-B/16, ViT-L/14), or a SiglipConfig; default ViT-B/32."""
         import torch
         import transformers
         torch.manual_seed(seed)
         cfg = transformers.CLIPConfig() if config is None else config
-        return cls.from_hf(transformers.CLIPModel(cfg).eval(), device=device)
+        model = transformers.SiglipModel if getattr(cfg, "model_type", "clip") == "siglip" else transformers.CLIPModel
+        return cls.from_hf(model(cfg).eval(), device=device)
 
     def close(self):
         if self._h:

@@ -131,6 +131,18 @@ def _load_tokenizer(path, model: ClipModel):
     if path is None or _synthetic_seed(path) is not None:
         return HashTokenizer(model.vocab_size, eos=model.eos_token_id if model.eos_token_id != 2 else model.vocab_size - 1,
                              max_len=model.max_positions)
+    if getattr(model, "is_siglip", False) and os.path.exists(os.path.join(str(path), "spiece.model")):
+        # SigLIP's sentencepiece tokenizer, padded to the model's positions as the model was trained (the text tower
+        # pools the last position given)
+        try:
+            import sentencepiece  # noqa: F401
+        except ImportError:
+            pass
+        else:
+            import transformers
+            sp = transformers.SiglipTokenizer.from_pretrained(path)
+            return lambda s: np.asarray(sp(s, padding="max_length", max_length=model.max_positions, truncation=True,
+                                           return_tensors="np")["input_ids"], dtype=np.int32)
     if not os.path.exists(os.path.join(str(path), "vocab.json")):
         raise FileNotFoundError(f"no CLIP tokenizer files (vocab.json) under {path!r}")
     import transformers
@@ -152,8 +164,11 @@ def load_clip(path=None, device: int = 0) -> ClipModel:
         if seed is not None:
             _CLIP_CACHE[key] = ClipModel.random_init(seed=seed, device=device)
         elif os.path.isdir(str(path)) and os.path.exists(os.path.join(str(path), "config.json")):
+            import json
             import transformers
-            hf = transformers.CLIPModel.from_pretrained(path).eval()
+            with open(os.path.join(str(path), "config.json")) as f:
+                siglip = json.load(f).get("model_type") == "siglip"
+            hf = (transformers.SiglipModel if siglip else transformers.CLIPModel).from_pretrained(path).eval()
             _CLIP_CACHE[key] = ClipModel.from_hf(hf, device=device)
         else:
             raise FileNotFoundError(f"CLIP model directory {path!r} not found (expected config.json + weights); "

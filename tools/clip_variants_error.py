@@ -15,7 +15,7 @@ import transformers
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from seesaw_amd.models.clip import ClipModel  # noqa: E402
-from tools.perf_clip_variants import MODELS, config  # noqa: E402
+from tools.perf_clip_variants import MODELS, SIGLIP, config  # noqa: E402
 
 
 def unit(x):
@@ -24,11 +24,12 @@ def unit(x):
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--tiles", type=int, default=6)
-ap.add_argument("--models", default="b16,l14", help="of tools/perf_clip_variants.py's MODELS; h14 = ViT-H/14 at 32 layers")
+ap.add_argument("--models", default="b16,l14", help="of tools/perf_clip_variants.py's MODELS; h14 = ViT-H/14 at 32 layers, "
+                "sig_b16 / sig_so400m = SigLIP base/16 at 12 and so400m/14 at 27 layers")
 args = ap.parse_args()
 for name in args.models.split(","):
     torch.manual_seed(1234)
-    hf = transformers.CLIPModel(config(name)).eval()
+    hf = (transformers.SiglipModel if name in SIGLIP else transformers.CLIPModel)(config(name)).eval()
     ours = ClipModel.from_hf(hf)
     torch.manual_seed(0)
     x = torch.randn(args.tiles, 3, 224, 224)

@@ -1,4 +1,5 @@
-"""Image tower forward of ViT-B/32, ViT-B/16 and ViT-L/14 (and, on request, OpenCLIP ViT-H/14 and bigG/14) at 200 tiles a
+"""Image tower forward of ViT-B/32, ViT-B/16 and ViT-L/14 (and, on request, OpenCLIP ViT-H/14 and bigG/14, and SigLIP
+base/16 and so400m/14 at 224 pixels: sig_b16, sig_so400m) at 200 tiles a
 call (GPU box), full depth, seeded random-init weights, no HF forward.
 
   python tools/perf_clip_variants.py [--models b32,b16,l14[,h14,bigg14]] [--tiles 200] [--reps 30] [--text]
@@ -26,20 +27,32 @@ MODELS = {
     # --text is given, keeps its widths at 2 layers so that the f32 blob stays a host-memory-sized thing
     "h14": ("ViT-H/14", 14, 1280, 16, 5120, 32, 1024, 16, 4096, 1024),
     "bigg14": ("ViT-bigG/14", 14, 1664, 16, 8192, 48, 1280, 20, 5120, 1280),
+    # SigLIP (transformers.SiglipModel, tanh GELU): no class token, the attention-pooling head, no projection; text tower at 2 layers
+    "sig_b16": ("SigLIP base/16", 16, 768, 12, 3072, 12, 768, 12, 3072, 768),
+    "sig_so400m": ("SigLIP so400m/14", 14, 1152, 16, 4304, 27, 1152, 16, 4304, 1152),
 }
 OPENCLIP = ("h14", "bigg14")
+SIGLIP = ("sig_b16", "sig_so400m")
 
 
-def tile_flops(patch, D, M, L, P, image=224):
-    """multiply-adds x 2 of one tile through the image tower as the reference's model runs it"""
-    T = (image // patch) ** 2 + 1
+def tile_flops(patch, D, M, L, P, image=224, siglip=False):
+    """multiply-adds x 2 of one tile through the image tower as the reference's model runs it (SigLIP: no class token, and
+    the pooling head as transformers writes it -- K and V projections of every token -- instead of the projection)"""
+    T = (image // patch) ** 2 + (0 if siglip else 1)
     layer = 2 * T * (3 * D * D + D * D + 2 * D * M) + 4 * T * T * D
-    return 2 * (T - 1) * D * 3 * patch * patch + L * layer + 2 * D * P, T
+    tail = 2 * T * 2 * D * D + 4 * T * D + 4 * D * D + 4 * D * M if siglip else 2 * D * P
+    return 2 * (T - (0 if siglip else 1)) * D * 3 * patch * patch + L * layer + tail, T
 
 
 def config(name):
     import transformers
     _, patch, vh, vn, vm, vl, th, tn, tm, proj = MODELS[name]
+    if name in SIGLIP:
+        return transformers.SiglipConfig(
+            text_config=dict(hidden_size=th, num_attention_heads=tn, intermediate_size=tm, num_hidden_layers=2, vocab_size=1000,
+                             max_position_embeddings=64, projection_size=proj),
+            vision_config=dict(hidden_size=vh, num_attention_heads=vn, intermediate_size=vm, num_hidden_layers=vl,
+                               patch_size=patch, image_size=224))
     extra_t = dict(num_hidden_layers=2, hidden_act="gelu") if name in OPENCLIP else {}
     extra_v = dict(hidden_act="gelu") if name in OPENCLIP else {}
     return transformers.CLIPConfig(
@@ -71,7 +84,7 @@ def main():
         title, patch, vh, vn, vm, vl, th, tn, tm, proj = MODELS[name]
         # ViT-B/32 is transformers' default config: created as every other tool does, which the parent commit can do too
         m = ClipModel.random_init(seed=1234) if name == "b32" else ClipModel.random_init(seed=1234, config=config(name))
-        flops, T = tile_flops(patch, vh, vm, vl, proj)
+        flops, T = tile_flops(patch, vh, vm, vl, proj, siglip=name in SIGLIP)
         x = torch.randn(B, 3, 224, 224, device=dev)
         out = torch.empty(B, proj, device=dev)
         s = torch.cuda.current_stream().cuda_stream
@@ -91,7 +104,7 @@ def main():
               f"{med * 1e3:.3f} ms (min {ts[0] * 1e3:.3f}, quartiles {q1 * 1e3:.3f} .. {q3 * 1e3:.3f}, max {ts[-1] * 1e3:.3f}); "
               f"{B / med:.0f} tiles/s; {B * flops / med / PEAK_BF16:.3f} of the dense bf16 peak (call time, model FLOPs)",
               flush=True)
-        if args.text:
+        if args.text and name not in SIGLIP:  # (the ids below are CLIP's)
             ids = np.random.default_rng(1).integers(1, 49000, size=(1, 9)).astype(np.int32)
             ids[0, 0], ids[0, 8] = 49406, 49407
             for _ in range(5):
